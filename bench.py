@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- QA-pairs/s of the RAU forward+backward on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1]): Ours_SS 8-step RAU, batch 256 PER GPU,
 14x14x512 features, 26-token questions (all full length), fp32, training mode
@@ -10,6 +10,13 @@ One "step" = zero grads + rau_forward + rau_backward (every parameter gradient
 in the three flat buffers) [+ RCCL average of those buffers when N > 1].  Inputs
 are resident in HBM before the timed region.  Noise/clip/Adam is NOT in the
 metric; it is timed separately as step_incl_update.
+
+A plain run sets up, warms up, times --steps steps and prints the JSON line.  Everything
+else it can measure (kernel profile and roofline, update / H2D / inference legs,
+other_configs, CPU baselines) runs only with --full.  --dump-outputs DIR writes what the
+last timed step computed (losses, argmax, logits, dopred, attention, question state and
+the three gradient buffers) as DIR/<name>.npy, float32, at most 64 MB in all; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1: one rank per GPU over RCCL.  `python bench.py --gpus N` launches its own ranks
 (`python -m torch.distributed.run` as a CHILD process, started before this process has
@@ -27,6 +34,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -156,6 +164,34 @@ def roofline_objects(prof, nprof, dtype, shape):
             "hbm_frac": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
         for k, v in bulk.items()}
     return {"roofline": roof, "bulk_kernels": bulk_kernels}
+
+
+DUMP_BYTES = 63_000_000   # --dump-outputs payload; leaves room for the .npy headers under 64 MB
+
+
+def step_outputs(m):
+    """What a caller of the timed step receives after it: the forward's outputs and the three
+    flat gradient buffers (float32; argmax as float32, exact for K < 2^24)."""
+    out = {"losses": m.losses(), "argmax": m.argmax().astype(np.float32), "logits": m.logits(),
+           "dopred": m.dopred(), "attention": m.attention(), "question_state": m.question_state()}
+    out.update({f"grad_{g}": a for g, a in m.get_grads().items()})
+    return out
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BYTES):
+    """Write each array as directory/<name>.npy in float32.  If they hold more than `budget` bytes in
+    all, every array keeps the same fraction of its elements (flattened), at positions drawn with a
+    seed fixed per name: the same arguments sample the same positions in every run."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, budget / total) if total else 1.0
+    for name, a in arrays.items():
+        if frac < 1.0:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.choice(a.size, int(a.size * frac), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 WORKLOADS = {("SS", 512, "f32"): "configs[1]", ("ResNet", 2048, "bf16"): "configs[2]",
@@ -290,15 +326,22 @@ def main():
     ap.add_argument("--epoch", type=int, default=0, help="epoch for the Full/ResNet gating vector")
     ap.add_argument("--graph", action="store_true",
                     help="replay each step as one hipGraph launch (rau_graph_step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the kernel profile / roofline, the update, H2D "
+                         "and inference legs, other_configs and the CPU baselines (a plain run does none)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--quick", action="store_true",
-                    help="A/B sweeps: the timed steps and the 3-step kernel profile only (no update, H2D, "
-                         "inference, other_configs or CPU-baseline legs)")
+                    help="with --full, for A/B sweeps: the timed steps and the 3-step kernel profile only (no "
+                         "update, H2D, inference, other_configs or CPU-baseline legs)")
     ap.add_argument("--other-config", choices=sorted(OTHER_CONFIGS), default=None,
                     help="(internal) run ONE other_configs leg in this process and print its JSON object")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the other_configs legs (configs[2], the configs[3] shard) of the default run")
+                    help="with --full: skip the other_configs legs (configs[2], the configs[3] shard)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.quick:
         args.no_cpu_baseline = args.no_other_configs = True
     if args.other_config:   # child of the default run: one leg, its own process, nothing else
@@ -427,9 +470,11 @@ def main():
         dt = float(tt.item())
     losses = m.losses()
     assert os.environ.get("RAU_DEV_SKIP") or np.all(np.isfinite(losses)), losses
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(m))
 
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         # per-kernel-class device time (HIP events on the ctx stream, outside the timed region)
         m.prof_reset()
         m.prof_enable(True)
@@ -528,12 +573,12 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             extra["cpu_baseline"] = cpu_baseline(cfgd, budget_s=12.0)
             extra["cpu_baseline_cxx"] = cpu_baseline_cxx(cfgd, budget_s=8.0)
-    elif world > 1:
+    elif world > 1 and args.full:
         # keep ranks in lock-step with rank 0's extra (collective-carrying) steps
         for i in range(3):
             step(1000 + i)
         fence()
-    if rank != 0 and world > 1 and not args.quick:
+    if rank != 0 and world > 1 and args.full and not args.quick:
         for i in range(5):
             step(2000 + i)
             m.update(step_t=i)

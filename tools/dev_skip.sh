@@ -11,7 +11,7 @@ mkdir -p gpurun_out
 out=gpurun_out/dev_skip.log
 : > $out
 run() { echo "== skip: ${1:-(nothing)}" >> $out
-  RAU_LIB=$R/rau_vqa_amd/librau_dev.so RAU_DEV_SKIP="$1" timeout -k 10 240 python3 bench.py --steps 20 --warmup 5 --quick ${BENCH_ARGS} 2>/dev/null | python3 -c "
+  RAU_LIB=$R/rau_vqa_amd/librau_dev.so RAU_DEV_SKIP="$1" timeout -k 10 240 python3 bench.py --full --steps 20 --warmup 5 --quick ${BENCH_ARGS} 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

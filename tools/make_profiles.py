@@ -1,15 +1,15 @@
 """Turn one round's rocprofv3 outputs into the committed profiles/ artefacts (development tool).
 
-Inputs (written on the GPU box by tools/profile_round.sh into gpurun_out/):
-  kt/      rocprofv3 --kernel-trace --stats           -- python3 bench.py --steps 20 --warmup 3
-  pmc_f/   rocprofv3 --pmc FETCH_SIZE --kernel-trace  -- python3 bench.py --steps 2 --warmup 1
+Inputs (written on the GPU box by tools/profile_round.sh into its output folder, default profile_out/):
+  kt/      rocprofv3 --kernel-trace --stats           -- python3 bench.py --full --steps 20 --warmup 3
+  pmc_f/   rocprofv3 --pmc FETCH_SIZE --kernel-trace  -- python3 bench.py --full --steps 2 --warmup 1
   pmc_w/   rocprofv3 --pmc WRITE_SIZE --kernel-trace  -- same
   pmc_sq/  rocprofv3 --pmc SQ_* GRBM_GUI_ACTIVE       -- same
-  bench_line.json   the JSON line of an un-profiled `python bench.py` on the same box
+  bench_line.json   the JSON line of an un-profiled `python bench.py --full` on the same box
 Outputs: profiles/<tag>_kernel_stats.csv, <tag>_pmc_<class>.json, <tag>_sq_counters.md,
 <tag>_bench_line.json, <tag>_summary.md.
 
-usage: python tools/make_profiles.py r02 gpurun_out
+usage: python tools/make_profiles.py r02 profile_out
 """
 import collections
 import csv
