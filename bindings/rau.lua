@@ -43,6 +43,12 @@ int rau_get_mask(rau_ctx* ctx, int site, uint8_t* keep, size_t n);
 int rau_set_batch(rau_ctx* ctx, const float* feats, const int32_t* tokens,
                   const int32_t* lens, const int32_t* labels);
 int rau_batch_feats(rau_ctx* ctx, float** feats_dev);
+int rau_set_batch_typed(rau_ctx* ctx, const void* feats, int feat_type, const int32_t* tokens,
+                        const int32_t* lens, const int32_t* labels);
+int rau_set_batch_async_typed(rau_ctx* ctx, int slot, const void* feats, int feat_type,
+                              const int32_t* tokens, const int32_t* lens, const int32_t* labels,
+                              int has_labels);
+int rau_batch_feat_type(rau_ctx* ctx, int* feat_type);
 int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_host,
                    int32_t** lens_host, int32_t** labels_host);
 int rau_set_batch_async(rau_ctx* ctx, int slot, const float* feats, const int32_t* tokens,
@@ -158,8 +164,15 @@ end
 function RAU:reset(seed, lo, hi) check(C.rau_init_uniform(self.h, seed or 123, lo or -0.08, hi or 0.08)) end
 
 -- feats: FloatTensor [B,D,W,H]; x: IntTensor [T,B]; x_len, y: IntTensor [B]  (loader.lua:1009)
+-- A HalfTensor feats goes up as fp16 (rau_set_batch_typed): half the bytes, the same results
+-- bit for bit as feats:float().
+local FEAT = { f32 = 0, f16 = 1, bf16 = 2 }   -- rau_feat_type
 function RAU:setBatch(feats, x, x_len, y)
-  check(C.rau_set_batch(self.h, feats:data(), x:data(), x_len:data(), y and y:data() or nil))
+  if torch.type(feats) == 'torch.HalfTensor' then
+    check(C.rau_set_batch_typed(self.h, feats:data(), FEAT.f16, x:data(), x_len:data(), y and y:data() or nil))
+  else
+    check(C.rau_set_batch(self.h, feats:data(), x:data(), x_len:data(), y and y:data() or nil))
+  end
 end
 
 -- Asynchronous, double-buffered upload (slot = 0 | 1): what SS:434-439 does every iteration, moved
@@ -168,22 +181,26 @@ end
 -- assemble the batch in; rau:setBatchAsync(slot) enqueues the upload of what is in them (pass
 -- tensors to have them copied into the staging first); rau:useBatch(slot) makes it the resident
 -- batch -- the step's streams wait for the copies by an event, the host never does.
-function RAU:batchSlot(slot)
+-- feat_type 'f16': the slot's feats come back as a HalfTensor over the start of its staging.
+function RAU:batchSlot(slot, feat_type)
   local f, x, l, y = ffi.new('float*[1]'), ffi.new('int32_t*[1]'), ffi.new('int32_t*[1]'), ffi.new('int32_t*[1]')
   check(C.rau_batch_slot(self.h, slot, f, x, l, y))
   local c = self.cfg
   local function addr(p) return tonumber(ffi.cast('intptr_t', p)) end
+  local n = c.B * c.D * c.S
   return {
-    feats = torch.FloatTensor(torch.FloatStorage(c.B * c.D * c.S, addr(f[0]))):resize(c.B, c.D, c.S),
+    feats = feat_type == 'f16' and torch.HalfTensor(torch.HalfStorage(n, addr(f[0]))):resize(c.B, c.D, c.S)
+            or torch.FloatTensor(torch.FloatStorage(n, addr(f[0]))):resize(c.B, c.D, c.S),
     x = torch.IntTensor(torch.IntStorage(c.T * c.B, addr(x[0]))):resize(c.T, c.B),
     x_len = torch.IntTensor(torch.IntStorage(c.B, addr(l[0]))),
     y = torch.IntTensor(torch.IntStorage(c.B, addr(y[0]))),
   }
 end
-function RAU:setBatchAsync(slot, feats, x, x_len, y, has_labels)
-  check(C.rau_set_batch_async(self.h, slot, feats and feats:data() or nil, x and x:data() or nil,
-                              x_len and x_len:data() or nil, y and y:data() or nil,
-                              (has_labels == false) and 0 or 1))
+function RAU:setBatchAsync(slot, feats, x, x_len, y, has_labels, feat_type)
+  local ft = FEAT[feat_type or (feats and torch.type(feats) == 'torch.HalfTensor' and 'f16') or 'f32']
+  check(C.rau_set_batch_async_typed(self.h, slot, feats and feats:data() or nil, ft, x and x:data() or nil,
+                                    x_len and x_len:data() or nil, y and y:data() or nil,
+                                    (has_labels == false) and 0 or 1))
 end
 function RAU:useBatch(slot) check(C.rau_use_batch(self.h, slot)) end
 

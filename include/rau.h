@@ -160,8 +160,35 @@ int rau_get_mask(rau_ctx* ctx, int site, uint8_t* keep, size_t n);
  * the LookupTable gradient a deterministic gather-sum. */
 int rau_set_batch(rau_ctx* ctx, const float* feats, const int32_t* tokens,
                   const int32_t* lens, const int32_t* labels);
-/* device pointer of the resident feature buffer (producer may write it directly) */
+/* device pointer of the resident feature buffer (producer may write it directly).  It is returned as it
+ * is: after a 16-bit batch (rau_set_batch_typed) its first B*D*Sp*2 bytes hold that batch's 16-bit
+ * elements at row pitch Sp (S rounded up to a multiple of 4), not floats. */
 int rau_batch_feats(rau_ctx* ctx, float** feats_dev);
+
+/* ---- 16-bit feature maps ---------------------------------------------------------------------------
+ * The element type of a batch's feature map.  16-bit maps halve the host-to-device transfer, the pinned
+ * staging and the host memory that holds the features.  Widening a 16-bit value to f32 is exact, and
+ * every pass that reads the batch widens first and then does the f32 arithmetic, so a batch given as
+ * fp16 or bf16 gives BIT-IDENTICAL results to the same batch given as f32 holding the widened values
+ * (finite inputs; fp16 subnormals included).  The type belongs to the batch, not to the ctx: each slot
+ * of the asynchronous path records the type of the batch it holds and rau_use_batch makes it current.
+ * rau_set_batch / rau_set_batch_async are the RAU_FEAT_F32 case.  An unknown type is RAU_ERR_INVALID. */
+typedef enum rau_feat_type {
+  RAU_FEAT_F32 = 0,
+  RAU_FEAT_F16 = 1,   /* IEEE binary16, passed as its bit patterns */
+  RAU_FEAT_BF16 = 2   /* bfloat16 bit patterns (the upper half of an f32) */
+} rau_feat_type;
+/* rau_set_batch with feats [B,D,S] of elements of feat_type (feats NULL: the resident buffer already
+ * holds the map, written through rau_batch_feats, in that type) */
+int rau_set_batch_typed(rau_ctx* ctx, const void* feats, int feat_type, const int32_t* tokens,
+                        const int32_t* lens, const int32_t* labels);
+/* rau_set_batch_async with feats of elements of feat_type; feats NULL: the slot's pinned staging
+ * (rau_batch_slot) already holds B*D*S elements of feat_type at its start */
+int rau_set_batch_async_typed(rau_ctx* ctx, int slot, const void* feats, int feat_type,
+                              const int32_t* tokens, const int32_t* lens, const int32_t* labels,
+                              int has_labels);
+/* element type of the resident batch */
+int rau_batch_feat_type(rau_ctx* ctx, int* feat_type);
 
 /* ---- asynchronous, double-buffered upload: SS:434-439 behind the loader's prefetch -------------
  * The reference re-uploads feats / x / x_len / y every iteration (SS:434-439) while its loader's

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/rau.h"   // rau_feat_type
+
 namespace rau {
 
 // ------------------------------------------------ split-K partials: fail closed (split_guard.hip)
@@ -305,20 +307,28 @@ hipError_t att_bwd_split(hipStream_t st, int nB, int M, int A, int S, const floa
                          float* T_to_dS, float* dz, float* du, float* dwsp, const float* Psrc,
                          const float* u, float* part, int da_ns = 0, int SL = 0,
                          const float* da_add = nullptr);
+// The feature-map passes below read the resident batch in its own element type ft (rau_feat_type:
+// RAU_FEAT_F32, or 16-bit RAU_FEAT_F16 / RAU_FEAT_BF16 bit patterns laid out like the f32 form), widen
+// each element exactly to f32 and then do the f32 form's arithmetic: results are bit-identical to an
+// f32 batch holding the widened values.  An unknown ft is hipErrorInvalidValue, nothing launched.
+inline bool feat_type_ok(int ft) { return ft == RAU_FEAT_F32 || ft == RAU_FEAT_F16 || ft == RAU_FEAT_BF16; }
 // xd[h][i] = X[i] * keep(h, i) * scale for h < H, i < per_hop (feature-map dropout, SS:239)
 // SL != Sp: rows of SL logical positions at pitch Sp (mask indexed logically, pad columns zeroed)
-hipError_t dropout_features(hipStream_t st, int H, size_t per_hop, const float* X,
+hipError_t dropout_features(hipStream_t st, int H, size_t per_hop, const void* X,
                             const uint32_t* mask, float mscale, float* xd, size_t mask_e0 = 0,
-                            int SL = 0, int Sp = 0);
+                            int SL = 0, int Sp = 0, int ft = RAU_FEAT_F32);
 // The same pass (f32 or, b16 != 0, bf16 output) drawing the site's keep bits itself instead of reading
 // them: per_hop % 16 == 0, logical == physical layout; bit-identical to fill_masks + dropout_features
 hipError_t dropout_features_gen(hipStream_t st, uint64_t seed, uint32_t site, uint32_t step, float p,
-                                const uint64_t* key_dev, int H, size_t per_hop, const float* X,
-                                float mscale, void* xd, int b16);
+                                const uint64_t* key_dev, int H, size_t per_hop, const void* X,
+                                float mscale, void* xd, int b16, int ft = RAU_FEAT_F32);
 // RAU_BF16 mode (S % 4 == 0): the same values stored as bf16, [h][i], the form conv_embed_fwd_b16 /
 // conv_embed_wgrad_b16 read
-hipError_t dropout_features_b16(hipStream_t st, int H, size_t per_hop, const float* X,
-                                const uint32_t* mask, float mscale, void* xd16);
+hipError_t dropout_features_b16(hipStream_t st, int H, size_t per_hop, const void* X,
+                                const uint32_t* mask, float mscale, void* xd16, int ft = RAU_FEAT_F32);
+// out[r][s] = widen(X[r][s]) for s < SL, 0 for SL <= s < Sp: the f32 image of a 16-bit feature map
+// (ft = RAU_FEAT_F16 / RAU_FEAT_BF16) at row pitch Sp, for the readers that take the unmasked batch
+hipError_t widen_features(hipStream_t st, size_t rows, int SL, int Sp, const void* X, float* out, int ft);
 // dst[n] += sum_rows X[row*ld + n]   (two-stage, deterministic; tmp >= 32*N floats)
 hipError_t colsum_acc(hipStream_t st, int rows, int N, const float* X, long ld, float* dst,
                       float* tmp);

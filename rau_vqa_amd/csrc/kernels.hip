@@ -1395,13 +1395,45 @@ hipError_t transpose2d(hipStream_t st, int rows, int cols, const float* in, floa
   return hipGetLastError();
 }
 
+// ---- element type of the resident feature map (rau_feat_type): f32, IEEE fp16 or bf16.  Widening a
+// 16-bit value to f32 is exact, so every pass below does exactly the f32 arithmetic of the f32 form on
+// the widened value.  fp16 is widened by integer operations: subnormal halves are normal f32 numbers
+// and come out unchanged under any denorm mode (no f16 / f32 denormal ever enters a float op).
+__device__ __forceinline__ float widen_f16(uint32_t h) {
+  const uint32_t sign = (h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
+  if (e == 0) {   // +-0 and subnormals: m * 2^-24, an exact product with a normal f32 result
+    const float v = (float)m * 0x1p-24f;
+    return __uint_as_float(__float_as_uint(v) | sign);
+  }
+  return __uint_as_float(sign | (e == 31 ? 0x7f800000u : (e + 112u) << 23) | (m << 13));
+}
+template <int FT>
+__device__ __forceinline__ float widen1(uint32_t h) {
+  return FT == RAU_FEAT_F16 ? widen_f16(h) : __uint_as_float(h << 16);
+}
+// element i of X (f32, or 16-bit bit patterns)
+template <int FT>
+__device__ __forceinline__ float load_feat(const void* __restrict__ X, size_t i) {
+  if (FT == RAU_FEAT_F32) return reinterpret_cast<const float*>(X)[i];
+  return widen1<FT>(reinterpret_cast<const uint16_t*>(X)[i]);
+}
+// quad q of X (elements 4q .. 4q+3): one 16-byte load for f32, one 8-byte load for 16-bit data
+template <int FT>
+__device__ __forceinline__ float4 load_feat4(const void* __restrict__ X, size_t q) {
+  if (FT == RAU_FEAT_F32) return reinterpret_cast<const float4*>(X)[q];
+  const uint2 v = reinterpret_cast<const uint2*>(X)[q];
+  return make_float4(widen1<FT>(v.x & 0xffffu), widen1<FT>(v.x >> 16), widen1<FT>(v.y & 0xffffu),
+                     widen1<FT>(v.y >> 16));
+}
+
 // feature-map dropout for every hop in one pass (reference SS:239, one mask per clone)
-__global__ void k_dropout_features(int H, size_t per4, const float4* __restrict__ X,
+template <int FT>
+__global__ void k_dropout_features(int H, size_t per4, const void* __restrict__ X,
                                    const uint32_t* __restrict__ mask, size_t e0, float mscale,
                                    float4* __restrict__ xd) {
   for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < per4;
        q += (size_t)gridDim.x * blockDim.x) {
-    const float4 x = X[q];
+    const float4 x = load_feat4<FT>(X, q);
     for (int h = 0; h < H; ++h) {
       const size_t e = e0 + ((size_t)h * per4 + q) * 4;
       const uint32_t nib = mask_nib(mask, e);
@@ -1416,12 +1448,13 @@ __global__ void k_dropout_features(int H, size_t per4, const float4* __restrict_
 }
 // RAU_BF16 mode: the same pass writing bf16 (RNE of the f32 value the other form stores, i.e. exactly
 // what the bf16 operand staging would have made of it), the only form the bf16 step path reads
-__global__ void k_dropout_features_b16(int H, size_t per4, const float4* __restrict__ X,
+template <int FT>
+__global__ void k_dropout_features_b16(int H, size_t per4, const void* __restrict__ X,
                                        const uint32_t* __restrict__ mask, size_t e0, float mscale,
                                        uint2* __restrict__ xd) {
   for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < per4;
        q += (size_t)gridDim.x * blockDim.x) {
-    const float4 x = X[q];
+    const float4 x = load_feat4<FT>(X, q);
     for (int h = 0; h < H; ++h) {
       const size_t e = e0 + ((size_t)h * per4 + q) * 4;
       const uint32_t nib = mask_nib(mask, e);
@@ -1440,10 +1473,10 @@ __global__ void k_dropout_features_b16(int H, size_t per4, const float4* __restr
 // travel through memory and fill_masks' pass over the site (44 us at D = 512, 163 us at D = 2048 per
 // step, in front of the first conv GEMM) disappears under this pass's HBM time.  Same (seed, site,
 // step, element) -> bit function as fill_masks: the masks are bit-identical.
-template <bool B16>
+template <bool B16, int FT>
 __global__ void k_dropout_features_gen(uint64_t seed, uint32_t site, uint32_t step, uint32_t thr,
                                        const uint64_t* __restrict__ key, int H, size_t per16,
-                                       const float4* __restrict__ X, float mscale,
+                                       const void* __restrict__ X, float mscale,
                                        void* __restrict__ xd) {
   if (key) {
     seed = key[0];
@@ -1454,7 +1487,7 @@ __global__ void k_dropout_features_gen(uint64_t seed, uint32_t site, uint32_t st
   // load / store instruction of the wave covers one contiguous KB (the owner's bits come by shuffle).
   // With each lane storing its own block's four quads the lanes of an instruction are 64 bytes apart
   // and every 128-byte line is written in four pieces (262 us at D = 512 against 190 us for a plain
-  // copy of the same bytes).
+  // copy of the same bytes).  16-bit input: a quad is 8 bytes, a load instruction one contiguous 512 B.
   const int l = threadIdx.x & 63, quad = l & 3, sub = l >> 2;
   for (size_t base = (blockIdx.x * (size_t)blockDim.x + (threadIdx.x & ~63u)); base < per16;
        base += (size_t)gridDim.x * blockDim.x) {
@@ -1464,7 +1497,7 @@ __global__ void k_dropout_features_gen(uint64_t seed, uint32_t site, uint32_t st
     for (int r = 0; r < 4; ++r) {
       const size_t blk = base + 16 * r + sub;
       ok[r] = blk < per16;
-      x[r] = ok[r] ? X[4 * blk + quad] : make_float4(0.f, 0.f, 0.f, 0.f);
+      x[r] = ok[r] ? load_feat4<FT>(X, 4 * blk + quad) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     const size_t mine = base + l < per16 ? base + l : per16 - 1;
     for (int h = 0; h < H; ++h) {
@@ -1491,24 +1524,39 @@ __global__ void k_dropout_features_gen(uint64_t seed, uint32_t site, uint32_t st
     }
   }
 }
+template <bool B16>
+static void launch_dropout_gen(hipStream_t st, int ft, dim3 grid, uint64_t seed, uint32_t site,
+                               uint32_t step, uint32_t thr, const uint64_t* key, int H, size_t per16,
+                               const void* X, float mscale, void* xd) {
+  if (ft == RAU_FEAT_F16)
+    hipLaunchKernelGGL((k_dropout_features_gen<B16, RAU_FEAT_F16>), grid, dim3(256), 0, st, seed, site, step,
+                       thr, key, H, per16, X, mscale, xd);
+  else if (ft == RAU_FEAT_BF16)
+    hipLaunchKernelGGL((k_dropout_features_gen<B16, RAU_FEAT_BF16>), grid, dim3(256), 0, st, seed, site, step,
+                       thr, key, H, per16, X, mscale, xd);
+  else
+    hipLaunchKernelGGL((k_dropout_features_gen<B16, RAU_FEAT_F32>), grid, dim3(256), 0, st, seed, site, step,
+                       thr, key, H, per16, X, mscale, xd);
+}
 hipError_t dropout_features_gen(hipStream_t st, uint64_t seed, uint32_t site, uint32_t step, float p,
-                                const uint64_t* key_dev, int H, size_t per_hop, const float* X,
-                                float mscale, void* xd, int b16) {
-  if (per_hop % 16 != 0) return hipErrorInvalidValue;
+                                const uint64_t* key_dev, int H, size_t per_hop, const void* X,
+                                float mscale, void* xd, int b16, int ft) {
+  if (per_hop % 16 != 0 || !feat_type_ok(ft)) return hipErrorInvalidValue;
   const uint32_t thr = (uint32_t)lroundf(p * 256.0f);
   const size_t per16 = per_hop / 16;
   if (b16)
-    hipLaunchKernelGGL(k_dropout_features_gen<true>, dim3(grid_for(per16)), dim3(256), 0, st, seed, site,
-                       step, thr, key_dev, H, per16, reinterpret_cast<const float4*>(X), mscale, xd);
+    launch_dropout_gen<true>(st, ft, dim3(grid_for(per16)), seed, site, step, thr, key_dev, H, per16, X,
+                             mscale, xd);
   else
-    hipLaunchKernelGGL(k_dropout_features_gen<false>, dim3(grid_for(per16)), dim3(256), 0, st, seed, site,
-                       step, thr, key_dev, H, per16, reinterpret_cast<const float4*>(X), mscale, xd);
+    launch_dropout_gen<false>(st, ft, dim3(grid_for(per16)), seed, site, step, thr, key_dev, H, per16, X,
+                              mscale, xd);
   return hipGetLastError();
 }
 // Pitched rows (S not a multiple of 4): the mask is defined over the LOGICAL tensor
 // [.., rows, SL], the data has row pitch Sp; pad columns are written as zeros.
+template <int FT>
 __global__ void k_dropout_features_pitch(int H, size_t rows, int SL, int Sp,
-                                         const float* __restrict__ X,
+                                         const void* __restrict__ X,
                                          const uint32_t* __restrict__ mask, size_t e0, float mscale,
                                          float* __restrict__ xd) {
   const size_t n = rows * Sp;
@@ -1516,7 +1564,7 @@ __global__ void k_dropout_features_pitch(int H, size_t rows, int SL, int Sp,
        i += (size_t)gridDim.x * blockDim.x) {
     const size_t r = i / Sp;
     const int s = (int)(i - r * Sp);
-    const float x = X[i];
+    const float x = load_feat<FT>(X, i);
     for (int h = 0; h < H; ++h) {
       float o = 0.f;
       if (s < SL) o = mask_bit(mask, e0 + ((size_t)h * rows + r) * SL + s) ? x * mscale : 0.f;
@@ -1524,27 +1572,70 @@ __global__ void k_dropout_features_pitch(int H, size_t rows, int SL, int Sp,
     }
   }
 }
-hipError_t dropout_features(hipStream_t st, int H, size_t per_hop, const float* X,
+// one launch of `kern`<FT> for the run-time element type ft
+#define LAUNCH_FT(kern, ft, grid, ...)                                                        \
+  do {                                                                                        \
+    if ((ft) == RAU_FEAT_F16)                                                                 \
+      hipLaunchKernelGGL(kern<RAU_FEAT_F16>, grid, dim3(256), 0, st, __VA_ARGS__);            \
+    else if ((ft) == RAU_FEAT_BF16)                                                           \
+      hipLaunchKernelGGL(kern<RAU_FEAT_BF16>, grid, dim3(256), 0, st, __VA_ARGS__);           \
+    else                                                                                      \
+      hipLaunchKernelGGL(kern<RAU_FEAT_F32>, grid, dim3(256), 0, st, __VA_ARGS__);            \
+  } while (0)
+hipError_t dropout_features(hipStream_t st, int H, size_t per_hop, const void* X,
                             const uint32_t* mask, float mscale, float* xd, size_t mask_e0, int SL,
-                            int Sp) {
+                            int Sp, int ft) {
+  if (!feat_type_ok(ft)) return hipErrorInvalidValue;
   if (SL != Sp) {
-    hipLaunchKernelGGL(k_dropout_features_pitch, dim3(grid_for(per_hop)), dim3(256), 0, st, H,
-                       per_hop / Sp, SL, Sp, X, mask, mask_e0, mscale, xd);
+    LAUNCH_FT(k_dropout_features_pitch, ft, dim3(grid_for(per_hop)), H, per_hop / Sp, SL, Sp, X, mask,
+              mask_e0, mscale, xd);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(k_dropout_features, dim3(grid_for(per_hop / 4)), dim3(256), 0, st, H,
-                     per_hop / 4, reinterpret_cast<const float4*>(X), mask, mask_e0, mscale,
-                     reinterpret_cast<float4*>(xd));
+  LAUNCH_FT(k_dropout_features, ft, dim3(grid_for(per_hop / 4)), H, per_hop / 4, X, mask, mask_e0, mscale,
+            reinterpret_cast<float4*>(xd));
   return hipGetLastError();
 }
 
-hipError_t dropout_features_b16(hipStream_t st, int H, size_t per_hop, const float* X,
-                                const uint32_t* mask, float mscale, void* xd16) {
-  hipLaunchKernelGGL(k_dropout_features_b16, dim3(grid_for(per_hop / 4)), dim3(256), 0, st, H,
-                     per_hop / 4, reinterpret_cast<const float4*>(X), mask, (size_t)0, mscale,
-                     reinterpret_cast<uint2*>(xd16));
+hipError_t dropout_features_b16(hipStream_t st, int H, size_t per_hop, const void* X,
+                                const uint32_t* mask, float mscale, void* xd16, int ft) {
+  if (!feat_type_ok(ft)) return hipErrorInvalidValue;
+  LAUNCH_FT(k_dropout_features_b16, ft, dim3(grid_for(per_hop / 4)), H, per_hop / 4, X, mask, (size_t)0,
+            mscale, reinterpret_cast<uint2*>(xd16));
   return hipGetLastError();
 }
+
+// 16-bit feature map -> its f32 image, [rows][Sp] with pad columns written as zeros (the form every
+// f32 reader of the resident batch expects).  Dense rows (SL == Sp): one 8-byte load and one 16-byte
+// store per quad.
+template <int FT>
+__global__ void k_widen_features(size_t per4, const void* __restrict__ X, float4* __restrict__ out) {
+  for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < per4;
+       q += (size_t)gridDim.x * blockDim.x)
+    out[q] = load_feat4<FT>(X, q);
+}
+template <int FT>
+__global__ void k_widen_features_pitch(size_t rows, int SL, int Sp, const void* __restrict__ X,
+                                       float* __restrict__ out) {
+  const size_t n = rows * Sp;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
+       i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / Sp;
+    const int s = (int)(i - r * Sp);
+    out[i] = s < SL ? load_feat<FT>(X, i) : 0.f;
+  }
+}
+hipError_t widen_features(hipStream_t st, size_t rows, int SL, int Sp, const void* X, float* out, int ft) {
+  if (ft != RAU_FEAT_F16 && ft != RAU_FEAT_BF16) return hipErrorInvalidValue;
+  if (SL != Sp) {
+    LAUNCH_FT(k_widen_features_pitch, ft, dim3(grid_for(rows * Sp)), rows, SL, Sp, X, out);
+    return hipGetLastError();
+  }
+  if ((rows * Sp) % 4 != 0) return hipErrorInvalidValue;
+  LAUNCH_FT(k_widen_features, ft, dim3(grid_for(rows * Sp / 4)), rows * Sp / 4, X,
+            reinterpret_cast<float4*>(out));
+  return hipGetLastError();
+}
+#undef LAUNCH_FT
 
 // ----------------------------------------------- deterministic column sums
 // dst[n] += sum_r X[r, n]: stage 1 sums kColChunks row chunks (fixed order inside a chunk),

@@ -75,10 +75,11 @@ struct ProfCls {
 // device buffers, pinned host staging the loader may fill in place, the host-side metadata
 // rau_forward needs, and the two events that order uploads against the steps.
 struct BatchSlot {
-  float* feats = nullptr;                                   // device, [B][D][Sp]
+  float* feats = nullptr;                                   // device, [B][D][Sp] (16-bit batch: its first half)
   int32_t *tokens = nullptr, *lens_d = nullptr, *labels_d = nullptr;
   int32_t *utok = nullptr, *ustart = nullptr, *upos = nullptr;
-  float* feats_h = nullptr;                                 // pinned host, dense [B][D][S]
+  float* feats_h = nullptr;                                 // pinned host, dense [B][D][S] (16-bit: first half)
+  int feat_type = RAU_FEAT_F32;                             // rau_feat_type of the batch the slot holds
   int32_t *tokens_h = nullptr, *lens_p = nullptr, *labels_h = nullptr;
   int32_t *utok_h = nullptr, *ustart_h = nullptr, *upos_h = nullptr;
   std::vector<int32_t> lens;
@@ -118,6 +119,9 @@ struct rau_ctx {
   Lin i2h[2], h2h[2];
   // batch
   float* feats = nullptr;
+  int feat_type = RAU_FEAT_F32;   // rau_feat_type of the resident batch (what `feats` holds)
+  float* xw = nullptr;            // f32 image of the unmasked batch the last forward read: feats, or (16-bit
+                                  // batch) the first B*D*Sp floats of xd, widened there by that forward
   int32_t *tokens = nullptr, *lens_d = nullptr, *labels_d = nullptr;
   std::vector<int32_t> lens_h;
   int max_len = 0;
@@ -181,6 +185,7 @@ struct rau_ctx {
   float *m_tmp[4] = {nullptr, nullptr, nullptr, nullptr};  // [B][max(Rq,R,M)] scratch
   float *m_dq = nullptr, *m_dc = nullptr, *m_dh = nullptr;  // [H][B][Q], [H][B][R], [H][B][R]
   float *m_Xp = nullptr, *m_a = nullptr, *m_da = nullptr, *m_dXd = nullptr;  // re-pitching (S % 4 != 0)
+  float* m_Xw = nullptr;   // [B][D][Sp]: f32 image of a 16-bit resident batch (X = NULL)
   float *m_dX = nullptr, *m_dZ = nullptr;          // [B][D][S], [B][M][S]: feature-map gradient, on request
   float *m_add = nullptr, *m_s = nullptr, *m_zero = nullptr;  // [B][M], [B], zeros [B][max(Q,R)]
   float *m_loss = nullptr;                         // [H] criterion outputs

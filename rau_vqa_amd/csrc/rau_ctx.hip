@@ -751,17 +751,21 @@ int index_batch(const rau_config& c, const int32_t* tokens, const int32_t* lens,
   return RAU_OK;
 }
 
-// H2D copies of one batch into a set of device buffers, enqueued on `s`
-int enqueue_batch(rau_ctx* ctx, hipStream_t s, const BatchSlot& d, const float* feats,
-                  const int32_t* tokens, const int32_t* lens, const int32_t* labels,
+// H2D copies of one batch into a set of device buffers, enqueued on `s`.  feats holds elements of
+// feat_type (4 or 2 bytes); prev_type is the type of what the device buffer holds now.
+int enqueue_batch(rau_ctx* ctx, hipStream_t s, const BatchSlot& d, const void* feats, int feat_type,
+                  int prev_type, const int32_t* tokens, const int32_t* lens, const int32_t* labels,
                   const int32_t* utok, const int32_t* ustart, const int32_t* upos) {
   const rau_config& c = ctx->cfg;
-  const size_t TB = (size_t)c.T * c.B;
+  const size_t TB = (size_t)c.T * c.B, es = feat_type == RAU_FEAT_F32 ? 4 : 2;
+  // pitched rows of another element size leave data in this type's pad columns: zero them first
+  if (feats && ctx->Sp != c.S && feat_type != prev_type)
+    HIPC(hipMemsetAsync(d.feats, 0, (size_t)c.B * c.D * ctx->Sp * sizeof(float), s));
   if (feats && ctx->Sp == c.S)   // dense on both sides: one linear copy (a DMA-engine transfer, no blit kernel)
-    HIPC(hipMemcpyAsync(d.feats, feats, (size_t)c.B * c.D * c.S * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(d.feats, feats, (size_t)c.B * c.D * c.S * es, hipMemcpyHostToDevice, s));
   else if (feats)   // rows of S positions into rows of Sp (pad columns stay zero)
-    HIPC(hipMemcpy2DAsync(d.feats, (size_t)ctx->Sp * sizeof(float), feats, (size_t)c.S * sizeof(float),
-                          (size_t)c.S * sizeof(float), (size_t)c.B * c.D, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpy2DAsync(d.feats, (size_t)ctx->Sp * es, feats, (size_t)c.S * es, (size_t)c.S * es,
+                          (size_t)c.B * c.D, hipMemcpyHostToDevice, s));
   HIPC(hipMemcpyAsync(d.tokens, tokens, TB * 4, hipMemcpyHostToDevice, s));
   HIPC(hipMemcpyAsync(d.lens_d, lens, (size_t)c.B * 4, hipMemcpyHostToDevice, s));
   if (labels) HIPC(hipMemcpyAsync(d.labels_d, labels, (size_t)c.B * 4, hipMemcpyHostToDevice, s));
@@ -775,6 +779,7 @@ void make_current(rau_ctx* ctx, int si) {
   BatchSlot& s = ctx->slot[si];
   ctx->cur_slot = si;
   ctx->feats = s.feats; ctx->tokens = s.tokens; ctx->lens_d = s.lens_d; ctx->labels_d = s.labels_d;
+  ctx->feat_type = s.feat_type;
   ctx->utok = s.utok; ctx->ustart = s.ustart; ctx->upos = s.upos;
   ctx->lens_h = s.lens;
   ctx->max_len = s.max_len;
@@ -793,7 +798,7 @@ int ensure_async(rau_ctx* ctx) {
   s0.feats = ctx->feats; s0.tokens = ctx->tokens; s0.lens_d = ctx->lens_d; s0.labels_d = ctx->labels_d;
   s0.utok = ctx->utok; s0.ustart = ctx->ustart; s0.upos = ctx->upos;
   s0.lens = ctx->lens_h; s0.max_len = ctx->max_len; s0.nuniq = ctx->nuniq;
-  s0.have = ctx->have_batch; s0.have_labels = ctx->have_labels;
+  s0.have = ctx->have_batch; s0.have_labels = ctx->have_labels; s0.feat_type = ctx->feat_type;
   BatchSlot& s1 = ctx->slot[1];
   if (int rc = dalloc(ctx, &s1.feats, (size_t)c.B * c.D * ctx->Sp)) return rc;
   if (int rc = dalloc(ctx, &s1.tokens, TB)) return rc;
@@ -831,7 +836,13 @@ extern "C" {
 
 int rau_set_batch(rau_ctx* ctx, const float* feats, const int32_t* tokens, const int32_t* lens,
                   const int32_t* labels) {
+  return rau_set_batch_typed(ctx, feats, RAU_FEAT_F32, tokens, lens, labels);
+}
+
+int rau_set_batch_typed(rau_ctx* ctx, const void* feats, int feat_type, const int32_t* tokens,
+                        const int32_t* lens, const int32_t* labels) {
   NEED(ctx && tokens && lens, "null argument");
+  NEED(feat_type_ok(feat_type), "rau_set_batch_typed: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)", feat_type);
   const rau_config& c = ctx->cfg;
   const size_t TB = (size_t)c.T * c.B;
   std::vector<int32_t> utok(TB), ustart(TB + 1), upos(TB);
@@ -843,10 +854,11 @@ int rau_set_batch(rau_ctx* ctx, const float* feats, const int32_t* tokens, const
   d.utok = ctx->utok; d.ustart = ctx->ustart; d.upos = ctx->upos;
   if (ctx->async_ready && ctx->slot[ctx->cur_slot].upload_pending)   // an async upload into the same buffers
     HIPC(hipStreamWaitEvent(ctx->st, ctx->slot[ctx->cur_slot].uploaded, 0));
-  if (int rc = enqueue_batch(ctx, ctx->st, d, feats, tokens, lens, labels, utok.data(), ustart.data(),
-                             upos.data()))
+  if (int rc = enqueue_batch(ctx, ctx->st, d, feats, feat_type, ctx->feat_type, tokens, lens, labels,
+                             utok.data(), ustart.data(), upos.data()))
     return rc;
   HIPC(hipStreamSynchronize(ctx->st));   // the caller's (pageable) buffers are free on return
+  ctx->feat_type = feat_type;
   ctx->lens_h.assign(lens, lens + c.B);
   ctx->max_len = max_len;
   ctx->nuniq = nuniq;
@@ -857,6 +869,7 @@ int rau_set_batch(rau_ctx* ctx, const float* feats, const int32_t* tokens, const
     BatchSlot& s = ctx->slot[ctx->cur_slot];
     s.lens = ctx->lens_h; s.max_len = max_len; s.nuniq = nuniq;
     s.have = true; s.have_labels = ctx->have_labels; s.upload_pending = false;
+    s.feat_type = feat_type;
   }
   return RAU_OK;
 }
@@ -880,7 +893,15 @@ int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_
 
 int rau_set_batch_async(rau_ctx* ctx, int slot, const float* feats, const int32_t* tokens,
                         const int32_t* lens, const int32_t* labels, int has_labels) {
+  return rau_set_batch_async_typed(ctx, slot, feats, RAU_FEAT_F32, tokens, lens, labels, has_labels);
+}
+
+int rau_set_batch_async_typed(rau_ctx* ctx, int slot, const void* feats, int feat_type,
+                              const int32_t* tokens, const int32_t* lens, const int32_t* labels,
+                              int has_labels) {
   NEED(ctx, "null ctx");
+  NEED(feat_type_ok(feat_type), "rau_set_batch_async_typed: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)",
+       feat_type);
   NEED(slot == 0 || slot == 1, "rau_set_batch_async: slot %d (0 or 1)", slot);
   if (int rc = ensure_async(ctx)) return rc;
   const rau_config& c = ctx->cfg;
@@ -901,7 +922,7 @@ int rau_set_batch_async(rau_ctx* ctx, int slot, const float* feats, const int32_
     s.upload_pending = false;
   }
   // NULL = the caller has filled the slot's pinned staging in place (rau_batch_slot)
-  if (feats && feats != s.feats_h) std::memcpy(s.feats_h, feats, nf * 4);
+  if (feats && feats != s.feats_h) std::memcpy(s.feats_h, feats, nf * (feat_type == RAU_FEAT_F32 ? 4 : 2));
   if (tokens && tokens != s.tokens_h) std::memcpy(s.tokens_h, tokens, TB * 4);
   if (lens && lens != s.lens_p) std::memcpy(s.lens_p, lens, (size_t)c.B * 4);
   if (labels && labels != s.labels_h) std::memcpy(s.labels_h, labels, (size_t)c.B * 4);
@@ -916,11 +937,12 @@ int rau_set_batch_async(rau_ctx* ctx, int slot, const float* feats, const int32_
     s.consumed_valid = true;
   }
   if (s.consumed_valid) HIPC(hipStreamWaitEvent(ctx->stc, s.consumed, 0));
-  if (int rc = enqueue_batch(ctx, ctx->stc, s, s.feats_h, s.tokens_h, s.lens_p,
+  if (int rc = enqueue_batch(ctx, ctx->stc, s, s.feats_h, feat_type, s.feat_type, s.tokens_h, s.lens_p,
                              with_labels ? s.labels_h : nullptr, s.utok_h, s.ustart_h, s.upos_h))
     return rc;
   HIPC(hipEventRecord(s.uploaded, ctx->stc));
   s.upload_pending = true;
+  s.feat_type = feat_type;
   s.lens.assign(s.lens_p, s.lens_p + c.B);
   s.max_len = max_len;
   s.nuniq = nuniq;
@@ -956,6 +978,12 @@ int rau_use_batch(rau_ctx* ctx, int slot) {
 int rau_batch_feats(rau_ctx* ctx, float** feats_dev) {
   NEED(ctx && feats_dev, "null argument");
   *feats_dev = ctx->feats;
+  return RAU_OK;
+}
+
+int rau_batch_feat_type(rau_ctx* ctx, int* feat_type) {
+  NEED(ctx && feat_type, "null argument");
+  *feat_type = ctx->feat_type;
   return RAU_OK;
 }
 
@@ -1444,22 +1472,33 @@ int rau_forward(rau_ctx* ctx) {
       if (int rc = gen_masks(ctx, -1, RAU_MASK_X, sb)) return rc;
     RUNS(sb, "transpose", 0, (double)M * D * 8, transpose2d(sb, M, D, ctx->i_embed.W, ctx->WiT, ctx->WiT16));
     RUNS(sb, "transpose", 0, (double)A * M * 8, transpose2d(sb, A, M, ctx->att_i.W, ctx->WpT, ctx->WpT16));
+    // the batch's element type: 16-bit maps are widened (exactly) by the pass that reads them
+    const int ft = ctx->feat_type;
+    const double xb = ft == RAU_FEAT_F32 ? 4 : 2;   // bytes per element read from the batch
     if (x_gen)
-      RUNS(sb, "dropout_features", 0, (double)(x16 ? H + 2 : 2 * H + 2) * B * D * S * 2,
+      RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * (x16 ? 2 : 4),
            dropout_features_gen(sb, ctx->seed, RAU_MASK_X, ctx->step, ctx->mp[RAU_MASK_X], ctx->dkey, H,
                                 (size_t)B * D * S, ctx->feats, sc(RAU_MASK_X),
-                                x16 ? (void*)ctx->xd16 : (void*)ctx->xd, x16 ? 1 : 0));
+                                x16 ? (void*)ctx->xd16 : (void*)ctx->xd, x16 ? 1 : 0, ft));
     else if (x16)
-      RUNS(sb, "dropout_features", 0, (double)(H + 2) * B * D * S * 2,
-           dropout_features_b16(sb, H, (size_t)B * D * S, ctx->feats, m_x, sc(RAU_MASK_X), ctx->xd16));
+      RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * 2,
+           dropout_features_b16(sb, H, (size_t)B * D * S, ctx->feats, m_x, sc(RAU_MASK_X), ctx->xd16, ft));
     else if (m_x)
-      RUNS(sb, "dropout_features", 0, (double)(H + 1) * B * D * S * 4,
+      RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * 4,
            dropout_features(sb, H, (size_t)B * D * S, ctx->feats, m_x, sc(RAU_MASK_X), ctx->xd, 0, SL,
-                            S));
+                            S, ft));
+    // no mask: the GEMMs read the batch itself -- a 16-bit one through its f32 image in xd (unused here),
+    // so that they are the f32 batch's kernels with the f32 batch's operands
+    ctx->xw = ctx->feats;
+    if (!m_x && ft != RAU_FEAT_F32) {
+      ctx->xw = ctx->xd;
+      RUNS(sb, "widen_features", 0, (double)B * D * S * (xb + 4),
+           widen_features(sb, (size_t)B * D, SL, S, ctx->feats, ctx->xw, ft));
+    }
     for (int h0 = 0; h0 < H; h0 += gsz[h0]) {
       const int nBI = ctx->I_shared ? B : gsz[h0] * B;
       const size_t hb = ctx->I_shared ? 0 : (size_t)h0 * B;  // first (hop, sample) row
-      const float* xin = m_x ? ctx->xd + hb * D * S : ctx->feats;
+      const float* xin = m_x ? ctx->xd + hb * D * S : ctx->xw;
       float* Ig = ctx->I + hb * M * S;
       float* Pg = ctx->I_shared ? ctx->P0 : ctx->T + hb * A * S;
       if (x16)
@@ -1777,7 +1816,7 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
           RUNS(sb, "conv_att_wgrad", gflop(A, M, (double)B * S), ((double)B * A * S + BM_ * S) * 4,
                conv_att_wgrad(sb, B, M, S, A, Th2, ctx->I, ctx->att_i.dW, ctx->slab2, ctx->bf16));
           RUNS(sb, "conv_embed_wgrad", gflop(M, D, (double)B * S), (BM_ * S + (double)B * D * S) * 4,
-               conv_embed_wgrad(sb, B, D, S, M, dZh, ctx->I, ctx->feats, ctx->i_embed.dW, ctx->slab2,
+               conv_embed_wgrad(sb, B, D, S, M, dZh, ctx->I, ctx->xw, ctx->i_embed.dW, ctx->slab2,
                                 ctx->bf16, ctx->i_embed.db));
         }
       }
@@ -1959,6 +1998,7 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
                  ((uint64_t)(zero_grads_first != 0) << 22);
   for (int i = 0; i < 5; ++i) key |= (uint64_t)ctx->mexplicit[i] << (24 + i);
   key |= (uint64_t)ctx->cur_slot << 30;   // the captured kernels hold the batch slot's device pointers
+  key |= (uint64_t)ctx->feat_type << 32;  // ... and read the batch in its element type
   if (int rc = upload_hop_weights(ctx, hop_w)) return rc;
   hipGraphExec_t exec = nullptr;
   for (auto& g : ctx->graphs)

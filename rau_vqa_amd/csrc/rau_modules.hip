@@ -76,6 +76,19 @@ int lin_wgrad(rau_ctx* ctx, Lin& l, const float* dY, const float* X, long ldx, b
                   bias ? l.db : nullptr, ctx->bf16 == 1));
   return 0;
 }
+// X = NULL ("the resident batch"): its f32 form at pitch Sp -- the buffer itself, or for a 16-bit batch
+// its exact widening into ctx-owned scratch (allocated on first use), so that the f32 kernels run on it
+int resident_feats(rau_ctx* ctx, const float** X) {
+  *X = ctx->feats;
+  if (ctx->feat_type == RAU_FEAT_F32) return 0;
+  const rau_config& c = ctx->cfg;
+  if (!ctx->m_Xw)
+    if (int rc = dalloc(ctx, &ctx->m_Xw, (size_t)c.B * c.D * ctx->Sp)) return rc;
+  RUN("widen_features", 0, (double)c.B * c.D * ctx->Sp * 6,
+      widen_features(ctx->st, (size_t)c.B * c.D, c.S, ctx->Sp, ctx->feats, ctx->m_Xw, ctx->feat_type));
+  *X = ctx->m_Xw;
+  return 0;
+}
 // [rows][w_src] -> [rows][w_dst] on the ctx stream (re-pitching of [.., S] tensors)
 int repitch(rau_ctx* ctx, float* dst, size_t w_dst, const float* src, size_t w_src, size_t rows) {
   const size_t w = std::min(w_dst, w_src);
@@ -264,9 +277,10 @@ int rau_multimodal_forward(rau_ctx* ctx, int h, const float* q, const float* X, 
   NEED(h >= 0 && h < c.H, "rau_multimodal_forward: h=%d out of [0,%d)", h, c.H);
   if (int rc = mod_alloc(ctx)) return rc;
   if (int rc = ensure_masks(ctx)) return rc;
+  const bool resident = !X;   // the batch's own map, already at pitch Sp
   if (!X) {
     if (!ctx->have_batch) return fail(RAU_ERR_STATE, "rau_multimodal_forward: no X and no batch");
-    X = ctx->feats;
+    if (int rc = resident_feats(ctx, &X)) return rc;
   }
   if (!c_prev) c_prev = ctx->m_zero;   // att_c / att_h zeros, SS:362-365
   if (!h_prev) h_prev = ctx->m_zero;
@@ -279,7 +293,7 @@ int rau_multimodal_forward(rau_ctx* ctx, int h, const float* q, const float* X, 
   const size_t BM_ = (size_t)B * M, BR_ = (size_t)B * R;
   ctx->I_shared = false;
   ctx->fwd_done = false;   // the step-level slots are being overwritten
-  if (S != SL && X != ctx->feats) {   // dense [B,D,SL] from the caller -> pitched (pad columns stay 0)
+  if (S != SL && !resident) {   // dense [B,D,SL] from the caller -> pitched (pad columns stay 0)
     if (int rc = repitch(ctx, ctx->m_Xp, S, X, SL, (size_t)B * D)) return rc;
     X = ctx->m_Xp;
   }
@@ -339,9 +353,10 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
   const rau_config& c = ctx->cfg;
   NEED(h >= 0 && h < c.H, "rau_multimodal_backward: h=%d out of [0,%d)", h, c.H);
   if (int rc = mod_alloc(ctx)) return rc;
+  const bool resident = !X;
   if (!X) {
     if (!ctx->have_batch) return fail(RAU_ERR_STATE, "rau_multimodal_backward: no X and no batch");
-    X = ctx->feats;
+    if (int rc = resident_feats(ctx, &X)) return rc;
   }
   if (!c_prev) c_prev = ctx->m_zero;
   if (!h_prev) h_prev = ctx->m_zero;
@@ -354,7 +369,7 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
   auto gflop = [](double mm, double n, double k) { return 2.0 * mm * n * k; };
   const size_t BM_ = (size_t)B * M, BS_ = (size_t)B * S, BR_ = (size_t)B * R;
   if (S != SL) {
-    if (X != ctx->feats) {   // the forward of this clone re-pitched the same X
+    if (!resident) {   // the forward of this clone re-pitched the same X
       if (int rc = repitch(ctx, ctx->m_Xp, S, X, SL, (size_t)B * D)) return rc;
       X = ctx->m_Xp;
     }

@@ -25,7 +25,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import t7
+from . import feat16, t7
 
 
 @dataclass
@@ -50,8 +50,10 @@ class DataClass:
     """One split's batch iterator (the reference's ``dataclass``)."""
 
     def __init__(self, qs: QuestionSet, img_names, batch_size, split="train", prefetch=False,
-                 seed=123):
+                 seed=123, feat_type="f32"):
         self.qs, self.img_names, self.batch_size, self.split = qs, list(img_names), batch_size, split
+        # element type of the feats next_batch_feat returns: "f32" | "f16" | "bf16" (uint16 bits)
+        self.feat_type = feat16.check_name(feat_type)
         self.n = int(qs.question.shape[0])
         if self.n < batch_size:
             raise ValueError(f"{self.n} examples < batch_size {batch_size}")
@@ -104,15 +106,18 @@ class DataClass:
                 for i, d in zip(idx, dt)]
 
     @staticmethod
-    def _load_feats(paths, D, W, H, out=None):
-        """Per-image feature files into one [B,D,W,H] array; `out` = a caller-owned destination
-        (the pinned staging of an upload slot: the batch is assembled where the H2D copy reads it)."""
+    def _load_feats(paths, D, W, H, out=None, feat_type="f32"):
+        """Per-image feature files into one [B,D,W,H] array of feat_type; `out` = a caller-owned
+        destination (the pinned staging of an upload slot: the batch is assembled where the H2D copy
+        reads it), whose dtype then decides.  f32 files are rounded into a 16-bit destination on
+        assignment; HalfTensor files are copied as they are into an fp16 one."""
         if out is None:
-            out = np.zeros((len(paths), D, W, H), np.float32)
+            out = np.zeros((len(paths), D, W, H), feat16.dtype_of(feat_type))
         else:
             out = out.reshape(len(paths), D, W, H)
-        for i, p in enumerate(paths):
-            out[i] = t7.load_feature(p, D, W, H).reshape(D, W, H)   # asserts the three sizes
+        keep_half = out.dtype != np.float32
+        for i, p in enumerate(paths):   # load_feature asserts the three sizes
+            feat16.store(out[i], t7.load_feature(p, D, W, H, keep_half).reshape(D, W, H))
         return out
 
     def _start_prefetch(self, tab_featpaths, D, W, H):
@@ -122,7 +127,7 @@ class DataClass:
 
         def work():
             try:
-                holder["feats"] = self._load_feats(paths, D, W, H, dest)
+                holder["feats"] = self._load_feats(paths, D, W, H, dest, self.feat_type)
             except Exception as e:   # surfaced on the consumer side
                 holder["error"] = e
         th = threading.Thread(target=work, daemon=True)
@@ -130,7 +135,7 @@ class DataClass:
         self._job = ((self.batch_index, tuple(paths)), th, holder)
 
     def next_batch_feat(self, tab_featpaths, feat_dim, feat_w=1, feat_h=1):
-        """-> feats [B,D,W,H] f32, x [T,B] i32, x_len [B] i32, a [B] | [B,nMC] i32, qids [B]."""
+        """-> feats [B,D,W,H] (f32, or the 16-bit feat_type), x [T,B] i32, x_len [B] i32, a [B] | [B,nMC] i32, qids [B]."""
         if isinstance(tab_featpaths, (str, os.PathLike)):
             tab_featpaths = [tab_featpaths]
         B = self.batch_size
@@ -145,7 +150,7 @@ class DataClass:
             if key == (self.batch_index, tuple(paths)):
                 feats = holder["feats"]
         if feats is None:
-            feats = self._load_feats(paths, feat_dim, feat_w, feat_h)
+            feats = self._load_feats(paths, feat_dim, feat_w, feat_h, feat_type=self.feat_type)
         x = np.ascontiguousarray(self.qs.question[idx].T, np.int32)          # transpose(1,2)
         x_len = np.ascontiguousarray(self.qs.lengths_q[idx], np.int32)
         qids = np.ascontiguousarray(self.qs.question_id[idx])
@@ -178,8 +183,9 @@ def _read_questions(vqa_dir):
         return {k: f[k] for k in f.files}
 
 
-def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=123):
-    """loader.lua:1294-1473 (without the valid_ratio split)."""
+def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=123, feat_type="f32"):
+    """loader.lua:1294-1473 (without the valid_ratio split); feat_type: element type of the
+    feature maps the iterators return ("f32" | "f16" | "bf16")."""
     with open(os.path.join(vqa_dir, "data_prepro.json")) as f:
         info = json.load(f)
     d = _read_questions(vqa_dir)
@@ -202,17 +208,19 @@ def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=12
     v.vocab_size = len(info["ix_to_word"]) + 1            # including ZEROPAD
     v.answer_size = len(info["ix_to_ans"])
     v.seq_len = v.max_sentence_len = int(train.question.shape[1])
-    v.train_data = DataClass(train, v.img_train, batch_size, "train", prefetch, seed)
-    v.test_data = DataClass(test, v.img_test, test_batch_size or batch_size, "test", prefetch, seed)
+    v.train_data = DataClass(train, v.img_train, batch_size, "train", prefetch, seed, feat_type)
+    v.test_data = DataClass(test, v.img_test, test_batch_size or batch_size, "test", prefetch, seed,
+                            feat_type)
     return v
 
 
-def feed(rau, batch):
-    """next_batch_feat's tuple -> rau_set_batch (the H2D of SS:434-439); returns qids."""
+def feed(rau, batch, feat_type=None):
+    """next_batch_feat's tuple -> rau_set_batch (the H2D of SS:434-439); returns qids.
+    feat_type: that of the feats (needed for bf16, which arrives as uint16 bits)."""
     feats, x, x_len, a, qids = batch
     B, D = feats.shape[0], feats.shape[1]
     labels = a if a.ndim == 1 else None                   # test batches carry MC ids, no labels
-    rau.set_batch(feats.reshape(B, D, -1), x, x_len, labels)
+    rau.set_batch(feats.reshape(B, D, -1), x, x_len, labels, feat_type=feat_type)
     return qids
 
 
@@ -233,28 +241,32 @@ class SlotFeeder:
             qids = feeder.next()                              # batch it+1 resident for the next step
     """
 
-    def __init__(self, rau, data: DataClass, tab_featpaths, feat_dim, feat_w=1, feat_h=1):
+    def __init__(self, rau, data: DataClass, tab_featpaths, feat_dim, feat_w=1, feat_h=1,
+                 feat_type=None):
         self.rau, self.data = rau, data
         self.args = (tab_featpaths, feat_dim, feat_w, feat_h)
         self.slot = 0                  # the slot the NEXT batch is assembled in
+        # element type of the maps in the staging and on the wire (default: the DataClass's)
+        self.feat_type = data.feat_type = feat16.check_name(feat_type or data.feat_type)
+        self._ft = {} if self.feat_type == "f32" else {"feat_type": self.feat_type}   # f32: the plain calls
         data.opt_prefetch = True
         data._job = None               # any batch prefetched before now went to ordinary memory
-        data._next_dest = lambda: self.rau.batch_slot(self.slot)["feats"]
+        data._next_dest = lambda: self.rau.batch_slot(self.slot, **self._ft)["feats"]
         self.qids = self._advance()    # batch 0: read synchronously (nothing to overlap with yet)
 
     def _advance(self):
         d, rau, s = self.data, self.rau, self.slot
-        view = rau.batch_slot(s)                      # (host-waits until the slot's last upload has left)
+        view = rau.batch_slot(s, **self._ft)          # (host-waits until the slot's last upload has left)
         self.slot = s ^ 1                             # the worker started by next_batch_feat fills the other
         feats, x, x_len, a, qids = d.next_batch_feat(*self.args)
         if not np.shares_memory(feats, view["feats"]):   # first batch / a re-drawn order: not prefetched in place
-            view["feats"][...] = feats.reshape(view["feats"].shape)
+            feat16.store(view["feats"], feats.reshape(view["feats"].shape))
         view["tokens"][...] = x
         view["lens"][...] = x_len
         labels = a.ndim == 1                          # test batches carry MC ids, no labels
         if labels:
             view["labels"][...] = a
-        rau.set_batch_async(s, has_labels=labels)     # staging filled in place: no host copy
+        rau.set_batch_async(s, has_labels=labels, **self._ft)   # staging filled in place: no host copy
         rau.use_batch(s)
         return qids
 

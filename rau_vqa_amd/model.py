@@ -14,6 +14,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
+from . import feat16
 
 
 @dataclass
@@ -184,9 +185,11 @@ class RAU:
         return m.reshape(shape)
 
     # ---- batch + the hot path
-    def set_batch(self, feats, tokens, lens, labels=None):
+    def set_batch(self, feats, tokens, lens, labels=None, feat_type=None):
+        """feat_type "f32" | "f16" | "bf16" (default: from the dtype, see feat16.infer): a 16-bit map
+        gives the same results, bit for bit, as the f32 map of its widened values."""
         c = self.cfg
-        feats = np.ascontiguousarray(feats, np.float32)
+        feats, ft = feat16.as_feats(feats, feat_type)
         tokens = np.ascontiguousarray(tokens, np.int32)
         lens = np.ascontiguousarray(lens, np.int32)
         if feats.size != c.B * c.D * c.S or tokens.shape != (c.T, c.B) or lens.shape != (c.B,):
@@ -197,28 +200,43 @@ class RAU:
             if labels.shape != (c.B,):
                 raise ValueError("labels shape")
             lp = labels.ctypes.data
-        L.check(self._lib.rau_set_batch(self._h, feats.ctypes.data, tokens.ctypes.data,
-                                        lens.ctypes.data, lp))
+        L.check(self._lib.rau_set_batch_typed(self._h, feats.ctypes.data, feat16.FEAT_TYPES[ft],
+                                              tokens.ctypes.data, lens.ctypes.data, lp))
+
+    def batch_feat_type(self) -> str:
+        """Element type of the resident batch's feature map."""
+        v = C.c_int()
+        L.check(self._lib.rau_batch_feat_type(self._h, C.byref(v)))
+        return feat16.FEAT_NAMES[v.value]
 
     # asynchronous, double-buffered upload (rau_batch_slot / rau_set_batch_async / rau_use_batch)
-    def batch_slot(self, slot):
+    def batch_slot(self, slot, feat_type="f32"):
         """numpy views of slot's PINNED staging: {feats [B,D,S], tokens [T,B], lens [B], labels [B]}.
-        A loader fills them in place; set_batch_async(slot) then uploads without a host copy."""
+        A loader fills them in place; set_batch_async(slot) then uploads without a host copy.
+        feats is a view of the staging's start in feat_type's dtype (bf16: uint16 bit patterns);
+        upload it with set_batch_async(slot, feat_type=<the same>)."""
         c = self.cfg
+        fdt = feat16.dtype_of(feat_type)
         p = [C.c_void_p() for _ in range(4)]
         L.check(self._lib.rau_batch_slot(self._h, slot, *[C.byref(x) for x in p]))
 
         def view(ptr, n, ct, dt, shape):
             return np.frombuffer((ct * n).from_address(ptr.value), dtype=dt).reshape(shape)
-        return {"feats": view(p[0], c.B * c.D * c.S, C.c_float, np.float32, (c.B, c.D, c.S)),
+        return {"feats": view(p[0], c.B * c.D * c.S, C.c_uint8 * fdt.itemsize, fdt, (c.B, c.D, c.S)),
                 "tokens": view(p[1], c.T * c.B, C.c_int32, np.int32, (c.T, c.B)),
                 "lens": view(p[2], c.B, C.c_int32, np.int32, (c.B,)),
                 "labels": view(p[3], c.B, C.c_int32, np.int32, (c.B,))}
 
-    def set_batch_async(self, slot, feats=None, tokens=None, lens=None, labels=None, has_labels=True):
+    def set_batch_async(self, slot, feats=None, tokens=None, lens=None, labels=None, has_labels=True,
+                        feat_type=None):
         """Enqueue the upload of a batch into `slot` on the copy stream and return.  Arrays left None
-        are taken from the slot's staging (filled in place through batch_slot)."""
+        are taken from the slot's staging (filled in place through batch_slot).  feat_type: as in
+        set_batch; with feats None it names what the staging holds (default "f32")."""
         c = self.cfg
+        if feats is None:
+            ft = feat16.check_name(feat_type or "f32")
+        else:
+            feats, ft = feat16.as_feats(feats, feat_type)
 
         def ptr(a, dt, n):
             if a is None:
@@ -227,11 +245,12 @@ class RAU:
             if a.size != n:
                 raise ValueError("batch shapes do not match the config")
             return a.ctypes.data, a
-        fp, fk = ptr(feats, np.float32, c.B * c.D * c.S)
+        fp, fk = ptr(feats, feat16.dtype_of(ft), c.B * c.D * c.S)
         tp, tk = ptr(tokens, np.int32, c.T * c.B)
         lp, lk = ptr(lens, np.int32, c.B)
         yp, yk = ptr(labels, np.int32, c.B)
-        L.check(self._lib.rau_set_batch_async(self._h, slot, fp, tp, lp, yp, int(bool(has_labels))))
+        L.check(self._lib.rau_set_batch_async_typed(self._h, slot, fp, feat16.FEAT_TYPES[ft], tp, lp, yp,
+                                                    int(bool(has_labels))))
 
     def use_batch(self, slot):
         L.check(self._lib.rau_use_batch(self._h, slot))

@@ -42,6 +42,7 @@ _STORAGE_DTYPES = {
     "torch.LongStorage": np.int64, "torch.IntStorage": np.int32,
     "torch.ShortStorage": np.int16, "torch.CharStorage": np.int8,
     "torch.ByteStorage": np.uint8,
+    "torch.HalfStorage": np.float16,          # IEEE binary16 (16-bit feature files)
     "torch.CudaStorage": np.float32,          # cutorch writes CudaStorage as floats
 }
 _TENSOR_TO_STORAGE = {k.replace("Storage", "Tensor"): k for k in _STORAGE_DTYPES}
@@ -211,6 +212,7 @@ class _Writer:
         elif isinstance(o, np.ndarray):
             self.obj(Tensor(o, {np.dtype(np.float64): "torch.DoubleTensor",
                                 np.dtype(np.float32): "torch.FloatTensor",
+                                np.dtype(np.float16): "torch.HalfTensor",
                                 np.dtype(np.int64): "torch.LongTensor",
                                 np.dtype(np.int32): "torch.IntTensor",
                                 np.dtype(np.uint8): "torch.ByteTensor"}[o.dtype]))
@@ -288,13 +290,15 @@ def load_snapshot(path):
     return snap.get("it"), snap.get("epoch"), snap.get("opt", {}), out
 
 
-def load_feature(path, D, W, H):
+def load_feature(path, D, W, H, keep_half=False):
     """One image's feature map as the loader hands it on (vqa_prepro_loader.lua:549-552):
-    FloatTensor [D, W, H] -> float32 [D, W*H] (a row of rau_set_batch's feats)."""
+    FloatTensor [D, W, H] -> float32 [D, W*H] (a row of rau_set_batch's feats).  keep_half: a
+    HalfTensor file stays float16 (no widening on the host; the device widens it exactly)."""
     t = load(path)
     if not isinstance(t, Tensor):
         raise T7Error("feature file does not hold a tensor")
-    a = np.ascontiguousarray(t.array, np.float32)
+    half = keep_half and t.array.dtype == np.float16
+    a = np.ascontiguousarray(t.array, np.float16 if half else np.float32)
     if a.shape != (D, W, H):
         raise T7Error(f"feature shape {a.shape} != ({D}, {W}, {H})")   # the loader's asserts
     return a.reshape(D, W * H)
