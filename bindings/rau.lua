@@ -104,6 +104,9 @@ int rau_get_dopred(rau_ctx* ctx, float* dopred);
 int rau_get_attention(rau_ctx* ctx, float* att);
 int rau_get_question_state(rau_ctx* ctx, float* q);
 int rau_get_att_state(rau_ctx* ctx, float* c, float* h);
+int rau_step_stats(rau_ctx* ctx, float* loss, float* loss_do_pred, int32_t* counts);
+int rau_predict(rau_ctx* ctx, const int32_t* mc_ans, int32_t n_mc, int32_t* oe, int32_t* mc);
+int rau_get_merged(rau_ctx* ctx, float* pred, float* att);
 int rau_noise_clip_adam(rau_ctx* ctx, int64_t step_t, float lr, float mult_lr,
                         float beta1, float beta2, float eps, float eta, float gamma,
                         float clip, uint64_t noise_seed, float* out_norms);
@@ -239,6 +242,42 @@ function RAU:answers(out) check(C.rau_get_argmax(self.h, out:data())); return ou
 function RAU:logits(out) check(C.rau_get_logits(self.h, out:data())); return out end
 function RAU:attention(out) check(C.rau_get_attention(self.h, out:data())); return out end
 function RAU:sync() check(C.rau_sync(self.h)) end
+
+-- feval's bookkeeping of the last forward (SS:476-556), on the device: tab_loss (nHop+2: per-hop CE,
+-- uni CE, select CE), tab_loss_do_pred (nHop: BCE of do_pred vs argmax_h == y) and the counts the
+-- accuracy tables add up (SS:491, 526, 536, 552-553), all 1-based Lua tables.  Valid from the
+-- forward through its backward.
+function RAU:stepStats()
+  local H = self.cfg.H
+  local l, d, c = ffi.new('float[?]', H + 2), ffi.new('float[?]', H), ffi.new('int32_t[?]', 4 * H + 3)
+  check(C.rau_step_stats(self.h, l, d, c))
+  local tab_loss, tab_loss_do_pred = {}, {}
+  local counts = { correct = {}, do_pred_correct = {}, fired = {}, selected = {}, did_correct = c[2 * H + 2] }
+  for i = 1, H + 2 do tab_loss[i] = l[i - 1]; counts.correct[i] = c[i - 1] end
+  for h = 1, H do
+    tab_loss_do_pred[h] = d[h - 1]
+    counts.do_pred_correct[h] = c[H + 2 + h - 1]
+    counts.fired[h] = c[2 * H + 3 + h - 1]
+    counts.selected[h] = c[3 * H + 3 + h - 1]
+  end
+  return tab_loss, tab_loss_do_pred, counts
+end
+
+-- predict_result + the eval loop's answer selection (SS:633-705, 877-900) on the last forward
+-- (evaluate mode): returns oe, mc as IntTensors [nHop+2, B] of 1-based answer ids (hops, uni,
+-- select); ans_mc: IntTensor [B, nMultChoice] (0 = empty slot) or nil (mc = nil)
+function RAU:predict(ans_mc)
+  local H, B = self.cfg.H, self.cfg.B
+  local oe = torch.IntTensor(H + 2, B)
+  if not ans_mc then
+    check(C.rau_predict(self.h, nil, 0, oe:data(), nil))
+    return oe, nil
+  end
+  ans_mc = ans_mc:int():contiguous()
+  local mc = torch.IntTensor(H + 2, B)
+  check(C.rau_predict(self.h, ans_mc:data(), ans_mc:size(2), oe:data(), mc:data()))
+  return oe, mc
+end
 
 -- data parallel (one process per GPU): rank 0 calls RAU.commId() and ships the 128-byte string
 -- to the other ranks (file, socket, ...); every rank then calls rau:commInit(n, rank, id) once

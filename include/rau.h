@@ -339,6 +339,34 @@ int rau_get_attention(rau_ctx* ctx, float* att /* [H,B,S] */);
 int rau_get_question_state(rau_ctx* ctx, float* q /* [B,Q] */);
 int rau_get_att_state(rau_ctx* ctx, float* c /* [H,B,R] */, float* h /* [H,B,R] */);
 
+/* ---- merged hops: feval's statistics and predict_result on the device ----------------------------
+ * Computed from the resident outputs of the last rau_forward / rau_graph_step (hop_merge.hip): valid
+ * from the end of that forward, through its rau_backward, until the next forward.  RAU_ERR_STATE,
+ * with nothing launched, when no step-level forward has run, when a module-level entry point has run
+ * since (it writes the same logits / do_pred / answer / loss slots), or when the batch slot whose
+ * labels that forward read has been uploaded into again since (an upload into the OTHER slot of the
+ * asynchronous path keeps them valid).
+ *
+ * feval's bookkeeping (SS:476-556), feval rule (last hop not forced).
+ * loss [H+2]: per-hop CE (bitwise = rau_get_losses), uni CE, select CE;
+ * loss_do_pred [H]: BCE of do_pred vs (argmax_h == y);
+ * counts [RAU_STATS_NCOUNTS(H)]: correct[H+2] | do_pred_correct[H] (masked by did_correct) |
+ *   did_correct | fired[H] (do_pred > 0.5) | selected[H] (samples whose select row is hop h).
+ * Any output may be NULL.  RAU_ERR_STATE also when that forward's batch had no labels.  Synchronising. */
+#define RAU_STATS_NCOUNTS(H) (4 * (H) + 3)
+int rau_step_stats(rau_ctx* ctx, float* loss, float* loss_do_pred, int32_t* counts);
+
+/* predict_result + the eval loop's answer selection (SS:633-705, 877-900), last hop forced.
+ * mc_ans: host [B, n_mc] candidate ids 1..K, 0 = empty slot (NULL: no MC; an id outside 0..K is
+ * RAU_ERR_INVALID).  The MC answer is the first maximum of the RAW logits times the 0/1 candidate
+ * mask, as in the reference: masked-out answers are +-0 and can beat negative candidates.
+ * oe, mc: [H+2, B] 1-based answer ids (hops, uni, select); either may be NULL, and mc is written
+ * only with an MC list.  Synchronising. */
+int rau_predict(rau_ctx* ctx, const int32_t* mc_ans, int32_t n_mc, int32_t* oe, int32_t* mc);
+/* merged rows of the last rau_predict: pred [2,B,K] (uni, select), att [2,B,S] (uni, select;
+ * select WITHOUT the reference's never-zeroed carry, which the host adds) -- either may be NULL */
+int rau_get_merged(rau_ctx* ctx, float* pred, float* att);
+
 /* ---- update: SS:597-630 + utils/optim_updates.lua:59-87 (row "next-1") -------
  * Gradient noise N(0, eta/((step_t+1)*gamma)), per-group L2 clip, Adam with
  * epsilon outside the sqrt; lr applies to EMBED and RNN, mult_lr to MULT

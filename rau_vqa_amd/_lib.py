@@ -129,6 +129,10 @@ _SIGS = {
     "rau_get_attention": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rau_get_question_state": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rau_get_att_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    # merged hops: feval's statistics and predict_result on the device
+    "rau_step_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rau_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rau_get_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_noise_clip_adam": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_float] * 8 +
                             [C.c_uint64, C.c_void_p]),
     "rau_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

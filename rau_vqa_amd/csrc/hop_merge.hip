@@ -1,0 +1,240 @@
+// hop_merge.hip -- the bookkeeping feval and predict_result do on top of the hop outputs, on the
+// resident outputs of the last step-level forward (logits [H,B,K], do_pred [H,B], argmax [H,B],
+// lossrow [H,B], attention [H,B,Sp]):
+//   step_stats   -- feval's joint-loss statistics (SS:476-556): CE of the uni and select merges,
+//                   the BCE of every hop's do_pred against (argmax_h == y), the accuracy counters;
+//   predict_rows -- predict_result's merges (SS:633-705) and the eval loop's open-ended and
+//                   multiple-choice answers (SS:877-900).
+// One workgroup of 256 threads per sample; merged rows are recomputed from the hop logits in
+// every pass (no LDS staging, so no limit on K).  The batch reduction is a second, single-
+// workgroup launch in a fixed order: no float atomics, repeated queries give the same bits.
+#include <hip/hip_runtime.h>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace rau {
+namespace {
+
+constexpr int kMT = 256;   // threads per sample: 4 waves
+
+// torch.max's first-max over the workgroup (k_ce_fwd's rule): the largest value, lowest index on ties
+__device__ __forceinline__ void block_first_max(float& mx, int& ai, float* s_val, int* s_idx) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(mx, o, 64);
+    const int oi = __shfl_xor(ai, o, 64);
+    if (ov > mx || (ov == mx && oi < ai)) { mx = ov; ai = oi; }
+  }
+  if (l == 0) { s_val[w] = mx; s_idx[w] = ai; }
+  __syncthreads();
+  mx = s_val[0]; ai = s_idx[0];
+#pragma unroll
+  for (int i = 1; i < 4; ++i)
+    if (s_val[i] > mx || (s_val[i] == mx && s_idx[i] < ai)) { mx = s_val[i]; ai = s_idx[i]; }
+  __syncthreads();   // the slots are reused by the next reduction
+}
+
+// workgroup sum in k_ce_fwd's order: wave_sum, then (w0 + w1) + (w2 + w3)
+__device__ __forceinline__ float block_sum(float v, float* s_sum) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  v = wave_sum(v);
+  if (l == 0) s_sum[w] = v;
+  __syncthreads();
+  const float r = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+  __syncthreads();
+  return r;
+}
+
+// Entry k of row r of one sample (lg = its logits row of hop 0, hop stride hs):
+//   r < H    hop r's logits;
+//   r == H   uni, SS:482 + 522: uni_pred:zero(), :add(l_h) for h = 1..H, :div(nHop) -- sequential
+//            adds from +0, then a true division;
+//   r == H+1 select, SS:505-507: select_pred:zero():add(l_h * cur_h); at most one cur_h is 1, the
+//            others add +-0, so the row is 0 + l_hsel (all +0 when no hop fired, hsel < 0).
+__device__ __forceinline__ float row_val(const float* __restrict__ lg, size_t hs, int H, int r, int hsel,
+                                         int k) {
+  if (r < H) return lg[(size_t)r * hs + k];
+  if (r == H) {
+    float s = 0.f;
+    for (int h = 0; h < H; ++h) s += lg[(size_t)h * hs + k];
+    return __fdiv_rn(s, (float)H);
+  }
+  return hsel >= 0 ? 0.f + lg[(size_t)hsel * hs + k] : 0.f;
+}
+
+// First hop whose do_pred fires (do_pred > 0.5, SS:501): the clamp(do - did) / clamp(did + do)
+// recurrence of SS:505, 515 selects exactly that one.  force_last: predict_result's rule (SS:685).
+__device__ __forceinline__ int select_hop(const float* __restrict__ dopred, int H, int B, int b,
+                                          bool force_last) {
+  for (int h = 0; h < H; ++h)
+    if (dopred[(size_t)h * B + b] > 0.5f || (force_last && h == H - 1)) return h;
+  return -1;
+}
+
+// CrossEntropyCriterion of row r against label y (0-based) with k_ce_fwd's formulation: max, sum of
+// exp(l - max) in the same thread-strided order, lse - l_y.  Also the row's first-max index.
+__device__ void row_ce(const float* __restrict__ lg, size_t hs, int H, int K, int r, int hsel, int y,
+                       float* s_val, int* s_idx, float* s_sum, float& ce, int& ans) {
+  const int tid = threadIdx.x;
+  float mx = -INFINITY;
+  int ai = 0x7fffffff;
+  for (int k = tid; k < K; k += kMT) {
+    const float v = row_val(lg, hs, H, r, hsel, k);
+    if (v > mx) { mx = v; ai = k; }
+  }
+  block_first_max(mx, ai, s_val, s_idx);
+  float den = 0.f;
+  for (int k = tid; k < K; k += kMT) den += expf(row_val(lg, hs, H, r, hsel, k) - mx);
+  den = block_sum(den, s_sum);
+  const float lse = mx + logf(den);
+  ce = lse - row_val(lg, hs, H, r, hsel, y);
+  ans = ai;
+}
+
+// One workgroup per sample: rowf[b] = {uni CE, select CE, BCE[H]},
+// rowi[b] = correct[H+2] | do_pred_correct[H] | did_correct | fired[H] | selected[H].
+__global__ __launch_bounds__(kMT) void k_step_stats_rows(int H, int B, int K,
+    const float* __restrict__ logits, const float* __restrict__ dopred,
+    const int32_t* __restrict__ argmax, const int32_t* __restrict__ labels,
+    float* __restrict__ rowf, int32_t* __restrict__ rowi) {
+  __shared__ float s_val[4];
+  __shared__ int s_idx[4];
+  __shared__ float s_sum[4];
+  const int b = blockIdx.x;
+  const size_t hs = (size_t)B * K;
+  const float* lg = logits + (size_t)b * K;
+  const int y = min(max(labels[b], 1), K) - 1;   // checked at upload; clamped like k_ce_fwd
+  const int hsel = select_hop(dopred, H, B, b, false);   // feval: the last hop is not forced
+  float ce_u, ce_s;
+  int a_u, a_s;
+  row_ce(lg, hs, H, K, H, hsel, y, s_val, s_idx, s_sum, ce_u, a_u);       // SS:522-530
+  row_ce(lg, hs, H, K, H + 1, hsel, y, s_val, s_idx, s_sum, ce_s, a_s);   // SS:532-540
+  if (threadIdx.x != 0) return;
+  float* f = rowf + (size_t)b * (H + 2);
+  int32_t* c = rowi + (size_t)b * (4 * H + 3);
+  f[0] = ce_u;
+  f[1] = ce_s;
+  int did = 0;   // did_correct, SS:513
+  for (int h = 0; h < H; ++h) {
+    const int gt = argmax[(size_t)h * B + b] == y + 1;   // do_pred_gt = (argmax_h == y), SS:490, 497
+    c[h] = gt;
+    did |= gt;
+  }
+  c[H] = a_u == y;
+  c[H + 1] = a_s == y;
+  c[2 * H + 2] = did;
+  for (int h = 0; h < H; ++h) {
+    const float x = dopred[(size_t)h * B + b];
+    const int fire = x > 0.5f;
+    const float t = c[h] ? 1.f : 0.f;
+    // nn.BCECriterion, SS:555: -(t log(x + eps) + (1 - t) log(1 - x + eps)), eps = 1e-12
+    f[2 + h] = -(t * logf(x + 1e-12f) + (1.f - t) * logf(1.f - x + 1e-12f));
+    c[H + 2 + h] = (fire == c[h]) && did;   // SS:552, masked by did_correct
+    c[2 * H + 3 + h] = fire;
+    c[3 * H + 3 + h] = h == hsel;
+  }
+}
+
+// One workgroup: out = loss[H+2] | loss_do_pred[H] (floats) | counts[4H+3] (int32).  Float columns
+// are reduced like k_loss_reduce (lane-strided over the batch, wave_sum, / B), so the per-hop CE is
+// bitwise the step's own rau_get_losses.
+__global__ __launch_bounds__(kMT) void k_step_stats_reduce(int H, int B, const float* __restrict__ lossrow,
+    const float* __restrict__ rowf, const int32_t* __restrict__ rowi, float* __restrict__ out) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int NF = H + 2, NL = 2 * H + 2, NC = 4 * H + 3;
+  for (int j = w; j < NL; j += 4) {
+    float acc = 0.f;
+    for (int b = l; b < B; b += 64)
+      acc += j < H ? lossrow[(size_t)j * B + b] : rowf[(size_t)b * NF + (j - H)];
+    acc = wave_sum(acc);
+    if (l == 0) out[j] = acc / (float)B;
+  }
+  int32_t* cnt = reinterpret_cast<int32_t*>(out + NL);
+  for (int j = threadIdx.x; j < NC; j += kMT) {
+    int s = 0;
+    for (int b = 0; b < B; ++b) s += rowi[(size_t)b * NC + j];
+    cnt[j] = s;
+  }
+}
+
+// One workgroup per sample: for each row r of {hops, uni, select} (predict rule: last hop forced)
+// the first-max answer of the row (oe) and of row * mc_mask (mc: the reference multiplies the RAW
+// logits by a 0/1 mask, SS:893-894, so masked-out entries are +-0 and +0 / -0 tie at the lower
+// index); the merged rows go to pred [2][B][K] and att_out [2][B][Sp] (select without any carry).
+__global__ __launch_bounds__(kMT) void k_predict_rows(int H, int B, int K, int Sp,
+    const float* __restrict__ logits, const float* __restrict__ dopred, const float* __restrict__ att,
+    const int32_t* __restrict__ mc, int n_mc, int32_t* __restrict__ oe, int32_t* __restrict__ mco,
+    float* __restrict__ pred, float* __restrict__ att_out) {
+  extern __shared__ uint32_t s_mask[];   // candidate bit set of the sample, (K + 31) / 32 words (mc only)
+  __shared__ float s_val[4];
+  __shared__ int s_idx[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const size_t hs = (size_t)B * K;
+  const float* lg = logits + (size_t)b * K;
+  const int hsel = select_hop(dopred, H, B, b, true);   // >= 0: the last hop always fires
+  if (mc) {   // test_mc_mask, SS:885-892: 0 = empty slot
+    const int nw = (K + 31) / 32;
+    for (int i = tid; i < nw; i += kMT) s_mask[i] = 0u;
+    __syncthreads();
+    for (int j = tid; j < n_mc; j += kMT) {
+      const int a = mc[(size_t)b * n_mc + j];
+      if (a >= 1 && a <= K) atomicOr(&s_mask[(a - 1) >> 5], 1u << ((a - 1) & 31));
+    }
+    __syncthreads();
+  }
+  for (int r = 0; r < H + 2; ++r) {
+    float mx = -INFINITY, mm = -INFINITY;
+    int ai = 0x7fffffff, mi = 0x7fffffff;
+    float* prow = (r >= H && pred) ? pred + ((size_t)(r - H) * B + b) * K : nullptr;
+    for (int k = tid; k < K; k += kMT) {
+      const float v = row_val(lg, hs, H, r, hsel, k);
+      if (prow) prow[k] = v;
+      if (v > mx) { mx = v; ai = k; }
+      if (mc) {
+        const float vm = v * (((s_mask[k >> 5] >> (k & 31)) & 1u) ? 1.f : 0.f);
+        if (vm > mm) { mm = vm; mi = k; }
+      }
+    }
+    block_first_max(mx, ai, s_val, s_idx);
+    if (mc) block_first_max(mm, mi, s_val, s_idx);
+    if (tid == 0) {
+      oe[(size_t)r * B + b] = ai + 1;
+      if (mc) mco[(size_t)r * B + b] = mi + 1;
+    }
+  }
+  if (!att_out) return;
+  // SS:681, 688, 700: uni = (0 + a_1 + .. + a_H) / H, select = 0 + a_hsel
+  const float* ab = att + (size_t)b * Sp;
+  const size_t as = (size_t)B * Sp;
+  for (int s = tid; s < Sp; s += kMT) {
+    float u = 0.f;
+    for (int h = 0; h < H; ++h) u += ab[(size_t)h * as + s];
+    att_out[(size_t)b * Sp + s] = __fdiv_rn(u, (float)H);
+    att_out[as + (size_t)b * Sp + s] = 0.f + ab[(size_t)hsel * as + s];
+  }
+}
+
+}  // namespace
+
+hipError_t step_stats(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
+                      const int32_t* argmax, const float* lossrow, const int32_t* labels, float* rowf,
+                      int32_t* rowi, float* out) {
+  hipLaunchKernelGGL(k_step_stats_rows, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, argmax, labels,
+                     rowf, rowi);
+  hipLaunchKernelGGL(k_step_stats_reduce, dim3(1), dim3(kMT), 0, st, H, B, lossrow, rowf, rowi, out);
+  return hipGetLastError();
+}
+
+size_t predict_rows_lds(int K) { return (size_t)((K + 31) / 32) * sizeof(uint32_t); }
+
+hipError_t predict_rows(hipStream_t st, int H, int B, int K, int Sp, const float* logits, const float* dopred,
+                        const float* att, const int32_t* mc, int n_mc, int32_t* oe, int32_t* mco, float* pred,
+                        float* att_out) {
+  hipLaunchKernelGGL(k_predict_rows, dim3(B), dim3(kMT), mc ? predict_rows_lds(K) : 0, st, H, B, K, Sp, logits,
+                     dopred, att, mc, n_mc, oe, mco, pred, att_out);
+  return hipGetLastError();
+}
+
+}  // namespace rau

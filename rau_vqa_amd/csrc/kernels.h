@@ -378,5 +378,18 @@ hipError_t finish_norm(hipStream_t st, int nparts, const float* partial, float* 
 hipError_t clip_adam(hipStream_t st, size_t n, float* x, float* g, float* m, float* v,
                      const float* norm, float clip, float stepsize, float beta1, float beta2,
                      float eps);
+// feval's statistics of the resident hop outputs (hop_merge.hip, SS:476-556): per-sample rows
+// rowf [B][H+2], rowi [B][4H+3], then one fixed-order batch reduction into
+// out = loss[H+2] | loss_do_pred[H] | int32 counts[4H+3]
+hipError_t step_stats(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
+                      const int32_t* argmax, const float* lossrow, const int32_t* labels, float* rowf,
+                      int32_t* rowi, float* out);
+// predict_result's merges + answers (SS:633-705, 877-900): oe / mco [H+2][B] 1-based, pred [2][B][K] and
+// att_out [2][B][Sp] (uni, select; either may be null); mc [B][n_mc] device ids 0..K (null: no MC)
+hipError_t predict_rows(hipStream_t st, int H, int B, int K, int Sp, const float* logits, const float* dopred,
+                        const float* att, const int32_t* mc, int n_mc, int32_t* oe, int32_t* mco, float* pred,
+                        float* att_out);
+// dynamic LDS bytes predict_rows takes with an MC list
+size_t predict_rows_lds(int K);
 
 }  // namespace rau

@@ -130,6 +130,7 @@ struct rau_ctx {
   int32_t *utok = nullptr, *ustart = nullptr, *upos = nullptr;
   // asynchronous, double-buffered upload (allocated at the first rau_batch_slot / rau_set_batch_async)
   BatchSlot slot[2];
+  uint64_t slot_serial[2] = {0, 0};   // uploads into each slot's device buffers so far
   int cur_slot = 0;
   bool async_ready = false;
   hipStream_t stc = nullptr;         // copy stream
@@ -202,6 +203,16 @@ struct rau_ctx {
   bool capturing = false;
   bool graph_last = false;       // the last backward ran inside a graph (its events are graph-internal)
   std::vector<std::pair<uint64_t, hipGraphExec_t>> graphs;
+  // merged hops (hop_merge.hip: rau_step_stats / rau_predict); buffers allocated on first use
+  bool mg_valid = false;          // logits / dopred / argmax_d / lossrow / a hold the last step-level forward's
+  bool mg_labels = false;         // ... of a batch with labels, read from mg_labels_d
+  const int32_t* mg_labels_d = nullptr;
+  int mg_slot = 0;                // the batch slot that forward read, and its upload serial then
+  uint64_t mg_serial = 0;
+  bool mg_ready = false, mg_merged = false;   // buffers allocated / a rau_predict has filled mg_pred, mg_att
+  float *mg_rowf = nullptr, *mg_out = nullptr, *mg_pred = nullptr, *mg_att = nullptr;
+  int32_t *mg_rowi = nullptr, *mg_ans = nullptr, *mg_mc = nullptr;
+  size_t mg_mc_cap = 0;           // int32 entries mg_mc holds
   // update
   float *npart = nullptr, *norms_d = nullptr;
   bool fwd_done = false, bwd_done = false;
@@ -236,6 +247,15 @@ inline void set_skinny_policy(const rau_ctx* ctx) {
   static const int env = [] { const char* e = std::getenv("RAU_SKINNY_DEEP"); return e ? (std::atoi(e) != 0 ? 1 : 0) : -1; }();
   skinny_dma_set_deep(env >= 0 ? env : (chain_bound(ctx) ? 1 : 0));
   lin_set_bf16(ctx->bf16 == 1);
+}
+// The hop outputs now hold the results of the forward just enqueued: rau_step_stats / rau_predict may
+// read them until the next forward, module-level call or upload into the batch slot it read.
+inline void merge_record(rau_ctx* ctx) {
+  ctx->mg_valid = true;
+  ctx->mg_labels = ctx->have_labels;
+  ctx->mg_labels_d = ctx->labels_d;
+  ctx->mg_slot = ctx->cur_slot;
+  ctx->mg_serial = ctx->slot_serial[ctx->cur_slot];
 }
 inline float mask_p(const rau_ctx* ctx, int site) {
   return ctx->mexplicit[site] ? ctx->mp_exact[site] : ctx->mp[site];

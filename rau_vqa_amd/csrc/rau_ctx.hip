@@ -854,6 +854,7 @@ int rau_set_batch_typed(rau_ctx* ctx, const void* feats, int feat_type, const in
   d.utok = ctx->utok; d.ustart = ctx->ustart; d.upos = ctx->upos;
   if (ctx->async_ready && ctx->slot[ctx->cur_slot].upload_pending)   // an async upload into the same buffers
     HIPC(hipStreamWaitEvent(ctx->st, ctx->slot[ctx->cur_slot].uploaded, 0));
+  ++ctx->slot_serial[ctx->cur_slot];
   if (int rc = enqueue_batch(ctx, ctx->st, d, feats, feat_type, ctx->feat_type, tokens, lens, labels,
                              utok.data(), ustart.data(), upos.data()))
     return rc;
@@ -937,6 +938,7 @@ int rau_set_batch_async_typed(rau_ctx* ctx, int slot, const void* feats, int fea
     s.consumed_valid = true;
   }
   if (s.consumed_valid) HIPC(hipStreamWaitEvent(ctx->stc, s.consumed, 0));
+  ++ctx->slot_serial[slot];
   if (int rc = enqueue_batch(ctx, ctx->stc, s, s.feats_h, feat_type, s.feat_type, s.tokens_h, s.lens_p,
                              with_labels ? s.labels_h : nullptr, s.utok_h, s.ustart_h, s.upos_h))
     return rc;
@@ -1312,6 +1314,7 @@ static bool head_dgrad_fwd(const rau_ctx* ctx) {
 int rau_forward(rau_ctx* ctx) {
   NEED(ctx, "null ctx");
   if (!ctx->have_batch) return fail(RAU_ERR_STATE, "rau_forward: no batch (call rau_set_batch)");
+  ctx->mg_valid = false;   // the hop outputs are being overwritten
   set_skinny_policy(ctx);
   const rau_config& c = ctx->cfg;
   const int B = c.B, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R,
@@ -1616,6 +1619,7 @@ int rau_forward(rau_ctx* ctx) {
   HIPC(hipStreamWaitEvent(st, ctx->evHd, 0));   // callers order against st only
   if (ctx->have_labels)
     RUN("loss_reduce", 0, 0, loss_reduce(st, H, B, ctx->lossrow, ctx->losses_d));
+  if (!ctx->capturing) merge_record(ctx);   // (rau_graph_step records behind its launch)
   ctx->fwd_done = true;
   ctx->dpre_fwd = head_dgrad_fwd(ctx);
   return RAU_OK;
@@ -2000,6 +2004,7 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
   key |= (uint64_t)ctx->cur_slot << 30;   // the captured kernels hold the batch slot's device pointers
   key |= (uint64_t)ctx->feat_type << 32;  // ... and read the batch in its element type
   if (int rc = upload_hop_weights(ctx, hop_w)) return rc;
+  ctx->mg_valid = false;
   hipGraphExec_t exec = nullptr;
   for (auto& g : ctx->graphs)
     if (g.first == key) exec = g.second;
@@ -2026,6 +2031,7 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
   }
   HIPC(hipGraphLaunch(exec, ctx->st));
   HIPC(hipEventRecord(ctx->evEnd, ctx->st));   // a real (non-captured) end-of-step event
+  merge_record(ctx);
   ctx->fwd_done = false;
   ctx->bwd_done = true;
   ctx->graph_last = true;
@@ -2061,6 +2067,7 @@ static int persist_check(rau_ctx* ctx) {
   ctx->enc_ws = ctx->enc_ws_train = false;
   ctx->persist_used = false;
   ctx->fwd_done = false;
+  ctx->mg_valid = false;
   return fail(RAU_ERR_DEVICE, "persistent encoder: a bounded wait on another workgroup's progress counter gave up; "
                               "the results of that step are invalid -- repeat it: this context now uses the "
                               "launch-per-step encoder");
@@ -2112,6 +2119,101 @@ int rau_get_att_state(rau_ctx* ctx, float* c, float* h) {
     if (int rc = d2h(ctx, c, ctx->cc + BR_, n * 4)) return rc;
   if (h)
     if (int rc = d2h(ctx, h, ctx->hh + BR_, n * 4)) return rc;
+  return RAU_OK;
+}
+
+// ---------------------------------------------- merged hops (hop_merge.hip): feval stats, predict_result
+static int merge_alloc(rau_ctx* ctx) {
+  if (ctx->mg_ready) return RAU_OK;
+  const rau_config& c = ctx->cfg;
+  const size_t B = c.B, H = c.H;
+#define CK(x) do { if (int rc_ = (x)) return rc_; } while (0)
+  CK(dalloc(ctx, &ctx->mg_rowf, B * (H + 2)));
+  CK(dalloc(ctx, &ctx->mg_rowi, B * RAU_STATS_NCOUNTS(H)));
+  CK(dalloc(ctx, &ctx->mg_out, (2 * H + 2) + RAU_STATS_NCOUNTS(H)));
+  CK(dalloc(ctx, &ctx->mg_ans, 2 * (H + 2) * B));
+  CK(dalloc(ctx, &ctx->mg_pred, 2 * B * c.K));
+  CK(dalloc(ctx, &ctx->mg_att, 2 * B * ctx->Sp));
+#undef CK
+  ctx->mg_ready = true;
+  return RAU_OK;
+}
+// may the hop outputs of the last forward be read?  (checked before anything is launched)
+static int merge_state(rau_ctx* ctx, const char* fn, bool need_labels) {
+  if (!ctx->mg_valid)
+    return fail(RAU_ERR_STATE, "%s: no step-level forward result (none has run yet, it failed, or a module-level "
+                "entry point has run since)", fn);
+  if (ctx->slot_serial[ctx->mg_slot] != ctx->mg_serial)
+    return fail(RAU_ERR_STATE, "%s: batch slot %d, which the last forward read, has been uploaded into since", fn,
+                ctx->mg_slot);
+  if (need_labels && !ctx->mg_labels)
+    return fail(RAU_ERR_STATE, "%s: the batch of the last forward had no labels", fn);
+  return RAU_OK;
+}
+
+int rau_step_stats(rau_ctx* ctx, float* loss, float* loss_do_pred, int32_t* counts) {
+  NEED(ctx, "null ctx");
+  if (int rc = merge_state(ctx, "rau_step_stats", true)) return rc;
+  if (int rc = merge_alloc(ctx)) return rc;
+  const rau_config& c = ctx->cfg;
+  const int H = c.H, B = c.B, K = c.K, NL = 2 * H + 2, NC = RAU_STATS_NCOUNTS(H);
+  RUN("step_stats", 0, (double)B * (2 * H + 2) * K * 4,
+      step_stats(ctx->st, H, B, K, ctx->logits, ctx->dopred, ctx->argmax_d, ctx->lossrow, ctx->mg_labels_d,
+                 ctx->mg_rowf, ctx->mg_rowi, ctx->mg_out));
+  std::vector<float> out((size_t)NL + NC);
+  if (int rc = d2h(ctx, out.data(), ctx->mg_out, out.size() * 4)) return rc;
+  if (loss) std::memcpy(loss, out.data(), (size_t)(H + 2) * 4);
+  if (loss_do_pred) std::memcpy(loss_do_pred, out.data() + H + 2, (size_t)H * 4);
+  if (counts) std::memcpy(counts, out.data() + NL, (size_t)NC * 4);
+  return RAU_OK;
+}
+
+int rau_predict(rau_ctx* ctx, const int32_t* mc_ans, int32_t n_mc, int32_t* oe, int32_t* mc) {
+  NEED(ctx, "null ctx");
+  const rau_config& c = ctx->cfg;
+  const int H = c.H, B = c.B, K = c.K;
+  const size_t nmc = mc_ans ? (size_t)B * n_mc : 0;
+  if (mc_ans) {
+    NEED(n_mc > 0, "rau_predict: n_mc=%d must be positive with an MC list", n_mc);
+    NEED(predict_rows_lds(K) <= 65536, "rau_predict: K=%d too large for the MC candidate mask", K);
+    for (size_t i = 0; i < nmc; ++i)
+      NEED(mc_ans[i] >= 0 && mc_ans[i] <= K, "rau_predict: mc_ans[%zu]=%d out of [0,%d] (0 = empty slot)", i,
+           mc_ans[i], K);
+  }
+  if (int rc = merge_state(ctx, "rau_predict", false)) return rc;
+  if (int rc = merge_alloc(ctx)) return rc;
+  if (nmc > ctx->mg_mc_cap) {   // grows only; the old buffer stays with the ctx until rau_destroy
+    if (int rc = dalloc(ctx, &ctx->mg_mc, nmc)) return rc;
+    ctx->mg_mc_cap = nmc;
+  }
+  if (nmc) HIPC(hipMemcpyAsync(ctx->mg_mc, mc_ans, nmc * 4, hipMemcpyHostToDevice, ctx->st));
+  int32_t* oe_d = ctx->mg_ans;
+  int32_t* mc_d = ctx->mg_ans + (size_t)(H + 2) * B;
+  RUN("predict_rows", 0, (double)B * (2 * H + 1) * K * 4,
+      predict_rows(ctx->st, H, B, K, ctx->Sp, ctx->logits, ctx->dopred, ctx->a, nmc ? ctx->mg_mc : nullptr,
+                   n_mc, oe_d, mc_d, ctx->mg_pred, ctx->mg_att));
+  ctx->mg_merged = false;
+  if (oe)
+    if (int rc = d2h(ctx, oe, oe_d, (size_t)(H + 2) * B * 4)) return rc;
+  if (mc && nmc)
+    if (int rc = d2h(ctx, mc, mc_d, (size_t)(H + 2) * B * 4)) return rc;
+  HIPC(hipStreamSynchronize(ctx->st));   // the caller's mc_ans is free on return
+  if (int rc = persist_check(ctx)) return rc;
+  ctx->mg_merged = true;
+  return RAU_OK;
+}
+
+int rau_get_merged(rau_ctx* ctx, float* pred, float* att) {
+  NEED(ctx, "null ctx");
+  if (!ctx->mg_merged) return fail(RAU_ERR_STATE, "rau_get_merged: no rau_predict has run");
+  const rau_config& c = ctx->cfg;
+  if (pred)
+    if (int rc = d2h(ctx, pred, ctx->mg_pred, (size_t)2 * c.B * c.K * 4)) return rc;
+  if (att) {
+    HIPC(hipMemcpy2DAsync(att, (size_t)c.S * 4, ctx->mg_att, (size_t)ctx->Sp * 4, (size_t)c.S * 4,
+                          (size_t)2 * c.B, hipMemcpyDeviceToHost, ctx->st));
+    HIPC(hipStreamSynchronize(ctx->st));
+  }
   return RAU_OK;
 }
 

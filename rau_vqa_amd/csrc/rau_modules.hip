@@ -18,6 +18,7 @@ namespace {
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int mod_alloc(rau_ctx* ctx) {
+  ctx->mg_valid = false;   // every module-level entry point comes here: the step-level hop outputs are stale
   if (ctx->mod_ready) return 0;
   // Callers hand in / get back DENSE [.., S] tensors.  Internally every [.., S] tensor uses the
   // position pitch Sp (S rounded up to a multiple of 4: 7x7 maps 49 -> 52), so when Sp != S the

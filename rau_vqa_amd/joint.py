@@ -1,0 +1,79 @@
+"""Host restatement of feval's joint-loss bookkeeping (SS:476-556), line by line.
+
+The reference's ``feval`` does more per iteration than the per-hop cross-entropy: it merges the hops
+into a "uni" row (mean of the hop logits) and a "select" row (the logits of the first hop whose
+do_pred fires; the last hop is NOT forced here, unlike predict_result), takes the CE and accuracy of
+both, and scores every hop's do_pred with nn.BCECriterion against do_pred_gt = (argmax_h == y).
+``RAU.step_stats`` computes the same numbers on the device (rau_step_stats); this module is the
+plain float32 statement they are checked against.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .predict import first_max
+
+BCE_EPS = np.float32(1e-12)   # nn.BCECriterion's eps
+
+
+def cross_entropy(pred, y):
+    """nn.CrossEntropyCriterion (sizeAverage) of [B, K] float32 rows, y 1-based [B]."""
+    mx = pred.max(axis=1)
+    lse = mx + np.log(np.exp(pred - mx[:, None]).sum(axis=1, dtype=np.float32))
+    row = lse - pred[np.arange(pred.shape[0]), y - 1]
+    return np.float32(row.sum(dtype=np.float32) / np.float32(pred.shape[0]))
+
+
+def bce(x, t):
+    """nn.BCECriterion (sizeAverage): -(t log(x + eps) + (1 - t) log(1 - x + eps)), mean over B."""
+    one = np.float32(1)
+    term = -(t * np.log(x + BCE_EPS) + (one - t) * np.log(one - x + BCE_EPS))
+    return np.float32(term.sum(dtype=np.float32) / np.float32(x.shape[0]))
+
+
+def feval_stats(logits, dopred, labels):
+    """logits [H, B, K], dopred [H, B], labels [B] (1-based) -> dict with the keys of
+    ``RAU.step_stats`` (loss [H+2], loss_do_pred [H], correct [H+2], do_pred_correct [H],
+    did_correct, fired [H], selected [H]) plus ``uni_ans`` / ``select_ans`` [B]."""
+    logits = np.asarray(logits, np.float32)
+    dopred = np.asarray(dopred, np.float32)
+    y = np.asarray(labels, np.int64)
+    H, B, K = logits.shape
+    uni_pred = np.zeros((B, K), np.float32)                  # uni_pred:zero(), SS:474
+    select_pred = np.zeros((B, K), np.float32)               # select_pred:zero(), SS:475
+    did_pred = np.zeros(B, np.float32)                       # did_pred:zero(), SS:476
+    did_correct = np.zeros(B, np.float32)                    # did_correct:zero(), SS:477
+    tab_loss, tab_do_pred, tab_do_pred_gt = [], [], []
+    correct, fired, selected = [], [], []
+    for h in range(H):
+        pred = logits[h]
+        uni_pred += pred                                     # SS:482
+        tab_do_pred.append(dopred[h])                        # SS:484
+        ans = first_max(pred)                                # SS:488
+        is_correct = (ans == y).astype(np.float32)           # SS:490
+        correct.append(int(is_correct.sum()))                # SS:491
+        tab_do_pred_gt.append(is_correct.copy())             # SS:497-498
+        do_pred = (dopred[h] > 0.5).astype(np.float32)       # SS:501
+        pred_cur_hop = np.clip(do_pred - did_pred, 0, 1)     # SS:505
+        select_pred += pred * pred_cur_hop[:, None]          # SS:506-507
+        fired.append(int(do_pred.sum()))
+        selected.append(int(pred_cur_hop.sum()))
+        did_correct = np.clip(did_correct + is_correct, 0, 1)   # SS:513
+        did_pred = np.clip(did_pred + do_pred, 0, 1)         # SS:515
+        tab_loss.append(cross_entropy(pred, y))              # SS:518-519
+    uni_pred = uni_pred / np.float32(H)                      # SS:522
+    uni_ans = first_max(uni_pred)                            # SS:524
+    correct.append(int((uni_ans == y).sum()))                # SS:526
+    tab_loss.append(cross_entropy(uni_pred, y))              # SS:529-530
+    select_ans = first_max(select_pred)                      # SS:534
+    correct.append(int((select_ans == y).sum()))             # SS:536
+    tab_loss.append(cross_entropy(select_pred, y))           # SS:539-540
+    do_pred_correct, tab_loss_do_pred = [], []
+    for h in range(H):
+        do_pred = (tab_do_pred[h] > 0.5).astype(np.float32)  # SS:549
+        do_pred_correct.append(int(((do_pred == tab_do_pred_gt[h]) * did_correct).sum()))   # SS:552
+        tab_loss_do_pred.append(bce(tab_do_pred[h], tab_do_pred_gt[h]))                      # SS:555
+    return {"loss": np.array(tab_loss, np.float32), "loss_do_pred": np.array(tab_loss_do_pred, np.float32),
+            "correct": np.array(correct, np.int32), "do_pred_correct": np.array(do_pred_correct, np.int32),
+            "did_correct": int(did_correct.sum()), "fired": np.array(fired, np.int32),
+            "selected": np.array(selected, np.int32), "uni_ans": uni_ans, "select_ans": select_ans}

@@ -311,6 +311,45 @@ class RAU:
         L.check(self._lib.rau_get_att_state(self._h, c.ctypes.data, h.ctypes.data))
         return c, h
 
+    # ---- merged hops on the device (valid from a forward through its backward, include/rau.h)
+    def step_stats(self):
+        """feval's bookkeeping of the last forward (SS:476-556, last hop not forced): ``loss`` [H+2]
+        (per-hop CE, uni CE, select CE), ``loss_do_pred`` [H] (BCE of do_pred vs argmax_h == y) and
+        the counts: ``correct`` [H+2], ``do_pred_correct`` [H] (masked by did_correct),
+        ``did_correct``, ``fired`` [H] (do_pred > 0.5), ``selected`` [H] (select row = hop h)."""
+        H = self.cfg.H
+        loss = np.empty(H + 2, np.float32)
+        ldp = np.empty(H, np.float32)
+        cnt = np.empty(4 * H + 3, np.int32)
+        L.check(self._lib.rau_step_stats(self._h, loss.ctypes.data, ldp.ctypes.data, cnt.ctypes.data))
+        return {"loss": loss, "loss_do_pred": ldp, "correct": cnt[:H + 2],
+                "do_pred_correct": cnt[H + 2:2 * H + 2], "did_correct": int(cnt[2 * H + 2]),
+                "fired": cnt[2 * H + 3:3 * H + 3], "selected": cnt[3 * H + 3:]}
+
+    def predict(self, mc_ans=None):
+        """predict_result's answers of the last forward (SS:633-705, 877-900, last hop forced):
+        (oe [H+2, B], mc [H+2, B] or None), 1-based, rows = hops, uni, select.  mc_ans: int
+        [B, n] candidate ids, 0 = empty slot."""
+        H, B = self.cfg.H, self.cfg.B
+        oe = np.empty((H + 2, B), np.int32)
+        if mc_ans is None:
+            L.check(self._lib.rau_predict(self._h, None, 0, oe.ctypes.data, None))
+            return oe, None
+        m = np.ascontiguousarray(mc_ans, np.int32)
+        if m.ndim != 2 or m.shape[0] != B:
+            raise ValueError("mc_ans must be [B, n]")
+        mc = np.empty((H + 2, B), np.int32)
+        L.check(self._lib.rau_predict(self._h, m.ctypes.data, m.shape[1], oe.ctypes.data, mc.ctypes.data))
+        return oe, mc
+
+    def merged(self):
+        """Merged rows of the last predict(): pred [2, B, K], att [2, B, S] (uni, select; select
+        without the reference's carried test_select_att)."""
+        pred = np.empty((2, self.cfg.B, self.cfg.K), np.float32)
+        att = np.empty((2, self.cfg.B, self.cfg.S), np.float32)
+        L.check(self._lib.rau_get_merged(self._h, pred.ctypes.data, att.ctypes.data))
+        return pred, att
+
     def outputs(self):
         c, h = self.att_state()
         return {"losses": self.losses(), "argmax": self.argmax(), "logits": self.logits(),

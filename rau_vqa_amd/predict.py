@@ -77,3 +77,25 @@ def predict_result(rau, feats, tokens, lens, mc_ans=None, select_att_state=None)
     tab_pred, tab_att = merge_hops(rau.logits(), rau.dopred(), rau.attention(), select_att_state)
     oe, mc = answers(tab_pred, mc_ans)
     return {"tab_pred": tab_pred, "tab_att": tab_att, "oe": oe, "mc": mc}
+
+
+def predict_result_device(rau, feats, tokens, lens, mc_ans=None, select_att_state=None, tabs=True):
+    """predict_result with the merges, the MC masking and the answers done on the device
+    (rau_predict): same keys, same values bit for bit.  The select attention row comes back without
+    the reference's carried test_select_att; select_att_state is added here, as merge_hops does.
+    tabs=False skips downloading the per-hop logits and maps: tab_pred / tab_att are then None and
+    only the answers (and nothing of [H, B, K]) cross PCIe."""
+    rau.evaluate()
+    rau.set_batch(feats, tokens, lens, None)
+    rau.forward()
+    oe, mc = rau.predict(mc_ans)
+    if not tabs:
+        return {"tab_pred": None, "tab_att": None, "oe": oe, "mc": mc}
+    pred, att = rau.merged()
+    if select_att_state is not None:
+        att[1] = np.array(select_att_state, np.float32) + att[1]   # never zeroed, SS:671-674
+    logits, hop_att = rau.logits(), rau.attention()
+    H = logits.shape[0]
+    tab_pred = [logits[h] for h in range(H)] + [pred[0], pred[1]]
+    tab_att = [hop_att[h] for h in range(H)] + [att[0], att[1]]
+    return {"tab_pred": tab_pred, "tab_att": tab_att, "oe": oe, "mc": mc}
