@@ -49,6 +49,13 @@ int rau_set_batch_async_typed(rau_ctx* ctx, int slot, const void* feats, int fea
                               const int32_t* tokens, const int32_t* lens, const int32_t* labels,
                               int has_labels);
 int rau_batch_feat_type(rau_ctx* ctx, int* feat_type);
+int rau_set_batch_images(rau_ctx* ctx, const void* feats, int feat_type, int n_images,
+                         const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                         const int32_t* labels);
+int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int feat_type, int n_images,
+                               const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                               const int32_t* labels, int has_labels);
+int rau_batch_images(rau_ctx* ctx, int* n_images);
 int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_host,
                    int32_t** lens_host, int32_t** labels_host);
 int rau_set_batch_async(rau_ctx* ctx, int slot, const float* feats, const int32_t* tokens,
@@ -206,6 +213,28 @@ function RAU:setBatchAsync(slot, feats, x, x_len, y, has_labels, feat_type)
                                     (has_labels == false) and 0 or 1))
 end
 function RAU:useBatch(slot) check(C.rau_use_batch(self.h, slot)) end
+
+-- A batch whose questions share feature maps: feats is the image TABLE [N,D,W,H] (Float- or HalfTensor),
+-- image_of an IntTensor [B] of 1-BASED table rows, as Torch indexes (feats:index(1, image_of:long()) is the
+-- plain batch); converted here to the 0-based row offsets of rau_set_batch_images.  Only the N maps are
+-- uploaded and, in evaluate mode, convolved.  slot = nil: the synchronous form.
+function RAU:setBatchImages(feats, image_of, x, x_len, y, slot, has_labels)
+  local ft = torch.type(feats) == 'torch.HalfTensor' and FEAT.f16 or FEAT.f32
+  local idx = image_of:int():add(-1)
+  if slot then
+    check(C.rau_set_batch_async_images(self.h, slot, feats:data(), ft, feats:size(1), idx:data(), x:data(),
+                                       x_len:data(), y and y:data() or nil, (has_labels == false) and 0 or 1))
+  else
+    check(C.rau_set_batch_images(self.h, feats:data(), ft, feats:size(1), idx:data(), x:data(), x_len:data(),
+                                 y and y:data() or nil))
+  end
+end
+-- 0 for a plain resident batch, else the number of maps in its image table
+function RAU:batchImages()
+  local n = ffi.new('int[1]')
+  check(C.rau_batch_images(self.h, n))
+  return n[0]
+end
 
 -- forward half of feval (SS:443-520); returns per-hop losses as a Lua table
 function RAU:forward(seed, step)

@@ -162,7 +162,8 @@ int rau_set_batch(rau_ctx* ctx, const float* feats, const int32_t* tokens,
                   const int32_t* lens, const int32_t* labels);
 /* device pointer of the resident feature buffer (producer may write it directly).  It is returned as it
  * is: after a 16-bit batch (rau_set_batch_typed) its first B*D*Sp*2 bytes hold that batch's 16-bit
- * elements at row pitch Sp (S rounded up to a multiple of 4), not floats. */
+ * elements at row pitch Sp (S rounded up to a multiple of 4), not floats; after a batch with an image
+ * table (rau_set_batch_images) it holds the table's N maps, not one map per sample. */
 int rau_batch_feats(rau_ctx* ctx, float** feats_dev);
 
 /* ---- 16-bit feature maps ---------------------------------------------------------------------------
@@ -189,6 +190,33 @@ int rau_set_batch_async_typed(rau_ctx* ctx, int slot, const void* feats, int fea
                               int has_labels);
 /* element type of the resident batch */
 int rau_batch_feat_type(rau_ctx* ctx, int* feat_type);
+
+/* ---- image tables: questions of one image share its feature map --------------------------------
+ * VQA asks several questions per image, so a batch may carry each distinct map once: feats is then a
+ * TABLE [n_images,D,S] (1 <= n_images <= B) of feat_type elements and image_of [B] (host, int32) gives
+ * the 0-based table row sample b looks at; tokens, lens and labels stay per sample.  Only n_images*D*S
+ * elements are uploaded.  The evaluate-mode forward computes i_embed and the attention pre-activation
+ * once per image and its attention kernels read sample b's tiles at row image_of[b]: results are BIT-
+ * IDENTICAL to the plain batch feats[image_of].  Every other consumer (train-mode forward,
+ * rau_graph_step, module-level calls with X == NULL) first gathers the table into per-sample maps on
+ * the device and then runs as on a plain batch; a captured step reads table and index from device
+ * memory, so a new table or a new n_images replays without recapture.  rau_backward after an evaluate-
+ * mode forward of a table batch is RAU_ERR_STATE (there is no per-sample I): take evaluate-mode
+ * gradients on plain batches.  image_of is range-checked like the token ids: an entry outside
+ * [0, n_images), or n_images outside [1, B], is RAU_ERR_INVALID and nothing is uploaded.  The index and
+ * the gathered copy are allocated at a context's first table batch.
+ * rau_set_batch_images is the synchronous form (feats NULL: the resident buffer already holds the
+ * table).  rau_set_batch_async_images is the slot form; feats NULL: the slot's pinned staging
+ * (rau_batch_slot) already holds n_images*D*S elements of feat_type at its start.  Whether a slot holds
+ * a table belongs to the batch in it, like the element type: rau_use_batch makes it current.
+ * rau_batch_images: 0 for a plain resident batch, else its n_images. */
+int rau_set_batch_images(rau_ctx* ctx, const void* feats, int feat_type, int n_images,
+                         const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                         const int32_t* labels);
+int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int feat_type, int n_images,
+                               const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                               const int32_t* labels, int has_labels);
+int rau_batch_images(rau_ctx* ctx, int* n_images);
 
 /* ---- asynchronous, double-buffered upload: SS:434-439 behind the loader's prefetch -------------
  * The reference re-uploads feats / x / x_len / y every iteration (SS:434-439) while its loader's

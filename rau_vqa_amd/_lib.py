@@ -81,6 +81,11 @@ _SIGS = {
     "rau_set_batch_async_typed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int]),
     "rau_batch_feat_type": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rau_set_batch_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "rau_set_batch_async_images": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "rau_batch_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rau_forward": (C.c_int, [C.c_void_p]),
     "rau_backward": (C.c_int, [C.c_void_p, C.c_void_p]),
     # module-level entry points: device pointers in, pointers to ctx-owned slots out

@@ -273,7 +273,9 @@ hipError_t lstm_bwd_multi(hipStream_t st, int order, int nB, int R, const LstmBw
 // [SL, S) get zero attention.
 // u_out: where to keep the finished u rows [nB][A] when T is not stored (T == nullptr).
 // waves: the caller's choice of waves per sample for the forward kernel (8 | 16; 0 = the default, 8)
-struct AttPartials { int u_ns = 0; const float* u_bias = nullptr; int z_ns = 0; const float* z_bias = nullptr; int SL = 0; float* u_out = nullptr; int waves = 0; };
+struct AttPartials { int u_ns = 0; const float* u_bias = nullptr; int z_ns = 0; const float* z_bias = nullptr; int SL = 0; float* u_out = nullptr; int waves = 0;
+                     // image table (forward only): sample b reads its P and I tiles at row img[b]; null = row b
+                     const int32_t* img = nullptr; };
 hipError_t att_fwd_fused(hipStream_t st, int nB, int M, int A, int S, const float* P,
                          const float* u, const float* ws, const float* bs, const float* zm,
                          const float* I, const float* qf, float* T, float* a, float* jv,
@@ -329,6 +331,11 @@ hipError_t dropout_features_b16(hipStream_t st, int H, size_t per_hop, const voi
 // out[r][s] = widen(X[r][s]) for s < SL, 0 for SL <= s < Sp: the f32 image of a 16-bit feature map
 // (ft = RAU_FEAT_F16 / RAU_FEAT_BF16) at row pitch Sp, for the readers that take the unmasked batch
 hipError_t widen_features(hipStream_t st, size_t rows, int SL, int Sp, const void* X, float* out, int ft);
+// Image table -> per-sample maps: out[b] = table[image_of[b]] for b < nB, maps of map_bytes bytes each
+// ([D][Sp] elements of any feature type, copied as they are in 16-byte vectors; map_bytes % 8 == 0).
+// image_of is a DEVICE index whose entries the host has range-checked against the table.
+hipError_t expand_features(hipStream_t st, int nB, size_t map_bytes, const void* table, const int32_t* image_of,
+                           void* out);
 // dst[n] += sum_rows X[row*ld + n]   (two-stage, deterministic; tmp >= 32*N floats)
 hipError_t colsum_acc(hipStream_t st, int rows, int N, const float* X, long ld, float* dst,
                       float* tmp);

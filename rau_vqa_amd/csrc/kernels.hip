@@ -412,6 +412,13 @@ __device__ __forceinline__ float block_sum_ordered(const float* red, int S, int 
   return v;
 }
 
+// Row of the P / I tile tables a forward workgroup reads: its own sample, or, for a batch that carries an
+// image table, that sample's entry of the device index.  Uniform per workgroup: one scalar load, held in an
+// SGPR (the host range-checked every entry against the table before the upload).
+__device__ __forceinline__ int att_tile_row(const AttPartials& ap, int b) {
+  return ap.img ? __builtin_amdgcn_readfirstlane(ap.img[b]) : b;
+}
+
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void k_att_fwd_fused(
     int M, int A, int S, const float* __restrict__ P, const float* __restrict__ u,
@@ -426,7 +433,8 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_fused(
   float* sc = as + S;                  // [2*NW] block scalars
   const int b = blockIdx.x, tid = threadIdx.x, l = tid & 63, w = tid >> 6;
   const int S4 = S >> 2;
-  const float* Pb = P + (size_t)b * A * S;
+  const int ib = att_tile_row(ap, b);   // row of the P / I tiles (image table), else b
+  const float* Pb = P + (size_t)ib * A * S;
   float* Tb = T + (size_t)b * A * S;
   const float* ub = u + (size_t)b * A;
   // K-split partials of u / zm (+ bias) are finished here, once, into LDS
@@ -520,7 +528,7 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_fused(
   }
   __syncthreads();
   // ---- phase 3: jv[m] = qf[m] + sum_s I[m,s] a[s]; one wave per row, kAttLoads rows in flight
-  const float* Ib = I + (size_t)b * M * S;
+  const float* Ib = I + (size_t)ib * M * S;
   for (int m0 = w * kAttLoads; m0 < M; m0 += NW * kAttLoads) {
     float part[kAttLoads];
 #pragma unroll
@@ -576,7 +584,8 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_dma(
   const int b = blockIdx.x, tid = threadIdx.x, l = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int S4 = S >> 2;
-  const float* Pb = P + (size_t)b * A * S;
+  const int ib = att_tile_row(ap, b);   // row of the P / I tiles (image table), else b
+  const float* Pb = P + (size_t)ib * A * S;
   const float* ub = u + (size_t)b * A;
   if (ap.u_ns) {
     for (int k = tid; k < A; k += NW * 64) {
@@ -681,7 +690,7 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_dma(
   __syncthreads();
   // ---- phase 3: jv[m] = qf[m] + sum_s I[m,s] a[s]; lane j collects the wave's row j
   {
-    const float* Ib = I + (size_t)b * M * S;
+    const float* Ib = I + (size_t)ib * M * S;
     const int nrows = w < M ? (M - w + NW - 1) / NW : 0;
     float4 av = make_float4(0.f, 0.f, 0.f, 0.f);
     if (lane_on) av = reinterpret_cast<const float4*>(as)[l];
@@ -1086,7 +1095,7 @@ __global__ __launch_bounds__(256) void k_att_score_part(
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
   const int S4 = S >> 2;
   const int rows = (A + NC - 1) / NC, k_lo = c * rows, k_hi = min(A, k_lo + rows);
-  const float* Pb = P + (size_t)b * A * S;
+  const float* Pb = P + (size_t)att_tile_row(ap, b) * A * S;
   for (int q0 = 0; q0 < S4; q0 += 64) {
     const int q = q0 + l;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1181,7 +1190,7 @@ __global__ __launch_bounds__(256) void k_att_ctx(
   }
   __syncthreads();
   const int rows = (M + NC - 1) / NC, m_lo = c * rows, m_hi = min(M, m_lo + rows);
-  const float* Ib = I + (size_t)b * M * S;
+  const float* Ib = I + (size_t)att_tile_row(ap, b) * M * S;
   for (int m0 = m_lo + w * kSplitLoads; m0 < m_hi; m0 += 4 * kSplitLoads) {
     float pr[kSplitLoads];
 #pragma unroll
@@ -1636,6 +1645,38 @@ hipError_t widen_features(hipStream_t st, size_t rows, int SL, int Sp, const voi
   return hipGetLastError();
 }
 #undef LAUNCH_FT
+
+// Image table -> per-sample maps: out[b] = table[image_of[b]], whole maps of `map_bytes` bytes ([D][Sp] elements
+// of the batch's type, pad columns included), moved as they are in vectors of sizeof(V) bytes along S at the
+// padded pitch.  blockIdx.y = sample, blockIdx.x = a slice of its map; the index entry is uniform per
+// workgroup.  The grid depends on (B, map size) only, so a captured launch serves any table.
+template <typename V>
+__global__ __launch_bounds__(256) void k_expand_features(size_t nvec, const V* __restrict__ table,
+                                                         const int32_t* __restrict__ image_of,
+                                                         V* __restrict__ out) {
+  const int b = blockIdx.y;
+  const int ib = __builtin_amdgcn_readfirstlane(image_of[b]);
+  const V* src = table + (size_t)ib * nvec;
+  V* dst = out + (size_t)b * nvec;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < nvec; i += (size_t)gridDim.x * blockDim.x)
+    dst[i] = src[i];
+}
+hipError_t expand_features(hipStream_t st, int nB, size_t map_bytes, const void* table, const int32_t* image_of,
+                           void* out) {
+  if (nB <= 0 || !table || !image_of || !out || map_bytes % 8 != 0) return hipErrorInvalidValue;
+  // f32 maps (Sp % 4 == 0) and 16-bit maps of an even number of rows are whole 16-byte vectors
+  const bool v16 = map_bytes % 16 == 0;
+  const size_t nvec = map_bytes / (v16 ? 16 : 8);
+  const int slices = (int)std::min<size_t>(16, (nvec + 1023) / 1024);   // >= 4 vectors per thread and slice
+  const dim3 grid(std::max(slices, 1), nB);
+  if (v16)
+    hipLaunchKernelGGL(k_expand_features<uint4>, grid, dim3(256), 0, st, nvec, static_cast<const uint4*>(table),
+                       image_of, static_cast<uint4*>(out));
+  else
+    hipLaunchKernelGGL(k_expand_features<uint2>, grid, dim3(256), 0, st, nvec, static_cast<const uint2*>(table),
+                       image_of, static_cast<uint2*>(out));
+  return hipGetLastError();
+}
 
 // ----------------------------------------------- deterministic column sums
 // dst[n] += sum_r X[r, n]: stage 1 sums kColChunks row chunks (fixed order inside a chunk),

@@ -80,6 +80,11 @@ struct BatchSlot {
   int32_t *utok = nullptr, *ustart = nullptr, *upos = nullptr;
   float* feats_h = nullptr;                                 // pinned host, dense [B][D][S] (16-bit: first half)
   int feat_type = RAU_FEAT_F32;                             // rau_feat_type of the batch the slot holds
+  // image table (rau_set_batch_images): `feats` holds n_images maps, sample b looks at map image_of_d[b];
+  // 0 = a plain batch.  The index buffers are allocated at the slot's first table batch.
+  int n_images = 0;
+  int32_t* image_of_d = nullptr;                            // device [B]
+  int32_t* image_of_h = nullptr;                            // pinned host [B] (asynchronous path)
   int32_t *tokens_h = nullptr, *lens_p = nullptr, *labels_h = nullptr;
   int32_t *utok_h = nullptr, *ustart_h = nullptr, *upos_h = nullptr;
   std::vector<int32_t> lens;
@@ -120,6 +125,15 @@ struct rau_ctx {
   // batch
   float* feats = nullptr;
   int feat_type = RAU_FEAT_F32;   // rau_feat_type of the resident batch (what `feats` holds)
+  int n_images = 0;               // the resident batch carries an image table of that many maps (0: plain batch);
+                                  // its device index is slot[cur_slot].image_of_d
+  float* feats_x = nullptr;       // [B][D][Sp] per-sample maps gathered from the table (expand_features), in the
+                                  // batch's element type; allocated at the first table batch
+  bool x_valid = false;           // feats_x holds the expansion of upload x_serial into slot x_slot
+  int x_slot = 0;
+  uint64_t x_serial = 0;
+  bool fwd_table = false;         // the last forward read P and I per IMAGE (evaluate-mode fast path): there
+                                  // is no per-sample I for a backward pass
   float* xw = nullptr;            // f32 image of the unmasked batch the last forward read: feats, or (16-bit
                                   // batch) the first B*D*Sp floats of xd, widened there by that forward
   int32_t *tokens = nullptr, *lens_d = nullptr, *labels_d = nullptr;
@@ -404,7 +418,11 @@ __attribute__((visibility("hidden"))) int hop_forward(rau_ctx* ctx, int h, const
     const float* hp, float* c_out, float* h_out, const float* Ih, const float* Pin,
     const int32_t* labels);
 __attribute__((visibility("hidden"))) int hop_forward_chain(rau_ctx* ctx, int h, const float* cp,
-    const float* hp, float* c_out, float* h_out, const float* Ih, const float* Pin);
+    const float* hp, float* c_out, float* h_out, const float* Ih, const float* Pin,
+    const int32_t* img = nullptr /* device index: sample b's Ih / Pin tiles are row img[b] (image table) */);
+// The resident batch as per-sample maps [B][D][Sp] in its element type: the buffer itself, or for a batch
+// with an image table its expansion (expand_features on the chain stream, once per upload).
+__attribute__((visibility("hidden"))) int batch_maps(rau_ctx* ctx, const float** maps);
 __attribute__((visibility("hidden"))) int hop_forward_head(rau_ctx* ctx, hipStream_t s, float* ws,
     size_t reg, int h0, int nh, const int32_t* labels);
 __attribute__((visibility("hidden"))) int hop_backward(rau_ctx* ctx, int h, const float* cp,

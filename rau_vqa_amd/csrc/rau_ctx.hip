@@ -557,6 +557,7 @@ void rau_destroy(rau_ctx* ctx) {
   if (ctx->stc) { hipStreamSynchronize(ctx->stc); hipStreamDestroy(ctx->stc); }
   for (BatchSlot& s : ctx->slot) {
     if (s.feats_h) hipHostFree(s.feats_h);
+    if (s.image_of_h) hipHostFree(s.image_of_h);
     if (s.uploaded) hipEventDestroy(s.uploaded);
     if (s.consumed) hipEventDestroy(s.consumed);
   }
@@ -752,20 +753,24 @@ int index_batch(const rau_config& c, const int32_t* tokens, const int32_t* lens,
 }
 
 // H2D copies of one batch into a set of device buffers, enqueued on `s`.  feats holds elements of
-// feat_type (4 or 2 bytes); prev_type is the type of what the device buffer holds now.
+// feat_type (4 or 2 bytes); prev_type is the type of what the device buffer holds now.  n_images > 0: feats is
+// an image table of that many maps and image_of (host, [B], checked) goes to the slot's device index.
 int enqueue_batch(rau_ctx* ctx, hipStream_t s, const BatchSlot& d, const void* feats, int feat_type,
                   int prev_type, const int32_t* tokens, const int32_t* lens, const int32_t* labels,
-                  const int32_t* utok, const int32_t* ustart, const int32_t* upos) {
+                  const int32_t* utok, const int32_t* ustart, const int32_t* upos, int n_images = 0,
+                  const int32_t* image_of = nullptr) {
   const rau_config& c = ctx->cfg;
   const size_t TB = (size_t)c.T * c.B, es = feat_type == RAU_FEAT_F32 ? 4 : 2;
+  const size_t maps = n_images > 0 ? (size_t)n_images : (size_t)c.B;   // only these cross the bus
+  if (n_images > 0) HIPC(hipMemcpyAsync(d.image_of_d, image_of, (size_t)c.B * 4, hipMemcpyHostToDevice, s));
   // pitched rows of another element size leave data in this type's pad columns: zero them first
   if (feats && ctx->Sp != c.S && feat_type != prev_type)
     HIPC(hipMemsetAsync(d.feats, 0, (size_t)c.B * c.D * ctx->Sp * sizeof(float), s));
   if (feats && ctx->Sp == c.S)   // dense on both sides: one linear copy (a DMA-engine transfer, no blit kernel)
-    HIPC(hipMemcpyAsync(d.feats, feats, (size_t)c.B * c.D * c.S * es, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(d.feats, feats, maps * c.D * c.S * es, hipMemcpyHostToDevice, s));
   else if (feats)   // rows of S positions into rows of Sp (pad columns stay zero)
     HIPC(hipMemcpy2DAsync(d.feats, (size_t)ctx->Sp * es, feats, (size_t)c.S * es, (size_t)c.S * es,
-                          (size_t)c.B * c.D, hipMemcpyHostToDevice, s));
+                          maps * c.D, hipMemcpyHostToDevice, s));
   HIPC(hipMemcpyAsync(d.tokens, tokens, TB * 4, hipMemcpyHostToDevice, s));
   HIPC(hipMemcpyAsync(d.lens_d, lens, (size_t)c.B * 4, hipMemcpyHostToDevice, s));
   if (labels) HIPC(hipMemcpyAsync(d.labels_d, labels, (size_t)c.B * 4, hipMemcpyHostToDevice, s));
@@ -780,6 +785,7 @@ void make_current(rau_ctx* ctx, int si) {
   ctx->cur_slot = si;
   ctx->feats = s.feats; ctx->tokens = s.tokens; ctx->lens_d = s.lens_d; ctx->labels_d = s.labels_d;
   ctx->feat_type = s.feat_type;
+  ctx->n_images = s.n_images;
   ctx->utok = s.utok; ctx->ustart = s.ustart; ctx->upos = s.upos;
   ctx->lens_h = s.lens;
   ctx->max_len = s.max_len;
@@ -787,6 +793,32 @@ void make_current(rau_ctx* ctx, int si) {
   ctx->have_batch = s.have;
   ctx->have_labels = s.have_labels;
   ctx->fwd_done = false;
+}
+
+// image table of a batch: n_images in [1, B], every entry of the host index a row of the table
+int check_table(const rau_config& c, int n_images, const int32_t* image_of) {
+  NEED(image_of, "null image_of");
+  NEED(n_images >= 1 && n_images <= c.B, "n_images=%d out of [1,%d]", n_images, c.B);
+  for (int b = 0; b < c.B; ++b)
+    NEED(image_of[b] >= 0 && image_of[b] < n_images, "image_of[%d]=%d out of [0,%d)", b, image_of[b], n_images);
+  return RAU_OK;
+}
+// first table batch of a slot: its device index (and pinned staging of it on the asynchronous path) and the
+// ctx's buffer of expanded per-sample maps
+int ensure_table(rau_ctx* ctx, int si, bool pinned) {
+  const rau_config& c = ctx->cfg;
+  BatchSlot& s = ctx->slot[si];
+  if (!s.image_of_d)
+    if (int rc = dalloc(ctx, &s.image_of_d, (size_t)c.B)) return rc;
+  if (!ctx->feats_x)
+    if (int rc = dalloc(ctx, &ctx->feats_x, (size_t)c.B * c.D * ctx->Sp)) return rc;
+  if (pinned && !s.image_of_h) {
+    void* h = nullptr;
+    hipError_t e = hipHostMalloc(&h, (size_t)c.B * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(image index staging): %s", hipGetErrorString(e));
+    s.image_of_h = static_cast<int32_t*>(h);
+  }
+  return RAU_OK;
 }
 
 // second set of device buffers, pinned staging for both slots, copy stream, events
@@ -799,6 +831,7 @@ int ensure_async(rau_ctx* ctx) {
   s0.utok = ctx->utok; s0.ustart = ctx->ustart; s0.upos = ctx->upos;
   s0.lens = ctx->lens_h; s0.max_len = ctx->max_len; s0.nuniq = ctx->nuniq;
   s0.have = ctx->have_batch; s0.have_labels = ctx->have_labels; s0.feat_type = ctx->feat_type;
+  s0.n_images = ctx->n_images;
   BatchSlot& s1 = ctx->slot[1];
   if (int rc = dalloc(ctx, &s1.feats, (size_t)c.B * c.D * ctx->Sp)) return rc;
   if (int rc = dalloc(ctx, &s1.tokens, TB)) return rc;
@@ -841,25 +874,39 @@ int rau_set_batch(rau_ctx* ctx, const float* feats, const int32_t* tokens, const
 
 int rau_set_batch_typed(rau_ctx* ctx, const void* feats, int feat_type, const int32_t* tokens,
                         const int32_t* lens, const int32_t* labels) {
+  return rau_set_batch_images(ctx, feats, feat_type, 0, nullptr, tokens, lens, labels);
+}
+
+// n_images == 0 with image_of == NULL is the plain batch (what rau_set_batch_typed passes)
+int rau_set_batch_images(rau_ctx* ctx, const void* feats, int feat_type, int n_images, const int32_t* image_of,
+                         const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
   NEED(ctx && tokens && lens, "null argument");
-  NEED(feat_type_ok(feat_type), "rau_set_batch_typed: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)", feat_type);
+  NEED(feat_type_ok(feat_type), "rau_set_batch: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)", feat_type);
   const rau_config& c = ctx->cfg;
+  const bool table = n_images != 0 || image_of != nullptr;
+  if (table) {
+    if (int rc = check_table(c, n_images, image_of)) return rc;
+  }
   const size_t TB = (size_t)c.T * c.B;
   std::vector<int32_t> utok(TB), ustart(TB + 1), upos(TB);
   int max_len = 0, nuniq = 0;
   if (int rc = index_batch(c, tokens, lens, labels, utok.data(), ustart.data(), upos.data(), &max_len, &nuniq))
     return rc;
+  if (table)
+    if (int rc = ensure_table(ctx, ctx->cur_slot, false)) return rc;
   BatchSlot d;   // the CURRENT device buffers (slot 0 unless rau_use_batch switched)
+  d.image_of_d = ctx->slot[ctx->cur_slot].image_of_d;
   d.feats = ctx->feats; d.tokens = ctx->tokens; d.lens_d = ctx->lens_d; d.labels_d = ctx->labels_d;
   d.utok = ctx->utok; d.ustart = ctx->ustart; d.upos = ctx->upos;
   if (ctx->async_ready && ctx->slot[ctx->cur_slot].upload_pending)   // an async upload into the same buffers
     HIPC(hipStreamWaitEvent(ctx->st, ctx->slot[ctx->cur_slot].uploaded, 0));
   ++ctx->slot_serial[ctx->cur_slot];
   if (int rc = enqueue_batch(ctx, ctx->st, d, feats, feat_type, ctx->feat_type, tokens, lens, labels,
-                             utok.data(), ustart.data(), upos.data()))
+                             utok.data(), ustart.data(), upos.data(), table ? n_images : 0, image_of))
     return rc;
   HIPC(hipStreamSynchronize(ctx->st));   // the caller's (pageable) buffers are free on return
   ctx->feat_type = feat_type;
+  ctx->n_images = ctx->slot[ctx->cur_slot].n_images = table ? n_images : 0;
   ctx->lens_h.assign(lens, lens + c.B);
   ctx->max_len = max_len;
   ctx->nuniq = nuniq;
@@ -900,17 +947,30 @@ int rau_set_batch_async(rau_ctx* ctx, int slot, const float* feats, const int32_
 int rau_set_batch_async_typed(rau_ctx* ctx, int slot, const void* feats, int feat_type,
                               const int32_t* tokens, const int32_t* lens, const int32_t* labels,
                               int has_labels) {
+  return rau_set_batch_async_images(ctx, slot, feats, feat_type, 0, nullptr, tokens, lens, labels, has_labels);
+}
+
+// n_images == 0 with image_of == NULL is the plain batch (what rau_set_batch_async_typed passes)
+int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int feat_type, int n_images,
+                               const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                               const int32_t* labels, int has_labels) {
   NEED(ctx, "null ctx");
-  NEED(feat_type_ok(feat_type), "rau_set_batch_async_typed: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)",
+  NEED(feat_type_ok(feat_type), "rau_set_batch_async: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)",
        feat_type);
   NEED(slot == 0 || slot == 1, "rau_set_batch_async: slot %d (0 or 1)", slot);
-  if (int rc = ensure_async(ctx)) return rc;
   const rau_config& c = ctx->cfg;
+  const bool table = n_images != 0 || image_of != nullptr;
+  if (table) {
+    if (int rc = check_table(c, n_images, image_of)) return rc;
+  }
+  if (int rc = ensure_async(ctx)) return rc;
+  if (table)
+    if (int rc = ensure_table(ctx, slot, true)) return rc;
   BatchSlot& s = ctx->slot[slot];
   if (slot == ctx->cur_slot && ctx->fwd_done)
     return fail(RAU_ERR_STATE, "rau_set_batch_async: slot %d is the current batch of a forward pass whose "
                 "backward has not run; upload into the other slot", slot);
-  const size_t TB = (size_t)c.T * c.B, nf = (size_t)c.B * c.D * c.S;
+  const size_t TB = (size_t)c.T * c.B, nf = (size_t)(table ? n_images : c.B) * c.D * c.S;
   const bool copies = (feats && feats != s.feats_h) || (tokens && tokens != s.tokens_h) ||
                       (lens && lens != s.lens_p) || (labels && labels != s.labels_h);
   (void)copies;
@@ -927,6 +987,7 @@ int rau_set_batch_async_typed(rau_ctx* ctx, int slot, const void* feats, int fea
   if (tokens && tokens != s.tokens_h) std::memcpy(s.tokens_h, tokens, TB * 4);
   if (lens && lens != s.lens_p) std::memcpy(s.lens_p, lens, (size_t)c.B * 4);
   if (labels && labels != s.labels_h) std::memcpy(s.labels_h, labels, (size_t)c.B * 4);
+  if (table) std::memcpy(s.image_of_h, image_of, (size_t)c.B * 4);
   const bool with_labels = labels != nullptr || has_labels != 0;
   int max_len = 0, nuniq = 0;
   if (int rc = index_batch(c, s.tokens_h, s.lens_p, with_labels ? s.labels_h : nullptr, s.utok_h, s.ustart_h,
@@ -940,11 +1001,13 @@ int rau_set_batch_async_typed(rau_ctx* ctx, int slot, const void* feats, int fea
   if (s.consumed_valid) HIPC(hipStreamWaitEvent(ctx->stc, s.consumed, 0));
   ++ctx->slot_serial[slot];
   if (int rc = enqueue_batch(ctx, ctx->stc, s, s.feats_h, feat_type, s.feat_type, s.tokens_h, s.lens_p,
-                             with_labels ? s.labels_h : nullptr, s.utok_h, s.ustart_h, s.upos_h))
+                             with_labels ? s.labels_h : nullptr, s.utok_h, s.ustart_h, s.upos_h,
+                             table ? n_images : 0, s.image_of_h))
     return rc;
   HIPC(hipEventRecord(s.uploaded, ctx->stc));
   s.upload_pending = true;
   s.feat_type = feat_type;
+  s.n_images = table ? n_images : 0;
   s.lens.assign(s.lens_p, s.lens_p + c.B);
   s.max_len = max_len;
   s.nuniq = nuniq;
@@ -989,6 +1052,36 @@ int rau_batch_feat_type(rau_ctx* ctx, int* feat_type) {
   return RAU_OK;
 }
 
+int rau_batch_images(rau_ctx* ctx, int* n_images) {
+  NEED(ctx && n_images, "null argument");
+  *n_images = ctx->n_images;
+  return RAU_OK;
+}
+
+}  // extern "C"
+
+int batch_maps(rau_ctx* ctx, const float** maps) {
+  *maps = ctx->feats;
+  if (!ctx->n_images) return RAU_OK;
+  const rau_config& c = ctx->cfg;
+  *maps = ctx->feats_x;
+  // a captured launch gathers on every replay (the table and the index live in device memory); otherwise once
+  // per upload into the slot
+  if (!ctx->capturing && ctx->x_valid && ctx->x_slot == ctx->cur_slot &&
+      ctx->x_serial == ctx->slot_serial[ctx->cur_slot])
+    return RAU_OK;
+  const size_t map_bytes = (size_t)c.D * ctx->Sp * (ctx->feat_type == RAU_FEAT_F32 ? 4 : 2);
+  hipStream_t st = ctx->st;
+  RUN("expand_features", 0, 2.0 * c.B * map_bytes,
+      expand_features(st, c.B, map_bytes, ctx->feats, ctx->slot[ctx->cur_slot].image_of_d, ctx->feats_x));
+  ctx->x_valid = true;
+  ctx->x_slot = ctx->cur_slot;
+  ctx->x_serial = ctx->slot_serial[ctx->cur_slot];
+  return RAU_OK;
+}
+
+extern "C" {
+
 }  // extern "C"
 
 // ================================================================ one hop
@@ -1002,7 +1095,7 @@ int rau_batch_feat_type(rau_ctx* ctx, int* feat_type) {
 // rau_forward runs the heads on the weight-gradient stream (idle during the forward pass), so the
 // hop-to-hop critical path is the chain alone; the module-level entry points run both on st.
 int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, float* c_out,
-                      float* h_out, const float* Ih, const float* Pin) {
+                      float* h_out, const float* Ih, const float* Pin, const int32_t* img) {
   const rau_config& c = ctx->cfg;
   const int B = c.B, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R;
   hipStream_t st = ctx->st;
@@ -1050,6 +1143,7 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
     // evaluate mode: no conv tile is resident while the hops run (I and P are hoisted), so the 16-wave form
     // fits and streams a sample faster (B = 256: 124.2 -> 129.5 k QA/s); the training step keeps 8
     ap.waves = ctx->mode == RAU_MODE_EVAL ? 16 : 0;
+    ap.img = img;   // image table: Pin and Ih hold one tile per image, sample b reads row img[b]
     if (!(ctx->att_split_env))
       RUN("att_fwd_fused", 2.0 * B * S * (A + M), ((double)B * A * S + BM_ * S) * 4,
           att_fwd_fused(st, B, M, A, S, Pin, slab_u, ctx->att_score.W, ctx->att_score.b, slab_z, Ih, qf,
@@ -1456,6 +1550,17 @@ int rau_forward(rau_ctx* ctx) {
   return 0;
   };
   ctx->I_shared = (m_x == nullptr);
+  // A batch with an image table.  Evaluate mode: nothing per sample touches the maps (no dropout on X), so
+  // i_embed and the attention pre-activation run once per IMAGE and the attention kernels read sample b's
+  // tiles at row image_of[b].  Everywhere else (train mode: per-sample masks; a captured step: its backward
+  // needs per-sample I) the table is gathered into per-sample maps first and the plain path runs on those.
+  const bool table_fwd = ctx->n_images > 0 && ctx->I_shared && ctx->mode == RAU_MODE_EVAL && !ctx->capturing;
+  const int nX = table_fwd ? ctx->n_images : B;   // maps the image-side passes read
+  const int32_t* img = table_fwd ? ctx->slot[ctx->cur_slot].image_of_d : nullptr;
+  const float* feats = ctx->feats;
+  if (!table_fwd)
+    if (int rc = batch_maps(ctx, &feats)) return rc;   // (on st, in front of evA: the bulk stream is ordered behind it)
+  ctx->fwd_table = table_fwd;
   if (ctx->I_shared) {   // evaluate mode: one launch group
     ctx->cur.assign(H, 0);
     ctx->cur[0] = H;
@@ -1481,25 +1586,25 @@ int rau_forward(rau_ctx* ctx) {
     if (x_gen)
       RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * (x16 ? 2 : 4),
            dropout_features_gen(sb, ctx->seed, RAU_MASK_X, ctx->step, ctx->mp[RAU_MASK_X], ctx->dkey, H,
-                                (size_t)B * D * S, ctx->feats, sc(RAU_MASK_X),
+                                (size_t)B * D * S, feats, sc(RAU_MASK_X),
                                 x16 ? (void*)ctx->xd16 : (void*)ctx->xd, x16 ? 1 : 0, ft));
     else if (x16)
       RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * 2,
-           dropout_features_b16(sb, H, (size_t)B * D * S, ctx->feats, m_x, sc(RAU_MASK_X), ctx->xd16, ft));
+           dropout_features_b16(sb, H, (size_t)B * D * S, feats, m_x, sc(RAU_MASK_X), ctx->xd16, ft));
     else if (m_x)
       RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * 4,
-           dropout_features(sb, H, (size_t)B * D * S, ctx->feats, m_x, sc(RAU_MASK_X), ctx->xd, 0, SL,
+           dropout_features(sb, H, (size_t)B * D * S, feats, m_x, sc(RAU_MASK_X), ctx->xd, 0, SL,
                             S, ft));
     // no mask: the GEMMs read the batch itself -- a 16-bit one through its f32 image in xd (unused here),
     // so that they are the f32 batch's kernels with the f32 batch's operands
-    ctx->xw = ctx->feats;
+    ctx->xw = const_cast<float*>(feats);
     if (!m_x && ft != RAU_FEAT_F32) {
       ctx->xw = ctx->xd;
-      RUNS(sb, "widen_features", 0, (double)B * D * S * (xb + 4),
-           widen_features(sb, (size_t)B * D, SL, S, ctx->feats, ctx->xw, ft));
+      RUNS(sb, "widen_features", 0, (double)nX * D * S * (xb + 4),
+           widen_features(sb, (size_t)nX * D, SL, S, feats, ctx->xw, ft));
     }
     for (int h0 = 0; h0 < H; h0 += gsz[h0]) {
-      const int nBI = ctx->I_shared ? B : gsz[h0] * B;
+      const int nBI = ctx->I_shared ? nX : gsz[h0] * B;
       const size_t hb = ctx->I_shared ? 0 : (size_t)h0 * B;  // first (hop, sample) row
       const float* xin = m_x ? ctx->xd + hb * D * S : ctx->xw;
       float* Ig = ctx->I + hb * M * S;
@@ -1577,7 +1682,7 @@ int rau_forward(rau_ctx* ctx) {
     if (int rc = hop_forward_chain(ctx, h, ctx->cc + (size_t)h * BR_, ctx->hh + (size_t)h * BR_,
                                    ctx->cc + (size_t)(h + 1) * BR_, ctx->hh + (size_t)(h + 1) * BR_,
                                    ctx->I + (ctx->I_shared ? 0 : (size_t)h * BM_ * S),
-                                   ctx->I_shared ? ctx->P0 : ctx->T + (size_t)h * B * A * S))
+                                   ctx->I_shared ? ctx->P0 : ctx->T + (size_t)h * B * A * S, img))
       return rc;
     // classifier + criterion heads of the finished hops: nothing on the recurrence waits for
     // them, so they run on the weight-gradient stream (idle in the forward pass), batched over
@@ -1646,6 +1751,10 @@ static int upload_hop_weights(rau_ctx* ctx, const float* hop_w) {
 int rau_backward(rau_ctx* ctx, const float* hop_w) {
   NEED(ctx && hop_w, "null argument");
   if (!ctx->fwd_done) return fail(RAU_ERR_STATE, "rau_backward: call rau_forward first");
+  if (ctx->fwd_table)
+    return fail(RAU_ERR_STATE, "rau_backward: the evaluate-mode forward of a batch with an image table computed "
+                "i_embed once per image, so there is no per-sample I to differentiate; take evaluate-mode "
+                "gradients on a plain batch (rau_set_batch)");
   set_skinny_policy(ctx);
   if (!ctx->have_labels) return fail(RAU_ERR_STATE, "rau_backward: batch has no labels");
   const rau_config& c = ctx->cfg;
@@ -2003,6 +2112,7 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
   for (int i = 0; i < 5; ++i) key |= (uint64_t)ctx->mexplicit[i] << (24 + i);
   key |= (uint64_t)ctx->cur_slot << 30;   // the captured kernels hold the batch slot's device pointers
   key |= (uint64_t)ctx->feat_type << 32;  // ... and read the batch in its element type
+  key |= (uint64_t)(ctx->n_images > 0) << 34;   // ... through the gather of an image table (any table, any N)
   if (int rc = upload_hop_weights(ctx, hop_w)) return rc;
   ctx->mg_valid = false;
   hipGraphExec_t exec = nullptr;
@@ -2030,6 +2140,11 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
     ctx->graphs.push_back({key, exec});
   }
   HIPC(hipGraphLaunch(exec, ctx->st));
+  if (ctx->n_images) {   // the graph's gather node has just filled feats_x from this upload
+    ctx->x_valid = true;
+    ctx->x_slot = ctx->cur_slot;
+    ctx->x_serial = ctx->slot_serial[ctx->cur_slot];
+  }
   HIPC(hipEventRecord(ctx->evEnd, ctx->st));   // a real (non-captured) end-of-step event
   merge_record(ctx);
   ctx->fwd_done = false;

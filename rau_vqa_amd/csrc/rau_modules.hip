@@ -80,13 +80,14 @@ int lin_wgrad(rau_ctx* ctx, Lin& l, const float* dY, const float* X, long ldx, b
 // X = NULL ("the resident batch"): its f32 form at pitch Sp -- the buffer itself, or for a 16-bit batch
 // its exact widening into ctx-owned scratch (allocated on first use), so that the f32 kernels run on it
 int resident_feats(rau_ctx* ctx, const float** X) {
-  *X = ctx->feats;
+  if (int rc = batch_maps(ctx, X)) return rc;   // a batch with an image table: its per-sample expansion
   if (ctx->feat_type == RAU_FEAT_F32) return 0;
+  const float* src = *X;
   const rau_config& c = ctx->cfg;
   if (!ctx->m_Xw)
     if (int rc = dalloc(ctx, &ctx->m_Xw, (size_t)c.B * c.D * ctx->Sp)) return rc;
   RUN("widen_features", 0, (double)c.B * c.D * ctx->Sp * 6,
-      widen_features(ctx->st, (size_t)c.B * c.D, c.S, ctx->Sp, ctx->feats, ctx->m_Xw, ctx->feat_type));
+      widen_features(ctx->st, (size_t)c.B * c.D, c.S, ctx->Sp, src, ctx->m_Xw, ctx->feat_type));
   *X = ctx->m_Xw;
   return 0;
 }

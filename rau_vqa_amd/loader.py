@@ -65,6 +65,7 @@ class DataClass:
         self.batch_order = np.arange(self.n)
         self._job = None          # (key, thread, result holder)
         self._next_dest = None    # SlotFeeder: where the prefetch worker assembles the next batch
+        self._unique = False      # the last next_batch_feat asked for an image table: so will the prefetched one
 
     # ---- batch order options, loader.lua:1219-1291
     def set_batch_order_option(self, opt):
@@ -106,15 +107,30 @@ class DataClass:
                 for i, d in zip(idx, dt)]
 
     @staticmethod
+    def _image_table(paths):
+        """The batch's distinct feature paths in order of first appearance, and image_of [B] int32: the
+        0-based row of that list each sample looks at.  Duplicates are found by path, so the questions of
+        one image need not be adjacent."""
+        row, uniq = {}, []
+        image_of = np.empty(len(paths), np.int32)
+        for b, p in enumerate(paths):
+            if p not in row:
+                row[p] = len(uniq)
+                uniq.append(p)
+            image_of[b] = row[p]
+        return uniq, image_of
+
+    @staticmethod
     def _load_feats(paths, D, W, H, out=None, feat_type="f32"):
         """Per-image feature files into one [B,D,W,H] array of feat_type; `out` = a caller-owned
         destination (the pinned staging of an upload slot: the batch is assembled where the H2D copy
-        reads it), whose dtype then decides.  f32 files are rounded into a 16-bit destination on
+        reads it), whose dtype then decides; fewer paths than it has room for (an image table) fill its
+        first len(paths) maps.  f32 files are rounded into a 16-bit destination on
         assignment; HalfTensor files are copied as they are into an fp16 one."""
         if out is None:
             out = np.zeros((len(paths), D, W, H), feat16.dtype_of(feat_type))
         else:
-            out = out.reshape(len(paths), D, W, H)
+            out = out.reshape(-1)[:len(paths) * D * W * H].reshape(len(paths), D, W, H)
         keep_half = out.dtype != np.float32
         for i, p in enumerate(paths):   # load_feature asserts the three sizes
             feat16.store(out[i], t7.load_feature(p, D, W, H, keep_half).reshape(D, W, H))
@@ -124,33 +140,40 @@ class DataClass:
         paths = self._paths(self.batch_index, tab_featpaths)
         holder = {}
         dest = self._next_dest() if self._next_dest is not None else None
+        unique = self._unique
+        files = self._image_table(paths)[0] if unique else paths
 
         def work():
             try:
-                holder["feats"] = self._load_feats(paths, D, W, H, dest, self.feat_type)
+                holder["feats"] = self._load_feats(files, D, W, H, dest, self.feat_type)
             except Exception as e:   # surfaced on the consumer side
                 holder["error"] = e
         th = threading.Thread(target=work, daemon=True)
         th.start()
-        self._job = ((self.batch_index, tuple(paths)), th, holder)
+        self._job = ((self.batch_index, tuple(paths), unique), th, holder)
 
-    def next_batch_feat(self, tab_featpaths, feat_dim, feat_w=1, feat_h=1):
-        """-> feats [B,D,W,H] (f32, or the 16-bit feat_type), x [T,B] i32, x_len [B] i32, a [B] | [B,nMC] i32, qids [B]."""
+    def next_batch_feat(self, tab_featpaths, feat_dim, feat_w=1, feat_h=1, unique=False):
+        """-> feats [B,D,W,H] (f32, or the 16-bit feat_type), x [T,B] i32, x_len [B] i32, a [B] | [B,nMC] i32, qids [B].
+        unique=True: every distinct feature file of the batch is read once, in order of first appearance;
+        feats is that image table [N,D,W,H] and image_of [B] i32 (0-based table rows) is appended to the
+        tuple: feats[image_of] is what unique=False returns."""
         if isinstance(tab_featpaths, (str, os.PathLike)):
             tab_featpaths = [tab_featpaths]
         B = self.batch_size
         idx = self.batch_order[self.batch_index:self.batch_index + B]
         paths = self._paths(self.batch_index, tab_featpaths)
+        files, image_of = self._image_table(paths) if unique else (paths, None)
+        self._unique = bool(unique)
         feats = None
         if self.opt_prefetch and self._job is not None:
             key, th, holder = self._job
             th.join()                                    # pool:synchronize()
             if "error" in holder:
                 raise holder["error"]
-            if key == (self.batch_index, tuple(paths)):
+            if key == (self.batch_index, tuple(paths), bool(unique)):
                 feats = holder["feats"]
         if feats is None:
-            feats = self._load_feats(paths, feat_dim, feat_w, feat_h, feat_type=self.feat_type)
+            feats = self._load_feats(files, feat_dim, feat_w, feat_h, feat_type=self.feat_type)
         x = np.ascontiguousarray(self.qs.question[idx].T, np.int32)          # transpose(1,2)
         x_len = np.ascontiguousarray(self.qs.lengths_q[idx], np.int32)
         qids = np.ascontiguousarray(self.qs.question_id[idx])
@@ -161,6 +184,8 @@ class DataClass:
             self.reorder()
         if self.opt_prefetch:
             self._start_prefetch(tab_featpaths, feat_dim, feat_w, feat_h)
+        if unique:
+            return feats, x, x_len, a, qids, image_of
         return feats, x, x_len, a, qids
 
 
@@ -216,11 +241,13 @@ def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=12
 
 def feed(rau, batch, feat_type=None):
     """next_batch_feat's tuple -> rau_set_batch (the H2D of SS:434-439); returns qids.
-    feat_type: that of the feats (needed for bf16, which arrives as uint16 bits)."""
-    feats, x, x_len, a, qids = batch
-    B, D = feats.shape[0], feats.shape[1]
+    feat_type: that of the feats (needed for bf16, which arrives as uint16 bits).  A tuple of
+    next_batch_feat(unique=True) goes up as an image table."""
+    feats, x, x_len, a, qids = batch[:5]
+    image_of = batch[5] if len(batch) > 5 else None
+    B, D = feats.shape[0], feats.shape[1]                 # (image table: B is its number of maps)
     labels = a if a.ndim == 1 else None                   # test batches carry MC ids, no labels
-    rau.set_batch(feats.reshape(B, D, -1), x, x_len, labels, feat_type=feat_type)
+    rau.set_batch(feats.reshape(B, D, -1), x, x_len, labels, feat_type=feat_type, image_of=image_of)
     return qids
 
 
@@ -242,8 +269,11 @@ class SlotFeeder:
     """
 
     def __init__(self, rau, data: DataClass, tab_featpaths, feat_dim, feat_w=1, feat_h=1,
-                 feat_type=None):
+                 feat_type=None, share_images=False):
         self.rau, self.data = rau, data
+        # every distinct image of a batch is read, staged and uploaded once (next_batch_feat(unique=True));
+        # the worker fills the first N maps of the slot's staging
+        self.share_images = bool(share_images)
         self.args = (tab_featpaths, feat_dim, feat_w, feat_h)
         self.slot = 0                  # the slot the NEXT batch is assembled in
         # element type of the maps in the staging and on the wire (default: the DataClass's)
@@ -258,15 +288,18 @@ class SlotFeeder:
         d, rau, s = self.data, self.rau, self.slot
         view = rau.batch_slot(s, **self._ft)          # (host-waits until the slot's last upload has left)
         self.slot = s ^ 1                             # the worker started by next_batch_feat fills the other
-        feats, x, x_len, a, qids = d.next_batch_feat(*self.args)
+        batch = d.next_batch_feat(*self.args, unique=self.share_images)
+        feats, x, x_len, a, qids = batch[:5]
+        table = {"image_of": batch[5], "n_images": feats.shape[0]} if self.share_images else {}
         if not np.shares_memory(feats, view["feats"]):   # first batch / a re-drawn order: not prefetched in place
-            feat16.store(view["feats"], feats.reshape(view["feats"].shape))
+            stage = view["feats"].reshape(-1)[:feats.size]
+            feat16.store(stage, feats.reshape(stage.shape))
         view["tokens"][...] = x
         view["lens"][...] = x_len
         labels = a.ndim == 1                          # test batches carry MC ids, no labels
         if labels:
             view["labels"][...] = a
-        rau.set_batch_async(s, has_labels=labels, **self._ft)   # staging filled in place: no host copy
+        rau.set_batch_async(s, has_labels=labels, **table, **self._ft)   # staging filled in place: no host copy
         rau.use_batch(s)
         return qids
 

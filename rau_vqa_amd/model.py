@@ -185,14 +185,30 @@ class RAU:
         return m.reshape(shape)
 
     # ---- batch + the hot path
-    def set_batch(self, feats, tokens, lens, labels=None, feat_type=None):
+    def _image_index(self, feats, image_of):
+        """(n_images, index array) of a batch whose feats [N, D, ...] is an image table."""
+        c = self.cfg
+        image_of = np.ascontiguousarray(image_of, np.int32)
+        n = int(feats.shape[0]) if feats.ndim >= 2 else 0
+        if image_of.shape != (c.B,) or n < 1 or feats.size != n * c.D * c.S:
+            raise ValueError("image table shapes do not match the config")
+        return n, image_of
+
+    def set_batch(self, feats, tokens, lens, labels=None, feat_type=None, image_of=None):
         """feat_type "f32" | "f16" | "bf16" (default: from the dtype, see feat16.infer): a 16-bit map
-        gives the same results, bit for bit, as the f32 map of its widened values."""
+        gives the same results, bit for bit, as the f32 map of its widened values.
+        image_of [B] (0-based rows): feats is an image TABLE [N, D, S] that the questions of one image
+        share; the same results, bit for bit, as the plain batch feats[image_of]."""
         c = self.cfg
         feats, ft = feat16.as_feats(feats, feat_type)
         tokens = np.ascontiguousarray(tokens, np.int32)
         lens = np.ascontiguousarray(lens, np.int32)
-        if feats.size != c.B * c.D * c.S or tokens.shape != (c.T, c.B) or lens.shape != (c.B,):
+        n_images = 0
+        if image_of is not None:
+            n_images, image_of = self._image_index(feats, image_of)
+        elif feats.size != c.B * c.D * c.S:
+            raise ValueError("batch shapes do not match the config")
+        if tokens.shape != (c.T, c.B) or lens.shape != (c.B,):
             raise ValueError("batch shapes do not match the config")
         lp = None
         if labels is not None:
@@ -200,8 +216,19 @@ class RAU:
             if labels.shape != (c.B,):
                 raise ValueError("labels shape")
             lp = labels.ctypes.data
+        if image_of is not None:
+            L.check(self._lib.rau_set_batch_images(self._h, feats.ctypes.data, feat16.FEAT_TYPES[ft], n_images,
+                                                   image_of.ctypes.data, tokens.ctypes.data, lens.ctypes.data,
+                                                   lp))
+            return
         L.check(self._lib.rau_set_batch_typed(self._h, feats.ctypes.data, feat16.FEAT_TYPES[ft],
                                               tokens.ctypes.data, lens.ctypes.data, lp))
+
+    def batch_images(self) -> int:
+        """0 for a plain resident batch, else the number of maps in its image table."""
+        v = C.c_int()
+        L.check(self._lib.rau_batch_images(self._h, C.byref(v)))
+        return v.value
 
     def batch_feat_type(self) -> str:
         """Element type of the resident batch's feature map."""
@@ -228,11 +255,22 @@ class RAU:
                 "labels": view(p[3], c.B, C.c_int32, np.int32, (c.B,))}
 
     def set_batch_async(self, slot, feats=None, tokens=None, lens=None, labels=None, has_labels=True,
-                        feat_type=None):
+                        feat_type=None, image_of=None, n_images=None):
         """Enqueue the upload of a batch into `slot` on the copy stream and return.  Arrays left None
         are taken from the slot's staging (filled in place through batch_slot).  feat_type: as in
-        set_batch; with feats None it names what the staging holds (default "f32")."""
+        set_batch; with feats None it names what the staging holds (default "f32").
+        image_of [B]: the batch carries an image table (see set_batch) of feats.shape[0] maps, or, with
+        feats None, of the n_images maps at the start of the slot's staging; only those are uploaded."""
         c = self.cfg
+        nmaps = c.B
+        if image_of is not None:
+            if feats is None:
+                image_of = np.ascontiguousarray(image_of, np.int32)
+                if image_of.shape != (c.B,) or n_images is None:
+                    raise ValueError("an in-place image table needs image_of [B] and n_images")
+                nmaps = int(n_images)
+            else:
+                nmaps, image_of = self._image_index(np.asarray(feats), image_of)
         if feats is None:
             ft = feat16.check_name(feat_type or "f32")
         else:
@@ -245,10 +283,15 @@ class RAU:
             if a.size != n:
                 raise ValueError("batch shapes do not match the config")
             return a.ctypes.data, a
-        fp, fk = ptr(feats, feat16.dtype_of(ft), c.B * c.D * c.S)
+        fp, fk = ptr(feats, feat16.dtype_of(ft), nmaps * c.D * c.S)
         tp, tk = ptr(tokens, np.int32, c.T * c.B)
         lp, lk = ptr(lens, np.int32, c.B)
         yp, yk = ptr(labels, np.int32, c.B)
+        if image_of is not None:
+            L.check(self._lib.rau_set_batch_async_images(self._h, slot, fp, feat16.FEAT_TYPES[ft], nmaps,
+                                                         image_of.ctypes.data, tp, lp, yp,
+                                                         int(bool(has_labels))))
+            return
         L.check(self._lib.rau_set_batch_async_typed(self._h, slot, fp, feat16.FEAT_TYPES[ft], tp, lp, yp,
                                                     int(bool(has_labels))))
 

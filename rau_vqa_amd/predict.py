@@ -67,26 +67,27 @@ def answers(tab_pred, mc_ans=None):
     return oe, mc
 
 
-def predict_result(rau, feats, tokens, lens, mc_ans=None, select_att_state=None):
+def predict_result(rau, feats, tokens, lens, mc_ans=None, select_att_state=None, image_of=None):
     """SS:633-705 + SS:877-900 for one batch: returns dict(tab_pred, tab_att, oe, mc).
     select_att_state: see merge_hops (carry tab_att[-1] from batch to batch to reproduce the
-    reference's never-zeroed test_select_att)."""
+    reference's never-zeroed test_select_att).  image_of: feats is an image table (RAU.set_batch)."""
     rau.evaluate()
-    rau.set_batch(feats, tokens, lens, None)
+    rau.set_batch(feats, tokens, lens, None, image_of=image_of)
     rau.forward()
     tab_pred, tab_att = merge_hops(rau.logits(), rau.dopred(), rau.attention(), select_att_state)
     oe, mc = answers(tab_pred, mc_ans)
     return {"tab_pred": tab_pred, "tab_att": tab_att, "oe": oe, "mc": mc}
 
 
-def predict_result_device(rau, feats, tokens, lens, mc_ans=None, select_att_state=None, tabs=True):
+def predict_result_device(rau, feats, tokens, lens, mc_ans=None, select_att_state=None, tabs=True,
+                          image_of=None):
     """predict_result with the merges, the MC masking and the answers done on the device
     (rau_predict): same keys, same values bit for bit.  The select attention row comes back without
     the reference's carried test_select_att; select_att_state is added here, as merge_hops does.
     tabs=False skips downloading the per-hop logits and maps: tab_pred / tab_att are then None and
-    only the answers (and nothing of [H, B, K]) cross PCIe."""
+    only the answers (and nothing of [H, B, K]) cross PCIe.  image_of: as in predict_result."""
     rau.evaluate()
-    rau.set_batch(feats, tokens, lens, None)
+    rau.set_batch(feats, tokens, lens, None, image_of=image_of)
     rau.forward()
     oe, mc = rau.predict(mc_ans)
     if not tabs:
