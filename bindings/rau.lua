@@ -56,6 +56,16 @@ int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int fe
                                const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
                                const int32_t* labels, int has_labels);
 int rau_batch_images(rau_ctx* ctx, int* n_images);
+int rau_bank_create(rau_ctx* ctx, int32_t capacity, int feat_type);
+int rau_bank_destroy(rau_ctx* ctx);
+int rau_bank_info(rau_ctx* ctx, int32_t* capacity, int* feat_type, int32_t* rows_filled);
+int rau_bank_put(rau_ctx* ctx, int32_t first, int32_t count, const void* feats, int src_type);
+int rau_bank_get(rau_ctx* ctx, int32_t first, int32_t count, void* feats);
+int rau_set_batch_bank(rau_ctx* ctx, int n_images, const int32_t* bank_rows, const int32_t* image_of,
+                       const int32_t* tokens, const int32_t* lens, const int32_t* labels);
+int rau_set_batch_async_bank(rau_ctx* ctx, int slot, int n_images, const int32_t* bank_rows,
+                             const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                             const int32_t* labels, int has_labels);
 int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_host,
                    int32_t** lens_host, int32_t** labels_host);
 int rau_set_batch_async(rau_ctx* ctx, int slot, const float* feats, const int32_t* tokens,
@@ -230,6 +240,33 @@ function RAU:setBatchImages(feats, image_of, x, x_len, y, slot, has_labels)
   end
 end
 -- 0 for a plain resident batch, else the number of maps in its image table
+-- Feature bank: every image's map once in device memory (rau_bank_*).  bankCreate(capacity, 'f32' | 'f16' |
+-- 'bf16'); bankPut(first, feats) takes a Float/HalfTensor [n,D,W,H] into the 1-based rows first .. first+n-1
+-- (FloatTensors into a 16-bit bank are narrowed on the device).
+function RAU:bankCreate(capacity, feat_type)
+  check(C.rau_bank_create(self.h, capacity, FEAT[feat_type or 'f32']))
+end
+function RAU:bankPut(first, feats)
+  local ft = torch.type(feats) == 'torch.HalfTensor' and FEAT.f16 or FEAT.f32
+  check(C.rau_bank_put(self.h, first - 1, feats:size(1), feats:data(), ft))
+end
+function RAU:bankDestroy()
+  check(C.rau_bank_destroy(self.h))
+end
+-- setBatchImages with the table taken from the bank: rows [N] Int/LongTensor of 1-BASED bank rows, image_of [B]
+-- 1-based positions in `rows`.  No feature map is read, staged or uploaded.  slot = nil: the synchronous form.
+function RAU:setBatchBank(rows, image_of, x, x_len, y, slot, has_labels)
+  local r = rows:int():add(-1)
+  local idx = image_of:int():add(-1)
+  if slot then
+    check(C.rau_set_batch_async_bank(self.h, slot, r:size(1), r:data(), idx:data(), x:data(), x_len:data(),
+                                     y and y:data() or nil, (has_labels == false) and 0 or 1))
+  else
+    check(C.rau_set_batch_bank(self.h, r:size(1), r:data(), idx:data(), x:data(), x_len:data(),
+                               y and y:data() or nil))
+  end
+end
+
 function RAU:batchImages()
   local n = ffi.new('int[1]')
   check(C.rau_batch_images(self.h, n))

@@ -218,6 +218,49 @@ int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int fe
                                const int32_t* labels, int has_labels);
 int rau_batch_images(rau_ctx* ctx, int* n_images);
 
+/* ---- feature bank: every image's map once in device memory, batches name their images by row ---
+ * A context may own ONE bank of `capacity` maps of D x S elements of feat_type, stored in the layout of the
+ * batch buffers (row pitch S rounded up to a multiple of 4), so a map is one contiguous run; offsets into
+ * the bank are 64-bit (it may exceed 4 GiB).  After the bank has been filled, a batch is tokens, lengths,
+ * labels and ROW NUMBERS: no feature byte is staged or crosses the bus during a step.
+ *   rau_bank_create   a second bank is RAU_ERR_STATE; an allocation that does not fit is RAU_ERR_NOMEM and
+ *                     leaves the context as it was.
+ *   rau_bank_destroy  frees it (rau_destroy does too); a batch drawn from it is no longer resident.
+ *   rau_bank_info     capacity, element type, number of distinct rows written so far (any may be NULL);
+ *                     RAU_ERR_STATE without a bank, like every call below.
+ *   rau_bank_put      host feats [count,D,S] of src_type into rows [first, first+count), in chunks through
+ *                     pinned staging; synchronising.  src_type equal to the bank's type is a copy;
+ *                     RAU_FEAT_F32 into a 16-bit bank is narrowed ON THE DEVICE, round to nearest even: the
+ *                     bits of numpy's float16 conversion (subnormals kept, overflow to infinity) and of
+ *                     bf16 rounding for every finite input.  Any other pair of types is RAU_ERR_INVALID, as
+ *                     is a row range outside [0, capacity).  It first waits for all enqueued work that reads
+ *                     the bank, so it may be called between steps to add or replace rows; a batch that was
+ *                     handed over BEFORE the put and is consumed after it may see either version of a
+ *                     replaced row.
+ *   rau_bank_get      rows [first, first+count) as dense [count,D,S] in the bank's type; synchronising.
+ * rau_set_batch_bank / rau_set_batch_async_bank mean exactly rau_set_batch_images /
+ * rau_set_batch_async_images with feats = bank[bank_rows] ([n_images] host int32) in the bank's element
+ * type: the same mode rules, RAU_ERR_STATE for a backward after an evaluate-mode forward, slot and
+ * rau_use_batch semantics, replay under rau_graph_step without recapture, rau_batch_images and
+ * rau_batch_feat_type; results are BIT-IDENTICAL to that table batch.  The slot form gathers on the copy
+ * stream behind the same events as an upload and touches no feature staging.  The table itself is gathered
+ * when the batch is handed over in evaluate mode (else by the first evaluate-mode forward that wants it);
+ * the consumers of per-sample maps gather those from the bank in one pass, so after a bank batch
+ * rau_batch_feats is defined only once an evaluate-mode forward has run.
+ * Nothing is enqueued on failure: no bank -> RAU_ERR_STATE; n_images outside [1,B], an image_of entry
+ * outside [0,n_images), a row outside [0,capacity) -> RAU_ERR_INVALID; a row that was never written
+ * (host-side record of rau_bank_put) -> RAU_ERR_STATE. */
+int rau_bank_create(rau_ctx* ctx, int32_t capacity, int feat_type);
+int rau_bank_destroy(rau_ctx* ctx);
+int rau_bank_info(rau_ctx* ctx, int32_t* capacity, int* feat_type, int32_t* rows_filled);
+int rau_bank_put(rau_ctx* ctx, int32_t first, int32_t count, const void* feats, int src_type);
+int rau_bank_get(rau_ctx* ctx, int32_t first, int32_t count, void* feats);
+int rau_set_batch_bank(rau_ctx* ctx, int n_images, const int32_t* bank_rows, const int32_t* image_of,
+                       const int32_t* tokens, const int32_t* lens, const int32_t* labels);
+int rau_set_batch_async_bank(rau_ctx* ctx, int slot, int n_images, const int32_t* bank_rows,
+                             const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                             const int32_t* labels, int has_labels);
+
 /* ---- asynchronous, double-buffered upload: SS:434-439 behind the loader's prefetch -------------
  * The reference re-uploads feats / x / x_len / y every iteration (SS:434-439) while its loader's
  * worker thread assembles the next batch (utils/vqa_prepro_loader.lua:931-958).  Here the ctx owns

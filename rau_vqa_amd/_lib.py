@@ -86,6 +86,16 @@ _SIGS = {
     "rau_set_batch_async_images": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "rau_batch_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    # feature bank: maps resident in device memory, batches name their images by row
+    "rau_bank_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int]),
+    "rau_bank_destroy": (C.c_int, [C.c_void_p]),
+    "rau_bank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int32)]),
+    "rau_bank_put": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int]),
+    "rau_bank_get": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "rau_set_batch_bank": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "rau_set_batch_async_bank": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_int]),
     "rau_forward": (C.c_int, [C.c_void_p]),
     "rau_backward": (C.c_int, [C.c_void_p, C.c_void_p]),
     # module-level entry points: device pointers in, pointers to ctx-owned slots out

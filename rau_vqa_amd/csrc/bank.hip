@@ -1,0 +1,117 @@
+// bank.hip -- the two kernels of the device-resident feature bank (rau_bank_*, include/rau.h): the gather
+// of whole maps out of the bank into the batch buffers, and the f32 -> fp16 / bf16 narrowing of rau_bank_put.
+// Both are byte movers bound by HBM; they live in a translation unit of their own so that the code object of
+// kernels.hip is the same with and without them.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace rau {
+
+static inline int grid_for(size_t n, int block = 256, int cap = 256 * 8) {
+  size_t g = (n + block - 1) / block;
+  if (g > (size_t)cap) g = cap;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
+// Feature bank -> batch buffers: out[i] = bank[rows[i]] for i < n, whole maps as above.  The bank may be far
+// larger than 4 GiB: the map's offset is formed in 64 bits from the wave-uniform row number, everything inside
+// a map is addressed relative to it.  rows is a DEVICE index the host has checked against the bank's capacity;
+// `capacity` bounds it once more here so that a stale index can never address outside the allocation.
+template <typename V>
+__global__ __launch_bounds__(256) void k_bank_gather(size_t nvec, const V* __restrict__ bank, int32_t capacity,
+                                                     const int32_t* __restrict__ rows, V* __restrict__ out) {
+  const int i = blockIdx.y;
+  int r = __builtin_amdgcn_readfirstlane(rows[i]);
+  r = min(max(r, 0), capacity - 1);
+  const V* src = bank + (size_t)r * nvec;
+  V* dst = out + (size_t)i * nvec;
+  const size_t step = (size_t)gridDim.x * blockDim.x;
+  size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  // four independent 16-byte loads in flight per lane before the first store
+  for (; v + 3 * step < nvec; v += 4 * step) {
+    const V a = *(src + v), b = *(src + v + step),
+            c = *(src + v + 2 * step), d = *(src + v + 3 * step);
+    dst[v] = a; dst[v + step] = b; dst[v + 2 * step] = c; dst[v + 3 * step] = d;
+  }
+  for (; v < nvec; v += step) dst[v] = *(src + v);
+}
+hipError_t bank_gather(hipStream_t st, int n, size_t map_bytes, const void* bank, int32_t capacity,
+                       const int32_t* rows, void* out) {
+  if (n <= 0 || n > 65535 || capacity <= 0 || !bank || !rows || !out || map_bytes % 8 != 0)
+    return hipErrorInvalidValue;
+  const bool v16 = map_bytes % 16 == 0;
+  const size_t nvec = map_bytes / (v16 ? 16 : 8);
+  const int slices = (int)std::min<size_t>(16, (nvec + 1023) / 1024);
+  const dim3 grid(std::max(slices, 1), n);
+  if (v16)
+    hipLaunchKernelGGL(k_bank_gather<uint4>, grid, dim3(256), 0, st, nvec, static_cast<const uint4*>(bank),
+                       capacity, rows, static_cast<uint4*>(out));
+  else
+    hipLaunchKernelGGL(k_bank_gather<uint2>, grid, dim3(256), 0, st, nvec, static_cast<const uint2*>(bank),
+                       capacity, rows, static_cast<uint2*>(out));
+  return hipGetLastError();
+}
+
+// f32 -> fp16 / bf16, round to nearest even, in integer arithmetic (independent of the wave's denormal and
+// rounding modes): the bits numpy's float16 conversion gives -- subnormals kept, overflow to infinity, NaN stays
+// NaN -- and feat16.bf16_bits' for bf16.
+__device__ __forceinline__ uint32_t narrow_f16_bits(uint32_t x) {
+  const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
+  if (a > 0x7f800000u) return sign | 0x7e00u | ((a >> 13) & 0x1ffu);   // NaN (quiet)
+  if (a >= 0x477ff000u) return sign | 0x7c00u;                          // >= 65520: infinity
+  if (a >= 0x38800000u) {                                               // normal fp16: rebias 127 -> 15
+    const uint32_t r = a - 0x38000000u, rem = r & 0x1fffu;
+    uint32_t h = r >> 13;
+    h += (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ? 1u : 0u;     // a carry runs into the exponent
+    return sign | h;
+  }
+  const uint32_t e = a >> 23;
+  if (e < 102u) return sign;                                            // below 2^-25: +-0
+  const uint32_t m = (a & 0x7fffffu) | 0x800000u, sh = 126u - e;        // subnormal: units of 2^-24, sh in 14..24
+  const uint32_t rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1u);
+  uint32_t h = m >> sh;
+  h += (rem > half || (rem == half && (h & 1u))) ? 1u : 0u;             // may round up to the smallest normal
+  return sign | h;
+}
+__device__ __forceinline__ uint32_t narrow_bf16_bits(uint32_t x) {
+  return (x + (((x >> 16) & 1u) + 0x7fffu)) >> 16;
+}
+// dense f32 rows [rows][SL] -> 16-bit rows at pitch Sp (a multiple of 4), pad columns zero; one thread forms
+// four neighbouring outputs and stores them as 8 bytes
+template <int FT>
+__global__ __launch_bounds__(256) void k_narrow_features(size_t nquad, int SL, int Sp,
+                                                         const float* __restrict__ src, uint2* __restrict__ out) {
+  const int qpr = Sp / 4;   // quads per row
+  for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < nquad; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = q / qpr;
+    const int s0 = (int)(q - r * qpr) * 4;
+    const float* p = src + r * SL + s0;
+    uint32_t h[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t x = s0 + k < SL ? __float_as_uint(p[k]) : 0u;
+      h[k] = (FT == RAU_FEAT_F16 ? narrow_f16_bits(x) : narrow_bf16_bits(x)) & 0xffffu;
+    }
+    out[q] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+  }
+}
+hipError_t narrow_features(hipStream_t st, size_t rows, int SL, int Sp, const float* src, void* out, int ft) {
+  if ((ft != RAU_FEAT_F16 && ft != RAU_FEAT_BF16) || Sp % 4 != 0 || SL > Sp || SL <= 0 || !src || !out)
+    return hipErrorInvalidValue;
+  if (rows == 0) return hipSuccess;
+  const size_t nquad = rows * (Sp / 4);
+  if (ft == RAU_FEAT_F16)
+    hipLaunchKernelGGL(k_narrow_features<RAU_FEAT_F16>, dim3(grid_for(nquad)), dim3(256), 0, st, nquad, SL, Sp, src,
+                       static_cast<uint2*>(out));
+  else
+    hipLaunchKernelGGL(k_narrow_features<RAU_FEAT_BF16>, dim3(grid_for(nquad)), dim3(256), 0, st, nquad, SL, Sp, src,
+                       static_cast<uint2*>(out));
+  return hipGetLastError();
+}
+
+}  // namespace rau

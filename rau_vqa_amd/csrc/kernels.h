@@ -336,6 +336,15 @@ hipError_t widen_features(hipStream_t st, size_t rows, int SL, int Sp, const voi
 // image_of is a DEVICE index whose entries the host has range-checked against the table.
 hipError_t expand_features(hipStream_t st, int nB, size_t map_bytes, const void* table, const int32_t* image_of,
                            void* out);
+// Feature bank -> batch buffers: out[i] = bank[rows[i]] for i < n (n <= 65535), maps of map_bytes bytes as in
+// expand_features; map offsets into the bank are 64-bit.  rows is a DEVICE index the host has checked; the
+// kernel clamps it into [0, capacity) all the same.
+hipError_t bank_gather(hipStream_t st, int n, size_t map_bytes, const void* bank, int32_t capacity,
+                       const int32_t* rows, void* out);
+// out[r][s] = narrow(src[r][s]) for s < SL, 0 for SL <= s < Sp: dense f32 rows into 16-bit rows (ft =
+// RAU_FEAT_F16 / RAU_FEAT_BF16) at pitch Sp (% 4 == 0), round to nearest even -- the bits of numpy's float16
+// conversion (subnormals, overflow to infinity) and of feat16.bf16_bits
+hipError_t narrow_features(hipStream_t st, size_t rows, int SL, int Sp, const float* src, void* out, int ft);
 // dst[n] += sum_rows X[row*ld + n]   (two-stage, deterministic; tmp >= 32*N floats)
 hipError_t colsum_acc(hipStream_t st, int rows, int N, const float* X, long ld, float* dst,
                       float* tmp);

@@ -85,6 +85,12 @@ struct BatchSlot {
   int n_images = 0;
   int32_t* image_of_d = nullptr;                            // device [B]
   int32_t* image_of_h = nullptr;                            // pinned host [B] (asynchronous path)
+  // bank batch (rau_set_batch_bank): a table batch whose maps are rows of the ctx's feature bank.  bank_idx_d holds
+  // rows[n_images] (padded to B) and then rows[image_of[b]] for every sample, so both gathers are one indexed copy.
+  bool bank = false;
+  bool table_ok = false;            // `feats` holds the gathered table (else only the index does: train-mode upload)
+  int32_t* bank_idx_d = nullptr;    // device [2B]
+  int32_t* bank_idx_h = nullptr;    // pinned host [2B]
   int32_t *tokens_h = nullptr, *lens_p = nullptr, *labels_h = nullptr;
   int32_t *utok_h = nullptr, *ustart_h = nullptr, *upos_h = nullptr;
   std::vector<int32_t> lens;
@@ -142,6 +148,15 @@ struct rau_ctx {
   bool have_batch = false, have_labels = false;
   int nuniq = 0;
   int32_t *utok = nullptr, *ustart = nullptr, *upos = nullptr;
+  // feature bank (rau_bank_*): every image's map once, in the batch buffers' layout [capacity][D][Sp]
+  void* bank = nullptr;
+  int32_t bank_cap = 0, bank_filled = 0;
+  int bank_type = RAU_FEAT_F32;
+  std::vector<uint8_t> bank_written;   // host record: row has been put
+  void* bank_pin[2] = {nullptr, nullptr};   // pinned staging of rau_bank_put, bank_chunk bytes each
+  float* bank_stage = nullptr;              // device: one chunk of f32 maps on their way to a 16-bit bank
+  size_t bank_chunk = 0;
+  hipEvent_t bank_ev[2] = {nullptr, nullptr};
   // asynchronous, double-buffered upload (allocated at the first rau_batch_slot / rau_set_batch_async)
   BatchSlot slot[2];
   uint64_t slot_serial[2] = {0, 0};   // uploads into each slot's device buffers so far

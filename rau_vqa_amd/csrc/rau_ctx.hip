@@ -32,6 +32,7 @@ static int prof_collect(rau_ctx* ctx) {
   HIPC(hipStreamSynchronize(ctx->st));
   HIPC(hipStreamSynchronize(ctx->st2));
   HIPC(hipStreamSynchronize(ctx->st3));
+  if (ctx->stc) HIPC(hipStreamSynchronize(ctx->stc));   // the bank gather of a slot upload is bracketed there
   FILE* tl = nullptr;   // RAU_PROF_TIMELINE=path: per-launch (class, stream, start, end) in ms
   if (const char* p = std::getenv("RAU_PROF_TIMELINE")) tl = std::fopen(p, "a");
   for (auto& r : ctx->precs) {
@@ -538,6 +539,7 @@ void rau_destroy(rau_ctx* ctx) {
   split_ws_unregister(ctx->slab);
   split_ws_unregister(ctx->slab2);
   split_ws_unregister(ctx->slab3);
+  rau_bank_destroy(ctx);
   for (void* p : ctx->allocs) hipFree(p);
   if (ctx->hopw_h) hipHostFree(ctx->hopw_h);
   for (auto& r : ctx->precs) {
@@ -558,6 +560,7 @@ void rau_destroy(rau_ctx* ctx) {
   for (BatchSlot& s : ctx->slot) {
     if (s.feats_h) hipHostFree(s.feats_h);
     if (s.image_of_h) hipHostFree(s.image_of_h);
+    if (s.bank_idx_h) hipHostFree(s.bank_idx_h);
     if (s.uploaded) hipEventDestroy(s.uploaded);
     if (s.consumed) hipEventDestroy(s.consumed);
   }
@@ -758,14 +761,24 @@ int index_batch(const rau_config& c, const int32_t* tokens, const int32_t* lens,
 int enqueue_batch(rau_ctx* ctx, hipStream_t s, const BatchSlot& d, const void* feats, int feat_type,
                   int prev_type, const int32_t* tokens, const int32_t* lens, const int32_t* labels,
                   const int32_t* utok, const int32_t* ustart, const int32_t* upos, int n_images = 0,
-                  const int32_t* image_of = nullptr) {
+                  const int32_t* image_of = nullptr, const int32_t* bank_idx = nullptr, bool bank_table = false) {
   const rau_config& c = ctx->cfg;
   const size_t TB = (size_t)c.T * c.B, es = feat_type == RAU_FEAT_F32 ? 4 : 2;
   const size_t maps = n_images > 0 ? (size_t)n_images : (size_t)c.B;   // only these cross the bus
   if (n_images > 0) HIPC(hipMemcpyAsync(d.image_of_d, image_of, (size_t)c.B * 4, hipMemcpyHostToDevice, s));
   // pitched rows of another element size leave data in this type's pad columns: zero them first
-  if (feats && ctx->Sp != c.S && feat_type != prev_type)
+  if ((feats || bank_idx) && ctx->Sp != c.S && feat_type != prev_type)
     HIPC(hipMemsetAsync(d.feats, 0, (size_t)c.B * c.D * ctx->Sp * sizeof(float), s));
+  // bank batch (feats == nullptr): only the two row indices cross the bus; the table is gathered inside device
+  // memory behind them, whole maps with their (zero) pad columns
+  if (bank_idx) {
+    HIPC(hipMemcpyAsync(d.bank_idx_d, bank_idx, 2 * (size_t)c.B * 4, hipMemcpyHostToDevice, s));
+    if (bank_table) {
+      const size_t map_bytes = (size_t)c.D * ctx->Sp * es;
+      RUNS(s, "bank_gather", 0, 2.0 * n_images * map_bytes,
+           bank_gather(s, n_images, map_bytes, ctx->bank, ctx->bank_cap, d.bank_idx_d, d.feats));
+    }
+  }
   if (feats && ctx->Sp == c.S)   // dense on both sides: one linear copy (a DMA-engine transfer, no blit kernel)
     HIPC(hipMemcpyAsync(d.feats, feats, maps * c.D * c.S * es, hipMemcpyHostToDevice, s));
   else if (feats)   // rows of S positions into rows of Sp (pad columns stay zero)
@@ -803,11 +816,37 @@ int check_table(const rau_config& c, int n_images, const int32_t* image_of) {
     NEED(image_of[b] >= 0 && image_of[b] < n_images, "image_of[%d]=%d out of [0,%d)", b, image_of[b], n_images);
   return RAU_OK;
 }
+// bank batch: a bank exists, the table is valid, every row lies in the bank and has been written; fills
+// idx[2B] = rows (padded with rows[0]) | rows[image_of[b]]
+int check_bank_rows(rau_ctx* ctx, int n_images, const int32_t* rows, const int32_t* image_of, int32_t* idx) {
+  const rau_config& c = ctx->cfg;
+  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_set_batch_bank: the context has no feature bank (rau_bank_create)");
+  NEED(rows, "null bank_rows");
+  if (int rc = check_table(c, n_images, image_of)) return rc;
+  for (int n = 0; n < n_images; ++n)
+    NEED(rows[n] >= 0 && rows[n] < ctx->bank_cap, "bank_rows[%d]=%d out of [0,%d)", n, rows[n], ctx->bank_cap);
+  for (int n = 0; n < n_images; ++n)
+    if (!ctx->bank_written[rows[n]])
+      return fail(RAU_ERR_STATE, "bank_rows[%d]=%d has never been written (rau_bank_put)", n, rows[n]);
+  for (int b = 0; b < c.B; ++b) {
+    idx[b] = rows[b < n_images ? b : 0];
+    idx[c.B + b] = rows[image_of[b]];
+  }
+  return RAU_OK;
+}
 // first table batch of a slot: its device index (and pinned staging of it on the asynchronous path) and the
 // ctx's buffer of expanded per-sample maps
-int ensure_table(rau_ctx* ctx, int si, bool pinned) {
+int ensure_table(rau_ctx* ctx, int si, bool pinned, bool bank = false) {
   const rau_config& c = ctx->cfg;
   BatchSlot& s = ctx->slot[si];
+  if (bank && !s.bank_idx_d)
+    if (int rc = dalloc(ctx, &s.bank_idx_d, 2 * (size_t)c.B)) return rc;
+  if (bank && pinned && !s.bank_idx_h) {
+    void* h = nullptr;
+    hipError_t e = hipHostMalloc(&h, 2 * (size_t)c.B * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(bank index staging): %s", hipGetErrorString(e));
+    s.bank_idx_h = static_cast<int32_t*>(h);
+  }
   if (!s.image_of_d)
     if (int rc = dalloc(ctx, &s.image_of_d, (size_t)c.B)) return rc;
   if (!ctx->feats_x)
@@ -831,7 +870,7 @@ int ensure_async(rau_ctx* ctx) {
   s0.utok = ctx->utok; s0.ustart = ctx->ustart; s0.upos = ctx->upos;
   s0.lens = ctx->lens_h; s0.max_len = ctx->max_len; s0.nuniq = ctx->nuniq;
   s0.have = ctx->have_batch; s0.have_labels = ctx->have_labels; s0.feat_type = ctx->feat_type;
-  s0.n_images = ctx->n_images;
+  s0.n_images = ctx->n_images;   // (s0.bank / table_ok / bank_idx_d are kept in the slot itself)
   BatchSlot& s1 = ctx->slot[1];
   if (int rc = dalloc(ctx, &s1.feats, (size_t)c.B * c.D * ctx->Sp)) return rc;
   if (int rc = dalloc(ctx, &s1.tokens, TB)) return rc;
@@ -877,14 +916,19 @@ int rau_set_batch_typed(rau_ctx* ctx, const void* feats, int feat_type, const in
   return rau_set_batch_images(ctx, feats, feat_type, 0, nullptr, tokens, lens, labels);
 }
 
-// n_images == 0 with image_of == NULL is the plain batch (what rau_set_batch_typed passes)
-int rau_set_batch_images(rau_ctx* ctx, const void* feats, int feat_type, int n_images, const int32_t* image_of,
-                         const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
-  NEED(ctx && tokens && lens, "null argument");
-  NEED(feat_type_ok(feat_type), "rau_set_batch: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)", feat_type);
+}  // extern "C"
+
+namespace {
+// rau_set_batch_images, or (bank_rows != nullptr, feats == nullptr) the same batch with its table drawn from the bank
+int set_batch_sync(rau_ctx* ctx, const void* feats, int feat_type, int n_images, const int32_t* image_of,
+                   const int32_t* tokens, const int32_t* lens, const int32_t* labels, const int32_t* bank_rows) {
   const rau_config& c = ctx->cfg;
   const bool table = n_images != 0 || image_of != nullptr;
-  if (table) {
+  std::vector<int32_t> bidx;
+  if (bank_rows) {
+    bidx.resize(2 * (size_t)c.B);
+    if (int rc = check_bank_rows(ctx, n_images, bank_rows, image_of, bidx.data())) return rc;
+  } else if (table) {
     if (int rc = check_table(c, n_images, image_of)) return rc;
   }
   const size_t TB = (size_t)c.T * c.B;
@@ -893,20 +937,27 @@ int rau_set_batch_images(rau_ctx* ctx, const void* feats, int feat_type, int n_i
   if (int rc = index_batch(c, tokens, lens, labels, utok.data(), ustart.data(), upos.data(), &max_len, &nuniq))
     return rc;
   if (table)
-    if (int rc = ensure_table(ctx, ctx->cur_slot, false)) return rc;
+    if (int rc = ensure_table(ctx, ctx->cur_slot, false, bank_rows != nullptr)) return rc;
   BatchSlot d;   // the CURRENT device buffers (slot 0 unless rau_use_batch switched)
   d.image_of_d = ctx->slot[ctx->cur_slot].image_of_d;
+  d.bank_idx_d = ctx->slot[ctx->cur_slot].bank_idx_d;
+  // the table itself is wanted by the evaluate-mode forward only; a train-mode step gathers per-sample maps
+  // straight from the bank (batch_maps), and a later evaluate-mode forward gathers the table then
+  const bool bank_table = bank_rows && ctx->mode == RAU_MODE_EVAL;
   d.feats = ctx->feats; d.tokens = ctx->tokens; d.lens_d = ctx->lens_d; d.labels_d = ctx->labels_d;
   d.utok = ctx->utok; d.ustart = ctx->ustart; d.upos = ctx->upos;
   if (ctx->async_ready && ctx->slot[ctx->cur_slot].upload_pending)   // an async upload into the same buffers
     HIPC(hipStreamWaitEvent(ctx->st, ctx->slot[ctx->cur_slot].uploaded, 0));
   ++ctx->slot_serial[ctx->cur_slot];
   if (int rc = enqueue_batch(ctx, ctx->st, d, feats, feat_type, ctx->feat_type, tokens, lens, labels,
-                             utok.data(), ustart.data(), upos.data(), table ? n_images : 0, image_of))
+                             utok.data(), ustart.data(), upos.data(), table ? n_images : 0, image_of,
+                             bank_rows ? bidx.data() : nullptr, bank_table))
     return rc;
   HIPC(hipStreamSynchronize(ctx->st));   // the caller's (pageable) buffers are free on return
   ctx->feat_type = feat_type;
   ctx->n_images = ctx->slot[ctx->cur_slot].n_images = table ? n_images : 0;
+  ctx->slot[ctx->cur_slot].bank = bank_rows != nullptr;
+  ctx->slot[ctx->cur_slot].table_ok = bank_table;
   ctx->lens_h.assign(lens, lens + c.B);
   ctx->max_len = max_len;
   ctx->nuniq = nuniq;
@@ -920,6 +971,25 @@ int rau_set_batch_images(rau_ctx* ctx, const void* feats, int feat_type, int n_i
     s.feat_type = feat_type;
   }
   return RAU_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// n_images == 0 with image_of == NULL is the plain batch (what rau_set_batch_typed passes)
+int rau_set_batch_images(rau_ctx* ctx, const void* feats, int feat_type, int n_images, const int32_t* image_of,
+                         const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
+  NEED(ctx && tokens && lens, "null argument");
+  NEED(feat_type_ok(feat_type), "rau_set_batch: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)", feat_type);
+  return set_batch_sync(ctx, feats, feat_type, n_images, image_of, tokens, lens, labels, nullptr);
+}
+
+int rau_set_batch_bank(rau_ctx* ctx, int n_images, const int32_t* bank_rows, const int32_t* image_of,
+                       const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
+  NEED(ctx && tokens && lens, "null argument");
+  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_set_batch_bank: the context has no feature bank (rau_bank_create)");
+  NEED(bank_rows, "null bank_rows");
+  return set_batch_sync(ctx, nullptr, ctx->bank_type, n_images, image_of, tokens, lens, labels, bank_rows);
 }
 
 int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_host,
@@ -950,22 +1020,27 @@ int rau_set_batch_async_typed(rau_ctx* ctx, int slot, const void* feats, int fea
   return rau_set_batch_async_images(ctx, slot, feats, feat_type, 0, nullptr, tokens, lens, labels, has_labels);
 }
 
-// n_images == 0 with image_of == NULL is the plain batch (what rau_set_batch_async_typed passes)
-int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int feat_type, int n_images,
-                               const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
-                               const int32_t* labels, int has_labels) {
-  NEED(ctx, "null ctx");
-  NEED(feat_type_ok(feat_type), "rau_set_batch_async: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)",
-       feat_type);
+}  // extern "C"
+
+namespace {
+// rau_set_batch_async_images, or (bank_rows != nullptr, feats == nullptr) the same batch with its table drawn from
+// the bank: nothing is written to the slot's feature staging and no feature byte crosses the bus
+int set_batch_slot(rau_ctx* ctx, int slot, const void* feats, int feat_type, int n_images,
+                   const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                   const int32_t* labels, int has_labels, const int32_t* bank_rows) {
   NEED(slot == 0 || slot == 1, "rau_set_batch_async: slot %d (0 or 1)", slot);
   const rau_config& c = ctx->cfg;
   const bool table = n_images != 0 || image_of != nullptr;
-  if (table) {
+  std::vector<int32_t> bidx;
+  if (bank_rows) {
+    bidx.resize(2 * (size_t)c.B);
+    if (int rc = check_bank_rows(ctx, n_images, bank_rows, image_of, bidx.data())) return rc;
+  } else if (table) {
     if (int rc = check_table(c, n_images, image_of)) return rc;
   }
   if (int rc = ensure_async(ctx)) return rc;
   if (table)
-    if (int rc = ensure_table(ctx, slot, true)) return rc;
+    if (int rc = ensure_table(ctx, slot, true, bank_rows != nullptr)) return rc;
   BatchSlot& s = ctx->slot[slot];
   if (slot == ctx->cur_slot && ctx->fwd_done)
     return fail(RAU_ERR_STATE, "rau_set_batch_async: slot %d is the current batch of a forward pass whose "
@@ -988,6 +1063,8 @@ int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int fe
   if (lens && lens != s.lens_p) std::memcpy(s.lens_p, lens, (size_t)c.B * 4);
   if (labels && labels != s.labels_h) std::memcpy(s.labels_h, labels, (size_t)c.B * 4);
   if (table) std::memcpy(s.image_of_h, image_of, (size_t)c.B * 4);
+  if (bank_rows) std::memcpy(s.bank_idx_h, bidx.data(), 2 * (size_t)c.B * 4);
+  const bool bank_table = bank_rows && ctx->mode == RAU_MODE_EVAL;   // (see set_batch_sync)
   const bool with_labels = labels != nullptr || has_labels != 0;
   int max_len = 0, nuniq = 0;
   if (int rc = index_batch(c, s.tokens_h, s.lens_p, with_labels ? s.labels_h : nullptr, s.utok_h, s.ustart_h,
@@ -1000,14 +1077,16 @@ int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int fe
   }
   if (s.consumed_valid) HIPC(hipStreamWaitEvent(ctx->stc, s.consumed, 0));
   ++ctx->slot_serial[slot];
-  if (int rc = enqueue_batch(ctx, ctx->stc, s, s.feats_h, feat_type, s.feat_type, s.tokens_h, s.lens_p,
-                             with_labels ? s.labels_h : nullptr, s.utok_h, s.ustart_h, s.upos_h,
-                             table ? n_images : 0, s.image_of_h))
+  if (int rc = enqueue_batch(ctx, ctx->stc, s, bank_rows ? nullptr : s.feats_h, feat_type, s.feat_type, s.tokens_h,
+                             s.lens_p, with_labels ? s.labels_h : nullptr, s.utok_h, s.ustart_h, s.upos_h,
+                             table ? n_images : 0, s.image_of_h, bank_rows ? s.bank_idx_h : nullptr, bank_table))
     return rc;
   HIPC(hipEventRecord(s.uploaded, ctx->stc));
   s.upload_pending = true;
   s.feat_type = feat_type;
   s.n_images = table ? n_images : 0;
+  s.bank = bank_rows != nullptr;
+  s.table_ok = bank_table;
   s.lens.assign(s.lens_p, s.lens_p + c.B);
   s.max_len = max_len;
   s.nuniq = nuniq;
@@ -1018,6 +1097,29 @@ int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int fe
     HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
   }
   return RAU_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// n_images == 0 with image_of == NULL is the plain batch (what rau_set_batch_async_typed passes)
+int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int feat_type, int n_images,
+                               const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                               const int32_t* labels, int has_labels) {
+  NEED(ctx, "null ctx");
+  NEED(feat_type_ok(feat_type), "rau_set_batch_async: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)",
+       feat_type);
+  return set_batch_slot(ctx, slot, feats, feat_type, n_images, image_of, tokens, lens, labels, has_labels, nullptr);
+}
+
+int rau_set_batch_async_bank(rau_ctx* ctx, int slot, int n_images, const int32_t* bank_rows,
+                             const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                             const int32_t* labels, int has_labels) {
+  NEED(ctx, "null ctx");
+  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_set_batch_async_bank: the context has no feature bank (rau_bank_create)");
+  NEED(bank_rows, "null bank_rows");
+  return set_batch_slot(ctx, slot, nullptr, ctx->bank_type, n_images, image_of, tokens, lens, labels, has_labels,
+                        bank_rows);
 }
 
 int rau_use_batch(rau_ctx* ctx, int slot) {
@@ -1058,6 +1160,166 @@ int rau_batch_images(rau_ctx* ctx, int* n_images) {
   return RAU_OK;
 }
 
+// ------------------------------------------------------------------ feature bank
+// Every enqueued reader of the bank (the gathers: copy stream and chain stream) has finished.
+static int bank_quiesce(rau_ctx* ctx) {
+  if (ctx->stc) HIPC(hipStreamSynchronize(ctx->stc));
+  HIPC(hipStreamSynchronize(ctx->st));
+  return RAU_OK;
+}
+static size_t bank_map_bytes(const rau_ctx* ctx) {
+  return (size_t)ctx->cfg.D * ctx->Sp * (ctx->bank_type == RAU_FEAT_F32 ? 4 : 2);
+}
+
+int rau_bank_create(rau_ctx* ctx, int32_t capacity, int feat_type) {
+  NEED(ctx, "null ctx");
+  NEED(feat_type_ok(feat_type), "rau_bank_create: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)", feat_type);
+  NEED(capacity >= 1, "rau_bank_create: capacity %d", capacity);
+  if (ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_create: the context already has a bank (rau_bank_destroy first)");
+  const size_t bytes = (size_t)capacity * ctx->cfg.D * ctx->Sp * (feat_type == RAU_FEAT_F32 ? 4 : 2);
+  void* d = nullptr;
+  hipError_t e = hipMalloc(&d, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();   // the failed allocation is reported here, not by the next launch
+    return fail(RAU_ERR_NOMEM, "rau_bank_create: hipMalloc(%zu bytes for %d maps) failed: %s", bytes, capacity,
+                hipGetErrorString(e));
+  }
+  e = hipMemsetAsync(d, 0, bytes, ctx->st);   // pad columns stay zero for the bank's lifetime
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
+  if (e != hipSuccess) {
+    hipFree(d);
+    return fail(RAU_ERR_DEVICE, "rau_bank_create: clearing the bank: %s", hipGetErrorString(e));
+  }
+  ctx->bank = d;
+  ctx->bank_cap = capacity;
+  ctx->bank_type = feat_type;
+  ctx->bank_filled = 0;
+  ctx->bank_written.assign((size_t)capacity, 0);
+  return RAU_OK;
+}
+
+int rau_bank_destroy(rau_ctx* ctx) {
+  NEED(ctx, "null ctx");
+  if (!ctx->bank) return RAU_OK;
+  if (int rc = bank_quiesce(ctx)) return rc;
+  // captured steps of bank batches hold the bank's address
+  for (auto it = ctx->graphs.begin(); it != ctx->graphs.end();)
+    if ((it->first >> 35) & 1) { hipGraphExecDestroy(it->second); it = ctx->graphs.erase(it); } else ++it;
+  for (int si = 0; si < 2; ++si) {   // a batch drawn from the bank is gone with it
+    BatchSlot& s = ctx->slot[si];
+    if (!s.bank) continue;
+    s.bank = s.table_ok = s.have = false;
+    if (si == ctx->cur_slot) ctx->have_batch = ctx->fwd_done = false;
+  }
+  hipFree(ctx->bank);
+  if (ctx->bank_stage) hipFree(ctx->bank_stage);
+  for (int k = 0; k < 2; ++k) {
+    if (ctx->bank_pin[k]) hipHostFree(ctx->bank_pin[k]);
+    if (ctx->bank_ev[k]) hipEventDestroy(ctx->bank_ev[k]);
+    ctx->bank_pin[k] = nullptr;
+    ctx->bank_ev[k] = nullptr;
+  }
+  ctx->bank = nullptr;
+  ctx->bank_stage = nullptr;
+  ctx->bank_chunk = 0;
+  ctx->bank_cap = ctx->bank_filled = 0;
+  ctx->bank_written.clear();
+  ctx->x_valid = false;
+  return RAU_OK;
+}
+
+int rau_bank_info(rau_ctx* ctx, int32_t* capacity, int* feat_type, int32_t* rows_filled) {
+  NEED(ctx, "null ctx");
+  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_info: the context has no feature bank");
+  if (capacity) *capacity = ctx->bank_cap;
+  if (feat_type) *feat_type = ctx->bank_type;
+  if (rows_filled) *rows_filled = ctx->bank_filled;
+  return RAU_OK;
+}
+
+int rau_bank_put(rau_ctx* ctx, int32_t first, int32_t count, const void* feats, int src_type) {
+  NEED(ctx && feats, "null argument");
+  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_put: the context has no feature bank (rau_bank_create)");
+  NEED(feat_type_ok(src_type), "rau_bank_put: src_type %d (RAU_FEAT_F32 | _F16 | _BF16)", src_type);
+  NEED(src_type == ctx->bank_type || src_type == RAU_FEAT_F32,
+       "rau_bank_put: maps of type %d into a bank of type %d (equal types, or f32 into a 16-bit bank)", src_type,
+       ctx->bank_type);
+  NEED(first >= 0 && count >= 1 && (int64_t)first + count <= ctx->bank_cap, "rau_bank_put: rows [%d,%d) out of [0,%d)",
+       first, first + count, ctx->bank_cap);
+  const rau_config& c = ctx->cfg;
+  const bool narrow = src_type != ctx->bank_type;
+  const size_t ses = src_type == RAU_FEAT_F32 ? 4 : 2, src_map = (size_t)c.D * c.S * ses, map_bytes = bank_map_bytes(ctx);
+  const size_t bes = ctx->bank_type == RAU_FEAT_F32 ? 4 : 2;
+  if (!ctx->bank_chunk) {   // staging sized for f32 sources: 32 MiB, at least one map
+    const size_t chunk = std::max<size_t>((size_t)32 << 20, (size_t)c.D * c.S * 4);
+    for (int k = 0; k < 2; ++k) {
+      if (!ctx->bank_pin[k]) {
+        hipError_t e = hipHostMalloc(&ctx->bank_pin[k], chunk, hipHostMallocDefault);
+        if (e != hipSuccess) {
+          ctx->bank_pin[k] = nullptr;
+          return fail(RAU_ERR_NOMEM, "rau_bank_put: hipHostMalloc(%zu bytes staging): %s", chunk, hipGetErrorString(e));
+        }
+      }
+      if (!ctx->bank_ev[k]) HIPC(hipEventCreateWithFlags(&ctx->bank_ev[k], hipEventDisableTiming));
+    }
+    ctx->bank_chunk = chunk;
+  }
+  if (narrow && !ctx->bank_stage) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->bank_stage), ctx->bank_chunk);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->bank_stage = nullptr;
+      return fail(RAU_ERR_NOMEM, "rau_bank_put: hipMalloc(%zu bytes staging): %s", ctx->bank_chunk, hipGetErrorString(e));
+    }
+  }
+  if (int rc = bank_quiesce(ctx)) return rc;   // enqueued gathers read the rows being replaced
+  const int32_t per = (int32_t)std::min<size_t>(ctx->bank_chunk / src_map, (size_t)count);
+  hipStream_t st = ctx->st;
+  bool used[2] = {false, false};
+  int k = 0;
+  for (int32_t r0 = 0; r0 < count; r0 += per, k ^= 1) {
+    const int32_t n = std::min(per, count - r0);
+    if (used[k]) HIPC(hipEventSynchronize(ctx->bank_ev[k]));   // the staging's last copy has left it
+    std::memcpy(ctx->bank_pin[k], static_cast<const char*>(feats) + (size_t)r0 * src_map, (size_t)n * src_map);
+    char* dst = static_cast<char*>(ctx->bank) + (size_t)(first + r0) * map_bytes;
+    if (narrow) {
+      // (one device staging: the stream orders the next chunk's copy behind this chunk's kernel)
+      HIPC(hipMemcpyAsync(ctx->bank_stage, ctx->bank_pin[k], (size_t)n * src_map, hipMemcpyHostToDevice, st));
+      RUN("bank_narrow", 0, (double)n * (src_map + map_bytes),
+          narrow_features(st, (size_t)n * c.D, c.S, ctx->Sp, ctx->bank_stage, dst, ctx->bank_type));
+    } else if (ctx->Sp == c.S) {
+      HIPC(hipMemcpyAsync(dst, ctx->bank_pin[k], (size_t)n * src_map, hipMemcpyHostToDevice, st));
+    } else {
+      HIPC(hipMemcpy2DAsync(dst, (size_t)ctx->Sp * bes, ctx->bank_pin[k], (size_t)c.S * bes, (size_t)c.S * bes,
+                            (size_t)n * c.D, hipMemcpyHostToDevice, st));
+    }
+    HIPC(hipEventRecord(ctx->bank_ev[k], st));
+    used[k] = true;
+  }
+  HIPC(hipStreamSynchronize(st));
+  for (int32_t r = first; r < first + count; ++r)
+    if (!ctx->bank_written[r]) { ctx->bank_written[r] = 1; ++ctx->bank_filled; }
+  ctx->x_valid = false;   // an expansion made from replaced rows is stale
+  return RAU_OK;
+}
+
+int rau_bank_get(rau_ctx* ctx, int32_t first, int32_t count, void* feats) {
+  NEED(ctx && feats, "null argument");
+  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_get: the context has no feature bank (rau_bank_create)");
+  NEED(first >= 0 && count >= 1 && (int64_t)first + count <= ctx->bank_cap, "rau_bank_get: rows [%d,%d) out of [0,%d)",
+       first, first + count, ctx->bank_cap);
+  const rau_config& c = ctx->cfg;
+  const size_t bes = ctx->bank_type == RAU_FEAT_F32 ? 4 : 2, map_bytes = bank_map_bytes(ctx);
+  const char* src = static_cast<const char*>(ctx->bank) + (size_t)first * map_bytes;
+  HIPC(hipStreamSynchronize(ctx->st));
+  if (ctx->Sp == c.S)
+    HIPC(hipMemcpy(feats, src, (size_t)count * map_bytes, hipMemcpyDeviceToHost));
+  else
+    HIPC(hipMemcpy2D(feats, (size_t)c.S * bes, src, (size_t)ctx->Sp * bes, (size_t)c.S * bes, (size_t)count * c.D,
+                     hipMemcpyDeviceToHost));
+  return RAU_OK;
+}
+
 }  // extern "C"
 
 int batch_maps(rau_ctx* ctx, const float** maps) {
@@ -1072,8 +1334,13 @@ int batch_maps(rau_ctx* ctx, const float** maps) {
     return RAU_OK;
   const size_t map_bytes = (size_t)c.D * ctx->Sp * (ctx->feat_type == RAU_FEAT_F32 ? 4 : 2);
   hipStream_t st = ctx->st;
-  RUN("expand_features", 0, 2.0 * c.B * map_bytes,
-      expand_features(st, c.B, map_bytes, ctx->feats, ctx->slot[ctx->cur_slot].image_of_d, ctx->feats_x));
+  const BatchSlot& bs = ctx->slot[ctx->cur_slot];
+  if (bs.bank)   // one pass with the composed index rows[image_of[b]] (the second half of the slot's bank index)
+    RUN("bank_gather", 0, 2.0 * c.B * map_bytes,
+        bank_gather(st, c.B, map_bytes, ctx->bank, ctx->bank_cap, bs.bank_idx_d + c.B, ctx->feats_x));
+  else
+    RUN("expand_features", 0, 2.0 * c.B * map_bytes,
+        expand_features(st, c.B, map_bytes, ctx->feats, bs.image_of_d, ctx->feats_x));
   ctx->x_valid = true;
   ctx->x_slot = ctx->cur_slot;
   ctx->x_serial = ctx->slot_serial[ctx->cur_slot];
@@ -1558,6 +1825,13 @@ int rau_forward(rau_ctx* ctx) {
   const int nX = table_fwd ? ctx->n_images : B;   // maps the image-side passes read
   const int32_t* img = table_fwd ? ctx->slot[ctx->cur_slot].image_of_d : nullptr;
   const float* feats = ctx->feats;
+  if (table_fwd && ctx->slot[ctx->cur_slot].bank && !ctx->slot[ctx->cur_slot].table_ok) {
+    // a bank batch handed over in train mode carries its row index only: the table is gathered now
+    const size_t map_bytes = (size_t)D * S * (ctx->feat_type == RAU_FEAT_F32 ? 4 : 2);
+    RUN("bank_gather", 0, 2.0 * nX * map_bytes,
+        bank_gather(st, nX, map_bytes, ctx->bank, ctx->bank_cap, ctx->slot[ctx->cur_slot].bank_idx_d, ctx->feats));
+    ctx->slot[ctx->cur_slot].table_ok = true;
+  }
   if (!table_fwd)
     if (int rc = batch_maps(ctx, &feats)) return rc;   // (on st, in front of evA: the bulk stream is ordered behind it)
   ctx->fwd_table = table_fwd;
@@ -2113,6 +2387,7 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
   key |= (uint64_t)ctx->cur_slot << 30;   // the captured kernels hold the batch slot's device pointers
   key |= (uint64_t)ctx->feat_type << 32;  // ... and read the batch in its element type
   key |= (uint64_t)(ctx->n_images > 0) << 34;   // ... through the gather of an image table (any table, any N)
+  key |= (uint64_t)ctx->slot[ctx->cur_slot].bank << 35;   // ... of a bank batch: out of the bank
   if (int rc = upload_hop_weights(ctx, hop_w)) return rc;
   ctx->mg_valid = false;
   hipGraphExec_t exec = nullptr;

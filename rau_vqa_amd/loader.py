@@ -66,6 +66,7 @@ class DataClass:
         self._job = None          # (key, thread, result holder)
         self._next_dest = None    # SlotFeeder: where the prefetch worker assembles the next batch
         self._unique = False      # the last next_batch_feat asked for an image table: so will the prefetched one
+        self._bank = None         # (key, files, row of every question): bank_rows' answer for one tab_featpaths
 
     # ---- batch order options, loader.lua:1219-1291
     def set_batch_order_option(self, opt):
@@ -174,6 +175,16 @@ class DataClass:
                 feats = holder["feats"]
         if feats is None:
             feats = self._load_feats(files, feat_dim, feat_w, feat_h, feat_type=self.feat_type)
+        x, x_len, a, qids = self._take(idx)
+        if self.opt_prefetch:
+            self._start_prefetch(tab_featpaths, feat_dim, feat_w, feat_h)
+        if unique:
+            return feats, x, x_len, a, qids, image_of
+        return feats, x, x_len, a, qids
+
+    def _take(self, idx):
+        """The question side of the batch `idx` (x, x_len, a, qids), and the step to the next batch."""
+        B = self.batch_size
         x = np.ascontiguousarray(self.qs.question[idx].T, np.int32)          # transpose(1,2)
         x_len = np.ascontiguousarray(self.qs.lengths_q[idx], np.int32)
         qids = np.ascontiguousarray(self.qs.question_id[idx])
@@ -182,11 +193,57 @@ class DataClass:
         self.batch_index += B
         if self.batch_index + B > self.n:                # loader.lua:911-913
             self.reorder()
-        if self.opt_prefetch:
-            self._start_prefetch(tab_featpaths, feat_dim, feat_w, feat_h)
-        if unique:
-            return feats, x, x_len, a, qids, image_of
-        return feats, x, x_len, a, qids
+        return x, x_len, a, qids
+
+    # ---- feature bank: every distinct image of the split lives in device memory, batches name rows
+    def bank_rows(self, tab_featpaths):
+        """-> (files, row_of): the split's distinct feature files in the order of their first question in
+        the data set (independent of the batch order), and {file: bank row}."""
+        if isinstance(tab_featpaths, (str, os.PathLike)):
+            tab_featpaths = [tab_featpaths]
+        key = tuple(str(p) for p in tab_featpaths)
+        if self._bank is None or self._bank[0] != key:
+            dt = self.qs.datatype if self.qs.datatype is not None else np.ones(self.n, int)
+            row_of, files, qrow = {}, [], np.empty(self.n, np.int32)
+            for i in range(self.n):
+                p = os.path.join(key[int(dt[i]) - 1], feature_name(self.img_names[int(self.qs.img_list[i]) - 1]))
+                if p not in row_of:
+                    row_of[p] = len(files)
+                    files.append(p)
+                qrow[i] = row_of[p]
+            self._bank = (key, files, row_of, qrow)
+        return list(self._bank[1]), dict(self._bank[2])
+
+    def fill_bank(self, rau, tab_featpaths, feat_dim, feat_w=1, feat_h=1, chunk=64):
+        """Reads every distinct feature file of the split ONCE and puts it into rau's bank at its
+        bank_rows row, `chunk` files per rau.bank_put.  f32 files go up as f32 whatever the bank's type
+        (a 16-bit bank narrows them on the device); HalfTensor files go into an fp16 bank as they are.
+        -> number of rows written."""
+        files, _ = self.bank_rows(tab_featpaths)
+        info = rau.bank_info()
+        if info["capacity"] < len(files):
+            raise ValueError(f"bank of {info['capacity']} maps < {len(files)} distinct images")
+        keep_half = info["feat_type"] == "f16"
+        for r0 in range(0, len(files), max(int(chunk), 1)):
+            maps = [t7.load_feature(p, feat_dim, feat_w, feat_h, keep_half) for p in files[r0:r0 + max(int(chunk), 1)]]
+            half = all(m.dtype == np.float16 for m in maps)
+            rau.bank_put(r0, np.stack([m if half else m.astype(np.float32) for m in maps]))
+        return len(files)
+
+    def next_batch_rows(self, tab_featpaths):
+        """-> rows [N] i32 (bank rows of the batch's distinct images, in order of first appearance),
+        image_of [B] i32, x, x_len, a, qids: next_batch_feat(unique=True) with bank rows in place of the
+        maps -- the same batches in the same order, epoch wrap included -- and no file access."""
+        self.bank_rows(tab_featpaths)
+        B = self.batch_size
+        idx = self.batch_order[self.batch_index:self.batch_index + B]
+        rows, first, image_of = np.unique(self._bank[3][idx], return_index=True, return_inverse=True)
+        order = np.argsort(first, kind="stable")          # np.unique sorts by value: back to first appearance
+        rank = np.empty_like(order)
+        rank[order] = np.arange(len(order))
+        x, x_len, a, qids = self._take(idx)
+        return (np.ascontiguousarray(rows[order], np.int32), np.ascontiguousarray(rank[image_of.reshape(-1)], np.int32),
+                x, x_len, a, qids)
 
 
 class VqaData:
@@ -242,7 +299,11 @@ def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=12
 def feed(rau, batch, feat_type=None):
     """next_batch_feat's tuple -> rau_set_batch (the H2D of SS:434-439); returns qids.
     feat_type: that of the feats (needed for bf16, which arrives as uint16 bits).  A tuple of
-    next_batch_feat(unique=True) goes up as an image table."""
+    next_batch_feat(unique=True) goes up as an image table, one of next_batch_rows as a bank batch."""
+    if batch[0].ndim == 1:                                # next_batch_rows: rows, image_of, x, x_len, a, qids
+        rows, image_of, x, x_len, a, qids = batch
+        rau.set_batch(None, x, x_len, a if a.ndim == 1 else None, bank_rows=rows, image_of=image_of)
+        return qids
     feats, x, x_len, a, qids = batch[:5]
     image_of = batch[5] if len(batch) > 5 else None
     B, D = feats.shape[0], feats.shape[1]                 # (image table: B is its number of maps)
@@ -269,8 +330,11 @@ class SlotFeeder:
     """
 
     def __init__(self, rau, data: DataClass, tab_featpaths, feat_dim, feat_w=1, feat_h=1,
-                 feat_type=None, share_images=False):
+                 feat_type=None, share_images=False, bank=False):
         self.rau, self.data = rau, data
+        # bank=True: the maps are in rau's feature bank (DataClass.fill_bank); a batch is next_batch_rows' tuple,
+        # there is no prefetch worker and nothing is written to the slots' feature staging
+        self.bank = bool(bank)
         # every distinct image of a batch is read, staged and uploaded once (next_batch_feat(unique=True));
         # the worker fills the first N maps of the slot's staging
         self.share_images = bool(share_images)
@@ -279,7 +343,7 @@ class SlotFeeder:
         # element type of the maps in the staging and on the wire (default: the DataClass's)
         self.feat_type = data.feat_type = feat16.check_name(feat_type or data.feat_type)
         self._ft = {} if self.feat_type == "f32" else {"feat_type": self.feat_type}   # f32: the plain calls
-        data.opt_prefetch = True
+        data.opt_prefetch = not self.bank
         data._job = None               # any batch prefetched before now went to ordinary memory
         data._next_dest = lambda: self.rau.batch_slot(self.slot, **self._ft)["feats"]
         self.qids = self._advance()    # batch 0: read synchronously (nothing to overlap with yet)
@@ -288,6 +352,16 @@ class SlotFeeder:
         d, rau, s = self.data, self.rau, self.slot
         view = rau.batch_slot(s, **self._ft)          # (host-waits until the slot's last upload has left)
         self.slot = s ^ 1                             # the worker started by next_batch_feat fills the other
+        if self.bank:
+            rows, image_of, x, x_len, a, qids = d.next_batch_rows(self.args[0])
+            view["tokens"][...] = x
+            view["lens"][...] = x_len
+            labels = a.ndim == 1
+            if labels:
+                view["labels"][...] = a
+            rau.set_batch_async(s, has_labels=labels, bank_rows=rows, image_of=image_of)
+            rau.use_batch(s)
+            return qids
         batch = d.next_batch_feat(*self.args, unique=self.share_images)
         feats, x, x_len, a, qids = batch[:5]
         table = {"image_of": batch[5], "n_images": feats.shape[0]} if self.share_images else {}

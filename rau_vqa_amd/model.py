@@ -194,12 +194,76 @@ class RAU:
             raise ValueError("image table shapes do not match the config")
         return n, image_of
 
-    def set_batch(self, feats, tokens, lens, labels=None, feat_type=None, image_of=None):
+    # ---- feature bank (rau_bank_*): every image's map once in device memory
+    def bank_create(self, capacity, feat_type="f32"):
+        """One bank of `capacity` maps [D, S] of feat_type per context."""
+        L.check(self._lib.rau_bank_create(self._h, int(capacity), feat16.FEAT_TYPES[feat16.check_name(feat_type)]))
+
+    def bank_destroy(self):
+        L.check(self._lib.rau_bank_destroy(self._h))
+
+    def bank_info(self):
+        """{"capacity", "feat_type", "rows_filled"} of the context's bank."""
+        cap, ft, n = C.c_int32(), C.c_int(), C.c_int32()
+        L.check(self._lib.rau_bank_info(self._h, C.byref(cap), C.byref(ft), C.byref(n)))
+        return {"capacity": cap.value, "feat_type": feat16.FEAT_NAMES[ft.value], "rows_filled": n.value}
+
+    def bank_put(self, first, feats, feat_type=None):
+        """feats [n, D, S] into rows first .. first+n-1.  Maps of the bank's type are copied; f32 maps
+        into a 16-bit bank are narrowed on the device (the bits feat16.store gives on the host)."""
+        c = self.cfg
+        feats, ft = feat16.as_feats(feats, feat_type)
+        n = feats.size // (c.D * c.S)
+        if n < 1 or feats.size != n * c.D * c.S:
+            raise ValueError("bank_put: feats is not [n, D, S]")
+        L.check(self._lib.rau_bank_put(self._h, int(first), n, feats.ctypes.data, feat16.FEAT_TYPES[ft]))
+
+    def bank_get(self, first, count):
+        """Rows first .. first+count-1 as [count, D, S] in the bank's element type (bf16: uint16 bits)."""
+        c = self.cfg
+        out = np.empty((int(count), c.D, c.S), feat16.dtype_of(self.bank_info()["feat_type"]))
+        L.check(self._lib.rau_bank_get(self._h, int(first), int(count), out.ctypes.data))
+        return out
+
+    def _bank_index(self, bank_rows, image_of):
+        """(n_images, rows, image_of) of a bank batch; image_of None with B rows is the identity."""
+        c = self.cfg
+        rows = np.ascontiguousarray(bank_rows, np.int32)
+        if rows.ndim != 1 or rows.size < 1:
+            raise ValueError("bank_rows must be a 1-d array of bank rows")
+        if image_of is None:
+            if rows.size != c.B:
+                raise ValueError("bank_rows without image_of needs one row per sample")
+            image_of = np.arange(c.B, dtype=np.int32)
+        image_of = np.ascontiguousarray(image_of, np.int32)
+        if image_of.shape != (c.B,):
+            raise ValueError("image_of must have B entries")
+        return int(rows.size), rows, image_of
+
+    def set_batch(self, feats, tokens, lens, labels=None, feat_type=None, image_of=None, bank_rows=None):
         """feat_type "f32" | "f16" | "bf16" (default: from the dtype, see feat16.infer): a 16-bit map
         gives the same results, bit for bit, as the f32 map of its widened values.
         image_of [B] (0-based rows): feats is an image TABLE [N, D, S] that the questions of one image
-        share; the same results, bit for bit, as the plain batch feats[image_of]."""
+        share; the same results, bit for bit, as the plain batch feats[image_of].
+        bank_rows [N] (feats None): the table is bank[bank_rows], gathered inside device memory."""
         c = self.cfg
+        if bank_rows is not None:
+            if feats is not None:
+                raise ValueError("a bank batch takes bank_rows, not feats")
+            n_images, rows, image_of = self._bank_index(bank_rows, image_of)
+            tokens = np.ascontiguousarray(tokens, np.int32)
+            lens = np.ascontiguousarray(lens, np.int32)
+            if tokens.shape != (c.T, c.B) or lens.shape != (c.B,):
+                raise ValueError("batch shapes do not match the config")
+            lp = None
+            if labels is not None:
+                labels = np.ascontiguousarray(labels, np.int32)
+                if labels.shape != (c.B,):
+                    raise ValueError("labels shape")
+                lp = labels.ctypes.data
+            L.check(self._lib.rau_set_batch_bank(self._h, n_images, rows.ctypes.data, image_of.ctypes.data,
+                                                 tokens.ctypes.data, lens.ctypes.data, lp))
+            return
         feats, ft = feat16.as_feats(feats, feat_type)
         tokens = np.ascontiguousarray(tokens, np.int32)
         lens = np.ascontiguousarray(lens, np.int32)
@@ -255,13 +319,26 @@ class RAU:
                 "labels": view(p[3], c.B, C.c_int32, np.int32, (c.B,))}
 
     def set_batch_async(self, slot, feats=None, tokens=None, lens=None, labels=None, has_labels=True,
-                        feat_type=None, image_of=None, n_images=None):
+                        feat_type=None, image_of=None, n_images=None, bank_rows=None):
         """Enqueue the upload of a batch into `slot` on the copy stream and return.  Arrays left None
         are taken from the slot's staging (filled in place through batch_slot).  feat_type: as in
         set_batch; with feats None it names what the staging holds (default "f32").
         image_of [B]: the batch carries an image table (see set_batch) of feats.shape[0] maps, or, with
-        feats None, of the n_images maps at the start of the slot's staging; only those are uploaded."""
+        feats None, of the n_images maps at the start of the slot's staging; only those are uploaded.
+        bank_rows [N] (feats None): the table is bank[bank_rows]; the slot's feature staging is not read."""
         c = self.cfg
+        if bank_rows is not None:
+            if feats is not None:
+                raise ValueError("a bank batch takes bank_rows, not feats")
+            nmaps, rows, image_of = self._bank_index(bank_rows, image_of)
+            keep = [None if a is None else np.ascontiguousarray(a, np.int32) for a in (tokens, lens, labels)]
+            for a, n in zip(keep, (c.T * c.B, c.B, c.B)):
+                if a is not None and a.size != n:
+                    raise ValueError("batch shapes do not match the config")
+            tp, lp, yp = [None if a is None else a.ctypes.data for a in keep]
+            L.check(self._lib.rau_set_batch_async_bank(self._h, slot, nmaps, rows.ctypes.data,
+                                                       image_of.ctypes.data, tp, lp, yp, int(bool(has_labels))))
+            return
         nmaps = c.B
         if image_of is not None:
             if feats is None:
