@@ -26,6 +26,8 @@ const char* rau_last_error(void);
 int rau_abi_version(void);
 int rau_create(const rau_config* cfg, rau_ctx** out);
 void rau_destroy(rau_ctx* ctx);
+int rau_set_batch_size(rau_ctx* ctx, int32_t n);
+int rau_batch_size(rau_ctx* ctx, int32_t* n, int32_t* capacity);
 int rau_params(rau_ctx* ctx, int group, float** weights, float** grads, size_t* n);
 int rau_layout_count(const rau_ctx* ctx, int group);
 int rau_layout_entry(const rau_ctx* ctx, int group, int index, const char** name,
@@ -166,7 +168,31 @@ function RAU.new(opt)
   local life = { alive = true }
   local self = setmetatable({ h = ffi.gc(h[0], function(p) life.alive = false; C.rau_destroy(p) end),
                               cfg = cfg[0], life = life, scratch = {} }, RAU)
+  self.n = self.cfg.B   -- current batch size (rau:setBatchSize); cfg.B stays the capacity
   return self
+end
+
+-- One context, batches of up to cfg.B rows: rau:setBatchSize(n) makes it behave, bit for bit, like a context
+-- created with B = n that holds the same parameters, gradients, optimizer state, dropout seed, mode and bank
+-- (the reference's test_* tensors of SS:387-410 on the training context).  The resident batch, both upload slots
+-- and the last results do not outlive the call; it drains the streams and clears the activation storage, so
+-- call it per epoch (train -> evaluate -> train), not per step.  rau:batchSize() -> current size, capacity.
+function RAU:setBatchSize(n)
+  if n < 1 or n > self.cfg.B then
+    error(string.format('rau:setBatchSize(%d): out of [1, %d] (the batch size the context was created with)',
+                        n, self.cfg.B), 2)
+  end
+  check(C.rau_set_batch_size(self.h, n))
+  self.n = n
+end
+function RAU:batchSize()
+  local n, cap = ffi.new('int32_t[1]'), ffi.new('int32_t[1]')
+  check(C.rau_batch_size(self.h, n, cap))
+  return n[0], cap[0]
+end
+-- the setBatch* family: a batch whose x_len has another row count than the current size switches first
+local function follow_rows(self, x_len)
+  if x_len and x_len:nElement() ~= self.n then self:setBatchSize(x_len:nElement()) end
 end
 
 -- nn.Module surface ----------------------------------------------------------
@@ -188,6 +214,7 @@ function RAU:reset(seed, lo, hi) check(C.rau_init_uniform(self.h, seed or 123, l
 -- bit for bit as feats:float().
 local FEAT = { f32 = 0, f16 = 1, bf16 = 2 }   -- rau_feat_type
 function RAU:setBatch(feats, x, x_len, y)
+  follow_rows(self, x_len)
   if torch.type(feats) == 'torch.HalfTensor' then
     check(C.rau_set_batch_typed(self.h, feats:data(), FEAT.f16, x:data(), x_len:data(), y and y:data() or nil))
   else
@@ -205,18 +232,19 @@ end
 function RAU:batchSlot(slot, feat_type)
   local f, x, l, y = ffi.new('float*[1]'), ffi.new('int32_t*[1]'), ffi.new('int32_t*[1]'), ffi.new('int32_t*[1]')
   check(C.rau_batch_slot(self.h, slot, f, x, l, y))
-  local c = self.cfg
+  local c, B = self.cfg, self.n   -- each array starts where the capacity puts it and is dense in the current size
   local function addr(p) return tonumber(ffi.cast('intptr_t', p)) end
-  local n = c.B * c.D * c.S
+  local n = B * c.D * c.S
   return {
-    feats = feat_type == 'f16' and torch.HalfTensor(torch.HalfStorage(n, addr(f[0]))):resize(c.B, c.D, c.S)
-            or torch.FloatTensor(torch.FloatStorage(n, addr(f[0]))):resize(c.B, c.D, c.S),
-    x = torch.IntTensor(torch.IntStorage(c.T * c.B, addr(x[0]))):resize(c.T, c.B),
-    x_len = torch.IntTensor(torch.IntStorage(c.B, addr(l[0]))),
-    y = torch.IntTensor(torch.IntStorage(c.B, addr(y[0]))),
+    feats = feat_type == 'f16' and torch.HalfTensor(torch.HalfStorage(n, addr(f[0]))):resize(B, c.D, c.S)
+            or torch.FloatTensor(torch.FloatStorage(n, addr(f[0]))):resize(B, c.D, c.S),
+    x = torch.IntTensor(torch.IntStorage(c.T * B, addr(x[0]))):resize(c.T, B),
+    x_len = torch.IntTensor(torch.IntStorage(B, addr(l[0]))),
+    y = torch.IntTensor(torch.IntStorage(B, addr(y[0]))),
   }
 end
 function RAU:setBatchAsync(slot, feats, x, x_len, y, has_labels, feat_type)
+  follow_rows(self, x_len)
   local ft = FEAT[feat_type or (feats and torch.type(feats) == 'torch.HalfTensor' and 'f16') or 'f32']
   check(C.rau_set_batch_async_typed(self.h, slot, feats and feats:data() or nil, ft, x and x:data() or nil,
                                     x_len and x_len:data() or nil, y and y:data() or nil,
@@ -229,6 +257,7 @@ function RAU:useBatch(slot) check(C.rau_use_batch(self.h, slot)) end
 -- plain batch); converted here to the 0-based row offsets of rau_set_batch_images.  Only the N maps are
 -- uploaded and, in evaluate mode, convolved.  slot = nil: the synchronous form.
 function RAU:setBatchImages(feats, image_of, x, x_len, y, slot, has_labels)
+  follow_rows(self, x_len)
   local ft = torch.type(feats) == 'torch.HalfTensor' and FEAT.f16 or FEAT.f32
   local idx = image_of:int():add(-1)
   if slot then
@@ -256,6 +285,7 @@ end
 -- setBatchImages with the table taken from the bank: rows [N] Int/LongTensor of 1-BASED bank rows, image_of [B]
 -- 1-based positions in `rows`.  No feature map is read, staged or uploaded.  slot = nil: the synchronous form.
 function RAU:setBatchBank(rows, image_of, x, x_len, y, slot, has_labels)
+  follow_rows(self, x_len)
   local r = rows:int():add(-1)
   local idx = image_of:int():add(-1)
   if slot then
@@ -333,7 +363,7 @@ end
 -- (evaluate mode): returns oe, mc as IntTensors [nHop+2, B] of 1-based answer ids (hops, uni,
 -- select); ans_mc: IntTensor [B, nMultChoice] (0 = empty slot) or nil (mc = nil)
 function RAU:predict(ans_mc)
-  local H, B = self.cfg.H, self.cfg.B
+  local H, B = self.cfg.H, self.n
   local oe = torch.IntTensor(H + 2, B)
   if not ans_mc then
     check(C.rau_predict(self.h, nil, 0, oe:data(), nil))
@@ -554,7 +584,7 @@ local function clone(self, kind, i)
     function m:forward(x_t)
       local o = ffi.new('float*[1]')
       check(C.rau_embed_forward(self.rau.h, self.i, ptr_of(x_t), o))
-      self.output = Tensor.wrap(self.rau, o[0], cfg.B, cfg.E)
+      self.output = Tensor.wrap(self.rau, o[0], self.rau.n, cfg.E)
       return self.output
     end
     function m:backward(x_t, d_we) check(C.rau_embed_backward(self.rau.h, self.i, ptr_of(x_t), ptr_of(d_we))) end
@@ -562,14 +592,14 @@ local function clone(self, kind, i)
     function m:forward(inp)   -- {x, state}
       local o = ffi.new('float*[1]')
       check(C.rau_deeplstm_forward(self.rau.h, self.i, ptr_of(inp[1]), ptr_of(inp[2]), o))
-      self.output = Tensor.wrap(self.rau, o[0], cfg.B, Q)
+      self.output = Tensor.wrap(self.rau, o[0], self.rau.n, Q)
       return self.output
     end
     function m:backward(inp, d_state_out)
       local dx, ds = ffi.new('float*[1]'), ffi.new('float*[1]')
       check(C.rau_deeplstm_backward(self.rau.h, self.i, ptr_of(inp[1]), ptr_of(inp[2]),
                                     ptr_of(d_state_out), dx, ds))
-      self.gradInput = { Tensor.wrap(self.rau, dx[0], cfg.B, cfg.E), Tensor.wrap(self.rau, ds[0], cfg.B, Q) }
+      self.gradInput = { Tensor.wrap(self.rau, dx[0], self.rau.n, cfg.E), Tensor.wrap(self.rau, ds[0], self.rau.n, Q) }
       return self.gradInput
     end
   elseif kind == 'multimodal' then
@@ -579,9 +609,9 @@ local function clone(self, kind, i)
       check(C.rau_multimodal_forward(self.rau.h, self.i, ptr_of(inp[1]), ptr_of(inp[2]),
                                      ptr_of(inp[3]), ptr_of(inp[4]), o[1], o[2], o[3], o[4], o[5]))
       local r = self.rau                                             -- {logits, dp, a, c, h}
-      self.output = { Tensor.wrap(r, o[1][0], cfg.B, cfg.K), Tensor.wrap(r, o[2][0], cfg.B),
-                      Tensor.wrap(r, o[3][0], cfg.B, cfg.S), Tensor.wrap(r, o[4][0], cfg.B, cfg.R),
-                      Tensor.wrap(r, o[5][0], cfg.B, cfg.R) }
+      self.output = { Tensor.wrap(r, o[1][0], self.rau.n, cfg.K), Tensor.wrap(r, o[2][0], self.rau.n),
+                      Tensor.wrap(r, o[3][0], self.rau.n, cfg.S), Tensor.wrap(r, o[4][0], self.rau.n, cfg.R),
+                      Tensor.wrap(r, o[5][0], self.rau.n, cfg.R) }
       return self.output
     end
     function m:backward(inp, g)   -- g = {d_logits, d_do_pred|nil, d_attprob|nil, d_c, d_h}
@@ -591,8 +621,8 @@ local function clone(self, kind, i)
                                       ptr_of(inp[3]), ptr_of(inp[4]), ptr_of(g[1]), ptr_of(g[2]),
                                       ptr_of(g[3]), ptr_of(g[4]), ptr_of(g[5]), o[1], nil, o[3], o[4]))
       local r = self.rau                                    -- {d_q, (d_X dead, SS:579), d_c, d_h}
-      self.gradInput = { Tensor.wrap(r, o[1][0], cfg.B, Q), nil, Tensor.wrap(r, o[3][0], cfg.B, cfg.R),
-                         Tensor.wrap(r, o[4][0], cfg.B, cfg.R) }
+      self.gradInput = { Tensor.wrap(r, o[1][0], self.rau.n, Q), nil, Tensor.wrap(r, o[3][0], self.rau.n, cfg.R),
+                         Tensor.wrap(r, o[4][0], self.rau.n, cfg.R) }
       return self.gradInput
     end
   elseif kind == 'criterion' then
@@ -604,7 +634,7 @@ local function clone(self, kind, i)
     function m:backward(logits, y, scale)
       local o = ffi.new('float*[1]')
       check(C.rau_criterion_backward(self.rau.h, self.i, ptr_of(logits), ptr_of(y), scale or 1, o))
-      return Tensor.wrap(self.rau, o[0], cfg.B, cfg.K)
+      return Tensor.wrap(self.rau, o[0], self.rau.n, cfg.K)
     end
   end
   function m:training() self.rau:training() end

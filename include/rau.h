@@ -89,7 +89,7 @@ typedef enum rau_dtype {
 /* Network hyper-parameters: the hard-coded locals of SS:202,209-229 plus the
  * data-defined sizes.  Q (question state width) is 4*Rq: 2 layers x {c,h}. */
 typedef struct rau_config {
-  int32_t B;    /* batch size per GPU (opt.batch_size) */
+  int32_t B;    /* batch size per GPU (opt.batch_size): the context's capacity, see rau_set_batch_size */
   int32_t T;    /* seq_len: rows of the token matrix x[T,B] */
   int32_t V;    /* vocab_size incl. ZEROPAD */
   int32_t E;    /* embed_dim = 200, SS:202 */
@@ -120,6 +120,41 @@ int rau_abi_version(void);
  * gradients, activations for T tokens and H hops, and the ctx stream. */
 int rau_create(const rau_config* cfg, rau_ctx** out);
 void rau_destroy(rau_ctx* ctx);
+
+/* ---- batch size: one context, batches of up to the B it was created for ------------------------
+ * The B of rau_create is the context's CAPACITY: every buffer is allocated for it once.  The reference trains
+ * at opt.batch_size and evaluates the same parameters at a size that divides the split (83 / 57 / 96,
+ * SS:85-95, its test_* state tensors SS:387-410); rau_set_batch_size(ctx, n), 1 <= n <= capacity, makes the
+ * SAME context run batches of n rows: it then behaves BIT FOR BIT like a context created with B = n in this
+ * process that holds the same parameters, gradients, Adam moments and step counts, dropout seed, mode, bank
+ * and communicator -- at every entry point of this header.  Every tensor shape uses n and is dense in it
+ * ([H,n,K] logits, [T,n] tokens, mask sites [H,n,D,S], the staging arrays of rau_batch_slot), and every
+ * batch-dependent launch decision is the one rau_create makes for n (one function serves both).
+ *   kept      parameters, gradients, optimizer state, the (seed, step) of rau_set_dropout_seed, the mode, the
+ *             feature bank and its rows, the communicator, rau_dev_alloc'ed memory, captured steps of other
+ *             sizes (rau_graph_step keys its cache by n: a step captured at 100 is found again after an
+ *             excursion to 83, never replayed at 83).
+ *   cleared   the resident batch, both slots of the asynchronous path (pending uploads are dropped), explicit
+ *             masks of rau_set_mask (the sites fall back to the seeded stream), the module-level output slots,
+ *             the last forward's results and merged hops: entry points that need them return RAU_ERR_STATE
+ *             with nothing launched, exactly as on a fresh context, until their inputs exist again.
+ *   n == the current size: a no-op that keeps everything.  n < 1 or n > capacity: RAU_ERR_INVALID, nothing
+ *   changes.  A split-K workspace can need MORE room at a smaller n (split counts are chosen per shape); if
+ *   that allocation fails: RAU_ERR_NOMEM and the context stays at the old size.  RAU_ERR_STATE while
+ *   profiling is on.  A persistent-encoder give-up (rau_sync) is a finding about the device, not the size:
+ *   the context keeps the launch-per-step encoder at every later size.
+ * Cost: the call drains the context's streams and clears all batch-dependent device storage, because the
+ * dense layouts move and the step relies on zeros a fresh context has (initial-state rows, pad columns of
+ * 7x7 maps).  Measured on an MI355X (tools/batch_size_time.py, table in LOG.md): 0.48 ms for 100 -> 83 and
+ * 0.79 ms for 256 -> 96 at the default widths (contexts of 1.7 and 3.8 GB), 0.63 ms for 80 -> 32 at D = 2048
+ * in bf16 mode (2.7 GB); the same in either direction, since it clears what the capacity allocated: the
+ * stream drain, about a hundred memsets and one synchronise, no workspace regrowth in any of those.  That is a
+ * third to a half of an evaluate-mode forward (1.5 ms at 83 rows): a per-epoch call (train / evaluate /
+ * ragged tail), not a per-step call.  A context that never calls it allocates and computes exactly what it
+ * did without it.  Synchronising.
+ * rau_batch_size: the current size and the capacity (either may be NULL). */
+int rau_set_batch_size(rau_ctx* ctx, int32_t n);
+int rau_batch_size(rau_ctx* ctx, int32_t* n, int32_t* capacity);
 
 /* ---- parameters: m:getParameters(), SS:322-324 ------------------------------
  * Flat DEVICE buffers (weights, gradients) of a group and its length in floats.
@@ -266,7 +301,9 @@ int rau_set_batch_async_bank(rau_ctx* ctx, int slot, int n_images, const int32_t
  * worker thread assembles the next batch (utils/vqa_prepro_loader.lua:931-958).  Here the ctx owns
  * TWO batch slots, each with device buffers and PINNED host staging:
  *   rau_batch_slot(slot)       -> host pointers of the slot's staging (feats [B,D,S], tokens [T,B],
- *                                 lens [B], labels [B]); the loader assembles the batch in place.
+ *                                 lens [B], labels [B]); the loader assembles the batch in place.  The four
+ *                                 pointers never move (each array has room for the capacity); a batch of the
+ *                                 current size n is written DENSE in n: [n,D,S], [T,n], [n], [n].
  *                                 Waits (on the host) until the slot's previous upload has left it:
  *                                 CALL IT BEFORE EVERY IN-PLACE REFILL, never cache its pointers across
  *                                 iterations (the host may run two steps ahead of the copy stream).

@@ -53,6 +53,8 @@ _SIGS = {
     "rau_abi_version": (C.c_int, []),
     "rau_create": (C.c_int, [C.POINTER(RauConfig), C.POINTER(C.c_void_p)]),
     "rau_destroy": (None, [C.c_void_p]),
+    "rau_set_batch_size": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rau_batch_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rau_params": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                              C.POINTER(C.c_size_t)]),
     "rau_layout_count": (C.c_int, [C.c_void_p, C.c_int]),

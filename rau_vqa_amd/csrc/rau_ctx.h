@@ -102,7 +102,9 @@ struct BatchSlot {
 };
 
 struct rau_ctx {
-  rau_config cfg;
+  rau_config cfg;             // cfg.B is the CURRENT batch size (rau_set_batch_size): what every layout, launch and
+                              // getter reads at call time -- the B of the fresh context this one is equivalent to
+  int cap = 0;                // the B of rau_create: what every buffer that depends on the batch size is allocated for
   int Q;
   int Sp = 0;                 // position pitch: cfg.S rounded up to a multiple of 4 (7x7 maps: 49 -> 52);
                               // every [.., S]-shaped device tensor uses it, pad columns hold zeros
@@ -122,6 +124,10 @@ struct rau_ctx {
   // the last forward used (evaluate mode: one group of H).
   std::vector<int> groups, cur, bgroups;   // bgroups: backward partition (empty = same as forward)
   std::vector<void*> allocs;
+  // what rau_set_batch_size clears: every dalloc'ed region except parameters, gradients, Adam moments, the Philox
+  // key and rau_dev_alloc'ed memory.  The layouts are dense in the current batch size, so after a change stale
+  // data would sit where the step expects the zeros of a fresh context (initial-state rows, pad columns).
+  std::vector<std::pair<void*, size_t>> scratch;
   Group grp[3];
   // mult
   Lin q_proj, h_proj, i_embed, att_q, att_i, att_score, att_mem, feat_attprob, lstm_i2h,
@@ -200,13 +206,15 @@ struct rau_ctx {
   int* perr_d = nullptr;
   int* perr_h = nullptr;
   bool persist_used = false;
+  bool persist_gave_up = false; // persist_check() turned the persistent encoder off: it stays off across resizes
   float* hopw_h = nullptr;    // pinned staging of the hop weights, 2 slots of H
   int hopw_slot = 0;
   // backward temporaries
   // dZ holds dI (gradient at i_embed's OUTPUT); the tanh derivative is applied by its consumers
   float *dpre, *dhn, *dg4, *dcn[2], *dhp[2], *dj, *da_lin, *dz, *du, *dwsp, *dZ,
       *dqt, *dQD, *dq, *slab, *slab2, *slab3, *coltmp3, *tmpS, *coltmp2, *dbi_part;
-  size_t slab3_floats = 0, slab2_floats = 0;
+  size_t slab3_floats = 0, slab2_floats = 0;   // what the current batch size asks for: the launch policy reads these
+  size_t slab_alloc = 0, slab2_alloc = 0, slab3_alloc = 0;   // floats really allocated (>= the above after a resize)
   float *dG1, *dG2, *dwe, *edc[2][2];
   size_t slab_floats = 0;
   // module-level entry points (rau_modules.hip); allocated on first use
@@ -290,8 +298,9 @@ inline float mask_p(const rau_ctx* ctx, int site) {
   return ctx->mexplicit[site] ? ctx->mp_exact[site] : ctx->mp[site];
 }
 
+// scratch = false: the region outlives rau_set_batch_size untouched (see rau_ctx::scratch)
 template <typename Tp>
-static int dalloc(rau_ctx* c, Tp** p, size_t count) {
+static int dalloc(rau_ctx* c, Tp** p, size_t count, bool scratch = true) {
   void* d = nullptr;
   const size_t bytes = std::max<size_t>(count, 1) * sizeof(Tp);
   hipError_t e = hipMalloc(&d, bytes);
@@ -300,6 +309,7 @@ static int dalloc(rau_ctx* c, Tp** p, size_t count) {
   e = hipMemsetAsync(d, 0, bytes, c->st);
   if (e != hipSuccess) return fail(RAU_ERR_DEVICE, "hipMemsetAsync: %s", hipGetErrorString(e));
   c->allocs.push_back(d);
+  if (scratch) c->scratch.push_back({d, bytes});
   *p = reinterpret_cast<Tp*>(d);
   return 0;
 }

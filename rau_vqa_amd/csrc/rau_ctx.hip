@@ -86,6 +86,133 @@ static int enc_wgrad_problems(rau_ctx* ctx, size_t row0, TnProblem* pr) {
   return n;
 }
 
+// ---- everything the batch size decides beyond the tensor shapes ---------------------------------
+// rau_create (for the capacity) and rau_set_batch_size (for the new size) both take it from here, so a
+// resized context launches what a context created at that size launches and cannot drift from it.
+struct BatchPlan {
+  std::vector<int> groups;                   // forward hop-group partition (rau_ctx::groups)
+  bool att_split, enc_ws, enc_ws_train;
+  size_t slab, slab2, slab3, att_part;       // workspace needs, floats
+  size_t mcount[5];                          // mask sites, elements
+};
+static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
+  const rau_config& c = ctx->cfg;
+  const int T = c.T, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R, K = c.K,
+            H = c.H, Q = ctx->Q;
+  // Default partition: pairs, then the last two hops alone.  The forward phase ends one hop after
+  // the last group's GEMMs and the backward bulk work can start one hop into the backward chain
+  // (measured on H = 8: 2,2,2,1,1 vs 2,2,2,2); pairs elsewhere keep the launches large.
+  // RAU_HOP_GROUPS="4,2,1,1" overrides (sizes must sum to H).
+  {
+    std::vector<int> sizes;
+    if (const char* eg = std::getenv("RAU_HOP_GROUPS")) {
+      int sum = 0;
+      for (const char* q = eg; *q;) {
+        const int v = std::atoi(q);
+        if (v < 1) { sizes.clear(); break; }
+        sizes.push_back(v);
+        sum += v;
+        while (*q && *q != ',') ++q;
+        if (*q == ',') ++q;
+      }
+      if (sum != H) sizes.clear();
+    }
+    if (sizes.empty() && B <= 64) {
+      // small batches are bound by the recurrence's launches, not by the conv GEMMs: one group
+      // (B = 32 / 64: 3.64 / 4.43 -> 3.55 / 4.33 ms; B = 128: 6.09 -> 6.49, so not there)
+      sizes.push_back(H);
+    }
+    if (sizes.empty()) {
+      int left = H;
+      while (left > 3) { sizes.push_back(2); left -= 2; }
+      while (left > 0) { sizes.push_back(1); left -= 1; }
+      if (H == 2) sizes = {1, 1};
+    }
+    p->groups.assign(H, 0);
+    int h0 = 0;
+    for (int n : sizes) { p->groups[h0] = n; h0 += n; }
+  }
+  p->mcount[RAU_MASK_WE] = (size_t)T * B * E;
+  p->mcount[RAU_MASK_RNN] = (size_t)T * B * Rq;
+  p->mcount[RAU_MASK_Q] = (size_t)H * B * Q;
+  p->mcount[RAU_MASK_X] = (size_t)H * B * D * SL;
+  p->mcount[RAU_MASK_MF] = (size_t)H * B * M;
+  p->att_part = att_split_part_floats(B, S);
+  // Same-box A/B (B=256, D=512, ms/step): fused 16-wave attention + split-K encoder 10.54-10.59,
+  // split attention + fused encoder step 10.92-10.95, round-1 library 10.75-10.82.  The split
+  // attention kernels and the fused LSTM step are faster ALONE (no bulk GEMM beside them): the
+  // evaluate-mode forward uses the fused LSTM step; RAU_ATT_SPLIT forces the split attention kernels.
+  // Small batches (one 16-wave workgroup per sample leaves most CUs idle): B = 32 / 64 / 128 fused
+  // 3.83 / 4.57 / 6.06 ms, split in 8 row chunks 3.63 / 4.39 / 6.05 ms -> split up to B = 64
+  // (RAU_ATT_FUSED keeps the fused kernels).
+  p->att_split = std::getenv("RAU_ATT_SPLIT") != nullptr ||
+                 (B <= 64 && std::getenv("RAU_ATT_FUSED") == nullptr);
+  {
+    // Weight-stationary persistent encoder (enc_ws.hip): chosen by shape, never by the environment in
+    // normal use -- contexts of up to 64 samples (the strong-scaling shards of configs[3]) are bound
+    // by the recurrence's launches.  RAU_ENC_WS=0|1 is the A/B override (DESIGN.md section 9).
+    const char* e = std::getenv("RAU_ENC_WS");
+    // measured in the step (MS weights, same box): B = 16 / 32 / 64 -> 3.00 / 3.49 / 4.46 ms with it,
+    // 3.16 / 3.52 / 4.26 without; evaluate-mode forward 14.3 / 26.8 / 45.9 k vs 10.8 / 20.8 / 40.4 k QA/s.
+    // Every workgroup reads all h rows of its sample half each step, so the traffic grows with B while
+    // the weights it avoids re-reading do not: training contexts up to 32 samples, inference up to 64.
+    // Its workgroups wait on each other's progress counters, so the whole grid must be resident at
+    // once: asked of THIS device (a CPX partition or a reduced-CU device says no and keeps the
+    // launch-per-step path).  If a bounded wait still gives up at run time (several contexts
+    // competing for the CUs), persist_check() below turns the path off for the ctx -- for good: what
+    // gave up was the device's residency, not the size, so a later rau_set_batch_size keeps it off.
+    const bool fits = !ctx->persist_gave_up && enc_ws_ok(B, Rq) && enc_ws_fits_device(B);
+    p->enc_ws_train = fits && (e ? std::atoi(e) != 0 : B <= 32);
+    p->enc_ws = fits && (e ? std::atoi(e) != 0 : B <= 64);
+  }
+  {
+    // split-K workspaces: one per stream (the two streams run concurrently)
+    size_t sl2 = std::max(conv_wgrad_slab_floats(H * B, A, M, S),
+                          conv_wgrad_slab_floats(H * B, M, D, S));
+    if (ctx->bf16) sl2 = std::max(sl2, wgrad16_slab_floats(H * B, M, D, S));
+    // The grouped Linear weight-gradient GEMMs' partial slabs.  They run on the weight-gradient stream
+    // (slab3) or, where the bulk stream is the longer path, at the END of the bulk stream (rau_backward):
+    // there they take the BULK stream's workspace -- each stream owns its workspace, and two launches that
+    // share one must be ordered by their stream.  (Round 4 first moved the mult group's GEMM to the bulk
+    // stream with slab3 still in its hands while the encoder group's GEMM used slab3 on the third stream:
+    // the two ran concurrently and overwrote each other's partials; tests/test_gpu_att_variants.py caught it.)
+    size_t grp_floats = 0;
+    {
+      TnProblem pr[13];   // (only the shapes are read here)
+      int n = mult_wgrad_problems(ctx, pr);
+      for (int hh = 1; hh <= H; ++hh)
+        grp_floats = std::max(grp_floats, gemm_tn_group_slab_floats(pr, n, hh * B));
+      n = enc_wgrad_problems(ctx, 0, pr);
+      for (int tt = 1; tt <= T; ++tt)
+        grp_floats = std::max(grp_floats, gemm_tn_group_slab_floats(pr, n, tt * B));
+    }
+    p->slab2 = std::max(sl2, grp_floats);
+    const int rowsH = H * B, rowsT = T * B;
+    const int shapes[][3] = {{K, M, rowsH},      {M, R, rowsH},      {4 * R, M, rowsH},
+                             {4 * R, R, rowsH},  {M, S, rowsH},      {S, R, rowsH},
+                             {A, M, rowsH},      {M, Q, rowsH},      {4 * Rq, E, rowsT},
+                             {4 * Rq, Rq, rowsT}};
+    // skinny split-K partials: every deferred GEMM of the hop loop must fit un-split in its share of
+    // the slab (a quarter to a sixth), whatever its output width (4R, 4Rq, K, Q, M, A or S)
+    size_t sl = (size_t)16 * B * std::max({4 * R, 4 * Rq, K, Q, M, A, S});
+    for (auto& sh : shapes) sl = std::max(sl, gemm_tn_slab_floats(sh[0], sh[1], sh[2]));
+    p->slab = sl;
+    // the weight-gradient stream's workspace also holds the grouped launches' partial slabs
+    p->slab3 = std::max(sl, grp_floats);
+  }
+}
+// the launch decisions of `p` become the context's (the workspaces are the caller's business)
+static void adopt_plan(rau_ctx* ctx, const BatchPlan& p) {
+  ctx->groups = p.groups;
+  for (int i = 0; i < 5; ++i) ctx->mcount[i] = p.mcount[i];
+  ctx->att_split_env = p.att_split;
+  ctx->enc_ws = p.enc_ws;
+  ctx->enc_ws_train = p.enc_ws_train;
+  ctx->slab_floats = p.slab;
+  ctx->slab2_floats = p.slab2;
+  ctx->slab3_floats = p.slab3;
+}
+
 // ================================================================== C ABI
 extern "C" {
 
@@ -206,38 +333,8 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
     hipDeviceGetStreamPriorityRange(&plo, &phi);
     hipStreamCreateWithPriority(&ctx->st3, hipStreamNonBlocking, plo);
   }
-  // Default partition: pairs, then the last two hops alone.  The forward phase ends one hop after
-  // the last group's GEMMs and the backward bulk work can start one hop into the backward chain
-  // (measured on H = 8: 2,2,2,1,1 vs 2,2,2,2); pairs elsewhere keep the launches large.
-  // RAU_HOP_GROUPS="4,2,1,1" overrides (sizes must sum to H).
+  ctx->cap = c.B;
   {
-    std::vector<int> sizes;
-    if (const char* eg = std::getenv("RAU_HOP_GROUPS")) {
-      int sum = 0;
-      for (const char* p = eg; *p;) {
-        const int v = std::atoi(p);
-        if (v < 1) { sizes.clear(); break; }
-        sizes.push_back(v);
-        sum += v;
-        while (*p && *p != ',') ++p;
-        if (*p == ',') ++p;
-      }
-      if (sum != c.H) sizes.clear();
-    }
-    if (sizes.empty() && c.B <= 64) {
-      // small batches are bound by the recurrence's launches, not by the conv GEMMs: one group
-      // (B = 32 / 64: 3.64 / 4.43 -> 3.55 / 4.33 ms; B = 128: 6.09 -> 6.49, so not there)
-      sizes.push_back(c.H);
-    }
-    if (sizes.empty()) {
-      int left = c.H;
-      while (left > 3) { sizes.push_back(2); left -= 2; }
-      while (left > 0) { sizes.push_back(1); left -= 1; }
-      if (c.H == 2) sizes = {1, 1};
-    }
-    ctx->groups.assign(c.H, 0);
-    int h0 = 0;
-    for (int n : sizes) { ctx->groups[h0] = n; h0 += n; }
     if (const char* eg = std::getenv("RAU_BWD_GROUPS")) {
       std::vector<int> bs;
       int sum = 0;
@@ -305,8 +402,8 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
     ctx->grp[RAU_GROUP_MULT].n = lb.off;
   }
   for (int gi = 0; gi < 3; ++gi) {
-    CK(dalloc(ctx, &ctx->grp[gi].w, ctx->grp[gi].n + 4));
-    CK(dalloc(ctx, &ctx->grp[gi].g, ctx->grp[gi].n + 4));
+    CK(dalloc(ctx, &ctx->grp[gi].w, ctx->grp[gi].n + 4, false));
+    CK(dalloc(ctx, &ctx->grp[gi].g, ctx->grp[gi].n + 4, false));
   }
   for (int L = 0; L < 2; ++L) {
     bind(ctx->i2h[L], ctx->grp[RAU_GROUP_RNN]);
@@ -317,6 +414,10 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
                &ctx->lstm_h2h, &ctx->lstm_out, &ctx->cls, &ctx->do_pred};
   for (Lin* l : ml) bind(*l, ctx->grp[RAU_GROUP_MULT]);
 
+  // ---- launch policy and workspace sizes of this batch size
+  BatchPlan plan;
+  plan_batch(ctx, B, &plan);
+  adopt_plan(ctx, plan);
   // ---- batch
   CK(dalloc(ctx, &ctx->feats, (size_t)B * D * S));
   CK(dalloc(ctx, &ctx->tokens, (size_t)T * B));
@@ -326,11 +427,6 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   CK(dalloc(ctx, &ctx->ustart, (size_t)T * B + 1));
   CK(dalloc(ctx, &ctx->upos, (size_t)T * B));
   // ---- masks (bit-packed, +1 word slack)
-  ctx->mcount[RAU_MASK_WE] = (size_t)T * B * E;
-  ctx->mcount[RAU_MASK_RNN] = (size_t)T * B * Rq;
-  ctx->mcount[RAU_MASK_Q] = (size_t)H * B * Q;
-  ctx->mcount[RAU_MASK_X] = (size_t)H * B * D * SL;
-  ctx->mcount[RAU_MASK_MF] = (size_t)H * B * M;
   for (int i = 0; i < 5; ++i) CK(dalloc(ctx, &ctx->mbits[i], (ctx->mcount[i] + 31) / 32 + 1));
   // ---- encoder
   const size_t TB = (size_t)T * B;
@@ -374,33 +470,9 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   CK(dalloc(ctx, &ctx->WiT, (size_t)M * D));
   CK(dalloc(ctx, &ctx->WpT, (size_t)A * M));
   CK(dalloc(ctx, &ctx->zm, (size_t)B * S));
-  CK(dalloc(ctx, &ctx->att_part, att_split_part_floats(B, S)));
-  // Same-box A/B (B=256, D=512, ms/step): fused 16-wave attention + split-K encoder 10.54-10.59,
-  // split attention + fused encoder step 10.92-10.95, round-1 library 10.75-10.82.  The split
-  // attention kernels and the fused LSTM step are faster ALONE (no bulk GEMM beside them): the
-  // evaluate-mode forward uses the fused LSTM step; RAU_ATT_SPLIT forces the split attention kernels.
-  // Small batches (one 16-wave workgroup per sample leaves most CUs idle): B = 32 / 64 / 128 fused
-  // 3.83 / 4.57 / 6.06 ms, split in 8 row chunks 3.63 / 4.39 / 6.05 ms -> split up to B = 64
-  // (RAU_ATT_FUSED keeps the fused kernels).
-  ctx->att_split_env = std::getenv("RAU_ATT_SPLIT") != nullptr ||
-                       (c.B <= 64 && std::getenv("RAU_ATT_FUSED") == nullptr);
+  CK(dalloc(ctx, &ctx->att_part, plan.att_part));
   {
-    // Weight-stationary persistent encoder (enc_ws.hip): chosen by shape, never by the environment in
-    // normal use -- contexts of up to 64 samples (the strong-scaling shards of configs[3]) are bound
-    // by the recurrence's launches.  RAU_ENC_WS=0|1 is the A/B override (DESIGN.md section 9).
-    const char* e = std::getenv("RAU_ENC_WS");
-    // measured in the step (MS weights, same box): B = 16 / 32 / 64 -> 3.00 / 3.49 / 4.46 ms with it,
-    // 3.16 / 3.52 / 4.26 without; evaluate-mode forward 14.3 / 26.8 / 45.9 k vs 10.8 / 20.8 / 40.4 k QA/s.
-    // Every workgroup reads all h rows of its sample half each step, so the traffic grows with B while
-    // the weights it avoids re-reading do not: training contexts up to 32 samples, inference up to 64.
-    // Its workgroups wait on each other's progress counters, so the whole grid must be resident at
-    // once: asked of THIS device (a CPX partition or a reduced-CU device says no and keeps the
-    // launch-per-step path).  If a bounded wait still gives up at run time (several contexts
-    // competing for the CUs), persist_check() below turns the path off for the ctx.
-    const bool fits = enc_ws_ok(B, Rq) && enc_ws_fits_device(B);
-    ctx->enc_ws_train = fits && (e ? std::atoi(e) != 0 : B <= 32);
     if (const char* ss = std::getenv("RAU_SIDE_SPLIT")) ctx->side_split_env = std::atoi(ss) != 0;
-    ctx->enc_ws = fits && (e ? std::atoi(e) != 0 : B <= 64);
     float* f = nullptr;
     CK(dalloc(ctx, &f, 16));
     ctx->ws_cnt = reinterpret_cast<unsigned*>(f);
@@ -454,45 +526,13 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   CK(dalloc(ctx, &ctx->dQD, HB * Q));
   CK(dalloc(ctx, &ctx->dq, (size_t)B * Q));
   {
-    // split-K workspaces: one per stream (the two streams run concurrently)
-    size_t sl2 = std::max(conv_wgrad_slab_floats(H * B, A, M, S),
-                          conv_wgrad_slab_floats(H * B, M, D, S));
-    if (ctx->bf16) sl2 = std::max(sl2, wgrad16_slab_floats(H * B, M, D, S));
-    // The grouped Linear weight-gradient GEMMs' partial slabs.  They run on the weight-gradient stream
-    // (slab3) or, where the bulk stream is the longer path, at the END of the bulk stream (rau_backward):
-    // there they take the BULK stream's workspace -- each stream owns its workspace, and two launches that
-    // share one must be ordered by their stream.  (Round 4 first moved the mult group's GEMM to the bulk
-    // stream with slab3 still in its hands while the encoder group's GEMM used slab3 on the third stream:
-    // the two ran concurrently and overwrote each other's partials; tests/test_gpu_att_variants.py caught it.)
-    size_t grp_floats = 0;
-    {
-      TnProblem pr[13];
-      int n = mult_wgrad_problems(ctx, pr);
-      for (int hh = 1; hh <= H; ++hh)
-        grp_floats = std::max(grp_floats, gemm_tn_group_slab_floats(pr, n, hh * B));
-      n = enc_wgrad_problems(ctx, 0, pr);
-      for (int tt = 1; tt <= T; ++tt)
-        grp_floats = std::max(grp_floats, gemm_tn_group_slab_floats(pr, n, tt * B));
-    }
-    sl2 = std::max(sl2, grp_floats);
-    CK(dalloc(ctx, &ctx->slab2, sl2));
-    ctx->slab2_floats = sl2;
-    const int rowsH = H * B, rowsT = T * B;
-    const int shapes[][3] = {{K, M, rowsH},      {M, R, rowsH},      {4 * R, M, rowsH},
-                             {4 * R, R, rowsH},  {M, S, rowsH},      {S, R, rowsH},
-                             {A, M, rowsH},      {M, Q, rowsH},      {4 * Rq, E, rowsT},
-                             {4 * Rq, Rq, rowsT}};
-    // skinny split-K partials: every deferred GEMM of the hop loop must fit un-split in its share of
-    // the slab (a quarter to a sixth), whatever its output width (4R, 4Rq, K, Q, M, A or S)
-    size_t sl = (size_t)16 * B * std::max({4 * R, 4 * Rq, K, Q, M, A, S});
-    for (auto& s : shapes) sl = std::max(sl, gemm_tn_slab_floats(s[0], s[1], s[2]));
-    ctx->slab_floats = sl;
-    CK(dalloc(ctx, &ctx->slab, sl));
-    {  // the weight-gradient stream's workspace also holds the grouped launches' partial slabs
-      const size_t sl3 = std::max(sl, grp_floats);
-      ctx->slab3_floats = sl3;
-      CK(dalloc(ctx, &ctx->slab3, sl3));
-    }
+    // split-K workspaces: one per stream (plan_batch)
+    CK(dalloc(ctx, &ctx->slab2, plan.slab2));
+    CK(dalloc(ctx, &ctx->slab, plan.slab));
+    CK(dalloc(ctx, &ctx->slab3, plan.slab3));
+    ctx->slab_alloc = plan.slab;
+    ctx->slab2_alloc = plan.slab2;
+    ctx->slab3_alloc = plan.slab3;
     // every consumer of K-split partials checks the span it is about to read against these (split_guard.hip)
     split_ws_register(ctx->slab, ctx->slab_floats);
     split_ws_register(ctx->slab2, ctx->slab2_floats);
@@ -512,7 +552,7 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
     CK(dalloc(ctx, &ctx->edc[L][0], (size_t)B * Rq));
     CK(dalloc(ctx, &ctx->edc[L][1], (size_t)B * Rq));
   }
-  CK(dalloc(ctx, &ctx->dkey, (size_t)2));
+  CK(dalloc(ctx, &ctx->dkey, (size_t)2, false));   // (seed, step) outlive a resize
   CK(dalloc(ctx, &ctx->npart, (size_t)1024));
   CK(dalloc(ctx, &ctx->norms_d, (size_t)4));
 #undef CK
@@ -838,22 +878,23 @@ int check_bank_rows(rau_ctx* ctx, int n_images, const int32_t* rows, const int32
 // ctx's buffer of expanded per-sample maps
 int ensure_table(rau_ctx* ctx, int si, bool pinned, bool bank = false) {
   const rau_config& c = ctx->cfg;
+  const size_t cap = (size_t)ctx->cap;   // sized once, for the capacity; contents are dense in the current size
   BatchSlot& s = ctx->slot[si];
   if (bank && !s.bank_idx_d)
-    if (int rc = dalloc(ctx, &s.bank_idx_d, 2 * (size_t)c.B)) return rc;
+    if (int rc = dalloc(ctx, &s.bank_idx_d, 2 * cap)) return rc;
   if (bank && pinned && !s.bank_idx_h) {
     void* h = nullptr;
-    hipError_t e = hipHostMalloc(&h, 2 * (size_t)c.B * 4, hipHostMallocDefault);
+    hipError_t e = hipHostMalloc(&h, 2 * cap * 4, hipHostMallocDefault);
     if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(bank index staging): %s", hipGetErrorString(e));
     s.bank_idx_h = static_cast<int32_t*>(h);
   }
   if (!s.image_of_d)
-    if (int rc = dalloc(ctx, &s.image_of_d, (size_t)c.B)) return rc;
+    if (int rc = dalloc(ctx, &s.image_of_d, cap)) return rc;
   if (!ctx->feats_x)
-    if (int rc = dalloc(ctx, &ctx->feats_x, (size_t)c.B * c.D * ctx->Sp)) return rc;
+    if (int rc = dalloc(ctx, &ctx->feats_x, cap * c.D * ctx->Sp)) return rc;
   if (pinned && !s.image_of_h) {
     void* h = nullptr;
-    hipError_t e = hipHostMalloc(&h, (size_t)c.B * 4, hipHostMallocDefault);
+    hipError_t e = hipHostMalloc(&h, cap * 4, hipHostMallocDefault);
     if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(image index staging): %s", hipGetErrorString(e));
     s.image_of_h = static_cast<int32_t*>(h);
   }
@@ -864,7 +905,10 @@ int ensure_table(rau_ctx* ctx, int si, bool pinned, bool bank = false) {
 int ensure_async(rau_ctx* ctx) {
   if (ctx->async_ready) return RAU_OK;
   const rau_config& c = ctx->cfg;
-  const size_t TB = (size_t)c.T * c.B, nf = (size_t)c.B * c.D * c.S;
+  // Sized for the capacity, and the staging's sub-arrays START where the capacity puts them; what a batch of the
+  // current size n writes into each of them is dense in n ([n,D,S], [T,n], [n], [n]).
+  const size_t B = (size_t)ctx->cap;
+  const size_t TB = (size_t)c.T * B, nf = B * c.D * c.S;
   BatchSlot& s0 = ctx->slot[0];
   s0.feats = ctx->feats; s0.tokens = ctx->tokens; s0.lens_d = ctx->lens_d; s0.labels_d = ctx->labels_d;
   s0.utok = ctx->utok; s0.ustart = ctx->ustart; s0.upos = ctx->upos;
@@ -872,16 +916,16 @@ int ensure_async(rau_ctx* ctx) {
   s0.have = ctx->have_batch; s0.have_labels = ctx->have_labels; s0.feat_type = ctx->feat_type;
   s0.n_images = ctx->n_images;   // (s0.bank / table_ok / bank_idx_d are kept in the slot itself)
   BatchSlot& s1 = ctx->slot[1];
-  if (int rc = dalloc(ctx, &s1.feats, (size_t)c.B * c.D * ctx->Sp)) return rc;
+  if (int rc = dalloc(ctx, &s1.feats, B * c.D * ctx->Sp)) return rc;
   if (int rc = dalloc(ctx, &s1.tokens, TB)) return rc;
-  if (int rc = dalloc(ctx, &s1.lens_d, (size_t)c.B)) return rc;
-  if (int rc = dalloc(ctx, &s1.labels_d, (size_t)c.B)) return rc;
+  if (int rc = dalloc(ctx, &s1.lens_d, B)) return rc;
+  if (int rc = dalloc(ctx, &s1.labels_d, B)) return rc;
   if (int rc = dalloc(ctx, &s1.utok, TB)) return rc;
   if (int rc = dalloc(ctx, &s1.ustart, TB + 1)) return rc;
   if (int rc = dalloc(ctx, &s1.upos, TB)) return rc;
   for (BatchSlot& s : ctx->slot) {
     // one pinned block per slot: feats | tokens | lens | labels | utok | ustart | upos
-    const size_t words = nf + TB + 2 * (size_t)c.B + TB + (TB + 1) + TB;
+    const size_t words = nf + TB + 2 * B + TB + (TB + 1) + TB;
     void* h = nullptr;
     hipError_t e = hipHostMalloc(&h, words * 4, hipHostMallocDefault);
     if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(batch staging, %zu bytes): %s", words * 4,
@@ -889,8 +933,8 @@ int ensure_async(rau_ctx* ctx) {
     s.feats_h = static_cast<float*>(h);
     s.tokens_h = reinterpret_cast<int32_t*>(s.feats_h + nf);
     s.lens_p = s.tokens_h + TB;
-    s.labels_h = s.lens_p + c.B;
-    s.utok_h = s.labels_h + c.B;
+    s.labels_h = s.lens_p + B;
+    s.utok_h = s.labels_h + B;
     s.ustart_h = s.utok_h + TB;
     s.upos_h = s.ustart_h + TB + 1;
     HIPC(hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming));
@@ -1157,6 +1201,111 @@ int rau_batch_feat_type(rau_ctx* ctx, int* feat_type) {
 int rau_batch_images(rau_ctx* ctx, int* n_images) {
   NEED(ctx && n_images, "null argument");
   *n_images = ctx->n_images;
+  return RAU_OK;
+}
+
+// ------------------------------------------------------------- batch size
+int rau_batch_size(rau_ctx* ctx, int32_t* n, int32_t* capacity) {
+  NEED(ctx, "null ctx");
+  if (n) *n = ctx->cfg.B;
+  if (capacity) *capacity = ctx->cap;
+  return RAU_OK;
+}
+
+// A split-K workspace the new size needs more of than is there (the needs are not monotonic in the batch size:
+// the split counts are chosen per shape): a second allocation, swapped in once all of them have succeeded.
+namespace {
+struct Regrow { float** ptr; size_t* have; size_t need; float* fresh; };
+}
+int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
+  NEED(ctx, "null ctx");
+  NEED(n >= 1 && n <= ctx->cap, "rau_set_batch_size: n=%d out of [1,%d] (the B of rau_create)", n, ctx->cap);
+  if (n == ctx->cfg.B) return RAU_OK;
+  if (ctx->prof_on) return fail(RAU_ERR_STATE, "rau_set_batch_size: profiling must be off");
+  BatchPlan plan;
+  plan_batch(ctx, n, &plan);
+  // ---- allocate first: a failure leaves the context at the old size
+  Regrow grow[3] = {{&ctx->slab, &ctx->slab_alloc, plan.slab, nullptr},
+                    {&ctx->slab2, &ctx->slab2_alloc, plan.slab2, nullptr},
+                    {&ctx->slab3, &ctx->slab3_alloc, plan.slab3, nullptr}};
+  for (Regrow& g : grow) {
+    if (g.need <= *g.have) continue;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&g.fresh), g.need * sizeof(float));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      for (Regrow& u : grow)
+        if (u.fresh) hipFree(u.fresh);
+      return fail(RAU_ERR_NOMEM, "rau_set_batch_size: hipMalloc(%zu bytes of split-K workspace) failed: %s; the "
+                  "context keeps %d samples", g.need * sizeof(float), hipGetErrorString(e), ctx->cfg.B);
+    }
+  }
+  // ---- nothing may still read or write what is about to change: all four streams drain (pending uploads of
+  // the asynchronous path included: they are dropped)
+  for (hipStream_t s : {ctx->stc, ctx->st3, ctx->st2, ctx->st})
+    if (s) HIPC(hipStreamSynchronize(s));
+  if (ctx->persist_used && ctx->perr_h && *ctx->perr_h) {
+    // the persistent encoder gave up in a step nobody has synchronised on yet: the finding is kept (persist_check)
+    ctx->persist_gave_up = true;
+    plan.enc_ws = plan.enc_ws_train = false;
+  }
+  for (Regrow& g : grow) {
+    if (!g.fresh) continue;
+    // captured steps hold the old workspace's address: all of them go (they are recaptured on demand)
+    for (auto& gr : ctx->graphs) hipGraphExecDestroy(gr.second);
+    ctx->graphs.clear();
+    split_ws_unregister(*g.ptr);
+    void* old = *g.ptr;
+    hipFree(old);
+    ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), old), ctx->allocs.end());
+    ctx->scratch.erase(std::remove_if(ctx->scratch.begin(), ctx->scratch.end(),
+                                      [&](const std::pair<void*, size_t>& r) { return r.first == old; }),
+                       ctx->scratch.end());
+    ctx->allocs.push_back(g.fresh);
+    ctx->scratch.push_back({g.fresh, g.need * sizeof(float)});
+    *g.ptr = g.fresh;
+    *g.have = g.need;
+  }
+  // ---- the switch: shapes, launch policy, and the fail-closed guard's picture of the workspaces (the spans a
+  // context of n samples would have registered; the allocations behind them are at least that large)
+  ctx->cfg.B = n;
+  adopt_plan(ctx, plan);
+  split_ws_register(ctx->slab, ctx->slab_floats);
+  split_ws_register(ctx->slab2, ctx->slab2_floats);
+  split_ws_register(ctx->slab3, ctx->slab3_floats);
+  // ---- every layout is dense in n, so what the old size left behind now lies where the step counts on the zeros
+  // of a fresh context (the initial-state rows of c1 / h1 / c2 / h2, the pad columns of 7x7 maps, workspaces whose
+  // tails are read as zeros): all batch-dependent storage is cleared, which is what rau_create leaves
+  for (const auto& r : ctx->scratch) HIPC(hipMemsetAsync(r.first, 0, r.second, ctx->st));
+  HIPC(hipStreamSynchronize(ctx->st));
+  // ---- host-side state of a fresh context: no batch, no uploads, seeded masks, no results
+  for (int si = 0; si < 2; ++si) {
+    BatchSlot& s = ctx->slot[si];
+    s.have = s.have_labels = s.upload_pending = s.consumed_valid = false;
+    s.bank = s.table_ok = false;
+    s.feat_type = RAU_FEAT_F32;
+    s.n_images = 0;
+    s.max_len = s.nuniq = 0;
+    s.lens.clear();
+    ++ctx->slot_serial[si];
+  }
+  if (ctx->async_ready) make_current(ctx, 0);
+  ctx->feat_type = RAU_FEAT_F32;
+  ctx->n_images = 0;
+  ctx->lens_h.clear();
+  ctx->max_len = ctx->nuniq = 0;
+  ctx->have_batch = ctx->have_labels = false;
+  ctx->x_valid = false;
+  ctx->fwd_table = false;
+  ctx->xw = nullptr;
+  ctx->fwd_done = ctx->bwd_done = false;
+  ctx->dpre_fwd = false;
+  ctx->I_shared = ctx->yq_shared = false;
+  ctx->cur.clear();
+  for (int i = 0; i < 5; ++i) ctx->mexplicit[i] = false;
+  ctx->mod_masks_valid = false;
+  ctx->mg_valid = ctx->mg_merged = ctx->mg_labels = false;
+  ctx->persist_used = false;
+  if (ctx->perr_h) *ctx->perr_h = 0;
   return RAU_OK;
 }
 
@@ -2388,6 +2537,7 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
   key |= (uint64_t)ctx->feat_type << 32;  // ... and read the batch in its element type
   key |= (uint64_t)(ctx->n_images > 0) << 34;   // ... through the gather of an image table (any table, any N)
   key |= (uint64_t)ctx->slot[ctx->cur_slot].bank << 35;   // ... of a bank batch: out of the bank
+  key |= (uint64_t)ctx->cfg.B << 36;      // every launch is shaped by the batch size (rau_set_batch_size)
   if (int rc = upload_hop_weights(ctx, hop_w)) return rc;
   ctx->mg_valid = false;
   hipGraphExec_t exec = nullptr;
@@ -2455,6 +2605,7 @@ static int persist_check(rau_ctx* ctx) {
   hipMemsetAsync(ctx->perr_d, 0, sizeof(int), ctx->st);
   hipStreamSynchronize(ctx->st);
   ctx->enc_ws = ctx->enc_ws_train = false;
+  ctx->persist_gave_up = true;
   ctx->persist_used = false;
   ctx->fwd_done = false;
   ctx->mg_valid = false;
@@ -2516,7 +2667,7 @@ int rau_get_att_state(rau_ctx* ctx, float* c, float* h) {
 static int merge_alloc(rau_ctx* ctx) {
   if (ctx->mg_ready) return RAU_OK;
   const rau_config& c = ctx->cfg;
-  const size_t B = c.B, H = c.H;
+  const size_t B = ctx->cap, H = c.H;   // sized for the capacity
 #define CK(x) do { if (int rc_ = (x)) return rc_; } while (0)
   CK(dalloc(ctx, &ctx->mg_rowf, B * (H + 2)));
   CK(dalloc(ctx, &ctx->mg_rowi, B * RAU_STATS_NCOUNTS(H)));
@@ -2619,8 +2770,8 @@ int rau_noise_clip_adam(rau_ctx* ctx, int64_t step_t, float lr, float mult_lr, f
   for (int gi = 0; gi < 3; ++gi) {
     Group& g = ctx->grp[gi];
     if (!g.m) {
-      if (int rc = dalloc(ctx, &g.m, g.n)) return rc;
-      if (int rc = dalloc(ctx, &g.v, g.n)) return rc;
+      if (int rc = dalloc(ctx, &g.m, g.n, false)) return rc;
+      if (int rc = dalloc(ctx, &g.v, g.n, false)) return rc;
     }
     g.adam_t += 1;
     const double bc1 = 1.0 - std::pow((double)beta1, (double)g.adam_t);

@@ -127,7 +127,7 @@ extern "C" {
 
 int rau_dev_alloc(rau_ctx* ctx, size_t n, float** out) {
   NEED(ctx && out, "null argument");
-  return dalloc(ctx, out, n);            // zero-filled, owned by the ctx
+  return dalloc(ctx, out, n, false);     // zero-filled, owned by the ctx; the caller's: no resize touches it
 }
 int rau_dev_free(rau_ctx* ctx, float* p) {
   NEED(ctx, "null ctx");

@@ -24,7 +24,7 @@ int mod_alloc(rau_ctx* ctx) {
   // position pitch Sp (S rounded up to a multiple of 4: 7x7 maps 49 -> 52), so when Sp != S the
   // feature map / d_attprob are re-pitched on the way in and attprob / d_X on the way out.
   const rau_config& c = ctx->cfg;
-  const size_t B = c.B, Q = ctx->Q;
+  const size_t B = ctx->cap, Q = ctx->Q;   // sized for the capacity; contents dense in the current batch size
   const size_t wide = std::max<size_t>({(size_t)c.Rq, (size_t)c.R, (size_t)c.M});
 #define CK(x) do { if (int rc_ = (x)) return rc_; } while (0)
   CK(dalloc(ctx, &ctx->m_state, (size_t)c.T * B * Q));
@@ -85,7 +85,7 @@ int resident_feats(rau_ctx* ctx, const float** X) {
   const float* src = *X;
   const rau_config& c = ctx->cfg;
   if (!ctx->m_Xw)
-    if (int rc = dalloc(ctx, &ctx->m_Xw, (size_t)c.B * c.D * ctx->Sp)) return rc;
+    if (int rc = dalloc(ctx, &ctx->m_Xw, (size_t)ctx->cap * c.D * ctx->Sp)) return rc;
   RUN("widen_features", 0, (double)c.B * c.D * ctx->Sp * 6,
       widen_features(ctx->st, (size_t)c.B * c.D, c.S, ctx->Sp, src, ctx->m_Xw, ctx->feat_type));
   *X = ctx->m_Xw;
@@ -431,8 +431,8 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
   // ---- feature-map gradient (the reference computes it and SS:579 throws it away): on request
   if (d_X) {
     if (!ctx->m_dX) {
-      if (int rc = dalloc(ctx, &ctx->m_dX, (size_t)B * D * S)) return rc;
-      if (int rc = dalloc(ctx, &ctx->m_dZ, BM_ * S)) return rc;
+      if (int rc = dalloc(ctx, &ctx->m_dX, (size_t)ctx->cap * D * S)) return rc;
+      if (int rc = dalloc(ctx, &ctx->m_dZ, (size_t)ctx->cap * M * S)) return rc;
     }
     RUN("mul_dtanh", 0, BM_ * S * 12.0, mul_dtanh(st, BM_ * S, dZh, Ih, ctx->m_dZ));
     RUN("conv_embed_dgrad", gflop(D, (double)B * S, M), (BM_ * S + (double)B * D * S) * 4,
@@ -440,7 +440,7 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
     float* dXo = ctx->m_dX;
     if (S != SL) {   // dense [B,D,SL] for the caller (reuses the re-pitch buffer's sibling)
       if (!ctx->m_dXd)
-        if (int rc = dalloc(ctx, &ctx->m_dXd, (size_t)B * D * SL)) return rc;
+        if (int rc = dalloc(ctx, &ctx->m_dXd, (size_t)ctx->cap * D * SL)) return rc;
       if (int rc = repitch(ctx, ctx->m_dXd, SL, ctx->m_dX, S, (size_t)B * D)) return rc;
       dXo = ctx->m_dXd;
     }

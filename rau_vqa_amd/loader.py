@@ -299,7 +299,9 @@ def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=12
 def feed(rau, batch, feat_type=None):
     """next_batch_feat's tuple -> rau_set_batch (the H2D of SS:434-439); returns qids.
     feat_type: that of the feats (needed for bf16, which arrives as uint16 bits).  A tuple of
-    next_batch_feat(unique=True) goes up as an image table, one of next_batch_rows as a bank batch."""
+    next_batch_feat(unique=True) goes up as an image table, one of next_batch_rows as a bank batch.
+    The batch may be smaller than the context's capacity (a test split at test_batch_size): set_batch
+    takes the size from x_len and switches the context to it."""
     if batch[0].ndim == 1:                                # next_batch_rows: rows, image_of, x, x_len, a, qids
         rows, image_of, x, x_len, a, qids = batch
         rau.set_batch(None, x, x_len, a if a.ndim == 1 else None, bank_rows=rows, image_of=image_of)
@@ -327,11 +329,19 @@ class SlotFeeder:
         for it in range(n):
             rau.forward(); rau.backward(w); ...              # enqueue step `it`
             qids = feeder.next()                              # batch it+1 resident for the next step
+
+    A feeder is BOUND to one batch size, the DataClass's: if the context runs another size when the
+    feeder is made (a test split at test_batch_size below the capacity) it is switched first
+    (rau.set_batch_size), and a feeder whose context has been switched since refuses to go on -- the
+    switch dropped the slots it had filled.  Make a new feeder after every set_batch_size.
     """
 
     def __init__(self, rau, data: DataClass, tab_featpaths, feat_dim, feat_w=1, feat_h=1,
                  feat_type=None, share_images=False, bank=False):
         self.rau, self.data = rau, data
+        self.n = int(data.batch_size)
+        if getattr(rau, "batch_size", self.n) != self.n:
+            rau.set_batch_size(self.n)     # raises above the capacity
         # bank=True: the maps are in rau's feature bank (DataClass.fill_bank); a batch is next_batch_rows' tuple,
         # there is no prefetch worker and nothing is written to the slots' feature staging
         self.bank = bool(bank)
@@ -350,6 +360,9 @@ class SlotFeeder:
 
     def _advance(self):
         d, rau, s = self.data, self.rau, self.slot
+        if getattr(rau, "batch_size", self.n) != self.n:
+            raise RuntimeError(f"this SlotFeeder feeds batches of {self.n}; the context now runs "
+                               f"{rau.batch_size}: make a new feeder after set_batch_size")
         view = rau.batch_slot(s, **self._ft)          # (host-waits until the slot's last upload has left)
         self.slot = s ^ 1                             # the worker started by next_batch_feat fills the other
         if self.bank:

@@ -20,7 +20,7 @@ from . import feat16
 @dataclass
 class Config:
     """Network sizes; defaults are the reference's hard-coded locals (SS:202-229)."""
-    B: int = 100
+    B: int = 100            # the context's CAPACITY: RAU.set_batch_size(n <= B) runs smaller batches on it
     T: int = 26
     V: int = 14000
     E: int = 200
@@ -44,10 +44,12 @@ class Config:
     def Q(self) -> int:
         return 4 * self.Rq
 
-    def mask_shapes(self):
-        return {"we": (self.T, self.B, self.E), "rnn": (self.T, self.B, self.Rq),
-                "q": (self.H, self.B, self.Q), "x": (self.H, self.B, self.D, self.S),
-                "mf": (self.H, self.B, self.M)}
+    def mask_shapes(self, n=None):
+        """Shapes of the five mask sites at batch size n (default: the capacity B)."""
+        B = self.B if n is None else int(n)
+        return {"we": (self.T, B, self.E), "rnn": (self.T, B, self.Rq),
+                "q": (self.H, B, self.Q), "x": (self.H, B, self.D, self.S),
+                "mf": (self.H, B, self.M)}
 
 
 def hop_weights(variant: str, H: int, epoch: int = 0):
@@ -83,6 +85,37 @@ class RAU:
         h = C.c_void_p()
         L.check(self._lib.rau_create(C.byref(c), C.byref(h)))
         self._h = h
+        self._n = int(cfg.B)       # current batch size (rau_set_batch_size); cfg.B stays the capacity
+
+    # ---- batch size: one context runs batches of up to cfg.B rows (rau_set_batch_size)
+    @property
+    def capacity(self) -> int:
+        return int(self.cfg.B)
+
+    @property
+    def batch_size(self) -> int:
+        """Rows of every batch and result tensor from now on (what set_batch_size last set)."""
+        return self._n
+
+    def set_batch_size(self, n: int):
+        """The context now behaves, bit for bit, like one created with B = n holding the same parameters,
+        gradients, optimizer state, dropout seed, mode and bank.  The resident batch, both upload slots,
+        explicit masks and the last results do not outlive the call (n == batch_size: a no-op).  It drains
+        the streams and clears the activation storage: per epoch, not per step."""
+        n = int(n)
+        if not 1 <= n <= self.capacity:
+            raise ValueError(f"batch size {n} out of [1, {self.capacity}] (the B the context was created with)")
+        L.check(self._lib.rau_set_batch_size(self._h, n))
+        self._n = n
+
+    def _rows(self, lens, what):
+        """The batch size a batch's lens [n] asks for, checked against the capacity (no library call)."""
+        if lens.ndim != 1 or lens.shape[0] < 1:
+            raise ValueError(f"{what}: lens must be [n]")
+        n = int(lens.shape[0])
+        if n > self.capacity:
+            raise ValueError(f"{what}: {n} rows exceed the context's capacity of {self.capacity}")
+        return n
 
     def close(self):
         if getattr(self, "_h", None):
@@ -179,18 +212,18 @@ class RAU:
             L.check(self._lib.rau_set_mask(self._h, L.MASK_SITES[k], m.ctypes.data, m.size))
 
     def get_mask(self, site: str):
-        shape = self.cfg.mask_shapes()[site]
+        shape = self.cfg.mask_shapes(self._n)[site]
         m = np.empty(int(np.prod(shape)), np.uint8)
         L.check(self._lib.rau_get_mask(self._h, L.MASK_SITES[site], m.ctypes.data, m.size))
         return m.reshape(shape)
 
     # ---- batch + the hot path
-    def _image_index(self, feats, image_of):
-        """(n_images, index array) of a batch whose feats [N, D, ...] is an image table."""
+    def _image_index(self, feats, image_of, rows):
+        """(n_images, index array) of a batch of `rows` samples whose feats [N, D, ...] is an image table."""
         c = self.cfg
         image_of = np.ascontiguousarray(image_of, np.int32)
         n = int(feats.shape[0]) if feats.ndim >= 2 else 0
-        if image_of.shape != (c.B,) or n < 1 or feats.size != n * c.D * c.S:
+        if image_of.shape != (rows,) or n < 1 or feats.size != n * c.D * c.S:
             raise ValueError("image table shapes do not match the config")
         return n, image_of
 
@@ -225,19 +258,18 @@ class RAU:
         L.check(self._lib.rau_bank_get(self._h, int(first), int(count), out.ctypes.data))
         return out
 
-    def _bank_index(self, bank_rows, image_of):
-        """(n_images, rows, image_of) of a bank batch; image_of None with B rows is the identity."""
-        c = self.cfg
+    def _bank_index(self, bank_rows, image_of, B):
+        """(n_images, rows, image_of) of a bank batch of B samples; image_of None with B rows is the identity."""
         rows = np.ascontiguousarray(bank_rows, np.int32)
         if rows.ndim != 1 or rows.size < 1:
             raise ValueError("bank_rows must be a 1-d array of bank rows")
         if image_of is None:
-            if rows.size != c.B:
+            if rows.size != B:
                 raise ValueError("bank_rows without image_of needs one row per sample")
-            image_of = np.arange(c.B, dtype=np.int32)
+            image_of = np.arange(B, dtype=np.int32)
         image_of = np.ascontiguousarray(image_of, np.int32)
-        if image_of.shape != (c.B,):
-            raise ValueError("image_of must have B entries")
+        if image_of.shape != (B,):
+            raise ValueError("image_of must have one entry per sample")
         return int(rows.size), rows, image_of
 
     def set_batch(self, feats, tokens, lens, labels=None, feat_type=None, image_of=None, bank_rows=None):
@@ -245,41 +277,47 @@ class RAU:
         gives the same results, bit for bit, as the f32 map of its widened values.
         image_of [B] (0-based rows): feats is an image TABLE [N, D, S] that the questions of one image
         share; the same results, bit for bit, as the plain batch feats[image_of].
-        bank_rows [N] (feats None): the table is bank[bank_rows], gathered inside device memory."""
+        bank_rows [N] (feats None): the table is bank[bank_rows], gathered inside device memory.
+        The batch size is lens.shape[0]: a batch of n <= capacity rows switches the context to n first
+        (set_batch_size); every array must agree on n, checked before anything reaches the library."""
         c = self.cfg
+        lens = np.ascontiguousarray(lens, np.int32)
+        B = self._rows(lens, "set_batch")
         if bank_rows is not None:
             if feats is not None:
                 raise ValueError("a bank batch takes bank_rows, not feats")
-            n_images, rows, image_of = self._bank_index(bank_rows, image_of)
+            n_images, rows, image_of = self._bank_index(bank_rows, image_of, B)
             tokens = np.ascontiguousarray(tokens, np.int32)
-            lens = np.ascontiguousarray(lens, np.int32)
-            if tokens.shape != (c.T, c.B) or lens.shape != (c.B,):
+            if tokens.shape != (c.T, B):
                 raise ValueError("batch shapes do not match the config")
             lp = None
             if labels is not None:
                 labels = np.ascontiguousarray(labels, np.int32)
-                if labels.shape != (c.B,):
+                if labels.shape != (B,):
                     raise ValueError("labels shape")
                 lp = labels.ctypes.data
+            if B != self._n:
+                self.set_batch_size(B)
             L.check(self._lib.rau_set_batch_bank(self._h, n_images, rows.ctypes.data, image_of.ctypes.data,
                                                  tokens.ctypes.data, lens.ctypes.data, lp))
             return
         feats, ft = feat16.as_feats(feats, feat_type)
         tokens = np.ascontiguousarray(tokens, np.int32)
-        lens = np.ascontiguousarray(lens, np.int32)
         n_images = 0
         if image_of is not None:
-            n_images, image_of = self._image_index(feats, image_of)
-        elif feats.size != c.B * c.D * c.S:
+            n_images, image_of = self._image_index(feats, image_of, B)
+        elif feats.size != B * c.D * c.S:
             raise ValueError("batch shapes do not match the config")
-        if tokens.shape != (c.T, c.B) or lens.shape != (c.B,):
+        if tokens.shape != (c.T, B):
             raise ValueError("batch shapes do not match the config")
         lp = None
         if labels is not None:
             labels = np.ascontiguousarray(labels, np.int32)
-            if labels.shape != (c.B,):
+            if labels.shape != (B,):
                 raise ValueError("labels shape")
             lp = labels.ctypes.data
+        if B != self._n:
+            self.set_batch_size(B)
         if image_of is not None:
             L.check(self._lib.rau_set_batch_images(self._h, feats.ctypes.data, feat16.FEAT_TYPES[ft], n_images,
                                                    image_of.ctypes.data, tokens.ctypes.data, lens.ctypes.data,
@@ -302,21 +340,22 @@ class RAU:
 
     # asynchronous, double-buffered upload (rau_batch_slot / rau_set_batch_async / rau_use_batch)
     def batch_slot(self, slot, feat_type="f32"):
-        """numpy views of slot's PINNED staging: {feats [B,D,S], tokens [T,B], lens [B], labels [B]}.
+        """numpy views of slot's PINNED staging: {feats [n,D,S], tokens [T,n], lens [n], labels [n]},
+        n = the current batch_size (each array starts where the capacity puts it and is dense in n).
         A loader fills them in place; set_batch_async(slot) then uploads without a host copy.
         feats is a view of the staging's start in feat_type's dtype (bf16: uint16 bit patterns);
         upload it with set_batch_async(slot, feat_type=<the same>)."""
-        c = self.cfg
+        c, B = self.cfg, self._n
         fdt = feat16.dtype_of(feat_type)
         p = [C.c_void_p() for _ in range(4)]
         L.check(self._lib.rau_batch_slot(self._h, slot, *[C.byref(x) for x in p]))
 
         def view(ptr, n, ct, dt, shape):
             return np.frombuffer((ct * n).from_address(ptr.value), dtype=dt).reshape(shape)
-        return {"feats": view(p[0], c.B * c.D * c.S, C.c_uint8 * fdt.itemsize, fdt, (c.B, c.D, c.S)),
-                "tokens": view(p[1], c.T * c.B, C.c_int32, np.int32, (c.T, c.B)),
-                "lens": view(p[2], c.B, C.c_int32, np.int32, (c.B,)),
-                "labels": view(p[3], c.B, C.c_int32, np.int32, (c.B,))}
+        return {"feats": view(p[0], B * c.D * c.S, C.c_uint8 * fdt.itemsize, fdt, (B, c.D, c.S)),
+                "tokens": view(p[1], c.T * B, C.c_int32, np.int32, (c.T, B)),
+                "lens": view(p[2], B, C.c_int32, np.int32, (B,)),
+                "labels": view(p[3], B, C.c_int32, np.int32, (B,))}
 
     def set_batch_async(self, slot, feats=None, tokens=None, lens=None, labels=None, has_labels=True,
                         feat_type=None, image_of=None, n_images=None, bank_rows=None):
@@ -325,29 +364,37 @@ class RAU:
         set_batch; with feats None it names what the staging holds (default "f32").
         image_of [B]: the batch carries an image table (see set_batch) of feats.shape[0] maps, or, with
         feats None, of the n_images maps at the start of the slot's staging; only those are uploaded.
-        bank_rows [N] (feats None): the table is bank[bank_rows]; the slot's feature staging is not read."""
+        bank_rows [N] (feats None): the table is bank[bank_rows]; the slot's feature staging is not read.
+        The batch size is lens.shape[0] when lens is given (the context is switched to it first, which
+        drops both slots' earlier uploads), else the current batch_size."""
         c = self.cfg
+        B = self._n
+        if lens is not None:
+            lens = np.ascontiguousarray(lens, np.int32)
+            B = self._rows(lens, "set_batch_async")
         if bank_rows is not None:
             if feats is not None:
                 raise ValueError("a bank batch takes bank_rows, not feats")
-            nmaps, rows, image_of = self._bank_index(bank_rows, image_of)
+            nmaps, rows, image_of = self._bank_index(bank_rows, image_of, B)
             keep = [None if a is None else np.ascontiguousarray(a, np.int32) for a in (tokens, lens, labels)]
-            for a, n in zip(keep, (c.T * c.B, c.B, c.B)):
+            for a, n in zip(keep, (c.T * B, B, B)):
                 if a is not None and a.size != n:
                     raise ValueError("batch shapes do not match the config")
+            if B != self._n:
+                self.set_batch_size(B)
             tp, lp, yp = [None if a is None else a.ctypes.data for a in keep]
             L.check(self._lib.rau_set_batch_async_bank(self._h, slot, nmaps, rows.ctypes.data,
                                                        image_of.ctypes.data, tp, lp, yp, int(bool(has_labels))))
             return
-        nmaps = c.B
+        nmaps = B
         if image_of is not None:
             if feats is None:
                 image_of = np.ascontiguousarray(image_of, np.int32)
-                if image_of.shape != (c.B,) or n_images is None:
+                if image_of.shape != (B,) or n_images is None:
                     raise ValueError("an in-place image table needs image_of [B] and n_images")
                 nmaps = int(n_images)
             else:
-                nmaps, image_of = self._image_index(np.asarray(feats), image_of)
+                nmaps, image_of = self._image_index(np.asarray(feats), image_of, B)
         if feats is None:
             ft = feat16.check_name(feat_type or "f32")
         else:
@@ -361,9 +408,11 @@ class RAU:
                 raise ValueError("batch shapes do not match the config")
             return a.ctypes.data, a
         fp, fk = ptr(feats, feat16.dtype_of(ft), nmaps * c.D * c.S)
-        tp, tk = ptr(tokens, np.int32, c.T * c.B)
-        lp, lk = ptr(lens, np.int32, c.B)
-        yp, yk = ptr(labels, np.int32, c.B)
+        tp, tk = ptr(tokens, np.int32, c.T * B)
+        lp, lk = ptr(lens, np.int32, B)
+        yp, yk = ptr(labels, np.int32, B)
+        if B != self._n:
+            self.set_batch_size(B)
         if image_of is not None:
             L.check(self._lib.rau_set_batch_async_images(self._h, slot, fp, feat16.FEAT_TYPES[ft], nmaps,
                                                          image_of.ctypes.data, tp, lp, yp,
@@ -411,22 +460,22 @@ class RAU:
         return self._out(self._lib.rau_get_losses, (self.cfg.H,))
 
     def argmax(self):
-        return self._out(self._lib.rau_get_argmax, (self.cfg.H, self.cfg.B), np.int32)
+        return self._out(self._lib.rau_get_argmax, (self.cfg.H, self._n), np.int32)
 
     def logits(self):
-        return self._out(self._lib.rau_get_logits, (self.cfg.H, self.cfg.B, self.cfg.K))
+        return self._out(self._lib.rau_get_logits, (self.cfg.H, self._n, self.cfg.K))
 
     def dopred(self):
-        return self._out(self._lib.rau_get_dopred, (self.cfg.H, self.cfg.B))
+        return self._out(self._lib.rau_get_dopred, (self.cfg.H, self._n))
 
     def attention(self):
-        return self._out(self._lib.rau_get_attention, (self.cfg.H, self.cfg.B, self.cfg.S))
+        return self._out(self._lib.rau_get_attention, (self.cfg.H, self._n, self.cfg.S))
 
     def question_state(self):
-        return self._out(self._lib.rau_get_question_state, (self.cfg.B, self.cfg.Q))
+        return self._out(self._lib.rau_get_question_state, (self._n, self.cfg.Q))
 
     def att_state(self):
-        c = np.empty((self.cfg.H, self.cfg.B, self.cfg.R), np.float32)
+        c = np.empty((self.cfg.H, self._n, self.cfg.R), np.float32)
         h = np.empty_like(c)
         L.check(self._lib.rau_get_att_state(self._h, c.ctypes.data, h.ctypes.data))
         return c, h
@@ -450,7 +499,7 @@ class RAU:
         """predict_result's answers of the last forward (SS:633-705, 877-900, last hop forced):
         (oe [H+2, B], mc [H+2, B] or None), 1-based, rows = hops, uni, select.  mc_ans: int
         [B, n] candidate ids, 0 = empty slot."""
-        H, B = self.cfg.H, self.cfg.B
+        H, B = self.cfg.H, self._n
         oe = np.empty((H + 2, B), np.int32)
         if mc_ans is None:
             L.check(self._lib.rau_predict(self._h, None, 0, oe.ctypes.data, None))
@@ -465,8 +514,8 @@ class RAU:
     def merged(self):
         """Merged rows of the last predict(): pred [2, B, K], att [2, B, S] (uni, select; select
         without the reference's carried test_select_att)."""
-        pred = np.empty((2, self.cfg.B, self.cfg.K), np.float32)
-        att = np.empty((2, self.cfg.B, self.cfg.S), np.float32)
+        pred = np.empty((2, self._n, self.cfg.K), np.float32)
+        att = np.empty((2, self._n, self.cfg.S), np.float32)
         L.check(self._lib.rau_get_merged(self._h, pred.ctypes.data, att.ctypes.data))
         return pred, att
 

@@ -50,7 +50,7 @@ class EmbedClone(_Clone):
     def forward(self, x_t):
         out = C.c_void_p()
         L.check(self._lib.rau_embed_forward(self._h, self.i, _p(x_t), C.byref(out)))
-        return self._view(out, self.rau.cfg.B, self.rau.cfg.E)
+        return self._view(out, self.rau.batch_size, self.rau.cfg.E)
 
     def backward(self, x_t, d_we):
         L.check(self._lib.rau_embed_backward(self._h, self.i, _p(x_t), _p(d_we)))
@@ -62,14 +62,14 @@ class DeepLSTMClone(_Clone):
     def forward(self, x, state):
         out = C.c_void_p()
         L.check(self._lib.rau_deeplstm_forward(self._h, self.i, _p(x), _p(state), C.byref(out)))
-        return self._view(out, self.rau.cfg.B, self.rau.cfg.Q)
+        return self._view(out, self.rau.batch_size, self.rau.cfg.Q)
 
     def backward(self, x, state, d_state_out):
         dx, ds = C.c_void_p(), C.c_void_p()
         L.check(self._lib.rau_deeplstm_backward(self._h, self.i, _p(x), _p(state),
                                                 _p(d_state_out), C.byref(dx), C.byref(ds)))
         c = self.rau.cfg
-        return self._view(dx, c.B, c.E), self._view(ds, c.B, c.Q)
+        return self._view(dx, self.rau.batch_size, c.E), self._view(ds, self.rau.batch_size, c.Q)
 
 
 class MultimodalClone(_Clone):
@@ -80,9 +80,9 @@ class MultimodalClone(_Clone):
         L.check(self._lib.rau_multimodal_forward(self._h, self.i, _p(q), _p(X), _p(c_prev),
                                                  _p(h_prev), *[C.byref(o) for o in outs]))
         c = self.rau.cfg
-        return (self._view(outs[0], c.B, c.K), self._view(outs[1], c.B),
-                self._view(outs[2], c.B, c.S), self._view(outs[3], c.B, c.R),
-                self._view(outs[4], c.B, c.R))
+        return (self._view(outs[0], self.rau.batch_size, c.K), self._view(outs[1], self.rau.batch_size),
+                self._view(outs[2], self.rau.batch_size, c.S), self._view(outs[3], self.rau.batch_size, c.R),
+                self._view(outs[4], self.rau.batch_size, c.R))
 
     def backward(self, q, X, c_prev, h_prev, d_logits, d_do_pred=None, d_attprob=None, d_c=None,
                  d_h=None, want_dX=False):
@@ -94,9 +94,9 @@ class MultimodalClone(_Clone):
             self._h, self.i, _p(q), _p(X), _p(c_prev), _p(h_prev), _p(d_logits), _p(d_do_pred),
             _p(d_attprob), _p(d_c), _p(d_h), *refs))
         c = self.rau.cfg
-        dX = self._view(outs[1], c.B, c.D, c.S) if want_dX else None
-        return (self._view(outs[0], c.B, c.Q), dX, self._view(outs[2], c.B, c.R),
-                self._view(outs[3], c.B, c.R))
+        dX = self._view(outs[1], self.rau.batch_size, c.D, c.S) if want_dX else None
+        return (self._view(outs[0], self.rau.batch_size, c.Q), dX, self._view(outs[2], self.rau.batch_size, c.R),
+                self._view(outs[3], self.rau.batch_size, c.R))
 
 
 class CriterionClone(_Clone):
@@ -112,7 +112,7 @@ class CriterionClone(_Clone):
         out = C.c_void_p()
         L.check(self._lib.rau_criterion_backward(self._h, self.i, _p(logits), _p(y), float(scale),
                                                  C.byref(out)))
-        return self._view(out, self.rau.cfg.B, self.rau.cfg.K)
+        return self._view(out, self.rau.batch_size, self.rau.cfg.K)
 
 
 def feval(rau, feats, x, x_len, y, hop_w):
@@ -136,17 +136,17 @@ def _feval(rau, feats, x, x_len, y, hop_w):
     crit = [CriterionClone(rau, h) for h in range(c.H)]
     max_len = int(x_len.max().item())                      # SS:444
     # ---- encoder forward, SS:446-462
-    state = [torch.zeros(c.B, c.Q, device=dev)]            # init_state, SS:358
+    state = [torch.zeros(rau.batch_size, c.Q, device=dev)]            # init_state, SS:358
     we = []
-    rnn_out = torch.zeros(c.B, c.Q, device=dev)
+    rnn_out = torch.zeros(rau.batch_size, c.Q, device=dev)
     for t in range(max_len):
         we.append(emb[t].forward(x[t]))
         state.append(rnn[t].forward(we[t], state[t]))
         sel = (x_len == t + 1).unsqueeze(1)                # SS:455-461
         rnn_out = torch.where(sel, state[t + 1], rnn_out)
     # ---- hops forward, SS:467-520
-    att_c = [torch.zeros(c.B, c.R, device=dev)]            # SS:362-365
-    att_h = [torch.zeros(c.B, c.R, device=dev)]
+    att_c = [torch.zeros(rau.batch_size, c.R, device=dev)]            # SS:362-365
+    att_h = [torch.zeros(rau.batch_size, c.R, device=dev)]
     logits, losses, answers = [], [], []
     for h in range(c.H):
         lg, _dp, _a, cn, hn = mm[h].forward(rnn_out, feats, att_c[h], att_h[h])
@@ -157,14 +157,14 @@ def _feval(rau, feats, x, x_len, y, hop_w):
         answers.append(torch.argmax(lg, dim=1) + 1)        # SS:488 (ties: see rau_get_argmax)
     # ---- hops backward, SS:561-579
     d_c = d_h = None                                       # zeros, SS:561-562
-    d_q = torch.zeros(c.B, c.Q, device=dev)
+    d_q = torch.zeros(rau.batch_size, c.Q, device=dev)
     for h in reversed(range(c.H)):
         dl = crit[h].backward(logits[h], y, float(hop_w[h]))   # SS:565-569
         dq_h, _dX, d_c, d_h = mm[h].backward(rnn_out, feats, att_c[h], att_h[h], dl, None, None,
                                               d_c, d_h)
         d_q += dq_h                                        # ConcatTable backward, SS:579
     # ---- encoder backward, SS:581-596
-    d_state = torch.zeros(c.B, c.Q, device=dev)
+    d_state = torch.zeros(rau.batch_size, c.Q, device=dev)
     for t in reversed(range(max_len)):
         sel = (x_len == t + 1).unsqueeze(1)                # rows REPLACED by dq, SS:584-591
         d_out = torch.where(sel, d_q, d_state)
@@ -387,34 +387,34 @@ def feval_dev(rau, feats, x, x_len_host, y, hop_w, row_loop=False):
 
     def select(dst, src, t):
         if row_loop:
-            for k in range(c.B):
+            for k in range(rau.batch_size):
                 if x_len_host[k] == t:
                     dst[k] = src[k]
         else:
             dst.select_rows(src, x_len_dev, t)
 
-    state = [DevTensor.zeros(rau, c.B, c.Q)]
+    state = [DevTensor.zeros(rau, rau.batch_size, c.Q)]
     we = []
-    rnn_out = DevTensor.zeros(rau, c.B, c.Q)
+    rnn_out = DevTensor.zeros(rau, rau.batch_size, c.Q)
     for t in range(max_len):
         o = C.c_void_p()
         L.check(lib.rau_embed_forward(h, t, _cp(x[t]), C.byref(o)))
-        we.append(DevTensor.wrap(rau, o, c.B, c.E))
+        we.append(DevTensor.wrap(rau, o, rau.batch_size, c.E))
         o = C.c_void_p()
         L.check(lib.rau_deeplstm_forward(h, t, _cp(we[t]), _cp(state[t]), C.byref(o)))
-        state.append(DevTensor.wrap(rau, o, c.B, c.Q))
+        state.append(DevTensor.wrap(rau, o, rau.batch_size, c.Q))
         select(rnn_out, state[t + 1], t + 1)
-    att_c, att_h = [DevTensor.zeros(rau, c.B, c.R)], [DevTensor.zeros(rau, c.B, c.R)]
-    uni = DevTensor.zeros(rau, c.B, c.K)
+    att_c, att_h = [DevTensor.zeros(rau, rau.batch_size, c.R)], [DevTensor.zeros(rau, rau.batch_size, c.R)]
+    uni = DevTensor.zeros(rau, rau.batch_size, c.K)
     logits, losses, correct = [], [], []
     for hop in range(c.H):
         outs = [C.c_void_p() for _ in range(5)]
         L.check(lib.rau_multimodal_forward(h, hop, _cp(rnn_out), _cp(feats), _cp(att_c[hop]),
                                            _cp(att_h[hop]), *[C.byref(o) for o in outs]))
-        lg = DevTensor.wrap(rau, outs[0], c.B, c.K)
+        lg = DevTensor.wrap(rau, outs[0], rau.batch_size, c.K)
         logits.append(lg)
-        att_c.append(DevTensor.wrap(rau, outs[3], c.B, c.R))
-        att_h.append(DevTensor.wrap(rau, outs[4], c.B, c.R))
+        att_c.append(DevTensor.wrap(rau, outs[3], rau.batch_size, c.R))
+        att_h.append(DevTensor.wrap(rau, outs[4], rau.batch_size, c.R))
         _, ans = lg.max(2)                                   # SS:488
         correct.append(ans.eq_sum(y))                        # SS:489-492
         uni.add(lg)                                          # SS:522-526
@@ -422,28 +422,28 @@ def feval_dev(rau, feats, x, x_len_host, y, hop_w, row_loop=False):
         L.check(lib.rau_criterion_forward(h, hop, _cp(lg), _cp(y), C.byref(loss)))
         losses.append(loss.value)
     d_c = d_h = None
-    d_q = DevTensor.zeros(rau, c.B, c.Q)
+    d_q = DevTensor.zeros(rau, rau.batch_size, c.Q)
     for hop in reversed(range(c.H)):
         o = C.c_void_p()
         L.check(lib.rau_criterion_backward(h, hop, _cp(logits[hop]), _cp(y), float(hop_w[hop]),
                                            C.byref(o)))
-        dl = DevTensor.wrap(rau, o, c.B, c.K)
+        dl = DevTensor.wrap(rau, o, rau.batch_size, c.K)
         outs = [C.c_void_p() for _ in range(4)]
         L.check(lib.rau_multimodal_backward(h, hop, _cp(rnn_out), _cp(feats), _cp(att_c[hop]),
                                             _cp(att_h[hop]), _cp(dl), None, None, _cp(d_c),
                                             _cp(d_h), C.byref(outs[0]), None, C.byref(outs[2]),
                                             C.byref(outs[3])))
-        d_q.add(DevTensor.wrap(rau, outs[0], c.B, c.Q))      # ConcatTable backward, SS:579
-        d_c = DevTensor.wrap(rau, outs[2], c.B, c.R)
-        d_h = DevTensor.wrap(rau, outs[3], c.B, c.R)
-    d_state = DevTensor.zeros(rau, c.B, c.Q)
-    d_out = DevTensor.zeros(rau, c.B, c.Q)
+        d_q.add(DevTensor.wrap(rau, outs[0], rau.batch_size, c.Q))      # ConcatTable backward, SS:579
+        d_c = DevTensor.wrap(rau, outs[2], rau.batch_size, c.R)
+        d_h = DevTensor.wrap(rau, outs[3], rau.batch_size, c.R)
+    d_state = DevTensor.zeros(rau, rau.batch_size, c.Q)
+    d_out = DevTensor.zeros(rau, rau.batch_size, c.Q)
     for t in reversed(range(max_len)):
         d_out.copy(d_state)
         select(d_out, d_q, t + 1)                            # rows REPLACED by dq, SS:584-591
         dx, ds = C.c_void_p(), C.c_void_p()
         L.check(lib.rau_deeplstm_backward(h, t, _cp(we[t]), _cp(state[t]), _cp(d_out),
                                           C.byref(dx), C.byref(ds)))
-        d_state = DevTensor.wrap(rau, ds, c.B, c.Q)
+        d_state = DevTensor.wrap(rau, ds, rau.batch_size, c.Q)
         L.check(lib.rau_embed_backward(h, t, _cp(x[t]), dx))
     return losses, correct, uni

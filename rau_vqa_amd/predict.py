@@ -85,7 +85,9 @@ def predict_result_device(rau, feats, tokens, lens, mc_ans=None, select_att_stat
     (rau_predict): same keys, same values bit for bit.  The select attention row comes back without
     the reference's carried test_select_att; select_att_state is added here, as merge_hops does.
     tabs=False skips downloading the per-hop logits and maps: tab_pred / tab_att are then None and
-    only the answers (and nothing of [H, B, K]) cross PCIe.  image_of: as in predict_result."""
+    only the answers (and nothing of [H, B, K]) cross PCIe.  image_of: as in predict_result.
+    Like predict_result it takes batches below the context's capacity (the test split's 83 rows on a
+    context trained at 100): set_batch switches the context to lens.shape[0] rows first."""
     rau.evaluate()
     rau.set_batch(feats, tokens, lens, None, image_of=image_of)
     rau.forward()
