@@ -1,0 +1,618 @@
+// rau_batch.hip -- how a batch reaches a context (include/rau.h: batch, 16-bit maps, image tables, feature
+// bank, asynchronous upload) and how the step reads it back (batch_maps).
+//
+// A context has two batch slots (rau_ctx.h: BatchSlot); slot[cur_slot] is the resident batch and the only
+// record of it.  There is ONE upload path with two front ends:
+//   set_batch_sync  -- into the current slot, on the chain stream, from the caller's memory; synchronising;
+//   set_batch_slot  -- into either slot, on the copy stream, from the slot's pinned staging; ordered against
+//                      the steps by the slot's two events, made current by rau_use_batch.
+// Both check the arguments (check_images, index_batch), describe the batch as one `Batch`, enqueue its copies
+// (enqueue_batch) and record what the slot now holds (hold).
+#include "rau_ctx.h"
+
+namespace {
+// Host-side half of a batch hand-over: argument checks and the distinct-token index over the live
+// positions (t < lens[b]) that makes the LookupTable gradient a fixed-order gather-sum.
+// utok / ustart / upos must hold T*B, T*B + 1, T*B entries.
+int index_batch(const rau_config& c, const int32_t* tokens, const int32_t* lens, const int32_t* labels,
+                int32_t* utok, int32_t* ustart, int32_t* upos, int* max_len_out, int* nuniq_out) {
+  int max_len = 0;
+  for (int b = 0; b < c.B; ++b) {
+    NEED(lens[b] >= 0 && lens[b] <= c.T, "lens[%d]=%d out of [0,%d]", b, lens[b], c.T);
+    max_len = std::max(max_len, lens[b]);
+  }
+  for (size_t i = 0; i < (size_t)c.T * c.B; ++i)
+    NEED(tokens[i] >= 1 && tokens[i] <= c.V, "token %d at %zu out of [1,%d]", tokens[i], i, c.V);
+  if (labels)
+    for (int b = 0; b < c.B; ++b)
+      NEED(labels[b] >= 1 && labels[b] <= c.K, "labels[%d]=%d out of [1,%d]", b, labels[b], c.K);
+  std::vector<std::pair<int32_t, int32_t>> pos;  // (token, position)
+  for (int t = 0; t < max_len; ++t)
+    for (int b = 0; b < c.B; ++b)
+      if (t < lens[b]) pos.push_back({tokens[(size_t)t * c.B + b], t * c.B + b});
+  std::sort(pos.begin(), pos.end());
+  const size_t TB = (size_t)c.T * c.B;
+  size_t nu = 0;
+  for (size_t i = 0; i < pos.size(); ++i) {
+    if (i == 0 || pos[i].first != pos[i - 1].first) {
+      utok[nu] = pos[i].first;
+      ustart[nu] = (int32_t)i;
+      ++nu;
+    }
+    upos[i] = pos[i].second;
+  }
+  // pad to the maximum token count: a graph-captured embed_bwd launches T*B blocks, the surplus
+  // ones see an empty range
+  for (size_t i = nu; i < TB; ++i) utok[i] = 1;
+  for (size_t i = nu; i <= TB; ++i) ustart[i] = (int32_t)pos.size();
+  for (size_t i = pos.size(); i < TB; ++i) upos[i] = 0;
+  *max_len_out = max_len;
+  *nuniq_out = (int)nu;
+  return RAU_OK;
+}
+
+// One batch on its way into a slot.  The first half is what the caller handed over; the asynchronous front end
+// re-points it at the slot's pinned staging once the batch has been copied there.
+struct Batch {
+  const void* feats = nullptr;   // B maps, or the n_images maps of a table, of feat_type; null: a bank batch
+  int feat_type = RAU_FEAT_F32;
+  int n_images = 0;              // n_images == 0 with image_of == null is the plain batch; once check_images has
+  const int32_t* image_of = nullptr;   // passed, n_images > 0 says "table"
+  const int32_t *tokens = nullptr, *lens = nullptr, *labels = nullptr;
+  const int32_t* bank_rows = nullptr;   // non-null: the table is bank[bank_rows]
+  // ---- worked out on the way in
+  const int32_t* bank_idx = nullptr;    // [2B], check_bank_rows
+  bool bank_table = false;              // the upload gathers the table itself (wants_table)
+  const int32_t *utok = nullptr, *ustart = nullptr, *upos = nullptr;   // index_batch
+  int max_len = 0, nuniq = 0;
+};
+
+// image table of a batch: n_images in [1, B], every entry of the host index a row of the table
+int check_table(const rau_config& c, int n_images, const int32_t* image_of) {
+  NEED(image_of, "null image_of");
+  NEED(n_images >= 1 && n_images <= c.B, "n_images=%d out of [1,%d]", n_images, c.B);
+  for (int b = 0; b < c.B; ++b)
+    NEED(image_of[b] >= 0 && image_of[b] < n_images, "image_of[%d]=%d out of [0,%d)", b, image_of[b], n_images);
+  return RAU_OK;
+}
+// what the two bank entry points ask before anything else
+int need_bank(const rau_ctx* ctx, const char* who, const int32_t* rows) {
+  if (!ctx->bank) return fail(RAU_ERR_STATE, "%s: the context has no feature bank (rau_bank_create)", who);
+  NEED(rows, "null bank_rows");
+  return RAU_OK;
+}
+// bank batch: the table is valid, every row lies in the bank and has been written; fills
+// idx[2B] = rows (padded with rows[0]) | rows[image_of[b]]
+int check_bank_rows(rau_ctx* ctx, int n_images, const int32_t* rows, const int32_t* image_of, int32_t* idx) {
+  const rau_config& c = ctx->cfg;
+  if (int rc = check_table(c, n_images, image_of)) return rc;
+  for (int n = 0; n < n_images; ++n)
+    NEED(rows[n] >= 0 && rows[n] < ctx->bank_cap, "bank_rows[%d]=%d out of [0,%d)", n, rows[n], ctx->bank_cap);
+  for (int n = 0; n < n_images; ++n)
+    if (!ctx->bank_written[rows[n]])
+      return fail(RAU_ERR_STATE, "bank_rows[%d]=%d has never been written (rau_bank_put)", n, rows[n]);
+  for (int b = 0; b < c.B; ++b) {
+    idx[b] = rows[b < n_images ? b : 0];
+    idx[c.B + b] = rows[image_of[b]];
+  }
+  return RAU_OK;
+}
+// the image half of a batch's argument checks; a bank batch's row index goes to idx[2B]
+int check_images(rau_ctx* ctx, const Batch& b, int32_t* idx) {
+  if (b.bank_rows) return check_bank_rows(ctx, b.n_images, b.bank_rows, b.image_of, idx);
+  if (b.n_images != 0 || b.image_of) return check_table(ctx->cfg, b.n_images, b.image_of);
+  return RAU_OK;
+}
+// A bank batch's table is wanted by the evaluate-mode forward only; a train-mode step gathers per-sample maps
+// straight from the bank (batch_maps), and a later evaluate-mode forward gathers the table then.
+bool wants_table(const rau_ctx* ctx, const Batch& b) { return b.bank_rows && ctx->mode == RAU_MODE_EVAL; }
+
+// first table batch of a slot: its device index (and pinned staging of it on the asynchronous path) and the
+// ctx's buffer of expanded per-sample maps
+int ensure_table(rau_ctx* ctx, int si, bool pinned, bool bank) {
+  const rau_config& c = ctx->cfg;
+  const size_t cap = (size_t)ctx->cap;   // sized once, for the capacity; contents are dense in the current size
+  BatchSlot& s = ctx->slot[si];
+  if (bank && !s.bank_idx_d)
+    if (int rc = dalloc(ctx, &s.bank_idx_d, 2 * cap)) return rc;
+  if (bank && pinned && !s.bank_idx_h) {
+    void* h = nullptr;
+    hipError_t e = hipHostMalloc(&h, 2 * cap * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(bank index staging): %s", hipGetErrorString(e));
+    s.bank_idx_h = static_cast<int32_t*>(h);
+  }
+  if (!s.image_of_d)
+    if (int rc = dalloc(ctx, &s.image_of_d, cap)) return rc;
+  if (!ctx->feats_x)
+    if (int rc = dalloc(ctx, &ctx->feats_x, cap * c.D * ctx->Sp)) return rc;
+  if (pinned && !s.image_of_h) {
+    void* h = nullptr;
+    hipError_t e = hipHostMalloc(&h, cap * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(image index staging): %s", hipGetErrorString(e));
+    s.image_of_h = static_cast<int32_t*>(h);
+  }
+  return RAU_OK;
+}
+
+// what the asynchronous path adds to rau_create's slot 0: slot 1's device buffers, pinned staging and events
+// for both slots, the copy stream
+int ensure_async(rau_ctx* ctx) {
+  if (ctx->async_ready) return RAU_OK;
+  const rau_config& c = ctx->cfg;
+  // Sized for the capacity, and the staging's sub-arrays START where the capacity puts them; what a batch of the
+  // current size n writes into each of them is dense in n ([n,D,S], [T,n], [n], [n]).
+  const size_t B = (size_t)ctx->cap;
+  const size_t TB = (size_t)c.T * B, nf = B * c.D * c.S;
+  BatchSlot& s1 = ctx->slot[1];
+  if (int rc = dalloc(ctx, &s1.feats, B * c.D * ctx->Sp)) return rc;
+  if (int rc = dalloc(ctx, &s1.tokens, TB)) return rc;
+  if (int rc = dalloc(ctx, &s1.lens_d, B)) return rc;
+  if (int rc = dalloc(ctx, &s1.labels_d, B)) return rc;
+  if (int rc = dalloc(ctx, &s1.utok, TB)) return rc;
+  if (int rc = dalloc(ctx, &s1.ustart, TB + 1)) return rc;
+  if (int rc = dalloc(ctx, &s1.upos, TB)) return rc;
+  for (BatchSlot& s : ctx->slot) {
+    // one pinned block per slot: feats | tokens | lens | labels | utok | ustart | upos
+    const size_t words = nf + TB + 2 * B + TB + (TB + 1) + TB;
+    void* h = nullptr;
+    hipError_t e = hipHostMalloc(&h, words * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(batch staging, %zu bytes): %s", words * 4,
+                                     hipGetErrorString(e));
+    s.feats_h = static_cast<float*>(h);
+    s.tokens_h = reinterpret_cast<int32_t*>(s.feats_h + nf);
+    s.lens_p = s.tokens_h + TB;
+    s.labels_h = s.lens_p + B;
+    s.utok_h = s.labels_h + B;
+    s.ustart_h = s.utok_h + TB;
+    s.upos_h = s.ustart_h + TB + 1;
+    HIPC(hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming));
+    HIPC(hipEventCreateWithFlags(&s.consumed, hipEventDisableTiming));
+  }
+  int plo = 0, phi = 0;
+  hipDeviceGetStreamPriorityRange(&plo, &phi);
+  HIPC(hipStreamCreateWithPriority(&ctx->stc, hipStreamNonBlocking, plo));
+  ctx->async_ready = true;
+  return RAU_OK;
+}
+
+// H2D copies of batch `b` into slot si's device buffers, enqueued on `st`: one more upload into that slot.
+int enqueue_batch(rau_ctx* ctx, hipStream_t st, int si, const Batch& b) {
+  const rau_config& c = ctx->cfg;
+  const BatchSlot& d = ctx->slot[si];
+  const size_t TB = (size_t)c.T * c.B, es = b.feat_type == RAU_FEAT_F32 ? 4 : 2;
+  const size_t maps = b.n_images > 0 ? (size_t)b.n_images : (size_t)c.B;   // only these cross the bus
+  ++ctx->slot_serial[si];
+  if (b.n_images > 0) HIPC(hipMemcpyAsync(d.image_of_d, b.image_of, (size_t)c.B * 4, hipMemcpyHostToDevice, st));
+  // pitched rows of another element size leave data in this type's pad columns: zero them first
+  if ((b.feats || b.bank_idx) && ctx->Sp != c.S && b.feat_type != d.held.feat_type)
+    HIPC(hipMemsetAsync(d.feats, 0, (size_t)c.B * c.D * ctx->Sp * sizeof(float), st));
+  // bank batch (feats == nullptr): only the two row indices cross the bus; the table is gathered inside device
+  // memory behind them, whole maps with their (zero) pad columns
+  if (b.bank_idx) {
+    HIPC(hipMemcpyAsync(d.bank_idx_d, b.bank_idx, 2 * (size_t)c.B * 4, hipMemcpyHostToDevice, st));
+    if (b.bank_table) {
+      const size_t map_bytes = (size_t)c.D * ctx->Sp * es;
+      RUNS(st, "bank_gather", 0, 2.0 * b.n_images * map_bytes,
+           bank_gather(st, b.n_images, map_bytes, ctx->bank, ctx->bank_cap, d.bank_idx_d, d.feats));
+    }
+  }
+  if (b.feats && ctx->Sp == c.S)   // dense on both sides: one linear copy (a DMA-engine transfer, no blit kernel)
+    HIPC(hipMemcpyAsync(d.feats, b.feats, maps * c.D * c.S * es, hipMemcpyHostToDevice, st));
+  else if (b.feats)   // rows of S positions into rows of Sp (pad columns stay zero)
+    HIPC(hipMemcpy2DAsync(d.feats, (size_t)ctx->Sp * es, b.feats, (size_t)c.S * es, (size_t)c.S * es,
+                          maps * c.D, hipMemcpyHostToDevice, st));
+  HIPC(hipMemcpyAsync(d.tokens, b.tokens, TB * 4, hipMemcpyHostToDevice, st));
+  HIPC(hipMemcpyAsync(d.lens_d, b.lens, (size_t)c.B * 4, hipMemcpyHostToDevice, st));
+  if (b.labels) HIPC(hipMemcpyAsync(d.labels_d, b.labels, (size_t)c.B * 4, hipMemcpyHostToDevice, st));
+  HIPC(hipMemcpyAsync(d.utok, b.utok, TB * 4, hipMemcpyHostToDevice, st));
+  HIPC(hipMemcpyAsync(d.upos, b.upos, TB * 4, hipMemcpyHostToDevice, st));
+  HIPC(hipMemcpyAsync(d.ustart, b.ustart, (TB + 1) * 4, hipMemcpyHostToDevice, st));
+  return RAU_OK;
+}
+// slot si now holds batch `b`
+void hold(rau_ctx* ctx, int si, const Batch& b) {
+  BatchDesc& d = ctx->slot[si].held;
+  d.feat_type = b.feat_type;
+  d.n_images = b.n_images;
+  d.bank = b.bank_rows != nullptr;
+  d.table_ok = b.bank_table;
+  d.lens.assign(b.lens, b.lens + ctx->cfg.B);
+  d.max_len = b.max_len;
+  d.nuniq = b.nuniq;
+  d.have = true;
+  d.have_labels = b.labels != nullptr;
+}
+
+void make_current(rau_ctx* ctx, int si) {
+  ctx->cur_slot = si;
+  ctx->fwd_done = false;
+}
+
+// rau_set_batch_images, or (b.bank_rows) the same batch with its table drawn from the bank
+int set_batch_sync(rau_ctx* ctx, Batch b) {
+  const rau_config& c = ctx->cfg;
+  std::vector<int32_t> bidx(b.bank_rows ? 2 * (size_t)c.B : 0);
+  if (int rc = check_images(ctx, b, bidx.data())) return rc;
+  const size_t TB = (size_t)c.T * c.B;
+  std::vector<int32_t> utok(TB), ustart(TB + 1), upos(TB);
+  if (int rc = index_batch(c, b.tokens, b.lens, b.labels, utok.data(), ustart.data(), upos.data(), &b.max_len,
+                           &b.nuniq))
+    return rc;
+  b.utok = utok.data(); b.ustart = ustart.data(); b.upos = upos.data();
+  b.bank_idx = b.bank_rows ? bidx.data() : nullptr;
+  b.bank_table = wants_table(ctx, b);
+  const int si = ctx->cur_slot;   // slot 0 unless rau_use_batch switched
+  BatchSlot& s = ctx->slot[si];
+  if (b.n_images)
+    if (int rc = ensure_table(ctx, si, false, b.bank_rows != nullptr)) return rc;
+  if (s.upload_pending)   // an async upload into the same buffers
+    HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
+  if (int rc = enqueue_batch(ctx, ctx->st, si, b)) return rc;
+  HIPC(hipStreamSynchronize(ctx->st));   // the caller's (pageable) buffers are free on return
+  s.upload_pending = false;
+  hold(ctx, si, b);
+  ctx->fwd_done = false;
+  return RAU_OK;
+}
+
+// rau_set_batch_async_images, or (b.bank_rows) the same batch with its table drawn from the bank: nothing is
+// written to the slot's feature staging and no feature byte crosses the bus
+int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
+  NEED(slot == 0 || slot == 1, "rau_set_batch_async: slot %d (0 or 1)", slot);
+  const rau_config& c = ctx->cfg;
+  std::vector<int32_t> bidx(b.bank_rows ? 2 * (size_t)c.B : 0);
+  if (int rc = check_images(ctx, b, bidx.data())) return rc;
+  if (int rc = ensure_async(ctx)) return rc;
+  if (b.n_images)
+    if (int rc = ensure_table(ctx, slot, true, b.bank_rows != nullptr)) return rc;
+  BatchSlot& s = ctx->slot[slot];
+  if (slot == ctx->cur_slot && ctx->fwd_done)
+    return fail(RAU_ERR_STATE, "rau_set_batch_async: slot %d is the current batch of a forward pass whose "
+                "backward has not run; upload into the other slot", slot);
+  const size_t TB = (size_t)c.T * c.B, nf = (size_t)(b.n_images ? b.n_images : c.B) * c.D * c.S;
+  // The slot's previous upload may not have left its pinned staging yet: index_batch below rewrites the
+  // pinned index arrays in every case, and the memcpys rewrite the rest, so wait for it either way.
+  // (A caller that refills the staging IN PLACE must call rau_batch_slot(slot) before every refill:
+  // that call performs the same wait before the caller's own writes -- include/rau.h.)
+  if (s.upload_pending) {
+    HIPC(hipEventSynchronize(s.uploaded));
+    s.upload_pending = false;
+  }
+  // NULL = the caller has filled the slot's pinned staging in place (rau_batch_slot)
+  if (b.feats && b.feats != s.feats_h) std::memcpy(s.feats_h, b.feats, nf * (b.feat_type == RAU_FEAT_F32 ? 4 : 2));
+  if (b.tokens && b.tokens != s.tokens_h) std::memcpy(s.tokens_h, b.tokens, TB * 4);
+  if (b.lens && b.lens != s.lens_p) std::memcpy(s.lens_p, b.lens, (size_t)c.B * 4);
+  if (b.labels && b.labels != s.labels_h) std::memcpy(s.labels_h, b.labels, (size_t)c.B * 4);
+  if (b.n_images) std::memcpy(s.image_of_h, b.image_of, (size_t)c.B * 4);
+  if (b.bank_rows) std::memcpy(s.bank_idx_h, bidx.data(), 2 * (size_t)c.B * 4);
+  // from here on the batch is the staging's
+  b.feats = b.bank_rows ? nullptr : s.feats_h;
+  b.tokens = s.tokens_h;
+  b.lens = s.lens_p;
+  b.labels = (b.labels || has_labels) ? s.labels_h : nullptr;
+  b.image_of = s.image_of_h;
+  b.bank_idx = b.bank_rows ? s.bank_idx_h : nullptr;
+  b.bank_table = wants_table(ctx, b);
+  b.utok = s.utok_h; b.ustart = s.ustart_h; b.upos = s.upos_h;
+  if (int rc = index_batch(c, b.tokens, b.lens, b.labels, s.utok_h, s.ustart_h, s.upos_h, &b.max_len, &b.nuniq))
+    return rc;
+  // device side: the slot's buffers may still be read by the last step that used them
+  if (slot == ctx->cur_slot) {
+    HIPC(hipEventRecord(s.consumed, ctx->st));
+    s.consumed_valid = true;
+  }
+  if (s.consumed_valid) HIPC(hipStreamWaitEvent(ctx->stc, s.consumed, 0));
+  if (int rc = enqueue_batch(ctx, ctx->stc, slot, b)) return rc;
+  HIPC(hipEventRecord(s.uploaded, ctx->stc));
+  s.upload_pending = true;
+  hold(ctx, slot, b);
+  if (slot == ctx->cur_slot) {   // re-filled in place: the next forward waits for the copies
+    make_current(ctx, slot);
+    HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
+  }
+  return RAU_OK;
+}
+
+// Every enqueued reader of the bank (the gathers: copy stream and chain stream) has finished.
+int bank_quiesce(rau_ctx* ctx) {
+  if (ctx->stc) HIPC(hipStreamSynchronize(ctx->stc));
+  HIPC(hipStreamSynchronize(ctx->st));
+  return RAU_OK;
+}
+size_t bank_map_bytes(const rau_ctx* ctx) {
+  return (size_t)ctx->cfg.D * ctx->Sp * (ctx->bank_type == RAU_FEAT_F32 ? 4 : 2);
+}
+}  // namespace
+
+int batch_maps(rau_ctx* ctx, const float** maps) {
+  const BatchSlot& bs = cur_batch(ctx);
+  *maps = bs.feats;
+  if (!bs.held.n_images) return RAU_OK;
+  const rau_config& c = ctx->cfg;
+  *maps = ctx->feats_x;
+  // a captured launch gathers on every replay (the table and the index live in device memory); otherwise once
+  // per upload into the slot
+  if (!ctx->capturing && ctx->x_valid && ctx->x_slot == ctx->cur_slot &&
+      ctx->x_serial == ctx->slot_serial[ctx->cur_slot])
+    return RAU_OK;
+  const size_t map_bytes = (size_t)c.D * ctx->Sp * (bs.held.feat_type == RAU_FEAT_F32 ? 4 : 2);
+  hipStream_t st = ctx->st;
+  if (bs.held.bank)   // one pass with the composed index rows[image_of[b]] (the second half of the slot's bank index)
+    RUN("bank_gather", 0, 2.0 * c.B * map_bytes,
+        bank_gather(st, c.B, map_bytes, ctx->bank, ctx->bank_cap, bs.bank_idx_d + c.B, ctx->feats_x));
+  else
+    RUN("expand_features", 0, 2.0 * c.B * map_bytes,
+        expand_features(st, c.B, map_bytes, bs.feats, bs.image_of_d, ctx->feats_x));
+  ctx->x_valid = true;
+  ctx->x_slot = ctx->cur_slot;
+  ctx->x_serial = ctx->slot_serial[ctx->cur_slot];
+  return RAU_OK;
+}
+
+extern "C" {
+
+// ------------------------------------------------------------------ batch
+int rau_set_batch(rau_ctx* ctx, const float* feats, const int32_t* tokens, const int32_t* lens,
+                  const int32_t* labels) {
+  return rau_set_batch_typed(ctx, feats, RAU_FEAT_F32, tokens, lens, labels);
+}
+
+int rau_set_batch_typed(rau_ctx* ctx, const void* feats, int feat_type, const int32_t* tokens,
+                        const int32_t* lens, const int32_t* labels) {
+  return rau_set_batch_images(ctx, feats, feat_type, 0, nullptr, tokens, lens, labels);
+}
+
+// n_images == 0 with image_of == NULL is the plain batch (what rau_set_batch_typed passes)
+int rau_set_batch_images(rau_ctx* ctx, const void* feats, int feat_type, int n_images, const int32_t* image_of,
+                         const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
+  NEED(ctx && tokens && lens, "null argument");
+  NEED(feat_type_ok(feat_type), "rau_set_batch: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)", feat_type);
+  return set_batch_sync(ctx, Batch{feats, feat_type, n_images, image_of, tokens, lens, labels, nullptr});
+}
+
+int rau_set_batch_bank(rau_ctx* ctx, int n_images, const int32_t* bank_rows, const int32_t* image_of,
+                       const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
+  NEED(ctx && tokens && lens, "null argument");
+  if (int rc = need_bank(ctx, "rau_set_batch_bank", bank_rows)) return rc;
+  return set_batch_sync(ctx, Batch{nullptr, ctx->bank_type, n_images, image_of, tokens, lens, labels, bank_rows});
+}
+
+int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_host,
+                   int32_t** lens_host, int32_t** labels_host) {
+  NEED(ctx, "null ctx");
+  NEED(slot == 0 || slot == 1, "rau_batch_slot: slot %d (0 or 1)", slot);
+  if (int rc = ensure_async(ctx)) return rc;
+  BatchSlot& s = ctx->slot[slot];
+  if (s.upload_pending) {   // the caller is about to overwrite the staging: its last copy must have left
+    HIPC(hipEventSynchronize(s.uploaded));
+    s.upload_pending = false;
+  }
+  if (feats_host) *feats_host = s.feats_h;
+  if (tokens_host) *tokens_host = s.tokens_h;
+  if (lens_host) *lens_host = s.lens_p;
+  if (labels_host) *labels_host = s.labels_h;
+  return RAU_OK;
+}
+
+int rau_set_batch_async(rau_ctx* ctx, int slot, const float* feats, const int32_t* tokens,
+                        const int32_t* lens, const int32_t* labels, int has_labels) {
+  return rau_set_batch_async_typed(ctx, slot, feats, RAU_FEAT_F32, tokens, lens, labels, has_labels);
+}
+
+int rau_set_batch_async_typed(rau_ctx* ctx, int slot, const void* feats, int feat_type,
+                              const int32_t* tokens, const int32_t* lens, const int32_t* labels,
+                              int has_labels) {
+  return rau_set_batch_async_images(ctx, slot, feats, feat_type, 0, nullptr, tokens, lens, labels, has_labels);
+}
+
+// n_images == 0 with image_of == NULL is the plain batch (what rau_set_batch_async_typed passes)
+int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int feat_type, int n_images,
+                               const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                               const int32_t* labels, int has_labels) {
+  NEED(ctx, "null ctx");
+  NEED(feat_type_ok(feat_type), "rau_set_batch_async: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)",
+       feat_type);
+  return set_batch_slot(ctx, slot, Batch{feats, feat_type, n_images, image_of, tokens, lens, labels, nullptr},
+                        has_labels);
+}
+
+int rau_set_batch_async_bank(rau_ctx* ctx, int slot, int n_images, const int32_t* bank_rows,
+                             const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                             const int32_t* labels, int has_labels) {
+  NEED(ctx, "null ctx");
+  if (int rc = need_bank(ctx, "rau_set_batch_async_bank", bank_rows)) return rc;
+  return set_batch_slot(ctx, slot,
+                        Batch{nullptr, ctx->bank_type, n_images, image_of, tokens, lens, labels, bank_rows},
+                        has_labels);
+}
+
+int rau_use_batch(rau_ctx* ctx, int slot) {
+  NEED(ctx, "null ctx");
+  NEED(slot == 0 || slot == 1, "rau_use_batch: slot %d (0 or 1)", slot);
+  if (int rc = ensure_async(ctx)) return rc;
+  BatchSlot& s = ctx->slot[slot];
+  if (!s.held.have) return fail(RAU_ERR_STATE, "rau_use_batch: slot %d holds no batch (rau_set_batch_async)", slot);
+  if (slot != ctx->cur_slot) {
+    // everything enqueued so far may still read the slot we are leaving (the forward's bulk work is
+    // joined into the chain stream by its hop events, the backward's by its end-of-step joins)
+    BatchSlot& p = cur_batch(ctx);
+    HIPC(hipEventRecord(p.consumed, ctx->st));
+    p.consumed_valid = true;
+  }
+  make_current(ctx, slot);
+  // the bulk and weight-gradient streams start each step behind an event of the chain stream,
+  // so ordering the chain stream behind the upload orders all three
+  HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
+  return RAU_OK;
+}
+
+int rau_batch_feats(rau_ctx* ctx, float** feats_dev) {
+  NEED(ctx && feats_dev, "null argument");
+  *feats_dev = cur_batch(ctx).feats;
+  return RAU_OK;
+}
+
+int rau_batch_feat_type(rau_ctx* ctx, int* feat_type) {
+  NEED(ctx && feat_type, "null argument");
+  *feat_type = cur_batch(ctx).held.feat_type;
+  return RAU_OK;
+}
+
+int rau_batch_images(rau_ctx* ctx, int* n_images) {
+  NEED(ctx && n_images, "null argument");
+  *n_images = cur_batch(ctx).held.n_images;
+  return RAU_OK;
+}
+
+// ------------------------------------------------------------------ feature bank
+int rau_bank_create(rau_ctx* ctx, int32_t capacity, int feat_type) {
+  NEED(ctx, "null ctx");
+  NEED(feat_type_ok(feat_type), "rau_bank_create: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)", feat_type);
+  NEED(capacity >= 1, "rau_bank_create: capacity %d", capacity);
+  if (ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_create: the context already has a bank (rau_bank_destroy first)");
+  const size_t bytes = (size_t)capacity * ctx->cfg.D * ctx->Sp * (feat_type == RAU_FEAT_F32 ? 4 : 2);
+  void* d = nullptr;
+  hipError_t e = hipMalloc(&d, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();   // the failed allocation is reported here, not by the next launch
+    return fail(RAU_ERR_NOMEM, "rau_bank_create: hipMalloc(%zu bytes for %d maps) failed: %s", bytes, capacity,
+                hipGetErrorString(e));
+  }
+  e = hipMemsetAsync(d, 0, bytes, ctx->st);   // pad columns stay zero for the bank's lifetime
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
+  if (e != hipSuccess) {
+    hipFree(d);
+    return fail(RAU_ERR_DEVICE, "rau_bank_create: clearing the bank: %s", hipGetErrorString(e));
+  }
+  ctx->bank = d;
+  ctx->bank_cap = capacity;
+  ctx->bank_type = feat_type;
+  ctx->bank_filled = 0;
+  ctx->bank_written.assign((size_t)capacity, 0);
+  return RAU_OK;
+}
+
+int rau_bank_destroy(rau_ctx* ctx) {
+  NEED(ctx, "null ctx");
+  if (!ctx->bank) return RAU_OK;
+  if (int rc = bank_quiesce(ctx)) return rc;
+  // captured steps of bank batches hold the bank's address
+  for (auto it = ctx->graphs.begin(); it != ctx->graphs.end();)
+    if ((it->first >> 35) & 1) { hipGraphExecDestroy(it->second); it = ctx->graphs.erase(it); } else ++it;
+  for (BatchSlot& s : ctx->slot) {   // a batch drawn from the bank is gone with it
+    if (!s.held.bank) continue;
+    const int ft = s.held.feat_type;   // (its maps are not: enqueue_batch's pad-column rule reads their type)
+    s.held = BatchDesc{};
+    s.held.feat_type = ft;
+    if (&s == &cur_batch(ctx)) ctx->fwd_done = false;
+  }
+  hipFree(ctx->bank);
+  if (ctx->bank_stage) hipFree(ctx->bank_stage);
+  for (int k = 0; k < 2; ++k) {
+    if (ctx->bank_pin[k]) hipHostFree(ctx->bank_pin[k]);
+    if (ctx->bank_ev[k]) hipEventDestroy(ctx->bank_ev[k]);
+    ctx->bank_pin[k] = nullptr;
+    ctx->bank_ev[k] = nullptr;
+  }
+  ctx->bank = nullptr;
+  ctx->bank_stage = nullptr;
+  ctx->bank_chunk = 0;
+  ctx->bank_cap = ctx->bank_filled = 0;
+  ctx->bank_written.clear();
+  ctx->x_valid = false;
+  return RAU_OK;
+}
+
+int rau_bank_info(rau_ctx* ctx, int32_t* capacity, int* feat_type, int32_t* rows_filled) {
+  NEED(ctx, "null ctx");
+  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_info: the context has no feature bank");
+  if (capacity) *capacity = ctx->bank_cap;
+  if (feat_type) *feat_type = ctx->bank_type;
+  if (rows_filled) *rows_filled = ctx->bank_filled;
+  return RAU_OK;
+}
+
+int rau_bank_put(rau_ctx* ctx, int32_t first, int32_t count, const void* feats, int src_type) {
+  NEED(ctx && feats, "null argument");
+  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_put: the context has no feature bank (rau_bank_create)");
+  NEED(feat_type_ok(src_type), "rau_bank_put: src_type %d (RAU_FEAT_F32 | _F16 | _BF16)", src_type);
+  NEED(src_type == ctx->bank_type || src_type == RAU_FEAT_F32,
+       "rau_bank_put: maps of type %d into a bank of type %d (equal types, or f32 into a 16-bit bank)", src_type,
+       ctx->bank_type);
+  NEED(first >= 0 && count >= 1 && (int64_t)first + count <= ctx->bank_cap, "rau_bank_put: rows [%d,%d) out of [0,%d)",
+       first, first + count, ctx->bank_cap);
+  const rau_config& c = ctx->cfg;
+  const bool narrow = src_type != ctx->bank_type;
+  const size_t ses = src_type == RAU_FEAT_F32 ? 4 : 2, src_map = (size_t)c.D * c.S * ses, map_bytes = bank_map_bytes(ctx);
+  const size_t bes = ctx->bank_type == RAU_FEAT_F32 ? 4 : 2;
+  if (!ctx->bank_chunk) {   // staging sized for f32 sources: 32 MiB, at least one map
+    const size_t chunk = std::max<size_t>((size_t)32 << 20, (size_t)c.D * c.S * 4);
+    for (int k = 0; k < 2; ++k) {
+      if (!ctx->bank_pin[k]) {
+        hipError_t e = hipHostMalloc(&ctx->bank_pin[k], chunk, hipHostMallocDefault);
+        if (e != hipSuccess) {
+          ctx->bank_pin[k] = nullptr;
+          return fail(RAU_ERR_NOMEM, "rau_bank_put: hipHostMalloc(%zu bytes staging): %s", chunk, hipGetErrorString(e));
+        }
+      }
+      if (!ctx->bank_ev[k]) HIPC(hipEventCreateWithFlags(&ctx->bank_ev[k], hipEventDisableTiming));
+    }
+    ctx->bank_chunk = chunk;
+  }
+  if (narrow && !ctx->bank_stage) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->bank_stage), ctx->bank_chunk);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->bank_stage = nullptr;
+      return fail(RAU_ERR_NOMEM, "rau_bank_put: hipMalloc(%zu bytes staging): %s", ctx->bank_chunk, hipGetErrorString(e));
+    }
+  }
+  if (int rc = bank_quiesce(ctx)) return rc;   // enqueued gathers read the rows being replaced
+  const int32_t per = (int32_t)std::min<size_t>(ctx->bank_chunk / src_map, (size_t)count);
+  hipStream_t st = ctx->st;
+  bool used[2] = {false, false};
+  int k = 0;
+  for (int32_t r0 = 0; r0 < count; r0 += per, k ^= 1) {
+    const int32_t n = std::min(per, count - r0);
+    if (used[k]) HIPC(hipEventSynchronize(ctx->bank_ev[k]));   // the staging's last copy has left it
+    std::memcpy(ctx->bank_pin[k], static_cast<const char*>(feats) + (size_t)r0 * src_map, (size_t)n * src_map);
+    char* dst = static_cast<char*>(ctx->bank) + (size_t)(first + r0) * map_bytes;
+    if (narrow) {
+      // (one device staging: the stream orders the next chunk's copy behind this chunk's kernel)
+      HIPC(hipMemcpyAsync(ctx->bank_stage, ctx->bank_pin[k], (size_t)n * src_map, hipMemcpyHostToDevice, st));
+      RUN("bank_narrow", 0, (double)n * (src_map + map_bytes),
+          narrow_features(st, (size_t)n * c.D, c.S, ctx->Sp, ctx->bank_stage, dst, ctx->bank_type));
+    } else if (ctx->Sp == c.S) {
+      HIPC(hipMemcpyAsync(dst, ctx->bank_pin[k], (size_t)n * src_map, hipMemcpyHostToDevice, st));
+    } else {
+      HIPC(hipMemcpy2DAsync(dst, (size_t)ctx->Sp * bes, ctx->bank_pin[k], (size_t)c.S * bes, (size_t)c.S * bes,
+                            (size_t)n * c.D, hipMemcpyHostToDevice, st));
+    }
+    HIPC(hipEventRecord(ctx->bank_ev[k], st));
+    used[k] = true;
+  }
+  HIPC(hipStreamSynchronize(st));
+  for (int32_t r = first; r < first + count; ++r)
+    if (!ctx->bank_written[r]) { ctx->bank_written[r] = 1; ++ctx->bank_filled; }
+  ctx->x_valid = false;   // an expansion made from replaced rows is stale
+  return RAU_OK;
+}
+
+int rau_bank_get(rau_ctx* ctx, int32_t first, int32_t count, void* feats) {
+  NEED(ctx && feats, "null argument");
+  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_get: the context has no feature bank (rau_bank_create)");
+  NEED(first >= 0 && count >= 1 && (int64_t)first + count <= ctx->bank_cap, "rau_bank_get: rows [%d,%d) out of [0,%d)",
+       first, first + count, ctx->bank_cap);
+  const rau_config& c = ctx->cfg;
+  const size_t bes = ctx->bank_type == RAU_FEAT_F32 ? 4 : 2, map_bytes = bank_map_bytes(ctx);
+  const char* src = static_cast<const char*>(ctx->bank) + (size_t)first * map_bytes;
+  HIPC(hipStreamSynchronize(ctx->st));
+  if (ctx->Sp == c.S)
+    HIPC(hipMemcpy(feats, src, (size_t)count * map_bytes, hipMemcpyDeviceToHost));
+  else
+    HIPC(hipMemcpy2D(feats, (size_t)c.S * bes, src, (size_t)ctx->Sp * bes, (size_t)c.S * bes, (size_t)count * c.D,
+                     hipMemcpyDeviceToHost));
+  return RAU_OK;
+}
+
+}  // extern "C"

@@ -71,33 +71,42 @@ struct ProfCls {
   double ms = 0, flops = 0, bytes = 0;
 };
 
-// One of the two batch slots of the asynchronous upload path (rau_set_batch_async / rau_use_batch):
-// device buffers, pinned host staging the loader may fill in place, the host-side metadata
-// rau_forward needs, and the two events that order uploads against the steps.
-struct BatchSlot {
-  float* feats = nullptr;                                   // device, [B][D][Sp] (16-bit batch: its first half)
-  int32_t *tokens = nullptr, *lens_d = nullptr, *labels_d = nullptr;
-  int32_t *utok = nullptr, *ustart = nullptr, *upos = nullptr;
-  float* feats_h = nullptr;                                 // pinned host, dense [B][D][S] (16-bit: first half)
-  int feat_type = RAU_FEAT_F32;                             // rau_feat_type of the batch the slot holds
+// What a batch slot holds.  A plain value: "no batch" is BatchDesc{}.
+struct BatchDesc {
+  int feat_type = RAU_FEAT_F32;     // rau_feat_type of the maps in `feats` (a cleared buffer counts as f32)
   // image table (rau_set_batch_images): `feats` holds n_images maps, sample b looks at map image_of_d[b];
-  // 0 = a plain batch.  The index buffers are allocated at the slot's first table batch.
+  // 0 = a plain batch
   int n_images = 0;
-  int32_t* image_of_d = nullptr;                            // device [B]
-  int32_t* image_of_h = nullptr;                            // pinned host [B] (asynchronous path)
-  // bank batch (rau_set_batch_bank): a table batch whose maps are rows of the ctx's feature bank.  bank_idx_d holds
-  // rows[n_images] (padded to B) and then rows[image_of[b]] for every sample, so both gathers are one indexed copy.
+  // bank batch (rau_set_batch_bank): a table batch whose maps are rows of the ctx's feature bank
   bool bank = false;
   bool table_ok = false;            // `feats` holds the gathered table (else only the index does: train-mode upload)
-  int32_t* bank_idx_d = nullptr;    // device [2B]
-  int32_t* bank_idx_h = nullptr;    // pinned host [2B]
-  int32_t *tokens_h = nullptr, *lens_p = nullptr, *labels_h = nullptr;
-  int32_t *utok_h = nullptr, *ustart_h = nullptr, *upos_h = nullptr;
   std::vector<int32_t> lens;
   int max_len = 0, nuniq = 0;
   bool have = false, have_labels = false;
+};
+// One of the two batch slots.  slot[cur_slot] is the resident batch (cur_batch() below): the only record of it.
+// Slot 0's device buffers exist from rau_create on; slot 1's, the pinned staging the loader may fill in place, the
+// events and the copy stream come with the first call of the asynchronous path (rau_batch_slot /
+// rau_set_batch_async / rau_use_batch).
+struct BatchSlot {
+  // ---- allocated once
+  float* feats = nullptr;                                   // device, [B][D][Sp] (16-bit batch: its first half)
+  int32_t *tokens = nullptr, *lens_d = nullptr, *labels_d = nullptr;
+  int32_t *utok = nullptr, *ustart = nullptr, *upos = nullptr;
+  int32_t* image_of_d = nullptr;    // device [B], allocated at the slot's first table batch
+  // bank_idx_d holds rows[n_images] (padded to B) and then rows[image_of[b]] for every sample, so both gathers
+  // of a bank batch are one indexed copy
+  int32_t* bank_idx_d = nullptr;    // device [2B], allocated at the slot's first bank batch
+  float* feats_h = nullptr;                                 // pinned host, dense [B][D][S] (16-bit: first half)
+  int32_t *tokens_h = nullptr, *lens_p = nullptr, *labels_h = nullptr;
+  int32_t *utok_h = nullptr, *ustart_h = nullptr, *upos_h = nullptr;
+  int32_t* image_of_h = nullptr;    // pinned host [B]
+  int32_t* bank_idx_h = nullptr;    // pinned host [2B]
   hipEvent_t uploaded = nullptr;    // recorded on the copy stream behind the slot's H2D copies
   hipEvent_t consumed = nullptr;    // recorded on the chain stream when the ctx switches away from the slot
+  // ---- what the device buffers hold
+  BatchDesc held;
+  // ---- upload ordering
   bool upload_pending = false, consumed_valid = false;
 };
 
@@ -134,11 +143,7 @@ struct rau_ctx {
       lstm_h2h, lstm_out, cls, do_pred;
   // rnn
   Lin i2h[2], h2h[2];
-  // batch
-  float* feats = nullptr;
-  int feat_type = RAU_FEAT_F32;   // rau_feat_type of the resident batch (what `feats` holds)
-  int n_images = 0;               // the resident batch carries an image table of that many maps (0: plain batch);
-                                  // its device index is slot[cur_slot].image_of_d
+  // batch (the resident one is slot[cur_slot], below)
   float* feats_x = nullptr;       // [B][D][Sp] per-sample maps gathered from the table (expand_features), in the
                                   // batch's element type; allocated at the first table batch
   bool x_valid = false;           // feats_x holds the expansion of upload x_serial into slot x_slot
@@ -148,12 +153,6 @@ struct rau_ctx {
                                   // is no per-sample I for a backward pass
   float* xw = nullptr;            // f32 image of the unmasked batch the last forward read: feats, or (16-bit
                                   // batch) the first B*D*Sp floats of xd, widened there by that forward
-  int32_t *tokens = nullptr, *lens_d = nullptr, *labels_d = nullptr;
-  std::vector<int32_t> lens_h;
-  int max_len = 0;
-  bool have_batch = false, have_labels = false;
-  int nuniq = 0;
-  int32_t *utok = nullptr, *ustart = nullptr, *upos = nullptr;
   // feature bank (rau_bank_*): every image's map once, in the batch buffers' layout [capacity][D][Sp]
   void* bank = nullptr;
   int32_t bank_cap = 0, bank_filled = 0;
@@ -163,11 +162,11 @@ struct rau_ctx {
   float* bank_stage = nullptr;              // device: one chunk of f32 maps on their way to a 16-bit bank
   size_t bank_chunk = 0;
   hipEvent_t bank_ev[2] = {nullptr, nullptr};
-  // asynchronous, double-buffered upload (allocated at the first rau_batch_slot / rau_set_batch_async)
+  // the two batch slots; the synchronous path uploads into the current one
   BatchSlot slot[2];
   uint64_t slot_serial[2] = {0, 0};   // uploads into each slot's device buffers so far
   int cur_slot = 0;
-  bool async_ready = false;
+  bool async_ready = false;          // slot 1, the staging, the events and the copy stream exist
   hipStream_t stc = nullptr;         // copy stream
   hipEvent_t hopw_ev[2] = {nullptr, nullptr};   // hop-weight staging slots: H2D copy done
   // dropout
@@ -263,6 +262,10 @@ struct rau_ctx {
   std::vector<hipEvent_t> evpool;
 };
 
+// The resident batch: what every reader of the batch goes through.
+inline BatchSlot& cur_batch(rau_ctx* ctx) { return ctx->slot[ctx->cur_slot]; }
+inline const BatchSlot& cur_batch(const rau_ctx* ctx) { return ctx->slot[ctx->cur_slot]; }
+
 // Effective drop probability of a mask site.  Masks the device draws itself (Philox, 8-bit draws)
 // drop with p quantised to 1/256 and scale by 1/(1-pq), so that E[mask * scale] = 1 exactly;
 // caller-supplied masks (rau_set_mask) are nn.Dropout's: scale 1/(1-p) with the configured p.
@@ -289,8 +292,8 @@ inline void set_skinny_policy(const rau_ctx* ctx) {
 // read them until the next forward, module-level call or upload into the batch slot it read.
 inline void merge_record(rau_ctx* ctx) {
   ctx->mg_valid = true;
-  ctx->mg_labels = ctx->have_labels;
-  ctx->mg_labels_d = ctx->labels_d;
+  ctx->mg_labels = cur_batch(ctx).held.have_labels;
+  ctx->mg_labels_d = cur_batch(ctx).labels_d;
   ctx->mg_slot = ctx->cur_slot;
   ctx->mg_serial = ctx->slot_serial[ctx->cur_slot];
 }

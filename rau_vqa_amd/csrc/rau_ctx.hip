@@ -419,13 +419,14 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   plan_batch(ctx, B, &plan);
   adopt_plan(ctx, plan);
   // ---- batch
-  CK(dalloc(ctx, &ctx->feats, (size_t)B * D * S));
-  CK(dalloc(ctx, &ctx->tokens, (size_t)T * B));
-  CK(dalloc(ctx, &ctx->lens_d, (size_t)B));
-  CK(dalloc(ctx, &ctx->labels_d, (size_t)B));
-  CK(dalloc(ctx, &ctx->utok, (size_t)T * B));
-  CK(dalloc(ctx, &ctx->ustart, (size_t)T * B + 1));
-  CK(dalloc(ctx, &ctx->upos, (size_t)T * B));
+  BatchSlot& s0 = ctx->slot[0];   // (slot 1 comes with the asynchronous path: rau_batch.hip)
+  CK(dalloc(ctx, &s0.feats, (size_t)B * D * S));
+  CK(dalloc(ctx, &s0.tokens, (size_t)T * B));
+  CK(dalloc(ctx, &s0.lens_d, (size_t)B));
+  CK(dalloc(ctx, &s0.labels_d, (size_t)B));
+  CK(dalloc(ctx, &s0.utok, (size_t)T * B));
+  CK(dalloc(ctx, &s0.ustart, (size_t)T * B + 1));
+  CK(dalloc(ctx, &s0.upos, (size_t)T * B));
   // ---- masks (bit-packed, +1 word slack)
   for (int i = 0; i < 5; ++i) CK(dalloc(ctx, &ctx->mbits[i], (ctx->mcount[i] + 31) / 32 + 1));
   // ---- encoder
@@ -751,459 +752,6 @@ int rau_get_mask(rau_ctx* ctx, int site, uint8_t* keep, size_t n) {
   return RAU_OK;
 }
 
-// ------------------------------------------------------------------ batch
-}  // extern "C"
-
-namespace {
-// Host-side half of a batch hand-over: argument checks and the distinct-token index over the live
-// positions (t < lens[b]) that makes the LookupTable gradient a fixed-order gather-sum.
-// utok / ustart / upos must hold T*B, T*B + 1, T*B entries.
-int index_batch(const rau_config& c, const int32_t* tokens, const int32_t* lens, const int32_t* labels,
-                int32_t* utok, int32_t* ustart, int32_t* upos, int* max_len_out, int* nuniq_out) {
-  int max_len = 0;
-  for (int b = 0; b < c.B; ++b) {
-    NEED(lens[b] >= 0 && lens[b] <= c.T, "lens[%d]=%d out of [0,%d]", b, lens[b], c.T);
-    max_len = std::max(max_len, lens[b]);
-  }
-  for (size_t i = 0; i < (size_t)c.T * c.B; ++i)
-    NEED(tokens[i] >= 1 && tokens[i] <= c.V, "token %d at %zu out of [1,%d]", tokens[i], i, c.V);
-  if (labels)
-    for (int b = 0; b < c.B; ++b)
-      NEED(labels[b] >= 1 && labels[b] <= c.K, "labels[%d]=%d out of [1,%d]", b, labels[b], c.K);
-  std::vector<std::pair<int32_t, int32_t>> pos;  // (token, position)
-  for (int t = 0; t < max_len; ++t)
-    for (int b = 0; b < c.B; ++b)
-      if (t < lens[b]) pos.push_back({tokens[(size_t)t * c.B + b], t * c.B + b});
-  std::sort(pos.begin(), pos.end());
-  const size_t TB = (size_t)c.T * c.B;
-  size_t nu = 0;
-  for (size_t i = 0; i < pos.size(); ++i) {
-    if (i == 0 || pos[i].first != pos[i - 1].first) {
-      utok[nu] = pos[i].first;
-      ustart[nu] = (int32_t)i;
-      ++nu;
-    }
-    upos[i] = pos[i].second;
-  }
-  // pad to the maximum token count: a graph-captured embed_bwd launches T*B blocks, the surplus
-  // ones see an empty range
-  for (size_t i = nu; i < TB; ++i) utok[i] = 1;
-  for (size_t i = nu; i <= TB; ++i) ustart[i] = (int32_t)pos.size();
-  for (size_t i = pos.size(); i < TB; ++i) upos[i] = 0;
-  *max_len_out = max_len;
-  *nuniq_out = (int)nu;
-  return RAU_OK;
-}
-
-// H2D copies of one batch into a set of device buffers, enqueued on `s`.  feats holds elements of
-// feat_type (4 or 2 bytes); prev_type is the type of what the device buffer holds now.  n_images > 0: feats is
-// an image table of that many maps and image_of (host, [B], checked) goes to the slot's device index.
-int enqueue_batch(rau_ctx* ctx, hipStream_t s, const BatchSlot& d, const void* feats, int feat_type,
-                  int prev_type, const int32_t* tokens, const int32_t* lens, const int32_t* labels,
-                  const int32_t* utok, const int32_t* ustart, const int32_t* upos, int n_images = 0,
-                  const int32_t* image_of = nullptr, const int32_t* bank_idx = nullptr, bool bank_table = false) {
-  const rau_config& c = ctx->cfg;
-  const size_t TB = (size_t)c.T * c.B, es = feat_type == RAU_FEAT_F32 ? 4 : 2;
-  const size_t maps = n_images > 0 ? (size_t)n_images : (size_t)c.B;   // only these cross the bus
-  if (n_images > 0) HIPC(hipMemcpyAsync(d.image_of_d, image_of, (size_t)c.B * 4, hipMemcpyHostToDevice, s));
-  // pitched rows of another element size leave data in this type's pad columns: zero them first
-  if ((feats || bank_idx) && ctx->Sp != c.S && feat_type != prev_type)
-    HIPC(hipMemsetAsync(d.feats, 0, (size_t)c.B * c.D * ctx->Sp * sizeof(float), s));
-  // bank batch (feats == nullptr): only the two row indices cross the bus; the table is gathered inside device
-  // memory behind them, whole maps with their (zero) pad columns
-  if (bank_idx) {
-    HIPC(hipMemcpyAsync(d.bank_idx_d, bank_idx, 2 * (size_t)c.B * 4, hipMemcpyHostToDevice, s));
-    if (bank_table) {
-      const size_t map_bytes = (size_t)c.D * ctx->Sp * es;
-      RUNS(s, "bank_gather", 0, 2.0 * n_images * map_bytes,
-           bank_gather(s, n_images, map_bytes, ctx->bank, ctx->bank_cap, d.bank_idx_d, d.feats));
-    }
-  }
-  if (feats && ctx->Sp == c.S)   // dense on both sides: one linear copy (a DMA-engine transfer, no blit kernel)
-    HIPC(hipMemcpyAsync(d.feats, feats, maps * c.D * c.S * es, hipMemcpyHostToDevice, s));
-  else if (feats)   // rows of S positions into rows of Sp (pad columns stay zero)
-    HIPC(hipMemcpy2DAsync(d.feats, (size_t)ctx->Sp * es, feats, (size_t)c.S * es, (size_t)c.S * es,
-                          maps * c.D, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d.tokens, tokens, TB * 4, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d.lens_d, lens, (size_t)c.B * 4, hipMemcpyHostToDevice, s));
-  if (labels) HIPC(hipMemcpyAsync(d.labels_d, labels, (size_t)c.B * 4, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d.utok, utok, TB * 4, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d.upos, upos, TB * 4, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d.ustart, ustart, (TB + 1) * 4, hipMemcpyHostToDevice, s));
-  return RAU_OK;
-}
-
-void make_current(rau_ctx* ctx, int si) {
-  BatchSlot& s = ctx->slot[si];
-  ctx->cur_slot = si;
-  ctx->feats = s.feats; ctx->tokens = s.tokens; ctx->lens_d = s.lens_d; ctx->labels_d = s.labels_d;
-  ctx->feat_type = s.feat_type;
-  ctx->n_images = s.n_images;
-  ctx->utok = s.utok; ctx->ustart = s.ustart; ctx->upos = s.upos;
-  ctx->lens_h = s.lens;
-  ctx->max_len = s.max_len;
-  ctx->nuniq = s.nuniq;
-  ctx->have_batch = s.have;
-  ctx->have_labels = s.have_labels;
-  ctx->fwd_done = false;
-}
-
-// image table of a batch: n_images in [1, B], every entry of the host index a row of the table
-int check_table(const rau_config& c, int n_images, const int32_t* image_of) {
-  NEED(image_of, "null image_of");
-  NEED(n_images >= 1 && n_images <= c.B, "n_images=%d out of [1,%d]", n_images, c.B);
-  for (int b = 0; b < c.B; ++b)
-    NEED(image_of[b] >= 0 && image_of[b] < n_images, "image_of[%d]=%d out of [0,%d)", b, image_of[b], n_images);
-  return RAU_OK;
-}
-// bank batch: a bank exists, the table is valid, every row lies in the bank and has been written; fills
-// idx[2B] = rows (padded with rows[0]) | rows[image_of[b]]
-int check_bank_rows(rau_ctx* ctx, int n_images, const int32_t* rows, const int32_t* image_of, int32_t* idx) {
-  const rau_config& c = ctx->cfg;
-  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_set_batch_bank: the context has no feature bank (rau_bank_create)");
-  NEED(rows, "null bank_rows");
-  if (int rc = check_table(c, n_images, image_of)) return rc;
-  for (int n = 0; n < n_images; ++n)
-    NEED(rows[n] >= 0 && rows[n] < ctx->bank_cap, "bank_rows[%d]=%d out of [0,%d)", n, rows[n], ctx->bank_cap);
-  for (int n = 0; n < n_images; ++n)
-    if (!ctx->bank_written[rows[n]])
-      return fail(RAU_ERR_STATE, "bank_rows[%d]=%d has never been written (rau_bank_put)", n, rows[n]);
-  for (int b = 0; b < c.B; ++b) {
-    idx[b] = rows[b < n_images ? b : 0];
-    idx[c.B + b] = rows[image_of[b]];
-  }
-  return RAU_OK;
-}
-// first table batch of a slot: its device index (and pinned staging of it on the asynchronous path) and the
-// ctx's buffer of expanded per-sample maps
-int ensure_table(rau_ctx* ctx, int si, bool pinned, bool bank = false) {
-  const rau_config& c = ctx->cfg;
-  const size_t cap = (size_t)ctx->cap;   // sized once, for the capacity; contents are dense in the current size
-  BatchSlot& s = ctx->slot[si];
-  if (bank && !s.bank_idx_d)
-    if (int rc = dalloc(ctx, &s.bank_idx_d, 2 * cap)) return rc;
-  if (bank && pinned && !s.bank_idx_h) {
-    void* h = nullptr;
-    hipError_t e = hipHostMalloc(&h, 2 * cap * 4, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(bank index staging): %s", hipGetErrorString(e));
-    s.bank_idx_h = static_cast<int32_t*>(h);
-  }
-  if (!s.image_of_d)
-    if (int rc = dalloc(ctx, &s.image_of_d, cap)) return rc;
-  if (!ctx->feats_x)
-    if (int rc = dalloc(ctx, &ctx->feats_x, cap * c.D * ctx->Sp)) return rc;
-  if (pinned && !s.image_of_h) {
-    void* h = nullptr;
-    hipError_t e = hipHostMalloc(&h, cap * 4, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(image index staging): %s", hipGetErrorString(e));
-    s.image_of_h = static_cast<int32_t*>(h);
-  }
-  return RAU_OK;
-}
-
-// second set of device buffers, pinned staging for both slots, copy stream, events
-int ensure_async(rau_ctx* ctx) {
-  if (ctx->async_ready) return RAU_OK;
-  const rau_config& c = ctx->cfg;
-  // Sized for the capacity, and the staging's sub-arrays START where the capacity puts them; what a batch of the
-  // current size n writes into each of them is dense in n ([n,D,S], [T,n], [n], [n]).
-  const size_t B = (size_t)ctx->cap;
-  const size_t TB = (size_t)c.T * B, nf = B * c.D * c.S;
-  BatchSlot& s0 = ctx->slot[0];
-  s0.feats = ctx->feats; s0.tokens = ctx->tokens; s0.lens_d = ctx->lens_d; s0.labels_d = ctx->labels_d;
-  s0.utok = ctx->utok; s0.ustart = ctx->ustart; s0.upos = ctx->upos;
-  s0.lens = ctx->lens_h; s0.max_len = ctx->max_len; s0.nuniq = ctx->nuniq;
-  s0.have = ctx->have_batch; s0.have_labels = ctx->have_labels; s0.feat_type = ctx->feat_type;
-  s0.n_images = ctx->n_images;   // (s0.bank / table_ok / bank_idx_d are kept in the slot itself)
-  BatchSlot& s1 = ctx->slot[1];
-  if (int rc = dalloc(ctx, &s1.feats, B * c.D * ctx->Sp)) return rc;
-  if (int rc = dalloc(ctx, &s1.tokens, TB)) return rc;
-  if (int rc = dalloc(ctx, &s1.lens_d, B)) return rc;
-  if (int rc = dalloc(ctx, &s1.labels_d, B)) return rc;
-  if (int rc = dalloc(ctx, &s1.utok, TB)) return rc;
-  if (int rc = dalloc(ctx, &s1.ustart, TB + 1)) return rc;
-  if (int rc = dalloc(ctx, &s1.upos, TB)) return rc;
-  for (BatchSlot& s : ctx->slot) {
-    // one pinned block per slot: feats | tokens | lens | labels | utok | ustart | upos
-    const size_t words = nf + TB + 2 * B + TB + (TB + 1) + TB;
-    void* h = nullptr;
-    hipError_t e = hipHostMalloc(&h, words * 4, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(batch staging, %zu bytes): %s", words * 4,
-                                     hipGetErrorString(e));
-    s.feats_h = static_cast<float*>(h);
-    s.tokens_h = reinterpret_cast<int32_t*>(s.feats_h + nf);
-    s.lens_p = s.tokens_h + TB;
-    s.labels_h = s.lens_p + B;
-    s.utok_h = s.labels_h + B;
-    s.ustart_h = s.utok_h + TB;
-    s.upos_h = s.ustart_h + TB + 1;
-    HIPC(hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming));
-    HIPC(hipEventCreateWithFlags(&s.consumed, hipEventDisableTiming));
-  }
-  int plo = 0, phi = 0;
-  hipDeviceGetStreamPriorityRange(&plo, &phi);
-  HIPC(hipStreamCreateWithPriority(&ctx->stc, hipStreamNonBlocking, plo));
-  ctx->async_ready = true;
-  return RAU_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int rau_set_batch(rau_ctx* ctx, const float* feats, const int32_t* tokens, const int32_t* lens,
-                  const int32_t* labels) {
-  return rau_set_batch_typed(ctx, feats, RAU_FEAT_F32, tokens, lens, labels);
-}
-
-int rau_set_batch_typed(rau_ctx* ctx, const void* feats, int feat_type, const int32_t* tokens,
-                        const int32_t* lens, const int32_t* labels) {
-  return rau_set_batch_images(ctx, feats, feat_type, 0, nullptr, tokens, lens, labels);
-}
-
-}  // extern "C"
-
-namespace {
-// rau_set_batch_images, or (bank_rows != nullptr, feats == nullptr) the same batch with its table drawn from the bank
-int set_batch_sync(rau_ctx* ctx, const void* feats, int feat_type, int n_images, const int32_t* image_of,
-                   const int32_t* tokens, const int32_t* lens, const int32_t* labels, const int32_t* bank_rows) {
-  const rau_config& c = ctx->cfg;
-  const bool table = n_images != 0 || image_of != nullptr;
-  std::vector<int32_t> bidx;
-  if (bank_rows) {
-    bidx.resize(2 * (size_t)c.B);
-    if (int rc = check_bank_rows(ctx, n_images, bank_rows, image_of, bidx.data())) return rc;
-  } else if (table) {
-    if (int rc = check_table(c, n_images, image_of)) return rc;
-  }
-  const size_t TB = (size_t)c.T * c.B;
-  std::vector<int32_t> utok(TB), ustart(TB + 1), upos(TB);
-  int max_len = 0, nuniq = 0;
-  if (int rc = index_batch(c, tokens, lens, labels, utok.data(), ustart.data(), upos.data(), &max_len, &nuniq))
-    return rc;
-  if (table)
-    if (int rc = ensure_table(ctx, ctx->cur_slot, false, bank_rows != nullptr)) return rc;
-  BatchSlot d;   // the CURRENT device buffers (slot 0 unless rau_use_batch switched)
-  d.image_of_d = ctx->slot[ctx->cur_slot].image_of_d;
-  d.bank_idx_d = ctx->slot[ctx->cur_slot].bank_idx_d;
-  // the table itself is wanted by the evaluate-mode forward only; a train-mode step gathers per-sample maps
-  // straight from the bank (batch_maps), and a later evaluate-mode forward gathers the table then
-  const bool bank_table = bank_rows && ctx->mode == RAU_MODE_EVAL;
-  d.feats = ctx->feats; d.tokens = ctx->tokens; d.lens_d = ctx->lens_d; d.labels_d = ctx->labels_d;
-  d.utok = ctx->utok; d.ustart = ctx->ustart; d.upos = ctx->upos;
-  if (ctx->async_ready && ctx->slot[ctx->cur_slot].upload_pending)   // an async upload into the same buffers
-    HIPC(hipStreamWaitEvent(ctx->st, ctx->slot[ctx->cur_slot].uploaded, 0));
-  ++ctx->slot_serial[ctx->cur_slot];
-  if (int rc = enqueue_batch(ctx, ctx->st, d, feats, feat_type, ctx->feat_type, tokens, lens, labels,
-                             utok.data(), ustart.data(), upos.data(), table ? n_images : 0, image_of,
-                             bank_rows ? bidx.data() : nullptr, bank_table))
-    return rc;
-  HIPC(hipStreamSynchronize(ctx->st));   // the caller's (pageable) buffers are free on return
-  ctx->feat_type = feat_type;
-  ctx->n_images = ctx->slot[ctx->cur_slot].n_images = table ? n_images : 0;
-  ctx->slot[ctx->cur_slot].bank = bank_rows != nullptr;
-  ctx->slot[ctx->cur_slot].table_ok = bank_table;
-  ctx->lens_h.assign(lens, lens + c.B);
-  ctx->max_len = max_len;
-  ctx->nuniq = nuniq;
-  ctx->have_batch = true;
-  ctx->have_labels = labels != nullptr;
-  ctx->fwd_done = false;
-  if (ctx->async_ready) {
-    BatchSlot& s = ctx->slot[ctx->cur_slot];
-    s.lens = ctx->lens_h; s.max_len = max_len; s.nuniq = nuniq;
-    s.have = true; s.have_labels = ctx->have_labels; s.upload_pending = false;
-    s.feat_type = feat_type;
-  }
-  return RAU_OK;
-}
-}  // namespace
-
-extern "C" {
-
-// n_images == 0 with image_of == NULL is the plain batch (what rau_set_batch_typed passes)
-int rau_set_batch_images(rau_ctx* ctx, const void* feats, int feat_type, int n_images, const int32_t* image_of,
-                         const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
-  NEED(ctx && tokens && lens, "null argument");
-  NEED(feat_type_ok(feat_type), "rau_set_batch: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)", feat_type);
-  return set_batch_sync(ctx, feats, feat_type, n_images, image_of, tokens, lens, labels, nullptr);
-}
-
-int rau_set_batch_bank(rau_ctx* ctx, int n_images, const int32_t* bank_rows, const int32_t* image_of,
-                       const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
-  NEED(ctx && tokens && lens, "null argument");
-  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_set_batch_bank: the context has no feature bank (rau_bank_create)");
-  NEED(bank_rows, "null bank_rows");
-  return set_batch_sync(ctx, nullptr, ctx->bank_type, n_images, image_of, tokens, lens, labels, bank_rows);
-}
-
-int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_host,
-                   int32_t** lens_host, int32_t** labels_host) {
-  NEED(ctx, "null ctx");
-  NEED(slot == 0 || slot == 1, "rau_batch_slot: slot %d (0 or 1)", slot);
-  if (int rc = ensure_async(ctx)) return rc;
-  BatchSlot& s = ctx->slot[slot];
-  if (s.upload_pending) {   // the caller is about to overwrite the staging: its last copy must have left
-    HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = false;
-  }
-  if (feats_host) *feats_host = s.feats_h;
-  if (tokens_host) *tokens_host = s.tokens_h;
-  if (lens_host) *lens_host = s.lens_p;
-  if (labels_host) *labels_host = s.labels_h;
-  return RAU_OK;
-}
-
-int rau_set_batch_async(rau_ctx* ctx, int slot, const float* feats, const int32_t* tokens,
-                        const int32_t* lens, const int32_t* labels, int has_labels) {
-  return rau_set_batch_async_typed(ctx, slot, feats, RAU_FEAT_F32, tokens, lens, labels, has_labels);
-}
-
-int rau_set_batch_async_typed(rau_ctx* ctx, int slot, const void* feats, int feat_type,
-                              const int32_t* tokens, const int32_t* lens, const int32_t* labels,
-                              int has_labels) {
-  return rau_set_batch_async_images(ctx, slot, feats, feat_type, 0, nullptr, tokens, lens, labels, has_labels);
-}
-
-}  // extern "C"
-
-namespace {
-// rau_set_batch_async_images, or (bank_rows != nullptr, feats == nullptr) the same batch with its table drawn from
-// the bank: nothing is written to the slot's feature staging and no feature byte crosses the bus
-int set_batch_slot(rau_ctx* ctx, int slot, const void* feats, int feat_type, int n_images,
-                   const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
-                   const int32_t* labels, int has_labels, const int32_t* bank_rows) {
-  NEED(slot == 0 || slot == 1, "rau_set_batch_async: slot %d (0 or 1)", slot);
-  const rau_config& c = ctx->cfg;
-  const bool table = n_images != 0 || image_of != nullptr;
-  std::vector<int32_t> bidx;
-  if (bank_rows) {
-    bidx.resize(2 * (size_t)c.B);
-    if (int rc = check_bank_rows(ctx, n_images, bank_rows, image_of, bidx.data())) return rc;
-  } else if (table) {
-    if (int rc = check_table(c, n_images, image_of)) return rc;
-  }
-  if (int rc = ensure_async(ctx)) return rc;
-  if (table)
-    if (int rc = ensure_table(ctx, slot, true, bank_rows != nullptr)) return rc;
-  BatchSlot& s = ctx->slot[slot];
-  if (slot == ctx->cur_slot && ctx->fwd_done)
-    return fail(RAU_ERR_STATE, "rau_set_batch_async: slot %d is the current batch of a forward pass whose "
-                "backward has not run; upload into the other slot", slot);
-  const size_t TB = (size_t)c.T * c.B, nf = (size_t)(table ? n_images : c.B) * c.D * c.S;
-  const bool copies = (feats && feats != s.feats_h) || (tokens && tokens != s.tokens_h) ||
-                      (lens && lens != s.lens_p) || (labels && labels != s.labels_h);
-  (void)copies;
-  // The slot's previous upload may not have left its pinned staging yet: index_batch below rewrites the
-  // pinned index arrays in every case, and the memcpys rewrite the rest, so wait for it either way.
-  // (A caller that refills the staging IN PLACE must call rau_batch_slot(slot) before every refill:
-  // that call performs the same wait before the caller's own writes -- include/rau.h.)
-  if (s.upload_pending) {
-    HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = false;
-  }
-  // NULL = the caller has filled the slot's pinned staging in place (rau_batch_slot)
-  if (feats && feats != s.feats_h) std::memcpy(s.feats_h, feats, nf * (feat_type == RAU_FEAT_F32 ? 4 : 2));
-  if (tokens && tokens != s.tokens_h) std::memcpy(s.tokens_h, tokens, TB * 4);
-  if (lens && lens != s.lens_p) std::memcpy(s.lens_p, lens, (size_t)c.B * 4);
-  if (labels && labels != s.labels_h) std::memcpy(s.labels_h, labels, (size_t)c.B * 4);
-  if (table) std::memcpy(s.image_of_h, image_of, (size_t)c.B * 4);
-  if (bank_rows) std::memcpy(s.bank_idx_h, bidx.data(), 2 * (size_t)c.B * 4);
-  const bool bank_table = bank_rows && ctx->mode == RAU_MODE_EVAL;   // (see set_batch_sync)
-  const bool with_labels = labels != nullptr || has_labels != 0;
-  int max_len = 0, nuniq = 0;
-  if (int rc = index_batch(c, s.tokens_h, s.lens_p, with_labels ? s.labels_h : nullptr, s.utok_h, s.ustart_h,
-                           s.upos_h, &max_len, &nuniq))
-    return rc;
-  // device side: the slot's buffers may still be read by the last step that used them
-  if (slot == ctx->cur_slot) {
-    HIPC(hipEventRecord(s.consumed, ctx->st));
-    s.consumed_valid = true;
-  }
-  if (s.consumed_valid) HIPC(hipStreamWaitEvent(ctx->stc, s.consumed, 0));
-  ++ctx->slot_serial[slot];
-  if (int rc = enqueue_batch(ctx, ctx->stc, s, bank_rows ? nullptr : s.feats_h, feat_type, s.feat_type, s.tokens_h,
-                             s.lens_p, with_labels ? s.labels_h : nullptr, s.utok_h, s.ustart_h, s.upos_h,
-                             table ? n_images : 0, s.image_of_h, bank_rows ? s.bank_idx_h : nullptr, bank_table))
-    return rc;
-  HIPC(hipEventRecord(s.uploaded, ctx->stc));
-  s.upload_pending = true;
-  s.feat_type = feat_type;
-  s.n_images = table ? n_images : 0;
-  s.bank = bank_rows != nullptr;
-  s.table_ok = bank_table;
-  s.lens.assign(s.lens_p, s.lens_p + c.B);
-  s.max_len = max_len;
-  s.nuniq = nuniq;
-  s.have = true;
-  s.have_labels = with_labels;
-  if (slot == ctx->cur_slot) {   // re-filled in place: the next forward waits for the copies
-    make_current(ctx, slot);
-    HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
-  }
-  return RAU_OK;
-}
-}  // namespace
-
-extern "C" {
-
-// n_images == 0 with image_of == NULL is the plain batch (what rau_set_batch_async_typed passes)
-int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int feat_type, int n_images,
-                               const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
-                               const int32_t* labels, int has_labels) {
-  NEED(ctx, "null ctx");
-  NEED(feat_type_ok(feat_type), "rau_set_batch_async: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)",
-       feat_type);
-  return set_batch_slot(ctx, slot, feats, feat_type, n_images, image_of, tokens, lens, labels, has_labels, nullptr);
-}
-
-int rau_set_batch_async_bank(rau_ctx* ctx, int slot, int n_images, const int32_t* bank_rows,
-                             const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
-                             const int32_t* labels, int has_labels) {
-  NEED(ctx, "null ctx");
-  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_set_batch_async_bank: the context has no feature bank (rau_bank_create)");
-  NEED(bank_rows, "null bank_rows");
-  return set_batch_slot(ctx, slot, nullptr, ctx->bank_type, n_images, image_of, tokens, lens, labels, has_labels,
-                        bank_rows);
-}
-
-int rau_use_batch(rau_ctx* ctx, int slot) {
-  NEED(ctx, "null ctx");
-  NEED(slot == 0 || slot == 1, "rau_use_batch: slot %d (0 or 1)", slot);
-  if (int rc = ensure_async(ctx)) return rc;
-  BatchSlot& s = ctx->slot[slot];
-  if (!s.have) return fail(RAU_ERR_STATE, "rau_use_batch: slot %d holds no batch (rau_set_batch_async)", slot);
-  if (slot != ctx->cur_slot) {
-    // everything enqueued so far may still read the slot we are leaving (the forward's bulk work is
-    // joined into the chain stream by its hop events, the backward's by its end-of-step joins)
-    BatchSlot& p = ctx->slot[ctx->cur_slot];
-    HIPC(hipEventRecord(p.consumed, ctx->st));
-    p.consumed_valid = true;
-  }
-  make_current(ctx, slot);
-  // the bulk and weight-gradient streams start each step behind an event of the chain stream,
-  // so ordering the chain stream behind the upload orders all three
-  HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
-  return RAU_OK;
-}
-
-int rau_batch_feats(rau_ctx* ctx, float** feats_dev) {
-  NEED(ctx && feats_dev, "null argument");
-  *feats_dev = ctx->feats;
-  return RAU_OK;
-}
-
-int rau_batch_feat_type(rau_ctx* ctx, int* feat_type) {
-  NEED(ctx && feat_type, "null argument");
-  *feat_type = ctx->feat_type;
-  return RAU_OK;
-}
-
-int rau_batch_images(rau_ctx* ctx, int* n_images) {
-  NEED(ctx && n_images, "null argument");
-  *n_images = ctx->n_images;
-  return RAU_OK;
-}
-
 // ------------------------------------------------------------- batch size
 int rau_batch_size(rau_ctx* ctx, int32_t* n, int32_t* capacity) {
   NEED(ctx, "null ctx");
@@ -1279,21 +827,11 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   HIPC(hipStreamSynchronize(ctx->st));
   // ---- host-side state of a fresh context: no batch, no uploads, seeded masks, no results
   for (int si = 0; si < 2; ++si) {
-    BatchSlot& s = ctx->slot[si];
-    s.have = s.have_labels = s.upload_pending = s.consumed_valid = false;
-    s.bank = s.table_ok = false;
-    s.feat_type = RAU_FEAT_F32;
-    s.n_images = 0;
-    s.max_len = s.nuniq = 0;
-    s.lens.clear();
+    ctx->slot[si].held = BatchDesc{};
+    ctx->slot[si].upload_pending = ctx->slot[si].consumed_valid = false;
     ++ctx->slot_serial[si];
   }
-  if (ctx->async_ready) make_current(ctx, 0);
-  ctx->feat_type = RAU_FEAT_F32;
-  ctx->n_images = 0;
-  ctx->lens_h.clear();
-  ctx->max_len = ctx->nuniq = 0;
-  ctx->have_batch = ctx->have_labels = false;
+  ctx->cur_slot = 0;
   ctx->x_valid = false;
   ctx->fwd_table = false;
   ctx->xw = nullptr;
@@ -1308,195 +846,6 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   if (ctx->perr_h) *ctx->perr_h = 0;
   return RAU_OK;
 }
-
-// ------------------------------------------------------------------ feature bank
-// Every enqueued reader of the bank (the gathers: copy stream and chain stream) has finished.
-static int bank_quiesce(rau_ctx* ctx) {
-  if (ctx->stc) HIPC(hipStreamSynchronize(ctx->stc));
-  HIPC(hipStreamSynchronize(ctx->st));
-  return RAU_OK;
-}
-static size_t bank_map_bytes(const rau_ctx* ctx) {
-  return (size_t)ctx->cfg.D * ctx->Sp * (ctx->bank_type == RAU_FEAT_F32 ? 4 : 2);
-}
-
-int rau_bank_create(rau_ctx* ctx, int32_t capacity, int feat_type) {
-  NEED(ctx, "null ctx");
-  NEED(feat_type_ok(feat_type), "rau_bank_create: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)", feat_type);
-  NEED(capacity >= 1, "rau_bank_create: capacity %d", capacity);
-  if (ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_create: the context already has a bank (rau_bank_destroy first)");
-  const size_t bytes = (size_t)capacity * ctx->cfg.D * ctx->Sp * (feat_type == RAU_FEAT_F32 ? 4 : 2);
-  void* d = nullptr;
-  hipError_t e = hipMalloc(&d, bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();   // the failed allocation is reported here, not by the next launch
-    return fail(RAU_ERR_NOMEM, "rau_bank_create: hipMalloc(%zu bytes for %d maps) failed: %s", bytes, capacity,
-                hipGetErrorString(e));
-  }
-  e = hipMemsetAsync(d, 0, bytes, ctx->st);   // pad columns stay zero for the bank's lifetime
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
-  if (e != hipSuccess) {
-    hipFree(d);
-    return fail(RAU_ERR_DEVICE, "rau_bank_create: clearing the bank: %s", hipGetErrorString(e));
-  }
-  ctx->bank = d;
-  ctx->bank_cap = capacity;
-  ctx->bank_type = feat_type;
-  ctx->bank_filled = 0;
-  ctx->bank_written.assign((size_t)capacity, 0);
-  return RAU_OK;
-}
-
-int rau_bank_destroy(rau_ctx* ctx) {
-  NEED(ctx, "null ctx");
-  if (!ctx->bank) return RAU_OK;
-  if (int rc = bank_quiesce(ctx)) return rc;
-  // captured steps of bank batches hold the bank's address
-  for (auto it = ctx->graphs.begin(); it != ctx->graphs.end();)
-    if ((it->first >> 35) & 1) { hipGraphExecDestroy(it->second); it = ctx->graphs.erase(it); } else ++it;
-  for (int si = 0; si < 2; ++si) {   // a batch drawn from the bank is gone with it
-    BatchSlot& s = ctx->slot[si];
-    if (!s.bank) continue;
-    s.bank = s.table_ok = s.have = false;
-    if (si == ctx->cur_slot) ctx->have_batch = ctx->fwd_done = false;
-  }
-  hipFree(ctx->bank);
-  if (ctx->bank_stage) hipFree(ctx->bank_stage);
-  for (int k = 0; k < 2; ++k) {
-    if (ctx->bank_pin[k]) hipHostFree(ctx->bank_pin[k]);
-    if (ctx->bank_ev[k]) hipEventDestroy(ctx->bank_ev[k]);
-    ctx->bank_pin[k] = nullptr;
-    ctx->bank_ev[k] = nullptr;
-  }
-  ctx->bank = nullptr;
-  ctx->bank_stage = nullptr;
-  ctx->bank_chunk = 0;
-  ctx->bank_cap = ctx->bank_filled = 0;
-  ctx->bank_written.clear();
-  ctx->x_valid = false;
-  return RAU_OK;
-}
-
-int rau_bank_info(rau_ctx* ctx, int32_t* capacity, int* feat_type, int32_t* rows_filled) {
-  NEED(ctx, "null ctx");
-  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_info: the context has no feature bank");
-  if (capacity) *capacity = ctx->bank_cap;
-  if (feat_type) *feat_type = ctx->bank_type;
-  if (rows_filled) *rows_filled = ctx->bank_filled;
-  return RAU_OK;
-}
-
-int rau_bank_put(rau_ctx* ctx, int32_t first, int32_t count, const void* feats, int src_type) {
-  NEED(ctx && feats, "null argument");
-  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_put: the context has no feature bank (rau_bank_create)");
-  NEED(feat_type_ok(src_type), "rau_bank_put: src_type %d (RAU_FEAT_F32 | _F16 | _BF16)", src_type);
-  NEED(src_type == ctx->bank_type || src_type == RAU_FEAT_F32,
-       "rau_bank_put: maps of type %d into a bank of type %d (equal types, or f32 into a 16-bit bank)", src_type,
-       ctx->bank_type);
-  NEED(first >= 0 && count >= 1 && (int64_t)first + count <= ctx->bank_cap, "rau_bank_put: rows [%d,%d) out of [0,%d)",
-       first, first + count, ctx->bank_cap);
-  const rau_config& c = ctx->cfg;
-  const bool narrow = src_type != ctx->bank_type;
-  const size_t ses = src_type == RAU_FEAT_F32 ? 4 : 2, src_map = (size_t)c.D * c.S * ses, map_bytes = bank_map_bytes(ctx);
-  const size_t bes = ctx->bank_type == RAU_FEAT_F32 ? 4 : 2;
-  if (!ctx->bank_chunk) {   // staging sized for f32 sources: 32 MiB, at least one map
-    const size_t chunk = std::max<size_t>((size_t)32 << 20, (size_t)c.D * c.S * 4);
-    for (int k = 0; k < 2; ++k) {
-      if (!ctx->bank_pin[k]) {
-        hipError_t e = hipHostMalloc(&ctx->bank_pin[k], chunk, hipHostMallocDefault);
-        if (e != hipSuccess) {
-          ctx->bank_pin[k] = nullptr;
-          return fail(RAU_ERR_NOMEM, "rau_bank_put: hipHostMalloc(%zu bytes staging): %s", chunk, hipGetErrorString(e));
-        }
-      }
-      if (!ctx->bank_ev[k]) HIPC(hipEventCreateWithFlags(&ctx->bank_ev[k], hipEventDisableTiming));
-    }
-    ctx->bank_chunk = chunk;
-  }
-  if (narrow && !ctx->bank_stage) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->bank_stage), ctx->bank_chunk);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->bank_stage = nullptr;
-      return fail(RAU_ERR_NOMEM, "rau_bank_put: hipMalloc(%zu bytes staging): %s", ctx->bank_chunk, hipGetErrorString(e));
-    }
-  }
-  if (int rc = bank_quiesce(ctx)) return rc;   // enqueued gathers read the rows being replaced
-  const int32_t per = (int32_t)std::min<size_t>(ctx->bank_chunk / src_map, (size_t)count);
-  hipStream_t st = ctx->st;
-  bool used[2] = {false, false};
-  int k = 0;
-  for (int32_t r0 = 0; r0 < count; r0 += per, k ^= 1) {
-    const int32_t n = std::min(per, count - r0);
-    if (used[k]) HIPC(hipEventSynchronize(ctx->bank_ev[k]));   // the staging's last copy has left it
-    std::memcpy(ctx->bank_pin[k], static_cast<const char*>(feats) + (size_t)r0 * src_map, (size_t)n * src_map);
-    char* dst = static_cast<char*>(ctx->bank) + (size_t)(first + r0) * map_bytes;
-    if (narrow) {
-      // (one device staging: the stream orders the next chunk's copy behind this chunk's kernel)
-      HIPC(hipMemcpyAsync(ctx->bank_stage, ctx->bank_pin[k], (size_t)n * src_map, hipMemcpyHostToDevice, st));
-      RUN("bank_narrow", 0, (double)n * (src_map + map_bytes),
-          narrow_features(st, (size_t)n * c.D, c.S, ctx->Sp, ctx->bank_stage, dst, ctx->bank_type));
-    } else if (ctx->Sp == c.S) {
-      HIPC(hipMemcpyAsync(dst, ctx->bank_pin[k], (size_t)n * src_map, hipMemcpyHostToDevice, st));
-    } else {
-      HIPC(hipMemcpy2DAsync(dst, (size_t)ctx->Sp * bes, ctx->bank_pin[k], (size_t)c.S * bes, (size_t)c.S * bes,
-                            (size_t)n * c.D, hipMemcpyHostToDevice, st));
-    }
-    HIPC(hipEventRecord(ctx->bank_ev[k], st));
-    used[k] = true;
-  }
-  HIPC(hipStreamSynchronize(st));
-  for (int32_t r = first; r < first + count; ++r)
-    if (!ctx->bank_written[r]) { ctx->bank_written[r] = 1; ++ctx->bank_filled; }
-  ctx->x_valid = false;   // an expansion made from replaced rows is stale
-  return RAU_OK;
-}
-
-int rau_bank_get(rau_ctx* ctx, int32_t first, int32_t count, void* feats) {
-  NEED(ctx && feats, "null argument");
-  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_get: the context has no feature bank (rau_bank_create)");
-  NEED(first >= 0 && count >= 1 && (int64_t)first + count <= ctx->bank_cap, "rau_bank_get: rows [%d,%d) out of [0,%d)",
-       first, first + count, ctx->bank_cap);
-  const rau_config& c = ctx->cfg;
-  const size_t bes = ctx->bank_type == RAU_FEAT_F32 ? 4 : 2, map_bytes = bank_map_bytes(ctx);
-  const char* src = static_cast<const char*>(ctx->bank) + (size_t)first * map_bytes;
-  HIPC(hipStreamSynchronize(ctx->st));
-  if (ctx->Sp == c.S)
-    HIPC(hipMemcpy(feats, src, (size_t)count * map_bytes, hipMemcpyDeviceToHost));
-  else
-    HIPC(hipMemcpy2D(feats, (size_t)c.S * bes, src, (size_t)ctx->Sp * bes, (size_t)c.S * bes, (size_t)count * c.D,
-                     hipMemcpyDeviceToHost));
-  return RAU_OK;
-}
-
-}  // extern "C"
-
-int batch_maps(rau_ctx* ctx, const float** maps) {
-  *maps = ctx->feats;
-  if (!ctx->n_images) return RAU_OK;
-  const rau_config& c = ctx->cfg;
-  *maps = ctx->feats_x;
-  // a captured launch gathers on every replay (the table and the index live in device memory); otherwise once
-  // per upload into the slot
-  if (!ctx->capturing && ctx->x_valid && ctx->x_slot == ctx->cur_slot &&
-      ctx->x_serial == ctx->slot_serial[ctx->cur_slot])
-    return RAU_OK;
-  const size_t map_bytes = (size_t)c.D * ctx->Sp * (ctx->feat_type == RAU_FEAT_F32 ? 4 : 2);
-  hipStream_t st = ctx->st;
-  const BatchSlot& bs = ctx->slot[ctx->cur_slot];
-  if (bs.bank)   // one pass with the composed index rows[image_of[b]] (the second half of the slot's bank index)
-    RUN("bank_gather", 0, 2.0 * c.B * map_bytes,
-        bank_gather(st, c.B, map_bytes, ctx->bank, ctx->bank_cap, bs.bank_idx_d + c.B, ctx->feats_x));
-  else
-    RUN("expand_features", 0, 2.0 * c.B * map_bytes,
-        expand_features(st, c.B, map_bytes, ctx->feats, bs.image_of_d, ctx->feats_x));
-  ctx->x_valid = true;
-  ctx->x_slot = ctx->cur_slot;
-  ctx->x_serial = ctx->slot_serial[ctx->cur_slot];
-  return RAU_OK;
-}
-
-extern "C" {
 
 }  // extern "C"
 
@@ -1818,18 +1167,19 @@ static int seam_mask() {
   return m;
 }
 static bool head_dgrad_fwd(const rau_ctx* ctx) {
-  return ctx->have_labels && ctx->mode == RAU_MODE_TRAIN && (seam_mask() & 1);
+  return cur_batch(ctx).held.have_labels && ctx->mode == RAU_MODE_TRAIN && (seam_mask() & 1);
 }
 
 int rau_forward(rau_ctx* ctx) {
   NEED(ctx, "null ctx");
-  if (!ctx->have_batch) return fail(RAU_ERR_STATE, "rau_forward: no batch (call rau_set_batch)");
+  BatchSlot& bs = cur_batch(ctx);
+  if (!bs.held.have) return fail(RAU_ERR_STATE, "rau_forward: no batch (call rau_set_batch)");
   ctx->mg_valid = false;   // the hop outputs are being overwritten
   set_skinny_policy(ctx);
   const rau_config& c = ctx->cfg;
   const int B = c.B, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R,
             H = c.H, Q = ctx->Q;
-  const int TL = ctx->max_len;
+  const int TL = bs.held.max_len;
   hipStream_t st = ctx->st;
   if (int rc = gen_masks(ctx, RAU_MASK_X)) return rc;
   const bool tr = ctx->mode == RAU_MODE_TRAIN;
@@ -1861,7 +1211,7 @@ int rau_forward(rau_ctx* ctx) {
     const int rows = TL * B;
     const size_t G4 = (size_t)B * 4 * Rq;
     RUN("embed_fwd", 0, rows * E * 8.0,
-        embed_fwd(st, rows, E, c.V, ctx->grp[RAU_GROUP_EMBED].w, ctx->tokens, m_we, sc(RAU_MASK_WE),
+        embed_fwd(st, rows, E, c.V, ctx->grp[RAU_GROUP_EMBED].w, bs.tokens, m_we, sc(RAU_MASK_WE),
                   ctx->we));
     const bool ws_path = (ctx->mode == RAU_MODE_EVAL ? ctx->enc_ws : ctx->enc_ws_train) && ctx->perr_h;
     // Layer-1 input projection of every token (no recurrence in it).  Only the first tokens' rows
@@ -1970,16 +1320,16 @@ int rau_forward(rau_ctx* ctx) {
   // i_embed and the attention pre-activation run once per IMAGE and the attention kernels read sample b's
   // tiles at row image_of[b].  Everywhere else (train mode: per-sample masks; a captured step: its backward
   // needs per-sample I) the table is gathered into per-sample maps first and the plain path runs on those.
-  const bool table_fwd = ctx->n_images > 0 && ctx->I_shared && ctx->mode == RAU_MODE_EVAL && !ctx->capturing;
-  const int nX = table_fwd ? ctx->n_images : B;   // maps the image-side passes read
-  const int32_t* img = table_fwd ? ctx->slot[ctx->cur_slot].image_of_d : nullptr;
-  const float* feats = ctx->feats;
-  if (table_fwd && ctx->slot[ctx->cur_slot].bank && !ctx->slot[ctx->cur_slot].table_ok) {
+  const bool table_fwd = bs.held.n_images > 0 && ctx->I_shared && ctx->mode == RAU_MODE_EVAL && !ctx->capturing;
+  const int nX = table_fwd ? bs.held.n_images : B;   // maps the image-side passes read
+  const int32_t* img = table_fwd ? bs.image_of_d : nullptr;
+  const float* feats = bs.feats;
+  if (table_fwd && bs.held.bank && !bs.held.table_ok) {
     // a bank batch handed over in train mode carries its row index only: the table is gathered now
-    const size_t map_bytes = (size_t)D * S * (ctx->feat_type == RAU_FEAT_F32 ? 4 : 2);
+    const size_t map_bytes = (size_t)D * S * (bs.held.feat_type == RAU_FEAT_F32 ? 4 : 2);
     RUN("bank_gather", 0, 2.0 * nX * map_bytes,
-        bank_gather(st, nX, map_bytes, ctx->bank, ctx->bank_cap, ctx->slot[ctx->cur_slot].bank_idx_d, ctx->feats));
-    ctx->slot[ctx->cur_slot].table_ok = true;
+        bank_gather(st, nX, map_bytes, ctx->bank, ctx->bank_cap, bs.bank_idx_d, bs.feats));
+    bs.held.table_ok = true;
   }
   if (!table_fwd)
     if (int rc = batch_maps(ctx, &feats)) return rc;   // (on st, in front of evA: the bulk stream is ordered behind it)
@@ -2004,7 +1354,7 @@ int rau_forward(rau_ctx* ctx) {
     RUNS(sb, "transpose", 0, (double)M * D * 8, transpose2d(sb, M, D, ctx->i_embed.W, ctx->WiT, ctx->WiT16));
     RUNS(sb, "transpose", 0, (double)A * M * 8, transpose2d(sb, A, M, ctx->att_i.W, ctx->WpT, ctx->WpT16));
     // the batch's element type: 16-bit maps are widened (exactly) by the pass that reads them
-    const int ft = ctx->feat_type;
+    const int ft = bs.held.feat_type;
     const double xb = ft == RAU_FEAT_F32 ? 4 : 2;   // bytes per element read from the batch
     if (x_gen)
       RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * (x16 ? 2 : 4),
@@ -2055,7 +1405,7 @@ int rau_forward(rau_ctx* ctx) {
 
   if (int rc = encoder_forward()) return rc;
   RUN("gather_q", 0, (double)B * Q * 8,
-      gather_q(st, B, Rq, TL, ctx->lens_d, ctx->c1, ctx->h1, ctx->c2, ctx->h2, ctx->q));
+      gather_q(st, B, Rq, TL, bs.lens_d, ctx->c1, ctx->h1, ctx->c2, ctx->h2, ctx->q));
 
   // ---------------- RAU hops, SS:467-520
   const size_t BM_ = (size_t)B * M, BR_ = (size_t)B * R;
@@ -2092,7 +1442,7 @@ int rau_forward(rau_ctx* ctx) {
   // Evaluate mode: dropout is the identity, so I is hop-invariant and computed once.
   HIPC(hipMemsetAsync(ctx->cc, 0, BR_ * sizeof(float), st));  // att_c, att_h zeros SS:362-365
   HIPC(hipMemsetAsync(ctx->hh, 0, BR_ * sizeof(float), st));
-  const int32_t* labels = ctx->have_labels ? ctx->labels_d : nullptr;
+  const int32_t* labels = bs.held.have_labels ? bs.labels_d : nullptr;
   const size_t reg3 = ctx->slab3_floats / 4;
   const int head_max = (int)std::max<size_t>(1, reg3 / ((size_t)B * c.K));  // rows the logits slab holds
   int gstart = 0;
@@ -2145,7 +1495,7 @@ int rau_forward(rau_ctx* ctx) {
   }
   HIPC(hipEventRecord(ctx->evHd, ctx->st3));
   HIPC(hipStreamWaitEvent(st, ctx->evHd, 0));   // callers order against st only
-  if (ctx->have_labels)
+  if (bs.held.have_labels)
     RUN("loss_reduce", 0, 0, loss_reduce(st, H, B, ctx->lossrow, ctx->losses_d));
   if (!ctx->capturing) merge_record(ctx);   // (rau_graph_step records behind its launch)
   ctx->fwd_done = true;
@@ -2179,11 +1529,12 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
                 "i_embed once per image, so there is no per-sample I to differentiate; take evaluate-mode "
                 "gradients on a plain batch (rau_set_batch)");
   set_skinny_policy(ctx);
-  if (!ctx->have_labels) return fail(RAU_ERR_STATE, "rau_backward: batch has no labels");
+  const BatchSlot& bs = cur_batch(ctx);
+  if (!bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_backward: batch has no labels");
   const rau_config& c = ctx->cfg;
   const int B = c.B, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R,
             K = c.K, H = c.H, Q = ctx->Q;
-  const int TL = ctx->max_len;
+  const int TL = bs.held.max_len;
   // Backward launch groups of the bulk stream.  Forward groups want to be large (the flattened-
   // column kernels lose a ragged last round per launch); the backward kernels do not (per-sample
   // dgrad tiles and the split-K weight gradients fill whole rounds at any hop count), and a
@@ -2462,7 +1813,7 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
             gemm_nn_batched_deferred(st, nb, B, Rq, 4 * Rq, Ap, 4 * Rq, Wp, Rq, ctx->slab,
                                      ctx->slab_floats, &nsp));
       LstmBwdCells cells{};
-      cells.lens = ctx->lens_d;
+      cells.lens = bs.lens_d;
       cells.dq_rs = Q;
       if (u >= 1) {  // layer-2 cell t = u
         LstmBwdCell& C2 = cells.c[cells.n++];
@@ -2501,7 +1852,7 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
           gemm_nn(st, rows, E, 4 * Rq, ctx->dG1, 4 * Rq, ctx->i2h[0].W, E, ctx->dwe, E, o));
     }
     RUN("embed_bwd", 0, (double)rows * E * 12,
-        embed_bwd(st, ctx->capturing ? c.T * B : ctx->nuniq, E, ctx->utok, ctx->ustart, ctx->upos, ctx->dwe, ctx->we, m_we,
+        embed_bwd(st, ctx->capturing ? c.T * B : bs.held.nuniq, E, bs.utok, bs.ustart, bs.upos, ctx->dwe, ctx->we, m_we,
                   sc(RAU_MASK_WE), ctx->grp[RAU_GROUP_EMBED].g));
     if (int rc = enc_wgrads(0, hi, ctx->evE)) return rc;
   }
@@ -2523,20 +1874,21 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
 // (uploaded here, in front of the launch).
 int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
   NEED(ctx && hop_w, "null argument");
-  if (!ctx->have_batch || !ctx->have_labels)
+  const BatchSlot& bs = cur_batch(ctx);
+  if (!bs.held.have || !bs.held.have_labels)
     return fail(RAU_ERR_STATE, "rau_graph_step: needs a batch with labels (rau_set_batch)");
   if (ctx->prof_on) return fail(RAU_ERR_STATE, "rau_graph_step: profiling must be off");
   const int H = ctx->cfg.H;
   int HA = 0;
   for (int h = 0; h < H; ++h)
     if (hop_w[h] != 0.f) HA = h + 1;
-  uint64_t key = (uint64_t)ctx->mode | ((uint64_t)ctx->max_len << 2) | ((uint64_t)HA << 12) |
+  uint64_t key = (uint64_t)ctx->mode | ((uint64_t)bs.held.max_len << 2) | ((uint64_t)HA << 12) |
                  ((uint64_t)(zero_grads_first != 0) << 22);
   for (int i = 0; i < 5; ++i) key |= (uint64_t)ctx->mexplicit[i] << (24 + i);
   key |= (uint64_t)ctx->cur_slot << 30;   // the captured kernels hold the batch slot's device pointers
-  key |= (uint64_t)ctx->feat_type << 32;  // ... and read the batch in its element type
-  key |= (uint64_t)(ctx->n_images > 0) << 34;   // ... through the gather of an image table (any table, any N)
-  key |= (uint64_t)ctx->slot[ctx->cur_slot].bank << 35;   // ... of a bank batch: out of the bank
+  key |= (uint64_t)bs.held.feat_type << 32;  // ... and read the batch in its element type
+  key |= (uint64_t)(bs.held.n_images > 0) << 34;   // ... through the gather of an image table (any table, any N)
+  key |= (uint64_t)bs.held.bank << 35;   // ... of a bank batch: out of the bank
   key |= (uint64_t)ctx->cfg.B << 36;      // every launch is shaped by the batch size (rau_set_batch_size)
   if (int rc = upload_hop_weights(ctx, hop_w)) return rc;
   ctx->mg_valid = false;
@@ -2565,7 +1917,7 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
     ctx->graphs.push_back({key, exec});
   }
   HIPC(hipGraphLaunch(exec, ctx->st));
-  if (ctx->n_images) {   // the graph's gather node has just filled feats_x from this upload
+  if (bs.held.n_images) {   // the graph's gather node has just filled feats_x from this upload
     ctx->x_valid = true;
     ctx->x_slot = ctx->cur_slot;
     ctx->x_serial = ctx->slot_serial[ctx->cur_slot];

@@ -81,13 +81,13 @@ int lin_wgrad(rau_ctx* ctx, Lin& l, const float* dY, const float* X, long ldx, b
 // its exact widening into ctx-owned scratch (allocated on first use), so that the f32 kernels run on it
 int resident_feats(rau_ctx* ctx, const float** X) {
   if (int rc = batch_maps(ctx, X)) return rc;   // a batch with an image table: its per-sample expansion
-  if (ctx->feat_type == RAU_FEAT_F32) return 0;
+  if (cur_batch(ctx).held.feat_type == RAU_FEAT_F32) return 0;
   const float* src = *X;
   const rau_config& c = ctx->cfg;
   if (!ctx->m_Xw)
     if (int rc = dalloc(ctx, &ctx->m_Xw, (size_t)ctx->cap * c.D * ctx->Sp)) return rc;
   RUN("widen_features", 0, (double)c.B * c.D * ctx->Sp * 6,
-      widen_features(ctx->st, (size_t)c.B * c.D, c.S, ctx->Sp, src, ctx->m_Xw, ctx->feat_type));
+      widen_features(ctx->st, (size_t)c.B * c.D, c.S, ctx->Sp, src, ctx->m_Xw, cur_batch(ctx).held.feat_type));
   *X = ctx->m_Xw;
   return 0;
 }
@@ -128,8 +128,8 @@ int rau_embed_forward(rau_ctx* ctx, int t, const int32_t* tokens_dev, float** we
   if (int rc = mod_alloc(ctx)) return rc;
   if (int rc = ensure_masks(ctx)) return rc;
   if (!tokens_dev) {
-    if (!ctx->have_batch) return fail(RAU_ERR_STATE, "rau_embed_forward: no tokens and no batch");
-    tokens_dev = ctx->tokens + (size_t)t * c.B;
+    if (!cur_batch(ctx).held.have) return fail(RAU_ERR_STATE, "rau_embed_forward: no tokens and no batch");
+    tokens_dev = cur_batch(ctx).tokens + (size_t)t * c.B;
   }
   const Masks m = masks_of(ctx);
   float* out = ctx->we + (size_t)t * c.B * c.E;
@@ -146,8 +146,8 @@ int rau_embed_backward(rau_ctx* ctx, int t, const int32_t* tokens_dev, const flo
   NEED(t >= 0 && t < c.T, "rau_embed_backward: t=%d out of [0,%d)", t, c.T);
   if (int rc = mod_alloc(ctx)) return rc;
   if (!tokens_dev) {
-    if (!ctx->have_batch) return fail(RAU_ERR_STATE, "rau_embed_backward: no tokens and no batch");
-    tokens_dev = ctx->tokens + (size_t)t * c.B;
+    if (!cur_batch(ctx).held.have) return fail(RAU_ERR_STATE, "rau_embed_backward: no tokens and no batch");
+    tokens_dev = cur_batch(ctx).tokens + (size_t)t * c.B;
   }
   const Masks m = masks_of(ctx);
   RUN("embed_bwd", 0, c.B * c.E * 12.0,
@@ -281,7 +281,7 @@ int rau_multimodal_forward(rau_ctx* ctx, int h, const float* q, const float* X, 
   if (int rc = ensure_masks(ctx)) return rc;
   const bool resident = !X;   // the batch's own map, already at pitch Sp
   if (!X) {
-    if (!ctx->have_batch) return fail(RAU_ERR_STATE, "rau_multimodal_forward: no X and no batch");
+    if (!cur_batch(ctx).held.have) return fail(RAU_ERR_STATE, "rau_multimodal_forward: no X and no batch");
     if (int rc = resident_feats(ctx, &X)) return rc;
   }
   if (!c_prev) c_prev = ctx->m_zero;   // att_c / att_h zeros, SS:362-365
@@ -357,7 +357,7 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
   if (int rc = mod_alloc(ctx)) return rc;
   const bool resident = !X;
   if (!X) {
-    if (!ctx->have_batch) return fail(RAU_ERR_STATE, "rau_multimodal_backward: no X and no batch");
+    if (!cur_batch(ctx).held.have) return fail(RAU_ERR_STATE, "rau_multimodal_backward: no X and no batch");
     if (int rc = resident_feats(ctx, &X)) return rc;
   }
   if (!c_prev) c_prev = ctx->m_zero;
@@ -483,8 +483,8 @@ int rau_criterion_forward(rau_ctx* ctx, int h, const float* logits, const int32_
   NEED(h >= 0 && h < c.H, "rau_criterion_forward: h=%d out of [0,%d)", h, c.H);
   if (int rc = mod_alloc(ctx)) return rc;
   if (!labels_dev) {
-    if (!ctx->have_labels) return fail(RAU_ERR_STATE, "rau_criterion_forward: no labels");
-    labels_dev = ctx->labels_d;
+    if (!cur_batch(ctx).held.have_labels) return fail(RAU_ERR_STATE, "rau_criterion_forward: no labels");
+    labels_dev = cur_batch(ctx).labels_d;
   }
   RUN("ce_fwd", 0, (double)c.B * c.K * 12,
       ce_fwd(ctx->st, c.B, c.K, c.M, logits, labels_dev, nullptr, nullptr, nullptr,
@@ -506,8 +506,8 @@ int rau_criterion_backward(rau_ctx* ctx, int h, const float* logits, const int32
   NEED(h >= 0 && h < c.H, "rau_criterion_backward: h=%d out of [0,%d)", h, c.H);
   if (int rc = mod_alloc(ctx)) return rc;
   if (!labels_dev) {
-    if (!ctx->have_labels) return fail(RAU_ERR_STATE, "rau_criterion_backward: no labels");
-    labels_dev = ctx->labels_d;
+    if (!cur_batch(ctx).held.have_labels) return fail(RAU_ERR_STATE, "rau_criterion_backward: no labels");
+    labels_dev = cur_batch(ctx).labels_d;
   }
   float* dl = ctx->dl + (size_t)h * c.B * c.K;
   RUN("ce_fwd", 0, (double)c.B * c.K * 12,
