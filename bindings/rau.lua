@@ -109,6 +109,8 @@ int rau_dev_select_rows(rau_ctx* ctx, float* dst, const float* src, int32_t rows
                         const int32_t* key_dev, int32_t value);
 int rau_dev_rowmax(rau_ctx* ctx, const float* x, int32_t rows, int32_t cols, float* max_dev,
                    int32_t* argmax_dev);
+int rau_dev_topk(rau_ctx* ctx, const float* x, int32_t rows, int32_t cols, int32_t k,
+                 float* val_dev, int32_t* idx_dev);
 int rau_dev_sum(rau_ctx* ctx, const float* x, size_t n, double* out_host);
 int rau_dev_count_eq(rau_ctx* ctx, const int32_t* a_dev, const int32_t* b_dev, int32_t n,
                      int32_t* count_host);
@@ -126,6 +128,7 @@ int rau_get_att_state(rau_ctx* ctx, float* c, float* h);
 int rau_step_stats(rau_ctx* ctx, float* loss, float* loss_do_pred, int32_t* counts);
 int rau_predict(rau_ctx* ctx, const int32_t* mc_ans, int32_t n_mc, int32_t* oe, int32_t* mc);
 int rau_get_merged(rau_ctx* ctx, float* pred, float* att);
+int rau_topk(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf);
 int rau_noise_clip_adam(rau_ctx* ctx, int64_t step_t, float lr, float mult_lr,
                         float beta1, float beta2, float eps, float eta, float gamma,
                         float clip, uint64_t noise_seed, float* out_norms);
@@ -375,6 +378,17 @@ function RAU:predict(ans_mc)
   return oe, mc
 end
 
+-- the k best open-ended answers of every predict_result row (hops, uni, select; last hop forced) of
+-- the last forward: ids (IntTensor, 1-based, ids[{r, b, 1}] == predict()'s oe[{r, b}]), their logits and
+-- their softmax confidences (FloatTensors), each [nHop+2, B, k], best first, ties by the lower id
+function RAU:topk(k)
+  local H, B = self.cfg.H, self.n
+  local ids = torch.IntTensor(H + 2, B, k)
+  local score, conf = torch.FloatTensor(H + 2, B, k), torch.FloatTensor(H + 2, B, k)
+  check(C.rau_topk(self.h, k, ids:data(), score:data(), conf:data()))
+  return ids, score, conf
+end
+
 -- data parallel (one process per GPU): rank 0 calls RAU.commId() and ships the 128-byte string
 -- to the other ranks (file, socket, ...); every rank then calls rau:commInit(n, rank, id) once
 -- and rau:allreduceGrads() between rau:backward(w) and rau:update(...)
@@ -490,6 +504,15 @@ function Tensor:max(dim)
   ring.k = ring.k % 4 + 1
   local v, i = ring[ring.k][1], ring[ring.k][2]
   check(C.rau_dev_rowmax(self.rau.h, self.ptr, r, c, v.ptr, i.ptr))
+  return v, i
+end
+-- torch.topk(t, k, 2, true, true): values [rows,k], best first, and their 1-based indices [rows,k];
+-- ties by the lower index, NaN last.  The results are the caller's (owned tensors).
+function Tensor:topk(k)
+  assert(#self.size == 2, 'only topk over dimension 2 of a matrix')
+  local r, c = self.size[1], self.size[2]
+  local v, i = Tensor.new(self.rau, r, k), IntTensor.new(self.rau, r, k)
+  check(C.rau_dev_topk(self.rau.h, self.ptr, r, c, k, v.ptr, i.ptr))
   return v, i
 end
 -- dst rows k with key[k] == value take src's rows: the whole `for k=1,B do if x_len[k]==t ...`

@@ -424,6 +424,17 @@ int rau_dev_select_rows(rau_ctx* ctx, float* dst, const float* src, int32_t rows
 /* torch.max(x, 2): per-row maximum and FIRST maximal index, 1-based (either output may be NULL) */
 int rau_dev_rowmax(rau_ctx* ctx, const float* x, int32_t rows, int32_t cols, float* max_dev,
                    int32_t* argmax_dev);
+/* torch.topk(x, k, 2, true, true): per row the k largest entries in descending order and their
+ * 1-based indices (either output may be NULL).  x [rows, cols], val_dev [rows, k], idx_dev [rows, k];
+ * rows >= 0 (0: nothing to do), cols > 0 (no alignment rule), 1 <= k <= cols, else RAU_ERR_INVALID with
+ * nothing launched.  The order is TOTAL: larger value first; equal values (float equality, so +0 == -0)
+ * by the LOWER index -- rau_dev_rowmax's first-max rule at every rank; +-inf order as values; NaN after
+ * everything, -inf included, NaNs among themselves by the lower index.  So the k indices of a row are
+ * distinct and in [1, cols] whatever the row holds, and rank 0 is rau_dev_rowmax on a row without NaN.
+ * val_dev holds the selected entries bit for bit (NaN payloads, the sign of a zero).  Repeated calls
+ * give the same bits.  Not synchronising. */
+int rau_dev_topk(rau_ctx* ctx, const float* x, int32_t rows, int32_t cols, int32_t k,
+                 float* val_dev, int32_t* idx_dev);
 int rau_dev_sum(rau_ctx* ctx, const float* x, size_t n, double* out_host);
 int rau_dev_count_eq(rau_ctx* ctx, const int32_t* a_dev, const int32_t* b_dev, int32_t n,
                      int32_t* count_host);
@@ -474,6 +485,20 @@ int rau_predict(rau_ctx* ctx, const int32_t* mc_ans, int32_t n_mc, int32_t* oe, 
 /* merged rows of the last rau_predict: pred [2,B,K] (uni, select), att [2,B,S] (uni, select;
  * select WITHOUT the reference's never-zeroed carry, which the host adds) -- either may be NULL */
 int rau_get_merged(rau_ctx* ctx, float* pred, float* att);
+/* The k best answers of every row of predict_result (H hops, uni, select; last hop forced, as
+ * rau_predict) of the last step-level forward, with their scores and softmax confidences.
+ * ids, score, conf: host [H+2, B, k]; any may be NULL.  Synchronising.
+ * ids: 1-based, in rau_dev_topk's total order, so ids[r, b, 0] is rau_predict's oe[r, b] on every
+ * finite row; score: the row's raw or merged logit at that id, bit for bit; conf: its softmax
+ * probability, expf(score - max) / sum expf(v - max) summed in the criterion's order (defined for
+ * finite rows; a non-finite row still gives distinct ids in [1, K]).  1 <= k <= K, else
+ * RAU_ERR_INVALID.  Valid when rau_predict is (RAU_ERR_STATE otherwise, nothing launched), in either
+ * mode; needs no labels; neither needs nor disturbs rau_predict, rau_get_merged or rau_step_stats.
+ * Its device staging is allocated at the first call and regrown for a larger k (RAU_ERR_NOMEM leaves
+ * the context usable).  Open-ended answers only: the reference's multiple-choice rule multiplies the
+ * raw logits by a 0/1 mask, so a ranked MC list would rank the masked-out zeros among the candidates;
+ * rau_predict stays the MC call. */
+int rau_topk(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf);
 
 /* ---- update: SS:597-630 + utils/optim_updates.lua:59-87 (row "next-1") -------
  * Gradient noise N(0, eta/((step_t+1)*gamma)), per-group L2 clip, Adam with

@@ -132,6 +132,8 @@ _SIGS = {
                                       C.c_void_p, C.c_int32]),
     "rau_dev_rowmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                  C.c_void_p]),
+    "rau_dev_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                               C.c_void_p]),
     "rau_dev_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double)]),
     "rau_dev_count_eq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                    C.POINTER(C.c_int32)]),
@@ -150,6 +152,7 @@ _SIGS = {
     "rau_step_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "rau_get_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rau_topk": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_noise_clip_adam": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_float] * 8 +
                             [C.c_uint64, C.c_void_p]),
     "rau_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -1,0 +1,50 @@
+// hop_merge.h -- the rows predict_result and feval read out of the resident hop outputs, for the
+// kernels that consume them (hop_merge.hip: statistics, first-max answers; topk.hip: ranked answers).
+// One definition of the merge arithmetic, so that every consumer sees the same bits.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "common.h"
+
+namespace rau {
+
+constexpr int kMT = 256;   // threads per sample: 4 waves
+
+// workgroup sum in k_ce_fwd's order: wave_sum, then (w0 + w1) + (w2 + w3)
+__device__ __forceinline__ float block_sum(float v, float* s_sum) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  v = wave_sum(v);
+  if (l == 0) s_sum[w] = v;
+  __syncthreads();
+  const float r = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+  __syncthreads();
+  return r;
+}
+
+// Entry k of row r of one sample (lg = its logits row of hop 0, hop stride hs):
+//   r < H    hop r's logits;
+//   r == H   uni, SS:482 + 522: uni_pred:zero(), :add(l_h) for h = 1..H, :div(nHop) -- sequential
+//            adds from +0, then a true division;
+//   r == H+1 select, SS:505-507: select_pred:zero():add(l_h * cur_h); at most one cur_h is 1, the
+//            others add +-0, so the row is 0 + l_hsel (all +0 when no hop fired, hsel < 0).
+__device__ __forceinline__ float row_val(const float* __restrict__ lg, size_t hs, int H, int r, int hsel,
+                                         int k) {
+  if (r < H) return lg[(size_t)r * hs + k];
+  if (r == H) {
+    float s = 0.f;
+    for (int h = 0; h < H; ++h) s += lg[(size_t)h * hs + k];
+    return __fdiv_rn(s, (float)H);
+  }
+  return hsel >= 0 ? 0.f + lg[(size_t)hsel * hs + k] : 0.f;
+}
+
+// First hop whose do_pred fires (do_pred > 0.5, SS:501): the clamp(do - did) / clamp(did + do)
+// recurrence of SS:505, 515 selects exactly that one.  force_last: predict_result's rule (SS:685).
+__device__ __forceinline__ int select_hop(const float* __restrict__ dopred, int H, int B, int b,
+                                          bool force_last) {
+  for (int h = 0; h < H; ++h)
+    if (dopred[(size_t)h * B + b] > 0.5f || (force_last && h == H - 1)) return h;
+  return -1;
+}
+
+}  // namespace rau

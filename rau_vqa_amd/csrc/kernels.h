@@ -407,5 +407,12 @@ hipError_t predict_rows(hipStream_t st, int H, int B, int K, int Sp, const float
                         float* att_out);
 // dynamic LDS bytes predict_rows takes with an MC list
 size_t predict_rows_lds(int K);
+// torch.topk(x, k, 2, true, true) of x [rows][cols] in the total order of include/rau.h (topk.hip):
+// val / idx [rows][k], idx 1-based, either may be null; rows > 0, 1 <= k <= cols
+hipError_t topk_rows(hipStream_t st, const float* x, int rows, int cols, int k, float* val, int32_t* idx);
+// the k best answers of predict_result's rows (hops, uni, select; last hop forced): ids / score / conf
+// [H+2][B][k], conf = softmax probability in row_ce's formulation; none may be null
+hipError_t topk_merged(hipStream_t st, int H, int B, int K, int k, const float* logits, const float* dopred,
+                       int32_t* ids, float* score, float* conf);
 
 }  // namespace rau

@@ -249,6 +249,10 @@ struct rau_ctx {
   float *mg_rowf = nullptr, *mg_out = nullptr, *mg_pred = nullptr, *mg_att = nullptr;
   int32_t *mg_rowi = nullptr, *mg_ans = nullptr, *mg_mc = nullptr;
   size_t mg_mc_cap = 0;           // int32 entries mg_mc holds
+  // rau_topk's staging: ids | score | conf, each [H+2][B][k]; room for [H+2][cap][mg_topk_k], allocated at
+  // its first call and regrown when a larger k is asked for
+  void* mg_topk = nullptr;
+  int mg_topk_k = 0;
   // update
   float *npart = nullptr, *norms_d = nullptr;
   bool fwd_done = false, bwd_done = false;

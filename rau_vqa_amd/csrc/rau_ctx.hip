@@ -2096,6 +2096,42 @@ int rau_predict(rau_ctx* ctx, const int32_t* mc_ans, int32_t n_mc, int32_t* oe, 
   return RAU_OK;
 }
 
+int rau_topk(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf) {
+  NEED(ctx, "null ctx");
+  const rau_config& c = ctx->cfg;
+  const int H = c.H, B = c.B, K = c.K;
+  NEED(k >= 1 && k <= K, "rau_topk: k=%d out of [1,%d] (the K of rau_create)", k, K);
+  if (int rc = merge_state(ctx, "rau_topk", false)) return rc;
+  if (k > ctx->mg_topk_k) {   // sized for the capacity; the smaller one goes once the larger one is there
+    uint32_t* fresh = nullptr;
+    if (int rc = dalloc(ctx, &fresh, (size_t)3 * (H + 2) * ctx->cap * k)) {
+      (void)hipGetLastError();   // the context stays as it was: nothing later may trip over this error
+      return rc;
+    }
+    if (void* old = ctx->mg_topk) {
+      HIPC(hipStreamSynchronize(ctx->st));
+      hipFree(old);
+      ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), old), ctx->allocs.end());
+      ctx->scratch.erase(std::remove_if(ctx->scratch.begin(), ctx->scratch.end(),
+                                        [&](const std::pair<void*, size_t>& r) { return r.first == old; }),
+                         ctx->scratch.end());
+    }
+    ctx->mg_topk = fresh;
+    ctx->mg_topk_k = k;
+  }
+  const size_t n = (size_t)(H + 2) * B * k;
+  int32_t* ids_d = static_cast<int32_t*>(ctx->mg_topk);
+  float* score_d = reinterpret_cast<float*>(ids_d + n);
+  float* conf_d = score_d + n;
+  RUN("topk_merged", 0, (double)B * (2 * H + 1) * K * 4,
+      topk_merged(ctx->st, H, B, K, k, ctx->logits, ctx->dopred, ids_d, score_d, conf_d));
+  if (ids) HIPC(hipMemcpyAsync(ids, ids_d, n * 4, hipMemcpyDeviceToHost, ctx->st));
+  if (score) HIPC(hipMemcpyAsync(score, score_d, n * 4, hipMemcpyDeviceToHost, ctx->st));
+  if (conf) HIPC(hipMemcpyAsync(conf, conf_d, n * 4, hipMemcpyDeviceToHost, ctx->st));
+  HIPC(hipStreamSynchronize(ctx->st));
+  return persist_check(ctx);
+}
+
 int rau_get_merged(rau_ctx* ctx, float* pred, float* att) {
   NEED(ctx, "null ctx");
   if (!ctx->mg_merged) return fail(RAU_ERR_STATE, "rau_get_merged: no rau_predict has run");

@@ -218,6 +218,14 @@ int rau_dev_rowmax(rau_ctx* ctx, const float* x, int32_t rows, int32_t cols, flo
   HIPC(hipGetLastError());
   return RAU_OK;
 }
+int rau_dev_topk(rau_ctx* ctx, const float* x, int32_t rows, int32_t cols, int32_t k, float* val_dev,
+                 int32_t* idx_dev) {
+  NEED(ctx && x, "null argument");
+  NEED(rows >= 0 && cols > 0, "rau_dev_topk: bad shape %d x %d", rows, cols);
+  NEED(k >= 1 && k <= cols, "rau_dev_topk: k=%d out of [1,%d]", k, cols);
+  if (rows) HIPC(rau::topk_rows(ctx->st, x, rows, cols, k, val_dev, idx_dev));
+  return RAU_OK;
+}
 int rau_dev_sum(rau_ctx* ctx, const float* x, size_t n, double* out_host) {
   NEED(ctx && out_host && (x || !n), "null argument");
   double* tmp = reinterpret_cast<double*>(ctx->norms_d);   // 4 floats = 2 doubles of scratch

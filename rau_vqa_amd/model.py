@@ -519,6 +519,19 @@ class RAU:
         L.check(self._lib.rau_get_merged(self._h, pred.ctypes.data, att.ctypes.data))
         return pred, att
 
+    def topk(self, k):
+        """The k best open-ended answers of every predict_result row of the last forward (hops, uni,
+        select; last hop forced, as predict()): (ids int32, score f32, conf f32), each [H+2, B, k],
+        best first.  Larger logit first, equal logits by the lower id, so ``ids[..., 0]`` is
+        predict()'s ``oe``; ``score`` is the row's logit at that id bit for bit, ``conf`` its softmax
+        probability.  predict.top_answers is the numpy restatement."""
+        shape = (self.cfg.H + 2, self._n, int(k))
+        ids = np.empty(shape, np.int32)
+        score = np.empty(shape, np.float32)
+        conf = np.empty(shape, np.float32)
+        L.check(self._lib.rau_topk(self._h, int(k), ids.ctypes.data, score.ctypes.data, conf.ctypes.data))
+        return ids, score, conf
+
     def outputs(self):
         c, h = self.att_state()
         return {"losses": self.losses(), "argmax": self.argmax(), "logits": self.logits(),

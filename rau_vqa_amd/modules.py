@@ -295,6 +295,14 @@ class DevTensor:
         i.is_int = True
         return v, i
 
+    def topk(self, k):                 # torch.topk(t, k, 2, true, true): (values [r,k], 1-based ids [r,k])
+        assert len(self.size) == 2
+        r, c = self.size
+        v, i = DevTensor.zeros(self.rau, r, k), DevTensor.zeros(self.rau, r, k)   # owned: released when collected
+        L.check(self.rau._lib.rau_dev_topk(self.rau._h, self.ptr, r, c, int(k), v.ptr, i.ptr))
+        i.is_int = True
+        return v, i
+
     def select_rows(self, src, key, value):
         r = self.size[0]
         L.check(self.rau._lib.rau_dev_select_rows(self.rau._h, self.ptr, src.ptr, r,

@@ -67,6 +67,42 @@ def answers(tab_pred, mc_ans=None):
     return oe, mc
 
 
+def rank_key(x):
+    """uint64 key whose DESCENDING order is the total order of rau_dev_topk / rau_topk on the f32
+    entries of x [..., K]: the high word is the monotone unsigned image of the float with -0
+    canonicalised to +0 and NaN below -inf, the low word is 0xffffffff - index, so equal values
+    order by the lower index and no two keys of a row are equal."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    nan = (u & np.uint32(0x7fffffff)) > np.uint32(0x7f800000)
+    u = np.where(u == np.uint32(0x80000000), np.uint32(0), u)
+    hi = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+    hi = np.where(nan, np.uint32(0), hi).astype(np.uint64)
+    lo = np.uint64(0xffffffff) - np.arange(u.shape[-1], dtype=np.uint64)
+    return (hi << np.uint64(32)) | lo
+
+
+def top_answers(tab_pred, k):
+    """The k best answers of every row of tab_pred ([R, B, K] or a list of R [B, K] arrays, as
+    merge_hops returns): (ids int32 1-based, score f32, conf f32), each [R, B, k], best first -- the
+    numpy statement of rau_topk's contract.  Larger value first; equal values (+0 == -0) by the lower
+    id, which extends first_max (SS:896, 900) to every rank; NaN after -inf, by the lower id.  score
+    is the entry itself, bit for bit; conf is the row's softmax probability, exp(score - max) /
+    sum exp(v - max) in float64, rounded to f32 at the end (defined for finite rows)."""
+    x = np.ascontiguousarray(np.stack([np.asarray(p, np.float32) for p in tab_pred]))
+    K = x.shape[-1]
+    if not 1 <= k <= K:
+        raise ValueError(f"k={k} out of [1,{K}]")
+    # a stable sort of the inverted key; keys are distinct, so stability only guards the statement
+    order = np.argsort(~rank_key(x), axis=-1, kind="stable")[..., :k]
+    score = np.take_along_axis(x, order, axis=-1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        x64 = x.astype(np.float64)
+        mx = np.take_along_axis(x64, order[..., :1], axis=-1)
+        e = np.exp(x64 - mx)
+        conf = np.exp(score.astype(np.float64) - mx) / e.sum(-1, keepdims=True)
+    return (order + 1).astype(np.int32), score, conf.astype(np.float32)
+
+
 def predict_result(rau, feats, tokens, lens, mc_ans=None, select_att_state=None, image_of=None):
     """SS:633-705 + SS:877-900 for one batch: returns dict(tab_pred, tab_att, oe, mc).
     select_att_state: see merge_hops (carry tab_att[-1] from batch to batch to reproduce the
@@ -80,20 +116,25 @@ def predict_result(rau, feats, tokens, lens, mc_ans=None, select_att_state=None,
 
 
 def predict_result_device(rau, feats, tokens, lens, mc_ans=None, select_att_state=None, tabs=True,
-                          image_of=None):
+                          image_of=None, topk=None):
     """predict_result with the merges, the MC masking and the answers done on the device
     (rau_predict): same keys, same values bit for bit.  The select attention row comes back without
     the reference's carried test_select_att; select_att_state is added here, as merge_hops does.
     tabs=False skips downloading the per-hop logits and maps: tab_pred / tab_att are then None and
     only the answers (and nothing of [H, B, K]) cross PCIe.  image_of: as in predict_result.
     Like predict_result it takes batches below the context's capacity (the test split's 83 rows on a
-    context trained at 100): set_batch switches the context to lens.shape[0] rows first."""
+    context trained at 100): set_batch switches the context to lens.shape[0] rows first.
+    topk=k adds top_ids, top_score, top_conf [H+2, B, k] (rau_topk: the k best open-ended answers of
+    every row with their logits and softmax confidences; top_answers states them in numpy)."""
     rau.evaluate()
     rau.set_batch(feats, tokens, lens, None, image_of=image_of)
     rau.forward()
     oe, mc = rau.predict(mc_ans)
+    top = {}
+    if topk is not None:
+        top["top_ids"], top["top_score"], top["top_conf"] = rau.topk(topk)
     if not tabs:
-        return {"tab_pred": None, "tab_att": None, "oe": oe, "mc": mc}
+        return {"tab_pred": None, "tab_att": None, "oe": oe, "mc": mc, **top}
     pred, att = rau.merged()
     if select_att_state is not None:
         att[1] = np.array(select_att_state, np.float32) + att[1]   # never zeroed, SS:671-674
@@ -101,4 +142,4 @@ def predict_result_device(rau, feats, tokens, lens, mc_ans=None, select_att_stat
     H = logits.shape[0]
     tab_pred = [logits[h] for h in range(H)] + [pred[0], pred[1]]
     tab_att = [hop_att[h] for h in range(H)] + [att[0], att[1]]
-    return {"tab_pred": tab_pred, "tab_att": tab_att, "oe": oe, "mc": mc}
+    return {"tab_pred": tab_pred, "tab_att": tab_att, "oe": oe, "mc": mc, **top}
