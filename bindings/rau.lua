@@ -215,11 +215,26 @@ function RAU:reset(seed, lo, hi) check(C.rau_init_uniform(self.h, seed or 123, l
 -- feats: FloatTensor [B,D,W,H]; x: IntTensor [T,B]; x_len, y: IntTensor [B]  (loader.lua:1009)
 -- A HalfTensor feats goes up as fp16 (rau_set_batch_typed): half the bytes, the same results
 -- bit for bit as feats:float().
-local FEAT = { f32 = 0, f16 = 1, bf16 = 2 }   -- rau_feat_type
-function RAU:setBatch(feats, x, x_len, y)
+-- fp8 maps (OCP e4m3fn / e5m2, one byte per element) travel as a ByteTensor of bit patterns and must be
+-- named: Torch7 has no fp8 tensor, so a ByteTensor without feat_type 'e4m3' | 'e5m2' is an error.
+local FEAT = { f32 = 0, f16 = 1, bf16 = 2, e4m3 = 4, e5m2 = 5 }   -- rau_feat_type (3 is reserved)
+local FEAT_BYTES = { f32 = 4, f16 = 2, bf16 = 2, e4m3 = 1, e5m2 = 1 }   -- bytes per element
+-- the rau_feat_type a tensor stands for: `feat_type` if given, else from the tensor's type
+local function feat_type_of(feats, feat_type)
+  local ty = feats and torch.type(feats)
+  if ty == 'torch.ByteTensor' then
+    assert(feat_type == 'e4m3' or feat_type == 'e5m2', "a ByteTensor of features needs feat_type 'e4m3' or 'e5m2'")
+  elseif feat_type == 'e4m3' or feat_type == 'e5m2' then
+    assert(feats == nil, 'fp8 features are a ByteTensor of bit patterns')
+  end
+  local name = feat_type or (ty == 'torch.HalfTensor' and 'f16') or 'f32'
+  return assert(FEAT[name], 'unknown feat_type ' .. tostring(name)), name
+end
+function RAU:setBatch(feats, x, x_len, y, feat_type)
   follow_rows(self, x_len)
-  if torch.type(feats) == 'torch.HalfTensor' then
-    check(C.rau_set_batch_typed(self.h, feats:data(), FEAT.f16, x:data(), x_len:data(), y and y:data() or nil))
+  local ft = feat_type_of(feats, feat_type)
+  if ft ~= FEAT.f32 then
+    check(C.rau_set_batch_typed(self.h, feats:data(), ft, x:data(), x_len:data(), y and y:data() or nil))
   else
     check(C.rau_set_batch(self.h, feats:data(), x:data(), x_len:data(), y and y:data() or nil))
   end
@@ -231,7 +246,8 @@ end
 -- assemble the batch in; rau:setBatchAsync(slot) enqueues the upload of what is in them (pass
 -- tensors to have them copied into the staging first); rau:useBatch(slot) makes it the resident
 -- batch -- the step's streams wait for the copies by an event, the host never does.
--- feat_type 'f16': the slot's feats come back as a HalfTensor over the start of its staging.
+-- feat_type 'f16': the slot's feats come back as a HalfTensor over the start of its staging; 'e4m3' | 'e5m2':
+-- as a ByteTensor (n bytes) over its start.
 function RAU:batchSlot(slot, feat_type)
   local f, x, l, y = ffi.new('float*[1]'), ffi.new('int32_t*[1]'), ffi.new('int32_t*[1]'), ffi.new('int32_t*[1]')
   check(C.rau_batch_slot(self.h, slot, f, x, l, y))
@@ -240,6 +256,8 @@ function RAU:batchSlot(slot, feat_type)
   local n = B * c.D * c.S
   return {
     feats = feat_type == 'f16' and torch.HalfTensor(torch.HalfStorage(n, addr(f[0]))):resize(B, c.D, c.S)
+            or FEAT_BYTES[feat_type or 'f32'] == 1
+               and torch.ByteTensor(torch.ByteStorage(n, addr(f[0]))):resize(B, c.D, c.S)
             or torch.FloatTensor(torch.FloatStorage(n, addr(f[0]))):resize(B, c.D, c.S),
     x = torch.IntTensor(torch.IntStorage(c.T * B, addr(x[0]))):resize(c.T, B),
     x_len = torch.IntTensor(torch.IntStorage(B, addr(l[0]))),
@@ -248,20 +266,21 @@ function RAU:batchSlot(slot, feat_type)
 end
 function RAU:setBatchAsync(slot, feats, x, x_len, y, has_labels, feat_type)
   follow_rows(self, x_len)
-  local ft = FEAT[feat_type or (feats and torch.type(feats) == 'torch.HalfTensor' and 'f16') or 'f32']
+  local ft = feat_type_of(feats, feat_type)
   check(C.rau_set_batch_async_typed(self.h, slot, feats and feats:data() or nil, ft, x and x:data() or nil,
                                     x_len and x_len:data() or nil, y and y:data() or nil,
                                     (has_labels == false) and 0 or 1))
 end
 function RAU:useBatch(slot) check(C.rau_use_batch(self.h, slot)) end
 
--- A batch whose questions share feature maps: feats is the image TABLE [N,D,W,H] (Float- or HalfTensor),
+-- A batch whose questions share feature maps: feats is the image TABLE [N,D,W,H] (Float- or HalfTensor, or a
+-- ByteTensor of fp8 codes with feat_type 'e4m3' | 'e5m2'),
 -- image_of an IntTensor [B] of 1-BASED table rows, as Torch indexes (feats:index(1, image_of:long()) is the
 -- plain batch); converted here to the 0-based row offsets of rau_set_batch_images.  Only the N maps are
 -- uploaded and, in evaluate mode, convolved.  slot = nil: the synchronous form.
-function RAU:setBatchImages(feats, image_of, x, x_len, y, slot, has_labels)
+function RAU:setBatchImages(feats, image_of, x, x_len, y, slot, has_labels, feat_type)
   follow_rows(self, x_len)
-  local ft = torch.type(feats) == 'torch.HalfTensor' and FEAT.f16 or FEAT.f32
+  local ft = feat_type_of(feats, feat_type)
   local idx = image_of:int():add(-1)
   if slot then
     check(C.rau_set_batch_async_images(self.h, slot, feats:data(), ft, feats:size(1), idx:data(), x:data(),
@@ -273,13 +292,14 @@ function RAU:setBatchImages(feats, image_of, x, x_len, y, slot, has_labels)
 end
 -- 0 for a plain resident batch, else the number of maps in its image table
 -- Feature bank: every image's map once in device memory (rau_bank_*).  bankCreate(capacity, 'f32' | 'f16' |
--- 'bf16'); bankPut(first, feats) takes a Float/HalfTensor [n,D,W,H] into the 1-based rows first .. first+n-1
--- (FloatTensors into a 16-bit bank are narrowed on the device).
+-- 'bf16' | 'e4m3' | 'e5m2'); bankPut(first, feats) takes a Float/HalfTensor [n,D,W,H] (or a ByteTensor of fp8
+-- codes with its feat_type) into the 1-based rows first .. first+n-1.  FloatTensors into a 16-bit or fp8 bank
+-- are narrowed on the device: round to nearest even; fp8 saturates at the largest finite value (448 / 57344).
 function RAU:bankCreate(capacity, feat_type)
   check(C.rau_bank_create(self.h, capacity, FEAT[feat_type or 'f32']))
 end
-function RAU:bankPut(first, feats)
-  local ft = torch.type(feats) == 'torch.HalfTensor' and FEAT.f16 or FEAT.f32
+function RAU:bankPut(first, feats, feat_type)
+  local ft = feat_type_of(feats, feat_type)
   check(C.rau_bank_put(self.h, first - 1, feats:size(1), feats:data(), ft))
 end
 function RAU:bankDestroy()

@@ -197,7 +197,8 @@ int rau_set_batch(rau_ctx* ctx, const float* feats, const int32_t* tokens,
                   const int32_t* lens, const int32_t* labels);
 /* device pointer of the resident feature buffer (producer may write it directly).  It is returned as it
  * is: after a 16-bit batch (rau_set_batch_typed) its first B*D*Sp*2 bytes hold that batch's 16-bit
- * elements at row pitch Sp (S rounded up to a multiple of 4), not floats; after a batch with an image
+ * elements at row pitch Sp (S rounded up to a multiple of 4), not floats; after an fp8 batch its first
+ * quarter (B*D*Sp bytes) holds that batch's 1-byte elements at row pitch Sp; after a batch with an image
  * table (rau_set_batch_images) it holds the table's N maps, not one map per sample. */
 int rau_batch_feats(rau_ctx* ctx, float** feats_dev);
 
@@ -208,11 +209,26 @@ int rau_batch_feats(rau_ctx* ctx, float** feats_dev);
  * fp16 or bf16 gives BIT-IDENTICAL results to the same batch given as f32 holding the widened values
  * (finite inputs; fp16 subnormals included).  The type belongs to the batch, not to the ctx: each slot
  * of the asynchronous path records the type of the batch it holds and rau_use_batch makes it current.
- * rau_set_batch / rau_set_batch_async are the RAU_FEAT_F32 case.  An unknown type is RAU_ERR_INVALID. */
+ * rau_set_batch / rau_set_batch_async are the RAU_FEAT_F32 case.  An unknown type is RAU_ERR_INVALID.
+ *
+ * fp8 maps: the two OCP 8-bit formats (NOT the MI300 "fnuz" forms), one byte per element, halve all of that
+ * once more.  e4m3fn: exponent bias 7, subnormals m * 2^-9, no infinities, S.1111.111 the only NaN, largest
+ * finite value 448.  e5m2: exponent bias 15, subnormals m * 2^-16, infinities and NaNs as in binary16 (a code
+ * is the upper byte of a binary16), largest finite value 57344.  Widening is exact for every code: subnormals
+ * become normal f32 numbers, +-0 keep their sign, e5m2 +-inf become +-inf, NaN codes become a NaN.  So the same
+ * contract holds: a batch given as fp8 gives BIT-IDENTICAL results to the same batch given as f32 holding the
+ * widened values (finite inputs), at every entry point that takes a feat_type, in both modes, in every context
+ * dtype, under rau_graph_step and at module level with X == NULL.
+ * What fp8 storage does to VQA accuracy is NOT measured and NOT claimed: the library's contract is exactness
+ * with respect to the stored values.  Choosing a format is the user's decision: e4m3 has 3 significand bits
+ * and range up to 448, e5m2 has 2 bits and range up to 57344.
+ * The value 3 is reserved: it is an unknown type (RAU_ERR_INVALID), like every value above 5. */
 typedef enum rau_feat_type {
   RAU_FEAT_F32 = 0,
   RAU_FEAT_F16 = 1,   /* IEEE binary16, passed as its bit patterns */
-  RAU_FEAT_BF16 = 2   /* bfloat16 bit patterns (the upper half of an f32) */
+  RAU_FEAT_BF16 = 2,  /* bfloat16 bit patterns (the upper half of an f32) */
+  RAU_FEAT_E4M3 = 4,  /* OCP e4m3fn bit patterns, one byte per element */
+  RAU_FEAT_E5M2 = 5   /* OCP e5m2 bit patterns (the upper byte of an IEEE binary16) */
 } rau_feat_type;
 /* rau_set_batch with feats [B,D,S] of elements of feat_type (feats NULL: the resident buffer already
  * holds the map, written through rau_batch_feats, in that type) */
@@ -267,7 +283,16 @@ int rau_batch_images(rau_ctx* ctx, int* n_images);
  *                     pinned staging; synchronising.  src_type equal to the bank's type is a copy;
  *                     RAU_FEAT_F32 into a 16-bit bank is narrowed ON THE DEVICE, round to nearest even: the
  *                     bits of numpy's float16 conversion (subnormals kept, overflow to infinity) and of
- *                     bf16 rounding for every finite input.  Any other pair of types is RAU_ERR_INVALID, as
+ *                     bf16 rounding for every finite input.  RAU_FEAT_F32 into an fp8 bank is narrowed on the
+ *                     device too, round to nearest even and SATURATING: every result beyond the largest finite
+ *                     value (448 / 57344) becomes that value with the input's sign, +-inf included (a clipped
+ *                     activation is usable; a NaN would poison a hop's softmax); NaN becomes a NaN code;
+ *                     magnitudes at or below half the smallest subnormal become +-0.  With mbits = 3 | 2, bias =
+ *                     7 | 15, emin = 1 - bias: a = |x|, e = max(floor(log2 a), emin), q = 2^(e - mbits),
+ *                     r = min(rint(a / q) * q, largest finite), rint to nearest even; r is encoded, as a
+ *                     subnormal when r < 2^emin, under the input's sign bit -- bit for bit what
+ *                     rau_vqa_amd.feat16.fp8_bits computes, not any vendor's conversion routine.
+ *                     Any other pair of types (f16 -> e4m3, e4m3 -> e5m2, ...) is RAU_ERR_INVALID, as
  *                     is a row range outside [0, capacity).  It first waits for all enqueued work that reads
  *                     the bank, so it may be called between steps to add or replace rows; a batch that was
  *                     handed over BEFORE the put and is consumed after it may see either version of a

@@ -1,5 +1,5 @@
 // bank.hip -- the two kernels of the device-resident feature bank (rau_bank_*, include/rau.h): the gather
-// of whole maps out of the bank into the batch buffers, and the f32 -> fp16 / bf16 narrowing of rau_bank_put.
+// of whole maps out of the bank into the batch buffers, and the f32 -> fp16 / bf16 / fp8 narrowing of rau_bank_put.
 // Both are byte movers bound by HBM; they live in a translation unit of their own so that the code object of
 // kernels.hip is the same with and without them.
 #include <hip/hip_runtime.h>
@@ -40,6 +40,8 @@ __global__ __launch_bounds__(256) void k_bank_gather(size_t nvec, const V* __res
   }
   for (; v < nvec; v += step) dst[v] = *(src + v);
 }
+// (map_bytes % 8: D % 4 == 0 and Sp % 4 == 0 make every map, fp8 included, a multiple of 16 bytes -- see
+// expand_features)
 hipError_t bank_gather(hipStream_t st, int n, size_t map_bytes, const void* bank, int32_t capacity,
                        const int32_t* rows, void* out) {
   if (n <= 0 || n > 65535 || capacity <= 0 || !bank || !rows || !out || map_bytes % 8 != 0)
@@ -81,11 +83,45 @@ __device__ __forceinline__ uint32_t narrow_f16_bits(uint32_t x) {
 __device__ __forceinline__ uint32_t narrow_bf16_bits(uint32_t x) {
   return (x + (((x >> 16) & 1u) + 0x7fffu)) >> 16;
 }
-// dense f32 rows [rows][SL] -> 16-bit rows at pitch Sp (a multiple of 4), pad columns zero; one thread forms
-// four neighbouring outputs and stores them as 8 bytes
+// f32 -> OCP fp8, round to nearest even and SATURATING, in integer arithmetic: MB mantissa bits, exponent bias
+// BIAS, MAXC the code of the largest finite value (e4m3fn: 3, 7, 0x7e = 448; e5m2: 2, 15, 0x7b = 57344).  Every
+// result beyond the largest finite value, +-inf included, is that value with the input's sign; NaN is the code
+// S.1111111 (a NaN in both formats); magnitudes at or below half the smallest subnormal are +-0.  The bits of
+// feat16.fp8_bits.
+template <int MB, int BIAS, uint32_t MAXC>
+__device__ __forceinline__ uint32_t narrow_fp8_bits(uint32_t x) {
+  const uint32_t sign = (x >> 24) & 0x80u, a = x & 0x7fffffffu;
+  if (a > 0x7f800000u) return sign | 0x7fu;
+  const uint32_t e = a >> 23;
+  uint32_t h;
+  if (e >= 128u - BIAS) {                                   // normal in the target: rebias 127 -> BIAS
+    const uint32_t r = a - ((127u - BIAS) << 23), sh = 23 - MB;
+    const uint32_t rem = r & ((1u << sh) - 1u), half = 1u << (sh - 1);
+    h = r >> sh;
+    h += (rem > half || (rem == half && (h & 1u))) ? 1u : 0u;   // a carry runs into the exponent
+    h = min(h, MAXC);
+  } else {                                                  // subnormal: units of 2^(1 - BIAS - MB)
+    const uint32_t sh = (151u - BIAS - MB) - e;             // >= 24 - MB
+    if (sh > 24u) return sign;                              // below half a unit (f32 subnormals and 0 too)
+    const uint32_t m = (a & 0x7fffffu) | 0x800000u;
+    const uint32_t rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1u);
+    h = m >> sh;
+    h += (rem > half || (rem == half && (h & 1u))) ? 1u : 0u;   // may round up to the smallest normal
+  }
+  return sign | h;
+}
+template <int FT>
+__device__ __forceinline__ uint32_t narrow1(uint32_t x) {
+  if (FT == RAU_FEAT_F16) return narrow_f16_bits(x) & 0xffffu;
+  if (FT == RAU_FEAT_E4M3) return narrow_fp8_bits<3, 7, 0x7eu>(x);
+  if (FT == RAU_FEAT_E5M2) return narrow_fp8_bits<2, 15, 0x7bu>(x);
+  return narrow_bf16_bits(x) & 0xffffu;
+}
+// dense f32 rows [rows][SL] -> 16-bit or fp8 rows at pitch Sp (a multiple of 4), pad columns zero; one thread
+// forms four neighbouring outputs and stores them as 8 bytes (fp8: as one 32-bit word)
 template <int FT>
 __global__ __launch_bounds__(256) void k_narrow_features(size_t nquad, int SL, int Sp,
-                                                         const float* __restrict__ src, uint2* __restrict__ out) {
+                                                         const float* __restrict__ src, void* __restrict__ out) {
   const int qpr = Sp / 4;   // quads per row
   for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < nquad; q += (size_t)gridDim.x * blockDim.x) {
     const size_t r = q / qpr;
@@ -95,22 +131,34 @@ __global__ __launch_bounds__(256) void k_narrow_features(size_t nquad, int SL, i
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const uint32_t x = s0 + k < SL ? __float_as_uint(p[k]) : 0u;
-      h[k] = (FT == RAU_FEAT_F16 ? narrow_f16_bits(x) : narrow_bf16_bits(x)) & 0xffffu;
+      h[k] = narrow1<FT>(x);
     }
-    out[q] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+    if (FT == RAU_FEAT_E4M3 || FT == RAU_FEAT_E5M2)
+      static_cast<uint32_t*>(out)[q] = h[0] | (h[1] << 8) | (h[2] << 16) | (h[3] << 24);
+    else
+      static_cast<uint2*>(out)[q] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
   }
 }
 hipError_t narrow_features(hipStream_t st, size_t rows, int SL, int Sp, const float* src, void* out, int ft) {
-  if ((ft != RAU_FEAT_F16 && ft != RAU_FEAT_BF16) || Sp % 4 != 0 || SL > Sp || SL <= 0 || !src || !out)
+  if (!feat_type_ok(ft) || ft == RAU_FEAT_F32 || Sp % 4 != 0 || SL > Sp || SL <= 0 || !src || !out)
     return hipErrorInvalidValue;
   if (rows == 0) return hipSuccess;
   const size_t nquad = rows * (Sp / 4);
-  if (ft == RAU_FEAT_F16)
-    hipLaunchKernelGGL(k_narrow_features<RAU_FEAT_F16>, dim3(grid_for(nquad)), dim3(256), 0, st, nquad, SL, Sp, src,
-                       static_cast<uint2*>(out));
-  else
-    hipLaunchKernelGGL(k_narrow_features<RAU_FEAT_BF16>, dim3(grid_for(nquad)), dim3(256), 0, st, nquad, SL, Sp, src,
-                       static_cast<uint2*>(out));
+  const dim3 grid(grid_for(nquad));
+  switch (ft) {
+    case RAU_FEAT_F16:
+      hipLaunchKernelGGL(k_narrow_features<RAU_FEAT_F16>, grid, dim3(256), 0, st, nquad, SL, Sp, src, out);
+      break;
+    case RAU_FEAT_BF16:
+      hipLaunchKernelGGL(k_narrow_features<RAU_FEAT_BF16>, grid, dim3(256), 0, st, nquad, SL, Sp, src, out);
+      break;
+    case RAU_FEAT_E4M3:
+      hipLaunchKernelGGL(k_narrow_features<RAU_FEAT_E4M3>, grid, dim3(256), 0, st, nquad, SL, Sp, src, out);
+      break;
+    default:
+      hipLaunchKernelGGL(k_narrow_features<RAU_FEAT_E5M2>, grid, dim3(256), 0, st, nquad, SL, Sp, src, out);
+      break;
+  }
   return hipGetLastError();
 }
 

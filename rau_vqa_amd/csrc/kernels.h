@@ -310,10 +310,20 @@ hipError_t att_bwd_split(hipStream_t st, int nB, int M, int A, int S, const floa
                          const float* u, float* part, int da_ns = 0, int SL = 0,
                          const float* da_add = nullptr);
 // The feature-map passes below read the resident batch in its own element type ft (rau_feat_type:
-// RAU_FEAT_F32, or 16-bit RAU_FEAT_F16 / RAU_FEAT_BF16 bit patterns laid out like the f32 form), widen
-// each element exactly to f32 and then do the f32 form's arithmetic: results are bit-identical to an
-// f32 batch holding the widened values.  An unknown ft is hipErrorInvalidValue, nothing launched.
-inline bool feat_type_ok(int ft) { return ft == RAU_FEAT_F32 || ft == RAU_FEAT_F16 || ft == RAU_FEAT_BF16; }
+// RAU_FEAT_F32, 16-bit RAU_FEAT_F16 / RAU_FEAT_BF16 or 8-bit RAU_FEAT_E4M3 / RAU_FEAT_E5M2 bit patterns laid
+// out like the f32 form), widen each element exactly to f32 and then do the f32 form's arithmetic: results
+// are bit-identical to an f32 batch holding the widened values.  An unknown ft (3 is reserved) is
+// hipErrorInvalidValue, nothing launched.
+inline bool feat_type_ok(int ft) {
+  return ft == RAU_FEAT_F32 || ft == RAU_FEAT_F16 || ft == RAU_FEAT_BF16 || ft == RAU_FEAT_E4M3 ||
+         ft == RAU_FEAT_E5M2;
+}
+// bytes of one element of a map of type ft (feat_type_ok(ft))
+inline size_t feat_elem_bytes(int ft) {
+  return ft == RAU_FEAT_F32 ? 4 : (ft == RAU_FEAT_E4M3 || ft == RAU_FEAT_E5M2) ? 1 : 2;
+}
+// the accepted types, as the error messages of the entry points list them
+#define RAU_FEAT_TYPE_LIST "RAU_FEAT_F32 | _F16 | _BF16 | _E4M3 | _E5M2"
 // xd[h][i] = X[i] * keep(h, i) * scale for h < H, i < per_hop (feature-map dropout, SS:239)
 // SL != Sp: rows of SL logical positions at pitch Sp (mask indexed logically, pad columns zeroed)
 hipError_t dropout_features(hipStream_t st, int H, size_t per_hop, const void* X,
@@ -328,11 +338,12 @@ hipError_t dropout_features_gen(hipStream_t st, uint64_t seed, uint32_t site, ui
 // conv_embed_wgrad_b16 read
 hipError_t dropout_features_b16(hipStream_t st, int H, size_t per_hop, const void* X,
                                 const uint32_t* mask, float mscale, void* xd16, int ft = RAU_FEAT_F32);
-// out[r][s] = widen(X[r][s]) for s < SL, 0 for SL <= s < Sp: the f32 image of a 16-bit feature map
-// (ft = RAU_FEAT_F16 / RAU_FEAT_BF16) at row pitch Sp, for the readers that take the unmasked batch
+// out[r][s] = widen(X[r][s]) for s < SL, 0 for SL <= s < Sp: the f32 image of a 16-bit or fp8 feature map
+// (any ft but RAU_FEAT_F32) at row pitch Sp, for the readers that take the unmasked batch
 hipError_t widen_features(hipStream_t st, size_t rows, int SL, int Sp, const void* X, float* out, int ft);
 // Image table -> per-sample maps: out[b] = table[image_of[b]] for b < nB, maps of map_bytes bytes each
-// ([D][Sp] elements of any feature type, copied as they are in 16-byte vectors; map_bytes % 8 == 0).
+// ([D][Sp] elements of any feature type, copied as they are in 16-byte vectors; map_bytes % 8 == 0, which
+// holds for every map a context can have: D % 4 == 0 and Sp % 4 == 0 make even an fp8 map a multiple of 16).
 // image_of is a DEVICE index whose entries the host has range-checked against the table.
 hipError_t expand_features(hipStream_t st, int nB, size_t map_bytes, const void* table, const int32_t* image_of,
                            void* out);
@@ -341,9 +352,10 @@ hipError_t expand_features(hipStream_t st, int nB, size_t map_bytes, const void*
 // kernel clamps it into [0, capacity) all the same.
 hipError_t bank_gather(hipStream_t st, int n, size_t map_bytes, const void* bank, int32_t capacity,
                        const int32_t* rows, void* out);
-// out[r][s] = narrow(src[r][s]) for s < SL, 0 for SL <= s < Sp: dense f32 rows into 16-bit rows (ft =
-// RAU_FEAT_F16 / RAU_FEAT_BF16) at pitch Sp (% 4 == 0), round to nearest even -- the bits of numpy's float16
-// conversion (subnormals, overflow to infinity) and of feat16.bf16_bits
+// out[r][s] = narrow(src[r][s]) for s < SL, 0 for SL <= s < Sp: dense f32 rows into 16-bit or fp8 rows (any ft
+// but RAU_FEAT_F32) at pitch Sp (% 4 == 0), round to nearest even -- the bits of numpy's float16 conversion
+// (subnormals, overflow to infinity), of feat16.bf16_bits, and of feat16.fp8_bits (SATURATING: everything
+// beyond the largest finite value, infinities included, becomes the largest finite value)
 hipError_t narrow_features(hipStream_t st, size_t rows, int SL, int Sp, const float* src, void* out, int ft);
 // dst[n] += sum_rows X[row*ld + n]   (two-stage, deterministic; tmp >= 32*N floats)
 hipError_t colsum_acc(hipStream_t st, int rows, int N, const float* X, long ld, float* dst,

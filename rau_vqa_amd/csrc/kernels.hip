@@ -1404,9 +1404,9 @@ hipError_t transpose2d(hipStream_t st, int rows, int cols, const float* in, floa
   return hipGetLastError();
 }
 
-// ---- element type of the resident feature map (rau_feat_type): f32, IEEE fp16 or bf16.  Widening a
-// 16-bit value to f32 is exact, so every pass below does exactly the f32 arithmetic of the f32 form on
-// the widened value.  fp16 is widened by integer operations: subnormal halves are normal f32 numbers
+// ---- element type of the resident feature map (rau_feat_type): f32, IEEE fp16, bf16, or OCP fp8 (e4m3fn,
+// e5m2).  Widening a narrow value to f32 is exact, so every pass below does exactly the f32 arithmetic of the
+// f32 form on the widened value.  fp16 is widened by integer operations: subnormal halves are normal f32 numbers
 // and come out unchanged under any denorm mode (no f16 / f32 denormal ever enters a float op).
 __device__ __forceinline__ float widen_f16(uint32_t h) {
   const uint32_t sign = (h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
@@ -1416,20 +1416,43 @@ __device__ __forceinline__ float widen_f16(uint32_t h) {
   }
   return __uint_as_float(sign | (e == 31 ? 0x7f800000u : (e + 112u) << 23) | (m << 13));
 }
+// OCP e4m3fn (bias 7, no infinities, S.1111.111 the only NaN), the same way: a subnormal is m * 2^-9, an exact
+// product of two normal f32 numbers.  (The hardware converts v_cvt_pk_f32_fp8 / _bf8 are not used: this form is
+// the contract, and it costs nothing beside the pass's memory time.)
+__device__ __forceinline__ float widen_e4m3(uint32_t c) {
+  const uint32_t sign = (c & 0x80u) << 24, e = (c >> 3) & 0xfu, m = c & 7u;
+  if (e == 0) {
+    const float v = (float)m * 0x1p-9f;
+    return __uint_as_float(__float_as_uint(v) | sign);
+  }
+  if ((c & 0x7fu) == 0x7fu) return __uint_as_float(sign | 0x7fc00000u);
+  return __uint_as_float(sign | ((e + 120u) << 23) | (m << 20));
+}
+// one element's bit pattern (16 or 8 bits, in the low end of h) -> f32.  e5m2 is the upper byte of a binary16.
 template <int FT>
 __device__ __forceinline__ float widen1(uint32_t h) {
-  return FT == RAU_FEAT_F16 ? widen_f16(h) : __uint_as_float(h << 16);
+  if (FT == RAU_FEAT_F16) return widen_f16(h);
+  if (FT == RAU_FEAT_E4M3) return widen_e4m3(h);
+  if (FT == RAU_FEAT_E5M2) return widen_f16(h << 8);
+  return __uint_as_float(h << 16);
 }
-// element i of X (f32, or 16-bit bit patterns)
+// element i of X (f32, or 16-bit / 8-bit bit patterns)
 template <int FT>
 __device__ __forceinline__ float load_feat(const void* __restrict__ X, size_t i) {
   if (FT == RAU_FEAT_F32) return reinterpret_cast<const float*>(X)[i];
+  if (FT == RAU_FEAT_E4M3 || FT == RAU_FEAT_E5M2) return widen1<FT>(reinterpret_cast<const uint8_t*>(X)[i]);
   return widen1<FT>(reinterpret_cast<const uint16_t*>(X)[i]);
 }
-// quad q of X (elements 4q .. 4q+3): one 16-byte load for f32, one 8-byte load for 16-bit data
+// quad q of X (elements 4q .. 4q+3): one 16-byte load for f32, one 8-byte load for 16-bit data, one 4-byte
+// load for fp8 (rows are at pitch Sp % 4 == 0 and buffers are 256-byte aligned, so each is aligned to its size)
 template <int FT>
 __device__ __forceinline__ float4 load_feat4(const void* __restrict__ X, size_t q) {
   if (FT == RAU_FEAT_F32) return reinterpret_cast<const float4*>(X)[q];
+  if (FT == RAU_FEAT_E4M3 || FT == RAU_FEAT_E5M2) {
+    const uint32_t v = reinterpret_cast<const uint32_t*>(X)[q];
+    return make_float4(widen1<FT>(v & 0xffu), widen1<FT>((v >> 8) & 0xffu), widen1<FT>((v >> 16) & 0xffu),
+                       widen1<FT>(v >> 24));
+  }
   const uint2 v = reinterpret_cast<const uint2*>(X)[q];
   return make_float4(widen1<FT>(v.x & 0xffffu), widen1<FT>(v.x >> 16), widen1<FT>(v.y & 0xffffu),
                      widen1<FT>(v.y >> 16));
@@ -1496,7 +1519,10 @@ __global__ void k_dropout_features_gen(uint64_t seed, uint32_t site, uint32_t st
   // load / store instruction of the wave covers one contiguous KB (the owner's bits come by shuffle).
   // With each lane storing its own block's four quads the lanes of an instruction are 64 bytes apart
   // and every 128-byte line is written in four pieces (262 us at D = 512 against 190 us for a plain
-  // copy of the same bytes).  16-bit input: a quad is 8 bytes, a load instruction one contiguous 512 B.
+  // copy of the same bytes).  16-bit input: a quad is 8 bytes, a load instruction one contiguous 512 B; fp8
+  // input: a quad is 4 bytes, a load instruction one contiguous 256 B (two whole lines); those loads are 1/13 of
+  // the pass's bytes at H = 3 with f32 output and less with more hops, so the arrangement stays as the stores
+  // want it (timings per input type: LOG.md, fp8 feature maps).
   const int l = threadIdx.x & 63, quad = l & 3, sub = l >> 2;
   for (size_t base = (blockIdx.x * (size_t)blockDim.x + (threadIdx.x & ~63u)); base < per16;
        base += (size_t)gridDim.x * blockDim.x) {
@@ -1537,15 +1563,17 @@ template <bool B16>
 static void launch_dropout_gen(hipStream_t st, int ft, dim3 grid, uint64_t seed, uint32_t site,
                                uint32_t step, uint32_t thr, const uint64_t* key, int H, size_t per16,
                                const void* X, float mscale, void* xd) {
-  if (ft == RAU_FEAT_F16)
-    hipLaunchKernelGGL((k_dropout_features_gen<B16, RAU_FEAT_F16>), grid, dim3(256), 0, st, seed, site, step,
-                       thr, key, H, per16, X, mscale, xd);
-  else if (ft == RAU_FEAT_BF16)
-    hipLaunchKernelGGL((k_dropout_features_gen<B16, RAU_FEAT_BF16>), grid, dim3(256), 0, st, seed, site, step,
-                       thr, key, H, per16, X, mscale, xd);
-  else
-    hipLaunchKernelGGL((k_dropout_features_gen<B16, RAU_FEAT_F32>), grid, dim3(256), 0, st, seed, site, step,
-                       thr, key, H, per16, X, mscale, xd);
+#define GEN_FT(FT)                                                                                        \
+  hipLaunchKernelGGL((k_dropout_features_gen<B16, FT>), grid, dim3(256), 0, st, seed, site, step, thr, key, H, \
+                     per16, X, mscale, xd)
+  switch (ft) {
+    case RAU_FEAT_F16: GEN_FT(RAU_FEAT_F16); break;
+    case RAU_FEAT_BF16: GEN_FT(RAU_FEAT_BF16); break;
+    case RAU_FEAT_E4M3: GEN_FT(RAU_FEAT_E4M3); break;
+    case RAU_FEAT_E5M2: GEN_FT(RAU_FEAT_E5M2); break;
+    default: GEN_FT(RAU_FEAT_F32); break;
+  }
+#undef GEN_FT
 }
 hipError_t dropout_features_gen(hipStream_t st, uint64_t seed, uint32_t site, uint32_t step, float p,
                                 const uint64_t* key_dev, int H, size_t per_hop, const void* X,
@@ -1588,6 +1616,10 @@ __global__ void k_dropout_features_pitch(int H, size_t rows, int SL, int Sp,
       hipLaunchKernelGGL(kern<RAU_FEAT_F16>, grid, dim3(256), 0, st, __VA_ARGS__);            \
     else if ((ft) == RAU_FEAT_BF16)                                                           \
       hipLaunchKernelGGL(kern<RAU_FEAT_BF16>, grid, dim3(256), 0, st, __VA_ARGS__);           \
+    else if ((ft) == RAU_FEAT_E4M3)                                                           \
+      hipLaunchKernelGGL(kern<RAU_FEAT_E4M3>, grid, dim3(256), 0, st, __VA_ARGS__);           \
+    else if ((ft) == RAU_FEAT_E5M2)                                                           \
+      hipLaunchKernelGGL(kern<RAU_FEAT_E5M2>, grid, dim3(256), 0, st, __VA_ARGS__);           \
     else                                                                                      \
       hipLaunchKernelGGL(kern<RAU_FEAT_F32>, grid, dim3(256), 0, st, __VA_ARGS__);            \
   } while (0)
@@ -1613,9 +1645,9 @@ hipError_t dropout_features_b16(hipStream_t st, int H, size_t per_hop, const voi
   return hipGetLastError();
 }
 
-// 16-bit feature map -> its f32 image, [rows][Sp] with pad columns written as zeros (the form every
-// f32 reader of the resident batch expects).  Dense rows (SL == Sp): one 8-byte load and one 16-byte
-// store per quad.
+// 16-bit or fp8 feature map -> its f32 image, [rows][Sp] with pad columns written as zeros (the form every
+// f32 reader of the resident batch expects).  Dense rows (SL == Sp): one 8-byte (fp8: 4-byte) load and one
+// 16-byte store per quad.
 template <int FT>
 __global__ void k_widen_features(size_t per4, const void* __restrict__ X, float4* __restrict__ out) {
   for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < per4;
@@ -1634,7 +1666,7 @@ __global__ void k_widen_features_pitch(size_t rows, int SL, int Sp, const void* 
   }
 }
 hipError_t widen_features(hipStream_t st, size_t rows, int SL, int Sp, const void* X, float* out, int ft) {
-  if (ft != RAU_FEAT_F16 && ft != RAU_FEAT_BF16) return hipErrorInvalidValue;
+  if (!feat_type_ok(ft) || ft == RAU_FEAT_F32) return hipErrorInvalidValue;
   if (SL != Sp) {
     LAUNCH_FT(k_widen_features_pitch, ft, dim3(grid_for(rows * Sp)), rows, SL, Sp, X, out);
     return hipGetLastError();
@@ -1664,7 +1696,10 @@ __global__ __launch_bounds__(256) void k_expand_features(size_t nvec, const V* _
 hipError_t expand_features(hipStream_t st, int nB, size_t map_bytes, const void* table, const int32_t* image_of,
                            void* out) {
   if (nB <= 0 || !table || !image_of || !out || map_bytes % 8 != 0) return hipErrorInvalidValue;
-  // f32 maps (Sp % 4 == 0) and 16-bit maps of an even number of rows are whole 16-byte vectors
+  // f32 maps (Sp % 4 == 0) and 16-bit maps of an even number of rows are whole 16-byte vectors.  rau_create
+  // accepts only D % 4 == 0, so a map of any element size, fp8 included (D * Sp bytes), is a multiple of 16
+  // bytes and the check above never refuses one; maps start at multiples of their size in 256-byte-aligned
+  // allocations, so every vector access is aligned to its size.
   const bool v16 = map_bytes % 16 == 0;
   const size_t nvec = map_bytes / (v16 ? 16 : 8);
   const int slices = (int)std::min<size_t>(16, (nvec + 1023) / 1024);   // >= 4 vectors per thread and slice

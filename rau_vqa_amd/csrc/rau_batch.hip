@@ -179,11 +179,12 @@ int ensure_async(rau_ctx* ctx) {
 int enqueue_batch(rau_ctx* ctx, hipStream_t st, int si, const Batch& b) {
   const rau_config& c = ctx->cfg;
   const BatchSlot& d = ctx->slot[si];
-  const size_t TB = (size_t)c.T * c.B, es = b.feat_type == RAU_FEAT_F32 ? 4 : 2;
+  const size_t TB = (size_t)c.T * c.B, es = feat_elem_bytes(b.feat_type);
   const size_t maps = b.n_images > 0 ? (size_t)b.n_images : (size_t)c.B;   // only these cross the bus
   ++ctx->slot_serial[si];
   if (b.n_images > 0) HIPC(hipMemcpyAsync(d.image_of_d, b.image_of, (size_t)c.B * 4, hipMemcpyHostToDevice, st));
-  // pitched rows of another element size leave data in this type's pad columns: zero them first
+  // pitched rows of another element size (4, 2 or 1 bytes) leave data in this type's pad columns: zero the
+  // whole buffer first, on any change of type
   if ((b.feats || b.bank_idx) && ctx->Sp != c.S && b.feat_type != d.held.feat_type)
     HIPC(hipMemsetAsync(d.feats, 0, (size_t)c.B * c.D * ctx->Sp * sizeof(float), st));
   // bank batch (feats == nullptr): only the two row indices cross the bus; the table is gathered inside device
@@ -279,7 +280,7 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
     s.upload_pending = false;
   }
   // NULL = the caller has filled the slot's pinned staging in place (rau_batch_slot)
-  if (b.feats && b.feats != s.feats_h) std::memcpy(s.feats_h, b.feats, nf * (b.feat_type == RAU_FEAT_F32 ? 4 : 2));
+  if (b.feats && b.feats != s.feats_h) std::memcpy(s.feats_h, b.feats, nf * feat_elem_bytes(b.feat_type));
   if (b.tokens && b.tokens != s.tokens_h) std::memcpy(s.tokens_h, b.tokens, TB * 4);
   if (b.lens && b.lens != s.lens_p) std::memcpy(s.lens_p, b.lens, (size_t)c.B * 4);
   if (b.labels && b.labels != s.labels_h) std::memcpy(s.labels_h, b.labels, (size_t)c.B * 4);
@@ -320,7 +321,7 @@ int bank_quiesce(rau_ctx* ctx) {
   return RAU_OK;
 }
 size_t bank_map_bytes(const rau_ctx* ctx) {
-  return (size_t)ctx->cfg.D * ctx->Sp * (ctx->bank_type == RAU_FEAT_F32 ? 4 : 2);
+  return (size_t)ctx->cfg.D * ctx->Sp * feat_elem_bytes(ctx->bank_type);
 }
 }  // namespace
 
@@ -335,7 +336,7 @@ int batch_maps(rau_ctx* ctx, const float** maps) {
   if (!ctx->capturing && ctx->x_valid && ctx->x_slot == ctx->cur_slot &&
       ctx->x_serial == ctx->slot_serial[ctx->cur_slot])
     return RAU_OK;
-  const size_t map_bytes = (size_t)c.D * ctx->Sp * (bs.held.feat_type == RAU_FEAT_F32 ? 4 : 2);
+  const size_t map_bytes = (size_t)c.D * ctx->Sp * feat_elem_bytes(bs.held.feat_type);
   hipStream_t st = ctx->st;
   if (bs.held.bank)   // one pass with the composed index rows[image_of[b]] (the second half of the slot's bank index)
     RUN("bank_gather", 0, 2.0 * c.B * map_bytes,
@@ -366,7 +367,7 @@ int rau_set_batch_typed(rau_ctx* ctx, const void* feats, int feat_type, const in
 int rau_set_batch_images(rau_ctx* ctx, const void* feats, int feat_type, int n_images, const int32_t* image_of,
                          const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
   NEED(ctx && tokens && lens, "null argument");
-  NEED(feat_type_ok(feat_type), "rau_set_batch: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)", feat_type);
+  NEED(feat_type_ok(feat_type), "rau_set_batch: feat_type %d (" RAU_FEAT_TYPE_LIST ")", feat_type);
   return set_batch_sync(ctx, Batch{feats, feat_type, n_images, image_of, tokens, lens, labels, nullptr});
 }
 
@@ -410,8 +411,7 @@ int rau_set_batch_async_images(rau_ctx* ctx, int slot, const void* feats, int fe
                                const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
                                const int32_t* labels, int has_labels) {
   NEED(ctx, "null ctx");
-  NEED(feat_type_ok(feat_type), "rau_set_batch_async: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)",
-       feat_type);
+  NEED(feat_type_ok(feat_type), "rau_set_batch_async: feat_type %d (" RAU_FEAT_TYPE_LIST ")", feat_type);
   return set_batch_slot(ctx, slot, Batch{feats, feat_type, n_images, image_of, tokens, lens, labels, nullptr},
                         has_labels);
 }
@@ -467,10 +467,10 @@ int rau_batch_images(rau_ctx* ctx, int* n_images) {
 // ------------------------------------------------------------------ feature bank
 int rau_bank_create(rau_ctx* ctx, int32_t capacity, int feat_type) {
   NEED(ctx, "null ctx");
-  NEED(feat_type_ok(feat_type), "rau_bank_create: feat_type %d (RAU_FEAT_F32 | _F16 | _BF16)", feat_type);
+  NEED(feat_type_ok(feat_type), "rau_bank_create: feat_type %d (" RAU_FEAT_TYPE_LIST ")", feat_type);
   NEED(capacity >= 1, "rau_bank_create: capacity %d", capacity);
   if (ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_create: the context already has a bank (rau_bank_destroy first)");
-  const size_t bytes = (size_t)capacity * ctx->cfg.D * ctx->Sp * (feat_type == RAU_FEAT_F32 ? 4 : 2);
+  const size_t bytes = (size_t)capacity * ctx->cfg.D * ctx->Sp * feat_elem_bytes(feat_type);
   void* d = nullptr;
   hipError_t e = hipMalloc(&d, bytes);
   if (e != hipSuccess) {
@@ -498,7 +498,7 @@ int rau_bank_destroy(rau_ctx* ctx) {
   if (int rc = bank_quiesce(ctx)) return rc;
   // captured steps of bank batches hold the bank's address
   for (auto it = ctx->graphs.begin(); it != ctx->graphs.end();)
-    if ((it->first >> 35) & 1) { hipGraphExecDestroy(it->second); it = ctx->graphs.erase(it); } else ++it;
+    if ((it->first >> 36) & 1) { hipGraphExecDestroy(it->second); it = ctx->graphs.erase(it); } else ++it;
   for (BatchSlot& s : ctx->slot) {   // a batch drawn from the bank is gone with it
     if (!s.held.bank) continue;
     const int ft = s.held.feat_type;   // (its maps are not: enqueue_batch's pad-column rule reads their type)
@@ -535,16 +535,16 @@ int rau_bank_info(rau_ctx* ctx, int32_t* capacity, int* feat_type, int32_t* rows
 int rau_bank_put(rau_ctx* ctx, int32_t first, int32_t count, const void* feats, int src_type) {
   NEED(ctx && feats, "null argument");
   if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_put: the context has no feature bank (rau_bank_create)");
-  NEED(feat_type_ok(src_type), "rau_bank_put: src_type %d (RAU_FEAT_F32 | _F16 | _BF16)", src_type);
+  NEED(feat_type_ok(src_type), "rau_bank_put: src_type %d (" RAU_FEAT_TYPE_LIST ")", src_type);
   NEED(src_type == ctx->bank_type || src_type == RAU_FEAT_F32,
-       "rau_bank_put: maps of type %d into a bank of type %d (equal types, or f32 into a 16-bit bank)", src_type,
+       "rau_bank_put: maps of type %d into a bank of type %d (equal types, or f32 into a 16-bit or fp8 bank)", src_type,
        ctx->bank_type);
   NEED(first >= 0 && count >= 1 && (int64_t)first + count <= ctx->bank_cap, "rau_bank_put: rows [%d,%d) out of [0,%d)",
        first, first + count, ctx->bank_cap);
   const rau_config& c = ctx->cfg;
   const bool narrow = src_type != ctx->bank_type;
-  const size_t ses = src_type == RAU_FEAT_F32 ? 4 : 2, src_map = (size_t)c.D * c.S * ses, map_bytes = bank_map_bytes(ctx);
-  const size_t bes = ctx->bank_type == RAU_FEAT_F32 ? 4 : 2;
+  const size_t ses = feat_elem_bytes(src_type), src_map = (size_t)c.D * c.S * ses, map_bytes = bank_map_bytes(ctx);
+  const size_t bes = feat_elem_bytes(ctx->bank_type);
   if (!ctx->bank_chunk) {   // staging sized for f32 sources: 32 MiB, at least one map
     const size_t chunk = std::max<size_t>((size_t)32 << 20, (size_t)c.D * c.S * 4);
     for (int k = 0; k < 2; ++k) {
@@ -604,7 +604,7 @@ int rau_bank_get(rau_ctx* ctx, int32_t first, int32_t count, void* feats) {
   NEED(first >= 0 && count >= 1 && (int64_t)first + count <= ctx->bank_cap, "rau_bank_get: rows [%d,%d) out of [0,%d)",
        first, first + count, ctx->bank_cap);
   const rau_config& c = ctx->cfg;
-  const size_t bes = ctx->bank_type == RAU_FEAT_F32 ? 4 : 2, map_bytes = bank_map_bytes(ctx);
+  const size_t bes = feat_elem_bytes(ctx->bank_type), map_bytes = bank_map_bytes(ctx);
   const char* src = static_cast<const char*>(ctx->bank) + (size_t)first * map_bytes;
   HIPC(hipStreamSynchronize(ctx->st));
   if (ctx->Sp == c.S)

@@ -1326,7 +1326,7 @@ int rau_forward(rau_ctx* ctx) {
   const float* feats = bs.feats;
   if (table_fwd && bs.held.bank && !bs.held.table_ok) {
     // a bank batch handed over in train mode carries its row index only: the table is gathered now
-    const size_t map_bytes = (size_t)D * S * (bs.held.feat_type == RAU_FEAT_F32 ? 4 : 2);
+    const size_t map_bytes = (size_t)D * S * feat_elem_bytes(bs.held.feat_type);
     RUN("bank_gather", 0, 2.0 * nX * map_bytes,
         bank_gather(st, nX, map_bytes, ctx->bank, ctx->bank_cap, bs.bank_idx_d, bs.feats));
     bs.held.table_ok = true;
@@ -1353,9 +1353,9 @@ int rau_forward(rau_ctx* ctx) {
       if (int rc = gen_masks(ctx, -1, RAU_MASK_X, sb)) return rc;
     RUNS(sb, "transpose", 0, (double)M * D * 8, transpose2d(sb, M, D, ctx->i_embed.W, ctx->WiT, ctx->WiT16));
     RUNS(sb, "transpose", 0, (double)A * M * 8, transpose2d(sb, A, M, ctx->att_i.W, ctx->WpT, ctx->WpT16));
-    // the batch's element type: 16-bit maps are widened (exactly) by the pass that reads them
+    // the batch's element type: 16-bit and fp8 maps are widened (exactly) by the pass that reads them
     const int ft = bs.held.feat_type;
-    const double xb = ft == RAU_FEAT_F32 ? 4 : 2;   // bytes per element read from the batch
+    const double xb = (double)feat_elem_bytes(ft);   // bytes per element read from the batch
     if (x_gen)
       RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * (x16 ? 2 : 4),
            dropout_features_gen(sb, ctx->seed, RAU_MASK_X, ctx->step, ctx->mp[RAU_MASK_X], ctx->dkey, H,
@@ -1886,10 +1886,10 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
                  ((uint64_t)(zero_grads_first != 0) << 22);
   for (int i = 0; i < 5; ++i) key |= (uint64_t)ctx->mexplicit[i] << (24 + i);
   key |= (uint64_t)ctx->cur_slot << 30;   // the captured kernels hold the batch slot's device pointers
-  key |= (uint64_t)bs.held.feat_type << 32;  // ... and read the batch in its element type
-  key |= (uint64_t)(bs.held.n_images > 0) << 34;   // ... through the gather of an image table (any table, any N)
-  key |= (uint64_t)bs.held.bank << 35;   // ... of a bank batch: out of the bank
-  key |= (uint64_t)ctx->cfg.B << 36;      // every launch is shaped by the batch size (rau_set_batch_size)
+  key |= (uint64_t)bs.held.feat_type << 32;  // ... and read the batch in its element type (three bits: 0..5)
+  key |= (uint64_t)(bs.held.n_images > 0) << 35;   // ... through the gather of an image table (any table, any N)
+  key |= (uint64_t)bs.held.bank << 36;   // ... of a bank batch: out of the bank (rau_bank_destroy reads this bit)
+  key |= (uint64_t)ctx->cfg.B << 37;      // every launch is shaped by the batch size (rau_set_batch_size)
   if (int rc = upload_hop_weights(ctx, hop_w)) return rc;
   ctx->mg_valid = false;
   hipGraphExec_t exec = nullptr;

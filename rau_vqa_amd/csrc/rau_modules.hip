@@ -77,7 +77,7 @@ int lin_wgrad(rau_ctx* ctx, Lin& l, const float* dY, const float* X, long ldx, b
                   bias ? l.db : nullptr, ctx->bf16 == 1));
   return 0;
 }
-// X = NULL ("the resident batch"): its f32 form at pitch Sp -- the buffer itself, or for a 16-bit batch
+// X = NULL ("the resident batch"): its f32 form at pitch Sp -- the buffer itself, or for a 16-bit or fp8 batch
 // its exact widening into ctx-owned scratch (allocated on first use), so that the f32 kernels run on it
 int resident_feats(rau_ctx* ctx, const float** X) {
   if (int rc = batch_maps(ctx, X)) return rc;   // a batch with an image table: its per-sample expansion
@@ -86,7 +86,7 @@ int resident_feats(rau_ctx* ctx, const float** X) {
   const rau_config& c = ctx->cfg;
   if (!ctx->m_Xw)
     if (int rc = dalloc(ctx, &ctx->m_Xw, (size_t)ctx->cap * c.D * ctx->Sp)) return rc;
-  RUN("widen_features", 0, (double)c.B * c.D * ctx->Sp * 6,
+  RUN("widen_features", 0, (double)c.B * c.D * ctx->Sp * (4 + feat_elem_bytes(cur_batch(ctx).held.feat_type)),
       widen_features(ctx->st, (size_t)c.B * c.D, c.S, ctx->Sp, src, ctx->m_Xw, cur_batch(ctx).held.feat_type));
   *X = ctx->m_Xw;
   return 0;

@@ -4,19 +4,31 @@ A batch may be handed over as f32, IEEE fp16 or bf16.  numpy has fp16 (``np.floa
 so bf16 maps travel as ``uint16`` bit patterns and must be named explicitly: a ``uint16`` array
 without ``feat_type="bf16"`` is an error, never a guess.  Widening either 16-bit form to f32 is exact,
 and the library's results for a 16-bit batch are bit-identical to those for the widened f32 batch.
+
+The two OCP fp8 formats, ``e4m3`` (e4m3fn: bias 7, no infinities, S.1111.111 the NaN, largest finite 448)
+and ``e5m2`` (bias 15, infinities and NaNs as in binary16, largest finite 57344), follow the same rules:
+they travel as ``uint8`` bit patterns and must be named explicitly -- a ``uint8`` array without
+``feat_type`` is an error, never a guess -- every code widens to f32 exactly, and results are
+bit-identical to those for the widened f32 batch.  ``fp8_bits`` is the narrowing contract (round to
+nearest even, saturating at the largest finite value), the one the device follows in ``bank_put``.
+What fp8 storage does to VQA accuracy is not measured and not claimed: the contract is exactness with
+respect to the stored values, and choosing a format is the user's decision (e4m3 has 3 significand bits
+and range up to 448, e5m2 has 2 bits and range up to 57344).
 Nothing here touches a device.
 """
 from __future__ import annotations
 
 import numpy as np
 
-FEAT_TYPES = {"f32": 0, "f16": 1, "bf16": 2}          # name -> rau_feat_type
+FEAT_TYPES = {"f32": 0, "f16": 1, "bf16": 2, "e4m3": 4, "e5m2": 5}   # name -> rau_feat_type (3 is reserved)
 FEAT_NAMES = {v: k for k, v in FEAT_TYPES.items()}
-_DTYPES = {"f32": np.float32, "f16": np.float16, "bf16": np.uint16}
+_DTYPES = {"f32": np.float32, "f16": np.float16, "bf16": np.uint16, "e4m3": np.uint8, "e5m2": np.uint8}
+# fp8 formats: (mantissa bits, exponent bias, largest finite value)
+_FP8 = {"e4m3": (3, 7, 448.0), "e5m2": (2, 15, 57344.0)}
 
 
 def dtype_of(feat_type: str):
-    """numpy dtype of a map of `feat_type` (bf16: its uint16 bit patterns)."""
+    """numpy dtype of a map of `feat_type` (bf16: its uint16 bit patterns; fp8: its uint8 bit patterns)."""
     check_name(feat_type)
     return np.dtype(_DTYPES[feat_type])
 
@@ -29,10 +41,14 @@ def check_name(feat_type: str) -> str:
 
 def infer(feats, feat_type=None) -> str:
     """The feature type a batch array stands for: `feat_type` if given, else from its dtype
-    (float16 -> "f16", other numbers -> "f32"; uint16 is ambiguous and rejected)."""
+    (float16 -> "f16", other numbers -> "f32"; uint16 and uint8 are ambiguous and rejected)."""
     dt = np.asarray(feats).dtype
     if feat_type is not None:
         check_name(feat_type)
+        if feat_type in _FP8 and dt != np.uint8:
+            raise ValueError(f"feat_type {feat_type!r} takes uint8 bit patterns, not {dt} (see fp8_bits)")
+        if feat_type not in _FP8 and dt == np.uint8:
+            raise ValueError(f"uint8 arrays are fp8 bit patterns (feat_type 'e4m3' | 'e5m2'), not {feat_type!r}")
         if feat_type == "bf16" and dt != np.uint16:
             raise ValueError(f"feat_type 'bf16' takes uint16 bit patterns, not {dt}")
         if feat_type == "f16" and dt == np.uint16:
@@ -40,12 +56,14 @@ def infer(feats, feat_type=None) -> str:
         return feat_type
     if dt == np.uint16:
         raise ValueError("uint16 feature maps need an explicit feat_type='bf16'")
+    if dt == np.uint8:
+        raise ValueError("uint8 feature maps need an explicit feat_type='e4m3' or 'e5m2'")
     return "f16" if dt == np.float16 else "f32"
 
 
 def as_feats(feats, feat_type=None):
     """-> (C-contiguous array in the element type, its name).  f32 and f16 arrays of another
-    floating type are converted by numpy (round to nearest even); bf16 must already be bits."""
+    floating type are converted by numpy (round to nearest even); bf16 and fp8 must already be bits."""
     name = infer(feats, feat_type)
     return np.ascontiguousarray(feats, _DTYPES[name]), name
 
@@ -56,18 +74,63 @@ def bf16_bits(a) -> np.ndarray:
     return ((x + (((x >> 16) & 1) + 0x7FFF)) >> 16).astype(np.uint16)
 
 
+def fp8_bits(a, feat_type: str) -> np.ndarray:
+    """f32 values -> OCP fp8 codes (uint8) of `feat_type` "e4m3" | "e5m2": THE narrowing contract.
+
+    Round to nearest even; every result beyond the largest finite value (448 / 57344) becomes that value
+    with the input's sign, +-inf included (saturating); NaN becomes a NaN code; magnitudes at or below half
+    the smallest subnormal become +-0; the sign is the input's sign bit.  With emin = 1 - bias:
+    e = max(floor(log2 |x|), emin), q = 2^(e - mbits), r = min(rint(|x| / q) * q, largest finite)."""
+    if feat_type not in _FP8:
+        raise ValueError(f"fp8_bits: feat_type {feat_type!r}: 'e4m3' or 'e5m2'")
+    mbits, bias, maxf = _FP8[feat_type]
+    emin = 1 - bias
+    x = np.ascontiguousarray(a, np.float32)
+    sign = ((x.view(np.uint32) >> 24) & 0x80).astype(np.uint8)
+    nan = np.isnan(x)
+    mag = np.abs(np.where(nan, np.float32(0), x).astype(np.float64))
+    mag = np.minimum(mag, 2.0 * maxf)                    # inf and huge values: anything that saturates
+    _, ex = np.frexp(mag)                                # mag = f * 2^ex, f in [0.5, 1): floor(log2) = ex - 1
+    e = np.maximum(ex.astype(np.int64) - 1, emin)        # (mag == 0: ex = 0, e = emin)
+    r = np.minimum(np.ldexp(np.rint(np.ldexp(mag, mbits - e)), e - mbits), maxf)   # rint: to nearest even
+    # r is a value of the format: encode it (rounding may have carried it into the next exponent)
+    _, ex = np.frexp(r)
+    e = np.maximum(ex.astype(np.int64) - 1, emin)
+    m = np.ldexp(r, mbits - e).astype(np.int64)          # in [0, 2^(mbits+1)); below 2^mbits: subnormal or zero
+    code = np.where(m < 2 ** mbits, m, ((e + bias) << mbits) | (m - 2 ** mbits)).astype(np.uint8)
+    return np.where(nan, np.uint8(0x7F), code) | sign
+
+
 def widen(a, feat_type: str) -> np.ndarray:
     """A map of `feat_type` as the f32 values it stands for (exact)."""
     check_name(feat_type)
     a = np.asarray(a)
+    if feat_type == "e5m2":                              # the upper byte of a binary16
+        return (a.astype(np.uint16) << 8).view(np.float16).astype(np.float32)
+    if feat_type == "e4m3":
+        c = a.astype(np.uint32)
+        e, m = (c >> 3) & 0xF, c & 7
+        v = np.where(e == 0, np.ldexp(m.astype(np.float32), -9),
+                     np.ldexp((8 + m).astype(np.float32), e.astype(np.int32) - 10)).astype(np.float32)
+        v = np.where((c & 0x7F) == 0x7F, np.float32(np.nan), v)
+        return (v.view(np.uint32) | ((c & 0x80) << 24)).view(np.float32)
     if feat_type == "bf16":
         return (a.astype(np.uint32) << 16).view(np.float32)
     return a.astype(np.float32)
 
 
-def store(dst: np.ndarray, src) -> None:
-    """dst[...] = src converted to dst's element type (float32, float16 or bf16 bits as uint16)."""
-    if dst.dtype == np.uint16:
+def store(dst: np.ndarray, src, feat_type=None) -> None:
+    """dst[...] = src converted to dst's element type (float32, float16, bf16 bits as uint16, or fp8 codes as
+    uint8).  A uint8 `dst` does not say which fp8 format it holds: name it with `feat_type` unless `src` is
+    uint8 codes already."""
+    if dst.dtype == np.uint8:
+        src = np.asarray(src)
+        if src.dtype != np.uint8:
+            if feat_type not in _FP8:
+                raise ValueError("store into uint8 (fp8 codes) needs feat_type='e4m3' or 'e5m2'")
+            src = fp8_bits(src.astype(np.float32), feat_type).reshape(dst.shape)
+        dst[...] = src
+    elif dst.dtype == np.uint16:
         src = np.asarray(src)
         dst[...] = src if src.dtype == np.uint16 else bf16_bits(src.astype(np.float32)).reshape(dst.shape)
     else:

@@ -52,7 +52,8 @@ class DataClass:
     def __init__(self, qs: QuestionSet, img_names, batch_size, split="train", prefetch=False,
                  seed=123, feat_type="f32"):
         self.qs, self.img_names, self.batch_size, self.split = qs, list(img_names), batch_size, split
-        # element type of the feats next_batch_feat returns: "f32" | "f16" | "bf16" (uint16 bits)
+        # element type of the feats next_batch_feat returns: "f32" | "f16" | "bf16" (uint16 bits) | "e4m3" | "e5m2"
+        # (uint8 codes: the files' f32 / f16 values narrowed on the host by feat16.fp8_bits)
         self.feat_type = feat16.check_name(feat_type)
         self.n = int(qs.question.shape[0])
         if self.n < batch_size:
@@ -127,14 +128,15 @@ class DataClass:
         destination (the pinned staging of an upload slot: the batch is assembled where the H2D copy
         reads it), whose dtype then decides; fewer paths than it has room for (an image table) fill its
         first len(paths) maps.  f32 files are rounded into a 16-bit destination on
-        assignment; HalfTensor files are copied as they are into an fp16 one."""
+        assignment; HalfTensor files are copied as they are into an fp16 one.  An fp8 destination (uint8:
+        `feat_type` says which format) takes feat16.fp8_bits of the files' values."""
         if out is None:
             out = np.zeros((len(paths), D, W, H), feat16.dtype_of(feat_type))
         else:
             out = out.reshape(-1)[:len(paths) * D * W * H].reshape(len(paths), D, W, H)
         keep_half = out.dtype != np.float32
         for i, p in enumerate(paths):   # load_feature asserts the three sizes
-            feat16.store(out[i], t7.load_feature(p, D, W, H, keep_half).reshape(D, W, H))
+            feat16.store(out[i], t7.load_feature(p, D, W, H, keep_half).reshape(D, W, H), feat_type)
         return out
 
     def _start_prefetch(self, tab_featpaths, D, W, H):
@@ -154,7 +156,7 @@ class DataClass:
         self._job = ((self.batch_index, tuple(paths), unique), th, holder)
 
     def next_batch_feat(self, tab_featpaths, feat_dim, feat_w=1, feat_h=1, unique=False):
-        """-> feats [B,D,W,H] (f32, or the 16-bit feat_type), x [T,B] i32, x_len [B] i32, a [B] | [B,nMC] i32, qids [B].
+        """-> feats [B,D,W,H] (f32, or the 16-bit / fp8 feat_type), x [T,B] i32, x_len [B] i32, a [B] | [B,nMC] i32, qids [B].
         unique=True: every distinct feature file of the batch is read once, in order of first appearance;
         feats is that image table [N,D,W,H] and image_of [B] i32 (0-based table rows) is appended to the
         tuple: feats[image_of] is what unique=False returns."""
@@ -217,7 +219,8 @@ class DataClass:
     def fill_bank(self, rau, tab_featpaths, feat_dim, feat_w=1, feat_h=1, chunk=64):
         """Reads every distinct feature file of the split ONCE and puts it into rau's bank at its
         bank_rows row, `chunk` files per rau.bank_put.  f32 files go up as f32 whatever the bank's type
-        (a 16-bit bank narrows them on the device); HalfTensor files go into an fp16 bank as they are.
+        (a 16-bit or fp8 bank narrows them on the device: for fp8, round to nearest even, saturating at the
+        largest finite value); HalfTensor files go into an fp16 bank as they are.
         -> number of rows written."""
         files, _ = self.bank_rows(tab_featpaths)
         info = rau.bank_info()
@@ -267,7 +270,8 @@ def _read_questions(vqa_dir):
 
 def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=123, feat_type="f32"):
     """loader.lua:1294-1473 (without the valid_ratio split); feat_type: element type of the
-    feature maps the iterators return ("f32" | "f16" | "bf16")."""
+    feature maps the iterators return ("f32" | "f16" | "bf16" | "e4m3" | "e5m2"; fp8 maps are the files'
+    values narrowed on the host, feat16.fp8_bits)."""
     with open(os.path.join(vqa_dir, "data_prepro.json")) as f:
         info = json.load(f)
     d = _read_questions(vqa_dir)
@@ -298,7 +302,7 @@ def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=12
 
 def feed(rau, batch, feat_type=None):
     """next_batch_feat's tuple -> rau_set_batch (the H2D of SS:434-439); returns qids.
-    feat_type: that of the feats (needed for bf16, which arrives as uint16 bits).  A tuple of
+    feat_type: that of the feats (needed for bf16 and fp8, which arrive as uint16 / uint8 bits).  A tuple of
     next_batch_feat(unique=True) goes up as an image table, one of next_batch_rows as a bank batch.
     The batch may be smaller than the context's capacity (a test split at test_batch_size): set_batch
     takes the size from x_len and switches the context to it."""
@@ -380,7 +384,7 @@ class SlotFeeder:
         table = {"image_of": batch[5], "n_images": feats.shape[0]} if self.share_images else {}
         if not np.shares_memory(feats, view["feats"]):   # first batch / a re-drawn order: not prefetched in place
             stage = view["feats"].reshape(-1)[:feats.size]
-            feat16.store(stage, feats.reshape(stage.shape))
+            feat16.store(stage, feats.reshape(stage.shape), self.feat_type)
         view["tokens"][...] = x
         view["lens"][...] = x_len
         labels = a.ndim == 1                          # test batches carry MC ids, no labels

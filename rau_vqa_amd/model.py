@@ -243,7 +243,9 @@ class RAU:
 
     def bank_put(self, first, feats, feat_type=None):
         """feats [n, D, S] into rows first .. first+n-1.  Maps of the bank's type are copied; f32 maps
-        into a 16-bit bank are narrowed on the device (the bits feat16.store gives on the host)."""
+        into a 16-bit or fp8 bank are narrowed on the device (the bits feat16.store gives on the host; fp8:
+        feat16.fp8_bits, round to nearest even, saturating at the largest finite value).  fp8 codes are
+        uint8 arrays and need feat_type="e4m3" | "e5m2"."""
         c = self.cfg
         feats, ft = feat16.as_feats(feats, feat_type)
         n = feats.size // (c.D * c.S)
@@ -252,7 +254,7 @@ class RAU:
         L.check(self._lib.rau_bank_put(self._h, int(first), n, feats.ctypes.data, feat16.FEAT_TYPES[ft]))
 
     def bank_get(self, first, count):
-        """Rows first .. first+count-1 as [count, D, S] in the bank's element type (bf16: uint16 bits)."""
+        """Rows first .. first+count-1 as [count, D, S] in the bank's element type (bf16: uint16 bits; fp8: uint8 codes)."""
         c = self.cfg
         out = np.empty((int(count), c.D, c.S), feat16.dtype_of(self.bank_info()["feat_type"]))
         L.check(self._lib.rau_bank_get(self._h, int(first), int(count), out.ctypes.data))
@@ -273,8 +275,9 @@ class RAU:
         return int(rows.size), rows, image_of
 
     def set_batch(self, feats, tokens, lens, labels=None, feat_type=None, image_of=None, bank_rows=None):
-        """feat_type "f32" | "f16" | "bf16" (default: from the dtype, see feat16.infer): a 16-bit map
-        gives the same results, bit for bit, as the f32 map of its widened values.
+        """feat_type "f32" | "f16" | "bf16" | "e4m3" | "e5m2" (default: from the dtype, see feat16.infer;
+        bf16 is uint16 bits, fp8 is uint8 codes, both must be named): a 16-bit or fp8 map gives the same
+        results, bit for bit, as the f32 map of its widened values.
         image_of [B] (0-based rows): feats is an image TABLE [N, D, S] that the questions of one image
         share; the same results, bit for bit, as the plain batch feats[image_of].
         bank_rows [N] (feats None): the table is bank[bank_rows], gathered inside device memory.
@@ -343,7 +346,8 @@ class RAU:
         """numpy views of slot's PINNED staging: {feats [n,D,S], tokens [T,n], lens [n], labels [n]},
         n = the current batch_size (each array starts where the capacity puts it and is dense in n).
         A loader fills them in place; set_batch_async(slot) then uploads without a host copy.
-        feats is a view of the staging's start in feat_type's dtype (bf16: uint16 bit patterns);
+        feats is a view of the staging's start in feat_type's dtype (bf16: uint16 bit patterns; fp8: uint8
+        codes, the first quarter of the staging);
         upload it with set_batch_async(slot, feat_type=<the same>)."""
         c, B = self.cfg, self._n
         fdt = feat16.dtype_of(feat_type)

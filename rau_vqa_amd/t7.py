@@ -293,7 +293,9 @@ def load_snapshot(path):
 def load_feature(path, D, W, H, keep_half=False):
     """One image's feature map as the loader hands it on (vqa_prepro_loader.lua:549-552):
     FloatTensor [D, W, H] -> float32 [D, W*H] (a row of rau_set_batch's feats).  keep_half: a
-    HalfTensor file stays float16 (no widening on the host; the device widens it exactly)."""
+    HalfTensor file stays float16 (no widening on the host; the device widens it exactly).  Torch7 has
+    no fp8 tensor: fp8 maps (feat16: "e4m3" | "e5m2") are made from these values by feat16.fp8_bits on the
+    host or by the bank's narrowing on the device, never read from a file."""
     t = load(path)
     if not isinstance(t, Tensor):
         raise T7Error("feature file does not hold a tensor")

@@ -12,7 +12,8 @@ f32 and f16 it times the evaluate-mode forward three ways:
 A training leg (forward + backward, f32 maps, plain batches) compares upload against bank the same way.
 All legs run in this one process, alternated --rounds times, so a leg's spread against itself stands next
 to the differences between legs.  Also reported: the bank gather's own time and bytes (rau_prof class
-`bank_gather`, alone on the stream) and rau_bank_put's rate with and without narrowing.  One JSON line:
+`bank_gather`, alone on the stream), rau_bank_put's rate with and without narrowing, and the fill time and
+bytes of an e4m3 bank (f32 maps narrowed on the device) beside the f16 bank.  One JSON line:
 
     python tools/bank_time.py --config 1 --batch 256 [--steps 30] [--rounds 5]
 """
@@ -61,7 +62,8 @@ def main():
     nsteps = max(args.steps, args.train_steps) + args.warmup + 2
     rows = {k: [rng.permutation(POOL)[:v["n"]].astype(np.int32) for _ in range(nsteps)] for k, v in kinds.items()}
 
-    put_gbs = {"f32_to_f32": [], "f16_to_f16": [], "f32_to_f16_narrowed": []}
+    put_gbs = {"f32_to_f32": [], "f16_to_f16": [], "f32_to_f16_narrowed": [], "f32_to_e4m3_narrowed": []}
+    fill_ms = {"f16": [], "e4m3": []}          # wall time of filling POOL rows from f32 maps, per bank type
 
     def fill(ft, narrowed=False):
         """a fresh bank of POOL maps of `ft`, filled with two puts of B maps; records the rate"""
@@ -72,7 +74,9 @@ def main():
         m.bank_put(0, src)
         m.bank_put(B, src)
         dt = time.perf_counter() - t0
-        put_gbs["f32_to_f16_narrowed" if narrowed else f"{ft}_to_{ft}"].append(2 * src.nbytes / dt / 1e9)
+        put_gbs[f"f32_to_{ft}_narrowed" if narrowed else f"{ft}_to_{ft}"].append(2 * src.nbytes / dt / 1e9)
+        if narrowed:
+            fill_ms[ft].append(dt * 1e3)
 
     def stage(kind, ft):
         """the leg's batch into the pinned staging of both slots, in place"""
@@ -154,6 +158,7 @@ def main():
                                            "bytes_moved": p["bytes"] / p["launches"],
                                            "GB_s": round(p["bytes"] / p["launches"] / (p["ms"] / p["launches"]) / 1e6, 1)}
         fill("f16", narrowed=True)
+        fill("e4m3", narrowed=True)
         # training: forward + backward on plain f32 batches, Philox masks
         m.training()
         m.set_dropout_seed(5, rnd)
@@ -171,6 +176,9 @@ def main():
            "eval": {k: {leg: summary(v) for leg, v in d.items()} for k, d in qa.items()},
            "train_plain_f32": {leg: summary(v) for leg, v in tr.items()},
            "bank_gather": gather,
+           "bank_fill_from_f32": {ft: {"rows": POOL, "bank_bytes": POOL * cfg.D * cfg.S * (2 if ft == "f16" else 1),
+                                       "ms_min": round(min(v), 2), "ms_median": round(float(np.median(v)), 2)}
+                                  for ft, v in fill_ms.items()},
            "bank_put_GB_s": {k: {"min": round(min(v), 2), "max": round(max(v), 2), "median": round(float(np.median(v)), 2)}
                              for k, v in put_gbs.items()}}
     print(json.dumps(res), flush=True)

@@ -1,4 +1,4 @@
-"""Fresh-batch cost of the training step with f32 and with 16-bit feature maps, on one GPU.
+"""Fresh-batch cost of the training step with f32, 16-bit and fp8 feature maps, on one GPU.
 
 For one workload (configs[1]: Ours_SS B = 256, D = 512, f32; configs[2]: Ours_ResNet B = 256,
 D = 2048, bf16 operands) it reports
@@ -7,10 +7,15 @@ D = 2048, bf16 operands) it reports
                          (batch i+1 uploading while step i runs, as bench.py's H2D leg), per feature type,
   * feat_bytes_per_step  feature bytes one step moves over the link, per feature type,
   * h2d_GBps             achieved pinned host-to-device rate: uploads alone (nothing else on the GPU),
-                         feature bytes / wall time of upload + the step stream waiting for it.
+                         feature bytes / wall time of upload + the step stream waiting for it,
+  * dropout_features_ms  the train-mode feature-map dropout pass alone (rau_prof class `dropout_features`,
+                         serialised by the profiler's events) reading a resident batch of each feature type.
 One JSON line per run.  Usage (one workload per process):
 
-    python tools/h2d_feats.py --config 1 [--steps 20] [--feat 16bit-type f16|bf16]
+    python tools/h2d_feats.py --config 1 [--steps 20] [--feat16 f16|bf16] [--types f32,f16,e4m3]
+
+--types names the feature types measured, in order (default: f32, the --feat16 type, e4m3); a library
+older than the fp8 types (RAU_LIB) is measured with --types f32,f16.
 """
 from __future__ import annotations
 
@@ -35,7 +40,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--feat16", choices=("f16", "bf16"), default="f16")
+    ap.add_argument("--types", default=None, help="comma-separated feature types (default: f32,<feat16>,e4m3)")
+    ap.add_argument("--prof-steps", type=int, default=5, help="profiled steps per type for dropout_features_ms")
     args = ap.parse_args()
+    types = args.types.split(",") if args.types else ["f32", args.feat16, "e4m3"]
     import torch  # noqa: F401  (before librau.so: one HIP runtime)
     from rau_vqa_amd import feat16, synth
     from rau_vqa_amd.model import RAU, Config, hop_weights
@@ -71,7 +79,7 @@ def main():
         for sl in (0, 1):
             v = m.batch_slot(sl, feat_type=ft)
             b = batches[sl]
-            feat16.store(v["feats"], b["feats"].reshape(v["feats"].shape))
+            feat16.store(v["feats"], b["feats"].reshape(v["feats"].shape), ft)
             for k in ("tokens", "lens", "labels"):
                 v[k][...] = np.asarray(b[k]).reshape(v[k].shape)
 
@@ -79,7 +87,7 @@ def main():
            "variant": w["variant"], "steps": args.steps}
     m.set_batch(**batches[0])
     out["resident_ms"] = round(timed(step, args.steps), 3)
-    for ft in ("f32", args.feat16):
+    for ft in types:
         fill(ft)
         m.set_batch_async(0, feat_type=ft)
 
@@ -95,10 +103,24 @@ def main():
             m.use_batch(i & 1)
             m.sync()
         ms = timed(upload, args.steps)
-        nbytes = n * (4 if ft == "f32" else 2)
+        nbytes = n * feat16.dtype_of(ft).itemsize
         out[f"feat_bytes_per_step_{ft}"] = nbytes
         out[f"upload_ms_{ft}"] = round(ms, 3)
         out[f"h2d_GBps_{ft}"] = round(nbytes / ms / 1e6, 2)
+    for ft in types:                                     # the dropout pass alone, per input type
+        typed = np.empty(batches[0]["feats"].shape, feat16.dtype_of(ft))
+        feat16.store(typed, batches[0]["feats"], ft)
+        m.set_batch(**dict(batches[0], feats=typed), feat_type=ft)
+        step(0)
+        m.sync()
+        m.prof_enable(True)
+        m.prof_reset()
+        for i in range(args.prof_steps):
+            step(1 + i)
+        p = m.prof()["dropout_features"]
+        m.prof_enable(False)
+        out[f"dropout_features_ms_{ft}"] = round(p["ms"] / p["launches"], 4)
+        out[f"dropout_features_GBps_{ft}"] = round(p["bytes"] / p["ms"] / 1e6, 1)
     m.close()
     print(json.dumps(out), flush=True)
 
