@@ -324,7 +324,7 @@ constexpr int dgrad_lds_bytes(int nst) { return (nst * DSTAGE + DBM + DSP) * 4; 
 
 // Shapes it takes: 14 x 14 maps, rows a multiple of 128, reduction a multiple of 16 (>= 3 stages), 16-byte
 // aligned rows.
-// RAU_DGRAD_DMA=0 keeps the register-staged per-sample kernel (A/B knob, DESIGN.md section 9);
+// RAU_DGRAD_DMA=0 keeps the register-staged per-sample kernel (A/B knob, DESIGN.md section 8);
 // RAU_DGRAD_DMA=2|3 selects the ring depth (default 3).
 static int dgrad_dma_mode() {
   static const int v = [] { const char* e = std::getenv("RAU_DGRAD_DMA"); return e ? std::atoi(e) : 3; }();

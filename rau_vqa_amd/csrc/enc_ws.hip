@@ -97,7 +97,7 @@ __device__ __forceinline__ void wait_counter(unsigned* c, unsigned want, int* er
   }
 }
 
-// BF: both operands of the gate products rounded to bf16 (rau_dtype RAU_BF16, lin_bf16() in kernels.h): the
+// BF: both operands of the gate products rounded to bf16 (rau_dtype RAU_BF16, LinMode::bf16 in kernels.h): the
 // stationary weights once while they are loaded, the h / x2 fragments in registers in front of their MFMAs
 template <int ORDER, bool KIND_B, bool BF>
 __device__ __forceinline__ void enc_ws_body(const EncWsParams& Q, const int wg, float* smem) {

@@ -129,7 +129,7 @@ struct GemmParams {
   const float* v1;     // dj [sample][M]
   const float* v2;     // a  [sample][S]
   float* rs_out;       // SC_DTANH A operand: row sums of the staged operand, partial [split][M]
-  int round16;         // f32 tiles: both operands rounded to bf16 while they are staged (lin_bf16(), kernels.h)
+  int round16;         // f32 tiles: both operands rounded to bf16 while they are staged (LinMode::bf16, kernels.h)
   int dbg;             // tools/kbench only: 1 = no global loads in the loop, 2 = no barriers
 };
 

@@ -30,7 +30,7 @@ static GemmParams lin_params(int M, int N, int K, const float* A, long lda, cons
   P.ymul = o.ymul; P.y_rs = o.y_rs;
   P.emask = o.emask; P.emask_e0 = o.emask_e0; P.emscale = o.emscale;
   P.alpha = o.alpha;
-  P.round16 = lin_bf16();
+  P.round16 = o.mode.bf16;
   return P;
 }
 
@@ -58,12 +58,12 @@ static hipError_t lin_gemm(hipStream_t st, int M, int N, int K, const float* A, 
   GemmParams P = lin_params(M, N, K, A, lda, W, ldw, C, ldc, o);
   if ((long)M * N >= 128L * 128 * 256 && !o.defer_splits)
     return launch_gemm<128, 128, BK, ASRC, BSRC, EPI_LIN>(st, P, 1);
-  if (o.slab && skinny_dma_ok(M, K, lda, ldw, BSRC == SRC_RC, 1, &N, &A, &W)) {
+  if (o.slab && skinny_dma_ok(o.mode.deep, M, K, lda, ldw, BSRC == SRC_RC, 1, &N, &A, &W)) {
     const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
-    const int s = skinny_dma_splits(M, K, tiles, (size_t)N, o.slab_floats);
+    const int s = skinny_dma_splits(o.mode.deep, M, K, tiles, (size_t)N, o.slab_floats);
     if ((size_t)s * M * N <= o.slab_floats && (s > 1 || o.defer_splits)) {
       const long off = 0;
-      hipError_t e = skinny_dma(st, BSRC == SRC_RC, 1, M, K, &A, lda, &W, ldw, &N, o.slab, &off, s);
+      hipError_t e = skinny_dma(st, o.mode, BSRC == SRC_RC, 1, M, K, &A, lda, &W, ldw, &N, o.slab, &off, s);
       if (e != hipSuccess) return e;
       if (o.defer_splits) {
         *o.defer_splits = s;
@@ -109,20 +109,20 @@ hipError_t gemm_nn(hipStream_t st, int M, int N, int K, const float* A, long lda
 // nb same-shape skinny problems in ONE launch, partials left in the slab laid out
 // [problem][split][M*N]; the consumer kernel reduces them (deferred, fixed order).
 template <int ASRC, int BSRC>
-static hipError_t batched_deferred(hipStream_t st, int nb, int M, int N, int K,
+static hipError_t batched_deferred(hipStream_t st, LinMode mode, int nb, int M, int N, int K,
                                    const float* const* A, long lda, const float* const* W,
                                    long ldw, float* slab, size_t slab_floats, int* splits) {
   if (nb < 1 || nb > 3) return hipErrorInvalidValue;
   {
     const int Ns[3] = {N, N, N};
-    if (skinny_dma_ok(M, K, lda, ldw, BSRC == SRC_RC, nb, Ns, A, W)) {
+    if (skinny_dma_ok(mode.deep, M, K, lda, ldw, BSRC == SRC_RC, nb, Ns, A, W)) {
       const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
-      const int s = skinny_dma_splits(M, K, nb * tiles, (size_t)nb * N, slab_floats);
+      const int s = skinny_dma_splits(mode.deep, M, K, nb * tiles, (size_t)nb * N, slab_floats);
       if ((size_t)nb * s * M * N <= slab_floats) {
         long off[3];
         for (int i = 0; i < nb; ++i) off[i] = (long)i * s * M * N;
         *splits = s;
-        return skinny_dma(st, BSRC == SRC_RC, nb, M, K, A, lda, W, ldw, Ns, slab, off, s);
+        return skinny_dma(st, mode, BSRC == SRC_RC, nb, M, K, A, lda, W, ldw, Ns, slab, off, s);
       }
     }
   }
@@ -132,6 +132,7 @@ static hipError_t batched_deferred(hipStream_t st, int nb, int M, int N, int K,
                  nb, M, N, K, slab_floats);
 #endif
   LinOpts o;
+  o.mode = mode;
   o.slab = slab;
   o.slab_floats = slab_floats / nb;
   GemmParams P = lin_params(M, N, K, A[0], lda, W[0], ldw, slab, N, o);
@@ -149,21 +150,21 @@ static hipError_t batched_deferred(hipStream_t st, int nb, int M, int N, int K,
   *splits = s;
   return launch_gemm<64, 64, BKS, ASRC, BSRC, EPI_SLAB>(st, P, s);
 }
-hipError_t gemm_nt_batched_deferred(hipStream_t st, int nb, int M, int N, int K,
+hipError_t gemm_nt_batched_deferred(hipStream_t st, LinMode mode, int nb, int M, int N, int K,
                                     const float* const* A, long lda, const float* const* W,
                                     long ldw, float* slab, size_t slab_floats, int* splits) {
-  return batched_deferred<SRC_KC, SRC_KC>(st, nb, M, N, K, A, lda, W, ldw, slab, slab_floats, splits);
+  return batched_deferred<SRC_KC, SRC_KC>(st, mode, nb, M, N, K, A, lda, W, ldw, slab, slab_floats, splits);
 }
-hipError_t gemm_nn_batched_deferred(hipStream_t st, int nb, int M, int N, int K,
+hipError_t gemm_nn_batched_deferred(hipStream_t st, LinMode mode, int nb, int M, int N, int K,
                                     const float* const* A, long lda, const float* const* W,
                                     long ldw, float* slab, size_t slab_floats, int* splits) {
-  return batched_deferred<SRC_KC, SRC_RC>(st, nb, M, N, K, A, lda, W, ldw, slab, slab_floats, splits);
+  return batched_deferred<SRC_KC, SRC_RC>(st, mode, nb, M, N, K, A, lda, W, ldw, slab, slab_floats, splits);
 }
 
 // nb (<= 3) skinny problems that share A and K but have different widths / weights, in ONE
 // launch; partials stay in the slab, problem i at slab + off[i] laid out [split][M][N[i]].
-hipError_t gemm_nt_hetero_deferred(hipStream_t st, int nb, int M, int K, const float* A, long lda,
-                                   const float* const* W, long ldw, const int* N, float* slab,
+hipError_t gemm_nt_hetero_deferred(hipStream_t st, LinMode mode, int nb, int M, int K, const float* A,
+                                   long lda, const float* const* W, long ldw, const int* N, float* slab,
                                    size_t slab_floats, int* splits, size_t* off) {
   if (nb < 1 || nb > 3) return hipErrorInvalidValue;
   int nmax = 0, tiles = 0;
@@ -175,8 +176,8 @@ hipError_t gemm_nt_hetero_deferred(hipStream_t st, int nb, int M, int K, const f
   }
   {
     const float* As[3] = {A, A, A};
-    if (skinny_dma_ok(M, K, lda, ldw, false, nb, N, As, W)) {
-      const int s = skinny_dma_splits(M, K, tiles, nsum, slab_floats);
+    if (skinny_dma_ok(mode.deep, M, K, lda, ldw, false, nb, N, As, W)) {
+      const int s = skinny_dma_splits(mode.deep, M, K, tiles, nsum, slab_floats);
       if ((size_t)s * M * nsum <= slab_floats) {
         long o2[3];
         size_t acc = 0;
@@ -186,7 +187,7 @@ hipError_t gemm_nt_hetero_deferred(hipStream_t st, int nb, int M, int K, const f
           acc += (size_t)s * M * N[i];
         }
         *splits = s;
-        return skinny_dma(st, false, nb, M, K, As, lda, W, ldw, N, slab, o2, s);
+        return skinny_dma(st, mode, false, nb, M, K, As, lda, W, ldw, N, slab, o2, s);
       }
     }
   }
@@ -205,6 +206,7 @@ hipError_t gemm_nt_hetero_deferred(hipStream_t st, int nb, int M, int K, const f
     s = (nk + per - 1) / per;
   }
   LinOpts o;
+  o.mode = mode;
   GemmParams P = lin_params(M, nmax, K, A, lda, W[0], ldw, slab, nmax, o);
   P.nk = nk;
   P.nbatch = nb;
@@ -239,6 +241,7 @@ size_t gemm_tn_slab_floats(int M, int N, int K) {
 hipError_t gemm_tn_acc(hipStream_t st, int M, int N, int K, const float* A, long lda,
                        const float* B, long ldb, float* C, long ldc, float* slab, float* dbias, int bf16) {
   LinOpts o;
+  o.mode.bf16 = bf16;   // feeds lin_params' round16 and, below, the choice of the bf16-staging tile
   o.accumulate = 1;
   const int s = tn_splits(M, N, K);
   float* rs = dbias ? slab + (s > 1 ? (size_t)s * M * N : 0) : nullptr;

@@ -20,6 +20,16 @@ void split_ws_unregister(const float* base);
 bool split_span_ok(const float* slab, long nsplit, size_t per_split_floats);
 
 // ------------------------------------------------------------ GEMM (gemm_lin.hip)
+// How a Linear product is formed: an argument of every launch, computed by the caller from its context at call
+// time (lin_mode, rau_ctx.h) -- there is no per-thread or per-process state behind these GEMMs.
+//  bf16: rau_dtype RAU_BF16 (BASELINE.json configs[2]: "bf16 MFMA gate/classifier GEMMs"): forward y = x W^T,
+//        input gradient dx = dy W and weight gradient dW += dy^T x, whichever kernel serves them, round both
+//        operands to bf16 (round to nearest even) and accumulate in f32.  skinny_dma.hip does it with bf16 MFMAs;
+//        the register-staged fallback tiles round while staging and keep the f32 MFMA (same products, another
+//        summation order).
+//  deep: skinny_dma.hip's stages are 32-deep where K % 64 == 0 (else 16-deep).  The depth also decides which
+//        shapes count as ragged and how many K splits a launch makes, i.e. the summation order.
+struct LinMode { int bf16 = 0; int deep = 0; };
 struct LinOpts {
   const float* bias = nullptr;    // + bias[n]
   const float* bias2 = nullptr;   // + bias2[n]
@@ -40,6 +50,7 @@ struct LinOpts {
   // deferred reduction: leave the K-split partials in `slab` ([splits][M*N]) and
   // report the split count; the consumer kernel (lstm_fwd / lstm_bwd) sums them
   int* defer_splits = nullptr;
+  LinMode mode;
 };
 // C[M,N] = epi(A[M,K] * W[N,K]^T)      (Linear forward)
 hipError_t gemm_nt(hipStream_t st, int M, int N, int K, const float* A, long lda,
@@ -50,23 +61,23 @@ hipError_t gemm_nn(hipStream_t st, int M, int N, int K, const float* A, long lda
 // nb (<= 3) same-shape problems C_i = A_i W_i^T (nt) / A_i W_i (nn) in one launch; the
 // K-split partials stay in `slab` as [problem][split][M*N] (*splits per problem) for a
 // consumer kernel to sum -- used by the encoder's layer wavefront.
-hipError_t gemm_nt_batched_deferred(hipStream_t st, int nb, int M, int N, int K,
+hipError_t gemm_nt_batched_deferred(hipStream_t st, LinMode mode, int nb, int M, int N, int K,
                                     const float* const* A, long lda, const float* const* W,
                                     long ldw, float* slab, size_t slab_floats, int* splits);
-hipError_t gemm_nn_batched_deferred(hipStream_t st, int nb, int M, int N, int K,
+hipError_t gemm_nn_batched_deferred(hipStream_t st, LinMode mode, int nb, int M, int N, int K,
                                     const float* const* A, long lda, const float* const* W,
                                     long ldw, float* slab, size_t slab_floats, int* splits);
 // nb (<= 3) Linear forwards x W_i^T that share x (and K) but differ in width, one launch;
 // problem i's partials at slab + off[i] as [*splits][M][N[i]]
-hipError_t gemm_nt_hetero_deferred(hipStream_t st, int nb, int M, int K, const float* A, long lda,
-                                   const float* const* W, long ldw, const int* N, float* slab,
+hipError_t gemm_nt_hetero_deferred(hipStream_t st, LinMode mode, int nb, int M, int K, const float* A,
+                                   long lda, const float* const* W, long ldw, const int* N, float* slab,
                                    size_t slab_floats, int* splits, size_t* off);
 // C[M,N] += A[K,M]^T * B[K,N]          (Linear weight gradient; deterministic split-K
 // through `slab`, which must hold gemm_tn_slab_floats(M,N,K) floats)
 size_t gemm_tn_slab_floats(int M, int N, int K);
 // dbias (optional): dbias[m] += sum_k A[k, m], from the same pass over A (Linear bias gradient)
-// bf16 != 0 (RAU_BF16 mode; BASELINE.json configs[2]: "bf16 MFMA gate/classifier GEMMs"): both operands
-// rounded to bf16 (RNE) while staged, f32 accumulate; dbias is summed from the UNROUNDED values
+// bf16 != 0 (LinMode::bf16): both operands rounded to bf16 (RNE) while staged, f32 accumulate; dbias is
+// summed from the UNROUNDED values
 hipError_t gemm_tn_acc(hipStream_t st, int M, int N, int K, const float* A, long lda,
                        const float* B, long ldb, float* C, long ldc, float* slab,
                        float* dbias = nullptr, int bf16 = 0);
@@ -165,23 +176,14 @@ hipError_t wgrad16(hipStream_t st, int nB, int ra, int rb, int S, const void* A1
 // A_p W_p (brc = true, W [K][N]) of one M and K; problem p's partials at slab + off[p] laid out
 // [split][M][N[p]].  _ok: K % 32 == 0, 16-byte aligned rows, [K][N] weights a multiple of 64 wide;
 // RAU_SKINNY_DMA_OFF=1 keeps the register-staged tile of gemm_core.h (A/B knob).
-bool skinny_dma_ok(int M, int K, long lda, long ldb, bool brc, int nprob, const int* N,
+// deep (LinMode::deep): 32-deep stages where K % 64 == 0, else 16-deep (one kernel template).  The three
+// functions of one launch must be given the same value: raggedness and the split count depend on the depth.
+bool skinny_dma_ok(int deep, int M, int K, long lda, long ldb, bool brc, int nprob, const int* N,
                    const float* const* A, const float* const* B);
-int skinny_dma_splits(int M, int K, int tiles_all, size_t cols_all, size_t slab_floats);
-// 16-deep or 32-deep stages (one kernel template; 32-deep needs K % 64 == 0): chosen for the calling
-// thread by skinny_dma_set_deep, which the step-level entry points set from chain_bound() (rau_ctx.h)
-void skinny_dma_set_deep(int on);
-// rau_dtype RAU_BF16 (BASELINE.json configs[2]: "bf16 MFMA gate/classifier GEMMs"): every Linear product
-// of the calling thread's launches -- forward y = x W^T and input gradient dx = dy W through gemm_nt /
-// gemm_nn and their batched forms, whichever kernel serves them -- rounds both operands to bf16 (round to
-// nearest even) and accumulates in f32.  skinny_dma.hip does it with bf16 MFMAs; the register-staged
-// fallback tiles round while staging and keep the f32 MFMA (same products, another summation order).
-// Set at every step-level entry point from the ctx's dtype (set_skinny_policy, rau_ctx.h).
-void lin_set_bf16(int on);
-int lin_bf16();
-hipError_t skinny_dma(hipStream_t st, bool brc, int nprob, int M, int K, const float* const* A,
-                      long lda, const float* const* B, long ldb, const int* N, float* slab,
-                      const long* off, int splits);
+int skinny_dma_splits(int deep, int M, int K, int tiles_all, size_t cols_all, size_t slab_floats);
+hipError_t skinny_dma(hipStream_t st, LinMode mode, bool brc, int nprob, int M, int K,
+                      const float* const* A, long lda, const float* const* B, long ldb, const int* N,
+                      float* slab, const long* off, int splits);
 // the same products with both operands staged by LDS-DMA (wgrad_dma.hip, round 3): 14 x 14 maps,
 // row counts multiples of 128, plain operands (dZ already final)
 bool wgrad_dma_ok(int ra, int rb, int S);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -18,13 +19,11 @@
 
 using namespace rau;
 
-// LinOpts pre-wired with the ctx's split-K workspace
 constexpr int kEncHeadTokens = 4;   // tokens whose layer-1 input projection stays on the chain stream
 constexpr int kEncSideChunks = 4;   // the other tokens' projection: that many launches on the third stream, each with
                                     // its own event -- the recurrence waits for the chunk it is about to read, not
                                     // for all of them (one launch of 22 x 256 rows took 0.3-0.45 ms beside the bulk
                                     // tiles and held the encoder at token 5)
-#define LINOPTS(name) LinOpts name; name.slab = ctx->slab; name.slab_floats = ctx->slab_floats
 
 // ------------------------------------------------------------------ errors
 // sets the calling thread's rau_last_error() message and returns `code`
@@ -110,6 +109,16 @@ struct BatchSlot {
   bool upload_pending = false, consumed_valid = false;
 };
 
+// What a stream owns besides its queue: launches that share a workspace must be ordered by their stream, so
+// whoever launches on `owner` takes the scratch from the same record (lin_opts below wires the slab into a GEMM).
+struct StreamWs {
+  hipStream_t owner = nullptr;   // a copy of the handle: rau_ctx::st, st2 or st3
+  float* slab = nullptr;         // split-K workspace
+  size_t floats = 0;             // what the current batch size asks for: the launch policy reads this
+  size_t alloc = 0;              // floats really allocated (>= floats after a resize)
+  float* coltmp = nullptr;       // column-sum scratch of colsum_acc (bulk and side stream)
+};
+
 struct rau_ctx {
   rau_config cfg;             // cfg.B is the CURRENT batch size (rau_set_batch_size): what every layout, launch and
                               // getter reads at call time -- the B of the fresh context this one is equivalent to
@@ -121,6 +130,7 @@ struct rau_ctx {
   hipStream_t st = nullptr;    // chain stream: recurrences, small GEMMs; what callers order against
   hipStream_t st2 = nullptr;   // bulk stream: hop-batched 1x1-conv GEMMs, overlapped with the chain
   hipStream_t st3 = nullptr;   // weight-gradient stream: throughput GEMMs nobody waits for until the end
+  StreamWs ws_chain, ws_bulk, ws_side;   // the workspaces of st, st2 and st3 (stream_ws() below lists them)
   hipEvent_t evA = nullptr, evD = nullptr, evW = nullptr, evE = nullptr, evW3 = nullptr,
              evM3 = nullptr, evEnd = nullptr, evE1 = nullptr, evHd = nullptr,
              evG0 = nullptr, evG = nullptr, evQ0 = nullptr, evQ = nullptr, evDq = nullptr;   // side-stream forks / joins
@@ -196,7 +206,7 @@ struct rau_ctx {
       *dl, *lossrow, *dopred, *losses_d, *hopw_d;
   int32_t* argmax_d;
   float* att_part = nullptr;  // [B][chunks][S] partial column sums of the split attention kernels
-  bool att_split_env = false; // RAU_ATT_SPLIT: 4-wave row-chunk attention kernels instead of the fused ones
+  bool att_split = false;     // 4-wave row-chunk attention kernels instead of the fused ones (plan_batch: by shape)
   // persistent encoder forward (enc_ws.hip): device error word (a bounded spin gave up), copied to pinned memory behind the launch
   bool enc_ws = false;          // weight-stationary persistent encoder forward (enc_ws.hip): evaluate mode
   bool enc_ws_train = false;    // ... and in training steps
@@ -211,11 +221,8 @@ struct rau_ctx {
   // backward temporaries
   // dZ holds dI (gradient at i_embed's OUTPUT); the tanh derivative is applied by its consumers
   float *dpre, *dhn, *dg4, *dcn[2], *dhp[2], *dj, *da_lin, *dz, *du, *dwsp, *dZ,
-      *dqt, *dQD, *dq, *slab, *slab2, *slab3, *coltmp3, *tmpS, *coltmp2, *dbi_part;
-  size_t slab3_floats = 0, slab2_floats = 0;   // what the current batch size asks for: the launch policy reads these
-  size_t slab_alloc = 0, slab2_alloc = 0, slab3_alloc = 0;   // floats really allocated (>= the above after a resize)
+      *dqt, *dQD, *dq, *tmpS, *dbi_part;
   float *dG1, *dG2, *dwe, *edc[2][2];
-  size_t slab_floats = 0;
   // module-level entry points (rau_modules.hip); allocated on first use
   bool mod_ready = false;
   float *m_state = nullptr, *m_dstate = nullptr;   // [T][B][Q] packed DeepLSTM state slots
@@ -285,12 +292,28 @@ inline bool side_split(const rau_ctx* ctx) {
   if (ctx->side_split_env >= 0) return ctx->side_split_env != 0;
   return chain_bound(ctx);
 }
-// The recurrence's skinny GEMMs with 32-deep stages (skinny_dma.hip, NH = 2) under the same predicate
-// (RAU_SKINNY_DEEP=0|1 overrides): set for the calling thread at every step-level entry point.
-inline void set_skinny_policy(const rau_ctx* ctx) {
+// How this context's Linear GEMMs are formed NOW: bf16 products by its dtype, and the recurrence's skinny GEMMs
+// with 32-deep stages (skinny_dma.hip, NH = 2) under the same predicate as the side split (RAU_SKINNY_DEEP=0|1
+// overrides).  chain_bound() depends on the mode and the batch size, which change after rau_create: computed at
+// every launch, never stored.
+inline LinMode lin_mode(const rau_ctx* ctx) {
   static const int env = [] { const char* e = std::getenv("RAU_SKINNY_DEEP"); return e ? (std::atoi(e) != 0 ? 1 : 0) : -1; }();
-  skinny_dma_set_deep(env >= 0 ? env : (chain_bound(ctx) ? 1 : 0));
-  lin_set_bf16(ctx->bf16 == 1);
+  LinMode m;
+  m.bf16 = ctx->bf16 == 1;
+  m.deep = env >= 0 ? env : (chain_bound(ctx) ? 1 : 0);
+  return m;
+}
+// The three workspaces, in the order of BatchPlan::ws (chain, bulk, side)
+inline std::array<StreamWs*, 3> stream_ws(rau_ctx* ctx) { return {&ctx->ws_chain, &ctx->ws_bulk, &ctx->ws_side}; }
+// Options of a Linear GEMM launched on ws.owner: the context's mode and that stream's split-K workspace.  Every
+// LinOpts that reaches a GEMM starts here; callers that carve a region out of the slab, or point it at other
+// scratch, overwrite slab / slab_floats afterwards.
+inline LinOpts lin_opts(const rau_ctx* ctx, const StreamWs& ws) {
+  LinOpts o;
+  o.mode = lin_mode(ctx);
+  o.slab = ws.slab;
+  o.slab_floats = ws.floats;
+  return o;
 }
 // The hop outputs now hold the results of the forward just enqueued: rau_step_stats / rau_predict may
 // read them until the next forward, module-level call or upload into the batch slot it read.
@@ -455,7 +478,7 @@ __attribute__((visibility("hidden"))) int hop_forward_chain(rau_ctx* ctx, int h,
 // The resident batch as per-sample maps [B][D][Sp] in its element type: the buffer itself, or for a batch
 // with an image table its expansion (expand_features on the chain stream, once per upload).
 __attribute__((visibility("hidden"))) int batch_maps(rau_ctx* ctx, const float** maps);
-__attribute__((visibility("hidden"))) int hop_forward_head(rau_ctx* ctx, hipStream_t s, float* ws,
-    size_t reg, int h0, int nh, const int32_t* labels);
+__attribute__((visibility("hidden"))) int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh,
+    const int32_t* labels);
 __attribute__((visibility("hidden"))) int hop_backward(rau_ctx* ctx, int h, const float* cp,
     const float* Ih, const HopGrad& g);

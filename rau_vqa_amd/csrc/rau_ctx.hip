@@ -92,7 +92,7 @@ static int enc_wgrad_problems(rau_ctx* ctx, size_t row0, TnProblem* pr) {
 struct BatchPlan {
   std::vector<int> groups;                   // forward hop-group partition (rau_ctx::groups)
   bool att_split, enc_ws, enc_ws_train;
-  size_t slab, slab2, slab3, att_part;       // workspace needs, floats
+  size_t ws[3], att_part;                    // workspace needs, floats: ws in the order of stream_ws()
   size_t mcount[5];                          // mask sites, elements
 };
 static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
@@ -150,7 +150,7 @@ static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
   {
     // Weight-stationary persistent encoder (enc_ws.hip): chosen by shape, never by the environment in
     // normal use -- contexts of up to 64 samples (the strong-scaling shards of configs[3]) are bound
-    // by the recurrence's launches.  RAU_ENC_WS=0|1 is the A/B override (DESIGN.md section 9).
+    // by the recurrence's launches.  RAU_ENC_WS=0|1 is the A/B override (DESIGN.md section 8).
     const char* e = std::getenv("RAU_ENC_WS");
     // measured in the step (MS weights, same box): B = 16 / 32 / 64 -> 3.00 / 3.49 / 4.46 ms with it,
     // 3.16 / 3.52 / 4.26 without; evaluate-mode forward 14.3 / 26.8 / 45.9 k vs 10.8 / 20.8 / 40.4 k QA/s.
@@ -170,12 +170,12 @@ static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
     size_t sl2 = std::max(conv_wgrad_slab_floats(H * B, A, M, S),
                           conv_wgrad_slab_floats(H * B, M, D, S));
     if (ctx->bf16) sl2 = std::max(sl2, wgrad16_slab_floats(H * B, M, D, S));
-    // The grouped Linear weight-gradient GEMMs' partial slabs.  They run on the weight-gradient stream
-    // (slab3) or, where the bulk stream is the longer path, at the END of the bulk stream (rau_backward):
-    // there they take the BULK stream's workspace -- each stream owns its workspace, and two launches that
-    // share one must be ordered by their stream.  (Round 4 first moved the mult group's GEMM to the bulk
-    // stream with slab3 still in its hands while the encoder group's GEMM used slab3 on the third stream:
-    // the two ran concurrently and overwrote each other's partials; tests/test_gpu_att_variants.py caught it.)
+    // The grouped Linear weight-gradient GEMMs' partial slabs.  They run on the weight-gradient stream or,
+    // where the bulk stream is the longer path, at the END of the bulk stream (rau_backward), and take the
+    // workspace of the stream they run on (StreamWs, rau_ctx.h): two launches that share a workspace must be
+    // ordered by their stream.  (Round 4 first moved the mult group's GEMM to the bulk stream with the third
+    // stream's slab still in its hands while the encoder group's GEMM used that slab on the third stream: the
+    // two ran concurrently and overwrote each other's partials; tests/test_gpu_att_variants.py caught it.)
     size_t grp_floats = 0;
     {
       TnProblem pr[13];   // (only the shapes are read here)
@@ -186,7 +186,7 @@ static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
       for (int tt = 1; tt <= T; ++tt)
         grp_floats = std::max(grp_floats, gemm_tn_group_slab_floats(pr, n, tt * B));
     }
-    p->slab2 = std::max(sl2, grp_floats);
+    p->ws[1] = std::max(sl2, grp_floats);
     const int rowsH = H * B, rowsT = T * B;
     const int shapes[][3] = {{K, M, rowsH},      {M, R, rowsH},      {4 * R, M, rowsH},
                              {4 * R, R, rowsH},  {M, S, rowsH},      {S, R, rowsH},
@@ -196,21 +196,19 @@ static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
     // the slab (a quarter to a sixth), whatever its output width (4R, 4Rq, K, Q, M, A or S)
     size_t sl = (size_t)16 * B * std::max({4 * R, 4 * Rq, K, Q, M, A, S});
     for (auto& sh : shapes) sl = std::max(sl, gemm_tn_slab_floats(sh[0], sh[1], sh[2]));
-    p->slab = sl;
+    p->ws[0] = sl;
     // the weight-gradient stream's workspace also holds the grouped launches' partial slabs
-    p->slab3 = std::max(sl, grp_floats);
+    p->ws[2] = std::max(sl, grp_floats);
   }
 }
 // the launch decisions of `p` become the context's (the workspaces are the caller's business)
 static void adopt_plan(rau_ctx* ctx, const BatchPlan& p) {
   ctx->groups = p.groups;
   for (int i = 0; i < 5; ++i) ctx->mcount[i] = p.mcount[i];
-  ctx->att_split_env = p.att_split;
+  ctx->att_split = p.att_split;
   ctx->enc_ws = p.enc_ws;
   ctx->enc_ws_train = p.enc_ws_train;
-  ctx->slab_floats = p.slab;
-  ctx->slab2_floats = p.slab2;
-  ctx->slab3_floats = p.slab3;
+  for (int i = 0; i < 3; ++i) stream_ws(ctx)[i]->floats = p.ws[i];
 }
 
 // ================================================================== C ABI
@@ -333,6 +331,8 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
     hipDeviceGetStreamPriorityRange(&plo, &phi);
     hipStreamCreateWithPriority(&ctx->st3, hipStreamNonBlocking, plo);
   }
+  const hipStream_t owners[3] = {ctx->st, ctx->st2, ctx->st3};
+  for (int i = 0; i < 3; ++i) stream_ws(ctx)[i]->owner = owners[i];
   ctx->cap = c.B;
   {
     if (const char* eg = std::getenv("RAU_BWD_GROUPS")) {
@@ -526,23 +526,17 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   CK(dalloc(ctx, &ctx->dqt, HB * M));
   CK(dalloc(ctx, &ctx->dQD, HB * Q));
   CK(dalloc(ctx, &ctx->dq, (size_t)B * Q));
-  {
-    // split-K workspaces: one per stream (plan_batch)
-    CK(dalloc(ctx, &ctx->slab2, plan.slab2));
-    CK(dalloc(ctx, &ctx->slab, plan.slab));
-    CK(dalloc(ctx, &ctx->slab3, plan.slab3));
-    ctx->slab_alloc = plan.slab;
-    ctx->slab2_alloc = plan.slab2;
-    ctx->slab3_alloc = plan.slab3;
-    // every consumer of K-split partials checks the span it is about to read against these (split_guard.hip)
-    split_ws_register(ctx->slab, ctx->slab_floats);
-    split_ws_register(ctx->slab2, ctx->slab2_floats);
-    split_ws_register(ctx->slab3, ctx->slab3_floats);
+  for (StreamWs* w : stream_ws(ctx)) {
+    // split-K workspaces: one per stream (plan_batch); every consumer of K-split partials checks the span it is
+    // about to read against these (split_guard.hip)
+    CK(dalloc(ctx, &w->slab, w->floats));
+    w->alloc = w->floats;
+    split_ws_register(w->slab, w->floats);
   }
   {
     const int widest = std::max({4 * R, 4 * Rq, K, M, S, A, Q});
-    CK(dalloc(ctx, &ctx->coltmp3, (size_t)32 * widest));
-    CK(dalloc(ctx, &ctx->coltmp2, (size_t)32 * widest));      // the bulk stream's column-sum scratch
+    CK(dalloc(ctx, &ctx->ws_side.coltmp, (size_t)32 * widest));
+    CK(dalloc(ctx, &ctx->ws_bulk.coltmp, (size_t)32 * widest));
     CK(dalloc(ctx, &ctx->dbi_part, (size_t)H * B * M));       // per-sample row sums of dZ
     CK(dalloc(ctx, &ctx->tmpS, (size_t)S));
   }
@@ -577,9 +571,7 @@ void rau_destroy(rau_ctx* ctx) {
   if (ctx->st2) hipStreamSynchronize(ctx->st2);
   if (ctx->st3) hipStreamSynchronize(ctx->st3);
   for (auto& g : ctx->graphs) hipGraphExecDestroy(g.second);
-  split_ws_unregister(ctx->slab);
-  split_ws_unregister(ctx->slab2);
-  split_ws_unregister(ctx->slab3);
+  for (StreamWs* w : stream_ws(ctx)) split_ws_unregister(w->slab);
   rau_bank_destroy(ctx);
   for (void* p : ctx->allocs) hipFree(p);
   if (ctx->hopw_h) hipHostFree(ctx->hopw_h);
@@ -762,9 +754,6 @@ int rau_batch_size(rau_ctx* ctx, int32_t* n, int32_t* capacity) {
 
 // A split-K workspace the new size needs more of than is there (the needs are not monotonic in the batch size:
 // the split counts are chosen per shape): a second allocation, swapped in once all of them have succeeded.
-namespace {
-struct Regrow { float** ptr; size_t* have; size_t need; float* fresh; };
-}
 int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   NEED(ctx, "null ctx");
   NEED(n >= 1 && n <= ctx->cap, "rau_set_batch_size: n=%d out of [1,%d] (the B of rau_create)", n, ctx->cap);
@@ -773,18 +762,17 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   BatchPlan plan;
   plan_batch(ctx, n, &plan);
   // ---- allocate first: a failure leaves the context at the old size
-  Regrow grow[3] = {{&ctx->slab, &ctx->slab_alloc, plan.slab, nullptr},
-                    {&ctx->slab2, &ctx->slab2_alloc, plan.slab2, nullptr},
-                    {&ctx->slab3, &ctx->slab3_alloc, plan.slab3, nullptr}};
-  for (Regrow& g : grow) {
-    if (g.need <= *g.have) continue;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&g.fresh), g.need * sizeof(float));
+  const auto wss = stream_ws(ctx);
+  float* fresh[3] = {nullptr, nullptr, nullptr};
+  for (int i = 0; i < 3; ++i) {
+    if (plan.ws[i] <= wss[i]->alloc) continue;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&fresh[i]), plan.ws[i] * sizeof(float));
     if (e != hipSuccess) {
       (void)hipGetLastError();
-      for (Regrow& u : grow)
-        if (u.fresh) hipFree(u.fresh);
+      for (float* f : fresh)
+        if (f) hipFree(f);
       return fail(RAU_ERR_NOMEM, "rau_set_batch_size: hipMalloc(%zu bytes of split-K workspace) failed: %s; the "
-                  "context keeps %d samples", g.need * sizeof(float), hipGetErrorString(e), ctx->cfg.B);
+                  "context keeps %d samples", plan.ws[i] * sizeof(float), hipGetErrorString(e), ctx->cfg.B);
     }
   }
   // ---- nothing may still read or write what is about to change: all four streams drain (pending uploads of
@@ -796,30 +784,28 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
     ctx->persist_gave_up = true;
     plan.enc_ws = plan.enc_ws_train = false;
   }
-  for (Regrow& g : grow) {
-    if (!g.fresh) continue;
+  for (int i = 0; i < 3; ++i) {
+    if (!fresh[i]) continue;
     // captured steps hold the old workspace's address: all of them go (they are recaptured on demand)
     for (auto& gr : ctx->graphs) hipGraphExecDestroy(gr.second);
     ctx->graphs.clear();
-    split_ws_unregister(*g.ptr);
-    void* old = *g.ptr;
+    split_ws_unregister(wss[i]->slab);
+    void* old = wss[i]->slab;
     hipFree(old);
     ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), old), ctx->allocs.end());
     ctx->scratch.erase(std::remove_if(ctx->scratch.begin(), ctx->scratch.end(),
                                       [&](const std::pair<void*, size_t>& r) { return r.first == old; }),
                        ctx->scratch.end());
-    ctx->allocs.push_back(g.fresh);
-    ctx->scratch.push_back({g.fresh, g.need * sizeof(float)});
-    *g.ptr = g.fresh;
-    *g.have = g.need;
+    ctx->allocs.push_back(fresh[i]);
+    ctx->scratch.push_back({fresh[i], plan.ws[i] * sizeof(float)});
+    wss[i]->slab = fresh[i];
+    wss[i]->alloc = plan.ws[i];
   }
   // ---- the switch: shapes, launch policy, and the fail-closed guard's picture of the workspaces (the spans a
   // context of n samples would have registered; the allocations behind them are at least that large)
   ctx->cfg.B = n;
   adopt_plan(ctx, plan);
-  split_ws_register(ctx->slab, ctx->slab_floats);
-  split_ws_register(ctx->slab2, ctx->slab2_floats);
-  split_ws_register(ctx->slab3, ctx->slab3_floats);
+  for (StreamWs* w : wss) split_ws_register(w->slab, w->floats);
   // ---- every layout is dense in n, so what the old size left behind now lies where the step counts on the zeros
   // of a fresh context (the initial-state rows of c1 / h1 / c2 / h2, the pad columns of 7x7 maps, workspaces whose
   // tails are read as zeros): all batch-dependent storage is cleared, which is what rau_create leaves
@@ -873,8 +859,9 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
   // Split-K partials of several of these GEMMs are summed by their CONSUMER kernel instead of a
   // reduce launch (each launch on this dependent chain costs 8-20 us next to the bulk GEMMs):
   // the slab is carved into four regions so that partials can stay alive side by side.
-  const size_t reg = ctx->slab_floats / 4;
-  float *slab_u = ctx->slab + reg, *slab_t = ctx->slab + 2 * reg;
+  const StreamWs& ws = ctx->ws_chain;
+  const size_t reg = ws.floats / 4;
+  float *slab_u = ws.slab + reg, *slab_t = ws.slab + 2 * reg;
   int ns_u = 0, ns_t = 0, ns_i = 0;
   size_t off[3];
   {  // the three Linears fed by h_prev alone -- q_embed's recurrent half (SS:234), attbymemory
@@ -882,7 +869,7 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
     const float* Wt[3] = {ctx->h_proj.W, ctx->att_mem.W, ctx->lstm_h2h.W};
     const int Nt[3] = {M, SL, 4 * R};
     RUN("small_gemm", gflop(B, M + SL + 4 * R, R), 0,
-        gemm_nt_hetero_deferred(st, 3, B, R, hp, R, Wt, R, Nt, slab_t, reg + reg / 2, &ns_t, off));
+        gemm_nt_hetero_deferred(st, lin_mode(ctx), 3, B, R, hp, R, Wt, R, Nt, slab_t, reg + reg / 2, &ns_t, off));
   }
   float *slab_z = slab_t + off[1], *slab_g = slab_t + off[2];
   {  // qf = tanh(Yq + h_prev Wh^T): the q half (with both biases) was computed for all hops at once
@@ -893,7 +880,7 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
     RUN("lin_reduce", 0, 0, lin_reduce_epilogue(st, B, M, ns_t, slab_t + off[0], qf, M, o));
   }
   {  // attbycontent SS:244-252: u = qf Wa^T (+ ba inside att_fwd_fused)
-    LinOpts o;
+    LinOpts o = lin_opts(ctx, ws);
     o.slab = slab_u; o.slab_floats = reg; o.defer_splits = &ns_u;
     RUN("small_gemm", gflop(B, A, M), 0, gemm_nt(st, B, A, M, qf, M, ctx->att_q.W, M, ctx->u, A, o));
   }
@@ -909,7 +896,7 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
     // fits and streams a sample faster (B = 256: 124.2 -> 129.5 k QA/s); the training step keeps 8
     ap.waves = ctx->mode == RAU_MODE_EVAL ? 16 : 0;
     ap.img = img;   // image table: Pin and Ih hold one tile per image, sample b reads row img[b]
-    if (!(ctx->att_split_env))
+    if (!ctx->att_split)
       RUN("att_fwd_fused", 2.0 * B * S * (A + M), ((double)B * A * S + BM_ * S) * 4,
           att_fwd_fused(st, B, M, A, S, Pin, slab_u, ctx->att_score.W, ctx->att_score.b, slab_z, Ih, qf,
                         nullptr, ah, ctx->jv, ap));
@@ -919,7 +906,7 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
                         ah, ctx->jv, ctx->att_part, ap));
   }
   {  // classifier SS:265-283
-    LINOPTS(o);
+    LinOpts o = lin_opts(ctx, ws);
     o.slab_floats = reg;
     o.bias = ctx->feat_attprob.b;
     o.addend = ctx->jv;
@@ -927,7 +914,7 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
     RUN("small_gemm", gflop(B, M, SL), 0, gemm_nt(st, B, M, SL, ah, S, ctx->feat_attprob.W, SL, jh, M, o));
   }
   {  // j Wx^T partials right behind the recurrent ones; the cell kernel sums both + both biases
-    LinOpts o;
+    LinOpts o = lin_opts(ctx, ws);
     o.slab = slab_g + (size_t)ns_h * B * 4 * R; o.slab_floats = reg / 2; o.defer_splits = &ns_i;
     RUN("small_gemm", gflop(B, 4 * R, M), 0,
         gemm_nt(st, B, 4 * R, M, jh, M, ctx->lstm_i2h.W, M, g4, 4 * R, o));
@@ -946,10 +933,11 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
 
 // merge_feat = dropout(j + h' Wo^T + bo), logits = merge_feat Wc^T + bc, do_pred, cross-entropy +
 // first-max argmax for hops [h0, h0 + nh): rows = nh * B.  h' rows are ctx->hh slots h0+1 .. (the
-// chain's h_out), `ws` a split-K workspace of >= 2 regions of `reg` floats owned by stream `s`.
-int hop_forward_head(rau_ctx* ctx, hipStream_t s, float* ws, size_t reg, int h0, int nh,
-                     const int32_t* labels) {
+// chain's h_out); it runs on ws.owner and uses the first two quarters of that stream's split-K workspace.
+int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const int32_t* labels) {
   const rau_config& c = ctx->cfg;
+  hipStream_t s = ws.owner;
+  const size_t reg = ws.floats / 4;
   const int B = c.B, M = c.M, R = c.R, K = c.K;
   const bool tr = ctx->mode == RAU_MODE_TRAIN;
   const uint32_t* m_mf = (tr && mask_p(ctx, RAU_MASK_MF) > 0.f) ? ctx->mbits[RAU_MASK_MF] : nullptr;
@@ -962,8 +950,8 @@ int hop_forward_head(rau_ctx* ctx, hipStream_t s, float* ws, size_t reg, int h0,
   float* lg = ctx->logits + (size_t)h0 * B * K;
   int ns_c = 0;
   {
-    LinOpts o;
-    o.slab = ws; o.slab_floats = reg;
+    LinOpts o = lin_opts(ctx, ws);
+    o.slab_floats = reg;
     o.bias = ctx->lstm_out.b;
     o.addend = jh;
     o.add_rs = M;
@@ -974,15 +962,15 @@ int hop_forward_head(rau_ctx* ctx, hipStream_t s, float* ws, size_t reg, int h0,
          gemm_nt(s, rows, M, R, hnew, R, ctx->lstm_out.W, R, mfh, M, o));
   }
   {  // out_score SS:280: partials finished (+ bias) by the criterion-head kernel
-    LinOpts o;
-    o.slab = ws + reg; o.slab_floats = reg; o.defer_splits = &ns_c;
+    LinOpts o = lin_opts(ctx, ws);
+    o.slab = ws.slab + reg; o.slab_floats = reg; o.defer_splits = &ns_c;
     RUNS(s, "head_gemm", gflop(rows, K, M), 0,
          gemm_nt(s, rows, K, M, mfh, M, ctx->cls.W, M, lg, K, o));
   }
   RUNS(s, "ce_fwd", 0, (double)rows * K * 12,
        ce_fwd(s, rows, K, M, lg, labels, mfh, ctx->do_pred.W, ctx->do_pred.b,
               ctx->dl + (size_t)h0 * B * K, ctx->lossrow + (size_t)h0 * B,
-              ctx->argmax_d + (size_t)h0 * B, ctx->dopred + (size_t)h0 * B, ws + reg, ns_c,
+              ctx->argmax_d + (size_t)h0 * B, ctx->dopred + (size_t)h0 * B, ws.slab + reg, ns_c,
               ctx->cls.b, lg, B));
   return RAU_OK;
 }
@@ -992,8 +980,7 @@ int hop_forward(rau_ctx* ctx, int h, const float* cp, const float* hp, float* c_
   if (int rc = hop_forward_chain(ctx, h, cp, hp, c_out, h_out, Ih, Pin)) return rc;
   if (h_out != ctx->hh + (size_t)(h + 1) * ctx->cfg.B * ctx->cfg.R)
     return fail(RAU_ERR_INVALID, "hop_forward: h_out must be the ctx's hop slot");
-  const size_t reg = ctx->slab_floats / 4;
-  return hop_forward_head(ctx, ctx->st, ctx->slab, reg, h, 1, labels);
+  return hop_forward_head(ctx, ctx->ws_chain, h, 1, labels);
 }
 
 // Backward of hop_forward (hand-derived, SURVEY 8a "exact backward of one hop"): from the
@@ -1028,15 +1015,16 @@ int hop_backward(rau_ctx* ctx, int h, const float* cp, const float* Ih, const Ho
   float* duh = ctx->du + (size_t)h * B * A;
   float* dqt = ctx->dqt + (size_t)h * BM_;
   float* dc_out = g.dc_out;
-  // split-K workspace: region 0 = partials that are reduced right away (LINOPTS default) or
+  // split-K workspace: region 0 = partials that are reduced right away (lin_opts' default) or
   // consumed by the next kernel; regions 1..3 = this hop's dj partials followed by the dh_prev
   // partials, which live until the next hop's lstm_bwd has read them
-  const size_t reg = ctx->slab_floats / 4;
-  float* X = ctx->slab + reg;
+  const StreamWs& ws = ctx->ws_chain;
+  const size_t reg = ws.floats / 4;
+  float* X = ws.slab + reg;
   const size_t Xcap = 3 * reg;
   if (!g.dpre_ready) {
     {  // dmf = dlogits Wc ; dpre = dmf (.) mask   (do_pred grad is zero, SS:566)
-      LINOPTS(o);
+      LinOpts o = lin_opts(ctx, ws);
       o.slab_floats = reg;
       o.addend = g.dmf_add;   // module-level callers: gradient through do_pred (zero in feval)
       o.add_rs = M;
@@ -1048,13 +1036,13 @@ int hop_backward(rau_ctx* ctx, int h, const float* cp, const float* Ih, const Ho
     }
     // dhn = dpre Wo + dh_next, the K-split partials of dpre Wo summed inside lstm_bwd
     int nsp = 0;
-    LINOPTS(o);
+    LinOpts o = lin_opts(ctx, ws);
     o.slab_floats = reg;
     o.defer_splits = &nsp;
     RUN("small_gemm", gflop(B, R, M), 0, gemm_nn(st, B, R, M, dpre, M, ctx->lstm_out.W, R, ctx->dhn, R, o));
     RUN("lstm_bwd", 0, BR_ * 4.0 * 12,
         lstm_bwd(st, GATES_ATT, B, R, g4, cp, R, ctx->tc + (size_t)h * BR_, nullptr, R, g.dh_next,
-                 g.dc_next, dg4, dc_out, nullptr, 0, nullptr, nullptr, 0, ctx->slab, nsp));
+                 g.dc_next, dg4, dc_out, nullptr, 0, nullptr, nullptr, 0, ws.slab, nsp));
   } else {
     // dhn rows of this hop + the previous hop_backward's dh_prev partials (+ dh_next if given)
     RUN("lstm_bwd", 0, BR_ * 4.0 * 12,
@@ -1070,25 +1058,21 @@ int hop_backward(rau_ctx* ctx, int h, const float* cp, const float* Ih, const Ho
     const float* Ap[2] = {dg4, dg4};
     const float* Wp[2] = {ctx->lstm_i2h.W, ctx->lstm_h2h.W};
     RUN("small_gemm", 2 * gflop(B, M, 4 * R), 0,
-        gemm_nn_batched_deferred(st, 2, B, M, 4 * R, Ap, 4 * R, Wp, M, X, Xcap / 2, &ns_j));
+        gemm_nn_batched_deferred(st, lin_mode(ctx), 2, B, M, 4 * R, Ap, 4 * R, Wp, M, X, Xcap / 2, &ns_j));
     dhp = X + (size_t)ns_j * BM_;
     ns_h = ns_j;
-  } else if (dead) {
-    LinOpts o1;
-    o1.slab = X; o1.slab_floats = Xcap / 4; o1.defer_splits = &ns_j;
-    RUN("small_gemm", gflop(B, M, 4 * R), 0,
-        gemm_nn(st, B, M, 4 * R, dg4, 4 * R, ctx->lstm_i2h.W, M, djh, M, o1));
-    dhp = X + (size_t)ns_j * BM_;
   } else {
-    LinOpts o1;
+    LinOpts o1 = lin_opts(ctx, ws);
     o1.slab = X; o1.slab_floats = Xcap / 4; o1.defer_splits = &ns_j;
     RUN("small_gemm", gflop(B, M, 4 * R), 0,
         gemm_nn(st, B, M, 4 * R, dg4, 4 * R, ctx->lstm_i2h.W, M, djh, M, o1));
     dhp = X + (size_t)ns_j * BM_;
-    LinOpts o2;
-    o2.slab = dhp; o2.slab_floats = Xcap / 4; o2.defer_splits = &ns_h;
-    RUN("small_gemm", gflop(B, R, 4 * R), 0,
-        gemm_nn(st, B, R, 4 * R, dg4, 4 * R, ctx->lstm_h2h.W, R, nullptr, R, o2));
+    if (!dead) {
+      LinOpts o2 = lin_opts(ctx, ws);
+      o2.slab = dhp; o2.slab_floats = Xcap / 4; o2.defer_splits = &ns_h;
+      RUN("small_gemm", gflop(B, R, 4 * R), 0,
+          gemm_nn(st, B, R, 4 * R, dg4, 4 * R, ctx->lstm_h2h.W, R, nullptr, R, o2));
+    }
   }
   {  // dj = dpre + sum of partials
     LinOpts o;
@@ -1098,29 +1082,29 @@ int hop_backward(rau_ctx* ctx, int h, const float* cp, const float* Ih, const Ho
   }
   int ns_a = 0;
   {  // da = dj Wf  (+ attselect term and the gradient at the attprob OUTPUT inside att_bwd_fused)
-    LINOPTS(o);
+    LinOpts o = lin_opts(ctx, ws);
     o.slab_floats = reg;
     o.defer_splits = &ns_a;
     RUN("small_gemm", gflop(B, SL, M), 0,
         gemm_nn(st, B, SL, M, djh, M, ctx->feat_attprob.W, SL, ctx->da_lin, S, o));
   }
-  if (!(ctx->att_split_env))
+  if (!ctx->att_split)
     RUN("att_bwd_fused", 2.0 * B * S * (A + M), ((double)B * A * S * 2 + BM_ * S) * 4,
-        att_bwd_fused(st, B, M, A, S, Ih, djh, ah, ctx->slab, ctx->att_score.W, Th, dzh, duh,
+        att_bwd_fused(st, B, M, A, S, Ih, djh, ah, ws.slab, ctx->att_score.W, Th, dzh, duh,
                       ctx->dwsp + (size_t)h * B * A, ctx->I_shared ? ctx->P0 : Th,
                       ctx->u + (size_t)h * B * A, ns_a, SL, g.da_out,
                       ctx->ds16_step ? (void*)((uint16_t*)ctx->dS16 + (size_t)h * B * A * S) : nullptr,
                       ctx->bf16 ? 8 : 0));
   else
     RUN("att_bwd_split", 2.0 * B * S * (A + M), ((double)B * A * S * 2 + BM_ * S) * 4,
-        att_bwd_split(st, B, M, A, S, Ih, djh, ah, ctx->slab, ctx->att_score.W, Th, dzh, duh,
+        att_bwd_split(st, B, M, A, S, Ih, djh, ah, ws.slab, ctx->att_score.W, Th, dzh, duh,
                       ctx->dwsp + (size_t)h * B * A, ctx->I_shared ? ctx->P0 : Th,
                       ctx->u + (size_t)h * B * A, ctx->att_part, ns_a, SL, g.da_out));
   if (g.ev_conv_ready) HIPC(hipEventRecord(g.ev_conv_ready, st));
   const size_t used = (size_t)(dhp - X);
   if (!dead) {  // dh_prev partials #2 = dz Wm
     int ns = 0;
-    LinOpts o;
+    LinOpts o = lin_opts(ctx, ws);
     o.slab = dhp + (size_t)ns_h * BR_;
     o.slab_floats = (Xcap - used) / 3;
     o.defer_splits = &ns;
@@ -1128,7 +1112,7 @@ int hop_backward(rau_ctx* ctx, int h, const float* cp, const float* Ih, const Ho
     ns_h += ns;
   }
   {  // dq~ = (dj + du Wa) (1 - qf^2)
-    LINOPTS(o);
+    LinOpts o = lin_opts(ctx, ws);
     o.slab_floats = reg;
     o.addend = djh;
     o.add_rs = M;
@@ -1138,7 +1122,7 @@ int hop_backward(rau_ctx* ctx, int h, const float* cp, const float* Ih, const Ho
   }
   if (!dead) {  // dh_prev partials #3 = dq~ Wh
     int ns = 0;
-    LinOpts o;
+    LinOpts o = lin_opts(ctx, ws);
     o.slab = dhp + (size_t)ns_h * BR_;
     o.slab_floats = (Xcap - used) / 3;
     o.defer_splits = &ns;
@@ -1159,7 +1143,7 @@ extern "C" {
 
 // ================================================================ forward
 // The forward / backward seam (the bulk stream and the matrix pipes wait there for the chain).  RAU_SEAM=<mask>
-// (A/B, DESIGN.md section 9; default 3): 1 = a train-mode forward with labels also forms the backward's two
+// (A/B, DESIGN.md section 8; default 3): 1 = a train-mode forward with labels also forms the backward's two
 // recurrence-free head products (dpre, dhn) behind each group's criterion head on the third stream;
 // 2 = a group's conv gradients start behind att_bwd of its first hop instead of behind the hop's last launch.
 static int seam_mask() {
@@ -1175,7 +1159,6 @@ int rau_forward(rau_ctx* ctx) {
   BatchSlot& bs = cur_batch(ctx);
   if (!bs.held.have) return fail(RAU_ERR_STATE, "rau_forward: no batch (call rau_set_batch)");
   ctx->mg_valid = false;   // the hop outputs are being overwritten
-  set_skinny_policy(ctx);
   const rau_config& c = ctx->cfg;
   const int B = c.B, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R,
             H = c.H, Q = ctx->Q;
@@ -1219,7 +1202,7 @@ int rau_forward(rau_ctx* ctx) {
     // (idle in the forward pass) and the wavefront waits for it where it first reads it.
     const int t_head = (!ws_path && side_split(ctx) && TL > kEncHeadTokens) ? kEncHeadTokens : TL;
     {
-      LINOPTS(o);
+      LinOpts o = lin_opts(ctx, ctx->ws_chain);
       o.bias = ctx->i2h[0].b;
       o.bias2 = ctx->h2h[0].b;
       RUN("enc_i2h_gemm", gflop(t_head * B, 4 * Rq, E), 0,
@@ -1228,8 +1211,7 @@ int rau_forward(rau_ctx* ctx) {
     if (t_head < TL) {
       HIPC(hipEventRecord(ctx->evG0, st));            // embed_fwd is done
       HIPC(hipStreamWaitEvent(ctx->st3, ctx->evG0, 0));
-      LinOpts o;
-      o.slab = ctx->slab3; o.slab_floats = ctx->slab3_floats;
+      LinOpts o = lin_opts(ctx, ctx->ws_side);
       o.bias = ctx->i2h[0].b;
       o.bias2 = ctx->h2h[0].b;
       // in chunks, so that the recurrence only ever waits for the rows it is about to read
@@ -1280,14 +1262,14 @@ int rau_forward(rau_ctx* ctx) {
       int nsp = 0;
       if (nb > 0)
         RUN("enc_h2h_gemm", gflop(B, 4 * Rq, Rq) * nb, 0,
-            gemm_nt_batched_deferred(st, nb, B, 4 * Rq, Rq, Ap, Rq, Wp, Rq, ctx->slab,
-                                     ctx->slab_floats, &nsp));
+            gemm_nt_batched_deferred(st, lin_mode(ctx), nb, B, 4 * Rq, Rq, Ap, Rq, Wp, Rq, ctx->ws_chain.slab,
+                                     ctx->ws_chain.floats, &nsp));
       LstmFwdCells cells{};
       if (s <= TL) {  // layer-1 cell t = s
         LstmFwdCell& C1 = cells.c[cells.n++];
         C1.g4 = ctx->G1 + (size_t)(s - 1) * G4;
         C1.has_input = 1;
-        C1.slab = i0 >= 0 ? ctx->slab + (size_t)i0 * nsp * G4 : nullptr;
+        C1.slab = i0 >= 0 ? ctx->ws_chain.slab + (size_t)i0 * nsp * G4 : nullptr;
         C1.nsplit = i0 >= 0 ? nsp : 0;
         C1.c_prev = ctx->c1 + (size_t)(s - 1) * BRq; C1.cp_rs = Rq;
         C1.c = ctx->c1 + (size_t)s * BRq; C1.c_rs = Rq;
@@ -1302,7 +1284,7 @@ int rau_forward(rau_ctx* ctx) {
         C2.g4 = ctx->G2 + (size_t)(t - 1) * G4;
         C2.has_input = 0;
         C2.b1 = ctx->i2h[1].b; C2.b2 = ctx->h2h[1].b;
-        C2.slab = ctx->slab + (size_t)i1 * nsp * G4;      // x2 W_i2h2^T then h2 W_h2h2^T partials
+        C2.slab = ctx->ws_chain.slab + (size_t)i1 * nsp * G4;      // x2 W_i2h2^T then h2 W_h2h2^T partials
         C2.nsplit = i2 >= 0 ? 2 * nsp : nsp;
         C2.c_prev = ctx->c2 + (size_t)(t - 1) * BRq; C2.cp_rs = Rq;
         C2.c = ctx->c2 + (size_t)t * BRq; C2.c_rs = Rq;
@@ -1418,7 +1400,7 @@ int rau_forward(rau_ctx* ctx) {
     // with dropout: hop 0's rows here, the other hops' rows on the weight-gradient stream (hop 1 waits)
     q_split = !ctx->yq_shared && side_split(ctx) && H > 1;
     const int qrows = (ctx->yq_shared || q_split) ? B : H * B;
-    LINOPTS(o);
+    LinOpts o = lin_opts(ctx, ctx->ws_chain);
     o.bias = ctx->q_proj.b;
     o.bias2 = ctx->h_proj.b;
     RUN("q_proj_gemm", gflop(qrows, M, Q), 0,
@@ -1427,8 +1409,7 @@ int rau_forward(rau_ctx* ctx) {
   if (q_split) {
     HIPC(hipEventRecord(ctx->evQ0, st));            // qd is complete
     HIPC(hipStreamWaitEvent(ctx->st3, ctx->evQ0, 0));
-    LinOpts o;
-    o.slab = ctx->slab3; o.slab_floats = ctx->slab3_floats;
+    LinOpts o = lin_opts(ctx, ctx->ws_side);
     o.bias = ctx->q_proj.b;
     o.bias2 = ctx->h_proj.b;
     RUNS(ctx->st3, "q_proj_gemm", gflop((H - 1) * B, M, Q), 0,
@@ -1443,8 +1424,8 @@ int rau_forward(rau_ctx* ctx) {
   HIPC(hipMemsetAsync(ctx->cc, 0, BR_ * sizeof(float), st));  // att_c, att_h zeros SS:362-365
   HIPC(hipMemsetAsync(ctx->hh, 0, BR_ * sizeof(float), st));
   const int32_t* labels = bs.held.have_labels ? bs.labels_d : nullptr;
-  const size_t reg3 = ctx->slab3_floats / 4;
-  const int head_max = (int)std::max<size_t>(1, reg3 / ((size_t)B * c.K));  // rows the logits slab holds
+  // rows the logits region of the head's workspace holds (hop_forward_head: a quarter of the side stream's slab)
+  const int head_max = (int)std::max<size_t>(1, ctx->ws_side.floats / 4 / ((size_t)B * c.K));
   int gstart = 0;
   for (int h = 0; h < H; ++h) {
     if (gsz[h]) {
@@ -1465,8 +1446,7 @@ int rau_forward(rau_ctx* ctx) {
       HIPC(hipEventRecord(ctx->evH[h], st));
       HIPC(hipStreamWaitEvent(ctx->st3, ctx->evH[h], 0));
       for (int h0 = gstart; h0 <= h; h0 += head_max)
-        if (int rc = hop_forward_head(ctx, ctx->st3, ctx->slab3, reg3, h0,
-                                      std::min(head_max, h + 1 - h0), labels))
+        if (int rc = hop_forward_head(ctx, ctx->ws_side, h0, std::min(head_max, h + 1 - h0), labels))
           return rc;
       if (head_dgrad_fwd(ctx)) {
         // The backward's first two products do not depend on the recurrence either: dpre = (dl Wc) (.) mask
@@ -1476,16 +1456,14 @@ int rau_forward(rau_ctx* ctx) {
         // products are linear in it, so rau_backward scales dl, dpre and dhn together.
         const int nh = h + 1 - gstart;
         const bool trm = ctx->mode == RAU_MODE_TRAIN;
-        LinOpts o;
-        o.slab = ctx->slab3; o.slab_floats = ctx->slab3_floats;
+        LinOpts o = lin_opts(ctx, ctx->ws_side);
         o.emask = (trm && mask_p(ctx, RAU_MASK_MF) > 0.f) ? ctx->mbits[RAU_MASK_MF] : nullptr;
         o.emask_e0 = (size_t)gstart * BM_;
         o.emscale = 1.f / (1.f - mask_p(ctx, RAU_MASK_MF));
         RUNS(ctx->st3, "head_dgrad", 2.0 * nh * B * M * c.K, 0,
              gemm_nn(ctx->st3, nh * B, M, c.K, ctx->dl + (size_t)gstart * B * c.K, c.K, ctx->cls.W, M,
                      ctx->dpre + (size_t)gstart * BM_, M, o));
-        LinOpts o2;
-        o2.slab = ctx->slab3; o2.slab_floats = ctx->slab3_floats;
+        const LinOpts o2 = lin_opts(ctx, ctx->ws_side);
         RUNS(ctx->st3, "head_dgrad", 2.0 * nh * B * R * M, 0,
              gemm_nn(ctx->st3, nh * B, R, M, ctx->dpre + (size_t)gstart * BM_, M, ctx->lstm_out.W, R,
                      ctx->dhn + (size_t)gstart * BR_, R, o2));
@@ -1528,7 +1506,6 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
     return fail(RAU_ERR_STATE, "rau_backward: the evaluate-mode forward of a batch with an image table computed "
                 "i_embed once per image, so there is no per-sample I to differentiate; take evaluate-mode "
                 "gradients on a plain batch (rau_set_batch)");
-  set_skinny_policy(ctx);
   const BatchSlot& bs = cur_batch(ctx);
   if (!bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_backward: batch has no labels");
   const rau_config& c = ctx->cfg;
@@ -1577,13 +1554,13 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
   // Off the recurrence: dpre = (dl Wc) (.) mask and dhn = dpre Wo for all active hops at once
   const uint32_t* m_mf = mk(RAU_MASK_MF);
   if (HA > 0 && !ctx->dpre_fwd) {
-    LINOPTS(o);
+    LinOpts o = lin_opts(ctx, ctx->ws_chain);
     o.emask = m_mf;
     o.emask_e0 = 0;
     o.emscale = sc(RAU_MASK_MF);
     RUN("head_dgrad", gflop(HA * B, M, K), 0,
         gemm_nn(st, HA * B, M, K, ctx->dl, K, ctx->cls.W, M, ctx->dpre, M, o));
-    LINOPTS(o2);
+    const LinOpts o2 = lin_opts(ctx, ctx->ws_chain);
     RUN("head_dgrad", gflop(HA * B, R, M), 0,
         gemm_nn(st, HA * B, R, M, ctx->dpre, M, ctx->lstm_out.W, R, ctx->dhn, R, o2));
   }
@@ -1591,7 +1568,7 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
   float* dh_part = nullptr;        // gradient at next_h: K-split partials left by the previous hop
   int dh_part_ns = 0;
   // bf16 mode, train-mode step on 14x14 maps: dS goes out as bf16 (its consumers below read that)
-  ctx->ds16_step = ctx->dS16 && !ctx->I_shared && !ctx->att_split_env && conv_dz_fused_ok(S, M, ctx->bf16);
+  ctx->ds16_step = ctx->dS16 && !ctx->I_shared && !ctx->att_split && conv_dz_fused_ok(S, M, ctx->bf16);
   struct Ds16Reset { rau_ctx* c; ~Ds16Reset() { c->ds16_step = false; } } ds16_reset{ctx};
   bool dq_side = false;
   int dq_rows_left = HA;           // hops [0, dq_rows_left) whose dq term this stream still owes
@@ -1626,8 +1603,7 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
       const int nh = std::min(h + gsz[h], HA) - h;
       HIPC(hipEventRecord(ctx->evK[h], st));
       HIPC(hipStreamWaitEvent(ctx->st3, ctx->evK[h], 0));
-      LinOpts o;
-      o.slab = ctx->slab3; o.slab_floats = ctx->slab3_floats;
+      const LinOpts o = lin_opts(ctx, ctx->ws_side);
       RUNS(ctx->st3, "q_proj_dgrad", gflop(nh * B, Q, M), 0,
            gemm_nn(ctx->st3, nh * B, Q, M, ctx->dqt + (size_t)h * BM_, M, ctx->q_proj.W, Q,
                    ctx->dQD + (size_t)h * B * Q, Q, o));
@@ -1642,6 +1618,7 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
     // dZ = (Wp^T dS + dj (x) a)(1 - I^2); dWp += dS I^T; dWi += dZ X'^T.
     if (gsz[h]) {   // h is the first hop of its group: the whole group's attention backward is done
       hipStream_t sb = ctx->st2;
+      float* slab_b = ctx->ws_bulk.slab;   // the bulk stream's split-K workspace
       if (!(seam_mask() & 2)) HIPC(hipEventRecord(ctx->evK[h], st));
       HIPC(hipStreamWaitEvent(sb, ctx->evK[h], 0));   // recorded inside hop_backward (ev_conv_ready)
       if (!ctx->I_shared) {
@@ -1667,32 +1644,32 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
                ((double)nH * A * S + 2.0 * nH * M * S) * 4,
                conv_att_dgrad(sb, nH, M, S, A, ctx->T + hb * A * S, ctx->att_i.W, ctx->dj + hb * M,
                               ctx->a + hb * S, ctx->dZ + hb * M * S, ctx->bf16));
-        {   // RAU_BULK2: the att_i weight gradient (independent of dZ) on the second bulk stream
+        {   // the att_i weight gradient (independent of dZ)
           if (ctx->ds16_step)
             RUNS(sb, "conv_att_wgrad", gflop(A, M, (double)nH * S),
                  (double)nH * A * S * 2 + (double)nH * M * S * 4,
                  conv_att_wgrad_ds16(sb, nH, M, S, A, (const uint16_t*)ctx->dS16 + hb * A * S,
-                                     ctx->I + hb * M * S, ctx->att_i.dW, ctx->slab2));
+                                     ctx->I + hb * M * S, ctx->att_i.dW, slab_b));
           else
           RUNS(sb, "conv_att_wgrad", gflop(A, M, (double)nH * S),
                ((double)nH * A * S + (double)nH * M * S) * 4,
                conv_att_wgrad(sb, nH, M, S, A, ctx->T + hb * A * S, ctx->I + hb * M * S,
-                              ctx->att_i.dW, ctx->slab2, ctx->bf16));
+                              ctx->att_i.dW, slab_b, ctx->bf16));
         }
         if (ctx->xd16 && dzf)
           RUNS(sb, "conv_embed_wgrad", gflop(M, D, (double)nH * S),
                (double)nH * M * S * 2 + (double)nH * D * S * 2,
                conv_embed_wgrad_b16(sb, nH, D, S, M, (const uint16_t*)ctx->dZ + hb * M * S,
-                                    (const uint16_t*)ctx->xd16 + hb * D * S, ctx->i_embed.dW, ctx->slab2));
+                                    (const uint16_t*)ctx->xd16 + hb * D * S, ctx->i_embed.dW, slab_b));
         else
           RUNS(sb, "conv_embed_wgrad", gflop(M, D, (double)nH * S),
                ((double)nH * M * S * (dzf ? 1 : 2) + (double)nH * D * S) * 4,
                conv_embed_wgrad(sb, nH, D, S, M, ctx->dZ + hb * M * S, ctx->I + hb * M * S,
-                                  ctx->xd + hb * D * S, ctx->i_embed.dW, ctx->slab2, ctx->bf16,
+                                  ctx->xd + hb * D * S, ctx->i_embed.dW, slab_b, ctx->bf16,
                                   ctx->i_embed.db, dzf));
         if (dzf && h == 0)   // last group: i_embed bias gradient = column sums of the per-sample rows
           RUNS(sb, "colsum", 0, (double)HA * B * M * 4,
-               colsum_acc(sb, HA * B, M, ctx->dbi_part, M, ctx->i_embed.db, ctx->coltmp2));
+               colsum_acc(sb, HA * B, M, ctx->dbi_part, M, ctx->i_embed.db, ctx->ws_bulk.coltmp));
       } else {
         for (int hh2 = 0; hh2 < HA; ++hh2) {  // evaluate mode: I (and X) shared by all hops
           float* Th2 = ctx->T + (size_t)hh2 * B * A * S;
@@ -1701,16 +1678,16 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
                conv_att_dgrad(sb, B, M, S, A, Th2, ctx->att_i.W, ctx->dj + (size_t)hh2 * BM_,
                               ctx->a + (size_t)hh2 * BS_, dZh, ctx->bf16));
           RUNS(sb, "conv_att_wgrad", gflop(A, M, (double)B * S), ((double)B * A * S + BM_ * S) * 4,
-               conv_att_wgrad(sb, B, M, S, A, Th2, ctx->I, ctx->att_i.dW, ctx->slab2, ctx->bf16));
+               conv_att_wgrad(sb, B, M, S, A, Th2, ctx->I, ctx->att_i.dW, slab_b, ctx->bf16));
           RUNS(sb, "conv_embed_wgrad", gflop(M, D, (double)B * S), (BM_ * S + (double)B * D * S) * 4,
-               conv_embed_wgrad(sb, B, D, S, M, dZh, ctx->I, ctx->xw, ctx->i_embed.dW, ctx->slab2,
+               conv_embed_wgrad(sb, B, D, S, M, dZh, ctx->I, ctx->xw, ctx->i_embed.dW, slab_b,
                                 ctx->bf16, ctx->i_embed.db));
         }
       }
     }
   }
   {  // dq = sum_h (dq~_h Wq) (.) mask_h     (ConcatTable backward, SS:579)
-    LINOPTS(o);
+    const LinOpts o = lin_opts(ctx, ctx->ws_chain);
     if (dq_rows_left > 0)
       RUN("q_proj_dgrad", gflop(dq_rows_left * B, Q, M), 0,
           gemm_nn(st, dq_rows_left * B, Q, M, ctx->dqt, M, ctx->q_proj.W, Q, ctx->dQD, Q, o));
@@ -1737,12 +1714,13 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
   // last conv gradient (round 4: 9.43 -> 9.38 ms with dgrad_dma.hip; conv_att_dgrad 0.47 -> 0.54 and
   // conv_att_wgrad 0.57 -> 0.60 of peak in the step).  The encoder group's GEMM (after the BPTT) measured
   // the same on either stream and stays on the third.  RAU_WG_BULK=<mask> overrides (A/B, DESIGN.md section
-  // 9): 1 = mult group on the bulk stream, 2 = encoder group too.  Not with the side-stream split (the
-  // third stream's split-K workspace would be shared).
+  // 8): 1 = mult group on the bulk stream, 2 = encoder group too.  Not with the side-stream split (the
+  // third stream's split-K workspace would be shared).  Each group takes the stream AND the scratch of one record.
   static const int wg_env = [] { const char* e = std::getenv("RAU_WG_BULK"); return e ? std::atoi(e) : -1; }();
   const int wg_bulk = side_split(ctx) ? 0 : wg_env >= 0 ? wg_env : (chain_bound(ctx) ? 0 : 1);
   auto mult_wgrads = [&]() -> int {
-    hipStream_t sw = (wg_bulk & 1) ? ctx->st2 : ctx->st3;
+    const StreamWs& ws = (wg_bulk & 1) ? ctx->ws_bulk : ctx->ws_side;
+    hipStream_t sw = ws.owner;
     HIPC(hipStreamWaitEvent(sw, ctx->evW, 0));
     const int rows = HA * B;                 // active hops only
     if (rows == 0) {
@@ -1754,18 +1732,14 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
       const int np = mult_wgrad_problems(ctx, pr);
       double fl = 0;
       for (int i = 0; i < np; ++i) fl += gflop(pr[i].M, pr[i].N, rows);
-      // the workspace of the stream it runs on
-      float* ws = (wg_bulk & 1) ? ctx->slab2 : ctx->slab3;
-      const size_t ws_floats = (wg_bulk & 1) ? ctx->slab2_floats : ctx->slab3_floats;
-      RUNS(sw, "wgrad_gemm", fl, 0, gemm_tn_group_acc(sw, pr, np, rows, ws, ws_floats, ctx->bf16 == 1));
+      RUNS(sw, "wgrad_gemm", fl, 0, gemm_tn_group_acc(sw, pr, np, rows, ws.slab, ws.floats, lin_mode(ctx).bf16));
     }
-    float* ct = (wg_bulk & 1) ? ctx->coltmp2 : ctx->coltmp3;   // the column-sum scratch of the stream it runs on
     // att_score: dws = sum dz T ; dbs = sum dz.  att_i bias: sum dS.  i_embed bias: sum dZ.
-    RUNS(sw, "colsum", 0, (double)rows * A * 4, colsum_acc(sw, rows, A, ctx->dwsp, A, ctx->att_score.dW, ct));
+    RUNS(sw, "colsum", 0, (double)rows * A * 4, colsum_acc(sw, rows, A, ctx->dwsp, A, ctx->att_score.dW, ws.coltmp));
     HIPC(hipMemsetAsync(ctx->tmpS, 0, S * sizeof(float), sw));
-    RUNS(sw, "colsum", 0, (double)rows * S * 4, colsum_acc(sw, rows, SL, ctx->dz, S, ctx->tmpS, ct));
-    RUNS(sw, "colsum", 0, S * 4.0, colsum_acc(sw, SL, 1, ctx->tmpS, 1, ctx->att_score.db, ct));
-    RUNS(sw, "colsum", 0, (double)rows * A * 4, colsum_acc(sw, rows, A, ctx->du, A, ctx->att_i.db, ct));
+    RUNS(sw, "colsum", 0, (double)rows * S * 4, colsum_acc(sw, rows, SL, ctx->dz, S, ctx->tmpS, ws.coltmp));
+    RUNS(sw, "colsum", 0, S * 4.0, colsum_acc(sw, SL, 1, ctx->tmpS, 1, ctx->att_score.db, ws.coltmp));
+    RUNS(sw, "colsum", 0, (double)rows * A * 4, colsum_acc(sw, rows, A, ctx->du, A, ctx->att_i.db, ws.coltmp));
     HIPC(hipEventRecord(ctx->evM3, sw));   // with evD: the mult group's gradients are final
     return 0;
   };
@@ -1778,14 +1752,14 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
   if (TL > 0) {
     const int rows = TL * B;
     const size_t G4 = (size_t)B * 4 * Rq;
-    // Encoder weight gradients, also on the weight-gradient stream.  Optionally (RAU_ENC_CHUNK)
-    // in two time chunks -- the gradients of tokens t > uc are final once wavefront step uc is
-    // done -- but running the first chunk under the second half of the BPTT slows that chain by
-    // more than the shorter tail saves (measured 11.05 vs 10.6 ms), so the default is one chunk
-    // behind the BPTT.
+    // Encoder weight gradients, also on the weight-gradient stream: one launch behind the BPTT.  (Two
+    // time chunks -- the gradients of tokens t > uc are final once wavefront step uc is done -- were
+    // tried: running the first chunk under the second half of the BPTT slows that chain by more than
+    // the shorter tail saves, measured 11.05 vs 10.6 ms.)
     auto enc_wgrads = [&](int t_lo, int t_hi, hipEvent_t ev) -> int {   // tokens t_lo < t <= t_hi
       if (t_hi <= t_lo) return 0;
-      hipStream_t sw = (wg_bulk & 2) ? ctx->st2 : ctx->st3;
+      const StreamWs& ws = (wg_bulk & 2) ? ctx->ws_bulk : ctx->ws_side;
+      hipStream_t sw = ws.owner;
       HIPC(hipEventRecord(ev, st));
       HIPC(hipStreamWaitEvent(sw, ev, 0));
       const size_t r0 = (size_t)t_lo * B;
@@ -1794,9 +1768,7 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
       const int np = enc_wgrad_problems(ctx, r0, pr);
       double fl = 0;
       for (int i = 0; i < np; ++i) fl += gflop(pr[i].M, pr[i].N, nr);
-      float* ws = (wg_bulk & 2) ? ctx->slab2 : ctx->slab3;   // the workspace of the stream it runs on
-      const size_t ws_floats = (wg_bulk & 2) ? ctx->slab2_floats : ctx->slab3_floats;
-      RUNS(sw, "wgrad_gemm", fl, 0, gemm_tn_group_acc(sw, pr, np, nr, ws, ws_floats, ctx->bf16 == 1));
+      RUNS(sw, "wgrad_gemm", fl, 0, gemm_tn_group_acc(sw, pr, np, nr, ws.slab, ws.floats, lin_mode(ctx).bf16));
       return 0;
     };
     const int hi = TL;
@@ -1810,8 +1782,8 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
       int nsp = 0;
       if (nb > 0)
         RUN("enc_h2h_dgrad", gflop(B, Rq, 4 * Rq) * nb, 0,
-            gemm_nn_batched_deferred(st, nb, B, Rq, 4 * Rq, Ap, 4 * Rq, Wp, Rq, ctx->slab,
-                                     ctx->slab_floats, &nsp));
+            gemm_nn_batched_deferred(st, lin_mode(ctx), nb, B, Rq, 4 * Rq, Ap, 4 * Rq, Wp, Rq, ctx->ws_chain.slab,
+                                     ctx->ws_chain.floats, &nsp));
       LstmBwdCells cells{};
       cells.lens = bs.lens_d;
       cells.dq_rs = Q;
@@ -1820,7 +1792,7 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
         C2.gates = ctx->G2 + (size_t)(u - 1) * G4;
         C2.c_prev = ctx->c2 + (size_t)(u - 1) * BRq; C2.cp_rs = Rq;
         C2.tanhc = ctx->tc2 + (size_t)(u - 1) * BRq;
-        C2.slabA = iq2 >= 0 ? ctx->slab + (size_t)iq2 * nsp * BRq : nullptr;
+        C2.slabA = iq2 >= 0 ? ctx->ws_chain.slab + (size_t)iq2 * nsp * BRq : nullptr;
         C2.nA = iq2 >= 0 ? nsp : 0;
         C2.slabB = nullptr; C2.nBp = 0; C2.maskB = nullptr; C2.maskB_e0 = 0; C2.mscaleB = 1.f;
         C2.dc_next = u < TL ? ctx->edc[1][(u + 1) & 1] : nullptr;
@@ -1834,9 +1806,9 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
         C1.gates = ctx->G1 + (size_t)u * G4;
         C1.c_prev = ctx->c1 + (size_t)u * BRq; C1.cp_rs = Rq;
         C1.tanhc = ctx->tc1 + (size_t)u * BRq;
-        C1.slabA = iq1 >= 0 ? ctx->slab + (size_t)iq1 * nsp * BRq : nullptr;
+        C1.slabA = iq1 >= 0 ? ctx->ws_chain.slab + (size_t)iq1 * nsp * BRq : nullptr;
         C1.nA = iq1 >= 0 ? nsp : 0;
-        C1.slabB = ctx->slab + (size_t)iqx * nsp * BRq;   // dG2[t] W_i2h2, then the dropout mask
+        C1.slabB = ctx->ws_chain.slab + (size_t)iqx * nsp * BRq;   // dG2[t] W_i2h2, then the dropout mask
         C1.nBp = nsp;
         C1.maskB = m_rnn; C1.maskB_e0 = (size_t)u * BRq; C1.mscaleB = sc(RAU_MASK_RNN);
         C1.dc_next = t < TL ? ctx->edc[0][(t + 1) & 1] : nullptr;
@@ -1847,7 +1819,7 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
       RUN("lstm_bwd", 0, BRq * 4.0 * 12 * cells.n, lstm_bwd_multi(st, GATES_DEEP, B, Rq, cells));
     }
     {  // gradient w.r.t. the word embeddings' tanh output, all tokens at once
-      LINOPTS(o);
+      const LinOpts o = lin_opts(ctx, ctx->ws_chain);
       RUN("enc_i2h_dgrad", gflop(rows, E, 4 * Rq), 0,
           gemm_nn(st, rows, E, 4 * Rq, ctx->dG1, 4 * Rq, ctx->i2h[0].W, E, ctx->dwe, E, o));
     }

@@ -11,6 +11,10 @@
 // weight gradient is accumulated by the clone's own :backward (accGradParameters).  The
 // step-level path is the fast one; this one exists for drop-in compatibility and as a
 // second, independently scheduled route to the same numbers (tests/test_gpu_modules.py).
+// Everything runs on the chain stream, and every step-level call joins all three streams before it returns,
+// so the bulk and side streams are idle here: that is why this file may borrow THEIR scratch (ws_side.slab /
+// .coltmp for the per-clone Linear weight gradients and column sums, ws_bulk.slab for the conv weight
+// gradients) while the chain stream's own slab holds the hop's partials.
 #include "rau_ctx.h"
 
 namespace {
@@ -73,8 +77,8 @@ int lin_wgrad(rau_ctx* ctx, Lin& l, const float* dY, const float* X, long ldx, b
               long ldy = 0) {
   const int B = ctx->cfg.B;
   RUN("wgrad_gemm", 2.0 * l.out * l.in * B, 0,
-      gemm_tn_acc(ctx->st, l.out, l.in, B, dY, ldy ? ldy : l.out, X, ldx, l.dW, l.in, ctx->slab3,
-                  bias ? l.db : nullptr, ctx->bf16 == 1));
+      gemm_tn_acc(ctx->st, l.out, l.in, B, dY, ldy ? ldy : l.out, X, ldx, l.dW, l.in, ctx->ws_side.slab,
+                  bias ? l.db : nullptr, lin_mode(ctx).bf16));
   return 0;
 }
 // X = NULL ("the resident batch"): its f32 form at pitch Sp -- the buffer itself, or for a 16-bit or fp8 batch
@@ -159,7 +163,6 @@ int rau_embed_backward(rau_ctx* ctx, int t, const int32_t* tokens_dev, const flo
 // ------------------------------------------------------------ DeepLSTM clone t
 int rau_deeplstm_forward(rau_ctx* ctx, int t, const float* x, const float* state,
                          float** state_out) {
-  if (ctx) set_skinny_policy(ctx);
   NEED(ctx && x && state_out, "null argument");
   const rau_config& c = ctx->cfg;
   NEED(t >= 0 && t < c.T, "rau_deeplstm_forward: t=%d out of [0,%d)", t, c.T);
@@ -177,11 +180,11 @@ int rau_deeplstm_forward(rau_ctx* ctx, int t, const float* x, const float* state
   float* x2 = ctx->x2 + (size_t)t * BRq;
   auto gflop = [](double mm, double n, double k) { return 2.0 * mm * n * k; };
   {  // layer 1: i2h(x) + h2h(prev_h), DeepLSTM.lua:42-44
-    LINOPTS(o);
+    LinOpts o = lin_opts(ctx, ctx->ws_chain);
     o.bias = ctx->i2h[0].b;
     o.bias2 = ctx->h2h[0].b;
     RUN("enc_i2h_gemm", gflop(B, 4 * Rq, E), 0, gemm_nt(st, B, 4 * Rq, E, x, E, ctx->i2h[0].W, E, G1, 4 * Rq, o));
-    LINOPTS(oa);
+    LinOpts oa = lin_opts(ctx, ctx->ws_chain);
     oa.accumulate = 1;
     RUN("enc_h2h_gemm", gflop(B, 4 * Rq, Rq), 0,
         gemm_nt(st, B, 4 * Rq, Rq, state + Rq, Q, ctx->h2h[0].W, Rq, G1, 4 * Rq, oa));
@@ -190,11 +193,11 @@ int rau_deeplstm_forward(rau_ctx* ctx, int t, const float* x, const float* state
                  ctx->tc1 + (size_t)t * BRq, x2, m.rnn, (size_t)t * BRq, m.s_rnn));
   }
   {  // layer 2 on dropout(h1), DeepLSTM.lua:39
-    LINOPTS(o);
+    LinOpts o = lin_opts(ctx, ctx->ws_chain);
     o.bias = ctx->i2h[1].b;
     o.bias2 = ctx->h2h[1].b;
     RUN("enc_h2h_gemm", gflop(B, 4 * Rq, Rq), 0, gemm_nt(st, B, 4 * Rq, Rq, x2, Rq, ctx->i2h[1].W, Rq, G2, 4 * Rq, o));
-    LINOPTS(oa);
+    LinOpts oa = lin_opts(ctx, ctx->ws_chain);
     oa.accumulate = 1;
     RUN("enc_h2h_gemm", gflop(B, 4 * Rq, Rq), 0,
         gemm_nt(st, B, 4 * Rq, Rq, state + 3 * Rq, Q, ctx->h2h[1].W, Rq, G2, 4 * Rq, oa));
@@ -208,7 +211,6 @@ int rau_deeplstm_forward(rau_ctx* ctx, int t, const float* x, const float* state
 
 int rau_deeplstm_backward(rau_ctx* ctx, int t, const float* x, const float* state,
                           const float* d_state_out, float** d_x, float** d_state) {
-  if (ctx) set_skinny_policy(ctx);
   NEED(ctx && x && d_state_out && d_x && d_state, "null argument");
   const rau_config& c = ctx->cfg;
   NEED(t >= 0 && t < c.T, "rau_deeplstm_backward: t=%d out of [0,%d)", t, c.T);
@@ -234,10 +236,10 @@ int rau_deeplstm_backward(rau_ctx* ctx, int t, const float* x, const float* stat
                nullptr, 0, nullptr, nullptr, 0));
   if (int rc = copy2d(ctx, dst + 2 * Rq, Q, dc_prev, Rq, Rq)) return rc;
   {
-    LINOPTS(o);   // grad at prev_h of layer 2
+    LinOpts o = lin_opts(ctx, ctx->ws_chain);   // grad at prev_h of layer 2
     RUN("enc_h2h_dgrad", gflop(B, Rq, 4 * Rq), 0,
         gemm_nn(st, B, Rq, 4 * Rq, dG2, 4 * Rq, ctx->h2h[1].W, Rq, dst + 3 * Rq, Q, o));
-    LINOPTS(o2);  // grad at layer-2 input, back through the inter-layer dropout
+    LinOpts o2 = lin_opts(ctx, ctx->ws_chain);  // grad at layer-2 input, back through the inter-layer dropout
     o2.emask = m.rnn;
     o2.emask_e0 = (size_t)t * BRq;
     o2.emscale = m.s_rnn;
@@ -252,10 +254,10 @@ int rau_deeplstm_backward(rau_ctx* ctx, int t, const float* x, const float* stat
                0, nullptr, nullptr, 0));
   if (int rc = copy2d(ctx, dst, Q, dc_prev, Rq, Rq)) return rc;
   {
-    LINOPTS(o);
+    LinOpts o = lin_opts(ctx, ctx->ws_chain);
     RUN("enc_h2h_dgrad", gflop(B, Rq, 4 * Rq), 0,
         gemm_nn(st, B, Rq, 4 * Rq, dG1, 4 * Rq, ctx->h2h[0].W, Rq, dst + Rq, Q, o));
-    LINOPTS(o2);
+    LinOpts o2 = lin_opts(ctx, ctx->ws_chain);
     RUN("enc_i2h_dgrad", gflop(B, E, 4 * Rq), 0,
         gemm_nn(st, B, E, 4 * Rq, dG1, 4 * Rq, ctx->i2h[0].W, E, dxo, E, o2));
   }
@@ -273,7 +275,6 @@ int rau_deeplstm_backward(rau_ctx* ctx, int t, const float* x, const float* stat
 int rau_multimodal_forward(rau_ctx* ctx, int h, const float* q, const float* X, const float* c_prev,
                            const float* h_prev, float** logits, float** do_pred, float** attprob,
                            float** c_out, float** h_out) {
-  if (ctx) set_skinny_policy(ctx);
   NEED(ctx && q, "null argument");
   const rau_config& c = ctx->cfg;
   NEED(h >= 0 && h < c.H, "rau_multimodal_forward: h=%d out of [0,%d)", h, c.H);
@@ -305,7 +306,7 @@ int rau_multimodal_forward(rau_ctx* ctx, int h, const float* q, const float* X, 
       apply_mask(st, (size_t)B * Q, (size_t)B * Q, q, m.q, m.s_q, qd, (size_t)h * B * Q));
   ctx->yq_shared = false;   // this path fills the hop's own rows
   {
-    LINOPTS(o);
+    LinOpts o = lin_opts(ctx, ctx->ws_chain);
     o.bias = ctx->q_proj.b;
     o.bias2 = ctx->h_proj.b;
     RUN("q_proj_gemm", gflop(B, M, Q), 0,
@@ -350,7 +351,6 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
                             const float* d_do_pred, const float* d_attprob, const float* d_c,
                             const float* d_h, float** d_q, float** d_X, float** d_c_prev,
                             float** d_h_prev) {
-  if (ctx) set_skinny_policy(ctx);
   NEED(ctx && q && d_logits, "null argument");
   const rau_config& c = ctx->cfg;
   NEED(h >= 0 && h < c.H, "rau_multimodal_backward: h=%d out of [0,%d)", h, c.H);
@@ -405,8 +405,8 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
   if (d_do_pred) {
     // m_add is free again once dpre has been formed: reuse it for s (.) mf rows
     RUN("dopred_bwd", 0, 0, row_scale(st, B, M, ctx->m_s, mfh, nullptr, ctx->m_add));
-    RUN("colsum", 0, 0, colsum_acc(st, B, M, ctx->m_add, M, ctx->do_pred.dW, ctx->coltmp3));
-    RUN("colsum", 0, 0, colsum_acc(st, B, 1, ctx->m_s, 1, ctx->do_pred.db, ctx->coltmp3));
+    RUN("colsum", 0, 0, colsum_acc(st, B, M, ctx->m_add, M, ctx->do_pred.dW, ctx->ws_side.coltmp));
+    RUN("colsum", 0, 0, colsum_acc(st, B, 1, ctx->m_s, 1, ctx->do_pred.db, ctx->ws_side.coltmp));
   }
   // ---- 1x1-conv gradients of this clone: dI = Wp^T dS + dj (x) a; dWp += dS I^T;
   // dWi += (dI (1-I^2)) X'^T; bias gradients
@@ -414,14 +414,14 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
       conv_att_dgrad(st, B, M, S, A, Th, ctx->att_i.W, ctx->dj + (size_t)h * BM_,
                      ctx->a + (size_t)h * BS_, dZh, ctx->bf16));
   RUN("conv_att_wgrad", gflop(A, M, (double)B * S), ((double)B * A * S + BM_ * S) * 4,
-      conv_att_wgrad(st, B, M, S, A, Th, Ih, ctx->att_i.dW, ctx->slab2, ctx->bf16));
+      conv_att_wgrad(st, B, M, S, A, Th, Ih, ctx->att_i.dW, ctx->ws_bulk.slab, ctx->bf16));
   RUN("conv_embed_wgrad", gflop(M, D, (double)B * S), (BM_ * S + (double)B * D * S) * 4,
-      conv_embed_wgrad(st, B, D, S, M, dZh, Ih, xin, ctx->i_embed.dW, ctx->slab2, ctx->bf16,
+      conv_embed_wgrad(st, B, D, S, M, dZh, Ih, xin, ctx->i_embed.dW, ctx->ws_bulk.slab, ctx->bf16,
                        ctx->i_embed.db));
   // ---- gradient w.r.t. q through q_embed's dropout
   float* dqo = ctx->m_dq + (size_t)h * B * Q;
   {
-    LINOPTS(o);
+    LinOpts o = lin_opts(ctx, ctx->ws_chain);
     o.emask = m.q;
     o.emask_e0 = (size_t)h * B * Q;
     o.emscale = m.s_q;
@@ -463,12 +463,12 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
   if (int rc = lin_wgrad(ctx, ctx->h_proj, ctx->dqt + (size_t)h * BM_, h_prev, R)) return rc;
   // attscore: dws = sum_b dwsp[b]; dbs = sum dz.  ifeatproj bias: sum_b du[b]
   RUN("colsum", 0, (double)B * A * 4,
-      colsum_acc(st, B, A, ctx->dwsp + (size_t)h * B * A, A, ctx->att_score.dW, ctx->coltmp3));
+      colsum_acc(st, B, A, ctx->dwsp + (size_t)h * B * A, A, ctx->att_score.dW, ctx->ws_side.coltmp));
   HIPC(hipMemsetAsync(ctx->tmpS, 0, S * sizeof(float), st));
-  RUN("colsum", 0, (double)B * S * 4, colsum_acc(st, B, SL, ctx->dz + (size_t)h * BS_, S, ctx->tmpS, ctx->coltmp3));
-  RUN("colsum", 0, S * 4.0, colsum_acc(st, SL, 1, ctx->tmpS, 1, ctx->att_score.db, ctx->coltmp3));
+  RUN("colsum", 0, (double)B * S * 4, colsum_acc(st, B, SL, ctx->dz + (size_t)h * BS_, S, ctx->tmpS, ctx->ws_side.coltmp));
+  RUN("colsum", 0, S * 4.0, colsum_acc(st, SL, 1, ctx->tmpS, 1, ctx->att_score.db, ctx->ws_side.coltmp));
   RUN("colsum", 0, (double)B * A * 4,
-      colsum_acc(st, B, A, ctx->du + (size_t)h * B * A, A, ctx->att_i.db, ctx->coltmp3));
+      colsum_acc(st, B, A, ctx->du + (size_t)h * B * A, A, ctx->att_i.db, ctx->ws_side.coltmp));
   if (d_q) *d_q = dqo;
   if (d_c_prev) *d_c_prev = g.dc_out;
   if (d_h_prev) *d_h_prev = g.dh_out;

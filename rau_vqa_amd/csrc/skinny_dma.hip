@@ -27,8 +27,8 @@
 //    waits and barriers per K; 32 KB and 90 registers.  Stand-alone 10-18 % faster on the recurrence's
 //    shapes (tools/linbench); in the step it pays where the recurrence is the longer path (bf16 mode
 //    -1.1 %, 64-sample contexts -1.9 %, evaluate-mode forward +1.5-3.5 %) and costs the f32 256-sample
-//    step 0.9 %, so the step-level entry points choose per calling thread (skinny_dma_set_deep, from
-//    chain_bound() in rau_ctx.h; K % 64 != 0 keeps NH = 1).
+//    step 0.9 %, so the caller chooses per launch (LinMode::deep, computed by lin_mode() in rau_ctx.h from
+//    chain_bound(); K % 64 != 0 keeps NH = 1).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -358,33 +358,28 @@ __global__ __launch_bounds__(256, BF ? 4 : 1) void k_skinny_dma(const SkinnyPara
 
 }  // namespace
 
-// Which form the calling thread's launches take: 32-deep stages where the caller says the recurrence
-// is the longer path and K allows it, else 16-deep stages.
-static thread_local int g_deep = 0;
-static thread_local int g_bf16 = 0;
-void skinny_dma_set_deep(int on) { g_deep = on; }
-void lin_set_bf16(int on) { g_bf16 = on; }
-int lin_bf16() { return g_bf16; }
-static int stage_depth(int K) { return (g_deep && K % 64 == 0) ? 32 : 16; }
+// Which form a launch takes: 32-deep stages where the caller says the recurrence is the longer path
+// (LinMode::deep) and K allows it, else 16-deep stages.
+static int stage_depth(int deep, int K) { return (deep && K % 64 == 0) ? 32 : 16; }
 
 // Ragged shapes (the RAG kernels): K not a whole even number of stages, or [K][N] weights whose N is not
 // a multiple of the 64-column tile.  RAU_SKINNY_RAGGED_OFF sends them to the register-staged tile as
 // rounds 1-3 did (A/B knob).
-static bool ragged(int K, bool brc, int nprob, const int* N) {
-  if (K % (2 * stage_depth(K)) != 0) return true;
+static bool ragged(int deep, int K, bool brc, int nprob, const int* N) {
+  if (K % (2 * stage_depth(deep, K)) != 0) return true;
   if (brc)
     for (int p = 0; p < nprob; ++p)
       if (N[p] % KT != 0) return true;
   return false;
 }
 
-bool skinny_dma_ok(int M, int K, long lda, long ldb, bool brc, int nprob, const int* N,
+bool skinny_dma_ok(int deep, int M, int K, long lda, long ldb, bool brc, int nprob, const int* N,
                    const float* const* A, const float* const* B) {
-  static const bool off = std::getenv("RAU_SKINNY_DMA_OFF") != nullptr;   // A/B knob (DESIGN.md section 9)
+  static const bool off = std::getenv("RAU_SKINNY_DMA_OFF") != nullptr;   // A/B knob (DESIGN.md section 8)
   static const bool rag_off = std::getenv("RAU_SKINNY_RAGGED_OFF") != nullptr;
   if (off || M < 1 || nprob < 1 || nprob > 3) return false;
   if (K < 4 || (K & 3) || (lda & 3) || (ldb & 3)) return false;
-  if (ragged(K, brc, nprob, N)) {
+  if (ragged(deep, K, brc, nprob, N)) {
     if (rag_off) return false;
     for (int p = 0; p < nprob; ++p)
       if (brc && (N[p] & 3)) return false;         // pieces are all inside or all outside a row
@@ -403,8 +398,8 @@ bool skinny_dma_ok(int M, int K, long lda, long ldb, bool brc, int nprob, const 
 }
 
 // K splits: about one workgroup per CU (256), an even number of K-steps per split
-int skinny_dma_splits(int M, int K, int tiles_all, size_t cols_all, size_t slab_floats) {
-  const int depth = stage_depth(K);
+int skinny_dma_splits(int deep, int M, int K, int tiles_all, size_t cols_all, size_t slab_floats) {
+  const int depth = stage_depth(deep, K);
   const int nk = (K + depth - 1) / depth;
   int s = (256 + tiles_all / 2) / tiles_all;   // 160 .. 512 measured equal in the step
   if (s > nk / 2) s = nk / 2;
@@ -415,11 +410,11 @@ int skinny_dma_splits(int M, int K, int tiles_all, size_t cols_all, size_t slab_
   return (nk + per - 1) / per;
 }
 
-hipError_t skinny_dma(hipStream_t st, bool brc, int nprob, int M, int K, const float* const* A,
-                      long lda, const float* const* B, long ldb, const int* N, float* slab,
-                      const long* off, int splits) {
-  const int depth = stage_depth(K);
-  const bool rag = ragged(K, brc, nprob, N);
+hipError_t skinny_dma(hipStream_t st, LinMode mode, bool brc, int nprob, int M, int K,
+                      const float* const* A, long lda, const float* const* B, long ldb, const int* N,
+                      float* slab, const long* off, int splits) {
+  const int depth = stage_depth(mode.deep, K);
+  const bool rag = ragged(mode.deep, K, brc, nprob, N);
   if (splits < 1 || nprob < 1 || nprob > 3 || (K & 3)) return hipErrorInvalidValue;
   SkinnyParams P{};
   P.M = M; P.K = K; P.nprob = nprob; P.splits = splits;
@@ -446,7 +441,7 @@ hipError_t skinny_dma(hipStream_t st, bool brc, int nprob, int M, int K, const f
                          grid, block, 0, st, P);
   };
   auto by_bf = [&](auto brc_t, auto nh_t) {
-    if (g_bf16) go(brc_t, nh_t, std::true_type{});
+    if (mode.bf16) go(brc_t, nh_t, std::true_type{});
     else go(brc_t, nh_t, std::false_type{});
   };
   auto by_nh = [&](auto brc_t) {

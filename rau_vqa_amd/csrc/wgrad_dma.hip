@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256 * NG, 2) void k_wgrad_dma(const WgradParams P) 
 
 // Shapes it takes: 14 x 14 maps, both row counts multiples of 128.
 bool wgrad_dma_ok(int ra, int rb, int S) {
-  static const bool off = std::getenv("RAU_WGRAD_DMA_OFF") != nullptr;   // A/B knob (DESIGN.md section 9)
+  static const bool off = std::getenv("RAU_WGRAD_DMA_OFF") != nullptr;   // A/B knob (DESIGN.md section 8)
   return !off && S == GS && ra % GT == 0 && rb % GT == 0;
 }
 

@@ -18,8 +18,9 @@ static float frand(unsigned& s) { s = s * 1664525u + 1013904223u; return ((s >> 
 
 int main(int argc, char** argv) {
   const int M = argc > 1 ? atoi(argv[1]) : 256;
-  if (argc > 2 && atoi(argv[2])) { rau::skinny_dma_set_deep(1); printf("32-deep stages\n"); }
-  if (argc > 3 && atoi(argv[3])) { rau::lin_set_bf16(1); printf("bf16 products\n"); }
+  rau::LinMode mode;
+  if (argc > 2 && atoi(argv[2])) { mode.deep = 1; printf("32-deep stages\n"); }
+  if (argc > 3 && atoi(argv[3])) { mode.bf16 = 1; printf("bf16 products\n"); }
   const int woff = argc > 4 ? atoi(argv[4]) : 0;   // W starts `woff` floats behind a 16-byte boundary
   if (woff) printf("W offset by %d floats\n", woff);
   struct Shape { int nn, N, K; };
@@ -47,6 +48,7 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(W, hW.data(), hW.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(b, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
     rau::LinOpts o;
+    o.mode = mode;
     o.bias = b;
     o.slab = slab;
     o.slab_floats = slab_floats;
