@@ -73,6 +73,9 @@ int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_
 int rau_set_batch_async(rau_ctx* ctx, int slot, const float* feats, const int32_t* tokens,
                         const int32_t* lens, const int32_t* labels, int has_labels);
 int rau_use_batch(rau_ctx* ctx, int slot);
+int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const float* w,
+                    const float* score);
+int rau_batch_answers(rau_ctx* ctx, int32_t* G);
 int rau_forward(rau_ctx* ctx);
 int rau_backward(rau_ctx* ctx, const float* hop_w);
 int rau_embed_forward(rau_ctx* ctx, int t, const int32_t* tokens_dev, float** we);
@@ -93,6 +96,10 @@ int rau_criterion_forward(rau_ctx* ctx, int h, const float* logits, const int32_
                           float* loss);
 int rau_criterion_backward(rau_ctx* ctx, int h, const float* logits,
                            const int32_t* labels_dev, float scale, float** d_logits);
+int rau_criterion_forward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
+                              const float* w_dev, float* loss);
+int rau_criterion_backward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
+                               const float* w_dev, float scale, float** d_logits);
 int rau_dev_alloc(rau_ctx* ctx, size_t n_floats, float** out);
 int rau_dev_free(rau_ctx* ctx, float* p);
 int rau_dev_fill(rau_ctx* ctx, float* dst, size_t n, float value);
@@ -126,6 +133,8 @@ int rau_get_attention(rau_ctx* ctx, float* att);
 int rau_get_question_state(rau_ctx* ctx, float* q);
 int rau_get_att_state(rau_ctx* ctx, float* c, float* h);
 int rau_step_stats(rau_ctx* ctx, float* loss, float* loss_do_pred, int32_t* counts);
+int rau_step_scores(rau_ctx* ctx, float* per_sample, float* total);
+int rau_predict_scores(rau_ctx* ctx, float* oe, float* mc, float* totals);
 int rau_predict(rau_ctx* ctx, const int32_t* mc_ans, int32_t n_mc, int32_t* oe, int32_t* mc);
 int rau_get_merged(rau_ctx* ctx, float* pred, float* att);
 int rau_topk(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf);
@@ -273,6 +282,24 @@ function RAU:setBatchAsync(slot, feats, x, x_len, y, has_labels, feat_type)
 end
 function RAU:useBatch(slot) check(C.rau_use_batch(self.h, slot)) end
 
+-- Multi-answer ground truth (rau_set_answers): ids IntTensor [B,G] of 1-based answer ids (0 = empty entry), w
+-- FloatTensor [B,G] of loss weights, score FloatTensor [B,G] of metric scores (nil: w), G <= 16.  slot = nil: the
+-- resident batch (call it after setBatch); slot = 0 | 1: after setBatchAsync(slot, ...) and before useBatch(slot).
+-- The set replaces y in the criterion head and in stepStats until the next batch goes into that slot.
+function RAU:setAnswers(ids, w, score, slot)
+  ids, w = ids:int():contiguous(), w:float():contiguous()
+  score = score and score:float():contiguous()
+  assert(ids:dim() == 2 and ids:size(1) == self.n and w:isSameSizeAs(ids), 'ids and w must be [B,G]')
+  assert(not score or score:isSameSizeAs(ids), 'score must be [B,G]')
+  check(C.rau_set_answers(self.h, slot or -1, ids:size(2), ids:data(), w:data(), score and score:data() or nil))
+end
+-- G of the resident batch's answer set, 0 without one
+function RAU:batchAnswers()
+  local g = ffi.new('int32_t[1]')
+  check(C.rau_batch_answers(self.h, g))
+  return g[0]
+end
+
 -- A batch whose questions share feature maps: feats is the image TABLE [N,D,W,H] (Float- or HalfTensor, or a
 -- ByteTensor of fp8 codes with feat_type 'e4m3' | 'e5m2'),
 -- image_of an IntTensor [B] of 1-BASED table rows, as Torch indexes (feats:index(1, image_of:long()) is the
@@ -380,6 +407,32 @@ function RAU:stepStats()
     counts.selected[h] = c[3 * H + 3 + h - 1]
   end
   return tab_loss, tab_loss_do_pred, counts
+end
+
+-- Metric scores of the last forward's answers against its batch's answer set (feval rule, as stepStats):
+-- FloatTensor [nHop+2, B] (hops, uni, select) and their batch sums as a 1-based Lua table.  With score =
+-- min(#humans / 3, 1) the sums are the VQA accuracy times B.
+function RAU:stepScores()
+  local H, B = self.cfg.H, self.n
+  local per, tot = torch.FloatTensor(H + 2, B), ffi.new('float[?]', H + 2)
+  check(C.rau_step_scores(self.h, per:data(), tot))
+  local t = {}
+  for i = 1, H + 2 do t[i] = tot[i - 1] end
+  return per, t
+end
+-- The same for the answers of the last predict() (last hop forced): oe scores, mc scores (nil without an MC
+-- list), and their batch sums { oe = {..}, mc = {..} | nil }
+function RAU:predictScores(with_mc)
+  local H, B = self.cfg.H, self.n
+  local oe, mc = torch.FloatTensor(H + 2, B), with_mc and torch.FloatTensor(H + 2, B) or nil
+  local tot = ffi.new('float[?]', 2 * (H + 2))
+  check(C.rau_predict_scores(self.h, oe:data(), mc and mc:data() or nil, tot))
+  local t = { oe = {}, mc = with_mc and {} or nil }
+  for i = 1, H + 2 do
+    t.oe[i] = tot[i - 1]
+    if with_mc then t.mc[i] = tot[H + 2 + i - 1] end
+  end
+  return oe, mc, t
 end
 
 -- predict_result + the eval loop's answer selection (SS:633-705, 877-900) on the last forward
@@ -679,6 +732,18 @@ local function clone(self, kind, i)
       check(C.rau_criterion_backward(self.rau.h, self.i, ptr_of(logits), ptr_of(y), scale or 1, o))
       return Tensor.wrap(self.rau, o[0], self.rau.n, cfg.K)
     end
+    -- the same criterion against an answer set in device memory: ids (RAU.IntTensor [B,G], 0 = empty entry) and
+    -- w (RAU.Tensor [B,G]), or raw device pointers
+    function m:forwardSet(logits, ids, w, G)
+      local l = ffi.new('float[1]')
+      check(C.rau_criterion_forward_set(self.rau.h, self.i, ptr_of(logits), G, ptr_of(ids), ptr_of(w), l))
+      return l[0]
+    end
+    function m:backwardSet(logits, ids, w, G, scale)
+      local o = ffi.new('float*[1]')
+      check(C.rau_criterion_backward_set(self.rau.h, self.i, ptr_of(logits), G, ptr_of(ids), ptr_of(w), scale or 1, o))
+      return Tensor.wrap(self.rau, o[0], self.rau.n, cfg.K)
+    end
   end
   function m:training() self.rau:training() end
   function m:evaluate() self.rau:evaluate() end
@@ -691,5 +756,10 @@ function RAU:embedClone(t) return clone(self, 'embed', t) end
 function RAU:rnnClone(t) return clone(self, 'rnn', t) end
 function RAU:multimodalClone(h) return clone(self, 'multimodal', h) end
 function RAU:criterion(h) return clone(self, 'criterion', h) end
+-- criteria[h] against an answer set, without making the clone: loss / d_logits (see forwardSet / backwardSet)
+function RAU:criterionForwardSet(h, logits, ids, w, G) return clone(self, 'criterion', h):forwardSet(logits, ids, w, G) end
+function RAU:criterionBackwardSet(h, logits, ids, w, G, scale)
+  return clone(self, 'criterion', h):backwardSet(logits, ids, w, G, scale)
+end
 
 return RAU

@@ -349,6 +349,37 @@ int rau_set_batch_async(rau_ctx* ctx, int slot, const float* feats, const int32_
                         const int32_t* lens, const int32_t* labels, int has_labels);
 int rau_use_batch(rau_ctx* ctx, int slot);
 
+/* ---- answer sets: multi-answer ground truth on a batch ------------------------------------------
+ * Every VQA question has ten human answers.  An answer set gives a batch, per sample, up to RAU_MAX_ANSWERS
+ * weighted answers in place of the one label: ids [n,G] int32 (1..K, or 0 for an empty entry), w [n,G] f32 loss
+ * weights, score [n,G] f32 metric scores (NULL: use w); n = the current batch size, 1 <= G <= RAU_MAX_ANSWERS.
+ * Entries with id 0 are ignored whatever their weight; duplicate ids in a row are allowed and add up; a row with
+ * no entry is an unlabelled sample: zero loss, zero gradient, never "correct".
+ *   slot = -1      the resident batch; synchronising, like rau_set_batch.
+ *   slot = 0 | 1   a slot of the asynchronous path: call it after rau_set_batch_async* on that slot and before
+ *                  rau_use_batch; the copies are enqueued on the copy stream behind the slot's batch and nothing
+ *                  is synchronised (a second set for the same upload first waits for the first one's copy).
+ * The set belongs to the slot's batch: any later batch upload into that slot and rau_set_batch_size clear it,
+ * rau_use_batch makes it current together with the batch, an upload into the other slot leaves it alone.  It
+ * REPLACES the batch's labels in the criterion head of rau_forward / rau_graph_step, in rau_step_stats, and in
+ * rau_criterion_forward / _backward called with labels_dev == NULL; a batch uploaded with labels == NULL and
+ * then given a set counts as labelled.  A forward that has run on the batch must be run again before
+ * rau_backward or rau_step_stats.  A batch without a set computes bit for bit what it did before sets existed.
+ * With lse the row's log-sum-exp, invB = 1/n and W_b = sum_g w[b,g] over the non-empty entries in order g = 0..G-1:
+ *   loss row   sum_g w[b,g] (lse - logit[y_g]), accumulated from 0 in g order (rau_get_losses: their mean over n)
+ *   d_logits   expf(logit[k] - lse) (W_b invB), then for g = 0..G-1 in order: if (ids[b,g] - 1 == k) -= w[b,g] invB
+ * every step's rounding is fixed (ce_set.hip: the first matching entry of a logit is subtracted inside the product's
+ * fused multiply-add, as the label path does), so duplicates are deterministic and G = 1, w = 1 gives the bits of
+ * the label path.  rau_graph_step keys its cache by G: a step captured without a set, or with another G, is never replayed.
+ * Errors, nothing uploaded, the previous set stays in force: RAU_ERR_INVALID for G out of range, an id outside
+ * 0..K, a negative or non-finite weight or score; RAU_ERR_STATE when the slot holds no batch, or (slot 0 | 1) it
+ * is the current batch of a forward whose backward has not run.
+ * rau_batch_answers: the G of the resident batch's set, 0 when it has none. */
+#define RAU_MAX_ANSWERS 16
+int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const float* w,
+                    const float* score);
+int rau_batch_answers(rau_ctx* ctx, int32_t* G);
+
 /* ---- the hot path ------------------------------------------------------------
  * rau_forward : SS:443-520  encoder unroll, length select, H-hop RAU, per-hop
  *               CrossEntropyCriterion forward, first-max argmax.
@@ -416,6 +447,13 @@ int rau_criterion_forward(rau_ctx* ctx, int h, const float* logits, const int32_
                           float* loss);
 int rau_criterion_backward(rau_ctx* ctx, int h, const float* logits,
                            const int32_t* labels_dev, float scale, float** d_logits);
+
+/* The same criterion against an answer set in DEVICE memory (ids_dev / w_dev [B,G], see rau_set_answers; the
+ * ids are clamped into [0, K] like labels_dev): the kernel the step's head uses with a set. */
+int rau_criterion_forward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
+                              const float* w_dev, float* loss);
+int rau_criterion_backward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
+                               const float* w_dev, float scale, float** d_logits);
 
 /* ---- device tensors: the tensor algebra feval does BETWEEN module calls ----------------------
  * The reference's loops copy state rows where x_len[k] == t (`rnn_out[k] = lst[k]`, SS:455-461;
@@ -499,6 +537,24 @@ int rau_get_att_state(rau_ctx* ctx, float* c /* [H,B,R] */, float* h /* [H,B,R] 
  * Any output may be NULL.  RAU_ERR_STATE also when that forward's batch had no labels.  Synchronising. */
 #define RAU_STATS_NCOUNTS(H) (4 * (H) + 3)
 int rau_step_stats(rau_ctx* ctx, float* loss, float* loss_do_pred, int32_t* counts);
+
+/* With an answer set (rau_set_answers) on that forward's batch, "argmax == y" becomes: the row's first-max
+ * answer is among the row's non-empty ids with score > 0 (never on a row without entries).  rau_step_stats uses
+ * that rule for correct[H+2], do_pred_gt (the BCE target) and did_correct, and the soft CE of rau_set_answers for
+ * the uni and select rows; the per-hop CE stays bitwise rau_get_losses.
+ * The metric score of an answer a of sample b is sum_g score[b,g] * [ids[b,g] == a], added from 0 in g order: exact
+ * to restate in float32.  With score = min(#humans / 3, 1) it is the VQA accuracy the evaluation server reports.
+ *   rau_step_scores     per_sample [H+2,n] (hops, uni, select; feval rule: last hop not forced), total [H+2] = their
+ *                       sums over the batch.  Valid exactly when rau_step_stats is.
+ *   rau_predict_scores  for the answers of the last rau_predict on the last forward (last hop forced): oe, mc
+ *                       [H+2,n], totals [2,H+2] (oe row, mc row); mc and totals[1] are written only if that
+ *                       rau_predict had an MC list.  RAU_ERR_STATE when no rau_predict has run on that forward.
+ * Any output may be NULL.  Both return RAU_ERR_STATE, with nothing launched, when the forward's batch had no answer
+ * set.  Totals are reduced by one workgroup in a fixed order (no float atomics): repeated calls give the same
+ * bits.  Synchronising. */
+int rau_step_scores(rau_ctx* ctx, float* per_sample /* [H+2,n] */, float* total /* [H+2] */);
+int rau_predict_scores(rau_ctx* ctx, float* oe /* [H+2,n] */, float* mc /* [H+2,n] */,
+                       float* totals /* [2,H+2] */);
 
 /* predict_result + the eval loop's answer selection (SS:633-705, 877-900), last hop forced.
  * mc_ans: host [B, n_mc] candidate ids 1..K, 0 = empty slot (NULL: no MC; an id outside 0..K is

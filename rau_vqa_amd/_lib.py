@@ -78,6 +78,9 @@ _SIGS = {
     "rau_set_batch_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int]),
     "rau_use_batch": (C.c_int, [C.c_void_p, C.c_int]),
+    # answer sets: multi-answer ground truth on a batch
+    "rau_set_answers": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rau_batch_answers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "rau_set_batch_typed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
     "rau_set_batch_async_typed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -115,6 +118,10 @@ _SIGS = {
                                         C.POINTER(C.c_float)]),
     "rau_criterion_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                          C.POINTER(C.c_void_p)]),
+    "rau_criterion_forward_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_float)]),
+    "rau_criterion_backward_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_float, C.POINTER(C.c_void_p)]),
     # device tensors (the tensor algebra feval does between module calls)
     "rau_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "rau_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -150,6 +157,8 @@ _SIGS = {
     "rau_get_att_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     # merged hops: feval's statistics and predict_result on the device
     "rau_step_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rau_step_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rau_predict_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "rau_get_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_topk": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

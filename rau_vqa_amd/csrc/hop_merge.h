@@ -21,6 +21,24 @@ __device__ __forceinline__ float block_sum(float v, float* s_sum) {
   return r;
 }
 
+// torch.max's first-max over the workgroup (k_ce_fwd's rule): the largest value, lowest index on ties
+__device__ __forceinline__ void block_first_max(float& mx, int& ai, float* s_val, int* s_idx) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(mx, o, 64);
+    const int oi = __shfl_xor(ai, o, 64);
+    if (ov > mx || (ov == mx && oi < ai)) { mx = ov; ai = oi; }
+  }
+  if (l == 0) { s_val[w] = mx; s_idx[w] = ai; }
+  __syncthreads();
+  mx = s_val[0]; ai = s_idx[0];
+#pragma unroll
+  for (int i = 1; i < 4; ++i)
+    if (s_val[i] > mx || (s_val[i] == mx && s_idx[i] < ai)) { mx = s_val[i]; ai = s_idx[i]; }
+  __syncthreads();   // the slots are reused by the next reduction
+}
+
 // Entry k of row r of one sample (lg = its logits row of hop 0, hop stride hs):
 //   r < H    hop r's logits;
 //   r == H   uni, SS:482 + 522: uni_pred:zero(), :add(l_h) for h = 1..H, :div(nHop) -- sequential

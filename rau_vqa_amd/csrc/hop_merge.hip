@@ -11,29 +11,11 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
-#include "hop_merge.h"   // kMT, block_sum, row_val, select_hop: shared with topk.hip
+#include "hop_merge.h"   // kMT, block_sum, block_first_max, row_val, select_hop: shared with topk.hip, ce_set.hip
 #include "kernels.h"
 
 namespace rau {
 namespace {
-
-// torch.max's first-max over the workgroup (k_ce_fwd's rule): the largest value, lowest index on ties
-__device__ __forceinline__ void block_first_max(float& mx, int& ai, float* s_val, int* s_idx) {
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(mx, o, 64);
-    const int oi = __shfl_xor(ai, o, 64);
-    if (ov > mx || (ov == mx && oi < ai)) { mx = ov; ai = oi; }
-  }
-  if (l == 0) { s_val[w] = mx; s_idx[w] = ai; }
-  __syncthreads();
-  mx = s_val[0]; ai = s_idx[0];
-#pragma unroll
-  for (int i = 1; i < 4; ++i)
-    if (s_val[i] > mx || (s_val[i] == mx && s_idx[i] < ai)) { mx = s_val[i]; ai = s_idx[i]; }
-  __syncthreads();   // the slots are reused by the next reduction
-}
 
 // CrossEntropyCriterion of row r against label y (0-based) with k_ce_fwd's formulation: max, sum of
 // exp(l - max) in the same thread-strided order, lse - l_y.  Also the row's first-max index.
@@ -96,6 +78,124 @@ __global__ __launch_bounds__(kMT) void k_step_stats_rows(int H, int B, int K,
     c[H + 2 + h] = (fire == c[h]) && did;   // SS:552, masked by did_correct
     c[2 * H + 3 + h] = fire;
     c[3 * H + 3 + h] = h == hsel;
+  }
+}
+
+// max, first-max index and log-sum-exp of row r, in row_ce's order
+__device__ void row_lse(const float* __restrict__ lg, size_t hs, int H, int K, int r, int hsel, float* s_val,
+                        int* s_idx, float* s_sum, float& lse, int& ans) {
+  const int tid = threadIdx.x;
+  float mx = -INFINITY;
+  int ai = 0x7fffffff;
+  for (int k = tid; k < K; k += kMT) {
+    const float v = row_val(lg, hs, H, r, hsel, k);
+    if (v > mx) { mx = v; ai = k; }
+  }
+  block_first_max(mx, ai, s_val, s_idx);
+  float den = 0.f;
+  for (int k = tid; k < K; k += kMT) den += expf(row_val(lg, hs, H, r, hsel, k) - mx);
+  den = block_sum(den, s_sum);
+  lse = mx + logf(den);
+  ans = ai;
+}
+
+// metric score of the 0-based answer a against the set in LDS: sum of the matching entries' scores in entry order
+__device__ __forceinline__ float set_score(const int* s_id, const float* s_sc, int G, int a) {
+  float s = 0.f;
+  for (int g = 0; g < G; ++g)
+    if (s_id[g] == a) s = __fadd_rn(s, s_sc[g]);
+  return s;
+}
+
+// k_step_stats_rows for a batch with an answer set (rau_set_answers): the label y becomes the set.  An answer
+// is correct when it carries a positive score (scores are >= 0: some matching non-empty entry has score > 0),
+// the uni / select CE are the soft CE of ce_set.hip, sum_g w_g (lse - row[y_g]) from 0 in entry order.  Also
+// rowscore [H+2][B]: the score of every row's answer.
+__global__ __launch_bounds__(kMT) void k_step_stats_rows_set(int H, int B, int K,
+    const float* __restrict__ logits, const float* __restrict__ dopred, const int32_t* __restrict__ argmax,
+    const int32_t* __restrict__ ids, const float* __restrict__ w, const float* __restrict__ score, int G,
+    float* __restrict__ rowf, int32_t* __restrict__ rowi, float* __restrict__ rowscore) {
+  __shared__ float s_val[4];
+  __shared__ int s_idx[4];
+  __shared__ float s_sum[4];
+  __shared__ int s_id[kMaxAnswers];
+  __shared__ float s_w[kMaxAnswers];
+  __shared__ float s_sc[kMaxAnswers];
+  const int b = blockIdx.x;
+  const size_t hs = (size_t)B * K;
+  const float* lg = logits + (size_t)b * K;
+  if (threadIdx.x < G) {
+    const size_t e = (size_t)b * G + threadIdx.x;
+    const int id = min(max(ids[e], 0), K);
+    s_id[threadIdx.x] = id - 1;
+    s_w[threadIdx.x] = id > 0 ? w[e] : 0.f;
+    s_sc[threadIdx.x] = id > 0 ? score[e] : 0.f;
+  }
+  __syncthreads();
+  const int hsel = select_hop(dopred, H, B, b, false);   // feval: the last hop is not forced
+  float lse_u, lse_s;
+  int a_u, a_s;
+  row_lse(lg, hs, H, K, H, hsel, s_val, s_idx, s_sum, lse_u, a_u);
+  row_lse(lg, hs, H, K, H + 1, hsel, s_val, s_idx, s_sum, lse_s, a_s);
+  if (threadIdx.x != 0) return;
+  float* f = rowf + (size_t)b * (H + 2);
+  int32_t* c = rowi + (size_t)b * (4 * H + 3);
+  float ce_u = 0.f, ce_s = 0.f;
+  for (int g = 0; g < G; ++g) {
+    if (s_id[g] < 0) continue;
+    ce_u = __fadd_rn(ce_u, __fmul_rn(s_w[g], lse_u - row_val(lg, hs, H, H, hsel, s_id[g])));
+    ce_s = __fadd_rn(ce_s, __fmul_rn(s_w[g], lse_s - row_val(lg, hs, H, H + 1, hsel, s_id[g])));
+  }
+  f[0] = ce_u;
+  f[1] = ce_s;
+  int did = 0;
+  for (int h = 0; h < H; ++h) {
+    const float sc = set_score(s_id, s_sc, G, argmax[(size_t)h * B + b] - 1);
+    rowscore[(size_t)h * B + b] = sc;
+    const int gt = sc > 0.f;
+    c[h] = gt;
+    did |= gt;
+  }
+  const float sc_u = set_score(s_id, s_sc, G, a_u), sc_s = set_score(s_id, s_sc, G, a_s);
+  rowscore[(size_t)H * B + b] = sc_u;
+  rowscore[(size_t)(H + 1) * B + b] = sc_s;
+  c[H] = sc_u > 0.f;
+  c[H + 1] = sc_s > 0.f;
+  c[2 * H + 2] = did;
+  for (int h = 0; h < H; ++h) {
+    const float x = dopred[(size_t)h * B + b];
+    const int fire = x > 0.5f;
+    const float t = c[h] ? 1.f : 0.f;
+    f[2 + h] = -(t * logf(x + 1e-12f) + (1.f - t) * logf(1.f - x + 1e-12f));
+    c[H + 2 + h] = (fire == c[h]) && did;
+    c[2 * H + 3 + h] = fire;
+    c[3 * H + 3 + h] = h == hsel;
+  }
+}
+
+// out[r][b] = score of the 1-based answer ans[r][b] against sample b's set; one thread per (r, b)
+__global__ __launch_bounds__(kMT) void k_answer_scores(int R, int B, int K, const int32_t* __restrict__ ans,
+    const int32_t* __restrict__ ids, const float* __restrict__ score, int G, float* __restrict__ out) {
+  const int i = blockIdx.x * kMT + threadIdx.x;
+  if (i >= R * B) return;
+  const int b = i % B, a = ans[i];
+  float s = 0.f;
+  for (int g = 0; g < G; ++g) {
+    const int id = min(max(ids[(size_t)b * G + g], 0), K);
+    if (id > 0 && id == a) s = __fadd_rn(s, score[(size_t)b * G + g]);
+  }
+  out[i] = s;
+}
+
+// One workgroup: tot[r] = sum_b x[r][b], lane-strided over the batch then wave_sum: a fixed order
+__global__ __launch_bounds__(kMT) void k_score_totals(int R, int B, const float* __restrict__ x,
+                                                      float* __restrict__ tot) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int r = w; r < R; r += 4) {
+    float acc = 0.f;
+    for (int b = l; b < B; b += 64) acc += x[(size_t)r * B + b];
+    acc = wave_sum(acc);
+    if (l == 0) tot[r] = acc;
   }
 }
 
@@ -186,6 +286,27 @@ hipError_t step_stats(hipStream_t st, int H, int B, int K, const float* logits, 
   hipLaunchKernelGGL(k_step_stats_rows, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, argmax, labels,
                      rowf, rowi);
   hipLaunchKernelGGL(k_step_stats_reduce, dim3(1), dim3(kMT), 0, st, H, B, lossrow, rowf, rowi, out);
+  return hipGetLastError();
+}
+
+hipError_t step_stats_set(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
+                          const int32_t* argmax, const float* lossrow, const int32_t* ids, const float* w,
+                          const float* score, int G, float* rowf, int32_t* rowi, float* out, float* rowscore,
+                          float* tot) {
+  if (G < 1 || G > kMaxAnswers || !ids || !w || !score) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_step_stats_rows_set, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, argmax, ids, w,
+                     score, G, rowf, rowi, rowscore);
+  hipLaunchKernelGGL(k_step_stats_reduce, dim3(1), dim3(kMT), 0, st, H, B, lossrow, rowf, rowi, out);
+  hipLaunchKernelGGL(k_score_totals, dim3(1), dim3(kMT), 0, st, H + 2, B, rowscore, tot);
+  return hipGetLastError();
+}
+
+hipError_t answer_scores(hipStream_t st, int R, int B, int K, const int32_t* ans, const int32_t* ids,
+                         const float* score, int G, float* out, float* tot) {
+  if (G < 1 || G > kMaxAnswers || !ids || !score) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_answer_scores, dim3((R * B + kMT - 1) / kMT), dim3(kMT), 0, st, R, B, K, ans, ids, score,
+                     G, out);
+  hipLaunchKernelGGL(k_score_totals, dim3(1), dim3(kMT), 0, st, R, B, out, tot);
   return hipGetLastError();
 }
 

@@ -373,6 +373,14 @@ hipError_t ce_fwd(hipStream_t st, int nB, int K, int M, const float* logits,
                   float* logits_out = nullptr,
                   int Bper = 0 /* rows are [hop][sample]: samples per hop (label period, 1/B) */);
 hipError_t loss_reduce(hipStream_t st, int H, int nB, const float* lossrow, float* losses);
+// ce_fwd against an answer set (ce_set.hip, rau_set_answers): ids / w [Bper][G] device, ids 1..K or 0 = empty
+// entry, 1 <= G <= kMaxAnswers; lossrow = sum_g w (lse - lg[y_g]), dl = softmax * (W / Bper) - sum_g onehot_g w / Bper
+// with W = the row's summed weights; everything else as ce_fwd.  G = 1, w = 1 gives ce_fwd's bits.
+constexpr int kMaxAnswers = 16;
+hipError_t ce_set_fwd(hipStream_t st, int nB, int K, int M, const float* logits, const int32_t* ids,
+                      const float* w, int G, const float* mf, const float* wd, const float* bd, float* dl,
+                      float* lossrow, int32_t* argmax, float* dopred, const float* part = nullptr,
+                      int nsplit = 0, const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0);
 hipError_t scale_hops(hipStream_t st, int H, size_t per_hop, const float* w_dev, float* x);
 // x_i[h][0 .. p_i) *= w[h] for three hop-major tensors in one launch
 hipError_t scale_hops3(hipStream_t st, int H, const float* w_dev, size_t p0, float* x0, size_t p1, float* x1,
@@ -414,6 +422,17 @@ hipError_t clip_adam(hipStream_t st, size_t n, float* x, float* g, float* m, flo
 hipError_t step_stats(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
                       const int32_t* argmax, const float* lossrow, const int32_t* labels, float* rowf,
                       int32_t* rowi, float* out);
+// step_stats of a batch with an answer set (ids / w / score [B][G] device): "correct" = the row's first-max
+// answer carries a positive score, uni / select CE are the soft CE of ce_set_fwd; also the metric score of every
+// row's answer, rowscore [H+2][B] (feval rule), and their fixed-order batch sums tot [H+2]
+hipError_t step_stats_set(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
+                          const int32_t* argmax, const float* lossrow, const int32_t* ids, const float* w,
+                          const float* score, int G, float* rowf, int32_t* rowi, float* out, float* rowscore,
+                          float* tot);
+// out[r][b] = sum_g score[b][g] * [ids[b][g] == ans[r][b]] in entry order (ans 1-based, [R][B]), tot[r] = the
+// fixed-order sum of row r over the batch
+hipError_t answer_scores(hipStream_t st, int R, int B, int K, const int32_t* ans, const int32_t* ids,
+                         const float* score, int G, float* out, float* tot);
 // predict_result's merges + answers (SS:633-705, 877-900): oe / mco [H+2][B] 1-based, pred [2][B][K] and
 // att_out [2][B][Sp] (uni, select; either may be null); mc [B][n_mc] device ids 0..K (null: no MC)
 hipError_t predict_rows(hipStream_t st, int H, int B, int K, int Sp, const float* logits, const float* dopred,

@@ -222,6 +222,7 @@ void hold(rau_ctx* ctx, int si, const Batch& b) {
   d.nuniq = b.nuniq;
   d.have = true;
   d.have_labels = b.labels != nullptr;
+  d.ans_G = 0;   // an answer set belongs to the batch it was given to
 }
 
 void make_current(rau_ctx* ctx, int si) {
@@ -250,7 +251,7 @@ int set_batch_sync(rau_ctx* ctx, Batch b) {
     HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
   if (int rc = enqueue_batch(ctx, ctx->st, si, b)) return rc;
   HIPC(hipStreamSynchronize(ctx->st));   // the caller's (pageable) buffers are free on return
-  s.upload_pending = false;
+  s.upload_pending = s.ans_pending = false;
   hold(ctx, si, b);
   ctx->fwd_done = false;
   return RAU_OK;
@@ -277,7 +278,7 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   // that call performs the same wait before the caller's own writes -- include/rau.h.)
   if (s.upload_pending) {
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = false;
+    s.upload_pending = s.ans_pending = false;
   }
   // NULL = the caller has filled the slot's pinned staging in place (rau_batch_slot)
   if (b.feats && b.feats != s.feats_h) std::memcpy(s.feats_h, b.feats, nf * feat_elem_bytes(b.feat_type));
@@ -310,6 +311,29 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   if (slot == ctx->cur_slot) {   // re-filled in place: the next forward waits for the copies
     make_current(ctx, slot);
     HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
+  }
+  return RAU_OK;
+}
+
+// first answer set of a slot: its device block ids | w | score (each [capacity][kMaxAnswers]) and the pinned
+// staging the copies read
+int ensure_answers(rau_ctx* ctx, int si) {
+  BatchSlot& s = ctx->slot[si];
+  const size_t n = (size_t)ctx->cap * kMaxAnswers;
+  if (!s.ans_ids_d) {
+    int32_t* d = nullptr;
+    if (int rc = dalloc(ctx, &d, 3 * n)) return rc;
+    s.ans_ids_d = d;
+    s.ans_w_d = reinterpret_cast<float*>(d + n);
+    s.ans_score_d = reinterpret_cast<float*>(d + 2 * n);
+    // dalloc clears the block on the chain stream; the slot form copies into it on the copy stream.  Once per slot.
+    HIPC(hipStreamSynchronize(ctx->st));
+  }
+  if (!s.ans_h) {
+    void* h = nullptr;
+    hipError_t e = hipHostMalloc(&h, 3 * n * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(answer staging): %s", hipGetErrorString(e));
+    s.ans_h = static_cast<int32_t*>(h);
   }
   return RAU_OK;
 }
@@ -386,7 +410,7 @@ int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_
   BatchSlot& s = ctx->slot[slot];
   if (s.upload_pending) {   // the caller is about to overwrite the staging: its last copy must have left
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = false;
+    s.upload_pending = s.ans_pending = false;
   }
   if (feats_host) *feats_host = s.feats_h;
   if (tokens_host) *tokens_host = s.tokens_h;
@@ -443,6 +467,76 @@ int rau_use_batch(rau_ctx* ctx, int slot) {
   // the bulk and weight-gradient streams start each step behind an event of the chain stream,
   // so ordering the chain stream behind the upload orders all three
   HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
+  return RAU_OK;
+}
+
+// An answer set for the batch in a slot (slot < 0: the resident batch, synchronous like rau_set_batch; 0 | 1: on
+// the copy stream behind the slot's batch, nothing synchronised).  Everything is checked before anything moves.
+int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const float* w, const float* score) {
+  NEED(ctx && ids && w, "null argument");
+  NEED(slot >= -1 && slot <= 1, "rau_set_answers: slot %d (-1 = the resident batch, 0 or 1)", slot);
+  const rau_config& c = ctx->cfg;
+  const int si = slot < 0 ? ctx->cur_slot : slot;
+  BatchSlot& s = ctx->slot[si];
+  if (!s.held.have)
+    return fail(RAU_ERR_STATE, "rau_set_answers: slot %d holds no batch (upload the batch first)", si);
+  if (slot >= 0 && si == ctx->cur_slot && ctx->fwd_done)
+    return fail(RAU_ERR_STATE, "rau_set_answers: slot %d is the current batch of a forward pass whose backward has "
+                "not run", si);
+  NEED(G >= 1 && G <= kMaxAnswers, "rau_set_answers: G=%d out of [1,%d]", G, kMaxAnswers);
+  const size_t n = (size_t)c.B * G;
+  for (size_t i = 0; i < n; ++i) {
+    NEED(ids[i] >= 0 && ids[i] <= c.K, "rau_set_answers: ids[%zu]=%d out of [0,%d] (0 = empty entry)", i, ids[i], c.K);
+    NEED(std::isfinite(w[i]) && w[i] >= 0.f, "rau_set_answers: w[%zu]=%g is negative or not finite", i, (double)w[i]);
+    if (score)
+      NEED(std::isfinite(score[i]) && score[i] >= 0.f, "rau_set_answers: score[%zu]=%g is negative or not finite", i,
+           (double)score[i]);
+  }
+  if (slot >= 0)
+    if (int rc = ensure_async(ctx)) return rc;
+  if (int rc = ensure_answers(ctx, si)) return rc;
+  if (s.ans_pending) {   // the staging's previous set has not left it yet (two sets for one upload)
+    HIPC(hipEventSynchronize(s.uploaded));
+    s.upload_pending = s.ans_pending = false;
+  }
+  int32_t* ids_h = s.ans_h;
+  float* w_h = reinterpret_cast<float*>(s.ans_h + n);
+  float* sc_h = reinterpret_cast<float*>(s.ans_h + 2 * n);
+  std::memcpy(ids_h, ids, n * 4);
+  std::memcpy(w_h, w, n * 4);
+  std::memcpy(sc_h, score ? score : w, n * 4);
+  hipStream_t st = slot < 0 ? ctx->st : ctx->stc;
+  if (slot < 0) {
+    if (s.upload_pending) HIPC(hipStreamWaitEvent(st, s.uploaded, 0));   // behind an asynchronous upload of the batch
+  } else {
+    // the slot's buffers may still be read by the last step that used them
+    if (si == ctx->cur_slot) {
+      HIPC(hipEventRecord(s.consumed, ctx->st));
+      s.consumed_valid = true;
+    }
+    if (s.consumed_valid) HIPC(hipStreamWaitEvent(st, s.consumed, 0));
+  }
+  HIPC(hipMemcpyAsync(s.ans_ids_d, ids_h, n * 4, hipMemcpyHostToDevice, st));
+  HIPC(hipMemcpyAsync(s.ans_w_d, w_h, n * 4, hipMemcpyHostToDevice, st));
+  HIPC(hipMemcpyAsync(s.ans_score_d, sc_h, n * 4, hipMemcpyHostToDevice, st));
+  if (slot < 0) {
+    HIPC(hipStreamSynchronize(st));
+    if (s.upload_pending) s.upload_pending = false;   // (the chain stream waited for it above)
+  } else {
+    HIPC(hipEventRecord(s.uploaded, st));   // rau_use_batch orders the step behind the set too
+    s.upload_pending = s.ans_pending = true;
+    if (si == ctx->cur_slot) HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
+  }
+  s.held.ans_G = G;
+  s.held.have_labels = true;   // the set is the batch's ground truth
+  if (si == ctx->cur_slot) ctx->fwd_done = false;
+  if (si == ctx->mg_slot) ctx->mg_valid = false;   // statistics of a forward that read the slot's previous targets
+  return RAU_OK;
+}
+
+int rau_batch_answers(rau_ctx* ctx, int32_t* G) {
+  NEED(ctx && G, "null argument");
+  *G = cur_batch(ctx).held.ans_G;
   return RAU_OK;
 }
 

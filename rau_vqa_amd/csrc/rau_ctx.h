@@ -82,6 +82,9 @@ struct BatchDesc {
   std::vector<int32_t> lens;
   int max_len = 0, nuniq = 0;
   bool have = false, have_labels = false;
+  // answer set (rau_set_answers): G entries per sample in the slot's ans_* buffers, 0 = none.  It replaces the
+  // labels for the criterion head and the statistics; a batch with a set counts as labelled.
+  int ans_G = 0;
 };
 // One of the two batch slots.  slot[cur_slot] is the resident batch (cur_batch() below): the only record of it.
 // Slot 0's device buffers exist from rau_create on; slot 1's, the pinned staging the loader may fill in place, the
@@ -101,6 +104,12 @@ struct BatchSlot {
   int32_t *utok_h = nullptr, *ustart_h = nullptr, *upos_h = nullptr;
   int32_t* image_of_h = nullptr;    // pinned host [B]
   int32_t* bank_idx_h = nullptr;    // pinned host [2B]
+  // answer set of the batch: ids | w | score, each [B][G] dense in the current size and G, room for
+  // [capacity][kMaxAnswers]; one device block and one pinned block, allocated at the slot's first set
+  int32_t* ans_ids_d = nullptr;
+  float *ans_w_d = nullptr, *ans_score_d = nullptr;
+  int32_t* ans_h = nullptr;         // pinned host: ids | w | score
+  bool ans_pending = false;         // a copy out of ans_h is behind the last record of `uploaded`
   hipEvent_t uploaded = nullptr;    // recorded on the copy stream behind the slot's H2D copies
   hipEvent_t consumed = nullptr;    // recorded on the chain stream when the ctx switches away from the slot
   // ---- what the device buffers hold
@@ -250,6 +259,12 @@ struct rau_ctx {
   bool mg_valid = false;          // logits / dopred / argmax_d / lossrow / a hold the last step-level forward's
   bool mg_labels = false;         // ... of a batch with labels, read from mg_labels_d
   const int32_t* mg_labels_d = nullptr;
+  int mg_ans_G = 0;               // ... or an answer set of that many entries, read from the three pointers
+  const int32_t* mg_ans_ids = nullptr;
+  const float *mg_ans_w = nullptr, *mg_ans_score = nullptr;
+  uint64_t mg_fwd = 0, mg_pred_fwd = 0;   // forwards recorded so far / the one the last rau_predict read
+  bool mg_pred_mc = false;        // that rau_predict had an MC list
+  float* mg_score = nullptr;      // rau_step_scores / rau_predict_scores: rows [2(H+2)][B] | totals [2(H+2)]
   int mg_slot = 0;                // the batch slot that forward read, and its upload serial then
   uint64_t mg_serial = 0;
   bool mg_ready = false, mg_merged = false;   // buffers allocated / a rau_predict has filled mg_pred, mg_att
@@ -321,6 +336,11 @@ inline void merge_record(rau_ctx* ctx) {
   ctx->mg_valid = true;
   ctx->mg_labels = cur_batch(ctx).held.have_labels;
   ctx->mg_labels_d = cur_batch(ctx).labels_d;
+  ctx->mg_ans_G = cur_batch(ctx).held.ans_G;
+  ctx->mg_ans_ids = cur_batch(ctx).ans_ids_d;
+  ctx->mg_ans_w = cur_batch(ctx).ans_w_d;
+  ctx->mg_ans_score = cur_batch(ctx).ans_score_d;
+  ++ctx->mg_fwd;
   ctx->mg_slot = ctx->cur_slot;
   ctx->mg_serial = ctx->slot_serial[ctx->cur_slot];
 }

@@ -594,6 +594,7 @@ void rau_destroy(rau_ctx* ctx) {
     if (s.feats_h) hipHostFree(s.feats_h);
     if (s.image_of_h) hipHostFree(s.image_of_h);
     if (s.bank_idx_h) hipHostFree(s.bank_idx_h);
+    if (s.ans_h) hipHostFree(s.ans_h);
     if (s.uploaded) hipEventDestroy(s.uploaded);
     if (s.consumed) hipEventDestroy(s.consumed);
   }
@@ -814,7 +815,7 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   // ---- host-side state of a fresh context: no batch, no uploads, seeded masks, no results
   for (int si = 0; si < 2; ++si) {
     ctx->slot[si].held = BatchDesc{};
-    ctx->slot[si].upload_pending = ctx->slot[si].consumed_valid = false;
+    ctx->slot[si].upload_pending = ctx->slot[si].consumed_valid = ctx->slot[si].ans_pending = false;
     ++ctx->slot_serial[si];
   }
   ctx->cur_slot = 0;
@@ -966,6 +967,15 @@ int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const int
     o.slab = ws.slab + reg; o.slab_floats = reg; o.defer_splits = &ns_c;
     RUNS(s, "head_gemm", gflop(rows, K, M), 0,
          gemm_nt(s, rows, K, M, mfh, M, ctx->cls.W, M, lg, K, o));
+  }
+  const BatchSlot& bs = cur_batch(ctx);
+  if (labels && bs.held.ans_G > 0) {   // the batch's answer set is its ground truth (rau_set_answers)
+    RUNS(s, "ce_set_fwd", 0, (double)rows * K * 12,
+         ce_set_fwd(s, rows, K, M, lg, bs.ans_ids_d, bs.ans_w_d, bs.held.ans_G, mfh, ctx->do_pred.W,
+                    ctx->do_pred.b, ctx->dl + (size_t)h0 * B * K, ctx->lossrow + (size_t)h0 * B,
+                    ctx->argmax_d + (size_t)h0 * B, ctx->dopred + (size_t)h0 * B, ws.slab + reg, ns_c,
+                    ctx->cls.b, lg, B));
+    return RAU_OK;
   }
   RUNS(s, "ce_fwd", 0, (double)rows * K * 12,
        ce_fwd(s, rows, K, M, lg, labels, mfh, ctx->do_pred.W, ctx->do_pred.b,
@@ -1861,7 +1871,8 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
   key |= (uint64_t)bs.held.feat_type << 32;  // ... and read the batch in its element type (three bits: 0..5)
   key |= (uint64_t)(bs.held.n_images > 0) << 35;   // ... through the gather of an image table (any table, any N)
   key |= (uint64_t)bs.held.bank << 36;   // ... of a bank batch: out of the bank (rau_bank_destroy reads this bit)
-  key |= (uint64_t)ctx->cfg.B << 37;      // every launch is shaped by the batch size (rau_set_batch_size)
+  key |= (uint64_t)bs.held.ans_G << 37;   // ... against an answer set of G entries (0 = labels): another head kernel
+  key |= (uint64_t)ctx->cfg.B << 42;      // every launch is shaped by the batch size (rau_set_batch_size)
   if (int rc = upload_hop_weights(ctx, hop_w)) return rc;
   ctx->mg_valid = false;
   hipGraphExec_t exec = nullptr;
@@ -1999,6 +2010,7 @@ static int merge_alloc(rau_ctx* ctx) {
   CK(dalloc(ctx, &ctx->mg_ans, 2 * (H + 2) * B));
   CK(dalloc(ctx, &ctx->mg_pred, 2 * B * c.K));
   CK(dalloc(ctx, &ctx->mg_att, 2 * B * ctx->Sp));
+  CK(dalloc(ctx, &ctx->mg_score, 2 * (H + 2) * B + 2 * (H + 2)));
 #undef CK
   ctx->mg_ready = true;
   return RAU_OK;
@@ -2022,15 +2034,68 @@ int rau_step_stats(rau_ctx* ctx, float* loss, float* loss_do_pred, int32_t* coun
   if (int rc = merge_alloc(ctx)) return rc;
   const rau_config& c = ctx->cfg;
   const int H = c.H, B = c.B, K = c.K, NL = 2 * H + 2, NC = RAU_STATS_NCOUNTS(H);
-  RUN("step_stats", 0, (double)B * (2 * H + 2) * K * 4,
-      step_stats(ctx->st, H, B, K, ctx->logits, ctx->dopred, ctx->argmax_d, ctx->lossrow, ctx->mg_labels_d,
-                 ctx->mg_rowf, ctx->mg_rowi, ctx->mg_out));
+  if (ctx->mg_ans_G > 0)
+    RUN("step_stats", 0, (double)B * (2 * H + 2) * K * 4,
+        step_stats_set(ctx->st, H, B, K, ctx->logits, ctx->dopred, ctx->argmax_d, ctx->lossrow, ctx->mg_ans_ids,
+                       ctx->mg_ans_w, ctx->mg_ans_score, ctx->mg_ans_G, ctx->mg_rowf, ctx->mg_rowi, ctx->mg_out,
+                       ctx->mg_score, ctx->mg_score + (size_t)2 * (H + 2) * ctx->cap));
+  else
+    RUN("step_stats", 0, (double)B * (2 * H + 2) * K * 4,
+        step_stats(ctx->st, H, B, K, ctx->logits, ctx->dopred, ctx->argmax_d, ctx->lossrow, ctx->mg_labels_d,
+                   ctx->mg_rowf, ctx->mg_rowi, ctx->mg_out));
   std::vector<float> out((size_t)NL + NC);
   if (int rc = d2h(ctx, out.data(), ctx->mg_out, out.size() * 4)) return rc;
   if (loss) std::memcpy(loss, out.data(), (size_t)(H + 2) * 4);
   if (loss_do_pred) std::memcpy(loss_do_pred, out.data() + H + 2, (size_t)H * 4);
   if (counts) std::memcpy(counts, out.data() + NL, (size_t)NC * 4);
   return RAU_OK;
+}
+
+// Metric scores of the answers (include/rau.h): rows [2(H+2)][cap] of mg_score, then 2(H+2) totals
+int rau_step_scores(rau_ctx* ctx, float* per_sample, float* total) {
+  NEED(ctx, "null ctx");
+  if (int rc = merge_state(ctx, "rau_step_scores", true)) return rc;
+  if (ctx->mg_ans_G <= 0)
+    return fail(RAU_ERR_STATE, "rau_step_scores: the batch of the last forward had no answer set (rau_set_answers)");
+  if (int rc = merge_alloc(ctx)) return rc;
+  const rau_config& c = ctx->cfg;
+  const int H = c.H, B = c.B, K = c.K;
+  float* tot_d = ctx->mg_score + (size_t)2 * (H + 2) * ctx->cap;
+  RUN("step_stats", 0, (double)B * (2 * H + 2) * K * 4,
+      step_stats_set(ctx->st, H, B, K, ctx->logits, ctx->dopred, ctx->argmax_d, ctx->lossrow, ctx->mg_ans_ids,
+                     ctx->mg_ans_w, ctx->mg_ans_score, ctx->mg_ans_G, ctx->mg_rowf, ctx->mg_rowi, ctx->mg_out,
+                     ctx->mg_score, tot_d));
+  if (per_sample)
+    HIPC(hipMemcpyAsync(per_sample, ctx->mg_score, (size_t)(H + 2) * B * 4, hipMemcpyDeviceToHost, ctx->st));
+  if (total) HIPC(hipMemcpyAsync(total, tot_d, (size_t)(H + 2) * 4, hipMemcpyDeviceToHost, ctx->st));
+  HIPC(hipStreamSynchronize(ctx->st));
+  return persist_check(ctx);
+}
+
+int rau_predict_scores(rau_ctx* ctx, float* oe, float* mc, float* totals) {
+  NEED(ctx, "null ctx");
+  if (int rc = merge_state(ctx, "rau_predict_scores", false)) return rc;
+  if (ctx->mg_ans_G <= 0)
+    return fail(RAU_ERR_STATE, "rau_predict_scores: the batch of the last forward had no answer set (rau_set_answers)");
+  if (!ctx->mg_merged || ctx->mg_pred_fwd != ctx->mg_fwd)
+    return fail(RAU_ERR_STATE, "rau_predict_scores: no rau_predict has run on the last forward");
+  const rau_config& c = ctx->cfg;
+  const int H = c.H, B = c.B, R = H + 2;
+  const int rows = ctx->mg_pred_mc ? 2 * R : R;   // mg_ans = oe [R][B] | mc [R][B]
+  float* tot_d = ctx->mg_score + (size_t)2 * R * ctx->cap;
+  RUN("answer_scores", 0, (double)rows * B * 8,
+      answer_scores(ctx->st, rows, B, c.K, ctx->mg_ans, ctx->mg_ans_ids, ctx->mg_ans_score, ctx->mg_ans_G,
+                    ctx->mg_score, tot_d));
+  if (oe) HIPC(hipMemcpyAsync(oe, ctx->mg_score, (size_t)R * B * 4, hipMemcpyDeviceToHost, ctx->st));
+  if (mc && ctx->mg_pred_mc)
+    HIPC(hipMemcpyAsync(mc, ctx->mg_score + (size_t)R * B, (size_t)R * B * 4, hipMemcpyDeviceToHost, ctx->st));
+  if (totals) {
+    HIPC(hipMemcpyAsync(totals, tot_d, (size_t)R * 4, hipMemcpyDeviceToHost, ctx->st));
+    if (ctx->mg_pred_mc)
+      HIPC(hipMemcpyAsync(totals + R, tot_d + R, (size_t)R * 4, hipMemcpyDeviceToHost, ctx->st));
+  }
+  HIPC(hipStreamSynchronize(ctx->st));
+  return persist_check(ctx);
 }
 
 int rau_predict(rau_ctx* ctx, const int32_t* mc_ans, int32_t n_mc, int32_t* oe, int32_t* mc) {
@@ -2065,6 +2130,8 @@ int rau_predict(rau_ctx* ctx, const int32_t* mc_ans, int32_t n_mc, int32_t* oe, 
   HIPC(hipStreamSynchronize(ctx->st));   // the caller's mc_ans is free on return
   if (int rc = persist_check(ctx)) return rc;
   ctx->mg_merged = true;
+  ctx->mg_pred_fwd = ctx->mg_fwd;
+  ctx->mg_pred_mc = nmc != 0;
   return RAU_OK;
 }
 

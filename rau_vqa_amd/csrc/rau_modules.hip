@@ -483,8 +483,11 @@ int rau_criterion_forward(rau_ctx* ctx, int h, const float* logits, const int32_
   NEED(h >= 0 && h < c.H, "rau_criterion_forward: h=%d out of [0,%d)", h, c.H);
   if (int rc = mod_alloc(ctx)) return rc;
   if (!labels_dev) {
-    if (!cur_batch(ctx).held.have_labels) return fail(RAU_ERR_STATE, "rau_criterion_forward: no labels");
-    labels_dev = cur_batch(ctx).labels_d;
+    const BatchSlot& bs = cur_batch(ctx);
+    if (!bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_criterion_forward: no labels");
+    if (bs.held.ans_G > 0)   // the resident batch's ground truth is its answer set
+      return rau_criterion_forward_set(ctx, h, logits, bs.held.ans_G, bs.ans_ids_d, bs.ans_w_d, loss);
+    labels_dev = bs.labels_d;
   }
   RUN("ce_fwd", 0, (double)c.B * c.K * 12,
       ce_fwd(ctx->st, c.B, c.K, c.M, logits, labels_dev, nullptr, nullptr, nullptr,
@@ -506,13 +509,54 @@ int rau_criterion_backward(rau_ctx* ctx, int h, const float* logits, const int32
   NEED(h >= 0 && h < c.H, "rau_criterion_backward: h=%d out of [0,%d)", h, c.H);
   if (int rc = mod_alloc(ctx)) return rc;
   if (!labels_dev) {
-    if (!cur_batch(ctx).held.have_labels) return fail(RAU_ERR_STATE, "rau_criterion_backward: no labels");
-    labels_dev = cur_batch(ctx).labels_d;
+    const BatchSlot& bs = cur_batch(ctx);
+    if (!bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_criterion_backward: no labels");
+    if (bs.held.ans_G > 0)
+      return rau_criterion_backward_set(ctx, h, logits, bs.held.ans_G, bs.ans_ids_d, bs.ans_w_d, scale, d_logits);
+    labels_dev = bs.labels_d;
   }
   float* dl = ctx->dl + (size_t)h * c.B * c.K;
   RUN("ce_fwd", 0, (double)c.B * c.K * 12,
       ce_fwd(ctx->st, c.B, c.K, c.M, logits, labels_dev, nullptr, nullptr, nullptr, dl,
              ctx->lossrow + (size_t)h * c.B, ctx->argmax_d + (size_t)h * c.B, nullptr));
+  if (scale != 1.f)   // dpred:mul(nHop), SS:569
+    RUN("scale_hops", 0, (double)c.B * c.K * 8, scale_inplace(ctx->st, (size_t)c.B * c.K, scale, dl));
+  *d_logits = dl;
+  return RAU_OK;
+}
+
+// criteria[h] against an answer set in device memory (ids / w [B,G]): the kernel of the step's head (ce_set.hip)
+int rau_criterion_forward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
+                              const float* w_dev, float* loss) {
+  NEED(ctx && logits && ids_dev && w_dev, "null argument");
+  const rau_config& c = ctx->cfg;
+  NEED(h >= 0 && h < c.H, "rau_criterion_forward_set: h=%d out of [0,%d)", h, c.H);
+  NEED(G >= 1 && G <= kMaxAnswers, "rau_criterion_forward_set: G=%d out of [1,%d]", G, kMaxAnswers);
+  if (int rc = mod_alloc(ctx)) return rc;
+  RUN("ce_set_fwd", 0, (double)c.B * c.K * 12,
+      ce_set_fwd(ctx->st, c.B, c.K, c.M, logits, ids_dev, w_dev, G, nullptr, nullptr, nullptr,
+                 ctx->dl + (size_t)h * c.B * c.K, ctx->lossrow + (size_t)h * c.B,
+                 ctx->argmax_d + (size_t)h * c.B, nullptr));
+  RUN("loss_reduce", 0, 0,
+      loss_reduce(ctx->st, 1, c.B, ctx->lossrow + (size_t)h * c.B, ctx->m_loss + h));
+  if (loss) {
+    HIPC(hipMemcpyAsync(loss, ctx->m_loss + h, sizeof(float), hipMemcpyDeviceToHost, ctx->st));
+    HIPC(hipStreamSynchronize(ctx->st));
+  }
+  return RAU_OK;
+}
+
+int rau_criterion_backward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
+                               const float* w_dev, float scale, float** d_logits) {
+  NEED(ctx && logits && ids_dev && w_dev && d_logits, "null argument");
+  const rau_config& c = ctx->cfg;
+  NEED(h >= 0 && h < c.H, "rau_criterion_backward_set: h=%d out of [0,%d)", h, c.H);
+  NEED(G >= 1 && G <= kMaxAnswers, "rau_criterion_backward_set: G=%d out of [1,%d]", G, kMaxAnswers);
+  if (int rc = mod_alloc(ctx)) return rc;
+  float* dl = ctx->dl + (size_t)h * c.B * c.K;
+  RUN("ce_set_fwd", 0, (double)c.B * c.K * 12,
+      ce_set_fwd(ctx->st, c.B, c.K, c.M, logits, ids_dev, w_dev, G, nullptr, nullptr, nullptr, dl,
+                 ctx->lossrow + (size_t)h * c.B, ctx->argmax_d + (size_t)h * c.B, nullptr));
   if (scale != 1.f)   // dpred:mul(nHop), SS:569
     RUN("scale_hops", 0, (double)c.B * c.K * 8, scale_inplace(ctx->st, (size_t)c.B * c.K, scale, dl));
   *d_logits = dl;

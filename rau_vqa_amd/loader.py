@@ -37,6 +37,16 @@ class QuestionSet:
     answers: np.ndarray = None    # [N] 1-based answer id (train)
     mc_ans: np.ndarray = None     # [N, nMC] (test)
     datatype: np.ndarray = None   # [N] 1-based index into tab_featpaths
+    # multi-answer ground truth (rau_set_answers), all optional: [N, G] answer ids (1-based, 0 = empty entry),
+    # loss weights, metric scores (None: the weights), e.g. vqa_scores(counts)
+    ans_ids: np.ndarray = None
+    ans_w: np.ndarray = None
+    ans_score: np.ndarray = None
+
+
+def vqa_scores(counts):
+    """The VQA accuracy of an answer that `counts` of the ten annotators gave: min(counts / 3, 1), float32."""
+    return np.minimum(np.asarray(counts, np.float32) / np.float32(3), np.float32(1)).astype(np.float32)
 
 
 def feature_name(img_path: str) -> str:
@@ -68,6 +78,7 @@ class DataClass:
         self._next_dest = None    # SlotFeeder: where the prefetch worker assembles the next batch
         self._unique = False      # the last next_batch_feat asked for an image table: so will the prefetched one
         self._bank = None         # (key, files, row of every question): bank_rows' answer for one tab_featpaths
+        self.last_answers = None  # (ids, w[, score]) rows of the batch last taken, when qs carries answer sets
 
     # ---- batch order options, loader.lua:1219-1291
     def set_batch_order_option(self, opt):
@@ -192,6 +203,12 @@ class DataClass:
         qids = np.ascontiguousarray(self.qs.question_id[idx])
         src = self.qs.answers if self.split == "train" else self.qs.mc_ans
         a = np.ascontiguousarray(src[idx], np.int32)
+        self.last_answers = None
+        if self.qs.ans_ids is not None and self.qs.ans_w is not None:
+            self.last_answers = (np.ascontiguousarray(self.qs.ans_ids[idx], np.int32),
+                                 np.ascontiguousarray(self.qs.ans_w[idx], np.float32))
+            if self.qs.ans_score is not None:
+                self.last_answers += (np.ascontiguousarray(self.qs.ans_score[idx], np.float32),)
         self.batch_index += B
         if self.batch_index + B > self.n:                # loader.lua:911-913
             self.reorder()
@@ -300,12 +317,21 @@ def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=12
     return v
 
 
-def feed(rau, batch, feat_type=None):
+def feed(rau, batch, feat_type=None, answers=None):
     """next_batch_feat's tuple -> rau_set_batch (the H2D of SS:434-439); returns qids.
     feat_type: that of the feats (needed for bf16 and fp8, which arrive as uint16 / uint8 bits).  A tuple of
     next_batch_feat(unique=True) goes up as an image table, one of next_batch_rows as a bank batch.
     The batch may be smaller than the context's capacity (a test split at test_batch_size): set_batch
-    takes the size from x_len and switches the context to it."""
+    takes the size from x_len and switches the context to it.
+    answers = (ids, w[, score]) rows of the batch (DataClass.last_answers, when its QuestionSet has ans_ids /
+    ans_w): attached with rau.set_answers once the batch is up; None changes nothing."""
+    qids = _feed_batch(rau, batch, feat_type)
+    if answers is not None:
+        rau.set_answers(*answers)
+    return qids
+
+
+def _feed_batch(rau, batch, feat_type):
     if batch[0].ndim == 1:                                # next_batch_rows: rows, image_of, x, x_len, a, qids
         rows, image_of, x, x_len, a, qids = batch
         rau.set_batch(None, x, x_len, a if a.ndim == 1 else None, bank_rows=rows, image_of=image_of)
@@ -377,6 +403,8 @@ class SlotFeeder:
             if labels:
                 view["labels"][...] = a
             rau.set_batch_async(s, has_labels=labels, bank_rows=rows, image_of=image_of)
+            if d.last_answers is not None:
+                rau.set_answers(*d.last_answers, slot=s)
             rau.use_batch(s)
             return qids
         batch = d.next_batch_feat(*self.args, unique=self.share_images)
@@ -391,6 +419,8 @@ class SlotFeeder:
         if labels:
             view["labels"][...] = a
         rau.set_batch_async(s, has_labels=labels, **table, **self._ft)   # staging filled in place: no host copy
+        if d.last_answers is not None:                # the QuestionSet carries answer sets: behind the upload
+            rau.set_answers(*d.last_answers, slot=s)
         rau.use_batch(s)
         return qids
 

@@ -274,7 +274,61 @@ class RAU:
             raise ValueError("image_of must have one entry per sample")
         return int(rows.size), rows, image_of
 
-    def set_batch(self, feats, tokens, lens, labels=None, feat_type=None, image_of=None, bank_rows=None):
+    # ---- answer sets: multi-answer ground truth (rau_set_answers)
+    MAX_ANSWERS = 16
+
+    def set_answers(self, ids, w, score=None, slot=None):
+        """Give the batch in `slot` (None: the resident batch; 0 | 1: after set_batch_async(slot), before
+        use_batch(slot)) an answer set in place of its labels: ids [n, G] int (1..K, 0 = empty entry), w [n, G]
+        loss weights, score [n, G] metric scores (None: w), G <= 16.  The criterion head then computes
+        sum_g w (lse - logit[y_g]) and its gradient, step_stats counts an answer as correct when it carries a
+        positive score, and step_scores / predict_scores return the scores.  predict.soft_ce / answer_score /
+        set_correct state the contract in numpy.  The set lasts until the next batch goes into that slot."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        w = np.ascontiguousarray(w, np.float32)
+        if ids.ndim != 2 or ids.shape[0] != self._n or w.shape != ids.shape:
+            raise ValueError(f"answer set: ids and w must be [{self._n}, G]")
+        if not 1 <= ids.shape[1] <= self.MAX_ANSWERS:
+            raise ValueError(f"answer set: G={ids.shape[1]} out of [1, {self.MAX_ANSWERS}]")
+        sp = None
+        if score is not None:
+            score = np.ascontiguousarray(score, np.float32)
+            if score.shape != ids.shape:
+                raise ValueError("answer set: score must have the shape of ids")
+            sp = score.ctypes.data
+        L.check(self._lib.rau_set_answers(self._h, -1 if slot is None else int(slot), int(ids.shape[1]),
+                                          ids.ctypes.data, w.ctypes.data, sp))
+
+    @property
+    def batch_answers(self) -> int:
+        """G of the resident batch's answer set, 0 when it has none."""
+        g = C.c_int32()
+        L.check(self._lib.rau_batch_answers(self._h, C.byref(g)))
+        return int(g.value)
+
+    def step_scores(self):
+        """Metric score of every row's answer of the last forward (feval rule, as step_stats) against its
+        batch's answer set: (per_sample [H+2, n], total [H+2]); rows = hops, uni, select."""
+        H = self.cfg.H
+        per = np.empty((H + 2, self._n), np.float32)
+        tot = np.empty(H + 2, np.float32)
+        L.check(self._lib.rau_step_scores(self._h, per.ctypes.data, tot.ctypes.data))
+        return per, tot
+
+    def predict_scores(self, mc=False):
+        """Metric scores of the last predict()'s answers (last hop forced): (oe [H+2, n], mc [H+2, n] or None,
+        totals [2, H+2]); mc=True asks for the MC rows (that predict() must have had an MC list: without one
+        they and totals[1] are not written and come back as zeros)."""
+        H = self.cfg.H
+        oe = np.empty((H + 2, self._n), np.float32)
+        mcs = np.zeros((H + 2, self._n), np.float32) if mc else None
+        tot = np.zeros((2, H + 2), np.float32)
+        L.check(self._lib.rau_predict_scores(self._h, oe.ctypes.data, None if mcs is None else mcs.ctypes.data,
+                                             tot.ctypes.data))
+        return oe, mcs, tot
+
+    def set_batch(self, feats, tokens, lens, labels=None, feat_type=None, image_of=None, bank_rows=None,
+                  answers=None):
         """feat_type "f32" | "f16" | "bf16" | "e4m3" | "e5m2" (default: from the dtype, see feat16.infer;
         bf16 is uint16 bits, fp8 is uint8 codes, both must be named): a 16-bit or fp8 map gives the same
         results, bit for bit, as the f32 map of its widened values.
@@ -282,7 +336,13 @@ class RAU:
         share; the same results, bit for bit, as the plain batch feats[image_of].
         bank_rows [N] (feats None): the table is bank[bank_rows], gathered inside device memory.
         The batch size is lens.shape[0]: a batch of n <= capacity rows switches the context to n first
-        (set_batch_size); every array must agree on n, checked before anything reaches the library."""
+        (set_batch_size); every array must agree on n, checked before anything reaches the library.
+        answers = (ids, w[, score]): set_answers on the batch once it is up."""
+        self._set_batch(feats, tokens, lens, labels, feat_type, image_of, bank_rows)
+        if answers is not None:
+            self.set_answers(*answers)
+
+    def _set_batch(self, feats, tokens, lens, labels, feat_type, image_of, bank_rows):
         c = self.cfg
         lens = np.ascontiguousarray(lens, np.int32)
         B = self._rows(lens, "set_batch")
@@ -362,7 +422,7 @@ class RAU:
                 "labels": view(p[3], B, C.c_int32, np.int32, (B,))}
 
     def set_batch_async(self, slot, feats=None, tokens=None, lens=None, labels=None, has_labels=True,
-                        feat_type=None, image_of=None, n_images=None, bank_rows=None):
+                        feat_type=None, image_of=None, n_images=None, bank_rows=None, answers=None):
         """Enqueue the upload of a batch into `slot` on the copy stream and return.  Arrays left None
         are taken from the slot's staging (filled in place through batch_slot).  feat_type: as in
         set_batch; with feats None it names what the staging holds (default "f32").
@@ -370,7 +430,15 @@ class RAU:
         feats None, of the n_images maps at the start of the slot's staging; only those are uploaded.
         bank_rows [N] (feats None): the table is bank[bank_rows]; the slot's feature staging is not read.
         The batch size is lens.shape[0] when lens is given (the context is switched to it first, which
-        drops both slots' earlier uploads), else the current batch_size."""
+        drops both slots' earlier uploads), else the current batch_size.
+        answers = (ids, w[, score]): set_answers(slot=slot) behind the upload, on the copy stream."""
+        self._set_batch_async(slot, feats, tokens, lens, labels, has_labels, feat_type, image_of, n_images,
+                              bank_rows)
+        if answers is not None:
+            self.set_answers(*answers, slot=slot)
+
+    def _set_batch_async(self, slot, feats, tokens, lens, labels, has_labels, feat_type, image_of, n_images,
+                         bank_rows):
         c = self.cfg
         B = self._n
         if lens is not None:

@@ -103,6 +103,105 @@ def top_answers(tab_pred, k):
     return (order + 1).astype(np.int32), score, conf.astype(np.float32)
 
 
+def soft_ce(pred, ids, w):
+    """Criterion of rau_set_answers on rows pred [B, K] float32 against the answer set ids [B, G] (1-based, 0 =
+    empty entry), w [B, G]: (rows [B] float32, their mean) with rows[b] = sum_g w[b,g] (lse_b - pred[b, y_g]),
+    every operation in float32, accumulated from 0 in g order.  G = 1, w = 1 is joint.cross_entropy."""
+    pred = np.asarray(pred, np.float32)
+    ids = np.asarray(ids, np.int64)
+    w = np.asarray(w, np.float32)
+    B = pred.shape[0]
+    mx = pred.max(axis=1)
+    lse = mx + np.log(np.exp(pred - mx[:, None]).sum(axis=1, dtype=np.float32))
+    rows = np.zeros(B, np.float32)
+    ar = np.arange(B)
+    for g in range(ids.shape[1]):
+        live = ids[:, g] > 0
+        term = w[:, g] * (lse - pred[ar, np.maximum(ids[:, g], 1) - 1])
+        rows = np.where(live, rows + term, rows).astype(np.float32)
+    return rows, np.float32(rows.sum(dtype=np.float32) / np.float32(B))
+
+
+def soft_ce_grad(pred, ids, w):
+    """d mean(soft_ce rows) / d pred as the device forms it: softmax * (W_b / B) - sum_g onehot(y_g) w_g / B,
+    W_b = the row's summed non-empty weights (float64: a reference, not a bit statement)."""
+    pred = np.asarray(pred, np.float64)
+    ids = np.asarray(ids, np.int64)
+    w = np.where(ids > 0, np.asarray(w, np.float64), 0.0)
+    B = pred.shape[0]
+    e = np.exp(pred - pred.max(axis=1, keepdims=True))
+    g = e / e.sum(axis=1, keepdims=True) * w.sum(axis=1, keepdims=True) / B
+    for b in range(B):
+        for j in range(ids.shape[1]):
+            if ids[b, j] > 0:
+                g[b, ids[b, j] - 1] -= w[b, j] / B
+    return g
+
+
+def answer_score(ans, ids, score):
+    """Metric score of the answers ans [..., B] (1-based) against the set: sum_g score[b,g] * [ids[b,g] == ans],
+    float32, added from 0 in g order; empty entries (id 0) never match.  Bit for bit what rau_step_scores /
+    rau_predict_scores return for the device's own answers."""
+    ans = np.asarray(ans, np.int64)
+    ids = np.asarray(ids, np.int64)
+    score = np.asarray(score, np.float32)
+    out = np.zeros(ans.shape, np.float32)
+    for g in range(ids.shape[1]):
+        hit = (ids[:, g] > 0) & (ans == ids[:, g])
+        out = np.where(hit, out + score[:, g], out).astype(np.float32)
+    return out
+
+
+def set_correct(ans, ids, score):
+    """The "correct" rule of a batch with an answer set: the answer is among the row's non-empty ids with
+    score > 0 (never on a row without entries).  Boolean, shape of ans."""
+    ans = np.asarray(ans, np.int64)
+    ids = np.asarray(ids, np.int64)
+    score = np.asarray(score, np.float32)
+    ok = np.zeros(ans.shape, bool)
+    for g in range(ids.shape[1]):
+        ok |= (ids[:, g] > 0) & (score[:, g] > 0) & (ans == ids[:, g])
+    return ok
+
+
+def set_stats(logits, dopred, ids, w, score=None):
+    """joint.feval_stats for a batch with an answer set (rau_step_stats with a set): the same keys, with
+    set_correct in place of (argmax == y) and soft_ce in place of the cross-entropy, plus ``score`` [H+2, B]:
+    answer_score of every row's answer (what rau_step_scores returns)."""
+    logits = np.asarray(logits, np.float32)
+    dopred = np.asarray(dopred, np.float32)
+    score = np.asarray(w if score is None else score, np.float32)
+    H, B, K = logits.shape
+    eps, one = np.float32(1e-12), np.float32(1)
+    fire = dopred > 0.5
+    first = np.where(fire.any(0), fire.argmax(0), -1)              # feval: the last hop is not forced
+    uni = np.zeros((B, K), np.float32)
+    for h in range(H):
+        uni += logits[h]
+    uni = uni / np.float32(H)
+    select = np.zeros((B, K), np.float32)
+    for b in range(B):
+        if first[b] >= 0:
+            select[b] = np.float32(0) + logits[first[b], b]
+    rows = [logits[h] for h in range(H)] + [uni, select]
+    ans = np.stack([first_max(r) for r in rows])
+    ok = set_correct(ans, ids, score)
+    did = ok[:H].any(0)
+    loss = np.array([soft_ce(r, ids, w)[1] for r in rows], np.float32)
+    ldp, dpc = [], []
+    for h in range(H):
+        t = ok[h].astype(np.float32)
+        x = dopred[h]
+        term = -(t * np.log(x + eps) + (one - t) * np.log(one - x + eps))
+        ldp.append(np.float32(term.sum(dtype=np.float32) / np.float32(B)))
+        dpc.append(int(((fire[h] == ok[h]) & did).sum()))
+    return {"loss": loss, "loss_do_pred": np.array(ldp, np.float32), "correct": ok.sum(1).astype(np.int32),
+            "do_pred_correct": np.array(dpc, np.int32), "did_correct": int(did.sum()),
+            "fired": fire.sum(1).astype(np.int32),
+            "selected": np.array([(first == h).sum() for h in range(H)], np.int32),
+            "ans": ans, "score": answer_score(ans, ids, score)}
+
+
 def predict_result(rau, feats, tokens, lens, mc_ans=None, select_att_state=None, image_of=None):
     """SS:633-705 + SS:877-900 for one batch: returns dict(tab_pred, tab_att, oe, mc).
     select_att_state: see merge_hops (carry tab_att[-1] from batch to batch to reproduce the
