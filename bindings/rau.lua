@@ -4,7 +4,7 @@ Presents the reference's nn.Module call surface for the RAU hot path so that
 experiments/Ours_*/LstmAttCtrlGradNoiseDontSelect.lua keeps its structure:
   :training() / :evaluate()          (SS:449-450, 479, 648-649, 676)
   :getParameters()                   (SS:322-324)  -> flat param / grad handles
-  feval's tensor half                (SS:428-596)  -> rau:forward() / rau:backward(w)
+  feval's tensor half                (SS:428-596)  -> rau:forward() / rau:backward(w [, select_w])
   adam(x, dx, lr, ...) x 3 + noise + clip (SS:597-630, 770-772) -> rau:update(...)
 
 No LuaJIT/Torch7 toolchain exists in the build image, so this file is shipped as
@@ -78,6 +78,8 @@ int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const
 int rau_batch_answers(rau_ctx* ctx, int32_t* G);
 int rau_forward(rau_ctx* ctx);
 int rau_backward(rau_ctx* ctx, const float* hop_w);
+int rau_backward_select(rau_ctx* ctx, const float* hop_w, const float* select_w);
+int rau_graph_step_select(rau_ctx* ctx, const float* hop_w, const float* select_w, int zero_grads_first);
 int rau_embed_forward(rau_ctx* ctx, int t, const int32_t* tokens_dev, float** we);
 int rau_embed_backward(rau_ctx* ctx, int t, const int32_t* tokens_dev, const float* d_we);
 int rau_deeplstm_forward(rau_ctx* ctx, int t, const float* x, const float* state,
@@ -366,11 +368,28 @@ function RAU:forward(seed, step)
 end
 
 -- backward half (SS:561-596); hop_w = per-hop criterion-gradient scale (SS:569 / Full:587-589)
-function RAU:backward(hop_w)
-  local H = self.cfg.H
+-- select_w (optional) = per-hop weight of the step-selection head's BCE gradient: the multiplier the reference
+-- fixes at 0 in d_do_pred:mul(0), SS:566; nil keeps that zero
+local function hop_array(H, t)
   local w = ffi.new('float[?]', H)
-  for i = 1, H do w[i - 1] = hop_w[i] end
-  check(C.rau_backward(self.h, w))
+  for i = 1, H do w[i - 1] = t[i] end
+  return w
+end
+function RAU:backward(hop_w, select_w)
+  local H = self.cfg.H
+  local w = hop_array(H, hop_w)
+  if select_w then
+    check(C.rau_backward_select(self.h, w, hop_array(H, select_w)))
+  else
+    check(C.rau_backward(self.h, w))
+  end
+end
+
+-- zeroGradParameters (unless zero_grads == false) + forward + backward as one captured graph launch
+function RAU:graphStep(hop_w, select_w, zero_grads)
+  local H = self.cfg.H
+  local z = (zero_grads == false) and 0 or 1
+  check(C.rau_graph_step_select(self.h, hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil, z))
 end
 
 function RAU:zeroGradParameters() check(C.rau_zero_grads(self.h)) end

@@ -385,11 +385,37 @@ int rau_batch_answers(rau_ctx* ctx, int32_t* G);
  *               CrossEntropyCriterion forward, first-max argmax.
  * rau_backward: SS:561-596  per-hop criterion backward scaled by hop_w[h]
  *               (SS:569 nHop / MS:568-570 one / Full:587-589 0|1), RAU BPTT,
- *               d_do_pred*0 and gradattprob=0, dq=sum over hops, encoder BPTT,
- *               LookupTable scatter.  Gradients ACCUMULATE into the flat grad
- *               buffers like accGradParameters; call rau_zero_grads first. */
+ *               gradattprob=0, dq=sum over hops, encoder BPTT, LookupTable
+ *               scatter; the gradient at do_pred is the reference's zero (SS:566)
+ *               here and per-hop weighted in rau_backward_select below.
+ *               Gradients ACCUMULATE into the flat grad buffers like
+ *               accGradParameters; call rau_zero_grads first. */
 int rau_forward(rau_ctx* ctx);
 int rau_backward(rau_ctx* ctx, const float* hop_w /* [H] host */);
+
+/* ---- training the step-selection head ----------------------------------------------------------
+ * do_pred = sum(sigmoid(Linear(M,1)(merge_feat))) (SS:281) decides every "select" output.  The reference forms
+ * its BCE gradient (criterion SS:555, :backward SS:565) and multiplies it by 0 (SS:566, the script's "DontSelect").
+ * rau_backward_select makes that multiplier a per-hop argument: select_w [H] host, NULL = zeros.
+ * For hop h and row b of the last step-level forward, n = the current batch size, x = do_pred[h,b], float32:
+ *   t   = rau_step_stats' do_pred_gt: 1 when the hop's first-max answer equals the label, or (answer set) is
+ *         among the row's non-empty ids with a positive score; else 0.  A constant: no gradient flows through it.
+ *   ddp = select_w[h] * ( -(t - x) / ((1 - x + eps) * (x + eps)) ) / n,   eps = 1e-12f, in this order
+ *         (nn.BCECriterion:backward with sizeAverage, scaled where the reference scales it)
+ *   s   = ddp * x * (1 - x)                                                (through the sigmoid)
+ *   dmf[h,b,:] += s * do_pred.weight, in front of the merge_feat dropout mask;
+ *   d(do_pred.weight) += sum_{h,b} s mf[h,b,:],  d(do_pred.bias) += sum_{h,b} s, summed in a fixed order (no
+ *   float atomics: repeated calls give the same bits); f32 dot products in every dtype, like the head itself.
+ * Active hops: [0, HA), HA - 1 the last hop with hop_w[h] != 0 or select_w[h] != 0; hops behind it are skipped.
+ * select_w == NULL or all zeros IS rau_backward: the same launches, the same bits.  Otherwise the forward's labels
+ * or answer set must still be there: RAU_ERR_STATE, nothing launched, when that batch had neither or its slot has
+ * been uploaded into since (the rule of rau_step_stats); every state rule of rau_backward applies as well.  A
+ * non-finite weight in either array: RAU_ERR_INVALID.  Its scratch ([H,B,M] floats) is allocated at the first
+ * call with a non-zero weight.
+ * rau_graph_step_select is rau_graph_step with that backward: select_w is read from device memory like hop_w, so
+ * it may change between replays; whether any entry is non-zero joins the cache key with the active-hop count. */
+int rau_backward_select(rau_ctx* ctx, const float* hop_w /* [H] host */, const float* select_w /* [H] host, NULL = zeros */);
+int rau_graph_step_select(rau_ctx* ctx, const float* hop_w, const float* select_w, int zero_grads_first);
 
 /* ---- module-level entry points: one call per nn.Module :forward / :backward -----
  * For hosts that keep feval's own loops (SS:443-596) and call the clones one by one.

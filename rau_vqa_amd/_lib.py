@@ -103,6 +103,9 @@ _SIGS = {
                                           C.c_void_p, C.c_void_p, C.c_int]),
     "rau_forward": (C.c_int, [C.c_void_p]),
     "rau_backward": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # the same with the step-selection head's BCE gradient, weighted per hop (NULL = zeros)
+    "rau_backward_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rau_graph_step_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     # module-level entry points: device pointers in, pointers to ctx-owned slots out
     "rau_embed_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_embed_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

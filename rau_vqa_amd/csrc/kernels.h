@@ -381,6 +381,15 @@ hipError_t ce_set_fwd(hipStream_t st, int nB, int K, int M, const float* logits,
                       const float* w, int G, const float* mf, const float* wd, const float* bd, float* dl,
                       float* lossrow, int32_t* argmax, float* dopred, const float* part = nullptr,
                       int nsplit = 0, const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0);
+// The step-selection head's gradient (select_bwd.hip, rau_backward_select).  rows = active hops x Bper, hop-major.
+// select_signal: s[r] = select_w[h] * BCE'(do_pred, do_pred_gt) / Bper * x (1 - x) and add[r][m] = s[r] wd[m];
+// do_pred_gt from the labels [Bper] (G == 0) or an answer set ids / score [Bper][G] (rau_step_stats' rules).
+// select_wgrad: dW[m] += sum_r s[r] mf[r][m], db[0] += sum_r s[r], one fixed-order pass (any M, any row count).
+hipError_t select_signal(hipStream_t st, int rows, int Bper, int K, int M, const float* dopred,
+                         const int32_t* argmax, const int32_t* labels, const int32_t* ids, const float* score,
+                         int G, const float* selw_dev, const float* wd, float* s, float* add);
+hipError_t select_wgrad(hipStream_t st, int rows, int M, const float* s, const float* mf, float* dW,
+                        float* db);
 hipError_t scale_hops(hipStream_t st, int H, size_t per_hop, const float* w_dev, float* x);
 // x_i[h][0 .. p_i) *= w[h] for three hop-major tensors in one launch
 hipError_t scale_hops3(hipStream_t st, int H, const float* w_dev, size_t p0, float* x0, size_t p1, float* x1,

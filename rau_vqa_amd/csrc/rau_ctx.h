@@ -225,8 +225,12 @@ struct rau_ctx {
   int* perr_h = nullptr;
   bool persist_used = false;
   bool persist_gave_up = false; // persist_check() turned the persistent encoder off: it stays off across resizes
-  float* hopw_h = nullptr;    // pinned staging of the hop weights, 2 slots of H
+  float* hopw_h = nullptr;    // pinned staging of the hop weights, 2 slots of 2H: hop_w [H] | select_w [H]
   int hopw_slot = 0;
+  // step-selection head's gradient (rau_backward_select, select_bwd.hip); hopw_d is [2H]: hop_w | select_w
+  float *sel_s = nullptr, *sel_add = nullptr;   // [H][cap] s rows, [H][cap][M] s (x) wd; allocated at first use
+  bool sel_capture = false;   // rau_graph_step_select is capturing a step with a non-zero select weight: its backward
+                              // forms dpre / dhn itself, so the forward leaves them alone
   // backward temporaries
   // dZ holds dI (gradient at i_embed's OUTPUT); the tanh derivative is applied by its consumers
   float *dpre, *dhn, *dg4, *dcn[2], *dhp[2], *dj, *da_lin, *dz, *du, *dwsp, *dZ,

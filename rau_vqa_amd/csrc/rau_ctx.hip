@@ -500,9 +500,9 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   CK(dalloc(ctx, &ctx->lossrow, HB));
   CK(dalloc(ctx, &ctx->dopred, HB));
   CK(dalloc(ctx, &ctx->losses_d, (size_t)H));
-  CK(dalloc(ctx, &ctx->hopw_d, (size_t)H));
+  CK(dalloc(ctx, &ctx->hopw_d, (size_t)2 * H));   // hop_w | select_w
   {  // ctx-owned pinned staging for the hop weights: the async upload never reads caller memory
-    hipError_t eh = hipHostMalloc((void**)&ctx->hopw_h, (size_t)2 * H * sizeof(float), hipHostMallocDefault);
+    hipError_t eh = hipHostMalloc((void**)&ctx->hopw_h, (size_t)4 * H * sizeof(float), hipHostMallocDefault);
     if (eh != hipSuccess) {
       rau_destroy(ctx);
       return fail(RAU_ERR_NOMEM, "hipHostMalloc(hop weights): %s", hipGetErrorString(eh));
@@ -1161,7 +1161,7 @@ static int seam_mask() {
   return m;
 }
 static bool head_dgrad_fwd(const rau_ctx* ctx) {
-  return cur_batch(ctx).held.have_labels && ctx->mode == RAU_MODE_TRAIN && (seam_mask() & 1);
+  return cur_batch(ctx).held.have_labels && ctx->mode == RAU_MODE_TRAIN && (seam_mask() & 1) && !ctx->sel_capture;
 }
 
 int rau_forward(rau_ctx* ctx) {
@@ -1494,23 +1494,29 @@ int rau_forward(rau_ctx* ctx) {
 // The caller's hop_w may be a temporary (and may be pinned memory, for which an async copy really
 // is asynchronous): stage it in the ctx's own pinned buffer first.  Two slots, alternated, so the
 // copy of step n is never overwritten by the host while step n+1's call prepares its own.
-static int upload_hop_weights(rau_ctx* ctx, const float* hop_w) {
+// select_w (null: none) travels behind hop_w in the same copy.
+static int upload_hop_weights(rau_ctx* ctx, const float* hop_w, const float* select_w = nullptr) {
   const int H = ctx->cfg.H;
   const int sl = (ctx->hopw_slot ^= 1);
-  float* stage = ctx->hopw_h + (size_t)sl * H;
+  float* stage = ctx->hopw_h + (size_t)sl * 2 * H;
   // a host that runs two or more steps ahead of the device must not overwrite a staging slot whose
   // copy has not been read yet: wait for the copy issued from this slot two calls ago
   if (!ctx->hopw_ev[sl]) HIPC(hipEventCreateWithFlags(&ctx->hopw_ev[sl], hipEventDisableTiming));
   else HIPC(hipEventSynchronize(ctx->hopw_ev[sl]));
   std::memcpy(stage, hop_w, (size_t)H * sizeof(float));
-  HIPC(hipMemcpyAsync(ctx->hopw_d, stage, (size_t)H * sizeof(float), hipMemcpyHostToDevice, ctx->st));
+  if (select_w) std::memcpy(stage + H, select_w, (size_t)H * sizeof(float));
+  HIPC(hipMemcpyAsync(ctx->hopw_d, stage, (size_t)(select_w ? 2 : 1) * H * sizeof(float), hipMemcpyHostToDevice,
+                      ctx->st));
   if (!ctx->capturing) HIPC(hipEventRecord(ctx->hopw_ev[sl], ctx->st));
   return 0;
 }
 
 // =============================================================== backward
-int rau_backward(rau_ctx* ctx, const float* hop_w) {
-  NEED(ctx && hop_w, "null argument");
+static int merge_state(rau_ctx* ctx, const char* fn, bool need_labels);
+// select_w: null, or the per-hop weights of the step-selection head's BCE with at least one of them non-zero
+// (rau_backward_select): the one place the two entry points differ is marked `sel` below.
+static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w) {
+  const bool sel = select_w != nullptr;
   if (!ctx->fwd_done) return fail(RAU_ERR_STATE, "rau_backward: call rau_forward first");
   if (ctx->fwd_table)
     return fail(RAU_ERR_STATE, "rau_backward: the evaluate-mode forward of a batch with an image table computed "
@@ -1518,6 +1524,14 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
                 "gradients on a plain batch (rau_set_batch)");
   const BatchSlot& bs = cur_batch(ctx);
   if (!bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_backward: batch has no labels");
+  // the head's target is read from that forward's labels or answer set: they must still be there (a captured
+  // step reads the resident batch, which rau_graph_step_select has checked)
+  if (sel && !ctx->capturing)
+    if (int rc = merge_state(ctx, "rau_backward_select", true)) return rc;
+  const int32_t* t_labels = ctx->capturing ? bs.labels_d : ctx->mg_labels_d;
+  const int t_G = ctx->capturing ? bs.held.ans_G : ctx->mg_ans_G;
+  const int32_t* t_ids = ctx->capturing ? bs.ans_ids_d : ctx->mg_ans_ids;
+  const float* t_score = ctx->capturing ? bs.ans_score_d : ctx->mg_ans_score;
   const rau_config& c = ctx->cfg;
   const int B = c.B, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R,
             K = c.K, H = c.H, Q = ctx->Q;
@@ -1545,9 +1559,9 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
 
   // dpred:mul(w[h])  SS:569 / MS:568-570 / Full:587-589
   if (!ctx->capturing) {  // (rau_graph_step uploads the weights before it launches the graph)
-    if (int rc = upload_hop_weights(ctx, hop_w)) return rc;
+    if (int rc = upload_hop_weights(ctx, hop_w, select_w)) return rc;
   }
-  if (ctx->dpre_fwd)   // the forward formed dpre / dhn from the unscaled dl: scale all three
+  if (ctx->dpre_fwd && !sel)   // the forward formed dpre / dhn from the unscaled dl: scale all three
     RUN("scale_hops", 0, (double)H * B * (K + M + R) * 8,
         scale_hops3(st, H, ctx->hopw_d, (size_t)B * K, ctx->dl, (size_t)B * M, ctx->dpre, (size_t)B * R, ctx->dhn));
   else
@@ -1558,13 +1572,21 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
   // their backward is identically zero and is skipped -- HA hops are "active".
   int HA = 0;
   for (int h = 0; h < H; ++h)
-    if (hop_w[h] != 0.f) HA = h + 1;
+    if (hop_w[h] != 0.f || (sel && select_w[h] != 0.f)) HA = h + 1;
 
   // ---------------- RAU BPTT, SS:561-578
-  // Off the recurrence: dpre = (dl Wc) (.) mask and dhn = dpre Wo for all active hops at once
+  // Off the recurrence: dpre = (dl Wc) (.) mask and dhn = dpre Wo for all active hops at once.
+  // sel: the gradient through do_pred, s (x) wd, joins dl Wc in front of the mask (HopGrad::dmf_add's position).
+  // A per-row term cannot be folded into what the forward formed (one scale per hop), so both products are
+  // formed here from the scaled dl -- which is also the order the bf16 emulation rounds in.
   const uint32_t* m_mf = mk(RAU_MASK_MF);
-  if (HA > 0 && !ctx->dpre_fwd) {
+  if (sel)
+    RUN("select_signal", 0, (double)HA * B * M * 4,
+        select_signal(st, HA * B, B, K, M, ctx->dopred, ctx->argmax_d, t_labels, t_ids, t_score, t_G,
+                      ctx->hopw_d + H, ctx->do_pred.W, ctx->sel_s, ctx->sel_add));
+  if (HA > 0 && (!ctx->dpre_fwd || sel)) {
     LinOpts o = lin_opts(ctx, ctx->ws_chain);
+    if (sel) { o.addend = ctx->sel_add; o.add_rs = M; }
     o.emask = m_mf;
     o.emask_e0 = 0;
     o.emscale = sc(RAU_MASK_MF);
@@ -1744,6 +1766,9 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
       for (int i = 0; i < np; ++i) fl += gflop(pr[i].M, pr[i].N, rows);
       RUNS(sw, "wgrad_gemm", fl, 0, gemm_tn_group_acc(sw, pr, np, rows, ws.slab, ws.floats, lin_mode(ctx).bf16));
     }
+    if (sel)   // the head's own weights: dwd += sum s mf, dbd += sum s (f32 dot products in every dtype)
+      RUNS(sw, "select_wgrad", 2.0 * rows * (M + 1), (double)rows * M * 4,
+           select_wgrad(sw, rows, M, ctx->sel_s, ctx->mf, ctx->do_pred.dW, ctx->do_pred.db));
     // att_score: dws = sum dz T ; dbs = sum dz.  att_i bias: sum dS.  i_embed bias: sum dZ.
     RUNS(sw, "colsum", 0, (double)rows * A * 4, colsum_acc(sw, rows, A, ctx->dwsp, A, ctx->att_score.dW, ws.coltmp));
     HIPC(hipMemsetAsync(ctx->tmpS, 0, S * sizeof(float), sw));
@@ -1848,14 +1873,48 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
   return RAU_OK;
 }
 
+int rau_backward(rau_ctx* ctx, const float* hop_w) {
+  NEED(ctx && hop_w, "null argument");
+  return backward_impl(ctx, hop_w, nullptr);
+}
+
+// Argument rules of the two *_select entry points: finite weights; *select_w becomes null when it holds no
+// non-zero entry (today's path, launch for launch); otherwise the head's scratch exists on return.
+static int select_args(rau_ctx* ctx, const char* fn, const float* hop_w, const float** select_w) {
+  NEED(ctx && hop_w, "null argument");
+  const int H = ctx->cfg.H;
+  bool any = false;
+  for (int h = 0; h < H; ++h) {
+    NEED(std::isfinite(hop_w[h]), "%s: hop_w[%d] is not finite", fn, h);
+    if (*select_w) {
+      NEED(std::isfinite((*select_w)[h]), "%s: select_w[%d] is not finite", fn, h);
+      any = any || (*select_w)[h] != 0.f;
+    }
+  }
+  if (!any) *select_w = nullptr;
+  if (any && !ctx->sel_add) {   // sized for the capacity, cleared by rau_set_batch_size like every activation
+    if (!ctx->sel_s)
+      if (int rc = dalloc(ctx, &ctx->sel_s, (size_t)H * ctx->cap)) return rc;
+    if (int rc = dalloc(ctx, &ctx->sel_add, (size_t)H * ctx->cap * ctx->cfg.M)) return rc;
+  }
+  return RAU_OK;
+}
+
+int rau_backward_select(rau_ctx* ctx, const float* hop_w, const float* select_w) {
+  if (int rc = select_args(ctx, "rau_backward_select", hop_w, &select_w)) return rc;
+  return backward_impl(ctx, hop_w, select_w);
+}
+
 // One training step's forward + backward (optionally with the gradient zeroing in front) as ONE
 // hipGraph launch.  The three streams, their fork/join events and every kernel argument are
 // captured once per step "shape" -- (mode, longest question, active hops, which mask sites are
 // explicit, zeroing or not) -- and replayed; what changes from step to step lives in device
 // memory: the batch (rau_set_batch), the Philox key (rau_set_dropout_seed) and the hop weights
 // (uploaded here, in front of the launch).
-int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
-  NEED(ctx && hop_w, "null argument");
+// select_w: as backward_impl's.  The weights are read from device memory, so they may change between replays;
+// whether there is a non-zero one decides the launches and joins the key, with the active-hop count.
+static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select_w, int zero_grads_first) {
+  const bool sel = select_w != nullptr;
   const BatchSlot& bs = cur_batch(ctx);
   if (!bs.held.have || !bs.held.have_labels)
     return fail(RAU_ERR_STATE, "rau_graph_step: needs a batch with labels (rau_set_batch)");
@@ -1863,7 +1922,7 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
   const int H = ctx->cfg.H;
   int HA = 0;
   for (int h = 0; h < H; ++h)
-    if (hop_w[h] != 0.f) HA = h + 1;
+    if (hop_w[h] != 0.f || (sel && select_w[h] != 0.f)) HA = h + 1;
   uint64_t key = (uint64_t)ctx->mode | ((uint64_t)bs.held.max_len << 2) | ((uint64_t)HA << 12) |
                  ((uint64_t)(zero_grads_first != 0) << 22);
   for (int i = 0; i < 5; ++i) key |= (uint64_t)ctx->mexplicit[i] << (24 + i);
@@ -1873,7 +1932,8 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
   key |= (uint64_t)bs.held.bank << 36;   // ... of a bank batch: out of the bank (rau_bank_destroy reads this bit)
   key |= (uint64_t)bs.held.ans_G << 37;   // ... against an answer set of G entries (0 = labels): another head kernel
   key |= (uint64_t)ctx->cfg.B << 42;      // every launch is shaped by the batch size (rau_set_batch_size)
-  if (int rc = upload_hop_weights(ctx, hop_w)) return rc;
+  key |= (uint64_t)sel << 31;             // ... and by the step-selection head's gradient being asked for
+  if (int rc = upload_hop_weights(ctx, hop_w, select_w)) return rc;
   ctx->mg_valid = false;
   hipGraphExec_t exec = nullptr;
   for (auto& g : ctx->graphs)
@@ -1882,10 +1942,12 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
     hipGraph_t graph = nullptr;
     HIPC(hipStreamBeginCapture(ctx->st, hipStreamCaptureModeRelaxed));
     ctx->capturing = true;
+    ctx->sel_capture = sel;
     int rc = zero_grads_first ? rau_zero_grads(ctx) : 0;
     if (!rc) rc = rau_forward(ctx);
-    if (!rc) rc = rau_backward(ctx, hop_w);
+    if (!rc) rc = backward_impl(ctx, hop_w, select_w);
     ctx->capturing = false;
+    ctx->sel_capture = false;
     hipError_t e = hipStreamEndCapture(ctx->st, &graph);
     if (rc) {
       if (graph) hipGraphDestroy(graph);
@@ -1911,6 +1973,16 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
   ctx->bwd_done = true;
   ctx->graph_last = true;
   return RAU_OK;
+}
+
+int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
+  NEED(ctx && hop_w, "null argument");
+  return graph_step_impl(ctx, hop_w, nullptr, zero_grads_first);
+}
+
+int rau_graph_step_select(rau_ctx* ctx, const float* hop_w, const float* select_w, int zero_grads_first) {
+  if (int rc = select_args(ctx, "rau_graph_step_select", hop_w, &select_w)) return rc;
+  return graph_step_impl(ctx, hop_w, select_w, zero_grads_first);
 }
 
 int rau_wait_grads(rau_ctx* ctx, int group, void* hip_stream) {

@@ -31,6 +31,35 @@ def bce(x, t):
     return np.float32(term.sum(dtype=np.float32) / np.float32(x.shape[0]))
 
 
+def _f32_unless_f64(a):
+    a = np.asarray(a)
+    return a if a.dtype == np.float64 else a.astype(np.float32)
+
+
+def bce_grad(x, t, w):
+    """nn.BCECriterion:backward (sizeAverage) scaled by w -- the reference's d_do_pred before its mul(0),
+    SS:565-566, and the contract of rau_backward_select: w * (-(t - x) / ((1 - x + eps) * (x + eps))) / n, in
+    this order, n = x.shape[-1].  x, t [..., n]; w a scalar, or [H] for [H, n] inputs.  Float32 arithmetic (the
+    device's), unless x is given as float64 (for references).  Torch tensors of one device are taken as they
+    are: only arithmetic is used."""
+    eps = float(BCE_EPS)
+    if hasattr(x, "is_cuda"):
+        return w * (-(t - x) / ((1 - x + eps) * (x + eps))) / float(x.shape[-1])
+    x = _f32_unless_f64(x)
+    t, w = np.asarray(t, x.dtype), np.asarray(w, x.dtype)
+    if w.ndim == 1:
+        w = w[:, None]
+    one, eps = x.dtype.type(1), x.dtype.type(eps)
+    return w * (-(t - x) / ((one - x + eps) * (x + eps))) / x.dtype.type(x.shape[-1])
+
+
+def select_signal(x, t, w):
+    """bce_grad through the head's sigmoid: the gradient at Linear(M,1)'s output, s = ddp * x * (1 - x)."""
+    if not hasattr(x, "is_cuda"):
+        x = _f32_unless_f64(x)
+    return bce_grad(x, t, w) * x * (1 - x)
+
+
 def feval_stats(logits, dopred, labels):
     """logits [H, B, K], dopred [H, B], labels [B] (1-based) -> dict with the keys of
     ``RAU.step_stats`` (loss [H+2], loss_do_pred [H], correct [H+2], do_pred_correct [H],

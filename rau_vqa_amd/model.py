@@ -499,18 +499,31 @@ class RAU:
     def forward(self):
         L.check(self._lib.rau_forward(self._h))
 
-    def backward(self, hop_w):
-        w = np.ascontiguousarray(hop_w, np.float32)
+    def _hop_array(self, w, what):
+        w = np.ascontiguousarray(w, np.float32)
         if w.shape != (self.cfg.H,):
-            raise ValueError("hop_w must have H entries")
-        L.check(self._lib.rau_backward(self._h, w.ctypes.data))
+            raise ValueError(f"{what} must have H entries")
+        return w
 
-    def graph_step(self, hop_w, zero_grads=True):
-        """zero_grads + forward + backward as one hipGraph launch (captured on first use)."""
-        w = np.ascontiguousarray(hop_w, np.float32)
-        if w.shape != (self.cfg.H,):
-            raise ValueError("hop_w must have H entries")
-        L.check(self._lib.rau_graph_step(self._h, w.ctypes.data, int(zero_grads)))
+    def backward(self, hop_w, select_w=None):
+        """select_w [H]: per-hop weight of the step-selection head's BCE gradient, the multiplier the
+        reference fixes at 0 (SS:566); None is that zero (rau_backward)."""
+        w = self._hop_array(hop_w, "hop_w")
+        if select_w is None:
+            L.check(self._lib.rau_backward(self._h, w.ctypes.data))
+        else:
+            sw = self._hop_array(select_w, "select_w")
+            L.check(self._lib.rau_backward_select(self._h, w.ctypes.data, sw.ctypes.data))
+
+    def graph_step(self, hop_w, zero_grads=True, select_w=None):
+        """zero_grads + forward + backward as one hipGraph launch (captured on first use); select_w as in
+        backward (read from device memory: it may change between replays)."""
+        w = self._hop_array(hop_w, "hop_w")
+        if select_w is None:
+            L.check(self._lib.rau_graph_step(self._h, w.ctypes.data, int(zero_grads)))
+        else:
+            sw = self._hop_array(select_w, "select_w")
+            L.check(self._lib.rau_graph_step_select(self._h, w.ctypes.data, sw.ctypes.data, int(zero_grads)))
 
     def sync(self):
         L.check(self._lib.rau_sync(self._h))

@@ -21,6 +21,7 @@ import torch
 
 from . import _lib as L
 from .dist import device_view
+from .joint import bce_grad
 
 
 def _p(t):
@@ -115,8 +116,10 @@ class CriterionClone(_Clone):
         return self._view(out, self.rau.batch_size, self.rau.cfg.K)
 
 
-def feval(rau, feats, x, x_len, y, hop_w):
+def feval(rau, feats, x, x_len, y, hop_w, select_w=None):
     """The tensor half of the reference's feval, loop for loop (SS:443-596), on the clones.
+    select_w [H] (None: the reference's zero, SS:566): hop h's multimodal clone receives
+    d_do_pred = joint.bce_grad(do_pred_h, argmax_h == y, select_w[h]), which trains the step-selection head.
 
     feats [B,D,S] float32, x [T,B] int32, x_len [B] int32, y [B] int32: CUDA tensors.
     Gradients accumulate into the ctx's flat buffers (zero them first).  Returns
@@ -124,10 +127,10 @@ def feval(rau, feats, x, x_len, y, hop_w):
     """
     ext = torch.cuda.ExternalStream(rau.stream(), device=feats.device)
     with torch.cuda.stream(ext):   # torch's glue ops join the ctx's own stream order
-        return _feval(rau, feats, x, x_len, y, hop_w)
+        return _feval(rau, feats, x, x_len, y, hop_w, select_w)
 
 
-def _feval(rau, feats, x, x_len, y, hop_w):
+def _feval(rau, feats, x, x_len, y, hop_w, select_w=None):
     c = rau.cfg
     dev = feats.device
     emb = [EmbedClone(rau, t) for t in range(c.T)]
@@ -147,10 +150,11 @@ def _feval(rau, feats, x, x_len, y, hop_w):
     # ---- hops forward, SS:467-520
     att_c = [torch.zeros(rau.batch_size, c.R, device=dev)]            # SS:362-365
     att_h = [torch.zeros(rau.batch_size, c.R, device=dev)]
-    logits, losses, answers = [], [], []
+    logits, losses, answers, dopred = [], [], [], []
     for h in range(c.H):
-        lg, _dp, _a, cn, hn = mm[h].forward(rnn_out, feats, att_c[h], att_h[h])
+        lg, dp, _a, cn, hn = mm[h].forward(rnn_out, feats, att_c[h], att_h[h])
         logits.append(lg)
+        dopred.append(dp)
         att_c.append(cn)
         att_h.append(hn)
         losses.append(crit[h].forward(lg, y))              # SS:518
@@ -160,7 +164,11 @@ def _feval(rau, feats, x, x_len, y, hop_w):
     d_q = torch.zeros(rau.batch_size, c.Q, device=dev)
     for h in reversed(range(c.H)):
         dl = crit[h].backward(logits[h], y, float(hop_w[h]))   # SS:565-569
-        dq_h, _dX, d_c, d_h = mm[h].backward(rnn_out, feats, att_c[h], att_h[h], dl, None, None,
+        d_dp = None                                        # d_do_pred:mul(0), SS:566
+        if select_w is not None and float(select_w[h]) != 0.0:
+            gt = (answers[h] == y).to(torch.float32)       # do_pred_gt, SS:490, 497
+            d_dp = bce_grad(dopred[h], gt, float(select_w[h])).contiguous()   # SS:565, times the weight
+        dq_h, _dX, d_c, d_h = mm[h].backward(rnn_out, feats, att_c[h], att_h[h], dl, d_dp, None,
                                               d_c, d_h)
         d_q += dq_h                                        # ConcatTable backward, SS:579
     # ---- encoder backward, SS:581-596
