@@ -281,31 +281,25 @@ __global__ __launch_bounds__(kMT) void k_predict_rows(int H, int B, int K, int S
 }  // namespace
 
 hipError_t step_stats(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
-                      const int32_t* argmax, const float* lossrow, const int32_t* labels, float* rowf,
-                      int32_t* rowi, float* out) {
-  hipLaunchKernelGGL(k_step_stats_rows, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, argmax, labels,
-                     rowf, rowi);
+                      const int32_t* argmax, const float* lossrow, const Truth& t, float* rowf, int32_t* rowi,
+                      float* out, float* rowscore, float* tot) {
+  if (t.G > 0 && (t.G > kMaxAnswers || !t.ids || !t.w || !t.score)) return hipErrorInvalidValue;
+  if (t.G > 0)
+    hipLaunchKernelGGL(k_step_stats_rows_set, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, argmax, t.ids,
+                       t.w, t.score, t.G, rowf, rowi, rowscore);
+  else
+    hipLaunchKernelGGL(k_step_stats_rows, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, argmax, t.labels,
+                       rowf, rowi);
   hipLaunchKernelGGL(k_step_stats_reduce, dim3(1), dim3(kMT), 0, st, H, B, lossrow, rowf, rowi, out);
+  if (t.G > 0) hipLaunchKernelGGL(k_score_totals, dim3(1), dim3(kMT), 0, st, H + 2, B, rowscore, tot);
   return hipGetLastError();
 }
 
-hipError_t step_stats_set(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
-                          const int32_t* argmax, const float* lossrow, const int32_t* ids, const float* w,
-                          const float* score, int G, float* rowf, int32_t* rowi, float* out, float* rowscore,
-                          float* tot) {
-  if (G < 1 || G > kMaxAnswers || !ids || !w || !score) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_step_stats_rows_set, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, argmax, ids, w,
-                     score, G, rowf, rowi, rowscore);
-  hipLaunchKernelGGL(k_step_stats_reduce, dim3(1), dim3(kMT), 0, st, H, B, lossrow, rowf, rowi, out);
-  hipLaunchKernelGGL(k_score_totals, dim3(1), dim3(kMT), 0, st, H + 2, B, rowscore, tot);
-  return hipGetLastError();
-}
-
-hipError_t answer_scores(hipStream_t st, int R, int B, int K, const int32_t* ans, const int32_t* ids,
-                         const float* score, int G, float* out, float* tot) {
-  if (G < 1 || G > kMaxAnswers || !ids || !score) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_answer_scores, dim3((R * B + kMT - 1) / kMT), dim3(kMT), 0, st, R, B, K, ans, ids, score,
-                     G, out);
+hipError_t answer_scores(hipStream_t st, int R, int B, int K, const int32_t* ans, const Truth& t, float* out,
+                         float* tot) {
+  if (t.G < 1 || t.G > kMaxAnswers || !t.ids || !t.score) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_answer_scores, dim3((R * B + kMT - 1) / kMT), dim3(kMT), 0, st, R, B, K, ans, t.ids, t.score,
+                     t.G, out);
   hipLaunchKernelGGL(k_score_totals, dim3(1), dim3(kMT), 0, st, R, B, out, tot);
   return hipGetLastError();
 }

@@ -381,13 +381,35 @@ hipError_t ce_set_fwd(hipStream_t st, int nB, int K, int M, const float* logits,
                       const float* w, int G, const float* mf, const float* wd, const float* bd, float* dl,
                       float* lossrow, int32_t* argmax, float* dopred, const float* part = nullptr,
                       int nsplit = 0, const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0);
+// The ground truth of a batch: what a criterion, a statistic or the selection head's target is read from.  A plain
+// value: "no ground truth" is Truth{}; G > 0 means the answer set replaces the labels.
+struct Truth {
+  const int32_t* labels = nullptr;   // [Bper] device, or null
+  const int32_t* ids = nullptr;      // answer set [Bper][G] (G > 0), device
+  const float *w = nullptr, *score = nullptr;
+  int G = 0;                         // 0 = labels
+  bool present() const { return labels || G > 0; }
+};
+// The criterion head against whichever target `t` holds: ce_set_fwd (G > 0) or ce_fwd (labels, or none); the other
+// arguments are the ones the two share.  criterion_class names the launch for the profile.
+inline const char* criterion_class(const Truth& t) { return t.G > 0 ? "ce_set_fwd" : "ce_fwd"; }
+inline hipError_t criterion_head(hipStream_t st, int nB, int K, int M, const float* logits, const Truth& t,
+                                 const float* mf, const float* wd, const float* bd, float* dl, float* lossrow,
+                                 int32_t* argmax, float* dopred, const float* part = nullptr, int nsplit = 0,
+                                 const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0) {
+  if (t.G > 0)
+    return ce_set_fwd(st, nB, K, M, logits, t.ids, t.w, t.G, mf, wd, bd, dl, lossrow, argmax, dopred, part, nsplit,
+                      bias, logits_out, Bper);
+  return ce_fwd(st, nB, K, M, logits, t.labels, mf, wd, bd, dl, lossrow, argmax, dopred, part, nsplit, bias,
+                logits_out, Bper);
+}
 // The step-selection head's gradient (select_bwd.hip, rau_backward_select).  rows = active hops x Bper, hop-major.
 // select_signal: s[r] = select_w[h] * BCE'(do_pred, do_pred_gt) / Bper * x (1 - x) and add[r][m] = s[r] wd[m];
-// do_pred_gt from the labels [Bper] (G == 0) or an answer set ids / score [Bper][G] (rau_step_stats' rules).
+// do_pred_gt from t's labels [Bper] (G == 0) or its answer set ids / score [Bper][G] (rau_step_stats' rules).
 // select_wgrad: dW[m] += sum_r s[r] mf[r][m], db[0] += sum_r s[r], one fixed-order pass (any M, any row count).
 hipError_t select_signal(hipStream_t st, int rows, int Bper, int K, int M, const float* dopred,
-                         const int32_t* argmax, const int32_t* labels, const int32_t* ids, const float* score,
-                         int G, const float* selw_dev, const float* wd, float* s, float* add);
+                         const int32_t* argmax, const Truth& t, const float* selw_dev, const float* wd, float* s,
+                         float* add);
 hipError_t select_wgrad(hipStream_t st, int rows, int M, const float* s, const float* mf, float* dW,
                         float* db);
 hipError_t scale_hops(hipStream_t st, int H, size_t per_hop, const float* w_dev, float* x);
@@ -428,20 +450,16 @@ hipError_t clip_adam(hipStream_t st, size_t n, float* x, float* g, float* m, flo
 // feval's statistics of the resident hop outputs (hop_merge.hip, SS:476-556): per-sample rows
 // rowf [B][H+2], rowi [B][4H+3], then one fixed-order batch reduction into
 // out = loss[H+2] | loss_do_pred[H] | int32 counts[4H+3]
+// against t's labels, or (G > 0) its answer set ids / w / score [B][G]: "correct" = the row's first-max answer
+// carries a positive score, uni / select CE are the soft CE of ce_set_fwd; a set also gives the metric score of
+// every row's answer, rowscore [H+2][B] (feval rule), and their fixed-order batch sums tot [H+2] (labels: unused)
 hipError_t step_stats(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
-                      const int32_t* argmax, const float* lossrow, const int32_t* labels, float* rowf,
-                      int32_t* rowi, float* out);
-// step_stats of a batch with an answer set (ids / w / score [B][G] device): "correct" = the row's first-max
-// answer carries a positive score, uni / select CE are the soft CE of ce_set_fwd; also the metric score of every
-// row's answer, rowscore [H+2][B] (feval rule), and their fixed-order batch sums tot [H+2]
-hipError_t step_stats_set(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
-                          const int32_t* argmax, const float* lossrow, const int32_t* ids, const float* w,
-                          const float* score, int G, float* rowf, int32_t* rowi, float* out, float* rowscore,
-                          float* tot);
-// out[r][b] = sum_g score[b][g] * [ids[b][g] == ans[r][b]] in entry order (ans 1-based, [R][B]), tot[r] = the
-// fixed-order sum of row r over the batch
-hipError_t answer_scores(hipStream_t st, int R, int B, int K, const int32_t* ans, const int32_t* ids,
-                         const float* score, int G, float* out, float* tot);
+                      const int32_t* argmax, const float* lossrow, const Truth& t, float* rowf, int32_t* rowi,
+                      float* out, float* rowscore, float* tot);
+// out[r][b] = sum_g score[b][g] * [ids[b][g] == ans[r][b]] over t's set in entry order (ans 1-based, [R][B]),
+// tot[r] = the fixed-order sum of row r over the batch
+hipError_t answer_scores(hipStream_t st, int R, int B, int K, const int32_t* ans, const Truth& t, float* out,
+                         float* tot);
 // predict_result's merges + answers (SS:633-705, 877-900): oe / mco [H+2][B] 1-based, pred [2][B][K] and
 // att_out [2][B][Sp] (uni, select; either may be null); mc [B][n_mc] device ids 0..K (null: no MC)
 hipError_t predict_rows(hipStream_t st, int H, int B, int K, int Sp, const float* logits, const float* dopred,

@@ -530,13 +530,13 @@ int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const
   s.held.ans_G = G;
   s.held.have_labels = true;   // the set is the batch's ground truth
   if (si == ctx->cur_slot) ctx->fwd_done = false;
-  if (si == ctx->mg_slot) ctx->mg_valid = false;   // statistics of a forward that read the slot's previous targets
+  if (si == ctx->mg.slot) ctx->mg.valid = false;   // statistics of a forward that read the slot's previous targets
   return RAU_OK;
 }
 
 int rau_batch_answers(rau_ctx* ctx, int32_t* G) {
   NEED(ctx && G, "null argument");
-  *G = cur_batch(ctx).held.ans_G;
+  *G = truth_of(cur_batch(ctx)).G;
   return RAU_OK;
 }
 

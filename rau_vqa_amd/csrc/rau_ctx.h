@@ -128,6 +128,37 @@ struct StreamWs {
   float* coltmp = nullptr;       // column-sum scratch of colsum_acc (bulk and side stream)
 };
 
+// The one place that maps a slot's buffers to a target: its labels, or (G > 0) the answer set in their place
+inline Truth truth_of(const BatchSlot& s) {
+  return s.held.have_labels ? Truth{s.labels_d, s.ans_ids_d, s.ans_w_d, s.ans_score_d, s.held.ans_G} : Truth{};
+}
+
+// Merged hops (rau_merge.hip: rau_step_stats / rau_predict / rau_topk): what those entry points know about the
+// last step-level forward.  rau_ctx::mg.
+struct MergeState {
+  // ---- what the last forward left (merge_record)
+  bool valid = false;             // logits / dopred / argmax_d / lossrow / a hold the last step-level forward's
+  Truth truth;                    // ... of a batch with this ground truth (read from the slot's device buffers)
+  int slot = 0;                   // the batch slot that forward read, and its upload serial then
+  uint64_t serial = 0, fwd = 0;   // ... / forwards recorded so far
+  // ---- what rau_predict left
+  bool merged = false;            // a rau_predict has filled pred, att
+  uint64_t pred_fwd = 0;          // the forward the last rau_predict read
+  bool pred_mc = false;           // that rau_predict had an MC list
+  // ---- buffers, allocated once (merge_alloc; mc and topk at their first use, regrown)
+  bool ready = false;
+  float *rowf = nullptr, *out = nullptr, *pred = nullptr, *att = nullptr;
+  int32_t *rowi = nullptr, *ans = nullptr, *mc = nullptr;
+  size_t mc_cap = 0;              // int32 entries mc holds
+  float* score = nullptr;         // rau_step_scores / rau_predict_scores: rows [2(H+2)][B] | totals [2(H+2)]
+  // rau_topk's staging: ids | score | conf, each [H+2][B][k]; room for [H+2][cap][topk_k], allocated at
+  // its first call and regrown when a larger k is asked for
+  void* topk = nullptr;
+  int topk_k = 0;
+  // no forward result, no rau_predict result, no ground truth: a fresh context's (rau_set_batch_size)
+  void invalidate() { valid = merged = false; truth = Truth{}; }
+};
+
 struct rau_ctx {
   rau_config cfg;             // cfg.B is the CURRENT batch size (rau_set_batch_size): what every layout, launch and
                               // getter reads at call time -- the B of the fresh context this one is equivalent to
@@ -259,26 +290,7 @@ struct rau_ctx {
   bool capturing = false;
   bool graph_last = false;       // the last backward ran inside a graph (its events are graph-internal)
   std::vector<std::pair<uint64_t, hipGraphExec_t>> graphs;
-  // merged hops (hop_merge.hip: rau_step_stats / rau_predict); buffers allocated on first use
-  bool mg_valid = false;          // logits / dopred / argmax_d / lossrow / a hold the last step-level forward's
-  bool mg_labels = false;         // ... of a batch with labels, read from mg_labels_d
-  const int32_t* mg_labels_d = nullptr;
-  int mg_ans_G = 0;               // ... or an answer set of that many entries, read from the three pointers
-  const int32_t* mg_ans_ids = nullptr;
-  const float *mg_ans_w = nullptr, *mg_ans_score = nullptr;
-  uint64_t mg_fwd = 0, mg_pred_fwd = 0;   // forwards recorded so far / the one the last rau_predict read
-  bool mg_pred_mc = false;        // that rau_predict had an MC list
-  float* mg_score = nullptr;      // rau_step_scores / rau_predict_scores: rows [2(H+2)][B] | totals [2(H+2)]
-  int mg_slot = 0;                // the batch slot that forward read, and its upload serial then
-  uint64_t mg_serial = 0;
-  bool mg_ready = false, mg_merged = false;   // buffers allocated / a rau_predict has filled mg_pred, mg_att
-  float *mg_rowf = nullptr, *mg_out = nullptr, *mg_pred = nullptr, *mg_att = nullptr;
-  int32_t *mg_rowi = nullptr, *mg_ans = nullptr, *mg_mc = nullptr;
-  size_t mg_mc_cap = 0;           // int32 entries mg_mc holds
-  // rau_topk's staging: ids | score | conf, each [H+2][B][k]; room for [H+2][cap][mg_topk_k], allocated at
-  // its first call and regrown when a larger k is asked for
-  void* mg_topk = nullptr;
-  int mg_topk_k = 0;
+  MergeState mg;                 // merged hops (rau_merge.hip): what may be read of the last forward
   // update
   float *npart = nullptr, *norms_d = nullptr;
   bool fwd_done = false, bwd_done = false;
@@ -337,16 +349,11 @@ inline LinOpts lin_opts(const rau_ctx* ctx, const StreamWs& ws) {
 // The hop outputs now hold the results of the forward just enqueued: rau_step_stats / rau_predict may
 // read them until the next forward, module-level call or upload into the batch slot it read.
 inline void merge_record(rau_ctx* ctx) {
-  ctx->mg_valid = true;
-  ctx->mg_labels = cur_batch(ctx).held.have_labels;
-  ctx->mg_labels_d = cur_batch(ctx).labels_d;
-  ctx->mg_ans_G = cur_batch(ctx).held.ans_G;
-  ctx->mg_ans_ids = cur_batch(ctx).ans_ids_d;
-  ctx->mg_ans_w = cur_batch(ctx).ans_w_d;
-  ctx->mg_ans_score = cur_batch(ctx).ans_score_d;
-  ++ctx->mg_fwd;
-  ctx->mg_slot = ctx->cur_slot;
-  ctx->mg_serial = ctx->slot_serial[ctx->cur_slot];
+  ctx->mg.valid = true;
+  ctx->mg.truth = truth_of(cur_batch(ctx));
+  ctx->mg.slot = ctx->cur_slot;
+  ctx->mg.serial = ctx->slot_serial[ctx->cur_slot];
+  ++ctx->mg.fwd;
 }
 inline float mask_p(const rau_ctx* ctx, int site) {
   return ctx->mexplicit[site] ? ctx->mp_exact[site] : ctx->mp[site];
@@ -366,6 +373,16 @@ static int dalloc(rau_ctx* c, Tp** p, size_t count, bool scratch = true) {
   if (scratch) c->scratch.push_back({d, bytes});
   *p = reinterpret_cast<Tp*>(d);
   return 0;
+}
+// Gives a dalloc'ed region back before rau_destroy: no launch may still read it, and neither rau_destroy (allocs)
+// nor rau_set_batch_size (which clears scratch) may see it again.
+static inline int dfree(rau_ctx* c, void* p) {
+  HIPC(hipStreamSynchronize(c->st));
+  hipFree(p);
+  c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), p), c->allocs.end());
+  auto& sc = c->scratch;
+  sc.erase(std::remove_if(sc.begin(), sc.end(), [p](const auto& r) { return r.first == p; }), sc.end());
+  return RAU_OK;
 }
 
 struct LayoutBuilder {
@@ -495,7 +512,7 @@ struct HopGrad {
 };
 __attribute__((visibility("hidden"))) int hop_forward(rau_ctx* ctx, int h, const float* cp,
     const float* hp, float* c_out, float* h_out, const float* Ih, const float* Pin,
-    const int32_t* labels);
+    const Truth& truth);
 __attribute__((visibility("hidden"))) int hop_forward_chain(rau_ctx* ctx, int h, const float* cp,
     const float* hp, float* c_out, float* h_out, const float* Ih, const float* Pin,
     const int32_t* img = nullptr /* device index: sample b's Ih / Pin tiles are row img[b] (image table) */);
@@ -503,6 +520,14 @@ __attribute__((visibility("hidden"))) int hop_forward_chain(rau_ctx* ctx, int h,
 // with an image table its expansion (expand_features on the chain stream, once per upload).
 __attribute__((visibility("hidden"))) int batch_maps(rau_ctx* ctx, const float** maps);
 __attribute__((visibility("hidden"))) int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh,
-    const int32_t* labels);
+    const Truth& truth);
 __attribute__((visibility("hidden"))) int hop_backward(rau_ctx* ctx, int h, const float* cp,
     const float* Ih, const HopGrad& g);
+
+// ---- shared between rau_ctx.hip and the merged-hops entry points (rau_merge.hip)
+extern "C" {   // defined among the result getters, inside rau_ctx.hip's extern "C" block
+// the persistent encoder's error word, read after a host synchronisation; the copy to the host that ends with both
+__attribute__((visibility("hidden"))) int persist_check(rau_ctx* ctx);
+__attribute__((visibility("hidden"))) int d2h(rau_ctx* ctx, void* host, const void* dev, size_t bytes);
+}
+__attribute__((visibility("hidden"))) int merge_state(rau_ctx* ctx, const char* fn, bool need_labels);  // rau_merge.hip

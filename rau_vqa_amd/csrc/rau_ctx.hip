@@ -828,7 +828,7 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   ctx->cur.clear();
   for (int i = 0; i < 5; ++i) ctx->mexplicit[i] = false;
   ctx->mod_masks_valid = false;
-  ctx->mg_valid = ctx->mg_merged = ctx->mg_labels = false;
+  ctx->mg.invalidate();
   ctx->persist_used = false;
   if (ctx->perr_h) *ctx->perr_h = 0;
   return RAU_OK;
@@ -935,7 +935,7 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
 // merge_feat = dropout(j + h' Wo^T + bo), logits = merge_feat Wc^T + bc, do_pred, cross-entropy +
 // first-max argmax for hops [h0, h0 + nh): rows = nh * B.  h' rows are ctx->hh slots h0+1 .. (the
 // chain's h_out); it runs on ws.owner and uses the first two quarters of that stream's split-K workspace.
-int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const int32_t* labels) {
+int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const Truth& truth) {
   const rau_config& c = ctx->cfg;
   hipStream_t s = ws.owner;
   const size_t reg = ws.floats / 4;
@@ -968,29 +968,19 @@ int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const int
     RUNS(s, "head_gemm", gflop(rows, K, M), 0,
          gemm_nt(s, rows, K, M, mfh, M, ctx->cls.W, M, lg, K, o));
   }
-  const BatchSlot& bs = cur_batch(ctx);
-  if (labels && bs.held.ans_G > 0) {   // the batch's answer set is its ground truth (rau_set_answers)
-    RUNS(s, "ce_set_fwd", 0, (double)rows * K * 12,
-         ce_set_fwd(s, rows, K, M, lg, bs.ans_ids_d, bs.ans_w_d, bs.held.ans_G, mfh, ctx->do_pred.W,
-                    ctx->do_pred.b, ctx->dl + (size_t)h0 * B * K, ctx->lossrow + (size_t)h0 * B,
-                    ctx->argmax_d + (size_t)h0 * B, ctx->dopred + (size_t)h0 * B, ws.slab + reg, ns_c,
-                    ctx->cls.b, lg, B));
-    return RAU_OK;
-  }
-  RUNS(s, "ce_fwd", 0, (double)rows * K * 12,
-       ce_fwd(s, rows, K, M, lg, labels, mfh, ctx->do_pred.W, ctx->do_pred.b,
-              ctx->dl + (size_t)h0 * B * K, ctx->lossrow + (size_t)h0 * B,
-              ctx->argmax_d + (size_t)h0 * B, ctx->dopred + (size_t)h0 * B, ws.slab + reg, ns_c,
-              ctx->cls.b, lg, B));
+  RUNS(s, criterion_class(truth), 0, (double)rows * K * 12,
+       criterion_head(s, rows, K, M, lg, truth, mfh, ctx->do_pred.W, ctx->do_pred.b, ctx->dl + (size_t)h0 * B * K,
+                      ctx->lossrow + (size_t)h0 * B, ctx->argmax_d + (size_t)h0 * B, ctx->dopred + (size_t)h0 * B,
+                      ws.slab + reg, ns_c, ctx->cls.b, lg, B));
   return RAU_OK;
 }
 
 int hop_forward(rau_ctx* ctx, int h, const float* cp, const float* hp, float* c_out, float* h_out,
-                const float* Ih, const float* Pin, const int32_t* labels) {
+                const float* Ih, const float* Pin, const Truth& truth) {
   if (int rc = hop_forward_chain(ctx, h, cp, hp, c_out, h_out, Ih, Pin)) return rc;
   if (h_out != ctx->hh + (size_t)(h + 1) * ctx->cfg.B * ctx->cfg.R)
     return fail(RAU_ERR_INVALID, "hop_forward: h_out must be the ctx's hop slot");
-  return hop_forward_head(ctx, ctx->ws_chain, h, 1, labels);
+  return hop_forward_head(ctx, ctx->ws_chain, h, 1, truth);
 }
 
 // Backward of hop_forward (hand-derived, SURVEY 8a "exact backward of one hop"): from the
@@ -1168,7 +1158,7 @@ int rau_forward(rau_ctx* ctx) {
   NEED(ctx, "null ctx");
   BatchSlot& bs = cur_batch(ctx);
   if (!bs.held.have) return fail(RAU_ERR_STATE, "rau_forward: no batch (call rau_set_batch)");
-  ctx->mg_valid = false;   // the hop outputs are being overwritten
+  ctx->mg.valid = false;   // the hop outputs are being overwritten
   const rau_config& c = ctx->cfg;
   const int B = c.B, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R,
             H = c.H, Q = ctx->Q;
@@ -1433,7 +1423,7 @@ int rau_forward(rau_ctx* ctx) {
   // Evaluate mode: dropout is the identity, so I is hop-invariant and computed once.
   HIPC(hipMemsetAsync(ctx->cc, 0, BR_ * sizeof(float), st));  // att_c, att_h zeros SS:362-365
   HIPC(hipMemsetAsync(ctx->hh, 0, BR_ * sizeof(float), st));
-  const int32_t* labels = bs.held.have_labels ? bs.labels_d : nullptr;
+  const Truth truth = truth_of(bs);
   // rows the logits region of the head's workspace holds (hop_forward_head: a quarter of the side stream's slab)
   const int head_max = (int)std::max<size_t>(1, ctx->ws_side.floats / 4 / ((size_t)B * c.K));
   int gstart = 0;
@@ -1456,7 +1446,7 @@ int rau_forward(rau_ctx* ctx) {
       HIPC(hipEventRecord(ctx->evH[h], st));
       HIPC(hipStreamWaitEvent(ctx->st3, ctx->evH[h], 0));
       for (int h0 = gstart; h0 <= h; h0 += head_max)
-        if (int rc = hop_forward_head(ctx, ctx->ws_side, h0, std::min(head_max, h + 1 - h0), labels))
+        if (int rc = hop_forward_head(ctx, ctx->ws_side, h0, std::min(head_max, h + 1 - h0), truth))
           return rc;
       if (head_dgrad_fwd(ctx)) {
         // The backward's first two products do not depend on the recurrence either: dpre = (dl Wc) (.) mask
@@ -1512,7 +1502,6 @@ static int upload_hop_weights(rau_ctx* ctx, const float* hop_w, const float* sel
 }
 
 // =============================================================== backward
-static int merge_state(rau_ctx* ctx, const char* fn, bool need_labels);
 // select_w: null, or the per-hop weights of the step-selection head's BCE with at least one of them non-zero
 // (rau_backward_select): the one place the two entry points differ is marked `sel` below.
 static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w) {
@@ -1528,10 +1517,7 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
   // step reads the resident batch, which rau_graph_step_select has checked)
   if (sel && !ctx->capturing)
     if (int rc = merge_state(ctx, "rau_backward_select", true)) return rc;
-  const int32_t* t_labels = ctx->capturing ? bs.labels_d : ctx->mg_labels_d;
-  const int t_G = ctx->capturing ? bs.held.ans_G : ctx->mg_ans_G;
-  const int32_t* t_ids = ctx->capturing ? bs.ans_ids_d : ctx->mg_ans_ids;
-  const float* t_score = ctx->capturing ? bs.ans_score_d : ctx->mg_ans_score;
+  const Truth t = ctx->capturing ? truth_of(bs) : ctx->mg.truth;
   const rau_config& c = ctx->cfg;
   const int B = c.B, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R,
             K = c.K, H = c.H, Q = ctx->Q;
@@ -1582,8 +1568,8 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
   const uint32_t* m_mf = mk(RAU_MASK_MF);
   if (sel)
     RUN("select_signal", 0, (double)HA * B * M * 4,
-        select_signal(st, HA * B, B, K, M, ctx->dopred, ctx->argmax_d, t_labels, t_ids, t_score, t_G,
-                      ctx->hopw_d + H, ctx->do_pred.W, ctx->sel_s, ctx->sel_add));
+        select_signal(st, HA * B, B, K, M, ctx->dopred, ctx->argmax_d, t, ctx->hopw_d + H, ctx->do_pred.W, ctx->sel_s,
+                      ctx->sel_add));
   if (HA > 0 && (!ctx->dpre_fwd || sel)) {
     LinOpts o = lin_opts(ctx, ctx->ws_chain);
     if (sel) { o.addend = ctx->sel_add; o.add_rs = M; }
@@ -1930,11 +1916,12 @@ static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select
   key |= (uint64_t)bs.held.feat_type << 32;  // ... and read the batch in its element type (three bits: 0..5)
   key |= (uint64_t)(bs.held.n_images > 0) << 35;   // ... through the gather of an image table (any table, any N)
   key |= (uint64_t)bs.held.bank << 36;   // ... of a bank batch: out of the bank (rau_bank_destroy reads this bit)
-  key |= (uint64_t)bs.held.ans_G << 37;   // ... against an answer set of G entries (0 = labels): another head kernel
+  // ... against an answer set of G entries (0 = labels): another head kernel (the one reader besides truth_of())
+  key |= (uint64_t)bs.held.ans_G << 37;
   key |= (uint64_t)ctx->cfg.B << 42;      // every launch is shaped by the batch size (rau_set_batch_size)
   key |= (uint64_t)sel << 31;             // ... and by the step-selection head's gradient being asked for
   if (int rc = upload_hop_weights(ctx, hop_w, select_w)) return rc;
-  ctx->mg_valid = false;
+  ctx->mg.valid = false;
   hipGraphExec_t exec = nullptr;
   for (auto& g : ctx->graphs)
     if (g.first == key) exec = g.second;
@@ -2006,7 +1993,7 @@ int rau_wait_grads(rau_ctx* ctx, int group, void* hip_stream) {
 // process or context held the CUs).  THAT step's results are invalid and the call says so -- once:
 // the word is cleared and the ctx falls back to the launch-per-step encoder for the rest of its life,
 // so repeating the step succeeds instead of failing forever.
-static int persist_check(rau_ctx* ctx) {
+int persist_check(rau_ctx* ctx) {
   if (!(ctx->persist_used && ctx->perr_h && *ctx->perr_h)) return RAU_OK;
   *ctx->perr_h = 0;
   hipMemsetAsync(ctx->perr_d, 0, sizeof(int), ctx->st);
@@ -2015,7 +2002,7 @@ static int persist_check(rau_ctx* ctx) {
   ctx->persist_gave_up = true;
   ctx->persist_used = false;
   ctx->fwd_done = false;
-  ctx->mg_valid = false;
+  ctx->mg.valid = false;
   return fail(RAU_ERR_DEVICE, "persistent encoder: a bounded wait on another workgroup's progress counter gave up; "
                               "the results of that step are invalid -- repeat it: this context now uses the "
                               "launch-per-step encoder");
@@ -2025,7 +2012,7 @@ int rau_sync(rau_ctx* ctx) {
   HIPC(hipStreamSynchronize(ctx->st));
   return persist_check(ctx);
 }
-static int d2h(rau_ctx* ctx, void* host, const void* dev, size_t bytes) {
+int d2h(rau_ctx* ctx, void* host, const void* dev, size_t bytes) {
   NEED(ctx && host, "null argument");
   HIPC(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->st));
   HIPC(hipStreamSynchronize(ctx->st));
@@ -2067,193 +2054,6 @@ int rau_get_att_state(rau_ctx* ctx, float* c, float* h) {
     if (int rc = d2h(ctx, c, ctx->cc + BR_, n * 4)) return rc;
   if (h)
     if (int rc = d2h(ctx, h, ctx->hh + BR_, n * 4)) return rc;
-  return RAU_OK;
-}
-
-// ---------------------------------------------- merged hops (hop_merge.hip): feval stats, predict_result
-static int merge_alloc(rau_ctx* ctx) {
-  if (ctx->mg_ready) return RAU_OK;
-  const rau_config& c = ctx->cfg;
-  const size_t B = ctx->cap, H = c.H;   // sized for the capacity
-#define CK(x) do { if (int rc_ = (x)) return rc_; } while (0)
-  CK(dalloc(ctx, &ctx->mg_rowf, B * (H + 2)));
-  CK(dalloc(ctx, &ctx->mg_rowi, B * RAU_STATS_NCOUNTS(H)));
-  CK(dalloc(ctx, &ctx->mg_out, (2 * H + 2) + RAU_STATS_NCOUNTS(H)));
-  CK(dalloc(ctx, &ctx->mg_ans, 2 * (H + 2) * B));
-  CK(dalloc(ctx, &ctx->mg_pred, 2 * B * c.K));
-  CK(dalloc(ctx, &ctx->mg_att, 2 * B * ctx->Sp));
-  CK(dalloc(ctx, &ctx->mg_score, 2 * (H + 2) * B + 2 * (H + 2)));
-#undef CK
-  ctx->mg_ready = true;
-  return RAU_OK;
-}
-// may the hop outputs of the last forward be read?  (checked before anything is launched)
-static int merge_state(rau_ctx* ctx, const char* fn, bool need_labels) {
-  if (!ctx->mg_valid)
-    return fail(RAU_ERR_STATE, "%s: no step-level forward result (none has run yet, it failed, or a module-level "
-                "entry point has run since)", fn);
-  if (ctx->slot_serial[ctx->mg_slot] != ctx->mg_serial)
-    return fail(RAU_ERR_STATE, "%s: batch slot %d, which the last forward read, has been uploaded into since", fn,
-                ctx->mg_slot);
-  if (need_labels && !ctx->mg_labels)
-    return fail(RAU_ERR_STATE, "%s: the batch of the last forward had no labels", fn);
-  return RAU_OK;
-}
-
-int rau_step_stats(rau_ctx* ctx, float* loss, float* loss_do_pred, int32_t* counts) {
-  NEED(ctx, "null ctx");
-  if (int rc = merge_state(ctx, "rau_step_stats", true)) return rc;
-  if (int rc = merge_alloc(ctx)) return rc;
-  const rau_config& c = ctx->cfg;
-  const int H = c.H, B = c.B, K = c.K, NL = 2 * H + 2, NC = RAU_STATS_NCOUNTS(H);
-  if (ctx->mg_ans_G > 0)
-    RUN("step_stats", 0, (double)B * (2 * H + 2) * K * 4,
-        step_stats_set(ctx->st, H, B, K, ctx->logits, ctx->dopred, ctx->argmax_d, ctx->lossrow, ctx->mg_ans_ids,
-                       ctx->mg_ans_w, ctx->mg_ans_score, ctx->mg_ans_G, ctx->mg_rowf, ctx->mg_rowi, ctx->mg_out,
-                       ctx->mg_score, ctx->mg_score + (size_t)2 * (H + 2) * ctx->cap));
-  else
-    RUN("step_stats", 0, (double)B * (2 * H + 2) * K * 4,
-        step_stats(ctx->st, H, B, K, ctx->logits, ctx->dopred, ctx->argmax_d, ctx->lossrow, ctx->mg_labels_d,
-                   ctx->mg_rowf, ctx->mg_rowi, ctx->mg_out));
-  std::vector<float> out((size_t)NL + NC);
-  if (int rc = d2h(ctx, out.data(), ctx->mg_out, out.size() * 4)) return rc;
-  if (loss) std::memcpy(loss, out.data(), (size_t)(H + 2) * 4);
-  if (loss_do_pred) std::memcpy(loss_do_pred, out.data() + H + 2, (size_t)H * 4);
-  if (counts) std::memcpy(counts, out.data() + NL, (size_t)NC * 4);
-  return RAU_OK;
-}
-
-// Metric scores of the answers (include/rau.h): rows [2(H+2)][cap] of mg_score, then 2(H+2) totals
-int rau_step_scores(rau_ctx* ctx, float* per_sample, float* total) {
-  NEED(ctx, "null ctx");
-  if (int rc = merge_state(ctx, "rau_step_scores", true)) return rc;
-  if (ctx->mg_ans_G <= 0)
-    return fail(RAU_ERR_STATE, "rau_step_scores: the batch of the last forward had no answer set (rau_set_answers)");
-  if (int rc = merge_alloc(ctx)) return rc;
-  const rau_config& c = ctx->cfg;
-  const int H = c.H, B = c.B, K = c.K;
-  float* tot_d = ctx->mg_score + (size_t)2 * (H + 2) * ctx->cap;
-  RUN("step_stats", 0, (double)B * (2 * H + 2) * K * 4,
-      step_stats_set(ctx->st, H, B, K, ctx->logits, ctx->dopred, ctx->argmax_d, ctx->lossrow, ctx->mg_ans_ids,
-                     ctx->mg_ans_w, ctx->mg_ans_score, ctx->mg_ans_G, ctx->mg_rowf, ctx->mg_rowi, ctx->mg_out,
-                     ctx->mg_score, tot_d));
-  if (per_sample)
-    HIPC(hipMemcpyAsync(per_sample, ctx->mg_score, (size_t)(H + 2) * B * 4, hipMemcpyDeviceToHost, ctx->st));
-  if (total) HIPC(hipMemcpyAsync(total, tot_d, (size_t)(H + 2) * 4, hipMemcpyDeviceToHost, ctx->st));
-  HIPC(hipStreamSynchronize(ctx->st));
-  return persist_check(ctx);
-}
-
-int rau_predict_scores(rau_ctx* ctx, float* oe, float* mc, float* totals) {
-  NEED(ctx, "null ctx");
-  if (int rc = merge_state(ctx, "rau_predict_scores", false)) return rc;
-  if (ctx->mg_ans_G <= 0)
-    return fail(RAU_ERR_STATE, "rau_predict_scores: the batch of the last forward had no answer set (rau_set_answers)");
-  if (!ctx->mg_merged || ctx->mg_pred_fwd != ctx->mg_fwd)
-    return fail(RAU_ERR_STATE, "rau_predict_scores: no rau_predict has run on the last forward");
-  const rau_config& c = ctx->cfg;
-  const int H = c.H, B = c.B, R = H + 2;
-  const int rows = ctx->mg_pred_mc ? 2 * R : R;   // mg_ans = oe [R][B] | mc [R][B]
-  float* tot_d = ctx->mg_score + (size_t)2 * R * ctx->cap;
-  RUN("answer_scores", 0, (double)rows * B * 8,
-      answer_scores(ctx->st, rows, B, c.K, ctx->mg_ans, ctx->mg_ans_ids, ctx->mg_ans_score, ctx->mg_ans_G,
-                    ctx->mg_score, tot_d));
-  if (oe) HIPC(hipMemcpyAsync(oe, ctx->mg_score, (size_t)R * B * 4, hipMemcpyDeviceToHost, ctx->st));
-  if (mc && ctx->mg_pred_mc)
-    HIPC(hipMemcpyAsync(mc, ctx->mg_score + (size_t)R * B, (size_t)R * B * 4, hipMemcpyDeviceToHost, ctx->st));
-  if (totals) {
-    HIPC(hipMemcpyAsync(totals, tot_d, (size_t)R * 4, hipMemcpyDeviceToHost, ctx->st));
-    if (ctx->mg_pred_mc)
-      HIPC(hipMemcpyAsync(totals + R, tot_d + R, (size_t)R * 4, hipMemcpyDeviceToHost, ctx->st));
-  }
-  HIPC(hipStreamSynchronize(ctx->st));
-  return persist_check(ctx);
-}
-
-int rau_predict(rau_ctx* ctx, const int32_t* mc_ans, int32_t n_mc, int32_t* oe, int32_t* mc) {
-  NEED(ctx, "null ctx");
-  const rau_config& c = ctx->cfg;
-  const int H = c.H, B = c.B, K = c.K;
-  const size_t nmc = mc_ans ? (size_t)B * n_mc : 0;
-  if (mc_ans) {
-    NEED(n_mc > 0, "rau_predict: n_mc=%d must be positive with an MC list", n_mc);
-    NEED(predict_rows_lds(K) <= 65536, "rau_predict: K=%d too large for the MC candidate mask", K);
-    for (size_t i = 0; i < nmc; ++i)
-      NEED(mc_ans[i] >= 0 && mc_ans[i] <= K, "rau_predict: mc_ans[%zu]=%d out of [0,%d] (0 = empty slot)", i,
-           mc_ans[i], K);
-  }
-  if (int rc = merge_state(ctx, "rau_predict", false)) return rc;
-  if (int rc = merge_alloc(ctx)) return rc;
-  if (nmc > ctx->mg_mc_cap) {   // grows only; the old buffer stays with the ctx until rau_destroy
-    if (int rc = dalloc(ctx, &ctx->mg_mc, nmc)) return rc;
-    ctx->mg_mc_cap = nmc;
-  }
-  if (nmc) HIPC(hipMemcpyAsync(ctx->mg_mc, mc_ans, nmc * 4, hipMemcpyHostToDevice, ctx->st));
-  int32_t* oe_d = ctx->mg_ans;
-  int32_t* mc_d = ctx->mg_ans + (size_t)(H + 2) * B;
-  RUN("predict_rows", 0, (double)B * (2 * H + 1) * K * 4,
-      predict_rows(ctx->st, H, B, K, ctx->Sp, ctx->logits, ctx->dopred, ctx->a, nmc ? ctx->mg_mc : nullptr,
-                   n_mc, oe_d, mc_d, ctx->mg_pred, ctx->mg_att));
-  ctx->mg_merged = false;
-  if (oe)
-    if (int rc = d2h(ctx, oe, oe_d, (size_t)(H + 2) * B * 4)) return rc;
-  if (mc && nmc)
-    if (int rc = d2h(ctx, mc, mc_d, (size_t)(H + 2) * B * 4)) return rc;
-  HIPC(hipStreamSynchronize(ctx->st));   // the caller's mc_ans is free on return
-  if (int rc = persist_check(ctx)) return rc;
-  ctx->mg_merged = true;
-  ctx->mg_pred_fwd = ctx->mg_fwd;
-  ctx->mg_pred_mc = nmc != 0;
-  return RAU_OK;
-}
-
-int rau_topk(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf) {
-  NEED(ctx, "null ctx");
-  const rau_config& c = ctx->cfg;
-  const int H = c.H, B = c.B, K = c.K;
-  NEED(k >= 1 && k <= K, "rau_topk: k=%d out of [1,%d] (the K of rau_create)", k, K);
-  if (int rc = merge_state(ctx, "rau_topk", false)) return rc;
-  if (k > ctx->mg_topk_k) {   // sized for the capacity; the smaller one goes once the larger one is there
-    uint32_t* fresh = nullptr;
-    if (int rc = dalloc(ctx, &fresh, (size_t)3 * (H + 2) * ctx->cap * k)) {
-      (void)hipGetLastError();   // the context stays as it was: nothing later may trip over this error
-      return rc;
-    }
-    if (void* old = ctx->mg_topk) {
-      HIPC(hipStreamSynchronize(ctx->st));
-      hipFree(old);
-      ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), old), ctx->allocs.end());
-      ctx->scratch.erase(std::remove_if(ctx->scratch.begin(), ctx->scratch.end(),
-                                        [&](const std::pair<void*, size_t>& r) { return r.first == old; }),
-                         ctx->scratch.end());
-    }
-    ctx->mg_topk = fresh;
-    ctx->mg_topk_k = k;
-  }
-  const size_t n = (size_t)(H + 2) * B * k;
-  int32_t* ids_d = static_cast<int32_t*>(ctx->mg_topk);
-  float* score_d = reinterpret_cast<float*>(ids_d + n);
-  float* conf_d = score_d + n;
-  RUN("topk_merged", 0, (double)B * (2 * H + 1) * K * 4,
-      topk_merged(ctx->st, H, B, K, k, ctx->logits, ctx->dopred, ids_d, score_d, conf_d));
-  if (ids) HIPC(hipMemcpyAsync(ids, ids_d, n * 4, hipMemcpyDeviceToHost, ctx->st));
-  if (score) HIPC(hipMemcpyAsync(score, score_d, n * 4, hipMemcpyDeviceToHost, ctx->st));
-  if (conf) HIPC(hipMemcpyAsync(conf, conf_d, n * 4, hipMemcpyDeviceToHost, ctx->st));
-  HIPC(hipStreamSynchronize(ctx->st));
-  return persist_check(ctx);
-}
-
-int rau_get_merged(rau_ctx* ctx, float* pred, float* att) {
-  NEED(ctx, "null ctx");
-  if (!ctx->mg_merged) return fail(RAU_ERR_STATE, "rau_get_merged: no rau_predict has run");
-  const rau_config& c = ctx->cfg;
-  if (pred)
-    if (int rc = d2h(ctx, pred, ctx->mg_pred, (size_t)2 * c.B * c.K * 4)) return rc;
-  if (att) {
-    HIPC(hipMemcpy2DAsync(att, (size_t)c.S * 4, ctx->mg_att, (size_t)ctx->Sp * 4, (size_t)c.S * 4,
-                          (size_t)2 * c.B, hipMemcpyDeviceToHost, ctx->st));
-    HIPC(hipStreamSynchronize(ctx->st));
-  }
   return RAU_OK;
 }
 

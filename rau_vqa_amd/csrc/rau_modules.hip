@@ -22,7 +22,7 @@ namespace {
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int mod_alloc(rau_ctx* ctx) {
-  ctx->mg_valid = false;   // every module-level entry point comes here: the step-level hop outputs are stale
+  ctx->mg.valid = false;   // every module-level entry point comes here: the step-level hop outputs are stale
   if (ctx->mod_ready) return 0;
   // Callers hand in / get back DENSE [.., S] tensors.  Internally every [.., S] tensor uses the
   // position pitch Sp (S rounded up to a multiple of 4: 7x7 maps 49 -> 52), so when Sp != S the
@@ -330,7 +330,7 @@ int rau_multimodal_forward(rau_ctx* ctx, int h, const float* q, const float* X, 
       conv_att_pre(st, B, M, S, A, Ih, ctx->WpT, ctx->att_i.b, Th, ctx->bf16));
   float* co = ctx->cc + (size_t)(h + 1) * BR_;
   float* ho = ctx->hh + (size_t)(h + 1) * BR_;
-  if (int rc = hop_forward(ctx, h, c_prev, h_prev, co, ho, Ih, Th, nullptr)) return rc;
+  if (int rc = hop_forward(ctx, h, c_prev, h_prev, co, ho, Ih, Th, Truth{})) return rc;
   if (logits) *logits = ctx->logits + (size_t)h * B * K;
   if (do_pred) *do_pred = ctx->dopred + (size_t)h * B;
   if (attprob) {
@@ -476,91 +476,65 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
 }
 
 // ------------------------------------------------------------ criteria[h]
-int rau_criterion_forward(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev,
-                          float* loss) {
-  NEED(ctx && logits, "null argument");
+// One body for the four entry points below (each has called mod_alloc): criteria[h] of `logits` against `t`, the
+// step's head kernel without do_pred.  d_logits null: the forward (loss to *loss if asked for); else the gradient.
+static int criterion(rau_ctx* ctx, int h, const float* logits, const Truth& t, float* loss, float scale,
+                     float** d_logits) {
   const rau_config& c = ctx->cfg;
-  NEED(h >= 0 && h < c.H, "rau_criterion_forward: h=%d out of [0,%d)", h, c.H);
-  if (int rc = mod_alloc(ctx)) return rc;
-  if (!labels_dev) {
-    const BatchSlot& bs = cur_batch(ctx);
-    if (!bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_criterion_forward: no labels");
-    if (bs.held.ans_G > 0)   // the resident batch's ground truth is its answer set
-      return rau_criterion_forward_set(ctx, h, logits, bs.held.ans_G, bs.ans_ids_d, bs.ans_w_d, loss);
-    labels_dev = bs.labels_d;
+  float* dl = ctx->dl + (size_t)h * c.B * c.K;
+  RUN(criterion_class(t), 0, (double)c.B * c.K * 12,
+      criterion_head(ctx->st, c.B, c.K, c.M, logits, t, nullptr, nullptr, nullptr, dl,
+                     ctx->lossrow + (size_t)h * c.B, ctx->argmax_d + (size_t)h * c.B, nullptr));
+  if (d_logits) {
+    if (scale != 1.f)   // dpred:mul(nHop), SS:569
+      RUN("scale_hops", 0, (double)c.B * c.K * 8, scale_inplace(ctx->st, (size_t)c.B * c.K, scale, dl));
+    *d_logits = dl;
+    return RAU_OK;
   }
-  RUN("ce_fwd", 0, (double)c.B * c.K * 12,
-      ce_fwd(ctx->st, c.B, c.K, c.M, logits, labels_dev, nullptr, nullptr, nullptr,
-             ctx->dl + (size_t)h * c.B * c.K, ctx->lossrow + (size_t)h * c.B,
-             ctx->argmax_d + (size_t)h * c.B, nullptr));
-  RUN("loss_reduce", 0, 0,
-      loss_reduce(ctx->st, 1, c.B, ctx->lossrow + (size_t)h * c.B, ctx->m_loss + h));
-  if (loss) {
-    HIPC(hipMemcpyAsync(loss, ctx->m_loss + h, sizeof(float), hipMemcpyDeviceToHost, ctx->st));
-    HIPC(hipStreamSynchronize(ctx->st));
-  }
+  RUN("loss_reduce", 0, 0, loss_reduce(ctx->st, 1, c.B, ctx->lossrow + (size_t)h * c.B, ctx->m_loss + h));
+  if (!loss) return RAU_OK;
+  HIPC(hipMemcpyAsync(loss, ctx->m_loss + h, sizeof(float), hipMemcpyDeviceToHost, ctx->st));
+  HIPC(hipStreamSynchronize(ctx->st));
   return RAU_OK;
+}
+
+int rau_criterion_forward(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev, float* loss) {
+  NEED(ctx && logits, "null argument");
+  NEED(h >= 0 && h < ctx->cfg.H, "rau_criterion_forward: h=%d out of [0,%d)", h, ctx->cfg.H);
+  if (int rc = mod_alloc(ctx)) return rc;
+  // labels_dev == NULL: the resident batch's ground truth, which may be its answer set
+  const Truth t = labels_dev ? Truth{labels_dev} : truth_of(cur_batch(ctx));
+  if (!t.present()) return fail(RAU_ERR_STATE, "rau_criterion_forward: no labels");
+  return criterion(ctx, h, logits, t, loss, 1.f, nullptr);
 }
 
 int rau_criterion_backward(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev,
                            float scale, float** d_logits) {
   NEED(ctx && logits && d_logits, "null argument");
-  const rau_config& c = ctx->cfg;
-  NEED(h >= 0 && h < c.H, "rau_criterion_backward: h=%d out of [0,%d)", h, c.H);
+  NEED(h >= 0 && h < ctx->cfg.H, "rau_criterion_backward: h=%d out of [0,%d)", h, ctx->cfg.H);
   if (int rc = mod_alloc(ctx)) return rc;
-  if (!labels_dev) {
-    const BatchSlot& bs = cur_batch(ctx);
-    if (!bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_criterion_backward: no labels");
-    if (bs.held.ans_G > 0)
-      return rau_criterion_backward_set(ctx, h, logits, bs.held.ans_G, bs.ans_ids_d, bs.ans_w_d, scale, d_logits);
-    labels_dev = bs.labels_d;
-  }
-  float* dl = ctx->dl + (size_t)h * c.B * c.K;
-  RUN("ce_fwd", 0, (double)c.B * c.K * 12,
-      ce_fwd(ctx->st, c.B, c.K, c.M, logits, labels_dev, nullptr, nullptr, nullptr, dl,
-             ctx->lossrow + (size_t)h * c.B, ctx->argmax_d + (size_t)h * c.B, nullptr));
-  if (scale != 1.f)   // dpred:mul(nHop), SS:569
-    RUN("scale_hops", 0, (double)c.B * c.K * 8, scale_inplace(ctx->st, (size_t)c.B * c.K, scale, dl));
-  *d_logits = dl;
-  return RAU_OK;
+  const Truth t = labels_dev ? Truth{labels_dev} : truth_of(cur_batch(ctx));
+  if (!t.present()) return fail(RAU_ERR_STATE, "rau_criterion_backward: no labels");
+  return criterion(ctx, h, logits, t, nullptr, scale, d_logits);
 }
 
-// criteria[h] against an answer set in device memory (ids / w [B,G]): the kernel of the step's head (ce_set.hip)
+// criteria[h] against an answer set in device memory (ids / w [B,G])
 int rau_criterion_forward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
                               const float* w_dev, float* loss) {
   NEED(ctx && logits && ids_dev && w_dev, "null argument");
-  const rau_config& c = ctx->cfg;
-  NEED(h >= 0 && h < c.H, "rau_criterion_forward_set: h=%d out of [0,%d)", h, c.H);
+  NEED(h >= 0 && h < ctx->cfg.H, "rau_criterion_forward_set: h=%d out of [0,%d)", h, ctx->cfg.H);
   NEED(G >= 1 && G <= kMaxAnswers, "rau_criterion_forward_set: G=%d out of [1,%d]", G, kMaxAnswers);
   if (int rc = mod_alloc(ctx)) return rc;
-  RUN("ce_set_fwd", 0, (double)c.B * c.K * 12,
-      ce_set_fwd(ctx->st, c.B, c.K, c.M, logits, ids_dev, w_dev, G, nullptr, nullptr, nullptr,
-                 ctx->dl + (size_t)h * c.B * c.K, ctx->lossrow + (size_t)h * c.B,
-                 ctx->argmax_d + (size_t)h * c.B, nullptr));
-  RUN("loss_reduce", 0, 0,
-      loss_reduce(ctx->st, 1, c.B, ctx->lossrow + (size_t)h * c.B, ctx->m_loss + h));
-  if (loss) {
-    HIPC(hipMemcpyAsync(loss, ctx->m_loss + h, sizeof(float), hipMemcpyDeviceToHost, ctx->st));
-    HIPC(hipStreamSynchronize(ctx->st));
-  }
-  return RAU_OK;
+  return criterion(ctx, h, logits, Truth{nullptr, ids_dev, w_dev, nullptr, G}, loss, 1.f, nullptr);
 }
 
 int rau_criterion_backward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
                                const float* w_dev, float scale, float** d_logits) {
   NEED(ctx && logits && ids_dev && w_dev && d_logits, "null argument");
-  const rau_config& c = ctx->cfg;
-  NEED(h >= 0 && h < c.H, "rau_criterion_backward_set: h=%d out of [0,%d)", h, c.H);
+  NEED(h >= 0 && h < ctx->cfg.H, "rau_criterion_backward_set: h=%d out of [0,%d)", h, ctx->cfg.H);
   NEED(G >= 1 && G <= kMaxAnswers, "rau_criterion_backward_set: G=%d out of [1,%d]", G, kMaxAnswers);
   if (int rc = mod_alloc(ctx)) return rc;
-  float* dl = ctx->dl + (size_t)h * c.B * c.K;
-  RUN("ce_set_fwd", 0, (double)c.B * c.K * 12,
-      ce_set_fwd(ctx->st, c.B, c.K, c.M, logits, ids_dev, w_dev, G, nullptr, nullptr, nullptr, dl,
-                 ctx->lossrow + (size_t)h * c.B, ctx->argmax_d + (size_t)h * c.B, nullptr));
-  if (scale != 1.f)   // dpred:mul(nHop), SS:569
-    RUN("scale_hops", 0, (double)c.B * c.K * 8, scale_inplace(ctx->st, (size_t)c.B * c.K, scale, dl));
-  *d_logits = dl;
-  return RAU_OK;
+  return criterion(ctx, h, logits, Truth{nullptr, ids_dev, w_dev, nullptr, G}, nullptr, scale, d_logits);
 }
 
 }  // extern "C"

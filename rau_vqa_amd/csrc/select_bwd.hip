@@ -75,13 +75,13 @@ __global__ __launch_bounds__(256) void k_select_wgrad(int rows, int M, const flo
 }  // namespace
 
 hipError_t select_signal(hipStream_t st, int rows, int Bper, int K, int M, const float* dopred,
-                         const int32_t* argmax, const int32_t* labels, const int32_t* ids, const float* score,
-                         int G, const float* selw, const float* wd, float* s, float* add) {
+                         const int32_t* argmax, const Truth& t, const float* selw, const float* wd, float* s,
+                         float* add) {
   if (rows <= 0) return hipSuccess;
-  if (Bper < 1 || rows % Bper || G < 0 || G > kMaxAnswers || (G > 0 ? !ids || !score : !labels))
+  if (Bper < 1 || rows % Bper || t.G < 0 || t.G > kMaxAnswers || (t.G > 0 ? !t.ids || !t.score : !t.labels))
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_select_signal, dim3(rows), dim3(256), 0, st, Bper, K, M, dopred, argmax, labels, ids,
-                     score, G, selw, wd, s, add);
+  hipLaunchKernelGGL(k_select_signal, dim3(rows), dim3(256), 0, st, Bper, K, M, dopred, argmax, t.labels, t.ids,
+                     t.score, t.G, selw, wd, s, add);
   return hipGetLastError();
 }
 
