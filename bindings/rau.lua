@@ -76,6 +76,8 @@ int rau_use_batch(rau_ctx* ctx, int slot);
 int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const float* w,
                     const float* score);
 int rau_batch_answers(rau_ctx* ctx, int32_t* G);
+int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n);
+int rau_batch_regions(rau_ctx* ctx, int* has);
 int rau_forward(rau_ctx* ctx);
 int rau_backward(rau_ctx* ctx, const float* hop_w);
 int rau_backward_select(rau_ctx* ctx, const float* hop_w, const float* select_w);
@@ -89,6 +91,10 @@ int rau_deeplstm_backward(rau_ctx* ctx, int t, const float* x, const float* stat
 int rau_multimodal_forward(rau_ctx* ctx, int h, const float* q, const float* X,
                            const float* c_prev, const float* h_prev, float** logits,
                            float** do_pred, float** attprob, float** c_out, float** h_out);
+int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const float* X,
+                                   const float* c_prev, const float* h_prev, const int32_t* regions_dev,
+                                   float** logits, float** do_pred, float** attprob, float** c_out,
+                                   float** h_out);
 int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
                             const float* c_prev, const float* h_prev, const float* d_logits,
                             const float* d_do_pred, const float* d_attprob,
@@ -300,6 +306,22 @@ function RAU:batchAnswers()
   local g = ffi.new('int32_t[1]')
   check(C.rau_batch_answers(self.h, g))
   return g[0]
+end
+
+-- Region counts (rau_set_regions): n IntTensor [B], 1 <= n[b] <= S; sample b attends to its first n[b] positions
+-- only (prefix-packed region features, padded grids), the others get attention and gradient exactly 0.  Always
+-- per SAMPLE: for an image table gather it first, n_image:index(1, image_of:long()).  slot as in setAnswers; the
+-- counts last until the next batch goes into that slot.
+function RAU:setRegions(n, slot)
+  n = n:int():contiguous()
+  assert(n:dim() == 1 and n:size(1) == self.n, 'n must be [B]')
+  check(C.rau_set_regions(self.h, slot or -1, n:data()))
+end
+-- whether the resident batch carries region counts
+function RAU:batchRegions()
+  local v = ffi.new('int[1]')
+  check(C.rau_batch_regions(self.h, v))
+  return v[0] ~= 0
 end
 
 -- A batch whose questions share feature maps: feats is the image TABLE [N,D,W,H] (Float- or HalfTensor, or a
@@ -718,11 +740,12 @@ local function clone(self, kind, i)
       return self.gradInput
     end
   elseif kind == 'multimodal' then
-    function m:forward(inp)   -- {q, X, c, h}
+    function m:forward(inp, regions)   -- {q, X, c, h}; regions: RAU.IntTensor [B] of region counts in device memory, or nil
       local o = {}
       for k = 1, 5 do o[k] = ffi.new('float*[1]') end
-      check(C.rau_multimodal_forward(self.rau.h, self.i, ptr_of(inp[1]), ptr_of(inp[2]),
-                                     ptr_of(inp[3]), ptr_of(inp[4]), o[1], o[2], o[3], o[4], o[5]))
+      check(C.rau_multimodal_forward_regions(self.rau.h, self.i, ptr_of(inp[1]), ptr_of(inp[2]),
+                                             ptr_of(inp[3]), ptr_of(inp[4]), regions and ptr_of(regions) or nil,
+                                             o[1], o[2], o[3], o[4], o[5]))
       local r = self.rau                                             -- {logits, dp, a, c, h}
       self.output = { Tensor.wrap(r, o[1][0], self.rau.n, cfg.K), Tensor.wrap(r, o[2][0], self.rau.n),
                       Tensor.wrap(r, o[3][0], self.rau.n, cfg.S), Tensor.wrap(r, o[4][0], self.rau.n, cfg.R),

@@ -380,6 +380,35 @@ int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const
                     const float* score);
 int rau_batch_answers(rau_ctx* ctx, int32_t* G);
 
+/* ---- region counts: attention over a sample's valid positions only -------------------------------
+ * Region features (bottom-up attention: 10-100 boxes per image) and aspect-preserving grids are stored
+ * prefix-packed and padded to S positions.  Region counts tell the attention which positions of a sample are
+ * real: n [batch] int32 host, 1 <= n[b] <= S.  Sample b attends to positions 0 .. n[b]-1; positions >= n[b] get
+ * attention exactly 0 in every hop, in train and evaluate mode, and with it gradient exactly 0 (the context sum,
+ * the softmax gradient, both conv gradients' terms at those positions and the attbymemory / feat_attprob weight
+ * gradients are all multiplied by that 0).  The features at masked positions must be finite (zero is
+ * recommended); they then influence no output and no gradient.  A count of 0 is invalid -- a softmax over nothing
+ * has no value: a caller with an empty image passes 1 and a zero map.
+ * n is always per SAMPLE: for an image-table or bank batch the host gathers n_image[image_of[b]] (4 bytes per
+ * sample, no feature byte added to the link).
+ *   slot = -1      the resident batch; synchronising, like rau_set_batch.
+ *   slot = 0 | 1   a slot of the asynchronous path: call it after rau_set_batch_async* on that slot and before
+ *                  rau_use_batch; the copy is enqueued on the copy stream behind the slot's batch and nothing is
+ *                  synchronised (a second call for the same upload first waits for the first one's copy).
+ * The counts belong to the slot's batch: any later batch upload into that slot and rau_set_batch_size clear them,
+ * rau_use_batch makes them current together with the batch, an upload into the other slot leaves them alone.  A
+ * forward that has run on the batch must be run again before rau_backward.  A batch without counts computes bit
+ * for bit, launch for launch, what it did before counts existed; counts all equal to S give the same bits too.
+ * rau_graph_step keys its cache by "has counts": a step captured without them is never replayed for a batch with
+ * them, nor the other way round.  The merged hops (rau_get_merged, rau_predict, rau_topk, rau_step_stats) read
+ * the attention and logits the forward left and so see the masked model.
+ * Errors, nothing uploaded, the previous counts stay in force: RAU_ERR_INVALID for a count outside 1..S;
+ * RAU_ERR_STATE when the slot holds no batch, or (slot 0 | 1) it is the current batch of a forward whose backward
+ * has not run.
+ * rau_batch_regions: *has = 1 when the resident batch carries counts, else 0. */
+int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n /* [batch] host */);
+int rau_batch_regions(rau_ctx* ctx, int* has);
+
 /* ---- the hot path ------------------------------------------------------------
  * rau_forward : SS:443-520  encoder unroll, length select, H-hop RAU, per-hop
  *               CrossEntropyCriterion forward, first-max argmax.
@@ -460,6 +489,15 @@ int rau_deeplstm_backward(rau_ctx* ctx, int t, const float* x, const float* stat
 int rau_multimodal_forward(rau_ctx* ctx, int h, const float* q, const float* X,
                            const float* c_prev, const float* h_prev, float** logits,
                            float** do_pred, float** attprob, float** c_out, float** h_out);
+/* rau_multimodal_forward with region counts (see rau_set_regions) in DEVICE memory: regions_dev [B] int32, NULL =
+ * none (the resident batch's own counts are NOT applied here: the caller passes what the clone is to see).
+ * Like ids in device tensors they cannot be range-checked by the call: the kernel clamps them into [1, S].
+ * rau_multimodal_backward needs no sibling: it reads the attention this forward saved, which is exactly 0 at the
+ * masked positions, and so is d_X there. */
+int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const float* X,
+                                   const float* c_prev, const float* h_prev, const int32_t* regions_dev,
+                                   float** logits, float** do_pred, float** attprob, float** c_out,
+                                   float** h_out);
 int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
                             const float* c_prev, const float* h_prev, const float* d_logits,
                             const float* d_do_pred, const float* d_attprob,

@@ -81,6 +81,9 @@ _SIGS = {
     # answer sets: multi-answer ground truth on a batch
     "rau_set_answers": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_batch_answers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    # region counts: attention over a sample's valid positions only
+    "rau_set_regions": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "rau_batch_regions": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rau_set_batch_typed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
     "rau_set_batch_async_typed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -115,6 +118,8 @@ _SIGS = {
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "rau_multimodal_forward": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 +
                                [C.POINTER(C.c_void_p)] * 5),
+    "rau_multimodal_forward_regions": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 +
+                                       [C.POINTER(C.c_void_p)] * 5),
     "rau_multimodal_backward": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 9 +
                                 [C.POINTER(C.c_void_p)] * 4),
     "rau_criterion_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,

@@ -277,11 +277,18 @@ hipError_t lstm_bwd_multi(hipStream_t st, int order, int nB, int R, const LstmBw
 // waves: the caller's choice of waves per sample for the forward kernel (8 | 16; 0 = the default, 8)
 struct AttPartials { int u_ns = 0; const float* u_bias = nullptr; int z_ns = 0; const float* z_bias = nullptr; int SL = 0; float* u_out = nullptr; int waves = 0;
                      // image table (forward only): sample b reads its P and I tiles at row img[b]; null = row b
-                     const int32_t* img = nullptr; };
+                     const int32_t* img = nullptr;
+                     // per-sample region counts (forward only): sample b attends to positions [0, min(SL, nreg[b]))
+                     // and gives the others attention exactly 0; indexed by the sample, never by img; null = none
+                     const int32_t* nreg = nullptr; };
 hipError_t att_fwd_fused(hipStream_t st, int nB, int M, int A, int S, const float* P,
                          const float* u, const float* ws, const float* bs, const float* zm,
                          const float* I, const float* qf, float* T, float* a, float* jv,
                          const AttPartials& ap = AttPartials());
+// Which of its two kernels att_fwd_fused launches for this shape: the LDS-DMA one (true) or the register-staged
+// one (T kept, S > 256 or not a multiple of 4, A or M above 512, or RAU_ATT_DMA_OFF set).  The step's launch
+// wrapper names the profile class after it: "att_fwd_fused" / "att_fwd_fused_regs".
+bool att_fwd_dma_ok(int M, int A, int S, bool keep_T, int waves_hint = 0);
 // One workgroup per sample, backward of the above: da = da_lin + sum_m dj I;
 // dz = softmax'(da); T -> dS = dz ws (1-T^2) in place; du = sum_s dS; dwsp = sum_s dz T.
 hipError_t att_bwd_fused(hipStream_t st, int nB, int M, int A, int S, const float* I,

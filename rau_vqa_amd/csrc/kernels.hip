@@ -418,6 +418,13 @@ __device__ __forceinline__ float block_sum_ordered(const float* red, int S, int 
 __device__ __forceinline__ int att_tile_row(const AttPartials& ap, int b) {
   return ap.img ? __builtin_amdgcn_readfirstlane(ap.img[b]) : b;
 }
+// Positions sample b attends to: the logical bound SL, or, for a batch that carries per-sample region counts,
+// min(SL, nreg[b]) -- indexed by the SAMPLE, not by the tile row above.  Uniform per workgroup like the tile
+// row: one scalar load.  Clamped to at least 1 (a softmax over nothing has no value; the host range-checks
+// what it uploads, counts handed over in device memory cannot be checked).
+__device__ __forceinline__ int att_positions(const AttPartials& ap, int b, int SL) {
+  return ap.nreg ? min(SL, max(1, __builtin_amdgcn_readfirstlane(ap.nreg[b]))) : SL;
+}
 
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void k_att_fwd_fused(
@@ -448,6 +455,7 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_fused(
     }
   }
   const int SL = ap.SL > 0 ? ap.SL : S;   // logical positions; [SL, S) are pad columns
+  const int SN = att_positions(ap, b, SL);   // ... of which this sample attends to [0, SN)
   if (ap.z_ns) {
     for (int s = tid; s < SL; s += NW * 64) {
       float v = ap.z_bias[s];
@@ -495,7 +503,7 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_fused(
   float mx = -INFINITY;
   for (int s = tid; s < S; s += (NW * 64)) {
     float z = -INFINITY;   // pad positions take no attention (and so no gradient)
-    if (s < SL) {
+    if (s < SN) {
       const float zmv = ap.z_ns ? zs[s] : zm[(size_t)b * S + s];
       z = block_sum_ordered<NW>(red, S, s) + bs[0] + zmv;
     }
@@ -595,6 +603,7 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_dma(
     }
   }
   const int SL = ap.SL > 0 ? ap.SL : S;   // logical positions; [SL, S) are pad columns
+  const int SN = att_positions(ap, b, SL);   // ... of which this sample attends to [0, SN)
   if (ap.z_ns) {
     for (int s = tid; s < SL; s += NW * 64) {
       float v = ap.z_bias[s];
@@ -655,8 +664,8 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_dma(
   // ---- phase 2: a = softmax(e + bs + zm)   (as in k_att_fwd_fused)
   float mx = -INFINITY;
   for (int s = tid; s < S; s += (NW * 64)) {
-    float z = -INFINITY;
-    if (s < SL) {
+    float z = -INFINITY;   // pad positions take no attention (and so no gradient)
+    if (s < SN) {
       const float zmv = ap.z_ns ? zs[s] : zm[(size_t)b * S + s];
       z = block_sum_ordered<NW>(red, S, s) + bs[0] + zmv;
     }
@@ -714,6 +723,22 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_dma(
   }
 }
 
+namespace {
+constexpr int kAttD8 = 8, kAttD16 = 4;   // ring depth of k_att_fwd_dma at 8 / 16 waves
+size_t att_fwd_dma_lds(int nw, int A, int S) {
+  const int d = nw == 8 ? kAttD8 : kAttD16;
+  return ((size_t)(nw + 2) * S + 2 * nw + A + (size_t)nw * d * S + 256) * sizeof(float);
+}
+}  // namespace
+
+// 14 x 14 (and any S % 4 == 0, S <= 256) maps on the step path (tanh(P + u) not kept): the LDS-DMA kernel
+bool att_fwd_dma_ok(int M, int A, int S, bool keep_T, int waves_hint) {
+  const bool dma_off = std::getenv("RAU_ATT_DMA_OFF") != nullptr;   // A/B knob; read per call: tests switch it between contexts
+  const int nw = att_waves(false, waves_hint);
+  return !dma_off && !keep_T && S % 4 == 0 && S <= 256 && A <= 64 * 8 && M <= 64 * 8 && (nw == 8 || nw == 16) &&
+         att_fwd_dma_lds(nw, A, S) <= 96 * 1024;
+}
+
 hipError_t att_fwd_fused(hipStream_t st, int nB, int M, int A, int S, const float* P,
                          const float* u, const float* ws, const float* bs, const float* zm,
                          const float* I, const float* qf, float* T, float* a, float* jv,
@@ -722,12 +747,9 @@ hipError_t att_fwd_fused(hipStream_t st, int nB, int M, int A, int S, const floa
       !split_span_ok(zm, ap.z_ns, (size_t)nB * (ap.SL ? ap.SL : S)))
     return kSplitStateError;
   const int nw = att_waves(false, ap.waves);
-  // 14 x 14 (and any S % 4 == 0, S <= 256) maps on the step path (tanh(P + u) not kept): the LDS-DMA kernel
-  static const bool dma_off = std::getenv("RAU_ATT_DMA_OFF") != nullptr;   // A/B knob
-  if (!dma_off && !T && S % 4 == 0 && S <= 256 && A <= 64 * 8 && M <= 64 * 8 && (nw == 8 || nw == 16)) {
-    constexpr int kD8 = 8, kD16 = 4;
-    const int d = nw == 8 ? kD8 : kD16;
-    const size_t ldsd = ((size_t)(nw + 2) * S + 2 * nw + A + (size_t)nw * d * S + 256) * sizeof(float);
+  if (att_fwd_dma_ok(M, A, S, T != nullptr, ap.waves)) {
+    constexpr int kD8 = kAttD8, kD16 = kAttD16;
+    const size_t ldsd = att_fwd_dma_lds(nw, A, S);
     static const bool attr = [] {   // once per process; magic static (contexts on several host threads)
       hipFuncSetAttribute(reinterpret_cast<const void*>(k_att_fwd_dma<8, kD8>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
@@ -736,15 +758,13 @@ hipError_t att_fwd_fused(hipStream_t st, int nB, int M, int A, int S, const floa
       return true;
     }();
     (void)attr;
-    if (ldsd <= 96 * 1024) {
-      if (nw == 8)
-        hipLaunchKernelGGL((k_att_fwd_dma<8, kD8>), dim3(nB), dim3(512), ldsd, st, M, A, S, P, u, ws, bs, zm, I,
-                           qf, a, jv, ap);
-      else
-        hipLaunchKernelGGL((k_att_fwd_dma<16, kD16>), dim3(nB), dim3(1024), ldsd, st, M, A, S, P, u, ws, bs, zm,
-                           I, qf, a, jv, ap);
-      return hipGetLastError();
-    }
+    if (nw == 8)
+      hipLaunchKernelGGL((k_att_fwd_dma<8, kD8>), dim3(nB), dim3(512), ldsd, st, M, A, S, P, u, ws, bs, zm, I,
+                         qf, a, jv, ap);
+    else
+      hipLaunchKernelGGL((k_att_fwd_dma<16, kD16>), dim3(nB), dim3(1024), ldsd, st, M, A, S, P, u, ws, bs, zm,
+                         I, qf, a, jv, ap);
+    return hipGetLastError();
   }
   const size_t lds = ((size_t)(nw + 2) * S + 2 * nw + A) * sizeof(float);
 #define ATT_FWD(NW_) hipLaunchKernelGGL(k_att_fwd_fused<NW_>, dim3(nB), dim3(NW_ * 64), lds, st, M, A, \
@@ -1150,10 +1170,11 @@ __global__ __launch_bounds__(256) void k_att_ctx(
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
   const int S4 = S >> 2;
   const int SL = ap.SL > 0 ? ap.SL : S;
+  const int SN = att_positions(ap, b, SL);   // the sample's own region count, where the batch carries one
   float mx = -INFINITY;
   for (int s = tid; s < S; s += 256) {
     float z = -INFINITY;   // pad positions take no attention (and so no gradient)
-    if (s < SL) {
+    if (s < SN) {
       float zmv;
       if (ap.z_ns) {
         zmv = ap.z_bias[s];

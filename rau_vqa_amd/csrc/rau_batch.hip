@@ -223,6 +223,7 @@ void hold(rau_ctx* ctx, int si, const Batch& b) {
   d.have = true;
   d.have_labels = b.labels != nullptr;
   d.ans_G = 0;   // an answer set belongs to the batch it was given to
+  d.regions = false;   // ... and so do region counts
 }
 
 void make_current(rau_ctx* ctx, int si) {
@@ -251,7 +252,7 @@ int set_batch_sync(rau_ctx* ctx, Batch b) {
     HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
   if (int rc = enqueue_batch(ctx, ctx->st, si, b)) return rc;
   HIPC(hipStreamSynchronize(ctx->st));   // the caller's (pageable) buffers are free on return
-  s.upload_pending = s.ans_pending = false;
+  s.upload_pending = s.ans_pending = s.reg_pending = false;
   hold(ctx, si, b);
   ctx->fwd_done = false;
   return RAU_OK;
@@ -278,7 +279,7 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   // that call performs the same wait before the caller's own writes -- include/rau.h.)
   if (s.upload_pending) {
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = false;
   }
   // NULL = the caller has filled the slot's pinned staging in place (rau_batch_slot)
   if (b.feats && b.feats != s.feats_h) std::memcpy(s.feats_h, b.feats, nf * feat_elem_bytes(b.feat_type));
@@ -334,6 +335,24 @@ int ensure_answers(rau_ctx* ctx, int si) {
     hipError_t e = hipHostMalloc(&h, 3 * n * 4, hipHostMallocDefault);
     if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(answer staging): %s", hipGetErrorString(e));
     s.ans_h = static_cast<int32_t*>(h);
+  }
+  return RAU_OK;
+}
+
+// first region counts of a slot: the device array [capacity] the attention kernels read and the pinned staging the
+// slot form copies from
+int ensure_regions(rau_ctx* ctx, int si) {
+  BatchSlot& s = ctx->slot[si];
+  if (!s.nreg_d) {
+    if (int rc = dalloc(ctx, &s.nreg_d, (size_t)ctx->cap)) return rc;
+    // dalloc clears the array on the chain stream; the slot form copies into it on the copy stream.  Once per slot.
+    HIPC(hipStreamSynchronize(ctx->st));
+  }
+  if (!s.nreg_h) {
+    void* h = nullptr;
+    hipError_t e = hipHostMalloc(&h, (size_t)ctx->cap * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(region count staging): %s", hipGetErrorString(e));
+    s.nreg_h = static_cast<int32_t*>(h);
   }
   return RAU_OK;
 }
@@ -410,7 +429,7 @@ int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_
   BatchSlot& s = ctx->slot[slot];
   if (s.upload_pending) {   // the caller is about to overwrite the staging: its last copy must have left
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = false;
   }
   if (feats_host) *feats_host = s.feats_h;
   if (tokens_host) *tokens_host = s.tokens_h;
@@ -497,7 +516,7 @@ int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const
   if (int rc = ensure_answers(ctx, si)) return rc;
   if (s.ans_pending) {   // the staging's previous set has not left it yet (two sets for one upload)
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = false;
   }
   int32_t* ids_h = s.ans_h;
   float* w_h = reinterpret_cast<float*>(s.ans_h + n);
@@ -537,6 +556,61 @@ int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const
 int rau_batch_answers(rau_ctx* ctx, int32_t* G) {
   NEED(ctx && G, "null argument");
   *G = truth_of(cur_batch(ctx)).G;
+  return RAU_OK;
+}
+
+// Region counts for the batch in a slot: rau_set_answers' slot and ordering rules.  Everything is checked before
+// anything moves.
+int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n) {
+  NEED(ctx && n, "null argument");
+  NEED(slot >= -1 && slot <= 1, "rau_set_regions: slot %d (-1 = the resident batch, 0 or 1)", slot);
+  const rau_config& c = ctx->cfg;
+  const int si = slot < 0 ? ctx->cur_slot : slot;
+  BatchSlot& s = ctx->slot[si];
+  if (!s.held.have)
+    return fail(RAU_ERR_STATE, "rau_set_regions: slot %d holds no batch (upload the batch first)", si);
+  if (slot >= 0 && si == ctx->cur_slot && ctx->fwd_done)
+    return fail(RAU_ERR_STATE, "rau_set_regions: slot %d is the current batch of a forward pass whose backward has "
+                "not run", si);
+  for (int b = 0; b < c.B; ++b)
+    NEED(n[b] >= 1 && n[b] <= c.S, "rau_set_regions: n[%d]=%d out of [1,%d]", b, n[b], c.S);
+  if (slot >= 0)
+    if (int rc = ensure_async(ctx)) return rc;
+  if (int rc = ensure_regions(ctx, si)) return rc;
+  if (s.reg_pending) {   // the staging's previous counts have not left it yet (two sets for one upload)
+    HIPC(hipEventSynchronize(s.uploaded));
+    s.upload_pending = s.ans_pending = s.reg_pending = false;
+  }
+  std::memcpy(s.nreg_h, n, (size_t)c.B * 4);
+  hipStream_t st = slot < 0 ? ctx->st : ctx->stc;
+  if (slot < 0) {
+    if (s.upload_pending) HIPC(hipStreamWaitEvent(st, s.uploaded, 0));   // behind an asynchronous upload of the batch
+  } else {
+    // the slot's buffers may still be read by the last step that used them
+    if (si == ctx->cur_slot) {
+      HIPC(hipEventRecord(s.consumed, ctx->st));
+      s.consumed_valid = true;
+    }
+    if (s.consumed_valid) HIPC(hipStreamWaitEvent(st, s.consumed, 0));
+  }
+  HIPC(hipMemcpyAsync(s.nreg_d, s.nreg_h, (size_t)c.B * 4, hipMemcpyHostToDevice, st));
+  if (slot < 0) {
+    HIPC(hipStreamSynchronize(st));
+    // (the chain stream waited for a pending upload above: every copy behind `uploaded` has left its staging)
+    s.upload_pending = s.ans_pending = s.reg_pending = false;
+  } else {
+    HIPC(hipEventRecord(s.uploaded, st));   // rau_use_batch orders the step behind the counts too
+    s.upload_pending = s.reg_pending = true;
+    if (si == ctx->cur_slot) HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
+  }
+  s.held.regions = true;
+  if (si == ctx->cur_slot) ctx->fwd_done = false;   // a forward that ran on the batch did not see these counts
+  return RAU_OK;
+}
+
+int rau_batch_regions(rau_ctx* ctx, int* has) {
+  NEED(ctx && has, "null argument");
+  *has = cur_batch(ctx).held.regions ? 1 : 0;
   return RAU_OK;
 }
 

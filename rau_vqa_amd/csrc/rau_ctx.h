@@ -85,6 +85,9 @@ struct BatchDesc {
   // answer set (rau_set_answers): G entries per sample in the slot's ans_* buffers, 0 = none.  It replaces the
   // labels for the criterion head and the statistics; a batch with a set counts as labelled.
   int ans_G = 0;
+  // region counts (rau_set_regions): sample b attends to the first nreg_d[b] positions only.  Like the answer set
+  // they belong to the batch: hold() drops them.
+  bool regions = false;
 };
 // One of the two batch slots.  slot[cur_slot] is the resident batch (cur_batch() below): the only record of it.
 // Slot 0's device buffers exist from rau_create on; slot 1's, the pinned staging the loader may fill in place, the
@@ -110,6 +113,11 @@ struct BatchSlot {
   float *ans_w_d = nullptr, *ans_score_d = nullptr;
   int32_t* ans_h = nullptr;         // pinned host: ids | w | score
   bool ans_pending = false;         // a copy out of ans_h is behind the last record of `uploaded`
+  // region counts of the batch: [capacity] device and pinned host, allocated at the slot's first set (a captured
+  // step holds nreg_d's address)
+  int32_t* nreg_d = nullptr;
+  int32_t* nreg_h = nullptr;
+  bool reg_pending = false;         // a copy out of nreg_h is behind the last record of `uploaded`
   hipEvent_t uploaded = nullptr;    // recorded on the copy stream behind the slot's H2D copies
   hipEvent_t consumed = nullptr;    // recorded on the chain stream when the ctx switches away from the slot
   // ---- what the device buffers hold
@@ -512,10 +520,11 @@ struct HopGrad {
 };
 __attribute__((visibility("hidden"))) int hop_forward(rau_ctx* ctx, int h, const float* cp,
     const float* hp, float* c_out, float* h_out, const float* Ih, const float* Pin,
-    const Truth& truth);
+    const Truth& truth, const int32_t* nreg = nullptr /* device [B] region counts, see hop_forward_chain */);
 __attribute__((visibility("hidden"))) int hop_forward_chain(rau_ctx* ctx, int h, const float* cp,
     const float* hp, float* c_out, float* h_out, const float* Ih, const float* Pin,
-    const int32_t* img = nullptr /* device index: sample b's Ih / Pin tiles are row img[b] (image table) */);
+    const int32_t* img = nullptr /* device index: sample b's Ih / Pin tiles are row img[b] (image table) */,
+    const int32_t* nreg = nullptr /* device [B]: sample b attends to its first nreg[b] positions only */);
 // The resident batch as per-sample maps [B][D][Sp] in its element type: the buffer itself, or for a batch
 // with an image table its expansion (expand_features on the chain stream, once per upload).
 __attribute__((visibility("hidden"))) int batch_maps(rau_ctx* ctx, const float** maps);

@@ -595,6 +595,7 @@ void rau_destroy(rau_ctx* ctx) {
     if (s.image_of_h) hipHostFree(s.image_of_h);
     if (s.bank_idx_h) hipHostFree(s.bank_idx_h);
     if (s.ans_h) hipHostFree(s.ans_h);
+    if (s.nreg_h) hipHostFree(s.nreg_h);
     if (s.uploaded) hipEventDestroy(s.uploaded);
     if (s.consumed) hipEventDestroy(s.consumed);
   }
@@ -816,6 +817,7 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   for (int si = 0; si < 2; ++si) {
     ctx->slot[si].held = BatchDesc{};
     ctx->slot[si].upload_pending = ctx->slot[si].consumed_valid = ctx->slot[si].ans_pending = false;
+    ctx->slot[si].reg_pending = false;
     ++ctx->slot_serial[si];
   }
   ctx->cur_slot = 0;
@@ -847,7 +849,7 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
 // rau_forward runs the heads on the weight-gradient stream (idle during the forward pass), so the
 // hop-to-hop critical path is the chain alone; the module-level entry points run both on st.
 int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, float* c_out,
-                      float* h_out, const float* Ih, const float* Pin, const int32_t* img) {
+                      float* h_out, const float* Ih, const float* Pin, const int32_t* img, const int32_t* nreg) {
   const rau_config& c = ctx->cfg;
   const int B = c.B, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R;
   hipStream_t st = ctx->st;
@@ -897,8 +899,11 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
     // fits and streams a sample faster (B = 256: 124.2 -> 129.5 k QA/s); the training step keeps 8
     ap.waves = ctx->mode == RAU_MODE_EVAL ? 16 : 0;
     ap.img = img;   // image table: Pin and Ih hold one tile per image, sample b reads row img[b]
+    ap.nreg = nreg;   // region counts: per SAMPLE, also where the tiles are per image
+    // (the profile tells the fused family's two kernels apart: the LDS-DMA one keeps the family's name)
+    const char* fused_cls = att_fwd_dma_ok(M, A, S, false, ap.waves) ? "att_fwd_fused" : "att_fwd_fused_regs";
     if (!ctx->att_split)
-      RUN("att_fwd_fused", 2.0 * B * S * (A + M), ((double)B * A * S + BM_ * S) * 4,
+      RUN(fused_cls, 2.0 * B * S * (A + M), ((double)B * A * S + BM_ * S) * 4,
           att_fwd_fused(st, B, M, A, S, Pin, slab_u, ctx->att_score.W, ctx->att_score.b, slab_z, Ih, qf,
                         nullptr, ah, ctx->jv, ap));
     else
@@ -976,8 +981,8 @@ int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const Tru
 }
 
 int hop_forward(rau_ctx* ctx, int h, const float* cp, const float* hp, float* c_out, float* h_out,
-                const float* Ih, const float* Pin, const Truth& truth) {
-  if (int rc = hop_forward_chain(ctx, h, cp, hp, c_out, h_out, Ih, Pin)) return rc;
+                const float* Ih, const float* Pin, const Truth& truth, const int32_t* nreg) {
+  if (int rc = hop_forward_chain(ctx, h, cp, hp, c_out, h_out, Ih, Pin, nullptr, nreg)) return rc;
   if (h_out != ctx->hh + (size_t)(h + 1) * ctx->cfg.B * ctx->cfg.R)
     return fail(RAU_ERR_INVALID, "hop_forward: h_out must be the ctx's hop slot");
   return hop_forward_head(ctx, ctx->ws_chain, h, 1, truth);
@@ -1436,7 +1441,8 @@ int rau_forward(rau_ctx* ctx) {
     if (int rc = hop_forward_chain(ctx, h, ctx->cc + (size_t)h * BR_, ctx->hh + (size_t)h * BR_,
                                    ctx->cc + (size_t)(h + 1) * BR_, ctx->hh + (size_t)(h + 1) * BR_,
                                    ctx->I + (ctx->I_shared ? 0 : (size_t)h * BM_ * S),
-                                   ctx->I_shared ? ctx->P0 : ctx->T + (size_t)h * B * A * S, img))
+                                   ctx->I_shared ? ctx->P0 : ctx->T + (size_t)h * B * A * S, img,
+                                   bs.held.regions ? bs.nreg_d : nullptr))
       return rc;
     // classifier + criterion heads of the finished hops: nothing on the recurrence waits for
     // them, so they run on the weight-gradient stream (idle in the forward pass), batched over
@@ -1920,6 +1926,8 @@ static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select
   key |= (uint64_t)bs.held.ans_G << 37;
   key |= (uint64_t)ctx->cfg.B << 42;      // every launch is shaped by the batch size (rau_set_batch_size)
   key |= (uint64_t)sel << 31;             // ... and by the step-selection head's gradient being asked for
+  // ... and the attention kernels hold the slot's region counts or a null pointer (rau_set_regions)
+  key |= (uint64_t)bs.held.regions << 62;
   if (int rc = upload_hop_weights(ctx, hop_w, select_w)) return rc;
   ctx->mg.valid = false;
   hipGraphExec_t exec = nullptr;

@@ -275,6 +275,13 @@ int rau_deeplstm_backward(rau_ctx* ctx, int t, const float* x, const float* stat
 int rau_multimodal_forward(rau_ctx* ctx, int h, const float* q, const float* X, const float* c_prev,
                            const float* h_prev, float** logits, float** do_pred, float** attprob,
                            float** c_out, float** h_out) {
+  return rau_multimodal_forward_regions(ctx, h, q, X, c_prev, h_prev, nullptr, logits, do_pred, attprob, c_out, h_out);
+}
+
+// regions_dev: [B] device region counts (the attention kernel clamps them into [1, S]); NULL = every position
+int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const float* X, const float* c_prev,
+                                   const float* h_prev, const int32_t* regions_dev, float** logits,
+                                   float** do_pred, float** attprob, float** c_out, float** h_out) {
   NEED(ctx && q, "null argument");
   const rau_config& c = ctx->cfg;
   NEED(h >= 0 && h < c.H, "rau_multimodal_forward: h=%d out of [0,%d)", h, c.H);
@@ -330,7 +337,7 @@ int rau_multimodal_forward(rau_ctx* ctx, int h, const float* q, const float* X, 
       conv_att_pre(st, B, M, S, A, Ih, ctx->WpT, ctx->att_i.b, Th, ctx->bf16));
   float* co = ctx->cc + (size_t)(h + 1) * BR_;
   float* ho = ctx->hh + (size_t)(h + 1) * BR_;
-  if (int rc = hop_forward(ctx, h, c_prev, h_prev, co, ho, Ih, Th, Truth{})) return rc;
+  if (int rc = hop_forward(ctx, h, c_prev, h_prev, co, ho, Ih, Th, Truth{}, regions_dev)) return rc;
   if (logits) *logits = ctx->logits + (size_t)h * B * K;
   if (do_pred) *do_pred = ctx->dopred + (size_t)h * B;
   if (attprob) {

@@ -42,6 +42,9 @@ class QuestionSet:
     ans_ids: np.ndarray = None
     ans_w: np.ndarray = None
     ans_score: np.ndarray = None
+    # region counts (rau_set_regions), optional: [number of images] valid positions of every image of the name
+    # list (prefix-packed region features padded to S), indexed like img_list
+    img_regions: np.ndarray = None
 
 
 def vqa_scores(counts):
@@ -79,6 +82,7 @@ class DataClass:
         self._unique = False      # the last next_batch_feat asked for an image table: so will the prefetched one
         self._bank = None         # (key, files, row of every question): bank_rows' answer for one tab_featpaths
         self.last_answers = None  # (ids, w[, score]) rows of the batch last taken, when qs carries answer sets
+        self.last_regions = None  # [B] per-sample region counts of the batch last taken, when qs carries img_regions
 
     # ---- batch order options, loader.lua:1219-1291
     def set_batch_order_option(self, opt):
@@ -209,6 +213,10 @@ class DataClass:
                                  np.ascontiguousarray(self.qs.ans_w[idx], np.float32))
             if self.qs.ans_score is not None:
                 self.last_answers += (np.ascontiguousarray(self.qs.ans_score[idx], np.float32),)
+        self.last_regions = None
+        if self.qs.img_regions is not None:              # per sample, whatever form the feats take
+            self.last_regions = np.ascontiguousarray(
+                np.asarray(self.qs.img_regions)[np.asarray(self.qs.img_list)[idx] - 1], np.int32)
         self.batch_index += B
         if self.batch_index + B > self.n:                # loader.lua:911-913
             self.reorder()
@@ -317,17 +325,35 @@ def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=12
     return v
 
 
-def feed(rau, batch, feat_type=None, answers=None):
+def feed(rau, batch, feat_type=None, answers=None, regions=None):
     """next_batch_feat's tuple -> rau_set_batch (the H2D of SS:434-439); returns qids.
     feat_type: that of the feats (needed for bf16 and fp8, which arrive as uint16 / uint8 bits).  A tuple of
     next_batch_feat(unique=True) goes up as an image table, one of next_batch_rows as a bank batch.
     The batch may be smaller than the context's capacity (a test split at test_batch_size): set_batch
     takes the size from x_len and switches the context to it.
     answers = (ids, w[, score]) rows of the batch (DataClass.last_answers, when its QuestionSet has ans_ids /
-    ans_w): attached with rau.set_answers once the batch is up; None changes nothing."""
-    qids = _feed_batch(rau, batch, feat_type)
-    if answers is not None:
-        rau.set_answers(*answers)
+    ans_w): attached with rau.set_answers once the batch is up; None changes nothing.
+    regions = per-sample region counts [B] of the batch (DataClass.last_regions, when its QuestionSet has
+    img_regions): attached with rau.set_regions once the batch is up; None changes nothing.
+    A batch given as a dict (the keyword arguments of RAU.set_batch: feats, tokens, lens, labels and optionally
+    image_of, bank_rows, answers, regions, qids) goes to set_batch as it is: its "regions" key is per sample, or
+    per image beside image_of / bank_rows; the regions= argument, when given, replaces it."""
+    if isinstance(batch, dict):
+        kw = {k: v for k, v in batch.items() if k != "qids"}
+        if feat_type is not None:
+            kw["feat_type"] = feat_type
+        if answers is not None:
+            kw["answers"] = answers
+        if regions is not None:
+            kw.pop("regions", None)
+        rau.set_batch(**kw)
+        qids = batch.get("qids")
+    else:
+        qids = _feed_batch(rau, batch, feat_type)
+        if answers is not None:
+            rau.set_answers(*answers)
+    if regions is not None:
+        rau.set_regions(regions)
     return qids
 
 
@@ -405,6 +431,8 @@ class SlotFeeder:
             rau.set_batch_async(s, has_labels=labels, bank_rows=rows, image_of=image_of)
             if d.last_answers is not None:
                 rau.set_answers(*d.last_answers, slot=s)
+            if d.last_regions is not None:
+                rau.set_regions(d.last_regions, slot=s)
             rau.use_batch(s)
             return qids
         batch = d.next_batch_feat(*self.args, unique=self.share_images)
@@ -421,6 +449,8 @@ class SlotFeeder:
         rau.set_batch_async(s, has_labels=labels, **table, **self._ft)   # staging filled in place: no host copy
         if d.last_answers is not None:                # the QuestionSet carries answer sets: behind the upload
             rau.set_answers(*d.last_answers, slot=s)
+        if d.last_regions is not None:                # ... and region counts: per sample, also for an image table
+            rau.set_regions(d.last_regions, slot=s)
         rau.use_batch(s)
         return qids
 

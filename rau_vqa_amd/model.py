@@ -52,6 +52,18 @@ class Config:
                 "mf": (self.H, B, self.M)}
 
 
+def regions_of(n_image, image_of):
+    """Per-sample region counts of a batch that names its images by row: n_image [N] counts of the table's (or
+    the bank rows') maps, image_of [B] 0-based rows -> int32 [B] = n_image[image_of], what set_regions takes."""
+    n_image = np.ascontiguousarray(n_image, np.int32)
+    image_of = np.ascontiguousarray(image_of, np.int64)
+    if n_image.ndim != 1 or image_of.ndim != 1:
+        raise ValueError("regions_of: n_image [N] and image_of [B] must be 1-d")
+    if image_of.size and (image_of.min() < 0 or image_of.max() >= n_image.size):
+        raise ValueError(f"regions_of: image_of out of [0, {n_image.size})")
+    return np.ascontiguousarray(n_image[image_of], np.int32)
+
+
 def hop_weights(variant: str, H: int, epoch: int = 0):
     """Per-hop scale of the criterion gradient for the four training scripts.
 
@@ -306,6 +318,36 @@ class RAU:
         L.check(self._lib.rau_batch_answers(self._h, C.byref(g)))
         return int(g.value)
 
+    # ---- region counts: attention over a sample's valid positions only (rau_set_regions)
+    def set_regions(self, n, slot=None):
+        """Give the batch in `slot` (None: the resident batch; 0 | 1: after set_batch_async(slot), before
+        use_batch(slot)) per-sample region counts n [batch] int, 1 <= n[b] <= S: sample b attends to its first
+        n[b] positions only, the others get attention and gradient exactly 0 in every hop (prefix-packed region
+        features padded to S, padded grids).  Features at masked positions must be finite; zero is recommended.
+        Always per sample: for an image table gather first (regions_of).  The counts last until the next batch
+        goes into that slot."""
+        n = np.ascontiguousarray(n, np.int32)
+        if n.shape != (self._n,):
+            raise ValueError(f"region counts must be [{self._n}], one per sample")
+        L.check(self._lib.rau_set_regions(self._h, -1 if slot is None else int(slot), n.ctypes.data))
+
+    def batch_regions(self) -> bool:
+        """Whether the resident batch carries region counts."""
+        v = C.c_int()
+        L.check(self._lib.rau_batch_regions(self._h, C.byref(v)))
+        return bool(v.value)
+
+    @staticmethod
+    def _sample_regions(regions, image_of, B):
+        """regions= of set_batch / set_batch_async as per-sample counts: [B] as given, or, for a batch with an
+        image table or bank rows, per-image [N] gathered through image_of (None: one image per sample)."""
+        if image_of is not None:
+            return regions_of(regions, image_of)
+        regions = np.ascontiguousarray(regions, np.int32)
+        if regions.shape != (B,):
+            raise ValueError(f"region counts must be [{B}], one per sample")
+        return regions
+
     def step_scores(self):
         """Metric score of every row's answer of the last forward (feval rule, as step_stats) against its
         batch's answer set: (per_sample [H+2, n], total [H+2]); rows = hops, uni, select."""
@@ -328,7 +370,7 @@ class RAU:
         return oe, mcs, tot
 
     def set_batch(self, feats, tokens, lens, labels=None, feat_type=None, image_of=None, bank_rows=None,
-                  answers=None):
+                  answers=None, regions=None):
         """feat_type "f32" | "f16" | "bf16" | "e4m3" | "e5m2" (default: from the dtype, see feat16.infer;
         bf16 is uint16 bits, fp8 is uint8 codes, both must be named): a 16-bit or fp8 map gives the same
         results, bit for bit, as the f32 map of its widened values.
@@ -337,10 +379,16 @@ class RAU:
         bank_rows [N] (feats None): the table is bank[bank_rows], gathered inside device memory.
         The batch size is lens.shape[0]: a batch of n <= capacity rows switches the context to n first
         (set_batch_size); every array must agree on n, checked before anything reaches the library.
-        answers = (ids, w[, score]): set_answers on the batch once it is up."""
+        answers = (ids, w[, score]): set_answers on the batch once it is up.
+        regions: set_regions on the batch once it is up; per sample [B], or with image_of / bank_rows per image
+        [N] (gathered here: regions_of)."""
+        if regions is not None:   # checked before anything reaches the library
+            regions = self._sample_regions(regions, image_of, int(np.asarray(lens).shape[0]))
         self._set_batch(feats, tokens, lens, labels, feat_type, image_of, bank_rows)
         if answers is not None:
             self.set_answers(*answers)
+        if regions is not None:
+            self.set_regions(regions)
 
     def _set_batch(self, feats, tokens, lens, labels, feat_type, image_of, bank_rows):
         c = self.cfg
@@ -422,7 +470,8 @@ class RAU:
                 "labels": view(p[3], B, C.c_int32, np.int32, (B,))}
 
     def set_batch_async(self, slot, feats=None, tokens=None, lens=None, labels=None, has_labels=True,
-                        feat_type=None, image_of=None, n_images=None, bank_rows=None, answers=None):
+                        feat_type=None, image_of=None, n_images=None, bank_rows=None, answers=None,
+                        regions=None):
         """Enqueue the upload of a batch into `slot` on the copy stream and return.  Arrays left None
         are taken from the slot's staging (filled in place through batch_slot).  feat_type: as in
         set_batch; with feats None it names what the staging holds (default "f32").
@@ -431,11 +480,17 @@ class RAU:
         bank_rows [N] (feats None): the table is bank[bank_rows]; the slot's feature staging is not read.
         The batch size is lens.shape[0] when lens is given (the context is switched to it first, which
         drops both slots' earlier uploads), else the current batch_size.
-        answers = (ids, w[, score]): set_answers(slot=slot) behind the upload, on the copy stream."""
+        answers = (ids, w[, score]): set_answers(slot=slot) behind the upload, on the copy stream.
+        regions: set_regions(slot=slot) behind the upload; per sample, or per image as in set_batch."""
+        if regions is not None:
+            B = self._n if lens is None else int(np.asarray(lens).shape[0])
+            regions = self._sample_regions(regions, image_of, B)
         self._set_batch_async(slot, feats, tokens, lens, labels, has_labels, feat_type, image_of, n_images,
                               bank_rows)
         if answers is not None:
             self.set_answers(*answers, slot=slot)
+        if regions is not None:
+            self.set_regions(regions, slot=slot)
 
     def _set_batch_async(self, slot, feats, tokens, lens, labels, has_labels, feat_type, image_of, n_images,
                          bank_rows):

@@ -76,10 +76,14 @@ class DeepLSTMClone(_Clone):
 class MultimodalClone(_Clone):
     """multimodal_clones[h]: {q, X, c, h} -> {logits, do_pred, attprob, c', h'} (SS:292-307)."""
 
-    def forward(self, q, X, c_prev, h_prev):
+    def forward(self, q, X, c_prev, h_prev, regions=None):
+        """regions: int32 CUDA tensor [B] of region counts (RAU.set_regions' meaning; the kernel clamps them into
+        [1, S]); None: every position.  backward() needs nothing more: it reads the attention saved here."""
         outs = [C.c_void_p() for _ in range(5)]
-        L.check(self._lib.rau_multimodal_forward(self._h, self.i, _p(q), _p(X), _p(c_prev),
-                                                 _p(h_prev), *[C.byref(o) for o in outs]))
+        if regions is not None and (regions.dtype != torch.int32 or regions.numel() != self.rau.batch_size):
+            raise ValueError("regions must be an int32 tensor with one count per sample")
+        L.check(self._lib.rau_multimodal_forward_regions(self._h, self.i, _p(q), _p(X), _p(c_prev),
+                                                         _p(h_prev), _p(regions), *[C.byref(o) for o in outs]))
         c = self.rau.cfg
         return (self._view(outs[0], self.rau.batch_size, c.K), self._view(outs[1], self.rau.batch_size),
                 self._view(outs[2], self.rau.batch_size, c.S), self._view(outs[3], self.rau.batch_size, c.R),
@@ -116,10 +120,12 @@ class CriterionClone(_Clone):
         return self._view(out, self.rau.batch_size, self.rau.cfg.K)
 
 
-def feval(rau, feats, x, x_len, y, hop_w, select_w=None):
+def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None):
     """The tensor half of the reference's feval, loop for loop (SS:443-596), on the clones.
     select_w [H] (None: the reference's zero, SS:566): hop h's multimodal clone receives
     d_do_pred = joint.bce_grad(do_pred_h, argmax_h == y, select_w[h]), which trains the step-selection head.
+
+    regions [B] int32 (None: every position): per-sample region counts, handed to every multimodal clone's forward.
 
     feats [B,D,S] float32, x [T,B] int32, x_len [B] int32, y [B] int32: CUDA tensors.
     Gradients accumulate into the ctx's flat buffers (zero them first).  Returns
@@ -127,10 +133,10 @@ def feval(rau, feats, x, x_len, y, hop_w, select_w=None):
     """
     ext = torch.cuda.ExternalStream(rau.stream(), device=feats.device)
     with torch.cuda.stream(ext):   # torch's glue ops join the ctx's own stream order
-        return _feval(rau, feats, x, x_len, y, hop_w, select_w)
+        return _feval(rau, feats, x, x_len, y, hop_w, select_w, regions)
 
 
-def _feval(rau, feats, x, x_len, y, hop_w, select_w=None):
+def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None):
     c = rau.cfg
     dev = feats.device
     emb = [EmbedClone(rau, t) for t in range(c.T)]
@@ -152,7 +158,7 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None):
     att_h = [torch.zeros(rau.batch_size, c.R, device=dev)]
     logits, losses, answers, dopred = [], [], [], []
     for h in range(c.H):
-        lg, dp, _a, cn, hn = mm[h].forward(rnn_out, feats, att_c[h], att_h[h])
+        lg, dp, _a, cn, hn = mm[h].forward(rnn_out, feats, att_c[h], att_h[h], regions=regions)
         logits.append(lg)
         dopred.append(dp)
         att_c.append(cn)
