@@ -117,7 +117,10 @@ const char* rau_last_error(void);
 int rau_abi_version(void);
 
 /* Builds the three protos + their clones (SS:200-347): allocates parameters,
- * gradients, activations for T tokens and H hops, and the ctx stream. */
+ * gradients, activations for T tokens and H hops, and the ctx stream.
+ * RAU_ERR_INVALID (before the device is touched) for a configuration outside what the kernels take: widths that
+ * are no positive multiple of 4, and an S above what the attention kernels' 64 KB of LDS hold -- 4096 positions
+ * for contexts of up to 64 samples, (16352 - A) / 18 above (900 at A = 128); the message names the bound. */
 int rau_create(const rau_config* cfg, rau_ctx** out);
 void rau_destroy(rau_ctx* ctx);
 

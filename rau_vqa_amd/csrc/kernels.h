@@ -318,6 +318,12 @@ hipError_t att_bwd_split(hipStream_t st, int nB, int M, int A, int S, const floa
                          float* T_to_dS, float* dz, float* du, float* dwsp, const float* Psrc,
                          const float* u, float* part, int da_ns = 0, int SL = 0,
                          const float* da_add = nullptr);
+// Largest position pitch at which every attention kernel of a family (split: the two above; else the two fused
+// ones) gets the dynamic LDS it asks for.  Above 256 positions those are the register-staged kernels, which
+// launch without hipFuncAttributeMaxDynamicSharedMemorySize and so with at most 64 KB: 4 S floats in the split
+// family (4096 positions); (nw + 2) S + 2 nw + A forward and (nw + 1) S + nw backward in the fused one, nw
+// waves -- the forward taken at the wider of its training and evaluate-mode forms (900 positions at A = 128).
+int att_max_pitch(bool split, int A, int bwd_waves_hint);
 // The feature-map passes below read the resident batch in its own element type ft (rau_feat_type:
 // RAU_FEAT_F32, 16-bit RAU_FEAT_F16 / RAU_FEAT_BF16 or 8-bit RAU_FEAT_E4M3 / RAU_FEAT_E5M2 bit patterns laid
 // out like the f32 form), widen each element exactly to f32 and then do the f32 form's arithmetic: results

@@ -3,6 +3,7 @@
 // allows), one wave per row for row reductions (64-lane shuffle trees), and
 // two-stage deterministic reductions instead of float atomics.
 #include "common.h"
+#include <algorithm>
 #include <cstdlib>
 
 #include "kernels.h"
@@ -1049,7 +1050,7 @@ __global__ __launch_bounds__(NW * 64) void k_att_bwd_dma(
 
 // whether att_bwd_fused takes the LDS-DMA kernel for these sizes (the only one that can write dS as bf16)
 static bool att_bwd_dma_sizes(int nw, int M, int A, int S) {
-  static const bool dma_off = std::getenv("RAU_ATT_DMA_OFF") != nullptr;   // A/B knob
+  const bool dma_off = std::getenv("RAU_ATT_DMA_OFF") != nullptr;   // A/B knob; read per call, as att_fwd_dma_ok does
   if (dma_off || S % 4 != 0 || S > 256 || A > 64 * 8 || M > 64 * 8 || (nw != 8 && nw != 16)) return false;
   const int d = nw == 8 ? 8 : 4;
   return ((size_t)(nw + 1) * S + nw + (size_t)nw * d * S + 256) * sizeof(float) <= 96 * 1024;
@@ -1402,6 +1403,16 @@ hipError_t att_bwd_split(hipStream_t st, int nB, int M, int A, int S, const floa
   hipLaunchKernelGGL(k_att_ds, dim3(nc, nB), dim3(256), (size_t)(S + 4) * sizeof(float), st, nB, A, S,
                      part, a, da_lin, ws, T_to_dS, dz, du, dwsp, Psrc, u, da_ns, SL, da_add);
   return hipGetLastError();
+}
+
+int att_max_pitch(bool split, int A, int bwd_waves_hint) {
+  constexpr long kFloats = 64 * 1024 / 4;   // what a launch gets without the attribute
+  long s = kFloats / 4;                      // k_att_score_part, k_att_da_part: [4][S]
+  if (!split) {
+    const int nf = std::max(att_waves(false, 0), att_waves(false, 16)), nb = att_waves(true, bwd_waves_hint);
+    s = std::min((kFloats - 2 * nf - A) / (nf + 2), (kFloats - nb) / (nb + 1));
+  }
+  return s > 0 ? (int)s & ~3 : 0;
 }
 
 // 32x32 LDS-tiled transpose (bulk stream; no chain priority)

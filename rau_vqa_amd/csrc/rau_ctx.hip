@@ -95,6 +95,10 @@ struct BatchPlan {
   size_t ws[3], att_part;                    // workspace needs, floats: ws in the order of stream_ws()
   size_t mcount[5];                          // mask sites, elements
 };
+// the attention family of a B-sample batch (measurements: plan_batch below)
+static bool att_family_split(int B) {
+  return std::getenv("RAU_ATT_SPLIT") != nullptr || (B <= 64 && std::getenv("RAU_ATT_FUSED") == nullptr);
+}
 static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
   const rau_config& c = ctx->cfg;
   const int T = c.T, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R, K = c.K,
@@ -145,8 +149,7 @@ static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
   // Small batches (one 16-wave workgroup per sample leaves most CUs idle): B = 32 / 64 / 128 fused
   // 3.83 / 4.57 / 6.06 ms, split in 8 row chunks 3.63 / 4.39 / 6.05 ms -> split up to B = 64
   // (RAU_ATT_FUSED keeps the fused kernels).
-  p->att_split = std::getenv("RAU_ATT_SPLIT") != nullptr ||
-                 (B <= 64 && std::getenv("RAU_ATT_FUSED") == nullptr);
+  p->att_split = att_family_split(B);
   {
     // Weight-stationary persistent encoder (enc_ws.hip): chosen by shape, never by the environment in
     // normal use -- contexts of up to 64 samples (the strong-scaling shards of configs[3]) are bound
@@ -263,6 +266,14 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   NEED(c.Rq > 0 && c.Rq % 4 == 0 && c.R > 0 && c.R % 4 == 0 && c.M > 0 && c.M % 4 == 0 &&
            c.A > 0 && c.A % 4 == 0 && c.D > 0 && c.D % 4 == 0,
        "rau_create: Rq,R,M,A,D must be positive multiples of 4");
+  {
+    // a context may shrink its batch (rau_set_batch_size), never grow it: the family of B samples is the narrower
+    const bool split = att_family_split(c.B);
+    const int smax = att_max_pitch(split, c.A, c.dtype ? 8 : 0);
+    NEED(c.S <= smax,   // (a multiple of 4: the same bound on the pitch)
+         "rau_create: S=%d is above the %d positions at which the %s attention kernels' LDS request still fits "
+         "the 64 KB of a launch (B=%d, A=%d)", c.S, smax, split ? "split" : "fused", c.B, c.A);
+  }
   NEED(c.dtype == RAU_F32 || c.dtype == RAU_BF16 || c.dtype == RAU_F32S,
        "rau_create: dtype %d not supported", c.dtype);
   const float ps[5] = {c.p_we, c.p_rnn, c.p_q, c.p_x, c.p_mf};

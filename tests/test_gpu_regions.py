@@ -25,7 +25,8 @@ TOL = 1e-4
 STATE, INVALID = -3, -1
 BITS = ("losses", "argmax", "logits", "dopred", "att", "q", "att_c", "att_h", "g_embed", "g_rnn", "g_mult")
 
-SHAPES = {"small": (util.SMALL, 0.5), "seven": (SEVEN, 0.5), "wide": (WIDE, 0.3)}
+BOXES = dict(B=8, T=5, V=40, E=8, Rq=16, D=24, S=100, M=40, A=20, R=16, K=12, H=3)   # box features at a fixed S
+SHAPES = {"small": (util.SMALL, 0.5), "seven": (SEVEN, 0.5), "wide": (WIDE, 0.3), "boxes": (BOXES, 0.5)}
 
 
 def counts_of(name):
@@ -34,6 +35,8 @@ def counts_of(name):
         return np.array([12, 7, 3, 1, 5, 12, 2, 9], np.int32)
     if name == "seven":
         return np.array([49, 48, 1, 17, 30, 5], np.int32)
+    if name == "boxes":
+        return np.array([100, 10, 99, 36, 1, 57, 64, 100], np.int32)
     n = np.random.default_rng(11).integers(1, WIDE["S"] + 1, WIDE["B"]).astype(np.int32)
     n[:6] = [196, 1, 195, 7, 64, 129]
     return n
@@ -118,6 +121,9 @@ CASES = [
     ("wide", {}, FUSED),                                                   # above 64 samples: the fused family
     ("wide", {"RAU_ATT_SPLIT": "1"}, SPLIT),
     ("wide", {"RAU_ATT_DMA_OFF": "1"}, REGS),
+    ("boxes", {}, SPLIT),
+    ("boxes", {"RAU_ATT_FUSED": "1"}, FUSED),
+    ("boxes", {"RAU_ATT_FUSED": "1", "RAU_ATT_DMA_OFF": "1"}, REGS),
 ]
 
 

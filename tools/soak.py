@@ -6,6 +6,7 @@ import numpy as np
 from tests import util
 from tests.test_gpu_parity import check
 from tests.test_gpu_fuzz import draw
+from tests.test_gpu_positions import CASES   # the S classes of the kernel dispatch
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 s0 = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 bad = 0
@@ -15,7 +16,7 @@ for seed in range(s0, s0 + n):
     dims = draw(rng)
     if seed % 2:   # every other case above the 64-sample switch
         dims["B"] = int(rng.integers(65, 150))
-        dims["S"] = int(rng.choice([49, 196, int(rng.integers(1, 60))]))
+        dims["S"] = int(rng.choice([49, 196, int(rng.integers(1, 60))] + sorted(CASES)))
     sh = util.shapes(dims)
     lens = rng.integers(0, dims["T"] + 1, dims["B"]).astype(np.int32)
     if lens.max() == 0: lens[0] = dims["T"]

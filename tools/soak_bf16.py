@@ -5,6 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from tests.test_gpu_bf16 import run
 from tests.test_gpu_fuzz import draw
+from tests.test_gpu_positions import CASES   # the S classes of the kernel dispatch
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 s0 = int(sys.argv[2]) if len(sys.argv) > 2 else 500
 bad = 0
@@ -12,7 +13,7 @@ t0 = time.time()
 for seed in range(s0, s0 + n):
     rng = np.random.default_rng(1000 + seed)
     dims = draw(rng)
-    dims["S"] = int(rng.choice([196, 196, 49, int(rng.integers(1, 60))]))
+    dims["S"] = int(rng.choice([196, 196, 49, int(rng.integers(1, 60))] + sorted(CASES)))
     if seed % 2: dims["B"] = int(rng.integers(65, 120))
     dims["H"] = min(dims["H"], 3)
     try:
