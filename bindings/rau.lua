@@ -4,7 +4,7 @@ Presents the reference's nn.Module call surface for the RAU hot path so that
 experiments/Ours_*/LstmAttCtrlGradNoiseDontSelect.lua keeps its structure:
   :training() / :evaluate()          (SS:449-450, 479, 648-649, 676)
   :getParameters()                   (SS:322-324)  -> flat param / grad handles
-  feval's tensor half                (SS:428-596)  -> rau:forward() / rau:backward(w [, select_w])
+  feval's tensor half                (SS:428-596)  -> rau:forward() / rau:backward(w, select_w, att_w)
   adam(x, dx, lr, ...) x 3 + noise + clip (SS:597-630, 770-772) -> rau:update(...)
 
 No LuaJIT/Torch7 toolchain exists in the build image, so this file is shipped as
@@ -82,6 +82,11 @@ int rau_forward(rau_ctx* ctx);
 int rau_backward(rau_ctx* ctx, const float* hop_w);
 int rau_backward_select(rau_ctx* ctx, const float* hop_w, const float* select_w);
 int rau_graph_step_select(rau_ctx* ctx, const float* hop_w, const float* select_w, int zero_grads_first);
+int rau_set_att_targets(rau_ctx* ctx, int slot, const float* t);
+int rau_batch_att_targets(rau_ctx* ctx, int* has);
+int rau_backward_att(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w);
+int rau_graph_step_att(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w, int zero_grads_first);
+int rau_att_stats(rau_ctx* ctx, float* loss, float* mass, int32_t* hits, int32_t* n_sup);
 int rau_embed_forward(rau_ctx* ctx, int t, const int32_t* tokens_dev, float** we);
 int rau_embed_backward(rau_ctx* ctx, int t, const int32_t* tokens_dev, const float* d_we);
 int rau_deeplstm_forward(rau_ctx* ctx, int t, const float* x, const float* state,
@@ -108,6 +113,10 @@ int rau_criterion_forward_set(rau_ctx* ctx, int h, const float* logits, int32_t 
                               const float* w_dev, float* loss);
 int rau_criterion_backward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
                                const float* w_dev, float scale, float** d_logits);
+int rau_att_criterion_forward(rau_ctx* ctx, int h, const float* attprob_dev, const float* t_dev,
+                              const int32_t* nreg_dev, float* loss);
+int rau_att_criterion_backward(rau_ctx* ctx, int h, const float* attprob_dev, const float* t_dev,
+                               const int32_t* nreg_dev, float scale, float** d_attprob);
 int rau_dev_alloc(rau_ctx* ctx, size_t n_floats, float** out);
 int rau_dev_free(rau_ctx* ctx, float* p);
 int rau_dev_fill(rau_ctx* ctx, float* dst, size_t n, float value);
@@ -324,6 +333,33 @@ function RAU:batchRegions()
   return v[0] ~= 0
 end
 
+-- Attention targets (rau_set_att_targets): t FloatTensor [B,S] (or [B,W,H]), entries finite and >= 0, one target map
+-- per SAMPLE; a row of zeros is an unsupervised sample.  backward(hop_w, select_w, att_w) then adds
+-- att_w[h] * mean_b sum_s t (-log(attprob_h + 1e-12)) to the objective.  slot as in setAnswers; the targets last
+-- until the next batch goes into that slot, and may be set after the forward.
+function RAU:setAttTargets(t, slot)
+  t = t:float():contiguous()
+  assert(t:size(1) == self.n and t:nElement() == self.n * self.cfg.S, 't must be [B,S]')
+  check(C.rau_set_att_targets(self.h, slot or -1, t:data()))
+end
+-- whether the resident batch carries attention targets
+function RAU:batchAttTargets()
+  local v = ffi.new('int[1]')
+  check(C.rau_batch_att_targets(self.h, v))
+  return v[0] ~= 0
+end
+-- ATT loss [H], attention mass on the target [H], pointing-game hits [H] (Lua tables) and the number of
+-- supervised rows, of the last forward against its batch's targets
+function RAU:attStats()
+  local H = self.cfg.H
+  local l, m = ffi.new('float[?]', H), ffi.new('float[?]', H)
+  local hits, n = ffi.new('int32_t[?]', H), ffi.new('int32_t[1]')
+  check(C.rau_att_stats(self.h, l, m, hits, n))
+  local loss, mass, hit = {}, {}, {}
+  for i = 1, H do loss[i] = l[i - 1]; mass[i] = m[i - 1]; hit[i] = hits[i - 1] end
+  return loss, mass, hit, n[0]
+end
+
 -- A batch whose questions share feature maps: feats is the image TABLE [N,D,W,H] (Float- or HalfTensor, or a
 -- ByteTensor of fp8 codes with feat_type 'e4m3' | 'e5m2'),
 -- image_of an IntTensor [B] of 1-BASED table rows, as Torch indexes (feats:index(1, image_of:long()) is the
@@ -407,10 +443,26 @@ function RAU:backward(hop_w, select_w)
   end
 end
 
+-- rau:backward(hop_w, select_w, att_w): att_w (optional) = per-hop weight of the attention supervision against
+-- setAttTargets' maps, where the reference passes gradattprob = zeros (SS:361, 573); nil keeps those zeros and
+-- is the two-argument form above
+local backward_select = RAU.backward
+function RAU:backward(hop_w, select_w, att_w)
+  if not att_w then return backward_select(self, hop_w, select_w) end
+  local H = self.cfg.H
+  check(C.rau_backward_att(self.h, hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil,
+                           hop_array(H, att_w)))
+end
+
 -- zeroGradParameters (unless zero_grads == false) + forward + backward as one captured graph launch
-function RAU:graphStep(hop_w, select_w, zero_grads)
+function RAU:graphStep(hop_w, select_w, zero_grads, att_w)
   local H = self.cfg.H
   local z = (zero_grads == false) and 0 or 1
+  if att_w then
+    check(C.rau_graph_step_att(self.h, hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil,
+                               hop_array(H, att_w), z))
+    return
+  end
   check(C.rau_graph_step_select(self.h, hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil, z))
 end
 

@@ -449,6 +449,58 @@ int rau_backward(rau_ctx* ctx, const float* hop_w /* [H] host */);
 int rau_backward_select(rau_ctx* ctx, const float* hop_w /* [H] host */, const float* select_w /* [H] host, NULL = zeros */);
 int rau_graph_step_select(rau_ctx* ctx, const float* hop_w, const float* select_w, int zero_grads_first);
 
+/* ---- attention supervision: train attprob on per-sample target maps ---------------------------------
+ * The fifth output of multimodal, the attention map (SS:306-307), gets the reference's constant zero gradient
+ * (gradattprob, SS:361, handed to every multimodals[h]:backward, SS:573).  With target maps on the batch -- human
+ * attention maps on grids, ground-truth boxes on region features -- rau_backward_att puts a loss there.
+ *
+ * Targets: t [n,S] float32 host, dense; n the current batch size, S the configured position count; every entry
+ * finite and >= 0.  Rows are not normalised by the library: a caller who wants a distribution passes one.  A row
+ * of zeros is an UNSUPERVISED sample: zero loss, zero gradient, not counted in the statistics.  Targets are always
+ * per SAMPLE, also for image-table and bank batches (a map belongs to a question).  With region counts on the
+ * batch (rau_set_regions) positions s >= n_reg[b] are ignored whatever they hold.
+ * slot = -1 | 0 | 1, ownership and lifetime are exactly those of rau_set_regions: the targets belong to the slot's
+ * batch; a later upload into that slot, or rau_set_batch_size, clears them; rau_use_batch makes them current; the
+ * slot form enqueues on the copy stream behind the slot's batch and synchronises nothing; device and pinned blocks
+ * are allocated at the slot's first set.  One difference: the forward does not read targets, so setting them after
+ * a forward needs no second forward.
+ * Errors, nothing uploaded, the previous targets stay in force: RAU_ERR_INVALID for a negative or non-finite
+ * entry; RAU_ERR_STATE when the slot holds no batch, or (slot 0 | 1) it is the current batch of a forward whose
+ * backward has not run.
+ * rau_batch_att_targets: *has = 1 when the resident batch carries targets, else 0.
+ *
+ * The loss of hop h, with a = attprob of the last step-level forward and eps = 1e-12f (nn.BCECriterion's):
+ *   ATT_h = (1/n) * sum_b sum_{s < n_reg[b]} t[b,s] * ( -log(a[h,b,s] + eps) )
+ * and the step's objective becomes sum_h hop_w[h]*CE_h + select_w[h]*BCE_h + att_w[h]*ATT_h.
+ * The gradient at the attprob output, float32, every operation rounded once, in this order:
+ *   da[h,b,s] = -( (att_w[h] * t[b,s]) / (a[h,b,s] + eps) ) / n
+ * exactly +0 where t[b,s] == 0 and where s >= n_reg[b].  It enters the attention backward in front of the softmax
+ * gradient, where the reference adds its zeros.  Because of eps it is finite for every a >= 0; the softmax
+ * gradient multiplies it by a, so where the softmax has underflowed to 0 the gradient VANISHES: a target on a
+ * position whose attention is exactly 0 (in particular one behind a region count) cannot pull it back.
+ * rau_backward_att: att_w [H] host, NULL = zeros.  att_w == NULL or all zeros IS rau_backward_select with the other
+ * two arguments: the same launches, the same bits, whether or not the batch carries targets.  Active hops: [0, HA),
+ * HA - 1 the last hop with any of the three weights non-zero.  A non-zero att_w on a batch without targets:
+ * RAU_ERR_STATE, nothing launched.  A non-finite weight: RAU_ERR_INVALID.  The scratch ([H,B,Sp] floats) is
+ * allocated at the first call with a non-zero att_w.
+ * rau_graph_step_att is rau_graph_step_select with that backward: att_w is read from device memory like hop_w, so
+ * it may change between replays; "any att_w non-zero" and "batch has targets" join the cache key.
+ *
+ * rau_att_stats: what a training loop logs, of the last step-level forward (train or evaluate mode; the rule of
+ * rau_step_stats) against its batch's targets; RAU_ERR_STATE without such a forward or without targets.  A row is
+ * supervised when some t[b,s] > 0 with s < n_reg[b].
+ *   loss[h]  = ATT_h
+ *   mass[h]  = mean over the supervised rows of sum_s a[h,b,s] * [t[b,s] > 0]     (0 when there is none)
+ *   hits[h]  = supervised rows whose first-max attention position has t > 0      (the pointing game)
+ *   *n_sup   = supervised rows
+ * Positions behind a region count are excluded from all of them.  Sums run in a fixed order without float
+ * atomics: repeated calls give the same bits.  Any output may be NULL. */
+int rau_set_att_targets(rau_ctx* ctx, int slot, const float* t /* [n,S] host, dense */);
+int rau_batch_att_targets(rau_ctx* ctx, int* has);
+int rau_backward_att(rau_ctx* ctx, const float* hop_w, const float* select_w /* NULL = zeros */, const float* att_w /* NULL = zeros */);
+int rau_graph_step_att(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w, int zero_grads_first);
+int rau_att_stats(rau_ctx* ctx, float* loss /* [H] */, float* mass /* [H] */, int32_t* hits /* [H] */, int32_t* n_sup);
+
 /* ---- module-level entry points: one call per nn.Module :forward / :backward -----
  * For hosts that keep feval's own loops (SS:443-596) and call the clones one by one.
  * t in [0,T) / h in [0,H) select the clone (the reference's embed_clones[t+1],
@@ -521,6 +573,17 @@ int rau_criterion_forward_set(rau_ctx* ctx, int h, const float* logits, int32_t 
                               const float* w_dev, float* loss);
 int rau_criterion_backward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
                                const float* w_dev, float scale, float** d_logits);
+
+/* The attention supervision above for hosts that call the clones one by one: attprob_dev [B,S] (the attprob output
+ * of rau_multimodal_forward), t_dev [B,S] targets and nreg_dev [B] region counts (NULL = none, clamped into [1, S]),
+ * all dense in DEVICE memory.  :forward -> *loss = ATT_h (host, may be NULL); :backward -> d_attprob [B,S]
+ * (ctx-owned, valid until the next call) = -((scale * t) / (attprob + eps)) / B in that order, which goes straight
+ * into rau_multimodal_backward's d_attprob.  Values in t_dev cannot be checked by the call: a negative or NaN
+ * entry counts as 0. */
+int rau_att_criterion_forward(rau_ctx* ctx, int h, const float* attprob_dev /* [B,S] */, const float* t_dev /* [B,S] */,
+                              const int32_t* nreg_dev /* NULL */, float* loss);
+int rau_att_criterion_backward(rau_ctx* ctx, int h, const float* attprob_dev, const float* t_dev,
+                               const int32_t* nreg_dev, float scale, float** d_attprob /* ctx-owned [B,S] */);
 
 /* ---- device tensors: the tensor algebra feval does BETWEEN module calls ----------------------
  * The reference's loops copy state rows where x_len[k] == t (`rnn_out[k] = lst[k]`, SS:455-461;

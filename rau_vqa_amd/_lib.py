@@ -109,6 +109,16 @@ _SIGS = {
     # the same with the step-selection head's BCE gradient, weighted per hop (NULL = zeros)
     "rau_backward_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_graph_step_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    # attention supervision: per-sample target maps on a batch, their loss at the attprob output
+    "rau_set_att_targets": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "rau_batch_att_targets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rau_backward_att": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rau_graph_step_att": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "rau_att_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "rau_att_criterion_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_float)]),
+    "rau_att_criterion_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                             C.POINTER(C.c_void_p)]),
     # module-level entry points: device pointers in, pointers to ctx-owned slots out
     "rau_embed_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_embed_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

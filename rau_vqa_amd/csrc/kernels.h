@@ -425,6 +425,16 @@ hipError_t select_signal(hipStream_t st, int rows, int Bper, int K, int M, const
                          float* add);
 hipError_t select_wgrad(hipStream_t st, int rows, int M, const float* s, const float* mf, float* dW,
                         float* db);
+// Attention supervision (att_sup.hip, rau_backward_att / rau_att_stats).  Rows are [hop][sample], hop-major: a and
+// da at row pitch a_rs / d_rs, the targets t [Bper] rows at pitch t_rs, nreg [Bper] region counts or null.
+// att_sup_grad: da[h,b,s] = -((w[h] t) / (a + 1e-12f)) / Bper below the count, +0 elsewhere, over the whole of d_rs;
+// w = w_dev [hops] (device), or with w_dev null `scale` for every hop.  One launch for all hops.
+// att_sup_stats: outf [2][hops] = ATT_h | mean attention mass on t > 0 over the supervised rows, outi [2][hops] =
+// pointing-game hits | supervised rows; rowf / rowi [2][hops * Bper] scratch.  Fixed summation order, no atomics.
+hipError_t att_sup_grad(hipStream_t st, int hops, int Bper, int S, const float* a, int a_rs, const float* t,
+                        int t_rs, const int32_t* nreg, const float* w_dev, float scale, float* da, int d_rs);
+hipError_t att_sup_stats(hipStream_t st, int hops, int Bper, int S, const float* a, int a_rs, const float* t,
+                         int t_rs, const int32_t* nreg, float* rowf, int32_t* rowi, float* outf, int32_t* outi);
 hipError_t scale_hops(hipStream_t st, int H, size_t per_hop, const float* w_dev, float* x);
 // x_i[h][0 .. p_i) *= w[h] for three hop-major tensors in one launch
 hipError_t scale_hops3(hipStream_t st, int H, const float* w_dev, size_t p0, float* x0, size_t p1, float* x1,

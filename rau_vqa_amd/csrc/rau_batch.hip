@@ -224,6 +224,7 @@ void hold(rau_ctx* ctx, int si, const Batch& b) {
   d.have_labels = b.labels != nullptr;
   d.ans_G = 0;   // an answer set belongs to the batch it was given to
   d.regions = false;   // ... and so do region counts
+  d.att_targets = false;   // ... and attention targets
 }
 
 void make_current(rau_ctx* ctx, int si) {
@@ -252,7 +253,7 @@ int set_batch_sync(rau_ctx* ctx, Batch b) {
     HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
   if (int rc = enqueue_batch(ctx, ctx->st, si, b)) return rc;
   HIPC(hipStreamSynchronize(ctx->st));   // the caller's (pageable) buffers are free on return
-  s.upload_pending = s.ans_pending = s.reg_pending = false;
+  s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
   hold(ctx, si, b);
   ctx->fwd_done = false;
   return RAU_OK;
@@ -279,7 +280,7 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   // that call performs the same wait before the caller's own writes -- include/rau.h.)
   if (s.upload_pending) {
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
   }
   // NULL = the caller has filled the slot's pinned staging in place (rau_batch_slot)
   if (b.feats && b.feats != s.feats_h) std::memcpy(s.feats_h, b.feats, nf * feat_elem_bytes(b.feat_type));
@@ -357,6 +358,24 @@ int ensure_regions(rau_ctx* ctx, int si) {
   return RAU_OK;
 }
 
+// first attention targets of a slot: the device block [capacity][Sp] the supervision kernels read (pad columns are
+// never written: they keep dalloc's zeros) and the pinned staging [capacity][S] the copies read
+int ensure_att_targets(rau_ctx* ctx, int si) {
+  BatchSlot& s = ctx->slot[si];
+  if (!s.att_t_d) {
+    if (int rc = dalloc(ctx, &s.att_t_d, (size_t)ctx->cap * ctx->Sp)) return rc;
+    // dalloc clears the block on the chain stream; the slot form copies into it on the copy stream.  Once per slot.
+    HIPC(hipStreamSynchronize(ctx->st));
+  }
+  if (!s.att_t_h) {
+    void* h = nullptr;
+    hipError_t e = hipHostMalloc(&h, (size_t)ctx->cap * ctx->cfg.S * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(attention target staging): %s", hipGetErrorString(e));
+    s.att_t_h = static_cast<float*>(h);
+  }
+  return RAU_OK;
+}
+
 // Every enqueued reader of the bank (the gathers: copy stream and chain stream) has finished.
 int bank_quiesce(rau_ctx* ctx) {
   if (ctx->stc) HIPC(hipStreamSynchronize(ctx->stc));
@@ -429,7 +448,7 @@ int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_
   BatchSlot& s = ctx->slot[slot];
   if (s.upload_pending) {   // the caller is about to overwrite the staging: its last copy must have left
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
   }
   if (feats_host) *feats_host = s.feats_h;
   if (tokens_host) *tokens_host = s.tokens_h;
@@ -516,7 +535,7 @@ int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const
   if (int rc = ensure_answers(ctx, si)) return rc;
   if (s.ans_pending) {   // the staging's previous set has not left it yet (two sets for one upload)
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
   }
   int32_t* ids_h = s.ans_h;
   float* w_h = reinterpret_cast<float*>(s.ans_h + n);
@@ -579,7 +598,7 @@ int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n) {
   if (int rc = ensure_regions(ctx, si)) return rc;
   if (s.reg_pending) {   // the staging's previous counts have not left it yet (two sets for one upload)
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
   }
   std::memcpy(s.nreg_h, n, (size_t)c.B * 4);
   hipStream_t st = slot < 0 ? ctx->st : ctx->stc;
@@ -597,7 +616,7 @@ int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n) {
   if (slot < 0) {
     HIPC(hipStreamSynchronize(st));
     // (the chain stream waited for a pending upload above: every copy behind `uploaded` has left its staging)
-    s.upload_pending = s.ans_pending = s.reg_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
   } else {
     HIPC(hipEventRecord(s.uploaded, st));   // rau_use_batch orders the step behind the counts too
     s.upload_pending = s.reg_pending = true;
@@ -611,6 +630,66 @@ int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n) {
 int rau_batch_regions(rau_ctx* ctx, int* has) {
   NEED(ctx && has, "null argument");
   *has = cur_batch(ctx).held.regions ? 1 : 0;
+  return RAU_OK;
+}
+
+// Attention targets for the batch in a slot: rau_set_regions' slot and ordering rules.  Everything is checked
+// before anything moves.  The forward does not read them, so fwd_done and the merged-hops record stay as they are.
+int rau_set_att_targets(rau_ctx* ctx, int slot, const float* t) {
+  NEED(ctx && t, "null argument");
+  NEED(slot >= -1 && slot <= 1, "rau_set_att_targets: slot %d (-1 = the resident batch, 0 or 1)", slot);
+  const rau_config& c = ctx->cfg;
+  const int si = slot < 0 ? ctx->cur_slot : slot;
+  BatchSlot& s = ctx->slot[si];
+  if (!s.held.have)
+    return fail(RAU_ERR_STATE, "rau_set_att_targets: slot %d holds no batch (upload the batch first)", si);
+  if (slot >= 0 && si == ctx->cur_slot && ctx->fwd_done)
+    return fail(RAU_ERR_STATE, "rau_set_att_targets: slot %d is the current batch of a forward pass whose backward "
+                "has not run", si);
+  const size_t n = (size_t)c.B * c.S;
+  for (size_t i = 0; i < n; ++i)
+    NEED(std::isfinite(t[i]) && t[i] >= 0.f, "rau_set_att_targets: t[%zu,%zu]=%g is negative or not finite", i / c.S,
+         i % c.S, (double)t[i]);
+  if (slot >= 0)
+    if (int rc = ensure_async(ctx)) return rc;
+  if (int rc = ensure_att_targets(ctx, si)) return rc;
+  if (s.att_pending) {   // the staging's previous maps have not left it yet (two sets for one upload)
+    HIPC(hipEventSynchronize(s.uploaded));
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
+  }
+  std::memcpy(s.att_t_h, t, n * 4);
+  hipStream_t st = slot < 0 ? ctx->st : ctx->stc;
+  if (slot < 0) {
+    if (s.upload_pending) HIPC(hipStreamWaitEvent(st, s.uploaded, 0));   // behind an asynchronous upload of the batch
+  } else {
+    // the slot's buffers may still be read by the last step that used them
+    if (si == ctx->cur_slot) {
+      HIPC(hipEventRecord(s.consumed, ctx->st));
+      s.consumed_valid = true;
+    }
+    if (s.consumed_valid) HIPC(hipStreamWaitEvent(st, s.consumed, 0));
+  }
+  if (ctx->Sp == c.S)
+    HIPC(hipMemcpyAsync(s.att_t_d, s.att_t_h, n * 4, hipMemcpyHostToDevice, st));
+  else   // rows of S positions into rows of Sp
+    HIPC(hipMemcpy2DAsync(s.att_t_d, (size_t)ctx->Sp * 4, s.att_t_h, (size_t)c.S * 4, (size_t)c.S * 4, c.B,
+                          hipMemcpyHostToDevice, st));
+  if (slot < 0) {
+    HIPC(hipStreamSynchronize(st));
+    // (the chain stream waited for a pending upload above: every copy behind `uploaded` has left its staging)
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
+  } else {
+    HIPC(hipEventRecord(s.uploaded, st));   // rau_use_batch orders the step behind the targets too
+    s.upload_pending = s.att_pending = true;
+    if (si == ctx->cur_slot) HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
+  }
+  s.held.att_targets = true;
+  return RAU_OK;
+}
+
+int rau_batch_att_targets(rau_ctx* ctx, int* has) {
+  NEED(ctx && has, "null argument");
+  *has = cur_batch(ctx).held.att_targets ? 1 : 0;
   return RAU_OK;
 }
 

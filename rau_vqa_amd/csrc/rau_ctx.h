@@ -88,6 +88,9 @@ struct BatchDesc {
   // region counts (rau_set_regions): sample b attends to the first nreg_d[b] positions only.  Like the answer set
   // they belong to the batch: hold() drops them.
   bool regions = false;
+  // attention targets (rau_set_att_targets): the slot's att_t_d holds a target map per sample.  They belong to the
+  // batch like the two above.
+  bool att_targets = false;
 };
 // One of the two batch slots.  slot[cur_slot] is the resident batch (cur_batch() below): the only record of it.
 // Slot 0's device buffers exist from rau_create on; slot 1's, the pinned staging the loader may fill in place, the
@@ -118,6 +121,11 @@ struct BatchSlot {
   int32_t* nreg_d = nullptr;
   int32_t* nreg_h = nullptr;
   bool reg_pending = false;         // a copy out of nreg_h is behind the last record of `uploaded`
+  // attention targets of the batch: device [capacity][Sp] at the attention's pitch (pad columns stay zero), pinned
+  // host [capacity][S] dense; allocated at the slot's first set (a captured step holds att_t_d's address)
+  float* att_t_d = nullptr;
+  float* att_t_h = nullptr;
+  bool att_pending = false;         // a copy out of att_t_h is behind the last record of `uploaded`
   hipEvent_t uploaded = nullptr;    // recorded on the copy stream behind the slot's H2D copies
   hipEvent_t consumed = nullptr;    // recorded on the chain stream when the ctx switches away from the slot
   // ---- what the device buffers hold
@@ -264,9 +272,15 @@ struct rau_ctx {
   int* perr_h = nullptr;
   bool persist_used = false;
   bool persist_gave_up = false; // persist_check() turned the persistent encoder off: it stays off across resizes
-  float* hopw_h = nullptr;    // pinned staging of the hop weights, 2 slots of 2H: hop_w [H] | select_w [H]
+  float* hopw_h = nullptr;    // pinned staging of the hop weights, 2 slots of 3H: hop_w [H] | select_w [H] | att_w [H]
   int hopw_slot = 0;
-  // step-selection head's gradient (rau_backward_select, select_bwd.hip); hopw_d is [2H]: hop_w | select_w
+  // attention supervision (rau_backward_att, att_sup.hip): the gradient at the attprob output of every hop,
+  // [H][cap][Sp] at the attention's pitch, allocated at the first call with a non-zero att_w
+  float* att_da = nullptr;
+  // ... and its statistics' scratch (rau_att_stats, rau_att_criterion_forward): rows [2][H*cap] | results [2][H]
+  float* att_sf = nullptr;
+  int32_t* att_si = nullptr;
+  // step-selection head's gradient (rau_backward_select, select_bwd.hip); hopw_d is [3H]: hop_w | select_w | att_w
   float *sel_s = nullptr, *sel_add = nullptr;   // [H][cap] s rows, [H][cap][M] s (x) wd; allocated at first use
   bool sel_capture = false;   // rau_graph_step_select is capturing a step with a non-zero select weight: its backward
                               // forms dpre / dhn itself, so the forward leaves them alone
@@ -285,6 +299,7 @@ struct rau_ctx {
   float *m_dX = nullptr, *m_dZ = nullptr;          // [B][D][S], [B][M][S]: feature-map gradient, on request
   float *m_add = nullptr, *m_s = nullptr, *m_zero = nullptr;  // [B][M], [B], zeros [B][max(Q,R)]
   float *m_loss = nullptr;                         // [H] criterion outputs
+  float *m_datt = nullptr;                         // [B][S] dense: rau_att_criterion_backward's d_attprob, on first use
   uint64_t mod_masks_seed = 0;                     // (seed, step) the device masks were drawn for
   uint32_t mod_masks_step = 0;
   bool mod_masks_valid = false;
@@ -540,3 +555,5 @@ __attribute__((visibility("hidden"))) int persist_check(rau_ctx* ctx);
 __attribute__((visibility("hidden"))) int d2h(rau_ctx* ctx, void* host, const void* dev, size_t bytes);
 }
 __attribute__((visibility("hidden"))) int merge_state(rau_ctx* ctx, const char* fn, bool need_labels);  // rau_merge.hip
+// rau_merge.hip: the statistics' scratch exists; ATT rows / results of `hops` hops of a [hops][B] attention block
+__attribute__((visibility("hidden"))) int att_stats_alloc(rau_ctx* ctx);

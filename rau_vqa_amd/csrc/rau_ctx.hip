@@ -511,9 +511,9 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   CK(dalloc(ctx, &ctx->lossrow, HB));
   CK(dalloc(ctx, &ctx->dopred, HB));
   CK(dalloc(ctx, &ctx->losses_d, (size_t)H));
-  CK(dalloc(ctx, &ctx->hopw_d, (size_t)2 * H));   // hop_w | select_w
+  CK(dalloc(ctx, &ctx->hopw_d, (size_t)3 * H));   // hop_w | select_w | att_w
   {  // ctx-owned pinned staging for the hop weights: the async upload never reads caller memory
-    hipError_t eh = hipHostMalloc((void**)&ctx->hopw_h, (size_t)4 * H * sizeof(float), hipHostMallocDefault);
+    hipError_t eh = hipHostMalloc((void**)&ctx->hopw_h, (size_t)6 * H * sizeof(float), hipHostMallocDefault);
     if (eh != hipSuccess) {
       rau_destroy(ctx);
       return fail(RAU_ERR_NOMEM, "hipHostMalloc(hop weights): %s", hipGetErrorString(eh));
@@ -607,6 +607,7 @@ void rau_destroy(rau_ctx* ctx) {
     if (s.bank_idx_h) hipHostFree(s.bank_idx_h);
     if (s.ans_h) hipHostFree(s.ans_h);
     if (s.nreg_h) hipHostFree(s.nreg_h);
+    if (s.att_t_h) hipHostFree(s.att_t_h);
     if (s.uploaded) hipEventDestroy(s.uploaded);
     if (s.consumed) hipEventDestroy(s.consumed);
   }
@@ -828,7 +829,7 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   for (int si = 0; si < 2; ++si) {
     ctx->slot[si].held = BatchDesc{};
     ctx->slot[si].upload_pending = ctx->slot[si].consumed_valid = ctx->slot[si].ans_pending = false;
-    ctx->slot[si].reg_pending = false;
+    ctx->slot[si].reg_pending = ctx->slot[si].att_pending = false;
     ++ctx->slot_serial[si];
   }
   ctx->cur_slot = 0;
@@ -1501,19 +1502,22 @@ int rau_forward(rau_ctx* ctx) {
 // The caller's hop_w may be a temporary (and may be pinned memory, for which an async copy really
 // is asynchronous): stage it in the ctx's own pinned buffer first.  Two slots, alternated, so the
 // copy of step n is never overwritten by the host while step n+1's call prepares its own.
-// select_w (null: none) travels behind hop_w in the same copy.
-static int upload_hop_weights(rau_ctx* ctx, const float* hop_w, const float* select_w = nullptr) {
+// select_w and att_w (null: none) travel behind hop_w in the same copy, each in its own block of H.
+static int upload_hop_weights(rau_ctx* ctx, const float* hop_w, const float* select_w = nullptr,
+                              const float* att_w = nullptr) {
   const int H = ctx->cfg.H;
   const int sl = (ctx->hopw_slot ^= 1);
-  float* stage = ctx->hopw_h + (size_t)sl * 2 * H;
+  float* stage = ctx->hopw_h + (size_t)sl * 3 * H;
   // a host that runs two or more steps ahead of the device must not overwrite a staging slot whose
   // copy has not been read yet: wait for the copy issued from this slot two calls ago
   if (!ctx->hopw_ev[sl]) HIPC(hipEventCreateWithFlags(&ctx->hopw_ev[sl], hipEventDisableTiming));
   else HIPC(hipEventSynchronize(ctx->hopw_ev[sl]));
   std::memcpy(stage, hop_w, (size_t)H * sizeof(float));
   if (select_w) std::memcpy(stage + H, select_w, (size_t)H * sizeof(float));
-  HIPC(hipMemcpyAsync(ctx->hopw_d, stage, (size_t)(select_w ? 2 : 1) * H * sizeof(float), hipMemcpyHostToDevice,
-                      ctx->st));
+  else if (att_w) std::memset(stage + H, 0, (size_t)H * sizeof(float));
+  if (att_w) std::memcpy(stage + 2 * H, att_w, (size_t)H * sizeof(float));
+  HIPC(hipMemcpyAsync(ctx->hopw_d, stage, (size_t)(att_w ? 3 : select_w ? 2 : 1) * H * sizeof(float),
+                      hipMemcpyHostToDevice, ctx->st));
   if (!ctx->capturing) HIPC(hipEventRecord(ctx->hopw_ev[sl], ctx->st));
   return 0;
 }
@@ -1521,9 +1525,14 @@ static int upload_hop_weights(rau_ctx* ctx, const float* hop_w, const float* sel
 // =============================================================== backward
 // select_w: null, or the per-hop weights of the step-selection head's BCE with at least one of them non-zero
 // (rau_backward_select): the one place the two entry points differ is marked `sel` below.
-static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w) {
-  const bool sel = select_w != nullptr;
+// att_w: null, or the per-hop weights of the attention supervision with at least one of them non-zero
+// (rau_backward_att): marked `att` below -- one launch, and HopGrad::da_out of every active hop.
+static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w = nullptr) {
+  const bool sel = select_w != nullptr, att = att_w != nullptr;
   if (!ctx->fwd_done) return fail(RAU_ERR_STATE, "rau_backward: call rau_forward first");
+  if (att && !cur_batch(ctx).held.att_targets)
+    return fail(RAU_ERR_STATE, "rau_backward_att: a non-zero att_w needs a batch with attention targets "
+                "(rau_set_att_targets)");
   if (ctx->fwd_table)
     return fail(RAU_ERR_STATE, "rau_backward: the evaluate-mode forward of a batch with an image table computed "
                 "i_embed once per image, so there is no per-sample I to differentiate; take evaluate-mode "
@@ -1562,7 +1571,7 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
 
   // dpred:mul(w[h])  SS:569 / MS:568-570 / Full:587-589
   if (!ctx->capturing) {  // (rau_graph_step uploads the weights before it launches the graph)
-    if (int rc = upload_hop_weights(ctx, hop_w, select_w)) return rc;
+    if (int rc = upload_hop_weights(ctx, hop_w, select_w, att_w)) return rc;
   }
   if (ctx->dpre_fwd && !sel)   // the forward formed dpre / dhn from the unscaled dl: scale all three
     RUN("scale_hops", 0, (double)H * B * (K + M + R) * 8,
@@ -1575,7 +1584,7 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
   // their backward is identically zero and is skipped -- HA hops are "active".
   int HA = 0;
   for (int h = 0; h < H; ++h)
-    if (hop_w[h] != 0.f || (sel && select_w[h] != 0.f)) HA = h + 1;
+    if (hop_w[h] != 0.f || (sel && select_w[h] != 0.f) || (att && att_w[h] != 0.f)) HA = h + 1;
 
   // ---------------- RAU BPTT, SS:561-578
   // Off the recurrence: dpre = (dl Wc) (.) mask and dhn = dpre Wo for all active hops at once.
@@ -1587,6 +1596,12 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
     RUN("select_signal", 0, (double)HA * B * M * 4,
         select_signal(st, HA * B, B, K, M, ctx->dopred, ctx->argmax_d, t, ctx->hopw_d + H, ctx->do_pred.W, ctx->sel_s,
                       ctx->sel_add));
+  // att: the gradient at the attprob output of all active hops, -(att_w[h] t / (a + eps)) / B, read by the attention
+  // backward of each hop (HopGrad::da_out).  The targets may have come after the forward: it does not read them.
+  if (att)
+    RUN("att_sup_grad", 0, (double)HA * B * S * 12,
+        att_sup_grad(st, HA, B, SL, ctx->a, S, bs.att_t_d, S, bs.held.regions ? bs.nreg_d : nullptr, ctx->hopw_d + 2 * H,
+                     0.f, ctx->att_da, S));
   if (HA > 0 && (!ctx->dpre_fwd || sel)) {
     LinOpts o = lin_opts(ctx, ctx->ws_chain);
     if (sel) { o.addend = ctx->sel_add; o.add_rs = M; }
@@ -1626,6 +1641,7 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
       // before the hop's backward is over (it matters for the first group: the forward / backward seam)
       g.ev_conv_ready = (gsz[h] && (seam_mask() & 2)) ? ctx->evK[h] : nullptr;
       g.dh_prev_dead = h == 0;   // hop 0's prev_h is the constant initial state: nothing reads its gradient
+      g.da_out = att ? ctx->att_da + (size_t)h * BS_ : nullptr;
       if (int rc = hop_backward(ctx, h, ctx->cc + (size_t)h * BR_,
                                 ctx->I + (ctx->I_shared ? 0 : (size_t)h * BM_ * S), g))
         return rc;
@@ -1881,20 +1897,32 @@ int rau_backward(rau_ctx* ctx, const float* hop_w) {
   return backward_impl(ctx, hop_w, nullptr);
 }
 
-// Argument rules of the two *_select entry points: finite weights; *select_w becomes null when it holds no
-// non-zero entry (today's path, launch for launch); otherwise the head's scratch exists on return.
-static int select_args(rau_ctx* ctx, const char* fn, const float* hop_w, const float** select_w) {
+// Argument rules of the *_select and *_att entry points: finite weights; *select_w / *att_w become null when they
+// hold no non-zero entry (the path without them, launch for launch); otherwise their scratch exists on return.
+static int select_args(rau_ctx* ctx, const char* fn, const float* hop_w, const float** select_w,
+                       const float** att_w = nullptr) {
   NEED(ctx && hop_w, "null argument");
   const int H = ctx->cfg.H;
-  bool any = false;
+  bool any = false, any_att = false;
   for (int h = 0; h < H; ++h) {
     NEED(std::isfinite(hop_w[h]), "%s: hop_w[%d] is not finite", fn, h);
     if (*select_w) {
       NEED(std::isfinite((*select_w)[h]), "%s: select_w[%d] is not finite", fn, h);
       any = any || (*select_w)[h] != 0.f;
     }
+    if (att_w && *att_w) {
+      NEED(std::isfinite((*att_w)[h]), "%s: att_w[%d] is not finite", fn, h);
+      any_att = any_att || (*att_w)[h] != 0.f;
+    }
   }
   if (!any) *select_w = nullptr;
+  if (att_w && !any_att) *att_w = nullptr;
+  if (any_att) {
+    if (!cur_batch(ctx).held.att_targets)
+      return fail(RAU_ERR_STATE, "%s: a non-zero att_w needs a batch with attention targets (rau_set_att_targets)", fn);
+    if (!ctx->att_da)   // sized for the capacity, cleared by rau_set_batch_size like every activation
+      if (int rc = dalloc(ctx, &ctx->att_da, (size_t)H * ctx->cap * ctx->Sp)) return rc;
+  }
   if (any && !ctx->sel_add) {   // sized for the capacity, cleared by rau_set_batch_size like every activation
     if (!ctx->sel_s)
       if (int rc = dalloc(ctx, &ctx->sel_s, (size_t)H * ctx->cap)) return rc;
@@ -1908,6 +1936,11 @@ int rau_backward_select(rau_ctx* ctx, const float* hop_w, const float* select_w)
   return backward_impl(ctx, hop_w, select_w);
 }
 
+int rau_backward_att(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w) {
+  if (int rc = select_args(ctx, "rau_backward_att", hop_w, &select_w, &att_w)) return rc;
+  return backward_impl(ctx, hop_w, select_w, att_w);
+}
+
 // One training step's forward + backward (optionally with the gradient zeroing in front) as ONE
 // hipGraph launch.  The three streams, their fork/join events and every kernel argument are
 // captured once per step "shape" -- (mode, longest question, active hops, which mask sites are
@@ -1915,9 +1948,10 @@ int rau_backward_select(rau_ctx* ctx, const float* hop_w, const float* select_w)
 // memory: the batch (rau_set_batch), the Philox key (rau_set_dropout_seed) and the hop weights
 // (uploaded here, in front of the launch).
 // select_w: as backward_impl's.  The weights are read from device memory, so they may change between replays;
-// whether there is a non-zero one decides the launches and joins the key, with the active-hop count.
-static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select_w, int zero_grads_first) {
-  const bool sel = select_w != nullptr;
+// whether there is a non-zero one decides the launches and joins the key, with the active-hop count.  att_w alike.
+static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select_w, int zero_grads_first,
+                           const float* att_w = nullptr) {
+  const bool sel = select_w != nullptr, att = att_w != nullptr;
   const BatchSlot& bs = cur_batch(ctx);
   if (!bs.held.have || !bs.held.have_labels)
     return fail(RAU_ERR_STATE, "rau_graph_step: needs a batch with labels (rau_set_batch)");
@@ -1925,7 +1959,7 @@ static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select
   const int H = ctx->cfg.H;
   int HA = 0;
   for (int h = 0; h < H; ++h)
-    if (hop_w[h] != 0.f || (sel && select_w[h] != 0.f)) HA = h + 1;
+    if (hop_w[h] != 0.f || (sel && select_w[h] != 0.f) || (att && att_w[h] != 0.f)) HA = h + 1;
   uint64_t key = (uint64_t)ctx->mode | ((uint64_t)bs.held.max_len << 2) | ((uint64_t)HA << 12) |
                  ((uint64_t)(zero_grads_first != 0) << 22);
   for (int i = 0; i < 5; ++i) key |= (uint64_t)ctx->mexplicit[i] << (24 + i);
@@ -1939,7 +1973,11 @@ static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select
   key |= (uint64_t)sel << 31;             // ... and by the step-selection head's gradient being asked for
   // ... and the attention kernels hold the slot's region counts or a null pointer (rau_set_regions)
   key |= (uint64_t)bs.held.regions << 62;
-  if (int rc = upload_hop_weights(ctx, hop_w, select_w)) return rc;
+  // ... and a step with a non-zero att_w has one more launch and hands every hop its da_out; the batch's targets
+  // (rau_set_att_targets) are what that launch reads
+  key |= (uint64_t)att << 23;
+  key |= (uint64_t)bs.held.att_targets << 29;
+  if (int rc = upload_hop_weights(ctx, hop_w, select_w, att_w)) return rc;
   ctx->mg.valid = false;
   hipGraphExec_t exec = nullptr;
   for (auto& g : ctx->graphs)
@@ -1951,7 +1989,7 @@ static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select
     ctx->sel_capture = sel;
     int rc = zero_grads_first ? rau_zero_grads(ctx) : 0;
     if (!rc) rc = rau_forward(ctx);
-    if (!rc) rc = backward_impl(ctx, hop_w, select_w);
+    if (!rc) rc = backward_impl(ctx, hop_w, select_w, att_w);
     ctx->capturing = false;
     ctx->sel_capture = false;
     hipError_t e = hipStreamEndCapture(ctx->st, &graph);
@@ -1989,6 +2027,12 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
 int rau_graph_step_select(rau_ctx* ctx, const float* hop_w, const float* select_w, int zero_grads_first) {
   if (int rc = select_args(ctx, "rau_graph_step_select", hop_w, &select_w)) return rc;
   return graph_step_impl(ctx, hop_w, select_w, zero_grads_first);
+}
+
+int rau_graph_step_att(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
+                       int zero_grads_first) {
+  if (int rc = select_args(ctx, "rau_graph_step_att", hop_w, &select_w, &att_w)) return rc;
+  return graph_step_impl(ctx, hop_w, select_w, zero_grads_first, att_w);
 }
 
 int rau_wait_grads(rau_ctx* ctx, int group, void* hip_stream) {

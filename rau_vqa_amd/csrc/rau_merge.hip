@@ -27,6 +27,16 @@ int merge_alloc(rau_ctx* ctx) {
 }
 }  // namespace
 
+// scratch of the attention-supervision statistics (att_sup.hip): rows [2][H*cap] | results [2][H], float and int32
+int att_stats_alloc(rau_ctx* ctx) {
+  const size_t n = 2 * (size_t)ctx->cfg.H * ctx->cap + 2 * (size_t)ctx->cfg.H;
+  if (!ctx->att_sf)
+    if (int rc = dalloc(ctx, &ctx->att_sf, n)) return rc;
+  if (!ctx->att_si)
+    if (int rc = dalloc(ctx, &ctx->att_si, n)) return rc;
+  return RAU_OK;
+}
+
 // may the hop outputs of the last forward be read?  (checked before anything is launched)
 int merge_state(rau_ctx* ctx, const char* fn, bool need_labels) {
   if (!ctx->mg.valid)
@@ -56,6 +66,33 @@ int rau_step_stats(rau_ctx* ctx, float* loss, float* loss_do_pred, int32_t* coun
   if (loss) std::memcpy(loss, out.data(), (size_t)(H + 2) * 4);
   if (loss_do_pred) std::memcpy(loss_do_pred, out.data() + H + 2, (size_t)H * 4);
   if (counts) std::memcpy(counts, out.data() + NL, (size_t)NC * 4);
+  return RAU_OK;
+}
+
+// Attention-supervision statistics of the last forward against its batch's target maps (include/rau.h)
+int rau_att_stats(rau_ctx* ctx, float* loss, float* mass, int32_t* hits, int32_t* n_sup) {
+  NEED(ctx, "null ctx");
+  if (int rc = merge_state(ctx, "rau_att_stats", false)) return rc;
+  const BatchSlot& bs = ctx->slot[ctx->mg.slot];
+  if (!bs.held.att_targets)
+    return fail(RAU_ERR_STATE, "rau_att_stats: the batch of the last forward has no attention targets "
+                "(rau_set_att_targets)");
+  if (int rc = att_stats_alloc(ctx)) return rc;
+  const rau_config& c = ctx->cfg;
+  const int H = c.H, B = c.B, S = ctx->Sp;
+  float* outf = ctx->att_sf + 2 * (size_t)H * ctx->cap;
+  int32_t* outi = ctx->att_si + 2 * (size_t)H * ctx->cap;
+  RUN("att_sup_stats", 0, (double)H * B * S * 8,
+      att_sup_stats(ctx->st, H, B, c.S, ctx->a, S, bs.att_t_d, S, bs.held.regions ? bs.nreg_d : nullptr, ctx->att_sf,
+                    ctx->att_si, outf, outi));
+  std::vector<float> of(2 * (size_t)H);
+  std::vector<int32_t> oi(2 * (size_t)H);
+  HIPC(hipMemcpyAsync(of.data(), outf, of.size() * 4, hipMemcpyDeviceToHost, ctx->st));
+  if (int rc = d2h(ctx, oi.data(), outi, oi.size() * 4)) return rc;
+  if (loss) std::memcpy(loss, of.data(), (size_t)H * 4);
+  if (mass) std::memcpy(mass, of.data() + H, (size_t)H * 4);
+  if (hits) std::memcpy(hits, oi.data(), (size_t)H * 4);
+  if (n_sup) *n_sup = oi[H];
   return RAU_OK;
 }
 

@@ -544,4 +544,39 @@ int rau_criterion_backward_set(rau_ctx* ctx, int h, const float* logits, int32_t
   return criterion(ctx, h, logits, Truth{nullptr, ids_dev, w_dev, nullptr, G}, nullptr, scale, d_logits);
 }
 
+// ------------------------------------------------------------ attention criterion of clone h
+// The step's attention supervision (att_sup.hip) on a dense attprob [B,S] the caller holds -- the attprob output of
+// rau_multimodal_forward -- against dense targets and optional region counts, all in device memory.
+int rau_att_criterion_forward(rau_ctx* ctx, int h, const float* attprob_dev, const float* t_dev,
+                              const int32_t* nreg_dev, float* loss) {
+  NEED(ctx && attprob_dev && t_dev, "null argument");
+  NEED(h >= 0 && h < ctx->cfg.H, "rau_att_criterion_forward: h=%d out of [0,%d)", h, ctx->cfg.H);
+  if (int rc = mod_alloc(ctx)) return rc;
+  if (int rc = att_stats_alloc(ctx)) return rc;
+  const rau_config& c = ctx->cfg;
+  float* outf = ctx->att_sf + 2 * (size_t)c.H * ctx->cap;
+  int32_t* outi = ctx->att_si + 2 * (size_t)c.H * ctx->cap;
+  RUN("att_sup_stats", 0, (double)c.B * c.S * 8,
+      att_sup_stats(ctx->st, 1, c.B, c.S, attprob_dev, c.S, t_dev, c.S, nreg_dev, ctx->att_sf, ctx->att_si, outf, outi));
+  if (!loss) return RAU_OK;
+  HIPC(hipMemcpyAsync(loss, outf, sizeof(float), hipMemcpyDeviceToHost, ctx->st));
+  HIPC(hipStreamSynchronize(ctx->st));
+  return RAU_OK;
+}
+
+int rau_att_criterion_backward(rau_ctx* ctx, int h, const float* attprob_dev, const float* t_dev,
+                               const int32_t* nreg_dev, float scale, float** d_attprob) {
+  NEED(ctx && attprob_dev && t_dev && d_attprob, "null argument");
+  NEED(h >= 0 && h < ctx->cfg.H, "rau_att_criterion_backward: h=%d out of [0,%d)", h, ctx->cfg.H);
+  NEED(std::isfinite(scale), "rau_att_criterion_backward: scale is not finite");
+  if (int rc = mod_alloc(ctx)) return rc;
+  const rau_config& c = ctx->cfg;
+  if (!ctx->m_datt)
+    if (int rc = dalloc(ctx, &ctx->m_datt, (size_t)ctx->cap * ctx->Sp)) return rc;
+  RUN("att_sup_grad", 0, (double)c.B * c.S * 12,
+      att_sup_grad(ctx->st, 1, c.B, c.S, attprob_dev, c.S, t_dev, c.S, nreg_dev, nullptr, scale, ctx->m_datt, c.S));
+  *d_attprob = ctx->m_datt;
+  return RAU_OK;
+}
+
 }  // extern "C"

@@ -60,6 +60,56 @@ def select_signal(x, t, w):
     return bce_grad(x, t, w) * x * (1 - x)
 
 
+def _att_valid(shape, nreg):
+    """[..., n, S] bool: position s of sample b lies below its region count (None: every position)."""
+    S = shape[-1]
+    if nreg is None:
+        return np.ones(shape[-2:], bool)
+    n = np.clip(np.asarray(nreg, np.int64), 1, S)
+    return np.arange(S)[None, :] < n[:, None]
+
+
+def att_ce(a, t, nreg=None):
+    """The attention supervision's loss (rau_backward_att): ATT = (1/n) sum_b sum_{s < nreg[b]} t (-log(a + eps)).
+    a [n, S] or [H, n, S] attention, t [n, S] targets >= 0, nreg [n] region counts or None -> a scalar, or [H].
+    Float32 arithmetic unless a is given as float64."""
+    a = _f32_unless_f64(a)
+    t = np.where(_att_valid(a.shape, nreg), np.asarray(t, a.dtype), a.dtype.type(0))
+    term = np.where(t > 0, t * -np.log(a + a.dtype.type(BCE_EPS)), a.dtype.type(0))
+    return term.sum(axis=(-2, -1), dtype=a.dtype) / a.dtype.type(a.shape[-2])
+
+
+def att_ce_grad(a, t, w, nreg=None):
+    """d(w * att_ce)/da, the contract of rau_backward_att: -((w * t) / (a + eps)) / n in this order, n = a.shape[-2];
+    exactly +0 where t == 0 or s >= nreg[b].  w a scalar, or [H] for [H, n, S] inputs.  Float32 arithmetic (the
+    device's), unless a is given as float64 (for references)."""
+    a = _f32_unless_f64(a)
+    t, w = np.asarray(t, a.dtype), np.asarray(w, a.dtype)
+    if w.ndim == 1:
+        w = w[:, None, None]
+    on = _att_valid(a.shape, nreg) & (t > 0)
+    t = np.where(on, t, a.dtype.type(0))
+    g = -((w * t) / (a + a.dtype.type(BCE_EPS))) / a.dtype.type(a.shape[-2])
+    return np.where(on, g, a.dtype.type(0)).astype(a.dtype)
+
+
+def att_stats(a, t, nreg=None):
+    """What RAU.att_stats reports, of a [H, n, S] against t [n, S] (nreg [n] or None), in float64: ``loss`` [H] =
+    att_ce, ``mass`` [H] = mean over the supervised rows of the attention on the positions with t > 0, ``hits`` [H]
+    = supervised rows whose first-max attention position has t > 0, ``n_sup`` = supervised rows (some t > 0 below
+    the count).  Positions behind a count take no part."""
+    a = np.asarray(a, np.float64)
+    valid = _att_valid(a.shape, nreg)
+    pos = (np.asarray(t) > 0) & valid                        # [n, S]
+    sup = pos.any(axis=1)
+    n_sup = int(sup.sum())
+    loss = att_ce(a, np.asarray(t, np.float64), nreg)
+    mass = (a * pos).sum(axis=2)[:, sup].sum(axis=1) / max(n_sup, 1)
+    arg = np.where(valid, a, -1.0).argmax(axis=2)            # first maximum below the count
+    hit = np.take_along_axis(np.broadcast_to(pos, a.shape), arg[..., None], axis=2)[..., 0] & sup
+    return {"loss": loss, "mass": mass, "hits": hit.sum(axis=1).astype(np.int32), "n_sup": n_sup}
+
+
 def feval_stats(logits, dopred, labels):
     """logits [H, B, K], dopred [H, B], labels [B] (1-based) -> dict with the keys of
     ``RAU.step_stats`` (loss [H+2], loss_do_pred [H], correct [H+2], do_pred_correct [H],

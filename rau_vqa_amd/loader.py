@@ -325,7 +325,7 @@ def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=12
     return v
 
 
-def feed(rau, batch, feat_type=None, answers=None, regions=None):
+def feed(rau, batch, feat_type=None, answers=None, regions=None, att_targets=None):
     """next_batch_feat's tuple -> rau_set_batch (the H2D of SS:434-439); returns qids.
     feat_type: that of the feats (needed for bf16 and fp8, which arrive as uint16 / uint8 bits).  A tuple of
     next_batch_feat(unique=True) goes up as an image table, one of next_batch_rows as a bank batch.
@@ -337,7 +337,10 @@ def feed(rau, batch, feat_type=None, answers=None, regions=None):
     img_regions): attached with rau.set_regions once the batch is up; None changes nothing.
     A batch given as a dict (the keyword arguments of RAU.set_batch: feats, tokens, lens, labels and optionally
     image_of, bank_rows, answers, regions, qids) goes to set_batch as it is: its "regions" key is per sample, or
-    per image beside image_of / bank_rows; the regions= argument, when given, replaces it."""
+    per image beside image_of / bank_rows; the regions= argument, when given, replaces it.
+    att_targets = per-sample attention target maps [B, S] of the batch (human attention maps, boxes rendered onto
+    the positions): attached with rau.set_att_targets once the batch is up; None changes nothing.  For a dict it
+    replaces the dict's own "att_targets" key."""
     if isinstance(batch, dict):
         kw = {k: v for k, v in batch.items() if k != "qids"}
         if feat_type is not None:
@@ -346,6 +349,8 @@ def feed(rau, batch, feat_type=None, answers=None, regions=None):
             kw["answers"] = answers
         if regions is not None:
             kw.pop("regions", None)
+        if att_targets is not None:
+            kw.pop("att_targets", None)
         rau.set_batch(**kw)
         qids = batch.get("qids")
     else:
@@ -354,6 +359,8 @@ def feed(rau, batch, feat_type=None, answers=None, regions=None):
             rau.set_answers(*answers)
     if regions is not None:
         rau.set_regions(regions)
+    if att_targets is not None:
+        rau.set_att_targets(att_targets)
     return qids
 
 

@@ -348,6 +348,43 @@ class RAU:
             raise ValueError(f"region counts must be [{B}], one per sample")
         return regions
 
+    # ---- attention targets: supervise attprob on per-sample maps (rau_set_att_targets)
+    def _att_targets(self, t, B):
+        """t as float32 [B, S], checked on the host: shape, finite, >= 0."""
+        t = np.ascontiguousarray(t, np.float32)
+        if t.ndim < 2 or t.shape[0] != B or t.size != B * self.cfg.S:
+            raise ValueError(f"attention targets must be [{B}, {self.cfg.S}], one map per sample")
+        if not np.isfinite(t).all() or (t < 0).any():
+            raise ValueError("attention targets must be finite and >= 0")
+        return t.reshape(B, self.cfg.S)
+
+    def set_att_targets(self, t, slot=None):
+        """Give the batch in `slot` (None: the resident batch; 0 | 1: after set_batch_async(slot), before
+        use_batch(slot)) per-sample attention targets t [batch, S] >= 0: backward(att_w=) / graph_step(att_w=) then
+        add att_w[h] * ATT_h, ATT_h = mean_b sum_s t (-log(attprob_h + 1e-12)), to the objective (joint.att_ce).  Rows
+        are not normalised here; a row of zeros is an unsupervised sample; with region counts, positions behind a
+        count are ignored.  Always per sample, also for image-table and bank batches.  The forward does not read
+        them: they may be set after it.  They last until the next batch goes into that slot."""
+        t = self._att_targets(t, self._n)
+        L.check(self._lib.rau_set_att_targets(self._h, -1 if slot is None else int(slot), t.ctypes.data))
+
+    def batch_att_targets(self) -> bool:
+        """Whether the resident batch carries attention targets."""
+        v = C.c_int()
+        L.check(self._lib.rau_batch_att_targets(self._h, C.byref(v)))
+        return bool(v.value)
+
+    def att_stats(self):
+        """Of the last forward against its batch's attention targets: ``loss`` [H] (ATT_h), ``mass`` [H] (mean
+        attention on the positions with t > 0, over the supervised rows), ``hits`` [H] (supervised rows whose
+        first-max attention position has t > 0) and ``n_sup`` (supervised rows).  joint.att_stats is the numpy
+        restatement."""
+        H = self.cfg.H
+        loss, mass = np.empty(H, np.float32), np.empty(H, np.float32)
+        hits, n = np.empty(H, np.int32), C.c_int32()
+        L.check(self._lib.rau_att_stats(self._h, loss.ctypes.data, mass.ctypes.data, hits.ctypes.data, C.byref(n)))
+        return {"loss": loss, "mass": mass, "hits": hits, "n_sup": int(n.value)}
+
     def step_scores(self):
         """Metric score of every row's answer of the last forward (feval rule, as step_stats) against its
         batch's answer set: (per_sample [H+2, n], total [H+2]); rows = hops, uni, select."""
@@ -370,7 +407,7 @@ class RAU:
         return oe, mcs, tot
 
     def set_batch(self, feats, tokens, lens, labels=None, feat_type=None, image_of=None, bank_rows=None,
-                  answers=None, regions=None):
+                  answers=None, regions=None, att_targets=None):
         """feat_type "f32" | "f16" | "bf16" | "e4m3" | "e5m2" (default: from the dtype, see feat16.infer;
         bf16 is uint16 bits, fp8 is uint8 codes, both must be named): a 16-bit or fp8 map gives the same
         results, bit for bit, as the f32 map of its widened values.
@@ -381,14 +418,19 @@ class RAU:
         (set_batch_size); every array must agree on n, checked before anything reaches the library.
         answers = (ids, w[, score]): set_answers on the batch once it is up.
         regions: set_regions on the batch once it is up; per sample [B], or with image_of / bank_rows per image
-        [N] (gathered here: regions_of)."""
+        [N] (gathered here: regions_of).
+        att_targets [B, S]: set_att_targets on the batch once it is up; always per sample."""
         if regions is not None:   # checked before anything reaches the library
             regions = self._sample_regions(regions, image_of, int(np.asarray(lens).shape[0]))
+        if att_targets is not None:
+            att_targets = self._att_targets(att_targets, int(np.asarray(lens).shape[0]))
         self._set_batch(feats, tokens, lens, labels, feat_type, image_of, bank_rows)
         if answers is not None:
             self.set_answers(*answers)
         if regions is not None:
             self.set_regions(regions)
+        if att_targets is not None:
+            self.set_att_targets(att_targets)
 
     def _set_batch(self, feats, tokens, lens, labels, feat_type, image_of, bank_rows):
         c = self.cfg
@@ -471,7 +513,7 @@ class RAU:
 
     def set_batch_async(self, slot, feats=None, tokens=None, lens=None, labels=None, has_labels=True,
                         feat_type=None, image_of=None, n_images=None, bank_rows=None, answers=None,
-                        regions=None):
+                        regions=None, att_targets=None):
         """Enqueue the upload of a batch into `slot` on the copy stream and return.  Arrays left None
         are taken from the slot's staging (filled in place through batch_slot).  feat_type: as in
         set_batch; with feats None it names what the staging holds (default "f32").
@@ -481,16 +523,21 @@ class RAU:
         The batch size is lens.shape[0] when lens is given (the context is switched to it first, which
         drops both slots' earlier uploads), else the current batch_size.
         answers = (ids, w[, score]): set_answers(slot=slot) behind the upload, on the copy stream.
-        regions: set_regions(slot=slot) behind the upload; per sample, or per image as in set_batch."""
+        regions: set_regions(slot=slot) behind the upload; per sample, or per image as in set_batch.
+        att_targets [B, S]: set_att_targets(slot=slot) behind the upload."""
         if regions is not None:
             B = self._n if lens is None else int(np.asarray(lens).shape[0])
             regions = self._sample_regions(regions, image_of, B)
+        if att_targets is not None:
+            att_targets = self._att_targets(att_targets, self._n if lens is None else int(np.asarray(lens).shape[0]))
         self._set_batch_async(slot, feats, tokens, lens, labels, has_labels, feat_type, image_of, n_images,
                               bank_rows)
         if answers is not None:
             self.set_answers(*answers, slot=slot)
         if regions is not None:
             self.set_regions(regions, slot=slot)
+        if att_targets is not None:
+            self.set_att_targets(att_targets, slot=slot)
 
     def _set_batch_async(self, slot, feats, tokens, lens, labels, has_labels, feat_type, image_of, n_images,
                          bank_rows):
@@ -560,21 +607,33 @@ class RAU:
             raise ValueError(f"{what} must have H entries")
         return w
 
-    def backward(self, hop_w, select_w=None):
+    def backward(self, hop_w, select_w=None, att_w=None):
         """select_w [H]: per-hop weight of the step-selection head's BCE gradient, the multiplier the
-        reference fixes at 0 (SS:566); None is that zero (rau_backward)."""
+        reference fixes at 0 (SS:566); None is that zero (rau_backward).
+        att_w [H]: per-hop weight of the attention supervision against the batch's targets (set_att_targets), where
+        the reference passes gradattprob = zeros (SS:361, 573); None is those zeros."""
         w = self._hop_array(hop_w, "hop_w")
-        if select_w is None:
+        if att_w is not None:
+            sw = None if select_w is None else self._hop_array(select_w, "select_w")
+            aw = self._hop_array(att_w, "att_w")
+            L.check(self._lib.rau_backward_att(self._h, w.ctypes.data, None if sw is None else sw.ctypes.data,
+                                               aw.ctypes.data))
+        elif select_w is None:
             L.check(self._lib.rau_backward(self._h, w.ctypes.data))
         else:
             sw = self._hop_array(select_w, "select_w")
             L.check(self._lib.rau_backward_select(self._h, w.ctypes.data, sw.ctypes.data))
 
-    def graph_step(self, hop_w, zero_grads=True, select_w=None):
-        """zero_grads + forward + backward as one hipGraph launch (captured on first use); select_w as in
-        backward (read from device memory: it may change between replays)."""
+    def graph_step(self, hop_w, zero_grads=True, select_w=None, att_w=None):
+        """zero_grads + forward + backward as one hipGraph launch (captured on first use); select_w and att_w as
+        in backward (read from device memory: they may change between replays)."""
         w = self._hop_array(hop_w, "hop_w")
-        if select_w is None:
+        if att_w is not None:
+            sw = None if select_w is None else self._hop_array(select_w, "select_w")
+            aw = self._hop_array(att_w, "att_w")
+            L.check(self._lib.rau_graph_step_att(self._h, w.ctypes.data, None if sw is None else sw.ctypes.data,
+                                                 aw.ctypes.data, int(zero_grads)))
+        elif select_w is None:
             L.check(self._lib.rau_graph_step(self._h, w.ctypes.data, int(zero_grads)))
         else:
             sw = self._hop_array(select_w, "select_w")

@@ -120,12 +120,33 @@ class CriterionClone(_Clone):
         return self._view(out, self.rau.batch_size, self.rau.cfg.K)
 
 
-def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None):
+class AttCriterionClone(_Clone):
+    """The attention supervision of hop h on the clone's attprob output: mean_b sum_s t (-log(attprob + 1e-12))
+    against targets t [B,S] (float32 CUDA tensor), regions [B] int32 or None (joint.att_ce / att_ce_grad)."""
+
+    def forward(self, attprob, t, regions=None):
+        loss = C.c_float()
+        L.check(self._lib.rau_att_criterion_forward(self._h, self.i, _p(attprob), _p(t), _p(regions),
+                                                    C.byref(loss)))
+        return loss.value
+
+    def backward(self, attprob, t, regions=None, scale=1.0):
+        """d_attprob [B,S] for MultimodalClone.backward (a ctx-owned slot: valid until the next call)."""
+        out = C.c_void_p()
+        L.check(self._lib.rau_att_criterion_backward(self._h, self.i, _p(attprob), _p(t), _p(regions), float(scale),
+                                                     C.byref(out)))
+        return self._view(out, self.rau.batch_size, self.rau.cfg.S)
+
+
+def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None):
     """The tensor half of the reference's feval, loop for loop (SS:443-596), on the clones.
     select_w [H] (None: the reference's zero, SS:566): hop h's multimodal clone receives
     d_do_pred = joint.bce_grad(do_pred_h, argmax_h == y, select_w[h]), which trains the step-selection head.
 
     regions [B] int32 (None: every position): per-sample region counts, handed to every multimodal clone's forward.
+
+    att_w [H] with att_targets [B,S] float32 (None: the reference's gradattprob zeros, SS:361, 573): hop h's
+    multimodal clone receives d_attprob = AttCriterionClone.backward(attprob_h, att_targets, regions, att_w[h]).
 
     feats [B,D,S] float32, x [T,B] int32, x_len [B] int32, y [B] int32: CUDA tensors.
     Gradients accumulate into the ctx's flat buffers (zero them first).  Returns
@@ -133,16 +154,19 @@ def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None):
     """
     ext = torch.cuda.ExternalStream(rau.stream(), device=feats.device)
     with torch.cuda.stream(ext):   # torch's glue ops join the ctx's own stream order
-        return _feval(rau, feats, x, x_len, y, hop_w, select_w, regions)
+        return _feval(rau, feats, x, x_len, y, hop_w, select_w, regions, att_w, att_targets)
 
 
-def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None):
+def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None):
+    if att_w is not None and att_targets is None and any(float(w) != 0.0 for w in att_w):
+        raise ValueError("feval: a non-zero att_w needs att_targets")
     c = rau.cfg
     dev = feats.device
     emb = [EmbedClone(rau, t) for t in range(c.T)]
     rnn = [DeepLSTMClone(rau, t) for t in range(c.T)]
     mm = [MultimodalClone(rau, h) for h in range(c.H)]
     crit = [CriterionClone(rau, h) for h in range(c.H)]
+    acrit = [AttCriterionClone(rau, h) for h in range(c.H)]
     max_len = int(x_len.max().item())                      # SS:444
     # ---- encoder forward, SS:446-462
     state = [torch.zeros(rau.batch_size, c.Q, device=dev)]            # init_state, SS:358
@@ -156,10 +180,11 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None):
     # ---- hops forward, SS:467-520
     att_c = [torch.zeros(rau.batch_size, c.R, device=dev)]            # SS:362-365
     att_h = [torch.zeros(rau.batch_size, c.R, device=dev)]
-    logits, losses, answers, dopred = [], [], [], []
+    logits, losses, answers, dopred, att = [], [], [], [], []
     for h in range(c.H):
-        lg, dp, _a, cn, hn = mm[h].forward(rnn_out, feats, att_c[h], att_h[h], regions=regions)
+        lg, dp, a, cn, hn = mm[h].forward(rnn_out, feats, att_c[h], att_h[h], regions=regions)
         logits.append(lg)
+        att.append(a)
         dopred.append(dp)
         att_c.append(cn)
         att_h.append(hn)
@@ -174,7 +199,10 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None):
         if select_w is not None and float(select_w[h]) != 0.0:
             gt = (answers[h] == y).to(torch.float32)       # do_pred_gt, SS:490, 497
             d_dp = bce_grad(dopred[h], gt, float(select_w[h])).contiguous()   # SS:565, times the weight
-        dq_h, _dX, d_c, d_h = mm[h].backward(rnn_out, feats, att_c[h], att_h[h], dl, d_dp, None,
+        d_a = None                                         # gradattprob zeros, SS:361, 573
+        if att_w is not None and float(att_w[h]) != 0.0:
+            d_a = acrit[h].backward(att[h], att_targets, regions, float(att_w[h]))
+        dq_h, _dX, d_c, d_h = mm[h].backward(rnn_out, feats, att_c[h], att_h[h], dl, d_dp, d_a,
                                               d_c, d_h)
         d_q += dq_h                                        # ConcatTable backward, SS:579
     # ---- encoder backward, SS:581-596
