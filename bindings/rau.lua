@@ -87,6 +87,12 @@ int rau_batch_att_targets(rau_ctx* ctx, int* has);
 int rau_backward_att(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w);
 int rau_graph_step_att(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w, int zero_grads_first);
 int rau_att_stats(rau_ctx* ctx, float* loss, float* mass, int32_t* hits, int32_t* n_sup);
+int rau_backward_merged(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
+                        const float* merge_w);
+int rau_graph_step_merged(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
+                          const float* merge_w, int zero_grads_first);
+int rau_merge_criterion_backward(rau_ctx* ctx, const float* logits_dev, const float* dopred_dev,
+                                 const int32_t* labels_dev, const float* merge_w, float* d_logits_dev);
 int rau_embed_forward(rau_ctx* ctx, int t, const int32_t* tokens_dev, float** we);
 int rau_embed_backward(rau_ctx* ctx, int t, const int32_t* tokens_dev, const float* d_we);
 int rau_deeplstm_forward(rau_ctx* ctx, int t, const float* x, const float* state,
@@ -454,10 +460,31 @@ function RAU:backward(hop_w, select_w, att_w)
                            hop_array(H, att_w)))
 end
 
+-- rau:backward(hop_w, select_w, att_w, merge_w): merge_w (optional) = {w_uni, w_sel}, the weights of the
+-- cross-entropies of the merged uni and select rows, which the reference only logs (SS:521-557: stepStats' loss[H+1]
+-- and loss[H+2]); nil keeps them out of the objective and is the three-argument form above
+local function merge_array(t)
+  local w = ffi.new('float[2]')
+  w[0], w[1] = t[1], t[2]
+  return w
+end
+local backward_att = RAU.backward
+function RAU:backward(hop_w, select_w, att_w, merge_w)
+  if not merge_w then return backward_att(self, hop_w, select_w, att_w) end
+  local H = self.cfg.H
+  check(C.rau_backward_merged(self.h, hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil,
+                              att_w and hop_array(H, att_w) or nil, merge_array(merge_w)))
+end
+
 -- zeroGradParameters (unless zero_grads == false) + forward + backward as one captured graph launch
-function RAU:graphStep(hop_w, select_w, zero_grads, att_w)
+function RAU:graphStep(hop_w, select_w, zero_grads, att_w, merge_w)
   local H = self.cfg.H
   local z = (zero_grads == false) and 0 or 1
+  if merge_w then
+    check(C.rau_graph_step_merged(self.h, hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil,
+                                  att_w and hop_array(H, att_w) or nil, merge_array(merge_w), z))
+    return
+  end
   if att_w then
     check(C.rau_graph_step_att(self.h, hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil,
                                hop_array(H, att_w), z))

@@ -501,6 +501,46 @@ int rau_backward_att(rau_ctx* ctx, const float* hop_w, const float* select_w /* 
 int rau_graph_step_att(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w, int zero_grads_first);
 int rau_att_stats(rau_ctx* ctx, float* loss /* [H] */, float* mass /* [H] */, int32_t* hits /* [H] */, int32_t* n_sup);
 
+/* ---- training the merged answers: the uni and select cross-entropies in the backward ----------------
+ * The answers handed out at test time are merged over the hops: the "uni" row, the mean of the hop logits (SS:482,
+ * 522), and the "select" row, the logits of the first hop whose do_pred fires (SS:505-507).  feval logs their
+ * cross-entropies (SS:521-557: rau_step_stats' loss[H] and loss[H+1]) and trains neither.  With
+ * merge_w = {w_uni, w_sel} (host, NULL = zeros) the step's objective becomes
+ *   sum_h ( hop_w[h]*CE_h + select_w[h]*BCE_h + att_w[h]*ATT_h ) + w_uni * CE(uni row) + w_sel * CE(select row)
+ * The two rows are those of rau_step_stats, bit for bit: uni = (0 + l_0 + .. + l_{H-1}) / H, select = 0 + l_hsel with
+ * hsel the first hop whose do_pred > 0.5 -- the FEVAL rule: the last hop is not forced, and a row on which no hop
+ * fired has the constant zero row.  So the two terms are the numbers rau_step_stats reports; there is no new getter.
+ * CE is the criterion's own against the forward's labels or answer set (rau_set_answers: the soft-target CE).
+ * With g(row)[b,k] = d CE(row) / d row[b,k] -- expf(row[k] - lse) (W_b invB), then for each matching entry in order
+ * -= w[b,g] invB, the rule and the roundings at rau_set_answers; a label is the set {y} with weight 1; invB = 1/n --
+ * the gradient at the hop logits, added to d_logits[h] behind its scaling by hop_w[h] and in front of everything
+ * that consumes it (the classifier's input, weight and bias gradients; with select_w the head's addend):
+ *   uni     every hop h in [0, H) receives (w_uni / H) * g(uni row)[b,:]
+ *   select  hop h receives w_sel * g(select row)[b,:] on the rows b with hsel(b) == h; a row on which no hop fired
+ *           receives nothing in any hop
+ * each product and each sum rounded once, uni first.  The gate do_pred > 0.5 is a constant: no gradient flows through
+ * it, as none flows through t in rau_backward_select.  A term whose weight is zero is skipped, not added as zeros.
+ * One launch for all hops, no float atomics: repeated calls give the same bits.
+ * rau_backward_merged: merge_w == NULL or both entries zero IS rau_backward_att with the other three arguments: the
+ * same launches, the same bits.  Otherwise every hop is active (HA = H: the uni row reads every hop), and the
+ * forward's labels or answer set must still be there: RAU_ERR_STATE, nothing launched, when that batch had neither or
+ * its slot has been uploaded into since (the rule of rau_step_stats); every state rule of rau_backward applies as
+ * well.  A non-finite weight in any array: RAU_ERR_INVALID.
+ * rau_graph_step_merged is rau_graph_step_att with that backward: merge_w is uploaded next to hop_w and read from
+ * device memory, so it may change between replays; "any merge_w non-zero" joins the cache key.
+ * rau_merge_criterion_backward, for hosts that call the clones one by one: logits_dev [H,n,K] and dopred_dev [H,n]
+ * dense in DEVICE memory (the outputs of the H multimodal clones, stacked), labels_dev [n] int32 or NULL = the
+ * resident batch's labels or answer set (RAU_ERR_STATE when it has neither); the two terms' gradient is ADDED into
+ * d_logits_dev [H,n,K] (16-byte aligned), which holds the caller's scaled per-hop criterion gradients and then goes
+ * hop by hop into rau_multimodal_backward.  Not synchronising. */
+int rau_backward_merged(rau_ctx* ctx, const float* hop_w, const float* select_w /* NULL = zeros */,
+                        const float* att_w /* NULL = zeros */, const float* merge_w /* [2] host: uni, select; NULL = zeros */);
+int rau_graph_step_merged(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
+                          const float* merge_w, int zero_grads_first);
+int rau_merge_criterion_backward(rau_ctx* ctx, const float* logits_dev /* [H,n,K] */, const float* dopred_dev /* [H,n] */,
+                                 const int32_t* labels_dev /* NULL: the resident batch's labels or answer set */,
+                                 const float* merge_w /* [2] host */, float* d_logits_dev /* [H,n,K], added into */);
+
 /* ---- module-level entry points: one call per nn.Module :forward / :backward -----
  * For hosts that keep feval's own loops (SS:443-596) and call the clones one by one.
  * t in [0,T) / h in [0,H) select the clone (the reference's embed_clones[t+1],

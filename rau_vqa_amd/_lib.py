@@ -119,6 +119,11 @@ _SIGS = {
                                             C.POINTER(C.c_float)]),
     "rau_att_criterion_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                              C.POINTER(C.c_void_p)]),
+    # the merged answers' cross-entropies (uni, select) as training terms
+    "rau_backward_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rau_graph_step_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "rau_merge_criterion_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
     # module-level entry points: device pointers in, pointers to ctx-owned slots out
     "rau_embed_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_embed_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -435,6 +435,13 @@ hipError_t att_sup_grad(hipStream_t st, int hops, int Bper, int S, const float* 
                         int t_rs, const int32_t* nreg, const float* w_dev, float scale, float* da, int d_rs);
 hipError_t att_sup_stats(hipStream_t st, int hops, int Bper, int S, const float* a, int a_rs, const float* t,
                          int t_rs, const int32_t* nreg, float* rowf, int32_t* rowi, float* outf, int32_t* outi);
+// The merged answers as training terms (merge_grad.hip, rau_backward_merged / rau_merge_criterion_backward):
+// dl [H][B][K] += the gradient of  w_uni CE(uni row) + w_sel CE(select row)  at the hop logits [H][B][K], the rows
+// hop_merge.h's under the feval rule (do_pred [H][B], the last hop not forced), the CE against t's labels [B] or
+// (G > 0) its answer set.  The two weights are read from mw_dev [2] (device), or with mw_dev null taken from
+// w_uni / w_sel; a zero weight's term is skipped.  One launch, one workgroup per sample; K % 4 == 0, dl 16-byte aligned.
+hipError_t merge_grad(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred, const Truth& t,
+                      const float* mw_dev, float w_uni, float w_sel, float* dl);
 hipError_t scale_hops(hipStream_t st, int H, size_t per_hop, const float* w_dev, float* x);
 // x_i[h][0 .. p_i) *= w[h] for three hop-major tensors in one launch
 hipError_t scale_hops3(hipStream_t st, int H, const float* w_dev, size_t p0, float* x0, size_t p1, float* x1,

@@ -272,7 +272,7 @@ struct rau_ctx {
   int* perr_h = nullptr;
   bool persist_used = false;
   bool persist_gave_up = false; // persist_check() turned the persistent encoder off: it stays off across resizes
-  float* hopw_h = nullptr;    // pinned staging of the hop weights, 2 slots of 3H: hop_w [H] | select_w [H] | att_w [H]
+  float* hopw_h = nullptr;    // pinned staging of the hop weights, 2 slots of 3H + 2: hop_w [H] | select_w [H] | att_w [H] | merge_w [2]
   int hopw_slot = 0;
   // attention supervision (rau_backward_att, att_sup.hip): the gradient at the attprob output of every hop,
   // [H][cap][Sp] at the attention's pitch, allocated at the first call with a non-zero att_w
@@ -280,10 +280,11 @@ struct rau_ctx {
   // ... and its statistics' scratch (rau_att_stats, rau_att_criterion_forward): rows [2][H*cap] | results [2][H]
   float* att_sf = nullptr;
   int32_t* att_si = nullptr;
-  // step-selection head's gradient (rau_backward_select, select_bwd.hip); hopw_d is [3H]: hop_w | select_w | att_w
+  // step-selection head's gradient (rau_backward_select, select_bwd.hip); hopw_d is [3H + 2]: hop_w | select_w | att_w | merge_w
   float *sel_s = nullptr, *sel_add = nullptr;   // [H][cap] s rows, [H][cap][M] s (x) wd; allocated at first use
-  bool sel_capture = false;   // rau_graph_step_select is capturing a step with a non-zero select weight: its backward
-                              // forms dpre / dhn itself, so the forward leaves them alone
+  bool sel_capture = false;   // rau_graph_step_select is capturing a step with a non-zero select weight (or
+                              // rau_graph_step_merged one with a non-zero merge weight): its backward forms
+                              // dpre / dhn itself, so the forward leaves them alone
   // backward temporaries
   // dZ holds dI (gradient at i_embed's OUTPUT); the tanh derivative is applied by its consumers
   float *dpre, *dhn, *dg4, *dcn[2], *dhp[2], *dj, *da_lin, *dz, *du, *dwsp, *dZ,

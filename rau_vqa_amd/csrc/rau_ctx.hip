@@ -511,9 +511,9 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   CK(dalloc(ctx, &ctx->lossrow, HB));
   CK(dalloc(ctx, &ctx->dopred, HB));
   CK(dalloc(ctx, &ctx->losses_d, (size_t)H));
-  CK(dalloc(ctx, &ctx->hopw_d, (size_t)3 * H));   // hop_w | select_w | att_w
+  CK(dalloc(ctx, &ctx->hopw_d, (size_t)3 * H + 2));   // hop_w | select_w | att_w | merge_w
   {  // ctx-owned pinned staging for the hop weights: the async upload never reads caller memory
-    hipError_t eh = hipHostMalloc((void**)&ctx->hopw_h, (size_t)6 * H * sizeof(float), hipHostMallocDefault);
+    hipError_t eh = hipHostMalloc((void**)&ctx->hopw_h, (size_t)2 * (3 * H + 2) * sizeof(float), hipHostMallocDefault);
     if (eh != hipSuccess) {
       rau_destroy(ctx);
       return fail(RAU_ERR_NOMEM, "hipHostMalloc(hop weights): %s", hipGetErrorString(eh));
@@ -1502,22 +1502,25 @@ int rau_forward(rau_ctx* ctx) {
 // The caller's hop_w may be a temporary (and may be pinned memory, for which an async copy really
 // is asynchronous): stage it in the ctx's own pinned buffer first.  Two slots, alternated, so the
 // copy of step n is never overwritten by the host while step n+1's call prepares its own.
-// select_w and att_w (null: none) travel behind hop_w in the same copy, each in its own block of H.
+// select_w and att_w (null: none) travel behind hop_w in the same copy, each in its own block of H; merge_w
+// (null: none) behind them in a block of 2.
 static int upload_hop_weights(rau_ctx* ctx, const float* hop_w, const float* select_w = nullptr,
-                              const float* att_w = nullptr) {
+                              const float* att_w = nullptr, const float* merge_w = nullptr) {
   const int H = ctx->cfg.H;
   const int sl = (ctx->hopw_slot ^= 1);
-  float* stage = ctx->hopw_h + (size_t)sl * 3 * H;
+  float* stage = ctx->hopw_h + (size_t)sl * (3 * H + 2);
   // a host that runs two or more steps ahead of the device must not overwrite a staging slot whose
   // copy has not been read yet: wait for the copy issued from this slot two calls ago
   if (!ctx->hopw_ev[sl]) HIPC(hipEventCreateWithFlags(&ctx->hopw_ev[sl], hipEventDisableTiming));
   else HIPC(hipEventSynchronize(ctx->hopw_ev[sl]));
   std::memcpy(stage, hop_w, (size_t)H * sizeof(float));
   if (select_w) std::memcpy(stage + H, select_w, (size_t)H * sizeof(float));
-  else if (att_w) std::memset(stage + H, 0, (size_t)H * sizeof(float));
+  else if (att_w || merge_w) std::memset(stage + H, 0, (size_t)H * sizeof(float));
   if (att_w) std::memcpy(stage + 2 * H, att_w, (size_t)H * sizeof(float));
-  HIPC(hipMemcpyAsync(ctx->hopw_d, stage, (size_t)(att_w ? 3 : select_w ? 2 : 1) * H * sizeof(float),
-                      hipMemcpyHostToDevice, ctx->st));
+  else if (merge_w) std::memset(stage + 2 * H, 0, (size_t)H * sizeof(float));
+  if (merge_w) std::memcpy(stage + 3 * H, merge_w, 2 * sizeof(float));
+  const size_t count = merge_w ? (size_t)3 * H + 2 : (size_t)(att_w ? 3 : select_w ? 2 : 1) * H;
+  HIPC(hipMemcpyAsync(ctx->hopw_d, stage, count * sizeof(float), hipMemcpyHostToDevice, ctx->st));
   if (!ctx->capturing) HIPC(hipEventRecord(ctx->hopw_ev[sl], ctx->st));
   return 0;
 }
@@ -1527,8 +1530,12 @@ static int upload_hop_weights(rau_ctx* ctx, const float* hop_w, const float* sel
 // (rau_backward_select): the one place the two entry points differ is marked `sel` below.
 // att_w: null, or the per-hop weights of the attention supervision with at least one of them non-zero
 // (rau_backward_att): marked `att` below -- one launch, and HopGrad::da_out of every active hop.
-static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w = nullptr) {
-  const bool sel = select_w != nullptr, att = att_w != nullptr;
+// merge_w: null, or the two weights of the merged rows' cross-entropies with at least one of them non-zero
+// (rau_backward_merged): marked `mrg` below -- one launch behind the hop scaling; like `sel` it is a per-row term,
+// so dpre / dhn are formed here, and every hop is active (the uni row reads them all).
+static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w = nullptr,
+                         const float* merge_w = nullptr) {
+  const bool sel = select_w != nullptr, att = att_w != nullptr, mrg = merge_w != nullptr;
   if (!ctx->fwd_done) return fail(RAU_ERR_STATE, "rau_backward: call rau_forward first");
   if (att && !cur_batch(ctx).held.att_targets)
     return fail(RAU_ERR_STATE, "rau_backward_att: a non-zero att_w needs a batch with attention targets "
@@ -1541,8 +1548,8 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
   if (!bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_backward: batch has no labels");
   // the head's target is read from that forward's labels or answer set: they must still be there (a captured
   // step reads the resident batch, which rau_graph_step_select has checked)
-  if (sel && !ctx->capturing)
-    if (int rc = merge_state(ctx, "rau_backward_select", true)) return rc;
+  if ((sel || mrg) && !ctx->capturing)
+    if (int rc = merge_state(ctx, sel ? "rau_backward_select" : "rau_backward_merged", true)) return rc;
   const Truth t = ctx->capturing ? truth_of(bs) : ctx->mg.truth;
   const rau_config& c = ctx->cfg;
   const int B = c.B, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R,
@@ -1571,13 +1578,18 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
 
   // dpred:mul(w[h])  SS:569 / MS:568-570 / Full:587-589
   if (!ctx->capturing) {  // (rau_graph_step uploads the weights before it launches the graph)
-    if (int rc = upload_hop_weights(ctx, hop_w, select_w, att_w)) return rc;
+    if (int rc = upload_hop_weights(ctx, hop_w, select_w, att_w, merge_w)) return rc;
   }
-  if (ctx->dpre_fwd && !sel)   // the forward formed dpre / dhn from the unscaled dl: scale all three
+  if (ctx->dpre_fwd && !sel && !mrg)   // the forward formed dpre / dhn from the unscaled dl: scale all three
     RUN("scale_hops", 0, (double)H * B * (K + M + R) * 8,
         scale_hops3(st, H, ctx->hopw_d, (size_t)B * K, ctx->dl, (size_t)B * M, ctx->dpre, (size_t)B * R, ctx->dhn));
   else
     RUN("scale_hops", 0, (double)H * B * K * 8, scale_hops(st, H, (size_t)B * K, ctx->hopw_d, ctx->dl));
+  // mrg: w_uni dCE(uni row) + w_sel dCE(select row) join the scaled dl of every hop, in front of all its consumers
+  // (head_dgrad and sel_add below, the classifier's weight gradient in mult_wgrads)
+  if (mrg)
+    RUN("merge_grad", 0, (double)H * B * K * 16,
+        merge_grad(st, H, B, K, ctx->logits, ctx->dopred, t, ctx->hopw_d + 3 * H, 0.f, 0.f, ctx->dl));
 
   // Hops behind the last one with a non-zero loss weight receive no gradient at all (zero
   // criterion gradient, zero recurrent gradient: Full/ResNet late-epoch gating, Full:587-589):
@@ -1585,6 +1597,7 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
   int HA = 0;
   for (int h = 0; h < H; ++h)
     if (hop_w[h] != 0.f || (sel && select_w[h] != 0.f) || (att && att_w[h] != 0.f)) HA = h + 1;
+  if (mrg) HA = H;
 
   // ---------------- RAU BPTT, SS:561-578
   // Off the recurrence: dpre = (dl Wc) (.) mask and dhn = dpre Wo for all active hops at once.
@@ -1602,7 +1615,7 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
     RUN("att_sup_grad", 0, (double)HA * B * S * 12,
         att_sup_grad(st, HA, B, SL, ctx->a, S, bs.att_t_d, S, bs.held.regions ? bs.nreg_d : nullptr, ctx->hopw_d + 2 * H,
                      0.f, ctx->att_da, S));
-  if (HA > 0 && (!ctx->dpre_fwd || sel)) {
+  if (HA > 0 && (!ctx->dpre_fwd || sel || mrg)) {
     LinOpts o = lin_opts(ctx, ctx->ws_chain);
     if (sel) { o.addend = ctx->sel_add; o.add_rs = M; }
     o.emask = m_mf;
@@ -1941,6 +1954,23 @@ int rau_backward_att(rau_ctx* ctx, const float* hop_w, const float* select_w, co
   return backward_impl(ctx, hop_w, select_w, att_w);
 }
 
+// Argument rule of the *_merged entry points: finite weights; *merge_w becomes null when both are zero (the path
+// without them, launch for launch).  Checked in front of select_args, which allocates.
+static int merged_args(const char* fn, const float** merge_w) {
+  if (!*merge_w) return RAU_OK;
+  NEED(std::isfinite((*merge_w)[0]) && std::isfinite((*merge_w)[1]), "%s: merge_w is not finite", fn);
+  if ((*merge_w)[0] == 0.f && (*merge_w)[1] == 0.f) *merge_w = nullptr;
+  return RAU_OK;
+}
+
+int rau_backward_merged(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
+                        const float* merge_w) {
+  NEED(ctx && hop_w, "null argument");
+  if (int rc = merged_args("rau_backward_merged", &merge_w)) return rc;
+  if (int rc = select_args(ctx, "rau_backward_merged", hop_w, &select_w, &att_w)) return rc;
+  return backward_impl(ctx, hop_w, select_w, att_w, merge_w);
+}
+
 // One training step's forward + backward (optionally with the gradient zeroing in front) as ONE
 // hipGraph launch.  The three streams, their fork/join events and every kernel argument are
 // captured once per step "shape" -- (mode, longest question, active hops, which mask sites are
@@ -1949,9 +1979,10 @@ int rau_backward_att(rau_ctx* ctx, const float* hop_w, const float* select_w, co
 // (uploaded here, in front of the launch).
 // select_w: as backward_impl's.  The weights are read from device memory, so they may change between replays;
 // whether there is a non-zero one decides the launches and joins the key, with the active-hop count.  att_w alike.
+// merge_w alike: "any merge_w non-zero" joins the key, and such a step runs all H hops.
 static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select_w, int zero_grads_first,
-                           const float* att_w = nullptr) {
-  const bool sel = select_w != nullptr, att = att_w != nullptr;
+                           const float* att_w = nullptr, const float* merge_w = nullptr) {
+  const bool sel = select_w != nullptr, att = att_w != nullptr, mrg = merge_w != nullptr;
   const BatchSlot& bs = cur_batch(ctx);
   if (!bs.held.have || !bs.held.have_labels)
     return fail(RAU_ERR_STATE, "rau_graph_step: needs a batch with labels (rau_set_batch)");
@@ -1960,6 +1991,7 @@ static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select
   int HA = 0;
   for (int h = 0; h < H; ++h)
     if (hop_w[h] != 0.f || (sel && select_w[h] != 0.f) || (att && att_w[h] != 0.f)) HA = h + 1;
+  if (mrg) HA = H;
   uint64_t key = (uint64_t)ctx->mode | ((uint64_t)bs.held.max_len << 2) | ((uint64_t)HA << 12) |
                  ((uint64_t)(zero_grads_first != 0) << 22);
   for (int i = 0; i < 5; ++i) key |= (uint64_t)ctx->mexplicit[i] << (24 + i);
@@ -1977,7 +2009,8 @@ static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select
   // (rau_set_att_targets) are what that launch reads
   key |= (uint64_t)att << 23;
   key |= (uint64_t)bs.held.att_targets << 29;
-  if (int rc = upload_hop_weights(ctx, hop_w, select_w, att_w)) return rc;
+  key |= (uint64_t)mrg << 63;             // ... and a step with a non-zero merge_w has the merge_grad launch
+  if (int rc = upload_hop_weights(ctx, hop_w, select_w, att_w, merge_w)) return rc;
   ctx->mg.valid = false;
   hipGraphExec_t exec = nullptr;
   for (auto& g : ctx->graphs)
@@ -1986,10 +2019,10 @@ static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select
     hipGraph_t graph = nullptr;
     HIPC(hipStreamBeginCapture(ctx->st, hipStreamCaptureModeRelaxed));
     ctx->capturing = true;
-    ctx->sel_capture = sel;
+    ctx->sel_capture = sel || mrg;
     int rc = zero_grads_first ? rau_zero_grads(ctx) : 0;
     if (!rc) rc = rau_forward(ctx);
-    if (!rc) rc = backward_impl(ctx, hop_w, select_w, att_w);
+    if (!rc) rc = backward_impl(ctx, hop_w, select_w, att_w, merge_w);
     ctx->capturing = false;
     ctx->sel_capture = false;
     hipError_t e = hipStreamEndCapture(ctx->st, &graph);
@@ -2033,6 +2066,14 @@ int rau_graph_step_att(rau_ctx* ctx, const float* hop_w, const float* select_w, 
                        int zero_grads_first) {
   if (int rc = select_args(ctx, "rau_graph_step_att", hop_w, &select_w, &att_w)) return rc;
   return graph_step_impl(ctx, hop_w, select_w, zero_grads_first, att_w);
+}
+
+int rau_graph_step_merged(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
+                          const float* merge_w, int zero_grads_first) {
+  NEED(ctx && hop_w, "null argument");
+  if (int rc = merged_args("rau_graph_step_merged", &merge_w)) return rc;
+  if (int rc = select_args(ctx, "rau_graph_step_merged", hop_w, &select_w, &att_w)) return rc;
+  return graph_step_impl(ctx, hop_w, select_w, zero_grads_first, att_w, merge_w);
 }
 
 int rau_wait_grads(rau_ctx* ctx, int group, void* hip_stream) {

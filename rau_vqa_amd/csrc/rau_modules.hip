@@ -544,6 +544,25 @@ int rau_criterion_backward_set(rau_ctx* ctx, int h, const float* logits, int32_t
   return criterion(ctx, h, logits, Truth{nullptr, ids_dev, w_dev, nullptr, G}, nullptr, scale, d_logits);
 }
 
+// ------------------------------------------------------------ the merged rows' criteria
+// The step's merge_grad launch (merge_grad.hip) on hop logits and do_pred the caller holds: feval's uni and select
+// rows are built from them under the feval rule and the gradient of  merge_w[0] CE(uni) + merge_w[1] CE(select)  is
+// ADDED into d_logits_dev [H,n,K] -- the caller's per-hop criterion gradients, already scaled.  It touches no
+// ctx-owned slot, so it may run between the hop loops of a module-level feval.
+int rau_merge_criterion_backward(rau_ctx* ctx, const float* logits_dev, const float* dopred_dev,
+                                 const int32_t* labels_dev, const float* merge_w, float* d_logits_dev) {
+  NEED(ctx && logits_dev && dopred_dev && merge_w && d_logits_dev, "null argument");
+  NEED(std::isfinite(merge_w[0]) && std::isfinite(merge_w[1]), "rau_merge_criterion_backward: merge_w is not finite");
+  NEED(((uintptr_t)d_logits_dev & 15) == 0, "rau_merge_criterion_backward: d_logits_dev is not 16-byte aligned");
+  const Truth t = labels_dev ? Truth{labels_dev} : truth_of(cur_batch(ctx));
+  if (!t.present()) return fail(RAU_ERR_STATE, "rau_merge_criterion_backward: no labels");
+  if (merge_w[0] == 0.f && merge_w[1] == 0.f) return RAU_OK;   // nothing to add
+  const rau_config& c = ctx->cfg;
+  RUN("merge_grad", 0, (double)c.H * c.B * c.K * 16,
+      merge_grad(ctx->st, c.H, c.B, c.K, logits_dev, dopred_dev, t, nullptr, merge_w[0], merge_w[1], d_logits_dev));
+  return RAU_OK;
+}
+
 // ------------------------------------------------------------ attention criterion of clone h
 // The step's attention supervision (att_sup.hip) on a dense attprob [B,S] the caller holds -- the attprob output of
 // rau_multimodal_forward -- against dense targets and optional region counts, all in device memory.

@@ -156,3 +156,82 @@ def feval_stats(logits, dopred, labels):
             "correct": np.array(correct, np.int32), "do_pred_correct": np.array(do_pred_correct, np.int32),
             "did_correct": int(did_correct.sum()), "fired": np.array(fired, np.int32),
             "selected": np.array(selected, np.int32), "uni_ans": uni_ans, "select_ans": select_ans}
+
+
+def merged_rows(logits, dopred):
+    """feval's two merged rows of logits [H, B, K] under do_pred [H, B], in the dtype of logits (float32 unless
+    float64 is given): (uni [B, K], select [B, K], hsel [B]).  uni: sequential adds from 0, then a division by H
+    (SS:482, 522); select: 0 + the logits of the first hop whose do_pred > 0.5 (SS:501-507, feval_stats' lines: the
+    clamp(do - did) recurrence picks that hop, the last hop is NOT forced), all zeros on a row where none fired;
+    hsel: that hop, -1 where none fired."""
+    logits = _f32_unless_f64(logits)
+    dt = logits.dtype
+    H, B, K = logits.shape
+    uni = np.zeros((B, K), dt)
+    select = np.zeros((B, K), dt)
+    did = np.zeros(B, bool)
+    hsel = np.full(B, -1, np.int64)
+    for h in range(H):
+        uni += logits[h]                                     # SS:482
+        do = np.asarray(dopred[h]) > 0.5                     # SS:501
+        cur = do & ~did                                      # SS:505
+        select += logits[h] * cur[:, None].astype(dt)        # SS:506-507
+        hsel[cur] = h
+        did |= do                                            # SS:515
+    return uni / dt.type(H), select, hsel
+
+
+def _ce_grad_rows(row, labels, answers):
+    """d CE(row) / d row for rows [B, K] against labels [B] (1-based) or answers = (ids [B, G], w [B, G]): the
+    criterion's gradient rule, softmax * (W_b / B) and then -= w_g / B at every non-empty entry in g order (a label
+    is the set {y} with weight 1), in row's dtype."""
+    dt = row.dtype
+    B = row.shape[0]
+    if answers is None:
+        ids = np.asarray(labels, np.int64).reshape(B, 1)
+        w = np.ones((B, 1), dt)
+    else:
+        ids = np.asarray(answers[0], np.int64)
+        w = np.where(ids > 0, np.asarray(answers[1], dt), dt.type(0)).astype(dt)
+    invB = dt.type(1) / dt.type(B)
+    mx = row.max(axis=1, keepdims=True)
+    lse = mx + np.log(np.exp(row - mx).sum(axis=1, keepdims=True, dtype=dt))
+    W = np.zeros(B, dt)
+    for g in range(ids.shape[1]):
+        W = W + w[:, g]
+    out = (np.exp(row - lse) * (W * invB)[:, None]).astype(dt)
+    ar = np.arange(B)
+    for g in range(ids.shape[1]):
+        live = ids[:, g] > 0
+        out[ar[live], ids[live, g] - 1] -= (w[live, g] * invB).astype(dt)
+    return out
+
+
+def merged_ce_grad(logits, dopred, labels=None, answers=None, merge_w=(0.0, 0.0)):
+    """The gradient of  merge_w[0] * CE(uni row, truth) + merge_w[1] * CE(select row, truth)  at the hop logits: the
+    contract of rau_backward_merged / rau_merge_criterion_backward, as the [H, B, K] array they ADD to d_logits.
+
+    logits [H, B, K], dopred [H, B]; truth is labels [B] (1-based) or answers = (ids [B, G], w [B, G]) (ids 1-based,
+    0 = empty entry; the soft-target CE of predict.soft_ce).  The rows are merged_rows' (the feval rule: the numbers
+    RAU.step_stats reports as loss[H] and loss[H+1]); CE is sizeAverage over the B rows.  With g(row) the criterion's
+    gradient at a row (softmax - target, times 1/B; for a set softmax * W_b / B - sum_g onehot(y_g) w_g / B):
+      uni     every hop h receives (merge_w[0] / H) * g(uni)[b, :]
+      select  hop hsel(b) receives merge_w[1] * g(select)[b, :]; rows on which no hop fired receive exactly 0 in
+              every hop (their select row is the constant zero row)
+    and no gradient flows through the gate do_pred > 0.5.  Float32 arithmetic (the device's order: each product and
+    sum rounded once, uni first), or float64 when logits is given as float64 (for references)."""
+    logits = _f32_unless_f64(logits)
+    dt = logits.dtype
+    H, B, K = logits.shape
+    if (labels is None) == (answers is None):
+        raise ValueError("merged_ce_grad: give labels or answers")
+    w_uni, w_sel = dt.type(merge_w[0]), dt.type(merge_w[1])
+    uni, select, hsel = merged_rows(logits, dopred)
+    out = np.zeros((H, B, K), dt)
+    if w_uni != 0:
+        out += ((w_uni / dt.type(H)) * _ce_grad_rows(uni, labels, answers))[None]
+    if w_sel != 0:
+        g_s = w_sel * _ce_grad_rows(select, labels, answers)
+        fired = np.nonzero(hsel >= 0)[0]
+        out[hsel[fired], fired] += g_s[fired]
+    return out

@@ -607,13 +607,27 @@ class RAU:
             raise ValueError(f"{what} must have H entries")
         return w
 
-    def backward(self, hop_w, select_w=None, att_w=None):
+    def _merge_array(self, w):
+        w = np.ascontiguousarray(w, np.float32)
+        if w.shape != (2,):
+            raise ValueError("merge_w must have 2 entries: uni, select")
+        return w
+
+    def backward(self, hop_w, select_w=None, att_w=None, merge_w=None):
         """select_w [H]: per-hop weight of the step-selection head's BCE gradient, the multiplier the
         reference fixes at 0 (SS:566); None is that zero (rau_backward).
         att_w [H]: per-hop weight of the attention supervision against the batch's targets (set_att_targets), where
-        the reference passes gradattprob = zeros (SS:361, 573); None is those zeros."""
+        the reference passes gradattprob = zeros (SS:361, 573); None is those zeros.
+        merge_w [2]: weights of the cross-entropies of the merged "uni" and "select" rows (step_stats' loss[H] and
+        loss[H+1], which the reference only logs); None is no such term."""
         w = self._hop_array(hop_w, "hop_w")
-        if att_w is not None:
+        if merge_w is not None:
+            sw = None if select_w is None else self._hop_array(select_w, "select_w")
+            aw = None if att_w is None else self._hop_array(att_w, "att_w")
+            mw = self._merge_array(merge_w)
+            L.check(self._lib.rau_backward_merged(self._h, w.ctypes.data, None if sw is None else sw.ctypes.data,
+                                                  None if aw is None else aw.ctypes.data, mw.ctypes.data))
+        elif att_w is not None:
             sw = None if select_w is None else self._hop_array(select_w, "select_w")
             aw = self._hop_array(att_w, "att_w")
             L.check(self._lib.rau_backward_att(self._h, w.ctypes.data, None if sw is None else sw.ctypes.data,
@@ -624,11 +638,18 @@ class RAU:
             sw = self._hop_array(select_w, "select_w")
             L.check(self._lib.rau_backward_select(self._h, w.ctypes.data, sw.ctypes.data))
 
-    def graph_step(self, hop_w, zero_grads=True, select_w=None, att_w=None):
-        """zero_grads + forward + backward as one hipGraph launch (captured on first use); select_w and att_w as
-        in backward (read from device memory: they may change between replays)."""
+    def graph_step(self, hop_w, zero_grads=True, select_w=None, att_w=None, merge_w=None):
+        """zero_grads + forward + backward as one hipGraph launch (captured on first use); select_w, att_w and
+        merge_w as in backward (read from device memory: they may change between replays)."""
         w = self._hop_array(hop_w, "hop_w")
-        if att_w is not None:
+        if merge_w is not None:
+            sw = None if select_w is None else self._hop_array(select_w, "select_w")
+            aw = None if att_w is None else self._hop_array(att_w, "att_w")
+            mw = self._merge_array(merge_w)
+            L.check(self._lib.rau_graph_step_merged(self._h, w.ctypes.data, None if sw is None else sw.ctypes.data,
+                                                    None if aw is None else aw.ctypes.data, mw.ctypes.data,
+                                                    int(zero_grads)))
+        elif att_w is not None:
             sw = None if select_w is None else self._hop_array(select_w, "select_w")
             aw = self._hop_array(att_w, "att_w")
             L.check(self._lib.rau_graph_step_att(self._h, w.ctypes.data, None if sw is None else sw.ctypes.data,

@@ -138,7 +138,20 @@ class AttCriterionClone(_Clone):
         return self._view(out, self.rau.batch_size, self.rau.cfg.S)
 
 
-def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None):
+def merge_criterion_backward(rau, logits, dopred, y, merge_w, d_logits):
+    """d_logits [H,B,K] += the gradient of merge_w[0] CE(uni row) + merge_w[1] CE(select row) at the hop logits
+    [H,B,K] under do_pred [H,B] (joint.merged_ce_grad); y [B] int32 labels, or None: the resident batch's labels or
+    answer set.  Contiguous float32 CUDA tensors; d_logits is updated in place and returned."""
+    c = rau.cfg
+    if tuple(logits.shape) != (c.H, rau.batch_size, c.K) or tuple(d_logits.shape) != tuple(logits.shape) \
+            or tuple(dopred.shape) != (c.H, rau.batch_size):
+        raise ValueError("merge_criterion_backward: logits / d_logits [H,B,K] and dopred [H,B] of the current batch size")
+    mw = (C.c_float * 2)(float(merge_w[0]), float(merge_w[1]))
+    L.check(rau._lib.rau_merge_criterion_backward(rau._h, _p(logits), _p(dopred), _p(y), mw, _p(d_logits)))
+    return d_logits
+
+
+def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None, merge_w=None):
     """The tensor half of the reference's feval, loop for loop (SS:443-596), on the clones.
     select_w [H] (None: the reference's zero, SS:566): hop h's multimodal clone receives
     d_do_pred = joint.bce_grad(do_pred_h, argmax_h == y, select_w[h]), which trains the step-selection head.
@@ -148,16 +161,20 @@ def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=Non
     att_w [H] with att_targets [B,S] float32 (None: the reference's gradattprob zeros, SS:361, 573): hop h's
     multimodal clone receives d_attprob = AttCriterionClone.backward(attprob_h, att_targets, regions, att_w[h]).
 
+    merge_w [2] (None: the reference, which only logs them, SS:521-557): weights of the cross-entropies of the merged
+    uni and select rows.  Their gradient at the hop logits is computed ONCE, behind the forward loop, by
+    merge_criterion_backward on the stacked logits / do_pred, and added to each hop's d_logits (joint.merged_ce_grad).
+
     feats [B,D,S] float32, x [T,B] int32, x_len [B] int32, y [B] int32: CUDA tensors.
     Gradients accumulate into the ctx's flat buffers (zero them first).  Returns
     (losses[H], argmax[H,B] as torch tensors of 1-based ids).
     """
     ext = torch.cuda.ExternalStream(rau.stream(), device=feats.device)
     with torch.cuda.stream(ext):   # torch's glue ops join the ctx's own stream order
-        return _feval(rau, feats, x, x_len, y, hop_w, select_w, regions, att_w, att_targets)
+        return _feval(rau, feats, x, x_len, y, hop_w, select_w, regions, att_w, att_targets, merge_w)
 
 
-def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None):
+def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None, merge_w=None):
     if att_w is not None and att_targets is None and any(float(w) != 0.0 for w in att_w):
         raise ValueError("feval: a non-zero att_w needs att_targets")
     c = rau.cfg
@@ -190,11 +207,16 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=No
         att_h.append(hn)
         losses.append(crit[h].forward(lg, y))              # SS:518
         answers.append(torch.argmax(lg, dim=1) + 1)        # SS:488 (ties: see rau_get_argmax)
+    # ---- the merged rows' criteria: every hop's scaled d_logits, plus the uni and select terms in one launch
+    d_merged = None
+    if merge_w is not None and any(float(w) != 0.0 for w in merge_w):
+        d_merged = torch.stack([crit[h].backward(logits[h], y, float(hop_w[h])) for h in range(c.H)])
+        merge_criterion_backward(rau, torch.stack(logits), torch.stack(dopred), y, merge_w, d_merged)
     # ---- hops backward, SS:561-579
     d_c = d_h = None                                       # zeros, SS:561-562
     d_q = torch.zeros(rau.batch_size, c.Q, device=dev)
     for h in reversed(range(c.H)):
-        dl = crit[h].backward(logits[h], y, float(hop_w[h]))   # SS:565-569
+        dl = crit[h].backward(logits[h], y, float(hop_w[h])) if d_merged is None else d_merged[h]   # SS:565-569
         d_dp = None                                        # d_do_pred:mul(0), SS:566
         if select_w is not None and float(select_w[h]) != 0.0:
             gt = (answers[h] == y).to(torch.float32)       # do_pred_gt, SS:490, 497
