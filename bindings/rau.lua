@@ -434,63 +434,40 @@ end
 -- backward half (SS:561-596); hop_w = per-hop criterion-gradient scale (SS:569 / Full:587-589)
 -- select_w (optional) = per-hop weight of the step-selection head's BCE gradient: the multiplier the reference
 -- fixes at 0 in d_do_pred:mul(0), SS:566; nil keeps that zero
+-- att_w (optional) = per-hop weight of the attention supervision against setAttTargets' maps, where the reference
+-- passes gradattprob = zeros (SS:361, 573); nil keeps those zeros
+-- merge_w (optional) = {w_uni, w_sel}, the weights of the cross-entropies of the merged uni and select rows, which
+-- the reference only logs (SS:521-557: stepStats' loss[H+1] and loss[H+2]); nil keeps them out of the objective
 local function hop_array(H, t)
   local w = ffi.new('float[?]', H)
   for i = 1, H do w[i - 1] = t[i] end
   return w
 end
-function RAU:backward(hop_w, select_w)
-  local H = self.cfg.H
-  local w = hop_array(H, hop_w)
-  if select_w then
-    check(C.rau_backward_select(self.h, w, hop_array(H, select_w)))
-  else
-    check(C.rau_backward(self.h, w))
-  end
-end
-
--- rau:backward(hop_w, select_w, att_w): att_w (optional) = per-hop weight of the attention supervision against
--- setAttTargets' maps, where the reference passes gradattprob = zeros (SS:361, 573); nil keeps those zeros and
--- is the two-argument form above
-local backward_select = RAU.backward
-function RAU:backward(hop_w, select_w, att_w)
-  if not att_w then return backward_select(self, hop_w, select_w) end
-  local H = self.cfg.H
-  check(C.rau_backward_att(self.h, hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil,
-                           hop_array(H, att_w)))
-end
-
--- rau:backward(hop_w, select_w, att_w, merge_w): merge_w (optional) = {w_uni, w_sel}, the weights of the
--- cross-entropies of the merged uni and select rows, which the reference only logs (SS:521-557: stepStats' loss[H+1]
--- and loss[H+2]); nil keeps them out of the objective and is the three-argument form above
 local function merge_array(t)
   local w = ffi.new('float[2]')
   w[0], w[1] = t[1], t[2]
   return w
 end
-local backward_att = RAU.backward
+-- the weight arguments of the entry points: a term left out is nil (NULL), and the last one given picks the entry point
+local function loss_args(H, hop_w, select_w, att_w, merge_w)
+  return hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil, att_w and hop_array(H, att_w) or nil,
+         merge_w and merge_array(merge_w) or nil
+end
 function RAU:backward(hop_w, select_w, att_w, merge_w)
-  if not merge_w then return backward_att(self, hop_w, select_w, att_w) end
-  local H = self.cfg.H
-  check(C.rau_backward_merged(self.h, hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil,
-                              att_w and hop_array(H, att_w) or nil, merge_array(merge_w)))
+  local w, sw, aw, mw = loss_args(self.cfg.H, hop_w, select_w, att_w, merge_w)
+  if mw then check(C.rau_backward_merged(self.h, w, sw, aw, mw))
+  elseif aw then check(C.rau_backward_att(self.h, w, sw, aw))
+  elseif sw then check(C.rau_backward_select(self.h, w, sw))
+  else check(C.rau_backward(self.h, w)) end
 end
 
 -- zeroGradParameters (unless zero_grads == false) + forward + backward as one captured graph launch
 function RAU:graphStep(hop_w, select_w, zero_grads, att_w, merge_w)
-  local H = self.cfg.H
+  local w, sw, aw, mw = loss_args(self.cfg.H, hop_w, select_w, att_w, merge_w)
   local z = (zero_grads == false) and 0 or 1
-  if merge_w then
-    check(C.rau_graph_step_merged(self.h, hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil,
-                                  att_w and hop_array(H, att_w) or nil, merge_array(merge_w), z))
-    return
-  end
-  if att_w then
-    check(C.rau_graph_step_att(self.h, hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil,
-                               hop_array(H, att_w), z))
-    return
-  end
-  check(C.rau_graph_step_select(self.h, hop_array(H, hop_w), select_w and hop_array(H, select_w) or nil, z))
+  if mw then check(C.rau_graph_step_merged(self.h, w, sw, aw, mw, z))
+  elseif aw then check(C.rau_graph_step_att(self.h, w, sw, aw, z))
+  else check(C.rau_graph_step_select(self.h, w, sw, z)) end
 end
 
 function RAU:zeroGradParameters() check(C.rau_zero_grads(self.h)) end

@@ -745,7 +745,7 @@ int rau_bank_destroy(rau_ctx* ctx) {
   if (int rc = bank_quiesce(ctx)) return rc;
   // captured steps of bank batches hold the bank's address
   for (auto it = ctx->graphs.begin(); it != ctx->graphs.end();)
-    if ((it->first >> 36) & 1) { hipGraphExecDestroy(it->second); it = ctx->graphs.erase(it); } else ++it;
+    if (it->key.bank) { hipGraphExecDestroy(it->exec); it = ctx->graphs.erase(it); } else ++it;
   for (BatchSlot& s : ctx->slot) {   // a batch drawn from the bank is gone with it
     if (!s.held.bank) continue;
     const int ft = s.held.feat_type;   // (its maps are not: enqueue_batch's pad-column rule reads their type)

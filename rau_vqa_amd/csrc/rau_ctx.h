@@ -12,6 +12,7 @@
 #include <cstring>
 #include <numeric>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/rau.h"
@@ -175,6 +176,61 @@ struct MergeState {
   void invalidate() { valid = merged = false; truth = Truth{}; }
 };
 
+// The hop-weight staging (two pinned slots in rau_ctx::hopw_h, one device copy in hopw_d), defined here only:
+// hop_w [H] | select_w [H] | att_w [H] | merge_w [2].  The members are offsets in floats.
+struct HopwLayout {
+  size_t select_w, att_w, merge_w, size;
+  explicit HopwLayout(int H) : select_w(H), att_w((size_t)2 * H), merge_w((size_t)3 * H), size((size_t)3 * H + 2) {}
+};
+// The loss terms of one step-level backward, normalised once (step_loss in rau_ctx.hip): what backward_impl,
+// graph_step_impl and upload_hop_weights read in place of the entry points' pointer arguments.
+struct StepLoss {
+  const float* hop_w = nullptr;      // [H] per-hop weights of the answer criterion
+  // null when the term is absent or all-zero: the path without it, launch for launch
+  const float* select_w = nullptr;   // [H] step-selection head's BCE (select_bwd.hip)
+  const float* att_w = nullptr;      // [H] attention supervision (att_sup.hip)
+  const float* merge_w = nullptr;    // [2] the merged rows' cross-entropies: uni, select (merge_grad.hip)
+  // Hops behind the last one with a non-zero loss weight receive no gradient at all (zero criterion gradient,
+  // zero recurrent gradient: Full/ResNet late-epoch gating, Full:587-589): their backward is identically zero
+  // and is skipped -- `active` hops are "active".  H with a merge_w: the uni row reads every hop.
+  int active = 0;
+  // select_w and merge_w are per-row terms, which cannot be folded into what the forward formed (one scale per
+  // hop): such a backward forms dpre / dhn itself from the scaled dl
+  bool forms_dpre() const { return select_w || merge_w; }
+};
+// What shapes a captured step (rau_graph_step): one executable graph per distinct value.
+struct StepKey {
+  int mode = 0;                 // rau_mode
+  int max_len = 0;              // the longest question: the encoder's token count
+  int active = 0;               // StepLoss::active: the hops the backward runs
+  bool zero = false;            // the gradient zeroing is in front of the step
+  bool mexplicit[5] = {};       // which mask sites are caller-supplied
+  int slot = 0;                 // the captured kernels hold the batch slot's device pointers
+  int feat_type = 0;            // ... and read the batch in its element type
+  bool table = false;           // ... through the gather of an image table (any table, any N)
+  bool bank = false;            // ... of a bank batch: out of the bank (rau_bank_destroy drops these)
+  // ... against an answer set of G entries (0 = labels): another head kernel (the one reader besides truth_of())
+  int ans_G = 0;
+  int B = 0;                    // every launch is shaped by the batch size (rau_set_batch_size)
+  bool sel = false;             // ... and by the step-selection head's gradient being asked for
+  // ... and the attention kernels hold the slot's region counts or a null pointer (rau_set_regions)
+  bool regions = false;
+  // ... and a step with a non-zero att_w has one more launch and hands every hop its da_out; the batch's targets
+  // (rau_set_att_targets) are what that launch reads
+  bool att = false;
+  bool att_targets = false;
+  bool mrg = false;             // ... and a step with a non-zero merge_w has the merge_grad launch
+  auto tied() const {
+    return std::tie(mode, max_len, active, zero, mexplicit[0], mexplicit[1], mexplicit[2], mexplicit[3], mexplicit[4],
+                    slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg);
+  }
+  bool operator==(const StepKey& o) const { return tied() == o.tied(); }
+};
+struct StepGraph {
+  StepKey key;
+  hipGraphExec_t exec;
+};
+
 struct rau_ctx {
   rau_config cfg;             // cfg.B is the CURRENT batch size (rau_set_batch_size): what every layout, launch and
                               // getter reads at call time -- the B of the fresh context this one is equivalent to
@@ -272,7 +328,7 @@ struct rau_ctx {
   int* perr_h = nullptr;
   bool persist_used = false;
   bool persist_gave_up = false; // persist_check() turned the persistent encoder off: it stays off across resizes
-  float* hopw_h = nullptr;    // pinned staging of the hop weights, 2 slots of 3H + 2: hop_w [H] | select_w [H] | att_w [H] | merge_w [2]
+  float* hopw_h = nullptr;    // pinned staging of the hop weights: 2 slots of HopwLayout::size
   int hopw_slot = 0;
   // attention supervision (rau_backward_att, att_sup.hip): the gradient at the attprob output of every hop,
   // [H][cap][Sp] at the attention's pitch, allocated at the first call with a non-zero att_w
@@ -280,11 +336,10 @@ struct rau_ctx {
   // ... and its statistics' scratch (rau_att_stats, rau_att_criterion_forward): rows [2][H*cap] | results [2][H]
   float* att_sf = nullptr;
   int32_t* att_si = nullptr;
-  // step-selection head's gradient (rau_backward_select, select_bwd.hip); hopw_d is [3H + 2]: hop_w | select_w | att_w | merge_w
+  // step-selection head's gradient (rau_backward_select, select_bwd.hip)
   float *sel_s = nullptr, *sel_add = nullptr;   // [H][cap] s rows, [H][cap][M] s (x) wd; allocated at first use
-  bool sel_capture = false;   // rau_graph_step_select is capturing a step with a non-zero select weight (or
-                              // rau_graph_step_merged one with a non-zero merge weight): its backward forms
-                              // dpre / dhn itself, so the forward leaves them alone
+  bool capture_bwd_forms_dpre = false;   // a step is being captured whose backward forms dpre / dhn itself
+                                         // (StepLoss::forms_dpre), so the forward leaves them alone
   // backward temporaries
   // dZ holds dI (gradient at i_embed's OUTPUT); the tanh derivative is applied by its consumers
   float *dpre, *dhn, *dg4, *dcn[2], *dhp[2], *dj, *da_lin, *dz, *du, *dwsp, *dZ,
@@ -313,7 +368,7 @@ struct rau_ctx {
   uint64_t* dkey = nullptr;      // device copy of (seed, step): what fill_masks reads
   bool capturing = false;
   bool graph_last = false;       // the last backward ran inside a graph (its events are graph-internal)
-  std::vector<std::pair<uint64_t, hipGraphExec_t>> graphs;
+  std::vector<StepGraph> graphs;
   MergeState mg;                 // merged hops (rau_merge.hip): what may be read of the last forward
   // update
   float *npart = nullptr, *norms_d = nullptr;

@@ -511,9 +511,9 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   CK(dalloc(ctx, &ctx->lossrow, HB));
   CK(dalloc(ctx, &ctx->dopred, HB));
   CK(dalloc(ctx, &ctx->losses_d, (size_t)H));
-  CK(dalloc(ctx, &ctx->hopw_d, (size_t)3 * H + 2));   // hop_w | select_w | att_w | merge_w
+  CK(dalloc(ctx, &ctx->hopw_d, HopwLayout(H).size));
   {  // ctx-owned pinned staging for the hop weights: the async upload never reads caller memory
-    hipError_t eh = hipHostMalloc((void**)&ctx->hopw_h, (size_t)2 * (3 * H + 2) * sizeof(float), hipHostMallocDefault);
+    hipError_t eh = hipHostMalloc((void**)&ctx->hopw_h, 2 * HopwLayout(H).size * sizeof(float), hipHostMallocDefault);
     if (eh != hipSuccess) {
       rau_destroy(ctx);
       return fail(RAU_ERR_NOMEM, "hipHostMalloc(hop weights): %s", hipGetErrorString(eh));
@@ -581,7 +581,8 @@ void rau_destroy(rau_ctx* ctx) {
   if (ctx->st) hipStreamSynchronize(ctx->st);
   if (ctx->st2) hipStreamSynchronize(ctx->st2);
   if (ctx->st3) hipStreamSynchronize(ctx->st3);
-  for (auto& g : ctx->graphs) hipGraphExecDestroy(g.second);
+  for (auto& g : ctx->graphs) hipGraphExecDestroy(g.exec);
+  ctx->graphs.clear();   // rau_bank_destroy below drops the bank batches' graphs: not a second time
   for (StreamWs* w : stream_ws(ctx)) split_ws_unregister(w->slab);
   rau_bank_destroy(ctx);
   for (void* p : ctx->allocs) hipFree(p);
@@ -801,7 +802,7 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   for (int i = 0; i < 3; ++i) {
     if (!fresh[i]) continue;
     // captured steps hold the old workspace's address: all of them go (they are recaptured on demand)
-    for (auto& gr : ctx->graphs) hipGraphExecDestroy(gr.second);
+    for (auto& gr : ctx->graphs) hipGraphExecDestroy(gr.exec);
     ctx->graphs.clear();
     split_ws_unregister(wss[i]->slab);
     void* old = wss[i]->slab;
@@ -1168,7 +1169,8 @@ static int seam_mask() {
   return m;
 }
 static bool head_dgrad_fwd(const rau_ctx* ctx) {
-  return cur_batch(ctx).held.have_labels && ctx->mode == RAU_MODE_TRAIN && (seam_mask() & 1) && !ctx->sel_capture;
+  return cur_batch(ctx).held.have_labels && ctx->mode == RAU_MODE_TRAIN && (seam_mask() & 1) &&
+         !ctx->capture_bwd_forms_dpre;
 }
 
 int rau_forward(rau_ctx* ctx) {
@@ -1502,44 +1504,37 @@ int rau_forward(rau_ctx* ctx) {
 // The caller's hop_w may be a temporary (and may be pinned memory, for which an async copy really
 // is asynchronous): stage it in the ctx's own pinned buffer first.  Two slots, alternated, so the
 // copy of step n is never overwritten by the host while step n+1's call prepares its own.
-// select_w and att_w (null: none) travel behind hop_w in the same copy, each in its own block of H; merge_w
-// (null: none) behind them in a block of 2.
-static int upload_hop_weights(rau_ctx* ctx, const float* hop_w, const float* select_w = nullptr,
-                              const float* att_w = nullptr, const float* merge_w = nullptr) {
+// The terms present travel behind hop_w in the same copy, each in its block of HopwLayout; an absent one in front
+// of a present one goes as zeros.
+static int upload_hop_weights(rau_ctx* ctx, const StepLoss& l) {
   const int H = ctx->cfg.H;
+  const HopwLayout at(H);
   const int sl = (ctx->hopw_slot ^= 1);
-  float* stage = ctx->hopw_h + (size_t)sl * (3 * H + 2);
+  float* stage = ctx->hopw_h + (size_t)sl * at.size;
   // a host that runs two or more steps ahead of the device must not overwrite a staging slot whose
   // copy has not been read yet: wait for the copy issued from this slot two calls ago
   if (!ctx->hopw_ev[sl]) HIPC(hipEventCreateWithFlags(&ctx->hopw_ev[sl], hipEventDisableTiming));
   else HIPC(hipEventSynchronize(ctx->hopw_ev[sl]));
-  std::memcpy(stage, hop_w, (size_t)H * sizeof(float));
-  if (select_w) std::memcpy(stage + H, select_w, (size_t)H * sizeof(float));
-  else if (att_w || merge_w) std::memset(stage + H, 0, (size_t)H * sizeof(float));
-  if (att_w) std::memcpy(stage + 2 * H, att_w, (size_t)H * sizeof(float));
-  else if (merge_w) std::memset(stage + 2 * H, 0, (size_t)H * sizeof(float));
-  if (merge_w) std::memcpy(stage + 3 * H, merge_w, 2 * sizeof(float));
-  const size_t count = merge_w ? (size_t)3 * H + 2 : (size_t)(att_w ? 3 : select_w ? 2 : 1) * H;
+  const size_t count = l.merge_w ? at.size : l.att_w ? at.merge_w : l.select_w ? at.att_w : at.select_w;
+  std::memset(stage, 0, count * sizeof(float));
+  std::memcpy(stage, l.hop_w, (size_t)H * sizeof(float));
+  if (l.select_w) std::memcpy(stage + at.select_w, l.select_w, (size_t)H * sizeof(float));
+  if (l.att_w) std::memcpy(stage + at.att_w, l.att_w, (size_t)H * sizeof(float));
+  if (l.merge_w) std::memcpy(stage + at.merge_w, l.merge_w, 2 * sizeof(float));
   HIPC(hipMemcpyAsync(ctx->hopw_d, stage, count * sizeof(float), hipMemcpyHostToDevice, ctx->st));
   if (!ctx->capturing) HIPC(hipEventRecord(ctx->hopw_ev[sl], ctx->st));
   return 0;
 }
 
 // =============================================================== backward
-// select_w: null, or the per-hop weights of the step-selection head's BCE with at least one of them non-zero
-// (rau_backward_select): the one place the two entry points differ is marked `sel` below.
-// att_w: null, or the per-hop weights of the attention supervision with at least one of them non-zero
-// (rau_backward_att): marked `att` below -- one launch, and HopGrad::da_out of every active hop.
-// merge_w: null, or the two weights of the merged rows' cross-entropies with at least one of them non-zero
-// (rau_backward_merged): marked `mrg` below -- one launch behind the hop scaling; like `sel` it is a per-row term,
-// so dpre / dhn are formed here, and every hop is active (the uni row reads them all).
-static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w = nullptr,
-                         const float* merge_w = nullptr) {
-  const bool sel = select_w != nullptr, att = att_w != nullptr, mrg = merge_w != nullptr;
+// The one place a backward with a select_w differs is marked `sel` below.  `att`: one launch, and HopGrad::da_out
+// of every active hop.  `mrg`: one launch behind the hop scaling; like `sel` it is a per-row term, so dpre / dhn
+// are formed here, and every hop is active (the uni row reads them all).
+static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
+  const bool sel = loss.select_w != nullptr, att = loss.att_w != nullptr, mrg = loss.merge_w != nullptr;
+  const int HA = loss.active;
+  const HopwLayout at(ctx->cfg.H);
   if (!ctx->fwd_done) return fail(RAU_ERR_STATE, "rau_backward: call rau_forward first");
-  if (att && !cur_batch(ctx).held.att_targets)
-    return fail(RAU_ERR_STATE, "rau_backward_att: a non-zero att_w needs a batch with attention targets "
-                "(rau_set_att_targets)");
   if (ctx->fwd_table)
     return fail(RAU_ERR_STATE, "rau_backward: the evaluate-mode forward of a batch with an image table computed "
                 "i_embed once per image, so there is no per-sample I to differentiate; take evaluate-mode "
@@ -1578,9 +1573,9 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
 
   // dpred:mul(w[h])  SS:569 / MS:568-570 / Full:587-589
   if (!ctx->capturing) {  // (rau_graph_step uploads the weights before it launches the graph)
-    if (int rc = upload_hop_weights(ctx, hop_w, select_w, att_w, merge_w)) return rc;
+    if (int rc = upload_hop_weights(ctx, loss)) return rc;
   }
-  if (ctx->dpre_fwd && !sel && !mrg)   // the forward formed dpre / dhn from the unscaled dl: scale all three
+  if (ctx->dpre_fwd && !loss.forms_dpre())   // the forward formed dpre / dhn from the unscaled dl: scale all three
     RUN("scale_hops", 0, (double)H * B * (K + M + R) * 8,
         scale_hops3(st, H, ctx->hopw_d, (size_t)B * K, ctx->dl, (size_t)B * M, ctx->dpre, (size_t)B * R, ctx->dhn));
   else
@@ -1589,15 +1584,7 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
   // (head_dgrad and sel_add below, the classifier's weight gradient in mult_wgrads)
   if (mrg)
     RUN("merge_grad", 0, (double)H * B * K * 16,
-        merge_grad(st, H, B, K, ctx->logits, ctx->dopred, t, ctx->hopw_d + 3 * H, 0.f, 0.f, ctx->dl));
-
-  // Hops behind the last one with a non-zero loss weight receive no gradient at all (zero
-  // criterion gradient, zero recurrent gradient: Full/ResNet late-epoch gating, Full:587-589):
-  // their backward is identically zero and is skipped -- HA hops are "active".
-  int HA = 0;
-  for (int h = 0; h < H; ++h)
-    if (hop_w[h] != 0.f || (sel && select_w[h] != 0.f) || (att && att_w[h] != 0.f)) HA = h + 1;
-  if (mrg) HA = H;
+        merge_grad(st, H, B, K, ctx->logits, ctx->dopred, t, ctx->hopw_d + at.merge_w, 0.f, 0.f, ctx->dl));
 
   // ---------------- RAU BPTT, SS:561-578
   // Off the recurrence: dpre = (dl Wc) (.) mask and dhn = dpre Wo for all active hops at once.
@@ -1607,15 +1594,15 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
   const uint32_t* m_mf = mk(RAU_MASK_MF);
   if (sel)
     RUN("select_signal", 0, (double)HA * B * M * 4,
-        select_signal(st, HA * B, B, K, M, ctx->dopred, ctx->argmax_d, t, ctx->hopw_d + H, ctx->do_pred.W, ctx->sel_s,
-                      ctx->sel_add));
+        select_signal(st, HA * B, B, K, M, ctx->dopred, ctx->argmax_d, t, ctx->hopw_d + at.select_w, ctx->do_pred.W,
+                      ctx->sel_s, ctx->sel_add));
   // att: the gradient at the attprob output of all active hops, -(att_w[h] t / (a + eps)) / B, read by the attention
   // backward of each hop (HopGrad::da_out).  The targets may have come after the forward: it does not read them.
   if (att)
     RUN("att_sup_grad", 0, (double)HA * B * S * 12,
-        att_sup_grad(st, HA, B, SL, ctx->a, S, bs.att_t_d, S, bs.held.regions ? bs.nreg_d : nullptr, ctx->hopw_d + 2 * H,
-                     0.f, ctx->att_da, S));
-  if (HA > 0 && (!ctx->dpre_fwd || sel || mrg)) {
+        att_sup_grad(st, HA, B, SL, ctx->a, S, bs.att_t_d, S, bs.held.regions ? bs.nreg_d : nullptr,
+                     ctx->hopw_d + at.att_w, 0.f, ctx->att_da, S));
+  if (HA > 0 && (!ctx->dpre_fwd || loss.forms_dpre())) {
     LinOpts o = lin_opts(ctx, ctx->ws_chain);
     if (sel) { o.addend = ctx->sel_add; o.add_rs = M; }
     o.emask = m_mf;
@@ -1905,31 +1892,27 @@ static int backward_impl(rau_ctx* ctx, const float* hop_w, const float* select_w
   return RAU_OK;
 }
 
-int rau_backward(rau_ctx* ctx, const float* hop_w) {
+// The loss terms an entry point was called with, normalised once: finite weights, named after `fn` (hop_w too, but
+// for rau_backward and rau_graph_step, which take it as it is: check_hop_w); a term without a non-zero entry
+// becomes null; a non-zero att_w needs the batch's targets; the scratch of every term left exists on return.
+static int step_loss(rau_ctx* ctx, const char* fn, bool check_hop_w, const float* hop_w, const float* select_w,
+                     const float* att_w, const float* merge_w, StepLoss* loss) {
   NEED(ctx && hop_w, "null argument");
-  return backward_impl(ctx, hop_w, nullptr);
-}
-
-// Argument rules of the *_select and *_att entry points: finite weights; *select_w / *att_w become null when they
-// hold no non-zero entry (the path without them, launch for launch); otherwise their scratch exists on return.
-static int select_args(rau_ctx* ctx, const char* fn, const float* hop_w, const float** select_w,
-                       const float** att_w = nullptr) {
-  NEED(ctx && hop_w, "null argument");
+  if (merge_w) {
+    NEED(std::isfinite(merge_w[0]) && std::isfinite(merge_w[1]), "%s: merge_w is not finite", fn);
+    if (merge_w[0] == 0.f && merge_w[1] == 0.f) merge_w = nullptr;
+  }
   const int H = ctx->cfg.H;
   bool any = false, any_att = false;
+  int active = 0;
   for (int h = 0; h < H; ++h) {
-    NEED(std::isfinite(hop_w[h]), "%s: hop_w[%d] is not finite", fn, h);
-    if (*select_w) {
-      NEED(std::isfinite((*select_w)[h]), "%s: select_w[%d] is not finite", fn, h);
-      any = any || (*select_w)[h] != 0.f;
-    }
-    if (att_w && *att_w) {
-      NEED(std::isfinite((*att_w)[h]), "%s: att_w[%d] is not finite", fn, h);
-      any_att = any_att || (*att_w)[h] != 0.f;
-    }
+    NEED(!check_hop_w || std::isfinite(hop_w[h]), "%s: hop_w[%d] is not finite", fn, h);
+    NEED(!select_w || std::isfinite(select_w[h]), "%s: select_w[%d] is not finite", fn, h);
+    NEED(!att_w || std::isfinite(att_w[h]), "%s: att_w[%d] is not finite", fn, h);
+    any = any || (select_w && select_w[h] != 0.f);
+    any_att = any_att || (att_w && att_w[h] != 0.f);
+    if (hop_w[h] != 0.f || (select_w && select_w[h] != 0.f) || (att_w && att_w[h] != 0.f)) active = h + 1;
   }
-  if (!any) *select_w = nullptr;
-  if (att_w && !any_att) *att_w = nullptr;
   if (any_att) {
     if (!cur_batch(ctx).held.att_targets)
       return fail(RAU_ERR_STATE, "%s: a non-zero att_w needs a batch with attention targets (rau_set_att_targets)", fn);
@@ -1941,34 +1924,30 @@ static int select_args(rau_ctx* ctx, const char* fn, const float* hop_w, const f
       if (int rc = dalloc(ctx, &ctx->sel_s, (size_t)H * ctx->cap)) return rc;
     if (int rc = dalloc(ctx, &ctx->sel_add, (size_t)H * ctx->cap * ctx->cfg.M)) return rc;
   }
+  *loss = StepLoss{hop_w, any ? select_w : nullptr, any_att ? att_w : nullptr, merge_w, merge_w ? H : active};
   return RAU_OK;
 }
 
+int rau_backward(rau_ctx* ctx, const float* hop_w) {
+  StepLoss loss;
+  if (int rc = step_loss(ctx, "rau_backward", false, hop_w, nullptr, nullptr, nullptr, &loss)) return rc;
+  return backward_impl(ctx, loss);
+}
 int rau_backward_select(rau_ctx* ctx, const float* hop_w, const float* select_w) {
-  if (int rc = select_args(ctx, "rau_backward_select", hop_w, &select_w)) return rc;
-  return backward_impl(ctx, hop_w, select_w);
+  StepLoss loss;
+  if (int rc = step_loss(ctx, "rau_backward_select", true, hop_w, select_w, nullptr, nullptr, &loss)) return rc;
+  return backward_impl(ctx, loss);
 }
-
 int rau_backward_att(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w) {
-  if (int rc = select_args(ctx, "rau_backward_att", hop_w, &select_w, &att_w)) return rc;
-  return backward_impl(ctx, hop_w, select_w, att_w);
+  StepLoss loss;
+  if (int rc = step_loss(ctx, "rau_backward_att", true, hop_w, select_w, att_w, nullptr, &loss)) return rc;
+  return backward_impl(ctx, loss);
 }
-
-// Argument rule of the *_merged entry points: finite weights; *merge_w becomes null when both are zero (the path
-// without them, launch for launch).  Checked in front of select_args, which allocates.
-static int merged_args(const char* fn, const float** merge_w) {
-  if (!*merge_w) return RAU_OK;
-  NEED(std::isfinite((*merge_w)[0]) && std::isfinite((*merge_w)[1]), "%s: merge_w is not finite", fn);
-  if ((*merge_w)[0] == 0.f && (*merge_w)[1] == 0.f) *merge_w = nullptr;
-  return RAU_OK;
-}
-
 int rau_backward_merged(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
                         const float* merge_w) {
-  NEED(ctx && hop_w, "null argument");
-  if (int rc = merged_args("rau_backward_merged", &merge_w)) return rc;
-  if (int rc = select_args(ctx, "rau_backward_merged", hop_w, &select_w, &att_w)) return rc;
-  return backward_impl(ctx, hop_w, select_w, att_w, merge_w);
+  StepLoss loss;
+  if (int rc = step_loss(ctx, "rau_backward_merged", true, hop_w, select_w, att_w, merge_w, &loss)) return rc;
+  return backward_impl(ctx, loss);
 }
 
 // One training step's forward + backward (optionally with the gradient zeroing in front) as ONE
@@ -1977,54 +1956,45 @@ int rau_backward_merged(rau_ctx* ctx, const float* hop_w, const float* select_w,
 // explicit, zeroing or not) -- and replayed; what changes from step to step lives in device
 // memory: the batch (rau_set_batch), the Philox key (rau_set_dropout_seed) and the hop weights
 // (uploaded here, in front of the launch).
-// select_w: as backward_impl's.  The weights are read from device memory, so they may change between replays;
-// whether there is a non-zero one decides the launches and joins the key, with the active-hop count.  att_w alike.
-// merge_w alike: "any merge_w non-zero" joins the key, and such a step runs all H hops.
-static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select_w, int zero_grads_first,
-                           const float* att_w = nullptr, const float* merge_w = nullptr) {
-  const bool sel = select_w != nullptr, att = att_w != nullptr, mrg = merge_w != nullptr;
+// The weights are read from device memory, so they may change between replays; which terms have a non-zero one
+// decides the launches and joins the key (StepKey), with the active-hop count.
+static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_first) {
   const BatchSlot& bs = cur_batch(ctx);
   if (!bs.held.have || !bs.held.have_labels)
     return fail(RAU_ERR_STATE, "rau_graph_step: needs a batch with labels (rau_set_batch)");
   if (ctx->prof_on) return fail(RAU_ERR_STATE, "rau_graph_step: profiling must be off");
-  const int H = ctx->cfg.H;
-  int HA = 0;
-  for (int h = 0; h < H; ++h)
-    if (hop_w[h] != 0.f || (sel && select_w[h] != 0.f) || (att && att_w[h] != 0.f)) HA = h + 1;
-  if (mrg) HA = H;
-  uint64_t key = (uint64_t)ctx->mode | ((uint64_t)bs.held.max_len << 2) | ((uint64_t)HA << 12) |
-                 ((uint64_t)(zero_grads_first != 0) << 22);
-  for (int i = 0; i < 5; ++i) key |= (uint64_t)ctx->mexplicit[i] << (24 + i);
-  key |= (uint64_t)ctx->cur_slot << 30;   // the captured kernels hold the batch slot's device pointers
-  key |= (uint64_t)bs.held.feat_type << 32;  // ... and read the batch in its element type (three bits: 0..5)
-  key |= (uint64_t)(bs.held.n_images > 0) << 35;   // ... through the gather of an image table (any table, any N)
-  key |= (uint64_t)bs.held.bank << 36;   // ... of a bank batch: out of the bank (rau_bank_destroy reads this bit)
-  // ... against an answer set of G entries (0 = labels): another head kernel (the one reader besides truth_of())
-  key |= (uint64_t)bs.held.ans_G << 37;
-  key |= (uint64_t)ctx->cfg.B << 42;      // every launch is shaped by the batch size (rau_set_batch_size)
-  key |= (uint64_t)sel << 31;             // ... and by the step-selection head's gradient being asked for
-  // ... and the attention kernels hold the slot's region counts or a null pointer (rau_set_regions)
-  key |= (uint64_t)bs.held.regions << 62;
-  // ... and a step with a non-zero att_w has one more launch and hands every hop its da_out; the batch's targets
-  // (rau_set_att_targets) are what that launch reads
-  key |= (uint64_t)att << 23;
-  key |= (uint64_t)bs.held.att_targets << 29;
-  key |= (uint64_t)mrg << 63;             // ... and a step with a non-zero merge_w has the merge_grad launch
-  if (int rc = upload_hop_weights(ctx, hop_w, select_w, att_w, merge_w)) return rc;
+  StepKey key;
+  key.mode = ctx->mode;
+  key.max_len = bs.held.max_len;
+  key.active = loss.active;
+  key.zero = zero_grads_first != 0;
+  std::copy(ctx->mexplicit, ctx->mexplicit + 5, key.mexplicit);
+  key.slot = ctx->cur_slot;
+  key.feat_type = bs.held.feat_type;
+  key.table = bs.held.n_images > 0;
+  key.bank = bs.held.bank;
+  key.ans_G = bs.held.ans_G;
+  key.B = ctx->cfg.B;
+  key.sel = loss.select_w != nullptr;
+  key.regions = bs.held.regions;
+  key.att = loss.att_w != nullptr;
+  key.att_targets = bs.held.att_targets;
+  key.mrg = loss.merge_w != nullptr;
+  if (int rc = upload_hop_weights(ctx, loss)) return rc;
   ctx->mg.valid = false;
   hipGraphExec_t exec = nullptr;
   for (auto& g : ctx->graphs)
-    if (g.first == key) exec = g.second;
+    if (g.key == key) exec = g.exec;
   if (!exec) {
     hipGraph_t graph = nullptr;
     HIPC(hipStreamBeginCapture(ctx->st, hipStreamCaptureModeRelaxed));
     ctx->capturing = true;
-    ctx->sel_capture = sel || mrg;
+    ctx->capture_bwd_forms_dpre = loss.forms_dpre();
     int rc = zero_grads_first ? rau_zero_grads(ctx) : 0;
     if (!rc) rc = rau_forward(ctx);
-    if (!rc) rc = backward_impl(ctx, hop_w, select_w, att_w, merge_w);
+    if (!rc) rc = backward_impl(ctx, loss);
     ctx->capturing = false;
-    ctx->sel_capture = false;
+    ctx->capture_bwd_forms_dpre = false;
     hipError_t e = hipStreamEndCapture(ctx->st, &graph);
     if (rc) {
       if (graph) hipGraphDestroy(graph);
@@ -2053,27 +2023,26 @@ static int graph_step_impl(rau_ctx* ctx, const float* hop_w, const float* select
 }
 
 int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first) {
-  NEED(ctx && hop_w, "null argument");
-  return graph_step_impl(ctx, hop_w, nullptr, zero_grads_first);
+  StepLoss loss;
+  if (int rc = step_loss(ctx, "rau_graph_step", false, hop_w, nullptr, nullptr, nullptr, &loss)) return rc;
+  return graph_step_impl(ctx, loss, zero_grads_first);
 }
-
 int rau_graph_step_select(rau_ctx* ctx, const float* hop_w, const float* select_w, int zero_grads_first) {
-  if (int rc = select_args(ctx, "rau_graph_step_select", hop_w, &select_w)) return rc;
-  return graph_step_impl(ctx, hop_w, select_w, zero_grads_first);
+  StepLoss loss;
+  if (int rc = step_loss(ctx, "rau_graph_step_select", true, hop_w, select_w, nullptr, nullptr, &loss)) return rc;
+  return graph_step_impl(ctx, loss, zero_grads_first);
 }
-
 int rau_graph_step_att(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
                        int zero_grads_first) {
-  if (int rc = select_args(ctx, "rau_graph_step_att", hop_w, &select_w, &att_w)) return rc;
-  return graph_step_impl(ctx, hop_w, select_w, zero_grads_first, att_w);
+  StepLoss loss;
+  if (int rc = step_loss(ctx, "rau_graph_step_att", true, hop_w, select_w, att_w, nullptr, &loss)) return rc;
+  return graph_step_impl(ctx, loss, zero_grads_first);
 }
-
 int rau_graph_step_merged(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
                           const float* merge_w, int zero_grads_first) {
-  NEED(ctx && hop_w, "null argument");
-  if (int rc = merged_args("rau_graph_step_merged", &merge_w)) return rc;
-  if (int rc = select_args(ctx, "rau_graph_step_merged", hop_w, &select_w, &att_w)) return rc;
-  return graph_step_impl(ctx, hop_w, select_w, zero_grads_first, att_w, merge_w);
+  StepLoss loss;
+  if (int rc = step_loss(ctx, "rau_graph_step_merged", true, hop_w, select_w, att_w, merge_w, &loss)) return rc;
+  return graph_step_impl(ctx, loss, zero_grads_first);
 }
 
 int rau_wait_grads(rau_ctx* ctx, int group, void* hip_stream) {

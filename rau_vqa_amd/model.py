@@ -613,6 +613,17 @@ class RAU:
             raise ValueError("merge_w must have 2 entries: uni, select")
         return w
 
+    def _loss_args(self, hop_w, select_w, att_w, merge_w):
+        """The entry-point family that takes these loss terms ("", "_select", "_att" or "_merged": the last term
+        given decides) and its weight arguments: pointers that keep their arrays alive, None for a term left out."""
+        arrs = [self._hop_array(hop_w, "hop_w"),
+                None if select_w is None else self._hop_array(select_w, "select_w"),
+                None if att_w is None else self._hop_array(att_w, "att_w"),
+                None if merge_w is None else self._merge_array(merge_w)]
+        n = max(i for i, a in enumerate(arrs) if a is not None)
+        return (("", "_select", "_att", "_merged")[n],
+                [None if a is None else a.ctypes.data_as(C.c_void_p) for a in arrs[:n + 1]])
+
     def backward(self, hop_w, select_w=None, att_w=None, merge_w=None):
         """select_w [H]: per-hop weight of the step-selection head's BCE gradient, the multiplier the
         reference fixes at 0 (SS:566); None is that zero (rau_backward).
@@ -620,45 +631,14 @@ class RAU:
         the reference passes gradattprob = zeros (SS:361, 573); None is those zeros.
         merge_w [2]: weights of the cross-entropies of the merged "uni" and "select" rows (step_stats' loss[H] and
         loss[H+1], which the reference only logs); None is no such term."""
-        w = self._hop_array(hop_w, "hop_w")
-        if merge_w is not None:
-            sw = None if select_w is None else self._hop_array(select_w, "select_w")
-            aw = None if att_w is None else self._hop_array(att_w, "att_w")
-            mw = self._merge_array(merge_w)
-            L.check(self._lib.rau_backward_merged(self._h, w.ctypes.data, None if sw is None else sw.ctypes.data,
-                                                  None if aw is None else aw.ctypes.data, mw.ctypes.data))
-        elif att_w is not None:
-            sw = None if select_w is None else self._hop_array(select_w, "select_w")
-            aw = self._hop_array(att_w, "att_w")
-            L.check(self._lib.rau_backward_att(self._h, w.ctypes.data, None if sw is None else sw.ctypes.data,
-                                               aw.ctypes.data))
-        elif select_w is None:
-            L.check(self._lib.rau_backward(self._h, w.ctypes.data))
-        else:
-            sw = self._hop_array(select_w, "select_w")
-            L.check(self._lib.rau_backward_select(self._h, w.ctypes.data, sw.ctypes.data))
+        family, ws = self._loss_args(hop_w, select_w, att_w, merge_w)
+        L.check(getattr(self._lib, "rau_backward" + family)(self._h, *ws))
 
     def graph_step(self, hop_w, zero_grads=True, select_w=None, att_w=None, merge_w=None):
         """zero_grads + forward + backward as one hipGraph launch (captured on first use); select_w, att_w and
         merge_w as in backward (read from device memory: they may change between replays)."""
-        w = self._hop_array(hop_w, "hop_w")
-        if merge_w is not None:
-            sw = None if select_w is None else self._hop_array(select_w, "select_w")
-            aw = None if att_w is None else self._hop_array(att_w, "att_w")
-            mw = self._merge_array(merge_w)
-            L.check(self._lib.rau_graph_step_merged(self._h, w.ctypes.data, None if sw is None else sw.ctypes.data,
-                                                    None if aw is None else aw.ctypes.data, mw.ctypes.data,
-                                                    int(zero_grads)))
-        elif att_w is not None:
-            sw = None if select_w is None else self._hop_array(select_w, "select_w")
-            aw = self._hop_array(att_w, "att_w")
-            L.check(self._lib.rau_graph_step_att(self._h, w.ctypes.data, None if sw is None else sw.ctypes.data,
-                                                 aw.ctypes.data, int(zero_grads)))
-        elif select_w is None:
-            L.check(self._lib.rau_graph_step(self._h, w.ctypes.data, int(zero_grads)))
-        else:
-            sw = self._hop_array(select_w, "select_w")
-            L.check(self._lib.rau_graph_step_select(self._h, w.ctypes.data, sw.ctypes.data, int(zero_grads)))
+        family, ws = self._loss_args(hop_w, select_w, att_w, merge_w)
+        L.check(getattr(self._lib, "rau_graph_step" + family)(self._h, *ws, int(zero_grads)))
 
     def sync(self):
         L.check(self._lib.rau_sync(self._h))
