@@ -10,7 +10,8 @@ attention and zero gradients.  The predicates, read off the code at this commit:
       conv_dz_fused_ok (gemm_conv.hip) says the same, and for the module-level feature-map gradient; the
       two forward convs take it only when the knob asks.  At Sp = 208 its LDS tile has no pad columns left.
   conv_wide_ok (conv_wide.hip)                       Sp == 196, rows % 64, reduction % 8: both forward convs, the
-      samples in groups of four (B = 6: one group + 2 on the general tile; B = 66: 64 + 2).
+      samples of a launch in groups of four, the rest on the general tile (B = 6, train mode: both hops in one
+      launch of 12, no rest; evaluate mode: 4 + 2; B = 66: one launch per hop, 64 + 2).
   dgrad_dma_ok (dgrad_dma.hip)                       Sp == 196, M % 128, A % 16, A >= 48, and not `light` (contexts
       above 64 samples): the attention dgrad's LDS-DMA tile.
   wgrad_dma_ok (wgrad_dma.hip)                       Sp == 196, both row counts % 128: both conv weight gradients
@@ -76,9 +77,9 @@ CASES = {
     176: (176, "general", "general", "32, 16-wide tail", "last S below the per-sample tile"),
     177: (180, "general", "sample+dZ", "32, 20-wide tail", "first S inside it, pitched, three pad columns"),
     180: (180, "general", "sample+dZ", "32, 20-wide tail", "inside it, unpitched"),
-    193: (196, "wide 4+2 / 64+2", "sample+dZ / dgrad_dma", "wgrad_dma", "every == 196 kernel, three pad columns"),
-    195: (196, "wide 4+2 / 64+2", "sample+dZ / dgrad_dma", "wgrad_dma", "every == 196 kernel, one pad column"),
-    196: (196, "wide 4+2 / 64+2", "sample+dZ / dgrad_dma", "wgrad_dma", "control"),
+    193: (196, "wide 12 / 64+2", "sample+dZ / dgrad_dma", "wgrad_dma", "every == 196 kernel, three pad columns"),
+    195: (196, "wide 12 / 64+2", "sample+dZ / dgrad_dma", "wgrad_dma", "every == 196 kernel, one pad column"),
+    196: (196, "wide 12 / 64+2", "sample+dZ / dgrad_dma", "wgrad_dma", "control"),
     197: (200, "general", "sample+dZ", "32, 8-wide tail", "Sp = 200, pitched"),
     200: (200, "general", "sample+dZ", "32, 8-wide tail", "Sp = 200, unpitched"),
     205: (208, "general", "sample+dZ", "32, 16-wide tail", "Sp = 208: 13 live column blocks, no LDS pad; pitched"),
@@ -107,10 +108,11 @@ def test_the_case_table_states_the_pitch():
 _REFERENCES = {}
 
 
-def check(monkeypatch, S, B, mode, env=None, prof=False):
+def check(monkeypatch, S, B, mode, env=None, prof=False, over=None):
     """tests/test_gpu_parity.check at (S, B); the fp64 reference of a problem is computed once for the families
     that run it.  prof: run the context with its profile on (every launch is then bracketed by two events:
-    only where a class is asserted, the rest runs as a training step does) and return what the step launched, by class."""
+    only where a class is asserted, the rest runs as a training step does) and return what the step launched, by class.
+    over: dimensions that replace F32's (tests/test_gpu_widths.py sweeps the widths through this)."""
     from oracle import ref_torch
     from rau_vqa_amd import model
     for k in ATT_ENV:
@@ -118,11 +120,13 @@ def check(monkeypatch, S, B, mode, env=None, prof=False):
     for k, v in (env or {}).items():
         monkeypatch.setenv(k, v)               # read when the context is created / at every launch
     real_step = ref_torch.step
+    dims = dict(F32, B=B, S=S, **(over or {}))
+    key = (mode,) + tuple(sorted(dims.items()))
 
     def step_once(*args, **kw):
-        if (S, B, mode) not in _REFERENCES:
-            _REFERENCES[S, B, mode] = real_step(*args, **kw)
-        return _REFERENCES[S, B, mode]
+        if key not in _REFERENCES:
+            _REFERENCES[key] = real_step(*args, **kw)
+        return _REFERENCES[key]
     launched = {}
 
     class Profiled(model.RAU):
@@ -137,16 +141,18 @@ def check(monkeypatch, S, B, mode, env=None, prof=False):
     monkeypatch.setattr(ref_torch, "step", step_once)
     if prof:
         monkeypatch.setattr(model, "RAU", Profiled)
-    sh = util.shapes(dict(F32, B=B, S=S))
+    sh = util.shapes(dims)
     errs = test_gpu_parity.check(sh, scale=SCALE, torch_oracle=True, mode=mode)
-    print(f"S={S} B={B} {mode}: largest error / bar {max(errs.values()) / test_gpu_parity.TOL:.3f}")
+    what = "".join(f" {k}={v}" for k, v in sorted((over or {}).items()))
+    print(f"S={S} B={B}{what} {mode}: largest error / bar {max(errs.values()) / test_gpu_parity.TOL:.3f}")
     return launched
 
 
 @pytest.mark.parametrize("mode", ["train", "eval"])
 @pytest.mark.parametrize("S", sorted(CASES))
 def test_small_batch(monkeypatch, S, mode):
-    """B = 6: one conv_wide group of four plus two; split attention family, `light` dgrad."""
+    """B = 6: conv_wide on 12 samples (train: the two hops in one launch) or on four plus two on the general tile
+    (evaluate); split attention family, `light` dgrad."""
     check(monkeypatch, S, 6, mode)
 
 
@@ -179,15 +185,16 @@ def test_bf16(S, mode):
 
 
 # ---------------------------------------------------------------- 3. module-level calls
-@pytest.mark.parametrize("S", S_MODULES)
-def test_module_level_feval(S):
-    """tests/test_gpu_fuzz.py::test_random_shapes_module_level_feval's body and bar at these S."""
+TOL_MODULES = 2e-5     # tests/test_gpu_fuzz.py::test_random_shapes_module_level_feval's bar
+
+
+def module_level_feval(dims, seed, label):
+    """tests/test_gpu_fuzz.py::test_random_shapes_module_level_feval's body and bar at `dims`."""
     import torch
     from rau_vqa_amd import modules
     from tests.test_gpu_modules import make_model, cuda
-    dims = dict(F32, B=6, S=S)
     sh = util.shapes(dims)
-    lens = np.random.default_rng(2000 + S).integers(0, dims["T"] + 1, dims["B"]).astype(np.int32)
+    lens = np.random.default_rng(seed).integers(0, dims["T"] + 1, dims["B"]).astype(np.int32)
     lens[0] = dims["T"]
     batch, params, masks = util.make_problem(sh, lens=lens, scale=SCALE)
     hop_w = np.full(sh.H, 1.0, np.float32)
@@ -204,9 +211,14 @@ def test_module_level_feval(S):
     g_step = m.get_grads()
     m.close()
     errs = {k: util.rel_err(g_mod[k], g_step[k]) for k in g_step}
-    print(f"S={S}: largest error / bar {max(errs.values()) / 2e-5:.3f}")
+    print(f"{label}: largest error / bar {max(errs.values()) / TOL_MODULES:.3f}")
     for k in g_step:
-        assert errs[k] < 2e-5, (k, dims)
+        assert errs[k] < TOL_MODULES, (k, dims)
+
+
+@pytest.mark.parametrize("S", S_MODULES)
+def test_module_level_feval(S):
+    module_level_feval(dict(F32, B=6, S=S), 2000 + S, f"S={S}")
 
 
 # ---------------------------------------------------------------- 6. the upper end
