@@ -78,6 +78,14 @@ int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const
 int rau_batch_answers(rau_ctx* ctx, int32_t* G);
 int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n);
 int rau_batch_regions(rau_ctx* ctx, int* has);
+int rau_set_batch_packed(rau_ctx* ctx, const void* rows, int feat_type, int n_maps, const int32_t* counts,
+                         const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
+                         const int32_t* labels);
+int rau_set_batch_async_packed(rau_ctx* ctx, int slot, const void* rows, int feat_type, int n_maps,
+                               const int32_t* counts, const int32_t* image_of, const int32_t* tokens,
+                               const int32_t* lens, const int32_t* labels, int has_labels);
+int rau_bank_put_packed(rau_ctx* ctx, int32_t first, int32_t count, const void* rows, int src_type,
+                        const int32_t* counts);
 int rau_forward(rau_ctx* ctx);
 int rau_backward(rau_ctx* ctx, const float* hop_w);
 int rau_backward_select(rau_ctx* ctx, const float* hop_w, const float* select_w);
@@ -383,6 +391,30 @@ function RAU:setBatchImages(feats, image_of, x, x_len, y, slot, has_labels, feat
                                  y and y:data() or nil))
   end
 end
+-- Packed region features (rau_set_batch_packed): rows is a Float/HalfTensor [sum(counts), D] (or a ByteTensor of
+-- fp8 codes with its feat_type), one row per box as the region files store them; counts an IntTensor [N] with
+-- 1 <= counts[i] <= S, map i owning counts[i] consecutive rows.  Only the rows are uploaded; the device transposes
+-- and zero-pads them and the counts become the batch's region counts (as by setRegions).  image_of nil: a plain
+-- batch, N == B; else an IntTensor [B] of 1-BASED map numbers, as in setBatchImages (counts are then per image).
+-- slot = nil: the synchronous form; slot = 0 | 1 with rows nil: the rows already lie at the start of the slot's staging.
+function RAU:setBatchPacked(rows, counts, x, x_len, y, image_of, slot, has_labels, feat_type)
+  follow_rows(self, x_len)
+  local ft = feat_type_of(rows, feat_type)
+  local n = counts:int():contiguous()
+  assert(n:dim() == 1 and (image_of or n:size(1) == self.n), 'counts must be [B] (or [N] beside image_of)')
+  assert(not rows or (rows:dim() == 2 and rows:size(1) == n:sum() and rows:size(2) == self.cfg.D),
+         'rows must be [sum(counts), D]')
+  local idx = image_of and image_of:int():add(-1)
+  if slot then
+    check(C.rau_set_batch_async_packed(self.h, slot, rows and rows:data() or nil, ft, n:size(1), n:data(),
+                                       idx and idx:data() or nil, x and x:data() or nil,
+                                       x_len and x_len:data() or nil, y and y:data() or nil,
+                                       (has_labels == false) and 0 or 1))
+  else
+    check(C.rau_set_batch_packed(self.h, rows:data(), ft, n:size(1), n:data(), idx and idx:data() or nil, x:data(),
+                                 x_len:data(), y and y:data() or nil))
+  end
+end
 -- 0 for a plain resident batch, else the number of maps in its image table
 -- Feature bank: every image's map once in device memory (rau_bank_*).  bankCreate(capacity, 'f32' | 'f16' |
 -- 'bf16' | 'e4m3' | 'e5m2'); bankPut(first, feats) takes a Float/HalfTensor [n,D,W,H] (or a ByteTensor of fp8
@@ -394,6 +426,14 @@ end
 function RAU:bankPut(first, feats, feat_type)
   local ft = feat_type_of(feats, feat_type)
   check(C.rau_bank_put(self.h, first - 1, feats:size(1), feats:data(), ft))
+end
+-- bankPut for packed region rows: rows [sum(counts), D], counts IntTensor [n]; the bank keeps the dense maps and
+-- no counts (keep them on the host and pass setRegions what a bank batch needs).
+function RAU:bankPutPacked(first, rows, counts, feat_type)
+  local ft = feat_type_of(rows, feat_type)
+  local n = counts:int():contiguous()
+  assert(rows:dim() == 2 and rows:size(1) == n:sum() and rows:size(2) == self.cfg.D, 'rows must be [sum(counts), D]')
+  check(C.rau_bank_put_packed(self.h, first - 1, n:size(1), rows:data(), ft, n:data()))
 end
 function RAU:bankDestroy()
   check(C.rau_bank_destroy(self.h))

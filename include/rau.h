@@ -412,6 +412,45 @@ int rau_batch_answers(rau_ctx* ctx, int32_t* G);
 int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n /* [batch] host */);
 int rau_batch_regions(rau_ctx* ctx, int* has);
 
+/* ---- packed region features: rows as the files store them, unpacked on the device ------------------
+ * Region feature files hold one row of D values per box.  A packed batch hands those rows over as they are:
+ * rows [sum(counts), D] of feat_type elements, row-major, map i owning counts[i] consecutive rows (1 <= counts[i]
+ * <= S), n_maps maps in all.  Only sum(counts) * D elements cross the link; one kernel (packed.hip) transposes them
+ * into the slot's feature buffer [n_maps, D, Sp] and writes zero bits behind each count, pad columns included, and
+ * the counts become the batch's region counts in the same call.  With off the exclusive prefix sum of counts,
+ *   dense[i, d, s] = rows[off[i] + s, d] for s < counts[i], all bits zero (+0 in every type) elsewhere
+ * (rau_vqa_amd.feat16.unpack_regions), and a packed batch gives, BIT FOR BIT, the results of the dense batch `dense`
+ * followed by rau_set_regions with counts (image_of == NULL: a plain batch, n_maps must equal the batch size) or
+ * with counts[image_of[b]] (an image table of n_maps maps, image_of [batch] as at rau_set_batch_images) -- in both
+ * modes, under rau_graph_step, at module level with X == NULL and in the merged hops.  rau_batch_feats,
+ * rau_batch_images, rau_batch_feat_type and rau_batch_regions report what they report for that dense batch; a later
+ * upload into the slot or rau_set_batch_size clears the counts, a later rau_set_regions replaces them.
+ *   rau_set_batch_packed        synchronising, like rau_set_batch; rows must not be NULL.
+ *   rau_set_batch_async_packed  the slot form: rows == NULL means the slot's pinned staging (rau_batch_slot) already
+ *                               holds the sum(counts) * D elements at its start.  The H2D copy of the rows, the
+ *                               unpack and the counts are enqueued on the copy stream behind the slot's events,
+ *                               where an upload's copies go; nothing is synchronised.
+ *   rau_bank_put_packed         rau_bank_put for packed rows: maps [first, first+count) from rows [sum(counts), D]
+ *                               of src_type, the same type pairs (f32 is narrowed on the device with the bits of
+ *                               rau_bank_put), chunking through pinned staging, quiescing and row bookkeeping.  The
+ *                               bank keeps dense maps: rau_bank_get returns the unpacked [count, D, S].  Counts are
+ *                               not stored in the bank; the host keeps them and passes rau_set_regions what a bank
+ *                               batch needs.
+ * The raw rows land in a device staging block per slot, sized for the capacity and allocated at the slot's first
+ * packed batch: a context that never sends one allocates and launches exactly what it did.
+ * Errors, nothing enqueued, the previous batch still resident: RAU_ERR_INVALID for a count outside 1..S, n_maps
+ * outside [1, batch], n_maps != batch without image_of, an image_of entry outside [0, n_maps), an unknown type;
+ * the slot and state rules of rau_set_batch_async_images; RAU_ERR_NOMEM from the staging allocation leaves the
+ * context usable. */
+int rau_set_batch_packed(rau_ctx* ctx, const void* rows, int feat_type, int n_maps, const int32_t* counts /* [n_maps] host */,
+                         const int32_t* image_of /* NULL: plain batch */, const int32_t* tokens, const int32_t* lens,
+                         const int32_t* labels);
+int rau_set_batch_async_packed(rau_ctx* ctx, int slot, const void* rows, int feat_type, int n_maps,
+                               const int32_t* counts, const int32_t* image_of, const int32_t* tokens,
+                               const int32_t* lens, const int32_t* labels, int has_labels);
+int rau_bank_put_packed(rau_ctx* ctx, int32_t first, int32_t count, const void* rows, int src_type,
+                        const int32_t* counts /* [count] host */);
+
 /* ---- the hot path ------------------------------------------------------------
  * rau_forward : SS:443-520  encoder unroll, length select, H-hop RAU, per-hop
  *               CrossEntropyCriterion forward, first-max argmax.

@@ -84,6 +84,12 @@ _SIGS = {
     # region counts: attention over a sample's valid positions only
     "rau_set_regions": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "rau_batch_regions": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    # packed region rows: transposed and zero-padded on the device, counts attached in the same call
+    "rau_set_batch_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "rau_set_batch_async_packed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "rau_bank_put_packed": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
     "rau_set_batch_typed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
     "rau_set_batch_async_typed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,

@@ -9,6 +9,7 @@
 // Both check the arguments (check_images, index_batch), describe the batch as one `Batch`, enqueue its copies
 // (enqueue_batch) and record what the slot now holds (hold).
 #include "rau_ctx.h"
+#include "packed.h"
 
 namespace {
 // Host-side half of a batch hand-over: argument checks and the distinct-token index over the live
@@ -60,6 +61,12 @@ struct Batch {
   const int32_t* image_of = nullptr;   // passed, n_images > 0 says "table"
   const int32_t *tokens = nullptr, *lens = nullptr, *labels = nullptr;
   const int32_t* bank_rows = nullptr;   // non-null: the table is bank[bank_rows]
+  // packed batch (rau_set_batch_packed): feats holds pk_rows region rows [pk_rows][D], map i owns pk_counts[i] of
+  // them; the maps (B of them, or the n_images of a table) are unpacked on the device
+  const int32_t* pk_counts = nullptr;
+  size_t pk_rows = 0;                   // sum of pk_counts (check_packed)
+  const int32_t* pk_meta = nullptr;     // off[maps] | cnt[maps]
+  const int32_t* pk_nreg = nullptr;     // [B] region counts per SAMPLE: pk_counts, or pk_counts[image_of]
   // ---- worked out on the way in
   const int32_t* bank_idx = nullptr;    // [2B], check_bank_rows
   bool bank_table = false;              // the upload gathers the table itself (wants_table)
@@ -96,6 +103,31 @@ int check_bank_rows(rau_ctx* ctx, int n_images, const int32_t* rows, const int32
     idx[c.B + b] = rows[image_of[b]];
   }
   return RAU_OK;
+}
+int ensure_packed(rau_ctx* ctx, int si, bool pinned);   // (below, next to ensure_regions)
+// packed batch: as many maps as samples unless an index names them, every count in [1, S]; *total = their sum
+int check_packed(const rau_config& c, int n_maps, const int32_t* counts, const int32_t* image_of, size_t* total) {
+  NEED(counts, "null counts");
+  NEED(n_maps >= 1 && n_maps <= c.B, "n_maps=%d out of [1,%d]", n_maps, c.B);
+  NEED(image_of || n_maps == c.B, "n_maps=%d without image_of: a plain batch has %d maps", n_maps, c.B);
+  size_t sum = 0;
+  for (int i = 0; i < n_maps; ++i) {
+    NEED(counts[i] >= 1 && counts[i] <= c.S, "counts[%d]=%d out of [1,%d]", i, counts[i], c.S);
+    sum += (size_t)counts[i];
+  }
+  *total = sum;
+  return RAU_OK;
+}
+// meta[2 * maps] = exclusive prefix sums | counts; nreg[B] = the count of the map each sample looks at
+void fill_packed(const rau_config& c, const Batch& b, int32_t* meta, int32_t* nreg) {
+  const int maps = b.n_images > 0 ? b.n_images : c.B;
+  int32_t off = 0;
+  for (int i = 0; i < maps; ++i) {
+    meta[i] = off;
+    meta[maps + i] = b.pk_counts[i];
+    off += b.pk_counts[i];
+  }
+  for (int s = 0; s < c.B; ++s) nreg[s] = b.pk_counts[b.image_of ? b.image_of[s] : s];
 }
 // the image half of a batch's argument checks; a bank batch's row index goes to idx[2B]
 int check_images(rau_ctx* ctx, const Batch& b, int32_t* idx) {
@@ -185,7 +217,9 @@ int enqueue_batch(rau_ctx* ctx, hipStream_t st, int si, const Batch& b) {
   if (b.n_images > 0) HIPC(hipMemcpyAsync(d.image_of_d, b.image_of, (size_t)c.B * 4, hipMemcpyHostToDevice, st));
   // pitched rows of another element size (4, 2 or 1 bytes) leave data in this type's pad columns: zero the
   // whole buffer first, on any change of type
-  if ((b.feats || b.bank_idx) && ctx->Sp != c.S && b.feat_type != d.held.feat_type)
+  // (a packed batch of B maps writes every pad column itself)
+  if ((b.feats || b.bank_idx) && ctx->Sp != c.S && b.feat_type != d.held.feat_type &&
+      !(b.pk_counts && maps == (size_t)c.B))
     HIPC(hipMemsetAsync(d.feats, 0, (size_t)c.B * c.D * ctx->Sp * sizeof(float), st));
   // bank batch (feats == nullptr): only the two row indices cross the bus; the table is gathered inside device
   // memory behind them, whole maps with their (zero) pad columns
@@ -197,7 +231,16 @@ int enqueue_batch(rau_ctx* ctx, hipStream_t st, int si, const Batch& b) {
            bank_gather(st, b.n_images, map_bytes, ctx->bank, ctx->bank_cap, d.bank_idx_d, d.feats));
     }
   }
-  if (b.feats && ctx->Sp == c.S)   // dense on both sides: one linear copy (a DMA-engine transfer, no blit kernel)
+  if (b.pk_counts) {
+    // packed rows: only sum(counts) * D elements cross the bus; the unpack writes whole maps, pad columns included,
+    // and the counts become the batch's region counts
+    HIPC(hipMemcpyAsync(d.pk_rows_d, b.feats, b.pk_rows * c.D * es, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d.pk_meta_d, b.pk_meta, 2 * maps * 4, hipMemcpyHostToDevice, st));
+    RUNS(st, "unpack_regions", 0, (double)(b.pk_rows * c.D + maps * c.D * ctx->Sp) * es,
+         unpack_regions(st, (int)maps, c.D, c.S, ctx->Sp, d.pk_rows_d, b.pk_rows, d.pk_meta_d, d.pk_meta_d + maps,
+                        d.feats, b.feat_type, b.feat_type));
+    HIPC(hipMemcpyAsync(d.nreg_d, b.pk_nreg, (size_t)c.B * 4, hipMemcpyHostToDevice, st));
+  } else if (b.feats && ctx->Sp == c.S)   // dense on both sides: one linear copy (a DMA-engine transfer, no blit kernel)
     HIPC(hipMemcpyAsync(d.feats, b.feats, maps * c.D * c.S * es, hipMemcpyHostToDevice, st));
   else if (b.feats)   // rows of S positions into rows of Sp (pad columns stay zero)
     HIPC(hipMemcpy2DAsync(d.feats, (size_t)ctx->Sp * es, b.feats, (size_t)c.S * es, (size_t)c.S * es,
@@ -223,7 +266,7 @@ void hold(rau_ctx* ctx, int si, const Batch& b) {
   d.have = true;
   d.have_labels = b.labels != nullptr;
   d.ans_G = 0;   // an answer set belongs to the batch it was given to
-  d.regions = false;   // ... and so do region counts
+  d.regions = b.pk_counts != nullptr;   // ... and so do region counts (a packed batch brings its own)
   d.att_targets = false;   // ... and attention targets
 }
 
@@ -236,6 +279,8 @@ void make_current(rau_ctx* ctx, int si) {
 int set_batch_sync(rau_ctx* ctx, Batch b) {
   const rau_config& c = ctx->cfg;
   std::vector<int32_t> bidx(b.bank_rows ? 2 * (size_t)c.B : 0);
+  if (b.pk_counts)
+    if (int rc = check_packed(c, b.n_images ? b.n_images : c.B, b.pk_counts, b.image_of, &b.pk_rows)) return rc;
   if (int rc = check_images(ctx, b, bidx.data())) return rc;
   const size_t TB = (size_t)c.T * c.B;
   std::vector<int32_t> utok(TB), ustart(TB + 1), upos(TB);
@@ -249,6 +294,15 @@ int set_batch_sync(rau_ctx* ctx, Batch b) {
   BatchSlot& s = ctx->slot[si];
   if (b.n_images)
     if (int rc = ensure_table(ctx, si, false, b.bank_rows != nullptr)) return rc;
+  std::vector<int32_t> pmeta, pnreg;
+  if (b.pk_counts) {
+    if (int rc = ensure_packed(ctx, si, false)) return rc;
+    pmeta.resize(2 * (size_t)c.B);
+    pnreg.resize((size_t)c.B);
+    fill_packed(c, b, pmeta.data(), pnreg.data());
+    b.pk_meta = pmeta.data();
+    b.pk_nreg = pnreg.data();
+  }
   if (s.upload_pending)   // an async upload into the same buffers
     HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
   if (int rc = enqueue_batch(ctx, ctx->st, si, b)) return rc;
@@ -265,15 +319,20 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   NEED(slot == 0 || slot == 1, "rau_set_batch_async: slot %d (0 or 1)", slot);
   const rau_config& c = ctx->cfg;
   std::vector<int32_t> bidx(b.bank_rows ? 2 * (size_t)c.B : 0);
+  if (b.pk_counts)
+    if (int rc = check_packed(c, b.n_images ? b.n_images : c.B, b.pk_counts, b.image_of, &b.pk_rows)) return rc;
   if (int rc = check_images(ctx, b, bidx.data())) return rc;
   if (int rc = ensure_async(ctx)) return rc;
   if (b.n_images)
     if (int rc = ensure_table(ctx, slot, true, b.bank_rows != nullptr)) return rc;
+  if (b.pk_counts)
+    if (int rc = ensure_packed(ctx, slot, true)) return rc;
   BatchSlot& s = ctx->slot[slot];
   if (slot == ctx->cur_slot && ctx->fwd_done)
     return fail(RAU_ERR_STATE, "rau_set_batch_async: slot %d is the current batch of a forward pass whose "
                 "backward has not run; upload into the other slot", slot);
-  const size_t TB = (size_t)c.T * c.B, nf = (size_t)(b.n_images ? b.n_images : c.B) * c.D * c.S;
+  const size_t TB = (size_t)c.T * c.B;
+  const size_t nf = b.pk_counts ? b.pk_rows * c.D : (size_t)(b.n_images ? b.n_images : c.B) * c.D * c.S;
   // The slot's previous upload may not have left its pinned staging yet: index_batch below rewrites the
   // pinned index arrays in every case, and the memcpys rewrite the rest, so wait for it either way.
   // (A caller that refills the staging IN PLACE must call rau_batch_slot(slot) before every refill:
@@ -289,6 +348,11 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   if (b.labels && b.labels != s.labels_h) std::memcpy(s.labels_h, b.labels, (size_t)c.B * 4);
   if (b.n_images) std::memcpy(s.image_of_h, b.image_of, (size_t)c.B * 4);
   if (b.bank_rows) std::memcpy(s.bank_idx_h, bidx.data(), 2 * (size_t)c.B * 4);
+  if (b.pk_counts) {   // (before image_of is re-pointed: both arrays still are the caller's)
+    fill_packed(c, b, s.pk_meta_h, s.nreg_h);
+    b.pk_meta = s.pk_meta_h;
+    b.pk_nreg = s.nreg_h;
+  }
   // from here on the batch is the staging's
   b.feats = b.bank_rows ? nullptr : s.feats_h;
   b.tokens = s.tokens_h;
@@ -309,6 +373,7 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   if (int rc = enqueue_batch(ctx, ctx->stc, slot, b)) return rc;
   HIPC(hipEventRecord(s.uploaded, ctx->stc));
   s.upload_pending = true;
+  if (b.pk_counts) s.reg_pending = true;   // a copy out of nreg_h is behind this record
   hold(ctx, slot, b);
   if (slot == ctx->cur_slot) {   // re-filled in place: the next forward waits for the copies
     make_current(ctx, slot);
@@ -376,12 +441,69 @@ int ensure_att_targets(rau_ctx* ctx, int si) {
   return RAU_OK;
 }
 
+// first packed batch of a slot: the device staging of the raw rows (sized for the capacity and the widest element),
+// the off | cnt arrays, the region counts; pinned staging of the small arrays on the asynchronous path
+int ensure_packed(rau_ctx* ctx, int si, bool pinned) {
+  const rau_config& c = ctx->cfg;
+  const size_t cap = (size_t)ctx->cap;
+  BatchSlot& s = ctx->slot[si];
+  if (int rc = ensure_regions(ctx, si)) return rc;
+  if (!s.pk_meta_d)
+    if (int rc = dalloc(ctx, &s.pk_meta_d, 2 * cap)) return rc;
+  if (pinned && !s.pk_meta_h) {
+    void* h = nullptr;
+    hipError_t e = hipHostMalloc(&h, 2 * cap * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(packed offsets staging): %s", hipGetErrorString(e));
+    s.pk_meta_h = static_cast<int32_t*>(h);
+  }
+  if (!s.pk_rows_d) {
+    float* d = nullptr;   // (not scratch: every packed batch overwrites what it reads)
+    if (int rc = dalloc(ctx, &d, cap * c.S * c.D, false)) {
+      (void)hipGetLastError();   // the failed allocation is reported here, not by the next launch
+      return rc;
+    }
+    s.pk_rows_d = d;
+    // dalloc clears the block on the chain stream; the slot form copies into it on the copy stream.  Once per slot.
+    HIPC(hipStreamSynchronize(ctx->st));
+  }
+  return RAU_OK;
+}
+
 // Every enqueued reader of the bank (the gathers: copy stream and chain stream) has finished.
 int bank_quiesce(rau_ctx* ctx) {
   if (ctx->stc) HIPC(hipStreamSynchronize(ctx->stc));
   HIPC(hipStreamSynchronize(ctx->st));
   return RAU_OK;
 }
+// rau_bank_put's two pinned staging halves with their events and, where a kernel reads the chunk (`stage`), the
+// device block it is copied to
+int ensure_bank_staging(rau_ctx* ctx, bool stage) {
+  const rau_config& c = ctx->cfg;
+  if (!ctx->bank_chunk) {   // staging sized for f32 sources: 32 MiB, at least one map
+    const size_t chunk = std::max<size_t>((size_t)32 << 20, (size_t)c.D * c.S * 4);
+    for (int k = 0; k < 2; ++k) {
+      if (!ctx->bank_pin[k]) {
+        hipError_t e = hipHostMalloc(&ctx->bank_pin[k], chunk, hipHostMallocDefault);
+        if (e != hipSuccess) {
+          ctx->bank_pin[k] = nullptr;
+          return fail(RAU_ERR_NOMEM, "rau_bank_put: hipHostMalloc(%zu bytes staging): %s", chunk, hipGetErrorString(e));
+        }
+      }
+      if (!ctx->bank_ev[k]) HIPC(hipEventCreateWithFlags(&ctx->bank_ev[k], hipEventDisableTiming));
+    }
+    ctx->bank_chunk = chunk;
+  }
+  if (stage && !ctx->bank_stage) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->bank_stage), ctx->bank_chunk);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->bank_stage = nullptr;
+      return fail(RAU_ERR_NOMEM, "rau_bank_put: hipMalloc(%zu bytes staging): %s", ctx->bank_chunk, hipGetErrorString(e));
+    }
+  }
+  return RAU_OK;
+}
+constexpr int kBankPackMaps = 4096;   // maps per chunk of rau_bank_put_packed (their off | cnt arrays)
 size_t bank_map_bytes(const rau_ctx* ctx) {
   return (size_t)ctx->cfg.D * ctx->Sp * feat_elem_bytes(ctx->bank_type);
 }
@@ -440,6 +562,19 @@ int rau_set_batch_bank(rau_ctx* ctx, int n_images, const int32_t* bank_rows, con
   return set_batch_sync(ctx, Batch{nullptr, ctx->bank_type, n_images, image_of, tokens, lens, labels, bank_rows});
 }
 
+// n_maps maps of counts[i] rows each; image_of == NULL: the plain batch, one map per sample
+int rau_set_batch_packed(rau_ctx* ctx, const void* rows, int feat_type, int n_maps, const int32_t* counts,
+                         const int32_t* image_of, const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
+  NEED(ctx && rows && tokens && lens, "null argument");
+  NEED(feat_type_ok(feat_type), "rau_set_batch_packed: feat_type %d (" RAU_FEAT_TYPE_LIST ")", feat_type);
+  NEED(counts, "rau_set_batch_packed: null counts");
+  NEED(n_maps >= 1 && n_maps <= ctx->cfg.B, "rau_set_batch_packed: n_maps=%d out of [1,%d]", n_maps, ctx->cfg.B);
+  NEED(image_of || n_maps == ctx->cfg.B, "rau_set_batch_packed: n_maps=%d without image_of (a plain batch has %d maps)",
+       n_maps, ctx->cfg.B);
+  return set_batch_sync(ctx, Batch{rows, feat_type, image_of ? n_maps : 0, image_of, tokens, lens, labels, nullptr,
+                                   counts});
+}
+
 int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_host,
                    int32_t** lens_host, int32_t** labels_host) {
   NEED(ctx, "null ctx");
@@ -485,6 +620,21 @@ int rau_set_batch_async_bank(rau_ctx* ctx, int slot, int n_images, const int32_t
   if (int rc = need_bank(ctx, "rau_set_batch_async_bank", bank_rows)) return rc;
   return set_batch_slot(ctx, slot,
                         Batch{nullptr, ctx->bank_type, n_images, image_of, tokens, lens, labels, bank_rows},
+                        has_labels);
+}
+
+// rows == NULL: the slot's pinned staging already holds the sum(counts) * D elements at its start
+int rau_set_batch_async_packed(rau_ctx* ctx, int slot, const void* rows, int feat_type, int n_maps,
+                               const int32_t* counts, const int32_t* image_of, const int32_t* tokens,
+                               const int32_t* lens, const int32_t* labels, int has_labels) {
+  NEED(ctx, "null ctx");
+  NEED(feat_type_ok(feat_type), "rau_set_batch_async_packed: feat_type %d (" RAU_FEAT_TYPE_LIST ")", feat_type);
+  NEED(counts, "rau_set_batch_async_packed: null counts");
+  NEED(n_maps >= 1 && n_maps <= ctx->cfg.B, "rau_set_batch_async_packed: n_maps=%d out of [1,%d]", n_maps, ctx->cfg.B);
+  NEED(image_of || n_maps == ctx->cfg.B,
+       "rau_set_batch_async_packed: n_maps=%d without image_of (a plain batch has %d maps)", n_maps, ctx->cfg.B);
+  return set_batch_slot(ctx, slot, Batch{rows, feat_type, image_of ? n_maps : 0, image_of, tokens, lens, labels,
+                                         nullptr, counts},
                         has_labels);
 }
 
@@ -755,11 +905,15 @@ int rau_bank_destroy(rau_ctx* ctx) {
   }
   hipFree(ctx->bank);
   if (ctx->bank_stage) hipFree(ctx->bank_stage);
+  if (ctx->bank_meta_d) hipFree(ctx->bank_meta_d);
+  ctx->bank_meta_d = nullptr;
   for (int k = 0; k < 2; ++k) {
     if (ctx->bank_pin[k]) hipHostFree(ctx->bank_pin[k]);
     if (ctx->bank_ev[k]) hipEventDestroy(ctx->bank_ev[k]);
+    if (ctx->bank_meta_pin[k]) hipHostFree(ctx->bank_meta_pin[k]);
     ctx->bank_pin[k] = nullptr;
     ctx->bank_ev[k] = nullptr;
+    ctx->bank_meta_pin[k] = nullptr;
   }
   ctx->bank = nullptr;
   ctx->bank_stage = nullptr;
@@ -792,28 +946,7 @@ int rau_bank_put(rau_ctx* ctx, int32_t first, int32_t count, const void* feats, 
   const bool narrow = src_type != ctx->bank_type;
   const size_t ses = feat_elem_bytes(src_type), src_map = (size_t)c.D * c.S * ses, map_bytes = bank_map_bytes(ctx);
   const size_t bes = feat_elem_bytes(ctx->bank_type);
-  if (!ctx->bank_chunk) {   // staging sized for f32 sources: 32 MiB, at least one map
-    const size_t chunk = std::max<size_t>((size_t)32 << 20, (size_t)c.D * c.S * 4);
-    for (int k = 0; k < 2; ++k) {
-      if (!ctx->bank_pin[k]) {
-        hipError_t e = hipHostMalloc(&ctx->bank_pin[k], chunk, hipHostMallocDefault);
-        if (e != hipSuccess) {
-          ctx->bank_pin[k] = nullptr;
-          return fail(RAU_ERR_NOMEM, "rau_bank_put: hipHostMalloc(%zu bytes staging): %s", chunk, hipGetErrorString(e));
-        }
-      }
-      if (!ctx->bank_ev[k]) HIPC(hipEventCreateWithFlags(&ctx->bank_ev[k], hipEventDisableTiming));
-    }
-    ctx->bank_chunk = chunk;
-  }
-  if (narrow && !ctx->bank_stage) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->bank_stage), ctx->bank_chunk);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->bank_stage = nullptr;
-      return fail(RAU_ERR_NOMEM, "rau_bank_put: hipMalloc(%zu bytes staging): %s", ctx->bank_chunk, hipGetErrorString(e));
-    }
-  }
+  if (int rc = ensure_bank_staging(ctx, narrow)) return rc;
   if (int rc = bank_quiesce(ctx)) return rc;   // enqueued gathers read the rows being replaced
   const int32_t per = (int32_t)std::min<size_t>(ctx->bank_chunk / src_map, (size_t)count);
   hipStream_t st = ctx->st;
@@ -837,6 +970,77 @@ int rau_bank_put(rau_ctx* ctx, int32_t first, int32_t count, const void* feats, 
     }
     HIPC(hipEventRecord(ctx->bank_ev[k], st));
     used[k] = true;
+  }
+  HIPC(hipStreamSynchronize(st));
+  for (int32_t r = first; r < first + count; ++r)
+    if (!ctx->bank_written[r]) { ctx->bank_written[r] = 1; ++ctx->bank_filled; }
+  ctx->x_valid = false;   // an expansion made from replaced rows is stale
+  return RAU_OK;
+}
+
+// rau_bank_put for packed region rows: map first + i owns counts[i] rows of `rows`.  Chunks of whole maps go
+// through the pinned staging into the device staging, and unpack_regions writes them into the bank's rows, dense
+// and zero behind each count (narrowing f32 on the way where the bank is narrower).
+int rau_bank_put_packed(rau_ctx* ctx, int32_t first, int32_t count, const void* rows, int src_type,
+                        const int32_t* counts) {
+  NEED(ctx && rows && counts, "null argument");
+  if (!ctx->bank) return fail(RAU_ERR_STATE, "rau_bank_put_packed: the context has no feature bank (rau_bank_create)");
+  NEED(feat_type_ok(src_type), "rau_bank_put_packed: src_type %d (" RAU_FEAT_TYPE_LIST ")", src_type);
+  NEED(src_type == ctx->bank_type || src_type == RAU_FEAT_F32,
+       "rau_bank_put_packed: rows of type %d into a bank of type %d (equal types, or f32 into a 16-bit or fp8 bank)",
+       src_type, ctx->bank_type);
+  NEED(first >= 0 && count >= 1 && (int64_t)first + count <= ctx->bank_cap,
+       "rau_bank_put_packed: rows [%d,%d) out of [0,%d)", first, first + count, ctx->bank_cap);
+  const rau_config& c = ctx->cfg;
+  for (int32_t i = 0; i < count; ++i)
+    NEED(counts[i] >= 1 && counts[i] <= c.S, "rau_bank_put_packed: counts[%d]=%d out of [1,%d]", i, counts[i], c.S);
+  if (int rc = ensure_bank_staging(ctx, true)) return rc;
+  for (int k = 0; k < 2; ++k)
+    if (!ctx->bank_meta_pin[k]) {
+      void* h = nullptr;
+      hipError_t e = hipHostMalloc(&h, 2 * (size_t)kBankPackMaps * 4, hipHostMallocDefault);
+      if (e != hipSuccess)
+        return fail(RAU_ERR_NOMEM, "rau_bank_put_packed: hipHostMalloc(offsets staging): %s", hipGetErrorString(e));
+      ctx->bank_meta_pin[k] = static_cast<int32_t*>(h);
+    }
+  if (!ctx->bank_meta_d) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->bank_meta_d), 2 * (size_t)kBankPackMaps * 4);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->bank_meta_d = nullptr;
+      return fail(RAU_ERR_NOMEM, "rau_bank_put_packed: hipMalloc(offsets): %s", hipGetErrorString(e));
+    }
+  }
+  if (int rc = bank_quiesce(ctx)) return rc;   // enqueued gathers read the rows being replaced
+  const size_t row_bytes = (size_t)c.D * feat_elem_bytes(src_type), map_bytes = bank_map_bytes(ctx);
+  const size_t chunk_rows = ctx->bank_chunk / row_bytes;   // >= S: the staging holds at least one f32 map
+  hipStream_t st = ctx->st;
+  bool used[2] = {false, false};
+  int k = 0;
+  const char* src = static_cast<const char*>(rows);
+  for (int32_t i0 = 0; i0 < count; k ^= 1) {
+    if (used[k]) HIPC(hipEventSynchronize(ctx->bank_ev[k]));   // the staging's last copies have left it
+    int32_t* meta = ctx->bank_meta_pin[k];
+    int32_t n = 0;
+    size_t nrows = 0;
+    while (i0 + n < count && n < kBankPackMaps && nrows + (size_t)counts[i0 + n] <= chunk_rows) {
+      meta[n] = (int32_t)nrows;
+      nrows += (size_t)counts[i0 + n];
+      ++n;
+    }
+    for (int32_t i = 0; i < n; ++i) meta[n + i] = counts[i0 + i];
+    std::memcpy(ctx->bank_pin[k], src, nrows * row_bytes);
+    char* dst = static_cast<char*>(ctx->bank) + (size_t)(first + i0) * map_bytes;
+    // (one device staging: the stream orders the next chunk's copies behind this chunk's kernel)
+    HIPC(hipMemcpyAsync(ctx->bank_stage, ctx->bank_pin[k], nrows * row_bytes, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(ctx->bank_meta_d, meta, 2 * (size_t)n * 4, hipMemcpyHostToDevice, st));
+    RUN("unpack_regions", 0, (double)(nrows * row_bytes + (size_t)n * map_bytes),
+        unpack_regions(st, n, c.D, c.S, ctx->Sp, ctx->bank_stage, nrows, ctx->bank_meta_d, ctx->bank_meta_d + n, dst,
+                       src_type, ctx->bank_type));
+    HIPC(hipEventRecord(ctx->bank_ev[k], st));
+    used[k] = true;
+    src += nrows * row_bytes;
+    i0 += n;
   }
   HIPC(hipStreamSynchronize(st));
   for (int32_t r = first; r < first + count; ++r)

@@ -127,6 +127,13 @@ struct BatchSlot {
   float* att_t_d = nullptr;
   float* att_t_h = nullptr;
   bool att_pending = false;         // a copy out of att_t_h is behind the last record of `uploaded`
+  // packed region rows (rau_set_batch_packed): the raw rows [sum(counts)][D] land in pk_rows_d (room for
+  // [capacity * S][D] floats) and unpack_regions transposes them into `feats`; pk_meta_d holds off[n_maps] |
+  // cnt[n_maps] (room for 2 * capacity), pk_meta_h is its pinned staging on the asynchronous path.  Allocated at
+  // the slot's first packed batch.
+  void* pk_rows_d = nullptr;
+  int32_t* pk_meta_d = nullptr;
+  int32_t* pk_meta_h = nullptr;
   hipEvent_t uploaded = nullptr;    // recorded on the copy stream behind the slot's H2D copies
   hipEvent_t consumed = nullptr;    // recorded on the chain stream when the ctx switches away from the slot
   // ---- what the device buffers hold
@@ -283,6 +290,9 @@ struct rau_ctx {
   void* bank_pin[2] = {nullptr, nullptr};   // pinned staging of rau_bank_put, bank_chunk bytes each
   float* bank_stage = nullptr;              // device: one chunk of f32 maps on their way to a 16-bit bank
   size_t bank_chunk = 0;
+  // rau_bank_put_packed: off | cnt of one chunk's maps (kBankPackMaps each), device and pinned per staging half
+  int32_t* bank_meta_d = nullptr;
+  int32_t* bank_meta_pin[2] = {nullptr, nullptr};
   hipEvent_t bank_ev[2] = {nullptr, nullptr};
   // the two batch slots; the synchronous path uploads into the current one
   BatchSlot slot[2];

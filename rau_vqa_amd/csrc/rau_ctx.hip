@@ -609,6 +609,7 @@ void rau_destroy(rau_ctx* ctx) {
     if (s.ans_h) hipHostFree(s.ans_h);
     if (s.nreg_h) hipHostFree(s.nreg_h);
     if (s.att_t_h) hipHostFree(s.att_t_h);
+    if (s.pk_meta_h) hipHostFree(s.pk_meta_h);
     if (s.uploaded) hipEventDestroy(s.uploaded);
     if (s.consumed) hipEventDestroy(s.consumed);
   }

@@ -135,3 +135,31 @@ def store(dst: np.ndarray, src, feat_type=None) -> None:
         dst[...] = src if src.dtype == np.uint16 else bf16_bits(src.astype(np.float32)).reshape(dst.shape)
     else:
         dst[...] = src
+
+
+def check_counts(counts, S: int) -> np.ndarray:
+    """Region counts of a packed batch as a 1-D int32 array: every entry in 1..S."""
+    n = np.asarray(counts)
+    if n.ndim != 1 or n.size < 1 or not np.issubdtype(n.dtype, np.integer):
+        raise ValueError(f"counts: a 1-D integer array with at least one entry, not {n.dtype}{n.shape}")
+    if n.min() < 1 or n.max() > S:
+        raise ValueError(f"counts must lie in 1..S={S}: got {int(n.min())}..{int(n.max())}")
+    return np.ascontiguousarray(n, np.int32)
+
+
+def unpack_regions(rows, counts, S: int) -> np.ndarray:
+    """Packed region rows -> dense maps: THE contract of the packed entry points.
+
+    rows [sum(counts), D] in any element type (float32, float16, uint16 or uint8 codes), counts [N] with
+    1 <= counts[i] <= S.  -> dense [N, D, S] of the same dtype with dense[i, :, s] = rows[off[i] + s, :] for
+    s < counts[i], off the exclusive prefix sum; every other element has all bits zero (+0 in every type)."""
+    n = check_counts(counts, S)
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[0] != int(n.sum()):
+        raise ValueError(f"rows {rows.shape}: expected [sum(counts)={int(n.sum())}, D]")
+    dense = np.zeros((n.size, rows.shape[1], S), rows.dtype)
+    off = 0
+    for i, c in enumerate(n):
+        dense[i, :, :c] = rows[off:off + c].T
+        off += int(c)
+    return dense

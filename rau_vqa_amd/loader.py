@@ -80,6 +80,7 @@ class DataClass:
         self._job = None          # (key, thread, result holder)
         self._next_dest = None    # SlotFeeder: where the prefetch worker assembles the next batch
         self._unique = False      # the last next_batch_feat asked for an image table: so will the prefetched one
+        self._packed = False      # ... for packed region rows: so will the prefetched one
         self._bank = None         # (key, files, row of every question): bank_rows' answer for one tab_featpaths
         self.last_answers = None  # (ids, w[, score]) rows of the batch last taken, when qs carries answer sets
         self.last_regions = None  # [B] per-sample region counts of the batch last taken, when qs carries img_regions
@@ -154,50 +155,85 @@ class DataClass:
             feat16.store(out[i], t7.load_feature(p, D, W, H, keep_half).reshape(D, W, H), feat_type)
         return out
 
+    @staticmethod
+    def _load_rows(paths, D, S, out=None, feat_type="f32"):
+        """Per-image region files [n, D] (t7.load_regions) -> (rows [sum(n), D] of feat_type, counts [len(paths)]
+        int32): every file read once, the rows concatenated without padding or transposing.  `out` = a caller-owned
+        destination (the pinned staging of an upload slot) whose start takes the rows and whose dtype decides.
+        n above S (the context's position count) is an error."""
+        dt = feat16.dtype_of(feat_type) if out is None else out.dtype
+        keep_half = dt != np.float32
+        maps = [t7.load_regions(p, D, keep_half) for p in paths]
+        counts = np.array([m.shape[0] for m in maps], np.int32)
+        if counts.max() > S:
+            raise ValueError(f"a region file holds {int(counts.max())} boxes, above S={S}")
+        total = int(counts.sum())
+        if out is None:
+            rows = np.empty((total, D), dt)
+        else:
+            if out.size < total * D:
+                raise ValueError("the packed rows do not fit the destination")
+            rows = out.reshape(-1)[:total * D].reshape(total, D)
+        off = 0
+        for m in maps:
+            feat16.store(rows[off:off + m.shape[0]], m, feat_type)
+            off += m.shape[0]
+        return rows, counts
+
     def _start_prefetch(self, tab_featpaths, D, W, H):
         paths = self._paths(self.batch_index, tab_featpaths)
         holder = {}
         dest = self._next_dest() if self._next_dest is not None else None
-        unique = self._unique
+        unique, packed = self._unique, self._packed
         files = self._image_table(paths)[0] if unique else paths
 
         def work():
             try:
-                holder["feats"] = self._load_feats(files, D, W, H, dest, self.feat_type)
+                if packed:
+                    holder["feats"] = self._load_rows(files, D, W * H, dest, self.feat_type)
+                else:
+                    holder["feats"] = self._load_feats(files, D, W, H, dest, self.feat_type)
             except Exception as e:   # surfaced on the consumer side
                 holder["error"] = e
         th = threading.Thread(target=work, daemon=True)
         th.start()
-        self._job = ((self.batch_index, tuple(paths), unique), th, holder)
+        self._job = ((self.batch_index, tuple(paths), unique, packed), th, holder)
 
-    def next_batch_feat(self, tab_featpaths, feat_dim, feat_w=1, feat_h=1, unique=False):
+    def next_batch_feat(self, tab_featpaths, feat_dim, feat_w=1, feat_h=1, unique=False, packed=False):
         """-> feats [B,D,W,H] (f32, or the 16-bit / fp8 feat_type), x [T,B] i32, x_len [B] i32, a [B] | [B,nMC] i32, qids [B].
         unique=True: every distinct feature file of the batch is read once, in order of first appearance;
         feats is that image table [N,D,W,H] and image_of [B] i32 (0-based table rows) is appended to the
-        tuple: feats[image_of] is what unique=False returns."""
+        tuple: feats[image_of] is what unique=False returns.
+        packed=True: the files are region files [n_boxes, D] (t7.load_regions), n_boxes <= feat_w * feat_h; every
+        file is read once and the rows are concatenated without padding: -> rows [sum(counts), D], counts [B] (with
+        unique=True: [N], per image), x, x_len, a, qids (and image_of).  feat16.unpack_regions(rows, counts, S) is
+        the feats of the dense files of the same boxes; RAU.set_batch_packed / loader.feed take the tuple."""
         if isinstance(tab_featpaths, (str, os.PathLike)):
             tab_featpaths = [tab_featpaths]
         B = self.batch_size
         idx = self.batch_order[self.batch_index:self.batch_index + B]
         paths = self._paths(self.batch_index, tab_featpaths)
         files, image_of = self._image_table(paths) if unique else (paths, None)
-        self._unique = bool(unique)
+        self._unique, self._packed = bool(unique), bool(packed)
         feats = None
         if self.opt_prefetch and self._job is not None:
             key, th, holder = self._job
             th.join()                                    # pool:synchronize()
             if "error" in holder:
                 raise holder["error"]
-            if key == (self.batch_index, tuple(paths), bool(unique)):
+            if key == (self.batch_index, tuple(paths), bool(unique), bool(packed)):
                 feats = holder["feats"]
-        if feats is None:
+        if feats is None and packed:
+            feats = self._load_rows(files, feat_dim, feat_w * feat_h, feat_type=self.feat_type)
+        elif feats is None:
             feats = self._load_feats(files, feat_dim, feat_w, feat_h, feat_type=self.feat_type)
         x, x_len, a, qids = self._take(idx)
         if self.opt_prefetch:
             self._start_prefetch(tab_featpaths, feat_dim, feat_w, feat_h)
+        head = feats if packed else (feats,)              # packed: (rows, counts)
         if unique:
-            return feats, x, x_len, a, qids, image_of
-        return feats, x, x_len, a, qids
+            return (*head, x, x_len, a, qids, image_of)
+        return (*head, x, x_len, a, qids)
 
     def _take(self, idx):
         """The question side of the batch `idx` (x, x_len, a, qids), and the step to the next batch."""
@@ -241,17 +277,34 @@ class DataClass:
             self._bank = (key, files, row_of, qrow)
         return list(self._bank[1]), dict(self._bank[2])
 
-    def fill_bank(self, rau, tab_featpaths, feat_dim, feat_w=1, feat_h=1, chunk=64):
+    def fill_bank(self, rau, tab_featpaths, feat_dim, feat_w=1, feat_h=1, chunk=64, packed=False):
         """Reads every distinct feature file of the split ONCE and puts it into rau's bank at its
         bank_rows row, `chunk` files per rau.bank_put.  f32 files go up as f32 whatever the bank's type
         (a 16-bit or fp8 bank narrows them on the device: for fp8, round to nearest even, saturating at the
         largest finite value); HalfTensor files go into an fp16 bank as they are.
-        -> number of rows written."""
+        -> number of rows written.
+        packed=True: the files are region files [n_boxes, D]; they go up as packed rows (rau.bank_put_packed: no
+        host transpose, no padding on the link) and the bank keeps the dense maps.  The bank stores no counts, so
+        this also fills the QuestionSet's img_regions (one count per image of the name list, 1 where the split
+        never asks about the image) and -> that array: next_batch_rows then leaves per-sample counts in
+        last_regions, as for any QuestionSet with img_regions."""
         files, _ = self.bank_rows(tab_featpaths)
         info = rau.bank_info()
         if info["capacity"] < len(files):
             raise ValueError(f"bank of {info['capacity']} maps < {len(files)} distinct images")
         keep_half = info["feat_type"] == "f16"
+        if packed:
+            per_row = np.empty(len(files), np.int32)
+            for r0 in range(0, len(files), max(int(chunk), 1)):
+                maps = [t7.load_regions(p, feat_dim, keep_half) for p in files[r0:r0 + max(int(chunk), 1)]]
+                half = all(m.dtype == np.float16 for m in maps)
+                counts = np.array([m.shape[0] for m in maps], np.int32)
+                rau.bank_put_packed(r0, np.concatenate([m if half else m.astype(np.float32) for m in maps]), counts)
+                per_row[r0:r0 + len(maps)] = counts
+            regions = np.ones(len(self.img_names), np.int32)
+            regions[np.asarray(self.qs.img_list) - 1] = per_row[self._bank[3]]
+            self.qs.img_regions = regions
+            return regions
         for r0 in range(0, len(files), max(int(chunk), 1)):
             maps = [t7.load_feature(p, feat_dim, feat_w, feat_h, keep_half) for p in files[r0:r0 + max(int(chunk), 1)]]
             half = all(m.dtype == np.float16 for m in maps)
@@ -328,7 +381,8 @@ def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=12
 def feed(rau, batch, feat_type=None, answers=None, regions=None, att_targets=None):
     """next_batch_feat's tuple -> rau_set_batch (the H2D of SS:434-439); returns qids.
     feat_type: that of the feats (needed for bf16 and fp8, which arrive as uint16 / uint8 bits).  A tuple of
-    next_batch_feat(unique=True) goes up as an image table, one of next_batch_rows as a bank batch.
+    next_batch_feat(unique=True) goes up as an image table, one of next_batch_rows as a bank batch, one of
+    next_batch_feat(packed=True) as packed region rows (set_batch_packed: its counts are the batch's regions).
     The batch may be smaller than the context's capacity (a test split at test_batch_size): set_batch
     takes the size from x_len and switches the context to it.
     answers = (ids, w[, score]) rows of the batch (DataClass.last_answers, when its QuestionSet has ans_ids /
@@ -369,6 +423,11 @@ def _feed_batch(rau, batch, feat_type):
         rows, image_of, x, x_len, a, qids = batch
         rau.set_batch(None, x, x_len, a if a.ndim == 1 else None, bank_rows=rows, image_of=image_of)
         return qids
+    if batch[0].ndim == 2:                                # next_batch_feat(packed=True): rows, counts, x, x_len, a, qids
+        rows, counts, x, x_len, a, qids = batch[:6]
+        rau.set_batch_packed(rows, counts, x, x_len, a if a.ndim == 1 else None, feat_type=feat_type,
+                             image_of=batch[6] if len(batch) > 6 else None)
+        return qids
     feats, x, x_len, a, qids = batch[:5]
     image_of = batch[5] if len(batch) > 5 else None
     B, D = feats.shape[0], feats.shape[1]                 # (image table: B is its number of maps)
@@ -400,7 +459,7 @@ class SlotFeeder:
     """
 
     def __init__(self, rau, data: DataClass, tab_featpaths, feat_dim, feat_w=1, feat_h=1,
-                 feat_type=None, share_images=False, bank=False):
+                 feat_type=None, share_images=False, bank=False, packed=False):
         self.rau, self.data = rau, data
         self.n = int(data.batch_size)
         if getattr(rau, "batch_size", self.n) != self.n:
@@ -411,6 +470,11 @@ class SlotFeeder:
         # every distinct image of a batch is read, staged and uploaded once (next_batch_feat(unique=True));
         # the worker fills the first N maps of the slot's staging
         self.share_images = bool(share_images)
+        # packed=True: the files are region files [n_boxes, D]; the worker concatenates their rows at the start of
+        # the slot's staging (no transpose, no padding) and the device unpacks them (rau_set_batch_async_packed)
+        self.packed = bool(packed)
+        if self.packed and self.bank:
+            raise ValueError("a bank feeder has no feature staging to pack (fill_bank(packed=True) fills the bank)")
         self.args = (tab_featpaths, feat_dim, feat_w, feat_h)
         self.slot = 0                  # the slot the NEXT batch is assembled in
         # element type of the maps in the staging and on the wire (default: the DataClass's)
@@ -442,9 +506,15 @@ class SlotFeeder:
                 rau.set_regions(d.last_regions, slot=s)
             rau.use_batch(s)
             return qids
-        batch = d.next_batch_feat(*self.args, unique=self.share_images)
-        feats, x, x_len, a, qids = batch[:5]
-        table = {"image_of": batch[5], "n_images": feats.shape[0]} if self.share_images else {}
+        batch = d.next_batch_feat(*self.args, unique=self.share_images, packed=self.packed)
+        if self.packed:
+            feats, counts, x, x_len, a, qids = batch[:6]
+            table = {"packed_counts": counts}
+            if self.share_images:
+                table["image_of"] = batch[6]
+        else:
+            feats, x, x_len, a, qids = batch[:5]
+            table = {"image_of": batch[5], "n_images": feats.shape[0]} if self.share_images else {}
         if not np.shares_memory(feats, view["feats"]):   # first batch / a re-drawn order: not prefetched in place
             stage = view["feats"].reshape(-1)[:feats.size]
             feat16.store(stage, feats.reshape(stage.shape), self.feat_type)
@@ -456,8 +526,8 @@ class SlotFeeder:
         rau.set_batch_async(s, has_labels=labels, **table, **self._ft)   # staging filled in place: no host copy
         if d.last_answers is not None:                # the QuestionSet carries answer sets: behind the upload
             rau.set_answers(*d.last_answers, slot=s)
-        if d.last_regions is not None:                # ... and region counts: per sample, also for an image table
-            rau.set_regions(d.last_regions, slot=s)
+        if d.last_regions is not None and not self.packed:   # ... and region counts: per sample, also for an image
+            rau.set_regions(d.last_regions, slot=s)          # table (a packed batch brought its own)
         rau.use_batch(s)
         return qids
 

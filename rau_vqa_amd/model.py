@@ -265,6 +265,20 @@ class RAU:
             raise ValueError("bank_put: feats is not [n, D, S]")
         L.check(self._lib.rau_bank_put(self._h, int(first), n, feats.ctypes.data, feat16.FEAT_TYPES[ft]))
 
+    def bank_put_packed(self, first, rows, counts, feat_type=None):
+        """Packed region rows [sum(counts), D] into bank rows first .. first+len(counts)-1: map i gets its
+        counts[i] rows transposed and zero bits behind them (feat16.unpack_regions), on the device.  The type
+        pairs of bank_put: rows of the bank's type are moved, f32 rows into a narrower bank are narrowed on the
+        way with bank_put's bits.  The bank keeps dense maps and no counts: keep them (QuestionSet.img_regions)
+        and pass regions= with the bank batch."""
+        c = self.cfg
+        counts = feat16.check_counts(counts, c.S)
+        rows, ft = feat16.as_feats(rows, feat_type)
+        if rows.ndim != 2 or rows.shape != (int(counts.sum()), c.D):
+            raise ValueError(f"bank_put_packed: rows {rows.shape} is not [sum(counts)={int(counts.sum())}, D={c.D}]")
+        L.check(self._lib.rau_bank_put_packed(self._h, int(first), int(counts.size), rows.ctypes.data,
+                                              feat16.FEAT_TYPES[ft], counts.ctypes.data))
+
     def bank_get(self, first, count):
         """Rows first .. first+count-1 as [count, D, S] in the bank's element type (bf16: uint16 bits; fp8: uint8 codes)."""
         c = self.cfg
@@ -432,6 +446,52 @@ class RAU:
         if att_targets is not None:
             self.set_att_targets(att_targets)
 
+    def _packed(self, rows, counts, image_of, B, feat_type):
+        """(rows or None, feat type, n_maps, counts, image_of or None) of a packed batch of B samples, checked on
+        the host: counts [n_maps] in 1..S, rows [sum(counts), D] (None: already in the slot's staging), n_maps == B
+        unless image_of [B] names the maps."""
+        c = self.cfg
+        counts = feat16.check_counts(counts, c.S)
+        if image_of is not None:
+            image_of = np.ascontiguousarray(image_of, np.int32)
+            if image_of.shape != (B,):
+                raise ValueError("image_of must have one entry per sample")
+        elif counts.size != B:
+            raise ValueError(f"a packed batch without image_of needs one count per sample: {counts.size} != {B}")
+        if rows is None:
+            return None, feat16.check_name(feat_type or "f32"), int(counts.size), counts, image_of
+        rows, ft = feat16.as_feats(rows, feat_type)
+        if rows.ndim != 2 or rows.shape != (int(counts.sum()), c.D):
+            raise ValueError(f"packed rows {rows.shape} are not [sum(counts)={int(counts.sum())}, D={c.D}]")
+        return rows, ft, int(counts.size), counts, image_of
+
+    def set_batch_packed(self, rows, counts, tokens, lens, labels=None, feat_type=None, image_of=None):
+        """A batch of region features as the files store them: rows [sum(counts), D], one row per box, map i
+        owning counts[i] consecutive rows (1..S).  Only the rows cross the link; the device transposes and
+        zero-pads them and the counts become the batch's region counts.  The same results, bit for bit, as
+        set_batch(feat16.unpack_regions(rows, counts, S), ..., regions=counts).  image_of [B]: the maps are an
+        image table of len(counts) maps (counts per IMAGE).  feat_type as in set_batch."""
+        c = self.cfg
+        lens = np.ascontiguousarray(lens, np.int32)
+        B = self._rows(lens, "set_batch_packed")
+        rows, ft, n_maps, counts, image_of = self._packed(rows, counts, image_of, B, feat_type)
+        if rows is None:
+            raise ValueError("set_batch_packed needs rows")
+        tokens = np.ascontiguousarray(tokens, np.int32)
+        if tokens.shape != (c.T, B):
+            raise ValueError("batch shapes do not match the config")
+        lp = None
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, np.int32)
+            if labels.shape != (B,):
+                raise ValueError("labels shape")
+            lp = labels.ctypes.data
+        if B != self._n:
+            self.set_batch_size(B)
+        L.check(self._lib.rau_set_batch_packed(self._h, rows.ctypes.data, feat16.FEAT_TYPES[ft], n_maps,
+                                               counts.ctypes.data, None if image_of is None else image_of.ctypes.data,
+                                               tokens.ctypes.data, lens.ctypes.data, lp))
+
     def _set_batch(self, feats, tokens, lens, labels, feat_type, image_of, bank_rows):
         c = self.cfg
         lens = np.ascontiguousarray(lens, np.int32)
@@ -513,7 +573,7 @@ class RAU:
 
     def set_batch_async(self, slot, feats=None, tokens=None, lens=None, labels=None, has_labels=True,
                         feat_type=None, image_of=None, n_images=None, bank_rows=None, answers=None,
-                        regions=None, att_targets=None):
+                        regions=None, att_targets=None, packed_counts=None):
         """Enqueue the upload of a batch into `slot` on the copy stream and return.  Arrays left None
         are taken from the slot's staging (filled in place through batch_slot).  feat_type: as in
         set_batch; with feats None it names what the staging holds (default "f32").
@@ -524,14 +584,19 @@ class RAU:
         drops both slots' earlier uploads), else the current batch_size.
         answers = (ids, w[, score]): set_answers(slot=slot) behind the upload, on the copy stream.
         regions: set_regions(slot=slot) behind the upload; per sample, or per image as in set_batch.
-        att_targets [B, S]: set_att_targets(slot=slot) behind the upload."""
+        att_targets [B, S]: set_att_targets(slot=slot) behind the upload.
+        packed_counts [N]: feats is packed region rows [sum(packed_counts), D] (see set_batch_packed), or, with
+        feats None, the slot's staging holds them at its start (batch_slot(...)["feats"] viewed flat); N is the
+        batch size, or with image_of the number of maps.  The counts become the batch's region counts."""
+        if packed_counts is not None and (regions is not None or bank_rows is not None):
+            raise ValueError("a packed batch brings its own region counts and its own rows")
         if regions is not None:
             B = self._n if lens is None else int(np.asarray(lens).shape[0])
             regions = self._sample_regions(regions, image_of, B)
         if att_targets is not None:
             att_targets = self._att_targets(att_targets, self._n if lens is None else int(np.asarray(lens).shape[0]))
         self._set_batch_async(slot, feats, tokens, lens, labels, has_labels, feat_type, image_of, n_images,
-                              bank_rows)
+                              bank_rows, packed_counts)
         if answers is not None:
             self.set_answers(*answers, slot=slot)
         if regions is not None:
@@ -540,12 +605,26 @@ class RAU:
             self.set_att_targets(att_targets, slot=slot)
 
     def _set_batch_async(self, slot, feats, tokens, lens, labels, has_labels, feat_type, image_of, n_images,
-                         bank_rows):
+                         bank_rows, packed_counts=None):
         c = self.cfg
         B = self._n
         if lens is not None:
             lens = np.ascontiguousarray(lens, np.int32)
             B = self._rows(lens, "set_batch_async")
+        if packed_counts is not None:
+            rows, ft, nmaps, counts, image_of = self._packed(feats, packed_counts, image_of, B, feat_type)
+            keep = [None if a is None else np.ascontiguousarray(a, np.int32) for a in (tokens, lens, labels)]
+            for a, n in zip(keep, (c.T * B, B, B)):
+                if a is not None and a.size != n:
+                    raise ValueError("batch shapes do not match the config")
+            if B != self._n:
+                self.set_batch_size(B)
+            tp, lp, yp = [None if a is None else a.ctypes.data for a in keep]
+            L.check(self._lib.rau_set_batch_async_packed(
+                self._h, slot, None if rows is None else rows.ctypes.data, feat16.FEAT_TYPES[ft], nmaps,
+                counts.ctypes.data, None if image_of is None else image_of.ctypes.data, tp, lp, yp,
+                int(bool(has_labels))))
+            return
         if bank_rows is not None:
             if feats is not None:
                 raise ValueError("a bank batch takes bank_rows, not feats")

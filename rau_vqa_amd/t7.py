@@ -306,6 +306,19 @@ def load_feature(path, D, W, H, keep_half=False):
     return a.reshape(D, W * H)
 
 
+def load_regions(path, D, keep_half=False):
+    """One image's region features as the files store them: a 2-D tensor [n_boxes, D], one row per box ->
+    float32 [n, D] (rows of rau_set_batch_packed).  keep_half: a HalfTensor file stays float16."""
+    t = load(path)
+    if not isinstance(t, Tensor):
+        raise T7Error("feature file does not hold a tensor")
+    half = keep_half and t.array.dtype == np.float16
+    a = np.ascontiguousarray(t.array, np.float16 if half else np.float32)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != D:
+        raise T7Error(f"region feature shape {a.shape} is not (n >= 1, {D})")
+    return a
+
+
 def remap_flat(flat, src_layout, dst_layout):
     """Re-order a flat parameter vector between two layouts of the same named tensors.
 
