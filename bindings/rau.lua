@@ -42,6 +42,8 @@ int rau_set_mode(rau_ctx* ctx, int mode);
 int rau_set_dropout_seed(rau_ctx* ctx, uint64_t seed, uint32_t step);
 int rau_set_mask(rau_ctx* ctx, int site, const uint8_t* keep, size_t n);
 int rau_get_mask(rau_ctx* ctx, int site, uint8_t* keep, size_t n);
+int rau_set_feat_dropout(rau_ctx* ctx, int kind);
+int rau_feat_dropout(rau_ctx* ctx, int* kind);
 int rau_set_batch(rau_ctx* ctx, const float* feats, const int32_t* tokens,
                   const int32_t* lens, const int32_t* labels);
 int rau_batch_feats(rau_ctx* ctx, float** feats_dev);
@@ -241,6 +243,18 @@ end
 -- nn.Module surface ----------------------------------------------------------
 function RAU:training() check(C.rau_set_mode(self.h, 0)); return self end
 function RAU:evaluate() check(C.rau_set_mode(self.h, 1)); return self end
+-- One feature-map dropout mask for all hops (RAU_XDROP_TIED) instead of the reference's mask per hop clone: a
+-- train-mode step then runs the two 1x1 convs and their gradients once.  on = false (or nil given as false)
+-- goes back to the reference's masks.  Between steps; a change drops an explicit feature-map mask.
+function RAU:tieFeatureDropout(on)
+  check(C.rau_set_feat_dropout(self.h, (on == nil or on) and 1 or 0))
+  return self
+end
+function RAU:featureDropoutTied()
+  local k = ffi.new('int[1]')
+  check(C.rau_feat_dropout(self.h, k))
+  return k[0] == 1
+end
 
 -- m:getParameters(): returns {ptr=device float*, grad=device float*, n=count}
 function RAU:getParameters(group)

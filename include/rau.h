@@ -191,6 +191,33 @@ int rau_set_mask(rau_ctx* ctx, int site, const uint8_t* keep, size_t n);
 /* reads back the keep flags the next/last forward uses (tests; synchronising) */
 int rau_get_mask(rau_ctx* ctx, int site, uint8_t* keep, size_t n);
 
+/* ---- feature-map dropout: one mask per hop clone, or one mask tied across the hops ------------
+ * The reference gives every hop clone its own Dropout mask on the raw feature map (SS:239, 343-347), so
+ * xd[h] = X (.) mask_h and both 1x1 convolutions run once per hop.  RAU_XDROP_TIED shares ONE mask among the
+ * hops (variational dropout over the steps of a weight-shared recurrence: a modelling option the reference does
+ * not have).  i_embed's output and the attention pre-activation are then hop-invariant: a train-mode step
+ * runs both convolutions once, and its backward sums what the hops hand back (dS_h, dj_h (x) a_h; the conv
+ * gradients are linear in them) and runs the three conv gradients once.
+ *   mask site    RAU_MASK_X has [B,D,S] elements in tied mode, not [H,B,D,S]: rau_set_mask / rau_get_mask check
+ *                against that count.  The device-drawn tied mask of a (seed, step) is the hop-0 slice of the
+ *                per-hop mask of the same (seed, step); the scale stays 1/(1-p).  Tied dropout computes what
+ *                per-hop dropout computes when it is given H equal masks.
+ *   the call     between steps, in either mode.  A CHANGE of kind drops a caller-supplied mask of site
+ *                RAU_MASK_X (the site falls back to the seeded stream) and the last forward: a backward without a
+ *                new forward is RAU_ERR_STATE.  Parameters, gradients, optimizer state, bank, batch slots and
+ *                the captured steps of the other kind stay (rau_graph_step keys its cache by the kind).  A
+ *                kind outside the two values: RAU_ERR_INVALID.  While a step is being captured: RAU_ERR_STATE.
+ *   numerics     the summed backward adds the hops in ascending order in f32 and gives the same bits on every
+ *                call; they are not the bits of the per-hop path fed H equal masks (another summation order).
+ *                RAU_BF16: the hop sums are rounded once, as sums.  The evaluate-mode backward and everything
+ *                under RAU_XDROP_PER_HOP compute exactly what they did without this call.
+ * The module-level entry points need nothing: a host that clones modules ties the masks by handing every
+ * clone the same one; rau_multimodal_forward under RAU_XDROP_TIED reads the one mask for every hop. */
+#define RAU_XDROP_PER_HOP 0   /* the reference: a mask per hop clone (default) */
+#define RAU_XDROP_TIED    1   /* one mask, shared by all hops */
+int rau_set_feat_dropout(rau_ctx* ctx, int kind);
+int rau_feat_dropout(rau_ctx* ctx, int* kind);
+
 /* ---- batch: what next_batch_feat returns + the H2D of SS:434-439 -------------
  * feats [B,D,S] float (NCHW with W*H flattened), tokens [T,B] int32, lens [B]
  * int32 (0..T), labels [B] int32 (1..K) or NULL for inference.  Copies to the

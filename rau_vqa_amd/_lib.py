@@ -21,6 +21,7 @@ GROUP_EMBED, GROUP_RNN, GROUP_MULT = 0, 1, 2
 GROUPS = {"embed": GROUP_EMBED, "rnn": GROUP_RNN, "mult": GROUP_MULT}
 MODE_TRAIN, MODE_EVAL = 0, 1
 MASK_SITES = {"we": 0, "rnn": 1, "q": 2, "x": 3, "mf": 4}
+XDROP_PER_HOP, XDROP_TIED = 0, 1
 
 
 class RauConfig(C.Structure):
@@ -71,6 +72,9 @@ _SIGS = {
     "rau_set_dropout_seed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32]),
     "rau_set_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "rau_get_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    # feature-map dropout: a mask per hop clone (0) or one mask tied across the hops (1)
+    "rau_set_feat_dropout": (C.c_int, [C.c_void_p, C.c_int]),
+    "rau_feat_dropout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rau_set_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_batch_feats": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_batch_slot": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

@@ -372,6 +372,12 @@ hipError_t bank_gather(hipStream_t st, int n, size_t map_bytes, const void* bank
 // (subnormals, overflow to infinity), of feat16.bf16_bits, and of feat16.fp8_bits (SATURATING: everything
 // beyond the largest finite value, infinities included, becomes the largest finite value)
 hipError_t narrow_features(hipStream_t st, size_t rows, int SL, int Sp, const float* src, void* out, int ft);
+// Tied feature-map dropout backward (tied_bwd.hip): the hop sums in front of the one set of conv gradients.
+// out[b][k][s] = sum_{h < HA} T[h][b][k][s] (ascending, f32), [B][A][Sp] per hop, pad columns s >= SL written as 0
+hipError_t hop_sum(hipStream_t st, int HA, int B, int A, int SL, int Sp, const float* T, float* out);
+// dZ[b][m][s] = fmaf(dj[h][b][m], a[h][b][s], dZ[b][m][s]) for h = 1 .. HA-1 (ascending); dj [HA][B][M],
+// a [HA][B][Sp], dZ [B][M][Sp]; HA >= 2
+hipError_t outer_sum(hipStream_t st, int HA, int B, int M, int Sp, const float* dj, const float* a, float* dZ);
 // dst[n] += sum_rows X[row*ld + n]   (two-stage, deterministic; tmp >= 32*N floats)
 hipError_t colsum_acc(hipStream_t st, int rows, int N, const float* X, long ld, float* dst,
                       float* tmp);

@@ -227,9 +227,11 @@ struct StepKey {
   bool att = false;
   bool att_targets = false;
   bool mrg = false;             // ... and a step with a non-zero merge_w has the merge_grad launch
+  // ... and under RAU_XDROP_TIED a train-mode step has one masked map, one conv group and the summed conv gradients
+  bool tied_x = false;
   auto tied() const {
     return std::tie(mode, max_len, active, zero, mexplicit[0], mexplicit[1], mexplicit[2], mexplicit[3], mexplicit[4],
-                    slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg);
+                    slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg, tied_x);
   }
   bool operator==(const StepKey& o) const { return tied() == o.tied(); }
 };
@@ -320,7 +322,12 @@ struct rau_ctx {
   bool dpre_fwd = false;    // the last forward already formed dpre / dhn of every hop (unscaled by the hop weights)
   bool ds16_step = false;   // set by rau_backward while its hop loop runs: hop_backward writes dS16, not T
   void* xd16 = nullptr;  // RAU_BF16 step path, S % 4 == 0: the same maps stored as bf16 (xd stays unwritten)
-  bool I_shared = false;  // evaluate mode: i_embed output is hop-invariant, computed once
+  bool I_shared = false;  // evaluate mode, p_x = 0 or a tied mask: i_embed output is hop-invariant, computed once
+  // feature-map dropout kind (rau_set_feat_dropout): RAU_XDROP_PER_HOP, or RAU_XDROP_TIED = one mask for all hops
+  int xdrop = RAU_XDROP_PER_HOP;
+  bool fwd_tied = false;            // the last forward was a train-mode one under RAU_XDROP_TIED: summed conv gradients
+  const float* x_shared = nullptr;  // ... and i_embed's input then: xd (the one masked map) or, without a mask, xw
+  float* dS_sum = nullptr;          // [cap][A][Sp] sum of the active hops' dS (tied_bwd.hip), allocated with the switch
   bool yq_shared = false; // no dropout on q (evaluate mode): q_embed's question half is hop-invariant, rows of hop 0 only
   float *WiT, *WpT;   // i_embed / ifeatproj weights transposed ([D][M], [M][A]), refreshed per forward
   float *P0;          // [B][A][S] hop-invariant attention pre-activation (evaluate mode)

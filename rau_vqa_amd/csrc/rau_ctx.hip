@@ -139,7 +139,8 @@ static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
   p->mcount[RAU_MASK_WE] = (size_t)T * B * E;
   p->mcount[RAU_MASK_RNN] = (size_t)T * B * Rq;
   p->mcount[RAU_MASK_Q] = (size_t)H * B * Q;
-  p->mcount[RAU_MASK_X] = (size_t)H * B * D * SL;
+  // one mask per hop clone, or (RAU_XDROP_TIED) one for all of them: hop 0's elements of the same stream
+  p->mcount[RAU_MASK_X] = (size_t)(ctx->xdrop == RAU_XDROP_TIED ? 1 : H) * B * D * SL;
   p->mcount[RAU_MASK_MF] = (size_t)H * B * M;
   p->att_part = att_split_part_floats(B, S);
   // Same-box A/B (B=256, D=512, ms/step): fused 16-wave attention + split-K encoder 10.54-10.59,
@@ -760,6 +761,33 @@ int rau_get_mask(rau_ctx* ctx, int site, uint8_t* keep, size_t n) {
   return RAU_OK;
 }
 
+// ------------------------------------------------- feature-map dropout kind
+// The forward reads ctx->xdrop (one masked map and the shared conv path in train mode), the backward what that
+// forward recorded (fwd_tied), plan_batch the size of the mask site; nothing else depends on the kind.
+int rau_set_feat_dropout(rau_ctx* ctx, int kind) {
+  NEED(ctx, "null ctx");
+  NEED(kind == RAU_XDROP_PER_HOP || kind == RAU_XDROP_TIED,
+       "rau_set_feat_dropout: kind %d is neither RAU_XDROP_PER_HOP nor RAU_XDROP_TIED", kind);
+  if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_feat_dropout: a step is being captured");
+  if (kind == ctx->xdrop) return RAU_OK;
+  // the hop sum of dS: allocated here, at the first use of the tied kind (never inside a captured step), for the
+  // capacity, and cleared by rau_set_batch_size like every activation
+  if (kind == RAU_XDROP_TIED && !ctx->dS_sum)
+    if (int rc = dalloc(ctx, &ctx->dS_sum, (size_t)ctx->cap * ctx->cfg.A * ctx->Sp)) return rc;
+  ctx->xdrop = kind;
+  const rau_config& c = ctx->cfg;
+  ctx->mcount[RAU_MASK_X] = (size_t)(kind == RAU_XDROP_TIED ? 1 : c.H) * c.B * c.D * c.S;
+  ctx->mexplicit[RAU_MASK_X] = false;   // a caller's mask has the other kind's shape: back to the seeded stream
+  ctx->mod_masks_valid = false;
+  ctx->fwd_done = false;                // the last forward is the other kind's: no backward without a new one
+  return RAU_OK;
+}
+int rau_feat_dropout(rau_ctx* ctx, int* kind) {
+  NEED(ctx && kind, "null argument");
+  *kind = ctx->xdrop;
+  return RAU_OK;
+}
+
 // ------------------------------------------------------------- batch size
 int rau_batch_size(rau_ctx* ctx, int32_t* n, int32_t* capacity) {
   NEED(ctx, "null ctx");
@@ -841,6 +869,8 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   ctx->fwd_done = ctx->bwd_done = false;
   ctx->dpre_fwd = false;
   ctx->I_shared = ctx->yq_shared = false;
+  ctx->fwd_tied = false;
+  ctx->x_shared = nullptr;
   ctx->cur.clear();
   for (int i = 0; i < 5; ++i) ctx->mexplicit[i] = false;
   ctx->mod_masks_valid = false;
@@ -1317,7 +1347,11 @@ int rau_forward(rau_ctx* ctx) {
   }
   return 0;
   };
-  ctx->I_shared = (m_x == nullptr);
+  // RAU_XDROP_TIED: every hop clone sees the SAME masked map, so a train-mode step takes the shared path too (one
+  // masked copy, both convs once) and its backward sums the hops in front of one set of conv gradients
+  const bool tied = tr && ctx->xdrop == RAU_XDROP_TIED;
+  ctx->I_shared = (m_x == nullptr) || tied;
+  ctx->fwd_tied = tied;
   // A batch with an image table.  Evaluate mode: nothing per sample touches the maps (no dropout on X), so
   // i_embed and the attention pre-activation run once per IMAGE and the attention kernels read sample b's
   // tiles at row image_of[b].  Everywhere else (train mode: per-sample masks; a captured step: its backward
@@ -1349,7 +1383,10 @@ int rau_forward(rau_ctx* ctx) {
     HIPC(hipStreamWaitEvent(sb, ctx->evA, 0));
     // feature-map dropout, SS:239: unless the caller supplied the mask, the pass that makes the H masked
     // copies draws the keep bits itself (they have no other reader on this path)
-    const bool x16 = m_x && ctx->xd16;   // bf16 mode: the hop copies of the feature map are stored as bf16
+    // bf16 mode: the hop copies of the feature map are stored as bf16 (to halve an H-fold buffer; the one tied
+    // copy stays f32 in xd and feeds the f32-storage kernels, which round their operands themselves)
+    const bool x16 = m_x && ctx->xd16 && !tied;
+    const int HX = tied ? 1 : H;         // masked copies: the mask site has HX * B * D * SL elements
     const bool x_gen = m_x && !ctx->mexplicit[RAU_MASK_X] && SL == S && ((size_t)B * D * S) % 16 == 0;
     if (!x_gen)
       if (int rc = gen_masks(ctx, -1, RAU_MASK_X, sb)) return rc;
@@ -1359,16 +1396,16 @@ int rau_forward(rau_ctx* ctx) {
     const int ft = bs.held.feat_type;
     const double xb = (double)feat_elem_bytes(ft);   // bytes per element read from the batch
     if (x_gen)
-      RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * (x16 ? 2 : 4),
-           dropout_features_gen(sb, ctx->seed, RAU_MASK_X, ctx->step, ctx->mp[RAU_MASK_X], ctx->dkey, H,
+      RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)HX * B * D * S * (x16 ? 2 : 4),
+           dropout_features_gen(sb, ctx->seed, RAU_MASK_X, ctx->step, ctx->mp[RAU_MASK_X], ctx->dkey, HX,
                                 (size_t)B * D * S, feats, sc(RAU_MASK_X),
                                 x16 ? (void*)ctx->xd16 : (void*)ctx->xd, x16 ? 1 : 0, ft));
     else if (x16)
       RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * 2,
            dropout_features_b16(sb, H, (size_t)B * D * S, feats, m_x, sc(RAU_MASK_X), ctx->xd16, ft));
     else if (m_x)
-      RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * 4,
-           dropout_features(sb, H, (size_t)B * D * S, feats, m_x, sc(RAU_MASK_X), ctx->xd, 0, SL,
+      RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)HX * B * D * S * 4,
+           dropout_features(sb, HX, (size_t)B * D * S, feats, m_x, sc(RAU_MASK_X), ctx->xd, 0, SL,
                             S, ft));
     // no mask: the GEMMs read the batch itself -- a 16-bit one through its f32 image in xd (unused here),
     // so that they are the f32 batch's kernels with the f32 batch's operands
@@ -1378,6 +1415,7 @@ int rau_forward(rau_ctx* ctx) {
       RUNS(sb, "widen_features", 0, (double)nX * D * S * (xb + 4),
            widen_features(sb, (size_t)nX * D, SL, S, feats, ctx->xw, ft));
     }
+    ctx->x_shared = m_x ? ctx->xd : ctx->xw;   // what the shared path's i_embed reads (and its weight gradient)
     for (int h0 = 0; h0 < H; h0 += gsz[h0]) {
       const int nBI = ctx->I_shared ? nX : gsz[h0] * B;
       const size_t hb = ctx->I_shared ? 0 : (size_t)h0 * B;  // first (hop, sample) row
@@ -1722,6 +1760,21 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
         if (dzf && h == 0)   // last group: i_embed bias gradient = column sums of the per-sample rows
           RUNS(sb, "colsum", 0, (double)HA * B * M * 4,
                colsum_acc(sb, HA * B, M, ctx->dbi_part, M, ctx->i_embed.db, ctx->ws_bulk.coltmp));
+      } else if (ctx->fwd_tied) {
+        // Tied feature-map dropout (train mode, I and X' shared): the conv gradients are linear in what each hop
+        // hands back, so the hops are summed first (tied_bwd.hip) and every conv gradient runs once, at n = B.
+        // The sum of dS goes to a buffer of its own: T keeps every hop's dS, as on the per-hop paths.
+        RUNS(sb, "hop_sum", 0, (double)(HA + 1) * B * A * S * 4, hop_sum(sb, HA, B, A, SL, S, ctx->T, ctx->dS_sum));
+        RUNS(sb, "conv_att_dgrad", gflop(M, (double)B * S, A), ((double)B * A * S + 2.0 * BM_ * S) * 4,
+             conv_att_dgrad(sb, B, M, S, A, ctx->dS_sum, ctx->att_i.W, ctx->dj, ctx->a, ctx->dZ, ctx->bf16));
+        if (HA > 1)   // + dj_h (x) a_h of the other active hops (hop 0's came out of the dgrad's epilogue)
+          RUNS(sb, "outer_sum", 2.0 * (HA - 1) * BM_ * S, (2.0 * BM_ * S + (double)(HA - 1) * (BM_ + BS_)) * 4,
+               outer_sum(sb, HA, B, M, S, ctx->dj, ctx->a, ctx->dZ));
+        RUNS(sb, "conv_att_wgrad", gflop(A, M, (double)B * S), ((double)B * A * S + BM_ * S) * 4,
+             conv_att_wgrad(sb, B, M, S, A, ctx->dS_sum, ctx->I, ctx->att_i.dW, slab_b, ctx->bf16));
+        RUNS(sb, "conv_embed_wgrad", gflop(M, D, (double)B * S), (2.0 * BM_ * S + (double)B * D * S) * 4,
+             conv_embed_wgrad(sb, B, D, S, M, ctx->dZ, ctx->I, ctx->x_shared, ctx->i_embed.dW, slab_b,
+                              ctx->bf16, ctx->i_embed.db));
       } else {
         for (int hh2 = 0; hh2 < HA; ++hh2) {  // evaluate mode: I (and X) shared by all hops
           float* Th2 = ctx->T + (size_t)hh2 * B * A * S;
@@ -1981,6 +2034,7 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
   key.att = loss.att_w != nullptr;
   key.att_targets = bs.held.att_targets;
   key.mrg = loss.merge_w != nullptr;
+  key.tied_x = ctx->xdrop == RAU_XDROP_TIED;
   if (int rc = upload_hop_weights(ctx, loss)) return rc;
   ctx->mg.valid = false;
   hipGraphExec_t exec = nullptr;

@@ -324,7 +324,9 @@ int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const fl
   if (m.x) {
     float* xd = ctx->xd + (size_t)h * B * D * S;
     RUN("dropout_features", 0, 2.0 * B * D * S * 4,
-        dropout_features(st, 1, (size_t)B * D * S, X, m.x, m.s_x, xd, (size_t)h * B * D * SL, SL, S));
+        dropout_features(st, 1, (size_t)B * D * S, X, m.x, m.s_x, xd,
+                         ctx->xdrop == RAU_XDROP_TIED ? 0 : (size_t)h * B * D * SL /* tied: every hop reads the one mask */,
+                         SL, S));
     xin = xd;
   }
   RUN("transpose", 0, (double)M * D * 8, transpose2d(st, M, D, ctx->i_embed.W, ctx->WiT));
@@ -454,7 +456,7 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
     if (m.x)   // the mask is indexed logically: applied on the dense tensor
       RUN("apply_mask", 0, (double)B * D * SL * 8,
           apply_mask(st, (size_t)B * D * SL, (size_t)B * D * SL, dXo, m.x, m.s_x, dXo,
-                     (size_t)h * B * D * SL));
+                     ctx->xdrop == RAU_XDROP_TIED ? 0 : (size_t)h * B * D * SL));
     *d_X = dXo;
   }
   // ---- accGradParameters of the clone's Linears

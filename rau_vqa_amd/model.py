@@ -44,11 +44,13 @@ class Config:
     def Q(self) -> int:
         return 4 * self.Rq
 
-    def mask_shapes(self, n=None):
-        """Shapes of the five mask sites at batch size n (default: the capacity B)."""
+    def mask_shapes(self, n=None, tied_x=False):
+        """Shapes of the five mask sites at batch size n (default: the capacity B).  tied_x: the feature-map
+        site of a context with RAU.tie_feature_dropout() on: one mask [B, D, S] shared by all hops."""
         B = self.B if n is None else int(n)
         return {"we": (self.T, B, self.E), "rnn": (self.T, B, self.Rq),
-                "q": (self.H, B, self.Q), "x": (self.H, B, self.D, self.S),
+                "q": (self.H, B, self.Q),
+                "x": (B, self.D, self.S) if tied_x else (self.H, B, self.D, self.S),
                 "mf": (self.H, B, self.M)}
 
 
@@ -218,13 +220,34 @@ class RAU:
     def set_dropout_seed(self, seed: int, step: int = 0):
         L.check(self._lib.rau_set_dropout_seed(self._h, seed, step))
 
+    def tie_feature_dropout(self, on=True):
+        """One feature-map dropout mask shared by all hops (rau_set_feat_dropout, RAU_XDROP_TIED) instead of
+        the reference's mask per hop clone: a train-mode step then runs the two 1x1 convolutions and their three
+        gradients once, not once per hop.  The "x" mask site becomes [B, D, S]; a seeded tied mask is hop 0's
+        slice of the per-hop one.  Between steps, in either mode; a change drops an explicit "x" mask and the
+        last forward."""
+        L.check(self._lib.rau_set_feat_dropout(self._h, L.XDROP_TIED if on else L.XDROP_PER_HOP))
+
+    @property
+    def feature_dropout_tied(self) -> bool:
+        k = C.c_int()
+        L.check(self._lib.rau_feat_dropout(self._h, C.byref(k)))
+        return k.value == L.XDROP_TIED
+
     def set_masks(self, masks):
+        """masks: site name -> keep flags in Config.mask_shapes' shape for the current batch size (the library
+        checks the element count).  With tie_feature_dropout() on, "x" is [B, D, S] or [1, B, D, S]: any other
+        shape, the per-hop [H, B, D, S] of H > 1 among them, is refused."""
         for k, m in masks.items():
             m = np.ascontiguousarray(m, np.uint8)
+            if k == "x" and self.feature_dropout_tied:
+                want = self.cfg.mask_shapes(self._n, tied_x=True)["x"]
+                if m.shape != want and m.shape != (1,) + want:
+                    raise ValueError(f"mask site x is tied across the hops: {want}, got {m.shape}")
             L.check(self._lib.rau_set_mask(self._h, L.MASK_SITES[k], m.ctypes.data, m.size))
 
     def get_mask(self, site: str):
-        shape = self.cfg.mask_shapes(self._n)[site]
+        shape = self.cfg.mask_shapes(self._n, tied_x=site == "x" and self.feature_dropout_tied)[site]
         m = np.empty(int(np.prod(shape)), np.uint8)
         L.check(self._lib.rau_get_mask(self._h, L.MASK_SITES[site], m.ctypes.data, m.size))
         return m.reshape(shape)
