@@ -44,6 +44,8 @@ int rau_set_mask(rau_ctx* ctx, int site, const uint8_t* keep, size_t n);
 int rau_get_mask(rau_ctx* ctx, int site, uint8_t* keep, size_t n);
 int rau_set_feat_dropout(rau_ctx* ctx, int kind);
 int rau_feat_dropout(rau_ctx* ctx, int* kind);
+int rau_set_answer_loss(rau_ctx* ctx, int kind);
+int rau_answer_loss(rau_ctx* ctx, int* kind);
 int rau_set_batch(rau_ctx* ctx, const float* feats, const int32_t* tokens,
                   const int32_t* lens, const int32_t* labels);
 int rau_batch_feats(rau_ctx* ctx, float** feats_dev);
@@ -129,6 +131,10 @@ int rau_criterion_forward_set(rau_ctx* ctx, int h, const float* logits, int32_t 
                               const float* w_dev, float* loss);
 int rau_criterion_backward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
                                const float* w_dev, float scale, float** d_logits);
+int rau_criterion_forward_bce(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev,
+                              int32_t G, const int32_t* ids_dev, const float* w_dev, float* loss);
+int rau_criterion_backward_bce(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev,
+                               int32_t G, const int32_t* ids_dev, const float* w_dev, float scale, float** d_logits);
 int rau_att_criterion_forward(rau_ctx* ctx, int h, const float* attprob_dev, const float* t_dev,
                               const int32_t* nreg_dev, float* loss);
 int rau_att_criterion_backward(rau_ctx* ctx, int h, const float* attprob_dev, const float* t_dev,
@@ -254,6 +260,21 @@ function RAU:featureDropoutTied()
   local k = ffi.new('int[1]')
   check(C.rau_feat_dropout(self.h, k))
   return k[0] == 1
+end
+-- The answer criterion of forward / graphStep: 'ce' (softmax cross-entropy, the reference's) or 'bce' (a sigmoid per
+-- answer, binary cross-entropy against the soft targets of the answer set).  Between steps; a change drops the last
+-- forward.  A non-zero merge_w is refused under 'bce'.
+local LOSS = { ce = 0, bce = 1 }
+function RAU:setAnswerLoss(kind)
+  local k = LOSS[kind]
+  if k == nil then error("setAnswerLoss: kind must be 'ce' or 'bce'") end
+  check(C.rau_set_answer_loss(self.h, k))
+  return self
+end
+function RAU:answerLoss()
+  local k = ffi.new('int[1]')
+  check(C.rau_answer_loss(self.h, k))
+  return k[0] == 1 and 'bce' or 'ce'
 end
 
 -- m:getParameters(): returns {ptr=device float*, grad=device float*, n=count}
@@ -894,6 +915,20 @@ local function clone(self, kind, i)
     function m:backwardSet(logits, ids, w, G, scale)
       local o = ffi.new('float*[1]')
       check(C.rau_criterion_backward_set(self.rau.h, self.i, ptr_of(logits), G, ptr_of(ids), ptr_of(w), scale or 1, o))
+      return Tensor.wrap(self.rau, o[0], self.rau.n, cfg.K)
+    end
+    -- the per-answer sigmoid criterion (BCE against soft targets): y = labels (RAU.IntTensor [B]), or y = nil and an
+    -- answer set ids / w / G as in forwardSet
+    function m:forwardBCE(logits, y, ids, w, G)
+      local l = ffi.new('float[1]')
+      check(C.rau_criterion_forward_bce(self.rau.h, self.i, ptr_of(logits), y and ptr_of(y) or nil, G or 0,
+                                        ids and ptr_of(ids) or nil, w and ptr_of(w) or nil, l))
+      return l[0]
+    end
+    function m:backwardBCE(logits, y, ids, w, G, scale)
+      local o = ffi.new('float*[1]')
+      check(C.rau_criterion_backward_bce(self.rau.h, self.i, ptr_of(logits), y and ptr_of(y) or nil, G or 0,
+                                         ids and ptr_of(ids) or nil, w and ptr_of(w) or nil, scale or 1, o))
       return Tensor.wrap(self.rau, o[0], self.rau.n, cfg.K)
     end
   end

@@ -218,6 +218,46 @@ int rau_get_mask(rau_ctx* ctx, int site, uint8_t* keep, size_t n);
 int rau_set_feat_dropout(rau_ctx* ctx, int kind);
 int rau_feat_dropout(rau_ctx* ctx, int* kind);
 
+/* ---- answer criterion: softmax cross-entropy, or a per-answer sigmoid with binary cross-entropy --------------
+ * The reference trains every hop's logits with nn.CrossEntropyCriterion (SS:310), and an answer set
+ * (rau_set_answers) with its soft-target form.  RAU_LOSS_BCE is the other common VQA objective: every answer k has
+ * its own sigmoid, trained with binary cross-entropy against a soft target t[k] in [0, 1] -- with rau_set_answers'
+ * weights w = min(#humans / 3, 1) the recipe of the bottom-up / top-down models.  It replaces the criterion of
+ * rau_forward and every rau_graph_step*; everything that reads logits and argmax only is the same under both.
+ * Per (hop, sample) row, with x the row's logits, n the current batch size and invB = 1 / n:
+ *   target     labels:      t[k] = [k == y]
+ *              answer set:  t[k] = min(1, sum_g w[b,g] [ids[b,g] - 1 == k]) over the non-empty entries, added from 0
+ *              in entry order in f32, then clamped: duplicates add up, deterministically.  Ids as at rau_set_answers.
+ *   loss row   sum_k ( max(x,0) - x t + log1pf(expf(-|x|)) ), summed over K and NOT divided by K (BCE-with-logits
+ *              times K); a hop's loss (rau_get_losses) is the mean of its rows over n.
+ *   gradient   d_logits[k] = (sigmoid(x) - t) invB, sigmoid from e = expf(-|x|) as x >= 0 ? 1/(1+e) : e/(1+e); the
+ *              difference and the product are each rounded once.  Finite for every finite x; the same bits on
+ *              every call (no atomics).
+ *   unlabelled a row whose set has no non-empty entry: loss 0, gradient +0, never "correct" -- as under RAU_LOSS_CE.
+ *              A row whose entries all carry weight 0 IS labelled, with the all-zero target: every answer is
+ *              pushed down.
+ *   the call   between steps, in either mode.  A CHANGE of kind drops the last forward: rau_backward*,
+ *              rau_step_stats and rau_step_scores without a new forward are RAU_ERR_STATE, nothing launched.
+ *              Parameters, gradients, optimizer state, bank, batch slots, answer sets, region counts and the
+ *              captured steps of the other kind stay (rau_graph_step keys its cache by the kind).  A kind outside
+ *              the two values: RAU_ERR_INVALID.  While a step is being captured: RAU_ERR_STATE.  rau_config is not
+ *              touched, and a context that never calls this computes exactly what it did without it.
+ *   with       hop_w, select_w and att_w as before: the select head's target do_pred_gt stays "the hop's first-max
+ *              answer equals the label / carries a positive score".
+ *   statistics rau_step_stats: loss[0..H) is rau_get_losses bit for bit; loss[H] and loss[H+1] are the same
+ *              criterion (same formula, same target) of the uni and select rows under the feval rule.  Counts,
+ *              loss_do_pred, rau_step_scores, rau_predict, rau_predict_scores, rau_get_merged: untouched.
+ *              rau_topk: conf stays the softmax probability; under RAU_LOSS_BCE the per-answer confidence is the
+ *              sigmoid of the returned score.
+ *   NOT built  training the merged rows: rau_backward_merged / rau_graph_step_merged with a non-zero merge_w under
+ *              RAU_LOSS_BCE are RAU_ERR_INVALID, nothing launched (NULL or zeros stays rau_backward_att);
+ *              rau_merge_criterion_backward is a cross-entropy function under either kind.
+ * The module-level rau_criterion_*_bce below are this criterion whatever the kind. */
+#define RAU_LOSS_CE  0   /* softmax cross-entropy: the reference, the default */
+#define RAU_LOSS_BCE 1   /* per-answer sigmoid, binary cross-entropy against soft targets */
+int rau_set_answer_loss(rau_ctx* ctx, int kind);
+int rau_answer_loss(rau_ctx* ctx, int* kind);
+
 /* ---- batch: what next_batch_feat returns + the H2D of SS:434-439 -------------
  * feats [B,D,S] float (NCHW with W*H flattened), tokens [T,B] int32, lens [B]
  * int32 (0..T), labels [B] int32 (1..K) or NULL for inference.  Copies to the
@@ -591,7 +631,8 @@ int rau_att_stats(rau_ctx* ctx, float* loss /* [H] */, float* mass /* [H] */, in
  * same launches, the same bits.  Otherwise every hop is active (HA = H: the uni row reads every hop), and the
  * forward's labels or answer set must still be there: RAU_ERR_STATE, nothing launched, when that batch had neither or
  * its slot has been uploaded into since (the rule of rau_step_stats); every state rule of rau_backward applies as
- * well.  A non-finite weight in any array: RAU_ERR_INVALID.
+ * well.  A non-finite weight in any array: RAU_ERR_INVALID.  The two terms are cross-entropies: under RAU_LOSS_BCE
+ * (rau_set_answer_loss) a non-zero merge_w is RAU_ERR_INVALID, nothing launched, here and in rau_graph_step_merged.
  * rau_graph_step_merged is rau_graph_step_att with that backward: merge_w is uploaded next to hop_w and read from
  * device memory, so it may change between replays; "any merge_w non-zero" joins the cache key.
  * rau_merge_criterion_backward, for hosts that call the clones one by one: logits_dev [H,n,K] and dopred_dev [H,n]
@@ -679,6 +720,16 @@ int rau_criterion_forward_set(rau_ctx* ctx, int h, const float* logits, int32_t 
                               const float* w_dev, float* loss);
 int rau_criterion_backward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
                                const float* w_dev, float scale, float** d_logits);
+
+/* The per-answer sigmoid criterion (RAU_LOSS_BCE at rau_set_answer_loss: target, loss row, gradient, roundings) on
+ * logits the caller holds: the kernel the step's head uses under that kind, whatever kind the context is switched
+ * to.  The target is labels_dev [B] int32 1-based, or with labels_dev NULL the answer set ids_dev / w_dev [B,G]
+ * (1 <= G <= 16; neither: RAU_ERR_INVALID); G, ids_dev and w_dev are ignored with labels.  :forward -> *loss (host,
+ * may be NULL) = the mean over B of the loss rows; :backward -> d_logits [B,K] = scale*(sigmoid - t)/B. */
+int rau_criterion_forward_bce(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev /* NULL: use the set */,
+                              int32_t G, const int32_t* ids_dev, const float* w_dev, float* loss);
+int rau_criterion_backward_bce(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev,
+                               int32_t G, const int32_t* ids_dev, const float* w_dev, float scale, float** d_logits);
 
 /* The attention supervision above for hosts that call the clones one by one: attprob_dev [B,S] (the attprob output
  * of rau_multimodal_forward), t_dev [B,S] targets and nreg_dev [B] region counts (NULL = none, clamped into [1, S]),
@@ -808,7 +859,8 @@ int rau_get_merged(rau_ctx* ctx, float* pred, float* att);
  * ids: 1-based, in rau_dev_topk's total order, so ids[r, b, 0] is rau_predict's oe[r, b] on every
  * finite row; score: the row's raw or merged logit at that id, bit for bit; conf: its softmax
  * probability, expf(score - max) / sum expf(v - max) summed in the criterion's order (defined for
- * finite rows; a non-finite row still gives distinct ids in [1, K]).  1 <= k <= K, else
+ * finite rows; a non-finite row still gives distinct ids in [1, K]; under RAU_LOSS_BCE conf is still this softmax
+ * probability -- the per-answer confidence of that criterion is the sigmoid of score).  1 <= k <= K, else
  * RAU_ERR_INVALID.  Valid when rau_predict is (RAU_ERR_STATE otherwise, nothing launched), in either
  * mode; needs no labels; neither needs nor disturbs rau_predict, rau_get_merged or rau_step_stats.
  * Its device staging is allocated at the first call and regrown for a larger k (RAU_ERR_NOMEM leaves

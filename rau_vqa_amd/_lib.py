@@ -22,6 +22,8 @@ GROUPS = {"embed": GROUP_EMBED, "rnn": GROUP_RNN, "mult": GROUP_MULT}
 MODE_TRAIN, MODE_EVAL = 0, 1
 MASK_SITES = {"we": 0, "rnn": 1, "q": 2, "x": 3, "mf": 4}
 XDROP_PER_HOP, XDROP_TIED = 0, 1
+LOSS_CE, LOSS_BCE = 0, 1
+LOSSES = {"ce": LOSS_CE, "bce": LOSS_BCE}
 
 
 class RauConfig(C.Structure):
@@ -75,6 +77,9 @@ _SIGS = {
     # feature-map dropout: a mask per hop clone (0) or one mask tied across the hops (1)
     "rau_set_feat_dropout": (C.c_int, [C.c_void_p, C.c_int]),
     "rau_feat_dropout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    # answer criterion of the step path: softmax cross-entropy (0) or per-answer sigmoid BCE (1)
+    "rau_set_answer_loss": (C.c_int, [C.c_void_p, C.c_int]),
+    "rau_answer_loss": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rau_set_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_batch_feats": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_batch_slot": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
@@ -155,6 +160,11 @@ _SIGS = {
                                             C.POINTER(C.c_float)]),
     "rau_criterion_backward_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_float, C.POINTER(C.c_void_p)]),
+    # the per-answer sigmoid criterion: labels, or (labels NULL) an answer set
+    "rau_criterion_forward_bce": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.POINTER(C.c_float)]),
+    "rau_criterion_backward_bce": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_float, C.POINTER(C.c_void_p)]),
     # device tensors (the tensor algebra feval does between module calls)
     "rau_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "rau_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),

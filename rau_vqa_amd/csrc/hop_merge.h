@@ -1,5 +1,6 @@
 // hop_merge.h -- the rows predict_result and feval read out of the resident hop outputs, for the
-// kernels that consume them (hop_merge.hip: statistics, first-max answers; topk.hip: ranked answers).
+// kernels that consume them (hop_merge.hip: statistics, first-max answers; topk.hip: ranked answers), and the
+// arithmetic of the per-answer sigmoid criterion (bce_head.hip: the step's head; hop_merge.hip: its statistics).
 // One definition of the merge arithmetic, so that every consumer sees the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -63,6 +64,26 @@ __device__ __forceinline__ int select_hop(const float* __restrict__ dopred, int 
   for (int h = 0; h < H; ++h)
     if (dopred[(size_t)h * B + b] > 0.5f || (force_last && h == H - 1)) return h;
   return -1;
+}
+
+// The per-answer sigmoid criterion (RAU_LOSS_BCE; bce_head.hip spells out the rounding), shared by the step's head
+// and the statistics of the merged rows.  The set in LDS: ng entries, s_id 0-based (-1 = empty), s_w its weight.
+// bce_target: t[k] = min(1, the matching entries' weights added from +0 in entry order).
+__device__ __forceinline__ float bce_target(const int* s_id, const float* s_w, int ng, int k) {
+  float t = 0.f;
+  for (int g = 0; g < ng; ++g)
+    if (s_id[g] == k) t = __fadd_rn(t, s_w[g]);
+  return fminf(t, 1.f);
+}
+// bce_term: (max(x,0) - x t) + log1p(e), e = expf(-|x|); every step rounded once, no fused multiply-add
+__device__ __forceinline__ float bce_term(float x, float t, float e) {
+  return __fadd_rn(__fsub_rn(fmaxf(x, 0.f), __fmul_rn(x, t)), log1pf(e));
+}
+// a row is labelled when its set has a non-empty entry
+__device__ __forceinline__ bool bce_labelled(const int* s_id, int ng) {
+  bool any = false;
+  for (int g = 0; g < ng; ++g) any = any || s_id[g] >= 0;
+  return any;
 }
 
 }  // namespace rau

@@ -1,7 +1,8 @@
 // hop_merge.hip -- the bookkeeping feval and predict_result do on top of the hop outputs, on the
 // resident outputs of the last step-level forward (logits [H,B,K], do_pred [H,B], argmax [H,B],
 // lossrow [H,B], attention [H,B,Sp]):
-//   step_stats   -- feval's joint-loss statistics (SS:476-556): CE of the uni and select merges,
+//   step_stats   -- feval's joint-loss statistics (SS:476-556): CE of the uni and select merges (under
+//                   RAU_LOSS_BCE their per-answer sigmoid criterion, k_step_stats_bce),
 //                   the BCE of every hop's do_pred against (argmax_h == y), the accuracy counters;
 //   predict_rows -- predict_result's merges (SS:633-705) and the eval loop's open-ended and
 //                   multiple-choice answers (SS:877-900).
@@ -173,6 +174,46 @@ __global__ __launch_bounds__(kMT) void k_step_stats_rows_set(int H, int B, int K
   }
 }
 
+// RAU_LOSS_BCE: the uni / select losses of rowf[b] become the per-answer sigmoid criterion of those rows against
+// the same target, in bce_head.hip's formulation and summation order (thread-strided in ascending k, block_sum);
+// a row whose set has no non-empty entry: 0.  Runs behind k_step_stats_rows(_set), which leaves everything else --
+// the counts, the do_pred BCE, the scores depend on logits and argmax only.  labels: G = 0.
+__global__ __launch_bounds__(kMT) void k_step_stats_bce(int H, int B, int K, const float* __restrict__ logits,
+    const float* __restrict__ dopred, const int32_t* __restrict__ labels, const int32_t* __restrict__ ids,
+    const float* __restrict__ w, int G, float* __restrict__ rowf) {
+  __shared__ float s_sum[4];
+  __shared__ int s_id[kMaxAnswers];
+  __shared__ float s_w[kMaxAnswers];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const size_t hs = (size_t)B * K;
+  const float* lg = logits + (size_t)b * K;
+  const int ng = G > 0 ? G : 1;
+  if (G > 0) {
+    if (tid < G) {
+      const size_t e = (size_t)b * G + tid;
+      const int id = min(max(ids[e], 0), K);
+      s_id[tid] = id - 1;
+      s_w[tid] = id > 0 ? w[e] : 0.f;
+    }
+  } else if (tid == 0) {
+    s_id[0] = min(max(labels[b], 1), K) - 1;
+    s_w[0] = 1.f;
+  }
+  __syncthreads();
+  const int hsel = select_hop(dopred, H, B, b, false);   // feval: the last hop is not forced
+  const bool labelled = bce_labelled(s_id, ng);
+  for (int r = H; r < H + 2; ++r) {
+    float acc = 0.f;
+    if (labelled)
+      for (int k = tid; k < K; k += kMT) {
+        const float x = row_val(lg, hs, H, r, hsel, k);
+        acc = __fadd_rn(acc, bce_term(x, bce_target(s_id, s_w, ng, k), expf(-fabsf(x))));
+      }
+    acc = block_sum(acc, s_sum);
+    if (tid == 0) rowf[(size_t)b * (H + 2) + (r - H)] = acc;
+  }
+}
+
 // out[r][b] = score of the 1-based answer ans[r][b] against sample b's set; one thread per (r, b)
 __global__ __launch_bounds__(kMT) void k_answer_scores(int R, int B, int K, const int32_t* __restrict__ ans,
     const int32_t* __restrict__ ids, const float* __restrict__ score, int G, float* __restrict__ out) {
@@ -290,6 +331,9 @@ hipError_t step_stats(hipStream_t st, int H, int B, int K, const float* logits, 
   else
     hipLaunchKernelGGL(k_step_stats_rows, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, argmax, t.labels,
                        rowf, rowi);
+  if (t.bce())   // the two merged rows' losses under the sigmoid criterion, in place of the softmax CE just written
+    hipLaunchKernelGGL(k_step_stats_bce, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, t.labels, t.ids, t.w,
+                       t.G, rowf);
   hipLaunchKernelGGL(k_step_stats_reduce, dim3(1), dim3(kMT), 0, st, H, B, lossrow, rowf, rowi, out);
   if (t.G > 0) hipLaunchKernelGGL(k_score_totals, dim3(1), dim3(kMT), 0, st, H + 2, B, rowscore, tot);
   return hipGetLastError();

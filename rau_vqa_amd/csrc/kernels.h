@@ -400,22 +400,37 @@ hipError_t ce_set_fwd(hipStream_t st, int nB, int K, int M, const float* logits,
                       const float* w, int G, const float* mf, const float* wd, const float* bd, float* dl,
                       float* lossrow, int32_t* argmax, float* dopred, const float* part = nullptr,
                       int nsplit = 0, const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0);
+// The criterion head as a per-answer sigmoid with binary cross-entropy (bce_head.hip, RAU_LOSS_BCE): ce_fwd's /
+// ce_set_fwd's contract with  t[k] = [k == y]  (labels) or  min(1, sum_g w_g [y_g == k])  (G > 0: ids / w [Bper][G]),
+// lossrow = sum_k max(x,0) - x t + log1p(exp(-|x|)),  dl = (sigmoid(x) - t) / Bper; a row whose set has no non-empty
+// entry: lossrow 0, dl +0.  labels == nullptr and G == 0: no loss / dl.
+hipError_t bce_fwd(hipStream_t st, int nB, int K, int M, const float* logits, const int32_t* labels,
+                   const int32_t* ids, const float* w, int G, const float* mf, const float* wd, const float* bd,
+                   float* dl, float* lossrow, int32_t* argmax, float* dopred, const float* part = nullptr,
+                   int nsplit = 0, const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0);
 // The ground truth of a batch: what a criterion, a statistic or the selection head's target is read from.  A plain
-// value: "no ground truth" is Truth{}; G > 0 means the answer set replaces the labels.
+// value: "no ground truth" is Truth{}; G > 0 means the answer set replaces the labels.  `loss` is the criterion the
+// answers are trained with (RAU_LOSS_CE / RAU_LOSS_BCE of include/rau.h): read by criterion_head and step_stats only.
 struct Truth {
   const int32_t* labels = nullptr;   // [Bper] device, or null
   const int32_t* ids = nullptr;      // answer set [Bper][G] (G > 0), device
   const float *w = nullptr, *score = nullptr;
   int G = 0;                         // 0 = labels
+  int loss = 0;                      // RAU_LOSS_CE
   bool present() const { return labels || G > 0; }
+  bool bce() const { return loss != 0; }
 };
-// The criterion head against whichever target `t` holds: ce_set_fwd (G > 0) or ce_fwd (labels, or none); the other
-// arguments are the ones the two share.  criterion_class names the launch for the profile.
-inline const char* criterion_class(const Truth& t) { return t.G > 0 ? "ce_set_fwd" : "ce_fwd"; }
+// The criterion head against whichever target `t` holds, with the criterion it names: bce_fwd (RAU_LOSS_BCE), else
+// ce_set_fwd (G > 0) or ce_fwd (labels, or none); the other arguments are the ones they share.  criterion_class
+// names the launch for the profile.
+inline const char* criterion_class(const Truth& t) { return t.bce() ? "bce_fwd" : t.G > 0 ? "ce_set_fwd" : "ce_fwd"; }
 inline hipError_t criterion_head(hipStream_t st, int nB, int K, int M, const float* logits, const Truth& t,
                                  const float* mf, const float* wd, const float* bd, float* dl, float* lossrow,
                                  int32_t* argmax, float* dopred, const float* part = nullptr, int nsplit = 0,
                                  const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0) {
+  if (t.bce())
+    return bce_fwd(st, nB, K, M, logits, t.labels, t.ids, t.w, t.G, mf, wd, bd, dl, lossrow, argmax, dopred, part,
+                   nsplit, bias, logits_out, Bper);
   if (t.G > 0)
     return ce_set_fwd(st, nB, K, M, logits, t.ids, t.w, t.G, mf, wd, bd, dl, lossrow, argmax, dopred, part, nsplit,
                       bias, logits_out, Bper);
@@ -488,7 +503,8 @@ hipError_t clip_adam(hipStream_t st, size_t n, float* x, float* g, float* m, flo
 // out = loss[H+2] | loss_do_pred[H] | int32 counts[4H+3]
 // against t's labels, or (G > 0) its answer set ids / w / score [B][G]: "correct" = the row's first-max answer
 // carries a positive score, uni / select CE are the soft CE of ce_set_fwd; a set also gives the metric score of
-// every row's answer, rowscore [H+2][B] (feval rule), and their fixed-order batch sums tot [H+2] (labels: unused)
+// every row's answer, rowscore [H+2][B] (feval rule), and their fixed-order batch sums tot [H+2] (labels: unused).
+// t.bce(): the uni / select losses are bce_fwd's criterion of those rows instead; nothing else changes
 hipError_t step_stats(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
                       const int32_t* argmax, const float* lossrow, const Truth& t, float* rowf, int32_t* rowi,
                       float* out, float* rowscore, float* tot);

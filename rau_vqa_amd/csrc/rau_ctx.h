@@ -229,9 +229,10 @@ struct StepKey {
   bool mrg = false;             // ... and a step with a non-zero merge_w has the merge_grad launch
   // ... and under RAU_XDROP_TIED a train-mode step has one masked map, one conv group and the summed conv gradients
   bool tied_x = false;
+  int ans_loss = 0;             // ... and the head kernel is the answer criterion's (rau_set_answer_loss)
   auto tied() const {
     return std::tie(mode, max_len, active, zero, mexplicit[0], mexplicit[1], mexplicit[2], mexplicit[3], mexplicit[4],
-                    slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg, tied_x);
+                    slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg, tied_x, ans_loss);
   }
   bool operator==(const StepKey& o) const { return tied() == o.tied(); }
 };
@@ -328,6 +329,9 @@ struct rau_ctx {
   bool fwd_tied = false;            // the last forward was a train-mode one under RAU_XDROP_TIED: summed conv gradients
   const float* x_shared = nullptr;  // ... and i_embed's input then: xd (the one masked map) or, without a mask, xw
   float* dS_sum = nullptr;          // [cap][A][Sp] sum of the active hops' dS (tied_bwd.hip), allocated with the switch
+  // the answer criterion of the step path (rau_set_answer_loss): RAU_LOSS_CE, or RAU_LOSS_BCE = per-answer sigmoid.
+  // Read through step_truth() only; the module-level criteria name theirs themselves.
+  int answer_loss = RAU_LOSS_CE;
   bool yq_shared = false; // no dropout on q (evaluate mode): q_embed's question half is hop-invariant, rows of hop 0 only
   float *WiT, *WpT;   // i_embed / ifeatproj weights transposed ([D][M], [M][A]), refreshed per forward
   float *P0;          // [B][A][S] hop-invariant attention pre-activation (evaluate mode)
@@ -442,11 +446,17 @@ inline LinOpts lin_opts(const rau_ctx* ctx, const StreamWs& ws) {
   o.slab_floats = ws.floats;
   return o;
 }
+// The resident batch's ground truth with the criterion the step path trains it with (rau_set_answer_loss)
+inline Truth step_truth(const rau_ctx* ctx) {
+  Truth t = truth_of(cur_batch(ctx));
+  t.loss = ctx->answer_loss;
+  return t;
+}
 // The hop outputs now hold the results of the forward just enqueued: rau_step_stats / rau_predict may
 // read them until the next forward, module-level call or upload into the batch slot it read.
 inline void merge_record(rau_ctx* ctx) {
   ctx->mg.valid = true;
-  ctx->mg.truth = truth_of(cur_batch(ctx));
+  ctx->mg.truth = step_truth(ctx);
   ctx->mg.slot = ctx->cur_slot;
   ctx->mg.serial = ctx->slot_serial[ctx->cur_slot];
   ++ctx->mg.fwd;

@@ -788,6 +788,27 @@ int rau_feat_dropout(rau_ctx* ctx, int* kind) {
   return RAU_OK;
 }
 
+// ------------------------------------------------------ answer criterion
+// The forward's head reads ctx->answer_loss through step_truth(); the merged-hops record carries the kind of the
+// forward it describes (MergeState::truth), the graph key the kind a step was captured under.  Nothing is allocated
+// and nothing else depends on the kind.
+int rau_set_answer_loss(rau_ctx* ctx, int kind) {
+  NEED(ctx, "null ctx");
+  NEED(kind == RAU_LOSS_CE || kind == RAU_LOSS_BCE,
+       "rau_set_answer_loss: kind %d is neither RAU_LOSS_CE nor RAU_LOSS_BCE", kind);
+  if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_answer_loss: a step is being captured");
+  if (kind == ctx->answer_loss) return RAU_OK;
+  ctx->answer_loss = kind;
+  ctx->fwd_done = false;   // dl and the loss rows are the other criterion's: no backward, no statistics without
+  ctx->mg.valid = false;   // a new forward
+  return RAU_OK;
+}
+int rau_answer_loss(rau_ctx* ctx, int* kind) {
+  NEED(ctx && kind, "null argument");
+  *kind = ctx->answer_loss;
+  return RAU_OK;
+}
+
 // ------------------------------------------------------------- batch size
 int rau_batch_size(rau_ctx* ctx, int32_t* n, int32_t* capacity) {
   NEED(ctx, "null ctx");
@@ -1481,7 +1502,7 @@ int rau_forward(rau_ctx* ctx) {
   // Evaluate mode: dropout is the identity, so I is hop-invariant and computed once.
   HIPC(hipMemsetAsync(ctx->cc, 0, BR_ * sizeof(float), st));  // att_c, att_h zeros SS:362-365
   HIPC(hipMemsetAsync(ctx->hh, 0, BR_ * sizeof(float), st));
-  const Truth truth = truth_of(bs);
+  const Truth truth = step_truth(ctx);
   // rows the logits region of the head's workspace holds (hop_forward_head: a quarter of the side stream's slab)
   const int head_max = (int)std::max<size_t>(1, ctx->ws_side.floats / 4 / ((size_t)B * c.K));
   int gstart = 0;
@@ -1584,7 +1605,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   // step reads the resident batch, which rau_graph_step_select has checked)
   if ((sel || mrg) && !ctx->capturing)
     if (int rc = merge_state(ctx, sel ? "rau_backward_select" : "rau_backward_merged", true)) return rc;
-  const Truth t = ctx->capturing ? truth_of(bs) : ctx->mg.truth;
+  const Truth t = ctx->capturing ? step_truth(ctx) : ctx->mg.truth;
   const rau_config& c = ctx->cfg;
   const int B = c.B, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R,
             K = c.K, H = c.H, Q = ctx->Q;
@@ -1955,6 +1976,10 @@ static int step_loss(rau_ctx* ctx, const char* fn, bool check_hop_w, const float
   if (merge_w) {
     NEED(std::isfinite(merge_w[0]) && std::isfinite(merge_w[1]), "%s: merge_w is not finite", fn);
     if (merge_w[0] == 0.f && merge_w[1] == 0.f) merge_w = nullptr;
+    // the merged rows' terms are cross-entropies (merge_grad.hip): not part of a step trained with RAU_LOSS_BCE
+    NEED(!merge_w || ctx->answer_loss == RAU_LOSS_CE,
+         "%s: a non-zero merge_w under RAU_LOSS_BCE (rau_set_answer_loss): the merged rows are trained with the "
+         "softmax cross-entropy only", fn);
   }
   const int H = ctx->cfg.H;
   bool any = false, any_att = false;
@@ -2035,6 +2060,7 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
   key.att_targets = bs.held.att_targets;
   key.mrg = loss.merge_w != nullptr;
   key.tied_x = ctx->xdrop == RAU_XDROP_TIED;
+  key.ans_loss = ctx->answer_loss;
   if (int rc = upload_hop_weights(ctx, loss)) return rc;
   ctx->mg.valid = false;
   hipGraphExec_t exec = nullptr;

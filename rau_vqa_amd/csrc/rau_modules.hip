@@ -546,6 +546,41 @@ int rau_criterion_backward_set(rau_ctx* ctx, int h, const float* logits, int32_t
   return criterion(ctx, h, logits, Truth{nullptr, ids_dev, w_dev, nullptr, G}, nullptr, scale, d_logits);
 }
 
+// criteria[h] as the per-answer sigmoid criterion (bce_head.hip), whatever rau_set_answer_loss says: against labels
+// in device memory, or (labels_dev NULL) an answer set in device memory
+static int bce_truth(const char* fn, const int32_t* labels_dev, int32_t G, const int32_t* ids_dev, const float* w_dev,
+                     Truth* t) {
+  if (labels_dev) {
+    *t = Truth{labels_dev};
+  } else {
+    NEED(ids_dev && w_dev, "%s: neither labels nor an answer set", fn);
+    NEED(G >= 1 && G <= kMaxAnswers, "%s: G=%d out of [1,%d]", fn, G, kMaxAnswers);
+    *t = Truth{nullptr, ids_dev, w_dev, nullptr, G};
+  }
+  t->loss = RAU_LOSS_BCE;
+  return RAU_OK;
+}
+
+int rau_criterion_forward_bce(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev, int32_t G,
+                              const int32_t* ids_dev, const float* w_dev, float* loss) {
+  NEED(ctx && logits, "null argument");
+  NEED(h >= 0 && h < ctx->cfg.H, "rau_criterion_forward_bce: h=%d out of [0,%d)", h, ctx->cfg.H);
+  Truth t;
+  if (int rc = bce_truth("rau_criterion_forward_bce", labels_dev, G, ids_dev, w_dev, &t)) return rc;
+  if (int rc = mod_alloc(ctx)) return rc;
+  return criterion(ctx, h, logits, t, loss, 1.f, nullptr);
+}
+
+int rau_criterion_backward_bce(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev, int32_t G,
+                               const int32_t* ids_dev, const float* w_dev, float scale, float** d_logits) {
+  NEED(ctx && logits && d_logits, "null argument");
+  NEED(h >= 0 && h < ctx->cfg.H, "rau_criterion_backward_bce: h=%d out of [0,%d)", h, ctx->cfg.H);
+  Truth t;
+  if (int rc = bce_truth("rau_criterion_backward_bce", labels_dev, G, ids_dev, w_dev, &t)) return rc;
+  if (int rc = mod_alloc(ctx)) return rc;
+  return criterion(ctx, h, logits, t, nullptr, scale, d_logits);
+}
+
 // ------------------------------------------------------------ the merged rows' criteria
 // The step's merge_grad launch (merge_grad.hip) on hop logits and do_pred the caller holds: feval's uni and select
 // rows are built from them under the feval rule and the gradient of  merge_w[0] CE(uni) + merge_w[1] CE(select)  is

@@ -234,6 +234,22 @@ class RAU:
         L.check(self._lib.rau_feat_dropout(self._h, C.byref(k)))
         return k.value == L.XDROP_TIED
 
+    def set_answer_loss(self, kind: str):
+        """The answer criterion of forward() / graph_step() (rau_set_answer_loss): "ce", the reference's softmax
+        cross-entropy (soft-target with an answer set), or "bce": one sigmoid per answer, binary cross-entropy
+        against the labels' one-hot rows or the answer set's soft targets min(1, sum of the weights on an answer)
+        -- predict.soft_bce / soft_bce_grad state it.  Losses are summed over the K answers.  Between steps, in
+        either mode; a change drops the last forward.  A non-zero merge_w is refused under "bce"."""
+        if kind not in L.LOSSES:
+            raise ValueError(f"answer loss {kind!r}: 'ce' or 'bce'")
+        L.check(self._lib.rau_set_answer_loss(self._h, L.LOSSES[kind]))
+
+    @property
+    def answer_loss(self) -> str:
+        k = C.c_int()
+        L.check(self._lib.rau_answer_loss(self._h, C.byref(k)))
+        return "bce" if k.value == L.LOSS_BCE else "ce"
+
     def set_masks(self, masks):
         """masks: site name -> keep flags in Config.mask_shapes' shape for the current batch size (the library
         checks the element count).  With tie_feature_dropout() on, "x" is [B, D, S] or [1, B, D, S]: any other

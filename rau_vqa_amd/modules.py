@@ -120,6 +120,37 @@ class CriterionClone(_Clone):
         return self._view(out, self.rau.batch_size, self.rau.cfg.K)
 
 
+class BCECriterionClone(_Clone):
+    """criteria[h] as the per-answer sigmoid criterion (rau_criterion_forward_bce / _backward_bce; predict.soft_bce):
+    y [B] int32 labels, or y None with answers = (ids [B,G] int32, w [B,G] float32) CUDA tensors.  Independent of
+    RAU.set_answer_loss."""
+
+    @staticmethod
+    def _set(y, answers):
+        if y is not None:
+            return 0, None, None
+        if answers is None:
+            raise ValueError("the sigmoid criterion needs labels or answers=(ids, w)")
+        ids, w = answers[0], answers[1]
+        if ids.dtype != torch.int32 or w.dtype != torch.float32 or ids.shape != w.shape or ids.dim() != 2:
+            raise ValueError("answers: ids int32 [B,G] and w float32 [B,G]")
+        return int(ids.shape[1]), ids, w
+
+    def forward(self, logits, y, answers=None):
+        G, ids, w = self._set(y, answers)
+        loss = C.c_float()
+        L.check(self._lib.rau_criterion_forward_bce(self._h, self.i, _p(logits), _p(y), G, _p(ids), _p(w),
+                                                    C.byref(loss)))
+        return loss.value
+
+    def backward(self, logits, y, answers=None, scale=1.0):
+        G, ids, w = self._set(y, answers)
+        out = C.c_void_p()
+        L.check(self._lib.rau_criterion_backward_bce(self._h, self.i, _p(logits), _p(y), G, _p(ids), _p(w),
+                                                     float(scale), C.byref(out)))
+        return self._view(out, self.rau.batch_size, self.rau.cfg.K)
+
+
 class AttCriterionClone(_Clone):
     """The attention supervision of hop h on the clone's attprob output: mean_b sum_s t (-log(attprob + 1e-12))
     against targets t [B,S] (float32 CUDA tensor), regions [B] int32 or None (joint.att_ce / att_ce_grad)."""
@@ -151,7 +182,8 @@ def merge_criterion_backward(rau, logits, dopred, y, merge_w, d_logits):
     return d_logits
 
 
-def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None, merge_w=None):
+def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None, merge_w=None,
+          loss="ce", answers=None):
     """The tensor half of the reference's feval, loop for loop (SS:443-596), on the clones.
     select_w [H] (None: the reference's zero, SS:566): hop h's multimodal clone receives
     d_do_pred = joint.bce_grad(do_pred_h, argmax_h == y, select_w[h]), which trains the step-selection head.
@@ -165,16 +197,28 @@ def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=Non
     uni and select rows.  Their gradient at the hop logits is computed ONCE, behind the forward loop, by
     merge_criterion_backward on the stacked logits / do_pred, and added to each hop's d_logits (joint.merged_ce_grad).
 
+    loss="bce": criteria[h] is the per-answer sigmoid criterion (BCECriterionClone) against y, or with y None
+    against answers = (ids [B,G] int32, w [B,G] float32); merge_w is refused with it (the merged rows' terms are
+    cross-entropies) and select_w needs labels.  answers is read under "bce" only.
+
     feats [B,D,S] float32, x [T,B] int32, x_len [B] int32, y [B] int32: CUDA tensors.
     Gradients accumulate into the ctx's flat buffers (zero them first).  Returns
     (losses[H], argmax[H,B] as torch tensors of 1-based ids).
     """
     ext = torch.cuda.ExternalStream(rau.stream(), device=feats.device)
     with torch.cuda.stream(ext):   # torch's glue ops join the ctx's own stream order
-        return _feval(rau, feats, x, x_len, y, hop_w, select_w, regions, att_w, att_targets, merge_w)
+        return _feval(rau, feats, x, x_len, y, hop_w, select_w, regions, att_w, att_targets, merge_w, loss, answers)
 
 
-def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None, merge_w=None):
+def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None, merge_w=None,
+           loss="ce", answer_set=None):
+    if loss not in ("ce", "bce"):
+        raise ValueError(f"feval: loss={loss!r}: 'ce' or 'bce'")
+    bce = loss == "bce"
+    if bce and merge_w is not None and any(float(w) != 0.0 for w in merge_w):
+        raise ValueError("feval: merge_w is not available with loss='bce'")
+    if bce and y is None and select_w is not None and any(float(w) != 0.0 for w in select_w):
+        raise ValueError("feval: select_w needs labels")
     if att_w is not None and att_targets is None and any(float(w) != 0.0 for w in att_w):
         raise ValueError("feval: a non-zero att_w needs att_targets")
     c = rau.cfg
@@ -183,6 +227,7 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=No
     rnn = [DeepLSTMClone(rau, t) for t in range(c.T)]
     mm = [MultimodalClone(rau, h) for h in range(c.H)]
     crit = [CriterionClone(rau, h) for h in range(c.H)]
+    bcrit = [BCECriterionClone(rau, h) for h in range(c.H)]
     acrit = [AttCriterionClone(rau, h) for h in range(c.H)]
     max_len = int(x_len.max().item())                      # SS:444
     # ---- encoder forward, SS:446-462
@@ -205,7 +250,7 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=No
         dopred.append(dp)
         att_c.append(cn)
         att_h.append(hn)
-        losses.append(crit[h].forward(lg, y))              # SS:518
+        losses.append(bcrit[h].forward(lg, y, answer_set) if bce else crit[h].forward(lg, y))   # SS:518
         answers.append(torch.argmax(lg, dim=1) + 1)        # SS:488 (ties: see rau_get_argmax)
     # ---- the merged rows' criteria: every hop's scaled d_logits, plus the uni and select terms in one launch
     d_merged = None
@@ -216,7 +261,10 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=No
     d_c = d_h = None                                       # zeros, SS:561-562
     d_q = torch.zeros(rau.batch_size, c.Q, device=dev)
     for h in reversed(range(c.H)):
-        dl = crit[h].backward(logits[h], y, float(hop_w[h])) if d_merged is None else d_merged[h]   # SS:565-569
+        if bce:
+            dl = bcrit[h].backward(logits[h], y, answer_set, float(hop_w[h]))
+        else:
+            dl = crit[h].backward(logits[h], y, float(hop_w[h])) if d_merged is None else d_merged[h]   # SS:565-569
         d_dp = None                                        # d_do_pred:mul(0), SS:566
         if select_w is not None and float(select_w[h]) != 0.0:
             gt = (answers[h] == y).to(torch.float32)       # do_pred_gt, SS:490, 497

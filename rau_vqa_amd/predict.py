@@ -138,6 +138,77 @@ def soft_ce_grad(pred, ids, w):
     return g
 
 
+def bce_target(ids, w, K):
+    """Target of the per-answer sigmoid criterion (rau_set_answer_loss, RAU_LOSS_BCE) for the answer set ids [B, G]
+    (1-based, 0 = empty entry; clamped into [0, K] as the device clamps them), w [B, G]: t [B, K] float32 with
+    t[b, k] = min(1, sum_g w[b, g] [ids[b, g] - 1 == k]) over the non-empty entries, added from 0 in g order in
+    float32, then clamped.  Bit for bit the device's target."""
+    ids = np.clip(np.asarray(ids, np.int64), 0, K)
+    w = np.asarray(w, np.float32)
+    B = ids.shape[0]
+    t = np.zeros((B, K), np.float32)
+    ar = np.arange(B)
+    for g in range(ids.shape[1]):
+        live = ids[:, g] > 0
+        col = np.maximum(ids[:, g], 1) - 1
+        t[ar[live], col[live]] = t[ar[live], col[live]] + w[live, g]     # one entry per row: no aliasing
+    return np.minimum(t, np.float32(1))
+
+
+def bce_target_labels(labels, K):
+    """bce_target of the one-entry sets {(y, 1)}: t[b, k] = [k == y_b - 1], labels 1-based, clamped into [1, K]."""
+    y = np.clip(np.asarray(labels, np.int64), 1, K)
+    return bce_target(y[:, None], np.ones((y.shape[0], 1), np.float32), K)
+
+
+def _block_sum(terms):
+    """Sum over the last axis in the order of the device's criterion heads: 256 partials, partial i adding the
+    entries i, i + 256, .. in ascending order from 0, then an xor butterfly over each group of 64 partials (offsets
+    32 .. 1) and (w0 + w1) + (w2 + w3).  In the dtype of terms."""
+    K = terms.shape[-1]
+    pad = (-K) % 256
+    x = np.concatenate([terms, np.zeros(terms.shape[:-1] + (pad,), terms.dtype)], axis=-1)
+    x = x.reshape(terms.shape[:-1] + (-1, 256))
+    part = np.zeros(terms.shape[:-1] + (256,), terms.dtype)
+    for i in range(x.shape[-2]):
+        part = part + x[..., i, :]
+    v = part.reshape(terms.shape[:-1] + (4, 64))
+    lane = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[..., lane ^ o]
+    wv = v[..., 0]
+    return (wv[..., 0] + wv[..., 1]) + (wv[..., 2] + wv[..., 3])
+
+
+def soft_bce(pred, ids, w, dtype=np.float32):
+    """The per-answer sigmoid criterion of RAU_LOSS_BCE on rows pred [B, K] against the answer set ids / w [B, G]:
+    (rows [B], their mean) with rows[b] = sum_k max(x,0) - x t + log1p(exp(-|x|)), t = bce_target -- summed over K,
+    not divided by K.  A row whose set has no non-empty entry is unlabelled: 0.  Labels y [B]: ids = y[:, None],
+    w = 1.  dtype float32 (the default) computes every step in float32 and sums in the device's order; the
+    exponential and the logarithm are numpy's, so this is a reference to a few ulp, not a bit statement."""
+    x = np.asarray(pred, dtype)
+    K = x.shape[1]
+    t = bce_target(ids, w, K).astype(dtype)
+    e = np.exp(-np.abs(x))
+    term = ((np.maximum(x, 0) - x * t) + np.log1p(e)).astype(dtype)
+    rows = _block_sum(term)
+    rows = np.where((np.asarray(ids) > 0).any(axis=1), rows, 0).astype(dtype)
+    return rows, dtype(rows.sum(dtype=dtype) / dtype(x.shape[0]))
+
+
+def soft_bce_grad(pred, ids, w, dtype=np.float32):
+    """d mean(soft_bce rows) / d pred as the device forms it: (sigmoid(x) - t) / B with the sigmoid from
+    e = exp(-|x|) as x >= 0 ? 1 / (1 + e) : e / (1 + e) -- finite for every finite x; +0 on unlabelled rows."""
+    x = np.asarray(pred, dtype)
+    B, K = x.shape
+    t = bce_target(ids, w, K).astype(dtype)
+    e = np.exp(-np.abs(x))
+    d = dtype(1) + e
+    sg = np.where(x >= 0, dtype(1) / d, e / d).astype(dtype)
+    g = ((sg - t) * (dtype(1) / dtype(B))).astype(dtype)
+    return np.where((np.asarray(ids) > 0).any(axis=1)[:, None], g, dtype(0)).astype(dtype)
+
+
 def answer_score(ans, ids, score):
     """Metric score of the answers ans [..., B] (1-based) against the set: sum_g score[b,g] * [ids[b,g] == ans],
     float32, added from 0 in g order; empty entries (id 0) never match.  Bit for bit what rau_step_scores /
@@ -164,10 +235,14 @@ def set_correct(ans, ids, score):
     return ok
 
 
-def set_stats(logits, dopred, ids, w, score=None):
+def set_stats(logits, dopred, ids, w, score=None, loss="ce"):
     """joint.feval_stats for a batch with an answer set (rau_step_stats with a set): the same keys, with
     set_correct in place of (argmax == y) and soft_ce in place of the cross-entropy, plus ``score`` [H+2, B]:
-    answer_score of every row's answer (what rau_step_scores returns)."""
+    answer_score of every row's answer (what rau_step_scores returns).  loss="bce": the statistics of a step under
+    RAU_LOSS_BCE -- ``loss`` is soft_bce of every row; everything else does not depend on the criterion."""
+    if loss not in ("ce", "bce"):
+        raise ValueError(f"loss={loss!r}: 'ce' or 'bce'")
+    row_loss = soft_bce if loss == "bce" else soft_ce
     logits = np.asarray(logits, np.float32)
     dopred = np.asarray(dopred, np.float32)
     score = np.asarray(w if score is None else score, np.float32)
@@ -187,7 +262,7 @@ def set_stats(logits, dopred, ids, w, score=None):
     ans = np.stack([first_max(r) for r in rows])
     ok = set_correct(ans, ids, score)
     did = ok[:H].any(0)
-    loss = np.array([soft_ce(r, ids, w)[1] for r in rows], np.float32)
+    loss = np.array([row_loss(r, ids, w)[1] for r in rows], np.float32)
     ldp, dpc = [], []
     for h in range(H):
         t = ok[h].astype(np.float32)
