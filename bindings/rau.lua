@@ -151,6 +151,8 @@ int rau_dev_sqrt(rau_ctx* ctx, float* x, size_t n);
 int rau_dev_add_scalar(rau_ctx* ctx, float* x, size_t n, float value);
 int rau_dev_adam(rau_ctx* ctx, float* x, const float* dx, float* m, float* v, size_t n, float lr,
                  float beta1, float beta2, float eps, int32_t t);
+int rau_dev_adamax(rau_ctx* ctx, float* x, const float* dx, float* m, float* u, size_t n, float lr,
+                   float beta1, float beta2, float eps, int32_t t);
 int rau_dev_select_rows(rau_ctx* ctx, float* dst, const float* src, int32_t rows, int32_t cols,
                         const int32_t* key_dev, int32_t value);
 int rau_dev_rowmax(rau_ctx* ctx, const float* x, int32_t rows, int32_t cols, float* max_dev,
@@ -180,6 +182,15 @@ int rau_topk(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf);
 int rau_noise_clip_adam(rau_ctx* ctx, int64_t step_t, float lr, float mult_lr,
                         float beta1, float beta2, float eps, float eta, float gamma,
                         float clip, uint64_t noise_seed, float* out_norms);
+typedef struct rau_update_opts {
+  int32_t rule, clip_scope;
+  float lr, mult_lr, beta1, beta2, eps, eta, gamma, clip;
+  uint64_t noise_seed;
+} rau_update_opts;
+void rau_update_opts_default(rau_update_opts* o);
+int rau_update(rau_ctx* ctx, int64_t step_t, const rau_update_opts* o, float* out_norms);
+int rau_get_opt_state(rau_ctx* ctx, int group, float* m, float* v, int64_t* t, int32_t* rule);
+int rau_set_opt_state(rau_ctx* ctx, int group, const float* m, const float* v, int64_t t, int32_t rule);
 int rau_stream(rau_ctx* ctx, void** hip_stream);
 int rau_wait_grads(rau_ctx* ctx, int group, void* hip_stream);
 int rau_comm_unique_id(void* id, size_t bytes);
@@ -555,6 +566,39 @@ function RAU:update(step_t, lr, mult_lr, eta, gamma, clip, seed)
   return norms[0], norms[1], norms[2]
 end
 
+-- the same step with a rule and a clip scope (rau_update): opts = { rule = 'adam' | 'adamax', clip_scope =
+-- 'group' | 'global', step_t =, lr =, mult_lr =, beta1 =, beta2 =, eps =, eta =, gamma =, clip =, seed = }; what
+-- is left out keeps rau_update_opts_default's value.  'adam' with 'group' is rau:update, bit for bit; 'adamax' and
+-- 'global' are not in the reference.  Returns the three group norms and the global norm.
+local RULE = { adam = 0, adamax = 1 }
+local SCOPE = { group = 0, global = 1 }
+function RAU:updateWith(opts)
+  local o = ffi.new('rau_update_opts[1]')
+  C.rau_update_opts_default(o)
+  if opts.rule then o[0].rule = assert(RULE[opts.rule], 'updateWith: unknown rule') end
+  if opts.clip_scope then o[0].clip_scope = assert(SCOPE[opts.clip_scope], 'updateWith: unknown clip_scope') end
+  for _, k in ipairs({ 'lr', 'mult_lr', 'beta1', 'beta2', 'eps', 'eta', 'gamma', 'clip' }) do
+    if opts[k] then o[0][k] = opts[k] end
+  end
+  if opts.seed then o[0].noise_seed = opts.seed end
+  local norms = ffi.new('float[4]')
+  check(C.rau_update(self.h, opts.step_t or 0, o, norms))
+  return norms[0], norms[1], norms[2], norms[3]
+end
+
+-- optimizer state of one group: m, v (FloatTensors of the group's length, filled; v holds the u of adamax),
+-- then t and the rule name.  Before the first update: zeros, 0, 'adam'.
+function RAU:optState(group, m, v)
+  local t, r = ffi.new('int64_t[1]'), ffi.new('int32_t[1]')
+  check(C.rau_get_opt_state(self.h, GROUP[group], m and m:data() or nil, v and v:data() or nil, t, r))
+  return tonumber(t[0]), (r[0] == 1) and 'adamax' or 'adam'
+end
+-- rau:setOptState(group, m, v, t, rule); m = v = nil with t = 0 resets the group to `rule`
+function RAU:setOptState(group, m, v, t, rule)
+  check(C.rau_set_opt_state(self.h, GROUP[group], m and m:data() or nil, v and v:data() or nil, t or 0,
+                            assert(RULE[rule or 'adam'], 'setOptState: unknown rule')))
+end
+
 -- answers: IntTensor [H,B] of 1-based class ids (torch.max first-max rule, SS:488)
 function RAU:answers(out) check(C.rau_get_argmax(self.h, out:data())); return out end
 function RAU:logits(out) check(C.rau_get_logits(self.h, out:data())); return out end
@@ -838,6 +882,19 @@ function RAU.adam(x, dx, lr, beta1, beta2, epsilon, state)
   state.t = state.t + 1
   check(C.rau_dev_adam(x.rau.h, x.ptr, dx.ptr, state.m.ptr, state.v.ptr, x:nElement(), lr, beta1, beta2,
                        epsilon, state.t))
+end
+-- its twin for adamax (not in the reference; the element arithmetic of rau:updateWith{rule = 'adamax'}):
+-- state.m / state.u / state.t, kept as RAU.adam keeps its own
+function RAU.adamax(x, dx, lr, beta1, beta2, epsilon, state)
+  beta1, beta2, epsilon = beta1 or 0.9, beta2 or 0.999, epsilon or 1e-8
+  if not state.m then
+    state.t = 0
+    state.m = Tensor.new(x.rau, x:nElement())
+    state.u = Tensor.new(x.rau, x:nElement())
+  end
+  state.t = state.t + 1
+  check(C.rau_dev_adamax(x.rau.h, x.ptr, dx.ptr, state.m.ptr, state.u.ptr, x:nElement(), lr, beta1, beta2,
+                         epsilon, state.t))
 end
 
 -- Module-level clones ---------------------------------------------------------

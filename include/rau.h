@@ -768,6 +768,11 @@ int rau_dev_sqrt(rau_ctx* ctx, float* x, size_t n);
 int rau_dev_add_scalar(rau_ctx* ctx, float* x, size_t n, float value);
 int rau_dev_adam(rau_ctx* ctx, float* x, const float* dx, float* m, float* v, size_t n, float lr,
                  float beta1, float beta2, float eps, int32_t t);
+/* Its twin for Adamax (not in the reference; the rule of rau_update's RAU_OPT_ADAMAX, same element arithmetic):
+ * m = beta1 m + (1-beta1) dx; u = max(beta2 u, |dx| + eps); x -= lr / (1-beta1^t) m / u.  Any n, any 4-byte-aligned
+ * pointers (16-byte accesses when all four allow). */
+int rau_dev_adamax(rau_ctx* ctx, float* x, const float* dx, float* m, float* u, size_t n, float lr,
+                   float beta1, float beta2, float eps, int32_t t);
 /* dst[k,:] = src[k,:] for the rows k with key_dev[k] == value (SS:455-461, 584-591) */
 int rau_dev_select_rows(rau_ctx* ctx, float* dst, const float* src, int32_t rows, int32_t cols,
                         const int32_t* key_dev, int32_t value);
@@ -878,6 +883,48 @@ int rau_noise_clip_adam(rau_ctx* ctx, int64_t step_t, float lr, float mult_lr,
                         float beta1, float beta2, float eps, float eta,
                         float gamma, float clip, uint64_t noise_seed,
                         float* out_norms);
+
+/* ---- update with a rule and a clip scope; optimizer state in and out --------------------------
+ * rau_update is the same step with two choices.  RAU_OPT_ADAM with RAU_CLIP_GROUP is what the reference does
+ * (SS:597-630: noise, one L2 clip per parameter group, then adam on each flat vector, SS:770-772) and gives
+ * the bits of rau_noise_clip_adam on the same state and arguments: weights, gradients, moments, out_norms[0..2].
+ * RAU_OPT_ADAMAX and RAU_CLIP_GLOBAL are NOT in the reference; they are the update of the bottom-up / top-down
+ * recipe: Adamax, and one gradient norm clipped over the whole model.
+ *   noise    the generator, counters and key (noise_seed + 3 step_t + group) of rau_noise_clip_adam in every rule
+ *            and scope; eta = 0 disables it.
+ *   norms    out_norms[4] (host, may be NULL): [0..2] the groups' pre-clip norms, [3] the global norm
+ *            sqrtf((s_embed + s_rnn) + s_mult) of the three f32 sums of squares, written in both scopes.
+ *   clip     scale = norm > clip ? clip / norm : 1 with the group's norm (GROUP) or the global norm for all three
+ *            groups (GLOBAL); the clipped gradient is written back.
+ *   ADAMAX   m = beta1 m + (1-beta1) g;  u = max(beta2 u, |g| + eps);  x -= (group_lr / (1 - beta1^t)) m / u, with u
+ *            kept where Adam keeps v, starting at 0 (torch.optim.Adamax's statement); the step size is formed on
+ *            the host in double, as Adam's is.
+ * A group's optimizer state (m, v, t) belongs to the rule that last wrote it: an update with the other rule while
+ * that group's t > 0 is RAU_ERR_STATE -- rau_noise_clip_adam on Adamax state included; reset the state first
+ * (rau_set_opt_state).  An unknown rule or scope, clip <= 0, gamma <= 0, eta < 0, step_t < 0: RAU_ERR_INVALID.
+ * In every error case nothing is launched and nothing changes.  At most two launches (update.hip), under the
+ * names upd_noise_sqnorm and upd_apply in rau_prof_entry.  Synchronising only with out_norms. */
+#define RAU_OPT_ADAM 0     /* the arithmetic of rau_noise_clip_adam */
+#define RAU_OPT_ADAMAX 1
+#define RAU_CLIP_GROUP 0   /* one norm per parameter group (the reference, SS:597-630) */
+#define RAU_CLIP_GLOBAL 1  /* one norm over the three groups together */
+typedef struct rau_update_opts {
+  int32_t rule, clip_scope;
+  float lr, mult_lr, beta1, beta2, eps, eta, gamma, clip;
+  uint64_t noise_seed;
+} rau_update_opts;
+/* RAU_OPT_ADAM, RAU_CLIP_GROUP, lr 3e-3, mult_lr 3e-4, betas 0.9 / 0.999, eps 1e-8, eta 0.01, gamma 0.55,
+ * clip 0.1, noise_seed 0 */
+void rau_update_opts_default(rau_update_opts* o);
+int rau_update(rau_ctx* ctx, int64_t step_t, const rau_update_opts* o, float* out_norms);
+/* The optimizer state of one group, host side: m, v [n of rau_params] (v holds Adamax's u), t = updates so far,
+ * rule = the rule that owns the state.  Before the first update the moments read as zeros, t = 0, rule =
+ * RAU_OPT_ADAM; any output may be NULL, and a reader allocates nothing.  rau_set_opt_state allocates the moments if
+ * need be; m = v = NULL with t = 0 resets the group (zero moments, t = 0) to `rule`: the way to change rule.
+ * RAU_ERR_INVALID, nothing changed: t < 0, t > 0 without both vectors, an unknown rule.  Both synchronise, as
+ * rau_get_params does.  The state survives rau_set_batch_size. */
+int rau_get_opt_state(rau_ctx* ctx, int group, float* m, float* v, int64_t* t, int32_t* rule);
+int rau_set_opt_state(rau_ctx* ctx, int group, const float* m, const float* v, int64_t t, int32_t rule);
 
 /* ---- data-parallel exchange (new: the reference is single-GPU) --------------------
  * One process and one rau_ctx per GPU.  Rank 0 obtains a communicator id and hands it to

@@ -34,6 +34,19 @@ class RauConfig(C.Structure):
                [("dtype", C.c_int32), ("device_id", C.c_int32)]
 
 
+OPT_ADAM, OPT_ADAMAX = 0, 1
+OPT_RULES = {"adam": OPT_ADAM, "adamax": OPT_ADAMAX}
+CLIP_GROUP, CLIP_GLOBAL = 0, 1
+CLIP_SCOPES = {"group": CLIP_GROUP, "global": CLIP_GLOBAL}
+
+
+class RauUpdateOpts(C.Structure):
+    """Mirror of ``rau_update_opts`` (include/rau.h)."""
+    _fields_ = [("rule", C.c_int32), ("clip_scope", C.c_int32)] + \
+               [(n, C.c_float) for n in ("lr", "mult_lr", "beta1", "beta2", "eps", "eta", "gamma", "clip")] + \
+               [("noise_seed", C.c_uint64)]
+
+
 class RauError(RuntimeError):
     pass
 
@@ -178,6 +191,8 @@ _SIGS = {
     "rau_dev_add_scalar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float]),
     "rau_dev_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32]),
+    "rau_dev_adamax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32]),
     "rau_dev_select_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_void_p, C.c_int32]),
     "rau_dev_rowmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
@@ -207,6 +222,12 @@ _SIGS = {
     "rau_topk": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_noise_clip_adam": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_float] * 8 +
                             [C.c_uint64, C.c_void_p]),
+    # the update with a rule and a clip scope; optimizer state in and out
+    "rau_update_opts_default": (None, [C.POINTER(RauUpdateOpts)]),
+    "rau_update": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(RauUpdateOpts), C.c_void_p]),
+    "rau_get_opt_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int32)]),
+    "rau_set_opt_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     "rau_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_wait_grads": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "rau_comm_unique_id": (C.c_int, [C.c_void_p, C.c_size_t]),

@@ -498,6 +498,25 @@ hipError_t finish_norm(hipStream_t st, int nparts, const float* partial, float* 
 hipError_t clip_adam(hipStream_t st, size_t n, float* x, float* g, float* m, float* v,
                      const float* norm, float clip, float stepsize, float beta1, float beta2,
                      float eps);
+// The same update with all three groups in every launch (update.hip, rau_update): the groups' pointers travel
+// by value and blockIdx.y names the group.  Two launches: upd_noise_sqnorm leaves kUpdParts partial sums of
+// squares per group (add_noise_sqnorm's, in its order); upd_apply finishes the norms in every workgroup
+// (finish_norm's order), writes norms[0..2] = group norms and norms[3] = sqrtf((s0 + s1) + s2), clips by the
+// group's norm or (global_clip) by norms[3], and applies the rule.  16-byte accesses where a group's four
+// pointers allow, scalar otherwise and for a tail of n % 4 elements.
+constexpr int kUpdParts = 1024;
+struct UpdGroups {
+  float *x[3], *g[3], *m[3], *v[3];
+  size_t n[3];
+  float step[3];       // the rule's step size with its bias correction, formed on the host in double
+  uint64_t seed[3];    // noise key of the group
+};
+hipError_t upd_noise_sqnorm(hipStream_t st, const UpdGroups& G, float nstd, float* partial /* [3][kUpdParts] */);
+hipError_t upd_apply(hipStream_t st, const UpdGroups& G, int rule /* rau_opt_rule */, bool global_clip, float clip,
+                     float beta1, float beta2, float eps, const float* partial, float* norms /* [4] */);
+// Adamax on one flat vector (rau_dev_adamax): adamax_elem on dx as it stands; any n, any 4-byte-aligned pointers
+hipError_t adamax_vec(hipStream_t st, size_t n, float* x, const float* dx, float* m, float* u, float stepsize,
+                      float beta1, float beta2, float eps);
 // feval's statistics of the resident hop outputs (hop_merge.hip, SS:476-556): per-sample rows
 // rowf [B][H+2], rowi [B][4H+3], then one fixed-order batch reduction into
 // out = loss[H+2] | loss_do_pred[H] | int32 counts[4H+3]

@@ -8,6 +8,7 @@
 
 #include "kernels.h"
 #include "philox.h"
+#include "update_elem.h"
 
 namespace rau {
 
@@ -2164,14 +2165,7 @@ hipError_t lin_reduce_epilogue(hipStream_t st, int M, int N, int splits, const f
 }
 
 // --------------------------------------------------- noise / clip / Adam (next-1)
-__device__ __forceinline__ float2 box_muller(uint32_t a, uint32_t b) {
-  const float u1 = ((a >> 8) + 1) * (1.0f / 16777216.0f);  // (0,1]
-  const float u2 = (b >> 8) * (1.0f / 16777216.0f);
-  const float r = sqrtf(-2.f * logf(u1));
-  float s, c;
-  sincosf(6.28318530717958647692f * u2, &s, &c);
-  return make_float2(r * c, r * s);
-}
+// the element arithmetic lives in update_elem.h, shared with update.hip: same statements, same bits
 __global__ void k_add_noise_sqnorm(size_t n, float* __restrict__ g, float nstd, uint64_t seed,
                                    uint32_t stream, float* __restrict__ partial) {
   RAU_CHAIN_PRIO();
@@ -2179,20 +2173,11 @@ __global__ void k_add_noise_sqnorm(size_t n, float* __restrict__ g, float nstd, 
   float acc = 0.f;
   for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q * 4 < n;
        q += (size_t)gridDim.x * blockDim.x) {
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (nstd > 0.f) {
-      const Philox4 o = philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), stream, 0xA5A5u,
-                                      (uint32_t)seed, (uint32_t)(seed >> 32));
-      const float2 n0 = box_muller(o.v[0], o.v[1]), n1 = box_muller(o.v[2], o.v[3]);
-      z[0] = n0.x; z[1] = n0.y; z[2] = n1.x; z[3] = n1.y;
-    }
+    float z[4];
+    noise_quad(q, stream, seed, nstd, z);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (q * 4 + j < n) {
-        const float v = g[q * 4 + j] + z[j] * nstd;
-        g[q * 4 + j] = v;
-        acc += v * v;
-      }
+      if (q * 4 + j < n) g[q * 4 + j] = noise_elem(g[q * 4 + j], z[j], nstd, acc);
   }
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = acc;
@@ -2225,17 +2210,16 @@ __global__ void k_clip_adam(size_t n, float* __restrict__ x, float* __restrict__
                             const float* __restrict__ norm, float clip, float stepsize,
                             float beta1, float beta2, float eps) {
   RAU_CHAIN_PRIO();
-  const float nv = norm[0];
-  const float sc = nv > clip ? clip / nv : 1.f;
+  const float sc = clip_scale(norm[0], clip);
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
        i += (size_t)gridDim.x * blockDim.x) {
     const float gi = g[i] * sc;
     g[i] = gi;
-    const float mi = m[i] * beta1 + (1.f - beta1) * gi;
-    const float vi = v[i] * beta2 + (1.f - beta2) * gi * gi;
+    float mi = m[i], vi = v[i], xi = x[i];
+    adam_elem(gi, mi, vi, xi, stepsize, beta1, beta2, eps);
     m[i] = mi;
     v[i] = vi;
-    x[i] -= stepsize * mi / (sqrtf(vi) + eps);
+    x[i] = xi;
   }
 }
 hipError_t clip_adam(hipStream_t st, size_t n, float* x, float* g, float* m, float* v,

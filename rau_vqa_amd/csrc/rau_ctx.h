@@ -54,10 +54,11 @@ struct Entry {
 struct Group {
   float* w = nullptr;
   float* g = nullptr;
-  float* m = nullptr;  // Adam moments (allocated on first update)
+  float* m = nullptr;  // optimizer moments (allocated on first update or rau_set_opt_state); v holds Adamax's u
   float* v = nullptr;
   size_t n = 0;
-  int64_t adam_t = 0;
+  int64_t adam_t = 0;  // updates so far, of either rule
+  int opt_rule = RAU_OPT_ADAM;   // the rule that owns m, v, adam_t: the other one is refused while adam_t > 0
   std::vector<Entry> layout;
 };
 struct ProfRec {
@@ -393,6 +394,7 @@ struct rau_ctx {
   MergeState mg;                 // merged hops (rau_merge.hip): what may be read of the last forward
   // update
   float *npart = nullptr, *norms_d = nullptr;
+  float* upd_part = nullptr;     // rau_update's partial sums of squares, [3][kUpdParts]
   bool fwd_done = false, bwd_done = false;
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -562,6 +562,7 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   CK(dalloc(ctx, &ctx->dkey, (size_t)2, false));   // (seed, step) outlive a resize
   CK(dalloc(ctx, &ctx->npart, (size_t)1024));
   CK(dalloc(ctx, &ctx->norms_d, (size_t)4));
+  CK(dalloc(ctx, &ctx->upd_part, (size_t)3 * kUpdParts));
 #undef CK
   {
     hipError_t es = hipStreamSynchronize(ctx->st);
@@ -2217,6 +2218,10 @@ int rau_noise_clip_adam(rau_ctx* ctx, int64_t step_t, float lr, float mult_lr, f
                         uint64_t noise_seed, float* out_norms) {
   NEED(ctx, "null ctx");
   NEED(step_t >= 0 && gamma > 0.f && eta >= 0.f && clip > 0.f, "bad update hyper-parameters");
+  for (int gi = 0; gi < 3; ++gi)   // the state belongs to the rule that last wrote it (rau_update)
+    if (ctx->grp[gi].adam_t > 0 && ctx->grp[gi].opt_rule != RAU_OPT_ADAM)
+      return fail(RAU_ERR_STATE, "rau_noise_clip_adam: group %d holds Adamax state (t = %lld); reset it with "
+                  "rau_set_opt_state first", gi, (long long)ctx->grp[gi].adam_t);
   hipStream_t st = ctx->st;
   // SS:598-599: var = eta / ((step_t+1) * gamma)
   const float nstd = eta > 0.f ? std::sqrt(eta / ((float)(step_t + 1) * gamma)) : 0.f;
@@ -2227,6 +2232,7 @@ int rau_noise_clip_adam(rau_ctx* ctx, int64_t step_t, float lr, float mult_lr, f
       if (int rc = dalloc(ctx, &g.v, g.n, false)) return rc;
     }
     g.adam_t += 1;
+    g.opt_rule = RAU_OPT_ADAM;
     const double bc1 = 1.0 - std::pow((double)beta1, (double)g.adam_t);
     const double bc2 = 1.0 - std::pow((double)beta2, (double)g.adam_t);
     const float group_lr = gi == RAU_GROUP_MULT ? mult_lr : lr;  // SS:770-772

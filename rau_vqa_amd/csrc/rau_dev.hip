@@ -199,6 +199,15 @@ int rau_dev_adam(rau_ctx* ctx, float* x, const float* dx, float* m, float* v, si
   HIPC(hipGetLastError());
   return RAU_OK;
 }
+int rau_dev_adamax(rau_ctx* ctx, float* x, const float* dx, float* m, float* u, size_t n, float lr,
+                   float beta1, float beta2, float eps, int32_t t) {
+  NEED(ctx && ((x && dx && m && u) || !n), "null argument");
+  NEED(t >= 1, "rau_dev_adamax: t = %d (the step counter AFTER its increment, >= 1)", t);
+  // the group path's step size (rau_update): on the host in double
+  const float step = (float)((double)lr / (1.0 - std::pow((double)beta1, (double)t)));
+  if (n) HIPC(rau::adamax_vec(ctx->st, n, x, dx, m, u, step, beta1, beta2, eps));
+  return RAU_OK;
+}
 int rau_dev_select_rows(rau_ctx* ctx, float* dst, const float* src, int32_t rows, int32_t cols,
                         const int32_t* key_dev, int32_t value) {
   NEED(ctx && dst && src && key_dev, "null argument");

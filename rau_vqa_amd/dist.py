@@ -118,6 +118,16 @@ class NativeGradAllReduce:
         self.rau.allreduce_grads()
 
 
+def reduced_update(rau, allreduce, step_t, **update_args):
+    """The data-parallel update: `allreduce()` (a GradAllReduce or NativeGradAllReduce of `rau`, or None on a
+    single rank) and then RAU.update with the SAME arguments on every rank -- rule, clip_scope and noise_seed
+    included, so every rank computes the identical norms (the global one too: it is taken over the reduced
+    gradients) and the identical step.  Returns RAU.update's norms."""
+    if allreduce is not None:
+        allreduce()
+    return rau.update(step_t, **update_args)
+
+
 def reduce_hop_stats(losses, argmax, labels, group=None):
     """Global per-hop loss and train accuracy from per-rank values (reference SS:491-492, 518:
     the per-hop correct counts and criterion outputs feval logs).  `losses` [H] are means over

@@ -188,20 +188,27 @@ class RAU:
             L.check(self._lib.rau_set_grads(self._h, L.GROUPS[g], a.ctypes.data, a.size))
 
     # ---- snapshots (torch.save / torch.load of SS:1188-1197, Eval.lua:113-114,344-347)
-    def save_snapshot(self, path, it, epoch, opt, cuda=True):
+    def save_snapshot(self, path, it, epoch, opt, cuda=True, optim=False):
+        """optim=True adds the optimizer state (opt_state) as one more field, so a run resumed from the file goes
+        on with its moments and step counts; a Torch7 reader of the reference ignores the field."""
         from . import t7
         self.sync()
-        t7.save_snapshot(path, self.get_params(), it, epoch, opt, cuda=cuda)
+        t7.save_snapshot(path, self.get_params(), it, epoch, opt, cuda=cuda,
+                         optim=self.opt_state() if optim else None)
 
     def load_snapshot(self, path):
-        """embed_param:copy(snap.params[1]) ...; returns (it, epoch, opt)."""
+        """embed_param:copy(snap.params[1]) ...; returns (it, epoch, opt).  A snapshot that carries the optimizer
+        state restores it as well; one without leaves the context's state as it is."""
         from . import t7
         it, epoch, opt, params = t7.load_snapshot(path)
         for g, a in params.items():
             if a.size != self.group_size(g):
                 raise ValueError(f"snapshot group {g} has {a.size} floats, model has "
                                  f"{self.group_size(g)}")
+        optim = t7.load_optim(path)
         self.set_params(params)
+        if optim is not None:
+            self.set_opt_state(*optim)
         return it, epoch, opt
 
     def init_uniform(self, seed=123, lo=-0.08, hi=0.08):
@@ -762,11 +769,62 @@ class RAU:
         L.check(self._lib.rau_sync(self._h))
 
     def update(self, step_t, lr=3e-3, mult_lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-8,
-               eta=0.01, gamma=0.55, clip=0.1, noise_seed=0):
-        norms = np.zeros(3, np.float32)
-        L.check(self._lib.rau_noise_clip_adam(self._h, step_t, lr, mult_lr, beta1, beta2, eps,
-                                              eta, gamma, clip, noise_seed, norms.ctypes.data))
+               eta=0.01, gamma=0.55, clip=0.1, noise_seed=0, rule="adam", clip_scope="group"):
+        """Noise, clip and the optimizer step.  With rule and clip_scope at their defaults this is the reference's
+        update (rau_noise_clip_adam) and returns the three groups' pre-clip norms.  rule="adamax" and / or
+        clip_scope="global" (neither is in the reference) go through rau_update and return four norms: the groups'
+        and the global one."""
+        if rule not in L.OPT_RULES:
+            raise ValueError(f"update: rule {rule!r} is not one of {sorted(L.OPT_RULES)}")
+        if clip_scope not in L.CLIP_SCOPES:
+            raise ValueError(f"update: clip_scope {clip_scope!r} is not one of {sorted(L.CLIP_SCOPES)}")
+        if rule == "adam" and clip_scope == "group":
+            norms = np.zeros(3, np.float32)
+            L.check(self._lib.rau_noise_clip_adam(self._h, step_t, lr, mult_lr, beta1, beta2, eps,
+                                                  eta, gamma, clip, noise_seed, norms.ctypes.data))
+            return norms
+        o = L.RauUpdateOpts(rule=L.OPT_RULES[rule], clip_scope=L.CLIP_SCOPES[clip_scope], lr=lr, mult_lr=mult_lr,
+                            beta1=beta1, beta2=beta2, eps=eps, eta=eta, gamma=gamma, clip=clip,
+                            noise_seed=noise_seed)
+        norms = np.zeros(4, np.float32)
+        L.check(self._lib.rau_update(self._h, step_t, C.byref(o), norms.ctypes.data))
         return norms
+
+    # ---- optimizer state (rau_get_opt_state / rau_set_opt_state): what a resumed run needs besides the parameters
+    def opt_state(self):
+        """-> ({group: (m, v, t)}, rule): the moments as float32 vectors (v holds Adamax's u), the update count
+        and the rule that owns the state ("adam" before the first update)."""
+        names = {v: k for k, v in L.OPT_RULES.items()}
+        out, rule = {}, None
+        for g in L.GROUPS:
+            n = self.group_size(g)
+            m, v = np.empty(n, np.float32), np.empty(n, np.float32)
+            t, r = C.c_int64(), C.c_int32()
+            L.check(self._lib.rau_get_opt_state(self._h, L.GROUPS[g], m.ctypes.data, v.ctypes.data,
+                                                C.byref(t), C.byref(r)))
+            out[g] = (m, v, int(t.value))
+            if rule is None:            # every update writes all three groups, so they agree
+                rule = r.value
+        return out, names[rule]
+
+    def set_opt_state(self, state, rule="adam"):
+        """state: {group: (m, v, t)} as opt_state returns it; groups not named keep theirs."""
+        if rule not in L.OPT_RULES:
+            raise ValueError(f"set_opt_state: rule {rule!r} is not one of {sorted(L.OPT_RULES)}")
+        for g, (m, v, t) in state.items():
+            m, v = np.ascontiguousarray(m, np.float32).ravel(), np.ascontiguousarray(v, np.float32).ravel()
+            n = self.group_size(g)
+            if m.size != n or v.size != n:
+                raise ValueError(f"set_opt_state: group {g} has {n} floats, got {m.size} and {v.size}")
+            L.check(self._lib.rau_set_opt_state(self._h, L.GROUPS[g], m.ctypes.data, v.ctypes.data, int(t),
+                                                L.OPT_RULES[rule]))
+
+    def reset_opt_state(self, rule="adam"):
+        """Zero moments and t = 0 in every group, owned by `rule` from now on: the way to change rule."""
+        if rule not in L.OPT_RULES:
+            raise ValueError(f"reset_opt_state: rule {rule!r} is not one of {sorted(L.OPT_RULES)}")
+        for g in L.GROUPS:
+            L.check(self._lib.rau_set_opt_state(self._h, L.GROUPS[g], None, None, 0, L.OPT_RULES[rule]))
 
     # ---- results
     def _out(self, fn, shape, dtype=np.float32):

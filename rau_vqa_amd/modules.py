@@ -463,6 +463,20 @@ def adam(x, dx, lr, beta1=0.9, beta2=0.999, epsilon=1e-8, state=None):
                                     float(lr), float(beta1), float(beta2), float(epsilon), state["t"]))
 
 
+def adamax(x, dx, lr, beta1=0.9, beta2=0.999, epsilon=1e-8, state=None):
+    """adam's twin for Adamax (not in the reference; RAU.update(rule="adamax")'s element arithmetic on one flat
+    device vector): state holds m, u (DevTensors, created on first use) and t, kept as adam keeps them."""
+    if state is None:
+        raise TypeError("adamax: pass a dict as `state` (it carries m, u and t between calls)")
+    if "m" not in state:
+        state["t"] = 0
+        state["m"] = DevTensor.zeros(x.rau, x.numel())
+        state["u"] = DevTensor.zeros(x.rau, x.numel())
+    state["t"] += 1
+    L.check(x.rau._lib.rau_dev_adamax(x.rau._h, x.ptr, dx.ptr, state["m"].ptr, state["u"].ptr, x.numel(),
+                                      float(lr), float(beta1), float(beta2), float(epsilon), state["t"]))
+
+
 def adam_statements(x, dx, lr, beta1=0.9, beta2=0.999, epsilon=1e-8, state=None):
     """The same update written as the reference's five tensor statements, one rau_dev_* call each
     (what RAU.Tensor's mul / add / addcmul / sqrt / addcdiv give a script that keeps its own adam)."""

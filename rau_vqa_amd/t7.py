@@ -261,18 +261,49 @@ def save(path, obj):
 GROUPS = ("embed", "rnn", "mult")     # checkpoint.params[1..3], SS:1196
 
 
-def save_snapshot(path, params, it, epoch, opt, cuda=True):
+def save_snapshot(path, params, it, epoch, opt, cuda=True, optim=None):
     """`torch.save(savefile, {it=, opt=, epoch=, params=})` of SS:1188-1197.
 
     params: {"embed","rnn","mult"} -> flat float32 vectors in THIS library's layout
     (rau_layout_entry).  The reference saves CudaTensors (its flat vectors live on the GPU);
     cuda=False writes FloatTensors, loadable by a Torch7 without cutorch.
+
+    optim: None (the reference's table, nothing added), or ({group: (m, v, t)}, rule) as RAU.opt_state
+    returns it: one more field beside `params`, `optim = {rule=, state={[1..3]={m=, v=, t=}}}`, which the
+    reference's readers never index (load_optim reads it back).
     """
     cls = "torch.CudaTensor" if cuda else "torch.FloatTensor"
     ckpt = {"it": it, "opt": dict(opt), "epoch": epoch,
             "params": {i + 1: Tensor(np.asarray(params[g], np.float32).ravel(), cls)
                        for i, g in enumerate(GROUPS)}}
+    if optim is not None:
+        state, rule = optim
+        ckpt["optim"] = {"rule": str(rule),
+                         "state": {i + 1: {"m": Tensor(np.asarray(state[g][0], np.float32).ravel(), cls),
+                                           "v": Tensor(np.asarray(state[g][1], np.float32).ravel(), cls),
+                                           "t": int(state[g][2])}
+                                   for i, g in enumerate(GROUPS)}}
     save(path, ckpt)
+
+
+def load_optim(path_or_snapshot):
+    """The optimizer field of a snapshot written with `optim`: ({group: (m, v, t)}, rule), or None when the
+    snapshot has none (every snapshot of the reference).  Takes a path or an already loaded snapshot table."""
+    snap = path_or_snapshot if isinstance(path_or_snapshot, dict) else load(path_or_snapshot)
+    if not isinstance(snap, dict) or "optim" not in snap:
+        return None
+    o = snap["optim"]
+    if not isinstance(o, dict) or not isinstance(o.get("state"), dict) or not isinstance(o.get("rule"), str):
+        raise T7Error("snapshot field `optim` is not {rule=, state=}")
+    out = {}
+    for i, g in enumerate(GROUPS):
+        e = o["state"].get(i + 1)
+        if not isinstance(e, dict) or not isinstance(e.get("m"), Tensor) or not isinstance(e.get("v"), Tensor) \
+                or not isinstance(e.get("t"), int) or e["t"] < 0:
+            raise T7Error(f"snapshot optim.state[{i + 1}] is not {{m=, v=, t=}}")
+        out[g] = (np.ascontiguousarray(e["m"].array, np.float32).ravel(),
+                  np.ascontiguousarray(e["v"].array, np.float32).ravel(), e["t"])
+    return out, o["rule"]
 
 
 def load_snapshot(path):
