@@ -105,6 +105,15 @@ int rau_graph_step_merged(rau_ctx* ctx, const float* hop_w, const float* select_
                           const float* merge_w, int zero_grads_first);
 int rau_merge_criterion_backward(rau_ctx* ctx, const float* logits_dev, const float* dopred_dev,
                                  const int32_t* labels_dev, const float* merge_w, float* d_logits_dev);
+typedef struct rau_out_grads {
+  const float* d_logits;
+  const float* d_dopred;
+  const float* d_attprob;
+} rau_out_grads;
+int rau_outputs_dev(rau_ctx* ctx, const float** logits, const float** dopred, const float** attprob,
+                    int32_t* att_pitch);
+int rau_backward_ext(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
+                     const float* merge_w, const rau_out_grads* g);
 int rau_embed_forward(rau_ctx* ctx, int t, const int32_t* tokens_dev, float** we);
 int rau_embed_backward(rau_ctx* ctx, int t, const int32_t* tokens_dev, const float* d_we);
 int rau_deeplstm_forward(rau_ctx* ctx, int t, const float* x, const float* state,
@@ -545,6 +554,32 @@ function RAU:backward(hop_w, select_w, att_w, merge_w)
   elseif aw then check(C.rau_backward_att(self.h, w, sw, aw))
   elseif sw then check(C.rau_backward_select(self.h, w, sw))
   else check(C.rau_backward(self.h, w)) end
+end
+
+-- the outputs of the last forward in device memory (rau_outputs_dev): logits [H,n,K], dopred [H,n] and attprob
+-- [H,n,pitch] as const float* cdata plus the pitch; valid until the next forward, ordered on the ctx's stream
+function RAU:outputsDev()
+  local lg, dp, at = ffi.new('const float*[1]'), ffi.new('const float*[1]'), ffi.new('const float*[1]')
+  local pitch = ffi.new('int32_t[1]')
+  check(C.rau_outputs_dev(self.h, lg, dp, at, pitch))
+  return lg[0], dp[0], at[0], pitch[0]
+end
+
+-- backward with the gradients of a term of the caller's own at those outputs (rau_backward_ext): grads = { logits =,
+-- dopred =, attprob = }, each a DEVICE float* (dense [H,n,K], [H,n], [H,n,S]) or nil; hop_w may be nil (zeros) then,
+-- and the batch needs labels only for a non-zero hop_w, select_w or merge_w
+function RAU:backwardExt(hop_w, select_w, att_w, merge_w, grads)
+  local H = self.cfg.H
+  local w = hop_w and hop_array(H, hop_w) or nil
+  local sw = select_w and hop_array(H, select_w) or nil
+  local aw = att_w and hop_array(H, att_w) or nil
+  local mw = merge_w and merge_array(merge_w) or nil
+  local g = nil
+  if grads then
+    g = ffi.new('rau_out_grads')
+    g.d_logits, g.d_dopred, g.d_attprob = grads.logits, grads.dopred, grads.attprob
+  end
+  check(C.rau_backward_ext(self.h, w, sw, aw, mw, g))
 end
 
 -- zeroGradParameters (unless zero_grads == false) + forward + backward as one captured graph launch

@@ -648,6 +648,61 @@ int rau_merge_criterion_backward(rau_ctx* ctx, const float* logits_dev /* [H,n,K
                                  const int32_t* labels_dev /* NULL: the resident batch's labels or answer set */,
                                  const float* merge_w /* [2] host */, float* d_logits_dev /* [H,n,K], added into */);
 
+/* ---- custom objectives: the step-level backward from caller-supplied gradients -----------------------
+ * For a term F(logits, do_pred, attprob) the library does not implement (distillation, de-biasing, focal or ranking
+ * losses, an attention penalty, a rule of one's own for do_pred) the caller reads the three outputs of the last
+ * step-level forward on the device, computes dF/d(output) there, and hands the gradients to the backward.  The
+ * step's objective becomes
+ *   sum_h ( hop_w[h]*CE_h + select_w[h]*BCE_h + att_w[h]*ATT_h ) + w_uni*CE(uni) + w_sel*CE(select) + F
+ * rau_outputs_dev: ctx-owned DEVICE pointers to the outputs of the last step-level forward (rau_forward or a
+ * rau_graph_step*); any out argument may be NULL.  n is the CURRENT batch size (rau_set_batch_size), not the
+ * capacity, and every tensor is dense in it: logits [H,n,K] with strides (n*K, K, 1), dopred [H,n] with strides
+ * (n, 1), attprob [H,n,pitch] with strides (n*pitch, pitch, 1), *att_pitch = pitch = S rounded up to a multiple of
+ * 4 (columns S..pitch-1 hold zeros; behind a sample's region count the probabilities are zeros).  The pointers stay
+ * valid until the next forward or rau_set_batch_size; their contents are ordered on the ctx's stream (rau_stream),
+ * and the call synchronises nothing: a caller on another stream orders itself behind an event of that stream.
+ * Read-only for the caller.  RAU_ERR_STATE when there has been no step-level forward (or a module-level call has
+ * overwritten its slots).
+ * rau_backward_ext: rau_backward_merged with g = {dF/dlogits, dF/ddo_pred, dF/dattprob}, all float32 in DEVICE
+ * memory, dense in the current batch size (d_attprob at pitch S, NOT the attention's pitch), each NULL = no such
+ * term; every operation below is float32, rounded once:
+ *   logits   behind the scaling by hop_w[h] (the product of rau_backward, the same bits) x = x + d_logits[h,b,k], in
+ *            front of the merged rows' terms and of every consumer (the classifier's input, weight and bias
+ *            gradients; the head's addend).  The forward of a batch without labels or answer set forms no criterion
+ *            gradient: then x = d_logits[h,b,k] exactly, or +0 without a d_logits.  One pass over [H,n,K].
+ *   do_pred  s_ext = (d_dopred[h,b] * x) * (1 - x) with x = do_pred[h,b] (through the sigmoid: the last line of the
+ *            rule at rau_backward_select); s = s_sel + s_ext with a select_w term, else s = s_ext; s * wd[m] enters
+ *            the gradient at merge_feat in front of its dropout mask, and s the head's weight and bias gradient,
+ *            exactly as rau_backward_select's s does.
+ *   attprob  da[h,b,s] = (att_w's value at rau_backward_att) + d_attprob[h,b,s] with an att_w term, else
+ *            d_attprob[h,b,s] exactly; positions behind a sample's region count receive exactly +0 whatever
+ *            d_attprob holds there.
+ * With any pointer non-NULL every hop is active (the host cannot see which rows are zero without a synchronisation),
+ * and the backward forms the head's two input-gradient products itself, as a step with a select_w does.  g == NULL
+ * or three NULL pointers, with a non-NULL hop_w, IS rau_backward_merged with the other four arguments: the same
+ * launches, the same bits.  hop_w may be NULL (zeros) only with a gradient in g.
+ * Labels: a batch with labels or an answer set is required exactly when a built-in term reads one -- a non-zero
+ * entry in hop_w, select_w or merge_w; then every state rule of rau_backward_merged applies.  An external-only
+ * backward (hop_w NULL or zeros, no select_w, no merge_w) runs on a batch uploaded without labels.  A non-zero att_w
+ * needs the batch's targets, as in rau_backward_att.  Evaluate mode, image-table and bank batches, region counts, the
+ * tied feature-map dropout, RAU_BF16 / RAU_F32S and both answer criteria work as in rau_backward; under RAU_LOSS_BCE
+ * a non-zero merge_w stays RAU_ERR_INVALID.  One backward per forward, as everywhere.  A d_logits that is not
+ * 16-byte aligned: RAU_ERR_INVALID, nothing launched.  The library cannot check DEVICE values: a non-finite entry in
+ * g gives non-finite gradients, not an error; the three arrays must stay unchanged until the backward's launches
+ * that read them are done (they are read on the ctx's stream, before rau_backward_ext's first GEMM).
+ * No atomics: repeated calls give the same bits.  There is no captured variant: the gradients are computed between
+ * the forward and the backward.  No gradient enters at the last hop's c' / h' (the reference's zeros, SS:561-562) or
+ * at the question state. */
+typedef struct rau_out_grads {
+  const float* d_logits;   /* [H,n,K] DEVICE, dense, 16-byte aligned; NULL = no such term */
+  const float* d_dopred;   /* [H,n]   DEVICE, dense;                  NULL = no such term */
+  const float* d_attprob;  /* [H,n,S] DEVICE, dense (NOT pitched);    NULL = no such term */
+} rau_out_grads;
+int rau_outputs_dev(rau_ctx* ctx, const float** logits /* [H,n,K] */, const float** dopred /* [H,n] */,
+                    const float** attprob /* [H,n,pitch] */, int32_t* att_pitch);
+int rau_backward_ext(rau_ctx* ctx, const float* hop_w /* [H] host, NULL = zeros */, const float* select_w,
+                     const float* att_w, const float* merge_w, const rau_out_grads* g /* NULL = none */);
+
 /* ---- module-level entry points: one call per nn.Module :forward / :backward -----
  * For hosts that keep feval's own loops (SS:443-596) and call the clones one by one.
  * t in [0,T) / h in [0,H) select the clone (the reference's embed_clones[t+1],

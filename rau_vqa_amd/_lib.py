@@ -47,6 +47,11 @@ class RauUpdateOpts(C.Structure):
                [("noise_seed", C.c_uint64)]
 
 
+class RauOutGrads(C.Structure):
+    """Mirror of ``rau_out_grads`` (include/rau.h): device pointers, None = no such term."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_logits", "d_dopred", "d_attprob")]
+
+
 class RauError(RuntimeError):
     pass
 
@@ -152,6 +157,11 @@ _SIGS = {
     "rau_graph_step_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "rau_merge_criterion_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p]),
+    # custom objectives: the outputs on the device, caller-supplied gradients into the step-level backward
+    "rau_outputs_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_int32)]),
+    "rau_backward_ext": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(RauOutGrads)]),
     # module-level entry points: device pointers in, pointers to ctx-owned slots out
     "rau_embed_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_embed_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -1,0 +1,55 @@
+"""The step-level path as a torch.autograd.Function: a loss written in torch on the step's outputs.
+
+``step(rau)`` runs ``rau.forward()`` and returns (logits [H,n,K], dopred [H,n], attprob [H,n,S]) as torch tensors
+that carry a gradient function.  ``loss.backward()`` on anything computed from them hands d loss / d output to the
+step-level backward (``RAU.backward(..., out_grads=...)``, rau_backward_ext), which accumulates the PARAMETER
+gradients in the ctx's flat buffers -- ``rau.zero_grads()`` before, ``rau.update()`` after, as on every other path.
+The built-in terms (hop_w, select_w, att_w, merge_w) are given to ``step`` and join the same backward.
+
+torch is plumbing here: the forward, the backward and the update are librau's kernels; torch evaluates the
+caller's loss and its gradient at the three outputs, on its own current stream.  The two streams are joined with
+events only (ExternalStream + wait_stream), never with a host synchronisation.
+"""
+from __future__ import annotations
+
+import torch
+
+
+class _Step(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, anchor, rau, hop_w, select_w, att_w, merge_w):
+        dev = torch.device("cuda", rau.cfg.device_id)
+        rau.forward()
+        own = torch.cuda.ExternalStream(rau.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        cur.wait_stream(own)                    # the outputs are ordered on the ctx's stream
+        # clones: autograd owns what it hands out, the views die with the next forward
+        outs = tuple(t.clone() for t in rau.output_tensors())
+        ctx.rau, ctx.weights, ctx.dev = rau, (hop_w, select_w, att_w, merge_w), dev
+        ctx.set_materialize_grads(False)        # an unused output's gradient stays None instead of a zero tensor
+        return outs
+
+    @staticmethod
+    def backward(ctx, d_logits, d_dopred, d_attprob):
+        rau = ctx.rau
+        # an output the loss did not use arrives as None and goes to the library as NULL
+        grads = {k: g.contiguous().float() for k, g in
+                 (("logits", d_logits), ("dopred", d_dopred), ("attprob", d_attprob)) if g is not None}
+        own = torch.cuda.ExternalStream(rau.stream(), device=ctx.dev)
+        own.wait_stream(torch.cuda.current_stream(ctx.dev))   # the gradients were written on torch's stream
+        for g in grads.values():
+            g.record_stream(own)               # the caching allocator must not hand them out before the ctx has read them
+        hop_w, select_w, att_w, merge_w = ctx.weights
+        rau.backward(hop_w, select_w, att_w, merge_w, out_grads=grads)
+        return (None,) * 6                      # parameter gradients live in the ctx's flat buffers
+
+
+def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None):
+    """forward of the resident batch -> (logits, dopred, attprob), differentiable at those three outputs.
+
+    hop_w, select_w, att_w, merge_w: the built-in terms of RAU.backward, added to whatever loss the caller builds
+    (hop_w None = zeros: an external-only objective, which needs no labels on the batch).  One ``backward()`` per
+    ``step``; an output that does not enter the loss costs nothing."""
+    # a leaf that requires grad makes autograd record the node: the real leaves are the ctx's parameters
+    anchor = torch.zeros((), device=torch.device("cuda", rau.cfg.device_id), requires_grad=True)
+    return _Step.apply(anchor, rau, hop_w, select_w, att_w, merge_w)

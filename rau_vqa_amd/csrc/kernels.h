@@ -463,6 +463,17 @@ hipError_t att_sup_stats(hipStream_t st, int hops, int Bper, int S, const float*
 // w_uni / w_sel; a zero weight's term is skipped.  One launch, one workgroup per sample; K % 4 == 0, dl 16-byte aligned.
 hipError_t merge_grad(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred, const Truth& t,
                       const float* mw_dev, float w_uni, float w_sel, float* dl);
+// Caller-supplied gradients at the step's outputs (ext_grad.hip, rau_backward_ext).  Each one launch, no atomics.
+// ext_dl: dl[h][i] = dl[h][i] * w_dev[h] + d[h][i] over H hops of per_hop floats (per_hop % 4 == 0, 16-byte aligned
+// bases); d null: the product alone; w_dev null (the forward wrote no dl): dl = d exactly, or +0 with d null too.
+// ext_signal: s[r] = (acc ? s[r] : nothing) + (ddp[r] * x) * (1 - x), x = dopred[r]; add[r][m] = s[r] wd[m].
+// ext_da: da[h,b,s] = (acc ? da[h,b,s] : nothing) + d[h,b,s] below the count, +0 elsewhere, over the whole of d_rs;
+// d dense [hops][Bper][S], da rows at pitch d_rs, nreg [Bper] region counts or null.
+hipError_t ext_dl(hipStream_t st, int H, size_t per_hop, const float* w_dev, const float* d, float* dl);
+hipError_t ext_signal(hipStream_t st, int rows, int M, const float* dopred, const float* ddp, const float* wd,
+                      bool acc, float* s, float* add);
+hipError_t ext_da(hipStream_t st, int hops, int Bper, int S, const float* d, const int32_t* nreg, bool acc,
+                  float* da, int d_rs);
 hipError_t scale_hops(hipStream_t st, int H, size_t per_hop, const float* w_dev, float* x);
 // x_i[h][0 .. p_i) *= w[h] for three hop-major tensors in one launch
 hipError_t scale_hops3(hipStream_t st, int H, const float* w_dev, size_t p0, float* x0, size_t p1, float* x1,

@@ -202,9 +202,14 @@ struct StepLoss {
   // zero recurrent gradient: Full/ResNet late-epoch gating, Full:587-589): their backward is identically zero
   // and is skipped -- `active` hops are "active".  H with a merge_w: the uni row reads every hop.
   int active = 0;
-  // select_w and merge_w are per-row terms, which cannot be folded into what the forward formed (one scale per
-  // hop): such a backward forms dpre / dhn itself from the scaled dl
-  bool forms_dpre() const { return select_w || merge_w; }
+  // caller-supplied gradients at the outputs (rau_backward_ext, ext_grad.hip): DEVICE pointers, null = no such
+  // term; step_loss() leaves the record empty when all three are null.  With any of them every hop is active.
+  rau_out_grads ext{nullptr, nullptr, nullptr};
+  bool has_ext() const { return ext.d_logits || ext.d_dopred || ext.d_attprob; }
+  bool hop_any = false;              // hop_w has a non-zero entry (an ext backward without one needs no labels)
+  // select_w, merge_w and the external gradients are per-row terms, which cannot be folded into what the forward
+  // formed (one scale per hop): such a backward forms dpre / dhn itself from the final dl
+  bool forms_dpre() const { return select_w || merge_w || has_ext(); }
 };
 // What shapes a captured step (rau_graph_step): one executable graph per distinct value.
 struct StepKey {
@@ -322,6 +327,7 @@ struct rau_ctx {
   void* WpT16 = nullptr;
   void* dS16 = nullptr;  // with xd16: the attention backward's dS as bf16 [H][B][A][S] (both consumers round it anyway)
   bool dpre_fwd = false;    // the last forward already formed dpre / dhn of every hop (unscaled by the hop weights)
+  bool fwd_dl = false;      // the last forward wrote dl: its batch had labels or an answer set (rau_backward_ext)
   bool ds16_step = false;   // set by rau_backward while its hop loop runs: hop_backward writes dS16, not T
   void* xd16 = nullptr;  // RAU_BF16 step path, S % 4 == 0: the same maps stored as bf16 (xd stays unwritten)
   bool I_shared = false;  // evaluate mode, p_x = 0 or a tied mask: i_embed output is hop-invariant, computed once

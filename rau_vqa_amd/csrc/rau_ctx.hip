@@ -1558,6 +1558,7 @@ int rau_forward(rau_ctx* ctx) {
     RUN("loss_reduce", 0, 0, loss_reduce(st, H, B, ctx->lossrow, ctx->losses_d));
   if (!ctx->capturing) merge_record(ctx);   // (rau_graph_step records behind its launch)
   ctx->fwd_done = true;
+  ctx->fwd_dl = bs.held.have_labels;
   ctx->dpre_fwd = head_dgrad_fwd(ctx);
   return RAU_OK;
 }
@@ -1591,8 +1592,14 @@ static int upload_hop_weights(rau_ctx* ctx, const StepLoss& l) {
 // The one place a backward with a select_w differs is marked `sel` below.  `att`: one launch, and HopGrad::da_out
 // of every active hop.  `mrg`: one launch behind the hop scaling; like `sel` it is a per-row term, so dpre / dhn
 // are formed here, and every hop is active (the uni row reads them all).
+// `ext` (rau_backward_ext): caller-supplied gradients join dl behind its scaling (ext_dl, in scale_hops' place), s
+// behind select_signal (ext_signal) and the attention addend behind att_sup_grad (ext_da); each of the three sites
+// then runs with or without its built-in term.  Per-row terms again: dpre / dhn are formed here, every hop is active.
 static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   const bool sel = loss.select_w != nullptr, att = loss.att_w != nullptr, mrg = loss.merge_w != nullptr;
+  const rau_out_grads& ext = loss.ext;
+  const bool sig = sel || ext.d_dopred;   // the head_dgrad addend and the selection head's weight gradient exist
+  const bool has_da = att || ext.d_attprob;   // every hop's attention backward is handed its da_out
   const int HA = loss.active;
   const HopwLayout at(ctx->cfg.H);
   if (!ctx->fwd_done) return fail(RAU_ERR_STATE, "rau_backward: call rau_forward first");
@@ -1601,7 +1608,12 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
                 "i_embed once per image, so there is no per-sample I to differentiate; take evaluate-mode "
                 "gradients on a plain batch (rau_set_batch)");
   const BatchSlot& bs = cur_batch(ctx);
-  if (!bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_backward: batch has no labels");
+  // an external-only backward reads no label: hop_w zeros, no select_w, no merge_w (att_w reads the targets alone)
+  const bool builtin = !loss.has_ext() || loss.hop_any || sel || mrg;
+  if (builtin && !bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_backward: batch has no labels");
+  if (builtin && loss.has_ext() && !ctx->fwd_dl)
+    return fail(RAU_ERR_STATE, "rau_backward_ext: the forward ran on a batch without labels, so there is no "
+                "criterion gradient for a non-zero hop_w, select_w or merge_w");
   // the head's target is read from that forward's labels or answer set: they must still be there (a captured
   // step reads the resident batch, which rau_graph_step_select has checked)
   if ((sel || mrg) && !ctx->capturing)
@@ -1636,7 +1648,11 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   if (!ctx->capturing) {  // (rau_graph_step uploads the weights before it launches the graph)
     if (int rc = upload_hop_weights(ctx, loss)) return rc;
   }
-  if (ctx->dpre_fwd && !loss.forms_dpre())   // the forward formed dpre / dhn from the unscaled dl: scale all three
+  if (ext.d_logits || (loss.has_ext() && !ctx->fwd_dl))
+    // one pass in scale_hops' place: dl * hop_w + d_logits; without a criterion gradient dl = d_logits (or +0)
+    RUN("ext_dl", (double)H * B * K * (ctx->fwd_dl ? 2 : 0), (double)H * B * K * (ctx->fwd_dl ? 12 : 8),
+        ext_dl(st, H, (size_t)B * K, ctx->fwd_dl ? ctx->hopw_d : nullptr, ext.d_logits, ctx->dl));
+  else if (ctx->dpre_fwd && !loss.forms_dpre())   // the forward formed dpre / dhn from the unscaled dl: scale all three
     RUN("scale_hops", 0, (double)H * B * (K + M + R) * 8,
         scale_hops3(st, H, ctx->hopw_d, (size_t)B * K, ctx->dl, (size_t)B * M, ctx->dpre, (size_t)B * R, ctx->dhn));
   else
@@ -1657,15 +1673,21 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
     RUN("select_signal", 0, (double)HA * B * M * 4,
         select_signal(st, HA * B, B, K, M, ctx->dopred, ctx->argmax_d, t, ctx->hopw_d + at.select_w, ctx->do_pred.W,
                       ctx->sel_s, ctx->sel_add));
+  if (ext.d_dopred)   // s (+)= (d_dopred x)(1 - x) through the sigmoid, and the addend formed from the final s
+    RUN("ext_signal", 0, (double)HA * B * M * 4,
+        ext_signal(st, HA * B, M, ctx->dopred, ext.d_dopred, ctx->do_pred.W, sel, ctx->sel_s, ctx->sel_add));
   // att: the gradient at the attprob output of all active hops, -(att_w[h] t / (a + eps)) / B, read by the attention
   // backward of each hop (HopGrad::da_out).  The targets may have come after the forward: it does not read them.
   if (att)
     RUN("att_sup_grad", 0, (double)HA * B * S * 12,
         att_sup_grad(st, HA, B, SL, ctx->a, S, bs.att_t_d, S, bs.held.regions ? bs.nreg_d : nullptr,
                      ctx->hopw_d + at.att_w, 0.f, ctx->att_da, S));
+  if (ext.d_attprob)   // the dense [H,n,S] gradient (added) into the pitched addend, zeros behind the counts
+    RUN("ext_da", 0, (double)HA * B * S * (att ? 12 : 8),
+        ext_da(st, HA, B, SL, ext.d_attprob, bs.held.regions ? bs.nreg_d : nullptr, att, ctx->att_da, S));
   if (HA > 0 && (!ctx->dpre_fwd || loss.forms_dpre())) {
     LinOpts o = lin_opts(ctx, ctx->ws_chain);
-    if (sel) { o.addend = ctx->sel_add; o.add_rs = M; }
+    if (sig) { o.addend = ctx->sel_add; o.add_rs = M; }
     o.emask = m_mf;
     o.emask_e0 = 0;
     o.emscale = sc(RAU_MASK_MF);
@@ -1702,7 +1724,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
       // before the hop's backward is over (it matters for the first group: the forward / backward seam)
       g.ev_conv_ready = (gsz[h] && (seam_mask() & 2)) ? ctx->evK[h] : nullptr;
       g.dh_prev_dead = h == 0;   // hop 0's prev_h is the constant initial state: nothing reads its gradient
-      g.da_out = att ? ctx->att_da + (size_t)h * BS_ : nullptr;
+      g.da_out = has_da ? ctx->att_da + (size_t)h * BS_ : nullptr;
       if (int rc = hop_backward(ctx, h, ctx->cc + (size_t)h * BR_,
                                 ctx->I + (ctx->I_shared ? 0 : (size_t)h * BM_ * S), g))
         return rc;
@@ -1861,7 +1883,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
       for (int i = 0; i < np; ++i) fl += gflop(pr[i].M, pr[i].N, rows);
       RUNS(sw, "wgrad_gemm", fl, 0, gemm_tn_group_acc(sw, pr, np, rows, ws.slab, ws.floats, lin_mode(ctx).bf16));
     }
-    if (sel)   // the head's own weights: dwd += sum s mf, dbd += sum s (f32 dot products in every dtype)
+    if (sig)   // the head's own weights: dwd += sum s mf, dbd += sum s (f32 dot products in every dtype)
       RUNS(sw, "select_wgrad", 2.0 * rows * (M + 1), (double)rows * M * 4,
            select_wgrad(sw, rows, M, ctx->sel_s, ctx->mf, ctx->do_pred.dW, ctx->do_pred.db));
     // att_score: dws = sum dz T ; dbs = sum dz.  att_i bias: sum dS.  i_embed bias: sum dZ.
@@ -1972,8 +1994,13 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
 // for rau_backward and rau_graph_step, which take it as it is: check_hop_w); a term without a non-zero entry
 // becomes null; a non-zero att_w needs the batch's targets; the scratch of every term left exists on return.
 static int step_loss(rau_ctx* ctx, const char* fn, bool check_hop_w, const float* hop_w, const float* select_w,
-                     const float* att_w, const float* merge_w, StepLoss* loss) {
+                     const float* att_w, const float* merge_w, StepLoss* loss, const rau_out_grads* g = nullptr) {
   NEED(ctx && hop_w, "null argument");
+  // the external record: all-null is absent (the caller's call then IS the one without it)
+  rau_out_grads ext{nullptr, nullptr, nullptr};
+  if (g) ext = *g;
+  const bool has_ext = ext.d_logits || ext.d_dopred || ext.d_attprob;
+  NEED((reinterpret_cast<uintptr_t>(ext.d_logits) & 15u) == 0, "%s: d_logits must be 16-byte aligned", fn);
   if (merge_w) {
     NEED(std::isfinite(merge_w[0]) && std::isfinite(merge_w[1]), "%s: merge_w is not finite", fn);
     if (merge_w[0] == 0.f && merge_w[1] == 0.f) merge_w = nullptr;
@@ -1983,9 +2010,10 @@ static int step_loss(rau_ctx* ctx, const char* fn, bool check_hop_w, const float
          "softmax cross-entropy only", fn);
   }
   const int H = ctx->cfg.H;
-  bool any = false, any_att = false;
+  bool any = false, any_att = false, hop_any = false;
   int active = 0;
   for (int h = 0; h < H; ++h) {
+    hop_any = hop_any || hop_w[h] != 0.f;
     NEED(!check_hop_w || std::isfinite(hop_w[h]), "%s: hop_w[%d] is not finite", fn, h);
     NEED(!select_w || std::isfinite(select_w[h]), "%s: select_w[%d] is not finite", fn, h);
     NEED(!att_w || std::isfinite(att_w[h]), "%s: att_w[%d] is not finite", fn, h);
@@ -1993,18 +2021,19 @@ static int step_loss(rau_ctx* ctx, const char* fn, bool check_hop_w, const float
     any_att = any_att || (att_w && att_w[h] != 0.f);
     if (hop_w[h] != 0.f || (select_w && select_w[h] != 0.f) || (att_w && att_w[h] != 0.f)) active = h + 1;
   }
-  if (any_att) {
-    if (!cur_batch(ctx).held.att_targets)
-      return fail(RAU_ERR_STATE, "%s: a non-zero att_w needs a batch with attention targets (rau_set_att_targets)", fn);
+  if (any_att && !cur_batch(ctx).held.att_targets)
+    return fail(RAU_ERR_STATE, "%s: a non-zero att_w needs a batch with attention targets (rau_set_att_targets)", fn);
+  if (any_att || ext.d_attprob) {
     if (!ctx->att_da)   // sized for the capacity, cleared by rau_set_batch_size like every activation
       if (int rc = dalloc(ctx, &ctx->att_da, (size_t)H * ctx->cap * ctx->Sp)) return rc;
   }
-  if (any && !ctx->sel_add) {   // sized for the capacity, cleared by rau_set_batch_size like every activation
+  if ((any || ext.d_dopred) && !ctx->sel_add) {   // sized for the capacity, cleared by rau_set_batch_size like every activation
     if (!ctx->sel_s)
       if (int rc = dalloc(ctx, &ctx->sel_s, (size_t)H * ctx->cap)) return rc;
     if (int rc = dalloc(ctx, &ctx->sel_add, (size_t)H * ctx->cap * ctx->cfg.M)) return rc;
   }
-  *loss = StepLoss{hop_w, any ? select_w : nullptr, any_att ? att_w : nullptr, merge_w, merge_w ? H : active};
+  *loss = StepLoss{hop_w, any ? select_w : nullptr, any_att ? att_w : nullptr, merge_w,
+                   (merge_w || has_ext) ? H : active, ext, hop_any};
   return RAU_OK;
 }
 
@@ -2028,6 +2057,33 @@ int rau_backward_merged(rau_ctx* ctx, const float* hop_w, const float* select_w,
   StepLoss loss;
   if (int rc = step_loss(ctx, "rau_backward_merged", true, hop_w, select_w, att_w, merge_w, &loss)) return rc;
   return backward_impl(ctx, loss);
+}
+// The same with caller-supplied gradients at the three outputs (StepLoss::ext).  hop_w may be null (zeros) here: an
+// external-only backward needs no label.  g null or all-null: rau_backward_merged, launch for launch.
+int rau_backward_ext(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
+                     const float* merge_w, const rau_out_grads* g) {
+  NEED(ctx, "null ctx");
+  const bool has_ext = g && (g->d_logits || g->d_dopred || g->d_attprob);
+  NEED(hop_w || has_ext, "rau_backward_ext: hop_w may be NULL only with a gradient in g");
+  const std::vector<float> zeros((size_t)ctx->cfg.H, 0.f);
+  StepLoss loss;
+  if (int rc = step_loss(ctx, has_ext ? "rau_backward_ext" : "rau_backward_merged", true,
+                         hop_w ? hop_w : zeros.data(), select_w, att_w, merge_w, &loss, g))
+    return rc;
+  return backward_impl(ctx, loss);   // (the staging copy of hop_w is taken before it returns)
+}
+// Device pointers to the outputs of the last step-level forward, for a caller that computes its own gradients on
+// the device.  Nothing is synchronised: the values are ordered on the ctx's stream.
+int rau_outputs_dev(rau_ctx* ctx, const float** logits, const float** dopred, const float** attprob,
+                    int32_t* att_pitch) {
+  NEED(ctx, "null ctx");
+  if (!ctx->mg.valid)
+    return fail(RAU_ERR_STATE, "rau_outputs_dev: no step-level forward to read (call rau_forward first)");
+  if (logits) *logits = ctx->logits;
+  if (dopred) *dopred = ctx->dopred;
+  if (attprob) *attprob = ctx->a;
+  if (att_pitch) *att_pitch = ctx->Sp;
+  return RAU_OK;
 }
 
 // One training step's forward + backward (optionally with the gradient zeroing in front) as ONE

@@ -60,6 +60,17 @@ def select_signal(x, t, w):
     return bce_grad(x, t, w) * x * (1 - x)
 
 
+def ext_signal(ddp, x):
+    """A gradient ddp at the do_pred output through the head's sigmoid: s_ext = (ddp * x) * (1 - x), in this order --
+    the contract of rau_backward_ext's d_dopred, and select_signal's own last step (select_signal(x, t, w) is
+    ext_signal(bce_grad(x, t, w), x) bit for bit).  Float32 arithmetic (the device's), unless x is given as
+    float64 (for references)."""
+    if not hasattr(x, "is_cuda"):
+        x = _f32_unless_f64(x)
+        ddp = np.asarray(ddp, x.dtype)
+    return (ddp * x) * (1 - x)
+
+
 def _att_valid(shape, nreg):
     """[..., n, S] bool: position s of sample b lies below its region count (None: every position)."""
     S = shape[-1]

@@ -749,15 +749,63 @@ class RAU:
         return (("", "_select", "_att", "_merged")[n],
                 [None if a is None else a.ctypes.data_as(C.c_void_p) for a in arrs[:n + 1]])
 
-    def backward(self, hop_w, select_w=None, att_w=None, merge_w=None):
+    def _out_grad(self, out_grads, key, shape):
+        """Device address of out_grads[key] (a contiguous float32 CUDA torch tensor of `shape`), None when absent."""
+        t = out_grads.get(key)
+        if t is None:
+            return None
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError(f"out_grads[{key!r}] must be a contiguous float32 CUDA torch tensor")
+        if t.device.index != self.cfg.device_id:
+            raise ValueError(f"out_grads[{key!r}] is on {t.device}, the context on cuda:{self.cfg.device_id}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"out_grads[{key!r}] has shape {tuple(t.shape)}, expected {shape}")
+        return t.data_ptr()
+
+    def backward(self, hop_w=None, select_w=None, att_w=None, merge_w=None, out_grads=None):
         """select_w [H]: per-hop weight of the step-selection head's BCE gradient, the multiplier the
         reference fixes at 0 (SS:566); None is that zero (rau_backward).
         att_w [H]: per-hop weight of the attention supervision against the batch's targets (set_att_targets), where
         the reference passes gradattprob = zeros (SS:361, 573); None is those zeros.
         merge_w [2]: weights of the cross-entropies of the merged "uni" and "select" rows (step_stats' loss[H] and
-        loss[H+1], which the reference only logs); None is no such term."""
-        family, ws = self._loss_args(hop_w, select_w, att_w, merge_w)
-        L.check(getattr(self._lib, "rau_backward" + family)(self._h, *ws))
+        loss[H+1], which the reference only logs); None is no such term.
+        out_grads: a dict with any of "logits" [H,n,K], "dopred" [H,n], "attprob" [H,n,S] -- the gradients of a
+        term of the caller's own at those outputs (output_tensors), contiguous float32 CUDA torch tensors that the
+        ctx's stream may read (order it behind the stream that wrote them).  The call then goes through
+        rau_backward_ext, where hop_w may be None (zeros); without out_grads it is exactly what it was."""
+        if out_grads is None:
+            if hop_w is None:
+                raise ValueError("hop_w is required without out_grads")
+            family, ws = self._loss_args(hop_w, select_w, att_w, merge_w)
+            L.check(getattr(self._lib, "rau_backward" + family)(self._h, *ws))
+            return
+        unknown = set(out_grads) - {"logits", "dopred", "attprob"}
+        if unknown:
+            raise ValueError(f"out_grads has unknown keys {sorted(unknown)}")
+        H, n = self.cfg.H, self._n
+        g = L.RauOutGrads(self._out_grad(out_grads, "logits", (H, n, self.cfg.K)),
+                          self._out_grad(out_grads, "dopred", (H, n)),
+                          self._out_grad(out_grads, "attprob", (H, n, self.cfg.S)))
+        arrs = [None if hop_w is None else self._hop_array(hop_w, "hop_w"),
+                None if select_w is None else self._hop_array(select_w, "select_w"),
+                None if att_w is None else self._hop_array(att_w, "att_w"),
+                None if merge_w is None else self._merge_array(merge_w)]
+        ws = [None if a is None else a.ctypes.data_as(C.c_void_p) for a in arrs]
+        L.check(self._lib.rau_backward_ext(self._h, *ws, C.byref(g)))
+
+    def output_tensors(self):
+        """Zero-copy torch views of the last step-level forward's outputs in device memory (rau_outputs_dev):
+        logits [H,n,K], dopred [H,n], attprob [H,n,S] -- the last a strided view of the pitched buffer.  Valid until
+        the next forward or set_batch_size, ordered on the ctx's stream (stream()), read-only."""
+        from .dist import device_view
+        lg, dp, at = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        pitch = C.c_int32()
+        L.check(self._lib.rau_outputs_dev(self._h, C.byref(lg), C.byref(dp), C.byref(at), C.byref(pitch)))
+        H, n, K, S, dev = self.cfg.H, self._n, self.cfg.K, self.cfg.S, self.cfg.device_id
+        return (device_view(lg.value, H * n * K, dev).view(H, n, K),
+                device_view(dp.value, H * n, dev).view(H, n),
+                device_view(at.value, H * n * pitch.value, dev).view(H, n, pitch.value)[:, :, :S])
 
     def graph_step(self, hop_w, zero_grads=True, select_w=None, att_w=None, merge_w=None):
         """zero_grads + forward + backward as one hipGraph launch (captured on first use); select_w, att_w and
