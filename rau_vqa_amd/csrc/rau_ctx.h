@@ -472,6 +472,20 @@ inline void merge_record(rau_ctx* ctx) {
 inline float mask_p(const rau_ctx* ctx, int site) {
   return ctx->mexplicit[site] ? ctx->mp_exact[site] : ctx->mp[site];
 }
+// The keep bits of every mask site -- null outside train mode and where nothing is dropped -- and its scale 1/(1-p)
+struct Masks {
+  const uint32_t *we, *rnn, *q, *x, *mf;
+  float s_we, s_rnn, s_q, s_x, s_mf;
+};
+__attribute__((visibility("hidden"))) inline Masks masks_of(const rau_ctx* ctx) {
+  const bool tr = ctx->mode == RAU_MODE_TRAIN;
+  auto mk = [&](int site) { return (tr && mask_p(ctx, site) > 0.f) ? (const uint32_t*)ctx->mbits[site] : nullptr; };
+  auto sc = [&](int site) { return 1.f / (1.f - mask_p(ctx, site)); };
+  return Masks{mk(RAU_MASK_WE), mk(RAU_MASK_RNN), mk(RAU_MASK_Q), mk(RAU_MASK_X), mk(RAU_MASK_MF),
+               sc(RAU_MASK_WE), sc(RAU_MASK_RNN), sc(RAU_MASK_Q), sc(RAU_MASK_X), sc(RAU_MASK_MF)};
+}
+// FLOPs of an [m, k] x [k, n] product, as the profile counts them
+inline double gflop(double m, double n, double k) { return 2.0 * m * n * k; }
 
 // scratch = false: the region outlives rau_set_batch_size untouched (see rau_ctx::scratch)
 template <typename Tp>
@@ -638,6 +652,25 @@ __attribute__((visibility("hidden"))) int hop_forward_head(rau_ctx* ctx, const S
     const Truth& truth);
 __attribute__((visibility("hidden"))) int hop_backward(rau_ctx* ctx, int h, const float* cp,
     const float* Ih, const HopGrad& g);
+// The image side of n maps on `s`: I = tanh(Wi x + bi) and P = Wp I + bp (x_is_b16: bf16 maps and weight copies)
+__attribute__((visibility("hidden"))) int image_forward(rau_ctx* ctx, hipStream_t s, int n, const void* x,
+    bool x_is_b16, float* I, float* P);
+// Its gradients: dZ = (Wp^T dS + dj (x) a)(1 - I^2); dWp += dS I^T; dWi += dZ X^T (+ the i_embed bias gradient).
+struct ConvGrads {
+  int n;                              // maps
+  const void* dS; bool ds_is_b16;     // [n][A][Sp], f32 or bf16 elements
+  const float *dj, *a, *I;            // [n][M], [n][Sp], [n][M][Sp]
+  const void* X; bool x_is_b16;       // [n][D][Sp] what i_embed read, f32 or bf16 elements
+  void* dZ; bool dz_is_b16;           // [n][M][Sp] out, stored as f32 or bf16
+  int dzf;                            // conv_dz_fused_ok: the dgrad applies (1 - I^2) itself ...
+  float* dbi_part;                    // ... and leaves the row sums of dZ here, [n][M]
+  int tied_hops;                      // > 1: dS is the sum of that many hops, outer_sum adds dj (x) a of hops 1..
+};
+// element i of a map buffer that holds bf16 (b16) or f32 elements
+inline void* map_elems(void* base, bool b16, size_t i) {
+  return b16 ? (void*)((uint16_t*)base + i) : (void*)((float*)base + i);
+}
+__attribute__((visibility("hidden"))) int conv_grads(rau_ctx* ctx, hipStream_t s, const ConvGrads& g);
 
 // ---- shared between rau_ctx.hip and the merged-hops entry points (rau_merge.hip)
 extern "C" {   // defined among the result getters, inside rau_ctx.hip's extern "C" block

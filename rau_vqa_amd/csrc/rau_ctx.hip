@@ -919,7 +919,6 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
   const rau_config& c = ctx->cfg;
   const int B = c.B, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R;
   hipStream_t st = ctx->st;
-  auto gflop = [](double m, double n, double k) { return 2.0 * m * n * k; };
   const size_t BM_ = (size_t)B * M, BS_ = (size_t)B * S, BR_ = (size_t)B * R;
   float* qf = ctx->qf + (size_t)h * BM_;
   float* ah = ctx->a + (size_t)h * BS_;
@@ -1011,9 +1010,7 @@ int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const Tru
   hipStream_t s = ws.owner;
   const size_t reg = ws.floats / 4;
   const int B = c.B, M = c.M, R = c.R, K = c.K;
-  const bool tr = ctx->mode == RAU_MODE_TRAIN;
-  const uint32_t* m_mf = (tr && mask_p(ctx, RAU_MASK_MF) > 0.f) ? ctx->mbits[RAU_MASK_MF] : nullptr;
-  auto gflop = [](double m, double n, double k) { return 2.0 * m * n * k; };
+  const Masks m = masks_of(ctx);
   const size_t BM_ = (size_t)B * M, BR_ = (size_t)B * R;
   const int rows = nh * B;
   const float* hnew = ctx->hh + (size_t)(h0 + 1) * BR_;
@@ -1027,9 +1024,7 @@ int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const Tru
     o.bias = ctx->lstm_out.b;
     o.addend = jh;
     o.add_rs = M;
-    o.emask = m_mf;
-    o.emask_e0 = (size_t)h0 * BM_;
-    o.emscale = 1.f / (1.f - mask_p(ctx, RAU_MASK_MF));
+    o.emask = m.mf; o.emask_e0 = (size_t)h0 * BM_; o.emscale = m.s_mf;
     RUNS(s, "head_gemm", gflop(rows, M, R), 0,
          gemm_nt(s, rows, M, R, hnew, R, ctx->lstm_out.W, R, mfh, M, o));
   }
@@ -1070,10 +1065,7 @@ int hop_backward(rau_ctx* ctx, int h, const float* cp, const float* Ih, const Ho
   const rau_config& c = ctx->cfg;
   const int B = c.B, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R, K = c.K;
   hipStream_t st = ctx->st;
-  const bool tr = ctx->mode == RAU_MODE_TRAIN;
-  const uint32_t* m_mf = (tr && mask_p(ctx, RAU_MASK_MF) > 0.f) ? ctx->mbits[RAU_MASK_MF] : nullptr;
-  auto sc = [&](int site) { return 1.f / (1.f - mask_p(ctx, site)); };
-  auto gflop = [](double m, double n, double k) { return 2.0 * m * n * k; };
+  const Masks m = masks_of(ctx);
   const size_t BM_ = (size_t)B * M, BS_ = (size_t)B * S, BR_ = (size_t)B * R;
   const float* qf = ctx->qf + (size_t)h * BM_;
   float* Th = ctx->T + (size_t)h * B * A * S;   // becomes dS in place
@@ -1099,9 +1091,7 @@ int hop_backward(rau_ctx* ctx, int h, const float* cp, const float* Ih, const Ho
       o.slab_floats = reg;
       o.addend = g.dmf_add;   // module-level callers: gradient through do_pred (zero in feval)
       o.add_rs = M;
-      o.emask = m_mf;
-      o.emask_e0 = (size_t)h * BM_;
-      o.emscale = sc(RAU_MASK_MF);
+      o.emask = m.mf; o.emask_e0 = (size_t)h * BM_; o.emscale = m.s_mf;
       RUN("small_gemm", gflop(B, M, K), 0,
           gemm_nn(st, B, M, K, g.dl, K, ctx->cls.W, M, dpre, M, o));
     }
@@ -1210,6 +1200,63 @@ int hop_backward(rau_ctx* ctx, int h, const float* cp, const float* Ih, const Ho
   return RAU_OK;
 }
 
+// ================================================================ image side
+// i_embed SS:238-242 and attbycontent's ifeatproj (SS:247-249), which is hop-invariant given I: P = Wp I + bp;
+// the per-hop half (+u, tanh, score, softmax, context) is att_fwd_fused.
+int image_forward(rau_ctx* ctx, hipStream_t s, int n, const void* x, bool x_is_b16, float* I, float* P) {
+  const rau_config& c = ctx->cfg;
+  const int D = c.D, S = ctx->Sp, M = c.M, A = c.A;
+  const double nS = (double)n * S;
+  if (x_is_b16) {
+    RUNS(s, "conv_embed_fwd", gflop(M, nS, D), nS * D * 2 + nS * M * 4,
+         conv_embed_fwd_b16(s, n, D, S, M, x, ctx->WiT16, ctx->i_embed.b, I));
+    RUNS(s, "conv_att_pre", gflop(A, nS, M), (nS * M + nS * A) * 4,
+         conv_att_pre_b16(s, n, M, S, A, I, ctx->WpT16, ctx->att_i.b, P));
+  } else {
+    RUNS(s, "conv_embed_fwd", gflop(M, nS, D), (nS * D + nS * M) * 4,
+         conv_embed_fwd(s, n, D, S, M, (const float*)x, ctx->WiT, ctx->i_embed.b, I, ctx->bf16));
+    RUNS(s, "conv_att_pre", gflop(A, nS, M), (nS * M + nS * A) * 4,
+         conv_att_pre(s, n, M, S, A, I, ctx->WpT, ctx->att_i.b, P, ctx->bf16));
+  }
+  return RAU_OK;
+}
+
+// The 1x1-conv gradients of g.n maps on `s`, with the bulk stream's split-K workspace: the dgrad, then the two
+// weight gradients (the att_i one is independent of dZ).  Where the per-sample tiling applies (g.dzf) the dgrad's
+// epilogue also applies (1 - I^2) and hands back per-sample row sums (the i_embed bias gradient): the i_embed
+// weight gradient then stages a plain operand (one global load and no VALU work per element less).
+int conv_grads(rau_ctx* ctx, hipStream_t s, const ConvGrads& g) {
+  const rau_config& c = ctx->cfg;
+  const int n = g.n, D = c.D, S = ctx->Sp, M = c.M, A = c.A;
+  const double nAS = (double)n * A * S, nMS = (double)n * M * S, nDS = (double)n * D * S;
+  float* slab = ctx->ws_bulk.slab;
+  if (g.dzf)
+    RUNS(s, "conv_att_dgrad", gflop(M, (double)n * S, A), (nAS + 3.0 * nMS) * 4,
+         conv_att_dgrad_dz(s, n, M, S, A, (const float*)g.dS, ctx->att_i.W, g.dj, g.a, g.I, (float*)g.dZ, g.dbi_part,
+                           g.dz_is_b16 ? 1 : 0, ctx->bf16, g.ds_is_b16 ? 1 : 0, chain_bound(ctx) ? 1 : 0));
+  else
+    RUNS(s, "conv_att_dgrad", gflop(M, (double)n * S, A), (nAS + 2.0 * nMS) * 4,
+         conv_att_dgrad(s, n, M, S, A, (const float*)g.dS, ctx->att_i.W, g.dj, g.a, (float*)g.dZ, ctx->bf16));
+  if (g.tied_hops > 1)   // + dj_h (x) a_h of the other active hops (hop 0's came out of the dgrad's epilogue)
+    RUNS(s, "outer_sum", 2.0 * (g.tied_hops - 1) * nMS,
+         (2.0 * nMS + (double)(g.tied_hops - 1) * ((double)n * M + (double)n * S)) * 4,
+         outer_sum(s, g.tied_hops, n, M, S, g.dj, g.a, (float*)g.dZ));
+  if (g.ds_is_b16)
+    RUNS(s, "conv_att_wgrad", gflop(A, M, (double)n * S), nAS * 2 + nMS * 4,
+         conv_att_wgrad_ds16(s, n, M, S, A, (const uint16_t*)g.dS, g.I, ctx->att_i.dW, slab));
+  else
+    RUNS(s, "conv_att_wgrad", gflop(A, M, (double)n * S), (nAS + nMS) * 4,
+         conv_att_wgrad(s, n, M, S, A, (const float*)g.dS, g.I, ctx->att_i.dW, slab, ctx->bf16));
+  if (g.x_is_b16)
+    RUNS(s, "conv_embed_wgrad", gflop(M, D, (double)n * S), nMS * 2 + nDS * 2,
+         conv_embed_wgrad_b16(s, n, D, S, M, (const uint16_t*)g.dZ, (const uint16_t*)g.X, ctx->i_embed.dW, slab));
+  else
+    RUNS(s, "conv_embed_wgrad", gflop(M, D, (double)n * S), (nMS * (g.dzf ? 1 : 2) + nDS) * 4,
+         conv_embed_wgrad(s, n, D, S, M, (const float*)g.dZ, g.I, (const float*)g.X, ctx->i_embed.dW, slab,
+                          ctx->bf16, ctx->i_embed.db, g.dzf));
+  return RAU_OK;
+}
+
 extern "C" {
 
 // ================================================================ forward
@@ -1226,48 +1273,22 @@ static bool head_dgrad_fwd(const rau_ctx* ctx) {
          !ctx->capture_bwd_forms_dpre;
 }
 
-int rau_forward(rau_ctx* ctx) {
-  NEED(ctx, "null ctx");
-  BatchSlot& bs = cur_batch(ctx);
-  if (!bs.held.have) return fail(RAU_ERR_STATE, "rau_forward: no batch (call rau_set_batch)");
-  ctx->mg.valid = false;   // the hop outputs are being overwritten
+// ---------------- encoder, SS:443-462
+// Layer-1 cell t+1 and layer-2 cell t do not depend on each other, so the two layers
+// advance as a wavefront: per step ONE batched split-K GEMM (h1 W_h2h1^T for layer 1;
+// x2 W_i2h2^T and h2 W_h2h2^T for layer 2; same shapes) and ONE two-cell LSTM kernel
+// that sums the partials -- TL+1 steps of 2 launches instead of 2*TL steps of 2.
+static int encoder_forward(rau_ctx* ctx, const Masks& m) {
+  const BatchSlot& bs = cur_batch(ctx);
   const rau_config& c = ctx->cfg;
-  const int B = c.B, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R,
-            H = c.H, Q = ctx->Q;
-  const int TL = bs.held.max_len;
-  hipStream_t st = ctx->st;
-  if (int rc = gen_masks(ctx, RAU_MASK_X)) return rc;
-  const bool tr = ctx->mode == RAU_MODE_TRAIN;
-  auto mk = [&](int site) -> const uint32_t* {
-    return (tr && mask_p(ctx, site) > 0.f) ? ctx->mbits[site] : nullptr;
-  };
-  auto sc = [&](int site) { return 1.f / (1.f - mask_p(ctx, site)); };
-  const uint32_t *m_we = mk(RAU_MASK_WE), *m_rnn = mk(RAU_MASK_RNN), *m_q = mk(RAU_MASK_Q),
-                 *m_x = mk(RAU_MASK_X);
+  const int B = c.B, E = c.E, Rq = c.Rq, TL = bs.held.max_len;
   const size_t BRq = (size_t)B * Rq;
-  auto gflop = [](double m, double n, double k) { return 2.0 * m * n * k; };
-
-  // ---------------- bulk stream: everything about the feature map that does not
-  // depend on the recurrence (overlaps the encoder and the hop loop below).
-  // i_embed SS:238-242: in train mode each hop clone has its own dropout mask on
-  // the feature map (SS:239, SS:343-347) -> xd[h] = X (.) mask_h, then GEMMs over
-  // groups of hops; in evaluate mode I is hop-invariant and computed once.
-  // attbycontent's ifeatproj (SS:247-249) is hop-invariant given I: P = Wp I + bp;
-  // the per-hop half (+u, tanh, score, softmax, context) is att_fwd_fused.
-  // Hops are launched in groups of `hop_group` so hop h's chain can start as soon
-  // as its group is done while the bulk stream works on the later groups.
-  // ---------------- encoder, SS:443-462
-  // Layer-1 cell t+1 and layer-2 cell t do not depend on each other, so the two layers
-  // advance as a wavefront: per step ONE batched split-K GEMM (h1 W_h2h1^T for layer 1;
-  // x2 W_i2h2^T and h2 W_h2h2^T for layer 2; same shapes) and ONE two-cell LSTM kernel
-  // that sums the partials -- TL+1 steps of 2 launches instead of 2*TL steps of 2.
-  auto encoder_forward = [&]() -> int {
+  hipStream_t st = ctx->st;
   if (TL > 0) {
     const int rows = TL * B;
     const size_t G4 = (size_t)B * 4 * Rq;
     RUN("embed_fwd", 0, rows * E * 8.0,
-        embed_fwd(st, rows, E, c.V, ctx->grp[RAU_GROUP_EMBED].w, bs.tokens, m_we, sc(RAU_MASK_WE),
-                  ctx->we));
+        embed_fwd(st, rows, E, c.V, ctx->grp[RAU_GROUP_EMBED].w, bs.tokens, m.we, m.s_we, ctx->we));
     const bool ws_path = (ctx->mode == RAU_MODE_EVAL ? ctx->enc_ws : ctx->enc_ws_train) && ctx->perr_h;
     // Layer-1 input projection of every token (no recurrence in it).  Only the first tokens' rows
     // are needed at once: they stay on this stream, the rest runs on the weight-gradient stream
@@ -1317,7 +1338,7 @@ int rau_forward(rau_ctx* ctx) {
       q.h2 = ctx->h2; q.c2 = ctx->c2; q.tc2 = ctx->tc2;
       q.Wh1 = ctx->h2h[0].W; q.Wi2 = ctx->i2h[1].W; q.Wh2 = ctx->h2h[1].W;
       q.bi2 = ctx->i2h[1].b; q.bh2 = ctx->h2h[1].b;
-      q.mask = m_rnn; q.mscale = sc(RAU_MASK_RNN);
+      q.mask = m.rnn; q.mscale = m.s_rnn;
       q.cnt = ctx->ws_cnt; q.err = ctx->perr_d;
       RUN("enc_ws", (double)TL * 3 * gflop(B, 4 * Rq, Rq), 0, enc_ws_forward(st, GATES_DEEP, q));
       HIPC(hipMemcpyAsync(ctx->perr_h, ctx->perr_d, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1348,7 +1369,7 @@ int rau_forward(rau_ctx* ctx) {
         C1.h = ctx->h1 + (size_t)s * BRq; C1.h_rs = Rq;
         C1.tanhc = ctx->tc1 + (size_t)(s - 1) * BRq;
         C1.drop_out = ctx->x2 + (size_t)(s - 1) * BRq;   // layer-2 input, DeepLSTM.lua:39
-        C1.mask = m_rnn; C1.mask_e0 = (size_t)(s - 1) * BRq; C1.mscale = sc(RAU_MASK_RNN);
+        C1.mask = m.rnn; C1.mask_e0 = (size_t)(s - 1) * BRq; C1.mscale = m.s_rnn;
       }
       if (s >= 2) {  // layer-2 cell t = s - 1
         const int t = s - 1;
@@ -1368,11 +1389,101 @@ int rau_forward(rau_ctx* ctx) {
     }
   }
   return 0;
-  };
+}
+
+// The passes on `sb` that make the maps the convs read out of the batch's nX maps `feats`.  In train mode each hop
+// clone has its own dropout mask on the feature map (SS:239, SS:343-347) -> xd[h] = X (.) mask_h (tied: one copy); in
+// evaluate mode the convs read the batch itself.  Sets ctx->xw and ctx->x_shared; *x16_out: the hop copies are bf16.
+static int feature_maps(rau_ctx* ctx, hipStream_t sb, const Masks& m, const float* feats, int nX, bool* x16_out) {
+  const rau_config& c = ctx->cfg;
+  const int B = c.B, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, H = c.H;
+  const bool tied = ctx->fwd_tied;
+  // feature-map dropout, SS:239: unless the caller supplied the mask, the pass that makes the H masked
+  // copies draws the keep bits itself (they have no other reader on this path)
+  // bf16 mode: the hop copies of the feature map are stored as bf16 (to halve an H-fold buffer; the one tied
+  // copy stays f32 in xd and feeds the f32-storage kernels, which round their operands themselves)
+  const bool x16 = m.x && ctx->xd16 && !tied;
+  const int HX = tied ? 1 : H;         // masked copies: the mask site has HX * B * D * SL elements
+  const bool x_gen = m.x && !ctx->mexplicit[RAU_MASK_X] && SL == S && ((size_t)B * D * S) % 16 == 0;
+  if (!x_gen)
+    if (int rc = gen_masks(ctx, -1, RAU_MASK_X, sb)) return rc;
+  RUNS(sb, "transpose", 0, (double)M * D * 8, transpose2d(sb, M, D, ctx->i_embed.W, ctx->WiT, ctx->WiT16));
+  RUNS(sb, "transpose", 0, (double)A * M * 8, transpose2d(sb, A, M, ctx->att_i.W, ctx->WpT, ctx->WpT16));
+  // the batch's element type: 16-bit and fp8 maps are widened (exactly) by the pass that reads them
+  const int ft = cur_batch(ctx).held.feat_type;
+  const double xb = (double)feat_elem_bytes(ft);   // bytes per element read from the batch
+  if (x_gen)
+    RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)HX * B * D * S * (x16 ? 2 : 4),
+         dropout_features_gen(sb, ctx->seed, RAU_MASK_X, ctx->step, ctx->mp[RAU_MASK_X], ctx->dkey, HX,
+                              (size_t)B * D * S, feats, m.s_x, x16 ? (void*)ctx->xd16 : (void*)ctx->xd,
+                              x16 ? 1 : 0, ft));
+  else if (x16)
+    RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * 2,
+         dropout_features_b16(sb, H, (size_t)B * D * S, feats, m.x, m.s_x, ctx->xd16, ft));
+  else if (m.x)
+    RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)HX * B * D * S * 4,
+         dropout_features(sb, HX, (size_t)B * D * S, feats, m.x, m.s_x, ctx->xd, 0, SL, S, ft));
+  // no mask: the GEMMs read the batch itself -- a 16-bit one through its f32 image in xd (unused here),
+  // so that they are the f32 batch's kernels with the f32 batch's operands
+  ctx->xw = const_cast<float*>(feats);
+  if (!m.x && ft != RAU_FEAT_F32) {
+    ctx->xw = ctx->xd;
+    RUNS(sb, "widen_features", 0, (double)nX * D * S * (xb + 4),
+         widen_features(sb, (size_t)nX * D, SL, S, feats, ctx->xw, ft));
+  }
+  ctx->x_shared = m.x ? ctx->xd : ctx->xw;   // what the shared path's i_embed reads (and its weight gradient)
+  *x16_out = x16;
+  return RAU_OK;
+}
+
+// dpre = (dl Wc (+ addend)) (.) mask and dhn = dpre Wo of hops [h0, h0 + nh) on ws.owner: the backward's two
+// products that do not depend on the recurrence.
+static int head_dgrad(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const float* addend) {
+  const rau_config& c = ctx->cfg;
+  const int B = c.B, M = c.M, R = c.R, K = c.K;
+  const size_t BM_ = (size_t)B * M, BR_ = (size_t)B * R;
+  const Masks m = masks_of(ctx);
+  hipStream_t s = ws.owner;
+  LinOpts o = lin_opts(ctx, ws);
+  if (addend) { o.addend = addend; o.add_rs = M; }
+  o.emask = m.mf; o.emask_e0 = (size_t)h0 * BM_; o.emscale = m.s_mf;
+  RUNS(s, "head_dgrad", gflop(nh * B, M, K), 0,
+       gemm_nn(s, nh * B, M, K, ctx->dl + (size_t)h0 * B * K, K, ctx->cls.W, M, ctx->dpre + (size_t)h0 * BM_, M, o));
+  const LinOpts o2 = lin_opts(ctx, ws);
+  RUNS(s, "head_dgrad", gflop(nh * B, R, M), 0,
+       gemm_nn(s, nh * B, R, M, ctx->dpre + (size_t)h0 * BM_, M, ctx->lstm_out.W, R, ctx->dhn + (size_t)h0 * BR_, R,
+               o2));
+  return RAU_OK;
+}
+
+// Classifier + criterion heads of the finished hops [gstart, h] on the side stream, head_max hops per launch
+static int forward_heads(rau_ctx* ctx, int gstart, int h, int head_max, const Truth& truth) {
+  for (int h0 = gstart; h0 <= h; h0 += head_max)
+    if (int rc = hop_forward_head(ctx, ctx->ws_side, h0, std::min(head_max, h + 1 - h0), truth)) return rc;
+  // The backward's first two products do not depend on the recurrence either: dpre = (dl Wc) (.) mask
+  // and dhn = dpre Wo of these hops follow their criterion head on the same (idle) stream, so the
+  // forward / backward seam -- where the bulk stream and the matrix pipes wait for the chain -- is two
+  // GEMMs shorter.  dl is not yet scaled by the hop weights (they arrive with rau_backward); both
+  // products are linear in it, so rau_backward scales dl, dpre and dhn together.
+  if (head_dgrad_fwd(ctx)) return head_dgrad(ctx, ctx->ws_side, gstart, h + 1 - gstart, nullptr);
+  return RAU_OK;
+}
+
+int rau_forward(rau_ctx* ctx) {
+  NEED(ctx, "null ctx");
+  BatchSlot& bs = cur_batch(ctx);
+  if (!bs.held.have) return fail(RAU_ERR_STATE, "rau_forward: no batch (call rau_set_batch)");
+  ctx->mg.valid = false;   // the hop outputs are being overwritten
+  const rau_config& c = ctx->cfg;
+  const int B = c.B, Rq = c.Rq, D = c.D, S = ctx->Sp, M = c.M, A = c.A, R = c.R, H = c.H, Q = ctx->Q;
+  const int TL = bs.held.max_len;
+  hipStream_t st = ctx->st;
+  if (int rc = gen_masks(ctx, RAU_MASK_X)) return rc;
+  const Masks m = masks_of(ctx);
   // RAU_XDROP_TIED: every hop clone sees the SAME masked map, so a train-mode step takes the shared path too (one
   // masked copy, both convs once) and its backward sums the hops in front of one set of conv gradients
-  const bool tied = tr && ctx->xdrop == RAU_XDROP_TIED;
-  ctx->I_shared = (m_x == nullptr) || tied;
+  const bool tied = ctx->mode == RAU_MODE_TRAIN && ctx->xdrop == RAU_XDROP_TIED;
+  ctx->I_shared = (m.x == nullptr) || tied;
   ctx->fwd_tied = tied;
   // A batch with an image table.  Evaluate mode: nothing per sample touches the maps (no dropout on X), so
   // i_embed and the attention pre-activation run once per IMAGE and the attention kernels read sample b's
@@ -1399,84 +1510,35 @@ int rau_forward(rau_ctx* ctx) {
     ctx->cur = ctx->groups;
   }
   const std::vector<int>& gsz = ctx->cur;
-  {
-    hipStream_t sb = ctx->st2;
-    HIPC(hipEventRecord(ctx->evA, st));
-    HIPC(hipStreamWaitEvent(sb, ctx->evA, 0));
-    // feature-map dropout, SS:239: unless the caller supplied the mask, the pass that makes the H masked
-    // copies draws the keep bits itself (they have no other reader on this path)
-    // bf16 mode: the hop copies of the feature map are stored as bf16 (to halve an H-fold buffer; the one tied
-    // copy stays f32 in xd and feeds the f32-storage kernels, which round their operands themselves)
-    const bool x16 = m_x && ctx->xd16 && !tied;
-    const int HX = tied ? 1 : H;         // masked copies: the mask site has HX * B * D * SL elements
-    const bool x_gen = m_x && !ctx->mexplicit[RAU_MASK_X] && SL == S && ((size_t)B * D * S) % 16 == 0;
-    if (!x_gen)
-      if (int rc = gen_masks(ctx, -1, RAU_MASK_X, sb)) return rc;
-    RUNS(sb, "transpose", 0, (double)M * D * 8, transpose2d(sb, M, D, ctx->i_embed.W, ctx->WiT, ctx->WiT16));
-    RUNS(sb, "transpose", 0, (double)A * M * 8, transpose2d(sb, A, M, ctx->att_i.W, ctx->WpT, ctx->WpT16));
-    // the batch's element type: 16-bit and fp8 maps are widened (exactly) by the pass that reads them
-    const int ft = bs.held.feat_type;
-    const double xb = (double)feat_elem_bytes(ft);   // bytes per element read from the batch
-    if (x_gen)
-      RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)HX * B * D * S * (x16 ? 2 : 4),
-           dropout_features_gen(sb, ctx->seed, RAU_MASK_X, ctx->step, ctx->mp[RAU_MASK_X], ctx->dkey, HX,
-                                (size_t)B * D * S, feats, sc(RAU_MASK_X),
-                                x16 ? (void*)ctx->xd16 : (void*)ctx->xd, x16 ? 1 : 0, ft));
-    else if (x16)
-      RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)H * B * D * S * 2,
-           dropout_features_b16(sb, H, (size_t)B * D * S, feats, m_x, sc(RAU_MASK_X), ctx->xd16, ft));
-    else if (m_x)
-      RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)HX * B * D * S * 4,
-           dropout_features(sb, HX, (size_t)B * D * S, feats, m_x, sc(RAU_MASK_X), ctx->xd, 0, SL,
-                            S, ft));
-    // no mask: the GEMMs read the batch itself -- a 16-bit one through its f32 image in xd (unused here),
-    // so that they are the f32 batch's kernels with the f32 batch's operands
-    ctx->xw = const_cast<float*>(feats);
-    if (!m_x && ft != RAU_FEAT_F32) {
-      ctx->xw = ctx->xd;
-      RUNS(sb, "widen_features", 0, (double)nX * D * S * (xb + 4),
-           widen_features(sb, (size_t)nX * D, SL, S, feats, ctx->xw, ft));
-    }
-    ctx->x_shared = m_x ? ctx->xd : ctx->xw;   // what the shared path's i_embed reads (and its weight gradient)
-    for (int h0 = 0; h0 < H; h0 += gsz[h0]) {
-      const int nBI = ctx->I_shared ? nX : gsz[h0] * B;
-      const size_t hb = ctx->I_shared ? 0 : (size_t)h0 * B;  // first (hop, sample) row
-      const float* xin = m_x ? ctx->xd + hb * D * S : ctx->xw;
-      float* Ig = ctx->I + hb * M * S;
-      float* Pg = ctx->I_shared ? ctx->P0 : ctx->T + hb * A * S;
-      if (x16)
-        RUNS(sb, "conv_embed_fwd", gflop(M, (double)nBI * S, D),
-             (double)nBI * D * S * 2 + (double)nBI * M * S * 4,
-             conv_embed_fwd_b16(sb, nBI, D, S, M, (const uint16_t*)ctx->xd16 + hb * D * S, ctx->WiT16,
-                                ctx->i_embed.b, Ig));
-      else
-        RUNS(sb, "conv_embed_fwd", gflop(M, (double)nBI * S, D),
-             ((double)nBI * D * S + (double)nBI * M * S) * 4,
-             conv_embed_fwd(sb, nBI, D, S, M, xin, ctx->WiT, ctx->i_embed.b, Ig, ctx->bf16));
-      if (x16)
-        RUNS(sb, "conv_att_pre", gflop(A, (double)nBI * S, M),
-             ((double)nBI * M * S + (double)nBI * A * S) * 4,
-             conv_att_pre_b16(sb, nBI, M, S, A, Ig, ctx->WpT16, ctx->att_i.b, Pg));
-      else
-        RUNS(sb, "conv_att_pre", gflop(A, (double)nBI * S, M),
-             ((double)nBI * M * S + (double)nBI * A * S) * 4,
-             conv_att_pre(sb, nBI, M, S, A, Ig, ctx->WpT, ctx->att_i.b, Pg, ctx->bf16));
-      HIPC(hipEventRecord(ctx->evF[h0], sb));
-    }
+  // ---------------- bulk stream: everything about the feature map that does not depend on the recurrence (overlaps
+  // the encoder and the hop loop below); in evaluate mode I is hop-invariant and computed once.  Hops are launched in
+  // groups of `hop_group` so hop h's chain can start as soon as its group is done while this stream works on the rest.
+  hipStream_t sb = ctx->st2;
+  HIPC(hipEventRecord(ctx->evA, st));
+  HIPC(hipStreamWaitEvent(sb, ctx->evA, 0));
+  bool x16 = false;
+  if (int rc = feature_maps(ctx, sb, m, feats, nX, &x16)) return rc;
+  for (int h0 = 0; h0 < H; h0 += gsz[h0]) {
+    const int nBI = ctx->I_shared ? nX : gsz[h0] * B;
+    const size_t hb = ctx->I_shared ? 0 : (size_t)h0 * B;  // first (hop, sample) row
+    const void* xin = x16 ? map_elems(ctx->xd16, true, hb * D * S) : m.x ? ctx->xd + hb * D * S : ctx->xw;
+    if (int rc = image_forward(ctx, sb, nBI, xin, x16, ctx->I + hb * M * S,
+                               ctx->I_shared ? ctx->P0 : ctx->T + hb * A * S))
+      return rc;
+    HIPC(hipEventRecord(ctx->evF[h0], sb));
   }
-
-  if (int rc = encoder_forward()) return rc;
+  if (int rc = encoder_forward(ctx, m)) return rc;
   RUN("gather_q", 0, (double)B * Q * 8,
       gather_q(st, B, Rq, TL, bs.lens_d, ctx->c1, ctx->h1, ctx->c2, ctx->h2, ctx->q));
 
   // ---------------- RAU hops, SS:467-520
   const size_t BM_ = (size_t)B * M, BR_ = (size_t)B * R;
   RUN("apply_mask", 0, (double)H * B * Q * 8,
-      apply_mask(st, (size_t)H * B * Q, (size_t)B * Q, ctx->q, m_q, sc(RAU_MASK_Q), ctx->qd));
+      apply_mask(st, (size_t)H * B * Q, (size_t)B * Q, ctx->q, m.q, m.s_q, ctx->qd));
   bool q_split = false;
   {  // q_embed's question half (SS:233) for every hop clone; without dropout on q (evaluate mode) the
      // clones see the same rows: computed once
-    ctx->yq_shared = (m_q == nullptr);
+    ctx->yq_shared = (m.q == nullptr);
     // with dropout: hop 0's rows here, the other hops' rows on the weight-gradient stream (hop 1 waits)
     q_split = !ctx->yq_shared && side_split(ctx) && H > 1;
     const int qrows = (ctx->yq_shared || q_split) ? B : H * B;
@@ -1497,10 +1559,6 @@ int rau_forward(rau_ctx* ctx) {
                  ctx->Yq + (size_t)B * M, M, o));
     HIPC(hipEventRecord(ctx->evQ, ctx->st3));
   }
-  // i_embed SS:238-242 does not depend on the recurrence: all hops in one launch.
-  // Train mode: each hop clone has its own dropout mask on the feature map
-  // (SS:239, SS:343-347) -> xd[h] = X (.) mask_h, then one GEMM over H*B samples.
-  // Evaluate mode: dropout is the identity, so I is hop-invariant and computed once.
   HIPC(hipMemsetAsync(ctx->cc, 0, BR_ * sizeof(float), st));  // att_c, att_h zeros SS:362-365
   HIPC(hipMemsetAsync(ctx->hh, 0, BR_ * sizeof(float), st));
   const Truth truth = step_truth(ctx);
@@ -1526,29 +1584,7 @@ int rau_forward(rau_ctx* ctx) {
     if (group_end || h + 1 - gstart >= head_max) {
       HIPC(hipEventRecord(ctx->evH[h], st));
       HIPC(hipStreamWaitEvent(ctx->st3, ctx->evH[h], 0));
-      for (int h0 = gstart; h0 <= h; h0 += head_max)
-        if (int rc = hop_forward_head(ctx, ctx->ws_side, h0, std::min(head_max, h + 1 - h0), truth))
-          return rc;
-      if (head_dgrad_fwd(ctx)) {
-        // The backward's first two products do not depend on the recurrence either: dpre = (dl Wc) (.) mask
-        // and dhn = dpre Wo of these hops follow their criterion head on the same (idle) stream, so the
-        // forward / backward seam -- where the bulk stream and the matrix pipes wait for the chain -- is two
-        // GEMMs shorter.  dl is not yet scaled by the hop weights (they arrive with rau_backward); both
-        // products are linear in it, so rau_backward scales dl, dpre and dhn together.
-        const int nh = h + 1 - gstart;
-        const bool trm = ctx->mode == RAU_MODE_TRAIN;
-        LinOpts o = lin_opts(ctx, ctx->ws_side);
-        o.emask = (trm && mask_p(ctx, RAU_MASK_MF) > 0.f) ? ctx->mbits[RAU_MASK_MF] : nullptr;
-        o.emask_e0 = (size_t)gstart * BM_;
-        o.emscale = 1.f / (1.f - mask_p(ctx, RAU_MASK_MF));
-        RUNS(ctx->st3, "head_dgrad", 2.0 * nh * B * M * c.K, 0,
-             gemm_nn(ctx->st3, nh * B, M, c.K, ctx->dl + (size_t)gstart * B * c.K, c.K, ctx->cls.W, M,
-                     ctx->dpre + (size_t)gstart * BM_, M, o));
-        const LinOpts o2 = lin_opts(ctx, ctx->ws_side);
-        RUNS(ctx->st3, "head_dgrad", 2.0 * nh * B * R * M, 0,
-             gemm_nn(ctx->st3, nh * B, R, M, ctx->dpre + (size_t)gstart * BM_, M, ctx->lstm_out.W, R,
-                     ctx->dhn + (size_t)gstart * BR_, R, o2));
-      }
+      if (int rc = forward_heads(ctx, gstart, h, head_max, truth)) return rc;
       gstart = h + 1;
     }
   }
@@ -1595,13 +1631,227 @@ static int upload_hop_weights(rau_ctx* ctx, const StepLoss& l) {
 // `ext` (rau_backward_ext): caller-supplied gradients join dl behind its scaling (ext_dl, in scale_hops' place), s
 // behind select_signal (ext_signal) and the attention addend behind att_sup_grad (ext_da); each of the three sites
 // then runs with or without its built-in term.  Per-row terms again: dpre / dhn are formed here, every hop is active.
+// The opening: from the loss terms to what the hop loop reads -- the final dl, the attention addend att_da and
+// (unless the forward left them) dpre / dhn of the active hops.  `t`: the ground truth the forward's head read.
+static int loss_gradients(rau_ctx* ctx, const StepLoss& loss, const Truth& t) {
+  const bool sel = loss.select_w != nullptr, att = loss.att_w != nullptr, mrg = loss.merge_w != nullptr;
+  const rau_out_grads& ext = loss.ext;
+  const rau_config& c = ctx->cfg;
+  const int B = c.B, S = ctx->Sp, SL = c.S, M = c.M, R = c.R, K = c.K, H = c.H, HA = loss.active;
+  const HopwLayout at(H);
+  const BatchSlot& bs = cur_batch(ctx);
+  hipStream_t st = ctx->st;
+  // dpred:mul(w[h])  SS:569 / MS:568-570 / Full:587-589
+  if (!ctx->capturing)   // (rau_graph_step uploads the weights before it launches the graph)
+    if (int rc = upload_hop_weights(ctx, loss)) return rc;
+  if (ext.d_logits || (loss.has_ext() && !ctx->fwd_dl))
+    // one pass in scale_hops' place: dl * hop_w + d_logits; without a criterion gradient dl = d_logits (or +0)
+    RUN("ext_dl", (double)H * B * K * (ctx->fwd_dl ? 2 : 0), (double)H * B * K * (ctx->fwd_dl ? 12 : 8),
+        ext_dl(st, H, (size_t)B * K, ctx->fwd_dl ? ctx->hopw_d : nullptr, ext.d_logits, ctx->dl));
+  else if (ctx->dpre_fwd && !loss.forms_dpre())   // the forward formed dpre / dhn from the unscaled dl: scale all three
+    RUN("scale_hops", 0, (double)H * B * (K + M + R) * 8,
+        scale_hops3(st, H, ctx->hopw_d, (size_t)B * K, ctx->dl, (size_t)B * M, ctx->dpre, (size_t)B * R, ctx->dhn));
+  else
+    RUN("scale_hops", 0, (double)H * B * K * 8, scale_hops(st, H, (size_t)B * K, ctx->hopw_d, ctx->dl));
+  // mrg: w_uni dCE(uni row) + w_sel dCE(select row) join the scaled dl of every hop, in front of all its consumers
+  // (head_dgrad and sel_add below, the classifier's weight gradient in mult_wgrads)
+  if (mrg)
+    RUN("merge_grad", 0, (double)H * B * K * 16,
+        merge_grad(st, H, B, K, ctx->logits, ctx->dopred, t, ctx->hopw_d + at.merge_w, 0.f, 0.f, ctx->dl));
+  // ---------------- RAU BPTT, SS:561-578
+  // Off the recurrence: dpre = (dl Wc) (.) mask and dhn = dpre Wo for all active hops at once.
+  // sel: the gradient through do_pred, s (x) wd, joins dl Wc in front of the mask (HopGrad::dmf_add's position).
+  // A per-row term cannot be folded into what the forward formed (one scale per hop), so both products are
+  // formed here from the scaled dl -- which is also the order the bf16 emulation rounds in.
+  if (sel)
+    RUN("select_signal", 0, (double)HA * B * M * 4,
+        select_signal(st, HA * B, B, K, M, ctx->dopred, ctx->argmax_d, t, ctx->hopw_d + at.select_w, ctx->do_pred.W,
+                      ctx->sel_s, ctx->sel_add));
+  if (ext.d_dopred)   // s (+)= (d_dopred x)(1 - x) through the sigmoid, and the addend formed from the final s
+    RUN("ext_signal", 0, (double)HA * B * M * 4,
+        ext_signal(st, HA * B, M, ctx->dopred, ext.d_dopred, ctx->do_pred.W, sel, ctx->sel_s, ctx->sel_add));
+  // att: the gradient at the attprob output of all active hops, -(att_w[h] t / (a + eps)) / B, read by the attention
+  // backward of each hop (HopGrad::da_out).  The targets may have come after the forward: it does not read them.
+  if (att)
+    RUN("att_sup_grad", 0, (double)HA * B * S * 12,
+        att_sup_grad(st, HA, B, SL, ctx->a, S, bs.att_t_d, S, bs.held.regions ? bs.nreg_d : nullptr,
+                     ctx->hopw_d + at.att_w, 0.f, ctx->att_da, S));
+  if (ext.d_attprob)   // the dense [H,n,S] gradient (added) into the pitched addend, zeros behind the counts
+    RUN("ext_da", 0, (double)HA * B * S * (att ? 12 : 8),
+        ext_da(st, HA, B, SL, ext.d_attprob, bs.held.regions ? bs.nreg_d : nullptr, att, ctx->att_da, S));
+  if (HA > 0 && (!ctx->dpre_fwd || loss.forms_dpre()))
+    return head_dgrad(ctx, ctx->ws_chain, 0, HA, (sel || ext.d_dopred) ? ctx->sel_add : nullptr);
+  return RAU_OK;
+}
+
+// The 1x1-conv gradients of the launch group that starts with hop h, on the bulk stream (dZ only feeds weight
+// gradients; the feature-map gradient is dead, SS:579, never formed); HA = the active hops.
+static int group_conv_grads(rau_ctx* ctx, int h, int group, int HA) {
+  const rau_config& c = ctx->cfg;
+  const int B = c.B, D = c.D, S = ctx->Sp, M = c.M, A = c.A;
+  hipStream_t sb = ctx->st2;
+  ConvGrads g{};
+  if (!ctx->I_shared) {
+    const size_t hb = (size_t)h * B;
+    g.n = (std::min(h + group, HA) - h) * B;   // active hops of this group
+    g.dzf = conv_dz_fused_ok(S, M, ctx->bf16);
+    g.ds_is_b16 = ctx->ds16_step;
+    g.dS = g.ds_is_b16 ? map_elems(ctx->dS16, true, hb * A * S) : ctx->T + hb * A * S;
+    g.dj = ctx->dj + hb * M; g.a = ctx->a + hb * S; g.I = ctx->I + hb * M * S;
+    g.x_is_b16 = g.dz_is_b16 = ctx->xd16 && g.dzf;
+    g.X = g.x_is_b16 ? map_elems(ctx->xd16, true, hb * D * S) : ctx->xd + hb * D * S;
+    g.dZ = map_elems(ctx->dZ, g.dz_is_b16, hb * M * S);
+    g.dbi_part = ctx->dbi_part + hb * M;
+    if (int rc = conv_grads(ctx, sb, g)) return rc;
+    if (g.dzf && h == 0)   // last group: i_embed bias gradient = column sums of the per-sample rows
+      RUNS(sb, "colsum", 0, (double)HA * B * M * 4,
+           colsum_acc(sb, HA * B, M, ctx->dbi_part, M, ctx->i_embed.db, ctx->ws_bulk.coltmp));
+    return RAU_OK;
+  }
+  g.n = B; g.I = ctx->I;
+  if (ctx->fwd_tied) {
+    // Tied feature-map dropout (train mode, I and X' shared): the conv gradients are linear in what each hop
+    // hands back, so the hops are summed first (tied_bwd.hip) and every conv gradient runs once, at n = B.
+    // The sum of dS goes to a buffer of its own: T keeps every hop's dS, as on the per-hop paths.
+    RUNS(sb, "hop_sum", 0, (double)(HA + 1) * B * A * S * 4, hop_sum(sb, HA, B, A, c.S, S, ctx->T, ctx->dS_sum));
+    g.dS = ctx->dS_sum; g.dj = ctx->dj; g.a = ctx->a; g.X = ctx->x_shared; g.dZ = ctx->dZ; g.tied_hops = HA;
+    return conv_grads(ctx, sb, g);
+  }
+  for (int hh2 = 0; hh2 < HA; ++hh2) {  // evaluate mode: I (and X) shared by all hops
+    const size_t hb = (size_t)hh2 * B;
+    g.dS = ctx->T + hb * A * S; g.dj = ctx->dj + hb * M; g.a = ctx->a + hb * S;
+    g.X = ctx->xw; g.dZ = ctx->dZ + hb * M * S;
+    if (int rc = conv_grads(ctx, sb, g)) return rc;
+  }
+  return RAU_OK;
+}
+
+// ---------------- mult-group weight gradients, one GEMM per weight over all active hops, on the stream and with
+// the scratch of one record (wg_bulk & 1: the bulk stream's).  sig: the selection head's weight gradient exists.
+static int mult_wgrads(rau_ctx* ctx, int HA, bool sig, int wg_bulk) {
+  const rau_config& c = ctx->cfg;
+  const int B = c.B, S = ctx->Sp, SL = c.S, M = c.M, A = c.A;
+  const StreamWs& ws = (wg_bulk & 1) ? ctx->ws_bulk : ctx->ws_side;
+  hipStream_t sw = ws.owner;
+  HIPC(hipStreamWaitEvent(sw, ctx->evW, 0));
+  const int rows = HA * B;                 // active hops only
+  if (rows == 0) {
+    HIPC(hipEventRecord(ctx->evM3, sw));
+    return 0;
+  }
+  TnProblem pr[13];   // dW += dY^T X and db += column sums of dY for the nine Linears: one grouped launch
+  const int np = mult_wgrad_problems(ctx, pr);
+  double fl = 0;
+  for (int i = 0; i < np; ++i) fl += gflop(pr[i].M, pr[i].N, rows);
+  RUNS(sw, "wgrad_gemm", fl, 0, gemm_tn_group_acc(sw, pr, np, rows, ws.slab, ws.floats, lin_mode(ctx).bf16));
+  if (sig)   // the head's own weights: dwd += sum s mf, dbd += sum s (f32 dot products in every dtype)
+    RUNS(sw, "select_wgrad", 2.0 * rows * (M + 1), (double)rows * M * 4,
+         select_wgrad(sw, rows, M, ctx->sel_s, ctx->mf, ctx->do_pred.dW, ctx->do_pred.db));
+  // att_score: dws = sum dz T ; dbs = sum dz.  att_i bias: sum dS.  i_embed bias: sum dZ.
+  RUNS(sw, "colsum", 0, (double)rows * A * 4, colsum_acc(sw, rows, A, ctx->dwsp, A, ctx->att_score.dW, ws.coltmp));
+  HIPC(hipMemsetAsync(ctx->tmpS, 0, S * sizeof(float), sw));
+  RUNS(sw, "colsum", 0, (double)rows * S * 4, colsum_acc(sw, rows, SL, ctx->dz, S, ctx->tmpS, ws.coltmp));
+  RUNS(sw, "colsum", 0, S * 4.0, colsum_acc(sw, SL, 1, ctx->tmpS, 1, ctx->att_score.db, ws.coltmp));
+  RUNS(sw, "colsum", 0, (double)rows * A * 4, colsum_acc(sw, rows, A, ctx->du, A, ctx->att_i.db, ws.coltmp));
+  HIPC(hipEventRecord(ctx->evM3, sw));   // with evD: the mult group's gradients are final
+  return 0;
+}
+
+// Encoder weight gradients of all TL tokens, also on the weight-gradient stream (wg_bulk & 2: the bulk stream):
+// one launch behind the BPTT.  (Two time chunks -- the gradients of tokens t > uc are final once wavefront step
+// uc is done -- were tried: running the first chunk under the second half of the BPTT slows that chain by more
+// than the shorter tail saves, measured 11.05 vs 10.6 ms.)
+static int enc_wgrads(rau_ctx* ctx, int TL, int wg_bulk) {
+  const StreamWs& ws = (wg_bulk & 2) ? ctx->ws_bulk : ctx->ws_side;
+  hipStream_t sw = ws.owner;
+  HIPC(hipEventRecord(ctx->evE, ctx->st));
+  HIPC(hipStreamWaitEvent(sw, ctx->evE, 0));
+  const int nr = TL * ctx->cfg.B;
+  TnProblem pr[13];
+  const int np = enc_wgrad_problems(ctx, 0, pr);
+  double fl = 0;
+  for (int i = 0; i < np; ++i) fl += gflop(pr[i].M, pr[i].N, nr);
+  RUNS(sw, "wgrad_gemm", fl, 0, gemm_tn_group_acc(sw, pr, np, nr, ws.slab, ws.floats, lin_mode(ctx).bf16));
+  return 0;
+}
+
+// ---------------- encoder BPTT, SS:581-596 -- the same two-layer wavefront, reversed:
+// step u handles layer-2 cell u and layer-1 cell u+1; their incoming dh are the
+// K-split partials of the previous step's dG (dG2 W_h2h2, dG2 W_i2h2 through the
+// inter-layer dropout, dG1 W_h2h1), one batched GEMM, summed inside the cell kernel.
+// Then the gradient at the word embeddings and the encoder's weight gradients.
+static int encoder_backward(rau_ctx* ctx, const Masks& m, int wg_bulk) {
+  const BatchSlot& bs = cur_batch(ctx);
+  const rau_config& c = ctx->cfg;
+  const int B = c.B, E = c.E, Rq = c.Rq, Q = ctx->Q, TL = bs.held.max_len;
+  const size_t BRq = (size_t)B * Rq;
+  hipStream_t st = ctx->st;
+  if (TL <= 0) return RAU_OK;
+  const int rows = TL * B;
+  const size_t G4 = (size_t)B * 4 * Rq;
+  for (int u = TL; u >= 0; --u) {
+    const float* Ap[3];
+    const float* Wp[3];
+    int nb = 0, iq2 = -1, iqx = -1, iq1 = -1;
+    if (u >= 1 && u + 1 <= TL) { Ap[nb] = ctx->dG2 + (size_t)u * G4; Wp[nb] = ctx->h2h[1].W; iq2 = nb++; }
+    if (u + 1 <= TL) { Ap[nb] = ctx->dG2 + (size_t)u * G4; Wp[nb] = ctx->i2h[1].W; iqx = nb++; }
+    if (u + 2 <= TL) { Ap[nb] = ctx->dG1 + (size_t)(u + 1) * G4; Wp[nb] = ctx->h2h[0].W; iq1 = nb++; }
+    int nsp = 0;
+    if (nb > 0)
+      RUN("enc_h2h_dgrad", gflop(B, Rq, 4 * Rq) * nb, 0,
+          gemm_nn_batched_deferred(st, lin_mode(ctx), nb, B, Rq, 4 * Rq, Ap, 4 * Rq, Wp, Rq, ctx->ws_chain.slab,
+                                   ctx->ws_chain.floats, &nsp));
+    LstmBwdCells cells{};
+    cells.lens = bs.lens_d;
+    cells.dq_rs = Q;
+    if (u >= 1) {  // layer-2 cell t = u
+      LstmBwdCell& C2 = cells.c[cells.n++];
+      C2.gates = ctx->G2 + (size_t)(u - 1) * G4;
+      C2.c_prev = ctx->c2 + (size_t)(u - 1) * BRq; C2.cp_rs = Rq;
+      C2.tanhc = ctx->tc2 + (size_t)(u - 1) * BRq;
+      C2.slabA = iq2 >= 0 ? ctx->ws_chain.slab + (size_t)iq2 * nsp * BRq : nullptr;
+      C2.nA = iq2 >= 0 ? nsp : 0;
+      C2.slabB = nullptr; C2.nBp = 0; C2.maskB = nullptr; C2.maskB_e0 = 0; C2.mscaleB = 1.f;
+      C2.dc_next = u < TL ? ctx->edc[1][(u + 1) & 1] : nullptr;
+      C2.dsum = ctx->dG2 + (size_t)(u - 1) * G4;
+      C2.dc_prev = ctx->edc[1][u & 1];
+      C2.t = u; C2.dq_c = ctx->dq + 2 * Rq; C2.dq_h = ctx->dq + 3 * Rq;
+    }
+    if (u + 1 <= TL) {  // layer-1 cell t = u + 1
+      const int t = u + 1;
+      LstmBwdCell& C1 = cells.c[cells.n++];
+      C1.gates = ctx->G1 + (size_t)u * G4;
+      C1.c_prev = ctx->c1 + (size_t)u * BRq; C1.cp_rs = Rq;
+      C1.tanhc = ctx->tc1 + (size_t)u * BRq;
+      C1.slabA = iq1 >= 0 ? ctx->ws_chain.slab + (size_t)iq1 * nsp * BRq : nullptr;
+      C1.nA = iq1 >= 0 ? nsp : 0;
+      C1.slabB = ctx->ws_chain.slab + (size_t)iqx * nsp * BRq;   // dG2[t] W_i2h2, then the dropout mask
+      C1.nBp = nsp;
+      C1.maskB = m.rnn; C1.maskB_e0 = (size_t)u * BRq; C1.mscaleB = m.s_rnn;
+      C1.dc_next = t < TL ? ctx->edc[0][(t + 1) & 1] : nullptr;
+      C1.dsum = ctx->dG1 + (size_t)u * G4;
+      C1.dc_prev = ctx->edc[0][t & 1];
+      C1.t = t; C1.dq_c = ctx->dq; C1.dq_h = ctx->dq + Rq;
+    }
+    RUN("lstm_bwd", 0, BRq * 4.0 * 12 * cells.n, lstm_bwd_multi(st, GATES_DEEP, B, Rq, cells));
+  }
+  {  // gradient w.r.t. the word embeddings' tanh output, all tokens at once
+    const LinOpts o = lin_opts(ctx, ctx->ws_chain);
+    RUN("enc_i2h_dgrad", gflop(rows, E, 4 * Rq), 0,
+        gemm_nn(st, rows, E, 4 * Rq, ctx->dG1, 4 * Rq, ctx->i2h[0].W, E, ctx->dwe, E, o));
+  }
+  RUN("embed_bwd", 0, (double)rows * E * 12,
+      embed_bwd(st, ctx->capturing ? c.T * B : bs.held.nuniq, E, bs.utok, bs.ustart, bs.upos, ctx->dwe, ctx->we, m.we,
+                m.s_we, ctx->grp[RAU_GROUP_EMBED].g));
+  return enc_wgrads(ctx, TL, wg_bulk);
+}
+
 static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   const bool sel = loss.select_w != nullptr, att = loss.att_w != nullptr, mrg = loss.merge_w != nullptr;
   const rau_out_grads& ext = loss.ext;
   const bool sig = sel || ext.d_dopred;   // the head_dgrad addend and the selection head's weight gradient exist
   const bool has_da = att || ext.d_attprob;   // every hop's attention backward is handed its da_out
   const int HA = loss.active;
-  const HopwLayout at(ctx->cfg.H);
   if (!ctx->fwd_done) return fail(RAU_ERR_STATE, "rau_backward: call rau_forward first");
   if (ctx->fwd_table)
     return fail(RAU_ERR_STATE, "rau_backward: the evaluate-mode forward of a batch with an image table computed "
@@ -1620,83 +1870,19 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
     if (int rc = merge_state(ctx, sel ? "rau_backward_select" : "rau_backward_merged", true)) return rc;
   const Truth t = ctx->capturing ? step_truth(ctx) : ctx->mg.truth;
   const rau_config& c = ctx->cfg;
-  const int B = c.B, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R,
-            K = c.K, H = c.H, Q = ctx->Q;
-  const int TL = bs.held.max_len;
+  const int B = c.B, S = ctx->Sp, M = c.M, R = c.R, K = c.K, Q = ctx->Q;
   // Backward launch groups of the bulk stream.  Forward groups want to be large (the flattened-
   // column kernels lose a ragged last round per launch); the backward kernels do not (per-sample
   // dgrad tiles and the split-K weight gradients fill whole rounds at any hop count), and a
   // group's gradients can only start once its LAST hop's chain is done, so the backward partition
   // is its own: RAU_BWD_GROUPS="1,1,2,2,2" (sizes in HOP order, must sum to H), default = the
   // forward partition.  Evaluate mode (I shared): one group.
-  std::vector<int> bsz_store;
-  if (!ctx->I_shared && !ctx->bgroups.empty()) bsz_store = ctx->bgroups;
-  const std::vector<int>& gsz = bsz_store.empty() ? ctx->cur : bsz_store;
+  const std::vector<int>& gsz = (!ctx->I_shared && !ctx->bgroups.empty()) ? ctx->bgroups : ctx->cur;
   hipStream_t st = ctx->st;
-  const bool tr = ctx->mode == RAU_MODE_TRAIN;
-  auto mk = [&](int site) -> const uint32_t* {
-    return (tr && mask_p(ctx, site) > 0.f) ? ctx->mbits[site] : nullptr;
-  };
-  auto sc = [&](int site) { return 1.f / (1.f - mask_p(ctx, site)); };
-  const uint32_t *m_we = mk(RAU_MASK_WE), *m_rnn = mk(RAU_MASK_RNN), *m_q = mk(RAU_MASK_Q);
-  auto gflop = [](double m, double n, double k) { return 2.0 * m * n * k; };
+  const Masks m = masks_of(ctx);
   const size_t BM_ = (size_t)B * M, BS_ = (size_t)B * S, BR_ = (size_t)B * R;
-  const size_t BRq = (size_t)B * Rq;
   ctx->fwd_done = false;  // dl is scaled in place below: one backward per forward
-
-  // dpred:mul(w[h])  SS:569 / MS:568-570 / Full:587-589
-  if (!ctx->capturing) {  // (rau_graph_step uploads the weights before it launches the graph)
-    if (int rc = upload_hop_weights(ctx, loss)) return rc;
-  }
-  if (ext.d_logits || (loss.has_ext() && !ctx->fwd_dl))
-    // one pass in scale_hops' place: dl * hop_w + d_logits; without a criterion gradient dl = d_logits (or +0)
-    RUN("ext_dl", (double)H * B * K * (ctx->fwd_dl ? 2 : 0), (double)H * B * K * (ctx->fwd_dl ? 12 : 8),
-        ext_dl(st, H, (size_t)B * K, ctx->fwd_dl ? ctx->hopw_d : nullptr, ext.d_logits, ctx->dl));
-  else if (ctx->dpre_fwd && !loss.forms_dpre())   // the forward formed dpre / dhn from the unscaled dl: scale all three
-    RUN("scale_hops", 0, (double)H * B * (K + M + R) * 8,
-        scale_hops3(st, H, ctx->hopw_d, (size_t)B * K, ctx->dl, (size_t)B * M, ctx->dpre, (size_t)B * R, ctx->dhn));
-  else
-    RUN("scale_hops", 0, (double)H * B * K * 8, scale_hops(st, H, (size_t)B * K, ctx->hopw_d, ctx->dl));
-  // mrg: w_uni dCE(uni row) + w_sel dCE(select row) join the scaled dl of every hop, in front of all its consumers
-  // (head_dgrad and sel_add below, the classifier's weight gradient in mult_wgrads)
-  if (mrg)
-    RUN("merge_grad", 0, (double)H * B * K * 16,
-        merge_grad(st, H, B, K, ctx->logits, ctx->dopred, t, ctx->hopw_d + at.merge_w, 0.f, 0.f, ctx->dl));
-
-  // ---------------- RAU BPTT, SS:561-578
-  // Off the recurrence: dpre = (dl Wc) (.) mask and dhn = dpre Wo for all active hops at once.
-  // sel: the gradient through do_pred, s (x) wd, joins dl Wc in front of the mask (HopGrad::dmf_add's position).
-  // A per-row term cannot be folded into what the forward formed (one scale per hop), so both products are
-  // formed here from the scaled dl -- which is also the order the bf16 emulation rounds in.
-  const uint32_t* m_mf = mk(RAU_MASK_MF);
-  if (sel)
-    RUN("select_signal", 0, (double)HA * B * M * 4,
-        select_signal(st, HA * B, B, K, M, ctx->dopred, ctx->argmax_d, t, ctx->hopw_d + at.select_w, ctx->do_pred.W,
-                      ctx->sel_s, ctx->sel_add));
-  if (ext.d_dopred)   // s (+)= (d_dopred x)(1 - x) through the sigmoid, and the addend formed from the final s
-    RUN("ext_signal", 0, (double)HA * B * M * 4,
-        ext_signal(st, HA * B, M, ctx->dopred, ext.d_dopred, ctx->do_pred.W, sel, ctx->sel_s, ctx->sel_add));
-  // att: the gradient at the attprob output of all active hops, -(att_w[h] t / (a + eps)) / B, read by the attention
-  // backward of each hop (HopGrad::da_out).  The targets may have come after the forward: it does not read them.
-  if (att)
-    RUN("att_sup_grad", 0, (double)HA * B * S * 12,
-        att_sup_grad(st, HA, B, SL, ctx->a, S, bs.att_t_d, S, bs.held.regions ? bs.nreg_d : nullptr,
-                     ctx->hopw_d + at.att_w, 0.f, ctx->att_da, S));
-  if (ext.d_attprob)   // the dense [H,n,S] gradient (added) into the pitched addend, zeros behind the counts
-    RUN("ext_da", 0, (double)HA * B * S * (att ? 12 : 8),
-        ext_da(st, HA, B, SL, ext.d_attprob, bs.held.regions ? bs.nreg_d : nullptr, att, ctx->att_da, S));
-  if (HA > 0 && (!ctx->dpre_fwd || loss.forms_dpre())) {
-    LinOpts o = lin_opts(ctx, ctx->ws_chain);
-    if (sig) { o.addend = ctx->sel_add; o.add_rs = M; }
-    o.emask = m_mf;
-    o.emask_e0 = 0;
-    o.emscale = sc(RAU_MASK_MF);
-    RUN("head_dgrad", gflop(HA * B, M, K), 0,
-        gemm_nn(st, HA * B, M, K, ctx->dl, K, ctx->cls.W, M, ctx->dpre, M, o));
-    const LinOpts o2 = lin_opts(ctx, ctx->ws_chain);
-    RUN("head_dgrad", gflop(HA * B, R, M), 0,
-        gemm_nn(st, HA * B, R, M, ctx->dpre, M, ctx->lstm_out.W, R, ctx->dhn, R, o2));
-  }
+  if (int rc = loss_gradients(ctx, loss, t)) return rc;
   const float* dc_next = nullptr;  // grad_att_c / grad_att_h zeros, SS:561-562
   float* dh_part = nullptr;        // gradient at next_h: K-split partials left by the previous hop
   int dh_part_ns = 0;
@@ -1711,9 +1897,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
       HopGrad g{};
       g.dl = ctx->dl + (size_t)h * B * K;
       g.dc_next = dc_next;
-      g.dh_next = nullptr;
       g.dc_out = dc_out;
-      g.dh_out = nullptr;
       g.dpre_ready = 1;
       g.dhn_all = ctx->dhn;
       g.dh_part = dh_part;
@@ -1751,88 +1935,9 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
     // start on the bulk stream, overlapping the remaining hops and the encoder BPTT:
     // dZ = (Wp^T dS + dj (x) a)(1 - I^2); dWp += dS I^T; dWi += dZ X'^T.
     if (gsz[h]) {   // h is the first hop of its group: the whole group's attention backward is done
-      hipStream_t sb = ctx->st2;
-      float* slab_b = ctx->ws_bulk.slab;   // the bulk stream's split-K workspace
       if (!(seam_mask() & 2)) HIPC(hipEventRecord(ctx->evK[h], st));
-      HIPC(hipStreamWaitEvent(sb, ctx->evK[h], 0));   // recorded inside hop_backward (ev_conv_ready)
-      if (!ctx->I_shared) {
-        const int nH = (std::min(h + gsz[h], HA) - h) * B;   // active hops of this group
-        const size_t hb = (size_t)h * B;
-        // Where the per-sample tiling applies the dgrad's epilogue also applies (1 - I^2) and
-        // hands back per-sample row sums (the i_embed bias gradient): the i_embed weight gradient
-        // then stages a plain operand (one global load and no VALU work per element less).
-        const int dzf = conv_dz_fused_ok(S, M, ctx->bf16);
-        if (dzf)
-          RUNS(sb, "conv_att_dgrad", gflop(M, (double)nH * S, A),
-               ((double)nH * A * S + 3.0 * nH * M * S) * 4,
-               conv_att_dgrad_dz(sb, nH, M, S, A,
-                                 ctx->ds16_step ? (const float*)((const uint16_t*)ctx->dS16 + hb * A * S)
-                                                : ctx->T + hb * A * S,
-                                 ctx->att_i.W, ctx->dj + hb * M,
-                                 ctx->a + hb * S, ctx->I + hb * M * S,
-                                 ctx->xd16 ? (float*)((uint16_t*)ctx->dZ + hb * M * S) : ctx->dZ + hb * M * S,
-                                 ctx->dbi_part + hb * M, ctx->xd16 ? 1 : 0, ctx->bf16, ctx->ds16_step ? 1 : 0,
-                                 chain_bound(ctx) ? 1 : 0));
-        else
-          RUNS(sb, "conv_att_dgrad", gflop(M, (double)nH * S, A),
-               ((double)nH * A * S + 2.0 * nH * M * S) * 4,
-               conv_att_dgrad(sb, nH, M, S, A, ctx->T + hb * A * S, ctx->att_i.W, ctx->dj + hb * M,
-                              ctx->a + hb * S, ctx->dZ + hb * M * S, ctx->bf16));
-        {   // the att_i weight gradient (independent of dZ)
-          if (ctx->ds16_step)
-            RUNS(sb, "conv_att_wgrad", gflop(A, M, (double)nH * S),
-                 (double)nH * A * S * 2 + (double)nH * M * S * 4,
-                 conv_att_wgrad_ds16(sb, nH, M, S, A, (const uint16_t*)ctx->dS16 + hb * A * S,
-                                     ctx->I + hb * M * S, ctx->att_i.dW, slab_b));
-          else
-          RUNS(sb, "conv_att_wgrad", gflop(A, M, (double)nH * S),
-               ((double)nH * A * S + (double)nH * M * S) * 4,
-               conv_att_wgrad(sb, nH, M, S, A, ctx->T + hb * A * S, ctx->I + hb * M * S,
-                              ctx->att_i.dW, slab_b, ctx->bf16));
-        }
-        if (ctx->xd16 && dzf)
-          RUNS(sb, "conv_embed_wgrad", gflop(M, D, (double)nH * S),
-               (double)nH * M * S * 2 + (double)nH * D * S * 2,
-               conv_embed_wgrad_b16(sb, nH, D, S, M, (const uint16_t*)ctx->dZ + hb * M * S,
-                                    (const uint16_t*)ctx->xd16 + hb * D * S, ctx->i_embed.dW, slab_b));
-        else
-          RUNS(sb, "conv_embed_wgrad", gflop(M, D, (double)nH * S),
-               ((double)nH * M * S * (dzf ? 1 : 2) + (double)nH * D * S) * 4,
-               conv_embed_wgrad(sb, nH, D, S, M, ctx->dZ + hb * M * S, ctx->I + hb * M * S,
-                                  ctx->xd + hb * D * S, ctx->i_embed.dW, slab_b, ctx->bf16,
-                                  ctx->i_embed.db, dzf));
-        if (dzf && h == 0)   // last group: i_embed bias gradient = column sums of the per-sample rows
-          RUNS(sb, "colsum", 0, (double)HA * B * M * 4,
-               colsum_acc(sb, HA * B, M, ctx->dbi_part, M, ctx->i_embed.db, ctx->ws_bulk.coltmp));
-      } else if (ctx->fwd_tied) {
-        // Tied feature-map dropout (train mode, I and X' shared): the conv gradients are linear in what each hop
-        // hands back, so the hops are summed first (tied_bwd.hip) and every conv gradient runs once, at n = B.
-        // The sum of dS goes to a buffer of its own: T keeps every hop's dS, as on the per-hop paths.
-        RUNS(sb, "hop_sum", 0, (double)(HA + 1) * B * A * S * 4, hop_sum(sb, HA, B, A, SL, S, ctx->T, ctx->dS_sum));
-        RUNS(sb, "conv_att_dgrad", gflop(M, (double)B * S, A), ((double)B * A * S + 2.0 * BM_ * S) * 4,
-             conv_att_dgrad(sb, B, M, S, A, ctx->dS_sum, ctx->att_i.W, ctx->dj, ctx->a, ctx->dZ, ctx->bf16));
-        if (HA > 1)   // + dj_h (x) a_h of the other active hops (hop 0's came out of the dgrad's epilogue)
-          RUNS(sb, "outer_sum", 2.0 * (HA - 1) * BM_ * S, (2.0 * BM_ * S + (double)(HA - 1) * (BM_ + BS_)) * 4,
-               outer_sum(sb, HA, B, M, S, ctx->dj, ctx->a, ctx->dZ));
-        RUNS(sb, "conv_att_wgrad", gflop(A, M, (double)B * S), ((double)B * A * S + BM_ * S) * 4,
-             conv_att_wgrad(sb, B, M, S, A, ctx->dS_sum, ctx->I, ctx->att_i.dW, slab_b, ctx->bf16));
-        RUNS(sb, "conv_embed_wgrad", gflop(M, D, (double)B * S), (2.0 * BM_ * S + (double)B * D * S) * 4,
-             conv_embed_wgrad(sb, B, D, S, M, ctx->dZ, ctx->I, ctx->x_shared, ctx->i_embed.dW, slab_b,
-                              ctx->bf16, ctx->i_embed.db));
-      } else {
-        for (int hh2 = 0; hh2 < HA; ++hh2) {  // evaluate mode: I (and X) shared by all hops
-          float* Th2 = ctx->T + (size_t)hh2 * B * A * S;
-          float* dZh = ctx->dZ + (size_t)hh2 * BM_ * S;
-          RUNS(sb, "conv_att_dgrad", gflop(M, (double)B * S, A), ((double)B * A * S + 2.0 * BM_ * S) * 4,
-               conv_att_dgrad(sb, B, M, S, A, Th2, ctx->att_i.W, ctx->dj + (size_t)hh2 * BM_,
-                              ctx->a + (size_t)hh2 * BS_, dZh, ctx->bf16));
-          RUNS(sb, "conv_att_wgrad", gflop(A, M, (double)B * S), ((double)B * A * S + BM_ * S) * 4,
-               conv_att_wgrad(sb, B, M, S, A, Th2, ctx->I, ctx->att_i.dW, slab_b, ctx->bf16));
-          RUNS(sb, "conv_embed_wgrad", gflop(M, D, (double)B * S), (BM_ * S + (double)B * D * S) * 4,
-               conv_embed_wgrad(sb, B, D, S, M, dZh, ctx->I, ctx->xw, ctx->i_embed.dW, slab_b,
-                                ctx->bf16, ctx->i_embed.db));
-        }
-      }
+      HIPC(hipStreamWaitEvent(ctx->st2, ctx->evK[h], 0));   // recorded inside hop_backward (ev_conv_ready)
+      if (int rc = group_conv_grads(ctx, h, gsz[h], HA)) return rc;
     }
   }
   {  // dq = sum_h (dq~_h Wq) (.) mask_h     (ConcatTable backward, SS:579)
@@ -1842,14 +1947,11 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
           gemm_nn(st, dq_rows_left * B, Q, M, ctx->dqt, M, ctx->q_proj.W, Q, ctx->dQD, Q, o));
     if (dq_side) HIPC(hipStreamWaitEvent(st, ctx->evDq, 0));
     RUN("dq_reduce", 0, (double)HA * B * Q * 4,
-        dq_reduce(st, HA, (size_t)B * Q, ctx->dQD, m_q, sc(RAU_MASK_Q), ctx->dq));
+        dq_reduce(st, HA, (size_t)B * Q, ctx->dQD, m.q, m.s_q, ctx->dq));
   }
   // bulk stream tail: the join event (the i_embed bias gradient comes out of conv_embed_wgrad:
   // row sums of its staged dZ operand)
-  {
-    hipStream_t sb = ctx->st2;
-    HIPC(hipEventRecord(ctx->evD, sb));
-  }
+  HIPC(hipEventRecord(ctx->evD, ctx->st2));
   // ---------------- mult-group weight gradients, one GEMM per weight over all hops.
   // Throughput work nothing else waits for: third stream, so the encoder BPTT (the
   // long latency-bound chain) starts right after dq instead of behind ~40 launches.
@@ -1867,119 +1969,8 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   // third stream's split-K workspace would be shared).  Each group takes the stream AND the scratch of one record.
   static const int wg_env = [] { const char* e = std::getenv("RAU_WG_BULK"); return e ? std::atoi(e) : -1; }();
   const int wg_bulk = side_split(ctx) ? 0 : wg_env >= 0 ? wg_env : (chain_bound(ctx) ? 0 : 1);
-  auto mult_wgrads = [&]() -> int {
-    const StreamWs& ws = (wg_bulk & 1) ? ctx->ws_bulk : ctx->ws_side;
-    hipStream_t sw = ws.owner;
-    HIPC(hipStreamWaitEvent(sw, ctx->evW, 0));
-    const int rows = HA * B;                 // active hops only
-    if (rows == 0) {
-      HIPC(hipEventRecord(ctx->evM3, sw));
-      return 0;
-    }
-    {  // dW += dY^T X and db += column sums of dY for the nine Linears: one grouped launch
-      TnProblem pr[13];
-      const int np = mult_wgrad_problems(ctx, pr);
-      double fl = 0;
-      for (int i = 0; i < np; ++i) fl += gflop(pr[i].M, pr[i].N, rows);
-      RUNS(sw, "wgrad_gemm", fl, 0, gemm_tn_group_acc(sw, pr, np, rows, ws.slab, ws.floats, lin_mode(ctx).bf16));
-    }
-    if (sig)   // the head's own weights: dwd += sum s mf, dbd += sum s (f32 dot products in every dtype)
-      RUNS(sw, "select_wgrad", 2.0 * rows * (M + 1), (double)rows * M * 4,
-           select_wgrad(sw, rows, M, ctx->sel_s, ctx->mf, ctx->do_pred.dW, ctx->do_pred.db));
-    // att_score: dws = sum dz T ; dbs = sum dz.  att_i bias: sum dS.  i_embed bias: sum dZ.
-    RUNS(sw, "colsum", 0, (double)rows * A * 4, colsum_acc(sw, rows, A, ctx->dwsp, A, ctx->att_score.dW, ws.coltmp));
-    HIPC(hipMemsetAsync(ctx->tmpS, 0, S * sizeof(float), sw));
-    RUNS(sw, "colsum", 0, (double)rows * S * 4, colsum_acc(sw, rows, SL, ctx->dz, S, ctx->tmpS, ws.coltmp));
-    RUNS(sw, "colsum", 0, S * 4.0, colsum_acc(sw, SL, 1, ctx->tmpS, 1, ctx->att_score.db, ws.coltmp));
-    RUNS(sw, "colsum", 0, (double)rows * A * 4, colsum_acc(sw, rows, A, ctx->du, A, ctx->att_i.db, ws.coltmp));
-    HIPC(hipEventRecord(ctx->evM3, sw));   // with evD: the mult group's gradients are final
-    return 0;
-  };
-  if (int rc = mult_wgrads()) return rc;
-
-  // ---------------- encoder BPTT, SS:581-596 -- the same two-layer wavefront, reversed:
-  // step u handles layer-2 cell u and layer-1 cell u+1; their incoming dh are the
-  // K-split partials of the previous step's dG (dG2 W_h2h2, dG2 W_i2h2 through the
-  // inter-layer dropout, dG1 W_h2h1), one batched GEMM, summed inside the cell kernel.
-  if (TL > 0) {
-    const int rows = TL * B;
-    const size_t G4 = (size_t)B * 4 * Rq;
-    // Encoder weight gradients, also on the weight-gradient stream: one launch behind the BPTT.  (Two
-    // time chunks -- the gradients of tokens t > uc are final once wavefront step uc is done -- were
-    // tried: running the first chunk under the second half of the BPTT slows that chain by more than
-    // the shorter tail saves, measured 11.05 vs 10.6 ms.)
-    auto enc_wgrads = [&](int t_lo, int t_hi, hipEvent_t ev) -> int {   // tokens t_lo < t <= t_hi
-      if (t_hi <= t_lo) return 0;
-      const StreamWs& ws = (wg_bulk & 2) ? ctx->ws_bulk : ctx->ws_side;
-      hipStream_t sw = ws.owner;
-      HIPC(hipEventRecord(ev, st));
-      HIPC(hipStreamWaitEvent(sw, ev, 0));
-      const size_t r0 = (size_t)t_lo * B;
-      const int nr = (t_hi - t_lo) * B;
-      TnProblem pr[13];
-      const int np = enc_wgrad_problems(ctx, r0, pr);
-      double fl = 0;
-      for (int i = 0; i < np; ++i) fl += gflop(pr[i].M, pr[i].N, nr);
-      RUNS(sw, "wgrad_gemm", fl, 0, gemm_tn_group_acc(sw, pr, np, nr, ws.slab, ws.floats, lin_mode(ctx).bf16));
-      return 0;
-    };
-    const int hi = TL;
-    for (int u = TL; u >= 0; --u) {
-      const float* Ap[3];
-      const float* Wp[3];
-      int nb = 0, iq2 = -1, iqx = -1, iq1 = -1;
-      if (u >= 1 && u + 1 <= TL) { Ap[nb] = ctx->dG2 + (size_t)u * G4; Wp[nb] = ctx->h2h[1].W; iq2 = nb++; }
-      if (u + 1 <= TL) { Ap[nb] = ctx->dG2 + (size_t)u * G4; Wp[nb] = ctx->i2h[1].W; iqx = nb++; }
-      if (u + 2 <= TL) { Ap[nb] = ctx->dG1 + (size_t)(u + 1) * G4; Wp[nb] = ctx->h2h[0].W; iq1 = nb++; }
-      int nsp = 0;
-      if (nb > 0)
-        RUN("enc_h2h_dgrad", gflop(B, Rq, 4 * Rq) * nb, 0,
-            gemm_nn_batched_deferred(st, lin_mode(ctx), nb, B, Rq, 4 * Rq, Ap, 4 * Rq, Wp, Rq, ctx->ws_chain.slab,
-                                     ctx->ws_chain.floats, &nsp));
-      LstmBwdCells cells{};
-      cells.lens = bs.lens_d;
-      cells.dq_rs = Q;
-      if (u >= 1) {  // layer-2 cell t = u
-        LstmBwdCell& C2 = cells.c[cells.n++];
-        C2.gates = ctx->G2 + (size_t)(u - 1) * G4;
-        C2.c_prev = ctx->c2 + (size_t)(u - 1) * BRq; C2.cp_rs = Rq;
-        C2.tanhc = ctx->tc2 + (size_t)(u - 1) * BRq;
-        C2.slabA = iq2 >= 0 ? ctx->ws_chain.slab + (size_t)iq2 * nsp * BRq : nullptr;
-        C2.nA = iq2 >= 0 ? nsp : 0;
-        C2.slabB = nullptr; C2.nBp = 0; C2.maskB = nullptr; C2.maskB_e0 = 0; C2.mscaleB = 1.f;
-        C2.dc_next = u < TL ? ctx->edc[1][(u + 1) & 1] : nullptr;
-        C2.dsum = ctx->dG2 + (size_t)(u - 1) * G4;
-        C2.dc_prev = ctx->edc[1][u & 1];
-        C2.t = u; C2.dq_c = ctx->dq + 2 * Rq; C2.dq_h = ctx->dq + 3 * Rq;
-      }
-      if (u + 1 <= TL) {  // layer-1 cell t = u + 1
-        const int t = u + 1;
-        LstmBwdCell& C1 = cells.c[cells.n++];
-        C1.gates = ctx->G1 + (size_t)u * G4;
-        C1.c_prev = ctx->c1 + (size_t)u * BRq; C1.cp_rs = Rq;
-        C1.tanhc = ctx->tc1 + (size_t)u * BRq;
-        C1.slabA = iq1 >= 0 ? ctx->ws_chain.slab + (size_t)iq1 * nsp * BRq : nullptr;
-        C1.nA = iq1 >= 0 ? nsp : 0;
-        C1.slabB = ctx->ws_chain.slab + (size_t)iqx * nsp * BRq;   // dG2[t] W_i2h2, then the dropout mask
-        C1.nBp = nsp;
-        C1.maskB = m_rnn; C1.maskB_e0 = (size_t)u * BRq; C1.mscaleB = sc(RAU_MASK_RNN);
-        C1.dc_next = t < TL ? ctx->edc[0][(t + 1) & 1] : nullptr;
-        C1.dsum = ctx->dG1 + (size_t)u * G4;
-        C1.dc_prev = ctx->edc[0][t & 1];
-        C1.t = t; C1.dq_c = ctx->dq; C1.dq_h = ctx->dq + Rq;
-      }
-      RUN("lstm_bwd", 0, BRq * 4.0 * 12 * cells.n, lstm_bwd_multi(st, GATES_DEEP, B, Rq, cells));
-    }
-    {  // gradient w.r.t. the word embeddings' tanh output, all tokens at once
-      const LinOpts o = lin_opts(ctx, ctx->ws_chain);
-      RUN("enc_i2h_dgrad", gflop(rows, E, 4 * Rq), 0,
-          gemm_nn(st, rows, E, 4 * Rq, ctx->dG1, 4 * Rq, ctx->i2h[0].W, E, ctx->dwe, E, o));
-    }
-    RUN("embed_bwd", 0, (double)rows * E * 12,
-        embed_bwd(st, ctx->capturing ? c.T * B : bs.held.nuniq, E, bs.utok, bs.ustart, bs.upos, ctx->dwe, ctx->we, m_we,
-                  sc(RAU_MASK_WE), ctx->grp[RAU_GROUP_EMBED].g));
-    if (int rc = enc_wgrads(0, hi, ctx->evE)) return rc;
-  }
+  if (int rc = mult_wgrads(ctx, HA, sig, wg_bulk)) return rc;
+  if (int rc = encoder_backward(ctx, m, wg_bulk)) return rc;
   HIPC(hipEventRecord(ctx->evW3, ctx->st3));
   HIPC(hipStreamWaitEvent(st, ctx->evW3, 0));
   if (wg_bulk) HIPC(hipEventRecord(ctx->evD, ctx->st2));   // the bulk stream got weight-gradient work behind its convs

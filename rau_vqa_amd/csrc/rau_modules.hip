@@ -58,20 +58,6 @@ int copy2d(rau_ctx* ctx, float* dst, size_t dst_rs, const float* src, size_t src
   return 0;
 }
 
-struct Masks {
-  const uint32_t *we, *rnn, *q, *x, *mf;
-  float s_we, s_rnn, s_q, s_x, s_mf;
-};
-Masks masks_of(rau_ctx* ctx) {
-  const bool tr = ctx->mode == RAU_MODE_TRAIN;
-  auto mk = [&](int site) -> const uint32_t* {
-    return (tr && mask_p(ctx, site) > 0.f) ? ctx->mbits[site] : nullptr;
-  };
-  auto sc = [&](int site) { return 1.f / (1.f - mask_p(ctx, site)); };
-  return Masks{mk(RAU_MASK_WE), mk(RAU_MASK_RNN), mk(RAU_MASK_Q), mk(RAU_MASK_X), mk(RAU_MASK_MF),
-               sc(RAU_MASK_WE), sc(RAU_MASK_RNN), sc(RAU_MASK_Q), sc(RAU_MASK_X), sc(RAU_MASK_MF)};
-}
-
 // dW += dY^T X and db += column sums of dY for one Linear, rows = one clone's batch
 int lin_wgrad(rau_ctx* ctx, Lin& l, const float* dY, const float* X, long ldx, bool bias = true,
               long ldy = 0) {
@@ -178,7 +164,6 @@ int rau_deeplstm_forward(rau_ctx* ctx, int t, const float* x, const float* state
   float* G1 = ctx->G1 + (size_t)t * G4;
   float* G2 = ctx->G2 + (size_t)t * G4;
   float* x2 = ctx->x2 + (size_t)t * BRq;
-  auto gflop = [](double mm, double n, double k) { return 2.0 * mm * n * k; };
   {  // layer 1: i2h(x) + h2h(prev_h), DeepLSTM.lua:42-44
     LinOpts o = lin_opts(ctx, ctx->ws_chain);
     o.bias = ctx->i2h[0].b;
@@ -227,7 +212,6 @@ int rau_deeplstm_backward(rau_ctx* ctx, int t, const float* x, const float* stat
   float* dG2 = ctx->dG2 + (size_t)t * G4;
   float* dxo = ctx->dwe + (size_t)t * B * E;
   float *dc_in = ctx->m_tmp[0], *dc_prev = ctx->m_tmp[1], *dx2 = ctx->m_tmp[2];
-  auto gflop = [](double mm, double n, double k) { return 2.0 * mm * n * k; };
   // ---- layer 2
   if (int rc = copy2d(ctx, dc_in, Rq, d_state_out + 2 * Rq, Q, Rq)) return rc;
   RUN("lstm_bwd", 0, BRq * 48.0,
@@ -299,7 +283,6 @@ int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const fl
   const int B = c.B, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R, K = c.K, Q = ctx->Q;
   hipStream_t st = ctx->st;
   const Masks m = masks_of(ctx);
-  auto gflop = [](double mm, double n, double k) { return 2.0 * mm * n * k; };
   const size_t BM_ = (size_t)B * M, BR_ = (size_t)B * R;
   ctx->I_shared = false;
   ctx->fwd_done = false;   // the step-level slots are being overwritten
@@ -333,10 +316,7 @@ int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const fl
   RUN("transpose", 0, (double)A * M * 8, transpose2d(st, A, M, ctx->att_i.W, ctx->WpT));
   float* Ih = ctx->I + (size_t)h * BM_ * S;
   float* Th = ctx->T + (size_t)h * B * A * S;
-  RUN("conv_embed_fwd", gflop(M, (double)B * S, D), ((double)B * D * S + BM_ * S) * 4,
-      conv_embed_fwd(st, B, D, S, M, xin, ctx->WiT, ctx->i_embed.b, Ih, ctx->bf16));
-  RUN("conv_att_pre", gflop(A, (double)B * S, M), (BM_ * S + (double)B * A * S) * 4,
-      conv_att_pre(st, B, M, S, A, Ih, ctx->WpT, ctx->att_i.b, Th, ctx->bf16));
+  if (int rc = image_forward(ctx, st, B, xin, false, Ih, Th)) return rc;
   float* co = ctx->cc + (size_t)(h + 1) * BR_;
   float* ho = ctx->hh + (size_t)(h + 1) * BR_;
   if (int rc = hop_forward(ctx, h, c_prev, h_prev, co, ho, Ih, Th, Truth{}, regions_dev)) return rc;
@@ -377,7 +357,6 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
   const int B = c.B, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R, Q = ctx->Q;
   hipStream_t st = ctx->st;
   const Masks m = masks_of(ctx);
-  auto gflop = [](double mm, double n, double k) { return 2.0 * mm * n * k; };
   const size_t BM_ = (size_t)B * M, BS_ = (size_t)B * S, BR_ = (size_t)B * R;
   if (S != SL) {
     if (!resident) {   // the forward of this clone re-pitched the same X
@@ -419,14 +398,10 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
   }
   // ---- 1x1-conv gradients of this clone: dI = Wp^T dS + dj (x) a; dWp += dS I^T;
   // dWi += (dI (1-I^2)) X'^T; bias gradients
-  RUN("conv_att_dgrad", gflop(M, (double)B * S, A), ((double)B * A * S + 2.0 * BM_ * S) * 4,
-      conv_att_dgrad(st, B, M, S, A, Th, ctx->att_i.W, ctx->dj + (size_t)h * BM_,
-                     ctx->a + (size_t)h * BS_, dZh, ctx->bf16));
-  RUN("conv_att_wgrad", gflop(A, M, (double)B * S), ((double)B * A * S + BM_ * S) * 4,
-      conv_att_wgrad(st, B, M, S, A, Th, Ih, ctx->att_i.dW, ctx->ws_bulk.slab, ctx->bf16));
-  RUN("conv_embed_wgrad", gflop(M, D, (double)B * S), (BM_ * S + (double)B * D * S) * 4,
-      conv_embed_wgrad(st, B, D, S, M, dZh, Ih, xin, ctx->i_embed.dW, ctx->ws_bulk.slab, ctx->bf16,
-                       ctx->i_embed.db));
+  ConvGrads cg{};
+  cg.n = B; cg.dS = Th; cg.dj = ctx->dj + (size_t)h * BM_; cg.a = ctx->a + (size_t)h * BS_; cg.I = Ih;
+  cg.X = xin; cg.dZ = dZh;
+  if (int rc = conv_grads(ctx, st, cg)) return rc;
   // ---- gradient w.r.t. q through q_embed's dropout
   float* dqo = ctx->m_dq + (size_t)h * B * Q;
   {
