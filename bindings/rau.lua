@@ -110,6 +110,11 @@ typedef struct rau_out_grads {
   const float* d_dopred;
   const float* d_attprob;
 } rau_out_grads;
+int rau_set_feat_grad(rau_ctx* ctx, int on);
+int rau_feat_grad(rau_ctx* ctx, int* on);
+int rau_feat_grad_dev(rau_ctx* ctx, const float** dX, int32_t* pitch);
+int rau_get_feat_grad(rau_ctx* ctx, float* host);
+int rau_set_batch_dev(rau_ctx* ctx, const float* feats_dev, const int32_t* tokens, const int32_t* lens, const int32_t* labels);
 int rau_outputs_dev(rau_ctx* ctx, const float** logits, const float** dopred, const float** attprob,
                     int32_t* att_pitch);
 int rau_backward_ext(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
@@ -563,6 +568,27 @@ function RAU:outputsDev()
   local pitch = ffi.new('int32_t[1]')
   check(C.rau_outputs_dev(self.h, lg, dp, at, pitch))
   return lg[0], dp[0], at[0], pitch[0]
+end
+
+-- Feature-map gradient (rau_set_feat_grad): with the switch on every backward / graphStep also leaves the gradient
+-- at the feature map behind, for a trainable stage in front of the library.  Batches with one map per sample only:
+-- the backward of an image-table or bank batch then errors (expand shared images in front of setBatchDev).
+function RAU:wantFeatureGrad(on)
+  check(C.rau_set_feat_grad(self.h, (on == nil or on) and 1 or 0))
+  return self
+end
+-- the last backward's result in device memory: const float* cdata [n,D,pitch] and the pitch (rau_feat_grad_dev);
+-- valid until the next forward, ordered on the ctx's stream
+function RAU:featureGrad()
+  local p, pitch = ffi.new('const float*[1]'), ffi.new('int32_t[1]')
+  check(C.rau_feat_grad_dev(self.h, p, pitch))
+  return p[0], pitch[0]
+end
+-- setBatch with the maps already on the device: feats_dev a DEVICE float* to dense [n,D,S] float32, ordered by the
+-- caller in front of the ctx's stream (rau_set_batch_dev); x, x_len, y host tensors as in setBatch
+function RAU:setBatchDev(feats_dev, x, x_len, y)
+  follow_rows(self, x_len)
+  check(C.rau_set_batch_dev(self.h, feats_dev, x:data(), x_len:data(), y and y:data() or nil))
 end
 
 -- backward with the gradients of a term of the caller's own at those outputs (rau_backward_ext): grads = { logits =,

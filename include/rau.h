@@ -703,6 +703,56 @@ int rau_outputs_dev(rau_ctx* ctx, const float** logits /* [H,n,K] */, const floa
 int rau_backward_ext(rau_ctx* ctx, const float* hop_w /* [H] host, NULL = zeros */, const float* select_w,
                      const float* att_w, const float* merge_w, const rau_out_grads* g /* NULL = none */);
 
+/* ---- feature-map gradient: the step-level backward as the head of a model whose image side is trained ----------
+ * The reference forms the gradient at the feature map and throws it away (SS:579), and so does the step path by
+ * default.  rau_set_feat_grad(ctx, 1) makes every step-level backward (rau_backward, _select, _att, _merged, _ext
+ * and every rau_graph_step*) also leave
+ *   dX[b,d,s] = sum_{h < HA} keep_h[b,d,s] * s_x * ( sum_m Wi[m,d] * dZ_h[b,m,s] )        (all float32)
+ * behind: dZ_h the gradient at i_embed's pre-activation of hop h (what the two conv weight gradients read), keep_h
+ * hop h's feature-map dropout bit (site RAU_MASK_X, caller-supplied or the seeded stream's: the bits the forward
+ * used), s_x = 1/(1-p_x), HA the active hops.  Tied dropout: the one mask behind the product of the summed dZ.
+ * Evaluate mode: no mask, scale 1.  Behind a sample's region count dZ is exactly 0 and so is dX.  Pitched maps
+ * (S % 4 != 0): the mask is indexed over the logical [.., S] tensor, the result's pad columns are zeros.  RAU_BF16:
+ * the product rounds both operands to bf16 and accumulates in f32, like every GEMM of that mode; mask and scale are
+ * applied in f32 behind it.  For 16-bit and fp8 batches the gradient is with respect to the widened f32 values.
+ *   the switch   off by default; between steps, in either mode.  While a step is being captured: RAU_ERR_STATE.
+ *                Off, every entry point computes and launches exactly what it did without this call; on, the
+ *                parameter gradients keep their bits.  The switch joins rau_graph_step's key.  The result buffer
+ *                [capacity, D, pitch] (and one hop's worth of scratch) is allocated at the first call with on != 0 and
+ *                survives rau_set_batch_size.
+ *   order        no float atomics: repeated calls give the same bits, a captured step the eager step's.  The hops
+ *                are added in f32 in a fixed order that depends on the backward's launch-group partition (groups in
+ *                the backward's order, last group first, the hops of a group ascending).
+ *   the result   is OVERWRITTEN by each backward, never accumulated (feature maps change with every batch);
+ *                rau_zero_grads does not touch it.
+ *   batches      one map per sample: plain, typed and packed batches, and rau_set_batch_dev below.  With the switch
+ *                on, the backward of an image-table or bank batch is RAU_ERR_STATE with nothing launched and no
+ *                gradient changed: a shared map's gradient is a sum over its questions, which the library does not
+ *                form.  A caller that shares images expands them on its side (x[image_of]) in front of
+ *                rau_set_batch_dev and sums the rows of the result per image (torch: autograd does).
+ *   the key      where the forward drew the feature-map bits inside its dropout pass they exist nowhere, and the
+ *                backward regenerates them from (seed, step): with the switch on, a rau_set_dropout_seed with another
+ *                key between a forward and its backward makes that backward RAU_ERR_STATE, nothing launched (run the
+ *                forward again).  A captured step holds both passes and reads the key from device memory.
+ *   ext          rau_backward_ext's rule stays: no gradient enters at the question state.
+ * rau_feat_grad_dev: the ctx-owned DEVICE pointer to the last backward's result [n, D, *pitch] (n the current batch
+ * size, *pitch = S rounded up to a multiple of 4), ordered on the ctx's stream; synchronises nothing; valid until
+ * the next forward or rau_set_batch_size.  RAU_ERR_STATE when the switch is off or no backward has run since the
+ * last forward.  rau_get_feat_grad: the download, dense [n,D,S]; synchronises.
+ * rau_set_batch_dev: rau_set_batch with the maps [n,D,S] float32, dense, already in DEVICE memory: one copy on the
+ * ctx's stream (re-pitching where S % 4 != 0) into the resident buffer, in the layout an f32 batch has there; the
+ * rest is rau_set_batch_typed(NULL, RAU_FEAT_F32, ..).  tokens / lens / labels are HOST arrays, copied into pinned
+ * staging of the ctx before the call returns; the call waits for no device work (only, from the third call on, for
+ * the index copy of the call two before it).  The caller orders the producer of feats_dev in front of the ctx's
+ * stream (an event of its stream, waited on by rau_stream) and keeps feats_dev unchanged until the copy has run.
+ * Answer sets, region counts and attention targets attach afterwards, as to any batch. */
+int rau_set_feat_grad(rau_ctx* ctx, int on);
+int rau_feat_grad(rau_ctx* ctx, int* on);
+int rau_feat_grad_dev(rau_ctx* ctx, const float** dX, int32_t* pitch);
+int rau_get_feat_grad(rau_ctx* ctx, float* host /* [n,D,S] dense */);
+int rau_set_batch_dev(rau_ctx* ctx, const float* feats_dev /* [n,D,S] f32, dense, DEVICE */, const int32_t* tokens,
+                      const int32_t* lens, const int32_t* labels);
+
 /* ---- module-level entry points: one call per nn.Module :forward / :backward -----
  * For hosts that keep feval's own loops (SS:443-596) and call the clones one by one.
  * t in [0,T) / h in [0,H) select the clone (the reference's embed_clones[t+1],

@@ -162,6 +162,12 @@ _SIGS = {
                                   C.POINTER(C.c_int32)]),
     "rau_backward_ext": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(RauOutGrads)]),
+    # feature-map gradient of the step-level backward; a batch whose maps are already on the device
+    "rau_set_feat_grad": (C.c_int, [C.c_void_p, C.c_int]),
+    "rau_feat_grad": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rau_feat_grad_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
+    "rau_get_feat_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rau_set_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # module-level entry points: device pointers in, pointers to ctx-owned slots out
     "rau_embed_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_embed_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

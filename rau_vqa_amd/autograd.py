@@ -6,6 +6,19 @@ step-level backward (``RAU.backward(..., out_grads=...)``, rau_backward_ext), wh
 gradients in the ctx's flat buffers -- ``rau.zero_grads()`` before, ``rau.update()`` after, as on every other path.
 The built-in terms (hop_w, select_w, att_w, merge_w) are given to ``step`` and join the same backward.
 
+``step(rau, ..., feats=x)`` also carries the gradient to the FEATURE MAP, for a torch module in front of the library
+(a CNN stage, a projection, an adapter).  x is the CUDA float tensor [n,D,S] the batch was made of::
+
+    rau.want_feature_grad()
+    x = proj(regions)                                        # any torch graph, on torch's current stream
+    own = torch.cuda.ExternalStream(rau.stream())
+    own.wait_stream(torch.cuda.current_stream())             # the ctx's copy of x runs behind its producer
+    rau.set_batch_dev(x, tokens, lens, labels)
+    logits, dopred, attprob = autograd.step(rau, hop_w, feats=x)
+    (my_loss(logits) + ...).backward()                       # x.grad flows on into proj's parameters
+
+The backward then returns a clone of ``rau.feature_grad_tensor()`` for x, ordered with events as the outputs are.
+
 torch is plumbing here: the forward, the backward and the update are librau's kernels; torch evaluates the
 caller's loss and its gradient at the three outputs, on its own current stream.  The two streams are joined with
 events only (ExternalStream + wait_stream), never with a host synchronisation.
@@ -26,6 +39,7 @@ class _Step(torch.autograd.Function):
         # clones: autograd owns what it hands out, the views die with the next forward
         outs = tuple(t.clone() for t in rau.output_tensors())
         ctx.rau, ctx.weights, ctx.dev = rau, (hop_w, select_w, att_w, merge_w), dev
+        ctx.has_feats = anchor.dim() == 3       # step(feats=x): x is the recorded input, not the scalar anchor
         ctx.set_materialize_grads(False)        # an unused output's gradient stays None instead of a zero tensor
         return outs
 
@@ -41,15 +55,31 @@ class _Step(torch.autograd.Function):
             g.record_stream(own)               # the caching allocator must not hand them out before the ctx has read them
         hop_w, select_w, att_w, merge_w = ctx.weights
         rau.backward(hop_w, select_w, att_w, merge_w, out_grads=grads)
-        return (None,) * 6                      # parameter gradients live in the ctx's flat buffers
+        gx = None
+        if ctx.has_feats:                       # the gradient at the feature map, for the graph in front of it
+            torch.cuda.current_stream(ctx.dev).wait_stream(own)
+            gx = rau.feature_grad_tensor().clone()
+            own.wait_stream(torch.cuda.current_stream(ctx.dev))   # the next step overwrites the buffer: behind the clone
+        return (gx,) + (None,) * 5              # parameter gradients live in the ctx's flat buffers
 
 
-def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None):
+def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, feats=None):
     """forward of the resident batch -> (logits, dopred, attprob), differentiable at those three outputs.
 
     hop_w, select_w, att_w, merge_w: the built-in terms of RAU.backward, added to whatever loss the caller builds
     (hop_w None = zeros: an external-only objective, which needs no labels on the batch).  One ``backward()`` per
-    ``step``; an output that does not enter the loss costs nothing."""
+    ``step``; an output that does not enter the loss costs nothing.
+
+    feats: the CUDA float tensor [n,D,S] the resident batch was made of (RAU.set_batch_dev), with the context's
+    feature-map gradient on (RAU.want_feature_grad): it becomes the recorded input and receives its gradient."""
+    if feats is not None:
+        c = rau.cfg
+        if not (isinstance(feats, torch.Tensor) and feats.is_cuda and tuple(feats.shape) == (rau.batch_size, c.D, c.S)):
+            raise ValueError(f"feats must be the CUDA tensor [n,D,S] = {(rau.batch_size, c.D, c.S)} given to set_batch_dev")
+        if not rau.feature_grad_wanted:
+            raise ValueError("step(feats=...) needs the feature-map gradient: call rau.want_feature_grad() first")
+        if feats.requires_grad:   # (a tensor nobody differentiates is a plain batch: the anchor below)
+            return _Step.apply(feats, rau, hop_w, select_w, att_w, merge_w)
     # a leaf that requires grad makes autograd record the node: the real leaves are the ctx's parameters
     anchor = torch.zeros((), device=torch.device("cuda", rau.cfg.device_id), requires_grad=True)
     return _Step.apply(anchor, rau, hop_w, select_w, att_w, merge_w)

@@ -178,6 +178,25 @@ hipError_t conv_embed_dgrad(hipStream_t st, int nB, int D, int S, int M, const f
   return launch_gemm<128, 128, BK, SRC_RC, SRC_RC_FLAT, EPI_CONV>(st, P, 1);
 }
 
+// The step path's feature-map gradient (xgrad.hip) takes the product in the context's dtype: exact f32 as above,
+// or with both operands rounded to bf16 while staged -- Wi from its f32 storage (no second copy of the weight),
+// dZ from f32 or from the 16-bit storage conv_att_dgrad_dz left it in.
+hipError_t conv_embed_dgrad_mode(hipStream_t st, int nB, int D, int S, int M, const void* dZ, int dz16,
+                                 const float* Wi, float* dX, int bf16) {
+  if (!bf16) return dz16 ? hipErrorInvalidValue : conv_embed_dgrad(st, nB, D, S, M, (const float*)dZ, Wi, dX);
+  GemmParams P{};
+  P.M = D; P.N = nB * S; P.K = M; P.nk = (M + BK - 1) / BK;
+  P.A = Wi; P.a_rs = D;
+  P.B = reinterpret_cast<const float*>(dZ); P.b_rs = S; P.b_bs = (long)M * S;   // dz16: in bf16 elements
+  P.S = S;
+  P.C = dX; P.c_bs = (long)D * S;
+  P.bias = nullptr;
+  P.act = 0;
+  if (bf16 == 2) return dz16 ? hipErrorInvalidValue : launch_gemm<128, 128, BK, SRC_RC, SRC_RC_FLAT, EPI_CONV, 2>(st, P, 1);
+  if (dz16) return launch_gemm<128, 128, BK, SRC_RC, SRC_RC_FLAT_B16, EPI_CONV, 1>(st, P, 1);
+  return launch_gemm<128, 128, BK, SRC_RC, SRC_RC_FLAT, EPI_CONV, 1>(st, P, 1);
+}
+
 static int conv_wgrad_splits(int nB, int rowsA, int rowsB) {
   const int tiles = ((rowsA + 127) / 128) * ((rowsB + 127) / 128);
   constexpr int target = 512;   // = one resident wave of workgroups (2 per CU x 256 CUs)

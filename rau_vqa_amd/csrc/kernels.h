@@ -160,6 +160,30 @@ hipError_t conv_att_wgrad_ds16(hipStream_t st, int nB, int M, int S, int A, cons
 // dX'[b,d,s] = sum_m Wi[m,d] dZ[b,m,s]   (dead in feval, SS:579; module-level API only)
 hipError_t conv_embed_dgrad(hipStream_t st, int nB, int D, int S, int M, const float* dZ,
                             const float* Wi, float* dX);
+// The same product in the context's dtype, for the step path's feature-map gradient: bf16 != 0 rounds both
+// operands while they are staged (Wi from its f32 storage, dZ from f32 or, dz16, from its bf16 storage)
+hipError_t conv_embed_dgrad_mode(hipStream_t st, int nB, int D, int S, int M, const void* dZ, int dz16,
+                                 const float* Wi, float* dX, int bf16);
+// ---- feature-map gradient of the step path (xgrad.hip)
+// Where hop h's keep bits of site RAU_MASK_X come from.  kind 0: no mask (scale 1); 1: `bits`, indexed over the
+// logical [.., SL] tensor from element e0; 2: regenerated with philox_keep16 from (seed, site, step) -- read from
+// `key` (device: seed, step) when it is set -- for the elements from e0 on (logical == physical layout).
+struct XMask {
+  int kind;
+  const uint32_t* bits;
+  size_t e0, hop_stride;   // first element of the first hop; elements per hop
+  uint64_t seed; uint32_t site, step, thr; const uint64_t* key;
+  float scale;
+};
+// dX[r][s] = (store ? 0 : dX[r][s]) + keep[r][s] * scale * G[r][s] for rows r < rows of pitch Sp (Sp % 4 == 0), pad
+// columns s >= SL written as zeros; one hop (the mask's first)
+hipError_t xgrad_accum(hipStream_t st, size_t rows, int SL, int Sp, const float* G, float* dX, const XMask& m,
+                       int store);
+// Exact f32, 14 x 14 class (xgrad_fused_ok): dX[b] (store ? = : +=) sum_{h < nh} keep_h * scale * Wi^T dZ_h[b] with
+// the hop loop inside the workgroup.  dZ [nh][nB][M][S] f32, Wi [M][D].
+bool xgrad_fused_ok(int D, int M, int S);
+hipError_t xgrad_fused(hipStream_t st, int nh, int nB, int D, int M, int S, const float* dZ, const float* Wi,
+                       float* dX, const XMask& m, int store);
 // dWp[k,m] += sum_{b,s} dS[b,k,s] I[b,m,s]   and, with dZ = dI (1 - I^2),
 // dWi[m,d] += sum_{b,s} dZ[b,m,s] X'[b,d,s]
 size_t conv_wgrad_slab_floats(int nB, int rowsA, int rowsB, int S);

@@ -555,6 +555,59 @@ int rau_set_batch_images(rau_ctx* ctx, const void* feats, int feat_type, int n_i
   return set_batch_sync(ctx, Batch{feats, feat_type, n_images, image_of, tokens, lens, labels, nullptr});
 }
 
+// rau_set_batch with the maps already in device memory (a producer in front of the library: rau_set_feat_grad).
+// One device-to-device copy on the chain stream, re-pitching where S % 4 != 0; the index arrays go through pinned
+// staging of the ctx (two halves, alternated like the hop weights'), so nothing here waits for the device.
+int rau_set_batch_dev(rau_ctx* ctx, const float* feats_dev, const int32_t* tokens, const int32_t* lens,
+                      const int32_t* labels) {
+  NEED(ctx && feats_dev && tokens && lens, "null argument");
+  if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_batch_dev: a step is being captured");
+  const rau_config& c = ctx->cfg;
+  const size_t TBc = (size_t)c.T * ctx->cap, TB = (size_t)c.T * c.B, Bc = (size_t)ctx->cap;
+  const size_t words = TBc + 2 * Bc + TBc + (TBc + 1) + TBc;   // tokens | lens | labels | utok | ustart | upos
+  const int sl = (ctx->bdev_slot ^= 1);
+  if (!ctx->bdev_h[sl]) {
+    void* h = nullptr;
+    hipError_t e = hipHostMalloc(&h, words * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(batch index staging): %s", hipGetErrorString(e));
+    ctx->bdev_h[sl] = static_cast<int32_t*>(h);
+    HIPC(hipEventCreateWithFlags(&ctx->bdev_ev[sl], hipEventDisableTiming));
+  } else {
+    HIPC(hipEventSynchronize(ctx->bdev_ev[sl]));   // the copies out of this half, two calls ago
+  }
+  int32_t* tok_h = ctx->bdev_h[sl];
+  int32_t* lens_h = tok_h + TBc;
+  int32_t* lab_h = lens_h + Bc;
+  int32_t* utok_h = lab_h + Bc;
+  int32_t* ustart_h = utok_h + TBc;
+  int32_t* upos_h = ustart_h + TBc + 1;
+  std::memcpy(tok_h, tokens, TB * 4);
+  std::memcpy(lens_h, lens, (size_t)c.B * 4);
+  if (labels) std::memcpy(lab_h, labels, (size_t)c.B * 4);
+  Batch b{nullptr, RAU_FEAT_F32, 0, nullptr, tok_h, lens_h, labels ? lab_h : nullptr, nullptr};
+  if (int rc = index_batch(c, b.tokens, b.lens, b.labels, utok_h, ustart_h, upos_h, &b.max_len, &b.nuniq)) return rc;
+  b.utok = utok_h; b.ustart = ustart_h; b.upos = upos_h;
+  const int si = ctx->cur_slot;
+  BatchSlot& s = ctx->slot[si];
+  hipStream_t st = ctx->st;
+  if (s.upload_pending) HIPC(hipStreamWaitEvent(st, s.uploaded, 0));   // an async upload into the same buffers
+  if (ctx->Sp == c.S) {
+    HIPC(hipMemcpyAsync(s.feats, feats_dev, (size_t)c.B * c.D * c.S * 4, hipMemcpyDeviceToDevice, st));
+  } else {
+    // rows of S floats into rows of Sp; another element type's rows leave data in the pad columns: cleared first
+    if (s.held.feat_type != RAU_FEAT_F32)
+      HIPC(hipMemsetAsync(s.feats, 0, (size_t)c.B * c.D * ctx->Sp * sizeof(float), st));
+    HIPC(hipMemcpy2DAsync(s.feats, (size_t)ctx->Sp * 4, feats_dev, (size_t)c.S * 4, (size_t)c.S * 4,
+                          (size_t)c.B * c.D, hipMemcpyDeviceToDevice, st));
+  }
+  if (int rc = enqueue_batch(ctx, st, si, b)) return rc;   // (feats == NULL: the index arrays only)
+  HIPC(hipEventRecord(ctx->bdev_ev[sl], st));
+  s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
+  hold(ctx, si, b);
+  ctx->fwd_done = false;
+  return RAU_OK;
+}
+
 int rau_set_batch_bank(rau_ctx* ctx, int n_images, const int32_t* bank_rows, const int32_t* image_of,
                        const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
   NEED(ctx && tokens && lens, "null argument");

@@ -236,9 +236,11 @@ struct StepKey {
   // ... and under RAU_XDROP_TIED a train-mode step has one masked map, one conv group and the summed conv gradients
   bool tied_x = false;
   int ans_loss = 0;             // ... and the head kernel is the answer criterion's (rau_set_answer_loss)
+  bool feat_grad = false;       // ... and with rau_set_feat_grad the conv gradients are followed by the feature-map gradient
   auto tied() const {
     return std::tie(mode, max_len, active, zero, mexplicit[0], mexplicit[1], mexplicit[2], mexplicit[3], mexplicit[4],
-                    slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg, tied_x, ans_loss);
+                    slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg, tied_x, ans_loss,
+                    feat_grad);
   }
   bool operator==(const StepKey& o) const { return tied() == o.tied(); }
 };
@@ -336,6 +338,21 @@ struct rau_ctx {
   bool fwd_tied = false;            // the last forward was a train-mode one under RAU_XDROP_TIED: summed conv gradients
   const float* x_shared = nullptr;  // ... and i_embed's input then: xd (the one masked map) or, without a mask, xw
   float* dS_sum = nullptr;          // [cap][A][Sp] sum of the active hops' dS (tied_bwd.hip), allocated with the switch
+  // feature-map gradient (rau_set_feat_grad, xgrad.hip): off = the step path as it is without it
+  bool feat_grad = false;
+  float* xg_dX = nullptr;           // [cap][D][Sp] the last backward's result, allocated with the switch
+  float* xg_tmp = nullptr;          // [cap][D][Sp] one hop's unmasked product (the unfused path)
+  float* xg_dz = nullptr;           // [cap][M][Sp] dI (1 - I^2) where the dgrad left dI (no fused tanh derivative)
+  bool xg_first = false;            // no launch of the running backward has written xg_dX yet: the next one stores
+  bool xg_valid = false;            // xg_dX holds the result of a backward since the last forward
+  bool fwd_xgen = false;            // the last forward drew the feature-map keep bits inside its dropout pass:
+                                    // they were never in memory, the backward regenerates them (philox.h)
+  uint64_t fwd_seed = 0;            // ... from the key that forward ran under: a rau_set_dropout_seed between it and
+  uint32_t fwd_step = 0;            // the backward would regenerate other bits, and is refused with the switch on
+  // rau_set_batch_dev: pinned staging of the index arrays, two halves alternated like hopw_h
+  int32_t* bdev_h[2] = {nullptr, nullptr};
+  hipEvent_t bdev_ev[2] = {nullptr, nullptr};
+  int bdev_slot = 0;
   // the answer criterion of the step path (rau_set_answer_loss): RAU_LOSS_CE, or RAU_LOSS_BCE = per-answer sigmoid.
   // Read through step_truth() only; the module-level criteria name theirs themselves.
   int answer_loss = RAU_LOSS_CE;

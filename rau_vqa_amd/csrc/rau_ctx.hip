@@ -616,6 +616,8 @@ void rau_destroy(rau_ctx* ctx) {
     if (s.consumed) hipEventDestroy(s.consumed);
   }
   for (hipEvent_t e : ctx->hopw_ev) if (e) hipEventDestroy(e);
+  for (hipEvent_t e : ctx->bdev_ev) if (e) hipEventDestroy(e);
+  for (int32_t* p : ctx->bdev_h) if (p) hipHostFree(p);
   for (hipEvent_t e : ctx->evF) hipEventDestroy(e);
   for (hipEvent_t e : ctx->evK) hipEventDestroy(e);
 
@@ -789,6 +791,57 @@ int rau_feat_dropout(rau_ctx* ctx, int* kind) {
   return RAU_OK;
 }
 
+// ------------------------------------------------- feature-map gradient
+// The backward reads ctx->feat_grad (group_conv_grads: one more block of launches per conv group on the bulk
+// stream) and the graph key carries it; nothing else depends on the switch.
+int rau_set_feat_grad(rau_ctx* ctx, int on) {
+  NEED(ctx, "null ctx");
+  if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_feat_grad: a step is being captured");
+  if (on) {
+    // for the capacity, at the first use (never inside a captured step); cleared by rau_set_batch_size like every
+    // activation.  xg_tmp: one hop's product; xg_dz: one hop's dZ where the dgrad leaves dI (every map size outside
+    // the 14 x 14 class, and the tied and evaluate-mode backward of any size: the mode may change after this call).
+    // Each pointer on its own: a call that failed half way is completed by the next one, and the switch stays off
+    // until all three exist.
+    const rau_config& c = ctx->cfg;
+    if (!ctx->xg_dX)
+      if (int rc = dalloc(ctx, &ctx->xg_dX, (size_t)ctx->cap * c.D * ctx->Sp)) return rc;
+    if (!ctx->xg_tmp)
+      if (int rc = dalloc(ctx, &ctx->xg_tmp, (size_t)ctx->cap * c.D * ctx->Sp)) return rc;
+    if (!ctx->xg_dz)
+      if (int rc = dalloc(ctx, &ctx->xg_dz, (size_t)ctx->cap * c.M * ctx->Sp)) return rc;
+  }
+  if ((on != 0) != ctx->feat_grad) ctx->xg_valid = false;
+  ctx->feat_grad = on != 0;
+  return RAU_OK;
+}
+int rau_feat_grad(rau_ctx* ctx, int* on) {
+  NEED(ctx && on, "null argument");
+  *on = ctx->feat_grad ? 1 : 0;
+  return RAU_OK;
+}
+static int feat_grad_state(rau_ctx* ctx, const char* fn) {
+  if (!ctx->feat_grad) return fail(RAU_ERR_STATE, "%s: the feature-map gradient is off (rau_set_feat_grad)", fn);
+  if (!ctx->xg_valid) return fail(RAU_ERR_STATE, "%s: no backward has run since the last forward", fn);
+  return RAU_OK;
+}
+int rau_feat_grad_dev(rau_ctx* ctx, const float** dX, int32_t* pitch) {
+  NEED(ctx, "null ctx");
+  if (int rc = feat_grad_state(ctx, "rau_feat_grad_dev")) return rc;
+  if (dX) *dX = ctx->xg_dX;
+  if (pitch) *pitch = ctx->Sp;
+  return RAU_OK;
+}
+int rau_get_feat_grad(rau_ctx* ctx, float* host) {
+  NEED(ctx && host, "null argument");
+  if (int rc = feat_grad_state(ctx, "rau_get_feat_grad")) return rc;
+  const rau_config& c = ctx->cfg;
+  HIPC(hipMemcpy2DAsync(host, (size_t)c.S * 4, ctx->xg_dX, (size_t)ctx->Sp * 4, (size_t)c.S * 4, (size_t)c.B * c.D,
+                        hipMemcpyDeviceToHost, ctx->st));
+  HIPC(hipStreamSynchronize(ctx->st));
+  return persist_check(ctx);
+}
+
 // ------------------------------------------------------ answer criterion
 // The forward's head reads ctx->answer_loss through step_truth(); the merged-hops record carries the kind of the
 // forward it describes (MergeState::truth), the graph key the kind a step was captured under.  Nothing is allocated
@@ -889,6 +942,7 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   ctx->fwd_table = false;
   ctx->xw = nullptr;
   ctx->fwd_done = ctx->bwd_done = false;
+  ctx->xg_valid = false;
   ctx->dpre_fwd = false;
   ctx->I_shared = ctx->yq_shared = false;
   ctx->fwd_tied = false;
@@ -1405,6 +1459,9 @@ static int feature_maps(rau_ctx* ctx, hipStream_t sb, const Masks& m, const floa
   const bool x16 = m.x && ctx->xd16 && !tied;
   const int HX = tied ? 1 : H;         // masked copies: the mask site has HX * B * D * SL elements
   const bool x_gen = m.x && !ctx->mexplicit[RAU_MASK_X] && SL == S && ((size_t)B * D * S) % 16 == 0;
+  ctx->fwd_xgen = x_gen;   // the bits never reach memory: a feature-map gradient regenerates them (xgrad.hip)
+  ctx->fwd_seed = ctx->seed;
+  ctx->fwd_step = ctx->step;
   if (!x_gen)
     if (int rc = gen_masks(ctx, -1, RAU_MASK_X, sb)) return rc;
   RUNS(sb, "transpose", 0, (double)M * D * 8, transpose2d(sb, M, D, ctx->i_embed.W, ctx->WiT, ctx->WiT16));
@@ -1474,6 +1531,7 @@ int rau_forward(rau_ctx* ctx) {
   BatchSlot& bs = cur_batch(ctx);
   if (!bs.held.have) return fail(RAU_ERR_STATE, "rau_forward: no batch (call rau_set_batch)");
   ctx->mg.valid = false;   // the hop outputs are being overwritten
+  ctx->xg_valid = false;   // ... and the feature-map gradient is another forward's
   const rau_config& c = ctx->cfg;
   const int B = c.B, Rq = c.Rq, D = c.D, S = ctx->Sp, M = c.M, A = c.A, R = c.R, H = c.H, Q = ctx->Q;
   const int TL = bs.held.max_len;
@@ -1684,8 +1742,52 @@ static int loss_gradients(rau_ctx* ctx, const StepLoss& loss, const Truth& t) {
   return RAU_OK;
 }
 
-// The 1x1-conv gradients of the launch group that starts with hop h, on the bulk stream (dZ only feeds weight
-// gradients; the feature-map gradient is dead, SS:579, never formed); HA = the active hops.
+// The feature-map gradient of `nh` hops from hop h0 on (rau_set_feat_grad), on the bulk stream behind the conv
+// gradients that formed their dZ: xg_dX (=, for the backward's first launch, else +=) sum_h keep_h s_x Wi^T dZ_h.
+// dz: hop h0's [B][M][Sp] block, nh of them; is_dI: it holds the gradient at i_embed's OUTPUT (the dgrad without
+// the fused tanh derivative), I the matching activations (I_stride floats from hop to hop, 0 = shared).
+// mask_hop: the first hop's slice of the mask site (tied: 0), mask_step hops per hop (tied, no mask: 0).
+static int feat_grad_hops(rau_ctx* ctx, hipStream_t sb, int nh, const void* dz, bool dz_is_b16, bool is_dI,
+                          const float* I, size_t I_stride, int mask_hop, int mask_step) {
+  const rau_config& c = ctx->cfg;
+  const int B = c.B, D = c.D, S = ctx->Sp, SL = c.S, M = c.M;
+  const Masks m = masks_of(ctx);
+  XMask xm{};
+  xm.kind = !m.x ? 0 : ctx->fwd_xgen ? 2 : 1;
+  xm.bits = m.x;
+  xm.hop_stride = (size_t)B * D * SL;
+  xm.seed = ctx->seed; xm.site = RAU_MASK_X; xm.step = ctx->step; xm.key = ctx->dkey;
+  xm.thr = (uint32_t)lroundf(ctx->mp[RAU_MASK_X] * 256.0f);
+  xm.scale = m.x ? m.s_x : 1.f;
+  const double fl = gflop(D, (double)B * S, M), by = ((double)B * M * S + (double)B * D * S) * 4;
+  if (!dz_is_b16 && !is_dI && !ctx->bf16 && xgrad_fused_ok(D, M, S) && S == SL) {
+    xm.e0 = (size_t)mask_hop * xm.hop_stride;
+    if (!mask_step) xm.hop_stride = 0;
+    RUNS(sb, "conv_embed_dgrad", nh * fl, (double)nh * B * M * S * 4 + (double)B * D * S * (ctx->xg_first ? 4 : 8),
+         xgrad_fused(sb, nh, B, D, M, S, (const float*)dz, ctx->i_embed.W, ctx->xg_dX, xm, ctx->xg_first ? 1 : 0));
+    ctx->xg_first = false;
+    return RAU_OK;
+  }
+  for (int k = 0; k < nh; ++k) {
+    const void* dzk = map_elems(const_cast<void*>(dz), dz_is_b16, (size_t)k * B * M * S);
+    if (is_dI) {
+      RUNS(sb, "mul_dtanh", 0, (double)B * M * S * 12,
+           mul_dtanh(sb, (size_t)B * M * S, (const float*)dzk, I + (size_t)k * I_stride, ctx->xg_dz));
+      dzk = ctx->xg_dz;
+    }
+    RUNS(sb, "conv_embed_dgrad", fl, by,
+         conv_embed_dgrad_mode(sb, B, D, S, M, dzk, dz_is_b16 ? 1 : 0, ctx->i_embed.W, ctx->xg_tmp, ctx->bf16));
+    xm.e0 = (size_t)(mask_hop + k * mask_step) * xm.hop_stride;
+    RUNS(sb, "xgrad_accum", 2.0 * B * D * S, (double)B * D * S * (ctx->xg_first ? 8 : 12),
+         xgrad_accum(sb, (size_t)B * D, SL, S, ctx->xg_tmp, ctx->xg_dX, xm, ctx->xg_first ? 1 : 0));
+    ctx->xg_first = false;
+  }
+  return RAU_OK;
+}
+
+// The 1x1-conv gradients of the launch group that starts with hop h, on the bulk stream (dZ feeds the weight
+// gradients; the feature-map gradient is dead in the reference, SS:579, and formed only under rau_set_feat_grad:
+// feat_grad_hops above); HA = the active hops.
 static int group_conv_grads(rau_ctx* ctx, int h, int group, int HA) {
   const rau_config& c = ctx->cfg;
   const int B = c.B, D = c.D, S = ctx->Sp, M = c.M, A = c.A;
@@ -1706,6 +1808,8 @@ static int group_conv_grads(rau_ctx* ctx, int h, int group, int HA) {
     if (g.dzf && h == 0)   // last group: i_embed bias gradient = column sums of the per-sample rows
       RUNS(sb, "colsum", 0, (double)HA * B * M * 4,
            colsum_acc(sb, HA * B, M, ctx->dbi_part, M, ctx->i_embed.db, ctx->ws_bulk.coltmp));
+    if (ctx->feat_grad)
+      return feat_grad_hops(ctx, sb, g.n / B, g.dZ, g.dz_is_b16, !g.dzf, g.I, (size_t)B * M * S, h, 1);
     return RAU_OK;
   }
   g.n = B; g.I = ctx->I;
@@ -1715,7 +1819,10 @@ static int group_conv_grads(rau_ctx* ctx, int h, int group, int HA) {
     // The sum of dS goes to a buffer of its own: T keeps every hop's dS, as on the per-hop paths.
     RUNS(sb, "hop_sum", 0, (double)(HA + 1) * B * A * S * 4, hop_sum(sb, HA, B, A, c.S, S, ctx->T, ctx->dS_sum));
     g.dS = ctx->dS_sum; g.dj = ctx->dj; g.a = ctx->a; g.X = ctx->x_shared; g.dZ = ctx->dZ; g.tied_hops = HA;
-    return conv_grads(ctx, sb, g);
+    if (int rc = conv_grads(ctx, sb, g)) return rc;
+    // one mask: keep * s_x * Wi^T (sum_h dZ_h), and dZ holds that sum (as dI: the tanh derivative is hop-invariant)
+    if (ctx->feat_grad) return feat_grad_hops(ctx, sb, 1, ctx->dZ, false, true, ctx->I, 0, 0, 0);
+    return RAU_OK;
   }
   for (int hh2 = 0; hh2 < HA; ++hh2) {  // evaluate mode: I (and X) shared by all hops
     const size_t hb = (size_t)hh2 * B;
@@ -1723,6 +1830,8 @@ static int group_conv_grads(rau_ctx* ctx, int h, int group, int HA) {
     g.X = ctx->xw; g.dZ = ctx->dZ + hb * M * S;
     if (int rc = conv_grads(ctx, sb, g)) return rc;
   }
+  if (ctx->feat_grad && HA > 0)   // no mask, scale 1: the hops in ascending order
+    return feat_grad_hops(ctx, sb, HA, ctx->dZ, false, true, ctx->I, 0, 0, 0);
   return RAU_OK;
 }
 
@@ -1858,6 +1967,17 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
                 "i_embed once per image, so there is no per-sample I to differentiate; take evaluate-mode "
                 "gradients on a plain batch (rau_set_batch)");
   const BatchSlot& bs = cur_batch(ctx);
+  if (ctx->feat_grad && bs.held.n_images > 0)
+    return fail(RAU_ERR_STATE, "rau_backward: the feature-map gradient (rau_set_feat_grad) of a batch with an image "
+                "table or bank rows is a sum over the questions of an image, which is not formed; expand the maps "
+                "per sample (rau_set_batch_dev) or turn the switch off");
+  // the feature-map keep bits that forward drew in its dropout pass exist nowhere: the backward regenerates them
+  // from the key, which must still be that forward's (a captured step holds both passes: the key cannot move)
+  if (ctx->feat_grad && !ctx->capturing && ctx->fwd_xgen && masks_of(ctx).x &&
+      (ctx->seed != ctx->fwd_seed || ctx->step != ctx->fwd_step))
+    return fail(RAU_ERR_STATE, "rau_backward: rau_set_dropout_seed was called between the forward and this backward; "
+                "with the feature-map gradient on (rau_set_feat_grad) the backward regenerates the forward's "
+                "feature-map dropout bits from the key: run the forward again");
   // an external-only backward reads no label: hop_w zeros, no select_w, no merge_w (att_w reads the targets alone)
   const bool builtin = !loss.has_ext() || loss.hop_any || sel || mrg;
   if (builtin && !bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_backward: batch has no labels");
@@ -1882,6 +2002,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   const Masks m = masks_of(ctx);
   const size_t BM_ = (size_t)B * M, BS_ = (size_t)B * S, BR_ = (size_t)B * R;
   ctx->fwd_done = false;  // dl is scaled in place below: one backward per forward
+  ctx->xg_first = true;   // (feat_grad) the first launch that writes xg_dX stores, the others add
   if (int rc = loss_gradients(ctx, loss, t)) return rc;
   const float* dc_next = nullptr;  // grad_att_c / grad_att_h zeros, SS:561-562
   float* dh_part = nullptr;        // gradient at next_h: K-split partials left by the previous hop
@@ -1949,6 +2070,8 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
     RUN("dq_reduce", 0, (double)HA * B * Q * 4,
         dq_reduce(st, HA, (size_t)B * Q, ctx->dQD, m.q, m.s_q, ctx->dq));
   }
+  if (ctx->feat_grad && ctx->xg_first)   // no active hop: the gradient is zero
+    HIPC(hipMemsetAsync(ctx->xg_dX, 0, (size_t)B * c.D * S * sizeof(float), ctx->st2));
   // bulk stream tail: the join event (the i_embed bias gradient comes out of conv_embed_wgrad:
   // row sums of its staged dZ operand)
   HIPC(hipEventRecord(ctx->evD, ctx->st2));
@@ -1978,6 +2101,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   HIPC(hipEventRecord(ctx->evEnd, st));
   ctx->bwd_done = true;
   ctx->graph_last = false;
+  ctx->xg_valid = ctx->feat_grad;
   return RAU_OK;
 }
 
@@ -2090,6 +2214,9 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
   if (!bs.held.have || !bs.held.have_labels)
     return fail(RAU_ERR_STATE, "rau_graph_step: needs a batch with labels (rau_set_batch)");
   if (ctx->prof_on) return fail(RAU_ERR_STATE, "rau_graph_step: profiling must be off");
+  if (ctx->feat_grad && bs.held.n_images > 0)
+    return fail(RAU_ERR_STATE, "rau_graph_step: the feature-map gradient (rau_set_feat_grad) of a batch with an image "
+                "table or bank rows is not formed; expand the maps per sample (rau_set_batch_dev)");
   StepKey key;
   key.mode = ctx->mode;
   key.max_len = bs.held.max_len;
@@ -2109,6 +2236,7 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
   key.mrg = loss.merge_w != nullptr;
   key.tied_x = ctx->xdrop == RAU_XDROP_TIED;
   key.ans_loss = ctx->answer_loss;
+  key.feat_grad = ctx->feat_grad;
   if (int rc = upload_hop_weights(ctx, loss)) return rc;
   ctx->mg.valid = false;
   hipGraphExec_t exec = nullptr;
@@ -2148,6 +2276,7 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
   ctx->fwd_done = false;
   ctx->bwd_done = true;
   ctx->graph_last = true;
+  ctx->xg_valid = ctx->feat_grad;
   return RAU_OK;
 }
 

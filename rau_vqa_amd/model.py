@@ -807,6 +807,75 @@ class RAU:
                 device_view(dp.value, H * n, dev).view(H, n),
                 device_view(at.value, H * n * pitch.value, dev).view(H, n, pitch.value)[:, :, :S])
 
+    def want_feature_grad(self, on=True):
+        """Every step-level backward (backward, graph_step) also leaves the gradient at the feature map behind
+        (rau_set_feat_grad): feature_grad() / feature_grad_tensor().  Off (the default) the step is what it was.
+        Batches with one map per sample only: with the switch on, the backward of an image-table or bank batch
+        raises; expand shared images on the caller's side (x[image_of]) in front of set_batch_dev."""
+        L.check(self._lib.rau_set_feat_grad(self._h, 1 if on else 0))
+
+    @property
+    def feature_grad_wanted(self) -> bool:
+        on = C.c_int(0)
+        L.check(self._lib.rau_feat_grad(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def feature_grad(self):
+        """The last backward's feature-map gradient [n,D,S] (numpy; synchronises)."""
+        out = np.empty((self._n, self.cfg.D, self.cfg.S), np.float32)
+        L.check(self._lib.rau_get_feat_grad(self._h, out.ctypes.data))
+        return out
+
+    def feature_grad_tensor(self):
+        """Zero-copy torch view [n,D,S] of the last backward's feature-map gradient in device memory
+        (rau_feat_grad_dev) -- strided where the maps are pitched (S % 4 != 0).  Valid until the next forward or
+        set_batch_size, ordered on the ctx's stream (stream()), read-only."""
+        from .dist import device_view
+        p, pitch = C.c_void_p(), C.c_int32()
+        L.check(self._lib.rau_feat_grad_dev(self._h, C.byref(p), C.byref(pitch)))
+        n, D, S, dev = self._n, self.cfg.D, self.cfg.S, self.cfg.device_id
+        return device_view(p.value, n * D * pitch.value, dev).view(n, D, pitch.value)[:, :, :S]
+
+    def set_batch_dev(self, feats_cuda, tokens, lens, labels=None, answers=None, regions=None, att_targets=None):
+        """set_batch with the maps already on the device: feats_cuda a contiguous float32 CUDA torch tensor
+        [n,D,S] on the ctx's device (rau_set_batch_dev: one copy on the ctx's stream, no host synchronisation).
+        The ctx's stream must be ordered behind the stream that wrote the tensor (autograd.step's docstring shows
+        the two lines); the tensor must stay unchanged until that copy has run.  answers, regions, att_targets as
+        in set_batch."""
+        import torch
+        c = self.cfg
+        lens = np.ascontiguousarray(lens, np.int32)
+        B = self._rows(lens, "set_batch_dev")
+        t = feats_cuda
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError("feats_cuda must be a contiguous float32 CUDA torch tensor")
+        if t.device.index != c.device_id:
+            raise ValueError(f"feats_cuda is on {t.device}, the context on cuda:{c.device_id}")
+        if tuple(t.shape) != (B, c.D, c.S):
+            raise ValueError(f"feats_cuda has shape {tuple(t.shape)}, expected {(B, c.D, c.S)}")
+        tokens = np.ascontiguousarray(tokens, np.int32)
+        if tokens.shape != (c.T, B):
+            raise ValueError("batch shapes do not match the config")
+        lp = None
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, np.int32)
+            if labels.shape != (B,):
+                raise ValueError("labels shape")
+            lp = labels.ctypes.data
+        if regions is not None:
+            regions = self._sample_regions(regions, None, B)
+        if att_targets is not None:
+            att_targets = self._att_targets(att_targets, B)
+        if B != self._n:
+            self.set_batch_size(B)
+        L.check(self._lib.rau_set_batch_dev(self._h, t.data_ptr(), tokens.ctypes.data, lens.ctypes.data, lp))
+        if answers is not None:
+            self.set_answers(*answers)
+        if regions is not None:
+            self.set_regions(regions)
+        if att_targets is not None:
+            self.set_att_targets(att_targets)
+
     def graph_step(self, hop_w, zero_grads=True, select_w=None, att_w=None, merge_w=None):
         """zero_grads + forward + backward as one hipGraph launch (captured on first use); select_w, att_w and
         merge_w as in backward (read from device memory: they may change between replays)."""
