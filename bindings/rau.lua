@@ -113,8 +113,11 @@ typedef struct rau_out_grads {
 int rau_set_feat_grad(rau_ctx* ctx, int on);
 int rau_feat_grad(rau_ctx* ctx, int* on);
 int rau_feat_grad_dev(rau_ctx* ctx, const float** dX, int32_t* pitch);
+int rau_feat_grad_rows(rau_ctx* ctx, int32_t* rows);
 int rau_get_feat_grad(rau_ctx* ctx, float* host);
 int rau_set_batch_dev(rau_ctx* ctx, const float* feats_dev, const int32_t* tokens, const int32_t* lens, const int32_t* labels);
+int rau_set_batch_dev_images(rau_ctx* ctx, const float* table_dev, int n_images, const int32_t* image_of,
+                             const int32_t* tokens, const int32_t* lens, const int32_t* labels);
 int rau_outputs_dev(rau_ctx* ctx, const float** logits, const float** dopred, const float** attprob,
                     int32_t* att_pitch);
 int rau_backward_ext(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
@@ -219,6 +222,7 @@ int rau_prof_count(rau_ctx* ctx);
 int rau_prof_entry(rau_ctx* ctx, int index, const char** name, int64_t* launches,
                    double* total_ms, double* flops, double* bytes);
 int rau_split_guard_check(size_t ws_floats, size_t offset, int nsplit, size_t per_split_floats);
+int rau_image_lists(int n, int n_images, const int32_t* image_of, int32_t* start, int32_t* samples);
 int rau_enc_ws_coresident(int batch, int blocks_per_cu, int n_cus);
 ]]
 
@@ -571,13 +575,23 @@ function RAU:outputsDev()
 end
 
 -- Feature-map gradient (rau_set_feat_grad): with the switch on every backward / graphStep also leaves the gradient
--- at the feature map behind, for a trainable stage in front of the library.  Batches with one map per sample only:
--- the backward of an image-table or bank batch then errors (expand shared images in front of setBatchDev).
-function RAU:wantFeatureGrad(on)
-  check(C.rau_set_feat_grad(self.h, (on == nil or on) and 1 or 0))
+-- at the feature map behind, for a trainable stage in front of the library.  perImage false / nil
+-- (RAU_FEAT_GRAD_SAMPLES): batches with one map per sample only, the backward of an image-table or bank batch then
+-- errors.  perImage true (RAU_FEAT_GRAD_IMAGES): an image-table batch leaves the gradient at the TABLE, [N,D,pitch],
+-- each image's samples summed in ascending order; every other batch as without it; bank batches stay refused.
+RAU.FEAT_GRAD_OFF, RAU.FEAT_GRAD_SAMPLES, RAU.FEAT_GRAD_IMAGES = 0, 1, 2
+function RAU:wantFeatureGrad(on, perImage)
+  local mode = (on == nil or on) and (perImage and RAU.FEAT_GRAD_IMAGES or RAU.FEAT_GRAD_SAMPLES) or RAU.FEAT_GRAD_OFF
+  check(C.rau_set_feat_grad(self.h, mode))
   return self
 end
--- the last backward's result in device memory: const float* cdata [n,D,pitch] and the pitch (rau_feat_grad_dev);
+-- the map count of the last backward's result (rau_feat_grad_rows): n, or the table's N under perImage
+function RAU:featureGradRows()
+  local rows = ffi.new('int32_t[1]')
+  check(C.rau_feat_grad_rows(self.h, rows))
+  return rows[0]
+end
+-- the last backward's result in device memory: const float* cdata [rows,D,pitch] and the pitch (rau_feat_grad_dev);
 -- valid until the next forward, ordered on the ctx's stream
 function RAU:featureGrad()
   local p, pitch = ffi.new('const float*[1]'), ffi.new('int32_t[1]')
@@ -589,6 +603,14 @@ end
 function RAU:setBatchDev(feats_dev, x, x_len, y)
   follow_rows(self, x_len)
   check(C.rau_set_batch_dev(self.h, feats_dev, x:data(), x_len:data(), y and y:data() or nil))
+end
+-- setBatchImages with the table already on the device: table_dev a DEVICE float* to dense [n_images,D,S] float32,
+-- image_of an IntTensor [B] of 1-BASED table rows (rau_set_batch_dev_images)
+function RAU:setBatchDevImages(table_dev, n_images, image_of, x, x_len, y)
+  follow_rows(self, x_len)
+  local idx = image_of:int():add(-1)
+  check(C.rau_set_batch_dev_images(self.h, table_dev, n_images, idx:data(), x:data(), x_len:data(),
+                                   y and y:data() or nil))
 end
 
 -- backward with the gradients of a term of the caller's own at those outputs (rau_backward_ext): grads = { logits =,

@@ -725,33 +725,56 @@ int rau_backward_ext(rau_ctx* ctx, const float* hop_w /* [H] host, NULL = zeros 
  *                the backward's order, last group first, the hops of a group ascending).
  *   the result   is OVERWRITTEN by each backward, never accumulated (feature maps change with every batch);
  *                rau_zero_grads does not touch it.
- *   batches      one map per sample: plain, typed and packed batches, and rau_set_batch_dev below.  With the switch
- *                on, the backward of an image-table or bank batch is RAU_ERR_STATE with nothing launched and no
- *                gradient changed: a shared map's gradient is a sum over its questions, which the library does not
- *                form.  A caller that shares images expands them on its side (x[image_of]) in front of
- *                rau_set_batch_dev and sums the rows of the result per image (torch: autograd does).
+ *   batches      RAU_FEAT_GRAD_SAMPLES (1): one map per sample -- plain, typed and packed batches, and
+ *                rau_set_batch_dev below.  The backward of an image-table or bank batch is RAU_ERR_STATE with nothing
+ *                launched and no gradient changed (in this mode a caller that shares images expands them on its
+ *                side, x[image_of], in front of rau_set_batch_dev; mode 2 forms the per-image sum instead).
+ *                RAU_FEAT_GRAD_IMAGES (2): on a batch with one map per sample the same launches and bits as mode 1.
+ *                On an IMAGE-TABLE batch (rau_set_batch_images, rau_set_batch_async_images + rau_use_batch, a packed
+ *                table with an image_of, rau_set_batch_dev_images below) the result is the gradient at the TABLE,
+ *                  dT[i,d,s] = sum_{h < HA} sum_{b: image_of[b] = i} keep_h[b,d,s] * s_x * (Wi^T dZ_h[b])[d,s]
+ *                as [N, D, pitch]: an image no sample names gets exact zeros, pad columns are zeros, the keep bits are
+ *                indexed by SAMPLE (explicit or regenerated, as in mode 1), tied dropout takes the one-mask product of
+ *                the summed dZ first.  Per hop launch the accumulator starts at +0 (the backward's first writing
+ *                launch) or at the stored value, an image's samples are added in ascending b, each term
+ *                keep ? g * s_x : 0 rounded once: with the identity table (N = n, image_of = 0..n-1) the bits are
+ *                those of the plain batch under mode 1.  The per-sample [n,D,pitch] gradient is not formed.  The
+ *                evaluate-mode forward of a table batch takes the gathered per-sample path under this mode (same
+ *                output bits), so its backward exists: per-image saliency.  Bank batches stay refused in both modes.
+ *                Any other value of `on`: RAU_ERR_INVALID.  rau_feat_grad reports the mode.
  *   the key      where the forward drew the feature-map bits inside its dropout pass they exist nowhere, and the
  *                backward regenerates them from (seed, step): with the switch on, a rau_set_dropout_seed with another
  *                key between a forward and its backward makes that backward RAU_ERR_STATE, nothing launched (run the
  *                forward again).  A captured step holds both passes and reads the key from device memory.
  *   ext          rau_backward_ext's rule stays: no gradient enters at the question state.
- * rau_feat_grad_dev: the ctx-owned DEVICE pointer to the last backward's result [n, D, *pitch] (n the current batch
- * size, *pitch = S rounded up to a multiple of 4), ordered on the ctx's stream; synchronises nothing; valid until
- * the next forward or rau_set_batch_size.  RAU_ERR_STATE when the switch is off or no backward has run since the
- * last forward.  rau_get_feat_grad: the download, dense [n,D,S]; synchronises.
+ * rau_feat_grad_dev: the ctx-owned DEVICE pointer to the last backward's result [rows, D, *pitch] (rows: the current
+ * batch size n, or the table's N where the gradient was formed per image; *pitch = S rounded up to a multiple of 4),
+ * ordered on the ctx's stream; synchronises nothing; valid until the next forward or rau_set_batch_size.
+ * RAU_ERR_STATE when the switch is off or no backward has run since the last forward.  rau_feat_grad_rows: that
+ * result's map count, under the same state rules.  rau_get_feat_grad: the download, dense [rows,D,S]; synchronises.
  * rau_set_batch_dev: rau_set_batch with the maps [n,D,S] float32, dense, already in DEVICE memory: one copy on the
  * ctx's stream (re-pitching where S % 4 != 0) into the resident buffer, in the layout an f32 batch has there; the
  * rest is rau_set_batch_typed(NULL, RAU_FEAT_F32, ..).  tokens / lens / labels are HOST arrays, copied into pinned
  * staging of the ctx before the call returns; the call waits for no device work (only, from the third call on, for
  * the index copy of the call two before it).  The caller orders the producer of feats_dev in front of the ctx's
  * stream (an event of its stream, waited on by rau_stream) and keeps feats_dev unchanged until the copy has run.
- * Answer sets, region counts and attention targets attach afterwards, as to any batch. */
+ * Answer sets, region counts and attention targets attach afterwards, as to any batch.
+ * rau_set_batch_dev_images: the same for an image table -- table_dev holds n_images maps [N,D,S] float32, dense, in
+ * DEVICE memory, image_of [n] is a HOST array checked like rau_set_batch_images' and staged in the same pinned halves;
+ * N maps are copied on the ctx's stream.  No host wait.  RAU_ERR_STATE while a step is being captured. */
+#define RAU_FEAT_GRAD_OFF 0
+#define RAU_FEAT_GRAD_SAMPLES 1
+#define RAU_FEAT_GRAD_IMAGES 2
 int rau_set_feat_grad(rau_ctx* ctx, int on);
 int rau_feat_grad(rau_ctx* ctx, int* on);
 int rau_feat_grad_dev(rau_ctx* ctx, const float** dX, int32_t* pitch);
-int rau_get_feat_grad(rau_ctx* ctx, float* host /* [n,D,S] dense */);
+int rau_feat_grad_rows(rau_ctx* ctx, int32_t* rows);
+int rau_get_feat_grad(rau_ctx* ctx, float* host /* [rows,D,S] dense */);
 int rau_set_batch_dev(rau_ctx* ctx, const float* feats_dev /* [n,D,S] f32, dense, DEVICE */, const int32_t* tokens,
                       const int32_t* lens, const int32_t* labels);
+int rau_set_batch_dev_images(rau_ctx* ctx, const float* table_dev /* [N,D,S] f32, dense, DEVICE */, int n_images,
+                             const int32_t* image_of /* host [n] */, const int32_t* tokens, const int32_t* lens,
+                             const int32_t* labels);
 
 /* ---- module-level entry points: one call per nn.Module :forward / :backward -----
  * For hosts that keep feval's own loops (SS:443-596) and call the clones one by one.
@@ -1081,9 +1104,14 @@ int rau_prof_entry(rau_ctx* ctx, int index, const char** name, int64_t* launches
  * offset is stale.
  * rau_enc_ws_coresident: 1 if the weight-stationary persistent encoder (whose workgroups wait on each
  * other's progress counters) may be selected for `batch` samples on a device that admits
- * `blocks_per_cu` of its workgroups per CU on `n_cus` CUs, else 0. */
+ * `blocks_per_cu` of its workgroups per CU on `n_cus` CUs, else 0.
+ * rau_image_lists: the sample lists of an image table as the batch code builds them for the per-image feature-map
+ * gradient (a stable counting sort over image_of): image i owns samples[start[i] .. start[i + 1]), ascending;
+ * start[n_images] = n.  RAU_ERR_INVALID for n < 1, n_images outside [1, n] or an index outside [0, n_images). */
 int rau_split_guard_check(size_t ws_floats, size_t offset, int nsplit, size_t per_split_floats);
 int rau_enc_ws_coresident(int batch, int blocks_per_cu, int n_cus);
+int rau_image_lists(int n, int n_images, const int32_t* image_of, int32_t* start /* [n_images+1] */,
+                    int32_t* samples /* [n] */);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,7 @@ MASK_SITES = {"we": 0, "rnn": 1, "q": 2, "x": 3, "mf": 4}
 XDROP_PER_HOP, XDROP_TIED = 0, 1
 LOSS_CE, LOSS_BCE = 0, 1
 LOSSES = {"ce": LOSS_CE, "bce": LOSS_BCE}
+FEAT_GRAD_OFF, FEAT_GRAD_SAMPLES, FEAT_GRAD_IMAGES = 0, 1, 2
 
 
 class RauConfig(C.Structure):
@@ -166,8 +167,11 @@ _SIGS = {
     "rau_set_feat_grad": (C.c_int, [C.c_void_p, C.c_int]),
     "rau_feat_grad": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rau_feat_grad_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
+    "rau_feat_grad_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "rau_get_feat_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rau_set_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rau_set_batch_dev_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
     # module-level entry points: device pointers in, pointers to ctx-owned slots out
     "rau_embed_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_embed_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -259,6 +263,7 @@ _SIGS = {
                                  C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                  C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rau_split_guard_check": (C.c_int, [C.c_size_t, C.c_size_t, C.c_int, C.c_size_t]),
+    "rau_image_lists": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_enc_ws_coresident": (C.c_int, [C.c_int, C.c_int, C.c_int]),
 }
 

@@ -19,6 +19,10 @@ The built-in terms (hop_w, select_w, att_w, merge_w) are given to ``step`` and j
 
 The backward then returns a clone of ``rau.feature_grad_tensor()`` for x, ordered with events as the outputs are.
 
+Questions that share images: ``rau.want_feature_grad(per_image=True)``, ``rau.set_batch_dev(table, ..., image_of=idx)``
+and ``step(rau, hop_w, feats=table)`` with the table [N,D,S] itself; table.grad is then the per-image sum, formed by
+the library in a fixed order (the same bits from run to run, which an index_select backward does not give).
+
 torch is plumbing here: the forward, the backward and the update are librau's kernels; torch evaluates the
 caller's loss and its gradient at the three outputs, on its own current stream.  The two streams are joined with
 events only (ExternalStream + wait_stream), never with a host synchronisation.
@@ -58,7 +62,7 @@ class _Step(torch.autograd.Function):
         gx = None
         if ctx.has_feats:                       # the gradient at the feature map, for the graph in front of it
             torch.cuda.current_stream(ctx.dev).wait_stream(own)
-            gx = rau.feature_grad_tensor().clone()
+            gx = rau.feature_grad_tensor().clone()   # [rows,D,S]: per sample, or per image of a table batch
             own.wait_stream(torch.cuda.current_stream(ctx.dev))   # the next step overwrites the buffer: behind the clone
         return (gx,) + (None,) * 5              # parameter gradients live in the ctx's flat buffers
 
@@ -71,13 +75,20 @@ def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, feats=None):
     ``step``; an output that does not enter the loss costs nothing.
 
     feats: the CUDA float tensor [n,D,S] the resident batch was made of (RAU.set_batch_dev), with the context's
-    feature-map gradient on (RAU.want_feature_grad): it becomes the recorded input and receives its gradient."""
+    feature-map gradient on (RAU.want_feature_grad): it becomes the recorded input and receives its gradient.  For a
+    resident image-table batch under want_feature_grad(per_image=True): the table [N,D,S]."""
     if feats is not None:
         c = rau.cfg
-        if not (isinstance(feats, torch.Tensor) and feats.is_cuda and tuple(feats.shape) == (rau.batch_size, c.D, c.S)):
-            raise ValueError(f"feats must be the CUDA tensor [n,D,S] = {(rau.batch_size, c.D, c.S)} given to set_batch_dev")
+        if not (isinstance(feats, torch.Tensor) and feats.is_cuda and feats.dim() == 3):
+            raise ValueError("feats must be the CUDA tensor given to set_batch_dev")
+        per_image = tuple(feats.shape) != (rau.batch_size, c.D, c.S)   # then: the table [N,D,S] of a resident table batch
+        if per_image and not (tuple(feats.shape[1:]) == (c.D, c.S) and 1 <= feats.shape[0] <= rau.batch_size):
+            raise ValueError(f"feats must be the CUDA tensor [n,D,S] = {(rau.batch_size, c.D, c.S)} given to "
+                             f"set_batch_dev, or the image table [N,D,S] given to it with image_of")
         if not rau.feature_grad_wanted:
             raise ValueError("step(feats=...) needs the feature-map gradient: call rau.want_feature_grad() first")
+        if per_image and rau.feature_grad_mode != 2:
+            raise ValueError("step(feats=table) needs the per-image gradient: rau.want_feature_grad(per_image=True)")
         if feats.requires_grad:   # (a tensor nobody differentiates is a plain batch: the anchor below)
             return _Step.apply(feats, rau, hop_w, select_w, att_w, merge_w)
     # a leaf that requires grad makes autograd record the node: the real leaves are the ctx's parameters

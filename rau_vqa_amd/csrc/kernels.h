@@ -179,6 +179,12 @@ struct XMask {
 // columns s >= SL written as zeros; one hop (the mask's first)
 hipError_t xgrad_accum(hipStream_t st, size_t rows, int SL, int Sp, const float* G, float* dX, const XMask& m,
                        int store);
+// The same pass per IMAGE of a table: dT[i][d][s] = (store ? 0 : dT[i][d][s]) + sum over the samples b of
+// img_samples[img_start[i] .. img_start[i + 1]), in that order, of keep[b][d][s] * scale * G[b][d][s], for the image
+// slots i < slots (an empty list: zeros under store, else untouched).  G [.][D][Sp], dT [slots][D][Sp]; the lists are
+// DEVICE arrays ([slots + 1], [samples]) read by the kernel: no argument depends on their contents.
+hipError_t xgrad_accum_img(hipStream_t st, int slots, int D, int SL, int Sp, const float* G, float* dT,
+                           const int32_t* img_start, const int32_t* img_samples, const XMask& m, int store);
 // Exact f32, 14 x 14 class (xgrad_fused_ok): dX[b] (store ? = : +=) sum_{h < nh} keep_h * scale * Wi^T dZ_h[b] with
 // the hop loop inside the workgroup.  dZ [nh][nB][M][S] f32, Wi [M][D].
 bool xgrad_fused_ok(int D, int M, int S);

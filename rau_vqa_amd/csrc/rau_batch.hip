@@ -69,6 +69,7 @@ struct Batch {
   const int32_t* pk_nreg = nullptr;     // [B] region counts per SAMPLE: pk_counts, or pk_counts[image_of]
   // ---- worked out on the way in
   const int32_t* bank_idx = nullptr;    // [2B], check_bank_rows
+  const int32_t* img_block = nullptr;   // table batch: image_of | img_start | img_samples as the slot stores them (stage_table)
   bool bank_table = false;              // the upload gathers the table itself (wants_table)
   const int32_t *utok = nullptr, *ustart = nullptr, *upos = nullptr;   // index_batch
   int max_len = 0, nuniq = 0;
@@ -81,6 +82,27 @@ int check_table(const rau_config& c, int n_images, const int32_t* image_of) {
   for (int b = 0; b < c.B; ++b)
     NEED(image_of[b] >= 0 && image_of[b] < n_images, "image_of[%d]=%d out of [0,%d)", b, image_of[b], n_images);
   return RAU_OK;
+}
+// The sample lists of a table (rau_image_lists): a stable counting sort over image_of, so image i owns
+// samples[start[i] .. start[i + 1]) in ascending sample order.  start has slots + 1 entries; the slots at and behind
+// n_images are empty (start = n).  image_of has passed check_table.
+void image_lists(int n, int n_images, const int32_t* image_of, int slots, int32_t* start, int32_t* samples) {
+  std::fill(start, start + slots + 1, 0);
+  for (int b = 0; b < n; ++b) ++start[image_of[b] + 1];
+  for (int i = 0; i < n_images; ++i) start[i + 1] += start[i];
+  for (int i = n_images + 1; i <= slots; ++i) start[i] = n;
+  std::vector<int32_t> at(start, start + n_images);
+  for (int b = 0; b < n; ++b) samples[at[image_of[b]]++] = b;
+}
+// A table batch's index block in the layout of BatchSlot::image_of_d: image_of [cap] | img_start [cap + 1] |
+// img_samples [cap], the lists over all `cap` image slots (the per-image gradient pass is launched over the capacity)
+size_t table_block_words(const rau_ctx* ctx) { return 3 * (size_t)ctx->cap + 1; }
+void stage_table(const rau_ctx* ctx, int n_images, const int32_t* image_of, int32_t* block) {
+  const int n = ctx->cfg.B, cap = ctx->cap;
+  std::copy(image_of, image_of + n, block);
+  std::fill(block + n, block + cap, 0);
+  image_lists(n, n_images, image_of, cap, block + cap, block + 2 * (size_t)cap + 1);
+  std::fill(block + 2 * (size_t)cap + 1 + n, block + table_block_words(ctx), 0);
 }
 // what the two bank entry points ask before anything else
 int need_bank(const rau_ctx* ctx, const char* who, const int32_t* rows) {
@@ -153,13 +175,16 @@ int ensure_table(rau_ctx* ctx, int si, bool pinned, bool bank) {
     if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(bank index staging): %s", hipGetErrorString(e));
     s.bank_idx_h = static_cast<int32_t*>(h);
   }
-  if (!s.image_of_d)
-    if (int rc = dalloc(ctx, &s.image_of_d, cap)) return rc;
+  if (!s.image_of_d) {
+    if (int rc = dalloc(ctx, &s.image_of_d, table_block_words(ctx))) return rc;
+    s.img_start_d = s.image_of_d + cap;
+    s.img_samples_d = s.img_start_d + cap + 1;
+  }
   if (!ctx->feats_x)
     if (int rc = dalloc(ctx, &ctx->feats_x, cap * c.D * ctx->Sp)) return rc;
   if (pinned && !s.image_of_h) {
     void* h = nullptr;
-    hipError_t e = hipHostMalloc(&h, cap * 4, hipHostMallocDefault);
+    hipError_t e = hipHostMalloc(&h, table_block_words(ctx) * 4, hipHostMallocDefault);
     if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(image index staging): %s", hipGetErrorString(e));
     s.image_of_h = static_cast<int32_t*>(h);
   }
@@ -214,7 +239,8 @@ int enqueue_batch(rau_ctx* ctx, hipStream_t st, int si, const Batch& b) {
   const size_t TB = (size_t)c.T * c.B, es = feat_elem_bytes(b.feat_type);
   const size_t maps = b.n_images > 0 ? (size_t)b.n_images : (size_t)c.B;   // only these cross the bus
   ++ctx->slot_serial[si];
-  if (b.n_images > 0) HIPC(hipMemcpyAsync(d.image_of_d, b.image_of, (size_t)c.B * 4, hipMemcpyHostToDevice, st));
+  if (b.n_images > 0)   // the index and the sample lists built from it: one block
+    HIPC(hipMemcpyAsync(d.image_of_d, b.img_block, table_block_words(ctx) * 4, hipMemcpyHostToDevice, st));
   // pitched rows of another element size (4, 2 or 1 bytes) leave data in this type's pad columns: zero the
   // whole buffer first, on any change of type
   // (a packed batch of B maps writes every pad column itself)
@@ -292,8 +318,13 @@ int set_batch_sync(rau_ctx* ctx, Batch b) {
   b.bank_table = wants_table(ctx, b);
   const int si = ctx->cur_slot;   // slot 0 unless rau_use_batch switched
   BatchSlot& s = ctx->slot[si];
-  if (b.n_images)
+  std::vector<int32_t> tblock;
+  if (b.n_images) {
     if (int rc = ensure_table(ctx, si, false, b.bank_rows != nullptr)) return rc;
+    tblock.resize(table_block_words(ctx));
+    stage_table(ctx, b.n_images, b.image_of, tblock.data());
+    b.img_block = tblock.data();
+  }
   std::vector<int32_t> pmeta, pnreg;
   if (b.pk_counts) {
     if (int rc = ensure_packed(ctx, si, false)) return rc;
@@ -346,7 +377,7 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   if (b.tokens && b.tokens != s.tokens_h) std::memcpy(s.tokens_h, b.tokens, TB * 4);
   if (b.lens && b.lens != s.lens_p) std::memcpy(s.lens_p, b.lens, (size_t)c.B * 4);
   if (b.labels && b.labels != s.labels_h) std::memcpy(s.labels_h, b.labels, (size_t)c.B * 4);
-  if (b.n_images) std::memcpy(s.image_of_h, b.image_of, (size_t)c.B * 4);
+  if (b.n_images) stage_table(ctx, b.n_images, b.image_of, s.image_of_h);
   if (b.bank_rows) std::memcpy(s.bank_idx_h, bidx.data(), 2 * (size_t)c.B * 4);
   if (b.pk_counts) {   // (before image_of is re-pointed: both arrays still are the caller's)
     fill_packed(c, b, s.pk_meta_h, s.nreg_h);
@@ -358,7 +389,7 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   b.tokens = s.tokens_h;
   b.lens = s.lens_p;
   b.labels = (b.labels || has_labels) ? s.labels_h : nullptr;
-  b.image_of = s.image_of_h;
+  b.image_of = b.img_block = s.image_of_h;
   b.bank_idx = b.bank_rows ? s.bank_idx_h : nullptr;
   b.bank_table = wants_table(ctx, b);
   b.utok = s.utok_h; b.ustart = s.ustart_h; b.upos = s.upos_h;
@@ -558,13 +589,20 @@ int rau_set_batch_images(rau_ctx* ctx, const void* feats, int feat_type, int n_i
 // rau_set_batch with the maps already in device memory (a producer in front of the library: rau_set_feat_grad).
 // One device-to-device copy on the chain stream, re-pitching where S % 4 != 0; the index arrays go through pinned
 // staging of the ctx (two halves, alternated like the hop weights'), so nothing here waits for the device.
-int rau_set_batch_dev(rau_ctx* ctx, const float* feats_dev, const int32_t* tokens, const int32_t* lens,
-                      const int32_t* labels) {
+// n_images > 0: feats_dev is an image table of that many maps and image_of names each sample's (rau_set_batch_dev_images).
+static int set_batch_dev(rau_ctx* ctx, const char* who, const float* feats_dev, int n_images, const int32_t* image_of,
+                         const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
   NEED(ctx && feats_dev && tokens && lens, "null argument");
-  if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_batch_dev: a step is being captured");
+  if (ctx->capturing) return fail(RAU_ERR_STATE, "%s: a step is being captured", who);
   const rau_config& c = ctx->cfg;
+  if (n_images != 0 || image_of)
+    if (int rc = check_table(c, n_images, image_of)) return rc;
   const size_t TBc = (size_t)c.T * ctx->cap, TB = (size_t)c.T * c.B, Bc = (size_t)ctx->cap;
-  const size_t words = TBc + 2 * Bc + TBc + (TBc + 1) + TBc;   // tokens | lens | labels | utok | ustart | upos
+  // tokens | lens | labels | utok | ustart | upos | a table's index block
+  const size_t words = TBc + 2 * Bc + TBc + (TBc + 1) + TBc + table_block_words(ctx);
+  const int si = ctx->cur_slot;
+  if (n_images)
+    if (int rc = ensure_table(ctx, si, false, false)) return rc;
   const int sl = (ctx->bdev_slot ^= 1);
   if (!ctx->bdev_h[sl]) {
     void* h = nullptr;
@@ -581,30 +619,57 @@ int rau_set_batch_dev(rau_ctx* ctx, const float* feats_dev, const int32_t* token
   int32_t* utok_h = lab_h + Bc;
   int32_t* ustart_h = utok_h + TBc;
   int32_t* upos_h = ustart_h + TBc + 1;
+  int32_t* img_h = upos_h + TBc;
   std::memcpy(tok_h, tokens, TB * 4);
   std::memcpy(lens_h, lens, (size_t)c.B * 4);
   if (labels) std::memcpy(lab_h, labels, (size_t)c.B * 4);
-  Batch b{nullptr, RAU_FEAT_F32, 0, nullptr, tok_h, lens_h, labels ? lab_h : nullptr, nullptr};
+  Batch b{nullptr, RAU_FEAT_F32, n_images, nullptr, tok_h, lens_h, labels ? lab_h : nullptr, nullptr};
   if (int rc = index_batch(c, b.tokens, b.lens, b.labels, utok_h, ustart_h, upos_h, &b.max_len, &b.nuniq)) return rc;
   b.utok = utok_h; b.ustart = ustart_h; b.upos = upos_h;
-  const int si = ctx->cur_slot;
+  if (n_images) {
+    stage_table(ctx, n_images, image_of, img_h);
+    b.image_of = b.img_block = img_h;
+  }
+  const size_t maps = n_images ? (size_t)n_images : (size_t)c.B;
   BatchSlot& s = ctx->slot[si];
   hipStream_t st = ctx->st;
   if (s.upload_pending) HIPC(hipStreamWaitEvent(st, s.uploaded, 0));   // an async upload into the same buffers
   if (ctx->Sp == c.S) {
-    HIPC(hipMemcpyAsync(s.feats, feats_dev, (size_t)c.B * c.D * c.S * 4, hipMemcpyDeviceToDevice, st));
+    HIPC(hipMemcpyAsync(s.feats, feats_dev, maps * c.D * c.S * 4, hipMemcpyDeviceToDevice, st));
   } else {
     // rows of S floats into rows of Sp; another element type's rows leave data in the pad columns: cleared first
     if (s.held.feat_type != RAU_FEAT_F32)
       HIPC(hipMemsetAsync(s.feats, 0, (size_t)c.B * c.D * ctx->Sp * sizeof(float), st));
     HIPC(hipMemcpy2DAsync(s.feats, (size_t)ctx->Sp * 4, feats_dev, (size_t)c.S * 4, (size_t)c.S * 4,
-                          (size_t)c.B * c.D, hipMemcpyDeviceToDevice, st));
+                          maps * c.D, hipMemcpyDeviceToDevice, st));
   }
   if (int rc = enqueue_batch(ctx, st, si, b)) return rc;   // (feats == NULL: the index arrays only)
   HIPC(hipEventRecord(ctx->bdev_ev[sl], st));
   s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
   hold(ctx, si, b);
   ctx->fwd_done = false;
+  return RAU_OK;
+}
+int rau_set_batch_dev(rau_ctx* ctx, const float* feats_dev, const int32_t* tokens, const int32_t* lens,
+                      const int32_t* labels) {
+  return set_batch_dev(ctx, "rau_set_batch_dev", feats_dev, 0, nullptr, tokens, lens, labels);
+}
+int rau_set_batch_dev_images(rau_ctx* ctx, const float* table_dev, int n_images, const int32_t* image_of,
+                             const int32_t* tokens, const int32_t* lens, const int32_t* labels) {
+  NEED(ctx, "null ctx");
+  NEED(image_of, "rau_set_batch_dev_images: null image_of");
+  return set_batch_dev(ctx, "rau_set_batch_dev_images", table_dev, n_images, image_of, tokens, lens, labels);
+}
+
+// host-only diagnostic: the lists stage_table builds, for the n_images images alone
+int rau_image_lists(int n, int n_images, const int32_t* image_of, int32_t* start, int32_t* samples) {
+  NEED(image_of && start && samples, "rau_image_lists: null argument");
+  NEED(n >= 1, "rau_image_lists: n=%d", n);
+  NEED(n_images >= 1 && n_images <= n, "rau_image_lists: n_images=%d out of [1,%d]", n_images, n);
+  for (int b = 0; b < n; ++b)
+    NEED(image_of[b] >= 0 && image_of[b] < n_images, "rau_image_lists: image_of[%d]=%d out of [0,%d)", b, image_of[b],
+         n_images);
+  image_lists(n, n_images, image_of, n_images, start, samples);
   return RAU_OK;
 }
 

@@ -103,14 +103,19 @@ struct BatchSlot {
   float* feats = nullptr;                                   // device, [B][D][Sp] (16-bit batch: its first half)
   int32_t *tokens = nullptr, *lens_d = nullptr, *labels_d = nullptr;
   int32_t *utok = nullptr, *ustart = nullptr, *upos = nullptr;
-  int32_t* image_of_d = nullptr;    // device [B], allocated at the slot's first table batch
+  // device, one block allocated at the slot's first table batch: image_of [cap] | img_start [cap + 1] |
+  // img_samples [cap].  The last two are the table's sample lists (rau_image_lists): image slot i owns
+  // img_samples[img_start[i] .. img_start[i + 1]), ascending; slots at and behind n_images are empty.  The per-image
+  // feature-map gradient reads them (xgrad.hip); a captured step holds their addresses, never their contents.
+  int32_t* image_of_d = nullptr;
+  int32_t *img_start_d = nullptr, *img_samples_d = nullptr;
   // bank_idx_d holds rows[n_images] (padded to B) and then rows[image_of[b]] for every sample, so both gathers
   // of a bank batch are one indexed copy
   int32_t* bank_idx_d = nullptr;    // device [2B], allocated at the slot's first bank batch
   float* feats_h = nullptr;                                 // pinned host, dense [B][D][S] (16-bit: first half)
   int32_t *tokens_h = nullptr, *lens_p = nullptr, *labels_h = nullptr;
   int32_t *utok_h = nullptr, *ustart_h = nullptr, *upos_h = nullptr;
-  int32_t* image_of_h = nullptr;    // pinned host [B]
+  int32_t* image_of_h = nullptr;    // pinned host, the device block's layout (3 * cap + 1 words)
   int32_t* bank_idx_h = nullptr;    // pinned host [2B]
   // answer set of the batch: ids | w | score, each [B][G] dense in the current size and G, room for
   // [capacity][kMaxAnswers]; one device block and one pinned block, allocated at the slot's first set
@@ -236,7 +241,8 @@ struct StepKey {
   // ... and under RAU_XDROP_TIED a train-mode step has one masked map, one conv group and the summed conv gradients
   bool tied_x = false;
   int ans_loss = 0;             // ... and the head kernel is the answer criterion's (rau_set_answer_loss)
-  bool feat_grad = false;       // ... and with rau_set_feat_grad the conv gradients are followed by the feature-map gradient
+  int feat_grad = 0;            // ... and with rau_set_feat_grad the conv gradients are followed by the feature-map
+                                // gradient: the mode (per sample / per image of a table: another accumulate kernel)
   auto tied() const {
     return std::tie(mode, max_len, active, zero, mexplicit[0], mexplicit[1], mexplicit[2], mexplicit[3], mexplicit[4],
                     slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg, tied_x, ans_loss,
@@ -339,8 +345,9 @@ struct rau_ctx {
   const float* x_shared = nullptr;  // ... and i_embed's input then: xd (the one masked map) or, without a mask, xw
   float* dS_sum = nullptr;          // [cap][A][Sp] sum of the active hops' dS (tied_bwd.hip), allocated with the switch
   // feature-map gradient (rau_set_feat_grad, xgrad.hip): off = the step path as it is without it
-  bool feat_grad = false;
+  int feat_grad = RAU_FEAT_GRAD_OFF;   // the mode: _SAMPLES, or _IMAGES = per image where the batch has a table
   float* xg_dX = nullptr;           // [cap][D][Sp] the last backward's result, allocated with the switch
+  int xg_rows = 0;                  // ... its map count: n, or the table's N under RAU_FEAT_GRAD_IMAGES
   float* xg_tmp = nullptr;          // [cap][D][Sp] one hop's unmasked product (the unfused path)
   float* xg_dz = nullptr;           // [cap][M][Sp] dI (1 - I^2) where the dgrad left dI (no fused tanh derivative)
   bool xg_first = false;            // no launch of the running backward has written xg_dX yet: the next one stores
@@ -432,6 +439,12 @@ struct rau_ctx {
 // The resident batch: what every reader of the batch goes through.
 inline BatchSlot& cur_batch(rau_ctx* ctx) { return ctx->slot[ctx->cur_slot]; }
 inline const BatchSlot& cur_batch(const rau_ctx* ctx) { return ctx->slot[ctx->cur_slot]; }
+// The resident batch's feature-map gradient is formed per IMAGE: RAU_FEAT_GRAD_IMAGES on an image table.  (A bank
+// batch has no gradient in either mode; on a batch with one map per sample the mode is RAU_FEAT_GRAD_SAMPLES.)
+inline bool xgrad_per_image(const rau_ctx* ctx) {
+  const BatchDesc& d = cur_batch(ctx).held;
+  return ctx->feat_grad == RAU_FEAT_GRAD_IMAGES && d.n_images > 0 && !d.bank;
+}
 
 // Effective drop probability of a mask site.  Masks the device draws itself (Philox, 8-bit draws)
 // drop with p quantised to 1/256 and scale by 1/(1-pq), so that E[mask * scale] = 1 exactly;

@@ -793,9 +793,12 @@ int rau_feat_dropout(rau_ctx* ctx, int* kind) {
 
 // ------------------------------------------------- feature-map gradient
 // The backward reads ctx->feat_grad (group_conv_grads: one more block of launches per conv group on the bulk
-// stream) and the graph key carries it; nothing else depends on the switch.
+// stream) and the graph key carries it.  Under RAU_FEAT_GRAD_IMAGES an image-table batch takes the per-image
+// accumulate pass (xgrad_per_image: feat_grad_hops) and, in evaluate mode, the gathered forward (rau_forward).
 int rau_set_feat_grad(rau_ctx* ctx, int on) {
   NEED(ctx, "null ctx");
+  NEED(on == RAU_FEAT_GRAD_OFF || on == RAU_FEAT_GRAD_SAMPLES || on == RAU_FEAT_GRAD_IMAGES,
+       "rau_set_feat_grad: mode %d is none of RAU_FEAT_GRAD_OFF, _SAMPLES, _IMAGES", on);
   if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_feat_grad: a step is being captured");
   if (on) {
     // for the capacity, at the first use (never inside a captured step); cleared by rau_set_batch_size like every
@@ -811,13 +814,14 @@ int rau_set_feat_grad(rau_ctx* ctx, int on) {
     if (!ctx->xg_dz)
       if (int rc = dalloc(ctx, &ctx->xg_dz, (size_t)ctx->cap * c.M * ctx->Sp)) return rc;
   }
-  if ((on != 0) != ctx->feat_grad) ctx->xg_valid = false;
-  ctx->feat_grad = on != 0;
+  // (a forward that ran under another mode stays differentiable or refused on its own record: fwd_table)
+  if (on != ctx->feat_grad) ctx->xg_valid = false;
+  ctx->feat_grad = on;
   return RAU_OK;
 }
 int rau_feat_grad(rau_ctx* ctx, int* on) {
   NEED(ctx && on, "null argument");
-  *on = ctx->feat_grad ? 1 : 0;
+  *on = ctx->feat_grad;
   return RAU_OK;
 }
 static int feat_grad_state(rau_ctx* ctx, const char* fn) {
@@ -832,11 +836,18 @@ int rau_feat_grad_dev(rau_ctx* ctx, const float** dX, int32_t* pitch) {
   if (pitch) *pitch = ctx->Sp;
   return RAU_OK;
 }
+int rau_feat_grad_rows(rau_ctx* ctx, int32_t* rows) {
+  NEED(ctx && rows, "null argument");
+  if (int rc = feat_grad_state(ctx, "rau_feat_grad_rows")) return rc;
+  *rows = ctx->xg_rows;
+  return RAU_OK;
+}
 int rau_get_feat_grad(rau_ctx* ctx, float* host) {
   NEED(ctx && host, "null argument");
   if (int rc = feat_grad_state(ctx, "rau_get_feat_grad")) return rc;
   const rau_config& c = ctx->cfg;
-  HIPC(hipMemcpy2DAsync(host, (size_t)c.S * 4, ctx->xg_dX, (size_t)ctx->Sp * 4, (size_t)c.S * 4, (size_t)c.B * c.D,
+  HIPC(hipMemcpy2DAsync(host, (size_t)c.S * 4, ctx->xg_dX, (size_t)ctx->Sp * 4, (size_t)c.S * 4,
+                        (size_t)ctx->xg_rows * c.D,
                         hipMemcpyDeviceToHost, ctx->st));
   HIPC(hipStreamSynchronize(ctx->st));
   return persist_check(ctx);
@@ -1547,7 +1558,9 @@ int rau_forward(rau_ctx* ctx) {
   // i_embed and the attention pre-activation run once per IMAGE and the attention kernels read sample b's
   // tiles at row image_of[b].  Everywhere else (train mode: per-sample masks; a captured step: its backward
   // needs per-sample I) the table is gathered into per-sample maps first and the plain path runs on those.
-  const bool table_fwd = bs.held.n_images > 0 && ctx->I_shared && ctx->mode == RAU_MODE_EVAL && !ctx->capturing;
+  // (Nor under RAU_FEAT_GRAD_IMAGES: the per-image gradient differentiates per-sample I.  Same output bits.)
+  const bool table_fwd = bs.held.n_images > 0 && ctx->I_shared && ctx->mode == RAU_MODE_EVAL && !ctx->capturing &&
+                         !xgrad_per_image(ctx);
   const int nX = table_fwd ? bs.held.n_images : B;   // maps the image-side passes read
   const int32_t* img = table_fwd ? bs.image_of_d : nullptr;
   const float* feats = bs.feats;
@@ -1747,6 +1760,8 @@ static int loss_gradients(rau_ctx* ctx, const StepLoss& loss, const Truth& t) {
 // dz: hop h0's [B][M][Sp] block, nh of them; is_dI: it holds the gradient at i_embed's OUTPUT (the dgrad without
 // the fused tanh derivative), I the matching activations (I_stride floats from hop to hop, 0 = shared).
 // mask_hop: the first hop's slice of the mask site (tied: 0), mask_step hops per hop (tied, no mask: 0).
+// RAU_FEAT_GRAD_IMAGES on an image table (xgrad_per_image): the same products, added per image into xg_dX as
+// [slots][D][Sp] in the order of the slot's sample lists; launched over the capacity's slots, whatever N is.
 static int feat_grad_hops(rau_ctx* ctx, hipStream_t sb, int nh, const void* dz, bool dz_is_b16, bool is_dI,
                           const float* I, size_t I_stride, int mask_hop, int mask_step) {
   const rau_config& c = ctx->cfg;
@@ -1760,7 +1775,9 @@ static int feat_grad_hops(rau_ctx* ctx, hipStream_t sb, int nh, const void* dz, 
   xm.thr = (uint32_t)lroundf(ctx->mp[RAU_MASK_X] * 256.0f);
   xm.scale = m.x ? m.s_x : 1.f;
   const double fl = gflop(D, (double)B * S, M), by = ((double)B * M * S + (double)B * D * S) * 4;
-  if (!dz_is_b16 && !is_dI && !ctx->bf16 && xgrad_fused_ok(D, M, S) && S == SL) {
+  const bool per_image = xgrad_per_image(ctx);   // (never fused: that kernel owns one sample's tile)
+  const BatchSlot& bs = cur_batch(ctx);
+  if (!per_image && !dz_is_b16 && !is_dI && !ctx->bf16 && xgrad_fused_ok(D, M, S) && S == SL) {
     xm.e0 = (size_t)mask_hop * xm.hop_stride;
     if (!mask_step) xm.hop_stride = 0;
     RUNS(sb, "conv_embed_dgrad", nh * fl, (double)nh * B * M * S * 4 + (double)B * D * S * (ctx->xg_first ? 4 : 8),
@@ -1778,8 +1795,14 @@ static int feat_grad_hops(rau_ctx* ctx, hipStream_t sb, int nh, const void* dz, 
     RUNS(sb, "conv_embed_dgrad", fl, by,
          conv_embed_dgrad_mode(sb, B, D, S, M, dzk, dz_is_b16 ? 1 : 0, ctx->i_embed.W, ctx->xg_tmp, ctx->bf16));
     xm.e0 = (size_t)(mask_hop + k * mask_step) * xm.hop_stride;
-    RUNS(sb, "xgrad_accum", 2.0 * B * D * S, (double)B * D * S * (ctx->xg_first ? 8 : 12),
-         xgrad_accum(sb, (size_t)B * D, SL, S, ctx->xg_tmp, ctx->xg_dX, xm, ctx->xg_first ? 1 : 0));
+    if (per_image)
+      RUNS(sb, "xgrad_accum_img", 2.0 * B * D * S,
+           ((double)B * 4 + (double)bs.held.n_images * (ctx->xg_first ? 4 : 8)) * D * S,
+           xgrad_accum_img(sb, ctx->cap, D, SL, S, ctx->xg_tmp, ctx->xg_dX, bs.img_start_d, bs.img_samples_d, xm,
+                           ctx->xg_first ? 1 : 0));
+    else
+      RUNS(sb, "xgrad_accum", 2.0 * B * D * S, (double)B * D * S * (ctx->xg_first ? 8 : 12),
+           xgrad_accum(sb, (size_t)B * D, SL, S, ctx->xg_tmp, ctx->xg_dX, xm, ctx->xg_first ? 1 : 0));
     ctx->xg_first = false;
   }
   return RAU_OK;
@@ -1967,7 +1990,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
                 "i_embed once per image, so there is no per-sample I to differentiate; take evaluate-mode "
                 "gradients on a plain batch (rau_set_batch)");
   const BatchSlot& bs = cur_batch(ctx);
-  if (ctx->feat_grad && bs.held.n_images > 0)
+  if (ctx->feat_grad && bs.held.n_images > 0 && !xgrad_per_image(ctx))
     return fail(RAU_ERR_STATE, "rau_backward: the feature-map gradient (rau_set_feat_grad) of a batch with an image "
                 "table or bank rows is a sum over the questions of an image, which is not formed; expand the maps "
                 "per sample (rau_set_batch_dev) or turn the switch off");
@@ -2070,7 +2093,8 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
     RUN("dq_reduce", 0, (double)HA * B * Q * 4,
         dq_reduce(st, HA, (size_t)B * Q, ctx->dQD, m.q, m.s_q, ctx->dq));
   }
-  if (ctx->feat_grad && ctx->xg_first)   // no active hop: the gradient is zero
+  // no active hop: the gradient is zero (n rows: all of a table's N <= n too, whichever N a replay meets)
+  if (ctx->feat_grad && ctx->xg_first)
     HIPC(hipMemsetAsync(ctx->xg_dX, 0, (size_t)B * c.D * S * sizeof(float), ctx->st2));
   // bulk stream tail: the join event (the i_embed bias gradient comes out of conv_embed_wgrad:
   // row sums of its staged dZ operand)
@@ -2101,7 +2125,8 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   HIPC(hipEventRecord(ctx->evEnd, st));
   ctx->bwd_done = true;
   ctx->graph_last = false;
-  ctx->xg_valid = ctx->feat_grad;
+  ctx->xg_valid = ctx->feat_grad != RAU_FEAT_GRAD_OFF;
+  ctx->xg_rows = xgrad_per_image(ctx) ? cur_batch(ctx).held.n_images : ctx->cfg.B;
   return RAU_OK;
 }
 
@@ -2214,7 +2239,7 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
   if (!bs.held.have || !bs.held.have_labels)
     return fail(RAU_ERR_STATE, "rau_graph_step: needs a batch with labels (rau_set_batch)");
   if (ctx->prof_on) return fail(RAU_ERR_STATE, "rau_graph_step: profiling must be off");
-  if (ctx->feat_grad && bs.held.n_images > 0)
+  if (ctx->feat_grad && bs.held.n_images > 0 && !xgrad_per_image(ctx))
     return fail(RAU_ERR_STATE, "rau_graph_step: the feature-map gradient (rau_set_feat_grad) of a batch with an image "
                 "table or bank rows is not formed; expand the maps per sample (rau_set_batch_dev)");
   StepKey key;
@@ -2276,7 +2301,8 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
   ctx->fwd_done = false;
   ctx->bwd_done = true;
   ctx->graph_last = true;
-  ctx->xg_valid = ctx->feat_grad;
+  ctx->xg_valid = ctx->feat_grad != RAU_FEAT_GRAD_OFF;
+  ctx->xg_rows = xgrad_per_image(ctx) ? cur_batch(ctx).held.n_images : ctx->cfg.B;
   return RAU_OK;
 }
 

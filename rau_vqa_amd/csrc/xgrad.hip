@@ -18,6 +18,26 @@
 //                  peak where the per-sample GEMM runs at 0.53, and loses to the unfused path by 0.39 ms per step at
 //                  configs[1]: a concluded negative, kept behind the knob with its tests.
 //
+//   k_xgrad_accum_img  RAU_FEAT_GRAD_IMAGES on an image-table batch: the accumulate pass per IMAGE.  It reads the same
+//                  per-sample product G [B][D][Sp] and writes dT [slots][D][Sp], dT[i] (=, +=) the terms of the
+//                  samples that name image i, in ascending sample order.  A workgroup owns (one image slot, 16
+//                  channel rows): the image's sample list -- a CSR pair in device memory, built by the batch code
+//                  with a stable counting sort -- is uniform over the workgroup and read through scalar loads, and
+//                  every access to G and dT is a 16-byte one over a contiguous run of quads.  The launch covers
+//                  every image slot of the CAPACITY and reads the lists from memory, so neither the geometry nor an
+//                  argument depends on N or on image_of: a captured step replays on any later table batch.  A slot
+//                  without samples (an unnamed image, a slot behind N) is written with zeros by the backward's
+//                  first launch and left alone by the others.  Per launch 4 B D S + (4 or 8) N D S bytes instead
+//                  of (8 or 12) B D S.
+//                  Regenerated bits are drawn per QUAD (philox_keep16 of the quad's 16-element block, its nibble),
+//                  the generic k_xgrad_accum<2>'s form, not with k_xgrad_accum_gen's wave-cooperative draw.  That
+//                  draw needs runs that start on a 16-element block and hold a multiple of four quads; a workgroup's
+//                  run here starts at element (b D + d0) S for each sample b of its list, which is on a block only
+//                  where D S % 16 == 0, so the per-quad form would have to stay as the fallback anyway.  Drawing a
+//                  block four times costs about 80 integer instructions per 16-byte quad and sample, arithmetic
+//                  that hides behind the pass's memory traffic.  The bits are the contract: the same function of
+//                  (seed, site, step, element) either way.
+//
 // Keep bits: read from the site's bit-packed mask where it is in memory (caller-supplied, or filled by fill_masks),
 // regenerated with philox_keep16 from the same (seed, site, step, element) where the forward drew them inside its
 // dropout pass (philox.h: the backward regenerates).  They are never inferred from the masked map: a zero feature
@@ -114,6 +134,60 @@ __global__ void k_xgrad_accum_gen(size_t n16, const float4* __restrict__ G, floa
       o.w += (nib & 8u) ? g.w * m.scale : 0.f;
       dX[q] = o;
     }
+  }
+}
+
+// The per-image form of k_xgrad_accum (file header).  grid = (ceil(D / XIMG_ROWS), image slots); the arithmetic per
+// term is k_xgrad_accum's -- keep ? g * scale : 0 rounded once, then added -- with the mask indexed by SAMPLE.
+constexpr int XIMG_ROWS = 16;
+template <int KIND>
+__global__ __launch_bounds__(256) void k_xgrad_accum_img(int D, int SL, int Sp, const float4* __restrict__ G,
+                                                         float4* __restrict__ dT,
+                                                         const int32_t* __restrict__ img_start,
+                                                         const int32_t* __restrict__ img_samples, const XMask m,
+                                                         int store) {
+  const int img = blockIdx.y;
+  const int beg = img_start[img], end = img_start[img + 1];
+  if (beg >= end && !store) return;   // nothing to add: the stored value stands
+  uint64_t seed = m.seed;
+  uint32_t step = m.step;
+  if (KIND == 2 && m.key) {
+    seed = m.key[0];
+    step = (uint32_t)m.key[1];
+  }
+  const int qpr = Sp >> 2;
+  const int d0 = blockIdx.x * XIMG_ROWS;
+  const int nq = min(XIMG_ROWS, D - d0) * qpr;
+  float4* out = dT + ((size_t)img * D + d0) * qpr;
+  for (int ql = threadIdx.x; ql < nq; ql += blockDim.x) {
+    const int dr = ql / qpr;
+    const int s = (ql - dr * qpr) * 4;
+    // positions of this quad that exist (pad columns of a pitched map do not)
+    const uint32_t valid = s + 4 <= SL ? 0xFu : s < SL ? (1u << (SL - s)) - 1u : 0u;
+    float4 o = store ? make_float4(0.f, 0.f, 0.f, 0.f) : out[ql];
+    for (int j = beg; j < end; ++j) {
+      const size_t r = (size_t)img_samples[j] * D + d0 + dr;   // the sample's row of G and of the logical mask
+      uint32_t nib;
+      if (KIND == 1 && SL != Sp) {   // the mask is indexed over the logical [.., SL] tensor
+        nib = 0;
+        for (int i = 0; i < 4; ++i)
+          if (s + i < SL) nib |= mask_bit(m.bits, m.e0 + r * SL + s + i) << i;
+      } else {
+        nib = keep_nib<KIND>(m, seed, step, m.e0 + r * SL + s) & valid;
+      }
+      const float4 g = G[r * qpr + (s >> 2)];
+      o.x += (nib & 1u) ? g.x * m.scale : 0.f;
+      o.y += (nib & 2u) ? g.y * m.scale : 0.f;
+      o.z += (nib & 4u) ? g.z * m.scale : 0.f;
+      o.w += (nib & 8u) ? g.w * m.scale : 0.f;
+    }
+    if (!valid) o = make_float4(0.f, 0.f, 0.f, 0.f);
+    else if (valid != 0xFu) {
+      if (!(valid & 2u)) o.y = 0.f;
+      if (!(valid & 4u)) o.z = 0.f;
+      if (!(valid & 8u)) o.w = 0.f;
+    }
+    out[ql] = o;
   }
 }
 
@@ -300,6 +374,23 @@ hipError_t xgrad_accum(hipStream_t st, size_t rows, int SL, int Sp, const float*
   } else if (m.kind == 2) hipLaunchKernelGGL(k_xgrad_accum<2>, grid, block, 0, st, rows, SL, Sp, G4, X4, m, store);
   else if (m.kind == 1) hipLaunchKernelGGL(k_xgrad_accum<1>, grid, block, 0, st, rows, SL, Sp, G4, X4, m, store);
   else hipLaunchKernelGGL(k_xgrad_accum<0>, grid, block, 0, st, rows, SL, Sp, G4, X4, m, store);
+  return hipGetLastError();
+}
+
+hipError_t xgrad_accum_img(hipStream_t st, int slots, int D, int SL, int Sp, const float* G, float* dT,
+                           const int32_t* img_start, const int32_t* img_samples, const XMask& m, int store) {
+  if (Sp % 4 != 0 || SL > Sp || (m.kind == 2 && (SL != Sp || m.e0 % 4 != 0)) || (m.kind == 1 && SL == Sp && m.e0 % 4 != 0))
+    return hipErrorInvalidValue;
+  if (slots < 1 || slots > 65535 || D < 1 || !img_start || !img_samples) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((D + XIMG_ROWS - 1) / XIMG_ROWS), (unsigned)slots), block(256);
+  const float4* G4 = reinterpret_cast<const float4*>(G);
+  float4* T4 = reinterpret_cast<float4*>(dT);
+  if (m.kind == 2)
+    hipLaunchKernelGGL(k_xgrad_accum_img<2>, grid, block, 0, st, D, SL, Sp, G4, T4, img_start, img_samples, m, store);
+  else if (m.kind == 1)
+    hipLaunchKernelGGL(k_xgrad_accum_img<1>, grid, block, 0, st, D, SL, Sp, G4, T4, img_start, img_samples, m, store);
+  else
+    hipLaunchKernelGGL(k_xgrad_accum_img<0>, grid, block, 0, st, D, SL, Sp, G4, T4, img_start, img_samples, m, store);
   return hipGetLastError();
 }
 

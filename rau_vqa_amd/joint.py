@@ -246,3 +246,26 @@ def merged_ce_grad(logits, dopred, labels=None, answers=None, merge_w=(0.0, 0.0)
         fired = np.nonzero(hsel >= 0)[0]
         out[hsel[fired], fired] += g_s[fired]
     return out
+
+
+def image_hop_sum(G, keep, p, S, Sp, image_of, n_images, order=None):
+    """The per-image feature-map gradient dT [n_images, D, Sp] float32 (rau_set_feat_grad, RAU_FEAT_GRAD_IMAGES) from
+    the per-hop, per-sample products G [HA, n, D, Sp] (pad columns of any content), the keep bits keep [HA, n, D, S]
+    over the LOGICAL tensor, indexed by SAMPLE (None: no mask, scale 1) and the drop probability p.  The device's
+    arithmetic: the hops in `order` (default ascending); per hop the accumulator starts at +0 (the first hop) or at
+    the stored value, an image's samples are taken in ascending b, each term keep ? G * s_x : 0 rounded once to
+    float32 and then added.  An image no sample names stays exactly zero; pad columns are zero."""
+    G = np.asarray(G, np.float32)
+    HA, n, D, _ = G.shape
+    image_of = np.asarray(image_of, np.int64)
+    if image_of.shape != (n,) or (n and (image_of.min() < 0 or image_of.max() >= n_images)):
+        raise ValueError(f"image_of must be [{n}] with entries in [0, {n_images})")
+    s_x = np.float32(1.0) if keep is None else np.float32(1.0 / (1.0 - p))
+    out = np.zeros((n_images, D, Sp), np.float32)
+    for h in (range(HA) if order is None else order):
+        for b in range(n):
+            term = G[h, b, :, :S] * s_x
+            if keep is not None:
+                term = np.where(np.asarray(keep[h][b]).reshape(D, S) != 0, term, np.float32(0))
+            out[image_of[b], :, :S] += term
+    return out

@@ -807,41 +807,58 @@ class RAU:
                 device_view(dp.value, H * n, dev).view(H, n),
                 device_view(at.value, H * n * pitch.value, dev).view(H, n, pitch.value)[:, :, :S])
 
-    def want_feature_grad(self, on=True):
+    def want_feature_grad(self, on=True, per_image=False):
         """Every step-level backward (backward, graph_step) also leaves the gradient at the feature map behind
         (rau_set_feat_grad): feature_grad() / feature_grad_tensor().  Off (the default) the step is what it was.
-        Batches with one map per sample only: with the switch on, the backward of an image-table or bank batch
-        raises; expand shared images on the caller's side (x[image_of]) in front of set_batch_dev."""
-        L.check(self._lib.rau_set_feat_grad(self._h, 1 if on else 0))
+        per_image=False (RAU_FEAT_GRAD_SAMPLES): batches with one map per sample only; the backward of an
+        image-table or bank batch raises.  per_image=True (RAU_FEAT_GRAD_IMAGES): the backward of an image-table
+        batch leaves the gradient at the TABLE, [N,D,S] -- each image's samples summed in ascending order, no
+        atomics, an unnamed image exactly zero; every other batch as with per_image=False; bank batches still raise."""
+        mode = L.FEAT_GRAD_OFF if not on else L.FEAT_GRAD_IMAGES if per_image else L.FEAT_GRAD_SAMPLES
+        L.check(self._lib.rau_set_feat_grad(self._h, mode))
 
     @property
     def feature_grad_wanted(self) -> bool:
+        return self.feature_grad_mode != L.FEAT_GRAD_OFF
+
+    @property
+    def feature_grad_mode(self) -> int:
+        """0 = off, 1 = per sample, 2 = per image where the batch has an image table (rau_feat_grad)."""
         on = C.c_int(0)
         L.check(self._lib.rau_feat_grad(self._h, C.byref(on)))
-        return bool(on.value)
+        return int(on.value)
+
+    def feature_grad_rows(self) -> int:
+        """The map count of the last backward's feature-map gradient (rau_feat_grad_rows): the batch size n, or the
+        table's N where it was formed per image."""
+        rows = C.c_int32(0)
+        L.check(self._lib.rau_feat_grad_rows(self._h, C.byref(rows)))
+        return int(rows.value)
 
     def feature_grad(self):
-        """The last backward's feature-map gradient [n,D,S] (numpy; synchronises)."""
-        out = np.empty((self._n, self.cfg.D, self.cfg.S), np.float32)
+        """The last backward's feature-map gradient [rows,D,S] (numpy; synchronises); rows = feature_grad_rows()."""
+        out = np.empty((self.feature_grad_rows(), self.cfg.D, self.cfg.S), np.float32)
         L.check(self._lib.rau_get_feat_grad(self._h, out.ctypes.data))
         return out
 
     def feature_grad_tensor(self):
-        """Zero-copy torch view [n,D,S] of the last backward's feature-map gradient in device memory
+        """Zero-copy torch view [rows,D,S] of the last backward's feature-map gradient in device memory
         (rau_feat_grad_dev) -- strided where the maps are pitched (S % 4 != 0).  Valid until the next forward or
         set_batch_size, ordered on the ctx's stream (stream()), read-only."""
         from .dist import device_view
         p, pitch = C.c_void_p(), C.c_int32()
         L.check(self._lib.rau_feat_grad_dev(self._h, C.byref(p), C.byref(pitch)))
-        n, D, S, dev = self._n, self.cfg.D, self.cfg.S, self.cfg.device_id
+        n, D, S, dev = self.feature_grad_rows(), self.cfg.D, self.cfg.S, self.cfg.device_id
         return device_view(p.value, n * D * pitch.value, dev).view(n, D, pitch.value)[:, :, :S]
 
-    def set_batch_dev(self, feats_cuda, tokens, lens, labels=None, answers=None, regions=None, att_targets=None):
+    def set_batch_dev(self, feats_cuda, tokens, lens, labels=None, answers=None, regions=None, att_targets=None,
+                      image_of=None):
         """set_batch with the maps already on the device: feats_cuda a contiguous float32 CUDA torch tensor
         [n,D,S] on the ctx's device (rau_set_batch_dev: one copy on the ctx's stream, no host synchronisation).
         The ctx's stream must be ordered behind the stream that wrote the tensor (autograd.step's docstring shows
         the two lines); the tensor must stay unchanged until that copy has run.  answers, regions, att_targets as
-        in set_batch."""
+        in set_batch.  image_of [n] (0-based rows): feats_cuda is an image TABLE [N,D,S] (rau_set_batch_dev_images);
+        regions may then be per image [N]."""
         import torch
         c = self.cfg
         lens = np.ascontiguousarray(lens, np.int32)
@@ -851,7 +868,11 @@ class RAU:
             raise ValueError("feats_cuda must be a contiguous float32 CUDA torch tensor")
         if t.device.index != c.device_id:
             raise ValueError(f"feats_cuda is on {t.device}, the context on cuda:{c.device_id}")
-        if tuple(t.shape) != (B, c.D, c.S):
+        if image_of is not None:
+            image_of = np.ascontiguousarray(image_of, np.int32)
+            if image_of.shape != (B,) or t.dim() != 3 or tuple(t.shape[1:]) != (c.D, c.S) or t.shape[0] < 1:
+                raise ValueError(f"an image table needs image_of [{B}] and feats_cuda [N, {c.D}, {c.S}]")
+        elif tuple(t.shape) != (B, c.D, c.S):
             raise ValueError(f"feats_cuda has shape {tuple(t.shape)}, expected {(B, c.D, c.S)}")
         tokens = np.ascontiguousarray(tokens, np.int32)
         if tokens.shape != (c.T, B):
@@ -863,12 +884,16 @@ class RAU:
                 raise ValueError("labels shape")
             lp = labels.ctypes.data
         if regions is not None:
-            regions = self._sample_regions(regions, None, B)
+            regions = self._sample_regions(regions, image_of, B)
         if att_targets is not None:
             att_targets = self._att_targets(att_targets, B)
         if B != self._n:
             self.set_batch_size(B)
-        L.check(self._lib.rau_set_batch_dev(self._h, t.data_ptr(), tokens.ctypes.data, lens.ctypes.data, lp))
+        if image_of is not None:
+            L.check(self._lib.rau_set_batch_dev_images(self._h, t.data_ptr(), int(t.shape[0]), image_of.ctypes.data,
+                                                       tokens.ctypes.data, lens.ctypes.data, lp))
+        else:
+            L.check(self._lib.rau_set_batch_dev(self._h, t.data_ptr(), tokens.ctypes.data, lens.ctypes.data, lp))
         if answers is not None:
             self.set_answers(*answers)
         if regions is not None:
