@@ -116,6 +116,10 @@ int rau_feat_grad_dev(rau_ctx* ctx, const float** dX, int32_t* pitch);
 int rau_feat_grad_rows(rau_ctx* ctx, int32_t* rows);
 int rau_get_feat_grad(rau_ctx* ctx, float* host);
 int rau_set_batch_dev(rau_ctx* ctx, const float* feats_dev, const int32_t* tokens, const int32_t* lens, const int32_t* labels);
+int rau_set_question_dev(rau_ctx* ctx, const void* q_dev, int q_type);
+int rau_batch_question(rau_ctx* ctx, int* has);
+int rau_question_grad_dev(rau_ctx* ctx, const float** dq);
+int rau_get_question_grad(rau_ctx* ctx, float* host);
 int rau_set_batch_dev_images(rau_ctx* ctx, const float* table_dev, int n_images, const int32_t* image_of,
                              const int32_t* tokens, const int32_t* lens, const int32_t* labels);
 int rau_outputs_dev(rau_ctx* ctx, const float** logits, const float** dopred, const float** attprob,
@@ -603,6 +607,30 @@ end
 function RAU:setBatchDev(feats_dev, x, x_len, y)
   follow_rows(self, x_len)
   check(C.rau_set_batch_dev(self.h, feats_dev, x:data(), x_len:data(), y and y:data() or nil))
+end
+-- Question state from the caller (rau_set_question_dev): q a DEVICE pointer to dense [n,Q] (Q = 4 Rq) elements of
+-- qtype 'f32' (default), 'f16' or 'bf16', ordered by the caller in front of the ctx's stream.  It attaches to the
+-- resident batch: forward / graphStep then read it in place of the built-in encoder's output and launch nothing of
+-- the encoder, the backward leaves questionGrad() behind and does not touch the embed and rnn gradients.  q == nil
+-- detaches it, and so does the next setBatch* / useBatch / setBatchSize.
+RAU.QUESTION_TYPES = {f32 = 0, f16 = 1, bf16 = 2}
+function RAU:setQuestionDev(q, qtype)
+  local t = RAU.QUESTION_TYPES[qtype or 'f32']
+  assert(t, 'setQuestionDev: qtype is one of f32, f16, bf16')
+  check(C.rau_set_question_dev(self.h, q, t))
+  return self
+end
+function RAU:batchQuestion()
+  local has = ffi.new('int[1]')
+  check(C.rau_batch_question(self.h, has))
+  return has[0] ~= 0
+end
+-- the last backward's gradient at the attached question in device memory: const float* cdata [n,Q]
+-- (rau_question_grad_dev); valid until the next forward, ordered on the ctx's stream
+function RAU:questionGrad()
+  local p = ffi.new('const float*[1]')
+  check(C.rau_question_grad_dev(self.h, p))
+  return p[0]
 end
 -- setBatchImages with the table already on the device: table_dev a DEVICE float* to dense [n_images,D,S] float32,
 -- image_of an IntTensor [B] of 1-BASED table rows (rau_set_batch_dev_images)

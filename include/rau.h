@@ -776,6 +776,64 @@ int rau_set_batch_dev_images(rau_ctx* ctx, const float* table_dev /* [N,D,S] f32
                              const int32_t* image_of /* host [n] */, const int32_t* tokens, const int32_t* lens,
                              const int32_t* labels);
 
+/* ---- question state from the caller: the step path behind another question encoder ------------------------------
+ * The step path's own encoder is the reference's (LookupTable, two-layer LSTM, length select); its output q [n,Q] is
+ * the only thing the hops read of it, and dq [n,Q] the only thing its backward reads of the hops.  These calls make
+ * that boundary public for a caller whose encoder is something else (a language model, a GRU, an adapter over cached
+ * text features).  No new GEMM or attention kernel is involved: the device work is one copy or widening pass, the
+ * hot path is the existing hop chain, launch for launch.
+ *   layout       Q = 4 * Rq.  q_dev is [n,Q] dense in DEVICE memory, n the current batch size (rau_set_batch_size).
+ *                The library does not interpret the four quarters (in the built-in encoder they are [c1 h1 c2 h2]).
+ *   type         q_type is RAU_FEAT_F32, RAU_FEAT_F16 or RAU_FEAT_BF16 (an encoder under autocast hands its output
+ *                over as it is).  Widening is exact: the result is bit-identical to the f32 question that holds the
+ *                widened values.  The fp8 types and unknown values: RAU_ERR_INVALID.
+ *   attaching    rau_set_question_dev attaches q to the RESIDENT batch, as rau_set_answers and rau_set_regions attach
+ *                theirs: one copy (f32) or widening pass (16-bit) on the ctx's stream into a ctx-owned [capacity,Q]
+ *                f32 buffer.  No host wait, no synchronisation.  The caller orders its producer in front of
+ *                rau_stream and keeps q_dev unchanged until the copy has run (rau_set_batch_dev's rule).  The tokens
+ *                and lens the batch was uploaded with are ignored by a step while a question is attached.  The
+ *                attached question survives any number of forwards.  Attaching again replaces the contents: the
+ *                per-step call of a training loop.  A forward that ran before the call has no backward (run it again).
+ *   detaching    q_dev == NULL detaches the question and returns the batch to the built-in encoder.  Every call that
+ *                makes another batch current detaches it too: rau_set_batch* (every form, the asynchronous ones when
+ *                they fill the current slot), rau_use_batch, and a rau_set_batch_size that changes the size (it drops
+ *                the batch).  rau_batch_question reports whether the resident batch has one.
+ *   forward      with a question attached rau_forward and every rau_graph_step* read q from that buffer; they launch
+ *                nothing of the encoder (embed_fwd, enc_i2h_gemm, enc_h2h_gemm, its lstm_fwd cells or enc_ws) and no
+ *                gather_q; the attention LSTM's lstm_fwd / lstm_bwd of every hop stay.
+ *                Every other launch is the built-in path's, with its bits, in train and evaluate mode.
+ *                rau_get_question_state returns the attached q.  Seeded dropout: under the same (seed, step) the keep
+ *                bits of the q, x and mf sites are the built-in path's; the we and rnn sites are not consumed.
+ *   backward     every step-level backward (rau_backward, _select, _att, _merged, _ext, the captured steps) runs the
+ *                hop chain and dq_reduce as before and launches nothing of the encoder's backward: no BPTT
+ *                (enc_h2h_dgrad, lstm_bwd), no enc_i2h_dgrad, no embed_bwd, no encoder weight-gradient GEMM.  The
+ *                EMBED and RNN gradient buffers are not touched -- neither written nor zeroed; they keep what
+ *                rau_zero_grads or earlier steps left.  The MULT group's gradients are the built-in path's bits.
+ *                rau_wait_grads stays valid for all three groups, rau_allreduce_grads works unchanged.
+ *   dq           dq[b,:] = sum_{h < HA} keep_q,h[b,:] * s_q * (dq~_h Wq)[b,:] in f32, hops added last first (the
+ *                built-in path's dq_reduce, the buffer its BPTT would have read).  It is OVERWRITTEN by each backward,
+ *                never accumulated; rau_zero_grads does not touch it.  With no active hop it is exact zeros.  No
+ *                atomics: repeated calls give the same bits, a captured step the eager step's.
+ *                rau_question_grad_dev hands out the ctx-owned DEVICE pointer [n,Q], ordered on the ctx's stream; it
+ *                synchronises nothing; valid until the next forward or rau_set_batch_size.  rau_get_question_grad:
+ *                the download, dense [n,Q]; synchronises.  Both are RAU_ERR_STATE when the last backward did not run
+ *                on an attached question, or no backward has run since the last forward.
+ *   captured     "a question is attached" joins rau_graph_step's key: a step captured without a question is never
+ *                replayed for a batch with one, nor the reverse.  A replay reads the buffer's current contents, so
+ *                attaching a new q each step needs no recapture.  rau_set_question_dev while a step is being
+ *                captured: RAU_ERR_STATE.
+ *   errors       nothing launched and nothing changed: a null ctx; no resident batch (RAU_ERR_STATE); a q_dev that is
+ *                not 16-byte aligned (RAU_ERR_INVALID); an unknown or unsupported type (RAU_ERR_INVALID).
+ *   unchanged    rau_backward_ext's rule stays: no EXTERNAL gradient enters at the question state.  The module-level
+ *                calls are unchanged.  rau_update / rau_noise_clip_adam are unchanged: they still update EMBED and
+ *                RNN (with noise on zero gradients) -- a caller who never uses the built-in encoder creates the
+ *                context with small V / T and ignores those groups.  A context that never attaches a question
+ *                computes and launches exactly what it did without these calls. */
+int rau_set_question_dev(rau_ctx* ctx, const void* q_dev /* [n,Q] DEVICE, dense; NULL = detach */, int q_type);
+int rau_batch_question(rau_ctx* ctx, int* has);
+int rau_question_grad_dev(rau_ctx* ctx, const float** dq /* [n,Q] f32 DEVICE */);
+int rau_get_question_grad(rau_ctx* ctx, float* host /* [n,Q] dense */);
+
 /* ---- module-level entry points: one call per nn.Module :forward / :backward -----
  * For hosts that keep feval's own loops (SS:443-596) and call the clones one by one.
  * t in [0,T) / h in [0,H) select the clone (the reference's embed_clones[t+1],

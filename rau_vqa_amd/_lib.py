@@ -172,6 +172,11 @@ _SIGS = {
     "rau_set_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_set_batch_dev_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
+    # question state from the caller: the step path behind another question encoder, dq back
+    "rau_set_question_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "rau_batch_question": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rau_question_grad_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "rau_get_question_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
     # module-level entry points: device pointers in, pointers to ctx-owned slots out
     "rau_embed_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_embed_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -23,6 +23,22 @@ Questions that share images: ``rau.want_feature_grad(per_image=True)``, ``rau.se
 and ``step(rau, hop_w, feats=table)`` with the table [N,D,S] itself; table.grad is then the per-image sum, formed by
 the library in a fixed order (the same bits from run to run, which an index_select backward does not give).
 
+``step(rau, ..., question=q)`` does the same on the QUESTION side: q is the CUDA tensor [n,Q] (Q = 4 Rq; float32,
+float16 or bfloat16) given to ``set_question``, the output of any torch question encoder -- a ``torch.nn.GRU`` over
+cached text features, a ``Linear`` adapter, a language model's pooled state -- in place of the built-in LSTM::
+
+    gru, adapt = torch.nn.GRU(300, 512).cuda(), torch.nn.Linear(512, rau.cfg.Q).cuda()
+    _, h = gru(words)                                        # [1,n,512], on torch's current stream
+    q = torch.tanh(adapt(h[0]))                              # [n,Q]
+    own.wait_stream(torch.cuda.current_stream())             # the ctx's copy of q runs behind its producer
+    rau.set_batch_dev(x, None, None, labels, question=q)     # or rau.set_question(q) on a resident batch
+    logits, dopred, attprob = autograd.step(rau, hop_w, question=q)
+    (my_loss(logits) + ...).backward()                       # q.grad flows on into adapt's and gru's parameters
+
+The backward returns a clone of ``rau.question_grad_tensor()`` for q, ordered with events like the feature-map
+gradient; the embed and rnn groups of the ctx receive nothing.  ``feats=`` and ``question=`` work together in one
+step and one ``loss.backward()``.
+
 torch is plumbing here: the forward, the backward and the update are librau's kernels; torch evaluates the
 caller's loss and its gradient at the three outputs, on its own current stream.  The two streams are joined with
 events only (ExternalStream + wait_stream), never with a host synchronisation.
@@ -34,7 +50,7 @@ import torch
 
 class _Step(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, rau, hop_w, select_w, att_w, merge_w):
+    def forward(ctx, anchor, question, rau, hop_w, select_w, att_w, merge_w):
         dev = torch.device("cuda", rau.cfg.device_id)
         rau.forward()
         own = torch.cuda.ExternalStream(rau.stream(), device=dev)
@@ -44,6 +60,7 @@ class _Step(torch.autograd.Function):
         outs = tuple(t.clone() for t in rau.output_tensors())
         ctx.rau, ctx.weights, ctx.dev = rau, (hop_w, select_w, att_w, merge_w), dev
         ctx.has_feats = anchor.dim() == 3       # step(feats=x): x is the recorded input, not the scalar anchor
+        ctx.q_dtype = None if question is None else question.dtype   # step(question=q): q is a recorded input too
         ctx.set_materialize_grads(False)        # an unused output's gradient stays None instead of a zero tensor
         return outs
 
@@ -64,10 +81,15 @@ class _Step(torch.autograd.Function):
             torch.cuda.current_stream(ctx.dev).wait_stream(own)
             gx = rau.feature_grad_tensor().clone()   # [rows,D,S]: per sample, or per image of a table batch
             own.wait_stream(torch.cuda.current_stream(ctx.dev))   # the next step overwrites the buffer: behind the clone
-        return (gx,) + (None,) * 5              # parameter gradients live in the ctx's flat buffers
+        gq = None
+        if ctx.q_dtype is not None:                  # the gradient at the attached question, for the encoder in front of it
+            torch.cuda.current_stream(ctx.dev).wait_stream(own)
+            gq = rau.question_grad_tensor().to(ctx.q_dtype, copy=True)   # [n,Q], in a 16-bit q's own type
+            own.wait_stream(torch.cuda.current_stream(ctx.dev))   # the next step overwrites the buffer: behind the clone
+        return (gx, gq) + (None,) * 5           # parameter gradients live in the ctx's flat buffers
 
 
-def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, feats=None):
+def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, feats=None, question=None):
     """forward of the resident batch -> (logits, dopred, attprob), differentiable at those three outputs.
 
     hop_w, select_w, att_w, merge_w: the built-in terms of RAU.backward, added to whatever loss the caller builds
@@ -76,7 +98,20 @@ def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, feats=None):
 
     feats: the CUDA float tensor [n,D,S] the resident batch was made of (RAU.set_batch_dev), with the context's
     feature-map gradient on (RAU.want_feature_grad): it becomes the recorded input and receives its gradient.  For a
-    resident image-table batch under want_feature_grad(per_image=True): the table [N,D,S]."""
+    resident image-table batch under want_feature_grad(per_image=True): the table [N,D,S].
+
+    question: the CUDA tensor [n,Q] attached to the resident batch (RAU.set_question, set_batch_dev(question=)): it
+    becomes a recorded input and receives the gradient at the question state."""
+    x = None   # the recorded feature-map input, where there is one
+    if question is not None:
+        if not (isinstance(question, torch.Tensor) and question.is_cuda and
+                tuple(question.shape) == (rau.batch_size, rau.cfg.Q)):
+            raise ValueError(f"question must be the CUDA tensor [n,Q] = {(rau.batch_size, rau.cfg.Q)} given to "
+                             f"set_question")
+        if not rau.batch_question:
+            raise ValueError("step(question=...) needs the question attached: call rau.set_question(q) first")
+        if not question.requires_grad:   # (a tensor nobody differentiates is just the attached question)
+            question = None
     if feats is not None:
         c = rau.cfg
         if not (isinstance(feats, torch.Tensor) and feats.is_cuda and feats.dim() == 3):
@@ -90,7 +125,8 @@ def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, feats=None):
         if per_image and rau.feature_grad_mode != 2:
             raise ValueError("step(feats=table) needs the per-image gradient: rau.want_feature_grad(per_image=True)")
         if feats.requires_grad:   # (a tensor nobody differentiates is a plain batch: the anchor below)
-            return _Step.apply(feats, rau, hop_w, select_w, att_w, merge_w)
-    # a leaf that requires grad makes autograd record the node: the real leaves are the ctx's parameters
-    anchor = torch.zeros((), device=torch.device("cuda", rau.cfg.device_id), requires_grad=True)
-    return _Step.apply(anchor, rau, hop_w, select_w, att_w, merge_w)
+            x = feats
+    if x is None:
+        # a leaf that requires grad makes autograd record the node: the real leaves are the ctx's parameters
+        x = torch.zeros((), device=torch.device("cuda", rau.cfg.device_id), requires_grad=True)
+    return _Step.apply(x, question, rau, hop_w, select_w, att_w, merge_w)

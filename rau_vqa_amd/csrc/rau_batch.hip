@@ -294,6 +294,7 @@ void hold(rau_ctx* ctx, int si, const Batch& b) {
   d.ans_G = 0;   // an answer set belongs to the batch it was given to
   d.regions = b.pk_counts != nullptr;   // ... and so do region counts (a packed batch brings its own)
   d.att_targets = false;   // ... and attention targets
+  d.question = false;      // ... and the caller's question state
 }
 
 void make_current(rau_ctx* ctx, int si) {
@@ -769,7 +770,9 @@ int rau_use_batch(rau_ctx* ctx, int slot) {
     HIPC(hipEventRecord(p.consumed, ctx->st));
     p.consumed_valid = true;
   }
+  cur_batch(ctx).held.question = false;   // a question is the resident batch's (rau_set_question_dev): it goes with it
   make_current(ctx, slot);
+  s.held.question = false;
   // the bulk and weight-gradient streams start each step behind an event of the chain stream,
   // so ordering the chain stream behind the upload orders all three
   HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
@@ -959,6 +962,62 @@ int rau_batch_att_targets(rau_ctx* ctx, int* has) {
   NEED(ctx && has, "null argument");
   *has = cur_batch(ctx).held.att_targets ? 1 : 0;
   return RAU_OK;
+}
+
+// The caller's question state for the resident batch: one copy (f32) or exact widening (16-bit) on the chain stream
+// into the slot's q_ext, behind every launch that reads the previous contents; nothing waits for the device.  The
+// flag is the batch's (BatchDesc::question): the step path branches on it, the graph key carries it.  Everything is
+// checked before anything moves.
+int rau_set_question_dev(rau_ctx* ctx, const void* q_dev, int q_type) {
+  NEED(ctx, "null ctx");
+  if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_question_dev: a step is being captured");
+  BatchSlot& s = cur_batch(ctx);
+  if (!s.held.have)
+    return fail(RAU_ERR_STATE, "rau_set_question_dev: no resident batch (upload the batch first)");
+  if (!q_dev) {   // detach: the next step runs the built-in encoder on the batch's tokens
+    if (s.held.question) ctx->fwd_done = false;   // a forward that read the question is not this batch's any more
+    s.held.question = false;
+    return RAU_OK;
+  }
+  NEED(q_type == RAU_FEAT_F32 || q_type == RAU_FEAT_F16 || q_type == RAU_FEAT_BF16,
+       "rau_set_question_dev: q_type %d is none of RAU_FEAT_F32, RAU_FEAT_F16, RAU_FEAT_BF16", q_type);
+  NEED((reinterpret_cast<uintptr_t>(q_dev) & 15u) == 0, "rau_set_question_dev: q_dev must be 16-byte aligned");
+  const size_t n = (size_t)ctx->cfg.B, Q = (size_t)ctx->Q;
+  if (!s.q_ext)   // for the capacity, at the slot's first question; cleared by rau_set_batch_size like every activation
+    if (int rc = dalloc(ctx, &s.q_ext, (size_t)ctx->cap * Q)) return rc;
+  hipStream_t st = ctx->st;
+  if (q_type == RAU_FEAT_F32)
+    HIPC(hipMemcpyAsync(s.q_ext, q_dev, n * Q * sizeof(float), hipMemcpyDeviceToDevice, st));
+  else   // Q = 4 Rq elements per row, rows dense: the unpitched path, 4 elements per thread
+    RUN("widen_features", 0, (double)n * Q * (4 + feat_elem_bytes(q_type)),
+        widen_features(st, n, (int)Q, (int)Q, q_dev, s.q_ext, q_type));
+  s.held.question = true;
+  ctx->fwd_done = false;   // a forward that ran on the batch did not read this question
+  return RAU_OK;
+}
+
+int rau_batch_question(rau_ctx* ctx, int* has) {
+  NEED(ctx && has, "null argument");
+  *has = cur_batch(ctx).held.question ? 1 : 0;
+  return RAU_OK;
+}
+
+static int question_grad_state(rau_ctx* ctx, const char* fn) {
+  if (!ctx->qg_valid)
+    return fail(RAU_ERR_STATE, "%s: no backward on an attached question (rau_set_question_dev) has run since the "
+                "last forward", fn);
+  return RAU_OK;
+}
+int rau_question_grad_dev(rau_ctx* ctx, const float** dq) {
+  NEED(ctx, "null ctx");
+  if (int rc = question_grad_state(ctx, "rau_question_grad_dev")) return rc;
+  if (dq) *dq = ctx->dq;
+  return RAU_OK;
+}
+int rau_get_question_grad(rau_ctx* ctx, float* host) {
+  NEED(ctx && host, "null argument");
+  if (int rc = question_grad_state(ctx, "rau_get_question_grad")) return rc;
+  return d2h(ctx, host, ctx->dq, (size_t)ctx->cfg.B * ctx->Q * sizeof(float));
 }
 
 int rau_batch_feats(rau_ctx* ctx, float** feats_dev) {

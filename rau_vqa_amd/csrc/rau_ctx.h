@@ -93,6 +93,9 @@ struct BatchDesc {
   // attention targets (rau_set_att_targets): the slot's att_t_d holds a target map per sample.  They belong to the
   // batch like the two above.
   bool att_targets = false;
+  // question state from the caller (rau_set_question_dev): the slot's q_ext holds q [n][Q] and the step reads it in
+  // place of the built-in encoder's output.  It belongs to the RESIDENT batch: hold() and rau_use_batch drop it.
+  bool question = false;
 };
 // One of the two batch slots.  slot[cur_slot] is the resident batch (cur_batch() below): the only record of it.
 // Slot 0's device buffers exist from rau_create on; slot 1's, the pinned staging the loader may fill in place, the
@@ -133,6 +136,9 @@ struct BatchSlot {
   float* att_t_d = nullptr;
   float* att_t_h = nullptr;
   bool att_pending = false;         // a copy out of att_t_h is behind the last record of `uploaded`
+  // the caller's question state (rau_set_question_dev): device [capacity][Q] f32, allocated at the slot's first
+  // attach (a captured step holds q_ext's address, never its contents)
+  float* q_ext = nullptr;
   // packed region rows (rau_set_batch_packed): the raw rows [sum(counts)][D] land in pk_rows_d (room for
   // [capacity * S][D] floats) and unpack_regions transposes them into `feats`; pk_meta_d holds off[n_maps] |
   // cnt[n_maps] (room for 2 * capacity), pk_meta_h is its pinned staging on the asynchronous path.  Allocated at
@@ -243,10 +249,12 @@ struct StepKey {
   int ans_loss = 0;             // ... and the head kernel is the answer criterion's (rau_set_answer_loss)
   int feat_grad = 0;            // ... and with rau_set_feat_grad the conv gradients are followed by the feature-map
                                 // gradient: the mode (per sample / per image of a table: another accumulate kernel)
+  bool question = false;        // ... and with a question attached (rau_set_question_dev) neither pass launches the
+                                // encoder: the hop chain reads the slot's q_ext
   auto tied() const {
     return std::tie(mode, max_len, active, zero, mexplicit[0], mexplicit[1], mexplicit[2], mexplicit[3], mexplicit[4],
                     slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg, tied_x, ans_loss,
-                    feat_grad);
+                    feat_grad, question);
   }
   bool operator==(const StepKey& o) const { return tied() == o.tied(); }
 };
@@ -356,6 +364,9 @@ struct rau_ctx {
                                     // they were never in memory, the backward regenerates them (philox.h)
   uint64_t fwd_seed = 0;            // ... from the key that forward ran under: a rau_set_dropout_seed between it and
   uint32_t fwd_step = 0;            // the backward would regenerate other bits, and is refused with the switch on
+  // question state from the caller (rau_set_question_dev): dq holds the gradient at the ATTACHED question of a
+  // backward since the last forward (rau_question_grad_dev); the q buffers are the slots' (BatchSlot::q_ext)
+  bool qg_valid = false;
   // rau_set_batch_dev: pinned staging of the index arrays, two halves alternated like hopw_h
   int32_t* bdev_h[2] = {nullptr, nullptr};
   hipEvent_t bdev_ev[2] = {nullptr, nullptr};
@@ -439,6 +450,11 @@ struct rau_ctx {
 // The resident batch: what every reader of the batch goes through.
 inline BatchSlot& cur_batch(rau_ctx* ctx) { return ctx->slot[ctx->cur_slot]; }
 inline const BatchSlot& cur_batch(const rau_ctx* ctx) { return ctx->slot[ctx->cur_slot]; }
+// What the hop chain reads as the question state: the caller's (rau_set_question_dev) or the built-in encoder's
+inline const float* question_state(const rau_ctx* ctx) {
+  const BatchSlot& s = cur_batch(ctx);
+  return s.held.question ? s.q_ext : ctx->q;
+}
 // The resident batch's feature-map gradient is formed per IMAGE: RAU_FEAT_GRAD_IMAGES on an image table.  (A bank
 // batch has no gradient in either mode; on a batch with one map per sample the mode is RAU_FEAT_GRAD_SAMPLES.)
 inline bool xgrad_per_image(const rau_ctx* ctx) {

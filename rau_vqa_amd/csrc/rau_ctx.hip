@@ -954,6 +954,7 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   ctx->xw = nullptr;
   ctx->fwd_done = ctx->bwd_done = false;
   ctx->xg_valid = false;
+  ctx->qg_valid = false;
   ctx->dpre_fwd = false;
   ctx->I_shared = ctx->yq_shared = false;
   ctx->fwd_tied = false;
@@ -1543,6 +1544,7 @@ int rau_forward(rau_ctx* ctx) {
   if (!bs.held.have) return fail(RAU_ERR_STATE, "rau_forward: no batch (call rau_set_batch)");
   ctx->mg.valid = false;   // the hop outputs are being overwritten
   ctx->xg_valid = false;   // ... and the feature-map gradient is another forward's
+  ctx->qg_valid = false;   // ... and so is the gradient at an attached question
   const rau_config& c = ctx->cfg;
   const int B = c.B, Rq = c.Rq, D = c.D, S = ctx->Sp, M = c.M, A = c.A, R = c.R, H = c.H, Q = ctx->Q;
   const int TL = bs.held.max_len;
@@ -1598,14 +1600,18 @@ int rau_forward(rau_ctx* ctx) {
       return rc;
     HIPC(hipEventRecord(ctx->evF[h0], sb));
   }
-  if (int rc = encoder_forward(ctx, m)) return rc;
-  RUN("gather_q", 0, (double)B * Q * 8,
-      gather_q(st, B, Rq, TL, bs.lens_d, ctx->c1, ctx->h1, ctx->c2, ctx->h2, ctx->q));
+  // a question from the caller (rau_set_question_dev) stands where the encoder's output would: nothing of the encoder
+  // is launched, the hop chain below is the same launch for launch
+  if (!bs.held.question) {
+    if (int rc = encoder_forward(ctx, m)) return rc;
+    RUN("gather_q", 0, (double)B * Q * 8,
+        gather_q(st, B, Rq, TL, bs.lens_d, ctx->c1, ctx->h1, ctx->c2, ctx->h2, ctx->q));
+  }
 
   // ---------------- RAU hops, SS:467-520
   const size_t BM_ = (size_t)B * M, BR_ = (size_t)B * R;
   RUN("apply_mask", 0, (double)H * B * Q * 8,
-      apply_mask(st, (size_t)H * B * Q, (size_t)B * Q, ctx->q, m.q, m.s_q, ctx->qd));
+      apply_mask(st, (size_t)H * B * Q, (size_t)B * Q, question_state(ctx), m.q, m.s_q, ctx->qd));
   bool q_split = false;
   {  // q_embed's question half (SS:233) for every hop clone; without dropout on q (evaluate mode) the
      // clones see the same rows: computed once
@@ -2117,7 +2123,12 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   static const int wg_env = [] { const char* e = std::getenv("RAU_WG_BULK"); return e ? std::atoi(e) : -1; }();
   const int wg_bulk = side_split(ctx) ? 0 : wg_env >= 0 ? wg_env : (chain_bound(ctx) ? 0 : 1);
   if (int rc = mult_wgrads(ctx, HA, sig, wg_bulk)) return rc;
-  if (int rc = encoder_backward(ctx, m, wg_bulk)) return rc;
+  // an attached question (rau_set_question_dev): dq above is the result, handed to the caller; no BPTT, no embedding
+  // gradient, no encoder weight-gradient GEMM -- the EMBED and RNN gradient buffers are not touched.  The joins
+  // below stand as they are: evW3 closes the third stream behind whatever it still runs (the mult group's block
+  // unless wg_bulk & 1), evD the bulk stream, and evEnd then covers all three groups.
+  if (!bs.held.question)
+    if (int rc = encoder_backward(ctx, m, wg_bulk)) return rc;
   HIPC(hipEventRecord(ctx->evW3, ctx->st3));
   HIPC(hipStreamWaitEvent(st, ctx->evW3, 0));
   if (wg_bulk) HIPC(hipEventRecord(ctx->evD, ctx->st2));   // the bulk stream got weight-gradient work behind its convs
@@ -2125,6 +2136,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   HIPC(hipEventRecord(ctx->evEnd, st));
   ctx->bwd_done = true;
   ctx->graph_last = false;
+  ctx->qg_valid = bs.held.question;
   ctx->xg_valid = ctx->feat_grad != RAU_FEAT_GRAD_OFF;
   ctx->xg_rows = xgrad_per_image(ctx) ? cur_batch(ctx).held.n_images : ctx->cfg.B;
   return RAU_OK;
@@ -2262,6 +2274,7 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
   key.tied_x = ctx->xdrop == RAU_XDROP_TIED;
   key.ans_loss = ctx->answer_loss;
   key.feat_grad = ctx->feat_grad;
+  key.question = bs.held.question;
   if (int rc = upload_hop_weights(ctx, loss)) return rc;
   ctx->mg.valid = false;
   hipGraphExec_t exec = nullptr;
@@ -2301,6 +2314,7 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
   ctx->fwd_done = false;
   ctx->bwd_done = true;
   ctx->graph_last = true;
+  ctx->qg_valid = bs.held.question;
   ctx->xg_valid = ctx->feat_grad != RAU_FEAT_GRAD_OFF;
   ctx->xg_rows = xgrad_per_image(ctx) ? cur_batch(ctx).held.n_images : ctx->cfg.B;
   return RAU_OK;
@@ -2402,7 +2416,7 @@ int rau_get_attention(rau_ctx* ctx, float* att) {
 }
 int rau_get_question_state(rau_ctx* ctx, float* q) {
   NEED(ctx, "null ctx");
-  return d2h(ctx, q, ctx->q, (size_t)ctx->cfg.B * ctx->Q * 4);
+  return d2h(ctx, q, question_state(ctx), (size_t)ctx->cfg.B * ctx->Q * 4);
 }
 int rau_get_att_state(rau_ctx* ctx, float* c, float* h) {
   NEED(ctx, "null ctx");

@@ -851,16 +851,69 @@ class RAU:
         n, D, S, dev = self.feature_grad_rows(), self.cfg.D, self.cfg.S, self.cfg.device_id
         return device_view(p.value, n * D * pitch.value, dev).view(n, D, pitch.value)[:, :, :S]
 
+    # ---- question state from the caller (rau_set_question_dev): another question encoder in front of the step path
+    def set_question(self, q_cuda):
+        """Attach the question state q [n,Q] (Q = 4 Rq) to the resident batch: a contiguous CUDA torch tensor of
+        float32, float16 or bfloat16 on the ctx's device -- the type is taken from the dtype, 16-bit values are
+        widened exactly.  One copy on the ctx's stream, no host synchronisation: order the ctx's stream behind the
+        stream that wrote the tensor and keep it unchanged until the copy has run (set_batch_dev's rule).  While it
+        is attached forward / graph_step read it in place of the built-in encoder's output and launch nothing of the
+        encoder; the backward leaves question_grad() behind and does not touch the embed and rnn gradients.  The
+        next set_batch* / use_batch / set_batch_size detaches it; attaching again replaces the contents."""
+        import torch
+        t = q_cuda
+        types = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in types and t.is_contiguous()):
+            raise ValueError("q_cuda must be a contiguous float32, float16 or bfloat16 CUDA torch tensor")
+        if t.device.index != self.cfg.device_id:
+            raise ValueError(f"q_cuda is on {t.device}, the context on cuda:{self.cfg.device_id}")
+        if tuple(t.shape) != (self._n, self.cfg.Q):
+            raise ValueError(f"q_cuda has shape {tuple(t.shape)}, expected {(self._n, self.cfg.Q)}")
+        L.check(self._lib.rau_set_question_dev(self._h, t.data_ptr(), feat16.FEAT_TYPES[types[t.dtype]]))
+
+    def clear_question(self):
+        """Detach the question: the resident batch is the built-in encoder's again."""
+        L.check(self._lib.rau_set_question_dev(self._h, None, 0))
+
+    @property
+    def batch_question(self) -> bool:
+        """The resident batch has a question attached (rau_batch_question)."""
+        has = C.c_int(0)
+        L.check(self._lib.rau_batch_question(self._h, C.byref(has)))
+        return bool(has.value)
+
+    def question_grad(self):
+        """The last backward's gradient at the attached question [n,Q] (numpy; synchronises)."""
+        out = np.empty((self._n, self.cfg.Q), np.float32)
+        L.check(self._lib.rau_get_question_grad(self._h, out.ctypes.data))
+        return out
+
+    def question_grad_tensor(self):
+        """Zero-copy torch view [n,Q] of the last backward's gradient at the attached question in device memory
+        (rau_question_grad_dev).  Valid until the next forward or set_batch_size, ordered on the ctx's stream
+        (stream()), read-only."""
+        from .dist import device_view
+        p = C.c_void_p()
+        L.check(self._lib.rau_question_grad_dev(self._h, C.byref(p)))
+        n, Q = self._n, self.cfg.Q
+        return device_view(p.value, n * Q, self.cfg.device_id).view(n, Q)
+
     def set_batch_dev(self, feats_cuda, tokens, lens, labels=None, answers=None, regions=None, att_targets=None,
-                      image_of=None):
+                      image_of=None, question=None):
         """set_batch with the maps already on the device: feats_cuda a contiguous float32 CUDA torch tensor
         [n,D,S] on the ctx's device (rau_set_batch_dev: one copy on the ctx's stream, no host synchronisation).
         The ctx's stream must be ordered behind the stream that wrote the tensor (autograd.step's docstring shows
         the two lines); the tensor must stay unchanged until that copy has run.  answers, regions, att_targets as
         in set_batch.  image_of [n] (0-based rows): feats_cuda is an image TABLE [N,D,S] (rau_set_batch_dev_images);
-        regions may then be per image [N]."""
+        regions may then be per image [N].  question: a CUDA tensor [n,Q] attached behind the upload (set_question);
+        tokens / lens may then be None -- the step does not read them, and id 1 with length 1 is uploaded."""
         import torch
         c = self.cfg
+        if question is not None and (tokens is None or lens is None):
+            if not (isinstance(question, torch.Tensor) and question.dim() == 2):
+                raise ValueError("question must be a CUDA torch tensor [n,Q]")
+            tokens = np.ones((c.T, int(question.shape[0])), np.int32)
+            lens = np.ones((int(question.shape[0]),), np.int32)
         lens = np.ascontiguousarray(lens, np.int32)
         B = self._rows(lens, "set_batch_dev")
         t = feats_cuda
@@ -900,6 +953,8 @@ class RAU:
             self.set_regions(regions)
         if att_targets is not None:
             self.set_att_targets(att_targets)
+        if question is not None:
+            self.set_question(question)
 
     def graph_step(self, hop_w, zero_grads=True, select_w=None, att_w=None, merge_w=None):
         """zero_grads + forward + backward as one hipGraph launch (captured on first use); select_w, att_w and
