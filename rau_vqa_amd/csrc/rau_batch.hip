@@ -297,11 +297,6 @@ void hold(rau_ctx* ctx, int si, const Batch& b) {
   d.question = false;      // ... and the caller's question state
 }
 
-void make_current(rau_ctx* ctx, int si) {
-  ctx->cur_slot = si;
-  ctx->fwd_done = false;
-}
-
 // rau_set_batch_images, or (b.bank_rows) the same batch with its table drawn from the bank
 int set_batch_sync(rau_ctx* ctx, Batch b) {
   const rau_config& c = ctx->cfg;
@@ -341,7 +336,7 @@ int set_batch_sync(rau_ctx* ctx, Batch b) {
   HIPC(hipStreamSynchronize(ctx->st));   // the caller's (pageable) buffers are free on return
   s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
   hold(ctx, si, b);
-  ctx->fwd_done = false;
+  drop_forward(ctx);
   return RAU_OK;
 }
 
@@ -360,7 +355,7 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   if (b.pk_counts)
     if (int rc = ensure_packed(ctx, slot, true)) return rc;
   BatchSlot& s = ctx->slot[slot];
-  if (slot == ctx->cur_slot && ctx->fwd_done)
+  if (slot == ctx->cur_slot && ctx->fwd.done)
     return fail(RAU_ERR_STATE, "rau_set_batch_async: slot %d is the current batch of a forward pass whose "
                 "backward has not run; upload into the other slot", slot);
   const size_t TB = (size_t)c.T * c.B;
@@ -408,7 +403,7 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   if (b.pk_counts) s.reg_pending = true;   // a copy out of nreg_h is behind this record
   hold(ctx, slot, b);
   if (slot == ctx->cur_slot) {   // re-filled in place: the next forward waits for the copies
-    make_current(ctx, slot);
+    drop_forward(ctx);
     HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
   }
   return RAU_OK;
@@ -648,7 +643,7 @@ static int set_batch_dev(rau_ctx* ctx, const char* who, const float* feats_dev, 
   HIPC(hipEventRecord(ctx->bdev_ev[sl], st));
   s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
   hold(ctx, si, b);
-  ctx->fwd_done = false;
+  drop_forward(ctx);
   return RAU_OK;
 }
 int rau_set_batch_dev(rau_ctx* ctx, const float* feats_dev, const int32_t* tokens, const int32_t* lens,
@@ -771,7 +766,8 @@ int rau_use_batch(rau_ctx* ctx, int slot) {
     p.consumed_valid = true;
   }
   cur_batch(ctx).held.question = false;   // a question is the resident batch's (rau_set_question_dev): it goes with it
-  make_current(ctx, slot);
+  ctx->cur_slot = slot;
+  drop_forward(ctx);
   s.held.question = false;
   // the bulk and weight-gradient streams start each step behind an event of the chain stream,
   // so ordering the chain stream behind the upload orders all three
@@ -789,7 +785,7 @@ int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const
   BatchSlot& s = ctx->slot[si];
   if (!s.held.have)
     return fail(RAU_ERR_STATE, "rau_set_answers: slot %d holds no batch (upload the batch first)", si);
-  if (slot >= 0 && si == ctx->cur_slot && ctx->fwd_done)
+  if (slot >= 0 && si == ctx->cur_slot && ctx->fwd.done)
     return fail(RAU_ERR_STATE, "rau_set_answers: slot %d is the current batch of a forward pass whose backward has "
                 "not run", si);
   NEED(G >= 1 && G <= kMaxAnswers, "rau_set_answers: G=%d out of [1,%d]", G, kMaxAnswers);
@@ -838,7 +834,7 @@ int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const
   }
   s.held.ans_G = G;
   s.held.have_labels = true;   // the set is the batch's ground truth
-  if (si == ctx->cur_slot) ctx->fwd_done = false;
+  if (si == ctx->cur_slot) drop_forward(ctx);
   if (si == ctx->mg.slot) ctx->mg.valid = false;   // statistics of a forward that read the slot's previous targets
   return RAU_OK;
 }
@@ -859,7 +855,7 @@ int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n) {
   BatchSlot& s = ctx->slot[si];
   if (!s.held.have)
     return fail(RAU_ERR_STATE, "rau_set_regions: slot %d holds no batch (upload the batch first)", si);
-  if (slot >= 0 && si == ctx->cur_slot && ctx->fwd_done)
+  if (slot >= 0 && si == ctx->cur_slot && ctx->fwd.done)
     return fail(RAU_ERR_STATE, "rau_set_regions: slot %d is the current batch of a forward pass whose backward has "
                 "not run", si);
   for (int b = 0; b < c.B; ++b)
@@ -894,7 +890,7 @@ int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n) {
     if (si == ctx->cur_slot) HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
   }
   s.held.regions = true;
-  if (si == ctx->cur_slot) ctx->fwd_done = false;   // a forward that ran on the batch did not see these counts
+  if (si == ctx->cur_slot) drop_forward(ctx);   // a forward that ran on the batch did not see these counts
   return RAU_OK;
 }
 
@@ -905,7 +901,7 @@ int rau_batch_regions(rau_ctx* ctx, int* has) {
 }
 
 // Attention targets for the batch in a slot: rau_set_regions' slot and ordering rules.  Everything is checked
-// before anything moves.  The forward does not read them, so fwd_done and the merged-hops record stay as they are.
+// before anything moves.  The forward does not read them: its record (rau_ctx::fwd) and the merged-hops record stay.
 int rau_set_att_targets(rau_ctx* ctx, int slot, const float* t) {
   NEED(ctx && t, "null argument");
   NEED(slot >= -1 && slot <= 1, "rau_set_att_targets: slot %d (-1 = the resident batch, 0 or 1)", slot);
@@ -914,7 +910,7 @@ int rau_set_att_targets(rau_ctx* ctx, int slot, const float* t) {
   BatchSlot& s = ctx->slot[si];
   if (!s.held.have)
     return fail(RAU_ERR_STATE, "rau_set_att_targets: slot %d holds no batch (upload the batch first)", si);
-  if (slot >= 0 && si == ctx->cur_slot && ctx->fwd_done)
+  if (slot >= 0 && si == ctx->cur_slot && ctx->fwd.done)
     return fail(RAU_ERR_STATE, "rau_set_att_targets: slot %d is the current batch of a forward pass whose backward "
                 "has not run", si);
   const size_t n = (size_t)c.B * c.S;
@@ -975,7 +971,7 @@ int rau_set_question_dev(rau_ctx* ctx, const void* q_dev, int q_type) {
   if (!s.held.have)
     return fail(RAU_ERR_STATE, "rau_set_question_dev: no resident batch (upload the batch first)");
   if (!q_dev) {   // detach: the next step runs the built-in encoder on the batch's tokens
-    if (s.held.question) ctx->fwd_done = false;   // a forward that read the question is not this batch's any more
+    if (s.held.question) drop_forward(ctx);   // a forward that read the question is not this batch's any more
     s.held.question = false;
     return RAU_OK;
   }
@@ -992,7 +988,7 @@ int rau_set_question_dev(rau_ctx* ctx, const void* q_dev, int q_type) {
     RUN("widen_features", 0, (double)n * Q * (4 + feat_elem_bytes(q_type)),
         widen_features(st, n, (int)Q, (int)Q, q_dev, s.q_ext, q_type));
   s.held.question = true;
-  ctx->fwd_done = false;   // a forward that ran on the batch did not read this question
+  drop_forward(ctx);   // a forward that ran on the batch did not read this question
   return RAU_OK;
 }
 
@@ -1003,7 +999,7 @@ int rau_batch_question(rau_ctx* ctx, int* has) {
 }
 
 static int question_grad_state(rau_ctx* ctx, const char* fn) {
-  if (!ctx->qg_valid)
+  if (!ctx->bwd.dq)
     return fail(RAU_ERR_STATE, "%s: no backward on an attached question (rau_set_question_dev) has run since the "
                 "last forward", fn);
   return RAU_OK;
@@ -1078,7 +1074,7 @@ int rau_bank_destroy(rau_ctx* ctx) {
     const int ft = s.held.feat_type;   // (its maps are not: enqueue_batch's pad-column rule reads their type)
     s.held = BatchDesc{};
     s.held.feat_type = ft;
-    if (&s == &cur_batch(ctx)) ctx->fwd_done = false;
+    if (&s == &cur_batch(ctx)) drop_forward(ctx);
   }
   hipFree(ctx->bank);
   if (ctx->bank_stage) hipFree(ctx->bank_stage);

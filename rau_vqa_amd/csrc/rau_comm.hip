@@ -96,10 +96,10 @@ int rau_comm_init(rau_ctx* ctx, int nranks, int rank, const void* id, size_t byt
 int rau_allreduce_grads(rau_ctx* ctx) {
   NEED(ctx, "null ctx");
   if (!ctx->comm) return fail(RAU_ERR_STATE, "rau_allreduce_grads: call rau_comm_init first");
-  if (!ctx->bwd_done) return fail(RAU_ERR_STATE, "rau_allreduce_grads: no rau_backward to reduce");
+  if (!ctx->bwd.done) return fail(RAU_ERR_STATE, "rau_allreduce_grads: no rau_backward to reduce");
   ncclComm_t comm = static_cast<ncclComm_t>(ctx->comm);
   hipStream_t sc = ctx->st_comm;
-  if (ctx->graph_last) {   // the step ran as a graph: only its end is a waitable event
+  if (ctx->bwd.graph) {   // the step ran as a graph: only its end is a waitable event
     HIPC(hipStreamWaitEvent(sc, ctx->evEnd, 0));
   } else {
     HIPC(hipStreamWaitEvent(sc, ctx->evD, 0));

@@ -222,7 +222,7 @@ struct StepLoss {
   // formed (one scale per hop): such a backward forms dpre / dhn itself from the final dl
   bool forms_dpre() const { return select_w || merge_w || has_ext(); }
 };
-// What shapes a captured step (rau_graph_step): one executable graph per distinct value.
+// What shapes a captured step (rau_graph_step): one executable graph per distinct value (step_key() below).
 struct StepKey {
   int mode = 0;                 // rau_mode
   int max_len = 0;              // the longest question: the encoder's token count
@@ -263,6 +263,37 @@ struct StepGraph {
   hipGraphExec_t exec;
 };
 
+// What the last step-level forward left for its backward.  rau_ctx::fwd: rau_forward fills it, drop_forward()
+// (below) is the one way to take the backward away, "no forward" is FwdRecord{} (rau_set_batch_size).
+struct FwdRecord {
+  bool done = false;              // a backward may run: a forward has, and nothing since has overwritten what it left
+  bool table = false;             // it read P and I per IMAGE (evaluate-mode fast path): no per-sample I to differentiate
+  // the two layout facts of the hop buffers; rau_multimodal_forward writes them too (false: it fills the hop's own rows)
+  bool I_shared = false;          // evaluate mode, p_x = 0 or a tied mask: i_embed output is hop-invariant, computed once
+  bool yq_shared = false;         // no dropout on q (evaluate mode): q_embed's question half is rows of hop 0 only
+  bool tied = false;              // a train-mode forward under RAU_XDROP_TIED: summed conv gradients
+  const float* x_shared = nullptr;  // ... and i_embed's input then: xd (the one masked map) or, without a mask, xw
+  float* xw = nullptr;            // f32 image of the unmasked batch it read: feats, or (16-bit batch) the first
+                                  // B*D*Sp floats of xd, widened there by that forward
+  bool xgen = false;              // it drew the feature-map keep bits inside its dropout pass: they were never in
+                                  // memory, the backward regenerates them (philox.h)
+  uint64_t seed = 0;              // ... from the key it ran under: a rau_set_dropout_seed between it and the
+  uint32_t step = 0;              // backward would regenerate other bits, and is refused with the switch on
+  bool dl = false;                // it wrote dl: its batch had labels or an answer set (rau_backward_ext)
+  bool dpre = false;              // it already formed dpre / dhn of every hop (unscaled by the hop weights)
+  std::vector<int> groups;        // the launch partition it used (rau_ctx::groups; evaluate mode: one group of H)
+};
+// What the last step-level backward left for the getters.  rau_ctx::bwd: record_backward (rau_ctx.hip) fills it for
+// backward_impl and graph_step_impl, "no backward" is BwdRecord{} (rau_set_batch_size).
+struct BwdRecord {
+  bool done = false;              // rau_wait_grads / rau_allreduce_grads have something to wait for
+  bool graph = false;             // it ran inside a graph (its events are graph-internal: only evEnd is waitable)
+  // of a backward since the last forward (rau_forward clears both, rau_set_feat_grad dX on a change of mode):
+  bool dq = false;                // rau_ctx::dq holds the gradient at the ATTACHED question (rau_question_grad_dev)
+  bool dX = false;                // xg_dX holds the feature-map gradient (rau_get_feat_grad) ...
+  int dX_rows = 0;                // ... its map count: n, or the table's N under RAU_FEAT_GRAD_IMAGES
+};
+
 struct rau_ctx {
   rau_config cfg;             // cfg.B is the CURRENT batch size (rau_set_batch_size): what every layout, launch and
                               // getter reads at call time -- the B of the fresh context this one is equivalent to
@@ -283,9 +314,8 @@ struct rau_ctx {
   std::vector<hipEvent_t> evH;       // per hop: forward chain done (the head stream waits on it)
   std::vector<hipEvent_t> evF, evK;  // per hop group: forward bulk done / backward chain done
   // hops per bulk launch (pipelines the bulk GEMMs with the hop loops): gsize[h] = n if hops
-  // [h, h+n) form one launch group, else 0.  `groups` is the configured partition, `cur` the one
-  // the last forward used (evaluate mode: one group of H).
-  std::vector<int> groups, cur, bgroups;   // bgroups: backward partition (empty = same as forward)
+  // [h, h+n) form one launch group, else 0.  `groups` is the configured partition (FwdRecord::groups: the last forward's).
+  std::vector<int> groups, bgroups;   // bgroups: backward partition (empty = same as forward)
   std::vector<void*> allocs;
   // what rau_set_batch_size clears: every dalloc'ed region except parameters, gradients, Adam moments, the Philox
   // key and rau_dev_alloc'ed memory.  The layouts are dense in the current batch size, so after a change stale
@@ -303,10 +333,6 @@ struct rau_ctx {
   bool x_valid = false;           // feats_x holds the expansion of upload x_serial into slot x_slot
   int x_slot = 0;
   uint64_t x_serial = 0;
-  bool fwd_table = false;         // the last forward read P and I per IMAGE (evaluate-mode fast path): there
-                                  // is no per-sample I for a backward pass
-  float* xw = nullptr;            // f32 image of the unmasked batch the last forward read: feats, or (16-bit
-                                  // batch) the first B*D*Sp floats of xd, widened there by that forward
   // feature bank (rau_bank_*): every image's map once, in the batch buffers' layout [capacity][D][Sp]
   void* bank = nullptr;
   int32_t bank_cap = 0, bank_filled = 0;
@@ -342,31 +368,15 @@ struct rau_ctx {
   void* WiT16 = nullptr;  // with xd16: bf16 copies of the transposed conv weights WiT, WpT
   void* WpT16 = nullptr;
   void* dS16 = nullptr;  // with xd16: the attention backward's dS as bf16 [H][B][A][S] (both consumers round it anyway)
-  bool dpre_fwd = false;    // the last forward already formed dpre / dhn of every hop (unscaled by the hop weights)
-  bool fwd_dl = false;      // the last forward wrote dl: its batch had labels or an answer set (rau_backward_ext)
-  bool ds16_step = false;   // set by rau_backward while its hop loop runs: hop_backward writes dS16, not T
   void* xd16 = nullptr;  // RAU_BF16 step path, S % 4 == 0: the same maps stored as bf16 (xd stays unwritten)
-  bool I_shared = false;  // evaluate mode, p_x = 0 or a tied mask: i_embed output is hop-invariant, computed once
   // feature-map dropout kind (rau_set_feat_dropout): RAU_XDROP_PER_HOP, or RAU_XDROP_TIED = one mask for all hops
   int xdrop = RAU_XDROP_PER_HOP;
-  bool fwd_tied = false;            // the last forward was a train-mode one under RAU_XDROP_TIED: summed conv gradients
-  const float* x_shared = nullptr;  // ... and i_embed's input then: xd (the one masked map) or, without a mask, xw
   float* dS_sum = nullptr;          // [cap][A][Sp] sum of the active hops' dS (tied_bwd.hip), allocated with the switch
   // feature-map gradient (rau_set_feat_grad, xgrad.hip): off = the step path as it is without it
   int feat_grad = RAU_FEAT_GRAD_OFF;   // the mode: _SAMPLES, or _IMAGES = per image where the batch has a table
-  float* xg_dX = nullptr;           // [cap][D][Sp] the last backward's result, allocated with the switch
-  int xg_rows = 0;                  // ... its map count: n, or the table's N under RAU_FEAT_GRAD_IMAGES
+  float* xg_dX = nullptr;           // [cap][D][Sp] the last backward's result (bwd.dX), allocated with the switch
   float* xg_tmp = nullptr;          // [cap][D][Sp] one hop's unmasked product (the unfused path)
   float* xg_dz = nullptr;           // [cap][M][Sp] dI (1 - I^2) where the dgrad left dI (no fused tanh derivative)
-  bool xg_first = false;            // no launch of the running backward has written xg_dX yet: the next one stores
-  bool xg_valid = false;            // xg_dX holds the result of a backward since the last forward
-  bool fwd_xgen = false;            // the last forward drew the feature-map keep bits inside its dropout pass:
-                                    // they were never in memory, the backward regenerates them (philox.h)
-  uint64_t fwd_seed = 0;            // ... from the key that forward ran under: a rau_set_dropout_seed between it and
-  uint32_t fwd_step = 0;            // the backward would regenerate other bits, and is refused with the switch on
-  // question state from the caller (rau_set_question_dev): dq holds the gradient at the ATTACHED question of a
-  // backward since the last forward (rau_question_grad_dev); the q buffers are the slots' (BatchSlot::q_ext)
-  bool qg_valid = false;
   // rau_set_batch_dev: pinned staging of the index arrays, two halves alternated like hopw_h
   int32_t* bdev_h[2] = {nullptr, nullptr};
   hipEvent_t bdev_ev[2] = {nullptr, nullptr};
@@ -374,7 +384,6 @@ struct rau_ctx {
   // the answer criterion of the step path (rau_set_answer_loss): RAU_LOSS_CE, or RAU_LOSS_BCE = per-answer sigmoid.
   // Read through step_truth() only; the module-level criteria name theirs themselves.
   int answer_loss = RAU_LOSS_CE;
-  bool yq_shared = false; // no dropout on q (evaluate mode): q_embed's question half is hop-invariant, rows of hop 0 only
   float *WiT, *WpT;   // i_embed / ifeatproj weights transposed ([D][M], [M][A]), refreshed per forward
   float *P0;          // [B][A][S] hop-invariant attention pre-activation (evaluate mode)
   float *qd, *Yq, *qf, *I, *T, *u, *zm, *a, *jv, *j, *g4, *cc, *hh, *tc, *mf, *logits,
@@ -401,8 +410,6 @@ struct rau_ctx {
   int32_t* att_si = nullptr;
   // step-selection head's gradient (rau_backward_select, select_bwd.hip)
   float *sel_s = nullptr, *sel_add = nullptr;   // [H][cap] s rows, [H][cap][M] s (x) wd; allocated at first use
-  bool capture_bwd_forms_dpre = false;   // a step is being captured whose backward forms dpre / dhn itself
-                                         // (StepLoss::forms_dpre), so the forward leaves them alone
   // backward temporaries
   // dZ holds dI (gradient at i_embed's OUTPUT); the tanh derivative is applied by its consumers
   float *dpre, *dhn, *dg4, *dcn[2], *dhp[2], *dj, *da_lin, *dz, *du, *dwsp, *dZ,
@@ -430,13 +437,13 @@ struct rau_ctx {
   // hipGraph replay of a whole step (rau_graph_step): one executable graph per step "shape"
   uint64_t* dkey = nullptr;      // device copy of (seed, step): what fill_masks reads
   bool capturing = false;
-  bool graph_last = false;       // the last backward ran inside a graph (its events are graph-internal)
   std::vector<StepGraph> graphs;
   MergeState mg;                 // merged hops (rau_merge.hip): what may be read of the last forward
   // update
   float *npart = nullptr, *norms_d = nullptr;
   float* upd_part = nullptr;     // rau_update's partial sums of squares, [3][kUpdParts]
-  bool fwd_done = false, bwd_done = false;
+  FwdRecord fwd;                 // what the last step-level forward left for its backward
+  BwdRecord bwd;                 // what the last step-level backward left for the getters
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool prof_on = false;
@@ -450,6 +457,8 @@ struct rau_ctx {
 // The resident batch: what every reader of the batch goes through.
 inline BatchSlot& cur_batch(rau_ctx* ctx) { return ctx->slot[ctx->cur_slot]; }
 inline const BatchSlot& cur_batch(const rau_ctx* ctx) { return ctx->slot[ctx->cur_slot]; }
+// The last forward has no backward any more, and nothing else: callers that also drop mg.valid say so next to this
+inline void drop_forward(rau_ctx* ctx) { ctx->fwd.done = false; }
 // What the hop chain reads as the question state: the caller's (rau_set_question_dev) or the built-in encoder's
 inline const float* question_state(const rau_ctx* ctx) {
   const BatchSlot& s = cur_batch(ctx);
@@ -460,6 +469,32 @@ inline const float* question_state(const rau_ctx* ctx) {
 inline bool xgrad_per_image(const rau_ctx* ctx) {
   const BatchDesc& d = cur_batch(ctx).held;
   return ctx->feat_grad == RAU_FEAT_GRAD_IMAGES && d.n_images > 0 && !d.bank;
+}
+// The key of the step that `loss` asks for on the resident batch, as the context is configured now
+inline StepKey step_key(const rau_ctx* ctx, const StepLoss& loss, bool zero) {
+  const BatchDesc& d = cur_batch(ctx).held;
+  StepKey key;
+  key.mode = ctx->mode;
+  key.max_len = d.max_len;
+  key.active = loss.active;
+  key.zero = zero;
+  std::copy(ctx->mexplicit, ctx->mexplicit + 5, key.mexplicit);
+  key.slot = ctx->cur_slot;
+  key.feat_type = d.feat_type;
+  key.table = d.n_images > 0;
+  key.bank = d.bank;
+  key.ans_G = d.ans_G;
+  key.B = ctx->cfg.B;
+  key.sel = loss.select_w != nullptr;
+  key.regions = d.regions;
+  key.att = loss.att_w != nullptr;
+  key.att_targets = d.att_targets;
+  key.mrg = loss.merge_w != nullptr;
+  key.tied_x = ctx->xdrop == RAU_XDROP_TIED;
+  key.ans_loss = ctx->answer_loss;
+  key.feat_grad = ctx->feat_grad;
+  key.question = d.question;
+  return key;
 }
 
 // Effective drop probability of a mask site.  Masks the device draws itself (Philox, 8-bit draws)
@@ -683,6 +718,7 @@ struct HopGrad {
                              // bulk stream's conv gradients of this hop read (dS, dj) exists from there on
   bool dh_prev_dead;      // the gradient at prev_h has no consumer (step-level hop 0: the initial state is a
                           // constant): its three products are not formed
+  bool ds16;              // step-level bf16 backward on 14x14 maps: the attention backward writes dS16, not T
 };
 __attribute__((visibility("hidden"))) int hop_forward(rau_ctx* ctx, int h, const float* cp,
     const float* hp, float* c_out, float* h_out, const float* Ih, const float* Pin,

@@ -766,7 +766,7 @@ int rau_get_mask(rau_ctx* ctx, int site, uint8_t* keep, size_t n) {
 
 // ------------------------------------------------- feature-map dropout kind
 // The forward reads ctx->xdrop (one masked map and the shared conv path in train mode), the backward what that
-// forward recorded (fwd_tied), plan_batch the size of the mask site; nothing else depends on the kind.
+// forward recorded (fwd.tied), plan_batch the size of the mask site; nothing else depends on the kind.
 int rau_set_feat_dropout(rau_ctx* ctx, int kind) {
   NEED(ctx, "null ctx");
   NEED(kind == RAU_XDROP_PER_HOP || kind == RAU_XDROP_TIED,
@@ -782,7 +782,7 @@ int rau_set_feat_dropout(rau_ctx* ctx, int kind) {
   ctx->mcount[RAU_MASK_X] = (size_t)(kind == RAU_XDROP_TIED ? 1 : c.H) * c.B * c.D * c.S;
   ctx->mexplicit[RAU_MASK_X] = false;   // a caller's mask has the other kind's shape: back to the seeded stream
   ctx->mod_masks_valid = false;
-  ctx->fwd_done = false;                // the last forward is the other kind's: no backward without a new one
+  drop_forward(ctx);                    // the last forward is the other kind's: no backward without a new one
   return RAU_OK;
 }
 int rau_feat_dropout(rau_ctx* ctx, int* kind) {
@@ -814,8 +814,8 @@ int rau_set_feat_grad(rau_ctx* ctx, int on) {
     if (!ctx->xg_dz)
       if (int rc = dalloc(ctx, &ctx->xg_dz, (size_t)ctx->cap * c.M * ctx->Sp)) return rc;
   }
-  // (a forward that ran under another mode stays differentiable or refused on its own record: fwd_table)
-  if (on != ctx->feat_grad) ctx->xg_valid = false;
+  // (a forward that ran under another mode stays differentiable or refused on its own record: fwd.table)
+  if (on != ctx->feat_grad) ctx->bwd.dX = false;
   ctx->feat_grad = on;
   return RAU_OK;
 }
@@ -826,7 +826,7 @@ int rau_feat_grad(rau_ctx* ctx, int* on) {
 }
 static int feat_grad_state(rau_ctx* ctx, const char* fn) {
   if (!ctx->feat_grad) return fail(RAU_ERR_STATE, "%s: the feature-map gradient is off (rau_set_feat_grad)", fn);
-  if (!ctx->xg_valid) return fail(RAU_ERR_STATE, "%s: no backward has run since the last forward", fn);
+  if (!ctx->bwd.dX) return fail(RAU_ERR_STATE, "%s: no backward has run since the last forward", fn);
   return RAU_OK;
 }
 int rau_feat_grad_dev(rau_ctx* ctx, const float** dX, int32_t* pitch) {
@@ -839,7 +839,7 @@ int rau_feat_grad_dev(rau_ctx* ctx, const float** dX, int32_t* pitch) {
 int rau_feat_grad_rows(rau_ctx* ctx, int32_t* rows) {
   NEED(ctx && rows, "null argument");
   if (int rc = feat_grad_state(ctx, "rau_feat_grad_rows")) return rc;
-  *rows = ctx->xg_rows;
+  *rows = ctx->bwd.dX_rows;
   return RAU_OK;
 }
 int rau_get_feat_grad(rau_ctx* ctx, float* host) {
@@ -847,7 +847,7 @@ int rau_get_feat_grad(rau_ctx* ctx, float* host) {
   if (int rc = feat_grad_state(ctx, "rau_get_feat_grad")) return rc;
   const rau_config& c = ctx->cfg;
   HIPC(hipMemcpy2DAsync(host, (size_t)c.S * 4, ctx->xg_dX, (size_t)ctx->Sp * 4, (size_t)c.S * 4,
-                        (size_t)ctx->xg_rows * c.D,
+                        (size_t)ctx->bwd.dX_rows * c.D,
                         hipMemcpyDeviceToHost, ctx->st));
   HIPC(hipStreamSynchronize(ctx->st));
   return persist_check(ctx);
@@ -864,7 +864,7 @@ int rau_set_answer_loss(rau_ctx* ctx, int kind) {
   if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_answer_loss: a step is being captured");
   if (kind == ctx->answer_loss) return RAU_OK;
   ctx->answer_loss = kind;
-  ctx->fwd_done = false;   // dl and the loss rows are the other criterion's: no backward, no statistics without
+  drop_forward(ctx);       // dl and the loss rows are the other criterion's: no backward, no statistics without
   ctx->mg.valid = false;   // a new forward
   return RAU_OK;
 }
@@ -950,16 +950,8 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   }
   ctx->cur_slot = 0;
   ctx->x_valid = false;
-  ctx->fwd_table = false;
-  ctx->xw = nullptr;
-  ctx->fwd_done = ctx->bwd_done = false;
-  ctx->xg_valid = false;
-  ctx->qg_valid = false;
-  ctx->dpre_fwd = false;
-  ctx->I_shared = ctx->yq_shared = false;
-  ctx->fwd_tied = false;
-  ctx->x_shared = nullptr;
-  ctx->cur.clear();
+  ctx->fwd = FwdRecord{};
+  ctx->bwd = BwdRecord{};
   for (int i = 0; i < 5; ++i) ctx->mexplicit[i] = false;
   ctx->mod_masks_valid = false;
   ctx->mg.invalidate();
@@ -1008,7 +1000,7 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
   float *slab_z = slab_t + off[1], *slab_g = slab_t + off[2];
   {  // qf = tanh(Yq + h_prev Wh^T): the q half (with both biases) was computed for all hops at once
     LinOpts o;
-    o.addend = ctx->Yq + (ctx->yq_shared ? 0 : (size_t)h * BM_);
+    o.addend = ctx->Yq + (ctx->fwd.yq_shared ? 0 : (size_t)h * BM_);
     o.add_rs = M;
     o.act = 1;
     RUN("lin_reduce", 0, 0, lin_reduce_epilogue(st, B, M, ns_t, slab_t + off[0], qf, M, o));
@@ -1218,14 +1210,14 @@ int hop_backward(rau_ctx* ctx, int h, const float* cp, const float* Ih, const Ho
   if (!ctx->att_split)
     RUN("att_bwd_fused", 2.0 * B * S * (A + M), ((double)B * A * S * 2 + BM_ * S) * 4,
         att_bwd_fused(st, B, M, A, S, Ih, djh, ah, ws.slab, ctx->att_score.W, Th, dzh, duh,
-                      ctx->dwsp + (size_t)h * B * A, ctx->I_shared ? ctx->P0 : Th,
+                      ctx->dwsp + (size_t)h * B * A, ctx->fwd.I_shared ? ctx->P0 : Th,
                       ctx->u + (size_t)h * B * A, ns_a, SL, g.da_out,
-                      ctx->ds16_step ? (void*)((uint16_t*)ctx->dS16 + (size_t)h * B * A * S) : nullptr,
+                      g.ds16 ? (void*)((uint16_t*)ctx->dS16 + (size_t)h * B * A * S) : nullptr,
                       ctx->bf16 ? 8 : 0));
   else
     RUN("att_bwd_split", 2.0 * B * S * (A + M), ((double)B * A * S * 2 + BM_ * S) * 4,
         att_bwd_split(st, B, M, A, S, Ih, djh, ah, ws.slab, ctx->att_score.W, Th, dzh, duh,
-                      ctx->dwsp + (size_t)h * B * A, ctx->I_shared ? ctx->P0 : Th,
+                      ctx->dwsp + (size_t)h * B * A, ctx->fwd.I_shared ? ctx->P0 : Th,
                       ctx->u + (size_t)h * B * A, ctx->att_part, ns_a, SL, g.da_out));
   if (g.ev_conv_ready) HIPC(hipEventRecord(g.ev_conv_ready, st));
   const size_t used = (size_t)(dhp - X);
@@ -1333,10 +1325,6 @@ extern "C" {
 static int seam_mask() {
   static const int m = [] { const char* e = std::getenv("RAU_SEAM"); return e ? std::atoi(e) : 3; }();
   return m;
-}
-static bool head_dgrad_fwd(const rau_ctx* ctx) {
-  return cur_batch(ctx).held.have_labels && ctx->mode == RAU_MODE_TRAIN && (seam_mask() & 1) &&
-         !ctx->capture_bwd_forms_dpre;
 }
 
 // ---------------- encoder, SS:443-462
@@ -1459,11 +1447,11 @@ static int encoder_forward(rau_ctx* ctx, const Masks& m) {
 
 // The passes on `sb` that make the maps the convs read out of the batch's nX maps `feats`.  In train mode each hop
 // clone has its own dropout mask on the feature map (SS:239, SS:343-347) -> xd[h] = X (.) mask_h (tied: one copy); in
-// evaluate mode the convs read the batch itself.  Sets ctx->xw and ctx->x_shared; *x16_out: the hop copies are bf16.
+// evaluate mode the convs read the batch itself.  Sets ctx->fwd.xw and ctx->fwd.x_shared; *x16_out: the hop copies are bf16.
 static int feature_maps(rau_ctx* ctx, hipStream_t sb, const Masks& m, const float* feats, int nX, bool* x16_out) {
   const rau_config& c = ctx->cfg;
   const int B = c.B, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, H = c.H;
-  const bool tied = ctx->fwd_tied;
+  const bool tied = ctx->fwd.tied;
   // feature-map dropout, SS:239: unless the caller supplied the mask, the pass that makes the H masked
   // copies draws the keep bits itself (they have no other reader on this path)
   // bf16 mode: the hop copies of the feature map are stored as bf16 (to halve an H-fold buffer; the one tied
@@ -1471,9 +1459,9 @@ static int feature_maps(rau_ctx* ctx, hipStream_t sb, const Masks& m, const floa
   const bool x16 = m.x && ctx->xd16 && !tied;
   const int HX = tied ? 1 : H;         // masked copies: the mask site has HX * B * D * SL elements
   const bool x_gen = m.x && !ctx->mexplicit[RAU_MASK_X] && SL == S && ((size_t)B * D * S) % 16 == 0;
-  ctx->fwd_xgen = x_gen;   // the bits never reach memory: a feature-map gradient regenerates them (xgrad.hip)
-  ctx->fwd_seed = ctx->seed;
-  ctx->fwd_step = ctx->step;
+  ctx->fwd.xgen = x_gen;   // the bits never reach memory: a feature-map gradient regenerates them (xgrad.hip)
+  ctx->fwd.seed = ctx->seed;
+  ctx->fwd.step = ctx->step;
   if (!x_gen)
     if (int rc = gen_masks(ctx, -1, RAU_MASK_X, sb)) return rc;
   RUNS(sb, "transpose", 0, (double)M * D * 8, transpose2d(sb, M, D, ctx->i_embed.W, ctx->WiT, ctx->WiT16));
@@ -1494,13 +1482,13 @@ static int feature_maps(rau_ctx* ctx, hipStream_t sb, const Masks& m, const floa
          dropout_features(sb, HX, (size_t)B * D * S, feats, m.x, m.s_x, ctx->xd, 0, SL, S, ft));
   // no mask: the GEMMs read the batch itself -- a 16-bit one through its f32 image in xd (unused here),
   // so that they are the f32 batch's kernels with the f32 batch's operands
-  ctx->xw = const_cast<float*>(feats);
+  ctx->fwd.xw = const_cast<float*>(feats);
   if (!m.x && ft != RAU_FEAT_F32) {
-    ctx->xw = ctx->xd;
+    ctx->fwd.xw = ctx->xd;
     RUNS(sb, "widen_features", 0, (double)nX * D * S * (xb + 4),
-         widen_features(sb, (size_t)nX * D, SL, S, feats, ctx->xw, ft));
+         widen_features(sb, (size_t)nX * D, SL, S, feats, ctx->fwd.xw, ft));
   }
-  ctx->x_shared = m.x ? ctx->xd : ctx->xw;   // what the shared path's i_embed reads (and its weight gradient)
+  ctx->fwd.x_shared = m.x ? ctx->xd : ctx->fwd.xw;   // what the shared path's i_embed reads (and its weight gradient)
   *x16_out = x16;
   return RAU_OK;
 }
@@ -1526,7 +1514,7 @@ static int head_dgrad(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const fl
 }
 
 // Classifier + criterion heads of the finished hops [gstart, h] on the side stream, head_max hops per launch
-static int forward_heads(rau_ctx* ctx, int gstart, int h, int head_max, const Truth& truth) {
+static int forward_heads(rau_ctx* ctx, int gstart, int h, int head_max, const Truth& truth, bool dpre) {
   for (int h0 = gstart; h0 <= h; h0 += head_max)
     if (int rc = hop_forward_head(ctx, ctx->ws_side, h0, std::min(head_max, h + 1 - h0), truth)) return rc;
   // The backward's first two products do not depend on the recurrence either: dpre = (dl Wc) (.) mask
@@ -1534,17 +1522,17 @@ static int forward_heads(rau_ctx* ctx, int gstart, int h, int head_max, const Tr
   // forward / backward seam -- where the bulk stream and the matrix pipes wait for the chain -- is two
   // GEMMs shorter.  dl is not yet scaled by the hop weights (they arrive with rau_backward); both
   // products are linear in it, so rau_backward scales dl, dpre and dhn together.
-  if (head_dgrad_fwd(ctx)) return head_dgrad(ctx, ctx->ws_side, gstart, h + 1 - gstart, nullptr);
+  if (dpre) return head_dgrad(ctx, ctx->ws_side, gstart, h + 1 - gstart, nullptr);
   return RAU_OK;
 }
 
-int rau_forward(rau_ctx* ctx) {
+// rau_forward; bwd_forms_dpre: the backward of this (captured) step forms dpre / dhn itself (StepLoss::forms_dpre)
+static int forward_impl(rau_ctx* ctx, bool bwd_forms_dpre) {
   NEED(ctx, "null ctx");
   BatchSlot& bs = cur_batch(ctx);
   if (!bs.held.have) return fail(RAU_ERR_STATE, "rau_forward: no batch (call rau_set_batch)");
   ctx->mg.valid = false;   // the hop outputs are being overwritten
-  ctx->xg_valid = false;   // ... and the feature-map gradient is another forward's
-  ctx->qg_valid = false;   // ... and so is the gradient at an attached question
+  ctx->bwd.dX = ctx->bwd.dq = false;   // ... and the gradients at the maps and at an attached question another forward's
   const rau_config& c = ctx->cfg;
   const int B = c.B, Rq = c.Rq, D = c.D, S = ctx->Sp, M = c.M, A = c.A, R = c.R, H = c.H, Q = ctx->Q;
   const int TL = bs.held.max_len;
@@ -1554,14 +1542,14 @@ int rau_forward(rau_ctx* ctx) {
   // RAU_XDROP_TIED: every hop clone sees the SAME masked map, so a train-mode step takes the shared path too (one
   // masked copy, both convs once) and its backward sums the hops in front of one set of conv gradients
   const bool tied = ctx->mode == RAU_MODE_TRAIN && ctx->xdrop == RAU_XDROP_TIED;
-  ctx->I_shared = (m.x == nullptr) || tied;
-  ctx->fwd_tied = tied;
+  ctx->fwd.I_shared = (m.x == nullptr) || tied;
+  ctx->fwd.tied = tied;
   // A batch with an image table.  Evaluate mode: nothing per sample touches the maps (no dropout on X), so
   // i_embed and the attention pre-activation run once per IMAGE and the attention kernels read sample b's
   // tiles at row image_of[b].  Everywhere else (train mode: per-sample masks; a captured step: its backward
   // needs per-sample I) the table is gathered into per-sample maps first and the plain path runs on those.
   // (Nor under RAU_FEAT_GRAD_IMAGES: the per-image gradient differentiates per-sample I.  Same output bits.)
-  const bool table_fwd = bs.held.n_images > 0 && ctx->I_shared && ctx->mode == RAU_MODE_EVAL && !ctx->capturing &&
+  const bool table_fwd = bs.held.n_images > 0 && ctx->fwd.I_shared && ctx->mode == RAU_MODE_EVAL && !ctx->capturing &&
                          !xgrad_per_image(ctx);
   const int nX = table_fwd ? bs.held.n_images : B;   // maps the image-side passes read
   const int32_t* img = table_fwd ? bs.image_of_d : nullptr;
@@ -1575,14 +1563,10 @@ int rau_forward(rau_ctx* ctx) {
   }
   if (!table_fwd)
     if (int rc = batch_maps(ctx, &feats)) return rc;   // (on st, in front of evA: the bulk stream is ordered behind it)
-  ctx->fwd_table = table_fwd;
-  if (ctx->I_shared) {   // evaluate mode: one launch group
-    ctx->cur.assign(H, 0);
-    ctx->cur[0] = H;
-  } else {
-    ctx->cur = ctx->groups;
-  }
-  const std::vector<int>& gsz = ctx->cur;
+  ctx->fwd.table = table_fwd;
+  std::vector<int>& gsz = ctx->fwd.groups;
+  gsz = ctx->groups;
+  if (ctx->fwd.I_shared) { gsz.assign(H, 0); gsz[0] = H; }   // evaluate mode: one launch group
   // ---------------- bulk stream: everything about the feature map that does not depend on the recurrence (overlaps
   // the encoder and the hop loop below); in evaluate mode I is hop-invariant and computed once.  Hops are launched in
   // groups of `hop_group` so hop h's chain can start as soon as its group is done while this stream works on the rest.
@@ -1592,11 +1576,11 @@ int rau_forward(rau_ctx* ctx) {
   bool x16 = false;
   if (int rc = feature_maps(ctx, sb, m, feats, nX, &x16)) return rc;
   for (int h0 = 0; h0 < H; h0 += gsz[h0]) {
-    const int nBI = ctx->I_shared ? nX : gsz[h0] * B;
-    const size_t hb = ctx->I_shared ? 0 : (size_t)h0 * B;  // first (hop, sample) row
-    const void* xin = x16 ? map_elems(ctx->xd16, true, hb * D * S) : m.x ? ctx->xd + hb * D * S : ctx->xw;
+    const int nBI = ctx->fwd.I_shared ? nX : gsz[h0] * B;
+    const size_t hb = ctx->fwd.I_shared ? 0 : (size_t)h0 * B;  // first (hop, sample) row
+    const void* xin = x16 ? map_elems(ctx->xd16, true, hb * D * S) : m.x ? ctx->xd + hb * D * S : ctx->fwd.xw;
     if (int rc = image_forward(ctx, sb, nBI, xin, x16, ctx->I + hb * M * S,
-                               ctx->I_shared ? ctx->P0 : ctx->T + hb * A * S))
+                               ctx->fwd.I_shared ? ctx->P0 : ctx->T + hb * A * S))
       return rc;
     HIPC(hipEventRecord(ctx->evF[h0], sb));
   }
@@ -1615,10 +1599,10 @@ int rau_forward(rau_ctx* ctx) {
   bool q_split = false;
   {  // q_embed's question half (SS:233) for every hop clone; without dropout on q (evaluate mode) the
      // clones see the same rows: computed once
-    ctx->yq_shared = (m.q == nullptr);
+    ctx->fwd.yq_shared = (m.q == nullptr);
     // with dropout: hop 0's rows here, the other hops' rows on the weight-gradient stream (hop 1 waits)
-    q_split = !ctx->yq_shared && side_split(ctx) && H > 1;
-    const int qrows = (ctx->yq_shared || q_split) ? B : H * B;
+    q_split = !ctx->fwd.yq_shared && side_split(ctx) && H > 1;
+    const int qrows = (ctx->fwd.yq_shared || q_split) ? B : H * B;
     LinOpts o = lin_opts(ctx, ctx->ws_chain);
     o.bias = ctx->q_proj.b;
     o.bias2 = ctx->h_proj.b;
@@ -1639,6 +1623,8 @@ int rau_forward(rau_ctx* ctx) {
   HIPC(hipMemsetAsync(ctx->cc, 0, BR_ * sizeof(float), st));  // att_c, att_h zeros SS:362-365
   HIPC(hipMemsetAsync(ctx->hh, 0, BR_ * sizeof(float), st));
   const Truth truth = step_truth(ctx);
+  // RAU_SEAM & 1: the heads are followed by the backward's two head products, unless that backward forms them itself
+  const bool dpre = bs.held.have_labels && ctx->mode == RAU_MODE_TRAIN && (seam_mask() & 1) && !bwd_forms_dpre;
   // rows the logits region of the head's workspace holds (hop_forward_head: a quarter of the side stream's slab)
   const int head_max = (int)std::max<size_t>(1, ctx->ws_side.floats / 4 / ((size_t)B * c.K));
   int gstart = 0;
@@ -1650,8 +1636,8 @@ int rau_forward(rau_ctx* ctx) {
     if (h == 1 && q_split) HIPC(hipStreamWaitEvent(st, ctx->evQ, 0));   // Yq rows of hops 1..
     if (int rc = hop_forward_chain(ctx, h, ctx->cc + (size_t)h * BR_, ctx->hh + (size_t)h * BR_,
                                    ctx->cc + (size_t)(h + 1) * BR_, ctx->hh + (size_t)(h + 1) * BR_,
-                                   ctx->I + (ctx->I_shared ? 0 : (size_t)h * BM_ * S),
-                                   ctx->I_shared ? ctx->P0 : ctx->T + (size_t)h * B * A * S, img,
+                                   ctx->I + (ctx->fwd.I_shared ? 0 : (size_t)h * BM_ * S),
+                                   ctx->fwd.I_shared ? ctx->P0 : ctx->T + (size_t)h * B * A * S, img,
                                    bs.held.regions ? bs.nreg_d : nullptr))
       return rc;
     // classifier + criterion heads of the finished hops: nothing on the recurrence waits for
@@ -1661,7 +1647,7 @@ int rau_forward(rau_ctx* ctx) {
     if (group_end || h + 1 - gstart >= head_max) {
       HIPC(hipEventRecord(ctx->evH[h], st));
       HIPC(hipStreamWaitEvent(ctx->st3, ctx->evH[h], 0));
-      if (int rc = forward_heads(ctx, gstart, h, head_max, truth)) return rc;
+      if (int rc = forward_heads(ctx, gstart, h, head_max, truth, dpre)) return rc;
       gstart = h + 1;
     }
   }
@@ -1670,11 +1656,12 @@ int rau_forward(rau_ctx* ctx) {
   if (bs.held.have_labels)
     RUN("loss_reduce", 0, 0, loss_reduce(st, H, B, ctx->lossrow, ctx->losses_d));
   if (!ctx->capturing) merge_record(ctx);   // (rau_graph_step records behind its launch)
-  ctx->fwd_done = true;
-  ctx->fwd_dl = bs.held.have_labels;
-  ctx->dpre_fwd = head_dgrad_fwd(ctx);
+  ctx->fwd.done = true;
+  ctx->fwd.dl = bs.held.have_labels;
+  ctx->fwd.dpre = dpre;
   return RAU_OK;
 }
+int rau_forward(rau_ctx* ctx) { return forward_impl(ctx, false); }
 
 // The caller's hop_w may be a temporary (and may be pinned memory, for which an async copy really
 // is asynchronous): stage it in the ctx's own pinned buffer first.  Two slots, alternated, so the
@@ -1721,11 +1708,11 @@ static int loss_gradients(rau_ctx* ctx, const StepLoss& loss, const Truth& t) {
   // dpred:mul(w[h])  SS:569 / MS:568-570 / Full:587-589
   if (!ctx->capturing)   // (rau_graph_step uploads the weights before it launches the graph)
     if (int rc = upload_hop_weights(ctx, loss)) return rc;
-  if (ext.d_logits || (loss.has_ext() && !ctx->fwd_dl))
+  if (ext.d_logits || (loss.has_ext() && !ctx->fwd.dl))
     // one pass in scale_hops' place: dl * hop_w + d_logits; without a criterion gradient dl = d_logits (or +0)
-    RUN("ext_dl", (double)H * B * K * (ctx->fwd_dl ? 2 : 0), (double)H * B * K * (ctx->fwd_dl ? 12 : 8),
-        ext_dl(st, H, (size_t)B * K, ctx->fwd_dl ? ctx->hopw_d : nullptr, ext.d_logits, ctx->dl));
-  else if (ctx->dpre_fwd && !loss.forms_dpre())   // the forward formed dpre / dhn from the unscaled dl: scale all three
+    RUN("ext_dl", (double)H * B * K * (ctx->fwd.dl ? 2 : 0), (double)H * B * K * (ctx->fwd.dl ? 12 : 8),
+        ext_dl(st, H, (size_t)B * K, ctx->fwd.dl ? ctx->hopw_d : nullptr, ext.d_logits, ctx->dl));
+  else if (ctx->fwd.dpre && !loss.forms_dpre())   // the forward formed dpre / dhn from the unscaled dl: scale all three
     RUN("scale_hops", 0, (double)H * B * (K + M + R) * 8,
         scale_hops3(st, H, ctx->hopw_d, (size_t)B * K, ctx->dl, (size_t)B * M, ctx->dpre, (size_t)B * R, ctx->dhn));
   else
@@ -1756,25 +1743,25 @@ static int loss_gradients(rau_ctx* ctx, const StepLoss& loss, const Truth& t) {
   if (ext.d_attprob)   // the dense [H,n,S] gradient (added) into the pitched addend, zeros behind the counts
     RUN("ext_da", 0, (double)HA * B * S * (att ? 12 : 8),
         ext_da(st, HA, B, SL, ext.d_attprob, bs.held.regions ? bs.nreg_d : nullptr, att, ctx->att_da, S));
-  if (HA > 0 && (!ctx->dpre_fwd || loss.forms_dpre()))
+  if (HA > 0 && (!ctx->fwd.dpre || loss.forms_dpre()))
     return head_dgrad(ctx, ctx->ws_chain, 0, HA, (sel || ext.d_dopred) ? ctx->sel_add : nullptr);
   return RAU_OK;
 }
 
 // The feature-map gradient of `nh` hops from hop h0 on (rau_set_feat_grad), on the bulk stream behind the conv
-// gradients that formed their dZ: xg_dX (=, for the backward's first launch, else +=) sum_h keep_h s_x Wi^T dZ_h.
+// gradients that formed their dZ: xg_dX (=, for the backward's first launch, `first`, else +=) sum_h keep_h s_x Wi^T dZ_h.
 // dz: hop h0's [B][M][Sp] block, nh of them; is_dI: it holds the gradient at i_embed's OUTPUT (the dgrad without
 // the fused tanh derivative), I the matching activations (I_stride floats from hop to hop, 0 = shared).
 // mask_hop: the first hop's slice of the mask site (tied: 0), mask_step hops per hop (tied, no mask: 0).
 // RAU_FEAT_GRAD_IMAGES on an image table (xgrad_per_image): the same products, added per image into xg_dX as
 // [slots][D][Sp] in the order of the slot's sample lists; launched over the capacity's slots, whatever N is.
 static int feat_grad_hops(rau_ctx* ctx, hipStream_t sb, int nh, const void* dz, bool dz_is_b16, bool is_dI,
-                          const float* I, size_t I_stride, int mask_hop, int mask_step) {
+                          const float* I, size_t I_stride, int mask_hop, int mask_step, bool& first) {
   const rau_config& c = ctx->cfg;
   const int B = c.B, D = c.D, S = ctx->Sp, SL = c.S, M = c.M;
   const Masks m = masks_of(ctx);
   XMask xm{};
-  xm.kind = !m.x ? 0 : ctx->fwd_xgen ? 2 : 1;
+  xm.kind = !m.x ? 0 : ctx->fwd.xgen ? 2 : 1;
   xm.bits = m.x;
   xm.hop_stride = (size_t)B * D * SL;
   xm.seed = ctx->seed; xm.site = RAU_MASK_X; xm.step = ctx->step; xm.key = ctx->dkey;
@@ -1786,9 +1773,9 @@ static int feat_grad_hops(rau_ctx* ctx, hipStream_t sb, int nh, const void* dz, 
   if (!per_image && !dz_is_b16 && !is_dI && !ctx->bf16 && xgrad_fused_ok(D, M, S) && S == SL) {
     xm.e0 = (size_t)mask_hop * xm.hop_stride;
     if (!mask_step) xm.hop_stride = 0;
-    RUNS(sb, "conv_embed_dgrad", nh * fl, (double)nh * B * M * S * 4 + (double)B * D * S * (ctx->xg_first ? 4 : 8),
-         xgrad_fused(sb, nh, B, D, M, S, (const float*)dz, ctx->i_embed.W, ctx->xg_dX, xm, ctx->xg_first ? 1 : 0));
-    ctx->xg_first = false;
+    RUNS(sb, "conv_embed_dgrad", nh * fl, (double)nh * B * M * S * 4 + (double)B * D * S * (first ? 4 : 8),
+         xgrad_fused(sb, nh, B, D, M, S, (const float*)dz, ctx->i_embed.W, ctx->xg_dX, xm, first ? 1 : 0));
+    first = false;
     return RAU_OK;
   }
   for (int k = 0; k < nh; ++k) {
@@ -1803,30 +1790,30 @@ static int feat_grad_hops(rau_ctx* ctx, hipStream_t sb, int nh, const void* dz, 
     xm.e0 = (size_t)(mask_hop + k * mask_step) * xm.hop_stride;
     if (per_image)
       RUNS(sb, "xgrad_accum_img", 2.0 * B * D * S,
-           ((double)B * 4 + (double)bs.held.n_images * (ctx->xg_first ? 4 : 8)) * D * S,
+           ((double)B * 4 + (double)bs.held.n_images * (first ? 4 : 8)) * D * S,
            xgrad_accum_img(sb, ctx->cap, D, SL, S, ctx->xg_tmp, ctx->xg_dX, bs.img_start_d, bs.img_samples_d, xm,
-                           ctx->xg_first ? 1 : 0));
+                           first ? 1 : 0));
     else
-      RUNS(sb, "xgrad_accum", 2.0 * B * D * S, (double)B * D * S * (ctx->xg_first ? 8 : 12),
-           xgrad_accum(sb, (size_t)B * D, SL, S, ctx->xg_tmp, ctx->xg_dX, xm, ctx->xg_first ? 1 : 0));
-    ctx->xg_first = false;
+      RUNS(sb, "xgrad_accum", 2.0 * B * D * S, (double)B * D * S * (first ? 8 : 12),
+           xgrad_accum(sb, (size_t)B * D, SL, S, ctx->xg_tmp, ctx->xg_dX, xm, first ? 1 : 0));
+    first = false;
   }
   return RAU_OK;
 }
 
 // The 1x1-conv gradients of the launch group that starts with hop h, on the bulk stream (dZ feeds the weight
 // gradients; the feature-map gradient is dead in the reference, SS:579, and formed only under rau_set_feat_grad:
-// feat_grad_hops above); HA = the active hops.
-static int group_conv_grads(rau_ctx* ctx, int h, int group, int HA) {
+// feat_grad_hops above, which owns dX_first); HA = the active hops; ds16: the hops left their dS as bf16 (HopGrad::ds16).
+static int group_conv_grads(rau_ctx* ctx, int h, int group, int HA, bool ds16, bool& dX_first) {
   const rau_config& c = ctx->cfg;
   const int B = c.B, D = c.D, S = ctx->Sp, M = c.M, A = c.A;
   hipStream_t sb = ctx->st2;
   ConvGrads g{};
-  if (!ctx->I_shared) {
+  if (!ctx->fwd.I_shared) {
     const size_t hb = (size_t)h * B;
     g.n = (std::min(h + group, HA) - h) * B;   // active hops of this group
     g.dzf = conv_dz_fused_ok(S, M, ctx->bf16);
-    g.ds_is_b16 = ctx->ds16_step;
+    g.ds_is_b16 = ds16;
     g.dS = g.ds_is_b16 ? map_elems(ctx->dS16, true, hb * A * S) : ctx->T + hb * A * S;
     g.dj = ctx->dj + hb * M; g.a = ctx->a + hb * S; g.I = ctx->I + hb * M * S;
     g.x_is_b16 = g.dz_is_b16 = ctx->xd16 && g.dzf;
@@ -1838,29 +1825,29 @@ static int group_conv_grads(rau_ctx* ctx, int h, int group, int HA) {
       RUNS(sb, "colsum", 0, (double)HA * B * M * 4,
            colsum_acc(sb, HA * B, M, ctx->dbi_part, M, ctx->i_embed.db, ctx->ws_bulk.coltmp));
     if (ctx->feat_grad)
-      return feat_grad_hops(ctx, sb, g.n / B, g.dZ, g.dz_is_b16, !g.dzf, g.I, (size_t)B * M * S, h, 1);
+      return feat_grad_hops(ctx, sb, g.n / B, g.dZ, g.dz_is_b16, !g.dzf, g.I, (size_t)B * M * S, h, 1, dX_first);
     return RAU_OK;
   }
   g.n = B; g.I = ctx->I;
-  if (ctx->fwd_tied) {
+  if (ctx->fwd.tied) {
     // Tied feature-map dropout (train mode, I and X' shared): the conv gradients are linear in what each hop
     // hands back, so the hops are summed first (tied_bwd.hip) and every conv gradient runs once, at n = B.
     // The sum of dS goes to a buffer of its own: T keeps every hop's dS, as on the per-hop paths.
     RUNS(sb, "hop_sum", 0, (double)(HA + 1) * B * A * S * 4, hop_sum(sb, HA, B, A, c.S, S, ctx->T, ctx->dS_sum));
-    g.dS = ctx->dS_sum; g.dj = ctx->dj; g.a = ctx->a; g.X = ctx->x_shared; g.dZ = ctx->dZ; g.tied_hops = HA;
+    g.dS = ctx->dS_sum; g.dj = ctx->dj; g.a = ctx->a; g.X = ctx->fwd.x_shared; g.dZ = ctx->dZ; g.tied_hops = HA;
     if (int rc = conv_grads(ctx, sb, g)) return rc;
     // one mask: keep * s_x * Wi^T (sum_h dZ_h), and dZ holds that sum (as dI: the tanh derivative is hop-invariant)
-    if (ctx->feat_grad) return feat_grad_hops(ctx, sb, 1, ctx->dZ, false, true, ctx->I, 0, 0, 0);
+    if (ctx->feat_grad) return feat_grad_hops(ctx, sb, 1, ctx->dZ, false, true, ctx->I, 0, 0, 0, dX_first);
     return RAU_OK;
   }
   for (int hh2 = 0; hh2 < HA; ++hh2) {  // evaluate mode: I (and X) shared by all hops
     const size_t hb = (size_t)hh2 * B;
     g.dS = ctx->T + hb * A * S; g.dj = ctx->dj + hb * M; g.a = ctx->a + hb * S;
-    g.X = ctx->xw; g.dZ = ctx->dZ + hb * M * S;
+    g.X = ctx->fwd.xw; g.dZ = ctx->dZ + hb * M * S;
     if (int rc = conv_grads(ctx, sb, g)) return rc;
   }
   if (ctx->feat_grad && HA > 0)   // no mask, scale 1: the hops in ascending order
-    return feat_grad_hops(ctx, sb, HA, ctx->dZ, false, true, ctx->I, 0, 0, 0);
+    return feat_grad_hops(ctx, sb, HA, ctx->dZ, false, true, ctx->I, 0, 0, 0, dX_first);
   return RAU_OK;
 }
 
@@ -1984,14 +1971,24 @@ static int encoder_backward(rau_ctx* ctx, const Masks& m, int wg_bulk) {
   return enc_wgrads(ctx, TL, wg_bulk);
 }
 
+// A step-level backward on the resident batch has been enqueued (graph: as a graph launch): what the getters may read
+static void record_backward(rau_ctx* ctx, bool graph) {
+  const BatchDesc& d = cur_batch(ctx).held;
+  ctx->bwd.done = true;
+  ctx->bwd.graph = graph;
+  ctx->bwd.dq = d.question;
+  ctx->bwd.dX = ctx->feat_grad != RAU_FEAT_GRAD_OFF;
+  ctx->bwd.dX_rows = xgrad_per_image(ctx) ? d.n_images : ctx->cfg.B;
+}
+
 static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   const bool sel = loss.select_w != nullptr, att = loss.att_w != nullptr, mrg = loss.merge_w != nullptr;
   const rau_out_grads& ext = loss.ext;
   const bool sig = sel || ext.d_dopred;   // the head_dgrad addend and the selection head's weight gradient exist
   const bool has_da = att || ext.d_attprob;   // every hop's attention backward is handed its da_out
   const int HA = loss.active;
-  if (!ctx->fwd_done) return fail(RAU_ERR_STATE, "rau_backward: call rau_forward first");
-  if (ctx->fwd_table)
+  if (!ctx->fwd.done) return fail(RAU_ERR_STATE, "rau_backward: call rau_forward first");
+  if (ctx->fwd.table)
     return fail(RAU_ERR_STATE, "rau_backward: the evaluate-mode forward of a batch with an image table computed "
                 "i_embed once per image, so there is no per-sample I to differentiate; take evaluate-mode "
                 "gradients on a plain batch (rau_set_batch)");
@@ -2002,15 +1999,15 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
                 "per sample (rau_set_batch_dev) or turn the switch off");
   // the feature-map keep bits that forward drew in its dropout pass exist nowhere: the backward regenerates them
   // from the key, which must still be that forward's (a captured step holds both passes: the key cannot move)
-  if (ctx->feat_grad && !ctx->capturing && ctx->fwd_xgen && masks_of(ctx).x &&
-      (ctx->seed != ctx->fwd_seed || ctx->step != ctx->fwd_step))
+  if (ctx->feat_grad && !ctx->capturing && ctx->fwd.xgen && masks_of(ctx).x &&
+      (ctx->seed != ctx->fwd.seed || ctx->step != ctx->fwd.step))
     return fail(RAU_ERR_STATE, "rau_backward: rau_set_dropout_seed was called between the forward and this backward; "
                 "with the feature-map gradient on (rau_set_feat_grad) the backward regenerates the forward's "
                 "feature-map dropout bits from the key: run the forward again");
   // an external-only backward reads no label: hop_w zeros, no select_w, no merge_w (att_w reads the targets alone)
   const bool builtin = !loss.has_ext() || loss.hop_any || sel || mrg;
   if (builtin && !bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_backward: batch has no labels");
-  if (builtin && loss.has_ext() && !ctx->fwd_dl)
+  if (builtin && loss.has_ext() && !ctx->fwd.dl)
     return fail(RAU_ERR_STATE, "rau_backward_ext: the forward ran on a batch without labels, so there is no "
                 "criterion gradient for a non-zero hop_w, select_w or merge_w");
   // the head's target is read from that forward's labels or answer set: they must still be there (a captured
@@ -2026,19 +2023,18 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   // group's gradients can only start once its LAST hop's chain is done, so the backward partition
   // is its own: RAU_BWD_GROUPS="1,1,2,2,2" (sizes in HOP order, must sum to H), default = the
   // forward partition.  Evaluate mode (I shared): one group.
-  const std::vector<int>& gsz = (!ctx->I_shared && !ctx->bgroups.empty()) ? ctx->bgroups : ctx->cur;
+  const std::vector<int>& gsz = (!ctx->fwd.I_shared && !ctx->bgroups.empty()) ? ctx->bgroups : ctx->fwd.groups;
   hipStream_t st = ctx->st;
   const Masks m = masks_of(ctx);
   const size_t BM_ = (size_t)B * M, BS_ = (size_t)B * S, BR_ = (size_t)B * R;
-  ctx->fwd_done = false;  // dl is scaled in place below: one backward per forward
-  ctx->xg_first = true;   // (feat_grad) the first launch that writes xg_dX stores, the others add
+  drop_forward(ctx);      // dl is scaled in place below: one backward per forward
+  bool dX_first = true;   // (feat_grad) the first launch that writes xg_dX stores, the others add
   if (int rc = loss_gradients(ctx, loss, t)) return rc;
   const float* dc_next = nullptr;  // grad_att_c / grad_att_h zeros, SS:561-562
   float* dh_part = nullptr;        // gradient at next_h: K-split partials left by the previous hop
   int dh_part_ns = 0;
   // bf16 mode, train-mode step on 14x14 maps: dS goes out as bf16 (its consumers below read that)
-  ctx->ds16_step = ctx->dS16 && !ctx->I_shared && !ctx->att_split && conv_dz_fused_ok(S, M, ctx->bf16);
-  struct Ds16Reset { rau_ctx* c; ~Ds16Reset() { c->ds16_step = false; } } ds16_reset{ctx};
+  const bool ds16 = ctx->dS16 && !ctx->fwd.I_shared && !ctx->att_split && conv_dz_fused_ok(S, M, ctx->bf16);
   bool dq_side = false;
   int dq_rows_left = HA;           // hops [0, dq_rows_left) whose dq term this stream still owes
   for (int h = HA - 1; h >= 0; --h) {
@@ -2059,8 +2055,9 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
       g.ev_conv_ready = (gsz[h] && (seam_mask() & 2)) ? ctx->evK[h] : nullptr;
       g.dh_prev_dead = h == 0;   // hop 0's prev_h is the constant initial state: nothing reads its gradient
       g.da_out = has_da ? ctx->att_da + (size_t)h * BS_ : nullptr;
+      g.ds16 = ds16;
       if (int rc = hop_backward(ctx, h, ctx->cc + (size_t)h * BR_,
-                                ctx->I + (ctx->I_shared ? 0 : (size_t)h * BM_ * S), g))
+                                ctx->I + (ctx->fwd.I_shared ? 0 : (size_t)h * BM_ * S), g))
         return rc;
     }
     dc_next = dc_out;
@@ -2087,7 +2084,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
     if (gsz[h]) {   // h is the first hop of its group: the whole group's attention backward is done
       if (!(seam_mask() & 2)) HIPC(hipEventRecord(ctx->evK[h], st));
       HIPC(hipStreamWaitEvent(ctx->st2, ctx->evK[h], 0));   // recorded inside hop_backward (ev_conv_ready)
-      if (int rc = group_conv_grads(ctx, h, gsz[h], HA)) return rc;
+      if (int rc = group_conv_grads(ctx, h, gsz[h], HA, ds16, dX_first)) return rc;
     }
   }
   {  // dq = sum_h (dq~_h Wq) (.) mask_h     (ConcatTable backward, SS:579)
@@ -2100,7 +2097,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
         dq_reduce(st, HA, (size_t)B * Q, ctx->dQD, m.q, m.s_q, ctx->dq));
   }
   // no active hop: the gradient is zero (n rows: all of a table's N <= n too, whichever N a replay meets)
-  if (ctx->feat_grad && ctx->xg_first)
+  if (ctx->feat_grad && dX_first)
     HIPC(hipMemsetAsync(ctx->xg_dX, 0, (size_t)B * c.D * S * sizeof(float), ctx->st2));
   // bulk stream tail: the join event (the i_embed bias gradient comes out of conv_embed_wgrad:
   // row sums of its staged dZ operand)
@@ -2134,11 +2131,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   if (wg_bulk) HIPC(hipEventRecord(ctx->evD, ctx->st2));   // the bulk stream got weight-gradient work behind its convs
   HIPC(hipStreamWaitEvent(st, ctx->evD, 0));  // join: every gradient is ordered on st
   HIPC(hipEventRecord(ctx->evEnd, st));
-  ctx->bwd_done = true;
-  ctx->graph_last = false;
-  ctx->qg_valid = bs.held.question;
-  ctx->xg_valid = ctx->feat_grad != RAU_FEAT_GRAD_OFF;
-  ctx->xg_rows = xgrad_per_image(ctx) ? cur_batch(ctx).held.n_images : ctx->cfg.B;
+  record_backward(ctx, false);
   return RAU_OK;
 }
 
@@ -2254,27 +2247,7 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
   if (ctx->feat_grad && bs.held.n_images > 0 && !xgrad_per_image(ctx))
     return fail(RAU_ERR_STATE, "rau_graph_step: the feature-map gradient (rau_set_feat_grad) of a batch with an image "
                 "table or bank rows is not formed; expand the maps per sample (rau_set_batch_dev)");
-  StepKey key;
-  key.mode = ctx->mode;
-  key.max_len = bs.held.max_len;
-  key.active = loss.active;
-  key.zero = zero_grads_first != 0;
-  std::copy(ctx->mexplicit, ctx->mexplicit + 5, key.mexplicit);
-  key.slot = ctx->cur_slot;
-  key.feat_type = bs.held.feat_type;
-  key.table = bs.held.n_images > 0;
-  key.bank = bs.held.bank;
-  key.ans_G = bs.held.ans_G;
-  key.B = ctx->cfg.B;
-  key.sel = loss.select_w != nullptr;
-  key.regions = bs.held.regions;
-  key.att = loss.att_w != nullptr;
-  key.att_targets = bs.held.att_targets;
-  key.mrg = loss.merge_w != nullptr;
-  key.tied_x = ctx->xdrop == RAU_XDROP_TIED;
-  key.ans_loss = ctx->answer_loss;
-  key.feat_grad = ctx->feat_grad;
-  key.question = bs.held.question;
+  const StepKey key = step_key(ctx, loss, zero_grads_first != 0);
   if (int rc = upload_hop_weights(ctx, loss)) return rc;
   ctx->mg.valid = false;
   hipGraphExec_t exec = nullptr;
@@ -2284,12 +2257,10 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
     hipGraph_t graph = nullptr;
     HIPC(hipStreamBeginCapture(ctx->st, hipStreamCaptureModeRelaxed));
     ctx->capturing = true;
-    ctx->capture_bwd_forms_dpre = loss.forms_dpre();
     int rc = zero_grads_first ? rau_zero_grads(ctx) : 0;
-    if (!rc) rc = rau_forward(ctx);
+    if (!rc) rc = forward_impl(ctx, loss.forms_dpre());   // such a backward forms dpre / dhn itself
     if (!rc) rc = backward_impl(ctx, loss);
     ctx->capturing = false;
-    ctx->capture_bwd_forms_dpre = false;
     hipError_t e = hipStreamEndCapture(ctx->st, &graph);
     if (rc) {
       if (graph) hipGraphDestroy(graph);
@@ -2311,12 +2282,8 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
   }
   HIPC(hipEventRecord(ctx->evEnd, ctx->st));   // a real (non-captured) end-of-step event
   merge_record(ctx);
-  ctx->fwd_done = false;
-  ctx->bwd_done = true;
-  ctx->graph_last = true;
-  ctx->qg_valid = bs.held.question;
-  ctx->xg_valid = ctx->feat_grad != RAU_FEAT_GRAD_OFF;
-  ctx->xg_rows = xgrad_per_image(ctx) ? cur_batch(ctx).held.n_images : ctx->cfg.B;
+  drop_forward(ctx);
+  record_backward(ctx, true);
   return RAU_OK;
 }
 
@@ -2345,9 +2312,9 @@ int rau_graph_step_merged(rau_ctx* ctx, const float* hop_w, const float* select_
 
 int rau_wait_grads(rau_ctx* ctx, int group, void* hip_stream) {
   if (int rc = check_group(ctx, group)) return rc;
-  if (!ctx->bwd_done) return fail(RAU_ERR_STATE, "rau_wait_grads: no rau_backward to wait for");
+  if (!ctx->bwd.done) return fail(RAU_ERR_STATE, "rau_wait_grads: no rau_backward to wait for");
   hipStream_t s = (hipStream_t)hip_stream;
-  if (group == RAU_GROUP_MULT && !ctx->graph_last) {
+  if (group == RAU_GROUP_MULT && !ctx->bwd.graph) {
     // final once the bulk stream's conv gradients (evD) and the weight-gradient stream's
     // mult block (evM3) are done -- i.e. before the encoder BPTT, which they overlap
     HIPC(hipStreamWaitEvent(s, ctx->evD, 0));
@@ -2372,7 +2339,7 @@ int persist_check(rau_ctx* ctx) {
   ctx->enc_ws = ctx->enc_ws_train = false;
   ctx->persist_gave_up = true;
   ctx->persist_used = false;
-  ctx->fwd_done = false;
+  drop_forward(ctx);
   ctx->mg.valid = false;
   return fail(RAU_ERR_DEVICE, "persistent encoder: a bounded wait on another workgroup's progress counter gave up; "
                               "the results of that step are invalid -- repeat it: this context now uses the "

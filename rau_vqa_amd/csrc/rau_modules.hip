@@ -284,8 +284,8 @@ int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const fl
   hipStream_t st = ctx->st;
   const Masks m = masks_of(ctx);
   const size_t BM_ = (size_t)B * M, BR_ = (size_t)B * R;
-  ctx->I_shared = false;
-  ctx->fwd_done = false;   // the step-level slots are being overwritten
+  ctx->fwd.I_shared = false;
+  drop_forward(ctx);   // the step-level slots are being overwritten
   if (S != SL && !resident) {   // dense [B,D,SL] from the caller -> pitched (pad columns stay 0)
     if (int rc = repitch(ctx, ctx->m_Xp, S, X, SL, (size_t)B * D)) return rc;
     X = ctx->m_Xp;
@@ -294,7 +294,7 @@ int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const fl
   float* qd = ctx->qd + (size_t)h * B * Q;
   RUN("apply_mask", 0, (double)B * Q * 8,
       apply_mask(st, (size_t)B * Q, (size_t)B * Q, q, m.q, m.s_q, qd, (size_t)h * B * Q));
-  ctx->yq_shared = false;   // this path fills the hop's own rows
+  ctx->fwd.yq_shared = false;   // this path fills the hop's own rows
   {
     LinOpts o = lin_opts(ctx, ctx->ws_chain);
     o.bias = ctx->q_proj.b;
