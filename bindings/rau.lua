@@ -124,6 +124,7 @@ int rau_set_batch_dev_images(rau_ctx* ctx, const float* table_dev, int n_images,
                              const int32_t* tokens, const int32_t* lens, const int32_t* labels);
 int rau_outputs_dev(rau_ctx* ctx, const float** logits, const float** dopred, const float** attprob,
                     int32_t* att_pitch);
+int rau_logits_pitch(rau_ctx* ctx, int32_t* pitch);
 int rau_backward_ext(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
                      const float* merge_w, const rau_out_grads* g);
 int rau_embed_forward(rau_ctx* ctx, int t, const int32_t* tokens_dev, float** we);
@@ -569,13 +570,21 @@ function RAU:backward(hop_w, select_w, att_w, merge_w)
   else check(C.rau_backward(self.h, w)) end
 end
 
--- the outputs of the last forward in device memory (rau_outputs_dev): logits [H,n,K], dopred [H,n] and attprob
+-- the outputs of the last forward in device memory (rau_outputs_dev): logits [H,n,K] (rows at logitsPitch()), dopred [H,n] and attprob
 -- [H,n,pitch] as const float* cdata plus the pitch; valid until the next forward, ordered on the ctx's stream
 function RAU:outputsDev()
   local lg, dp, at = ffi.new('const float*[1]'), ffi.new('const float*[1]'), ffi.new('const float*[1]')
   local pitch = ffi.new('int32_t[1]')
   check(C.rau_outputs_dev(self.h, lg, dp, at, pitch))
   return lg[0], dp[0], at[0], pitch[0]
+end
+
+-- row pitch of outputsDev()'s logits (rau_logits_pitch): K where K % 4 == 0, else K rounded up to a multiple of 4
+-- with +0 in columns K..pitch-1
+function RAU:logitsPitch()
+  local pitch = ffi.new('int32_t[1]')
+  check(C.rau_logits_pitch(self.h, pitch))
+  return pitch[0]
 end
 
 -- Feature-map gradient (rau_set_feat_grad): with the switch on every backward / graphStep also leaves the gradient

@@ -100,7 +100,8 @@ typedef struct rau_config {
   int32_t M;    /* multfeat_dim = 512, SS:220 */
   int32_t A;    /* attfeat_dim = 256, SS:221 */
   int32_t R;    /* att_rnn_size = 512, SS:225 (1 layer, dropout 0) */
-  int32_t K;    /* answer_size = 1000, SS:222 */
+  int32_t K;    /* answer_size = 1000, SS:222; any K >= 2 (3129, 3113, 1842 ..): not a multiple of 4: rows padded
+                 * internally (rau_logits_pitch; host-side results stay dense [.., K]) */
   int32_t H;    /* nHop */
   float p_we, p_rnn, p_q, p_x, p_mf;  /* dropout probabilities, 0.5 each (device masks resolve p to
                                        * 1/256; the 1/(1-p) scale uses the same quantised p) */
@@ -118,8 +119,8 @@ int rau_abi_version(void);
 
 /* Builds the three protos + their clones (SS:200-347): allocates parameters,
  * gradients, activations for T tokens and H hops, and the ctx stream.
- * RAU_ERR_INVALID (before the device is touched) for a configuration outside what the kernels take: widths that
- * are no positive multiple of 4, and an S above what the attention kernels' 64 KB of LDS hold -- 4096 positions
+ * RAU_ERR_INVALID (before the device is touched) for a configuration outside what the kernels take: widths (E, Rq,
+ * D, M, A, R) that are no positive multiple of 4, K < 2 (one answer is no classification problem), and an S above what the attention kernels' 64 KB of LDS hold -- 4096 positions
  * for contexts of up to 64 samples, (16352 - A) / 18 above (900 at A = 128); the message names the bound. */
 int rau_create(const rau_config* cfg, rau_ctx** out);
 void rau_destroy(rau_ctx* ctx);
@@ -658,7 +659,12 @@ int rau_merge_criterion_backward(rau_ctx* ctx, const float* logits_dev /* [H,n,K
  * rau_graph_step*); any out argument may be NULL.  n is the CURRENT batch size (rau_set_batch_size), not the
  * capacity, and every tensor is dense in it: logits [H,n,K] with strides (n*K, K, 1), dopred [H,n] with strides
  * (n, 1), attprob [H,n,pitch] with strides (n*pitch, pitch, 1), *att_pitch = pitch = S rounded up to a multiple of
- * 4 (columns S..pitch-1 hold zeros; behind a sample's region count the probabilities are zeros).  The pointers stay
+ * 4 (columns S..pitch-1 hold zeros; behind a sample's region count the probabilities are zeros).
+ * rau_logits_pitch: the logits have a pitch too where K % 4 != 0.  *pitch = K where K % 4 == 0 (dense rows, the
+ * strides above), else K rounded up to a multiple of 4: the logits of rau_outputs_dev then have strides
+ * (n*pitch, pitch, 1) with this pitch, and columns K..pitch-1 of every row hold +0.  The host-side getters
+ * (rau_get_logits, rau_get_merged, rau_topk, ...) always return dense [.., K] rows, and the gradient
+ * rau_backward_ext takes stays DENSE [H,n,K] whatever the pitch (d_logits below), as d_attprob does.  The pointers stay
  * valid until the next forward or rau_set_batch_size; their contents are ordered on the ctx's stream (rau_stream),
  * and the call synchronises nothing: a caller on another stream orders itself behind an event of that stream.
  * Read-only for the caller.  RAU_ERR_STATE when there has been no step-level forward (or a module-level call has
@@ -694,12 +700,13 @@ int rau_merge_criterion_backward(rau_ctx* ctx, const float* logits_dev /* [H,n,K
  * the forward and the backward.  No gradient enters at the last hop's c' / h' (the reference's zeros, SS:561-562) or
  * at the question state. */
 typedef struct rau_out_grads {
-  const float* d_logits;   /* [H,n,K] DEVICE, dense, 16-byte aligned; NULL = no such term */
+  const float* d_logits;   /* [H,n,K] DEVICE, dense (NOT pitched), 16-byte aligned; NULL = no such term */
   const float* d_dopred;   /* [H,n]   DEVICE, dense;                  NULL = no such term */
   const float* d_attprob;  /* [H,n,S] DEVICE, dense (NOT pitched);    NULL = no such term */
 } rau_out_grads;
-int rau_outputs_dev(rau_ctx* ctx, const float** logits /* [H,n,K] */, const float** dopred /* [H,n] */,
+int rau_outputs_dev(rau_ctx* ctx, const float** logits /* [H,n,K] at rau_logits_pitch */, const float** dopred /* [H,n] */,
                     const float** attprob /* [H,n,pitch] */, int32_t* att_pitch);
+int rau_logits_pitch(rau_ctx* ctx, int32_t* pitch);
 int rau_backward_ext(rau_ctx* ctx, const float* hop_w /* [H] host, NULL = zeros */, const float* select_w,
                      const float* att_w, const float* merge_w, const rau_out_grads* g /* NULL = none */);
 

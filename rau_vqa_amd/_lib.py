@@ -161,6 +161,7 @@ _SIGS = {
     # custom objectives: the outputs on the device, caller-supplied gradients into the step-level backward
     "rau_outputs_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                   C.POINTER(C.c_int32)]),
+    "rau_logits_pitch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "rau_backward_ext": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(RauOutGrads)]),
     # feature-map gradient of the step-level backward; a batch whose maps are already on the device

@@ -1,7 +1,8 @@
 """The step-level path as a torch.autograd.Function: a loss written in torch on the step's outputs.
 
 ``step(rau)`` runs ``rau.forward()`` and returns (logits [H,n,K], dopred [H,n], attprob [H,n,S]) as torch tensors
-that carry a gradient function.  ``loss.backward()`` on anything computed from them hands d loss / d output to the
+that carry a gradient function (dense clones: the row pitch of the device buffers, ``RAU.logits_pitch`` for an answer
+count that is no multiple of 4, never shows, and the gradients go back dense).  ``loss.backward()`` on anything computed from them hands d loss / d output to the
 step-level backward (``RAU.backward(..., out_grads=...)``, rau_backward_ext), which accumulates the PARAMETER
 gradients in the ctx's flat buffers -- ``rau.zero_grads()`` before, ``rau.update()`` after, as on every other path.
 The built-in terms (hop_w, select_w, att_w, merge_w) are given to ``step`` and join the same backward.

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void k_bce_fwd(int nB, int K, int M, const flo
     const float* __restrict__ mf, const float* __restrict__ wd, const float* __restrict__ bd,
     float* __restrict__ dl, float* __restrict__ lossrow, int32_t* __restrict__ argmax, float* __restrict__ dopred,
     const float* __restrict__ part, int nsplit, const float* __restrict__ bias, float* __restrict__ logits_out,
-    int Bper) {
+    int Bper, int ld) {
   RAU_CHAIN_PRIO();
   __shared__ float s_val[4];
   __shared__ int s_idx[4];
@@ -62,12 +62,13 @@ __global__ __launch_bounds__(256) void k_bce_fwd(int nB, int K, int M, const flo
     for (int k = tid; k < K; k += 256) {
       float v = bias[k];
       for (int sp = 0; sp < nsplit; ++sp) v += part[((size_t)sp * nB + b) * K + k];
-      logits_out[(size_t)b * K + k] = v;
+      logits_out[(size_t)b * ld + k] = v;
     }
+    for (int k = K + tid; k < ld; k += 256) logits_out[(size_t)b * ld + k] = 0.f;   // the row's pad
     logits = logits_out;
   }
   __syncthreads();   // the set; each thread reads back only the logits it finished itself
-  const float* lg = logits + (size_t)b * K;
+  const float* lg = logits + (size_t)b * ld;
   float mx = -INFINITY;
   int ai = 0x7fffffff;
   for (int k = tid; k < K; k += 256) {
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void k_bce_fwd(int nB, int K, int M, const flo
     float acc = 0.f;
     for (int k = tid; k < K; k += 256) {
       if (!labelled) {   // an unlabelled sample (uniform per workgroup)
-        dl[(size_t)b * K + k] = 0.f;
+        dl[(size_t)b * ld + k] = 0.f;
         continue;
       }
       const float t = bce_target(s_id, s_w, ng, k);
@@ -91,8 +92,9 @@ __global__ __launch_bounds__(256) void k_bce_fwd(int nB, int K, int M, const flo
       acc = __fadd_rn(acc, bce_term(x, t, e));
       const float d = __fadd_rn(1.f, e);
       const float sg = x >= 0.f ? __fdiv_rn(1.f, d) : __fdiv_rn(e, d);
-      dl[(size_t)b * K + k] = __fmul_rn(__fsub_rn(sg, t), invB);
+      dl[(size_t)b * ld + k] = __fmul_rn(__fsub_rn(sg, t), invB);
     }
+    for (int k = K + tid; k < ld; k += 256) dl[(size_t)b * ld + k] = 0.f;   // the row's pad
     acc = block_sum(acc, s_sum);
     if (tid == 0) lossrow[b] = acc;
   }
@@ -109,11 +111,12 @@ __global__ __launch_bounds__(256) void k_bce_fwd(int nB, int K, int M, const flo
 hipError_t bce_fwd(hipStream_t st, int nB, int K, int M, const float* logits, const int32_t* labels,
                    const int32_t* ids, const float* w, int G, const float* mf, const float* wd, const float* bd,
                    float* dl, float* lossrow, int32_t* argmax, float* dopred, const float* part, int nsplit,
-                   const float* bias, float* logits_out, int Bper) {
+                   const float* bias, float* logits_out, int Bper, int ld) {
   if (G < 0 || G > kMaxAnswers || (G > 0 && (!ids || !w))) return hipErrorInvalidValue;
   if (!split_span_ok(part, nsplit, (size_t)nB * K)) return kSplitStateError;
+  if (ld != 0 && ld < K) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_bce_fwd, dim3(nB), dim3(256), 0, st, nB, K, M, logits, labels, ids, w, G, mf, wd, bd, dl,
-                     lossrow, argmax, dopred, part, nsplit, bias, logits_out, Bper > 0 ? Bper : nB);
+                     lossrow, argmax, dopred, part, nsplit, bias, logits_out, Bper > 0 ? Bper : nB, ld ? ld : K);
   return hipGetLastError();
 }
 

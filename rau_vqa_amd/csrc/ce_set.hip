@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void k_ce_set_fwd(int nB, int K, int M, const 
     const float* __restrict__ wd, const float* __restrict__ bd, float* __restrict__ dl,
     float* __restrict__ lossrow, int32_t* __restrict__ argmax, float* __restrict__ dopred,
     const float* __restrict__ part, int nsplit, const float* __restrict__ bias, float* __restrict__ logits_out,
-    int Bper) {
+    int Bper, int ld) {
   RAU_CHAIN_PRIO();
   __shared__ float s_val[4];
   __shared__ int s_idx[4];
@@ -48,12 +48,13 @@ __global__ __launch_bounds__(256) void k_ce_set_fwd(int nB, int K, int M, const 
     for (int k = tid; k < K; k += 256) {
       float v = bias[k];
       for (int sp = 0; sp < nsplit; ++sp) v += part[((size_t)sp * nB + b) * K + k];
-      logits_out[(size_t)b * K + k] = v;
+      logits_out[(size_t)b * ld + k] = v;
     }
+    for (int k = K + tid; k < ld; k += 256) logits_out[(size_t)b * ld + k] = 0.f;   // the row's pad
     logits = logits_out;
   }
   __syncthreads();   // the set, and the finished logits thread 0 reads below
-  const float* lg = logits + (size_t)b * K;
+  const float* lg = logits + (size_t)b * ld;
   float mx = -INFINITY;
   int ai = 0x7fffffff;
   for (int k = tid; k < K; k += 256) {
@@ -78,8 +79,9 @@ __global__ __launch_bounds__(256) void k_ce_set_fwd(int nB, int K, int M, const 
         p = hit ? __fsub_rn(p, s_wb[g]) : __fmaf_rn(e, scale, -s_wb[g]);
         hit = true;
       }
-    dl[(size_t)b * K + k] = p;
+    dl[(size_t)b * ld + k] = p;
   }
+  for (int k = K + tid; k < ld; k += 256) dl[(size_t)b * ld + k] = 0.f;   // the row's pad
   if (tid == 0) {
     float acc = 0.f;
     for (int g = 0; g < G; ++g)
@@ -99,11 +101,12 @@ __global__ __launch_bounds__(256) void k_ce_set_fwd(int nB, int K, int M, const 
 hipError_t ce_set_fwd(hipStream_t st, int nB, int K, int M, const float* logits, const int32_t* ids,
                       const float* w, int G, const float* mf, const float* wd, const float* bd, float* dl,
                       float* lossrow, int32_t* argmax, float* dopred, const float* part, int nsplit,
-                      const float* bias, float* logits_out, int Bper) {
+                      const float* bias, float* logits_out, int Bper, int ld) {
   if (G < 1 || G > kMaxAnswers || !ids || !w) return hipErrorInvalidValue;
   if (!split_span_ok(part, nsplit, (size_t)nB * K)) return kSplitStateError;
+  if (ld != 0 && ld < K) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_ce_set_fwd, dim3(nB), dim3(256), 0, st, nB, K, M, logits, ids, w, G, mf, wd, bd, dl,
-                     lossrow, argmax, dopred, part, nsplit, bias, logits_out, Bper > 0 ? Bper : nB);
+                     lossrow, argmax, dopred, part, nsplit, bias, logits_out, Bper > 0 ? Bper : nB, ld ? ld : K);
   return hipGetLastError();
 }
 

@@ -50,6 +50,29 @@ __global__ __launch_bounds__(256) void k_ext_dl(size_t per4, size_t n4, const fl
   }
 }
 
+// The ragged form (K % 4 != 0): d is dense [H][rows][K], x has rows at pitch ld = K rounded up to a multiple of 4.
+// One thread per element of x; the pad columns K..ld-1 are written +0 whatever they held.  The arithmetic of an
+// element is k_ext_dl's.
+template <bool HAVE_DL, bool HAVE_D>
+__global__ __launch_bounds__(256) void k_ext_dl_rag(size_t rows_per_hop, int K, int ld, size_t n,
+    const float* __restrict__ w, const float* __restrict__ d, float* __restrict__ x) {
+  RAU_CHAIN_PRIO();
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i / (size_t)ld;
+    const int k = (int)(i - row * (size_t)ld);
+    float v = 0.f;
+    if (k < K) {
+      if (HAVE_DL) {
+        v = __fmul_rn(x[i], w[row / rows_per_hop]);
+        if (HAVE_D) v = __fadd_rn(v, d[row * (size_t)K + k]);
+      } else if (HAVE_D) {
+        v = d[row * (size_t)K + k];
+      }
+    }
+    x[i] = v;
+  }
+}
+
 // one 256-thread workgroup per row r = h * Bper + b, as k_select_signal; every thread forms the row's (uniform) s
 template <bool ACC>
 __global__ __launch_bounds__(256) void k_ext_signal(int M, const float* __restrict__ dopred,
@@ -108,7 +131,20 @@ int grid_for(size_t n) { return (int)std::min<size_t>(std::max<size_t>((n + 255)
 
 }  // namespace
 
-hipError_t ext_dl(hipStream_t st, int H, size_t per_hop, const float* w_dev, const float* d, float* dl) {
+hipError_t ext_dl(hipStream_t st, int H, size_t rows_per_hop, int K, int ld, const float* w_dev, const float* d,
+                  float* dl) {
+  if (K < 1 || ld < K) return hipErrorInvalidValue;
+  if (ld != K) {   // dense ragged d into the pitched dl
+    const size_t n = rows_per_hop * H * (size_t)ld;
+    if (n == 0) return hipSuccess;
+    const dim3 grid(grid_for(n)), block(256);
+    if (w_dev && d) hipLaunchKernelGGL((k_ext_dl_rag<true, true>), grid, block, 0, st, rows_per_hop, K, ld, n, w_dev, d, dl);
+    else if (w_dev) hipLaunchKernelGGL((k_ext_dl_rag<true, false>), grid, block, 0, st, rows_per_hop, K, ld, n, w_dev, d, dl);
+    else if (d) hipLaunchKernelGGL((k_ext_dl_rag<false, true>), grid, block, 0, st, rows_per_hop, K, ld, n, w_dev, d, dl);
+    else hipLaunchKernelGGL((k_ext_dl_rag<false, false>), grid, block, 0, st, rows_per_hop, K, ld, n, w_dev, d, dl);
+    return hipGetLastError();
+  }
+  const size_t per_hop = rows_per_hop * (size_t)K;
   const size_t n = per_hop * H;
   if (n == 0) return hipSuccess;
   if ((per_hop & 3) || !aligned16(dl) || (d && !aligned16(d))) return hipErrorInvalidValue;

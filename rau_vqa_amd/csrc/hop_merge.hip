@@ -40,7 +40,7 @@ __device__ void row_ce(const float* __restrict__ lg, size_t hs, int H, int K, in
 
 // One workgroup per sample: rowf[b] = {uni CE, select CE, BCE[H]},
 // rowi[b] = correct[H+2] | do_pred_correct[H] | did_correct | fired[H] | selected[H].
-__global__ __launch_bounds__(kMT) void k_step_stats_rows(int H, int B, int K,
+__global__ __launch_bounds__(kMT) void k_step_stats_rows(int H, int B, int K, int ld,
     const float* __restrict__ logits, const float* __restrict__ dopred,
     const int32_t* __restrict__ argmax, const int32_t* __restrict__ labels,
     float* __restrict__ rowf, int32_t* __restrict__ rowi) {
@@ -48,8 +48,8 @@ __global__ __launch_bounds__(kMT) void k_step_stats_rows(int H, int B, int K,
   __shared__ int s_idx[4];
   __shared__ float s_sum[4];
   const int b = blockIdx.x;
-  const size_t hs = (size_t)B * K;
-  const float* lg = logits + (size_t)b * K;
+  const size_t hs = (size_t)B * ld;   // rows at pitch ld >= K
+  const float* lg = logits + (size_t)b * ld;
   const int y = min(max(labels[b], 1), K) - 1;   // checked at upload; clamped like k_ce_fwd
   const int hsel = select_hop(dopred, H, B, b, false);   // feval: the last hop is not forced
   float ce_u, ce_s;
@@ -112,7 +112,7 @@ __device__ __forceinline__ float set_score(const int* s_id, const float* s_sc, i
 // is correct when it carries a positive score (scores are >= 0: some matching non-empty entry has score > 0),
 // the uni / select CE are the soft CE of ce_set.hip, sum_g w_g (lse - row[y_g]) from 0 in entry order.  Also
 // rowscore [H+2][B]: the score of every row's answer.
-__global__ __launch_bounds__(kMT) void k_step_stats_rows_set(int H, int B, int K,
+__global__ __launch_bounds__(kMT) void k_step_stats_rows_set(int H, int B, int K, int ld,
     const float* __restrict__ logits, const float* __restrict__ dopred, const int32_t* __restrict__ argmax,
     const int32_t* __restrict__ ids, const float* __restrict__ w, const float* __restrict__ score, int G,
     float* __restrict__ rowf, int32_t* __restrict__ rowi, float* __restrict__ rowscore) {
@@ -123,8 +123,8 @@ __global__ __launch_bounds__(kMT) void k_step_stats_rows_set(int H, int B, int K
   __shared__ float s_w[kMaxAnswers];
   __shared__ float s_sc[kMaxAnswers];
   const int b = blockIdx.x;
-  const size_t hs = (size_t)B * K;
-  const float* lg = logits + (size_t)b * K;
+  const size_t hs = (size_t)B * ld;   // rows at pitch ld >= K
+  const float* lg = logits + (size_t)b * ld;
   if (threadIdx.x < G) {
     const size_t e = (size_t)b * G + threadIdx.x;
     const int id = min(max(ids[e], 0), K);
@@ -178,15 +178,15 @@ __global__ __launch_bounds__(kMT) void k_step_stats_rows_set(int H, int B, int K
 // the same target, in bce_head.hip's formulation and summation order (thread-strided in ascending k, block_sum);
 // a row whose set has no non-empty entry: 0.  Runs behind k_step_stats_rows(_set), which leaves everything else --
 // the counts, the do_pred BCE, the scores depend on logits and argmax only.  labels: G = 0.
-__global__ __launch_bounds__(kMT) void k_step_stats_bce(int H, int B, int K, const float* __restrict__ logits,
+__global__ __launch_bounds__(kMT) void k_step_stats_bce(int H, int B, int K, int ld, const float* __restrict__ logits,
     const float* __restrict__ dopred, const int32_t* __restrict__ labels, const int32_t* __restrict__ ids,
     const float* __restrict__ w, int G, float* __restrict__ rowf) {
   __shared__ float s_sum[4];
   __shared__ int s_id[kMaxAnswers];
   __shared__ float s_w[kMaxAnswers];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const size_t hs = (size_t)B * K;
-  const float* lg = logits + (size_t)b * K;
+  const size_t hs = (size_t)B * ld;   // rows at pitch ld >= K
+  const float* lg = logits + (size_t)b * ld;
   const int ng = G > 0 ? G : 1;
   if (G > 0) {
     if (tid < G) {
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(kMT) void k_step_stats_reduce(int H, int B, const f
 // the first-max answer of the row (oe) and of row * mc_mask (mc: the reference multiplies the RAW
 // logits by a 0/1 mask, SS:893-894, so masked-out entries are +-0 and +0 / -0 tie at the lower
 // index); the merged rows go to pred [2][B][K] and att_out [2][B][Sp] (select without any carry).
-__global__ __launch_bounds__(kMT) void k_predict_rows(int H, int B, int K, int Sp,
+__global__ __launch_bounds__(kMT) void k_predict_rows(int H, int B, int K, int ld, int Sp,
     const float* __restrict__ logits, const float* __restrict__ dopred, const float* __restrict__ att,
     const int32_t* __restrict__ mc, int n_mc, int32_t* __restrict__ oe, int32_t* __restrict__ mco,
     float* __restrict__ pred, float* __restrict__ att_out) {
@@ -274,8 +274,8 @@ __global__ __launch_bounds__(kMT) void k_predict_rows(int H, int B, int K, int S
   __shared__ float s_val[4];
   __shared__ int s_idx[4];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const size_t hs = (size_t)B * K;
-  const float* lg = logits + (size_t)b * K;
+  const size_t hs = (size_t)B * ld;   // rows at pitch ld >= K
+  const float* lg = logits + (size_t)b * ld;
   const int hsel = select_hop(dopred, H, B, b, true);   // >= 0: the last hop always fires
   if (mc) {   // test_mc_mask, SS:885-892: 0 = empty slot
     const int nw = (K + 31) / 32;
@@ -290,7 +290,9 @@ __global__ __launch_bounds__(kMT) void k_predict_rows(int H, int B, int K, int S
   for (int r = 0; r < H + 2; ++r) {
     float mx = -INFINITY, mm = -INFINITY;
     int ai = 0x7fffffff, mi = 0x7fffffff;
-    float* prow = (r >= H && pred) ? pred + ((size_t)(r - H) * B + b) * K : nullptr;
+    float* prow = (r >= H && pred) ? pred + ((size_t)(r - H) * B + b) * ld : nullptr;
+    if (prow)   // the merged row's pad
+      for (int k = K + tid; k < ld; k += kMT) prow[k] = 0.f;
     for (int k = tid; k < K; k += kMT) {
       const float v = row_val(lg, hs, H, r, hsel, k);
       if (prow) prow[k] = v;
@@ -323,16 +325,18 @@ __global__ __launch_bounds__(kMT) void k_predict_rows(int H, int B, int K, int S
 
 hipError_t step_stats(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
                       const int32_t* argmax, const float* lossrow, const Truth& t, float* rowf, int32_t* rowi,
-                      float* out, float* rowscore, float* tot) {
+                      float* out, float* rowscore, float* tot, int ld) {
+  if (ld == 0) ld = K;
+  if (ld < K) return hipErrorInvalidValue;
   if (t.G > 0 && (t.G > kMaxAnswers || !t.ids || !t.w || !t.score)) return hipErrorInvalidValue;
   if (t.G > 0)
-    hipLaunchKernelGGL(k_step_stats_rows_set, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, argmax, t.ids,
+    hipLaunchKernelGGL(k_step_stats_rows_set, dim3(B), dim3(kMT), 0, st, H, B, K, ld, logits, dopred, argmax, t.ids,
                        t.w, t.score, t.G, rowf, rowi, rowscore);
   else
-    hipLaunchKernelGGL(k_step_stats_rows, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, argmax, t.labels,
+    hipLaunchKernelGGL(k_step_stats_rows, dim3(B), dim3(kMT), 0, st, H, B, K, ld, logits, dopred, argmax, t.labels,
                        rowf, rowi);
   if (t.bce())   // the two merged rows' losses under the sigmoid criterion, in place of the softmax CE just written
-    hipLaunchKernelGGL(k_step_stats_bce, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, t.labels, t.ids, t.w,
+    hipLaunchKernelGGL(k_step_stats_bce, dim3(B), dim3(kMT), 0, st, H, B, K, ld, logits, dopred, t.labels, t.ids, t.w,
                        t.G, rowf);
   hipLaunchKernelGGL(k_step_stats_reduce, dim3(1), dim3(kMT), 0, st, H, B, lossrow, rowf, rowi, out);
   if (t.G > 0) hipLaunchKernelGGL(k_score_totals, dim3(1), dim3(kMT), 0, st, H + 2, B, rowscore, tot);
@@ -352,8 +356,10 @@ size_t predict_rows_lds(int K) { return (size_t)((K + 31) / 32) * sizeof(uint32_
 
 hipError_t predict_rows(hipStream_t st, int H, int B, int K, int Sp, const float* logits, const float* dopred,
                         const float* att, const int32_t* mc, int n_mc, int32_t* oe, int32_t* mco, float* pred,
-                        float* att_out) {
-  hipLaunchKernelGGL(k_predict_rows, dim3(B), dim3(kMT), mc ? predict_rows_lds(K) : 0, st, H, B, K, Sp, logits,
+                        float* att_out, int ld) {
+  if (ld == 0) ld = K;
+  if (ld < K) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_predict_rows, dim3(B), dim3(kMT), mc ? predict_rows_lds(K) : 0, st, H, B, K, ld, Sp, logits,
                      dopred, att, mc, n_mc, oe, mco, pred, att_out);
   return hipGetLastError();
 }

@@ -415,12 +415,14 @@ hipError_t colsum_acc(hipStream_t st, int rows, int N, const float* X, long ld, 
 // (labels == nullptr: no loss/dl; mf == nullptr: no do_pred)
 // nsplit > 0: the logits arrive as K-split partials `part` [split][nB][K] (+ bias) and are
 // finished here into logits_out
+// ld: row pitch of logits / logits_out / dl (0 = K, dense); the partials stay dense in K.  With ld > K the kernel
+// writes +0 into columns K..ld-1 of every row it writes (dl with a ground truth, logits_out with partials)
 hipError_t ce_fwd(hipStream_t st, int nB, int K, int M, const float* logits,
                   const int32_t* labels, const float* mf, const float* wd, const float* bd,
                   float* dl, float* lossrow, int32_t* argmax, float* dopred,
                   const float* part = nullptr, int nsplit = 0, const float* bias = nullptr,
                   float* logits_out = nullptr,
-                  int Bper = 0 /* rows are [hop][sample]: samples per hop (label period, 1/B) */);
+                  int Bper = 0 /* rows are [hop][sample]: samples per hop (label period, 1/B) */, int ld = 0);
 hipError_t loss_reduce(hipStream_t st, int H, int nB, const float* lossrow, float* losses);
 // ce_fwd against an answer set (ce_set.hip, rau_set_answers): ids / w [Bper][G] device, ids 1..K or 0 = empty
 // entry, 1 <= G <= kMaxAnswers; lossrow = sum_g w (lse - lg[y_g]), dl = softmax * (W / Bper) - sum_g onehot_g w / Bper
@@ -429,7 +431,8 @@ constexpr int kMaxAnswers = 16;
 hipError_t ce_set_fwd(hipStream_t st, int nB, int K, int M, const float* logits, const int32_t* ids,
                       const float* w, int G, const float* mf, const float* wd, const float* bd, float* dl,
                       float* lossrow, int32_t* argmax, float* dopred, const float* part = nullptr,
-                      int nsplit = 0, const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0);
+                      int nsplit = 0, const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0,
+                      int ld = 0);
 // The criterion head as a per-answer sigmoid with binary cross-entropy (bce_head.hip, RAU_LOSS_BCE): ce_fwd's /
 // ce_set_fwd's contract with  t[k] = [k == y]  (labels) or  min(1, sum_g w_g [y_g == k])  (G > 0: ids / w [Bper][G]),
 // lossrow = sum_k max(x,0) - x t + log1p(exp(-|x|)),  dl = (sigmoid(x) - t) / Bper; a row whose set has no non-empty
@@ -437,7 +440,7 @@ hipError_t ce_set_fwd(hipStream_t st, int nB, int K, int M, const float* logits,
 hipError_t bce_fwd(hipStream_t st, int nB, int K, int M, const float* logits, const int32_t* labels,
                    const int32_t* ids, const float* w, int G, const float* mf, const float* wd, const float* bd,
                    float* dl, float* lossrow, int32_t* argmax, float* dopred, const float* part = nullptr,
-                   int nsplit = 0, const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0);
+                   int nsplit = 0, const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0, int ld = 0);
 // The ground truth of a batch: what a criterion, a statistic or the selection head's target is read from.  A plain
 // value: "no ground truth" is Truth{}; G > 0 means the answer set replaces the labels.  `loss` is the criterion the
 // answers are trained with (RAU_LOSS_CE / RAU_LOSS_BCE of include/rau.h): read by criterion_head and step_stats only.
@@ -457,15 +460,16 @@ inline const char* criterion_class(const Truth& t) { return t.bce() ? "bce_fwd" 
 inline hipError_t criterion_head(hipStream_t st, int nB, int K, int M, const float* logits, const Truth& t,
                                  const float* mf, const float* wd, const float* bd, float* dl, float* lossrow,
                                  int32_t* argmax, float* dopred, const float* part = nullptr, int nsplit = 0,
-                                 const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0) {
+                                 const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0,
+                                 int ld = 0) {
   if (t.bce())
     return bce_fwd(st, nB, K, M, logits, t.labels, t.ids, t.w, t.G, mf, wd, bd, dl, lossrow, argmax, dopred, part,
-                   nsplit, bias, logits_out, Bper);
+                   nsplit, bias, logits_out, Bper, ld);
   if (t.G > 0)
     return ce_set_fwd(st, nB, K, M, logits, t.ids, t.w, t.G, mf, wd, bd, dl, lossrow, argmax, dopred, part, nsplit,
-                      bias, logits_out, Bper);
+                      bias, logits_out, Bper, ld);
   return ce_fwd(st, nB, K, M, logits, t.labels, mf, wd, bd, dl, lossrow, argmax, dopred, part, nsplit, bias,
-                logits_out, Bper);
+                logits_out, Bper, ld);
 }
 // The step-selection head's gradient (select_bwd.hip, rau_backward_select).  rows = active hops x Bper, hop-major.
 // select_signal: s[r] = select_w[h] * BCE'(do_pred, do_pred_gt) / Bper * x (1 - x) and add[r][m] = s[r] wd[m];
@@ -490,16 +494,21 @@ hipError_t att_sup_stats(hipStream_t st, int hops, int Bper, int S, const float*
 // dl [H][B][K] += the gradient of  w_uni CE(uni row) + w_sel CE(select row)  at the hop logits [H][B][K], the rows
 // hop_merge.h's under the feval rule (do_pred [H][B], the last hop not forced), the CE against t's labels [B] or
 // (G > 0) its answer set.  The two weights are read from mw_dev [2] (device), or with mw_dev null taken from
-// w_uni / w_sel; a zero weight's term is skipped.  One launch, one workgroup per sample; K % 4 == 0, dl 16-byte aligned.
+// w_uni / w_sel; a zero weight's term is skipped.  One launch, one workgroup per sample; dl 16-byte aligned.
+// ld: row pitch of logits and dl (0 = K, which then must be a multiple of 4; else a multiple of 4 >= K, and the pad
+// columns K..ld-1 of every row of dl the kernel touches leave as +0).
 hipError_t merge_grad(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred, const Truth& t,
-                      const float* mw_dev, float w_uni, float w_sel, float* dl);
+                      const float* mw_dev, float w_uni, float w_sel, float* dl, int ld = 0);
 // Caller-supplied gradients at the step's outputs (ext_grad.hip, rau_backward_ext).  Each one launch, no atomics.
-// ext_dl: dl[h][i] = dl[h][i] * w_dev[h] + d[h][i] over H hops of per_hop floats (per_hop % 4 == 0, 16-byte aligned
-// bases); d null: the product alone; w_dev null (the forward wrote no dl): dl = d exactly, or +0 with d null too.
+// ext_dl: dl[h][r][k] = dl[h][r][k] * w_dev[h] + d[h][r][k] over H hops of rows_per_hop rows of K floats; d dense
+// [H][rows][K], dl rows at pitch ld.  ld == K: 16-byte accesses (rows_per_hop K % 4 == 0, 16-byte aligned bases);
+// ld > K (the answer pitch of a K % 4 != 0 context): one element per thread, +0 written into columns K..ld-1.
+// d null: the product alone; w_dev null (the forward wrote no dl): dl = d exactly, or +0 with d null too.
 // ext_signal: s[r] = (acc ? s[r] : nothing) + (ddp[r] * x) * (1 - x), x = dopred[r]; add[r][m] = s[r] wd[m].
 // ext_da: da[h,b,s] = (acc ? da[h,b,s] : nothing) + d[h,b,s] below the count, +0 elsewhere, over the whole of d_rs;
 // d dense [hops][Bper][S], da rows at pitch d_rs, nreg [Bper] region counts or null.
-hipError_t ext_dl(hipStream_t st, int H, size_t per_hop, const float* w_dev, const float* d, float* dl);
+hipError_t ext_dl(hipStream_t st, int H, size_t rows_per_hop, int K, int ld, const float* w_dev, const float* d,
+                  float* dl);
 hipError_t ext_signal(hipStream_t st, int rows, int M, const float* dopred, const float* ddp, const float* wd,
                       bool acc, float* s, float* add);
 hipError_t ext_da(hipStream_t st, int hops, int Bper, int S, const float* d, const int32_t* nreg, bool acc,
@@ -567,16 +576,17 @@ hipError_t adamax_vec(hipStream_t st, size_t n, float* x, const float* dx, float
 // t.bce(): the uni / select losses are bce_fwd's criterion of those rows instead; nothing else changes
 hipError_t step_stats(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
                       const int32_t* argmax, const float* lossrow, const Truth& t, float* rowf, int32_t* rowi,
-                      float* out, float* rowscore, float* tot);
+                      float* out, float* rowscore, float* tot, int ld = 0 /* row pitch of logits, 0 = K */);
 // out[r][b] = sum_g score[b][g] * [ids[b][g] == ans[r][b]] over t's set in entry order (ans 1-based, [R][B]),
 // tot[r] = the fixed-order sum of row r over the batch
 hipError_t answer_scores(hipStream_t st, int R, int B, int K, const int32_t* ans, const Truth& t, float* out,
                          float* tot);
 // predict_result's merges + answers (SS:633-705, 877-900): oe / mco [H+2][B] 1-based, pred [2][B][K] and
-// att_out [2][B][Sp] (uni, select; either may be null); mc [B][n_mc] device ids 0..K (null: no MC)
+// att_out [2][B][Sp] (uni, select; either may be null); mc [B][n_mc] device ids 0..K (null: no MC).  ld: row pitch
+// of logits AND of pred (0 = K); with ld > K the pad columns of pred are written +0
 hipError_t predict_rows(hipStream_t st, int H, int B, int K, int Sp, const float* logits, const float* dopred,
                         const float* att, const int32_t* mc, int n_mc, int32_t* oe, int32_t* mco, float* pred,
-                        float* att_out);
+                        float* att_out, int ld = 0);
 // dynamic LDS bytes predict_rows takes with an MC list
 size_t predict_rows_lds(int K);
 // torch.topk(x, k, 2, true, true) of x [rows][cols] in the total order of include/rau.h (topk.hip):
@@ -585,6 +595,6 @@ hipError_t topk_rows(hipStream_t st, const float* x, int rows, int cols, int k, 
 // the k best answers of predict_result's rows (hops, uni, select; last hop forced): ids / score / conf
 // [H+2][B][k], conf = softmax probability in row_ce's formulation; none may be null
 hipError_t topk_merged(hipStream_t st, int H, int B, int K, int k, const float* logits, const float* dopred,
-                       int32_t* ids, float* score, float* conf);
+                       int32_t* ids, float* score, float* conf, int ld = 0 /* row pitch of logits, 0 = K */);
 
 }  // namespace rau

@@ -1843,7 +1843,7 @@ __global__ void k_ce_fwd(int nB, int K, int M, const float* __restrict__ logits,
                          int32_t* __restrict__ argmax, float* __restrict__ dopred,
                          const float* __restrict__ part, int nsplit,
                          const float* __restrict__ bias, float* __restrict__ logits_out,
-                         int Bper) {
+                         int Bper, int ld) {
   RAU_CHAIN_PRIO();
   __shared__ float s_val[4];
   __shared__ int s_idx[4];
@@ -1854,12 +1854,13 @@ __global__ void k_ce_fwd(int nB, int K, int M, const float* __restrict__ logits,
     for (int k = tid; k < K; k += 256) {
       float v = bias[k];
       for (int sp = 0; sp < nsplit; ++sp) v += part[((size_t)sp * nB + b) * K + k];
-      logits_out[(size_t)b * K + k] = v;
+      logits_out[(size_t)b * ld + k] = v;
     }
+    for (int k = K + tid; k < ld; k += 256) logits_out[(size_t)b * ld + k] = 0.f;   // the row's pad
     __syncthreads();   // the label's logit below is read by thread 0
     logits = logits_out;
   }
-  const float* lg = logits + (size_t)b * K;
+  const float* lg = logits + (size_t)b * ld;
   // max + first argmax
   float mx = -INFINITY;
   int ai = 0x7fffffff;
@@ -1894,8 +1895,9 @@ __global__ void k_ce_fwd(int nB, int K, int M, const float* __restrict__ logits,
     for (int k = tid; k < K; k += 256) {
       float p = expf(lg[k] - lse) * invB;
       if (k == y) p -= invB;
-      dl[(size_t)b * K + k] = p;
+      dl[(size_t)b * ld + k] = p;
     }
+    for (int k = K + tid; k < ld; k += 256) dl[(size_t)b * ld + k] = 0.f;   // the row's pad
     if (tid == 0) lossrow[b] = lse - lg[y];
   }
   // do_pred
@@ -1911,11 +1913,12 @@ __global__ void k_ce_fwd(int nB, int K, int M, const float* __restrict__ logits,
 hipError_t ce_fwd(hipStream_t st, int nB, int K, int M, const float* logits,
                   const int32_t* labels, const float* mf, const float* wd, const float* bd,
                   float* dl, float* lossrow, int32_t* argmax, float* dopred, const float* part,
-                  int nsplit, const float* bias, float* logits_out, int Bper) {
+                  int nsplit, const float* bias, float* logits_out, int Bper, int ld) {
   if (!split_span_ok(part, nsplit, (size_t)nB * K)) return kSplitStateError;
+  if (ld != 0 && ld < K) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_ce_fwd, dim3(nB), dim3(256), 0, st, nB, K, M, logits, labels, mf, wd, bd,
                      dl, lossrow, argmax, dopred, part, nsplit, bias, logits_out,
-                     Bper > 0 ? Bper : nB);
+                     Bper > 0 ? Bper : nB, ld ? ld : K);
   return hipGetLastError();
 }
 

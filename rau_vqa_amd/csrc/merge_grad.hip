@@ -19,9 +19,10 @@
 // their max and sum of expf(v - max) in the criterion's order (thread-strided, block_sum).  Where 2 K floats fit in
 // kMergeLds bytes the rows are kept in LDS and pass 2 reads them back 16 bytes wide; otherwise pass 2 recomputes
 // them.  8 KB of LDS at K = 1000 leaves the workgroups per CU to the wave slots, not to the LDS.  Pass 2 is the
-// read-modify-write of dl[h,b,:] for every hop that receives a term, 16 bytes per access (K % 4 == 0 by
-// rau_create's rule).  A workgroup owns its sample's rows of dl: no atomics, no scratch in device memory, the same
-// bits on every call.
+// read-modify-write of dl[h,b,:] for every hop that receives a term, 16 bytes per access over the row pitch ld (a
+// multiple of 4; K itself where K % 4 == 0).  kRag (ld > K): the last quad's lanes behind K take no term and leave
+// as +0; the staged rows sit at pitch ld, so what decides the staging is 2 ld floats.  A workgroup owns its sample's
+// rows of dl: no atomics, no scratch in device memory, the same bits on every call.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -31,15 +32,15 @@
 namespace rau {
 namespace {
 
-constexpr size_t kMergeLds = 32768;   // bytes of LDS the two staged rows may take: K <= 4096
+constexpr size_t kMergeLds = 32768;   // bytes of LDS the two staged rows may take: a pitch of up to 4096
 
-template <bool kStage>
-__global__ __launch_bounds__(kMT) void k_merge_grad(int H, int B, int K, const float* __restrict__ logits,
+template <bool kStage, bool kRag>
+__global__ __launch_bounds__(kMT) void k_merge_grad(int H, int B, int K, int ld, const float* __restrict__ logits,
     const float* __restrict__ dopred, const int32_t* __restrict__ labels, const int32_t* __restrict__ ids,
     const float* __restrict__ w, int G, const float* __restrict__ mw_dev, float w_uni, float w_sel,
     float* __restrict__ dl) {
   RAU_CHAIN_PRIO();
-  extern __shared__ float4 s_rows4[];   // kStage: the uni row [K], then the select row [K]
+  extern __shared__ float4 s_rows4[];   // kStage: the uni row [ld], then the select row [ld]
   __shared__ float s_val[4];
   __shared__ int s_idx[4];
   __shared__ float s_sum[4];
@@ -52,8 +53,8 @@ __global__ __launch_bounds__(kMT) void k_merge_grad(int H, int B, int K, const f
   const int hsel = select_hop(dopred, H, B, b, false);   // feval: the last hop is not forced
   const bool term[2] = {wu != 0.f, ws != 0.f && hsel >= 0};
   if (!term[0] && !term[1]) return;   // uniform over the workgroup
-  const size_t hs = (size_t)B * K;
-  const float* lg = logits + (size_t)b * K;
+  const size_t hs = (size_t)B * ld;
+  const float* lg = logits + (size_t)b * ld;
   const float invB = 1.f / (float)B;
   const int Gs = G > 0 ? G : 1;   // a label is a set of one entry with weight 1
   if (tid < Gs) {
@@ -83,27 +84,27 @@ __global__ __launch_bounds__(kMT) void k_merge_grad(int H, int B, int K, const f
     int ai = 0x7fffffff;
     for (int k = tid; k < K; k += kMT) {
       const float v = row_val(lg, hs, H, H + r, hsel, k);
-      if (kStage) s_rows[(size_t)r * K + k] = v;
+      if (kStage) s_rows[(size_t)r * ld + k] = v;
       if (v > mx) { mx = v; ai = k; }
     }
     block_first_max(mx, ai, s_val, s_idx);
     float den = 0.f;
     for (int k = tid; k < K; k += kMT)   // (a thread re-reads the entries it staged itself)
-      den += expf((kStage ? s_rows[(size_t)r * K + k] : row_val(lg, hs, H, H + r, hsel, k)) - mx);
+      den += expf((kStage ? s_rows[(size_t)r * ld + k] : row_val(lg, hs, H, H + r, hsel, k)) - mx);
     den = block_sum(den, s_sum);   // its barriers also publish the staged row to the workgroup
     lse[r] = mx + logf(den);
   }
   // ---- pass 2: dl[h,b,:] of every hop that receives a term
   const float cu = __fdiv_rn(wu, (float)H);
-  float* dlb = dl + (size_t)b * K;
-  for (int k0 = tid * 4; k0 < K; k0 += kMT * 4) {
+  float* dlb = dl + (size_t)b * ld;
+  for (int k0 = tid * 4; k0 < ld; k0 += kMT * 4) {
     float g[2][4] = {};
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       if (!term[r]) continue;
       float v[4];
       if (kStage) {
-        const float4 q = s_rows4[((size_t)r * K + k0) >> 2];
+        const float4 q = s_rows4[((size_t)r * ld + k0) >> 2];
         v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
       } else {
 #pragma unroll
@@ -111,6 +112,7 @@ __global__ __launch_bounds__(kMT) void k_merge_grad(int H, int B, int K, const f
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
+        if (kRag && k0 + j >= K) continue;   // a pad lane: no term (g stays 0; what v holds there is not a logit)
         const float e = expf(v[j] - lse[r]);
         float p = __fmul_rn(e, scale);
         bool hit = false;
@@ -132,6 +134,7 @@ __global__ __launch_bounds__(kMT) void k_merge_grad(int H, int B, int K, const f
       for (int j = 0; j < 4; ++j) {
         if (term[0]) x[j] = __fadd_rn(x[j], __fmul_rn(cu, g[0][j]));
         if (sel_here) x[j] = __fadd_rn(x[j], __fmul_rn(ws, g[1][j]));
+        if (kRag && k0 + j >= K) x[j] = 0.f;   // the pad leaves as +0
       }
       *p4 = make_float4(x[0], x[1], x[2], x[3]);
     }
@@ -141,17 +144,24 @@ __global__ __launch_bounds__(kMT) void k_merge_grad(int H, int B, int K, const f
 }  // namespace
 
 hipError_t merge_grad(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred, const Truth& t,
-                      const float* mw_dev, float w_uni, float w_sel, float* dl) {
+                      const float* mw_dev, float w_uni, float w_sel, float* dl, int ld) {
   if (B <= 0) return hipSuccess;
-  if (H < 1 || K < 4 || (K & 3) || t.G < 0 || t.G > kMaxAnswers || (t.G > 0 ? !t.ids || !t.w : !t.labels))
+  if (ld == 0) ld = K;
+  if (H < 1 || K < 1 || ld < K || (ld & 3) || t.G < 0 || t.G > kMaxAnswers || (t.G > 0 ? !t.ids || !t.w : !t.labels))
     return hipErrorInvalidValue;
-  const size_t rows = (size_t)2 * K * sizeof(float);
-  if (rows <= kMergeLds)
-    hipLaunchKernelGGL(k_merge_grad<true>, dim3(B), dim3(kMT), rows, st, H, B, K, logits, dopred, t.labels, t.ids,
-                       t.w, t.G, mw_dev, w_uni, w_sel, dl);
-  else
-    hipLaunchKernelGGL(k_merge_grad<false>, dim3(B), dim3(kMT), 0, st, H, B, K, logits, dopred, t.labels, t.ids, t.w,
-                       t.G, mw_dev, w_uni, w_sel, dl);
+  const size_t rows = (size_t)2 * ld * sizeof(float);   // what is staged: the two rows at the pitch
+  const bool stage = rows <= kMergeLds;
+#define RAU_MERGE_GRAD(S, R)                                                                                       \
+  hipLaunchKernelGGL((k_merge_grad<S, R>), dim3(B), dim3(kMT), S ? rows : 0, st, H, B, K, ld, logits, dopred,      \
+                     t.labels, t.ids, t.w, t.G, mw_dev, w_uni, w_sel, dl)
+  if (ld == K) {
+    if (stage) RAU_MERGE_GRAD(true, false);
+    else RAU_MERGE_GRAD(false, false);
+  } else {
+    if (stage) RAU_MERGE_GRAD(true, true);
+    else RAU_MERGE_GRAD(false, true);
+  }
+#undef RAU_MERGE_GRAD
   return hipGetLastError();
 }
 

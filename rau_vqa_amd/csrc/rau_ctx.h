@@ -301,6 +301,8 @@ struct rau_ctx {
   int Q;
   int Sp = 0;                 // position pitch: cfg.S rounded up to a multiple of 4 (7x7 maps: 49 -> 52);
                               // every [.., S]-shaped device tensor uses it, pad columns hold zeros
+  int Kp = 0;                 // answer pitch: cfg.K rounded up to a multiple of 4 (3129 -> 3132); the row pitch of
+                              // logits, dl and mg.pred, pad columns hold +0.  K % 4 == 0: Kp == K, nothing changes
   int bf16 = 0;               // cfg.dtype == RAU_BF16: bf16-operand conv GEMMs
   hipStream_t st = nullptr;    // chain stream: recurrences, small GEMMs; what callers order against
   hipStream_t st2 = nullptr;   // bulk stream: hop-batched 1x1-conv GEMMs, overlapped with the chain
@@ -459,6 +461,11 @@ inline BatchSlot& cur_batch(rau_ctx* ctx) { return ctx->slot[ctx->cur_slot]; }
 inline const BatchSlot& cur_batch(const rau_ctx* ctx) { return ctx->slot[ctx->cur_slot]; }
 // The last forward has no backward any more, and nothing else: callers that also drop mg.valid say so next to this
 inline void drop_forward(rau_ctx* ctx) { ctx->fwd.done = false; }
+// The module-level calls that exchange dense [B,K] tensors with the caller need K % 4 == 0 (their rows feed the
+// 16-byte loaders directly): on any other context they are refused before anything is launched.
+#define NEED_DENSE_K(ctx, fn)                                                                              \
+  NEED((ctx)->Kp == (ctx)->cfg.K, "%s: module-level calls exchange dense [B,K] rows and need K %% 4 == 0 " \
+       "(K=%d); use the step-level path", fn, (ctx)->cfg.K)
 // What the hop chain reads as the question state: the caller's (rau_set_question_dev) or the built-in encoder's
 inline const float* question_state(const rau_ctx* ctx) {
   const BatchSlot& s = cur_batch(ctx);

@@ -56,13 +56,13 @@ static int prof_collect(rau_ctx* ctx) {
 // dimension = position pitch, Linear size = logical S).
 static int mult_wgrad_problems(rau_ctx* ctx, TnProblem* pr) {
   const rau_config& c = ctx->cfg;
-  const int S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R, K = c.K, Q = ctx->Q;
+  const int S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R, Q = ctx->Q;
   const size_t BR_ = (size_t)c.B * R;
   const float* hprev = ctx->hh;            // h_{0..H-1}
   const float* hnew = ctx->hh + BR_;       // h_{1..H}
   struct WG { Lin* l; const float* dY; long ldy; const float* X; long ldx; };
   const WG wgs[] = {
-      {&ctx->cls, ctx->dl, K, ctx->mf, M},             {&ctx->lstm_out, ctx->dpre, M, hnew, R},
+      {&ctx->cls, ctx->dl, ctx->Kp, ctx->mf, M},            {&ctx->lstm_out, ctx->dpre, M, hnew, R},
       {&ctx->lstm_i2h, ctx->dg4, 4 * R, ctx->j, M},    {&ctx->lstm_h2h, ctx->dg4, 4 * R, hprev, R},
       {&ctx->feat_attprob, ctx->dj, M, ctx->a, S},     {&ctx->att_mem, ctx->dz, S, hprev, R},
       {&ctx->att_q, ctx->du, A, ctx->qf, M},           {&ctx->q_proj, ctx->dqt, M, ctx->qd, Q},
@@ -263,7 +263,7 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   NEED(c.B > 0 && c.T > 0 && c.V > 1 && c.H > 0, "rau_create: B,T,H must be > 0 and V > 1");
   NEED(c.E > 0 && c.E % 4 == 0, "rau_create: E=%d must be a positive multiple of 4", c.E);
   NEED(c.S > 0, "rau_create: S=%d must be positive", c.S);
-  NEED(c.K > 0 && c.K % 4 == 0, "rau_create: K=%d must be a positive multiple of 4", c.K);
+  NEED(c.K >= 2, "rau_create: K=%d: a classification problem has at least two answers", c.K);
   NEED(c.Rq > 0 && c.Rq % 4 == 0 && c.R > 0 && c.R % 4 == 0 && c.M > 0 && c.M % 4 == 0 &&
            c.A > 0 && c.A % 4 == 0 && c.D > 0 && c.D % 4 == 0,
        "rau_create: Rq,R,M,A,D must be positive multiples of 4");
@@ -297,6 +297,7 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   ctx->cfg = c;
   ctx->Q = 4 * c.Rq;
   ctx->Sp = (c.S + 3) & ~3;
+  ctx->Kp = (c.K + 3) & ~3;
   ctx->bf16 = c.dtype;   // 0 exact f32, 1 bf16-rounded operands, 2 split operands (conv GEMMs)
   // The device Philox masks keep an element when an 8-bit draw >= round(p * 256) (fill_masks): the
   // effective drop probability is p quantised to 1/256, and the inverted-dropout scale 1/(1-p)
@@ -507,8 +508,8 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   CK(dalloc(ctx, &ctx->hh, (HB + B) * R));
   CK(dalloc(ctx, &ctx->tc, HB * R));
   CK(dalloc(ctx, &ctx->mf, HB * M));
-  CK(dalloc(ctx, &ctx->logits, HB * K));
-  CK(dalloc(ctx, &ctx->dl, HB * K));
+  CK(dalloc(ctx, &ctx->logits, HB * ctx->Kp));   // rows at the answer pitch, +0 in the pad
+  CK(dalloc(ctx, &ctx->dl, HB * ctx->Kp));
   CK(dalloc(ctx, &ctx->lossrow, HB));
   CK(dalloc(ctx, &ctx->dopred, HB));
   CK(dalloc(ctx, &ctx->losses_d, (size_t)H));
@@ -1067,14 +1068,14 @@ int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const Tru
   const rau_config& c = ctx->cfg;
   hipStream_t s = ws.owner;
   const size_t reg = ws.floats / 4;
-  const int B = c.B, M = c.M, R = c.R, K = c.K;
+  const int B = c.B, M = c.M, R = c.R, K = c.K, Kp = ctx->Kp;
   const Masks m = masks_of(ctx);
   const size_t BM_ = (size_t)B * M, BR_ = (size_t)B * R;
   const int rows = nh * B;
   const float* hnew = ctx->hh + (size_t)(h0 + 1) * BR_;
   const float* jh = ctx->j + (size_t)h0 * BM_;
   float* mfh = ctx->mf + (size_t)h0 * BM_;
-  float* lg = ctx->logits + (size_t)h0 * B * K;
+  float* lg = ctx->logits + (size_t)h0 * B * Kp;
   int ns_c = 0;
   {
     LinOpts o = lin_opts(ctx, ws);
@@ -1090,12 +1091,12 @@ int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const Tru
     LinOpts o = lin_opts(ctx, ws);
     o.slab = ws.slab + reg; o.slab_floats = reg; o.defer_splits = &ns_c;
     RUNS(s, "head_gemm", gflop(rows, K, M), 0,
-         gemm_nt(s, rows, K, M, mfh, M, ctx->cls.W, M, lg, K, o));
+         gemm_nt(s, rows, K, M, mfh, M, ctx->cls.W, M, lg, Kp, o));
   }
   RUNS(s, criterion_class(truth), 0, (double)rows * K * 12,
-       criterion_head(s, rows, K, M, lg, truth, mfh, ctx->do_pred.W, ctx->do_pred.b, ctx->dl + (size_t)h0 * B * K,
+       criterion_head(s, rows, K, M, lg, truth, mfh, ctx->do_pred.W, ctx->do_pred.b, ctx->dl + (size_t)h0 * B * Kp,
                       ctx->lossrow + (size_t)h0 * B, ctx->argmax_d + (size_t)h0 * B, ctx->dopred + (size_t)h0 * B,
-                      ws.slab + reg, ns_c, ctx->cls.b, lg, B));
+                      ws.slab + reg, ns_c, ctx->cls.b, lg, B, Kp));
   return RAU_OK;
 }
 
@@ -1151,7 +1152,7 @@ int hop_backward(rau_ctx* ctx, int h, const float* cp, const float* Ih, const Ho
       o.add_rs = M;
       o.emask = m.mf; o.emask_e0 = (size_t)h * BM_; o.emscale = m.s_mf;
       RUN("small_gemm", gflop(B, M, K), 0,
-          gemm_nn(st, B, M, K, g.dl, K, ctx->cls.W, M, dpre, M, o));
+          gemm_nn(st, B, M, K, g.dl, ctx->Kp, ctx->cls.W, M, dpre, M, o));
     }
     // dhn = dpre Wo + dh_next, the K-split partials of dpre Wo summed inside lstm_bwd
     int nsp = 0;
@@ -1505,7 +1506,8 @@ static int head_dgrad(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const fl
   if (addend) { o.addend = addend; o.add_rs = M; }
   o.emask = m.mf; o.emask_e0 = (size_t)h0 * BM_; o.emscale = m.s_mf;
   RUNS(s, "head_dgrad", gflop(nh * B, M, K), 0,
-       gemm_nn(s, nh * B, M, K, ctx->dl + (size_t)h0 * B * K, K, ctx->cls.W, M, ctx->dpre + (size_t)h0 * BM_, M, o));
+       gemm_nn(s, nh * B, M, K, ctx->dl + (size_t)h0 * B * ctx->Kp, ctx->Kp, ctx->cls.W, M,
+               ctx->dpre + (size_t)h0 * BM_, M, o));
   const LinOpts o2 = lin_opts(ctx, ws);
   RUNS(s, "head_dgrad", gflop(nh * B, R, M), 0,
        gemm_nn(s, nh * B, R, M, ctx->dpre + (size_t)h0 * BM_, M, ctx->lstm_out.W, R, ctx->dhn + (size_t)h0 * BR_, R,
@@ -1701,7 +1703,7 @@ static int loss_gradients(rau_ctx* ctx, const StepLoss& loss, const Truth& t) {
   const bool sel = loss.select_w != nullptr, att = loss.att_w != nullptr, mrg = loss.merge_w != nullptr;
   const rau_out_grads& ext = loss.ext;
   const rau_config& c = ctx->cfg;
-  const int B = c.B, S = ctx->Sp, SL = c.S, M = c.M, R = c.R, K = c.K, H = c.H, HA = loss.active;
+  const int B = c.B, S = ctx->Sp, SL = c.S, M = c.M, R = c.R, K = c.K, Kp = ctx->Kp, H = c.H, HA = loss.active;
   const HopwLayout at(H);
   const BatchSlot& bs = cur_batch(ctx);
   hipStream_t st = ctx->st;
@@ -1711,17 +1713,17 @@ static int loss_gradients(rau_ctx* ctx, const StepLoss& loss, const Truth& t) {
   if (ext.d_logits || (loss.has_ext() && !ctx->fwd.dl))
     // one pass in scale_hops' place: dl * hop_w + d_logits; without a criterion gradient dl = d_logits (or +0)
     RUN("ext_dl", (double)H * B * K * (ctx->fwd.dl ? 2 : 0), (double)H * B * K * (ctx->fwd.dl ? 12 : 8),
-        ext_dl(st, H, (size_t)B * K, ctx->fwd.dl ? ctx->hopw_d : nullptr, ext.d_logits, ctx->dl));
+        ext_dl(st, H, (size_t)B, K, Kp, ctx->fwd.dl ? ctx->hopw_d : nullptr, ext.d_logits, ctx->dl));
   else if (ctx->fwd.dpre && !loss.forms_dpre())   // the forward formed dpre / dhn from the unscaled dl: scale all three
     RUN("scale_hops", 0, (double)H * B * (K + M + R) * 8,
-        scale_hops3(st, H, ctx->hopw_d, (size_t)B * K, ctx->dl, (size_t)B * M, ctx->dpre, (size_t)B * R, ctx->dhn));
+        scale_hops3(st, H, ctx->hopw_d, (size_t)B * Kp, ctx->dl, (size_t)B * M, ctx->dpre, (size_t)B * R, ctx->dhn));
   else
-    RUN("scale_hops", 0, (double)H * B * K * 8, scale_hops(st, H, (size_t)B * K, ctx->hopw_d, ctx->dl));
+    RUN("scale_hops", 0, (double)H * B * K * 8, scale_hops(st, H, (size_t)B * Kp, ctx->hopw_d, ctx->dl));
   // mrg: w_uni dCE(uni row) + w_sel dCE(select row) join the scaled dl of every hop, in front of all its consumers
   // (head_dgrad and sel_add below, the classifier's weight gradient in mult_wgrads)
   if (mrg)
     RUN("merge_grad", 0, (double)H * B * K * 16,
-        merge_grad(st, H, B, K, ctx->logits, ctx->dopred, t, ctx->hopw_d + at.merge_w, 0.f, 0.f, ctx->dl));
+        merge_grad(st, H, B, K, ctx->logits, ctx->dopred, t, ctx->hopw_d + at.merge_w, 0.f, 0.f, ctx->dl, Kp));
   // ---------------- RAU BPTT, SS:561-578
   // Off the recurrence: dpre = (dl Wc) (.) mask and dhn = dpre Wo for all active hops at once.
   // sel: the gradient through do_pred, s (x) wd, joins dl Wc in front of the mask (HopGrad::dmf_add's position).
@@ -2016,7 +2018,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
     if (int rc = merge_state(ctx, sel ? "rau_backward_select" : "rau_backward_merged", true)) return rc;
   const Truth t = ctx->capturing ? step_truth(ctx) : ctx->mg.truth;
   const rau_config& c = ctx->cfg;
-  const int B = c.B, S = ctx->Sp, M = c.M, R = c.R, K = c.K, Q = ctx->Q;
+  const int B = c.B, S = ctx->Sp, M = c.M, R = c.R, Q = ctx->Q;
   // Backward launch groups of the bulk stream.  Forward groups want to be large (the flattened-
   // column kernels lose a ragged last round per launch); the backward kernels do not (per-sample
   // dgrad tiles and the split-K weight gradients fill whole rounds at any hop count), and a
@@ -2041,7 +2043,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
     float* dc_out = ctx->dcn[h & 1];
     {
       HopGrad g{};
-      g.dl = ctx->dl + (size_t)h * B * K;
+      g.dl = ctx->dl + (size_t)h * B * ctx->Kp;
       g.dc_next = dc_next;
       g.dc_out = dc_out;
       g.dpre_ready = 1;
@@ -2230,6 +2232,11 @@ int rau_outputs_dev(rau_ctx* ctx, const float** logits, const float** dopred, co
   if (att_pitch) *att_pitch = ctx->Sp;
   return RAU_OK;
 }
+int rau_logits_pitch(rau_ctx* ctx, int32_t* pitch) {
+  NEED(ctx && pitch, "rau_logits_pitch: null argument");
+  *pitch = ctx->Kp;
+  return RAU_OK;
+}
 
 // One training step's forward + backward (optionally with the gradient zeroing in front) as ONE
 // hipGraph launch.  The three streams, their fork/join events and every kernel argument are
@@ -2366,7 +2373,13 @@ int rau_get_argmax(rau_ctx* ctx, int32_t* ans) {
 }
 int rau_get_logits(rau_ctx* ctx, float* logits) {
   NEED(ctx, "null ctx");
-  return d2h(ctx, logits, ctx->logits, (size_t)ctx->cfg.H * ctx->cfg.B * ctx->cfg.K * 4);
+  NEED(logits, "null argument");
+  const rau_config& c = ctx->cfg;   // dense [H,n,K] on the host, rows at the answer pitch on the device
+  if (ctx->Kp == c.K) return d2h(ctx, logits, ctx->logits, (size_t)c.H * c.B * c.K * 4);
+  HIPC(hipMemcpy2DAsync(logits, (size_t)c.K * 4, ctx->logits, (size_t)ctx->Kp * 4, (size_t)c.K * 4, (size_t)c.H * c.B,
+                        hipMemcpyDeviceToHost, ctx->st));
+  HIPC(hipStreamSynchronize(ctx->st));
+  return persist_check(ctx);
 }
 int rau_get_dopred(rau_ctx* ctx, float* dopred) {
   NEED(ctx, "null ctx");

@@ -18,7 +18,7 @@ int merge_alloc(rau_ctx* ctx) {
   CK(dalloc(ctx, &ctx->mg.rowi, B * RAU_STATS_NCOUNTS(H)));
   CK(dalloc(ctx, &ctx->mg.out, (2 * H + 2) + RAU_STATS_NCOUNTS(H)));
   CK(dalloc(ctx, &ctx->mg.ans, 2 * (H + 2) * B));
-  CK(dalloc(ctx, &ctx->mg.pred, 2 * B * c.K));
+  CK(dalloc(ctx, &ctx->mg.pred, 2 * B * ctx->Kp));   // rows at the answer pitch, like the logits
   CK(dalloc(ctx, &ctx->mg.att, 2 * B * ctx->Sp));
   CK(dalloc(ctx, &ctx->mg.score, 2 * (H + 2) * B + 2 * (H + 2)));
 #undef CK
@@ -60,7 +60,7 @@ int rau_step_stats(rau_ctx* ctx, float* loss, float* loss_do_pred, int32_t* coun
   const int H = c.H, B = c.B, K = c.K, NL = 2 * H + 2, NC = RAU_STATS_NCOUNTS(H);
   RUN("step_stats", 0, (double)B * (2 * H + 2) * K * 4,
       step_stats(ctx->st, H, B, K, ctx->logits, ctx->dopred, ctx->argmax_d, ctx->lossrow, ctx->mg.truth, ctx->mg.rowf,
-                 ctx->mg.rowi, ctx->mg.out, ctx->mg.score, ctx->mg.score + (size_t)2 * (H + 2) * ctx->cap));
+                 ctx->mg.rowi, ctx->mg.out, ctx->mg.score, ctx->mg.score + (size_t)2 * (H + 2) * ctx->cap, ctx->Kp));
   std::vector<float> out((size_t)NL + NC);
   if (int rc = d2h(ctx, out.data(), ctx->mg.out, out.size() * 4)) return rc;
   if (loss) std::memcpy(loss, out.data(), (size_t)(H + 2) * 4);
@@ -108,7 +108,7 @@ int rau_step_scores(rau_ctx* ctx, float* per_sample, float* total) {
   float* tot_d = ctx->mg.score + (size_t)2 * (H + 2) * ctx->cap;
   RUN("step_stats", 0, (double)B * (2 * H + 2) * K * 4,
       step_stats(ctx->st, H, B, K, ctx->logits, ctx->dopred, ctx->argmax_d, ctx->lossrow, ctx->mg.truth, ctx->mg.rowf,
-                 ctx->mg.rowi, ctx->mg.out, ctx->mg.score, tot_d));
+                 ctx->mg.rowi, ctx->mg.out, ctx->mg.score, tot_d, ctx->Kp));
   if (per_sample)
     HIPC(hipMemcpyAsync(per_sample, ctx->mg.score, (size_t)(H + 2) * B * 4, hipMemcpyDeviceToHost, ctx->st));
   if (total) HIPC(hipMemcpyAsync(total, tot_d, (size_t)(H + 2) * 4, hipMemcpyDeviceToHost, ctx->st));
@@ -164,7 +164,7 @@ int rau_predict(rau_ctx* ctx, const int32_t* mc_ans, int32_t n_mc, int32_t* oe, 
   int32_t* mc_d = ctx->mg.ans + (size_t)(H + 2) * B;
   RUN("predict_rows", 0, (double)B * (2 * H + 1) * K * 4,
       predict_rows(ctx->st, H, B, K, ctx->Sp, ctx->logits, ctx->dopred, ctx->a, nmc ? ctx->mg.mc : nullptr,
-                   n_mc, oe_d, mc_d, ctx->mg.pred, ctx->mg.att));
+                   n_mc, oe_d, mc_d, ctx->mg.pred, ctx->mg.att, ctx->Kp));
   ctx->mg.merged = false;
   if (oe)
     if (int rc = d2h(ctx, oe, oe_d, (size_t)(H + 2) * B * 4)) return rc;
@@ -200,7 +200,7 @@ int rau_topk(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf) {
   float* score_d = reinterpret_cast<float*>(ids_d + n);
   float* conf_d = score_d + n;
   RUN("topk_merged", 0, (double)B * (2 * H + 1) * K * 4,
-      topk_merged(ctx->st, H, B, K, k, ctx->logits, ctx->dopred, ids_d, score_d, conf_d));
+      topk_merged(ctx->st, H, B, K, k, ctx->logits, ctx->dopred, ids_d, score_d, conf_d, ctx->Kp));
   if (ids) HIPC(hipMemcpyAsync(ids, ids_d, n * 4, hipMemcpyDeviceToHost, ctx->st));
   if (score) HIPC(hipMemcpyAsync(score, score_d, n * 4, hipMemcpyDeviceToHost, ctx->st));
   if (conf) HIPC(hipMemcpyAsync(conf, conf_d, n * 4, hipMemcpyDeviceToHost, ctx->st));
@@ -212,8 +212,16 @@ int rau_get_merged(rau_ctx* ctx, float* pred, float* att) {
   NEED(ctx, "null ctx");
   if (!ctx->mg.merged) return fail(RAU_ERR_STATE, "rau_get_merged: no rau_predict has run");
   const rau_config& c = ctx->cfg;
-  if (pred)
-    if (int rc = d2h(ctx, pred, ctx->mg.pred, (size_t)2 * c.B * c.K * 4)) return rc;
+  if (pred) {
+    if (ctx->Kp == c.K) {
+      if (int rc = d2h(ctx, pred, ctx->mg.pred, (size_t)2 * c.B * c.K * 4)) return rc;
+    } else {   // dense [2,n,K] on the host, rows at the answer pitch on the device
+      HIPC(hipMemcpy2DAsync(pred, (size_t)c.K * 4, ctx->mg.pred, (size_t)ctx->Kp * 4, (size_t)c.K * 4, (size_t)2 * c.B,
+                            hipMemcpyDeviceToHost, ctx->st));
+      HIPC(hipStreamSynchronize(ctx->st));
+      if (int rc = persist_check(ctx)) return rc;
+    }
+  }
   if (att) {
     HIPC(hipMemcpy2DAsync(att, (size_t)c.S * 4, ctx->mg.att, (size_t)ctx->Sp * 4, (size_t)c.S * 4,
                           (size_t)2 * c.B, hipMemcpyDeviceToHost, ctx->st));

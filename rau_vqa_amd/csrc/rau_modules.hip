@@ -267,6 +267,7 @@ int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const fl
                                    const float* h_prev, const int32_t* regions_dev, float** logits,
                                    float** do_pred, float** attprob, float** c_out, float** h_out) {
   NEED(ctx && q, "null argument");
+  NEED_DENSE_K(ctx, "rau_multimodal_forward");
   const rau_config& c = ctx->cfg;
   NEED(h >= 0 && h < c.H, "rau_multimodal_forward: h=%d out of [0,%d)", h, c.H);
   if (int rc = mod_alloc(ctx)) return rc;
@@ -341,6 +342,7 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
                             const float* d_h, float** d_q, float** d_X, float** d_c_prev,
                             float** d_h_prev) {
   NEED(ctx && q && d_logits, "null argument");
+  NEED_DENSE_K(ctx, "rau_multimodal_backward");
   const rau_config& c = ctx->cfg;
   NEED(h >= 0 && h < c.H, "rau_multimodal_backward: h=%d out of [0,%d)", h, c.H);
   if (int rc = mod_alloc(ctx)) return rc;
@@ -484,6 +486,7 @@ static int criterion(rau_ctx* ctx, int h, const float* logits, const Truth& t, f
 
 int rau_criterion_forward(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev, float* loss) {
   NEED(ctx && logits, "null argument");
+  NEED_DENSE_K(ctx, "rau_criterion_forward");
   NEED(h >= 0 && h < ctx->cfg.H, "rau_criterion_forward: h=%d out of [0,%d)", h, ctx->cfg.H);
   if (int rc = mod_alloc(ctx)) return rc;
   // labels_dev == NULL: the resident batch's ground truth, which may be its answer set
@@ -495,6 +498,7 @@ int rau_criterion_forward(rau_ctx* ctx, int h, const float* logits, const int32_
 int rau_criterion_backward(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev,
                            float scale, float** d_logits) {
   NEED(ctx && logits && d_logits, "null argument");
+  NEED_DENSE_K(ctx, "rau_criterion_backward");
   NEED(h >= 0 && h < ctx->cfg.H, "rau_criterion_backward: h=%d out of [0,%d)", h, ctx->cfg.H);
   if (int rc = mod_alloc(ctx)) return rc;
   const Truth t = labels_dev ? Truth{labels_dev} : truth_of(cur_batch(ctx));
@@ -506,6 +510,7 @@ int rau_criterion_backward(rau_ctx* ctx, int h, const float* logits, const int32
 int rau_criterion_forward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
                               const float* w_dev, float* loss) {
   NEED(ctx && logits && ids_dev && w_dev, "null argument");
+  NEED_DENSE_K(ctx, "rau_criterion_forward_set");
   NEED(h >= 0 && h < ctx->cfg.H, "rau_criterion_forward_set: h=%d out of [0,%d)", h, ctx->cfg.H);
   NEED(G >= 1 && G <= kMaxAnswers, "rau_criterion_forward_set: G=%d out of [1,%d]", G, kMaxAnswers);
   if (int rc = mod_alloc(ctx)) return rc;
@@ -515,6 +520,7 @@ int rau_criterion_forward_set(rau_ctx* ctx, int h, const float* logits, int32_t 
 int rau_criterion_backward_set(rau_ctx* ctx, int h, const float* logits, int32_t G, const int32_t* ids_dev,
                                const float* w_dev, float scale, float** d_logits) {
   NEED(ctx && logits && ids_dev && w_dev && d_logits, "null argument");
+  NEED_DENSE_K(ctx, "rau_criterion_backward_set");
   NEED(h >= 0 && h < ctx->cfg.H, "rau_criterion_backward_set: h=%d out of [0,%d)", h, ctx->cfg.H);
   NEED(G >= 1 && G <= kMaxAnswers, "rau_criterion_backward_set: G=%d out of [1,%d]", G, kMaxAnswers);
   if (int rc = mod_alloc(ctx)) return rc;
@@ -539,6 +545,7 @@ static int bce_truth(const char* fn, const int32_t* labels_dev, int32_t G, const
 int rau_criterion_forward_bce(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev, int32_t G,
                               const int32_t* ids_dev, const float* w_dev, float* loss) {
   NEED(ctx && logits, "null argument");
+  NEED_DENSE_K(ctx, "rau_criterion_forward_bce");
   NEED(h >= 0 && h < ctx->cfg.H, "rau_criterion_forward_bce: h=%d out of [0,%d)", h, ctx->cfg.H);
   Truth t;
   if (int rc = bce_truth("rau_criterion_forward_bce", labels_dev, G, ids_dev, w_dev, &t)) return rc;
@@ -549,6 +556,7 @@ int rau_criterion_forward_bce(rau_ctx* ctx, int h, const float* logits, const in
 int rau_criterion_backward_bce(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev, int32_t G,
                                const int32_t* ids_dev, const float* w_dev, float scale, float** d_logits) {
   NEED(ctx && logits && d_logits, "null argument");
+  NEED_DENSE_K(ctx, "rau_criterion_backward_bce");
   NEED(h >= 0 && h < ctx->cfg.H, "rau_criterion_backward_bce: h=%d out of [0,%d)", h, ctx->cfg.H);
   Truth t;
   if (int rc = bce_truth("rau_criterion_backward_bce", labels_dev, G, ids_dev, w_dev, &t)) return rc;
@@ -564,6 +572,7 @@ int rau_criterion_backward_bce(rau_ctx* ctx, int h, const float* logits, const i
 int rau_merge_criterion_backward(rau_ctx* ctx, const float* logits_dev, const float* dopred_dev,
                                  const int32_t* labels_dev, const float* merge_w, float* d_logits_dev) {
   NEED(ctx && logits_dev && dopred_dev && merge_w && d_logits_dev, "null argument");
+  NEED_DENSE_K(ctx, "rau_merge_criterion_backward");
   NEED(std::isfinite(merge_w[0]) && std::isfinite(merge_w[1]), "rau_merge_criterion_backward: merge_w is not finite");
   NEED(((uintptr_t)d_logits_dev & 15) == 0, "rau_merge_criterion_backward: d_logits_dev is not 16-byte aligned");
   const Truth t = labels_dev ? Truth{labels_dev} : truth_of(cur_batch(ctx));

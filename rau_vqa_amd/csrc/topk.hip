@@ -112,13 +112,13 @@ __global__ __launch_bounds__(kMT) void k_topk_rows(int cols, int k, int staged, 
 
 // Workgroup r * B + b: row r of {hops, uni, select} of sample b (predict rule: last hop forced, so
 // hsel >= 0 and a row where no hop fired cannot occur); outputs [H+2][B][k].
-__global__ __launch_bounds__(kMT) void k_topk_merged(int H, int B, int K, int k, int staged,
+__global__ __launch_bounds__(kMT) void k_topk_merged(int H, int B, int K, int ld, int k, int staged,
     const float* __restrict__ logits, const float* __restrict__ dopred, int32_t* __restrict__ ids,
     float* __restrict__ score, float* __restrict__ conf) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int r = blockIdx.x / B, b = blockIdx.x % B;
-  const size_t hs = (size_t)B * K;
-  const float* lg = logits + (size_t)b * K;
+  const size_t hs = (size_t)B * ld;   // rows at pitch ld >= K
+  const float* lg = logits + (size_t)b * ld;
   const int hsel = select_hop(dopred, H, B, b, true);
   const size_t o = (size_t)blockIdx.x * k;
   topk_row([&](int c) { return row_val(lg, hs, H, r, hsel, c); }, K, k, staged != 0, smem, score + o, ids + o,
@@ -136,8 +136,10 @@ hipError_t topk_rows(hipStream_t st, const float* x, int rows, int cols, int k, 
 }
 
 hipError_t topk_merged(hipStream_t st, int H, int B, int K, int k, const float* logits, const float* dopred,
-                       int32_t* ids, float* score, float* conf) {
-  hipLaunchKernelGGL(k_topk_merged, dim3((H + 2) * B), dim3(kMT), topk_lds(K), st, H, B, K, k,
+                       int32_t* ids, float* score, float* conf, int ld) {
+  if (ld == 0) ld = K;
+  if (ld < K) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_topk_merged, dim3((H + 2) * B), dim3(kMT), topk_lds(K), st, H, B, K, ld, k,
                      K <= kStageFloats ? 1 : 0, logits, dopred, ids, score, conf);
   return hipGetLastError();
 }

@@ -796,16 +796,26 @@ class RAU:
 
     def output_tensors(self):
         """Zero-copy torch views of the last step-level forward's outputs in device memory (rau_outputs_dev):
-        logits [H,n,K], dopred [H,n], attprob [H,n,S] -- the last a strided view of the pitched buffer.  Valid until
-        the next forward or set_batch_size, ordered on the ctx's stream (stream()), read-only."""
+        logits [H,n,K], dopred [H,n], attprob [H,n,S] -- the last a strided view of the pitched buffer, and so are the
+        logits where K % 4 != 0 (logits_pitch).  Valid until the next forward or set_batch_size, ordered on the ctx's
+        stream (stream()), read-only."""
         from .dist import device_view
         lg, dp, at = C.c_void_p(), C.c_void_p(), C.c_void_p()
         pitch = C.c_int32()
         L.check(self._lib.rau_outputs_dev(self._h, C.byref(lg), C.byref(dp), C.byref(at), C.byref(pitch)))
         H, n, K, S, dev = self.cfg.H, self._n, self.cfg.K, self.cfg.S, self.cfg.device_id
-        return (device_view(lg.value, H * n * K, dev).view(H, n, K),
+        kp = self.logits_pitch
+        return (device_view(lg.value, H * n * kp, dev).view(H, n, kp)[:, :, :K],
                 device_view(dp.value, H * n, dev).view(H, n),
                 device_view(at.value, H * n * pitch.value, dev).view(H, n, pitch.value)[:, :, :S])
+
+    @property
+    def logits_pitch(self) -> int:
+        """Row pitch of the logits in device memory (rau_logits_pitch): K where K % 4 == 0, else K rounded up to a
+        multiple of 4 with +0 in columns K..pitch-1.  output_tensors() hides it; out_grads stay dense [H,n,K]."""
+        pitch = C.c_int32()
+        L.check(self._lib.rau_logits_pitch(self._h, C.byref(pitch)))
+        return int(pitch.value)
 
     def want_feature_grad(self, on=True, per_image=False):
         """Every step-level backward (backward, graph_step) also leaves the gradient at the feature map behind

@@ -214,6 +214,9 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=No
            loss="ce", answer_set=None):
     if loss not in ("ce", "bce"):
         raise ValueError(f"feval: loss={loss!r}: 'ce' or 'bce'")
+    if rau.cfg.K % 4:   # the clones exchange dense [B,K] rows: refused here, before the encoder loop launches anything
+        raise L.RauError(f"librau error -1: feval: module-level calls exchange dense [B,K] rows and need K % 4 == 0 "
+                         f"(K={rau.cfg.K}); use the step-level path")
     bce = loss == "bce"
     if bce and merge_w is not None and any(float(w) != 0.0 for w in merge_w):
         raise ValueError("feval: merge_w is not available with loss='bce'")
