@@ -82,6 +82,8 @@ int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const
 int rau_batch_answers(rau_ctx* ctx, int32_t* G);
 int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n);
 int rau_batch_regions(rau_ctx* ctx, int* has);
+int rau_set_sample_weights(rau_ctx* ctx, int slot, const float* s);
+int rau_batch_sample_weights(rau_ctx* ctx, int* has);
 int rau_set_batch_packed(rau_ctx* ctx, const void* rows, int feat_type, int n_maps, const int32_t* counts,
                          const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
                          const int32_t* labels);
@@ -175,6 +177,7 @@ int rau_dev_adam(rau_ctx* ctx, float* x, const float* dx, float* m, float* v, si
                  float beta1, float beta2, float eps, int32_t t);
 int rau_dev_adamax(rau_ctx* ctx, float* x, const float* dx, float* m, float* u, size_t n, float lr,
                    float beta1, float beta2, float eps, int32_t t);
+int rau_dev_scale_rows(rau_ctx* ctx, float* x, int32_t rows, int32_t cols, int32_t ld, const float* s_dev);
 int rau_dev_select_rows(rau_ctx* ctx, float* dst, const float* src, int32_t rows, int32_t cols,
                         const int32_t* key_dev, int32_t value);
 int rau_dev_rowmax(rau_ctx* ctx, const float* x, int32_t rows, int32_t cols, float* max_dev,
@@ -189,6 +192,7 @@ int rau_dev_download(rau_ctx* ctx, void* host, const void* src_dev, size_t bytes
 int rau_graph_step(rau_ctx* ctx, const float* hop_w, int zero_grads_first);
 int rau_sync(rau_ctx* ctx);
 int rau_get_losses(rau_ctx* ctx, float* losses);
+int rau_get_loss_rows(rau_ctx* ctx, float* rows);
 int rau_get_argmax(rau_ctx* ctx, int32_t* ans);
 int rau_get_logits(rau_ctx* ctx, float* logits);
 int rau_get_dopred(rau_ctx* ctx, float* dopred);
@@ -414,6 +418,31 @@ function RAU:batchRegions()
   local v = ffi.new('int[1]')
   check(C.rau_batch_regions(self.h, v))
   return v[0] ~= 0
+end
+
+-- Per-sample loss weights (rau_set_sample_weights): s FloatTensor [B], finite and >= 0; every built-in mean of the
+-- step path, (1/n) sum_b row_b, becomes (1/n) sum_b s[b] row_b.  Never renormalised by the library.  nil detaches
+-- them.  slot as in setAnswers; the weights last until the next batch goes into that slot.
+function RAU:setSampleWeights(s, slot)
+  if s == nil then
+    check(C.rau_set_sample_weights(self.h, slot or -1, nil))
+    return
+  end
+  s = s:float():contiguous()
+  assert(s:dim() == 1 and s:size(1) == self.n, 's must be [B]')
+  check(C.rau_set_sample_weights(self.h, slot or -1, s:data()))
+end
+-- whether the resident batch carries sample weights
+function RAU:batchSampleWeights()
+  local v = ffi.new('int[1]')
+  check(C.rau_batch_sample_weights(self.h, v))
+  return v[0] ~= 0
+end
+-- the per-sample loss rows [H][B] of the last forward (with weights: the weighted rows) as a FloatTensor
+function RAU:lossRows()
+  local t = torch.FloatTensor(self.cfg.H, self.n)
+  check(C.rau_get_loss_rows(self.h, t:data()))
+  return t
 end
 
 -- Attention targets (rau_set_att_targets): t FloatTensor [B,S] (or [B,W,H]), entries finite and >= 0, one target map

@@ -480,6 +480,44 @@ int rau_batch_answers(rau_ctx* ctx, int32_t* G);
 int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n /* [batch] host */);
 int rau_batch_regions(rau_ctx* ctx, int* has);
 
+/* ---- per-sample loss weights: every training term of the step path, weighted per sample ------------
+ * Every objective the step path trains is a mean over the batch, (1/n) sum_b row_b: the answer criterion (softmax
+ * CE with labels, soft-target CE with an answer set, the sigmoid head), the step-selection BCE, the attention
+ * supervision and the two merged rows.  With weights s [n] on the batch each becomes (1/n) sum_b s_b row_b.  The
+ * library NEVER renormalises: whether sum s = n is the caller's decision.  Uses: class- or question-type-balanced
+ * training, down-weighting noisy questions, importance sampling, switching single rows of a batch off (s_b = 0).
+ * s [n] float32 host, n the current batch size; every entry finite and >= 0; NULL detaches the weights (nothing is
+ * copied; a forward that ran with them must be run again).  The weights are always per SAMPLE, on plain, typed,
+ * packed, image-table, bank and device (rau_set_batch_dev*) batches, with or without an attached question.
+ * slot = -1 | 0 | 1, ownership and lifetime are exactly those of rau_set_regions: -1 is the resident batch and
+ * synchronises; 0 | 1 is a slot of the asynchronous path, between rau_set_batch_async* and rau_use_batch, enqueued
+ * on the copy stream, nothing synchronised; the weights belong to the slot's batch; a later upload into that slot,
+ * or rau_set_batch_size, clears them; rau_use_batch makes them current with the batch.  The forward's criterion
+ * head reads them: a forward that has run on the batch must be run again before rau_backward.
+ * Arithmetic, float32, every product rounded once (invB = 1 / n):
+ *   answer criterion and merged rows   invB is replaced by s_b * invB wherever it is used (W invB, w_g invB, the
+ *                                      sigmoid head's (sigmoid - t) invB); the loss row written is s_b * row
+ *   selection BCE                      select_w[h] is replaced by select_w[h] * s_b, the rest unchanged
+ *   attention supervision              att_w[h] is replaced by att_w[h] * s_b, the rest unchanged
+ *   statistics                         rau_get_losses, rau_get_loss_rows and rau_step_stats' loss[0..H) are the
+ *                                      weighted rows' means; rau_step_stats' uni / select losses and loss_do_pred
+ *                                      and rau_att_stats' loss take s_b per row (s_b * row, then the mean)
+ * UNWEIGHTED, always: every count, rau_att_stats' mass, hits and n_sup, the metric scores (rau_step_scores,
+ * rau_predict_scores), rau_predict, rau_topk.  Caller-supplied gradients (rau_out_grads) are the caller's and are
+ * not weighted.  Module-level criteria do not read the weights (rau_dev_scale_rows weights their gradients).
+ * A batch without weights computes and launches exactly what it did before weights existed; weights all equal to
+ * 1 give the same bits (1 * invB is exact).  A sample with s_b = 0 contributes exactly zero to d_logits, to the
+ * select signal, to the attention addend, to the merged terms and to every loss.  No atomics, no device scratch,
+ * the same bits on every call; one 4-byte load per workgroup that owns a row.
+ * rau_graph_step keys its cache by "has weights": a step captured without them is never replayed for a batch with
+ * them, nor the other way round; a replay reads the current weights of the resident batch.
+ * Errors, nothing uploaded, the previous weights stay in force: RAU_ERR_INVALID for a negative or non-finite
+ * weight; RAU_ERR_STATE when the slot holds no batch, or (slot 0 | 1) it is the current batch of a forward whose
+ * backward has not run.
+ * rau_batch_sample_weights: *has = 1 when the resident batch carries weights, else 0. */
+int rau_set_sample_weights(rau_ctx* ctx, int slot, const float* s /* [batch] host; NULL = detach */);
+int rau_batch_sample_weights(rau_ctx* ctx, int* has);
+
 /* ---- packed region features: rows as the files store them, unpacked on the device ------------------
  * Region feature files hold one row of D values per box.  A packed batch hands those rows over as they are:
  * rows [sum(counts), D] of feat_type elements, row-major, map i owning counts[i] consecutive rows (1 <= counts[i]
@@ -969,6 +1007,10 @@ int rau_dev_adamax(rau_ctx* ctx, float* x, const float* dx, float* m, float* u, 
 /* dst[k,:] = src[k,:] for the rows k with key_dev[k] == value (SS:455-461, 584-591) */
 int rau_dev_select_rows(rau_ctx* ctx, float* dst, const float* src, int32_t rows, int32_t cols,
                         const int32_t* key_dev, int32_t value);
+/* x[r, 0..cols) *= s_dev[r] for r < rows, rows of x at pitch ld >= cols (floats), each product rounded once; columns
+ * cols..ld-1 are not touched.  For module-level hosts that weight a [B, K] criterion gradient per sample themselves.
+ * 16-byte accesses where ld % 4 == 0 and x is 16-byte aligned; any cols.  Not synchronising. */
+int rau_dev_scale_rows(rau_ctx* ctx, float* x, int32_t rows, int32_t cols, int32_t ld, const float* s_dev /* [rows] */);
 /* torch.max(x, 2): per-row maximum and FIRST maximal index, 1-based (either output may be NULL) */
 int rau_dev_rowmax(rau_ctx* ctx, const float* x, int32_t rows, int32_t cols, float* max_dev,
                    int32_t* argmax_dev);
@@ -998,7 +1040,17 @@ int rau_graph_step(rau_ctx* ctx, const float* hop_w /* [H] host */, int zero_gra
 
 /* ---- results (valid after rau_sync; these calls synchronise themselves) ------ */
 int rau_sync(rau_ctx* ctx);
+/* rau_get_losses: the per-hop means of the loss rows the last step-level forward on a batch with a ground truth
+ * wrote (with sample weights: of the weighted rows).  It has NO state check: before such a forward, or after
+ * something has invalidated that forward's record (rau_set_sample_weights or rau_set_answers on its slot, a
+ * module-level entry point, rau_set_batch_size), it returns whatever the buffer holds -- the old means, or zeros.
+ * rau_get_loss_rows is the checked form of the same data. */
 int rau_get_losses(rau_ctx* ctx, float* losses /* [H] */);
+/* The per-sample loss rows of the last step-level forward, dense [H,n]: the rows rau_get_losses averages (with
+ * sample weights: the weighted rows).  Unlike rau_get_losses it is gated on that forward's record: RAU_ERR_STATE when
+ * no step-level forward on a batch with a ground truth has run, or when its record has been invalidated since (the
+ * cases listed above), where rau_get_losses would still hand back stale means. */
+int rau_get_loss_rows(rau_ctx* ctx, float* rows /* [H,n] */);
 int rau_get_argmax(rau_ctx* ctx, int32_t* ans /* [H,B] 1-based */);
 int rau_get_logits(rau_ctx* ctx, float* logits /* [H,B,K] */);
 int rau_get_dopred(rau_ctx* ctx, float* dopred /* [H,B] */);

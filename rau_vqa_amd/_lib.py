@@ -112,6 +112,8 @@ _SIGS = {
     # region counts: attention over a sample's valid positions only
     "rau_set_regions": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "rau_batch_regions": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rau_set_sample_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "rau_batch_sample_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     # packed region rows: transposed and zero-padded on the device, counts attached in the same call
     "rau_set_batch_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
@@ -219,6 +221,7 @@ _SIGS = {
                                C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32]),
     "rau_dev_adamax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32]),
+    "rau_dev_scale_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "rau_dev_select_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_void_p, C.c_int32]),
     "rau_dev_rowmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
@@ -233,6 +236,7 @@ _SIGS = {
     "rau_graph_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "rau_sync": (C.c_int, [C.c_void_p]),
     "rau_get_losses": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rau_get_loss_rows": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rau_get_argmax": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rau_get_logits": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rau_get_dopred": (C.c_int, [C.c_void_p, C.c_void_p]),

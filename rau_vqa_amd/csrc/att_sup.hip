@@ -7,6 +7,8 @@
 //   da[h,b,s]  = -( (w[h] * t) / (a + eps) ) / n          float32, every step rounded once, in this order
 // and exactly +0 where t == 0, where s >= n_reg[b] and in the pitch padding.  eps keeps the value finite for every
 // a >= 0; the softmax gradient multiplies it by a, so where a has underflowed to 0 nothing flows back.
+// With sample weights s (rau_set_sample_weights) w[h] is replaced by __fmul_rn(w[h], s_b) in da and a row's loss sum
+// enters ATT_h as __fmul_rn(s_b, sum); mass, hits and the supervised-row count stay unweighted.
 // k_att_grad writes da for all active hops in one launch, over the whole pitch (zeros included): the buffer is the
 // attention-backward kernels' pitched addend (HopGrad::da_out) and needs no clearing.
 // Statistics: a row is SUPERVISED when some t[b,s] > 0 with s < n_reg[b].  k_att_rows forms per (hop, sample) row
@@ -35,13 +37,15 @@ __device__ __forceinline__ float att_grad_1(float w, float t, float a, float n) 
 template <bool VEC>
 __global__ __launch_bounds__(64 * kRowsPerWg) void k_att_grad(int rows, int Bper, int S, const float* __restrict__ a,
     int a_rs, const float* __restrict__ t, int t_rs, const int32_t* __restrict__ nreg,
-    const float* __restrict__ w_dev, float scale, float* __restrict__ da, int d_rs) {
+    const float* __restrict__ w_dev, float scale, float* __restrict__ da, int d_rs,
+    const float* __restrict__ sw) {
   RAU_CHAIN_PRIO();
   const int r = blockIdx.x * kRowsPerWg + (threadIdx.x >> 6), l = threadIdx.x & 63;
   if (r >= rows) return;
   const int h = r / Bper, b = r - h * Bper;
   const int nv = nreg ? min(max(nreg[b], 1), S) : S;   // clamped like the attention kernels' counts
-  const float w = w_dev ? w_dev[h] : scale, n = (float)Bper;
+  // the hop weight times the sample weight, one rounded product (no weights: times 1, exact); one load per row
+  const float w = __fmul_rn(w_dev ? w_dev[h] : scale, sw ? sw[b] : 1.f), n = (float)Bper;
   const float* ar = a + (size_t)r * a_rs;
   const float* tr = t + (size_t)b * t_rs;
   float* dr = da + (size_t)r * d_rs;
@@ -81,7 +85,7 @@ __device__ __forceinline__ float wave_sum_rn(float v) {
 // rowf [2][rows]: loss sum | mass; rowi [2][rows]: supervised | hit
 __global__ __launch_bounds__(64 * kRowsPerWg) void k_att_rows(int rows, int Bper, int S, const float* __restrict__ a,
     int a_rs, const float* __restrict__ t, int t_rs, const int32_t* __restrict__ nreg, float* __restrict__ rowf,
-    int32_t* __restrict__ rowi) {
+    int32_t* __restrict__ rowi, const float* __restrict__ sw) {
   const int r = blockIdx.x * kRowsPerWg + (threadIdx.x >> 6), l = threadIdx.x & 63;
   if (r >= rows) return;
   const int b = r % Bper;
@@ -104,7 +108,7 @@ __global__ __launch_bounds__(64 * kRowsPerWg) void k_att_rows(int rows, int Bper
   wave_first_max(best, arg);
   sup = __any(sup) ? 1 : 0;
   if (l == 0) {
-    rowf[r] = loss;
+    rowf[r] = __fmul_rn(sw ? sw[b] : 1.f, loss);
     rowf[rows + r] = mass;
     rowi[r] = sup;
     rowi[rows + r] = (sup && arg < nv && tr[arg] > 0.f) ? 1 : 0;
@@ -148,7 +152,8 @@ bool vec_ok(const void* a, int a_rs, const void* t, int t_rs, const void* d, int
 }  // namespace
 
 hipError_t att_sup_grad(hipStream_t st, int hops, int Bper, int S, const float* a, int a_rs, const float* t,
-                        int t_rs, const int32_t* nreg, const float* w_dev, float scale, float* da, int d_rs) {
+                        int t_rs, const int32_t* nreg, const float* w_dev, float scale, float* da, int d_rs,
+                        const float* sw) {
   const int rows = hops * Bper;
   if (rows <= 0) return hipSuccess;
   if (Bper < 1 || S < 1 || a_rs < S || t_rs < S || d_rs < S) return hipErrorInvalidValue;
@@ -156,20 +161,21 @@ hipError_t att_sup_grad(hipStream_t st, int hops, int Bper, int S, const float* 
   // VEC reads a and t in whole quads below the count: both rows must reach the end of the quad that holds S - 1
   if (vec_ok(a, a_rs, t, t_rs, da, d_rs))
     hipLaunchKernelGGL(k_att_grad<true>, grid, block, 0, st, rows, Bper, S, a, a_rs, t, t_rs, nreg, w_dev, scale, da,
-                       d_rs);
+                       d_rs, sw);
   else
     hipLaunchKernelGGL(k_att_grad<false>, grid, block, 0, st, rows, Bper, S, a, a_rs, t, t_rs, nreg, w_dev, scale, da,
-                       d_rs);
+                       d_rs, sw);
   return hipGetLastError();
 }
 
 hipError_t att_sup_stats(hipStream_t st, int hops, int Bper, int S, const float* a, int a_rs, const float* t,
-                         int t_rs, const int32_t* nreg, float* rowf, int32_t* rowi, float* outf, int32_t* outi) {
+                         int t_rs, const int32_t* nreg, float* rowf, int32_t* rowi, float* outf, int32_t* outi,
+                         const float* sw) {
   const int rows = hops * Bper;
   if (rows <= 0) return hipSuccess;
   if (Bper < 1 || S < 1 || a_rs < S || t_rs < S) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_att_rows, dim3((rows + kRowsPerWg - 1) / kRowsPerWg), dim3(64 * kRowsPerWg), 0, st, rows,
-                     Bper, S, a, a_rs, t, t_rs, nreg, rowf, rowi);
+                     Bper, S, a, a_rs, t, t_rs, nreg, rowf, rowi, sw);
   hipLaunchKernelGGL(k_att_finish, dim3(hops), dim3(64), 0, st, hops, Bper, rowf, rowi, outf, outi);
   return hipGetLastError();
 }

@@ -7,6 +7,8 @@
 //            answer set:  t[k] = min(1, sum_g w_g [y_g == k])               (ids clamped like k_ce_set_fwd's)
 //   lossrow  = sum_k ( max(x,0) - x t + log1p(exp(-|x|)) )                  summed over K, NOT divided by K
 //   dl[k]    = (sigmoid(x) - t) invB
+// With a sample weight s_b (rau_set_sample_weights) invB is __fmul_rn(s_b, 1 / Bper) and the loss row written is
+// __fmul_rn(s_b, lossrow); without weights s_b = 1 and both are exact.  One 4-byte load per workgroup.
 // The rounding of every step is spelled out, so duplicates are deterministic and repeated calls give the same bits:
 //   t        the matching non-empty entries' weights are added from +0 in entry order, each sum rounded once
 //            (__fadd_rn), then fminf(., 1); labels are the set {(y, 1)}, so t is exactly 0 or 1
@@ -35,7 +37,7 @@ __global__ __launch_bounds__(256) void k_bce_fwd(int nB, int K, int M, const flo
     const float* __restrict__ mf, const float* __restrict__ wd, const float* __restrict__ bd,
     float* __restrict__ dl, float* __restrict__ lossrow, int32_t* __restrict__ argmax, float* __restrict__ dopred,
     const float* __restrict__ part, int nsplit, const float* __restrict__ bias, float* __restrict__ logits_out,
-    int Bper, int ld) {
+    int Bper, int ld, const float* __restrict__ sw) {
   RAU_CHAIN_PRIO();
   __shared__ float s_val[4];
   __shared__ int s_idx[4];
@@ -79,7 +81,8 @@ __global__ __launch_bounds__(256) void k_bce_fwd(int nB, int K, int M, const flo
   if (tid == 0) argmax[b] = ai + 1;
   if (truth) {
     const bool labelled = bce_labelled(s_id, ng);
-    const float invB = 1.f / (float)Bper;
+    const float sb = sw ? sw[b % Bper] : 1.f;
+    const float invB = __fmul_rn(sb, 1.f / (float)Bper);
     float acc = 0.f;
     for (int k = tid; k < K; k += 256) {
       if (!labelled) {   // an unlabelled sample (uniform per workgroup)
@@ -96,7 +99,7 @@ __global__ __launch_bounds__(256) void k_bce_fwd(int nB, int K, int M, const flo
     }
     for (int k = K + tid; k < ld; k += 256) dl[(size_t)b * ld + k] = 0.f;   // the row's pad
     acc = block_sum(acc, s_sum);
-    if (tid == 0) lossrow[b] = acc;
+    if (tid == 0) lossrow[b] = __fmul_rn(sb, acc);
   }
   // do_pred
   if (!mf) return;   // criterion-only use (uniform per launch)
@@ -111,12 +114,13 @@ __global__ __launch_bounds__(256) void k_bce_fwd(int nB, int K, int M, const flo
 hipError_t bce_fwd(hipStream_t st, int nB, int K, int M, const float* logits, const int32_t* labels,
                    const int32_t* ids, const float* w, int G, const float* mf, const float* wd, const float* bd,
                    float* dl, float* lossrow, int32_t* argmax, float* dopred, const float* part, int nsplit,
-                   const float* bias, float* logits_out, int Bper, int ld) {
+                   const float* bias, float* logits_out, int Bper, int ld, const float* sw) {
   if (G < 0 || G > kMaxAnswers || (G > 0 && (!ids || !w))) return hipErrorInvalidValue;
   if (!split_span_ok(part, nsplit, (size_t)nB * K)) return kSplitStateError;
   if (ld != 0 && ld < K) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_bce_fwd, dim3(nB), dim3(256), 0, st, nB, K, M, logits, labels, ids, w, G, mf, wd, bd, dl,
-                     lossrow, argmax, dopred, part, nsplit, bias, logits_out, Bper > 0 ? Bper : nB, ld ? ld : K);
+                     lossrow, argmax, dopred, part, nsplit, bias, logits_out, Bper > 0 ? Bper : nB, ld ? ld : K,
+                     sw);
   return hipGetLastError();
 }
 

@@ -4,6 +4,8 @@
 // 0 = empty; weights w >= 0).  With W = sum of the non-empty weights in entry order:
 //   lossrow = sum_g w_g (lse - lg[y_g])                       accumulated from 0 in entry order
 //   dl[k]   = expf(lg[k] - lse) (W invB), then for g = 0..G-1 in order: if (y_g == k) dl[k] -= w_g invB
+// With a sample weight s_b (rau_set_sample_weights) invB is __fmul_rn(s_b, 1 / Bper) in both products and the loss
+// row written is __fmul_rn(s_b, lossrow); without weights s_b = 1 and both are exact.  One load per workgroup.
 // The rounding of every step is spelled out, so duplicates are deterministic: the products w_g invB, W invB and
 // w_g (lse - lg[y_g]) and every sum are rounded once, and the FIRST matching entry of a logit is subtracted inside
 // the product's fused multiply-add, fma(e, W invB, -w_g invB) -- which is what k_ce_fwd's
@@ -24,7 +26,7 @@ __global__ __launch_bounds__(256) void k_ce_set_fwd(int nB, int K, int M, const 
     const float* __restrict__ wd, const float* __restrict__ bd, float* __restrict__ dl,
     float* __restrict__ lossrow, int32_t* __restrict__ argmax, float* __restrict__ dopred,
     const float* __restrict__ part, int nsplit, const float* __restrict__ bias, float* __restrict__ logits_out,
-    int Bper, int ld) {
+    int Bper, int ld, const float* __restrict__ sw) {
   RAU_CHAIN_PRIO();
   __shared__ float s_val[4];
   __shared__ int s_idx[4];
@@ -34,7 +36,8 @@ __global__ __launch_bounds__(256) void k_ce_set_fwd(int nB, int K, int M, const 
   __shared__ float s_wb[kMaxAnswers];    // w * invB
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
-  const float invB = 1.f / (float)Bper;
+  const float sb = sw ? sw[b % Bper] : 1.f;
+  const float invB = __fmul_rn(sb, 1.f / (float)Bper);
   if (tid < G) {
     // rows = [hop][sample]: the sets repeat every Bper rows; ids clamped like k_ce_fwd's labels
     const size_t e = (size_t)(b % Bper) * G + tid;
@@ -86,7 +89,7 @@ __global__ __launch_bounds__(256) void k_ce_set_fwd(int nB, int K, int M, const 
     float acc = 0.f;
     for (int g = 0; g < G; ++g)
       if (s_id[g] >= 0) acc = __fadd_rn(acc, __fmul_rn(s_w[g], lse - lg[s_id[g]]));
-    lossrow[b] = acc;
+    lossrow[b] = __fmul_rn(sb, acc);
   }
   // do_pred
   if (!mf) return;   // criterion-only use (uniform per launch)
@@ -101,12 +104,13 @@ __global__ __launch_bounds__(256) void k_ce_set_fwd(int nB, int K, int M, const 
 hipError_t ce_set_fwd(hipStream_t st, int nB, int K, int M, const float* logits, const int32_t* ids,
                       const float* w, int G, const float* mf, const float* wd, const float* bd, float* dl,
                       float* lossrow, int32_t* argmax, float* dopred, const float* part, int nsplit,
-                      const float* bias, float* logits_out, int Bper, int ld) {
+                      const float* bias, float* logits_out, int Bper, int ld, const float* sw) {
   if (G < 1 || G > kMaxAnswers || !ids || !w) return hipErrorInvalidValue;
   if (!split_span_ok(part, nsplit, (size_t)nB * K)) return kSplitStateError;
   if (ld != 0 && ld < K) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_ce_set_fwd, dim3(nB), dim3(256), 0, st, nB, K, M, logits, ids, w, G, mf, wd, bd, dl,
-                     lossrow, argmax, dopred, part, nsplit, bias, logits_out, Bper > 0 ? Bper : nB, ld ? ld : K);
+                     lossrow, argmax, dopred, part, nsplit, bias, logits_out, Bper > 0 ? Bper : nB, ld ? ld : K,
+                     sw);
   return hipGetLastError();
 }
 

@@ -242,15 +242,19 @@ __global__ __launch_bounds__(kMT) void k_score_totals(int R, int B, const float*
 
 // One workgroup: out = loss[H+2] | loss_do_pred[H] (floats) | counts[4H+3] (int32).  Float columns
 // are reduced like k_loss_reduce (lane-strided over the batch, wave_sum, / B), so the per-hop CE is
-// bitwise the step's own rau_get_losses.
+// bitwise the step's own rau_get_losses.  sw (rau_set_sample_weights, or null): the uni / select losses and the
+// do_pred BCE enter their sums as __fmul_rn(sw[b], row) -- lossrow already holds the weighted rows; the counts stay
+// unweighted.
 __global__ __launch_bounds__(kMT) void k_step_stats_reduce(int H, int B, const float* __restrict__ lossrow,
-    const float* __restrict__ rowf, const int32_t* __restrict__ rowi, float* __restrict__ out) {
+    const float* __restrict__ rowf, const int32_t* __restrict__ rowi, float* __restrict__ out,
+    const float* __restrict__ sw) {
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int NF = H + 2, NL = 2 * H + 2, NC = 4 * H + 3;
   for (int j = w; j < NL; j += 4) {
     float acc = 0.f;
     for (int b = l; b < B; b += 64)
-      acc += j < H ? lossrow[(size_t)j * B + b] : rowf[(size_t)b * NF + (j - H)];
+      acc += j < H ? lossrow[(size_t)j * B + b]
+                   : sw ? __fmul_rn(sw[b], rowf[(size_t)b * NF + (j - H)]) : rowf[(size_t)b * NF + (j - H)];
     acc = wave_sum(acc);
     if (l == 0) out[j] = acc / (float)B;
   }
@@ -338,7 +342,7 @@ hipError_t step_stats(hipStream_t st, int H, int B, int K, const float* logits, 
   if (t.bce())   // the two merged rows' losses under the sigmoid criterion, in place of the softmax CE just written
     hipLaunchKernelGGL(k_step_stats_bce, dim3(B), dim3(kMT), 0, st, H, B, K, ld, logits, dopred, t.labels, t.ids, t.w,
                        t.G, rowf);
-  hipLaunchKernelGGL(k_step_stats_reduce, dim3(1), dim3(kMT), 0, st, H, B, lossrow, rowf, rowi, out);
+  hipLaunchKernelGGL(k_step_stats_reduce, dim3(1), dim3(kMT), 0, st, H, B, lossrow, rowf, rowi, out, t.sw);
   if (t.G > 0) hipLaunchKernelGGL(k_score_totals, dim3(1), dim3(kMT), 0, st, H + 2, B, rowscore, tot);
   return hipGetLastError();
 }

@@ -422,7 +422,10 @@ hipError_t ce_fwd(hipStream_t st, int nB, int K, int M, const float* logits,
                   float* dl, float* lossrow, int32_t* argmax, float* dopred,
                   const float* part = nullptr, int nsplit = 0, const float* bias = nullptr,
                   float* logits_out = nullptr,
-                  int Bper = 0 /* rows are [hop][sample]: samples per hop (label period, 1/B) */, int ld = 0);
+                  int Bper = 0 /* rows are [hop][sample]: samples per hop (label period, 1/B) */, int ld = 0,
+                  // per-sample loss weights [Bper] (device) or null: invB becomes __fmul_rn(sw[b], invB) and the loss
+                  // row __fmul_rn(sw[b], row); the same argument of ce_set_fwd and bce_fwd
+                  const float* sw = nullptr);
 hipError_t loss_reduce(hipStream_t st, int H, int nB, const float* lossrow, float* losses);
 // ce_fwd against an answer set (ce_set.hip, rau_set_answers): ids / w [Bper][G] device, ids 1..K or 0 = empty
 // entry, 1 <= G <= kMaxAnswers; lossrow = sum_g w (lse - lg[y_g]), dl = softmax * (W / Bper) - sum_g onehot_g w / Bper
@@ -432,7 +435,7 @@ hipError_t ce_set_fwd(hipStream_t st, int nB, int K, int M, const float* logits,
                       const float* w, int G, const float* mf, const float* wd, const float* bd, float* dl,
                       float* lossrow, int32_t* argmax, float* dopred, const float* part = nullptr,
                       int nsplit = 0, const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0,
-                      int ld = 0);
+                      int ld = 0, const float* sw = nullptr);
 // The criterion head as a per-answer sigmoid with binary cross-entropy (bce_head.hip, RAU_LOSS_BCE): ce_fwd's /
 // ce_set_fwd's contract with  t[k] = [k == y]  (labels) or  min(1, sum_g w_g [y_g == k])  (G > 0: ids / w [Bper][G]),
 // lossrow = sum_k max(x,0) - x t + log1p(exp(-|x|)),  dl = (sigmoid(x) - t) / Bper; a row whose set has no non-empty
@@ -440,7 +443,8 @@ hipError_t ce_set_fwd(hipStream_t st, int nB, int K, int M, const float* logits,
 hipError_t bce_fwd(hipStream_t st, int nB, int K, int M, const float* logits, const int32_t* labels,
                    const int32_t* ids, const float* w, int G, const float* mf, const float* wd, const float* bd,
                    float* dl, float* lossrow, int32_t* argmax, float* dopred, const float* part = nullptr,
-                   int nsplit = 0, const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0, int ld = 0);
+                   int nsplit = 0, const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0, int ld = 0,
+                   const float* sw = nullptr);
 // The ground truth of a batch: what a criterion, a statistic or the selection head's target is read from.  A plain
 // value: "no ground truth" is Truth{}; G > 0 means the answer set replaces the labels.  `loss` is the criterion the
 // answers are trained with (RAU_LOSS_CE / RAU_LOSS_BCE of include/rau.h): read by criterion_head and step_stats only.
@@ -450,6 +454,9 @@ struct Truth {
   const float *w = nullptr, *score = nullptr;
   int G = 0;                         // 0 = labels
   int loss = 0;                      // RAU_LOSS_CE
+  // per-sample loss weights [Bper] (device; rau_set_sample_weights) or null: every kernel that forms a training
+  // term from this target multiplies the term's 1 / Bper (or hop weight) by sw[b]; set by step_truth() only
+  const float* sw = nullptr;
   bool present() const { return labels || G > 0; }
   bool bce() const { return loss != 0; }
 };
@@ -464,15 +471,15 @@ inline hipError_t criterion_head(hipStream_t st, int nB, int K, int M, const flo
                                  int ld = 0) {
   if (t.bce())
     return bce_fwd(st, nB, K, M, logits, t.labels, t.ids, t.w, t.G, mf, wd, bd, dl, lossrow, argmax, dopred, part,
-                   nsplit, bias, logits_out, Bper, ld);
+                   nsplit, bias, logits_out, Bper, ld, t.sw);
   if (t.G > 0)
     return ce_set_fwd(st, nB, K, M, logits, t.ids, t.w, t.G, mf, wd, bd, dl, lossrow, argmax, dopred, part, nsplit,
-                      bias, logits_out, Bper, ld);
+                      bias, logits_out, Bper, ld, t.sw);
   return ce_fwd(st, nB, K, M, logits, t.labels, mf, wd, bd, dl, lossrow, argmax, dopred, part, nsplit, bias,
-                logits_out, Bper, ld);
+                logits_out, Bper, ld, t.sw);
 }
 // The step-selection head's gradient (select_bwd.hip, rau_backward_select).  rows = active hops x Bper, hop-major.
-// select_signal: s[r] = select_w[h] * BCE'(do_pred, do_pred_gt) / Bper * x (1 - x) and add[r][m] = s[r] wd[m];
+// select_signal: s[r] = (select_w[h] * t.sw[b]) * BCE'(do_pred, do_pred_gt) / Bper * x (1 - x), add[r][m] = s[r] wd[m];
 // do_pred_gt from t's labels [Bper] (G == 0) or its answer set ids / score [Bper][G] (rau_step_stats' rules).
 // select_wgrad: dW[m] += sum_r s[r] mf[r][m], db[0] += sum_r s[r], one fixed-order pass (any M, any row count).
 hipError_t select_signal(hipStream_t st, int rows, int Bper, int K, int M, const float* dopred,
@@ -484,12 +491,16 @@ hipError_t select_wgrad(hipStream_t st, int rows, int M, const float* s, const f
 // da at row pitch a_rs / d_rs, the targets t [Bper] rows at pitch t_rs, nreg [Bper] region counts or null.
 // att_sup_grad: da[h,b,s] = -((w[h] t) / (a + 1e-12f)) / Bper below the count, +0 elsewhere, over the whole of d_rs;
 // w = w_dev [hops] (device), or with w_dev null `scale` for every hop.  One launch for all hops.
+// sw [Bper] (device) or null: per-sample loss weights -- w[h] becomes __fmul_rn(w[h], sw[b]) in the gradient, a row's
+// loss sum __fmul_rn(sw[b], sum) in the statistics (mass, hits and the supervised rows stay unweighted).
 // att_sup_stats: outf [2][hops] = ATT_h | mean attention mass on t > 0 over the supervised rows, outi [2][hops] =
 // pointing-game hits | supervised rows; rowf / rowi [2][hops * Bper] scratch.  Fixed summation order, no atomics.
 hipError_t att_sup_grad(hipStream_t st, int hops, int Bper, int S, const float* a, int a_rs, const float* t,
-                        int t_rs, const int32_t* nreg, const float* w_dev, float scale, float* da, int d_rs);
+                        int t_rs, const int32_t* nreg, const float* w_dev, float scale, float* da, int d_rs,
+                        const float* sw = nullptr);
 hipError_t att_sup_stats(hipStream_t st, int hops, int Bper, int S, const float* a, int a_rs, const float* t,
-                         int t_rs, const int32_t* nreg, float* rowf, int32_t* rowi, float* outf, int32_t* outi);
+                         int t_rs, const int32_t* nreg, float* rowf, int32_t* rowi, float* outf, int32_t* outi,
+                         const float* sw = nullptr);
 // The merged answers as training terms (merge_grad.hip, rau_backward_merged / rau_merge_criterion_backward):
 // dl [H][B][K] += the gradient of  w_uni CE(uni row) + w_sel CE(select row)  at the hop logits [H][B][K], the rows
 // hop_merge.h's under the feval rule (do_pred [H][B], the last hop not forced), the CE against t's labels [B] or

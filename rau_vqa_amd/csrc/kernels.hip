@@ -1843,7 +1843,7 @@ __global__ void k_ce_fwd(int nB, int K, int M, const float* __restrict__ logits,
                          int32_t* __restrict__ argmax, float* __restrict__ dopred,
                          const float* __restrict__ part, int nsplit,
                          const float* __restrict__ bias, float* __restrict__ logits_out,
-                         int Bper, int ld) {
+                         int Bper, int ld, const float* __restrict__ sw) {
   RAU_CHAIN_PRIO();
   __shared__ float s_val[4];
   __shared__ int s_idx[4];
@@ -1891,14 +1891,17 @@ __global__ void k_ce_fwd(int nB, int K, int M, const float* __restrict__ logits,
   if (labels) {
     // rows = [hop][sample]: labels repeat every Bper rows; clamped like the token ids above
     const int y = min(max(labels[b % Bper], 1), K) - 1;
-    const float invB = 1.f / (float)Bper;
+    // sample weight s_b (rau_set_sample_weights; none: 1, and both products below are exact): invB becomes
+    // s_b invB, the loss row s_b (lse - lg[y]), each product rounded once.  One 4-byte load per workgroup.
+    const float sb = sw ? sw[b % Bper] : 1.f;
+    const float invB = __fmul_rn(sb, 1.f / (float)Bper);
     for (int k = tid; k < K; k += 256) {
       float p = expf(lg[k] - lse) * invB;
       if (k == y) p -= invB;
       dl[(size_t)b * ld + k] = p;
     }
     for (int k = K + tid; k < ld; k += 256) dl[(size_t)b * ld + k] = 0.f;   // the row's pad
-    if (tid == 0) lossrow[b] = lse - lg[y];
+    if (tid == 0) lossrow[b] = __fmul_rn(sb, lse - lg[y]);
   }
   // do_pred
   if (!mf) return;   // criterion-only use (uniform per launch)
@@ -1913,12 +1916,12 @@ __global__ void k_ce_fwd(int nB, int K, int M, const float* __restrict__ logits,
 hipError_t ce_fwd(hipStream_t st, int nB, int K, int M, const float* logits,
                   const int32_t* labels, const float* mf, const float* wd, const float* bd,
                   float* dl, float* lossrow, int32_t* argmax, float* dopred, const float* part,
-                  int nsplit, const float* bias, float* logits_out, int Bper, int ld) {
+                  int nsplit, const float* bias, float* logits_out, int Bper, int ld, const float* sw) {
   if (!split_span_ok(part, nsplit, (size_t)nB * K)) return kSplitStateError;
   if (ld != 0 && ld < K) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_ce_fwd, dim3(nB), dim3(256), 0, st, nB, K, M, logits, labels, mf, wd, bd,
                      dl, lossrow, argmax, dopred, part, nsplit, bias, logits_out,
-                     Bper > 0 ? Bper : nB, ld ? ld : K);
+                     Bper > 0 ? Bper : nB, ld ? ld : K, sw);
   return hipGetLastError();
 }
 

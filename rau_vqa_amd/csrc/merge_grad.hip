@@ -10,7 +10,9 @@
 // formulation with every rounding spelled out:
 //   g[k] = expf(row[k] - lse) (W invB), then for g = 0..G-1 in order: if (y_g == k) g[k] -= w_g invB
 // (the first matching entry inside the product's fused multiply-add); a label is the set {y} with w = 1, which gives
-// k_ce_fwd's  expf(row[k] - lse) invB - [k == y] invB.  The update of one element, each step rounded once:
+// k_ce_fwd's  expf(row[k] - lse) invB - [k == y] invB.  With a sample weight s_b (rau_set_sample_weights) invB is
+// __fmul_rn(s_b, 1 / B) in both products, as in the criterion heads; without weights s_b = 1 and it is 1 / B exactly.
+// The update of one element, each step rounded once:
 //   x = dl[h,b,k];  x = x + (w_uni / H) g_u[k];  if (h == hsel) x = x + w_sel g_s[k]
 // A term whose weight is zero is SKIPPED, not added as zero: dl keeps its bits (the sign of a -0 included).
 //
@@ -38,7 +40,7 @@ template <bool kStage, bool kRag>
 __global__ __launch_bounds__(kMT) void k_merge_grad(int H, int B, int K, int ld, const float* __restrict__ logits,
     const float* __restrict__ dopred, const int32_t* __restrict__ labels, const int32_t* __restrict__ ids,
     const float* __restrict__ w, int G, const float* __restrict__ mw_dev, float w_uni, float w_sel,
-    float* __restrict__ dl) {
+    float* __restrict__ dl, const float* __restrict__ sw) {
   RAU_CHAIN_PRIO();
   extern __shared__ float4 s_rows4[];   // kStage: the uni row [ld], then the select row [ld]
   __shared__ float s_val[4];
@@ -55,7 +57,7 @@ __global__ __launch_bounds__(kMT) void k_merge_grad(int H, int B, int K, int ld,
   if (!term[0] && !term[1]) return;   // uniform over the workgroup
   const size_t hs = (size_t)B * ld;
   const float* lg = logits + (size_t)b * ld;
-  const float invB = 1.f / (float)B;
+  const float invB = __fmul_rn(sw ? sw[b] : 1.f, 1.f / (float)B);   // one 4-byte load per workgroup
   const int Gs = G > 0 ? G : 1;   // a label is a set of one entry with weight 1
   if (tid < Gs) {
     int id;
@@ -153,7 +155,7 @@ hipError_t merge_grad(hipStream_t st, int H, int B, int K, const float* logits, 
   const bool stage = rows <= kMergeLds;
 #define RAU_MERGE_GRAD(S, R)                                                                                       \
   hipLaunchKernelGGL((k_merge_grad<S, R>), dim3(B), dim3(kMT), S ? rows : 0, st, H, B, K, ld, logits, dopred,      \
-                     t.labels, t.ids, t.w, t.G, mw_dev, w_uni, w_sel, dl)
+                     t.labels, t.ids, t.w, t.G, mw_dev, w_uni, w_sel, dl, t.sw)
   if (ld == K) {
     if (stage) RAU_MERGE_GRAD(true, false);
     else RAU_MERGE_GRAD(false, false);

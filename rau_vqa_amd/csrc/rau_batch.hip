@@ -294,6 +294,7 @@ void hold(rau_ctx* ctx, int si, const Batch& b) {
   d.ans_G = 0;   // an answer set belongs to the batch it was given to
   d.regions = b.pk_counts != nullptr;   // ... and so do region counts (a packed batch brings its own)
   d.att_targets = false;   // ... and attention targets
+  d.sample_w = false;      // ... and per-sample loss weights
   d.question = false;      // ... and the caller's question state
 }
 
@@ -334,7 +335,7 @@ int set_batch_sync(rau_ctx* ctx, Batch b) {
     HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
   if (int rc = enqueue_batch(ctx, ctx->st, si, b)) return rc;
   HIPC(hipStreamSynchronize(ctx->st));   // the caller's (pageable) buffers are free on return
-  s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
+  s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
   hold(ctx, si, b);
   drop_forward(ctx);
   return RAU_OK;
@@ -366,7 +367,7 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   // that call performs the same wait before the caller's own writes -- include/rau.h.)
   if (s.upload_pending) {
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
   }
   // NULL = the caller has filled the slot's pinned staging in place (rau_batch_slot)
   if (b.feats && b.feats != s.feats_h) std::memcpy(s.feats_h, b.feats, nf * feat_elem_bytes(b.feat_type));
@@ -446,6 +447,24 @@ int ensure_regions(rau_ctx* ctx, int si) {
     hipError_t e = hipHostMalloc(&h, (size_t)ctx->cap * 4, hipHostMallocDefault);
     if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(region count staging): %s", hipGetErrorString(e));
     s.nreg_h = static_cast<int32_t*>(h);
+  }
+  return RAU_OK;
+}
+
+// first sample weights of a slot: the device array [capacity] the loss kernels read and the pinned staging the copies
+// read
+int ensure_sample_weights(rau_ctx* ctx, int si) {
+  BatchSlot& s = ctx->slot[si];
+  if (!s.sw_d) {
+    if (int rc = dalloc(ctx, &s.sw_d, (size_t)ctx->cap)) return rc;
+    // dalloc clears the array on the chain stream; the slot form copies into it on the copy stream.  Once per slot.
+    HIPC(hipStreamSynchronize(ctx->st));
+  }
+  if (!s.sw_h) {
+    void* h = nullptr;
+    hipError_t e = hipHostMalloc(&h, (size_t)ctx->cap * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(sample weight staging): %s", hipGetErrorString(e));
+    s.sw_h = static_cast<float*>(h);
   }
   return RAU_OK;
 }
@@ -641,7 +660,7 @@ static int set_batch_dev(rau_ctx* ctx, const char* who, const float* feats_dev, 
   }
   if (int rc = enqueue_batch(ctx, st, si, b)) return rc;   // (feats == NULL: the index arrays only)
   HIPC(hipEventRecord(ctx->bdev_ev[sl], st));
-  s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
+  s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
   hold(ctx, si, b);
   drop_forward(ctx);
   return RAU_OK;
@@ -697,7 +716,7 @@ int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_
   BatchSlot& s = ctx->slot[slot];
   if (s.upload_pending) {   // the caller is about to overwrite the staging: its last copy must have left
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
   }
   if (feats_host) *feats_host = s.feats_h;
   if (tokens_host) *tokens_host = s.tokens_h;
@@ -802,7 +821,7 @@ int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const
   if (int rc = ensure_answers(ctx, si)) return rc;
   if (s.ans_pending) {   // the staging's previous set has not left it yet (two sets for one upload)
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
   }
   int32_t* ids_h = s.ans_h;
   float* w_h = reinterpret_cast<float*>(s.ans_h + n);
@@ -865,7 +884,7 @@ int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n) {
   if (int rc = ensure_regions(ctx, si)) return rc;
   if (s.reg_pending) {   // the staging's previous counts have not left it yet (two sets for one upload)
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
   }
   std::memcpy(s.nreg_h, n, (size_t)c.B * 4);
   hipStream_t st = slot < 0 ? ctx->st : ctx->stc;
@@ -883,7 +902,7 @@ int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n) {
   if (slot < 0) {
     HIPC(hipStreamSynchronize(st));
     // (the chain stream waited for a pending upload above: every copy behind `uploaded` has left its staging)
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
   } else {
     HIPC(hipEventRecord(s.uploaded, st));   // rau_use_batch orders the step behind the counts too
     s.upload_pending = s.reg_pending = true;
@@ -922,7 +941,7 @@ int rau_set_att_targets(rau_ctx* ctx, int slot, const float* t) {
   if (int rc = ensure_att_targets(ctx, si)) return rc;
   if (s.att_pending) {   // the staging's previous maps have not left it yet (two sets for one upload)
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
   }
   std::memcpy(s.att_t_h, t, n * 4);
   hipStream_t st = slot < 0 ? ctx->st : ctx->stc;
@@ -944,7 +963,7 @@ int rau_set_att_targets(rau_ctx* ctx, int slot, const float* t) {
   if (slot < 0) {
     HIPC(hipStreamSynchronize(st));
     // (the chain stream waited for a pending upload above: every copy behind `uploaded` has left its staging)
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
   } else {
     HIPC(hipEventRecord(s.uploaded, st));   // rau_use_batch orders the step behind the targets too
     s.upload_pending = s.att_pending = true;
@@ -957,6 +976,69 @@ int rau_set_att_targets(rau_ctx* ctx, int slot, const float* t) {
 int rau_batch_att_targets(rau_ctx* ctx, int* has) {
   NEED(ctx && has, "null argument");
   *has = cur_batch(ctx).held.att_targets ? 1 : 0;
+  return RAU_OK;
+}
+
+// Per-sample loss weights for the batch in a slot: rau_set_regions' slot and ordering rules; NULL detaches them.
+// Everything is checked before anything moves.  The forward's head reads them: a forward that ran must run again.
+int rau_set_sample_weights(rau_ctx* ctx, int slot, const float* sw) {
+  NEED(ctx, "null ctx");
+  NEED(slot >= -1 && slot <= 1, "rau_set_sample_weights: slot %d (-1 = the resident batch, 0 or 1)", slot);
+  if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_sample_weights: a step is being captured");
+  const rau_config& c = ctx->cfg;
+  const int si = slot < 0 ? ctx->cur_slot : slot;
+  BatchSlot& s = ctx->slot[si];
+  if (!s.held.have)
+    return fail(RAU_ERR_STATE, "rau_set_sample_weights: slot %d holds no batch (upload the batch first)", si);
+  if (slot >= 0 && si == ctx->cur_slot && ctx->fwd.done)
+    return fail(RAU_ERR_STATE, "rau_set_sample_weights: slot %d is the current batch of a forward pass whose backward "
+                "has not run", si);
+  if (!sw) {   // detach: nothing moves, the next step is the unweighted one
+    if (s.held.sample_w && si == ctx->cur_slot) drop_forward(ctx);
+    s.held.sample_w = false;
+    return RAU_OK;
+  }
+  for (int b = 0; b < c.B; ++b)
+    NEED(std::isfinite(sw[b]) && sw[b] >= 0.f, "rau_set_sample_weights: s[%d]=%g is negative or not finite", b,
+         (double)sw[b]);
+  if (slot >= 0)
+    if (int rc = ensure_async(ctx)) return rc;
+  if (int rc = ensure_sample_weights(ctx, si)) return rc;
+  if (s.sw_pending) {   // the staging's previous weights have not left it yet (two sets for one upload)
+    HIPC(hipEventSynchronize(s.uploaded));
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+  }
+  std::memcpy(s.sw_h, sw, (size_t)c.B * 4);
+  hipStream_t st = slot < 0 ? ctx->st : ctx->stc;
+  if (slot < 0) {
+    if (s.upload_pending) HIPC(hipStreamWaitEvent(st, s.uploaded, 0));   // behind an asynchronous upload of the batch
+  } else {
+    // the slot's buffers may still be read by the last step that used them
+    if (si == ctx->cur_slot) {
+      HIPC(hipEventRecord(s.consumed, ctx->st));
+      s.consumed_valid = true;
+    }
+    if (s.consumed_valid) HIPC(hipStreamWaitEvent(st, s.consumed, 0));
+  }
+  HIPC(hipMemcpyAsync(s.sw_d, s.sw_h, (size_t)c.B * 4, hipMemcpyHostToDevice, st));
+  if (slot < 0) {
+    HIPC(hipStreamSynchronize(st));
+    // (the chain stream waited for a pending upload above: every copy behind `uploaded` has left its staging)
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+  } else {
+    HIPC(hipEventRecord(s.uploaded, st));   // rau_use_batch orders the step behind the weights too
+    s.upload_pending = s.sw_pending = true;
+    if (si == ctx->cur_slot) HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
+  }
+  s.held.sample_w = true;
+  if (si == ctx->cur_slot) drop_forward(ctx);   // a forward that ran on the batch did not see these weights
+  if (si == ctx->mg.slot) ctx->mg.valid = false;   // statistics of a forward whose weights have just been overwritten
+  return RAU_OK;
+}
+
+int rau_batch_sample_weights(rau_ctx* ctx, int* has) {
+  NEED(ctx && has, "null argument");
+  *has = cur_batch(ctx).held.sample_w ? 1 : 0;
   return RAU_OK;
 }
 

@@ -93,6 +93,9 @@ struct BatchDesc {
   // attention targets (rau_set_att_targets): the slot's att_t_d holds a target map per sample.  They belong to the
   // batch like the two above.
   bool att_targets = false;
+  // per-sample loss weights (rau_set_sample_weights): the slot's sw_d holds one weight per sample, read by every
+  // kernel that forms a training term (step_truth()).  They belong to the batch like the three above.
+  bool sample_w = false;
   // question state from the caller (rau_set_question_dev): the slot's q_ext holds q [n][Q] and the step reads it in
   // place of the built-in encoder's output.  It belongs to the RESIDENT batch: hold() and rau_use_batch drop it.
   bool question = false;
@@ -136,6 +139,11 @@ struct BatchSlot {
   float* att_t_d = nullptr;
   float* att_t_h = nullptr;
   bool att_pending = false;         // a copy out of att_t_h is behind the last record of `uploaded`
+  // per-sample loss weights of the batch: [capacity] device and pinned host, allocated at the slot's first set (a
+  // captured step holds sw_d's address, never its contents)
+  float* sw_d = nullptr;
+  float* sw_h = nullptr;
+  bool sw_pending = false;          // a copy out of sw_h is behind the last record of `uploaded`
   // the caller's question state (rau_set_question_dev): device [capacity][Q] f32, allocated at the slot's first
   // attach (a captured step holds q_ext's address, never its contents)
   float* q_ext = nullptr;
@@ -251,10 +259,12 @@ struct StepKey {
                                 // gradient: the mode (per sample / per image of a table: another accumulate kernel)
   bool question = false;        // ... and with a question attached (rau_set_question_dev) neither pass launches the
                                 // encoder: the hop chain reads the slot's q_ext
+  bool sample_w = false;        // ... and the kernels that form the training terms hold the slot's sample weights
+                                // or a null pointer (rau_set_sample_weights); a replay reads the current weights
   auto tied() const {
     return std::tie(mode, max_len, active, zero, mexplicit[0], mexplicit[1], mexplicit[2], mexplicit[3], mexplicit[4],
                     slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg, tied_x, ans_loss,
-                    feat_grad, question);
+                    feat_grad, question, sample_w);
   }
   bool operator==(const StepKey& o) const { return tied() == o.tied(); }
 };
@@ -501,6 +511,7 @@ inline StepKey step_key(const rau_ctx* ctx, const StepLoss& loss, bool zero) {
   key.ans_loss = ctx->answer_loss;
   key.feat_grad = ctx->feat_grad;
   key.question = d.question;
+  key.sample_w = d.sample_w;
   return key;
 }
 
@@ -544,8 +555,10 @@ inline LinOpts lin_opts(const rau_ctx* ctx, const StreamWs& ws) {
 }
 // The resident batch's ground truth with the criterion the step path trains it with (rau_set_answer_loss)
 inline Truth step_truth(const rau_ctx* ctx) {
-  Truth t = truth_of(cur_batch(ctx));
+  const BatchSlot& s = cur_batch(ctx);
+  Truth t = truth_of(s);
   t.loss = ctx->answer_loss;
+  t.sw = s.held.sample_w ? s.sw_d : nullptr;   // the step path's terms only: module-level criteria stay unweighted
   return t;
 }
 // The hop outputs now hold the results of the forward just enqueued: rau_step_stats / rau_predict may

@@ -611,6 +611,7 @@ void rau_destroy(rau_ctx* ctx) {
     if (s.bank_idx_h) hipHostFree(s.bank_idx_h);
     if (s.ans_h) hipHostFree(s.ans_h);
     if (s.nreg_h) hipHostFree(s.nreg_h);
+    if (s.sw_h) hipHostFree(s.sw_h);
     if (s.att_t_h) hipHostFree(s.att_t_h);
     if (s.pk_meta_h) hipHostFree(s.pk_meta_h);
     if (s.uploaded) hipEventDestroy(s.uploaded);
@@ -946,7 +947,7 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
   for (int si = 0; si < 2; ++si) {
     ctx->slot[si].held = BatchDesc{};
     ctx->slot[si].upload_pending = ctx->slot[si].consumed_valid = ctx->slot[si].ans_pending = false;
-    ctx->slot[si].reg_pending = ctx->slot[si].att_pending = false;
+    ctx->slot[si].reg_pending = ctx->slot[si].att_pending = ctx->slot[si].sw_pending = false;
     ++ctx->slot_serial[si];
   }
   ctx->cur_slot = 0;
@@ -1741,7 +1742,7 @@ static int loss_gradients(rau_ctx* ctx, const StepLoss& loss, const Truth& t) {
   if (att)
     RUN("att_sup_grad", 0, (double)HA * B * S * 12,
         att_sup_grad(st, HA, B, SL, ctx->a, S, bs.att_t_d, S, bs.held.regions ? bs.nreg_d : nullptr,
-                     ctx->hopw_d + at.att_w, 0.f, ctx->att_da, S));
+                     ctx->hopw_d + at.att_w, 0.f, ctx->att_da, S, t.sw));
   if (ext.d_attprob)   // the dense [H,n,S] gradient (added) into the pitched addend, zeros behind the counts
     RUN("ext_da", 0, (double)HA * B * S * (att ? 12 : 8),
         ext_da(st, HA, B, SL, ext.d_attprob, bs.held.regions ? bs.nreg_d : nullptr, att, ctx->att_da, S));
@@ -2366,6 +2367,14 @@ int d2h(rau_ctx* ctx, void* host, const void* dev, size_t bytes) {
 int rau_get_losses(rau_ctx* ctx, float* losses) {
   NEED(ctx, "null ctx");
   return d2h(ctx, losses, ctx->losses_d, ctx->cfg.H * sizeof(float));
+}
+// The per-sample loss rows the losses are the means of (with sample weights: the weighted rows), dense [H, n]
+int rau_get_loss_rows(rau_ctx* ctx, float* rows) {
+  NEED(ctx && rows, "null argument");
+  if (!ctx->mg.valid || !ctx->mg.truth.present())
+    return fail(RAU_ERR_STATE, "rau_get_loss_rows: no step-level forward on a batch with a ground truth has left its "
+                "loss rows (none has run yet, it failed, or a module-level entry point has run since)");
+  return d2h(ctx, rows, ctx->lossrow, (size_t)ctx->cfg.H * ctx->cfg.B * sizeof(float));
 }
 int rau_get_argmax(rau_ctx* ctx, int32_t* ans) {
   NEED(ctx, "null ctx");

@@ -37,6 +37,27 @@ __global__ void k_select_rows(int rows, int cols, const int32_t* __restrict__ ke
        i += (size_t)gridDim.x * blockDim.x)
     if (key[i / cols] == value) dst[i] = src[i];
 }
+// x[r, 0..cols) *= s[r] over the row pitch ld, one workgroup per row (one 4-byte load of s[r]); each product rounded
+// once.  VEC (ld % 4 == 0, x 16-byte aligned): the cols / 4 whole quads go 16 bytes wide, the cols % 4 tail scalar;
+// columns cols..ld-1 are never touched.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_scale_rows(int cols, size_t ld, const float* __restrict__ s,
+                                                    float* __restrict__ x) {
+  const float sr = s[blockIdx.x];
+  float* row = x + (size_t)blockIdx.x * ld;
+  int k0 = 0;
+  if (VEC) {
+    const int nq = cols >> 2;
+    float4* row4 = reinterpret_cast<float4*>(row);
+    for (int q = threadIdx.x; q < nq; q += 256) {
+      float4 v = row4[q];
+      v.x = __fmul_rn(v.x, sr); v.y = __fmul_rn(v.y, sr); v.z = __fmul_rn(v.z, sr); v.w = __fmul_rn(v.w, sr);
+      row4[q] = v;
+    }
+    k0 = nq << 2;
+  }
+  for (int k = k0 + threadIdx.x; k < cols; k += 256) row[k] = __fmul_rn(row[k], sr);
+}
 // torch.max(x, 2): per row the maximum and the FIRST index attaining it, 1-based
 __global__ void k_rowmax(int cols, const float* __restrict__ x, float* __restrict__ mv,
                          int32_t* __restrict__ mi) {
@@ -216,6 +237,18 @@ int rau_dev_select_rows(rau_ctx* ctx, float* dst, const float* src, int32_t rows
   if (n)
     hipLaunchKernelGGL(k_select_rows, dim3(blocks_for(n)), dim3(256), 0, ctx->st, rows, cols, key_dev,
                        value, src, dst);
+  HIPC(hipGetLastError());
+  return RAU_OK;
+}
+int rau_dev_scale_rows(rau_ctx* ctx, float* x, int32_t rows, int32_t cols, int32_t ld, const float* s_dev) {
+  NEED(ctx && x && s_dev, "null argument");
+  NEED(rows >= 0 && cols > 0 && ld >= cols, "rau_dev_scale_rows: bad shape %d x %d at pitch %d", rows, cols, ld);
+  if (rows) {
+    if ((ld & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15u) == 0)
+      hipLaunchKernelGGL(k_scale_rows<true>, dim3(rows), dim3(256), 0, ctx->st, cols, (size_t)ld, s_dev, x);
+    else
+      hipLaunchKernelGGL(k_scale_rows<false>, dim3(rows), dim3(256), 0, ctx->st, cols, (size_t)ld, s_dev, x);
+  }
   HIPC(hipGetLastError());
   return RAU_OK;
 }

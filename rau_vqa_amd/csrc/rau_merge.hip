@@ -84,7 +84,7 @@ int rau_att_stats(rau_ctx* ctx, float* loss, float* mass, int32_t* hits, int32_t
   int32_t* outi = ctx->att_si + 2 * (size_t)H * ctx->cap;
   RUN("att_sup_stats", 0, (double)H * B * S * 8,
       att_sup_stats(ctx->st, H, B, c.S, ctx->a, S, bs.att_t_d, S, bs.held.regions ? bs.nreg_d : nullptr, ctx->att_sf,
-                    ctx->att_si, outf, outi));
+                    ctx->att_si, outf, outi, ctx->mg.truth.sw));
   std::vector<float> of(2 * (size_t)H);
   std::vector<int32_t> oi(2 * (size_t)H);
   HIPC(hipMemcpyAsync(of.data(), outf, of.size() * 4, hipMemcpyDeviceToHost, ctx->st));

@@ -7,6 +7,8 @@
 //         k_step_stats_rows' / k_step_stats_rows_set's rule; a constant
 //   ddp = select_w[h] * ( -(t - x) / ((1 - x + eps) * (x + eps)) ) / n
 //   s   = ddp * x * (1 - x)                                   (through the sigmoid)
+// With a sample weight s_b (rau_set_sample_weights) select_w[h] is replaced by __fmul_rn(select_w[h], s_b), the rest
+// of the formula unchanged; without weights s_b = 1 and the product is select_w[h] exactly.
 // k_select_signal writes s [rows] and the rank-1 term add[r][m] = s[r] wd[m] that enters dmf in front of the
 // merge_feat dropout mask (the addend of the head_dgrad GEMM); k_select_wgrad adds sum_r s[r] mf[r][:] to the
 // head's weight gradient and sum_r s[r] to its bias gradient in one pass, summed in a fixed order: no atomics,
@@ -23,7 +25,7 @@ namespace {
 __global__ __launch_bounds__(256) void k_select_signal(int Bper, int K, int M, const float* __restrict__ dopred,
     const int32_t* __restrict__ argmax, const int32_t* __restrict__ labels, const int32_t* __restrict__ ids,
     const float* __restrict__ score, int G, const float* __restrict__ selw, const float* __restrict__ wd,
-    float* __restrict__ s_out, float* __restrict__ add) {
+    float* __restrict__ s_out, float* __restrict__ add, const float* __restrict__ sw) {
   RAU_CHAIN_PRIO();
   const int r = blockIdx.x;
   const int h = r / Bper, b = r - h * Bper;
@@ -45,7 +47,8 @@ __global__ __launch_bounds__(256) void k_select_signal(int Bper, int K, int M, c
   const float eps = 1e-12f;
   const float num = -__fsub_rn(t, x);
   const float den = __fmul_rn(__fadd_rn(__fsub_rn(1.f, x), eps), __fadd_rn(x, eps));
-  const float ddp = __fdiv_rn(__fmul_rn(selw[h], __fdiv_rn(num, den)), (float)Bper);
+  const float wh = __fmul_rn(selw[h], sw ? sw[b] : 1.f);   // one 4-byte load per workgroup
+  const float ddp = __fdiv_rn(__fmul_rn(wh, __fdiv_rn(num, den)), (float)Bper);
   const float s = __fmul_rn(__fmul_rn(ddp, x), __fsub_rn(1.f, x));
   if (threadIdx.x == 0) s_out[r] = s;
   for (int m = threadIdx.x; m < M; m += 256) add[(size_t)r * M + m] = __fmul_rn(s, wd[m]);
@@ -81,7 +84,7 @@ hipError_t select_signal(hipStream_t st, int rows, int Bper, int K, int M, const
   if (Bper < 1 || rows % Bper || t.G < 0 || t.G > kMaxAnswers || (t.G > 0 ? !t.ids || !t.score : !t.labels))
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_select_signal, dim3(rows), dim3(256), 0, st, Bper, K, M, dopred, argmax, t.labels, t.ids,
-                     t.score, t.G, selw, wd, s, add);
+                     t.score, t.G, selw, wd, s, add, t.sw);
   return hipGetLastError();
 }
 

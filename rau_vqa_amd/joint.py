@@ -16,18 +16,35 @@ from .predict import first_max
 BCE_EPS = np.float32(1e-12)   # nn.BCECriterion's eps
 
 
-def cross_entropy(pred, y):
-    """nn.CrossEntropyCriterion (sizeAverage) of [B, K] float32 rows, y 1-based [B]."""
+def weighted_mean(rows, s=None):
+    """(1/n) sum_b s_b rows[..., b]: what every built-in mean of the step path becomes under per-sample loss weights
+    s [n] (rau_set_sample_weights; never renormalised).  Each product s_b * row is rounded once in the dtype of rows
+    (float32 unless float64 is given), then the rows are summed and divided by n.  s None: the plain mean."""
+    rows = _f32_unless_f64(rows)
+    dt = rows.dtype
+    if s is not None:
+        rows = (np.asarray(s, dt) * rows).astype(dt)
+    return (rows.sum(axis=-1, dtype=dt) / dt.type(rows.shape[-1])).astype(dt)
+
+
+def cross_entropy(pred, y, sample_w=None):
+    """nn.CrossEntropyCriterion (sizeAverage) of [B, K] float32 rows, y 1-based [B]; sample_w [B]: weighted_mean of
+    the rows."""
     mx = pred.max(axis=1)
     lse = mx + np.log(np.exp(pred - mx[:, None]).sum(axis=1, dtype=np.float32))
     row = lse - pred[np.arange(pred.shape[0]), y - 1]
+    if sample_w is not None:
+        row = (np.asarray(sample_w, np.float32) * row).astype(np.float32)
     return np.float32(row.sum(dtype=np.float32) / np.float32(pred.shape[0]))
 
 
-def bce(x, t):
-    """nn.BCECriterion (sizeAverage): -(t log(x + eps) + (1 - t) log(1 - x + eps)), mean over B."""
+def bce(x, t, sample_w=None):
+    """nn.BCECriterion (sizeAverage): -(t log(x + eps) + (1 - t) log(1 - x + eps)), mean over B; sample_w [B]:
+    weighted_mean of the terms."""
     one = np.float32(1)
     term = -(t * np.log(x + BCE_EPS) + (one - t) * np.log(one - x + BCE_EPS))
+    if sample_w is not None:
+        term = (np.asarray(sample_w, np.float32) * term).astype(np.float32)
     return np.float32(term.sum(dtype=np.float32) / np.float32(x.shape[0]))
 
 
@@ -39,7 +56,8 @@ def _f32_unless_f64(a):
 def bce_grad(x, t, w):
     """nn.BCECriterion:backward (sizeAverage) scaled by w -- the reference's d_do_pred before its mul(0),
     SS:565-566, and the contract of rau_backward_select: w * (-(t - x) / ((1 - x + eps) * (x + eps))) / n, in
-    this order, n = x.shape[-1].  x, t [..., n]; w a scalar, or [H] for [H, n] inputs.  Float32 arithmetic (the
+    this order, n = x.shape[-1].  x, t [..., n]; w a scalar, or [H] for [H, n] inputs, or [H, n]: hop weight times
+    sample weight as ONE rounded product, select_w[h] * s_b (hop_sample_weights).  Float32 arithmetic (the
     device's), unless x is given as float64 (for references).  Torch tensors of one device are taken as they
     are: only arithmetic is used."""
     eps = float(BCE_EPS)
@@ -53,8 +71,16 @@ def bce_grad(x, t, w):
     return w * (-(t - x) / ((one - x + eps) * (x + eps))) / x.dtype.type(x.shape[-1])
 
 
+def hop_sample_weights(w, s, dtype=np.float32):
+    """[H, n] = w[h] * s[b], each product rounded once in dtype: the weight array bce_grad, select_signal and
+    att_ce_grad take for a batch with per-sample loss weights s (the device's __fmul_rn(select_w[h], s_b))."""
+    w, s = np.asarray(w, dtype), np.asarray(s, dtype)
+    return (w[:, None] * s[None, :]).astype(dtype)
+
+
 def select_signal(x, t, w):
-    """bce_grad through the head's sigmoid: the gradient at Linear(M,1)'s output, s = ddp * x * (1 - x)."""
+    """bce_grad through the head's sigmoid: the gradient at Linear(M,1)'s output, s = ddp * x * (1 - x); w as in
+    bce_grad (a scalar, [H] or [H, n])."""
     if not hasattr(x, "is_cuda"):
         x = _f32_unless_f64(x)
     return bce_grad(x, t, w) * x * (1 - x)
@@ -80,51 +106,60 @@ def _att_valid(shape, nreg):
     return np.arange(S)[None, :] < n[:, None]
 
 
-def att_ce(a, t, nreg=None):
+def att_ce(a, t, nreg=None, sample_w=None):
     """The attention supervision's loss (rau_backward_att): ATT = (1/n) sum_b sum_{s < nreg[b]} t (-log(a + eps)).
     a [n, S] or [H, n, S] attention, t [n, S] targets >= 0, nreg [n] region counts or None -> a scalar, or [H].
-    Float32 arithmetic unless a is given as float64."""
+    sample_w [n]: per-sample loss weights, ATT = (1/n) sum_b s_b sum_s term[b, s]: every term of sample b is
+    multiplied by s_b (each product rounded once) and the sum is the unweighted one's, so weights all equal to 1 give
+    the unweighted bits.  Float32 arithmetic unless a is given as float64."""
     a = _f32_unless_f64(a)
     t = np.where(_att_valid(a.shape, nreg), np.asarray(t, a.dtype), a.dtype.type(0))
     term = np.where(t > 0, t * -np.log(a + a.dtype.type(BCE_EPS)), a.dtype.type(0))
+    if sample_w is not None:
+        term = (np.asarray(sample_w, a.dtype)[:, None] * term).astype(a.dtype)
     return term.sum(axis=(-2, -1), dtype=a.dtype) / a.dtype.type(a.shape[-2])
 
 
 def att_ce_grad(a, t, w, nreg=None):
     """d(w * att_ce)/da, the contract of rau_backward_att: -((w * t) / (a + eps)) / n in this order, n = a.shape[-2];
-    exactly +0 where t == 0 or s >= nreg[b].  w a scalar, or [H] for [H, n, S] inputs.  Float32 arithmetic (the
-    device's), unless a is given as float64 (for references)."""
+    exactly +0 where t == 0 or s >= nreg[b].  w a scalar, or [H] for [H, n, S] inputs, or [H, n]: hop weight times
+    sample weight as one rounded product, att_w[h] * s_b (hop_sample_weights).  Float32 arithmetic (the device's),
+    unless a is given as float64 (for references)."""
     a = _f32_unless_f64(a)
     t, w = np.asarray(t, a.dtype), np.asarray(w, a.dtype)
     if w.ndim == 1:
         w = w[:, None, None]
+    elif w.ndim == 2:
+        w = w[:, :, None]
     on = _att_valid(a.shape, nreg) & (t > 0)
     t = np.where(on, t, a.dtype.type(0))
     g = -((w * t) / (a + a.dtype.type(BCE_EPS))) / a.dtype.type(a.shape[-2])
     return np.where(on, g, a.dtype.type(0)).astype(a.dtype)
 
 
-def att_stats(a, t, nreg=None):
+def att_stats(a, t, nreg=None, sample_w=None):
     """What RAU.att_stats reports, of a [H, n, S] against t [n, S] (nreg [n] or None), in float64: ``loss`` [H] =
     att_ce, ``mass`` [H] = mean over the supervised rows of the attention on the positions with t > 0, ``hits`` [H]
     = supervised rows whose first-max attention position has t > 0, ``n_sup`` = supervised rows (some t > 0 below
-    the count).  Positions behind a count take no part."""
+    the count).  Positions behind a count take no part.  sample_w [n]: ``loss`` takes s_b per row (att_ce's); mass,
+    hits and n_sup stay unweighted."""
     a = np.asarray(a, np.float64)
     valid = _att_valid(a.shape, nreg)
     pos = (np.asarray(t) > 0) & valid                        # [n, S]
     sup = pos.any(axis=1)
     n_sup = int(sup.sum())
-    loss = att_ce(a, np.asarray(t, np.float64), nreg)
+    loss = att_ce(a, np.asarray(t, np.float64), nreg, sample_w)
     mass = (a * pos).sum(axis=2)[:, sup].sum(axis=1) / max(n_sup, 1)
     arg = np.where(valid, a, -1.0).argmax(axis=2)            # first maximum below the count
     hit = np.take_along_axis(np.broadcast_to(pos, a.shape), arg[..., None], axis=2)[..., 0] & sup
     return {"loss": loss, "mass": mass, "hits": hit.sum(axis=1).astype(np.int32), "n_sup": n_sup}
 
 
-def feval_stats(logits, dopred, labels):
+def feval_stats(logits, dopred, labels, sample_w=None):
     """logits [H, B, K], dopred [H, B], labels [B] (1-based) -> dict with the keys of
     ``RAU.step_stats`` (loss [H+2], loss_do_pred [H], correct [H+2], do_pred_correct [H],
-    did_correct, fired [H], selected [H]) plus ``uni_ans`` / ``select_ans`` [B]."""
+    did_correct, fired [H], selected [H]) plus ``uni_ans`` / ``select_ans`` [B].
+    sample_w [B] (rau_set_sample_weights): every loss takes s_b per row; the counts stay unweighted."""
     logits = np.asarray(logits, np.float32)
     dopred = np.asarray(dopred, np.float32)
     y = np.asarray(labels, np.int64)
@@ -150,19 +185,19 @@ def feval_stats(logits, dopred, labels):
         selected.append(int(pred_cur_hop.sum()))
         did_correct = np.clip(did_correct + is_correct, 0, 1)   # SS:513
         did_pred = np.clip(did_pred + do_pred, 0, 1)         # SS:515
-        tab_loss.append(cross_entropy(pred, y))              # SS:518-519
+        tab_loss.append(cross_entropy(pred, y, sample_w))    # SS:518-519
     uni_pred = uni_pred / np.float32(H)                      # SS:522
     uni_ans = first_max(uni_pred)                            # SS:524
     correct.append(int((uni_ans == y).sum()))                # SS:526
-    tab_loss.append(cross_entropy(uni_pred, y))              # SS:529-530
+    tab_loss.append(cross_entropy(uni_pred, y, sample_w))    # SS:529-530
     select_ans = first_max(select_pred)                      # SS:534
     correct.append(int((select_ans == y).sum()))             # SS:536
-    tab_loss.append(cross_entropy(select_pred, y))           # SS:539-540
+    tab_loss.append(cross_entropy(select_pred, y, sample_w))   # SS:539-540
     do_pred_correct, tab_loss_do_pred = [], []
     for h in range(H):
         do_pred = (tab_do_pred[h] > 0.5).astype(np.float32)  # SS:549
         do_pred_correct.append(int(((do_pred == tab_do_pred_gt[h]) * did_correct).sum()))   # SS:552
-        tab_loss_do_pred.append(bce(tab_do_pred[h], tab_do_pred_gt[h]))                      # SS:555
+        tab_loss_do_pred.append(bce(tab_do_pred[h], tab_do_pred_gt[h], sample_w))            # SS:555
     return {"loss": np.array(tab_loss, np.float32), "loss_do_pred": np.array(tab_loss_do_pred, np.float32),
             "correct": np.array(correct, np.int32), "do_pred_correct": np.array(do_pred_correct, np.int32),
             "did_correct": int(did_correct.sum()), "fired": np.array(fired, np.int32),

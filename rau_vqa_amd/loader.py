@@ -378,7 +378,7 @@ def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=12
     return v
 
 
-def feed(rau, batch, feat_type=None, answers=None, regions=None, att_targets=None):
+def feed(rau, batch, feat_type=None, answers=None, regions=None, att_targets=None, sample_w=None):
     """next_batch_feat's tuple -> rau_set_batch (the H2D of SS:434-439); returns qids.
     feat_type: that of the feats (needed for bf16 and fp8, which arrive as uint16 / uint8 bits).  A tuple of
     next_batch_feat(unique=True) goes up as an image table, one of next_batch_rows as a bank batch, one of
@@ -394,7 +394,10 @@ def feed(rau, batch, feat_type=None, answers=None, regions=None, att_targets=Non
     per image beside image_of / bank_rows; the regions= argument, when given, replaces it.
     att_targets = per-sample attention target maps [B, S] of the batch (human attention maps, boxes rendered onto
     the positions): attached with rau.set_att_targets once the batch is up; None changes nothing.  For a dict it
-    replaces the dict's own "att_targets" key."""
+    replaces the dict's own "att_targets" key.
+    sample_w = per-sample loss weights [B] of the batch (class- or question-type balancing, importance weights):
+    attached with rau.set_sample_weights once the batch is up; None changes nothing.  For a dict it replaces the
+    dict's own "sample_w" key."""
     if isinstance(batch, dict):
         kw = {k: v for k, v in batch.items() if k != "qids"}
         if feat_type is not None:
@@ -405,6 +408,8 @@ def feed(rau, batch, feat_type=None, answers=None, regions=None, att_targets=Non
             kw.pop("regions", None)
         if att_targets is not None:
             kw.pop("att_targets", None)
+        if sample_w is not None:
+            kw.pop("sample_w", None)
         rau.set_batch(**kw)
         qids = batch.get("qids")
     else:
@@ -415,6 +420,8 @@ def feed(rau, batch, feat_type=None, answers=None, regions=None, att_targets=Non
         rau.set_regions(regions)
     if att_targets is not None:
         rau.set_att_targets(att_targets)
+    if sample_w is not None:
+        rau.set_sample_weights(sample_w)
     return qids
 
 
@@ -452,6 +459,9 @@ class SlotFeeder:
             rau.forward(); rau.backward(w); ...              # enqueue step `it`
             qids = feeder.next()                              # batch it+1 resident for the next step
 
+    sample_w: a callable qids -> per-sample loss weights [B] (None: no weights); the weights go up behind every
+    batch's upload, on the copy stream (rau.set_sample_weights(slot=)).
+
     A feeder is BOUND to one batch size, the DataClass's: if the context runs another size when the
     feeder is made (a test split at test_batch_size below the capacity) it is switched first
     (rau.set_batch_size), and a feeder whose context has been switched since refuses to go on -- the
@@ -459,8 +469,9 @@ class SlotFeeder:
     """
 
     def __init__(self, rau, data: DataClass, tab_featpaths, feat_dim, feat_w=1, feat_h=1,
-                 feat_type=None, share_images=False, bank=False, packed=False):
+                 feat_type=None, share_images=False, bank=False, packed=False, sample_w=None):
         self.rau, self.data = rau, data
+        self.sample_w = sample_w
         self.n = int(data.batch_size)
         if getattr(rau, "batch_size", self.n) != self.n:
             rau.set_batch_size(self.n)     # raises above the capacity
@@ -504,6 +515,8 @@ class SlotFeeder:
                 rau.set_answers(*d.last_answers, slot=s)
             if d.last_regions is not None:
                 rau.set_regions(d.last_regions, slot=s)
+            if self.sample_w is not None:
+                rau.set_sample_weights(self.sample_w(qids), slot=s)
             rau.use_batch(s)
             return qids
         batch = d.next_batch_feat(*self.args, unique=self.share_images, packed=self.packed)
@@ -528,6 +541,8 @@ class SlotFeeder:
             rau.set_answers(*d.last_answers, slot=s)
         if d.last_regions is not None and not self.packed:   # ... and region counts: per sample, also for an image
             rau.set_regions(d.last_regions, slot=s)          # table (a packed batch brought its own)
+        if self.sample_w is not None:                 # ... and per-sample loss weights, looked up by question id
+            rau.set_sample_weights(self.sample_w(qids), slot=s)
         rau.use_batch(s)
         return qids
 

@@ -408,6 +408,46 @@ class RAU:
             raise ValueError(f"region counts must be [{B}], one per sample")
         return regions
 
+    # ---- per-sample loss weights: every training term of the step path (rau_set_sample_weights)
+    @staticmethod
+    def _sample_weights(s, B, normalize=False):
+        """s as float32 [B], checked on the host: shape, finite, >= 0.  normalize: rescaled in float64 so that the
+        weights sum to B (all-zero weights cannot be)."""
+        s = np.asarray(s)
+        if s.shape != (B,):
+            raise ValueError(f"sample weights must be [{B}], one per sample")
+        s64 = s.astype(np.float64)
+        if not np.isfinite(s64).all() or (s64 < 0).any():
+            raise ValueError("sample weights must be finite and >= 0")
+        if normalize:
+            tot = float(s64.sum())
+            if not tot > 0.0:
+                raise ValueError("sample weights that are all zero cannot be normalised")
+            s64 = s64 * (B / tot)
+        return np.ascontiguousarray(s64, np.float32)
+
+    def set_sample_weights(self, s, slot=-1, normalize=False):
+        """Give the batch in `slot` (-1 or None: the resident batch; 0 | 1: after set_batch_async(slot), before
+        use_batch(slot)) per-sample loss weights s [batch] >= 0: every built-in mean (1/n) sum_b row_b of the step
+        path -- the answer criterion, the selection BCE, the attention supervision, the merged rows -- becomes
+        (1/n) sum_b s_b row_b (joint.weighted_mean), and losses(), loss_rows(), step_stats()' and att_stats()' losses
+        follow; counts, metric scores and predictions stay unweighted.  The library never renormalises;
+        normalize=True rescales here, in float64, so that the weights sum to n.  A forward that already ran must be
+        run again.  The weights last until the next batch goes into that slot."""
+        s = self._sample_weights(s, self._n, normalize)
+        L.check(self._lib.rau_set_sample_weights(self._h, -1 if slot is None else int(slot), s.ctypes.data))
+
+    def clear_sample_weights(self, slot=-1):
+        """Detach the weights of the batch in `slot`: the next step is the unweighted one, bit for bit."""
+        L.check(self._lib.rau_set_sample_weights(self._h, -1 if slot is None else int(slot), None))
+
+    @property
+    def batch_sample_weights(self) -> bool:
+        """Whether the resident batch carries per-sample loss weights."""
+        v = C.c_int()
+        L.check(self._lib.rau_batch_sample_weights(self._h, C.byref(v)))
+        return bool(v.value)
+
     # ---- attention targets: supervise attprob on per-sample maps (rau_set_att_targets)
     def _att_targets(self, t, B):
         """t as float32 [B, S], checked on the host: shape, finite, >= 0."""
@@ -467,7 +507,7 @@ class RAU:
         return oe, mcs, tot
 
     def set_batch(self, feats, tokens, lens, labels=None, feat_type=None, image_of=None, bank_rows=None,
-                  answers=None, regions=None, att_targets=None):
+                  answers=None, regions=None, att_targets=None, sample_w=None):
         """feat_type "f32" | "f16" | "bf16" | "e4m3" | "e5m2" (default: from the dtype, see feat16.infer;
         bf16 is uint16 bits, fp8 is uint8 codes, both must be named): a 16-bit or fp8 map gives the same
         results, bit for bit, as the f32 map of its widened values.
@@ -479,11 +519,14 @@ class RAU:
         answers = (ids, w[, score]): set_answers on the batch once it is up.
         regions: set_regions on the batch once it is up; per sample [B], or with image_of / bank_rows per image
         [N] (gathered here: regions_of).
-        att_targets [B, S]: set_att_targets on the batch once it is up; always per sample."""
+        att_targets [B, S]: set_att_targets on the batch once it is up; always per sample.
+        sample_w [B]: set_sample_weights on the batch once it is up; always per sample."""
         if regions is not None:   # checked before anything reaches the library
             regions = self._sample_regions(regions, image_of, int(np.asarray(lens).shape[0]))
         if att_targets is not None:
             att_targets = self._att_targets(att_targets, int(np.asarray(lens).shape[0]))
+        if sample_w is not None:
+            sample_w = self._sample_weights(sample_w, int(np.asarray(lens).shape[0]))
         self._set_batch(feats, tokens, lens, labels, feat_type, image_of, bank_rows)
         if answers is not None:
             self.set_answers(*answers)
@@ -491,6 +534,8 @@ class RAU:
             self.set_regions(regions)
         if att_targets is not None:
             self.set_att_targets(att_targets)
+        if sample_w is not None:
+            self.set_sample_weights(sample_w)
 
     def _packed(self, rows, counts, image_of, B, feat_type):
         """(rows or None, feat type, n_maps, counts, image_of or None) of a packed batch of B samples, checked on
@@ -619,7 +664,7 @@ class RAU:
 
     def set_batch_async(self, slot, feats=None, tokens=None, lens=None, labels=None, has_labels=True,
                         feat_type=None, image_of=None, n_images=None, bank_rows=None, answers=None,
-                        regions=None, att_targets=None, packed_counts=None):
+                        regions=None, att_targets=None, packed_counts=None, sample_w=None):
         """Enqueue the upload of a batch into `slot` on the copy stream and return.  Arrays left None
         are taken from the slot's staging (filled in place through batch_slot).  feat_type: as in
         set_batch; with feats None it names what the staging holds (default "f32").
@@ -633,7 +678,8 @@ class RAU:
         att_targets [B, S]: set_att_targets(slot=slot) behind the upload.
         packed_counts [N]: feats is packed region rows [sum(packed_counts), D] (see set_batch_packed), or, with
         feats None, the slot's staging holds them at its start (batch_slot(...)["feats"] viewed flat); N is the
-        batch size, or with image_of the number of maps.  The counts become the batch's region counts."""
+        batch size, or with image_of the number of maps.  The counts become the batch's region counts.
+        sample_w [B]: set_sample_weights(slot=slot) behind the upload."""
         if packed_counts is not None and (regions is not None or bank_rows is not None):
             raise ValueError("a packed batch brings its own region counts and its own rows")
         if regions is not None:
@@ -641,6 +687,8 @@ class RAU:
             regions = self._sample_regions(regions, image_of, B)
         if att_targets is not None:
             att_targets = self._att_targets(att_targets, self._n if lens is None else int(np.asarray(lens).shape[0]))
+        if sample_w is not None:
+            sample_w = self._sample_weights(sample_w, self._n if lens is None else int(np.asarray(lens).shape[0]))
         self._set_batch_async(slot, feats, tokens, lens, labels, has_labels, feat_type, image_of, n_images,
                               bank_rows, packed_counts)
         if answers is not None:
@@ -649,6 +697,8 @@ class RAU:
             self.set_regions(regions, slot=slot)
         if att_targets is not None:
             self.set_att_targets(att_targets, slot=slot)
+        if sample_w is not None:
+            self.set_sample_weights(sample_w, slot=slot)
 
     def _set_batch_async(self, slot, feats, tokens, lens, labels, has_labels, feat_type, image_of, n_images,
                          bank_rows, packed_counts=None):
@@ -909,14 +959,15 @@ class RAU:
         return device_view(p.value, n * Q, self.cfg.device_id).view(n, Q)
 
     def set_batch_dev(self, feats_cuda, tokens, lens, labels=None, answers=None, regions=None, att_targets=None,
-                      image_of=None, question=None):
+                      image_of=None, question=None, sample_w=None):
         """set_batch with the maps already on the device: feats_cuda a contiguous float32 CUDA torch tensor
         [n,D,S] on the ctx's device (rau_set_batch_dev: one copy on the ctx's stream, no host synchronisation).
         The ctx's stream must be ordered behind the stream that wrote the tensor (autograd.step's docstring shows
         the two lines); the tensor must stay unchanged until that copy has run.  answers, regions, att_targets as
         in set_batch.  image_of [n] (0-based rows): feats_cuda is an image TABLE [N,D,S] (rau_set_batch_dev_images);
         regions may then be per image [N].  question: a CUDA tensor [n,Q] attached behind the upload (set_question);
-        tokens / lens may then be None -- the step does not read them, and id 1 with length 1 is uploaded."""
+        tokens / lens may then be None -- the step does not read them, and id 1 with length 1 is uploaded.
+        sample_w [n]: set_sample_weights behind the upload."""
         import torch
         c = self.cfg
         if question is not None and (tokens is None or lens is None):
@@ -950,6 +1001,8 @@ class RAU:
             regions = self._sample_regions(regions, image_of, B)
         if att_targets is not None:
             att_targets = self._att_targets(att_targets, B)
+        if sample_w is not None:
+            sample_w = self._sample_weights(sample_w, B)
         if B != self._n:
             self.set_batch_size(B)
         if image_of is not None:
@@ -963,6 +1016,8 @@ class RAU:
             self.set_regions(regions)
         if att_targets is not None:
             self.set_att_targets(att_targets)
+        if sample_w is not None:
+            self.set_sample_weights(sample_w)
         if question is not None:
             self.set_question(question)
 
@@ -1041,6 +1096,11 @@ class RAU:
 
     def losses(self):
         return self._out(self._lib.rau_get_losses, (self.cfg.H,))
+
+    def loss_rows(self):
+        """The per-sample loss rows [H, n] of the last forward: losses() is their mean over n.  With sample weights
+        these are the weighted rows s_b * row."""
+        return self._out(self._lib.rau_get_loss_rows, (self.cfg.H, self._n))
 
     def argmax(self):
         return self._out(self._lib.rau_get_argmax, (self.cfg.H, self._n), np.int32)

@@ -182,8 +182,19 @@ def merge_criterion_backward(rau, logits, dopred, y, merge_w, d_logits):
     return d_logits
 
 
+def scale_rows(rau, x, s):
+    """x[r, :] *= s[r] in place (rau_dev_scale_rows): x a contiguous float32 CUDA tensor [rows] or [rows, cols], s
+    [rows] float32 on the same device.  How a module-level host weights a criterion gradient per sample."""
+    rows = int(x.shape[0])
+    cols = x.numel() // rows if rows else 1
+    if tuple(s.shape) != (rows,) or not x.is_contiguous():
+        raise ValueError("scale_rows: x contiguous [rows, ...], s [rows]")
+    L.check(rau._lib.rau_dev_scale_rows(rau._h, _p(x), rows, cols, cols, _p(s)))
+    return x
+
+
 def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None, merge_w=None,
-          loss="ce", answers=None):
+          loss="ce", answers=None, sample_w=None):
     """The tensor half of the reference's feval, loop for loop (SS:443-596), on the clones.
     select_w [H] (None: the reference's zero, SS:566): hop h's multimodal clone receives
     d_do_pred = joint.bce_grad(do_pred_h, argmax_h == y, select_w[h]), which trains the step-selection head.
@@ -201,17 +212,23 @@ def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=Non
     against answers = (ids [B,G] int32, w [B,G] float32); merge_w is refused with it (the merged rows' terms are
     cross-entropies) and select_w needs labels.  answers is read under "bce" only.
 
+    sample_w [B] float32 (None: every sample equal): per-sample loss weights.  Every criterion gradient formed here
+    -- d_logits of every hop (the merged rows' terms included), d_do_pred, d_attprob -- has its row b multiplied by
+    sample_w[b] (scale_rows) before it enters the clone's backward: the objective of the step path under
+    rau_set_sample_weights.  The returned losses are the criteria's own and stay unweighted.
+
     feats [B,D,S] float32, x [T,B] int32, x_len [B] int32, y [B] int32: CUDA tensors.
     Gradients accumulate into the ctx's flat buffers (zero them first).  Returns
     (losses[H], argmax[H,B] as torch tensors of 1-based ids).
     """
     ext = torch.cuda.ExternalStream(rau.stream(), device=feats.device)
     with torch.cuda.stream(ext):   # torch's glue ops join the ctx's own stream order
-        return _feval(rau, feats, x, x_len, y, hop_w, select_w, regions, att_w, att_targets, merge_w, loss, answers)
+        return _feval(rau, feats, x, x_len, y, hop_w, select_w, regions, att_w, att_targets, merge_w, loss, answers,
+                      sample_w)
 
 
 def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None, merge_w=None,
-           loss="ce", answer_set=None):
+           loss="ce", answer_set=None, sample_w=None):
     if loss not in ("ce", "bce"):
         raise ValueError(f"feval: loss={loss!r}: 'ce' or 'bce'")
     if rau.cfg.K % 4:   # the clones exchange dense [B,K] rows: refused here, before the encoder loop launches anything
@@ -226,6 +243,11 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=No
         raise ValueError("feval: a non-zero att_w needs att_targets")
     c = rau.cfg
     dev = feats.device
+    sw = None
+    if sample_w is not None:
+        sw = torch.as_tensor(sample_w, dtype=torch.float32, device=dev).contiguous()
+        if tuple(sw.shape) != (rau.batch_size,):
+            raise ValueError(f"feval: sample_w must be [{rau.batch_size}], one per sample")
     emb = [EmbedClone(rau, t) for t in range(c.T)]
     rnn = [DeepLSTMClone(rau, t) for t in range(c.T)]
     mm = [MultimodalClone(rau, h) for h in range(c.H)]
@@ -268,13 +290,19 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=No
             dl = bcrit[h].backward(logits[h], y, answer_set, float(hop_w[h]))
         else:
             dl = crit[h].backward(logits[h], y, float(hop_w[h])) if d_merged is None else d_merged[h]   # SS:565-569
+        if sw is not None:
+            dl = scale_rows(rau, dl, sw)
         d_dp = None                                        # d_do_pred:mul(0), SS:566
         if select_w is not None and float(select_w[h]) != 0.0:
             gt = (answers[h] == y).to(torch.float32)       # do_pred_gt, SS:490, 497
             d_dp = bce_grad(dopred[h], gt, float(select_w[h])).contiguous()   # SS:565, times the weight
+            if sw is not None:
+                d_dp = scale_rows(rau, d_dp, sw)
         d_a = None                                         # gradattprob zeros, SS:361, 573
         if att_w is not None and float(att_w[h]) != 0.0:
             d_a = acrit[h].backward(att[h], att_targets, regions, float(att_w[h]))
+            if sw is not None:
+                d_a = scale_rows(rau, d_a, sw)
         dq_h, _dX, d_c, d_h = mm[h].backward(rnn_out, feats, att_c[h], att_h[h], dl, d_dp, d_a,
                                               d_c, d_h)
         d_q += dq_h                                        # ConcatTable backward, SS:579

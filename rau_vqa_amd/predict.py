@@ -235,11 +235,13 @@ def set_correct(ans, ids, score):
     return ok
 
 
-def set_stats(logits, dopred, ids, w, score=None, loss="ce"):
+def set_stats(logits, dopred, ids, w, score=None, loss="ce", sample_w=None):
     """joint.feval_stats for a batch with an answer set (rau_step_stats with a set): the same keys, with
     set_correct in place of (argmax == y) and soft_ce in place of the cross-entropy, plus ``score`` [H+2, B]:
     answer_score of every row's answer (what rau_step_scores returns).  loss="bce": the statistics of a step under
-    RAU_LOSS_BCE -- ``loss`` is soft_bce of every row; everything else does not depend on the criterion."""
+    RAU_LOSS_BCE -- ``loss`` is soft_bce of every row; everything else does not depend on the criterion.
+    sample_w [B] (rau_set_sample_weights): every loss is the mean of s_b * row (each product rounded once in
+    float32); the counts and the scores stay unweighted."""
     if loss not in ("ce", "bce"):
         raise ValueError(f"loss={loss!r}: 'ce' or 'bce'")
     row_loss = soft_bce if loss == "bce" else soft_ce
@@ -262,13 +264,19 @@ def set_stats(logits, dopred, ids, w, score=None, loss="ce"):
     ans = np.stack([first_max(r) for r in rows])
     ok = set_correct(ans, ids, score)
     did = ok[:H].any(0)
-    loss = np.array([row_loss(r, ids, w)[1] for r in rows], np.float32)
+    sw = None if sample_w is None else np.asarray(sample_w, np.float32)
+
+    def mean(r):   # (1/B) sum_b s_b r_b
+        r = r if sw is None else (sw * r).astype(np.float32)
+        return np.float32(r.sum(dtype=np.float32) / np.float32(B))
+    loss = np.array([row_loss(r, ids, w)[1] if sw is None else mean(row_loss(r, ids, w)[0]) for r in rows],
+                    np.float32)
     ldp, dpc = [], []
     for h in range(H):
         t = ok[h].astype(np.float32)
         x = dopred[h]
         term = -(t * np.log(x + eps) + (one - t) * np.log(one - x + eps))
-        ldp.append(np.float32(term.sum(dtype=np.float32) / np.float32(B)))
+        ldp.append(mean(term))
         dpc.append(int(((fire[h] == ok[h]) & did).sum()))
     return {"loss": loss, "loss_do_pred": np.array(ldp, np.float32), "correct": ok.sum(1).astype(np.int32),
             "do_pred_correct": np.array(dpc, np.int32), "did_correct": int(did.sum()),
