@@ -217,6 +217,20 @@ void rau_update_opts_default(rau_update_opts* o);
 int rau_update(rau_ctx* ctx, int64_t step_t, const rau_update_opts* o, float* out_norms);
 int rau_get_opt_state(rau_ctx* ctx, int group, float* m, float* v, int64_t* t, int32_t* rule);
 int rau_set_opt_state(rau_ctx* ctx, int group, const float* m, const float* v, int64_t t, int32_t rule);
+typedef struct rau_update_extras {
+  float weight_decay;
+  float ema_decay;
+} rau_update_extras;
+void rau_update_extras_default(rau_update_extras* e);
+int rau_update_ex(rau_ctx* ctx, int64_t step_t, const rau_update_opts* o, const rau_update_extras* e,
+                  float* out_norms);
+int rau_set_layer_opts(rau_ctx* ctx, int group, int index, float lr_scale, float decay_weight, float decay_bias);
+int rau_get_layer_opts(rau_ctx* ctx, int group, int index, float* lr_scale, float* decay_weight, float* decay_bias);
+int rau_ema_reset(rau_ctx* ctx);
+int rau_ema_swap(rau_ctx* ctx);
+int rau_ema_state(rau_ctx* ctx, int* has, int* swapped);
+int rau_get_ema(rau_ctx* ctx, int group, float* host, size_t n);
+int rau_set_ema(rau_ctx* ctx, int group, const float* host, size_t n);
 int rau_stream(rau_ctx* ctx, void** hip_stream);
 int rau_wait_grads(rau_ctx* ctx, int group, void* hip_stream);
 int rau_comm_unique_id(void* id, size_t bytes);
@@ -733,6 +747,44 @@ function RAU:updateWith(opts)
   local norms = ffi.new('float[4]')
   check(C.rau_update(self.h, opts.step_t or 0, o, norms))
   return norms[0], norms[1], norms[2], norms[3]
+end
+
+-- rau:updateWith's step with decoupled weight decay, per-layer options and the weight average (rau_update_ex): the
+-- fields of rau:updateWith plus weight_decay = (AdamW's order, under 'adamax' too) and ema_decay = (needs
+-- rau:emaReset() first).  Frozen layers are in none of the four norms returned.
+function RAU:updateEx(opts)
+  local o = ffi.new('rau_update_opts[1]')
+  C.rau_update_opts_default(o)
+  if opts.rule then o[0].rule = assert(RULE[opts.rule], 'updateEx: unknown rule') end
+  if opts.clip_scope then o[0].clip_scope = assert(SCOPE[opts.clip_scope], 'updateEx: unknown clip_scope') end
+  for _, k in ipairs({ 'lr', 'mult_lr', 'beta1', 'beta2', 'eps', 'eta', 'gamma', 'clip' }) do
+    if opts[k] then o[0][k] = opts[k] end
+  end
+  if opts.seed then o[0].noise_seed = opts.seed end
+  local x = ffi.new('rau_update_extras[1]')
+  C.rau_update_extras_default(x)
+  if opts.weight_decay then x[0].weight_decay = opts.weight_decay end
+  if opts.ema_decay then x[0].ema_decay = opts.ema_decay end
+  local norms = ffi.new('float[4]')
+  check(C.rau_update_ex(self.h, opts.step_t or 0, o, x, norms))
+  return norms[0], norms[1], norms[2], norms[3]
+end
+-- one layer's options: group 'embed' | 'rnn' | 'mult', index = the layer's 0-based place in its group (its weight
+-- and bias are entries 2 index and 2 index + 1 of the layout); nil keeps the value.  lr_scale = 0 freezes the layer.
+function RAU:setLayerOpts(group, index, lr_scale, decay_weight, decay_bias)
+  local v = ffi.new('float[3]')
+  check(C.rau_get_layer_opts(self.h, GROUP[group], index, v, v + 1, v + 2))
+  check(C.rau_set_layer_opts(self.h, GROUP[group], index, lr_scale or v[0], decay_weight or v[1],
+                             decay_bias or v[2]))
+end
+-- the weight average: emaReset() starts it at the current weights; emaSwap() exchanges weights and average in
+-- place (evaluate, then swap back: every update is refused while swapped) and returns the new `swapped` flag
+function RAU:emaReset() check(C.rau_ema_reset(self.h)) end
+function RAU:emaSwap()
+  check(C.rau_ema_swap(self.h))
+  local sw = ffi.new('int[1]')
+  check(C.rau_ema_state(self.h, nil, sw))
+  return sw[0] == 1
 end
 
 -- optimizer state of one group: m, v (FloatTensors of the group's length, filled; v holds the u of adamax),

@@ -1171,6 +1171,73 @@ int rau_update(rau_ctx* ctx, int64_t step_t, const rau_update_opts* o, float* ou
 int rau_get_opt_state(rau_ctx* ctx, int group, float* m, float* v, int64_t* t, int32_t* rule);
 int rau_set_opt_state(rau_ctx* ctx, int group, const float* m, const float* v, int64_t t, int32_t rule);
 
+/* ---- update with decoupled weight decay, per-layer step sizes and a weight average ---------------
+ * rau_update_ex is rau_update with three more choices (none is in the reference).  rau_update_opts is unchanged and
+ * means what it means to rau_update: the noise generator, keys and counters, the norms, the clip, the rule-ownership
+ * rule of the optimizer state and the validation of `o` are rau_update's.  With `e` at its defaults (NULL counts as
+ * defaults) and every layer at its defaults, rau_update_ex gives rau_update's bits in weights, gradients, moments and
+ * all four norms, in both rules and scopes, with and without noise.  Two launches (update.hip), under the names
+ * upd_ex_sqnorm and upd_ex_apply in rau_prof_entry; no atomics, no cooperative launch.  Synchronising only with
+ * out_norms.
+ *
+ * Layers and segments.  A LAYER is one named unit of a parameter group: unit i of RNN and MULT is rau_layout_entry's
+ * entries 2i ("<name>.weight", [out,in]) and 2i + 1 ("<name>.bias", [out]); EMBED has the one unit 0,
+ * word_embed.weight, with no bias.  That is 1 + 4 + 13 units.  `index` below is the unit's index i.  A SEGMENT is the
+ * weight part or the bias part of one unit: at most 1, 8 and 26 per group.  Segment ends are not multiples of 4 and a
+ * bias can be one element; every coefficient below is per ELEMENT, by the segment the element lies in.
+ *   rau_set_layer_opts  lr_scale (default 1), decay_weight (default 1), decay_bias (default 0) of one unit; kept in
+ *                       the context until set again, through rau_set_batch_size as well.  lr_scale or a decay
+ *                       multiplier negative or non-finite, a bad group or index: RAU_ERR_INVALID, nothing changed.
+ *                       rau_update and rau_noise_clip_adam do not look at layer options.
+ *   step size           a segment's step size is its group's with lr_scale multiplied in, formed on the host in
+ *                       double like rau_update's: (float)(group_lr * lr_scale * sqrt(1 - beta2^t) / (1 - beta1^t)) for
+ *                       RAU_OPT_ADAM, (float)(group_lr * lr_scale / (1 - beta1^t)) for RAU_OPT_ADAMAX.
+ *   frozen              lr_scale == 0 freezes the unit: the x, m, v, average AND gradient of its elements keep their
+ *                       bits (no noise, no clip write-back), and its elements add nothing to any norm in out_norms,
+ *                       group or global -- a frozen layer is not part of the model being clipped, as in torch where
+ *                       it has no .grad.  Its noise counters are simply not drawn; every other element's noise is what
+ *                       it would be with nothing frozen.  The backward still forms its gradient.
+ *   weight_decay        decoupled, torch.optim.AdamW's order: first x = x f (one rounded product) with
+ *                       f = (float)(1 - group_lr * lr_scale * weight_decay * decay_weight) for a weight segment and
+ *                       decay_bias in decay_weight's place for a bias segment, formed on the host in double; then the
+ *                       rule runs on the decayed x.  A segment whose f is exactly 1 skips the multiplication.  It is
+ *                       this decoupled form under RAU_OPT_ADAMAX too, NOT torch.optim.Adamax's L2 term (which adds
+ *                       weight_decay x to the gradient).  The decay enters neither the gradient, nor the moments, nor
+ *                       the norms.  weight_decay < 0 or non-finite: RAU_ERR_INVALID.
+ *   ema_decay = d       in [0, 1), else RAU_ERR_INVALID.  d > 0: after the rule, on the new x, e = (d e) + ((1-d) x)
+ *                       with both products and the sum rounded and 1-d formed once on the host in float; frozen
+ *                       segments are skipped.  d == 0: the average is neither read nor written.  d > 0 without an
+ *                       average (rau_ema_reset / rau_set_ema): RAU_ERR_STATE.
+ * The average.  One more vector per group, of the group's length; it survives rau_set_batch_size like the optimizer
+ * state.
+ *   rau_ema_reset       average := current weights, all three groups (allocated at the first use; RAU_ERR_NOMEM).
+ *   rau_set_ema / rau_get_ema   one group's average from / to the host, n = the group's length (else
+ *                       RAU_ERR_INVALID); both synchronise, as rau_set_params does.  rau_set_ema allocates like
+ *                       rau_ema_reset: when there was no average, all three start as the current weights and this
+ *                       group's is then replaced.  rau_get_ema without an average: RAU_ERR_STATE.
+ *   rau_ema_swap        exchanges weights and average in place: one launch over the three groups, no allocation;
+ *                       RAU_ERR_STATE without an average.  It toggles `swapped`.  While swapped, rau_get_params, the
+ *                       forward, the statistics and snapshots see the averaged weights, and rau_get_ema the trained
+ *                       ones; rau_noise_clip_adam, rau_update and rau_update_ex return RAU_ERR_STATE with nothing
+ *                       launched, and so do rau_ema_reset and rau_set_ema.  Two swaps restore every bit.
+ *   rau_ema_state       has = 0 | 1 (an average exists), swapped = 0 | 1; either output may be NULL.
+ * In every error case nothing is launched and nothing changes. */
+typedef struct rau_update_extras {
+  float weight_decay;
+  float ema_decay;
+} rau_update_extras;
+/* 0, 0 */
+void rau_update_extras_default(rau_update_extras* e);
+int rau_update_ex(rau_ctx* ctx, int64_t step_t, const rau_update_opts* o, const rau_update_extras* e,
+                  float* out_norms);
+int rau_set_layer_opts(rau_ctx* ctx, int group, int index, float lr_scale, float decay_weight, float decay_bias);
+int rau_get_layer_opts(rau_ctx* ctx, int group, int index, float* lr_scale, float* decay_weight, float* decay_bias);
+int rau_ema_reset(rau_ctx* ctx);
+int rau_ema_swap(rau_ctx* ctx);
+int rau_ema_state(rau_ctx* ctx, int* has, int* swapped);
+int rau_get_ema(rau_ctx* ctx, int group, float* host, size_t n);
+int rau_set_ema(rau_ctx* ctx, int group, const float* host, size_t n);
+
 /* ---- data-parallel exchange (new: the reference is single-GPU) --------------------
  * One process and one rau_ctx per GPU.  Rank 0 obtains a communicator id and hands it to
  * the other ranks by any host channel (file, socket, MPI, torch.distributed); every rank

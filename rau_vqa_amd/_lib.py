@@ -48,6 +48,11 @@ class RauUpdateOpts(C.Structure):
                [("noise_seed", C.c_uint64)]
 
 
+class RauUpdateExtras(C.Structure):
+    """Mirror of ``rau_update_extras`` (include/rau.h): what rau_update_ex takes beside rau_update_opts."""
+    _fields_ = [("weight_decay", C.c_float), ("ema_decay", C.c_float)]
+
+
 class RauOutGrads(C.Structure):
     """Mirror of ``rau_out_grads`` (include/rau.h): device pointers, None = no such term."""
     _fields_ = [(n, C.c_void_p) for n in ("d_logits", "d_dopred", "d_attprob")]
@@ -258,6 +263,17 @@ _SIGS = {
     "rau_get_opt_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
                                     C.POINTER(C.c_int32)]),
     "rau_set_opt_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    # decoupled weight decay, per-layer options, the weight average
+    "rau_update_extras_default": (None, [C.POINTER(RauUpdateExtras)]),
+    "rau_update_ex": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(RauUpdateOpts), C.POINTER(RauUpdateExtras),
+                                C.c_void_p]),
+    "rau_set_layer_opts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]),
+    "rau_get_layer_opts": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 3),
+    "rau_ema_reset": (C.c_int, [C.c_void_p]),
+    "rau_ema_swap": (C.c_int, [C.c_void_p]),
+    "rau_ema_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rau_get_ema": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "rau_set_ema": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "rau_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_wait_grads": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "rau_comm_unique_id": (C.c_int, [C.c_void_p, C.c_size_t]),

@@ -575,6 +575,26 @@ struct UpdGroups {
 hipError_t upd_noise_sqnorm(hipStream_t st, const UpdGroups& G, float nstd, float* partial /* [3][kUpdParts] */);
 hipError_t upd_apply(hipStream_t st, const UpdGroups& G, int rule /* rau_opt_rule */, bool global_clip, float clip,
                      float beta1, float beta2, float eps, const float* partial, float* norms /* [4] */);
+// rau_update_ex's two launches (update.hip): the same passes with a segment table.  A segment is the weight or the
+// bias part of one layout entry; the segments of group g are first[g] .. first[g+1]-1, `end` is a segment's end offset
+// in its group (the last one's is the group's n; ends are NOT multiples of 4), `step` its step size, `f` its decay
+// factor (1: none), `frozen` != 0: its elements are neither read into a norm nor written.  The sums' element order,
+// the partials and the finish are upd_noise_sqnorm's / upd_apply's; UpdGroups::step is not read.  ema[g] (all three
+// or none) is the weight average, updated after the rule with decay d and omd = 1 - d.
+constexpr int kUpdSegs = 36;       // 1 + 8 + 26 segments, padded
+constexpr int kUpdGroupSegs = 26;  // the most one group has
+struct UpdSegs {
+  size_t end[kUpdSegs];
+  float step[kUpdSegs], f[kUpdSegs];
+  uint32_t frozen[kUpdSegs];
+  int first[4];
+};
+hipError_t upd_ex_sqnorm(hipStream_t st, const UpdGroups& G, const UpdSegs& T, float nstd, float* partial);
+hipError_t upd_ex_apply(hipStream_t st, const UpdGroups& G, const UpdSegs& T, int rule, bool global_clip, float clip,
+                        float beta1, float beta2, float eps, float* const ema[3] /* or null */, float d, float omd,
+                        const float* partial, float* norms /* [4] */);
+// x[g] <-> e[g] for the three groups in one launch (rau_ema_swap): 16-byte accesses where both pointers allow
+hipError_t ema_swap(hipStream_t st, float* const x[3], float* const e[3], const size_t n[3]);
 // Adamax on one flat vector (rau_dev_adamax): adamax_elem on dx as it stands; any n, any 4-byte-aligned pointers
 hipError_t adamax_vec(hipStream_t st, size_t n, float* x, const float* dx, float* m, float* u, float stepsize,
                       float beta1, float beta2, float eps);

@@ -51,6 +51,9 @@ struct Entry {
   size_t off;
   int rows, cols;
 };
+struct LayerOpt {   // rau_set_layer_opts
+  float lr_scale = 1.f, decay_w = 1.f, decay_b = 0.f;
+};
 struct Group {
   float* w = nullptr;
   float* g = nullptr;
@@ -60,6 +63,8 @@ struct Group {
   int64_t adam_t = 0;  // updates so far, of either rule
   int opt_rule = RAU_OPT_ADAM;   // the rule that owns m, v, adam_t: the other one is refused while adam_t > 0
   std::vector<Entry> layout;
+  float* ema = nullptr;          // the weight average (rau_ema_reset / rau_set_ema allocate all three groups')
+  std::vector<LayerOpt> lopt;    // per unit (weight + bias of one named layer); empty = every unit at its defaults
 };
 struct ProfRec {
   int cls;
@@ -454,6 +459,7 @@ struct rau_ctx {
   // update
   float *npart = nullptr, *norms_d = nullptr;
   float* upd_part = nullptr;     // rau_update's partial sums of squares, [3][kUpdParts]
+  bool ema_swapped = false;      // rau_ema_swap: the weights' buffers hold the average and the other way round
   FwdRecord fwd;                 // what the last step-level forward left for its backward
   BwdRecord bwd;                 // what the last step-level backward left for the getters
   // timing

@@ -2423,6 +2423,9 @@ int rau_noise_clip_adam(rau_ctx* ctx, int64_t step_t, float lr, float mult_lr, f
                         uint64_t noise_seed, float* out_norms) {
   NEED(ctx, "null ctx");
   NEED(step_t >= 0 && gamma > 0.f && eta >= 0.f && clip > 0.f, "bad update hyper-parameters");
+  if (ctx->ema_swapped)   // reachable only through rau_ema_swap
+    return fail(RAU_ERR_STATE, "rau_noise_clip_adam: the weights are swapped with their average (rau_ema_swap); "
+                "swap back first");
   for (int gi = 0; gi < 3; ++gi)   // the state belongs to the rule that last wrote it (rau_update)
     if (ctx->grp[gi].adam_t > 0 && ctx->grp[gi].opt_rule != RAU_OPT_ADAM)
       return fail(RAU_ERR_STATE, "rau_noise_clip_adam: group %d holds Adamax state (t = %lld); reset it with "

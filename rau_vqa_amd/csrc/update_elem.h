@@ -6,7 +6,9 @@
 // itself instead of leaving it to the compiler's contraction pass:
 //   noise   v = fma(nstd, z, g), acc = fma(v, v, acc)            (fused)
 //   Adam    m = (m b1) + ((1-b1) g), v = (v b2) + (((1-b2) g) g)  (every product and sum rounded)
-// These are the roundings the kernels had before this file existed.
+//   decay   x = x f                                               (rau_update_ex; skipped when f == 1)
+//   average e = (d e) + ((1-d) x)                                 (rau_update_ex; every product and the sum rounded)
+// The first two are the roundings the kernels had before this file existed.
 #pragma once
 #include "common.h"
 #include "philox.h"
@@ -63,6 +65,18 @@ __device__ __forceinline__ void adamax_elem(float gi, float& m, float& u, float&
   m = mi;
   u = ui;
   x = x - stepsize * mi / ui;
+}
+// Decoupled weight decay (rau_update_ex), BEFORE the rule's step as in torch.optim.AdamW: x = x f, one rounded
+// product; f = (float)(1 - group_lr lr_scale weight_decay decay) comes from the host's double.  f == 1: x keeps
+// its bits without a multiplication
+__device__ __forceinline__ void decay_elem(float& x, float f) {
+  if (f != 1.f) x = x * f;
+}
+// The weight average (rau_update_ex), AFTER the rule's step, on the new x: e = (d e) + ((1-d) x), both products and
+// the sum rounded; omd = 1 - d is formed once on the host in float
+__device__ __forceinline__ void ema_elem(float& e, float x, float d, float omd) {
+#pragma clang fp contract(off)
+  e = d * e + omd * x;
 }
 
 }  // namespace rau

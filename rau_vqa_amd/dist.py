@@ -122,7 +122,9 @@ def reduced_update(rau, allreduce, step_t, **update_args):
     """The data-parallel update: `allreduce()` (a GradAllReduce or NativeGradAllReduce of `rau`, or None on a
     single rank) and then RAU.update with the SAME arguments on every rank -- rule, clip_scope and noise_seed
     included, so every rank computes the identical norms (the global one too: it is taken over the reduced
-    gradients) and the identical step.  Returns RAU.update's norms."""
+    gradients) and the identical step.  The keywords are forwarded as they are, weight_decay and ema_decay
+    included; layer options (RAU.set_layer_opts, freeze) and the weight average live in each rank's context and are
+    not exchanged, so they must be set identically on every rank.  Returns RAU.update's norms."""
     if allreduce is not None:
         allreduce()
     return rau.update(step_t, **update_args)

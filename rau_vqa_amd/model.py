@@ -8,7 +8,9 @@ All arithmetic happens in librau.so; this file only moves pointers.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import fnmatch
 from dataclasses import dataclass
 
 import numpy as np
@@ -85,6 +87,35 @@ def hop_weights(variant: str, H: int, epoch: int = 0):
         if epoch >= stop:
             w[h] = 0.0
     return w
+
+
+LAYER_DEFAULTS = (1.0, 1.0, 0.0)      # lr_scale, decay, bias_decay of rau_set_layer_opts
+
+
+def layer_units(layouts):
+    """{group: [(entry name, ...)]} as RAU.layout gives it -> [(layer name, group, index)]: unit i of a group is its
+    entries 2i ("<name>.weight") and 2i + 1 ("<name>.bias"); word_embed has the weight only."""
+    out = []
+    for g in L.GROUPS:
+        names = [e[0] for e in layouts[g]]
+        for i in range(0, len(names), 2):
+            pair = names[i:i + 2]
+            base = pair[0][:-len(".weight")]
+            if pair != [base + ".weight", base + ".bias"][:len(pair)]:
+                raise ValueError(f"layout of {g}: {pair} is not a weight and its bias")
+            out.append((base, g, i // 2))
+    return out
+
+
+def match_layers(name_or_glob, units):
+    """The units a name or an fnmatch pattern addresses: an exact name first (also with the .weight / .bias of one
+    of its entries), else every unit the pattern matches.  Nothing matched: KeyError."""
+    key = str(name_or_glob)
+    exact = {key} | {key[:-len(s)] for s in (".weight", ".bias") if key.endswith(s)}
+    hit = [u for u in units if u[0] in exact] or [u for u in units if fnmatch.fnmatchcase(u[0], key)]
+    if not hit:
+        raise KeyError(f"no layer matches {key!r}; layers: {[u[0] for u in units]}")
+    return hit
 
 
 class RAU:
@@ -188,19 +219,22 @@ class RAU:
             L.check(self._lib.rau_set_grads(self._h, L.GROUPS[g], a.ctypes.data, a.size))
 
     # ---- snapshots (torch.save / torch.load of SS:1188-1197, Eval.lua:113-114,344-347)
-    def save_snapshot(self, path, it, epoch, opt, cuda=True, optim=False):
+    def save_snapshot(self, path, it, epoch, opt, cuda=True, optim=False, ema=False):
         """optim=True adds the optimizer state (opt_state) as one more field, so a run resumed from the file goes
-        on with its moments and step counts; a Torch7 reader of the reference ignores the field."""
+        on with its moments and step counts; ema=True adds the weight average (ema) as another, next to it.  A
+        Torch7 reader of the reference ignores both fields.  While the weights are swapped with their average
+        (ema_swap, averaged) `params` holds the averaged weights and `ema` the trained ones."""
         from . import t7
         self.sync()
         t7.save_snapshot(path, self.get_params(), it, epoch, opt, cuda=cuda,
-                         optim=self.opt_state() if optim else None)
+                         optim=self.opt_state() if optim else None, ema=self.ema() if ema else None)
 
     def load_snapshot(self, path):
         """embed_param:copy(snap.params[1]) ...; returns (it, epoch, opt).  A snapshot that carries the optimizer
-        state restores it as well; one without leaves the context's state as it is."""
+        state restores it as well, and so with the weight average; one without leaves the context's as it is."""
         from . import t7
         it, epoch, opt, params = t7.load_snapshot(path)
+        ema = t7.load_ema(path)
         for g, a in params.items():
             if a.size != self.group_size(g):
                 raise ValueError(f"snapshot group {g} has {a.size} floats, model has "
@@ -209,6 +243,8 @@ class RAU:
         self.set_params(params)
         if optim is not None:
             self.set_opt_state(*optim)
+        if ema is not None:
+            self.set_ema(ema)
         return it, epoch, opt
 
     def init_uniform(self, seed=123, lo=-0.08, hi=0.08):
@@ -1031,16 +1067,20 @@ class RAU:
         L.check(self._lib.rau_sync(self._h))
 
     def update(self, step_t, lr=3e-3, mult_lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-8,
-               eta=0.01, gamma=0.55, clip=0.1, noise_seed=0, rule="adam", clip_scope="group"):
+               eta=0.01, gamma=0.55, clip=0.1, noise_seed=0, rule="adam", clip_scope="group",
+               weight_decay=0.0, ema_decay=0.0):
         """Noise, clip and the optimizer step.  With rule and clip_scope at their defaults this is the reference's
         update (rau_noise_clip_adam) and returns the three groups' pre-clip norms.  rule="adamax" and / or
         clip_scope="global" (neither is in the reference) go through rau_update and return four norms: the groups'
-        and the global one."""
+        and the global one.  A non-zero weight_decay (decoupled, AdamW's order, under either rule) or ema_decay (the
+        weight average: ema_reset first), or any layer option off its default (set_layer_opts, freeze), goes through
+        rau_update_ex and returns four norms as well; frozen layers are in none of them."""
         if rule not in L.OPT_RULES:
             raise ValueError(f"update: rule {rule!r} is not one of {sorted(L.OPT_RULES)}")
         if clip_scope not in L.CLIP_SCOPES:
             raise ValueError(f"update: clip_scope {clip_scope!r} is not one of {sorted(L.CLIP_SCOPES)}")
-        if rule == "adam" and clip_scope == "group":
+        extras = weight_decay != 0 or ema_decay != 0 or bool(getattr(self, "_layer_custom", None))
+        if rule == "adam" and clip_scope == "group" and not extras:
             norms = np.zeros(3, np.float32)
             L.check(self._lib.rau_noise_clip_adam(self._h, step_t, lr, mult_lr, beta1, beta2, eps,
                                                   eta, gamma, clip, noise_seed, norms.ctypes.data))
@@ -1049,8 +1089,93 @@ class RAU:
                             beta1=beta1, beta2=beta2, eps=eps, eta=eta, gamma=gamma, clip=clip,
                             noise_seed=noise_seed)
         norms = np.zeros(4, np.float32)
+        if extras:
+            x = L.RauUpdateExtras(weight_decay=weight_decay, ema_decay=ema_decay)
+            L.check(self._lib.rau_update_ex(self._h, step_t, C.byref(o), C.byref(x), norms.ctypes.data))
+            return norms
         L.check(self._lib.rau_update(self._h, step_t, C.byref(o), norms.ctypes.data))
         return norms
+
+    # ---- per-layer options (rau_set_layer_opts): a layer is a named unit, weight and bias, of the layout
+    def layers(self):
+        """[(name, group, index)]: the units rau_set_layer_opts addresses, in layout order."""
+        if getattr(self, "_layers", None) is None:
+            self._layers = layer_units({g: self.layout(g) for g in L.GROUPS})
+        return self._layers
+
+    def set_layer_opts(self, name_or_glob, lr_scale=None, decay=None, bias_decay=None):
+        """Step-size scale, weight-decay multiplier of the weight and of the bias (defaults 1, 1, 0) of the layer
+        named, or of every layer an fnmatch pattern such as "classifier.*" matches; what is None keeps its value.
+        lr_scale = 0 freezes.  Returns the names changed; a name or pattern that matches nothing is a KeyError.
+        Only updates with these options in force (RAU.update routes them to rau_update_ex) look at them."""
+        hit = match_layers(name_or_glob, self.layers())
+        for name, g, i in hit:
+            cur = self._layer_get(g, i)
+            new = tuple(float(c if v is None else v) for c, v in zip(cur, (lr_scale, decay, bias_decay)))
+            L.check(self._lib.rau_set_layer_opts(self._h, L.GROUPS[g], i, *new))
+            if getattr(self, "_layer_custom", None) is None:
+                self._layer_custom = set()
+            (self._layer_custom.discard if new == LAYER_DEFAULTS else self._layer_custom.add)(name)
+        return [name for name, _, _ in hit]
+
+    def _layer_get(self, group, index):
+        v = [C.c_float(), C.c_float(), C.c_float()]
+        L.check(self._lib.rau_get_layer_opts(self._h, L.GROUPS[group], index, *(C.byref(x) for x in v)))
+        return tuple(float(x.value) for x in v)
+
+    def layer_opts(self):
+        """{name: (lr_scale, decay, bias_decay)} of every layer."""
+        return {name: self._layer_get(g, i) for name, g, i in self.layers()}
+
+    def freeze(self, *names):
+        """lr_scale = 0: the layers' weights, moments, average and gradients keep their bits, and they are in no
+        norm.  The backward still forms their gradients."""
+        return [n for p in names for n in self.set_layer_opts(p, lr_scale=0.0)]
+
+    def unfreeze(self, *names):
+        """lr_scale back to 1 (for another scale use set_layer_opts)."""
+        return [n for p in names for n in self.set_layer_opts(p, lr_scale=1.0)]
+
+    # ---- the weight average (rau_ema_*): updated by update(ema_decay=...), swapped in for evaluation
+    def ema_reset(self):
+        """average := current weights (allocated at the first use)."""
+        L.check(self._lib.rau_ema_reset(self._h))
+
+    def ema_swap(self):
+        """Exchange weights and average in place, one launch.  While swapped every reader of the weights sees the
+        average and every update is refused; a second swap restores every bit."""
+        L.check(self._lib.rau_ema_swap(self._h))
+
+    def _ema_state(self):
+        has, sw = C.c_int(), C.c_int()
+        L.check(self._lib.rau_ema_state(self._h, C.byref(has), C.byref(sw)))
+        return bool(has.value), bool(sw.value)
+
+    @property
+    def has_ema(self) -> bool:
+        return self._ema_state()[0]
+
+    @property
+    def ema_swapped(self) -> bool:
+        return self._ema_state()[1]
+
+    def ema(self):
+        """{group: float32 vector}: the average (while swapped: the trained weights)."""
+        return {g: self._get(self._lib.rau_get_ema, g) for g in L.GROUPS}
+
+    def set_ema(self, ema):
+        for g, a in ema.items():
+            a = np.ascontiguousarray(a, np.float32)
+            L.check(self._lib.rau_set_ema(self._h, L.GROUPS[g], a.ctypes.data, a.size))
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """with m.averaged(): ... runs its body on the averaged weights and swaps back on the way out."""
+        self.ema_swap()
+        try:
+            yield self
+        finally:
+            self.ema_swap()
 
     # ---- optimizer state (rau_get_opt_state / rau_set_opt_state): what a resumed run needs besides the parameters
     def opt_state(self):

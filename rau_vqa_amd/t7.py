@@ -261,7 +261,7 @@ def save(path, obj):
 GROUPS = ("embed", "rnn", "mult")     # checkpoint.params[1..3], SS:1196
 
 
-def save_snapshot(path, params, it, epoch, opt, cuda=True, optim=None):
+def save_snapshot(path, params, it, epoch, opt, cuda=True, optim=None, ema=None):
     """`torch.save(savefile, {it=, opt=, epoch=, params=})` of SS:1188-1197.
 
     params: {"embed","rnn","mult"} -> flat float32 vectors in THIS library's layout
@@ -271,6 +271,9 @@ def save_snapshot(path, params, it, epoch, opt, cuda=True, optim=None):
     optim: None (the reference's table, nothing added), or ({group: (m, v, t)}, rule) as RAU.opt_state
     returns it: one more field beside `params`, `optim = {rule=, state={[1..3]={m=, v=, t=}}}`, which the
     reference's readers never index (load_optim reads it back).
+
+    ema: None, or {group: flat float32 vector} as RAU.ema returns it, the weight average: one more field next to
+    `optim`, `ema = {[1..3] = tensor}`, which the reference's readers never index either (load_ema reads it back).
     """
     cls = "torch.CudaTensor" if cuda else "torch.FloatTensor"
     ckpt = {"it": it, "opt": dict(opt), "epoch": epoch,
@@ -283,7 +286,25 @@ def save_snapshot(path, params, it, epoch, opt, cuda=True, optim=None):
                                            "v": Tensor(np.asarray(state[g][1], np.float32).ravel(), cls),
                                            "t": int(state[g][2])}
                                    for i, g in enumerate(GROUPS)}}
+    if ema is not None:
+        ckpt["ema"] = {i + 1: Tensor(np.asarray(ema[g], np.float32).ravel(), cls) for i, g in enumerate(GROUPS)}
     save(path, ckpt)
+
+
+def load_ema(path_or_snapshot):
+    """The weight average of a snapshot written with `ema`: {group: flat float32 vector}, or None when the snapshot
+    has none.  Takes a path or an already loaded snapshot table."""
+    snap = path_or_snapshot if isinstance(path_or_snapshot, dict) else load(path_or_snapshot)
+    if not isinstance(snap, dict) or "ema" not in snap:
+        return None
+    e = snap["ema"]
+    out = {}
+    for i, g in enumerate(GROUPS):
+        t = e.get(i + 1) if isinstance(e, dict) else None
+        if not isinstance(t, Tensor):
+            raise T7Error(f"snapshot ema[{i + 1}] is missing or not a tensor")
+        out[g] = np.ascontiguousarray(t.array, np.float32).ravel()
+    return out
 
 
 def load_optim(path_or_snapshot):
