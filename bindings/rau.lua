@@ -84,6 +84,8 @@ int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n);
 int rau_batch_regions(rau_ctx* ctx, int* has);
 int rau_set_sample_weights(rau_ctx* ctx, int slot, const float* s);
 int rau_batch_sample_weights(rau_ctx* ctx, int* has);
+int rau_set_candidates(rau_ctx* ctx, int slot, int32_t C, const int32_t* cand);
+int rau_batch_candidates(rau_ctx* ctx, int32_t* C);
 int rau_set_batch_packed(rau_ctx* ctx, const void* rows, int feat_type, int n_maps, const int32_t* counts,
                          const int32_t* image_of, const int32_t* tokens, const int32_t* lens,
                          const int32_t* labels);
@@ -159,6 +161,12 @@ int rau_criterion_forward_bce(rau_ctx* ctx, int h, const float* logits, const in
                               int32_t G, const int32_t* ids_dev, const float* w_dev, float* loss);
 int rau_criterion_backward_bce(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev,
                                int32_t G, const int32_t* ids_dev, const float* w_dev, float scale, float** d_logits);
+int rau_criterion_forward_cand(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev,
+                               int32_t G, const int32_t* ids_dev, const float* w_dev, int32_t C, const int32_t* cand_dev,
+                               int kind, float* loss);
+int rau_criterion_backward_cand(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev, int32_t G,
+                                const int32_t* ids_dev, const float* w_dev, int32_t C, const int32_t* cand_dev, int kind,
+                                float scale, float** d_logits);
 int rau_att_criterion_forward(rau_ctx* ctx, int h, const float* attprob_dev, const float* t_dev,
                               const int32_t* nreg_dev, float* loss);
 int rau_att_criterion_backward(rau_ctx* ctx, int h, const float* attprob_dev, const float* t_dev,
@@ -205,6 +213,8 @@ int rau_predict_scores(rau_ctx* ctx, float* oe, float* mc, float* totals);
 int rau_predict(rau_ctx* ctx, const int32_t* mc_ans, int32_t n_mc, int32_t* oe, int32_t* mc);
 int rau_get_merged(rau_ctx* ctx, float* pred, float* att);
 int rau_topk(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf);
+int rau_cand_stats(rau_ctx* ctx, float* loss, int32_t* correct, float* score, int32_t* n_lab);
+int rau_topk_cand(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf);
 int rau_noise_clip_adam(rau_ctx* ctx, int64_t step_t, float lr, float mult_lr,
                         float beta1, float beta2, float eps, float eta, float gamma,
                         float clip, uint64_t noise_seed, float* out_norms);
@@ -451,6 +461,43 @@ function RAU:batchSampleWeights()
   local v = ffi.new('int[1]')
   check(C.rau_batch_sample_weights(self.h, v))
   return v[0] ~= 0
+end
+-- Multiple-choice candidates (rau_set_candidates): cand IntTensor [B,C] of 1-based answer ids (0 = empty entry),
+-- C <= 32; the criterion head is normalised over a sample's candidates only (VQA v1: its 18 choices).  nil detaches
+-- them.  slot as in setAnswers; the list lasts until the next batch goes into that slot.
+function RAU:setCandidates(cand, slot)
+  if cand == nil then
+    check(C.rau_set_candidates(self.h, slot or -1, 0, nil))
+    return
+  end
+  cand = cand:int():contiguous()
+  assert(cand:dim() == 2 and cand:size(1) == self.n, 'cand must be [B,C]')
+  check(C.rau_set_candidates(self.h, slot or -1, cand:size(2), cand:data()))
+end
+-- C of the resident batch's candidates, 0 without them
+function RAU:batchCandidates()
+  local c = ffi.new('int32_t[1]')
+  check(C.rau_batch_candidates(self.h, c))
+  return c[0]
+end
+-- MC statistics of the last forward on a batch with candidates (feval rule): loss (restricted criterion), correct,
+-- score per row of nHop+2 (hops, uni, select) and the number of labelled rows
+function RAU:candStats()
+  local R = self.cfg.H + 2
+  local loss, score = torch.FloatTensor(R), torch.FloatTensor(R)
+  local correct = torch.IntTensor(R)
+  local nlab = ffi.new('int32_t[1]')
+  check(C.rau_cand_stats(self.h, loss:data(), correct:data(), score:data(), nlab))
+  return {loss = loss, correct = correct, score = score, n_lab = nlab[0]}
+end
+-- the k best candidates of every predict_result row of the last forward: ids (IntTensor, 1-based, 0 behind the live
+-- candidates), their logits and their confidences over the candidates, each [nHop+2, B, k]
+function RAU:topkCand(k)
+  local H, B = self.cfg.H, self.n
+  local ids = torch.IntTensor(H + 2, B, k)
+  local score, conf = torch.FloatTensor(H + 2, B, k), torch.FloatTensor(H + 2, B, k)
+  check(C.rau_topk_cand(self.h, k, ids:data(), score:data(), conf:data()))
+  return ids, score, conf
 end
 -- the per-sample loss rows [H][B] of the last forward (with weights: the weighted rows) as a FloatTensor
 function RAU:lossRows()

@@ -518,6 +518,55 @@ int rau_batch_regions(rau_ctx* ctx, int* has);
 int rau_set_sample_weights(rau_ctx* ctx, int slot, const float* s /* [batch] host; NULL = detach */);
 int rau_batch_sample_weights(rau_ctx* ctx, int* has);
 
+/* ---- multiple-choice candidates: the criterion restricted to a sample's candidate answers ---------------
+ * VQA v1 gives every question 18 candidate answers, Visual7W four; answer-type restricted evaluation has the same
+ * shape.  Candidates tell the criterion head which answers a sample is normalised over: cand [n,C] int32 host,
+ * cand[b,c] an answer id in 1..K or 0 for an empty entry, n the current batch size, 1 <= C <= RAU_MAX_CANDIDATES.
+ * A duplicate id in a row counts once: an entry equal to an earlier entry of the row is dead.  L_b = the live
+ * entries of row b.  A row with no live entry is an unlabelled sample: loss 0, gradient +0.  NULL or C == 0
+ * detaches the list (nothing is copied; a forward that ran with it must be run again).
+ * slot = -1 | 0 | 1, ownership and lifetime are exactly those of rau_set_answers: -1 is the resident batch and
+ * synchronises; 0 | 1 is a slot of the asynchronous path, between rau_set_batch_async* and rau_use_batch, enqueued on
+ * the copy stream, nothing synchronised; the list belongs to the slot's batch; a later upload into that slot, or
+ * rau_set_batch_size, clears it; rau_use_batch makes it current with the batch.  A forward that has run on the batch
+ * must be run again before rau_backward or the statistics.  Works on plain, typed, packed, image-table, bank and
+ * device batches, with or without an attached question.
+ * With candidates the criterion head of rau_forward / rau_graph_step is cand_head.hip's kernel in place of the
+ * full-vocabulary one.  Unchanged: the logits, do_pred, the argmax over ALL K (rau_get_argmax, the open-ended answer,
+ * the step-selection head's target).  Restricted, with x the row's logits and invB = s_b / n (s_b the sample weight,
+ * or 1):
+ *   kept truth  set entries (rau_set_answers), or the label as the set {(y, 1)}, whose id is not in L_b are dropped:
+ *               they count as empty entries
+ *   softmax     m = max_{c in L} x_c; den = sum_{c in L} expf(x_c - m), added from +0 in entry order; lse = m + logf(den);
+ *               W = the kept weights added in entry order
+ *               loss row   sum_g w_g (lse - x[y_g]) over the kept entries in order, times s_b last
+ *               d_logits   k in L: expf(x_k - lse) (W invB), then for the kept g in order: if (y_g == k) -= w_g invB
+ *                          (the first match inside the product's fused multiply-add, as at rau_set_answers);
+ *                          k not in L: +0.  A row without a kept entry is unlabelled.
+ *   sigmoid     (RAU_LOSS_BCE) t_c = min(1, the kept matching weights added in order);
+ *               loss row   sum_{c in L} max(x_c,0) - x_c t_c + log1p(exp(-|x_c|)), from +0 in entry order, times s_b
+ *               d_logits   k_c in L: (sigmoid(x_c) - t_c) invB; +0 elsewhere.  A row is labelled when its kept set has
+ *               a non-empty entry.
+ * So a row whose one live candidate is its truth has loss 0 and gradient 0 up to the rounding of expf(0).  No atomics,
+ * no device scratch, the same bits on every call.  Everything downstream of d_logits and the loss rows (hop_w,
+ * select_w, att_w, rau_backward_ext, region counts, sample weights, tied dropout, the feature-map and question
+ * gradients, bf16 mode, any K) works unchanged; rau_get_losses, rau_get_loss_rows and rau_step_stats' loss[0..H) are
+ * the restricted rows.  Everything else of rau_step_stats, and rau_step_scores, rau_predict, rau_topk and
+ * rau_predict_scores, stay open-ended statistics over all K; the MC ones are rau_cand_stats / rau_topk_cand below.
+ * The deliberate gap: the merged rows' terms (merge_w) are full-vocabulary cross-entropies, so a non-zero merge_w on
+ * a batch with candidates is RAU_ERR_INVALID, nothing launched, in rau_backward_merged, rau_backward_ext and
+ * rau_graph_step_merged (NULL or zeros stays the path without it).
+ * A batch without candidates computes and launches exactly what it did before candidates existed.  rau_graph_step
+ * keys its cache by C: a step captured without candidates, or with another C, is never replayed; a replay reads the
+ * current list of the resident batch.
+ * Errors, nothing uploaded, the previous list stays in force: RAU_ERR_INVALID for C out of range or an id outside
+ * 0..K; RAU_ERR_STATE when the slot holds no batch, or (slot 0 | 1) it is the current batch of a forward whose
+ * backward has not run, or while a step is being captured.
+ * rau_batch_candidates: the C of the resident batch's list, 0 when it has none. */
+#define RAU_MAX_CANDIDATES 32
+int rau_set_candidates(rau_ctx* ctx, int slot, int32_t C, const int32_t* cand /* [n,C] host; NULL or C == 0: detach */);
+int rau_batch_candidates(rau_ctx* ctx, int32_t* C);
+
 /* ---- packed region features: rows as the files store them, unpacked on the device ------------------
  * Region feature files hold one row of D values per box.  A packed batch hands those rows over as they are:
  * rows [sum(counts), D] of feat_type elements, row-major, map i owning counts[i] consecutive rows (1 <= counts[i]
@@ -672,6 +721,8 @@ int rau_att_stats(rau_ctx* ctx, float* loss /* [H] */, float* mass /* [H] */, in
  * its slot has been uploaded into since (the rule of rau_step_stats); every state rule of rau_backward applies as
  * well.  A non-finite weight in any array: RAU_ERR_INVALID.  The two terms are cross-entropies: under RAU_LOSS_BCE
  * (rau_set_answer_loss) a non-zero merge_w is RAU_ERR_INVALID, nothing launched, here and in rau_graph_step_merged.
+ * They are full-vocabulary cross-entropies too: on a batch with candidates (rau_set_candidates) a non-zero merge_w
+ * is RAU_ERR_INVALID, nothing launched, here, in rau_backward_ext and in rau_graph_step_merged.
  * rau_graph_step_merged is rau_graph_step_att with that backward: merge_w is uploaded next to hop_w and read from
  * device memory, so it may change between replays; "any merge_w non-zero" joins the cache key.
  * rau_merge_criterion_backward, for hosts that call the clones one by one: logits_dev [H,n,K] and dopred_dev [H,n]
@@ -962,6 +1013,18 @@ int rau_criterion_forward_bce(rau_ctx* ctx, int h, const float* logits, const in
 int rau_criterion_backward_bce(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev,
                                int32_t G, const int32_t* ids_dev, const float* w_dev, float scale, float** d_logits);
 
+/* The criterion restricted to candidates (rau_set_candidates: kept truth, loss row, gradient, roundings) on logits
+ * the caller holds: the kernel the step's head uses on a batch with candidates.  cand_dev [B,C] int32 in DEVICE
+ * memory (1 <= C <= RAU_MAX_CANDIDATES, ids clamped into [0, K]); the target is labels_dev [B] or with labels_dev NULL
+ * the answer set ids_dev / w_dev [B,G] (neither: RAU_ERR_INVALID); kind = RAU_LOSS_CE or RAU_LOSS_BCE.  :forward ->
+ * *loss (host, may be NULL) = the mean over B of the loss rows; :backward -> d_logits [B,K] = scale * the gradient. */
+int rau_criterion_forward_cand(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev /* NULL: use the set */,
+                               int32_t G, const int32_t* ids_dev, const float* w_dev, int32_t C, const int32_t* cand_dev,
+                               int kind, float* loss);
+int rau_criterion_backward_cand(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev, int32_t G,
+                                const int32_t* ids_dev, const float* w_dev, int32_t C, const int32_t* cand_dev, int kind,
+                                float scale, float** d_logits);
+
 /* The attention supervision above for hosts that call the clones one by one: attprob_dev [B,S] (the attprob output
  * of rau_multimodal_forward), t_dev [B,S] targets and nreg_dev [B] region counts (NULL = none, clamped into [1, S]),
  * all dense in DEVICE memory.  :forward -> *loss = ATT_h (host, may be NULL); :backward -> d_attprob [B,S]
@@ -1116,8 +1179,32 @@ int rau_get_merged(rau_ctx* ctx, float* pred, float* att);
  * Its device staging is allocated at the first call and regrown for a larger k (RAU_ERR_NOMEM leaves
  * the context usable).  Open-ended answers only: the reference's multiple-choice rule multiplies the
  * raw logits by a 0/1 mask, so a ranked MC list would rank the masked-out zeros among the candidates;
- * rau_predict stays the MC call. */
+ * rau_predict stays the MC call of that rule, rau_topk_cand below ranks a batch's candidates among themselves. */
 int rau_topk(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf);
+
+/* Multiple-choice statistics and ranked MC answers of the last step-level forward on a batch WITH candidates
+ * (rau_set_candidates; cand_rank.hip).  The rows are the merged rows above (H hops, uni, select); a row's live
+ * candidates are ranked among themselves in rau_dev_topk's total order: larger logit first, ties by the lower answer
+ * id, NaN last.  Both return RAU_ERR_STATE, nothing launched, without such a forward or when its batch had no
+ * candidates.  Any output may be NULL.  Synchronising; no float atomics, the same bits on every call.
+ *   rau_topk_cand   predict rule (last hop forced, as rau_topk; valid when rau_predict is, needs no labels).  ids,
+ *                   score, conf [H+2, n, k]: the k best candidates, their logits (bit for bit the row's value) and
+ *                   conf = expf(v - m) / den over the live candidates (m, den as at rau_set_candidates).  Ranks at
+ *                   and behind the number of live candidates: id 0, score -INFINITY, conf +0.  1 <= k <= C, else
+ *                   RAU_ERR_INVALID.
+ *                   Rank 0 is the first maximum of the candidates' logits: the masking rule a softmax over the
+ *                   candidates implies.  It equals rau_predict's mc whenever the best candidate's logit is positive;
+ *                   it differs BY DESIGN where the reference's multiply rule lets a masked-out zero win (a row whose
+ *                   candidates are all negative).  rau_predict stays as it is.
+ *   rau_cand_stats  feval rule (last hop not forced, as rau_step_stats); also RAU_ERR_STATE without a ground truth.
+ *                   Per row of H+2: loss = the restricted criterion of rau_set_candidates (mean over n, sample weights
+ *                   applied; under RAU_LOSS_BCE the restricted sigmoid criterion), loss[0..H) bitwise rau_get_losses;
+ *                   correct = the labelled rows whose rank-0 candidate is the label, or carries a positive score in
+ *                   the answer set; score = the summed metric score of that candidate (labels: 1 when correct),
+ *                   reduced in rau_step_scores' fixed order.  n_lab = the labelled rows: those with a kept truth
+ *                   entry.  Counts and scores are unweighted. */
+int rau_cand_stats(rau_ctx* ctx, float* loss /* [H+2] */, int32_t* correct /* [H+2] */, float* score /* [H+2] */, int32_t* n_lab);
+int rau_topk_cand(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf /* [H+2, n, k] host */);
 
 /* ---- update: SS:597-630 + utils/optim_updates.lua:59-87 (row "next-1") -------
  * Gradient noise N(0, eta/((step_t+1)*gamma)), per-group L2 clip, Adam with

@@ -119,6 +119,9 @@ _SIGS = {
     "rau_batch_regions": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rau_set_sample_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "rau_batch_sample_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    # multiple-choice candidates of a batch: the criterion head restricted to them
+    "rau_set_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_void_p]),
+    "rau_batch_candidates": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     # packed region rows: transposed and zero-padded on the device, counts attached in the same call
     "rau_set_batch_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
@@ -211,6 +214,11 @@ _SIGS = {
                                             C.c_void_p, C.POINTER(C.c_float)]),
     "rau_criterion_backward_bce": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                              C.c_void_p, C.c_float, C.POINTER(C.c_void_p)]),
+    "rau_criterion_forward_cand": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "rau_criterion_backward_cand": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.c_float,
+                                              C.POINTER(C.c_void_p)]),
     # device tensors (the tensor algebra feval does between module calls)
     "rau_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "rau_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -255,6 +263,8 @@ _SIGS = {
     "rau_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "rau_get_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_topk": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rau_cand_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "rau_topk_cand": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_noise_clip_adam": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_float] * 8 +
                             [C.c_uint64, C.c_void_p]),
     # the update with a rule and a clip scope; optimizer state in and out

@@ -1,5 +1,6 @@
 // hop_merge.h -- the rows predict_result and feval read out of the resident hop outputs, for the
-// kernels that consume them (hop_merge.hip: statistics, first-max answers; topk.hip: ranked answers), and the
+// kernels that consume them (hop_merge.hip: statistics, first-max answers; topk.hip: ranked answers; cand_rank.hip:
+// ranked candidates and MC statistics), and the
 // arithmetic of the per-answer sigmoid criterion (bce_head.hip: the step's head; hop_merge.hip: its statistics).
 // One definition of the merge arithmetic, so that every consumer sees the same bits.
 #pragma once
@@ -84,6 +85,19 @@ __device__ __forceinline__ bool bce_labelled(const int* s_id, int ng) {
   bool any = false;
   for (int g = 0; g < ng; ++g) any = any || s_id[g] >= 0;
   return any;
+}
+
+// The TOTAL order of include/rau.h (rau_dev_topk) as a 64-bit key: the high word is the monotone unsigned image of
+// the float (-0 canonicalised to +0, NaN below -inf), the low word is 0xffffffff - index.  A larger key ranks first:
+// larger value, equal values by the lower index, NaN last by index.  Shared by topk.hip and cand_rank.hip.
+__device__ __forceinline__ uint32_t order_bits(float v) {
+  uint32_t u = __float_as_uint(v);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;   // NaN: after everything, -inf (0x007fffff) included
+  if (u == 0x80000000u) u = 0u;                     // -0 == +0
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ uint64_t make_key(float v, int c) {
+  return ((uint64_t)order_bits(v) << 32) | (uint64_t)(0xffffffffu - (uint32_t)c);
 }
 
 }  // namespace rau

@@ -457,18 +457,48 @@ struct Truth {
   // per-sample loss weights [Bper] (device; rau_set_sample_weights) or null: every kernel that forms a training
   // term from this target multiplies the term's 1 / Bper (or hop weight) by sw[b]; set by step_truth() only
   const float* sw = nullptr;
+  // multiple-choice candidates [Bper][C] (device; rau_set_candidates), C = 0: none.  The criterion is then restricted
+  // to the row's live candidates (cand_head.hip); set by step_truth() and the module-level _cand calls only
+  const int32_t* cand = nullptr;
+  int C = 0;
   bool present() const { return labels || G > 0; }
   bool bce() const { return loss != 0; }
 };
-// The criterion head against whichever target `t` holds, with the criterion it names: bce_fwd (RAU_LOSS_BCE), else
-// ce_set_fwd (G > 0) or ce_fwd (labels, or none); the other arguments are the ones they share.  criterion_class
-// names the launch for the profile.
-inline const char* criterion_class(const Truth& t) { return t.bce() ? "bce_fwd" : t.G > 0 ? "ce_set_fwd" : "ce_fwd"; }
+// The criterion head restricted to a row's candidates (cand_head.hip, rau_set_candidates): ce_fwd's / ce_set_fwd's /
+// bce_fwd's launch contract -- argmax over ALL K, do_pred, finishing of the partials -- with the criterion `kind`
+// (RAU_LOSS_CE / RAU_LOSS_BCE) normalised over the live candidates only.  cand [Bper][C] device, ids 1..K or 0 = empty
+// entry, 1 <= C <= kMaxCandidates; the target is labels [Bper] or (G > 0) the set ids / w [Bper][G]; neither: no loss,
+// no dl.  dl rows are cleared with 16-byte stores: with a target, ld (0 = K) % 4 == 0 and dl 16-byte aligned.
+constexpr int kMaxCandidates = 32;
+hipError_t cand_fwd(hipStream_t st, int kind, int nB, int K, int M, const float* logits, const int32_t* labels,
+                    const int32_t* ids, const float* w, int G, const int32_t* cand, int C, const float* mf,
+                    const float* wd, const float* bd, float* dl, float* lossrow, int32_t* argmax, float* dopred,
+                    const float* part = nullptr, int nsplit = 0, const float* bias = nullptr,
+                    float* logits_out = nullptr, int Bper = 0, int ld = 0, const float* sw = nullptr);
+// Ranked candidates and MC statistics of the merged rows (cand_rank.hip, rau_topk_cand / rau_cand_stats): one wave
+// per (row of H+2, sample), lane c holds candidate c.  Rows are hop_merge.h's; logits at pitch ld (0 = K).
+// cand_topk: predict rule (last hop forced); ids / score / conf [H+2][B][k], 1 <= k <= C.
+// cand_stats: feval rule; rows = rowf [2][B] | rowsc [H+2][B] floats, rowi = correct [H+2][B] | labelled [B];
+// out = loss [H+2] | score [H+2] (floats) | correct [H+2] | n_lab (int32), reduced by one workgroup in a fixed order
+// (loss[:H] from lossrow in loss_reduce's order).
+hipError_t cand_topk(hipStream_t st, int H, int B, int K, int k, const float* logits, const float* dopred,
+                     const int32_t* cand, int C, int32_t* ids, float* score, float* conf, int ld);
+hipError_t cand_stats(hipStream_t st, int H, int B, int K, const float* logits, const float* dopred,
+                      const float* lossrow, const Truth& t, float* rows, int32_t* rowi, float* out, int ld);
+// The criterion head against whichever target `t` holds, with the criterion it names: cand_fwd when the batch names
+// candidates (t.C > 0), else bce_fwd (RAU_LOSS_BCE), else ce_set_fwd (G > 0) or ce_fwd (labels, or none); the other
+// arguments are the ones they share.  criterion_class names the launch for the profile.
+inline const char* criterion_class(const Truth& t) {
+  return t.C > 0 ? "cand_fwd" : t.bce() ? "bce_fwd" : t.G > 0 ? "ce_set_fwd" : "ce_fwd";
+}
 inline hipError_t criterion_head(hipStream_t st, int nB, int K, int M, const float* logits, const Truth& t,
                                  const float* mf, const float* wd, const float* bd, float* dl, float* lossrow,
                                  int32_t* argmax, float* dopred, const float* part = nullptr, int nsplit = 0,
                                  const float* bias = nullptr, float* logits_out = nullptr, int Bper = 0,
                                  int ld = 0) {
+  if (t.C > 0)
+    return cand_fwd(st, t.loss, nB, K, M, logits, t.labels, t.ids, t.w, t.G, t.cand, t.C, mf, wd, bd, dl, lossrow,
+                    argmax, dopred, part, nsplit, bias, logits_out, Bper, ld, t.sw);
   if (t.bce())
     return bce_fwd(st, nB, K, M, logits, t.labels, t.ids, t.w, t.G, mf, wd, bd, dl, lossrow, argmax, dopred, part,
                    nsplit, bias, logits_out, Bper, ld, t.sw);

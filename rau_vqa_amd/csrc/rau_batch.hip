@@ -295,6 +295,7 @@ void hold(rau_ctx* ctx, int si, const Batch& b) {
   d.regions = b.pk_counts != nullptr;   // ... and so do region counts (a packed batch brings its own)
   d.att_targets = false;   // ... and attention targets
   d.sample_w = false;      // ... and per-sample loss weights
+  d.cand_C = 0;            // ... and multiple-choice candidates
   d.question = false;      // ... and the caller's question state
 }
 
@@ -335,7 +336,7 @@ int set_batch_sync(rau_ctx* ctx, Batch b) {
     HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
   if (int rc = enqueue_batch(ctx, ctx->st, si, b)) return rc;
   HIPC(hipStreamSynchronize(ctx->st));   // the caller's (pageable) buffers are free on return
-  s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+  s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
   hold(ctx, si, b);
   drop_forward(ctx);
   return RAU_OK;
@@ -367,7 +368,7 @@ int set_batch_slot(rau_ctx* ctx, int slot, Batch b, int has_labels) {
   // that call performs the same wait before the caller's own writes -- include/rau.h.)
   if (s.upload_pending) {
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
   }
   // NULL = the caller has filled the slot's pinned staging in place (rau_batch_slot)
   if (b.feats && b.feats != s.feats_h) std::memcpy(s.feats_h, b.feats, nf * feat_elem_bytes(b.feat_type));
@@ -465,6 +466,25 @@ int ensure_sample_weights(rau_ctx* ctx, int si) {
     hipError_t e = hipHostMalloc(&h, (size_t)ctx->cap * 4, hipHostMallocDefault);
     if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(sample weight staging): %s", hipGetErrorString(e));
     s.sw_h = static_cast<float*>(h);
+  }
+  return RAU_OK;
+}
+
+// first candidate list of a slot: the device array [capacity][kMaxCandidates] the criterion head reads and the pinned
+// staging the copies read
+int ensure_candidates(rau_ctx* ctx, int si) {
+  BatchSlot& s = ctx->slot[si];
+  const size_t n = (size_t)ctx->cap * kMaxCandidates;
+  if (!s.cand_d) {
+    if (int rc = dalloc(ctx, &s.cand_d, n)) return rc;
+    // dalloc clears the array on the chain stream; the slot form copies into it on the copy stream.  Once per slot.
+    HIPC(hipStreamSynchronize(ctx->st));
+  }
+  if (!s.cand_h) {
+    void* h = nullptr;
+    hipError_t e = hipHostMalloc(&h, n * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(RAU_ERR_NOMEM, "hipHostMalloc(candidate staging): %s", hipGetErrorString(e));
+    s.cand_h = static_cast<int32_t*>(h);
   }
   return RAU_OK;
 }
@@ -660,7 +680,7 @@ static int set_batch_dev(rau_ctx* ctx, const char* who, const float* feats_dev, 
   }
   if (int rc = enqueue_batch(ctx, st, si, b)) return rc;   // (feats == NULL: the index arrays only)
   HIPC(hipEventRecord(ctx->bdev_ev[sl], st));
-  s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+  s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
   hold(ctx, si, b);
   drop_forward(ctx);
   return RAU_OK;
@@ -716,7 +736,7 @@ int rau_batch_slot(rau_ctx* ctx, int slot, float** feats_host, int32_t** tokens_
   BatchSlot& s = ctx->slot[slot];
   if (s.upload_pending) {   // the caller is about to overwrite the staging: its last copy must have left
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
   }
   if (feats_host) *feats_host = s.feats_h;
   if (tokens_host) *tokens_host = s.tokens_h;
@@ -821,7 +841,7 @@ int rau_set_answers(rau_ctx* ctx, int slot, int32_t G, const int32_t* ids, const
   if (int rc = ensure_answers(ctx, si)) return rc;
   if (s.ans_pending) {   // the staging's previous set has not left it yet (two sets for one upload)
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
   }
   int32_t* ids_h = s.ans_h;
   float* w_h = reinterpret_cast<float*>(s.ans_h + n);
@@ -884,7 +904,7 @@ int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n) {
   if (int rc = ensure_regions(ctx, si)) return rc;
   if (s.reg_pending) {   // the staging's previous counts have not left it yet (two sets for one upload)
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
   }
   std::memcpy(s.nreg_h, n, (size_t)c.B * 4);
   hipStream_t st = slot < 0 ? ctx->st : ctx->stc;
@@ -902,7 +922,7 @@ int rau_set_regions(rau_ctx* ctx, int slot, const int32_t* n) {
   if (slot < 0) {
     HIPC(hipStreamSynchronize(st));
     // (the chain stream waited for a pending upload above: every copy behind `uploaded` has left its staging)
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
   } else {
     HIPC(hipEventRecord(s.uploaded, st));   // rau_use_batch orders the step behind the counts too
     s.upload_pending = s.reg_pending = true;
@@ -941,7 +961,7 @@ int rau_set_att_targets(rau_ctx* ctx, int slot, const float* t) {
   if (int rc = ensure_att_targets(ctx, si)) return rc;
   if (s.att_pending) {   // the staging's previous maps have not left it yet (two sets for one upload)
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
   }
   std::memcpy(s.att_t_h, t, n * 4);
   hipStream_t st = slot < 0 ? ctx->st : ctx->stc;
@@ -963,7 +983,7 @@ int rau_set_att_targets(rau_ctx* ctx, int slot, const float* t) {
   if (slot < 0) {
     HIPC(hipStreamSynchronize(st));
     // (the chain stream waited for a pending upload above: every copy behind `uploaded` has left its staging)
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
   } else {
     HIPC(hipEventRecord(s.uploaded, st));   // rau_use_batch orders the step behind the targets too
     s.upload_pending = s.att_pending = true;
@@ -1006,7 +1026,7 @@ int rau_set_sample_weights(rau_ctx* ctx, int slot, const float* sw) {
   if (int rc = ensure_sample_weights(ctx, si)) return rc;
   if (s.sw_pending) {   // the staging's previous weights have not left it yet (two sets for one upload)
     HIPC(hipEventSynchronize(s.uploaded));
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
   }
   std::memcpy(s.sw_h, sw, (size_t)c.B * 4);
   hipStream_t st = slot < 0 ? ctx->st : ctx->stc;
@@ -1024,7 +1044,7 @@ int rau_set_sample_weights(rau_ctx* ctx, int slot, const float* sw) {
   if (slot < 0) {
     HIPC(hipStreamSynchronize(st));
     // (the chain stream waited for a pending upload above: every copy behind `uploaded` has left its staging)
-    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = false;
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
   } else {
     HIPC(hipEventRecord(s.uploaded, st));   // rau_use_batch orders the step behind the weights too
     s.upload_pending = s.sw_pending = true;
@@ -1039,6 +1059,75 @@ int rau_set_sample_weights(rau_ctx* ctx, int slot, const float* sw) {
 int rau_batch_sample_weights(rau_ctx* ctx, int* has) {
   NEED(ctx && has, "null argument");
   *has = cur_batch(ctx).held.sample_w ? 1 : 0;
+  return RAU_OK;
+}
+
+// Multiple-choice candidates for the batch in a slot: rau_set_answers' slot and ordering rules; NULL or C == 0
+// detaches them.  Everything is checked before anything moves.  The forward's head reads them: a forward that ran
+// must run again.
+int rau_set_candidates(rau_ctx* ctx, int slot, int32_t C, const int32_t* cand) {
+  NEED(ctx, "null ctx");
+  NEED(slot >= -1 && slot <= 1, "rau_set_candidates: slot %d (-1 = the resident batch, 0 or 1)", slot);
+  if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_candidates: a step is being captured");
+  const rau_config& c = ctx->cfg;
+  const int si = slot < 0 ? ctx->cur_slot : slot;
+  BatchSlot& s = ctx->slot[si];
+  if (!s.held.have)
+    return fail(RAU_ERR_STATE, "rau_set_candidates: slot %d holds no batch (upload the batch first)", si);
+  if (slot >= 0 && si == ctx->cur_slot && ctx->fwd.done)
+    return fail(RAU_ERR_STATE, "rau_set_candidates: slot %d is the current batch of a forward pass whose backward has "
+                "not run", si);
+  if (!cand || C == 0) {   // detach: nothing moves, the next step is the one without candidates
+    if (s.held.cand_C > 0) {
+      if (si == ctx->cur_slot) drop_forward(ctx);
+      if (si == ctx->mg.slot) ctx->mg.valid = false;
+    }
+    s.held.cand_C = 0;
+    return RAU_OK;
+  }
+  NEED(C >= 1 && C <= kMaxCandidates, "rau_set_candidates: C=%d out of [1,%d]", C, kMaxCandidates);
+  const size_t n = (size_t)c.B * C;
+  for (size_t i = 0; i < n; ++i)
+    NEED(cand[i] >= 0 && cand[i] <= c.K, "rau_set_candidates: cand[%zu]=%d out of [0,%d] (0 = empty entry)", i, cand[i],
+         c.K);
+  if (slot >= 0)
+    if (int rc = ensure_async(ctx)) return rc;
+  if (int rc = ensure_candidates(ctx, si)) return rc;
+  if (s.cand_pending) {   // the staging's previous list has not left it yet (two lists for one upload)
+    HIPC(hipEventSynchronize(s.uploaded));
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
+  }
+  std::memcpy(s.cand_h, cand, n * 4);
+  hipStream_t st = slot < 0 ? ctx->st : ctx->stc;
+  if (slot < 0) {
+    if (s.upload_pending) HIPC(hipStreamWaitEvent(st, s.uploaded, 0));   // behind an asynchronous upload of the batch
+  } else {
+    // the slot's buffers may still be read by the last step that used them
+    if (si == ctx->cur_slot) {
+      HIPC(hipEventRecord(s.consumed, ctx->st));
+      s.consumed_valid = true;
+    }
+    if (s.consumed_valid) HIPC(hipStreamWaitEvent(st, s.consumed, 0));
+  }
+  HIPC(hipMemcpyAsync(s.cand_d, s.cand_h, n * 4, hipMemcpyHostToDevice, st));
+  if (slot < 0) {
+    HIPC(hipStreamSynchronize(st));
+    // (the chain stream waited for a pending upload above: every copy behind `uploaded` has left its staging)
+    s.upload_pending = s.ans_pending = s.reg_pending = s.att_pending = s.sw_pending = s.cand_pending = false;
+  } else {
+    HIPC(hipEventRecord(s.uploaded, st));   // rau_use_batch orders the step behind the list too
+    s.upload_pending = s.cand_pending = true;
+    if (si == ctx->cur_slot) HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
+  }
+  s.held.cand_C = C;
+  if (si == ctx->cur_slot) drop_forward(ctx);   // a forward that ran on the batch did not see this list
+  if (si == ctx->mg.slot) ctx->mg.valid = false;   // statistics of a forward whose list has just been overwritten
+  return RAU_OK;
+}
+
+int rau_batch_candidates(rau_ctx* ctx, int32_t* C) {
+  NEED(ctx && C, "null argument");
+  *C = cur_batch(ctx).held.cand_C;
   return RAU_OK;
 }
 

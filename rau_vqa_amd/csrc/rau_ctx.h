@@ -101,6 +101,9 @@ struct BatchDesc {
   // per-sample loss weights (rau_set_sample_weights): the slot's sw_d holds one weight per sample, read by every
   // kernel that forms a training term (step_truth()).  They belong to the batch like the three above.
   bool sample_w = false;
+  // multiple-choice candidates (rau_set_candidates): C entries per sample in the slot's cand_d, 0 = none.  The
+  // criterion head and the MC statistics read them (step_truth()).  They belong to the batch like the four above.
+  int cand_C = 0;
   // question state from the caller (rau_set_question_dev): the slot's q_ext holds q [n][Q] and the step reads it in
   // place of the built-in encoder's output.  It belongs to the RESIDENT batch: hold() and rau_use_batch drop it.
   bool question = false;
@@ -149,6 +152,11 @@ struct BatchSlot {
   float* sw_d = nullptr;
   float* sw_h = nullptr;
   bool sw_pending = false;          // a copy out of sw_h is behind the last record of `uploaded`
+  // candidates of the batch: [B][C] dense in the current size and C, room for [capacity][kMaxCandidates]; device and
+  // pinned host, allocated at the slot's first list (a captured step holds cand_d's address, never its contents)
+  int32_t* cand_d = nullptr;
+  int32_t* cand_h = nullptr;
+  bool cand_pending = false;        // a copy out of cand_h is behind the last record of `uploaded`
   // the caller's question state (rau_set_question_dev): device [capacity][Q] f32, allocated at the slot's first
   // attach (a captured step holds q_ext's address, never its contents)
   float* q_ext = nullptr;
@@ -204,6 +212,10 @@ struct MergeState {
   // its first call and regrown when a larger k is asked for
   void* topk = nullptr;
   int topk_k = 0;
+  // rau_topk_cand / rau_cand_stats (cand_rank.hip), one block allocated at the first call of either: the ranked
+  // lists' staging ids | score | conf, room for [H+2][cap][kMaxCandidates] each, then the statistics' rows
+  // (H+4) * cap floats, (H+3) * cap int32, and their results 3 (H+2) + 1 words
+  uint32_t* cand = nullptr;
   // no forward result, no rau_predict result, no ground truth: a fresh context's (rau_set_batch_size)
   void invalidate() { valid = merged = false; truth = Truth{}; }
 };
@@ -266,10 +278,12 @@ struct StepKey {
                                 // encoder: the hop chain reads the slot's q_ext
   bool sample_w = false;        // ... and the kernels that form the training terms hold the slot's sample weights
                                 // or a null pointer (rau_set_sample_weights); a replay reads the current weights
+  int cand_C = 0;               // ... against C candidates per sample (0 = none): another head kernel, which holds the
+                                // slot's list (rau_set_candidates); a replay reads the current list
   auto tied() const {
     return std::tie(mode, max_len, active, zero, mexplicit[0], mexplicit[1], mexplicit[2], mexplicit[3], mexplicit[4],
                     slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg, tied_x, ans_loss,
-                    feat_grad, question, sample_w);
+                    feat_grad, question, sample_w, cand_C);
   }
   bool operator==(const StepKey& o) const { return tied() == o.tied(); }
 };
@@ -518,6 +532,7 @@ inline StepKey step_key(const rau_ctx* ctx, const StepLoss& loss, bool zero) {
   key.feat_grad = ctx->feat_grad;
   key.question = d.question;
   key.sample_w = d.sample_w;
+  key.cand_C = d.cand_C;
   return key;
 }
 
@@ -565,6 +580,8 @@ inline Truth step_truth(const rau_ctx* ctx) {
   Truth t = truth_of(s);
   t.loss = ctx->answer_loss;
   t.sw = s.held.sample_w ? s.sw_d : nullptr;   // the step path's terms only: module-level criteria stay unweighted
+  t.cand = s.held.cand_C > 0 ? s.cand_d : nullptr;   // ... and so do the candidates (with or without a ground truth)
+  t.C = s.held.cand_C;
   return t;
 }
 // The hop outputs now hold the results of the forward just enqueued: rau_step_stats / rau_predict may

@@ -612,6 +612,7 @@ void rau_destroy(rau_ctx* ctx) {
     if (s.ans_h) hipHostFree(s.ans_h);
     if (s.nreg_h) hipHostFree(s.nreg_h);
     if (s.sw_h) hipHostFree(s.sw_h);
+    if (s.cand_h) hipHostFree(s.cand_h);
     if (s.att_t_h) hipHostFree(s.att_t_h);
     if (s.pk_meta_h) hipHostFree(s.pk_meta_h);
     if (s.uploaded) hipEventDestroy(s.uploaded);
@@ -948,6 +949,7 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
     ctx->slot[si].held = BatchDesc{};
     ctx->slot[si].upload_pending = ctx->slot[si].consumed_valid = ctx->slot[si].ans_pending = false;
     ctx->slot[si].reg_pending = ctx->slot[si].att_pending = ctx->slot[si].sw_pending = false;
+    ctx->slot[si].cand_pending = false;
     ++ctx->slot_serial[si];
   }
   ctx->cur_slot = 0;
@@ -2156,6 +2158,10 @@ static int step_loss(rau_ctx* ctx, const char* fn, bool check_hop_w, const float
     NEED(!merge_w || ctx->answer_loss == RAU_LOSS_CE,
          "%s: a non-zero merge_w under RAU_LOSS_BCE (rau_set_answer_loss): the merged rows are trained with the "
          "softmax cross-entropy only", fn);
+    // ... and over the whole vocabulary: not part of a step whose criterion is restricted to candidates
+    NEED(!merge_w || cur_batch(ctx).held.cand_C == 0,
+         "%s: a non-zero merge_w on a batch with candidates (rau_set_candidates): the merged rows are trained with "
+         "the full-vocabulary cross-entropy only", fn);
   }
   const int H = ctx->cfg.H;
   bool any = false, any_att = false, hop_any = false;

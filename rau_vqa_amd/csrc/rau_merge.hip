@@ -1,7 +1,8 @@
 // rau_merge.hip -- the merged-hops entry points of include/rau.h: what is read from the hop outputs of the last
 // step-level forward after it has run (kernels: hop_merge.hip, topk.hip): feval's statistics and metric scores
 // (rau_step_stats, rau_step_scores), predict_result's answers and theirs (rau_predict, rau_predict_scores), ranked
-// answers (rau_topk) and the merged rows (rau_get_merged).
+// answers (rau_topk), the merged rows (rau_get_merged), and for a batch with candidates the MC statistics and ranked MC
+// answers (rau_cand_stats, rau_topk_cand; kernels: cand_rank.hip).
 // What they know about that forward is one record, rau_ctx::mg (rau_ctx.h: MergeState): merge_record() fills it
 // behind a forward, merge_state() decides whether it may still be read, and whoever overwrites the hop outputs or
 // the targets clears `valid`.  The target is the record's Truth, taken from the batch slot when the forward ran --
@@ -204,6 +205,71 @@ int rau_topk(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf) {
   if (ids) HIPC(hipMemcpyAsync(ids, ids_d, n * 4, hipMemcpyDeviceToHost, ctx->st));
   if (score) HIPC(hipMemcpyAsync(score, score_d, n * 4, hipMemcpyDeviceToHost, ctx->st));
   if (conf) HIPC(hipMemcpyAsync(conf, conf_d, n * 4, hipMemcpyDeviceToHost, ctx->st));
+  HIPC(hipStreamSynchronize(ctx->st));
+  return persist_check(ctx);
+}
+
+// ---- multiple-choice candidates against the merged rows (cand_rank.hip).  mg.cand, one block: the ranked lists'
+// staging | the statistics' float rows | their int32 rows | their results
+namespace {
+struct CandBufs {
+  int32_t* ids; float* score; float* conf;   // [H+2][cap][kMaxCandidates] each (dense in the call's n and k)
+  float* rows; int32_t* rowi; float* out;
+};
+int cand_bufs(rau_ctx* ctx, CandBufs* cb) {
+  const size_t R = (size_t)ctx->cfg.H + 2, cap = ctx->cap, list = R * cap * kMaxCandidates;
+  if (!ctx->mg.cand)
+    if (int rc = dalloc(ctx, &ctx->mg.cand, 3 * list + (R + 2) * cap + (R + 1) * cap + 3 * R + 1)) return rc;
+  uint32_t* p = ctx->mg.cand;
+  cb->ids = reinterpret_cast<int32_t*>(p);
+  cb->score = reinterpret_cast<float*>(p + list);
+  cb->conf = reinterpret_cast<float*>(p + 2 * list);
+  cb->rows = reinterpret_cast<float*>(p + 3 * list);
+  cb->rowi = reinterpret_cast<int32_t*>(p + 3 * list + (R + 2) * cap);
+  cb->out = reinterpret_cast<float*>(p + 3 * list + (R + 2) * cap + (R + 1) * cap);
+  return RAU_OK;
+}
+}  // namespace
+
+int rau_cand_stats(rau_ctx* ctx, float* loss, int32_t* correct, float* score, int32_t* n_lab) {
+  NEED(ctx, "null ctx");
+  if (int rc = merge_state(ctx, "rau_cand_stats", true)) return rc;
+  if (ctx->mg.truth.C <= 0)
+    return fail(RAU_ERR_STATE, "rau_cand_stats: the batch of the last forward had no candidates (rau_set_candidates)");
+  CandBufs cb;
+  if (int rc = cand_bufs(ctx, &cb)) return rc;
+  const rau_config& c = ctx->cfg;
+  const int H = c.H, B = c.B, R = H + 2;
+  RUN("cand_stats", 0, (double)R * B * ctx->mg.truth.C * 8,
+      cand_stats(ctx->st, H, B, c.K, ctx->logits, ctx->dopred, ctx->lossrow, ctx->mg.truth, cb.rows, cb.rowi, cb.out,
+                 ctx->Kp));
+  std::vector<uint32_t> out((size_t)3 * R + 1);
+  if (int rc = d2h(ctx, out.data(), cb.out, out.size() * 4)) return rc;
+  if (loss) std::memcpy(loss, out.data(), (size_t)R * 4);
+  if (score) std::memcpy(score, out.data() + R, (size_t)R * 4);
+  if (correct) std::memcpy(correct, out.data() + 2 * R, (size_t)R * 4);
+  if (n_lab) std::memcpy(n_lab, out.data() + 3 * R, 4);
+  return RAU_OK;
+}
+
+int rau_topk_cand(rau_ctx* ctx, int32_t k, int32_t* ids, float* score, float* conf) {
+  NEED(ctx, "null ctx");
+  if (int rc = merge_state(ctx, "rau_topk_cand", false)) return rc;
+  const int C = ctx->mg.truth.C;
+  if (C <= 0)
+    return fail(RAU_ERR_STATE, "rau_topk_cand: the batch of the last forward had no candidates (rau_set_candidates)");
+  NEED(k >= 1 && k <= C, "rau_topk_cand: k=%d out of [1,%d] (the C of rau_set_candidates)", k, C);
+  CandBufs cb;
+  if (int rc = cand_bufs(ctx, &cb)) return rc;
+  const rau_config& c = ctx->cfg;
+  const int H = c.H, B = c.B;
+  const size_t n = (size_t)(H + 2) * B * k;
+  RUN("cand_topk", 0, (double)(H + 2) * B * C * 8,
+      cand_topk(ctx->st, H, B, c.K, k, ctx->logits, ctx->dopred, ctx->mg.truth.cand, C, cb.ids, cb.score, cb.conf,
+                ctx->Kp));
+  if (ids) HIPC(hipMemcpyAsync(ids, cb.ids, n * 4, hipMemcpyDeviceToHost, ctx->st));
+  if (score) HIPC(hipMemcpyAsync(score, cb.score, n * 4, hipMemcpyDeviceToHost, ctx->st));
+  if (conf) HIPC(hipMemcpyAsync(conf, cb.conf, n * 4, hipMemcpyDeviceToHost, ctx->st));
   HIPC(hipStreamSynchronize(ctx->st));
   return persist_check(ctx);
 }

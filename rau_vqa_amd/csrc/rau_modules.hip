@@ -564,6 +564,45 @@ int rau_criterion_backward_bce(rau_ctx* ctx, int h, const float* logits, const i
   return criterion(ctx, h, logits, t, nullptr, scale, d_logits);
 }
 
+// criteria[h] restricted to candidates in device memory (cand_head.hip): against labels, or (labels_dev NULL) an
+// answer set, with the criterion `kind`
+static int cand_truth(rau_ctx* ctx, const char* fn, int h, const int32_t* labels_dev, int32_t G, const int32_t* ids_dev,
+                      const float* w_dev, int32_t C, const int32_t* cand_dev, int kind, Truth* t) {
+  NEED(h >= 0 && h < ctx->cfg.H, "%s: h=%d out of [0,%d)", fn, h, ctx->cfg.H);
+  NEED(kind == RAU_LOSS_CE || kind == RAU_LOSS_BCE, "%s: kind=%d (RAU_LOSS_CE or RAU_LOSS_BCE)", fn, kind);
+  NEED(cand_dev, "%s: no candidates", fn);
+  NEED(C >= 1 && C <= kMaxCandidates, "%s: C=%d out of [1,%d]", fn, C, kMaxCandidates);
+  if (int rc = bce_truth(fn, labels_dev, G, ids_dev, w_dev, t)) return rc;
+  t->loss = kind;
+  t->cand = cand_dev;
+  t->C = C;
+  return RAU_OK;
+}
+
+int rau_criterion_forward_cand(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev, int32_t G,
+                               const int32_t* ids_dev, const float* w_dev, int32_t C, const int32_t* cand_dev,
+                               int kind, float* loss) {
+  NEED(ctx && logits, "null argument");
+  NEED_DENSE_K(ctx, "rau_criterion_forward_cand");
+  Truth t;
+  if (int rc = cand_truth(ctx, "rau_criterion_forward_cand", h, labels_dev, G, ids_dev, w_dev, C, cand_dev, kind, &t))
+    return rc;
+  if (int rc = mod_alloc(ctx)) return rc;
+  return criterion(ctx, h, logits, t, loss, 1.f, nullptr);
+}
+
+int rau_criterion_backward_cand(rau_ctx* ctx, int h, const float* logits, const int32_t* labels_dev, int32_t G,
+                                const int32_t* ids_dev, const float* w_dev, int32_t C, const int32_t* cand_dev,
+                                int kind, float scale, float** d_logits) {
+  NEED(ctx && logits && d_logits, "null argument");
+  NEED_DENSE_K(ctx, "rau_criterion_backward_cand");
+  Truth t;
+  if (int rc = cand_truth(ctx, "rau_criterion_backward_cand", h, labels_dev, G, ids_dev, w_dev, C, cand_dev, kind, &t))
+    return rc;
+  if (int rc = mod_alloc(ctx)) return rc;
+  return criterion(ctx, h, logits, t, nullptr, scale, d_logits);
+}
+
 // ------------------------------------------------------------ the merged rows' criteria
 // The step's merge_grad launch (merge_grad.hip) on hop logits and do_pred the caller holds: feval's uni and select
 // rows are built from them under the feval rule and the gradient of  merge_w[0] CE(uni) + merge_w[1] CE(select)  is

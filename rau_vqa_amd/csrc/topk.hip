@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
-#include "hop_merge.h"
+#include "hop_merge.h"   // order_bits, make_key: the total order's keys
 #include "kernels.h"
 
 namespace rau {
@@ -24,16 +24,6 @@ namespace {
 
 constexpr int kStageFloats = 4096;   // 16 KiB of LDS per workgroup at the most
 constexpr int kHeadBytes = 80;       // s_key [2][4] uint64 | s_sum [4] float; the staged row follows, 16-byte aligned
-
-__device__ __forceinline__ uint32_t order_bits(float v) {
-  uint32_t u = __float_as_uint(v);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;   // NaN: after everything, -inf (0x007fffff) included
-  if (u == 0x80000000u) u = 0u;                     // -0 == +0
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ uint64_t make_key(float v, int c) {
-  return ((uint64_t)order_bits(v) << 32) | (uint64_t)(0xffffffffu - (uint32_t)c);
-}
 
 // The largest key strictly below `prev` over the workgroup; 0 (no entry has that key: it would need
 // index 0xffffffff) when there is none.  s_key is one of two alternating slots of four, so one barrier

@@ -378,7 +378,7 @@ def load_data(vqa_dir, batch_size, prefetch=False, test_batch_size=None, seed=12
     return v
 
 
-def feed(rau, batch, feat_type=None, answers=None, regions=None, att_targets=None, sample_w=None):
+def feed(rau, batch, feat_type=None, answers=None, regions=None, att_targets=None, sample_w=None, candidates=None):
     """next_batch_feat's tuple -> rau_set_batch (the H2D of SS:434-439); returns qids.
     feat_type: that of the feats (needed for bf16 and fp8, which arrive as uint16 / uint8 bits).  A tuple of
     next_batch_feat(unique=True) goes up as an image table, one of next_batch_rows as a bank batch, one of
@@ -397,7 +397,10 @@ def feed(rau, batch, feat_type=None, answers=None, regions=None, att_targets=Non
     replaces the dict's own "att_targets" key.
     sample_w = per-sample loss weights [B] of the batch (class- or question-type balancing, importance weights):
     attached with rau.set_sample_weights once the batch is up; None changes nothing.  For a dict it replaces the
-    dict's own "sample_w" key."""
+    dict's own "sample_w" key.
+    candidates = per-sample multiple-choice candidates [B, C] of the batch (VQA v1's 18 choices): attached with
+    rau.set_candidates once the batch is up; None changes nothing.  For a dict it replaces the dict's own
+    "candidates" key."""
     if isinstance(batch, dict):
         kw = {k: v for k, v in batch.items() if k != "qids"}
         if feat_type is not None:
@@ -410,6 +413,8 @@ def feed(rau, batch, feat_type=None, answers=None, regions=None, att_targets=Non
             kw.pop("att_targets", None)
         if sample_w is not None:
             kw.pop("sample_w", None)
+        if candidates is not None:
+            kw.pop("candidates", None)
         rau.set_batch(**kw)
         qids = batch.get("qids")
     else:
@@ -422,6 +427,8 @@ def feed(rau, batch, feat_type=None, answers=None, regions=None, att_targets=Non
         rau.set_att_targets(att_targets)
     if sample_w is not None:
         rau.set_sample_weights(sample_w)
+    if candidates is not None:
+        rau.set_candidates(candidates)
     return qids
 
 
@@ -461,6 +468,8 @@ class SlotFeeder:
 
     sample_w: a callable qids -> per-sample loss weights [B] (None: no weights); the weights go up behind every
     batch's upload, on the copy stream (rau.set_sample_weights(slot=)).
+    candidates: a callable qids -> multiple-choice candidates [B, C] (None: none); they go up the same way
+    (rau.set_candidates(slot=)).
 
     A feeder is BOUND to one batch size, the DataClass's: if the context runs another size when the
     feeder is made (a test split at test_batch_size below the capacity) it is switched first
@@ -469,9 +478,11 @@ class SlotFeeder:
     """
 
     def __init__(self, rau, data: DataClass, tab_featpaths, feat_dim, feat_w=1, feat_h=1,
-                 feat_type=None, share_images=False, bank=False, packed=False, sample_w=None):
+                 feat_type=None, share_images=False, bank=False, packed=False, sample_w=None,
+                 candidates=None):
         self.rau, self.data = rau, data
         self.sample_w = sample_w
+        self.candidates = candidates
         self.n = int(data.batch_size)
         if getattr(rau, "batch_size", self.n) != self.n:
             rau.set_batch_size(self.n)     # raises above the capacity
@@ -517,6 +528,8 @@ class SlotFeeder:
                 rau.set_regions(d.last_regions, slot=s)
             if self.sample_w is not None:
                 rau.set_sample_weights(self.sample_w(qids), slot=s)
+            if self.candidates is not None:
+                rau.set_candidates(self.candidates(qids), slot=s)
             rau.use_batch(s)
             return qids
         batch = d.next_batch_feat(*self.args, unique=self.share_images, packed=self.packed)
@@ -543,6 +556,8 @@ class SlotFeeder:
             rau.set_regions(d.last_regions, slot=s)          # table (a packed batch brought its own)
         if self.sample_w is not None:                 # ... and per-sample loss weights, looked up by question id
             rau.set_sample_weights(self.sample_w(qids), slot=s)
+        if self.candidates is not None:               # ... and multiple-choice candidates, the same way
+            rau.set_candidates(self.candidates(qids), slot=s)
         rau.use_batch(s)
         return qids
 

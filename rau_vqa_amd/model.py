@@ -484,6 +484,68 @@ class RAU:
         L.check(self._lib.rau_batch_sample_weights(self._h, C.byref(v)))
         return bool(v.value)
 
+    # ---- multiple-choice candidates: the criterion restricted to them (rau_set_candidates)
+    MAX_CANDIDATES = 32
+
+    def _candidates(self, cand, B):
+        """cand as int32 [B, C], checked on the host: shape, 1 <= C <= 32, ids in 0..K."""
+        cand = np.ascontiguousarray(cand, np.int32)
+        if cand.ndim != 2 or cand.shape[0] != B:
+            raise ValueError(f"candidates must be [{B}, C], one list per sample")
+        if not 1 <= cand.shape[1] <= self.MAX_CANDIDATES:
+            raise ValueError(f"candidates: C={cand.shape[1]} out of [1, {self.MAX_CANDIDATES}]")
+        if cand.min() < 0 or cand.max() > self.cfg.K:
+            raise ValueError(f"candidates: an id outside [0, {self.cfg.K}] (0 = empty entry)")
+        return cand
+
+    def set_candidates(self, cand, slot=None):
+        """Give the batch in `slot` (None: the resident batch; 0 | 1: after set_batch_async(slot), before
+        use_batch(slot)) multiple-choice candidates cand [batch, C] int (1..K, 0 = empty entry; a duplicate counts
+        once), C <= 32 -- VQA v1's 18 choices, Visual7W's four.  The criterion head is then normalised over a
+        sample's candidates only (predict.cand_ce / cand_bce state it in numpy), losses() and loss_rows() are the
+        restricted rows, cand_stats() and top_candidates() read the MC statistics and ranked MC answers; argmax(),
+        step_stats()' counts, predict() and topk() stay open-ended.  A forward that already ran must be run again.
+        The list lasts until the next batch goes into that slot."""
+        cand = self._candidates(cand, self._n)
+        L.check(self._lib.rau_set_candidates(self._h, -1 if slot is None else int(slot), int(cand.shape[1]),
+                                             cand.ctypes.data))
+
+    def clear_candidates(self, slot=None):
+        """Detach the candidates of the batch in `slot`: the next step is the full-vocabulary one, bit for bit."""
+        L.check(self._lib.rau_set_candidates(self._h, -1 if slot is None else int(slot), 0, None))
+
+    @property
+    def batch_candidates(self) -> int:
+        """C of the resident batch's candidates, 0 when it has none."""
+        v = C.c_int32()
+        L.check(self._lib.rau_batch_candidates(self._h, C.byref(v)))
+        return int(v.value)
+
+    def cand_stats(self):
+        """MC statistics of the last forward on a batch with candidates (feval rule, as step_stats), per row of
+        {hops, uni, select}: ``loss`` [H+2] the restricted criterion (loss[:H] bitwise losses()), ``correct`` [H+2]
+        the labelled rows whose best candidate is the label or carries a positive score, ``score`` [H+2] that
+        candidate's summed metric score, and ``n_lab`` the labelled rows.  predict.cand_stats is the numpy
+        restatement."""
+        R = self.cfg.H + 2
+        loss, score = np.empty(R, np.float32), np.empty(R, np.float32)
+        correct, n = np.empty(R, np.int32), C.c_int32()
+        L.check(self._lib.rau_cand_stats(self._h, loss.ctypes.data, correct.ctypes.data, score.ctypes.data, C.byref(n)))
+        return {"loss": loss, "correct": correct, "score": score, "n_lab": int(n.value)}
+
+    def top_candidates(self, k):
+        """The k best candidates of every predict_result row of the last forward (hops, uni, select; last hop
+        forced, as predict()): (ids int32, score f32, conf f32), each [H+2, B, k], best first; conf is the softmax
+        over the row's live candidates; ranks behind their number are id 0, score -inf, conf 0.  Rank 0 is
+        predict()'s ``mc`` whenever the best candidate's logit is positive.  predict.top_candidates is the numpy
+        restatement."""
+        shape = (self.cfg.H + 2, self._n, int(k))
+        ids = np.empty(shape, np.int32)
+        score = np.empty(shape, np.float32)
+        conf = np.empty(shape, np.float32)
+        L.check(self._lib.rau_topk_cand(self._h, int(k), ids.ctypes.data, score.ctypes.data, conf.ctypes.data))
+        return ids, score, conf
+
     # ---- attention targets: supervise attprob on per-sample maps (rau_set_att_targets)
     def _att_targets(self, t, B):
         """t as float32 [B, S], checked on the host: shape, finite, >= 0."""
@@ -543,7 +605,7 @@ class RAU:
         return oe, mcs, tot
 
     def set_batch(self, feats, tokens, lens, labels=None, feat_type=None, image_of=None, bank_rows=None,
-                  answers=None, regions=None, att_targets=None, sample_w=None):
+                  answers=None, regions=None, att_targets=None, sample_w=None, candidates=None):
         """feat_type "f32" | "f16" | "bf16" | "e4m3" | "e5m2" (default: from the dtype, see feat16.infer;
         bf16 is uint16 bits, fp8 is uint8 codes, both must be named): a 16-bit or fp8 map gives the same
         results, bit for bit, as the f32 map of its widened values.
@@ -556,8 +618,11 @@ class RAU:
         regions: set_regions on the batch once it is up; per sample [B], or with image_of / bank_rows per image
         [N] (gathered here: regions_of).
         att_targets [B, S]: set_att_targets on the batch once it is up; always per sample.
-        sample_w [B]: set_sample_weights on the batch once it is up; always per sample."""
-        if regions is not None:   # checked before anything reaches the library
+        sample_w [B]: set_sample_weights on the batch once it is up; always per sample.
+        candidates [B, C]: set_candidates on the batch once it is up; always per sample."""
+        if candidates is not None:   # checked before anything reaches the library
+            candidates = self._candidates(candidates, int(np.asarray(lens).shape[0]))
+        if regions is not None:
             regions = self._sample_regions(regions, image_of, int(np.asarray(lens).shape[0]))
         if att_targets is not None:
             att_targets = self._att_targets(att_targets, int(np.asarray(lens).shape[0]))
@@ -572,6 +637,8 @@ class RAU:
             self.set_att_targets(att_targets)
         if sample_w is not None:
             self.set_sample_weights(sample_w)
+        if candidates is not None:
+            self.set_candidates(candidates)
 
     def _packed(self, rows, counts, image_of, B, feat_type):
         """(rows or None, feat type, n_maps, counts, image_of or None) of a packed batch of B samples, checked on
@@ -592,15 +659,19 @@ class RAU:
             raise ValueError(f"packed rows {rows.shape} are not [sum(counts)={int(counts.sum())}, D={c.D}]")
         return rows, ft, int(counts.size), counts, image_of
 
-    def set_batch_packed(self, rows, counts, tokens, lens, labels=None, feat_type=None, image_of=None):
+    def set_batch_packed(self, rows, counts, tokens, lens, labels=None, feat_type=None, image_of=None,
+                         candidates=None):
         """A batch of region features as the files store them: rows [sum(counts), D], one row per box, map i
         owning counts[i] consecutive rows (1..S).  Only the rows cross the link; the device transposes and
         zero-pads them and the counts become the batch's region counts.  The same results, bit for bit, as
         set_batch(feat16.unpack_regions(rows, counts, S), ..., regions=counts).  image_of [B]: the maps are an
-        image table of len(counts) maps (counts per IMAGE).  feat_type as in set_batch."""
+        image table of len(counts) maps (counts per IMAGE).  feat_type as in set_batch.  candidates [B, C]:
+        set_candidates on the batch once it is up."""
         c = self.cfg
         lens = np.ascontiguousarray(lens, np.int32)
         B = self._rows(lens, "set_batch_packed")
+        if candidates is not None:
+            candidates = self._candidates(candidates, B)
         rows, ft, n_maps, counts, image_of = self._packed(rows, counts, image_of, B, feat_type)
         if rows is None:
             raise ValueError("set_batch_packed needs rows")
@@ -618,6 +689,8 @@ class RAU:
         L.check(self._lib.rau_set_batch_packed(self._h, rows.ctypes.data, feat16.FEAT_TYPES[ft], n_maps,
                                                counts.ctypes.data, None if image_of is None else image_of.ctypes.data,
                                                tokens.ctypes.data, lens.ctypes.data, lp))
+        if candidates is not None:
+            self.set_candidates(candidates)
 
     def _set_batch(self, feats, tokens, lens, labels, feat_type, image_of, bank_rows):
         c = self.cfg
@@ -700,7 +773,7 @@ class RAU:
 
     def set_batch_async(self, slot, feats=None, tokens=None, lens=None, labels=None, has_labels=True,
                         feat_type=None, image_of=None, n_images=None, bank_rows=None, answers=None,
-                        regions=None, att_targets=None, packed_counts=None, sample_w=None):
+                        regions=None, att_targets=None, packed_counts=None, sample_w=None, candidates=None):
         """Enqueue the upload of a batch into `slot` on the copy stream and return.  Arrays left None
         are taken from the slot's staging (filled in place through batch_slot).  feat_type: as in
         set_batch; with feats None it names what the staging holds (default "f32").
@@ -715,7 +788,10 @@ class RAU:
         packed_counts [N]: feats is packed region rows [sum(packed_counts), D] (see set_batch_packed), or, with
         feats None, the slot's staging holds them at its start (batch_slot(...)["feats"] viewed flat); N is the
         batch size, or with image_of the number of maps.  The counts become the batch's region counts.
-        sample_w [B]: set_sample_weights(slot=slot) behind the upload."""
+        sample_w [B]: set_sample_weights(slot=slot) behind the upload.
+        candidates [B, C]: set_candidates(slot=slot) behind the upload."""
+        if candidates is not None:
+            candidates = self._candidates(candidates, self._n if lens is None else int(np.asarray(lens).shape[0]))
         if packed_counts is not None and (regions is not None or bank_rows is not None):
             raise ValueError("a packed batch brings its own region counts and its own rows")
         if regions is not None:
@@ -735,6 +811,8 @@ class RAU:
             self.set_att_targets(att_targets, slot=slot)
         if sample_w is not None:
             self.set_sample_weights(sample_w, slot=slot)
+        if candidates is not None:
+            self.set_candidates(candidates, slot=slot)
 
     def _set_batch_async(self, slot, feats, tokens, lens, labels, has_labels, feat_type, image_of, n_images,
                          bank_rows, packed_counts=None):
@@ -995,7 +1073,7 @@ class RAU:
         return device_view(p.value, n * Q, self.cfg.device_id).view(n, Q)
 
     def set_batch_dev(self, feats_cuda, tokens, lens, labels=None, answers=None, regions=None, att_targets=None,
-                      image_of=None, question=None, sample_w=None):
+                      image_of=None, question=None, sample_w=None, candidates=None):
         """set_batch with the maps already on the device: feats_cuda a contiguous float32 CUDA torch tensor
         [n,D,S] on the ctx's device (rau_set_batch_dev: one copy on the ctx's stream, no host synchronisation).
         The ctx's stream must be ordered behind the stream that wrote the tensor (autograd.step's docstring shows
@@ -1003,7 +1081,8 @@ class RAU:
         in set_batch.  image_of [n] (0-based rows): feats_cuda is an image TABLE [N,D,S] (rau_set_batch_dev_images);
         regions may then be per image [N].  question: a CUDA tensor [n,Q] attached behind the upload (set_question);
         tokens / lens may then be None -- the step does not read them, and id 1 with length 1 is uploaded.
-        sample_w [n]: set_sample_weights behind the upload."""
+        sample_w [n]: set_sample_weights behind the upload.
+        candidates [n, C]: set_candidates behind the upload."""
         import torch
         c = self.cfg
         if question is not None and (tokens is None or lens is None):
@@ -1039,6 +1118,8 @@ class RAU:
             att_targets = self._att_targets(att_targets, B)
         if sample_w is not None:
             sample_w = self._sample_weights(sample_w, B)
+        if candidates is not None:
+            candidates = self._candidates(candidates, B)
         if B != self._n:
             self.set_batch_size(B)
         if image_of is not None:
@@ -1054,6 +1135,8 @@ class RAU:
             self.set_att_targets(att_targets)
         if sample_w is not None:
             self.set_sample_weights(sample_w)
+        if candidates is not None:
+            self.set_candidates(candidates)
         if question is not None:
             self.set_question(question)
 

@@ -151,6 +151,37 @@ class BCECriterionClone(_Clone):
         return self._view(out, self.rau.batch_size, self.rau.cfg.K)
 
 
+class CandCriterionClone(_Clone):
+    """criteria[h] restricted to multiple-choice candidates (rau_criterion_forward_cand / _backward_cand;
+    predict.cand_ce / cand_bce): cand [B,C] int32 CUDA tensor (1..K, 0 = empty entry), y [B] int32 labels or y None
+    with answers = (ids [B,G] int32, w [B,G] float32); kind "ce" or "bce"."""
+
+    KINDS = {"ce": 0, "bce": 1}
+
+    @staticmethod
+    def _cand(cand):
+        if cand.dtype != torch.int32 or cand.dim() != 2 or not cand.is_contiguous():
+            raise ValueError("candidates: a contiguous int32 [B,C] tensor")
+        if not 1 <= cand.shape[1] <= 32:
+            raise ValueError(f"candidates: C={cand.shape[1]} out of [1, 32]")
+        return int(cand.shape[1])
+
+    def forward(self, logits, y, cand, answers=None, kind="ce"):
+        G, ids, w = BCECriterionClone._set(y, answers)
+        loss = C.c_float()
+        L.check(self._lib.rau_criterion_forward_cand(self._h, self.i, _p(logits), _p(y), G, _p(ids), _p(w),
+                                                     self._cand(cand), _p(cand), self.KINDS[kind], C.byref(loss)))
+        return loss.value
+
+    def backward(self, logits, y, cand, answers=None, kind="ce", scale=1.0):
+        G, ids, w = BCECriterionClone._set(y, answers)
+        out = C.c_void_p()
+        L.check(self._lib.rau_criterion_backward_cand(self._h, self.i, _p(logits), _p(y), G, _p(ids), _p(w),
+                                                      self._cand(cand), _p(cand), self.KINDS[kind], float(scale),
+                                                      C.byref(out)))
+        return self._view(out, self.rau.batch_size, self.rau.cfg.K)
+
+
 class AttCriterionClone(_Clone):
     """The attention supervision of hop h on the clone's attprob output: mean_b sum_s t (-log(attprob + 1e-12))
     against targets t [B,S] (float32 CUDA tensor), regions [B] int32 or None (joint.att_ce / att_ce_grad)."""
@@ -194,7 +225,7 @@ def scale_rows(rau, x, s):
 
 
 def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None, merge_w=None,
-          loss="ce", answers=None, sample_w=None):
+          loss="ce", answers=None, sample_w=None, candidates=None):
     """The tensor half of the reference's feval, loop for loop (SS:443-596), on the clones.
     select_w [H] (None: the reference's zero, SS:566): hop h's multimodal clone receives
     d_do_pred = joint.bce_grad(do_pred_h, argmax_h == y, select_w[h]), which trains the step-selection head.
@@ -217,6 +248,10 @@ def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=Non
     sample_w[b] (scale_rows) before it enters the clone's backward: the objective of the step path under
     rau_set_sample_weights.  The returned losses are the criteria's own and stay unweighted.
 
+    candidates [B,C] int32 CUDA tensor (None: the full vocabulary): criteria[h] is the criterion restricted to each
+    sample's candidates (CandCriterionClone, under either loss; with answers also under "ce"); merge_w is refused
+    with them (the merged rows' terms are full-vocabulary cross-entropies).
+
     feats [B,D,S] float32, x [T,B] int32, x_len [B] int32, y [B] int32: CUDA tensors.
     Gradients accumulate into the ctx's flat buffers (zero them first).  Returns
     (losses[H], argmax[H,B] as torch tensors of 1-based ids).
@@ -224,11 +259,11 @@ def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=Non
     ext = torch.cuda.ExternalStream(rau.stream(), device=feats.device)
     with torch.cuda.stream(ext):   # torch's glue ops join the ctx's own stream order
         return _feval(rau, feats, x, x_len, y, hop_w, select_w, regions, att_w, att_targets, merge_w, loss, answers,
-                      sample_w)
+                      sample_w, candidates)
 
 
 def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None, merge_w=None,
-           loss="ce", answer_set=None, sample_w=None):
+           loss="ce", answer_set=None, sample_w=None, candidates=None):
     if loss not in ("ce", "bce"):
         raise ValueError(f"feval: loss={loss!r}: 'ce' or 'bce'")
     if rau.cfg.K % 4:   # the clones exchange dense [B,K] rows: refused here, before the encoder loop launches anything
@@ -237,6 +272,8 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=No
     bce = loss == "bce"
     if bce and merge_w is not None and any(float(w) != 0.0 for w in merge_w):
         raise ValueError("feval: merge_w is not available with loss='bce'")
+    if candidates is not None and merge_w is not None and any(float(w) != 0.0 for w in merge_w):
+        raise ValueError("feval: merge_w is not available with candidates")
     if bce and y is None and select_w is not None and any(float(w) != 0.0 for w in select_w):
         raise ValueError("feval: select_w needs labels")
     if att_w is not None and att_targets is None and any(float(w) != 0.0 for w in att_w):
@@ -254,6 +291,7 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=No
     crit = [CriterionClone(rau, h) for h in range(c.H)]
     bcrit = [BCECriterionClone(rau, h) for h in range(c.H)]
     acrit = [AttCriterionClone(rau, h) for h in range(c.H)]
+    ccrit = [CandCriterionClone(rau, h) for h in range(c.H)]
     max_len = int(x_len.max().item())                      # SS:444
     # ---- encoder forward, SS:446-462
     state = [torch.zeros(rau.batch_size, c.Q, device=dev)]            # init_state, SS:358
@@ -275,7 +313,10 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=No
         dopred.append(dp)
         att_c.append(cn)
         att_h.append(hn)
-        losses.append(bcrit[h].forward(lg, y, answer_set) if bce else crit[h].forward(lg, y))   # SS:518
+        if candidates is not None:
+            losses.append(ccrit[h].forward(lg, y, candidates, answer_set, loss))
+        else:
+            losses.append(bcrit[h].forward(lg, y, answer_set) if bce else crit[h].forward(lg, y))   # SS:518
         answers.append(torch.argmax(lg, dim=1) + 1)        # SS:488 (ties: see rau_get_argmax)
     # ---- the merged rows' criteria: every hop's scaled d_logits, plus the uni and select terms in one launch
     d_merged = None
@@ -286,7 +327,9 @@ def _feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=No
     d_c = d_h = None                                       # zeros, SS:561-562
     d_q = torch.zeros(rau.batch_size, c.Q, device=dev)
     for h in reversed(range(c.H)):
-        if bce:
+        if candidates is not None:
+            dl = ccrit[h].backward(logits[h], y, candidates, answer_set, loss, float(hop_w[h]))
+        elif bce:
             dl = bcrit[h].backward(logits[h], y, answer_set, float(hop_w[h]))
         else:
             dl = crit[h].backward(logits[h], y, float(hop_w[h])) if d_merged is None else d_merged[h]   # SS:565-569

@@ -235,6 +235,25 @@ def set_correct(ans, ids, score):
     return ok
 
 
+def feval_rows(logits, dopred):
+    """feval's merged rows of hop logits [H, B, K] float32 (SS:482-540; the last hop is NOT forced): (uni, select,
+    first) with uni = (0 + l_0 + .. + l_{H-1}) / H, select = 0 + l_first on the rows where a hop fired (the zero row
+    elsewhere) and first [B] the first hop whose do_pred > 0.5, -1 when none fires.  Bit for bit the device's rows."""
+    logits = np.asarray(logits, np.float32)
+    H, B, K = logits.shape
+    fire = np.asarray(dopred, np.float32) > 0.5
+    first = np.where(fire.any(0), fire.argmax(0), -1)              # feval: the last hop is not forced
+    uni = np.zeros((B, K), np.float32)
+    for h in range(H):
+        uni += logits[h]
+    uni = uni / np.float32(H)
+    select = np.zeros((B, K), np.float32)
+    for b in range(B):
+        if first[b] >= 0:
+            select[b] = np.float32(0) + logits[first[b], b]
+    return uni, select, first
+
+
 def set_stats(logits, dopred, ids, w, score=None, loss="ce", sample_w=None):
     """joint.feval_stats for a batch with an answer set (rau_step_stats with a set): the same keys, with
     set_correct in place of (argmax == y) and soft_ce in place of the cross-entropy, plus ``score`` [H+2, B]:
@@ -251,15 +270,7 @@ def set_stats(logits, dopred, ids, w, score=None, loss="ce", sample_w=None):
     H, B, K = logits.shape
     eps, one = np.float32(1e-12), np.float32(1)
     fire = dopred > 0.5
-    first = np.where(fire.any(0), fire.argmax(0), -1)              # feval: the last hop is not forced
-    uni = np.zeros((B, K), np.float32)
-    for h in range(H):
-        uni += logits[h]
-    uni = uni / np.float32(H)
-    select = np.zeros((B, K), np.float32)
-    for b in range(B):
-        if first[b] >= 0:
-            select[b] = np.float32(0) + logits[first[b], b]
+    uni, select, first = feval_rows(logits, dopred)
     rows = [logits[h] for h in range(H)] + [uni, select]
     ans = np.stack([first_max(r) for r in rows])
     ok = set_correct(ans, ids, score)
@@ -325,3 +336,228 @@ def predict_result_device(rau, feats, tokens, lens, mc_ans=None, select_att_stat
     tab_pred = [logits[h] for h in range(H)] + [pred[0], pred[1]]
     tab_att = [hop_att[h] for h in range(H)] + [att[0], att[1]]
     return {"tab_pred": tab_pred, "tab_att": tab_att, "oe": oe, "mc": mc, **top}
+
+
+# ---- multiple-choice candidates (rau_set_candidates): the numpy statement of the restricted criterion, the ranked
+# candidates and the MC statistics.  cand [B, C] int, 1-based answer ids, 0 = empty entry.
+
+def cand_live(cand):
+    """[B, C] bool: the live entries of a candidate list -- non-empty and equal to no EARLIER entry of the row (a
+    duplicate id counts once)."""
+    cand = np.asarray(cand, np.int64)
+    live = cand > 0
+    for c in range(1, cand.shape[1]):
+        live[:, c] &= ~(cand[:, :c] == cand[:, c:c + 1]).any(axis=1)
+    return live
+
+
+def cand_kept(cand, ids):
+    """[B, G] bool: the kept truth -- set entries (labels y: ids = y[:, None]) that are non-empty and whose id is a
+    live candidate of the row.  The others count as empty entries; a row without a kept entry is unlabelled."""
+    cand = np.asarray(cand, np.int64)
+    ids = np.asarray(ids, np.int64)
+    live = cand_live(cand)
+    inl = ((ids[:, :, None] == cand[:, None, :]) & live[:, None, :]).any(axis=2)
+    return (ids > 0) & inl
+
+
+def _cand_args(logits, cand, ids, w, sample_w, dtype):
+    x = np.asarray(logits, dtype)
+    B, K = x.shape
+    cand = np.clip(np.asarray(cand, np.int64), 0, K)
+    ids = np.clip(np.asarray(ids, np.int64), 0, K)
+    if ids.ndim == 1:
+        ids = ids[:, None]
+    w = np.ones(ids.shape, dtype) if w is None else np.asarray(w, dtype)
+    if cand.ndim != 2 or cand.shape[0] != B or ids.shape[0] != B or w.shape != ids.shape:
+        raise ValueError("cand must be [B, C], ids and w [B, G] for logits [B, K]")
+    sw = np.ones(B, dtype) if sample_w is None else np.asarray(sample_w, dtype)
+    return x, cand, ids, w, sw, cand_live(cand), cand_kept(cand, ids)
+
+
+def _cand_lse(x, cols, dtype):
+    """m, lse of x over the columns `cols` (entry order): den added from +0 in that order, each step rounded once"""
+    m = x[cols].max()
+    den = dtype(0)
+    for c in cols:
+        den = dtype(den + np.exp(dtype(x[c] - m)))
+    return m, dtype(m + np.log(den))
+
+
+def cand_ce(logits, cand, ids, w=None, sample_w=None, dtype=np.float32):
+    """The softmax criterion restricted to candidates (rau_set_candidates) on rows logits [B, K] against the answer
+    set ids / w [B, G] (labels y [B]: ids = y, w = None): (rows [B], their mean) with, over the live candidates L of
+    a row in entry order, m = max x_c, den = sum expf(x_c - m), lse = m + log(den) and rows[b] = s_b * sum_g w_g
+    (lse - x[y_g]) over the KEPT entries (cand_kept) from 0 in g order.  A row without a kept entry: 0.  Every step
+    in `dtype` and in the device's order; exp and log are numpy's, so float32 is a reference to a few ulp."""
+    x, cand, ids, w, sw, live, kept = _cand_args(logits, cand, ids, w, sample_w, dtype)
+    B = x.shape[0]
+    rows = np.zeros(B, dtype)
+    for b in range(B):
+        if not kept[b].any():
+            continue
+        _, lse = _cand_lse(x[b], cand[b][live[b]] - 1, dtype)
+        acc = dtype(0)
+        for g in np.nonzero(kept[b])[0]:
+            acc = dtype(acc + dtype(w[b, g] * dtype(lse - x[b, ids[b, g] - 1])))
+        rows[b] = dtype(sw[b] * acc)
+    return rows, dtype(rows.sum(dtype=dtype) / dtype(B))
+
+
+def cand_ce_grad(logits, cand, ids, w=None, sample_w=None, dtype=np.float32):
+    """d mean(cand_ce rows) / d logits [B, K] as the device forms it: for k in L expf(x_k - lse) (W invB), then for
+    the kept g in order: if (y_g == k) -= w_g invB, the first match inside a fused multiply-add; +0 outside L and on
+    rows without a kept entry.  invB = s_b * (1 / B), W = the kept weights added in order."""
+    x, cand, ids, w, sw, live, kept = _cand_args(logits, cand, ids, w, sample_w, dtype)
+    B = x.shape[0]
+    g_out = np.zeros(x.shape, dtype)
+    for b in range(B):
+        if not kept[b].any():
+            continue
+        cols = cand[b][live[b]] - 1
+        _, lse = _cand_lse(x[b], cols, dtype)
+        invB = dtype(sw[b] * dtype(dtype(1) / dtype(B)))
+        W = dtype(0)
+        for g in np.nonzero(kept[b])[0]:
+            W = dtype(W + w[b, g])
+        scale = dtype(W * invB)
+        for k in cols:
+            e = np.exp(dtype(x[b, k] - lse))
+            p, hit = dtype(e * scale), False
+            for g in np.nonzero(kept[b])[0]:
+                if ids[b, g] - 1 == k:
+                    wb = dtype(w[b, g] * invB)
+                    p = dtype(p - wb) if hit else dtype(np.float64(e) * np.float64(scale) - np.float64(wb))
+                    hit = True
+            g_out[b, k] = p
+    return g_out
+
+
+def _cand_bce_rows(x, cand, ids, w, live, kept, b, dtype):
+    """(cols, t, e) of row b: its live candidates' columns, their targets over the kept entries, expf(-|x|)"""
+    cols = cand[b][live[b]] - 1
+    t = np.zeros(len(cols), dtype)
+    for i, k in enumerate(cols):
+        for g in np.nonzero(kept[b])[0]:
+            if ids[b, g] - 1 == k:
+                t[i] = dtype(t[i] + w[b, g])
+    return cols, np.minimum(t, dtype(1)), np.exp(-np.abs(x[b, cols]))
+
+
+def cand_bce(logits, cand, ids, w=None, sample_w=None, dtype=np.float32):
+    """The per-answer sigmoid criterion restricted to candidates: (rows [B], their mean) with rows[b] = s_b *
+    sum_{c in L} (max(x_c,0) - x_c t_c) + log1p(exp(-|x_c|)), added from 0 in entry order, t_c = min(1, the kept
+    matching weights added in order).  A row without a kept entry is unlabelled: 0."""
+    x, cand, ids, w, sw, live, kept = _cand_args(logits, cand, ids, w, sample_w, dtype)
+    B = x.shape[0]
+    rows = np.zeros(B, dtype)
+    for b in range(B):
+        if not kept[b].any():
+            continue
+        cols, t, e = _cand_bce_rows(x, cand, ids, w, live, kept, b, dtype)
+        xc = x[b, cols]
+        term = ((np.maximum(xc, 0) - (xc * t).astype(dtype)).astype(dtype) + np.log1p(e)).astype(dtype)
+        acc = dtype(0)
+        for v in term:
+            acc = dtype(acc + v)
+        rows[b] = dtype(sw[b] * acc)
+    return rows, dtype(rows.sum(dtype=dtype) / dtype(B))
+
+
+def cand_bce_grad(logits, cand, ids, w=None, sample_w=None, dtype=np.float32):
+    """d mean(cand_bce rows) / d logits [B, K]: (sigmoid(x_c) - t_c) invB at the live candidates' columns, the sigmoid
+    from e = exp(-|x|) as x >= 0 ? 1 / (1 + e) : e / (1 + e); +0 elsewhere and on unlabelled rows."""
+    x, cand, ids, w, sw, live, kept = _cand_args(logits, cand, ids, w, sample_w, dtype)
+    B = x.shape[0]
+    g_out = np.zeros(x.shape, dtype)
+    for b in range(B):
+        if not kept[b].any():
+            continue
+        cols, t, e = _cand_bce_rows(x, cand, ids, w, live, kept, b, dtype)
+        xc = x[b, cols]
+        d = (dtype(1) + e).astype(dtype)
+        sg = np.where(xc >= 0, dtype(1) / d, e / d).astype(dtype)
+        invB = dtype(sw[b] * dtype(dtype(1) / dtype(B)))
+        g_out[b, cols] = ((sg - t).astype(dtype) * invB).astype(dtype)
+    return g_out
+
+
+def top_candidates(tab_pred, cand, k):
+    """The k best CANDIDATES of every row of tab_pred ([R, B, K] or a list of R [B, K] arrays, the merged rows
+    top_answers reads): (ids int32 1-based, score f32, conf f32), each [R, B, k] -- the numpy statement of
+    rau_topk_cand.  A row's live candidates (cand_live) are ranked among themselves in top_answers' total order
+    (rank_key: larger value first, ties by the lower answer id, NaN last); score is the row's entry, bit for bit;
+    conf = exp(v - m) / sum_{c in L} exp(x_c - m) in float64, rounded to f32 at the end.  Ranks at and behind the
+    number of live candidates: id 0, score -inf, conf 0.  Rank 0 is the first maximum of the candidates' logits; the
+    reference's multiply rule (answers(tab_pred, mc_ans)) agrees with it whenever that logit is positive."""
+    x = np.ascontiguousarray(np.stack([np.asarray(p, np.float32) for p in tab_pred]))
+    R, B, K = x.shape
+    cand = np.asarray(cand, np.int64)
+    if cand.ndim != 2 or cand.shape[0] != B:
+        raise ValueError(f"cand must be [{B}, C]")
+    C = cand.shape[1]
+    if not 1 <= k <= C:
+        raise ValueError(f"k={k} out of [1,{C}]")
+    if cand.min() < 0 or cand.max() > K:
+        raise ValueError(f"candidate id outside [0,{K}]")
+    live = cand_live(cand)
+    key = rank_key(x)
+    ids = np.zeros((R, B, k), np.int32)
+    score = np.full((R, B, k), -np.inf, np.float32)
+    conf = np.zeros((R, B, k), np.float32)
+    for b in range(B):
+        cols = cand[b][live[b]] - 1
+        if len(cols) == 0:
+            continue
+        for r in range(R):
+            order = cols[np.argsort(~key[r, b, cols], kind="stable")]
+            v = x[r, b, order]
+            n = min(k, len(order))
+            ids[r, b, :n] = order[:n] + 1
+            score[r, b, :n] = v[:n]
+            with np.errstate(invalid="ignore", over="ignore"):
+                v64 = x[r, b, cols].astype(np.float64)
+                m = v64.max()
+                conf[r, b, :n] = (np.exp(v[:n].astype(np.float64) - m) / np.exp(v64 - m).sum()).astype(np.float32)
+    return ids, score, conf
+
+
+def _wave_total(x):
+    """Sum over the last axis in the order of the device's batch totals (rau_step_scores, rau_cand_stats): 64 partials,
+    partial l adding the entries l, l + 64, .. in ascending order from 0, then an xor butterfly (offsets 32 .. 1)."""
+    x = np.asarray(x, np.float32)
+    pad = (-x.shape[-1]) % 64
+    x = np.concatenate([x, np.zeros(x.shape[:-1] + (pad,), np.float32)], axis=-1).reshape(x.shape[:-1] + (-1, 64))
+    v = np.zeros(x.shape[:-2] + (64,), np.float32)
+    for i in range(x.shape[-2]):
+        v = v + x[..., i, :]
+    lane = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[..., lane ^ o]
+    return v[..., 0]
+
+
+def cand_stats(logits, dopred, cand, ids, w=None, score=None, loss="ce", sample_w=None):
+    """The MC statistics of a step on a batch with candidates (rau_cand_stats), feval rule: for every row of
+    {hops, uni, select} (feval_rows) ``loss`` [H+2] = the mean of cand_ce (loss="bce": cand_bce) with the sample
+    weights, ``correct`` [H+2] = the labelled rows whose rank-0 candidate (top_candidates) carries a positive score in
+    the set, ``score`` [H+2] = that candidate's summed metric score (added in the device's fixed order), ``n_lab`` = the rows with a kept truth entry,
+    ``ans`` [H+2, B] the rank-0 candidates.  Labels y [B]: ids = y, w = score = None (weight and score 1)."""
+    if loss not in ("ce", "bce"):
+        raise ValueError(f"loss={loss!r}: 'ce' or 'bce'")
+    logits = np.asarray(logits, np.float32)
+    H, B, K = logits.shape
+    ids = np.asarray(ids, np.int64)
+    if ids.ndim == 1:
+        ids = ids[:, None]
+    w = np.ones(ids.shape, np.float32) if w is None else np.asarray(w, np.float32)
+    score = np.asarray(w if score is None else score, np.float32)
+    uni, select, _ = feval_rows(logits, dopred)
+    rows = [logits[h] for h in range(H)] + [uni, select]
+    row_loss = cand_bce if loss == "bce" else cand_ce
+    lab = cand_kept(cand, ids).any(axis=1)
+    ans = top_candidates(rows, cand, 1)[0][:, :, 0]
+    sc = np.where(lab[None, :], answer_score(ans, ids, score), np.float32(0)).astype(np.float32)
+    return {"loss": np.array([row_loss(r, cand, ids, w, sample_w)[1] for r in rows], np.float32),
+            "correct": (sc > 0).sum(1).astype(np.int32), "score": _wave_total(sc),
+            "n_lab": int(lab.sum()), "ans": ans}
