@@ -438,7 +438,8 @@ int rau_use_batch(rau_ctx* ctx, int slot);
  * rau_backward or rau_step_stats.  A batch without a set computes bit for bit what it did before sets existed.
  * With lse the row's log-sum-exp, invB = 1/n and W_b = sum_g w[b,g] over the non-empty entries in order g = 0..G-1:
  *   loss row   sum_g w[b,g] (lse - logit[y_g]), accumulated from 0 in g order (rau_get_losses: their mean over n)
- *   d_logits   expf(logit[k] - lse) (W_b invB), then for g = 0..G-1 in order: if (ids[b,g] - 1 == k) -= w[b,g] invB
+ *   d_logits   (expf(logit[k] - mx) / den) (W_b invB) -- mx the row's maximum, den = sum_k expf(logit[k] - mx), so that
+ *              the probabilities of a row at |logit| ~ 1e4 still sum to 1 --, then for g = 0..G-1 in order: if (ids[b,g] - 1 == k) -= w[b,g] invB
  * every step's rounding is fixed (ce_set.hip: the first matching entry of a logit is subtracted inside the product's
  * fused multiply-add, as the label path does), so duplicates are deterministic and G = 1, w = 1 gives the bits of
  * the label path.  rau_graph_step keys its cache by G: a step captured without a set, or with another G, is never replayed.
@@ -540,7 +541,7 @@ int rau_batch_sample_weights(rau_ctx* ctx, int* has);
  *   softmax     m = max_{c in L} x_c; den = sum_{c in L} expf(x_c - m), added from +0 in entry order; lse = m + logf(den);
  *               W = the kept weights added in entry order
  *               loss row   sum_g w_g (lse - x[y_g]) over the kept entries in order, times s_b last
- *               d_logits   k in L: expf(x_k - lse) (W invB), then for the kept g in order: if (y_g == k) -= w_g invB
+ *               d_logits   k in L: (expf(x_k - m) / den) (W invB), then for the kept g in order: if (y_g == k) -= w_g invB
  *                          (the first match inside the product's fused multiply-add, as at rau_set_answers);
  *                          k not in L: +0.  A row without a kept entry is unlabelled.
  *   sigmoid     (RAU_LOSS_BCE) t_c = min(1, the kept matching weights added in order);
@@ -705,7 +706,7 @@ int rau_att_stats(rau_ctx* ctx, float* loss /* [H] */, float* mass /* [H] */, in
  * hsel the first hop whose do_pred > 0.5 -- the FEVAL rule: the last hop is not forced, and a row on which no hop
  * fired has the constant zero row.  So the two terms are the numbers rau_step_stats reports; there is no new getter.
  * CE is the criterion's own against the forward's labels or answer set (rau_set_answers: the soft-target CE).
- * With g(row)[b,k] = d CE(row) / d row[b,k] -- expf(row[k] - lse) (W_b invB), then for each matching entry in order
+ * With g(row)[b,k] = d CE(row) / d row[b,k] -- (expf(row[k] - mx) / den) (W_b invB), then for each matching entry in order
  * -= w[b,g] invB, the rule and the roundings at rau_set_answers; a label is the set {y} with weight 1; invB = 1/n --
  * the gradient at the hop logits, added to d_logits[h] behind its scaling by hop_w[h] and in front of everything
  * that consumes it (the classifier's input, weight and bias gradients; with select_w the head's addend):

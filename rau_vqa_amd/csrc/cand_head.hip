@@ -8,7 +8,7 @@
 //   softmax     m = max_{c in L} x_c;  den = sum_{c in L} expf(x_c - m) added from +0 in entry order;
 //               lse = m + logf(den);  W = the kept weights added from +0 in entry order
 //               lossrow = sum_g w_g (lse - x[y_g]) over the kept entries, from +0 in entry order
-//               dl[k]   = expf(x_k - lse) (W invB), then for the kept g in order: if (y_g == k) dl[k] -= w_g invB
+//               dl[k]   = (expf(x_k - m) / den) (W invB), then for the kept g in order: if (y_g == k) dl[k] -= w_g invB
 //               for k in L, +0 elsewhere; a row without a kept entry is unlabelled: lossrow 0, dl +0
 //   sigmoid     t_c = bce_target over the kept entries;  lossrow = sum_{c in L} bce_term(x_c, t_c, expf(-|x_c|)) from
 //               +0 in entry order;  dl[k_c] = (sigmoid(x_c) - t_c) invB, +0 elsewhere; a row is labelled when its
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void k_cand_fwd(int nB, int K, int M, const fl
         for (int g = 0; g < ng; ++g) W = __fadd_rn(W, s_w[g]);
         const float scale = __fmul_rn(W, invB);
         if (mine >= 0) {
-          const float e = expf(s_x[tid] - lse);
+          const float e = s_e[tid] / den;   // expf(x - m) / den, as the full-vocabulary heads form it
           float p = __fmul_rn(e, scale);
           bool hit = false;
           for (int g = 0; g < ng; ++g)

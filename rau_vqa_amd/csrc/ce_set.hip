@@ -3,7 +3,7 @@
 // do_pred; chain priority) with a soft target in place of the one label.  A row's set is G entries (ids 1..K,
 // 0 = empty; weights w >= 0).  With W = sum of the non-empty weights in entry order:
 //   lossrow = sum_g w_g (lse - lg[y_g])                       accumulated from 0 in entry order
-//   dl[k]   = expf(lg[k] - lse) (W invB), then for g = 0..G-1 in order: if (y_g == k) dl[k] -= w_g invB
+//   dl[k]   = (expf(lg[k] - mx) / den) (W invB), then for g = 0..G-1 in order: if (y_g == k) dl[k] -= w_g invB
 // With a sample weight s_b (rau_set_sample_weights) invB is __fmul_rn(s_b, 1 / Bper) in both products and the loss
 // row written is __fmul_rn(s_b, lossrow); without weights s_b = 1 and both are exact.  One load per workgroup.
 // The rounding of every step is spelled out, so duplicates are deterministic: the products w_g invB, W invB and
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void k_ce_set_fwd(int nB, int K, int M, const 
   for (int g = 0; g < G; ++g) W = __fadd_rn(W, s_w[g]);
   const float scale = __fmul_rn(W, invB);
   for (int k = tid; k < K; k += 256) {
-    const float e = expf(lg[k] - lse);
+    const float e = expf(lg[k] - mx) / den;
     float p = __fmul_rn(e, scale);
     bool hit = false;
     for (int g = 0; g < G; ++g)

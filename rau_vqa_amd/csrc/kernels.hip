@@ -1896,7 +1896,9 @@ __global__ void k_ce_fwd(int nB, int K, int M, const float* __restrict__ logits,
     const float sb = sw ? sw[b % Bper] : 1.f;
     const float invB = __fmul_rn(sb, 1.f / (float)Bper);
     for (int k = tid; k < K; k += 256) {
-      float p = expf(lg[k] - lse) * invB;
+      // the probability as expf(x - mx) / den, not expf(x - lse): at |x| ~ 1e4 lse has an ulp of 1e-3, and a row
+      // of equal logits then misses sum p = 1 by 1e-4 (tests/test_gpu_range.py)
+      float p = (expf(lg[k] - mx) / den) * invB;
       if (k == y) p -= invB;
       dl[(size_t)b * ld + k] = p;
     }

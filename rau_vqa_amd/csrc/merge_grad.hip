@@ -8,9 +8,9 @@
 // The rows are hop_merge.h's row_val(r = H) / row_val(r = H + 1) under select_hop(force_last = false) -- the feval
 // rule, the bits rau_step_stats reads -- and g(row) is the criterion's own gradient at that row, ce_set.hip's
 // formulation with every rounding spelled out:
-//   g[k] = expf(row[k] - lse) (W invB), then for g = 0..G-1 in order: if (y_g == k) g[k] -= w_g invB
+//   g[k] = (expf(row[k] - mx) / den) (W invB), then for g = 0..G-1 in order: if (y_g == k) g[k] -= w_g invB
 // (the first matching entry inside the product's fused multiply-add); a label is the set {y} with w = 1, which gives
-// k_ce_fwd's  expf(row[k] - lse) invB - [k == y] invB.  With a sample weight s_b (rau_set_sample_weights) invB is
+// k_ce_fwd's  (expf(row[k] - mx) / den) invB - [k == y] invB.  With a sample weight s_b (rau_set_sample_weights) invB is
 // __fmul_rn(s_b, 1 / B) in both products, as in the criterion heads; without weights s_b = 1 and it is 1 / B exactly.
 // The update of one element, each step rounded once:
 //   x = dl[h,b,k];  x = x + (w_uni / H) g_u[k];  if (h == hsel) x = x + w_sel g_s[k]
@@ -78,8 +78,8 @@ __global__ __launch_bounds__(kMT) void k_merge_grad(int H, int B, int K, int ld,
   float W = 0.f;
   for (int g = 0; g < Gs; ++g) W = __fadd_rn(W, s_w[g]);
   const float scale = __fmul_rn(W, invB);
-  // ---- pass 1: the rows, their max and log-sum-exp in row_ce's order
-  float lse[2] = {0.f, 0.f};
+  // ---- pass 1: the rows, their max and softmax denominator in row_ce's order
+  float rmx[2] = {0.f, 0.f}, rden[2] = {1.f, 1.f};
   for (int r = 0; r < 2; ++r) {
     if (!term[r]) continue;
     float mx = -INFINITY;
@@ -94,7 +94,8 @@ __global__ __launch_bounds__(kMT) void k_merge_grad(int H, int B, int K, int ld,
     for (int k = tid; k < K; k += kMT)   // (a thread re-reads the entries it staged itself)
       den += expf((kStage ? s_rows[(size_t)r * ld + k] : row_val(lg, hs, H, H + r, hsel, k)) - mx);
     den = block_sum(den, s_sum);   // its barriers also publish the staged row to the workgroup
-    lse[r] = mx + logf(den);
+    rmx[r] = mx;
+    rden[r] = den;
   }
   // ---- pass 2: dl[h,b,:] of every hop that receives a term
   const float cu = __fdiv_rn(wu, (float)H);
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(kMT) void k_merge_grad(int H, int B, int K, int ld,
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (kRag && k0 + j >= K) continue;   // a pad lane: no term (g stays 0; what v holds there is not a logit)
-        const float e = expf(v[j] - lse[r]);
+        const float e = expf(v[j] - rmx[r]) / rden[r];
         float p = __fmul_rn(e, scale);
         bool hit = false;
         for (int a = 0; a < Gs; ++a)

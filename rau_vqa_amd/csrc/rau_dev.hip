@@ -75,6 +75,8 @@ __global__ void k_rowmax(int cols, const float* __restrict__ x, float* __restric
     if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
   }
   if (threadIdx.x == 0) {
+    // no element above -inf: the first index, the one rau_dev_topk ranks first on such a row
+    if (bi == 0x7fffffff) bi = 0;
     if (mv) mv[blockIdx.x] = best;
     if (mi) mi[blockIdx.x] = bi + 1;
   }

@@ -241,11 +241,11 @@ def _ce_grad_rows(row, labels, answers):
         w = np.where(ids > 0, np.asarray(answers[1], dt), dt.type(0)).astype(dt)
     invB = dt.type(1) / dt.type(B)
     mx = row.max(axis=1, keepdims=True)
-    lse = mx + np.log(np.exp(row - mx).sum(axis=1, keepdims=True, dtype=dt))
+    ex = np.exp(row - mx)
     W = np.zeros(B, dt)
     for g in range(ids.shape[1]):
         W = W + w[:, g]
-    out = (np.exp(row - lse) * (W * invB)[:, None]).astype(dt)
+    out = ((ex / ex.sum(axis=1, keepdims=True, dtype=dt)) * (W * invB)[:, None]).astype(dt)
     ar = np.arange(B)
     for g in range(ids.shape[1]):
         live = ids[:, g] > 0

@@ -376,12 +376,12 @@ def _cand_args(logits, cand, ids, w, sample_w, dtype):
 
 
 def _cand_lse(x, cols, dtype):
-    """m, lse of x over the columns `cols` (entry order): den added from +0 in that order, each step rounded once"""
+    """m, den, lse of x over the columns `cols` (entry order): den added from +0 in that order, each step rounded once"""
     m = x[cols].max()
     den = dtype(0)
     for c in cols:
         den = dtype(den + np.exp(dtype(x[c] - m)))
-    return m, dtype(m + np.log(den))
+    return m, den, dtype(m + np.log(den))
 
 
 def cand_ce(logits, cand, ids, w=None, sample_w=None, dtype=np.float32):
@@ -396,7 +396,7 @@ def cand_ce(logits, cand, ids, w=None, sample_w=None, dtype=np.float32):
     for b in range(B):
         if not kept[b].any():
             continue
-        _, lse = _cand_lse(x[b], cand[b][live[b]] - 1, dtype)
+        _, _, lse = _cand_lse(x[b], cand[b][live[b]] - 1, dtype)
         acc = dtype(0)
         for g in np.nonzero(kept[b])[0]:
             acc = dtype(acc + dtype(w[b, g] * dtype(lse - x[b, ids[b, g] - 1])))
@@ -405,7 +405,7 @@ def cand_ce(logits, cand, ids, w=None, sample_w=None, dtype=np.float32):
 
 
 def cand_ce_grad(logits, cand, ids, w=None, sample_w=None, dtype=np.float32):
-    """d mean(cand_ce rows) / d logits [B, K] as the device forms it: for k in L expf(x_k - lse) (W invB), then for
+    """d mean(cand_ce rows) / d logits [B, K] as the device forms it: for k in L (expf(x_k - m) / den) (W invB), then for
     the kept g in order: if (y_g == k) -= w_g invB, the first match inside a fused multiply-add; +0 outside L and on
     rows without a kept entry.  invB = s_b * (1 / B), W = the kept weights added in order."""
     x, cand, ids, w, sw, live, kept = _cand_args(logits, cand, ids, w, sample_w, dtype)
@@ -415,14 +415,14 @@ def cand_ce_grad(logits, cand, ids, w=None, sample_w=None, dtype=np.float32):
         if not kept[b].any():
             continue
         cols = cand[b][live[b]] - 1
-        _, lse = _cand_lse(x[b], cols, dtype)
+        m, den, _ = _cand_lse(x[b], cols, dtype)
         invB = dtype(sw[b] * dtype(dtype(1) / dtype(B)))
         W = dtype(0)
         for g in np.nonzero(kept[b])[0]:
             W = dtype(W + w[b, g])
         scale = dtype(W * invB)
         for k in cols:
-            e = np.exp(dtype(x[b, k] - lse))
+            e = dtype(np.exp(dtype(x[b, k] - m)) / den)
             p, hit = dtype(e * scale), False
             for g in np.nonzero(kept[b])[0]:
                 if ids[b, g] - 1 == k:

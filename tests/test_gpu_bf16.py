@@ -46,10 +46,11 @@ TOL_EXACT = 3e-2        # outputs, relative to their max norm
 TOL_EXACT_GRAD = 1.5e-2  # gradients, relative to the un-cancelled magnitude (module docstring)
 
 
-def run(dims, scale, mode="train", lens="ragged"):
+def run(dims, scale, mode="train", lens="ragged", problem=None):
+    """problem: a prepared (batch, params, masks) in place of util.make_problem's (tests/range_cases.py)."""
     from rau_vqa_amd.model import RAU, Config
     sh = util.shapes(dims)
-    batch, params, masks = util.make_problem(sh, lens=lens, scale=scale)
+    batch, params, masks = problem or util.make_problem(sh, lens=lens, scale=scale)
     hop_w = np.full(sh.H, float(sh.H), np.float32)
     mk = masks if mode == "train" else None
     args = (sh, params, batch["feats"], batch["tokens"], batch["lens"], batch["labels"], mk, hop_w)

@@ -40,11 +40,12 @@ def run_gpu(sh, batch, params, masks, hop_w, mode="train"):
     return out, layouts
 
 
-def check(sh, seed=123, lens="ragged", mode="train", hop_w=None, scale=None, torch_oracle=False):
+def check(sh, seed=123, lens="ragged", mode="train", hop_w=None, scale=None, torch_oracle=False, problem=None):
     """torch_oracle: take the fp64 reference from the autograd restatement (oracle/ref_torch.py,
     BLAS-backed, seconds at the model's real dimensions) instead of the C++ oracle; the two agree
-    to 1e-10 (tests/test_oracle_agree.py)."""
-    batch, params, masks = util.make_problem(sh, seed=seed, lens=lens, scale=scale)
+    to 1e-10 (tests/test_oracle_agree.py).
+    problem: a prepared (batch, params, masks) in place of util.make_problem's (tests/range_cases.py)."""
+    batch, params, masks = problem or util.make_problem(sh, seed=seed, lens=lens, scale=scale)
     if hop_w is None:
         hop_w = np.full(sh.H, float(sh.H), np.float32)
     if torch_oracle:
