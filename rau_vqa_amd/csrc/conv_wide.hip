@@ -27,7 +27,6 @@
 //     stores straight from registers: the epilogue needs no LDS and no barrier).
 // Exact f32: every output element is the same k-ordered fmaf chain as in the other two tilings
 // (bitwise equal results).
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 

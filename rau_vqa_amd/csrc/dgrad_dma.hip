@@ -32,7 +32,6 @@
 // Exact f32: every output element is the same k-ordered fmaf chain and the same epilogue arithmetic as
 // gemm_sample.hip's; results equal to f32 rounding (tools/convbench: 1 ulp in a tenth of the words -- the
 // compiler contracts the epilogue's multiply-adds differently in the two kernels).
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
@@ -324,20 +323,15 @@ constexpr int dgrad_lds_bytes(int nst) { return (nst * DSTAGE + DBM + DSP) * 4; 
 
 // Shapes it takes: 14 x 14 maps, rows a multiple of 128, reduction a multiple of 16 (>= 3 stages), 16-byte
 // aligned rows.
-// RAU_DGRAD_DMA=0 keeps the register-staged per-sample kernel (A/B knob);
-// RAU_DGRAD_DMA=2|3 selects the ring depth (default 3).
-static int dgrad_dma_mode() {
-  static const int v = [] { const char* e = std::getenv("RAU_DGRAD_DMA"); return e ? std::atoi(e) : 3; }();
-  return v;
-}
-bool dgrad_dma_ok(int M, int K, int S, long w_rs) {
-  return dgrad_dma_mode() != 0 && S == DS && M % DBM == 0 && K % DBK == 0 && K >= 3 * DBK && w_rs % 4 == 0;
+// cm.dgrad_ring: 0 keeps the register-staged per-sample kernel, 2 | 3 is the ring depth.
+bool dgrad_dma_ok(const ConvMode& cm, int M, int K, int S, long w_rs) {
+  return cm.dgrad_ring != 0 && S == DS && M % DBM == 0 && K % DBK == 0 && K >= 3 * DBK && w_rs % 4 == 0;
 }
 
-hipError_t dgrad_dma(hipStream_t st, int nB, int M, int K, int S, const float* Wt, long w_rs,
+hipError_t dgrad_dma(hipStream_t st, const ConvMode& cm, int nB, int M, int K, int S, const float* Wt, long w_rs,
                      const float* X, long x_bs, float* C, long c_bs, const float* dj, const float* av,
                      const float* Y, float* rs) {
-  if (!dgrad_dma_ok(M, K, S, w_rs) || x_bs % 4 != 0 || c_bs % 4 != 0) return hipErrorInvalidValue;
+  if (!dgrad_dma_ok(cm, M, K, S, w_rs) || x_bs % 4 != 0 || c_bs % 4 != 0) return hipErrorInvalidValue;
   if (nB == 0) return hipSuccess;
   DgradParams P{};
   P.M = M; P.K = K; P.nB = nB; P.tiles_m = M / DBM;
@@ -355,7 +349,7 @@ hipError_t dgrad_dma(hipStream_t st, int nB, int M, int K, int S, const float* W
   }();
   if (attr_err != hipSuccess) return attr_err;
   const dim3 grid(P.tiles_m * nB), block(256);
-  if (dgrad_dma_mode() == 2) hipLaunchKernelGGL((k_dgrad_dma<2>), grid, block, dgrad_lds_bytes(2), st, P);
+  if (cm.dgrad_ring == 2) hipLaunchKernelGGL((k_dgrad_dma<2>), grid, block, dgrad_lds_bytes(2), st, P);
   else hipLaunchKernelGGL((k_dgrad_dma<3>), grid, block, dgrad_lds_bytes(3), st, P);
   return hipGetLastError();
 }

@@ -58,7 +58,7 @@ static hipError_t lin_gemm(hipStream_t st, int M, int N, int K, const float* A, 
   GemmParams P = lin_params(M, N, K, A, lda, W, ldw, C, ldc, o);
   if ((long)M * N >= 128L * 128 * 256 && !o.defer_splits)
     return launch_gemm<128, 128, BK, ASRC, BSRC, EPI_LIN>(st, P, 1);
-  if (o.slab && skinny_dma_ok(o.mode.deep, M, K, lda, ldw, BSRC == SRC_RC, 1, &N, &A, &W)) {
+  if (o.slab && skinny_dma_ok(o.mode, M, K, lda, ldw, BSRC == SRC_RC, 1, &N, &A, &W)) {
     const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
     const int s = skinny_dma_splits(o.mode.deep, M, K, tiles, (size_t)N, o.slab_floats);
     if ((size_t)s * M * N <= o.slab_floats && (s > 1 || o.defer_splits)) {
@@ -115,7 +115,7 @@ static hipError_t batched_deferred(hipStream_t st, LinMode mode, int nb, int M, 
   if (nb < 1 || nb > 3) return hipErrorInvalidValue;
   {
     const int Ns[3] = {N, N, N};
-    if (skinny_dma_ok(mode.deep, M, K, lda, ldw, BSRC == SRC_RC, nb, Ns, A, W)) {
+    if (skinny_dma_ok(mode, M, K, lda, ldw, BSRC == SRC_RC, nb, Ns, A, W)) {
       const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
       const int s = skinny_dma_splits(mode.deep, M, K, nb * tiles, (size_t)nb * N, slab_floats);
       if ((size_t)nb * s * M * N <= slab_floats) {
@@ -176,7 +176,7 @@ hipError_t gemm_nt_hetero_deferred(hipStream_t st, LinMode mode, int nb, int M, 
   }
   {
     const float* As[3] = {A, A, A};
-    if (skinny_dma_ok(mode.deep, M, K, lda, ldw, false, nb, N, As, W)) {
+    if (skinny_dma_ok(mode, M, K, lda, ldw, false, nb, N, As, W)) {
       const int s = skinny_dma_splits(mode.deep, M, K, tiles, nsum, slab_floats);
       if ((size_t)s * M * nsum <= slab_floats) {
         long o2[3];

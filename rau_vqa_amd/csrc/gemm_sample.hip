@@ -21,7 +21,6 @@
 // k-major with pitches = 16 mod 32 floats (conflict-free 16-lane fragment reads), double buffered,
 // one barrier per K-step, register-staged global loads one step ahead -- the structure of
 // gemm_core.h.  Exact f32 (fmaf chains).  Used when 176 < S <= 208 and S % 4 == 0.
-#include <cstdlib>
 
 #include "common.h"
 #include "kernels.h"
@@ -234,12 +233,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_sample(const SampleParams P) {
 
 }  // namespace
 
-// which: 1 = i_embed forward, 2 = ifeatproj forward, 4 = attention dgrad, 8 = i_embed dgrad.
-// RAU_CONV_SAMPLE=<mask> selects which of them use this tiling (default below).
-bool conv_sample_ok(int S, int which) {
-  static const int mask = [] { const char* e = std::getenv("RAU_CONV_SAMPLE");
-                               return e ? std::atoi(e) : 12; }();
-  return (mask & which) && S % 4 == 0 && S > 176 && S <= SBN;
+// which: 1 = i_embed forward, 2 = ifeatproj forward, 4 = attention dgrad, 8 = i_embed dgrad;
+// cm.sample selects which of them use this tiling.
+bool conv_sample_ok(const ConvMode& cm, int S, int which) {
+  return (cm.sample & which) && S % 4 == 0 && S > 176 && S <= SBN;
 }
 
 // EPI 0: C = act(acc + bias[m]);  EPI 1: C = acc + dj[b,m] a[b,s];

@@ -29,7 +29,9 @@ bool split_span_ok(const float* slab, long nsplit, size_t per_split_floats);
 //        summation order).
 //  deep: skinny_dma.hip's stages are 32-deep where K % 64 == 0 (else 16-deep).  The depth also decides which
 //        shapes count as ragged and how many K splits a launch makes, i.e. the summation order.
-struct LinMode { int bf16 = 0; int deep = 0; };
+//  dma, ragged, align16: which problems skinny_dma.hip takes at all (skinny_dma_ok): none / no ragged shapes /
+//        only operands on 16-byte boundaries; the others keep the register-staged tile of gemm_core.h.
+struct LinMode { int bf16 = 0; int deep = 0; int dma = 1; int ragged = 1; int align16 = 0; };
 struct LinOpts {
   const float* bias = nullptr;    // + bias[n]
   const float* bias2 = nullptr;   // + bias2[n]
@@ -96,9 +98,22 @@ hipError_t gemm_tn_group_acc(hipStream_t st, const TnProblem* pr, int np, int K,
 // feature map with dropout already applied, see dropout_features; nB may be H*B)
 // bf16 != 0 (rau_dtype RAU_BF16) on the five hop-batched conv GEMMs: operands rounded to bf16
 // while staged into LDS, f32 accumulate (v_mfma_f32_32x32x16_bf16); tensors in HBM stay f32.
-hipError_t conv_embed_fwd(hipStream_t st, int nB, int D, int S, int M, const float* X,
-                          const float* WiT /* [D][M] */, const float* bi, float* I, int bf16 = 0,
-                          int one_per_cu = 0 /* cap residency at one workgroup per CU */);
+// How a conv product is formed: an argument of every launcher and of every predicate that sizes a buffer for one,
+// computed by the caller from its context (conv_mode, policy.h) -- the same record at both places.
+struct ConvMode {
+  int bf16 = 0;          // rau_dtype: 0 exact f32, 1 bf16-rounded operands, 2 split operands
+  int one_per_cu = 0;    // forward convs: cap residency at one workgroup per CU
+  int light = 0;         // conv_att_dgrad_dz: the caller's recurrence is the longer path, keep the f32 product on the
+                         // 176-register tile instead of dgrad_dma's 240 (two per CU)
+  int wide = 3;          // forward convs on the wide tiling: 1 i_embed, 2 ifeatproj
+  int wide_per_cu = 1;   // ... its workgroups per CU (1 | 2)
+  int sample = 12;       // products on the per-sample tiling (conv_sample_ok's `which`)
+  int dgrad_ring = 3;    // dgrad_dma.hip: 0 off, else its ring depth (2 | 3)
+  int wgrad_dma = 1, wgrad16 = 1;   // wgrad_dma.hip / wgrad16.hip on (else their register-staged predecessors)
+  int wgrad_groups = 0;  // wgrad_dma.hip's wave groups per workgroup (1 | 2), 0 = by shape
+};
+hipError_t conv_embed_fwd(hipStream_t st, const ConvMode& cm, int nB, int D, int S, int M, const float* X,
+                          const float* WiT /* [D][M] */, const float* bi, float* I);
 // RAU_BF16 mode with the feature maps stored as bf16 (X16 [nB][D][S] bf16; S % 4 == 0)
 hipError_t conv_embed_fwd_b16(hipStream_t st, int nB, int D, int S, int M, const void* X16,
                               const void* WiT16, const float* bi, float* I);
@@ -106,12 +121,12 @@ hipError_t conv_embed_fwd_b16(hipStream_t st, int nB, int D, int S, int M, const
 hipError_t conv_att_pre_b16(hipStream_t st, int nB, int M, int S, int A, const float* I,
                             const void* WpT16, const float* bp, float* Pout);
 // P[b,k,s] = sum_m Wp[k,m] I[b,m,s] + bp[k]   (hop-invariant half of SS:244-252)
-hipError_t conv_att_pre(hipStream_t st, int nB, int M, int S, int A, const float* I,
-                        const float* WpT /* [M][A] */, const float* bp, float* P, int bf16 = 0,
-                        int one_per_cu = 0);
+hipError_t conv_att_pre(hipStream_t st, const ConvMode& cm, int nB, int M, int S, int A, const float* I,
+                        const float* WpT /* [M][A] */, const float* bp, float* P);
 // Same three products with one sample per tile (gemm_sample.hip), used for 14 x 14 maps:
 // C[b,m,s] = epi(sum_k Wt[k,m] X[b,k,s]); epi 0: act(. + bias[m]), epi 1: . + dj[b,m] a[b,s]
-bool conv_sample_ok(int S, int which);
+// which: 1 = i_embed forward, 2 = ifeatproj forward, 4 = attention dgrad, 8 = i_embed dgrad (ConvMode::sample)
+bool conv_sample_ok(const ConvMode& cm, int S, int which);
 hipError_t conv_sample(hipStream_t st, int epi, int nB, int M, int K, int S, const float* Wt,
                        long w_rs, const float* X, long x_bs, float* C, long c_bs,
                        const float* bias, int act, const float* dj, const float* av,
@@ -127,21 +142,17 @@ hipError_t conv_wide(hipStream_t st, int epi, int nB, int M, int K, int S, const
 hipError_t transpose2d(hipStream_t st, int rows, int cols, const float* in, float* out,
                        void* out16 = nullptr);   // out16: a bf16 copy of out (RAU_BF16 mode)
 // dI[b,m,s] = sum_k Wp[k,m] dS[b,k,s] + dj[b,m] a[b,s]   (gradient at i_embed's output)
-hipError_t conv_att_dgrad(hipStream_t st, int nB, int M, int S, int A, const float* dS,
-                          const float* Wp, const float* dj, const float* a, float* dI,
-                          int bf16 = 0);
+hipError_t conv_att_dgrad(hipStream_t st, const ConvMode& cm, int nB, int M, int S, int A, const float* dS,
+                          const float* Wp, const float* dj, const float* a, float* dI);
 // Same product with the gradient through i_embed's tanh and the bias-gradient row sums in its
 // epilogue: dZ[b,m,s] = (sum_k Wp[k,m] dS[b,k,s] + dj[b,m] a[b,s]) (1 - I[b,m,s]^2),
 // rs[b,m] = sum_s dZ[b,m,s].  Only where the per-sample tiling applies (conv_dz_fused_ok): the
 // i_embed weight gradient then takes dZ with its plain operand loader (dz_final below).
-bool conv_dz_fused_ok(int S, int M, int bf16);
-hipError_t conv_att_dgrad_dz(hipStream_t st, int nB, int M, int S, int A, const float* dS,
+bool conv_dz_fused_ok(const ConvMode& cm, int S, int M);
+hipError_t conv_att_dgrad_dz(hipStream_t st, const ConvMode& cm, int nB, int M, int S, int A, const float* dS,
                              const float* Wp, const float* dj, const float* a, const float* I,
                              float* dZ, float* rs, int dz16 = 0,    // dz16: dZ stored as bf16
-                             int bf16 = 0,    // RAU_BF16 mode ...
-                             int ds16 = 0,    // ... and dS points at bf16 elements (dgrad16 only)
-                             int light = 0);  // the caller's recurrence is the longer path: keep the f32 product
-                                              // on the 176-register tile instead of dgrad_dma's 240 (two per CU)
+                             int ds16 = 0);   // RAU_BF16 mode: dS points at bf16 elements (dgrad16 only)
 // RAU_BF16 mode, 14 x 14 maps, M % 128 == 0, K % 32 == 0 (dgrad16.hip): the product above with both GEMM
 // operands rounded to bf16 while staged, f32 accumulate and epilogue; C = dZ as f32 or bf16 elements
 bool dgrad16_ok(int M, int K, int S, long w_rs);
@@ -150,20 +161,20 @@ hipError_t dgrad16(hipStream_t st, int nB, int M, int K, int S, const float* Wt,
                    const float* Y, float* rs, int c16, int x16 = 0 /* X stored as bf16 */);
 // f32 mode, 14 x 14 maps, M % 128 == 0, K % 16 == 0 (dgrad_dma.hip, round 4): the same product and epilogue on
 // per-sample tiles with both operands staged by LDS-DMA; bitwise the results of conv_sample's EPI 2
-bool dgrad_dma_ok(int M, int K, int S, long w_rs);
-hipError_t dgrad_dma(hipStream_t st, int nB, int M, int K, int S, const float* Wt, long w_rs,
+bool dgrad_dma_ok(const ConvMode& cm, int M, int K, int S, long w_rs);
+hipError_t dgrad_dma(hipStream_t st, const ConvMode& cm, int nB, int M, int K, int S, const float* Wt, long w_rs,
                      const float* X, long x_bs, float* C, long c_bs, const float* dj, const float* av,
                      const float* Y, float* rs);
 // dWp += sum dS I^T in RAU_BF16 mode with dS stored as bf16 (att_bwd_fused's dS16), I f32
 hipError_t conv_att_wgrad_ds16(hipStream_t st, int nB, int M, int S, int A, const void* dS16,
                                const float* I, float* dWp, float* slab);
 // dX'[b,d,s] = sum_m Wi[m,d] dZ[b,m,s]   (dead in feval, SS:579; module-level API only)
-hipError_t conv_embed_dgrad(hipStream_t st, int nB, int D, int S, int M, const float* dZ,
+hipError_t conv_embed_dgrad(hipStream_t st, const ConvMode& cm, int nB, int D, int S, int M, const float* dZ,
                             const float* Wi, float* dX);
-// The same product in the context's dtype, for the step path's feature-map gradient: bf16 != 0 rounds both
+// The same product in the context's dtype, for the step path's feature-map gradient: cm.bf16 != 0 rounds both
 // operands while they are staged (Wi from its f32 storage, dZ from f32 or, dz16, from its bf16 storage)
-hipError_t conv_embed_dgrad_mode(hipStream_t st, int nB, int D, int S, int M, const void* dZ, int dz16,
-                                 const float* Wi, float* dX, int bf16);
+hipError_t conv_embed_dgrad_mode(hipStream_t st, const ConvMode& cm, int nB, int D, int S, int M, const void* dZ,
+                                 int dz16, const float* Wi, float* dX);
 // ---- feature-map gradient of the step path (xgrad.hip)
 // Where hop h's keep bits of site RAU_MASK_X come from.  kind 0: no mask (scale 1); 1: `bits`, indexed over the
 // logical [.., SL] tensor from element e0; 2: regenerated with philox_keep16 from (seed, site, step) -- read from
@@ -187,7 +198,7 @@ hipError_t xgrad_accum_img(hipStream_t st, int slots, int D, int SL, int Sp, con
                            const int32_t* img_start, const int32_t* img_samples, const XMask& m, int store);
 // Exact f32, 14 x 14 class (xgrad_fused_ok): dX[b] (store ? = : +=) sum_{h < nh} keep_h * scale * Wi^T dZ_h[b] with
 // the hop loop inside the workgroup.  dZ [nh][nB][M][S] f32, Wi [M][D].
-bool xgrad_fused_ok(int D, int M, int S);
+bool xgrad_fused_ok(bool on /* the caller's policy: off = the unfused path */, int D, int M, int S);
 hipError_t xgrad_fused(hipStream_t st, int nh, int nB, int D, int M, int S, const float* dZ, const float* Wi,
                        float* dX, const XMask& m, int store);
 // dWp[k,m] += sum_{b,s} dS[b,k,s] I[b,m,s]   and, with dZ = dI (1 - I^2),
@@ -195,20 +206,20 @@ hipError_t xgrad_fused(hipStream_t st, int nh, int nB, int D, int M, int S, cons
 size_t conv_wgrad_slab_floats(int nB, int rowsA, int rowsB, int S);
 // bf16-operand i_embed weight gradient on 14 x 14 maps, 256 x 256 tiles fed by LDS-DMA
 // (wgrad16.hip, round 3): dW[ra][rb] += sum_{b,s} A16[b][ra][s] B16[b][rb][s], operands bf16 in HBM
-// (a_bs / b_bs in elements).  _ok: S == 196, ra and rb multiples of 256; RAU_WGRAD16_OFF=1 keeps the
-// 128 x 128 register-staged tile (A/B knob).  The slab must hold wgrad16_slab_floats().
-bool wgrad16_ok(int ra, int rb, int S);
-size_t wgrad16_slab_floats(int nB, int ra, int rb, int S);
-hipError_t wgrad16(hipStream_t st, int nB, int ra, int rb, int S, const void* A16, long a_bs,
+// (a_bs / b_bs in elements).  _ok: cm.wgrad16, S == 196, ra and rb multiples of 256; else the 128 x 128
+// register-staged tile.  The slab must hold wgrad16_slab_floats() of the same mode.
+bool wgrad16_ok(const ConvMode& cm, int ra, int rb, int S);
+size_t wgrad16_slab_floats(const ConvMode& cm, int nB, int ra, int rb, int S);
+hipError_t wgrad16(hipStream_t st, const ConvMode& cm, int nB, int ra, int rb, int S, const void* A16, long a_bs,
                    const void* B16, long b_bs, float* dW, float* slab);
 // Split-K partials of the recurrence's skinny Linear GEMMs with LDS-DMA operand staging
 // (skinny_dma.hip, round 3): nprob (<= 3) problems C_p = A_p W_p^T (brc = false, W [N][K]) or
 // A_p W_p (brc = true, W [K][N]) of one M and K; problem p's partials at slab + off[p] laid out
-// [split][M][N[p]].  _ok: K % 32 == 0, 16-byte aligned rows, [K][N] weights a multiple of 64 wide;
-// RAU_SKINNY_DMA_OFF=1 keeps the register-staged tile of gemm_core.h (A/B knob).
+// [split][M][N[p]].  _ok: mode.dma, K % 4 == 0, dword-aligned rows (mode.align16: 16-byte), ragged shapes
+// only with mode.ragged; else the register-staged tile of gemm_core.h.
 // deep (LinMode::deep): 32-deep stages where K % 64 == 0, else 16-deep (one kernel template).  The three
 // functions of one launch must be given the same value: raggedness and the split count depend on the depth.
-bool skinny_dma_ok(int deep, int M, int K, long lda, long ldb, bool brc, int nprob, const int* N,
+bool skinny_dma_ok(LinMode mode, int M, int K, long lda, long ldb, bool brc, int nprob, const int* N,
                    const float* const* A, const float* const* B);
 int skinny_dma_splits(int deep, int M, int K, int tiles_all, size_t cols_all, size_t slab_floats);
 hipError_t skinny_dma(hipStream_t st, LinMode mode, bool brc, int nprob, int M, int K,
@@ -216,17 +227,17 @@ hipError_t skinny_dma(hipStream_t st, LinMode mode, bool brc, int nprob, int M, 
                       float* slab, const long* off, int splits);
 // the same products with both operands staged by LDS-DMA (wgrad_dma.hip, round 3): 14 x 14 maps,
 // row counts multiples of 128, plain operands (dZ already final)
-bool wgrad_dma_ok(int ra, int rb, int S);
-hipError_t wgrad_dma(hipStream_t st, int nB, int ra, int rb, int S, const float* A, long a_bs,
+bool wgrad_dma_ok(const ConvMode& cm, int ra, int rb, int S);
+hipError_t wgrad_dma(hipStream_t st, const ConvMode& cm, int nB, int ra, int rb, int S, const float* A, long a_bs,
                      const float* B, long b_bs, float* dW, float* slab, int splits);
-hipError_t conv_att_wgrad(hipStream_t st, int nB, int M, int S, int A, const float* dS,
-                          const float* I, float* dWp, float* slab, int bf16 = 0);
-hipError_t conv_embed_wgrad(hipStream_t st, int nB, int D, int S, int M, const float* dI,
+hipError_t conv_att_wgrad(hipStream_t st, const ConvMode& cm, int nB, int M, int S, int A, const float* dS,
+                          const float* I, float* dWp, float* slab);
+hipError_t conv_embed_wgrad(hipStream_t st, const ConvMode& cm, int nB, int D, int S, int M, const float* dI,
                             const float* I, const float* X, float* dWi, float* slab,
-                            int bf16 = 0, float* dbi = nullptr /* += sum_{b,s} dZ[b,m,s] */,
+                            float* dbi = nullptr /* += sum_{b,s} dZ[b,m,s] */,
                             int dz_final = 0 /* dI already holds dZ: no tanh factor, no dbi */);
 // same with dZ already final and both operands stored as bf16 (conv_att_dgrad_dz with dz16)
-hipError_t conv_embed_wgrad_b16(hipStream_t st, int nB, int D, int S, int M, const void* dZ16,
+hipError_t conv_embed_wgrad_b16(hipStream_t st, const ConvMode& cm, int nB, int D, int S, int M, const void* dZ16,
                                 const void* X16, float* dWi, float* slab);
 
 // --------------------------------------------------------- pointwise (kernels.hip)
@@ -304,24 +315,30 @@ hipError_t lstm_bwd_multi(hipStream_t st, int order, int nB, int R, const LstmBw
 // SL: logical number of positions when the tensors' pitch S is padded (7x7 maps); positions
 // [SL, S) get zero attention.
 // u_out: where to keep the finished u rows [nB][A] when T is not stored (T == nullptr).
-// waves: the caller's choice of waves per sample for the forward kernel (8 | 16; 0 = the default, 8)
-struct AttPartials { int u_ns = 0; const float* u_bias = nullptr; int z_ns = 0; const float* z_bias = nullptr; int SL = 0; float* u_out = nullptr; int waves = 0;
+struct AttPartials { int u_ns = 0; const float* u_bias = nullptr; int z_ns = 0; const float* z_bias = nullptr; int SL = 0; float* u_out = nullptr;
                      // image table (forward only): sample b reads its P and I tiles at row img[b]; null = row b
                      const int32_t* img = nullptr;
                      // per-sample region counts (forward only): sample b attends to positions [0, min(SL, nreg[b]))
                      // and gives the others attention exactly 0; indexed by the sample, never by img; null = none
                      const int32_t* nreg = nullptr; };
-hipError_t att_fwd_fused(hipStream_t st, int nB, int M, int A, int S, const float* P,
+// Which form an attention launch takes: an argument of the four launchers and of their predicates, computed by the
+// caller from its context (att_mode, policy.h).
+struct AttMode {
+  int dma = 1;                        // the fused family's LDS-DMA kernels on (else its register-staged ones)
+  int waves_fwd = 8, waves_bwd = 16;  // waves per workgroup of the fused kernels (8 | 16)
+  int chunks = 0;                     // row chunks per sample of the split family (1..8), 0 = by batch size
+};
+hipError_t att_fwd_fused(hipStream_t st, const AttMode& am, int nB, int M, int A, int S, const float* P,
                          const float* u, const float* ws, const float* bs, const float* zm,
                          const float* I, const float* qf, float* T, float* a, float* jv,
                          const AttPartials& ap = AttPartials());
 // Which of its two kernels att_fwd_fused launches for this shape: the LDS-DMA one (true) or the register-staged
-// one (T kept, S > 256 or not a multiple of 4, A or M above 512, or RAU_ATT_DMA_OFF set).  The step's launch
+// one (T kept, S > 256 or not a multiple of 4, A or M above 512, or am.dma off).  The step's launch
 // wrapper names the profile class after it: "att_fwd_fused" / "att_fwd_fused_regs".
-bool att_fwd_dma_ok(int M, int A, int S, bool keep_T, int waves_hint = 0);
+bool att_fwd_dma_ok(const AttMode& am, int M, int A, int S, bool keep_T);
 // One workgroup per sample, backward of the above: da = da_lin + sum_m dj I;
 // dz = softmax'(da); T -> dS = dz ws (1-T^2) in place; du = sum_s dS; dwsp = sum_s dz T.
-hipError_t att_bwd_fused(hipStream_t st, int nB, int M, int A, int S, const float* I,
+hipError_t att_bwd_fused(hipStream_t st, const AttMode& am, int nB, int M, int A, int S, const float* I,
                          const float* dj, const float* a, const float* da_lin,
                          const float* ws, float* T_to_dS, float* dz, float* du, float* dwsp,
                          const float* Psrc = nullptr /* T not kept: recompute tanh(Psrc + u) */,
@@ -331,19 +348,18 @@ hipError_t att_bwd_fused(hipStream_t st, int nB, int M, int A, int S, const floa
                          int da_ns = 0, int SL = 0, const float* da_add = nullptr,
                          // dS16 != nullptr (only where att_bwd_dma_ok): dS leaves as bf16 [nB][A][S] there
                          // and T_to_dS keeps P
-                         void* dS16 = nullptr,
-                         int waves_hint = 0 /* 8 | 16 waves per workgroup where RAU_ATT_WAVES_BWD is unset */);
-bool att_bwd_dma_ok(int M, int A, int S, int waves_hint = 0);
+                         void* dS16 = nullptr);
+bool att_bwd_dma_ok(const AttMode& am, int M, int A, int S);
 // The same two passes cut into 4-wave workgroups (NC row chunks per sample, two launches per
 // pass): they always fit next to resident bulk-GEMM workgroups.  `part` is scratch of
 // att_split_part_floats(nB, S) floats.  T is never kept (the backward recomputes tanh(Psrc + u)
 // when Psrc is given, else reads T).
 size_t att_split_part_floats(int nB, int S);
-hipError_t att_fwd_split(hipStream_t st, int nB, int M, int A, int S, const float* P,
+hipError_t att_fwd_split(hipStream_t st, const AttMode& am, int nB, int M, int A, int S, const float* P,
                          const float* u, const float* ws, const float* bs, const float* zm,
                          const float* I, const float* qf, float* a, float* jv, float* part,
                          const AttPartials& ap = AttPartials());
-hipError_t att_bwd_split(hipStream_t st, int nB, int M, int A, int S, const float* I,
+hipError_t att_bwd_split(hipStream_t st, const AttMode& am, int nB, int M, int A, int S, const float* I,
                          const float* dj, const float* a, const float* da_lin, const float* ws,
                          float* T_to_dS, float* dz, float* du, float* dwsp, const float* Psrc,
                          const float* u, float* part, int da_ns = 0, int SL = 0,
@@ -352,8 +368,9 @@ hipError_t att_bwd_split(hipStream_t st, int nB, int M, int A, int S, const floa
 // ones) gets the dynamic LDS it asks for.  Above 256 positions those are the register-staged kernels, which
 // launch without hipFuncAttributeMaxDynamicSharedMemorySize and so with at most 64 KB: 4 S floats in the split
 // family (4096 positions); (nw + 2) S + 2 nw + A forward and (nw + 1) S + nw backward in the fused one, nw
-// waves -- the forward taken at the wider of its training and evaluate-mode forms (900 positions at A = 128).
-int att_max_pitch(bool split, int A, int bwd_waves_hint);
+// waves -- the caller names the forward's at the wider of its training and evaluate-mode forms (900 positions
+// at A = 128).
+int att_max_pitch(bool split, int A, int waves_fwd, int waves_bwd);
 // The feature-map passes below read the resident batch in its own element type ft (rau_feat_type:
 // RAU_FEAT_F32, 16-bit RAU_FEAT_F16 / RAU_FEAT_BF16 or 8-bit RAU_FEAT_E4M3 / RAU_FEAT_E5M2 bit patterns laid
 // out like the f32 form), widen each element exactly to f32 and then do the f32 form's arithmetic: results

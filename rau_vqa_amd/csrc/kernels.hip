@@ -4,7 +4,6 @@
 // two-stage deterministic reductions instead of float atomics.
 #include "common.h"
 #include <algorithm>
-#include <cstdlib>
 
 #include "kernels.h"
 #include "philox.h"
@@ -385,22 +384,10 @@ hipError_t lstm_bwd_multi(hipStream_t st, int order, int nB, int R, const LstmBw
 // kernels is 257 VGPRs per SIMD: the forward kernel's 4 x 102 do not fit and its workgroups waited
 // for conv tiles (130 us each) to retire -- 117-265 us per launch in the step against 52 alone.
 // With 8 waves (2 x 104) it starts at once: 10.02 -> 9.78 ms per step.  The backward kernel (48
-// VGPRs) fits either way and stays at 16.  RAU_ATT_WAVES_FWD / RAU_ATT_WAVES_BWD (8 or 16) override.
-// hint: the caller's choice where the environment does not override (0 = the default: 8 forward, 16
-// backward).  RAU_BF16 mode asks for 8 backward waves: beside that mode's two 206-register dgrad tiles a
+// VGPRs) fits either way and stays at 16.  The caller chooses (AttMode::waves_fwd / waves_bwd, 8 or 16).
+// RAU_BF16 mode asks for 8 backward waves: beside that mode's two 206-register dgrad tiles a
 // SIMD has ~100 registers free, which two waves of 28 fit and four do not (step 8.28 -> 8.04 ms at
 // D = 2048; f32 mode: no difference).
-static int att_waves(bool bwd, int hint = 0) {
-  static const int v[2] = {
-      [] { const char* e = std::getenv("RAU_ATT_WAVES_FWD"); const int n = e ? std::atoi(e) : 0;
-           return (n == 8 || n == 16) ? n : 0; }(),
-      [] { const char* e = std::getenv("RAU_ATT_WAVES_BWD"); const int n = e ? std::atoi(e) : 0;
-           return (n == 8 || n == 16) ? n : 0; }()};
-  const int env = v[bwd ? 1 : 0];
-  if (env) return env;
-  if (hint == 8 || hint == 16) return hint;
-  return bwd ? 16 : 8;
-}
 
 constexpr int kAttLoads = 8;   // independent row loads a wave issues before it consumes the first
 constexpr int kAttLoadsT = 4;  // same, in the tanh-heavy loops (register budget: the kernels must fit
@@ -734,22 +721,22 @@ size_t att_fwd_dma_lds(int nw, int A, int S) {
 }  // namespace
 
 // 14 x 14 (and any S % 4 == 0, S <= 256) maps on the step path (tanh(P + u) not kept): the LDS-DMA kernel
-bool att_fwd_dma_ok(int M, int A, int S, bool keep_T, int waves_hint) {
-  const bool dma_off = std::getenv("RAU_ATT_DMA_OFF") != nullptr;   // A/B knob; read per call: tests switch it between contexts
-  const int nw = att_waves(false, waves_hint);
-  return !dma_off && !keep_T && S % 4 == 0 && S <= 256 && A <= 64 * 8 && M <= 64 * 8 && (nw == 8 || nw == 16) &&
+bool att_fwd_dma_ok(const AttMode& am, int M, int A, int S, bool keep_T) {
+  const int nw = am.waves_fwd;
+  return am.dma && !keep_T && S % 4 == 0 && S <= 256 && A <= 64 * 8 && M <= 64 * 8 && (nw == 8 || nw == 16) &&
          att_fwd_dma_lds(nw, A, S) <= 96 * 1024;
 }
 
-hipError_t att_fwd_fused(hipStream_t st, int nB, int M, int A, int S, const float* P,
+hipError_t att_fwd_fused(hipStream_t st, const AttMode& am, int nB, int M, int A, int S, const float* P,
                          const float* u, const float* ws, const float* bs, const float* zm,
                          const float* I, const float* qf, float* T, float* a, float* jv,
                          const AttPartials& ap) {
   if (!split_span_ok(u, ap.u_ns, (size_t)nB * A) ||
       !split_span_ok(zm, ap.z_ns, (size_t)nB * (ap.SL ? ap.SL : S)))
     return kSplitStateError;
-  const int nw = att_waves(false, ap.waves);
-  if (att_fwd_dma_ok(M, A, S, T != nullptr, ap.waves)) {
+  const int nw = am.waves_fwd;
+  if (nw != 8 && nw != 16) return hipErrorInvalidValue;
+  if (att_fwd_dma_ok(am, M, A, S, T != nullptr)) {
     constexpr int kD8 = kAttD8, kD16 = kAttD16;
     const size_t ldsd = att_fwd_dma_lds(nw, A, S);
     static const bool attr = [] {   // once per process; magic static (contexts on several host threads)
@@ -1050,22 +1037,22 @@ __global__ __launch_bounds__(NW * 64) void k_att_bwd_dma(
 }
 
 // whether att_bwd_fused takes the LDS-DMA kernel for these sizes (the only one that can write dS as bf16)
-static bool att_bwd_dma_sizes(int nw, int M, int A, int S) {
-  const bool dma_off = std::getenv("RAU_ATT_DMA_OFF") != nullptr;   // A/B knob; read per call, as att_fwd_dma_ok does
-  if (dma_off || S % 4 != 0 || S > 256 || A > 64 * 8 || M > 64 * 8 || (nw != 8 && nw != 16)) return false;
+bool att_bwd_dma_ok(const AttMode& am, int M, int A, int S) {
+  const int nw = am.waves_bwd;
+  if (!am.dma || S % 4 != 0 || S > 256 || A > 64 * 8 || M > 64 * 8 || (nw != 8 && nw != 16)) return false;
   const int d = nw == 8 ? 8 : 4;
   return ((size_t)(nw + 1) * S + nw + (size_t)nw * d * S + 256) * sizeof(float) <= 96 * 1024;
 }
-bool att_bwd_dma_ok(int M, int A, int S, int waves_hint) { return att_bwd_dma_sizes(att_waves(true, waves_hint), M, A, S); }
 
-hipError_t att_bwd_fused(hipStream_t st, int nB, int M, int A, int S, const float* I,
+hipError_t att_bwd_fused(hipStream_t st, const AttMode& am, int nB, int M, int A, int S, const float* I,
                          const float* dj, const float* a, const float* da_lin,
                          const float* ws, float* T_to_dS, float* dz, float* du, float* dwsp,
                          const float* Psrc, const float* u, int da_ns, int SL,
-                         const float* da_add, void* dS16, int waves_hint) {
+                         const float* da_add, void* dS16) {
   if (!split_span_ok(da_lin, da_ns, (size_t)nB * (SL ? SL : S))) return kSplitStateError;
-  const int nw = att_waves(true, waves_hint);
-  if (Psrc && u && att_bwd_dma_sizes(nw, M, A, S)) {
+  const int nw = am.waves_bwd;
+  if (nw != 8 && nw != 16) return hipErrorInvalidValue;
+  if (Psrc && u && att_bwd_dma_ok(am, M, A, S)) {
     constexpr int kD8 = 8, kD16 = 4;
     const int d = nw == 8 ? kD8 : kD16;
     const size_t ldsd = ((size_t)(nw + 1) * S + nw + (size_t)nw * d * S + 256) * sizeof(float);
@@ -1238,21 +1225,19 @@ __global__ __launch_bounds__(256) void k_att_ctx(
 }
 
 // row chunks per sample: 8 for small batches (the launch should still cover the chip), else 4
-static int att_chunks(int nB) {
-  const char* e = std::getenv("RAU_ATT_CHUNKS");   // read per call: tests switch it between contexts
-  const int n = e ? std::atoi(e) : 0;
-  return (n >= 1 && n <= 8) ? n : (nB <= 64 ? 8 : 4);
+static int att_chunks(const AttMode& am, int nB) {
+  return (am.chunks >= 1 && am.chunks <= 8) ? am.chunks : (nB <= 64 ? 8 : 4);
 }
 size_t att_split_part_floats(int nB, int S) { return (size_t)nB * 8 * S; }
 
-hipError_t att_fwd_split(hipStream_t st, int nB, int M, int A, int S, const float* P,
+hipError_t att_fwd_split(hipStream_t st, const AttMode& am, int nB, int M, int A, int S, const float* P,
                          const float* u, const float* ws, const float* bs, const float* zm,
                          const float* I, const float* qf, float* a, float* jv, float* part,
                          const AttPartials& ap) {
   if (!split_span_ok(u, ap.u_ns, (size_t)nB * A) ||
       !split_span_ok(zm, ap.z_ns, (size_t)nB * (ap.SL ? ap.SL : S)))
     return kSplitStateError;
-  const int nc = att_chunks(nB);
+  const int nc = att_chunks(am, nB);
   hipLaunchKernelGGL(k_att_score_part, dim3(nc, nB), dim3(256), (size_t)4 * S * sizeof(float), st, nB,
                      A, S, P, u, ws, part, ap);
   hipLaunchKernelGGL(k_att_ctx, dim3(nc, nB), dim3(256), (size_t)(S + 8) * sizeof(float), st, nB, M, S,
@@ -1393,12 +1378,12 @@ __global__ __launch_bounds__(256) void k_att_ds(
   }
 }
 
-hipError_t att_bwd_split(hipStream_t st, int nB, int M, int A, int S, const float* I,
+hipError_t att_bwd_split(hipStream_t st, const AttMode& am, int nB, int M, int A, int S, const float* I,
                          const float* dj, const float* a, const float* da_lin, const float* ws,
                          float* T_to_dS, float* dz, float* du, float* dwsp, const float* Psrc,
                          const float* u, float* part, int da_ns, int SL, const float* da_add) {
   if (!split_span_ok(da_lin, da_ns, (size_t)nB * (SL ? SL : S))) return kSplitStateError;
-  const int nc = att_chunks(nB);
+  const int nc = att_chunks(am, nB);
   hipLaunchKernelGGL(k_att_da_part, dim3(nc, nB), dim3(256), (size_t)4 * S * sizeof(float), st, M, S, I,
                      dj, part);
   hipLaunchKernelGGL(k_att_ds, dim3(nc, nB), dim3(256), (size_t)(S + 4) * sizeof(float), st, nB, A, S,
@@ -1406,11 +1391,11 @@ hipError_t att_bwd_split(hipStream_t st, int nB, int M, int A, int S, const floa
   return hipGetLastError();
 }
 
-int att_max_pitch(bool split, int A, int bwd_waves_hint) {
+int att_max_pitch(bool split, int A, int waves_fwd, int waves_bwd) {
   constexpr long kFloats = 64 * 1024 / 4;   // what a launch gets without the attribute
   long s = kFloats / 4;                      // k_att_score_part, k_att_da_part: [4][S]
   if (!split) {
-    const int nf = std::max(att_waves(false, 0), att_waves(false, 16)), nb = att_waves(true, bwd_waves_hint);
+    const int nf = waves_fwd, nb = waves_bwd;
     s = std::min((kFloats - 2 * nf - A) / (nf + 2), (kFloats - nb) / (nb + 1));
   }
   return s > 0 ? (int)s & ~3 : 0;

@@ -17,6 +17,7 @@
 
 #include "../../include/rau.h"
 #include "kernels.h"
+#include "policy.h"
 
 using namespace rau;
 
@@ -333,6 +334,8 @@ struct rau_ctx {
   int Kp = 0;                 // answer pitch: cfg.K rounded up to a multiple of 4 (3129 -> 3132); the row pitch of
                               // logits, dl and mg.pred, pad columns hold +0.  K % 4 == 0: Kp == K, nothing changes
   int bf16 = 0;               // cfg.dtype == RAU_BF16: bf16-operand conv GEMMs
+  Policy policy;              // the A/B variables as rau_create found them: a context runs under the environment
+                              // it was created in (policy.h)
   hipStream_t st = nullptr;    // chain stream: recurrences, small GEMMs; what callers order against
   hipStream_t st2 = nullptr;   // bulk stream: hop-batched 1x1-conv GEMMs, overlapped with the chain
   hipStream_t st3 = nullptr;   // weight-gradient stream: throughput GEMMs nobody waits for until the end
@@ -425,7 +428,6 @@ struct rau_ctx {
   // persistent encoder forward (enc_ws.hip): device error word (a bounded spin gave up), copied to pinned memory behind the launch
   bool enc_ws = false;          // weight-stationary persistent encoder forward (enc_ws.hip): evaluate mode
   bool enc_ws_train = false;    // ... and in training steps
-  int side_split_env = -1;      // RAU_SIDE_SPLIT=0|1 (A/B variable); -1 = by shape, see side_split()
   unsigned* ws_cnt = nullptr;   // its 16 progress counters
   int* perr_d = nullptr;
   int* perr_h = nullptr;
@@ -548,19 +550,19 @@ inline bool chain_bound(const rau_ctx* ctx) {
   return ctx->mode == RAU_MODE_EVAL || ctx->bf16 || ctx->cfg.B <= 64;
 }
 inline bool side_split(const rau_ctx* ctx) {
-  if (ctx->side_split_env >= 0) return ctx->side_split_env != 0;
+  if (ctx->policy.side_split >= 0) return ctx->policy.side_split != 0;
   return chain_bound(ctx);
 }
 // How this context's Linear GEMMs are formed NOW: bf16 products by its dtype, and the recurrence's skinny GEMMs
-// with 32-deep stages (skinny_dma.hip, NH = 2) under the same predicate as the side split (RAU_SKINNY_DEEP=0|1
+// with 32-deep stages (skinny_dma.hip, NH = 2) under the same predicate as the side split (Policy::skinny_deep
 // overrides).  chain_bound() depends on the mode and the batch size, which change after rau_create: computed at
 // every launch, never stored.
-inline LinMode lin_mode(const rau_ctx* ctx) {
-  static const int env = [] { const char* e = std::getenv("RAU_SKINNY_DEEP"); return e ? (std::atoi(e) != 0 ? 1 : 0) : -1; }();
-  LinMode m;
-  m.bf16 = ctx->bf16 == 1;
-  m.deep = env >= 0 ? env : (chain_bound(ctx) ? 1 : 0);
-  return m;
+inline LinMode lin_mode(const rau_ctx* ctx) { return lin_mode(ctx->policy, ctx->bf16, chain_bound(ctx)); }
+// The same for its conv products (every launcher and every predicate that sizes a buffer for one takes this) and
+// for its attention kernels
+inline ConvMode conv_mode(const rau_ctx* ctx) { return conv_mode(ctx->policy, ctx->bf16, chain_bound(ctx)); }
+inline AttMode att_mode(const rau_ctx* ctx) {
+  return att_mode(ctx->policy, ctx->bf16, ctx->mode == RAU_MODE_EVAL);
 }
 // The three workspaces, in the order of BatchPlan::ws (chain, bulk, side)
 inline std::array<StreamWs*, 3> stream_ws(rau_ctx* ctx) { return {&ctx->ws_chain, &ctx->ws_bulk, &ctx->ws_side}; }

@@ -96,9 +96,7 @@ struct BatchPlan {
   size_t mcount[5];                          // mask sites, elements
 };
 // the attention family of a B-sample batch (measurements: plan_batch below)
-static bool att_family_split(int B) {
-  return std::getenv("RAU_ATT_SPLIT") != nullptr || (B <= 64 && std::getenv("RAU_ATT_FUSED") == nullptr);
-}
+static bool att_family_split(const Policy& pol, int B) { return pol.att_split || (B <= 64 && !pol.att_fused); }
 static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
   const rau_config& c = ctx->cfg;
   const int T = c.T, E = c.E, Rq = c.Rq, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R, K = c.K,
@@ -107,34 +105,20 @@ static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
   // the last group's GEMMs and the backward bulk work can start one hop into the backward chain
   // (measured on H = 8: 2,2,2,1,1 vs 2,2,2,2); pairs elsewhere keep the launches large.
   // RAU_HOP_GROUPS="4,2,1,1" overrides (sizes must sum to H).
-  {
+  p->groups = hop_partition(ctx->policy.hop_groups, H);
+  if (p->groups.empty()) {
     std::vector<int> sizes;
-    if (const char* eg = std::getenv("RAU_HOP_GROUPS")) {
-      int sum = 0;
-      for (const char* q = eg; *q;) {
-        const int v = std::atoi(q);
-        if (v < 1) { sizes.clear(); break; }
-        sizes.push_back(v);
-        sum += v;
-        while (*q && *q != ',') ++q;
-        if (*q == ',') ++q;
-      }
-      if (sum != H) sizes.clear();
-    }
-    if (sizes.empty() && B <= 64) {
+    if (B <= 64) {
       // small batches are bound by the recurrence's launches, not by the conv GEMMs: one group
       // (B = 32 / 64: 3.64 / 4.43 -> 3.55 / 4.33 ms; B = 128: 6.09 -> 6.49, so not there)
       sizes.push_back(H);
-    }
-    if (sizes.empty()) {
+    } else {
       int left = H;
       while (left > 3) { sizes.push_back(2); left -= 2; }
       while (left > 0) { sizes.push_back(1); left -= 1; }
       if (H == 2) sizes = {1, 1};
     }
-    p->groups.assign(H, 0);
-    int h0 = 0;
-    for (int n : sizes) { p->groups[h0] = n; h0 += n; }
+    p->groups = hop_partition(sizes, H);
   }
   p->mcount[RAU_MASK_WE] = (size_t)T * B * E;
   p->mcount[RAU_MASK_RNN] = (size_t)T * B * Rq;
@@ -150,12 +134,12 @@ static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
   // Small batches (one 16-wave workgroup per sample leaves most CUs idle): B = 32 / 64 / 128 fused
   // 3.83 / 4.57 / 6.06 ms, split in 8 row chunks 3.63 / 4.39 / 6.05 ms -> split up to B = 64
   // (RAU_ATT_FUSED keeps the fused kernels).
-  p->att_split = att_family_split(B);
+  p->att_split = att_family_split(ctx->policy, B);
   {
     // Weight-stationary persistent encoder (enc_ws.hip): chosen by shape, never by the environment in
     // normal use -- contexts of up to 64 samples (the strong-scaling shards of configs[3]) are bound
     // by the recurrence's launches.  RAU_ENC_WS=0|1 is the A/B override.
-    const char* e = std::getenv("RAU_ENC_WS");
+    const int e = ctx->policy.enc_ws;
     // measured in the step (MS weights, same box): B = 16 / 32 / 64 -> 3.00 / 3.49 / 4.46 ms with it,
     // 3.16 / 3.52 / 4.26 without; evaluate-mode forward 14.3 / 26.8 / 45.9 k vs 10.8 / 20.8 / 40.4 k QA/s.
     // Every workgroup reads all h rows of its sample half each step, so the traffic grows with B while
@@ -166,14 +150,14 @@ static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
     // competing for the CUs), persist_check() below turns the path off for the ctx -- for good: what
     // gave up was the device's residency, not the size, so a later rau_set_batch_size keeps it off.
     const bool fits = !ctx->persist_gave_up && enc_ws_ok(B, Rq) && enc_ws_fits_device(B);
-    p->enc_ws_train = fits && (e ? std::atoi(e) != 0 : B <= 32);
-    p->enc_ws = fits && (e ? std::atoi(e) != 0 : B <= 64);
+    p->enc_ws_train = fits && (e >= 0 ? e != 0 : B <= 32);
+    p->enc_ws = fits && (e >= 0 ? e != 0 : B <= 64);
   }
   {
     // split-K workspaces: one per stream (the two streams run concurrently)
     size_t sl2 = std::max(conv_wgrad_slab_floats(H * B, A, M, S),
                           conv_wgrad_slab_floats(H * B, M, D, S));
-    if (ctx->bf16) sl2 = std::max(sl2, wgrad16_slab_floats(H * B, M, D, S));
+    if (ctx->bf16) sl2 = std::max(sl2, wgrad16_slab_floats(conv_mode(ctx), H * B, M, D, S));
     // The grouped Linear weight-gradient GEMMs' partial slabs.  They run on the weight-gradient stream or,
     // where the bulk stream is the longer path, at the END of the bulk stream (rau_backward), and take the
     // workspace of the stream they run on (StreamWs, rau_ctx.h): two launches that share a workspace must be
@@ -267,10 +251,13 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   NEED(c.Rq > 0 && c.Rq % 4 == 0 && c.R > 0 && c.R % 4 == 0 && c.M > 0 && c.M % 4 == 0 &&
            c.A > 0 && c.A % 4 == 0 && c.D > 0 && c.D % 4 == 0,
        "rau_create: Rq,R,M,A,D must be positive multiples of 4");
+  const Policy policy = policy_from_env();   // once: the context never looks at the environment again
   {
     // a context may shrink its batch (rau_set_batch_size), never grow it: the family of B samples is the narrower
-    const bool split = att_family_split(c.B);
-    const int smax = att_max_pitch(split, c.A, c.dtype ? 8 : 0);
+    const bool split = att_family_split(policy, c.B);
+    // (the forward at the wider of its training and evaluate-mode forms)
+    const AttMode tr = att_mode(policy, c.dtype, false), ev = att_mode(policy, c.dtype, true);
+    const int smax = att_max_pitch(split, c.A, std::max(tr.waves_fwd, ev.waves_fwd), tr.waves_bwd);
     NEED(c.S <= smax,   // (a multiple of 4: the same bound on the pitch)
          "rau_create: S=%d is above the %d positions at which the %s attention kernels' LDS request still fits "
          "the 64 KB of a launch (B=%d, A=%d)", c.S, smax, split ? "split" : "fused", c.B, c.A);
@@ -295,6 +282,7 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
 
   rau_ctx* ctx = new rau_ctx();
   ctx->cfg = c;
+  ctx->policy = policy;
   ctx->Q = 4 * c.Rq;
   ctx->Sp = (c.S + 3) & ~3;
   ctx->Kp = (c.K + 3) & ~3;
@@ -347,25 +335,7 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   const hipStream_t owners[3] = {ctx->st, ctx->st2, ctx->st3};
   for (int i = 0; i < 3; ++i) stream_ws(ctx)[i]->owner = owners[i];
   ctx->cap = c.B;
-  {
-    if (const char* eg = std::getenv("RAU_BWD_GROUPS")) {
-      std::vector<int> bs;
-      int sum = 0;
-      for (const char* p = eg; *p;) {
-        const int v = std::atoi(p);
-        if (v < 1) { bs.clear(); sum = -1; break; }
-        bs.push_back(v);
-        sum += v;
-        while (*p && *p != ',') ++p;
-        if (*p == ',') ++p;
-      }
-      if (sum == c.H) {
-        ctx->bgroups.assign(c.H, 0);
-        int b0 = 0;
-        for (int n : bs) { ctx->bgroups[b0] = n; b0 += n; }
-      }
-    }
-  }
+  ctx->bgroups = hop_partition(policy.bwd_groups, c.H);
   ctx->evF.resize(c.H);
   ctx->evK.resize(c.H);
 
@@ -462,7 +432,7 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   CK(dalloc(ctx, &ctx->qf, HB * M));
   CK(dalloc(ctx, &ctx->xd, HB * D * S));
   // bf16 mode on maps the fused-dZ backward handles (the only backward that reads the bf16 form)
-  if (ctx->bf16 == 1 && ctx->Sp == c.S && conv_dz_fused_ok(S, M, 1) && !std::getenv("RAU_XD_F32")) {
+  if (ctx->bf16 == 1 && ctx->Sp == c.S && conv_dz_fused_ok(conv_mode(ctx), S, M) && !policy.xd_f32) {
     float* x16 = nullptr;
     CK(dalloc(ctx, &x16, (HB * D * S + 1) / 2));
     ctx->xd16 = x16;
@@ -471,7 +441,7 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
     CK(dalloc(ctx, &p16, ((size_t)A * M + 1) / 2));
     ctx->WiT16 = w16;
     ctx->WpT16 = p16;
-    if (dgrad16_ok(M, A, S, M) && att_bwd_dma_ok(M, A, S, 8)) {
+    if (dgrad16_ok(M, A, S, M) && att_bwd_dma_ok(att_mode(ctx), M, A, S)) {
       float* d16 = nullptr;
       CK(dalloc(ctx, &d16, (HB * A * S + 1) / 2));
       ctx->dS16 = d16;
@@ -486,7 +456,6 @@ int rau_create(const rau_config* cfg, rau_ctx** out) {
   CK(dalloc(ctx, &ctx->zm, (size_t)B * S));
   CK(dalloc(ctx, &ctx->att_part, plan.att_part));
   {
-    if (const char* ss = std::getenv("RAU_SIDE_SPLIT")) ctx->side_split_env = std::atoi(ss) != 0;
     float* f = nullptr;
     CK(dalloc(ctx, &f, 16));
     ctx->ws_cnt = reinterpret_cast<unsigned*>(f);
@@ -1023,19 +992,19 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
     ap.SL = SL;
     ap.u_out = ctx->u + (size_t)h * B * A;   // tanh(P + u) itself is not kept: 25 % less traffic here
     // evaluate mode: no conv tile is resident while the hops run (I and P are hoisted), so the 16-wave form
-    // fits and streams a sample faster (B = 256: 124.2 -> 129.5 k QA/s); the training step keeps 8
-    ap.waves = ctx->mode == RAU_MODE_EVAL ? 16 : 0;
+    // fits and streams a sample faster (B = 256: 124.2 -> 129.5 k QA/s); the training step keeps 8 (att_mode)
+    const AttMode am = att_mode(ctx);
     ap.img = img;   // image table: Pin and Ih hold one tile per image, sample b reads row img[b]
     ap.nreg = nreg;   // region counts: per SAMPLE, also where the tiles are per image
     // (the profile tells the fused family's two kernels apart: the LDS-DMA one keeps the family's name)
-    const char* fused_cls = att_fwd_dma_ok(M, A, S, false, ap.waves) ? "att_fwd_fused" : "att_fwd_fused_regs";
+    const char* fused_cls = att_fwd_dma_ok(am, M, A, S, false) ? "att_fwd_fused" : "att_fwd_fused_regs";
     if (!ctx->att_split)
       RUN(fused_cls, 2.0 * B * S * (A + M), ((double)B * A * S + BM_ * S) * 4,
-          att_fwd_fused(st, B, M, A, S, Pin, slab_u, ctx->att_score.W, ctx->att_score.b, slab_z, Ih, qf,
+          att_fwd_fused(st, am, B, M, A, S, Pin, slab_u, ctx->att_score.W, ctx->att_score.b, slab_z, Ih, qf,
                         nullptr, ah, ctx->jv, ap));
     else
       RUN("att_fwd_split", 2.0 * B * S * (A + M), ((double)B * A * S + BM_ * S) * 4,
-          att_fwd_split(st, B, M, A, S, Pin, slab_u, ctx->att_score.W, ctx->att_score.b, slab_z, Ih, qf,
+          att_fwd_split(st, am, B, M, A, S, Pin, slab_u, ctx->att_score.W, ctx->att_score.b, slab_z, Ih, qf,
                         ah, ctx->jv, ctx->att_part, ap));
   }
   {  // classifier SS:265-283
@@ -1213,14 +1182,13 @@ int hop_backward(rau_ctx* ctx, int h, const float* cp, const float* Ih, const Ho
   }
   if (!ctx->att_split)
     RUN("att_bwd_fused", 2.0 * B * S * (A + M), ((double)B * A * S * 2 + BM_ * S) * 4,
-        att_bwd_fused(st, B, M, A, S, Ih, djh, ah, ws.slab, ctx->att_score.W, Th, dzh, duh,
+        att_bwd_fused(st, att_mode(ctx), B, M, A, S, Ih, djh, ah, ws.slab, ctx->att_score.W, Th, dzh, duh,
                       ctx->dwsp + (size_t)h * B * A, ctx->fwd.I_shared ? ctx->P0 : Th,
                       ctx->u + (size_t)h * B * A, ns_a, SL, g.da_out,
-                      g.ds16 ? (void*)((uint16_t*)ctx->dS16 + (size_t)h * B * A * S) : nullptr,
-                      ctx->bf16 ? 8 : 0));
+                      g.ds16 ? (void*)((uint16_t*)ctx->dS16 + (size_t)h * B * A * S) : nullptr));
   else
     RUN("att_bwd_split", 2.0 * B * S * (A + M), ((double)B * A * S * 2 + BM_ * S) * 4,
-        att_bwd_split(st, B, M, A, S, Ih, djh, ah, ws.slab, ctx->att_score.W, Th, dzh, duh,
+        att_bwd_split(st, att_mode(ctx), B, M, A, S, Ih, djh, ah, ws.slab, ctx->att_score.W, Th, dzh, duh,
                       ctx->dwsp + (size_t)h * B * A, ctx->fwd.I_shared ? ctx->P0 : Th,
                       ctx->u + (size_t)h * B * A, ctx->att_part, ns_a, SL, g.da_out));
   if (g.ev_conv_ready) HIPC(hipEventRecord(g.ev_conv_ready, st));
@@ -1276,9 +1244,9 @@ int image_forward(rau_ctx* ctx, hipStream_t s, int n, const void* x, bool x_is_b
          conv_att_pre_b16(s, n, M, S, A, I, ctx->WpT16, ctx->att_i.b, P));
   } else {
     RUNS(s, "conv_embed_fwd", gflop(M, nS, D), (nS * D + nS * M) * 4,
-         conv_embed_fwd(s, n, D, S, M, (const float*)x, ctx->WiT, ctx->i_embed.b, I, ctx->bf16));
+         conv_embed_fwd(s, conv_mode(ctx), n, D, S, M, (const float*)x, ctx->WiT, ctx->i_embed.b, I));
     RUNS(s, "conv_att_pre", gflop(A, nS, M), (nS * M + nS * A) * 4,
-         conv_att_pre(s, n, M, S, A, I, ctx->WpT, ctx->att_i.b, P, ctx->bf16));
+         conv_att_pre(s, conv_mode(ctx), n, M, S, A, I, ctx->WpT, ctx->att_i.b, P));
   }
   return RAU_OK;
 }
@@ -1292,13 +1260,14 @@ int conv_grads(rau_ctx* ctx, hipStream_t s, const ConvGrads& g) {
   const int n = g.n, D = c.D, S = ctx->Sp, M = c.M, A = c.A;
   const double nAS = (double)n * A * S, nMS = (double)n * M * S, nDS = (double)n * D * S;
   float* slab = ctx->ws_bulk.slab;
+  const ConvMode cm = conv_mode(ctx);   // (light: contexts whose recurrence is the longer path, chain_bound)
   if (g.dzf)
     RUNS(s, "conv_att_dgrad", gflop(M, (double)n * S, A), (nAS + 3.0 * nMS) * 4,
-         conv_att_dgrad_dz(s, n, M, S, A, (const float*)g.dS, ctx->att_i.W, g.dj, g.a, g.I, (float*)g.dZ, g.dbi_part,
-                           g.dz_is_b16 ? 1 : 0, ctx->bf16, g.ds_is_b16 ? 1 : 0, chain_bound(ctx) ? 1 : 0));
+         conv_att_dgrad_dz(s, cm, n, M, S, A, (const float*)g.dS, ctx->att_i.W, g.dj, g.a, g.I, (float*)g.dZ,
+                           g.dbi_part, g.dz_is_b16 ? 1 : 0, g.ds_is_b16 ? 1 : 0));
   else
     RUNS(s, "conv_att_dgrad", gflop(M, (double)n * S, A), (nAS + 2.0 * nMS) * 4,
-         conv_att_dgrad(s, n, M, S, A, (const float*)g.dS, ctx->att_i.W, g.dj, g.a, (float*)g.dZ, ctx->bf16));
+         conv_att_dgrad(s, cm, n, M, S, A, (const float*)g.dS, ctx->att_i.W, g.dj, g.a, (float*)g.dZ));
   if (g.tied_hops > 1)   // + dj_h (x) a_h of the other active hops (hop 0's came out of the dgrad's epilogue)
     RUNS(s, "outer_sum", 2.0 * (g.tied_hops - 1) * nMS,
          (2.0 * nMS + (double)(g.tied_hops - 1) * ((double)n * M + (double)n * S)) * 4,
@@ -1308,28 +1277,24 @@ int conv_grads(rau_ctx* ctx, hipStream_t s, const ConvGrads& g) {
          conv_att_wgrad_ds16(s, n, M, S, A, (const uint16_t*)g.dS, g.I, ctx->att_i.dW, slab));
   else
     RUNS(s, "conv_att_wgrad", gflop(A, M, (double)n * S), (nAS + nMS) * 4,
-         conv_att_wgrad(s, n, M, S, A, (const float*)g.dS, g.I, ctx->att_i.dW, slab, ctx->bf16));
+         conv_att_wgrad(s, cm, n, M, S, A, (const float*)g.dS, g.I, ctx->att_i.dW, slab));
   if (g.x_is_b16)
     RUNS(s, "conv_embed_wgrad", gflop(M, D, (double)n * S), nMS * 2 + nDS * 2,
-         conv_embed_wgrad_b16(s, n, D, S, M, (const uint16_t*)g.dZ, (const uint16_t*)g.X, ctx->i_embed.dW, slab));
+         conv_embed_wgrad_b16(s, cm, n, D, S, M, (const uint16_t*)g.dZ, (const uint16_t*)g.X, ctx->i_embed.dW, slab));
   else
     RUNS(s, "conv_embed_wgrad", gflop(M, D, (double)n * S), (nMS * (g.dzf ? 1 : 2) + nDS) * 4,
-         conv_embed_wgrad(s, n, D, S, M, (const float*)g.dZ, g.I, (const float*)g.X, ctx->i_embed.dW, slab,
-                          ctx->bf16, ctx->i_embed.db, g.dzf));
+         conv_embed_wgrad(s, cm, n, D, S, M, (const float*)g.dZ, g.I, (const float*)g.X, ctx->i_embed.dW, slab,
+                          ctx->i_embed.db, g.dzf));
   return RAU_OK;
 }
 
 extern "C" {
 
 // ================================================================ forward
-// The forward / backward seam (the bulk stream and the matrix pipes wait there for the chain).  RAU_SEAM=<mask>
-// (A/B; default 3): 1 = a train-mode forward with labels also forms the backward's two
+// The forward / backward seam (the bulk stream and the matrix pipes wait there for the chain).  Policy::seam
+// (RAU_SEAM=<mask>, A/B; default 3): 1 = a train-mode forward with labels also forms the backward's two
 // recurrence-free head products (dpre, dhn) behind each group's criterion head on the third stream;
 // 2 = a group's conv gradients start behind att_bwd of its first hop instead of behind the hop's last launch.
-static int seam_mask() {
-  static const int m = [] { const char* e = std::getenv("RAU_SEAM"); return e ? std::atoi(e) : 3; }();
-  return m;
-}
 
 // ---------------- encoder, SS:443-462
 // Layer-1 cell t+1 and layer-2 cell t do not depend on each other, so the two layers
@@ -1366,7 +1331,7 @@ static int encoder_forward(rau_ctx* ctx, const Masks& m) {
       o.bias = ctx->i2h[0].b;
       o.bias2 = ctx->h2h[0].b;
       // in chunks, so that the recurrence only ever waits for the rows it is about to read
-      static const int nchunk_env = [] { const char* e = std::getenv("RAU_ENC_CHUNKS"); return e ? std::atoi(e) : 0; }();
+      const int nchunk_env = ctx->policy.enc_chunks;   // RAU_ENC_CHUNKS
       const int nchunk = std::max(1, std::min(nchunk_env > 0 ? nchunk_env : kEncSideChunks,
                                               std::min(kEncSideChunks, TL - t_head)));
       const int per = (TL - t_head + nchunk - 1) / nchunk;
@@ -1629,7 +1594,7 @@ static int forward_impl(rau_ctx* ctx, bool bwd_forms_dpre) {
   HIPC(hipMemsetAsync(ctx->hh, 0, BR_ * sizeof(float), st));
   const Truth truth = step_truth(ctx);
   // RAU_SEAM & 1: the heads are followed by the backward's two head products, unless that backward forms them itself
-  const bool dpre = bs.held.have_labels && ctx->mode == RAU_MODE_TRAIN && (seam_mask() & 1) && !bwd_forms_dpre;
+  const bool dpre = bs.held.have_labels && ctx->mode == RAU_MODE_TRAIN && (ctx->policy.seam & 1) && !bwd_forms_dpre;
   // rows the logits region of the head's workspace holds (hop_forward_head: a quarter of the side stream's slab)
   const int head_max = (int)std::max<size_t>(1, ctx->ws_side.floats / 4 / ((size_t)B * c.K));
   int gstart = 0;
@@ -1775,7 +1740,7 @@ static int feat_grad_hops(rau_ctx* ctx, hipStream_t sb, int nh, const void* dz, 
   const double fl = gflop(D, (double)B * S, M), by = ((double)B * M * S + (double)B * D * S) * 4;
   const bool per_image = xgrad_per_image(ctx);   // (never fused: that kernel owns one sample's tile)
   const BatchSlot& bs = cur_batch(ctx);
-  if (!per_image && !dz_is_b16 && !is_dI && !ctx->bf16 && xgrad_fused_ok(D, M, S) && S == SL) {
+  if (!per_image && !dz_is_b16 && !is_dI && !ctx->bf16 && xgrad_fused_ok(ctx->policy.xgrad_fused, D, M, S) && S == SL) {
     xm.e0 = (size_t)mask_hop * xm.hop_stride;
     if (!mask_step) xm.hop_stride = 0;
     RUNS(sb, "conv_embed_dgrad", nh * fl, (double)nh * B * M * S * 4 + (double)B * D * S * (first ? 4 : 8),
@@ -1791,7 +1756,7 @@ static int feat_grad_hops(rau_ctx* ctx, hipStream_t sb, int nh, const void* dz, 
       dzk = ctx->xg_dz;
     }
     RUNS(sb, "conv_embed_dgrad", fl, by,
-         conv_embed_dgrad_mode(sb, B, D, S, M, dzk, dz_is_b16 ? 1 : 0, ctx->i_embed.W, ctx->xg_tmp, ctx->bf16));
+         conv_embed_dgrad_mode(sb, conv_mode(ctx), B, D, S, M, dzk, dz_is_b16 ? 1 : 0, ctx->i_embed.W, ctx->xg_tmp));
     xm.e0 = (size_t)(mask_hop + k * mask_step) * xm.hop_stride;
     if (per_image)
       RUNS(sb, "xgrad_accum_img", 2.0 * B * D * S,
@@ -1817,7 +1782,7 @@ static int group_conv_grads(rau_ctx* ctx, int h, int group, int HA, bool ds16, b
   if (!ctx->fwd.I_shared) {
     const size_t hb = (size_t)h * B;
     g.n = (std::min(h + group, HA) - h) * B;   // active hops of this group
-    g.dzf = conv_dz_fused_ok(S, M, ctx->bf16);
+    g.dzf = conv_dz_fused_ok(conv_mode(ctx), S, M);
     g.ds_is_b16 = ds16;
     g.dS = g.ds_is_b16 ? map_elems(ctx->dS16, true, hb * A * S) : ctx->T + hb * A * S;
     g.dj = ctx->dj + hb * M; g.a = ctx->a + hb * S; g.I = ctx->I + hb * M * S;
@@ -2039,7 +2004,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   float* dh_part = nullptr;        // gradient at next_h: K-split partials left by the previous hop
   int dh_part_ns = 0;
   // bf16 mode, train-mode step on 14x14 maps: dS goes out as bf16 (its consumers below read that)
-  const bool ds16 = ctx->dS16 && !ctx->fwd.I_shared && !ctx->att_split && conv_dz_fused_ok(S, M, ctx->bf16);
+  const bool ds16 = ctx->dS16 && !ctx->fwd.I_shared && !ctx->att_split && conv_dz_fused_ok(conv_mode(ctx), S, M);
   bool dq_side = false;
   int dq_rows_left = HA;           // hops [0, dq_rows_left) whose dq term this stream still owes
   for (int h = HA - 1; h >= 0; --h) {
@@ -2057,7 +2022,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
       g.dh_part_ns_out = &dh_part_ns;
       // h is the first hop of its launch group: its conv gradients may start behind att_bwd, three launches
       // before the hop's backward is over (it matters for the first group: the forward / backward seam)
-      g.ev_conv_ready = (gsz[h] && (seam_mask() & 2)) ? ctx->evK[h] : nullptr;
+      g.ev_conv_ready = (gsz[h] && (ctx->policy.seam & 2)) ? ctx->evK[h] : nullptr;
       g.dh_prev_dead = h == 0;   // hop 0's prev_h is the constant initial state: nothing reads its gradient
       g.da_out = has_da ? ctx->att_da + (size_t)h * BS_ : nullptr;
       g.ds16 = ds16;
@@ -2087,7 +2052,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
     // start on the bulk stream, overlapping the remaining hops and the encoder BPTT:
     // dZ = (Wp^T dS + dj (x) a)(1 - I^2); dWp += dS I^T; dWi += dZ X'^T.
     if (gsz[h]) {   // h is the first hop of its group: the whole group's attention backward is done
-      if (!(seam_mask() & 2)) HIPC(hipEventRecord(ctx->evK[h], st));
+      if (!(ctx->policy.seam & 2)) HIPC(hipEventRecord(ctx->evK[h], st));
       HIPC(hipStreamWaitEvent(ctx->st2, ctx->evK[h], 0));   // recorded inside hop_backward (ev_conv_ready)
       if (int rc = group_conv_grads(ctx, h, gsz[h], HA, ds16, dX_first)) return rc;
     }
@@ -2122,7 +2087,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   // the same on either stream and stays on the third.  RAU_WG_BULK=<mask> overrides (A/B, DESIGN.md section
   // 8): 1 = mult group on the bulk stream, 2 = encoder group too.  Not with the side-stream split (the
   // third stream's split-K workspace would be shared).  Each group takes the stream AND the scratch of one record.
-  static const int wg_env = [] { const char* e = std::getenv("RAU_WG_BULK"); return e ? std::atoi(e) : -1; }();
+  const int wg_env = ctx->policy.wg_bulk;
   const int wg_bulk = side_split(ctx) ? 0 : wg_env >= 0 ? wg_env : (chain_bound(ctx) ? 0 : 1);
   if (int rc = mult_wgrads(ctx, HA, sig, wg_bulk)) return rc;
   // an attached question (rau_set_question_dev): dq above is the result, handed to the caller; no BPTT, no embedding

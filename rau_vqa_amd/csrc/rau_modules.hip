@@ -422,7 +422,7 @@ int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
     }
     RUN("mul_dtanh", 0, BM_ * S * 12.0, mul_dtanh(st, BM_ * S, dZh, Ih, ctx->m_dZ));
     RUN("conv_embed_dgrad", gflop(D, (double)B * S, M), (BM_ * S + (double)B * D * S) * 4,
-        conv_embed_dgrad(st, B, D, S, M, ctx->m_dZ, ctx->i_embed.W, ctx->m_dX));
+        conv_embed_dgrad(st, conv_mode(ctx), B, D, S, M, ctx->m_dZ, ctx->i_embed.W, ctx->m_dX));
     float* dXo = ctx->m_dX;
     if (S != SL) {   // dense [B,D,SL] for the caller (reuses the re-pitch buffer's sibling)
       if (!ctx->m_dXd)

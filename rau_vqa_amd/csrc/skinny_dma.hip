@@ -32,7 +32,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -363,8 +362,8 @@ __global__ __launch_bounds__(256, BF ? 4 : 1) void k_skinny_dma(const SkinnyPara
 static int stage_depth(int deep, int K) { return (deep && K % 64 == 0) ? 32 : 16; }
 
 // Ragged shapes (the RAG kernels): K not a whole even number of stages, or [K][N] weights whose N is not
-// a multiple of the 64-column tile.  RAU_SKINNY_RAGGED_OFF sends them to the register-staged tile as
-// rounds 1-3 did (A/B knob).
+// a multiple of the 64-column tile.  Without LinMode::ragged they go to the register-staged tile as in
+// rounds 1-3.
 static bool ragged(int deep, int K, bool brc, int nprob, const int* N) {
   if (K % (2 * stage_depth(deep, K)) != 0) return true;
   if (brc)
@@ -373,14 +372,12 @@ static bool ragged(int deep, int K, bool brc, int nprob, const int* N) {
   return false;
 }
 
-bool skinny_dma_ok(int deep, int M, int K, long lda, long ldb, bool brc, int nprob, const int* N,
+bool skinny_dma_ok(LinMode mode, int M, int K, long lda, long ldb, bool brc, int nprob, const int* N,
                    const float* const* A, const float* const* B) {
-  static const bool off = std::getenv("RAU_SKINNY_DMA_OFF") != nullptr;   // A/B knob
-  static const bool rag_off = std::getenv("RAU_SKINNY_RAGGED_OFF") != nullptr;
-  if (off || M < 1 || nprob < 1 || nprob > 3) return false;
+  if (!mode.dma || M < 1 || nprob < 1 || nprob > 3) return false;
   if (K < 4 || (K & 3) || (lda & 3) || (ldb & 3)) return false;
-  if (ragged(deep, K, brc, nprob, N)) {
-    if (rag_off) return false;
+  if (ragged(mode.deep, K, brc, nprob, N)) {
+    if (!mode.ragged) return false;
     for (int p = 0; p < nprob; ++p)
       if (brc && (N[p] & 3)) return false;         // pieces are all inside or all outside a row
   }
@@ -389,9 +386,8 @@ bool skinny_dma_ok(int deep, int M, int K, long lda, long ldb, bool brc, int npr
     // global_load_lds_dwordx4 takes any dword-aligned global address (checked with tools/linbench: same
     // results, same speed); the flat parameter vector puts every weight behind attscore's 1 x A + 1 block
     // one float off a 16-byte boundary, and rounds 1-3 sent all of those GEMMs to the register-staged tile.
-    // RAU_SKINNY_ALIGN16 restores that (A/B knob).
-    static const bool align16 = std::getenv("RAU_SKINNY_ALIGN16") != nullptr;
-    const uintptr_t am = align16 ? 15 : 3;
+    // LinMode::align16 restores that.
+    const uintptr_t am = mode.align16 ? 15 : 3;
     if ((reinterpret_cast<uintptr_t>(A[p]) & am) || (reinterpret_cast<uintptr_t>(B[p]) & am)) return false;
   }
   return true;

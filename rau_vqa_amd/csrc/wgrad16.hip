@@ -35,7 +35,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 #include <type_traits>
 
 #include "kernels.h"
@@ -279,19 +278,18 @@ int wgrad16_splits(int nB, int ra, int rb) {
 
 }  // namespace
 
-bool wgrad16_ok(int ra, int rb, int S) {
-  static const bool off = std::getenv("RAU_WGRAD16_OFF") != nullptr;
-  return !off && S == HS && ra >= HTZ && rb >= HTX && ra % HTZ == 0 && rb % HTX == 0;
+bool wgrad16_ok(const ConvMode& cm, int ra, int rb, int S) {
+  return cm.wgrad16 && S == HS && ra >= HTZ && rb >= HTX && ra % HTZ == 0 && rb % HTX == 0;
 }
 
-size_t wgrad16_slab_floats(int nB, int ra, int rb, int S) {
-  if (!wgrad16_ok(ra, rb, S)) return 0;
+size_t wgrad16_slab_floats(const ConvMode& cm, int nB, int ra, int rb, int S) {
+  if (!wgrad16_ok(cm, ra, rb, S)) return 0;
   return (size_t)wgrad16_splits(nB, ra, rb) * ra * rb;
 }
 
-hipError_t wgrad16(hipStream_t st, int nB, int ra, int rb, int S, const void* A16, long a_bs,
+hipError_t wgrad16(hipStream_t st, const ConvMode& cm, int nB, int ra, int rb, int S, const void* A16, long a_bs,
                    const void* B16, long b_bs, float* dW, float* slab) {
-  if (!wgrad16_ok(ra, rb, S) || nB < 1) return hipErrorInvalidValue;
+  if (!wgrad16_ok(cm, ra, rb, S) || nB < 1) return hipErrorInvalidValue;
   if ((double)nB * (double)(a_bs > b_bs ? a_bs : b_bs) * 2 >= 2147483648.0 * 8) return hipErrorInvalidValue;
   Wgrad16Params P{};
   P.ra = ra; P.rb = rb; P.nB = nB;

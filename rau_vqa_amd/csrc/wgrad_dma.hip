@@ -256,15 +256,14 @@ __global__ __launch_bounds__(256 * NG, 2) void k_wgrad_dma(const WgradParams P) 
 }  // namespace
 
 // Shapes it takes: 14 x 14 maps, both row counts multiples of 128.
-bool wgrad_dma_ok(int ra, int rb, int S) {
-  static const bool off = std::getenv("RAU_WGRAD_DMA_OFF") != nullptr;   // A/B knob
-  return !off && S == GS && ra % GT == 0 && rb % GT == 0;
+bool wgrad_dma_ok(const ConvMode& cm, int ra, int rb, int S) {
+  return cm.wgrad_dma && S == GS && ra % GT == 0 && rb % GT == 0;
 }
 
 // dW[ra, rb] += sum_{b,s} A[b,ra,s] B[b,rb,s]; slab: >= splits * ra * rb floats (conv_wgrad_slab_floats)
-hipError_t wgrad_dma(hipStream_t st, int nB, int ra, int rb, int S, const float* A, long a_bs,
+hipError_t wgrad_dma(hipStream_t st, const ConvMode& cm, int nB, int ra, int rb, int S, const float* A, long a_bs,
                      const float* B, long b_bs, float* dW, float* slab, int splits) {
-  if (!wgrad_dma_ok(ra, rb, S) || nB < 1 || splits < 1) return hipErrorInvalidValue;
+  if (!wgrad_dma_ok(cm, ra, rb, S) || nB < 1 || splits < 1) return hipErrorInvalidValue;
   WgradParams P{};
   P.ra = ra; P.rb = rb; P.nB = nB;
   P.tiles_a = ra / GT; P.tiles_b = rb / GT;
@@ -276,9 +275,8 @@ hipError_t wgrad_dma(hipStream_t st, int nB, int ra, int rb, int S, const float*
   // gradient (8 tiles: 1.26x -> 1.13x of the algorithmic bytes, time unchanged: 0.607 vs 0.601 of peak in the
   // step).  One for the i_embed weight gradient (16 tiles, 1.12x): there the eight waves on one barrier
   // measured slower (0.69-0.75 vs 0.73-0.79 of peak alone, 0.67 vs 0.72 in the step, step 9.45-9.51 vs
-  // 9.37-9.39 ms).  RAU_WGRAD_GROUPS=1|2 forces either form for both (A/B).
-  static const int genv = [] { const char* e = std::getenv("RAU_WGRAD_GROUPS"); return e ? std::atoi(e) : 0; }();
-  const int groups = genv == 1 || genv == 2 ? genv : (P.tiles_a * P.tiles_b <= 8 ? 2 : 1);
+  // 9.37-9.39 ms).  cm.wgrad_groups = 1 | 2 forces either form for both.
+  const int groups = cm.wgrad_groups ? cm.wgrad_groups : (P.tiles_a * P.tiles_b <= 8 ? 2 : 1);
   if (groups == 2 && splits >= 2) {
     const int s2 = (splits + 1) / 2;
     P.spb = (nB + s2 - 1) / s2;

@@ -43,7 +43,6 @@
 // dropout pass (philox.h: the backward regenerates).  They are never inferred from the masked map: a zero feature
 // under a kept bit keeps its gradient.  The hop sum is a fixed-order f32 sum, no atomics.
 #include <algorithm>
-#include <cstdlib>
 
 #include "common.h"
 #include "kernels.h"
@@ -394,16 +393,11 @@ hipError_t xgrad_accum_img(hipStream_t st, int slots, int D, int SL, int Sp, con
   return hipGetLastError();
 }
 
-// RAU_XGRAD_FUSED=1 (A/B knob) selects the fused kernel on the shapes it takes; the default is the unfused path,
-// which measured faster in the step (LOG.md: 11.85 vs 12.25 ms at configs[1]; one wave per SIMD costs the fused
-// tile more than the temporary's traffic costs the other).  Unlike the other knobs it is read at every launch, not
-// once per process, so that the tests run both paths against the oracle in one process.  A captured step keeps the
-// path that was current when it was captured (the graph key does not carry the variable): set it before the
-// process's first step and leave it, as with every A/B variable.
-bool xgrad_fused_ok(int D, int M, int S) {
-  const char* e = std::getenv("RAU_XGRAD_FUSED");
-  const int on = e ? std::atoi(e) : 0;
-  return on != 0 && S % 4 == 0 && S > 176 && S <= XBN && D % 4 == 0 && D > 0 && M > 0;
+// on (RAU_XGRAD_FUSED=1, an A/B knob) selects the fused kernel on the shapes it takes; the default is the unfused
+// path, which measured faster in the step (LOG.md: 11.85 vs 12.25 ms at configs[1]; one wave per SIMD costs the
+// fused tile more than the temporary's traffic costs the other).
+bool xgrad_fused_ok(bool on, int D, int M, int S) {
+  return on && S % 4 == 0 && S > 176 && S <= XBN && D % 4 == 0 && D > 0 && M > 0;
 }
 
 hipError_t xgrad_fused(hipStream_t st, int nh, int nB, int D, int M, int S, const float* dZ, const float* Wi,

@@ -1,5 +1,5 @@
 """One step with the feature-map gradient on, run as its own process by tests/test_gpu_featgrad.py: one setting of
-RAU_XGRAD_FUSED the way a user sets an A/B variable, before the process's first step.  The named problem under its
+RAU_XGRAD_FUSED the way a user sets an A/B variable, before the process creates its context.  The named problem under its
 explicit masks, dX saved to the given .npy file."""
 import os
 import sys

@@ -1,5 +1,5 @@
 """One parity check of the step path at 14x14 maps, run as its own process by tests/test_gpu_knobs.py
-(librau reads most A/B variables once per process).  Prints OK or raises."""
+(a context reads the A/B variables when it is created).  Prints OK or raises."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import util

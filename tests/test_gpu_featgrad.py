@@ -6,8 +6,8 @@ dX is compared with util.rel_err: f32 rows at TOL = 1e-4 (the project's gradient
 bar of tests/test_gpu_bf16.py (TOL_BASE + ONE_FLIP + SAFETY x the largest shift of the nudged emulations).
 
 Paths.  The default is the unfused path (GEMM of one hop into a temporary + masked accumulate); RAU_XGRAD_FUSED=1
-selects the fused kernel on the shapes it takes (it measured slower in the step: LOG.md).  librau reads this
-variable at every call, so the oracle rows run both paths in one process.
+selects the fused kernel on the shapes it takes (it measured slower in the step: LOG.md).  A context reads the
+variable when it is created, and every row creates its own, so the oracle rows run both paths in one process.
 
 Shapes.  X196 reaches the fused kernel with two row tiles (128 + 8 channels), a ragged K tail (M = 72 = 4.5 x 16) and
 13 column blocks of which 12 columns are pad; S = 192 is the other side of full column blocks; B = 5 an odd grid for

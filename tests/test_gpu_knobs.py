@@ -1,6 +1,6 @@
-"""Every A/B environment variable librau.so still reads (DESIGN.md section 9) keeps the parity bar:
+"""Every A/B environment variable librau.so still reads (DESIGN.md section 8) keeps the parity bar:
 each setting runs tests/knob_check.py -- train and evaluate mode against the fp64 oracle, 1e-4 -- in
-its own process, because most of them are read once per process."""
+its own process, the way a user sets one: before the process creates its first context."""
 import os
 import subprocess
 import sys

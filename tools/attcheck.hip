@@ -5,7 +5,7 @@
 #include <cstdlib>
 #include <vector>
 #include <cmath>
-#include "../rau_vqa_amd/csrc/kernels.h"
+#include "../rau_vqa_amd/csrc/policy.h"
 using namespace rau;
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); exit(1);} } while (0)
 static std::vector<std::vector<float>> keep;
@@ -25,7 +25,7 @@ int main(int argc, char** argv) {
   float* qf = dev_rand((size_t)nB * M, 0.5f);
   float *a, *jv; CK(hipMalloc(&a, (size_t)nB * S * 4)); CK(hipMalloc(&jv, (size_t)nB * M * 4));
   CK(hipMemset(a, 0, (size_t)nB * S * 4)); CK(hipMemset(jv, 0, (size_t)nB * M * 4));
-  CK(att_fwd_fused(st, nB, M, A, S, P, u, ws, bs, zm, I, qf, nullptr, a, jv));
+  CK(att_fwd_fused(st, att_mode(policy_from_env(), 0, false), nB, M, A, S, P, u, ws, bs, zm, I, qf, nullptr, a, jv));
   CK(hipStreamSynchronize(st));
   std::vector<float> h((size_t)nB * (S + M));
   CK(hipMemcpy(h.data(), a, (size_t)nB * S * 4, hipMemcpyDeviceToHost));

@@ -9,7 +9,7 @@
 #include <functional>
 #include <vector>
 #include <cmath>
-#include "../rau_vqa_amd/csrc/kernels.h"
+#include "../rau_vqa_amd/csrc/policy.h"
 #include "exp_fwd16.h"
 #include "exp_wide2.h"
 using namespace rau;
@@ -62,6 +62,7 @@ int main(int argc, char** argv) {
   const char* what = argc > 2 ? argv[2] : "all";
   auto want = [&](const char* w) { return !strcmp(what, "all") || !strcmp(what, w); };
   const int S = 196, M = 512, A = 256;
+  const ConvMode cm = conv_mode(policy_from_env(), 0, false);   // the A/B variables, as the library reads them
   hipStream_t st; CK(hipStreamCreate(&st));
   srand(1234);
 
@@ -76,7 +77,7 @@ int main(int argc, char** argv) {
       float *I0, *I1; CK(hipMalloc(&I0, (size_t)nB * M * S * 4)); CK(hipMalloc(&I1, (size_t)nB * M * S * 4));
       CK(hipMemset(I0, 0xff, (size_t)nB * M * S * 4)); CK(hipMemset(I1, 0xee, (size_t)nB * M * S * 4));
       const double fl = 2.0 * M * (double)nB * S * D;
-      CK(conv_embed_fwd(st, nB, D, S, M, X, WiT, bi, I0, 0, 0));
+      CK(conv_embed_fwd(st, cm, nB, D, S, M, X, WiT, bi, I0));
       CK(conv_wide(st, 0, nB, M, D, S, WiT, M, X, (long)D * S, I1, (long)M * S, bi, 1, nullptr, nullptr, nullptr, nullptr, 0, 2));
       CK(hipStreamSynchronize(st));
       compare("wide(2/CU) vs round-2 kernel", I1, I0, (size_t)nB * M * S);
@@ -97,7 +98,7 @@ int main(int argc, char** argv) {
           report("wide2 128x392, 1 per CU", timeit(st, 10, [&] { return conv_wide2(st, nB, M, D, S, WiT, M, X, (long)D * S, I1, (long)M * S, bi, 1, 1); }), fl);
           report("wide2 128x392, 2 per CU", timeit(st, 10, [&] { return conv_wide2(st, nB, M, D, S, WiT, M, X, (long)D * S, I1, (long)M * S, bi, 1, 2); }), fl);
         }
-        report("round-2 flattened 128x128", timeit(st, 10, [&] { return conv_embed_fwd(st, nB, D, S, M, X, WiT, bi, I0, 0, 0); }), fl);
+        report("round-2 flattened 128x128", timeit(st, 10, [&] { return conv_embed_fwd(st, cm, nB, D, S, M, X, WiT, bi, I0); }), fl);
         report("round-2 per-sample 128x208", timeit(st, 10, [&] { return conv_sample(st, 0, nB, M, D, S, WiT, M, X, (long)D * S, I0, (long)M * S, bi, 1, nullptr, nullptr); }), fl);
         report("wide 64x784, 2 per CU", timeit(st, 10, [&] { return conv_wide(st, 0, nB, M, D, S, WiT, M, X, (long)D * S, I1, (long)M * S, bi, 1, nullptr, nullptr, nullptr, nullptr, 0, 2); }), fl);
         report("wide 64x784, 1 per CU", timeit(st, 10, [&] { return conv_wide(st, 0, nB, M, D, S, WiT, M, X, (long)D * S, I1, (long)M * S, bi, 1, nullptr, nullptr, nullptr, nullptr, 0, 1); }), fl);
@@ -115,7 +116,7 @@ int main(int argc, char** argv) {
       float *P0, *P1; CK(hipMalloc(&P0, (size_t)nB * A * S * 4)); CK(hipMalloc(&P1, (size_t)nB * A * S * 4));
       CK(hipMemset(P0, 0xff, (size_t)nB * A * S * 4)); CK(hipMemset(P1, 0xee, (size_t)nB * A * S * 4));
       const double fl = 2.0 * A * (double)nB * S * M;
-      CK(conv_att_pre(st, nB, M, S, A, I, WpT, bp, P0, 0, 0));
+      CK(conv_att_pre(st, cm, nB, M, S, A, I, WpT, bp, P0));
       CK(conv_wide(st, 0, nB, A, M, S, WpT, A, I, (long)M * S, P1, (long)A * S, bp, 0, nullptr, nullptr, nullptr, nullptr, 0, 2));
       CK(hipStreamSynchronize(st));
       compare("wide vs round-2 kernel", P1, P0, (size_t)nB * A * S);
@@ -130,7 +131,7 @@ int main(int argc, char** argv) {
           report("wide2 128x392, 1 per CU", timeit(st, 10, [&] { return conv_wide2(st, nB, A, M, S, WpT, A, I, (long)M * S, P1, (long)A * S, bp, 0, 1); }), fl);
           report("wide2 128x392, 2 per CU", timeit(st, 10, [&] { return conv_wide2(st, nB, A, M, S, WpT, A, I, (long)M * S, P1, (long)A * S, bp, 0, 2); }), fl);
         }
-        report("round-2 flattened 128x128", timeit(st, 10, [&] { return conv_att_pre(st, nB, M, S, A, I, WpT, bp, P0, 0, 0); }), fl);
+        report("round-2 flattened 128x128", timeit(st, 10, [&] { return conv_att_pre(st, cm, nB, M, S, A, I, WpT, bp, P0); }), fl);
         report("wide 64x784, 2 per CU", timeit(st, 10, [&] { return conv_wide(st, 0, nB, A, M, S, WpT, A, I, (long)M * S, P1, (long)A * S, bp, 0, nullptr, nullptr, nullptr, nullptr, 0, 2); }), fl);
         report("wide 64x784, 1 per CU", timeit(st, 10, [&] { return conv_wide(st, 0, nB, A, M, S, WpT, A, I, (long)M * S, P1, (long)A * S, bp, 0, nullptr, nullptr, nullptr, nullptr, 0, 1); }), fl);
       }
@@ -156,9 +157,9 @@ int main(int argc, char** argv) {
       CK(hipStreamSynchronize(st));
       compare("dZ: wide vs round-2 per-sample", Z1, Z0, (size_t)nB * M * S);
       compare("row sums", r1, r0, (size_t)nB * M);
-      if (dgrad_dma_ok(M, A, S, M)) {   // round 4: per-sample tiles fed by LDS-DMA (dgrad_dma.hip)
+      if (dgrad_dma_ok(cm, M, A, S, M)) {   // round 4: per-sample tiles fed by LDS-DMA (dgrad_dma.hip)
         CK(hipMemset(Z1, 0xdd, (size_t)nB * M * S * 4)); CK(hipMemset(r1, 0xdd, (size_t)nB * M * 4));
-        CK(dgrad_dma(st, nB, M, A, S, Wp, M, dS, (long)A * S, Z1, (long)M * S, dj, av, I, r1));
+        CK(dgrad_dma(st, cm, nB, M, A, S, Wp, M, dS, (long)A * S, Z1, (long)M * S, dj, av, I, r1));
         CK(hipStreamSynchronize(st));
         compare("dZ: dgrad_dma vs round-2 per-sample", Z1, Z0, (size_t)nB * M * S);
         compare("row sums (dgrad_dma)", r1, r0, (size_t)nB * M);
@@ -167,8 +168,8 @@ int main(int argc, char** argv) {
         report("round-2 per-sample 128x208", timeit(st, 10, [&] { return conv_sample(st, 2, nB, M, A, S, Wp, M, dS, (long)A * S, Z0, (long)M * S, nullptr, 0, dj, av, I, r0, 0); }), fl);
         report("wide 64x784, 2 per CU", timeit(st, 10, [&] { return conv_wide(st, 2, nB, M, A, S, Wp, M, dS, (long)A * S, Z1, (long)M * S, nullptr, 0, dj, av, I, r1, 0, 2); }), fl);
         report("wide 64x784, 1 per CU", timeit(st, 10, [&] { return conv_wide(st, 2, nB, M, A, S, Wp, M, dS, (long)A * S, Z1, (long)M * S, nullptr, 0, dj, av, I, r1, 0, 1); }), fl);
-        if (dgrad_dma_ok(M, A, S, M))
-          report("dgrad_dma per-sample 128x208 (RAU_DGRAD_DMA=2|3: ring depth)", timeit(st, 10, [&] { return dgrad_dma(st, nB, M, A, S, Wp, M, dS, (long)A * S, Z1, (long)M * S, dj, av, I, r1); }), fl);
+        if (dgrad_dma_ok(cm, M, A, S, M))
+          report("dgrad_dma per-sample 128x208 (RAU_DGRAD_DMA=2|3: ring depth)", timeit(st, 10, [&] { return dgrad_dma(st, cm, nB, M, A, S, Wp, M, dS, (long)A * S, Z1, (long)M * S, dj, av, I, r1); }), fl);
       }
       CK(hipFree(dS)); CK(hipFree(Wp)); CK(hipFree(dj)); CK(hipFree(av)); CK(hipFree(I));
       CK(hipFree(Z0)); CK(hipFree(Z1)); CK(hipFree(r0)); CK(hipFree(r1));
@@ -188,7 +189,7 @@ int main(int argc, char** argv) {
       CK(hipMemcpy(dB, hB.data(), hB.size() * 4, hipMemcpyHostToDevice));
       CK(hipMalloc(&dW, (size_t)M * D * 4)); CK(hipMemset(dW, 0, (size_t)M * D * 4));
       CK(hipMalloc(&slab, conv_wgrad_slab_floats(nb, M, D, S) * 4)); rau::split_ws_register(slab, (conv_wgrad_slab_floats(nb, M, D, S) * 4) / 4);
-      CK(conv_embed_wgrad(st, nb, D, S, M, dA, nullptr, dB, dW, slab, 0, nullptr, 1));
+      CK(conv_embed_wgrad(st, cm, nb, D, S, M, dA, nullptr, dB, dW, slab, nullptr, 1));
       CK(hipStreamSynchronize(st));
       std::vector<float> hW((size_t)M * D);
       CK(hipMemcpy(hW.data(), dW, hW.size() * 4, hipMemcpyDeviceToHost));
@@ -213,8 +214,8 @@ int main(int argc, char** argv) {
       CK(hipMalloc(&slab, sl * 4)); rau::split_ws_register(slab, (sl * 4) / 4);
       printf("conv weight gradients  nB=%d\n", nB);
       for (int rep = 0; rep < 2; ++rep) {
-        report("conv_att_wgrad (256 x 512)", timeit(st, 10, [&] { return conv_att_wgrad(st, nB, M, S, A, dS, I, dWp, slab, 0); }), 2.0 * A * M * (double)nB * S);
-        report("conv_embed_wgrad (512 x 512)", timeit(st, 10, [&] { return conv_embed_wgrad(st, nB, D, S, M, dZ, nullptr, X, dWi, slab, 0, nullptr, 1); }), 2.0 * M * D * (double)nB * S);
+        report("conv_att_wgrad (256 x 512)", timeit(st, 10, [&] { return conv_att_wgrad(st, cm, nB, M, S, A, dS, I, dWp, slab); }), 2.0 * A * M * (double)nB * S);
+        report("conv_embed_wgrad (512 x 512)", timeit(st, 10, [&] { return conv_embed_wgrad(st, cm, nB, D, S, M, dZ, nullptr, X, dWi, slab, nullptr, 1); }), 2.0 * M * D * (double)nB * S);
       }
       CK(hipFree(dS)); CK(hipFree(I)); CK(hipFree(dZ)); CK(hipFree(X)); CK(hipFree(dWp)); CK(hipFree(dWi)); CK(hipFree(slab));
     }
@@ -235,9 +236,9 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(dA, hA.data(), hA.size() * 2, hipMemcpyHostToDevice));
         CK(hipMemcpy(dB, hB.data(), hB.size() * 2, hipMemcpyHostToDevice));
         CK(hipMalloc(&dW, (size_t)M * D * 4)); CK(hipMemset(dW, 0, (size_t)M * D * 4));
-        size_t sl = conv_wgrad_slab_floats(nb, M, D, S); if (wgrad16_slab_floats(nb, M, D, S) > sl) sl = wgrad16_slab_floats(nb, M, D, S);
+        size_t sl = conv_wgrad_slab_floats(nb, M, D, S); if (wgrad16_slab_floats(cm, nb, M, D, S) > sl) sl = wgrad16_slab_floats(cm, nb, M, D, S);
         CK(hipMalloc(&slab, sl * 4)); rau::split_ws_register(slab, (sl * 4) / 4);
-        CK(conv_embed_wgrad_b16(st, nb, D, S, M, dA, dB, dW, slab));
+        CK(conv_embed_wgrad_b16(st, cm, nb, D, S, M, dA, dB, dW, slab));
         CK(hipStreamSynchronize(st));
         std::vector<float> hW((size_t)M * D);
         CK(hipMemcpy(hW.data(), dW, hW.size() * 4, hipMemcpyDeviceToHost));
@@ -259,11 +260,11 @@ int main(int argc, char** argv) {
         CK(hipMalloc(&dZ, (size_t)nB * M * S * 2)); CK(hipMalloc(&X, (size_t)nB * D * S * 2));
         CK(hipMemset(dZ, 0x3c, (size_t)nB * M * S * 2)); CK(hipMemset(X, 0x3b, (size_t)nB * D * S * 2));
         CK(hipMalloc(&dWi, (size_t)M * D * 4));
-        size_t sl = conv_wgrad_slab_floats(nB, M, D, S); if (wgrad16_slab_floats(nB, M, D, S) > sl) sl = wgrad16_slab_floats(nB, M, D, S);
+        size_t sl = conv_wgrad_slab_floats(nB, M, D, S); if (wgrad16_slab_floats(cm, nB, M, D, S) > sl) sl = wgrad16_slab_floats(cm, nB, M, D, S);
         CK(hipMalloc(&slab, sl * 4)); rau::split_ws_register(slab, (sl * 4) / 4);
         const double bytes = ((double)nB * M * S + (double)nB * D * S) * 2;
         for (int rep = 0; rep < 2; ++rep) {
-          const double us = timeit(st, 10, [&] { return conv_embed_wgrad_b16(st, nB, D, S, M, dZ, X, dWi, slab); });
+          const double us = timeit(st, 10, [&] { return conv_embed_wgrad_b16(st, cm, nB, D, S, M, dZ, X, dWi, slab); });
           printf("  conv_embed_wgrad_b16 D=%d nB=%d: %.1f us  %.2f TB/s algorithmic  %.0f TFLOP/s\n", D, nB, us,
                  bytes / us * 1e-6, 2.0 * M * D * (double)nB * S / us * 1e-6);
         }

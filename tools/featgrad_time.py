@@ -11,8 +11,8 @@ of the timed window:
   * parent_ms   the step of ANOTHER build of the library given with --parent-lib (the commit before this feature,
                 built by the caller: it is not part of the tree).
 Method: every leg is warmed up, then timed over --steps steps, --rounds times; off / on / tied alternate inside one
-process, started with RAU_XGRAD_FUSED=0; the fused leg runs in a child started with RAU_XGRAD_FUSED=1 (the library
-reads the variable at every launch; a process per setting keeps the legs apart) and the parent library runs as a
+process, started with RAU_XGRAD_FUSED=0; the fused leg runs in a child started with RAU_XGRAD_FUSED=1 (a context
+reads the variable when it is created; a process per setting keeps the legs apart) and the parent library runs as a
 child process of its own BEFORE and AFTER this build's.  Reported per leg: the median of the rounds and their spread
 (max - min); fused_gain_ms = on - fused, and fused_beats_default says whether that exceeds the larger of the two
 spreads.  A last pair of children profiles one step with the switch on (profile_on: the default, profile_fused:

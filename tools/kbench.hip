@@ -7,7 +7,7 @@
 #include <functional>
 #include <vector>
 #include "../rau_vqa_amd/csrc/gemm_core.h"
-#include "../rau_vqa_amd/csrc/kernels.h"
+#include "../rau_vqa_amd/csrc/policy.h"
 #include <cstring>
 using namespace rau;
 
@@ -102,6 +102,9 @@ static void report(const char* name, double us, double flops) {
 int main(int argc, char** argv) {
   const int B = argc > 1 ? atoi(argv[1]) : 256;
   const int D = 512, S = 196, M = 512, A = 256;
+  const Policy pol = policy_from_env();   // the A/B variables, as the library reads them
+  const ConvMode cm = conv_mode(pol, 0, false);
+  const AttMode am = att_mode(pol, 0, false);
   hipStream_t st; CK(hipStreamCreate(&st));
   float* X = dev_rand((size_t)B * D * S);
   float* Wi = dev_rand((size_t)M * D, 0.08f), *bi = dev_rand(M, 0.08f);
@@ -167,7 +170,7 @@ int main(int argc, char** argv) {
     return 0;
   }
   if (only[0] && strcmp(only, "conv") && strcmp(only, "all")) return 0;
-  report("conv_embed_fwd", timeit(st, 20, [&] { return conv_embed_fwd(st, B, D, S, M, X, Wi, bi, I); }), 2.0 * M * NS * D);
+  report("conv_embed_fwd", timeit(st, 20, [&] { return conv_embed_fwd(st, cm, B, D, S, M, X, Wi, bi, I); }), 2.0 * M * NS * D);
   {
     const int H = 8;
     float* xd; CK(hipMalloc(&xd, (size_t)H * B * D * S * 4));
@@ -175,18 +178,18 @@ int main(int argc, char** argv) {
     uint32_t* m8; CK(hipMalloc(&m8, (size_t)H * B * D * S / 8 + 64));
     CK(fill_masks(st, 1, 3, 0, 0.5f, (size_t)H * B * D * S, m8));
     report("dropout_features x8", timeit(st, 10, [&] { return dropout_features(st, H, (size_t)B * D * S, X, m8, 2.f, xd); }), 0);
-    report("conv_embed_fwd x8 hops", timeit(st, 5, [&] { return conv_embed_fwd(st, H * B, D, S, M, xd, Wi, bi, I8); }), 2.0 * M * NS * D * H);
-    report("conv_embed_wgrad x8 hops", timeit(st, 5, [&] { return conv_embed_wgrad(st, H * B, D, S, M, I8, I8, xd, dWi, slab); }), 2.0 * M * NS * D * H);
+    report("conv_embed_fwd x8 hops", timeit(st, 5, [&] { return conv_embed_fwd(st, cm, H * B, D, S, M, xd, Wi, bi, I8); }), 2.0 * M * NS * D * H);
+    report("conv_embed_wgrad x8 hops", timeit(st, 5, [&] { return conv_embed_wgrad(st, cm, H * B, D, S, M, I8, I8, xd, dWi, slab); }), 2.0 * M * NS * D * H);
     CK(hipFree(xd)); CK(hipFree(I8)); CK(hipFree(m8));
   }
-  report("conv_att_pre", timeit(st, 20, [&] { return conv_att_pre(st, B, M, S, A, I, Wp, bp, T); }), 2.0 * A * NS * M);
+  report("conv_att_pre", timeit(st, 20, [&] { return conv_att_pre(st, cm, B, M, S, A, I, Wp, bp, T); }), 2.0 * A * NS * M);
   { float* jv; CK(hipMalloc(&jv, (size_t)B * M * 4));
-    report("att_fwd_fused", timeit(st, 20, [&] { return att_fwd_fused(st, B, M, A, S, T, u, ws, bp, dz, I, dj, T, a, jv); }), 0);
+    report("att_fwd_fused", timeit(st, 20, [&] { return att_fwd_fused(st, am, B, M, A, S, T, u, ws, bp, dz, I, dj, T, a, jv); }), 0);
     float* du; CK(hipMalloc(&du, (size_t)B * A * 8));
-    report("att_bwd_fused", timeit(st, 20, [&] { return att_bwd_fused(st, B, M, A, S, I, dj, a, dz, ws, T, epart, du, du + B * A); }), 0); }
-  report("conv_att_dgrad", timeit(st, 20, [&] { return conv_att_dgrad(st, B, M, S, A, T, Wp, dj, a, dZ); }), 2.0 * A * NS * M);
-  report("conv_att_wgrad", timeit(st, 20, [&] { return conv_att_wgrad(st, B, M, S, A, T, I, dWp, slab); }), 2.0 * A * NS * M);
-  report("conv_embed_wgrad", timeit(st, 20, [&] { return conv_embed_wgrad(st, B, D, S, M, dZ, I, X, dWi, slab); }), 2.0 * M * NS * D);
+    report("att_bwd_fused", timeit(st, 20, [&] { return att_bwd_fused(st, am, B, M, A, S, I, dj, a, dz, ws, T, epart, du, du + B * A); }), 0); }
+  report("conv_att_dgrad", timeit(st, 20, [&] { return conv_att_dgrad(st, cm, B, M, S, A, T, Wp, dj, a, dZ); }), 2.0 * A * NS * M);
+  report("conv_att_wgrad", timeit(st, 20, [&] { return conv_att_wgrad(st, cm, B, M, S, A, T, I, dWp, slab); }), 2.0 * A * NS * M);
+  report("conv_embed_wgrad", timeit(st, 20, [&] { return conv_embed_wgrad(st, cm, B, D, S, M, dZ, I, X, dWi, slab); }), 2.0 * M * NS * D);
   // small GEMMs
   float* h = dev_rand((size_t)B * 2048, 0.5f), *W = dev_rand((size_t)2048 * 2048, 0.08f);
   float* C; CK(hipMalloc(&C, (size_t)8 * B * 2048 * 4));

@@ -10,7 +10,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "../rau_vqa_amd/csrc/kernels.h"
+#include "../rau_vqa_amd/csrc/policy.h"
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); return 1; } } while (0)
 
@@ -18,7 +18,7 @@ static float frand(unsigned& s) { s = s * 1664525u + 1013904223u; return ((s >> 
 
 int main(int argc, char** argv) {
   const int M = argc > 1 ? atoi(argv[1]) : 256;
-  rau::LinMode mode;
+  rau::LinMode mode = rau::lin_mode(rau::policy_from_env(), 0, false);   // RAU_SKINNY_* as the library reads them
   if (argc > 2 && atoi(argv[2])) { mode.deep = 1; printf("32-deep stages\n"); }
   if (argc > 3 && atoi(argv[3])) { mode.bf16 = 1; printf("bf16 products\n"); }
   const int woff = argc > 4 ? atoi(argv[4]) : 0;   // W starts `woff` floats behind a 16-byte boundary
