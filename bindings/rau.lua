@@ -119,6 +119,10 @@ int rau_feat_grad(rau_ctx* ctx, int* on);
 int rau_feat_grad_dev(rau_ctx* ctx, const float** dX, int32_t* pitch);
 int rau_feat_grad_rows(rau_ctx* ctx, int32_t* rows);
 int rau_get_feat_grad(rau_ctx* ctx, float* host);
+int rau_set_feat_norm(rau_ctx* ctx, int kind, float eps);
+int rau_feat_norm(rau_ctx* ctx, int* kind, float* eps);
+int rau_norm_feats_dev(rau_ctx* ctx, const float** xn, const float** nrm, int32_t* pitch, int32_t* rows);
+int rau_get_norm_feats(rau_ctx* ctx, float* xn_host, float* nrm_host);
 int rau_set_batch_dev(rau_ctx* ctx, const float* feats_dev, const int32_t* tokens, const int32_t* lens, const int32_t* labels);
 int rau_set_question_dev(rau_ctx* ctx, const void* q_dev, int q_type);
 int rau_batch_question(rau_ctx* ctx, int* has);
@@ -186,6 +190,8 @@ int rau_dev_adam(rau_ctx* ctx, float* x, const float* dx, float* m, float* v, si
 int rau_dev_adamax(rau_ctx* ctx, float* x, const float* dx, float* m, float* u, size_t n, float lr,
                    float beta1, float beta2, float eps, int32_t t);
 int rau_dev_scale_rows(rau_ctx* ctx, float* x, int32_t rows, int32_t cols, int32_t ld, const float* s_dev);
+int rau_dev_l2norm(rau_ctx* ctx, const float* x_dev, int32_t n, float eps, float* y_dev, float* nrm_dev);
+int rau_dev_l2norm_backward(rau_ctx* ctx, const float* y_dev, const float* nrm_dev, float eps, const float* g_dev, int32_t n, float* dx_dev);
 int rau_dev_select_rows(rau_ctx* ctx, float* dst, const float* src, int32_t rows, int32_t cols,
                         const int32_t* key_dev, int32_t value);
 int rau_dev_rowmax(rau_ctx* ctx, const float* x, int32_t rows, int32_t cols, float* max_dev,
@@ -700,6 +706,30 @@ function RAU:featureGrad()
   local p, pitch = ffi.new('const float*[1]'), ffi.new('int32_t[1]')
   check(C.rau_feat_grad_dev(self.h, p, pitch))
   return p[0], pitch[0]
+end
+-- Per-position L2 normalisation of the batch's maps (rau_set_feat_norm): with the switch on every forward / graphStep
+-- first normalises each position's channel vector, x / max(||x||_2, eps) in float32 whatever the stored type, and runs
+-- on the result as on a float32 batch; with wantFeatureGrad the gradient goes back through it to the raw maps.
+-- on = false goes back to the maps as stored; eps defaults to 1e-12.  Between steps; a change drops the last forward.
+RAU.XNORM_NONE, RAU.XNORM_L2 = 0, 1
+function RAU:normalizeFeatures(on, eps)
+  check(C.rau_set_feat_norm(self.h, (on == nil or on) and RAU.XNORM_L2 or RAU.XNORM_NONE, eps or 1e-12))
+  return self
+end
+-- kind (RAU.XNORM_*) and eps (rau_feat_norm)
+function RAU:featNorm()
+  local kind, eps = ffi.new('int[1]'), ffi.new('float[1]')
+  check(C.rau_feat_norm(self.h, kind, eps))
+  return kind[0], eps[0]
+end
+-- the last forward's normalised maps in device memory: const float* cdata xn [rows,D,pitch] and nrm [rows,pitch], the
+-- pitch and the map count (rau_norm_feats_dev: N after the evaluate-mode forward of an image table, else n); valid
+-- until the next forward, ordered on the ctx's stream
+function RAU:normFeats()
+  local xn, nrm = ffi.new('const float*[1]'), ffi.new('const float*[1]')
+  local pitch, rows = ffi.new('int32_t[1]'), ffi.new('int32_t[1]')
+  check(C.rau_norm_feats_dev(self.h, xn, nrm, pitch, rows))
+  return xn[0], nrm[0], pitch[0], rows[0]
 end
 -- setBatch with the maps already on the device: feats_dev a DEVICE float* to dense [n,D,S] float32, ordered by the
 -- caller in front of the ctx's stream (rau_set_batch_dev); x, x_len, y host tensors as in setBatch

@@ -873,6 +873,51 @@ int rau_set_batch_dev_images(rau_ctx* ctx, const float* table_dev /* [N,D,S] f32
                              const int32_t* image_of /* host [n] */, const int32_t* tokens, const int32_t* lens,
                              const int32_t* labels);
 
+/* ---- per-position L2 normalisation of the feature maps, on the device ---------------------------------------------
+ * Grid-feature pipelines (SAN, HieCoAtt, MCB, MLB, MUTAN on res5c maps) normalise every position's channel vector
+ * before attention.  rau_set_feat_norm(ctx, RAU_XNORM_L2, eps) makes every step-level forward do that first, for each
+ * map x [D,S] of the batch and each position s:
+ *   nrm[s]  = sqrt(sum_d x[d,s]^2)               x widened exactly to float32 first, whatever the stored type
+ *   xn[d,s] = x[d,s] * (1 / max(nrm[s], eps))    torch.nn.functional.normalize(x, p=2, dim=channel, eps=eps)
+ * and everything behind it -- dropout in every form, both convs, the weight gradients that read the maps -- runs on
+ * xn as on a float32 batch, launch for launch: the results are bit for bit those of a context with the switch off
+ * that was given xn as a plain batch.  So 16-bit and fp8 maps are stored raw, widened exactly and normalised in f32.
+ *   values       an all-zero position gives nrm = 0 and +0 outputs; pad columns (S <= s < pitch) of xn and nrm are
+ *                +0; region counts do not enter (all S positions are normalised, the attention ignores what lies
+ *                behind a count as before).  Non-finite inputs, and inputs whose sum of squares overflows float32,
+ *                are outside the contract.
+ *   order        the sum over D is a fixed-order float32 sum (each square and each addition rounded once, no fma, no
+ *                atomics) that depends on (D, S, pitch) alone: the same map gives the same bits as a sample's map, a
+ *                row of an image table and a bank row, in every call, eagerly and in a replay.
+ *   maps         the pass runs over the maps the image side reads: the N table rows in the evaluate-mode forward of
+ *                an image-table or bank batch, else the n per-sample maps.
+ *   gradient     with rau_set_feat_grad on, one more launch takes the feature-map gradient back through the
+ *                normalisation, in place: with G the gradient at xn, c[s] = sum_d G[d,s] xn[d,s] (the same fixed
+ *                order) and r = 1 / max(nrm, eps):  dX = r (G - xn c) where nrm >= eps,  dX = r G (= G / eps) where
+ *                nrm < eps (the forward is linear there).  rau_feat_grad_dev / rau_get_feat_grad then hold the
+ *                gradient at the RAW maps (per image under RAU_FEAT_GRAD_IMAGES: an image no sample names keeps its
+ *                zero row).  Pad columns stay +0.
+ *   the switch   off by default (RAU_XNORM_NONE): such a context allocates, launches and computes exactly what it did
+ *                without this call.  eps must be finite and > 0 (else RAU_ERR_INVALID, like an unknown kind); while
+ *                a step is being captured: RAU_ERR_STATE.  Setting the same kind and eps again changes nothing.  Any
+ *                change drops the last forward: no backward, statistics or outputs until a new forward has run.
+ *                xn [capacity, D, pitch] and nrm [capacity, pitch] are allocated at the first call that turns the
+ *                switch on (RAU_ERR_NOMEM leaves the switch as it was) and cleared by rau_set_batch_size, which
+ *                keeps the switch.  Kind and the bits of eps join rau_graph_step's key; a replay normalises what
+ *                the slot holds then.  The pass runs in every forward; xn is not cached across steps.
+ * rau_feat_norm reports kind and eps (either pointer may be NULL).
+ * rau_norm_feats_dev: the ctx-owned DEVICE pointers to the last forward's xn [rows, D, *pitch] and nrm [rows, *pitch]
+ * (rows: N after an evaluate-mode table forward, else n), ordered on the ctx's stream; synchronises nothing; any
+ * output pointer may be NULL.  RAU_ERR_STATE when the switch is off or no forward has run since it was set.
+ * rau_get_norm_feats: the download, dense; synchronises; same state rules. */
+#define RAU_XNORM_NONE 0   /* the default */
+#define RAU_XNORM_L2   1
+int rau_set_feat_norm(rau_ctx* ctx, int kind, float eps);
+int rau_feat_norm(rau_ctx* ctx, int* kind, float* eps);
+int rau_norm_feats_dev(rau_ctx* ctx, const float** xn, const float** nrm, int32_t* pitch, int32_t* rows);
+int rau_get_norm_feats(rau_ctx* ctx, float* xn_host /* [rows,D,S] dense, may be NULL */,
+                       float* nrm_host /* [rows,S] dense, may be NULL */);
+
 /* ---- question state from the caller: the step path behind another question encoder ------------------------------
  * The step path's own encoder is the reference's (LookupTable, two-layer LSTM, length select); its output q [n,Q] is
  * the only thing the hops read of it, and dq [n,Q] the only thing its backward reads of the hops.  These calls make
@@ -1075,6 +1120,14 @@ int rau_dev_select_rows(rau_ctx* ctx, float* dst, const float* src, int32_t rows
  * cols..ld-1 are not touched.  For module-level hosts that weight a [B, K] criterion gradient per sample themselves.
  * 16-byte accesses where ld % 4 == 0 and x is 16-byte aligned; any cols.  Not synchronising. */
 int rau_dev_scale_rows(rau_ctx* ctx, float* x, int32_t rows, int32_t cols, int32_t ld, const float* s_dev /* [rows] */);
+/* The two kernels of rau_set_feat_norm (above) for hosts that drive the module-level calls and own their X: dense
+ * float32 [n,D,S] tensors in device memory, D and S the context's, any n >= 0, on the ctx's stream, not synchronising.
+ * rau_dev_l2norm: y = normalize(x) and, unless NULL, nrm [n,S].  rau_dev_l2norm_backward: dx = the gradient at x for
+ * the gradient g at y, from the forward's y and nrm.  Where S % 4 == 0 every pointer must be 16-byte aligned. */
+int rau_dev_l2norm(rau_ctx* ctx, const float* x_dev /* [n,D,S] dense f32 */, int32_t n, float eps,
+                   float* y_dev /* may alias x_dev */, float* nrm_dev /* [n,S], may be NULL */);
+int rau_dev_l2norm_backward(rau_ctx* ctx, const float* y_dev, const float* nrm_dev, float eps,
+                            const float* g_dev, int32_t n, float* dx_dev /* may alias g_dev */);
 /* torch.max(x, 2): per-row maximum and FIRST maximal index, 1-based (either output may be NULL) */
 int rau_dev_rowmax(rau_ctx* ctx, const float* x, int32_t rows, int32_t cols, float* max_dev,
                    int32_t* argmax_dev);

@@ -25,6 +25,7 @@ XDROP_PER_HOP, XDROP_TIED = 0, 1
 LOSS_CE, LOSS_BCE = 0, 1
 LOSSES = {"ce": LOSS_CE, "bce": LOSS_BCE}
 FEAT_GRAD_OFF, FEAT_GRAD_SAMPLES, FEAT_GRAD_IMAGES = 0, 1, 2
+XNORM_NONE, XNORM_L2 = 0, 1
 
 
 class RauConfig(C.Structure):
@@ -180,6 +181,12 @@ _SIGS = {
     "rau_feat_grad_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
     "rau_feat_grad_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "rau_get_feat_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # per-position L2 normalisation of the batch's maps in front of the image side
+    "rau_set_feat_norm": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "rau_feat_norm": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "rau_norm_feats_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rau_get_norm_feats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_set_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rau_set_batch_dev_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
@@ -235,6 +242,9 @@ _SIGS = {
     "rau_dev_adamax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32]),
     "rau_dev_scale_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "rau_dev_l2norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "rau_dev_l2norm_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32,
+                                          C.c_void_p]),
     "rau_dev_select_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_void_p, C.c_int32]),
     "rau_dev_rowmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,

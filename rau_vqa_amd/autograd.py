@@ -20,6 +20,9 @@ The built-in terms (hop_w, select_w, att_w, merge_w) are given to ``step`` and j
 
 The backward then returns a clone of ``rau.feature_grad_tensor()`` for x, ordered with events as the outputs are.
 
+With ``rau.normalize_features()`` on, the library L2-normalises x per position itself and x.grad is the gradient at the
+raw x (through the normalisation): nothing changes in the calls above.
+
 Questions that share images: ``rau.want_feature_grad(per_image=True)``, ``rau.set_batch_dev(table, ..., image_of=idx)``
 and ``step(rau, hop_w, feats=table)`` with the table [N,D,S] itself; table.grad is then the per-image sum, formed by
 the library in a fixed order (the same bits from run to run, which an index_select backward does not give).

@@ -403,6 +403,22 @@ hipError_t dropout_features_b16(hipStream_t st, int H, size_t per_hop, const voi
 // out[r][s] = widen(X[r][s]) for s < SL, 0 for SL <= s < Sp: the f32 image of a 16-bit or fp8 feature map
 // (any ft but RAU_FEAT_F32) at row pitch Sp, for the readers that take the unmasked batch
 hipError_t widen_features(hipStream_t st, size_t rows, int SL, int Sp, const void* X, float* out, int ft);
+// Per-position L2 normalisation (featnorm.hip): for each of n_maps maps [D][Sp] of element type ft,
+//   nrm[m][s] = sqrt(sum_d x[d][s]^2),  xn[m][d][s] = x[d][s] * (1 / max(nrm[m][s], eps))
+// on the exactly widened values, in f32, the sum in a fixed order that depends on (D, SL, Sp) alone; an all-zero
+// position gives nrm = 0 and +0 outputs; columns SL <= s < Sp of xn and nrm are written as +0.  Sp % 4 == 0, or
+// SL == Sp (a dense tensor: single-element accesses).  xn may be X (f32, in place); nrm may be null.  Non-finite
+// inputs and sums of squares that overflow f32 are outside the contract.  eps finite and > 0.
+hipError_t l2norm_features(hipStream_t st, int n_maps, int D, int SL, int Sp, const void* X, int ft, float eps,
+                           float* xn, float* nrm);
+// Its gradient, in place on dX [rows][D][Sp] (on entry the gradient G at xn): with c[s] = sum_d G[d][s] xn[d][s] in the
+// same fixed order and r = 1 / max(nrm, eps), dX = r (G - xn c) where nrm >= eps and r G where nrm < eps; pad
+// columns leave as +0.  Row i reads map i of xn / nrm, or -- with the per-image sample lists of an image table
+// (img_start [rows + 1], img_samples; both or neither) -- the map of the first sample of list i; a row whose list
+// is empty is not touched.
+hipError_t l2norm_backward(hipStream_t st, int rows, int D, int SL, int Sp, const float* xn, const float* nrm,
+                           float eps, float* dX, const int32_t* img_start = nullptr,
+                           const int32_t* img_samples = nullptr);
 // Image table -> per-sample maps: out[b] = table[image_of[b]] for b < nB, maps of map_bytes bytes each
 // ([D][Sp] elements of any feature type, copied as they are in 16-byte vectors; map_bytes % 8 == 0, which
 // holds for every map a context can have: D % 4 == 0 and Sp % 4 == 0 make even an fp8 map a multiple of 16).

@@ -281,10 +281,12 @@ struct StepKey {
                                 // or a null pointer (rau_set_sample_weights); a replay reads the current weights
   int cand_C = 0;               // ... against C candidates per sample (0 = none): another head kernel, which holds the
                                 // slot's list (rau_set_candidates); a replay reads the current list
+  int xnorm = 0;                // ... and with rau_set_feat_norm the image side starts with the normalisation pass (and
+  uint32_t xnorm_eps = 0;       // the backward may end with its gradient), which holds eps as an argument: its bits
   auto tied() const {
     return std::tie(mode, max_len, active, zero, mexplicit[0], mexplicit[1], mexplicit[2], mexplicit[3], mexplicit[4],
                     slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg, tied_x, ans_loss,
-                    feat_grad, question, sample_w, cand_C);
+                    feat_grad, question, sample_w, cand_C, xnorm, xnorm_eps);
   }
   bool operator==(const StepKey& o) const { return tied() == o.tied(); }
 };
@@ -312,6 +314,8 @@ struct FwdRecord {
   bool dl = false;                // it wrote dl: its batch had labels or an answer set (rau_backward_ext)
   bool dpre = false;              // it already formed dpre / dhn of every hop (unscaled by the hop weights)
   std::vector<int> groups;        // the launch partition it used (rau_ctx::groups; evaluate mode: one group of H)
+  int xn_rows = 0;                // (rau_set_feat_norm) xn / nrm hold that many normalised maps of it: n, or the table's N
+                                  // after an evaluate-mode table forward; 0 = none.  Outlives drop_forward().
 };
 // What the last step-level backward left for the getters.  rau_ctx::bwd: record_backward (rau_ctx.hip) fills it for
 // backward_impl and graph_step_impl, "no backward" is BwdRecord{} (rau_set_batch_size).
@@ -411,6 +415,12 @@ struct rau_ctx {
   float* xg_dX = nullptr;           // [cap][D][Sp] the last backward's result (bwd.dX), allocated with the switch
   float* xg_tmp = nullptr;          // [cap][D][Sp] one hop's unmasked product (the unfused path)
   float* xg_dz = nullptr;           // [cap][M][Sp] dI (1 - I^2) where the dgrad left dI (no fused tanh derivative)
+  // per-position L2 normalisation of the batch's maps (rau_set_feat_norm, featnorm.hip): off = the step path as it is
+  int xnorm = RAU_XNORM_NONE;
+  float xnorm_eps = 1e-12f;
+  float* xn = nullptr;              // [cap][D][Sp] the last forward's normalised maps (fwd.xn_rows of them): what the
+                                    // image side reads as an f32 batch; allocated with the switch, like nrm
+  float* nrm = nullptr;             // [cap][Sp] their norms
   // rau_set_batch_dev: pinned staging of the index arrays, two halves alternated like hopw_h
   int32_t* bdev_h[2] = {nullptr, nullptr};
   hipEvent_t bdev_ev[2] = {nullptr, nullptr};
@@ -535,6 +545,8 @@ inline StepKey step_key(const rau_ctx* ctx, const StepLoss& loss, bool zero) {
   key.question = d.question;
   key.sample_w = d.sample_w;
   key.cand_C = d.cand_C;
+  key.xnorm = ctx->xnorm;
+  if (ctx->xnorm) std::memcpy(&key.xnorm_eps, &ctx->xnorm_eps, sizeof(float));
   return key;
 }
 

@@ -825,6 +825,73 @@ int rau_get_feat_grad(rau_ctx* ctx, float* host) {
   return persist_check(ctx);
 }
 
+// ------------------------------------------------- feature-map normalisation
+// The forward reads ctx->xnorm (feature_maps: one l2norm_features launch in front of everything that reads the maps,
+// which then see an f32 batch), the backward too (one l2norm_backward behind the feature-map gradient); the graph key
+// carries the kind and the bits of eps.  Nothing else depends on the switch.
+int rau_set_feat_norm(rau_ctx* ctx, int kind, float eps) {
+  NEED(ctx, "null ctx");
+  NEED(kind == RAU_XNORM_NONE || kind == RAU_XNORM_L2,
+       "rau_set_feat_norm: kind %d is neither RAU_XNORM_NONE nor RAU_XNORM_L2", kind);
+  NEED(std::isfinite(eps) && eps > 0.f, "rau_set_feat_norm: eps = %g must be finite and > 0", (double)eps);
+  if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_feat_norm: a step is being captured");
+  if (kind == ctx->xnorm && (eps == ctx->xnorm_eps || kind == RAU_XNORM_NONE)) {
+    ctx->xnorm_eps = eps;   // (off and off: only the value rau_feat_norm reports moves)
+    return RAU_OK;
+  }
+  if (kind != RAU_XNORM_NONE) {
+    // for the capacity, at the first use (never inside a captured step); cleared by rau_set_batch_size like every
+    // activation.  Each pointer on its own: a call that failed half way is completed by the next one, and the
+    // switch stays as it was until both exist.
+    const rau_config& c = ctx->cfg;
+    if (!ctx->xn)
+      if (int rc = dalloc(ctx, &ctx->xn, (size_t)ctx->cap * c.D * ctx->Sp)) return rc;
+    if (!ctx->nrm)
+      if (int rc = dalloc(ctx, &ctx->nrm, (size_t)ctx->cap * ctx->Sp)) return rc;
+  }
+  ctx->xnorm = kind;
+  ctx->xnorm_eps = eps;
+  ctx->fwd.xn_rows = 0;
+  ctx->bwd.dX = false;
+  drop_forward(ctx);       // the last forward read other maps: no backward, no statistics, no outputs without
+  ctx->mg.valid = false;   // a new forward
+  return RAU_OK;
+}
+int rau_feat_norm(rau_ctx* ctx, int* kind, float* eps) {
+  NEED(ctx, "null ctx");
+  if (kind) *kind = ctx->xnorm;
+  if (eps) *eps = ctx->xnorm_eps;
+  return RAU_OK;
+}
+static int feat_norm_state(rau_ctx* ctx, const char* fn) {
+  if (!ctx->xnorm) return fail(RAU_ERR_STATE, "%s: the normalisation is off (rau_set_feat_norm)", fn);
+  if (!ctx->fwd.xn_rows) return fail(RAU_ERR_STATE, "%s: no forward has run since the switch was set", fn);
+  return RAU_OK;
+}
+int rau_norm_feats_dev(rau_ctx* ctx, const float** xn, const float** nrm, int32_t* pitch, int32_t* rows) {
+  NEED(ctx, "null ctx");
+  if (int rc = feat_norm_state(ctx, "rau_norm_feats_dev")) return rc;
+  if (xn) *xn = ctx->xn;
+  if (nrm) *nrm = ctx->nrm;
+  if (pitch) *pitch = ctx->Sp;
+  if (rows) *rows = ctx->fwd.xn_rows;
+  return RAU_OK;
+}
+int rau_get_norm_feats(rau_ctx* ctx, float* xn_host, float* nrm_host) {
+  NEED(ctx, "null ctx");
+  if (int rc = feat_norm_state(ctx, "rau_get_norm_feats")) return rc;
+  const rau_config& c = ctx->cfg;
+  const size_t rows = (size_t)ctx->fwd.xn_rows;
+  if (xn_host)
+    HIPC(hipMemcpy2DAsync(xn_host, (size_t)c.S * 4, ctx->xn, (size_t)ctx->Sp * 4, (size_t)c.S * 4, rows * c.D,
+                          hipMemcpyDeviceToHost, ctx->st));
+  if (nrm_host)
+    HIPC(hipMemcpy2DAsync(nrm_host, (size_t)c.S * 4, ctx->nrm, (size_t)ctx->Sp * 4, (size_t)c.S * 4, rows,
+                          hipMemcpyDeviceToHost, ctx->st));
+  HIPC(hipStreamSynchronize(ctx->st));
+  return persist_check(ctx);
+}
+
 // ------------------------------------------------------ answer criterion
 // The forward's head reads ctx->answer_loss through step_truth(); the merged-hops record carries the kind of the
 // forward it describes (MergeState::truth), the graph key the kind a step was captured under.  Nothing is allocated
@@ -1421,6 +1488,18 @@ static int feature_maps(rau_ctx* ctx, hipStream_t sb, const Masks& m, const floa
   const rau_config& c = ctx->cfg;
   const int B = c.B, D = c.D, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, H = c.H;
   const bool tied = ctx->fwd.tied;
+  // the batch's element type: 16-bit and fp8 maps are widened (exactly) by the pass that reads them
+  int ft = cur_batch(ctx).held.feat_type;
+  // rau_set_feat_norm: the nX maps are normalised per position first, and everything below -- dropout in its three
+  // forms, the no-mask path, the weight gradients' x_shared -- runs on xn as on an f32 batch (no widen pass either)
+  ctx->fwd.xn_rows = 0;
+  if (ctx->xnorm) {
+    RUNS(sb, "l2norm_features", 3.0 * nX * D * S, (double)nX * D * S * (feat_elem_bytes(ft) + 4),
+         l2norm_features(sb, nX, D, SL, S, feats, ft, ctx->xnorm_eps, ctx->xn, ctx->nrm));
+    feats = ctx->xn;
+    ft = RAU_FEAT_F32;
+    ctx->fwd.xn_rows = nX;
+  }
   // feature-map dropout, SS:239: unless the caller supplied the mask, the pass that makes the H masked
   // copies draws the keep bits itself (they have no other reader on this path)
   // bf16 mode: the hop copies of the feature map are stored as bf16 (to halve an H-fold buffer; the one tied
@@ -1435,8 +1514,6 @@ static int feature_maps(rau_ctx* ctx, hipStream_t sb, const Masks& m, const floa
     if (int rc = gen_masks(ctx, -1, RAU_MASK_X, sb)) return rc;
   RUNS(sb, "transpose", 0, (double)M * D * 8, transpose2d(sb, M, D, ctx->i_embed.W, ctx->WiT, ctx->WiT16));
   RUNS(sb, "transpose", 0, (double)A * M * 8, transpose2d(sb, A, M, ctx->att_i.W, ctx->WpT, ctx->WpT16));
-  // the batch's element type: 16-bit and fp8 maps are widened (exactly) by the pass that reads them
-  const int ft = cur_batch(ctx).held.feat_type;
   const double xb = (double)feat_elem_bytes(ft);   // bytes per element read from the batch
   if (x_gen)
     RUNS(sb, "dropout_features", 0, (double)B * D * S * xb + (double)HX * B * D * S * (x16 ? 2 : 4),
@@ -2069,6 +2146,16 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   // no active hop: the gradient is zero (n rows: all of a table's N <= n too, whichever N a replay meets)
   if (ctx->feat_grad && dX_first)
     HIPC(hipMemsetAsync(ctx->xg_dX, 0, (size_t)B * c.D * S * sizeof(float), ctx->st2));
+  // rau_set_feat_norm: xg_dX holds the gradient at the normalised maps; back through the normalisation, in place.
+  // Per image (xgrad_per_image) every slot of the capacity, like the accumulate pass: slot i reads the xn of its
+  // list's first sample (all of them are that image's map), a slot without samples keeps its zeros.
+  if (ctx->feat_grad && ctx->xnorm) {
+    const bool per_image = xgrad_per_image(ctx);
+    const int rows = per_image ? ctx->cap : B;
+    RUNS(ctx->st2, "l2norm_backward", 5.0 * rows * c.D * S, (double)rows * c.D * S * 12,
+         l2norm_backward(ctx->st2, rows, c.D, c.S, S, ctx->xn, ctx->nrm, ctx->xnorm_eps, ctx->xg_dX,
+                         per_image ? bs.img_start_d : nullptr, per_image ? bs.img_samples_d : nullptr));
+  }
   // bulk stream tail: the join event (the i_embed bias gradient comes out of conv_embed_wgrad:
   // row sums of its staged dZ operand)
   HIPC(hipEventRecord(ctx->evD, ctx->st2));
@@ -2260,6 +2347,7 @@ static int graph_step_impl(rau_ctx* ctx, const StepLoss& loss, int zero_grads_fi
     ctx->x_serial = ctx->slot_serial[ctx->cur_slot];
   }
   HIPC(hipEventRecord(ctx->evEnd, ctx->st));   // a real (non-captured) end-of-step event
+  ctx->fwd.xn_rows = ctx->xnorm ? ctx->cfg.B : 0;   // (a captured forward normalises the gathered per-sample maps)
   merge_record(ctx);
   drop_forward(ctx);
   record_backward(ctx, true);

@@ -254,6 +254,34 @@ int rau_dev_scale_rows(rau_ctx* ctx, float* x, int32_t rows, int32_t cols, int32
   HIPC(hipGetLastError());
   return RAU_OK;
 }
+// The two kernels of rau_set_feat_norm on the caller's dense [n,D,S] tensors, for hosts that keep the module-level
+// loops and own their X (featnorm.hip: S % 4 == 0 takes the 16-byte form, any other S the single-element one).
+int rau_dev_l2norm(rau_ctx* ctx, const float* x_dev, int32_t n, float eps, float* y_dev, float* nrm_dev) {
+  NEED(ctx && x_dev && y_dev, "null argument");
+  NEED(n >= 0, "rau_dev_l2norm: n = %d", n);
+  NEED(std::isfinite(eps) && eps > 0.f, "rau_dev_l2norm: eps = %g must be finite and > 0", (double)eps);
+  const rau_config& c = ctx->cfg;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(y_dev) |
+                         reinterpret_cast<uintptr_t>(nrm_dev);
+  NEED(c.S % 4 != 0 || (bits & 15u) == 0, "rau_dev_l2norm: the tensors must be 16-byte aligned (S %% 4 == 0)");
+  HIPC(rau::l2norm_features(ctx->st, n, c.D, c.S, c.S, x_dev, RAU_FEAT_F32, eps, y_dev, nrm_dev));
+  return RAU_OK;
+}
+int rau_dev_l2norm_backward(rau_ctx* ctx, const float* y_dev, const float* nrm_dev, float eps, const float* g_dev,
+                            int32_t n, float* dx_dev) {
+  NEED(ctx && y_dev && nrm_dev && g_dev && dx_dev, "null argument");
+  NEED(n >= 0, "rau_dev_l2norm_backward: n = %d", n);
+  NEED(std::isfinite(eps) && eps > 0.f, "rau_dev_l2norm_backward: eps = %g must be finite and > 0", (double)eps);
+  NEED(dx_dev != y_dev, "rau_dev_l2norm_backward: dx_dev may alias g_dev, not y_dev");
+  const rau_config& c = ctx->cfg;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(y_dev) | reinterpret_cast<uintptr_t>(nrm_dev) |
+                         reinterpret_cast<uintptr_t>(g_dev) | reinterpret_cast<uintptr_t>(dx_dev);
+  NEED(c.S % 4 != 0 || (bits & 15u) == 0, "rau_dev_l2norm_backward: the tensors must be 16-byte aligned (S %% 4 == 0)");
+  if (dx_dev != g_dev && n)   // the kernel works in place
+    HIPC(hipMemcpyAsync(dx_dev, g_dev, (size_t)n * c.D * c.S * sizeof(float), hipMemcpyDeviceToDevice, ctx->st));
+  HIPC(rau::l2norm_backward(ctx->st, n, c.D, c.S, c.S, y_dev, nrm_dev, eps, dx_dev));
+  return RAU_OK;
+}
 int rau_dev_rowmax(rau_ctx* ctx, const float* x, int32_t rows, int32_t cols, float* max_dev,
                    int32_t* argmax_dev) {
   NEED(ctx && x, "null argument");

@@ -163,3 +163,23 @@ def unpack_regions(rows, counts, S: int) -> np.ndarray:
         dense[i, :, :c] = rows[off:off + c].T
         off += int(c)
     return dense
+
+
+def l2_normalize(x, eps=1e-12) -> np.ndarray:
+    """Per-position L2 normalisation of maps [..., D, S] over the channel axis, the statement of
+    ``rau_set_feat_norm``: ``x / max(sqrt(sum_d x^2), eps)``, computed in float64 and rounded to float32 once."""
+    x = np.asarray(x, np.float64)
+    nrm = np.sqrt(np.sum(x * x, axis=-2, keepdims=True))
+    return (x / np.maximum(nrm, float(eps))).astype(np.float32)
+
+
+def l2_normalize_grad(x, g, eps=1e-12) -> np.ndarray:
+    """Gradient at ``x`` of ``l2_normalize(x, eps)`` for the gradient ``g`` at its output (same shape): with
+    ``xn = x / max(nrm, eps)`` and ``c = sum_d g xn``, ``(g - xn c) / nrm`` where ``nrm >= eps`` and ``g / eps``
+    where ``nrm < eps`` (the forward is linear there).  float64, rounded to float32 once."""
+    x, g = np.asarray(x, np.float64), np.asarray(g, np.float64)
+    nrm = np.sqrt(np.sum(x * x, axis=-2, keepdims=True))
+    r = 1.0 / np.maximum(nrm, float(eps))
+    xn = x * r
+    c = np.sum(g * xn, axis=-2, keepdims=True)
+    return (r * (g - np.where(nrm >= float(eps), xn * c, 0.0))).astype(np.float32)

@@ -1025,6 +1025,81 @@ class RAU:
         n, D, S, dev = self.feature_grad_rows(), self.cfg.D, self.cfg.S, self.cfg.device_id
         return device_view(p.value, n * D * pitch.value, dev).view(n, D, pitch.value)[:, :, :S]
 
+    # ---- per-position L2 normalisation of the batch's maps (rau_set_feat_norm)
+    def normalize_features(self, on=True, eps=1e-12):
+        """Every step-level forward first L2-normalises each position's channel vector of the batch's maps on the
+        device, x / max(||x||_2, eps) over D in float32 (torch.nn.functional.normalize(x, dim=1, eps=eps) on
+        [n,D,S]) -- whatever type the maps are stored in -- and runs on the result as on a float32 batch; with
+        want_feature_grad the gradient goes back through the normalisation to the raw maps.  Off (the default) the
+        step is what it was.  A change drops the last forward."""
+        L.check(self._lib.rau_set_feat_norm(self._h, L.XNORM_L2 if on else L.XNORM_NONE, float(eps)))
+
+    @property
+    def features_normalized(self):
+        """(kind, eps) of rau_feat_norm: kind 0 = off, 1 = L2."""
+        kind, eps = C.c_int(0), C.c_float(0.0)
+        L.check(self._lib.rau_feat_norm(self._h, C.byref(kind), C.byref(eps)))
+        return int(kind.value), float(eps.value)
+
+    def _norm_feats_dev(self):
+        xn, nrm, pitch, rows = C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
+        L.check(self._lib.rau_norm_feats_dev(self._h, C.byref(xn), C.byref(nrm), C.byref(pitch), C.byref(rows)))
+        return xn.value, nrm.value, int(pitch.value), int(rows.value)
+
+    def norm_feats(self):
+        """The last forward's normalised maps and their norms, (xn [rows,D,S], nrm [rows,S]) (numpy; synchronises):
+        rows = N after the evaluate-mode forward of an image-table or bank batch, else n."""
+        rows = self._norm_feats_dev()[3]
+        xn = np.empty((rows, self.cfg.D, self.cfg.S), np.float32)
+        nrm = np.empty((rows, self.cfg.S), np.float32)
+        L.check(self._lib.rau_get_norm_feats(self._h, xn.ctypes.data, nrm.ctypes.data))
+        return xn, nrm
+
+    def norm_feats_tensors(self):
+        """Zero-copy torch views (xn [rows,D,S], nrm [rows,S]) of the same in device memory (rau_norm_feats_dev) --
+        strided where the maps are pitched (S % 4 != 0).  Valid until the next forward or set_batch_size, ordered on
+        the ctx's stream (stream()), read-only."""
+        from .dist import device_view
+        xn, nrm, pitch, rows = self._norm_feats_dev()
+        D, S, dev = self.cfg.D, self.cfg.S, self.cfg.device_id
+        return (device_view(xn, rows * D * pitch, dev).view(rows, D, pitch)[:, :, :S],
+                device_view(nrm, rows * pitch, dev).view(rows, pitch)[:, :S])
+
+    def _dev_maps(self, t, what, shape=None):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous float32 CUDA torch tensor")
+        if t.device.index != self.cfg.device_id:
+            raise ValueError(f"{what} is on {t.device}, the context on cuda:{self.cfg.device_id}")
+        want = shape if shape is not None else (int(t.shape[0]) if t.dim() else 0, self.cfg.D, self.cfg.S)
+        if tuple(t.shape) != tuple(want):
+            raise ValueError(f"{what} has shape {tuple(t.shape)}, expected {tuple(want)}")
+        return t
+
+    def l2norm(self, x, eps=1e-12, out=None):
+        """rau_dev_l2norm on a contiguous float32 CUDA tensor x [n,D,S] (any n): returns (y, nrm), new tensors, or
+        y written into `out` (which may be x).  On the ctx's stream, no synchronisation: order it behind the stream
+        that wrote x, as for set_batch_dev."""
+        import torch
+        x = self._dev_maps(x, "x")
+        y = torch.empty_like(x) if out is None else self._dev_maps(out, "out", x.shape)
+        nrm = torch.empty((x.shape[0], self.cfg.S), dtype=torch.float32, device=x.device)
+        L.check(self._lib.rau_dev_l2norm(self._h, x.data_ptr(), int(x.shape[0]), float(eps), y.data_ptr(),
+                                         nrm.data_ptr()))
+        return y, nrm
+
+    def l2norm_backward(self, y, nrm, g, eps=1e-12, out=None):
+        """rau_dev_l2norm_backward: the gradient at x for the gradient g [n,D,S] at y = l2norm(x), from that call's
+        y and nrm; a new tensor, or written into `out` (which may be g).  Same stream rule as l2norm."""
+        import torch
+        y = self._dev_maps(y, "y")
+        g = self._dev_maps(g, "g", y.shape)
+        nrm = self._dev_maps(nrm, "nrm", (y.shape[0], self.cfg.S))
+        dx = torch.empty_like(g) if out is None else self._dev_maps(out, "out", y.shape)
+        L.check(self._lib.rau_dev_l2norm_backward(self._h, y.data_ptr(), nrm.data_ptr(), float(eps), g.data_ptr(),
+                                                  int(y.shape[0]), dx.data_ptr()))
+        return dx
+
     # ---- question state from the caller (rau_set_question_dev): another question encoder in front of the step path
     def set_question(self, q_cuda):
         """Attach the question state q [n,Q] (Q = 4 Rq) to the resident batch: a contiguous CUDA torch tensor of

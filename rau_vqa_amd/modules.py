@@ -225,7 +225,7 @@ def scale_rows(rau, x, s):
 
 
 def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=None, att_targets=None, merge_w=None,
-          loss="ce", answers=None, sample_w=None, candidates=None):
+          loss="ce", answers=None, sample_w=None, candidates=None, normalize=None):
     """The tensor half of the reference's feval, loop for loop (SS:443-596), on the clones.
     select_w [H] (None: the reference's zero, SS:566): hop h's multimodal clone receives
     d_do_pred = joint.bce_grad(do_pred_h, argmax_h == y, select_w[h]), which trains the step-selection head.
@@ -252,12 +252,18 @@ def feval(rau, feats, x, x_len, y, hop_w, select_w=None, regions=None, att_w=Non
     sample's candidates (CandCriterionClone, under either loss; with answers also under "ce"); merge_w is refused
     with them (the merged rows' terms are full-vocabulary cross-entropies).
 
+    normalize (None: the maps as they are): an eps > 0 -- every position's channel vector of feats is L2-normalised
+    on the device first (rau.l2norm: the step path's pass under rau_set_feat_norm, the same bits), into a tensor of
+    its own, and the clones read that.
+
     feats [B,D,S] float32, x [T,B] int32, x_len [B] int32, y [B] int32: CUDA tensors.
     Gradients accumulate into the ctx's flat buffers (zero them first).  Returns
     (losses[H], argmax[H,B] as torch tensors of 1-based ids).
     """
     ext = torch.cuda.ExternalStream(rau.stream(), device=feats.device)
     with torch.cuda.stream(ext):   # torch's glue ops join the ctx's own stream order
+        if normalize is not None:
+            feats = rau.l2norm(feats, eps=float(normalize))[0]
         return _feval(rau, feats, x, x_len, y, hop_w, select_w, regions, att_w, att_targets, merge_w, loss, answers,
                       sample_w, candidates)
 
