@@ -281,6 +281,15 @@ SCENARIOS = {s.name: s for s in [
     _p("peak_before_count", 100, (36,), dead=(37,), regions=37),
     _p("peak_second_trip", 260, (257,)),
     _p("two_peaks", 260, (3, 200)),
+    # above 400 positions, up to the attention kernels' bounds (4096 split, 900 fused): under near-uniform attention
+    # a lost position is 1 / S of a weight gradient, 2.4e-4 at 4096; under a placed peak it is the whole gradient
+    _p("peak_last_4096", 4096, (4095,)),
+    _p("peak_before_pad_4093", 4093, (4092,)),
+    _p("two_peaks_4096", 4096, (255, 4000)),
+    _p("peak_third_trip_772", 772, (769,)),
+    _p("peak_last_900", 900, (899,)),
+    _p("peak_before_pad_897", 897, (896,)),
+    _p("peak_before_count_900", 900, (700,), dead=(701,), regions=701),
     Scenario("sat_i_embed", _sat_i_embed, regime_i_embed),
     Scenario("sat_i_embed_tied", _sat_i_embed_tied, regime_i_embed),
     Scenario("sat_addfeat", _sat_addfeat, regime_addfeat),
@@ -293,6 +302,10 @@ SCENARIOS = {s.name: s for s in [
     Scenario("sat_i_embed_bf16", lambda p, rng: _sat_i_embed(p, rng, BF16_I_EMBED_FACTOR), regime_i_embed),
 ]}
 PEAKS = tuple(n for n, s in SCENARIOS.items() if s.regime is regime_peak)
+# rau_create refuses the fused attention family above 900 positions at F32's A (kernels.hip att_max_pitch): contexts
+# of more than 64 samples, and RAU_ATT_FUSED at any batch size, take the scenarios up to there
+FUSED_MAX_S = 900
+PEAKS_ABOVE_400 = tuple(n for n in PEAKS if SCENARIOS[n].S > 400)
 
 
 def _step_args(p, mode, hop_w):

@@ -37,7 +37,13 @@ BITS = ("losses", "argmax", "logits", "dopred", "att", "q", "att_c", "att_h", "g
 SHAPES = {"edge": (util.EDGE, 0.5), "small": (util.SMALL, 0.5), "seven": (SEVEN, 0.5), "wide": (WIDE, 0.3),
           "boxes": (BOXES, 0.5),
           "s195": (dict(F32, B=6, S=195), 0.2),      # a pitched 14 x 14 map: one pad column
-          "s400": (dict(F32, B=6, S=400), 0.2)}      # a row longer than a workgroup
+          "s400": (dict(F32, B=6, S=400), 0.2),      # a row longer than a workgroup
+          # the split family's bound, small widths: 16 trips of every row loop, targets on the last position
+          "s4096": (dict(B=6, T=4, V=40, E=8, Rq=16, D=24, S=4096, M=40, A=20, R=16, K=12, H=2), 0.2)}
+# Under near-uniform attention over 4096 positions no a reaches att_ref's 10 * A_MIN = 1e-3 and no target could be
+# placed.  attbymemory's bias + 8 at these positions gives each of them about 1 / (10 + 4096 e^-8) = 0.09: targets()
+# then places its rows on them, the last position among them, and row 0's one-hot target is moved onto it.
+BOOSTED = {"s4096": (0, 255, 256, 1023, 2048, 4000, 4092, 4093, 4094, 4095)}
 COUNTS = {"small": np.array([12, 7, 3, 1, 5, 12, 2, 9], np.int32),
           "boxes": np.array([100, 10, 99, 36, 1, 57, 64, 100], np.int32)}
 
@@ -56,10 +62,17 @@ def reference(name, counts=False, hop_zero=False):
     dims, scale = SHAPES[name]
     sh = util.shapes(dims)
     batch, params, masks = util.make_problem(sh, scale=scale)
+    if name in BOOSTED:
+        from tests import range_cases
+        range_cases.views(sh, params)["att_mem.b"][list(BOOSTED[name])] += 8.0
     n = COUNTS[name] if counts else None
     hop_w = np.zeros(sh.H, np.float32) if hop_zero else hop_weights(sh.H)
     fwd = att_ref.step(sh, params, batch, masks, hop_w, nreg=n, backward=False)
     t = att_ref.targets(fwd["att"], n)
+    if name in BOOSTED:
+        assert t[2:5, sh.S - 1].all() and set(np.flatnonzero(t.any(axis=0))) <= set(BOOSTED[name])
+        t[0] = 0.0
+        t[0, sh.S - 1] = 1.0
     if n is not None:                          # values behind the counts are to be ignored: make them loud
         for b, nb in enumerate(n):
             t[b, nb:] = 7.0
@@ -146,6 +159,7 @@ CASES = [
     ("wide", {}, FUSED_F),                     # B = 80, S = 196: fused by default
     ("s195", {}, SPLIT_F),                     # a pitched 14 x 14 map
     ("s400", {}, SPLIT_F),                     # 400 positions: the row loop of k_att_grad
+    ("s4096", {}, SPLIT_F),                    # 4096 positions, targets on the last one
 ]
 
 

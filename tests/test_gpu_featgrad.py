@@ -101,6 +101,11 @@ VARIANTS = ("explicit", "philox", "evaluate", "tied", "regions", "trailing_zero"
 # kernel (evaluate mode and the tied mask hand it dI, not dZ: they stay on the unfused path under either setting)
 CASES = [(n, v, "unfused") for n in SHAPES for v in VARIANTS] + \
         [(n, v, "fused") for n in SHAPES if n in FUSED for v in VARIANTS if v not in ("evaluate", "tied")]
+# the largest position counts of the two attention families, small widths: the i_embed dgrad over 900 and 4096
+# columns per sample and xgrad_accum's rows of that length, with dZ (train), dI (evaluate) and region counts
+X900 = dict(B=6, T=4, V=30, E=8, Rq=16, D=40, S=900, M=24, A=20, R=16, K=12, H=3)
+SHAPES.update(X900=X900, X4096=dict(X900, S=4096))
+CASES += [(n, v, "unfused") for n in ("X900", "X4096") for v in ("explicit", "evaluate", "regions")]
 
 
 @pytest.fixture

@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 EPS = 1e-3
 HOP_W = [2.0, 0.5]
 U = 2.0 ** -24
-NUM_SHAPES = [(4, 5), (36, 49), (512, 196), (2048, 16)]
+NUM_SHAPES = [(4, 5), (36, 49), (512, 196), (2048, 16), (36, 900)]     # 900: the fused attention family's bound
 TYPES = ("f32", "f16", "bf16", "e4m3", "e5m2")
 _CACHE = {}
 
@@ -255,7 +255,7 @@ def test_every_batch_form_gives_the_plain_batch(mode):
 
 
 # ------------------------------------------------------------------------------------------ 4. the fp64 oracle
-@pytest.mark.parametrize("S", [49, 196])
+@pytest.mark.parametrize("S", [49, 196, 900])
 def test_against_the_oracle_on_float64_normalised_maps(S):
     sh, batch, params, masks = problem(8, S)
     batch["feats"] = special_maps(3, 8, S, seed=13)

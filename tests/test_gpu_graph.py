@@ -22,11 +22,17 @@ def _mk(sh, params, dtype="f32"):
 # forms) and the side-stream split of the chain's non-recurrent GEMMs; BF16_TILES has the widths
 # dgrad16.hip (M % 128, A % 32) and wgrad16.hip (M, D % 256) accept on a 14x14 map.
 BF16_TILES = dict(B=12, T=6, V=60, E=64, Rq=64, D=256, S=196, M=256, A=64, R=64, K=200, H=3)
+# the largest position counts that rau_create accepts: the fused attention family's (contexts above 64 samples) and
+# the split family's, at small widths
+FUSED_900 = dict(B=66, T=5, V=40, E=8, Rq=16, D=24, S=900, M=40, A=20, R=16, K=12, H=2)
+SPLIT_4096 = dict(FUSED_900, B=6, S=4096)
 
 
 @pytest.mark.parametrize("dims,dtype", [(util.SMALL, "f32"), (util.MEDIUM, "f32"),
-                                        (util.SMALL, "bf16"), (util.MEDIUM, "bf16"), (BF16_TILES, "bf16")],
-                         ids=["small-f32", "medium-f32", "small-bf16", "medium-bf16", "tiles-bf16"])
+                                        (util.SMALL, "bf16"), (util.MEDIUM, "bf16"), (BF16_TILES, "bf16"),
+                                        (FUSED_900, "f32"), (SPLIT_4096, "f32")],
+                         ids=["small-f32", "medium-f32", "small-bf16", "medium-bf16", "tiles-bf16",
+                              "fused-900-f32", "split-4096-f32"])
 def test_graph_step_matches_eager_bitwise(dims, dtype):
     sh = util.shapes(dims)
     _, params, _ = util.make_problem(sh, scale=0.3)

@@ -39,6 +39,9 @@ SHAPES = {
     "boxes68": (dict(BOXES, D=68), [100, 10, 99, 36, 1, 57, 64, 100]),
     "boxes132": (dict(BOXES, D=132), [100, 10, 99, 36, 1, 57, 64, 100]),
     "big": (BIG, [36, 1]),
+    # the fused attention family's bound: 15 position tiles, the last one 4 wide; counts on tile edges (257, 513),
+    # inside the last tile (899, 900) and far below it
+    "boxes900": (dict(BOXES, S=900), [900, 10, 899, 257, 1, 513, 770, 900]),
 }
 
 
@@ -83,8 +86,8 @@ def at_pitch(dense, Sp):
 
 
 # ---------------------------------------------------------------- 1. kernel
-KERNEL_CASES = [("boxes", ft) for ft in TYPES] + [(n, ft) for n in ("seven", "edge", "boxes68", "boxes132", "big")
-                                                  for ft in ("f32", "e4m3")]
+KERNEL_CASES = [("boxes", ft) for ft in TYPES] + [(n, ft) for n in ("seven", "edge", "boxes68", "boxes132", "big",
+                                                                    "boxes900") for ft in ("f32", "e4m3")]
 
 
 @pytest.mark.parametrize("name,ft", KERNEL_CASES, ids=[f"{n}-{ft}" for n, ft in KERNEL_CASES])
@@ -213,7 +216,7 @@ def test_f32_rows_are_narrowed_with_the_bits_of_bank_put(name):
 
 
 # ---------------------------------------------------------------- 3. step identity
-IDENT = [("boxes", "f32"), ("seven", "bf16")]
+IDENT = [("boxes", "f32"), ("seven", "bf16"), ("boxes900", "f32")]
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])

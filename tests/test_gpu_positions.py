@@ -48,7 +48,12 @@ LDS-DMA attention kernels; 257, 260 second trip of the q0 loop with one lane liv
 3. module-level feval against the step path on the same context (2e-5, tests/test_gpu_fuzz.py's bar).
 4. (tests/test_gpu_regions.py: region counts at S = 100.)
 6. rau_create's refusal above the attention kernels' LDS bound, on contexts that are never created.
+7. From 400 positions to that bound (LARGE below, a table of its own: most of CASES' parametrisations do not apply
+   up there): the checks of 1, 2 and 3 on contexts that are created and run, in both attention families and both
+   modes.  tests/test_positions_host.py holds every label of the table, and every bound, to the launches in
+   kernels.hip and to rau_create.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -97,7 +102,68 @@ S_FUSED = (100, 180, 195, 208, 256, 260, 400)
 S_BF16 = (100, 180, 195, 200, 208, 256, 260)
 S_MODULES = (100, 180, 200, 208, 256, 260, 400)
 
+# From 400 positions to the bound (section 7).  Per row: the pitch; the trips of `for (q0 = 0; q0 < Sp / 4; q0 += 64)`
+# and the lanes live in the last one; conv_wgrad's chunk depth in f32 (bf16 mode: always 32) and its chunks per
+# sample; the pad columns; whether the pitch is the largest that rau_create accepts for the row's family, A and wave
+# counts.  over: what replaces F32's dimensions; env: read when the context is created.
+# tests/test_positions_host.py recomputes every label from S and holds `bound` to the launches' LDS requests.
+Large = collections.namedtuple("Large", "sec S pitch trips lanes depth chunks pad bound why over env")
+
+
+def _L(sec, S, pitch, trips, lanes, depth, chunks, pad, why, bound=False, over=None, env=None):
+    return Large(sec, S, pitch, trips, lanes, depth, chunks, pad, bound, why, over or {}, env or {})
+
+
+FUSED6 = {"RAU_ATT_FUSED": "1"}
+FWD8 = {"RAU_ATT_WAVES_FWD": "8"}      # the evaluate-mode forward on 8 waves as well: the backward's term binds
+TINY = dict(D=16, M=32, A=16)          # the B = 64 corner: memory and the oracle's time stay small
+LARGE = [
+    # split family, B = 6 (att_chunks = 8), train and evaluate mode
+    _L("split", 512, 512, 2, 64, 32, 16, 0, "S4 = 128: two q0 trips that end exactly, two exact trips of `s += 256`"),
+    _L("split", 513, 516, 3, 1, 32, 17, 3, "third trip with one lane live, pitched"),
+    _L("split", 516, 516, 3, 1, 32, 17, 0, "the same, unpitched"),
+    _L("split", 769, 772, 4, 1, 32, 25, 3, "fourth trip with one lane live, pitched"),
+    _L("split", 772, 772, 4, 1, 32, 25, 0, "the same, unpitched"),
+    _L("split", 896, 896, 4, 32, 28, 32, 0, "28-deep conv chunks at 32 chunks"),
+    _L("split", 2048, 2048, 8, 64, 32, 64, 0, "32 KB of LDS, eight trips"),
+    _L("split", 4088, 4088, 16, 62, 28, 146, 0, "28-deep chunks at 146 chunks; last trip with 62 lanes"),
+    _L("split", 4093, 4096, 16, 64, 32, 128, 3, "three pad columns at the bound", bound=True),
+    _L("split", 4096, 4096, 16, 64, 32, 128, 0, "the bound: a 65536-byte request", bound=True),
+    # the largest context of the family: att_chunks = 8 still, att_split_part_floats at its maximum
+    _L("split64", 4096, 4096, 16, 64, 32, 128, 0, "B = 64 at the bound", bound=True, over=TINY),
+    # fused family, B = 66, train mode (8 forward waves) and evaluate mode (16: the term that binds)
+    _L("fused", 512, 512, 2, 64, 32, 16, 0, "two exact trips; two exact trips of `s += NW * 64` at 8 waves"),
+    _L("fused", 516, 516, 3, 1, 32, 17, 0, "third trip with one lane live"),
+    _L("fused", 768, 768, 3, 64, 32, 24, 0, "three exact trips"),
+    _L("fused", 772, 772, 4, 1, 32, 25, 0, "fourth trip with one lane live"),
+    _L("fused", 896, 896, 4, 32, 28, 32, 0, "28-deep conv chunks at 32 chunks"),
+    _L("fused", 897, 900, 4, 33, 32, 29, 3, "three pad columns at the bound", bound=True),
+    _L("fused", 900, 900, 4, 33, 32, 29, 0, "the bound at A = 128: 18 Sp + 32 + A floats", bound=True),
+    _L("fused", 889, 892, 4, 31, 32, 28, 3, "the bound at A = 256, pitched", bound=True, over=dict(A=256)),
+    _L("fused", 892, 892, 4, 31, 32, 28, 0, "the bound at A = 256", bound=True, over=dict(A=256)),
+    _L("fused", 904, 904, 4, 34, 32, 29, 0, "the bound at A = 16", bound=True, over=dict(A=16)),
+    _L("fused", 960, 960, 4, 48, 32, 30, 0, "the backward's bound, 17 Sp + 16 floats, with 8 forward waves in "
+       "both modes", bound=True, env=FWD8),
+    # fused family at B = 6, the forward's class asserted from the profile
+    _L("fused6", 516, 516, 3, 1, 32, 17, 0, "register-staged pair, third trip", env=FUSED6),
+    _L("fused6", 772, 772, 4, 1, 32, 25, 0, "fourth trip", env=FUSED6),
+    _L("fused6", 900, 900, 4, 33, 32, 29, 0, "the bound", bound=True, env=FUSED6),
+]
+# bf16 mode (B16: A = 64, B = 6, split family) and the module-level calls (F32, B = 6): rows of S alone
+S_BF16_LARGE = [(516, "train"), (900, "train"), (4096, "train"), (900, "eval"), (4096, "eval")]
+S_MODULES_LARGE = (516, 900, 4096)
+
+
+def large_rows(sec):
+    return [r for r in LARGE if r.sec == sec]
+
+
+def large_id(r):
+    return "-".join([str(r.S)] + [f"{k}{v}" for k, v in sorted(r.over.items())] + sorted(r.env))
+
+
 ATT_ENV = ("RAU_ATT_SPLIT", "RAU_ATT_FUSED", "RAU_ATT_DMA_OFF", "RAU_ATT_CHUNKS")
+WAVE_ENV = ("RAU_ATT_WAVES_FWD", "RAU_ATT_WAVES_BWD")
 
 
 def test_the_case_table_states_the_pitch():
@@ -115,7 +181,7 @@ def check(monkeypatch, S, B, mode, env=None, prof=False, over=None):
     over: dimensions that replace F32's (tests/test_gpu_widths.py sweeps the widths through this)."""
     from oracle import ref_torch
     from rau_vqa_amd import model
-    for k in ATT_ENV:
+    for k in ATT_ENV + WAVE_ENV:
         monkeypatch.delenv(k, raising=False)
     for k, v in (env or {}).items():
         monkeypatch.setenv(k, v)               # read when the context is created / at every launch
@@ -229,14 +295,23 @@ def test_module_level_feval(S):
     (dict(B=66), 901, True, b"900 positions at which the fused"),
     (dict(B=66, A=256), 893, True, b"892 positions at which the fused"),
     (dict(B=66, dtype=1), 901, True, b"900 positions at which the fused"),
+    (dict(B=66), 900, False, None),                    # the bounds that section 7 runs
+    (dict(B=66, A=256), 892, False, None),
+    (dict(B=66, A=16), 904, False, None),
+    (dict(B=66, A=16), 905, True, b"904 positions at which the fused"),
+    (dict(B=66, env=FWD8), 960, False, None),          # `env`: set when rau_create reads its policy, not a dimension
+    (dict(B=66, env=FWD8), 961, True, b"960 positions at which the fused"),
 ])
 def test_create_refuses_what_an_attention_kernel_cannot_launch(monkeypatch, over, S, refused, family):
     """By reading (kernels.hip att_max_pitch), nothing is launched: the configuration checks of rau_create come
     before it touches the device, so an accepted S is told apart by getting past them -- here to the device
     check, which device_id = -1 fails."""
     from rau_vqa_amd import _lib
-    for k in ATT_ENV + ("RAU_ATT_WAVES_FWD", "RAU_ATT_WAVES_BWD"):
+    over = dict(over)
+    for k in ATT_ENV + WAVE_ENV:
         monkeypatch.delenv(k, raising=False)
+    for k, v in over.pop("env", {}).items():
+        monkeypatch.setenv(k, v)
     lib = _lib.lib()
     cfg = _lib.RauConfig()
     lib.rau_default_config(C.byref(cfg))
@@ -250,3 +325,50 @@ def test_create_refuses_what_an_attention_kernel_cannot_launch(monkeypatch, over
         assert family in msg and b"64 KB" in msg, msg
     else:
         assert b"device_id" in msg, msg
+
+
+# ---------------------------------------------------------------- 7. from 400 positions to the bound
+def clear_env(monkeypatch):
+    for k in ATT_ENV + WAVE_ENV:
+        monkeypatch.delenv(k, raising=False)
+
+
+def test_the_large_table_states_the_pitch():
+    assert all(r.pitch == (r.S + 3) & ~3 and 400 < r.S for r in LARGE)
+
+
+@pytest.mark.parametrize("mode", ["train", "eval"])
+@pytest.mark.parametrize("row", large_rows("split") + large_rows("split64"), ids=large_id)
+def test_split_family_to_its_bound(monkeypatch, row, mode):
+    """B = 6, and B = 64 at the bound: k_att_score_part and k_att_da_part with 4 Sp floats of LDS, up to the 64 KB
+    that a launch gets; up to 16 trips of the q0 loop."""
+    check(monkeypatch, row.S, 64 if row.sec == "split64" else 6, mode, row.env, over=row.over)
+
+
+@pytest.mark.parametrize("mode", ["train", "eval"])
+@pytest.mark.parametrize("row", large_rows("fused"), ids=large_id)
+def test_fused_family_to_its_bound(monkeypatch, row, mode):
+    """B = 66.  Evaluate mode runs the forward on 16 waves: (16 + 2) Sp + 32 + A floats, the request that sets the
+    bound; under RAU_ATT_WAVES_FWD=8 the 16-wave backward sets it."""
+    check(monkeypatch, row.S, 66, mode, row.env, over=row.over)
+
+
+@pytest.mark.parametrize("row", large_rows("fused6"), ids=large_id)
+def test_fused_family_at_a_small_batch_to_its_bound(monkeypatch, row):
+    launched = check(monkeypatch, row.S, 6, "train", row.env, prof=True)
+    fwd = {k: v for k, v in launched.items() if k.startswith("att_fwd")}
+    assert fwd == {"att_fwd_fused_regs": F32["H"]}, launched
+
+
+@pytest.mark.parametrize("S,mode", S_BF16_LARGE)
+def test_bf16_to_the_bound(monkeypatch, S, mode):
+    """conv_wgrad's 32-deep bf16 chunks up to 128 per sample, the split attention family on bf16-mode operands.
+    tests/test_positions_host.py holds the emulation alone to the same bars at these S."""
+    clear_env(monkeypatch)
+    test_gpu_bf16.run(dict(B16, S=S), SCALE, mode)
+
+
+@pytest.mark.parametrize("S", S_MODULES_LARGE)
+def test_module_level_feval_to_the_bound(monkeypatch, S):
+    clear_env(monkeypatch)
+    module_level_feval(dict(F32, B=6, S=S), 2000 + S, f"S={S}")

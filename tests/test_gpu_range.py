@@ -6,7 +6,8 @@ and their regime predicates, tests/test_range_host.py what the references alone 
    larger of the two f32 restatements' errors on that slice, from the references alone (at most 2e-4 on a single-site
    scenario, tests/test_range_host.py).  `error / bar` is printed per case.  Beyond the max-norm: everything finite,
    attention >= 0 with rows summing to 1 within 1e-6, pad columns and positions behind a region count exactly +0, a
-   placed peak exactly 1.0f (two: 0.5f / 0.5f) and exactly 0 elsewhere, the attention argmax fp64's.
+   placed peak exactly 1.0f (two: 0.5f / 0.5f) and exactly 0 elsewhere, the attention argmax fp64's.  The peaks above
+   400 positions (range_cases.PEAKS_ABOVE_400) run in the split family to 4096 and in the fused one to its bound of 900.
 2. bf16 mode through tests/test_gpu_bf16.run, bars unchanged; the rows are range_cases.BF16_CASES.
 3. The consumers of big logits: loss rows, rau_step_stats' merged losses, rau_topk's confidences, the answer-set
    criterion, rau_backward_merged.
@@ -29,7 +30,10 @@ pytestmark = pytest.mark.gpu
 MODES = ("train", "eval")
 FUSED_ENVS = {"FUSED": {"RAU_ATT_FUSED": "1"}, "FUSED DMA_OFF": {"RAU_ATT_FUSED": "1", "RAU_ATT_DMA_OFF": "1"}}
 # the fused family and its register-staged form at B = 6: every placed peak, saturated addfeat, combined
-FUSED_CASES = rc.PEAKS + ("sat_addfeat", "combined")
+FUSED_CASES = tuple(n for n in rc.PEAKS if n not in rc.PEAKS_ABOVE_400) + ("sat_addfeat", "combined")
+# the peaks above 400 positions that the fused family can be created for (the others are the split family's alone);
+# RAU_ATT_DMA_OFF changes nothing above 256 positions
+FUSED_ABOVE_400 = tuple(n for n in rc.PEAKS_ABOVE_400 if rc.SCENARIOS[n].S <= rc.FUSED_MAX_S)
 STEP_CASES = tuple(n for n in rc.SCENARIOS if n not in ("sat_i_embed_bf16", "sat_i_embed_tied"))
 
 
@@ -151,7 +155,14 @@ def test_fused_family(monkeypatch, name, env, mode):
     step_case(monkeypatch, name, mode, env=FUSED_ENVS[env])
 
 
-@pytest.mark.parametrize("name", ["combined", "peak_first"])
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name", FUSED_ABOVE_400)
+def test_fused_family_above_400_positions(monkeypatch, name, mode):
+    """The register-staged pair at B = 6, up to the family's bound of 900 positions."""
+    step_case(monkeypatch, name, mode, env=FUSED_ENVS["FUSED"])
+
+
+@pytest.mark.parametrize("name", ["combined", "peak_first"] + list(FUSED_ABOVE_400))
 def test_large_batch(monkeypatch, name):
     """B = 66: the fused family and the `light` policies without a knob."""
     step_case(monkeypatch, name, "train", B=66)

@@ -26,7 +26,9 @@ STATE, INVALID = -3, -1
 BITS = ("losses", "argmax", "logits", "dopred", "att", "q", "att_c", "att_h", "g_embed", "g_rnn", "g_mult")
 
 BOXES = dict(B=8, T=5, V=40, E=8, Rq=16, D=24, S=100, M=40, A=20, R=16, K=12, H=3)   # box features at a fixed S
-SHAPES = {"small": (util.SMALL, 0.5), "seven": (SEVEN, 0.5), "wide": (WIDE, 0.3), "boxes": (BOXES, 0.5)}
+# above 400 positions: the fused family's bound at these widths' class (900), the split family's (4096)
+SHAPES = {"small": (util.SMALL, 0.5), "seven": (SEVEN, 0.5), "wide": (WIDE, 0.3), "boxes": (BOXES, 0.5),
+          "boxes900": (dict(BOXES, S=900), 0.5), "boxes4096": (dict(BOXES, S=4096), 0.5)}
 
 
 def counts_of(name):
@@ -37,6 +39,10 @@ def counts_of(name):
         return np.array([49, 48, 1, 17, 30, 5], np.int32)
     if name == "boxes":
         return np.array([100, 10, 99, 36, 1, 57, 64, 100], np.int32)
+    if name in ("boxes900", "boxes4096"):
+        # S, S - 1, 1; the first position of the second and third q0 trip's quad; a count in the last trip
+        S = SHAPES[name][0]["S"]
+        return np.array([S, 10, S - 1, 257, 1, 513, S - 130, S], np.int32)
     n = np.random.default_rng(11).integers(1, WIDE["S"] + 1, WIDE["B"]).astype(np.int32)
     n[:6] = [196, 1, 195, 7, 64, 129]
     return n
@@ -124,6 +130,8 @@ CASES = [
     ("boxes", {}, SPLIT),
     ("boxes", {"RAU_ATT_FUSED": "1"}, FUSED),
     ("boxes", {"RAU_ATT_FUSED": "1", "RAU_ATT_DMA_OFF": "1"}, REGS),
+    ("boxes900", {"RAU_ATT_FUSED": "1"}, REGS),                            # above 256 positions: k_att_fwd_fused
+    ("boxes4096", {}, SPLIT),                                              # k_att_ctx over 16 trips of `s += 256`
 ]
 
 

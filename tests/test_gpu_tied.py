@@ -35,7 +35,8 @@ def problem(name):
     dims, scale, over = {"small": (util.SMALL, 0.5, {}), "edge": (util.EDGE, 0.5, {}),
                          "medium": (util.MEDIUM, 0.2, {}), "s49": (S49, 0.5, {}),
                          "px0": (util.SMALL, 0.5, dict(p_x=0.0)),
-                         "b5": (dict(util.SMALL, B=5), 0.5, {})}[name]
+                         "b5": (dict(util.SMALL, B=5), 0.5, {}),
+                         "s900": (dict(util.SMALL, S=900), 0.5, {})}[name]
     sh = util.shapes(dims, **over)
     batch, params, masks = util.make_problem(sh, scale=scale)
     masks = dict(masks, x=np.ascontiguousarray(masks["x"][0]))   # hop 0's mask is the tied one
@@ -128,7 +129,8 @@ def layouts_of(m):
     ("small", (3, 0, 0)),        # HA 1
     ("small", (0, 0, 0)),        # HA 0
     ("px0", (3, 3, 3)),          # no mask at all, the switch on: the summed backward on the unmasked map
-], ids=["small", "edge-h1", "medium-s196", "s49-pitched", "hopw-110", "hopw-300", "hopw-000", "px0"])
+    ("s900", (3, 3, 3)),         # the fused attention family's bound: tied_bwd.hip's sums over 900 positions
+], ids=["small", "edge-h1", "medium-s196", "s49-pitched", "hopw-110", "hopw-300", "hopw-000", "px0", "s900"])
 def test_tied_step_against_the_oracle(name, hop_w):
     sh, batch, params, masks = problem(name)
     m = model(sh, params)

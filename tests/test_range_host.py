@@ -9,6 +9,9 @@ Measured (F32 dims, B = 6, largest slice error of the two f32 restatements, trai
   sat_i_embed 2.8e-6 / 2.2e-6   sat_addfeat 2.9e-6 / 2.2e-6     sat_att_lstm 1.9e-6 / 5.2e-6
   sat_encoder 5.3e-6 / 2.3e-6   sat_q_embed 2.9e-6 / 5.2e-6     big_logits_top 1.0e-5 / 3.4e-6
   big_logits_bottom 3.7e-5 / 2.3e-5 (att_score.b)               combined (not capped) 8.2e-6 / 9.6e-6
+  above 400 positions: peak_last_4096 7.1e-7 / 4.6e-7   peak_before_pad_4093 6.1e-7 / 5.1e-7   two_peaks_4096 2.8e-6 /
+  2.8e-6 (att_mem.b)   peak_third_trip_772 6.8e-7 / 7.4e-7   peak_last_900 4.4e-7 / 5.1e-7   peak_before_pad_897
+  5.3e-7 / 5.5e-7   peak_before_count_900 9.8e-7 / 6.8e-7
 The two fp64 oracles: at most 2.5e-13 absolute (combined, logits of magnitude 338).
 """
 import numpy as np
