@@ -135,6 +135,17 @@ int rau_outputs_dev(rau_ctx* ctx, const float** logits, const float** dopred, co
 int rau_logits_pitch(rau_ctx* ctx, int32_t* pitch);
 int rau_backward_ext(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
                      const float* merge_w, const rau_out_grads* g);
+int rau_set_state_dev(rau_ctx* ctx, const void* c0_dev, const void* h0_dev, int type);
+int rau_batch_state(rau_ctx* ctx, int* has);
+int rau_state_dev(rau_ctx* ctx, const float** c, const float** h);
+typedef struct rau_state_grads {
+  const float* d_h;
+  const float* d_c_last;
+} rau_state_grads;
+int rau_backward_state(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
+                       const float* merge_w, const rau_out_grads* g, const rau_state_grads* sg);
+int rau_state_grad_dev(rau_ctx* ctx, const float** d_c0, const float** d_h0);
+int rau_get_state_grad(rau_ctx* ctx, float* d_c0_host, float* d_h0_host);
 int rau_embed_forward(rau_ctx* ctx, int t, const int32_t* tokens_dev, float** we);
 int rau_embed_backward(rau_ctx* ctx, int t, const int32_t* tokens_dev, const float* d_we);
 int rau_deeplstm_forward(rau_ctx* ctx, int t, const float* x, const float* state,
@@ -785,6 +796,56 @@ function RAU:backwardExt(hop_w, select_w, att_w, merge_w, grads)
     g.d_logits, g.d_dopred, g.d_attprob = grads.logits, grads.dopred, grads.attprob
   end
   check(C.rau_backward_ext(self.h, w, sw, aw, mw, g))
+end
+
+-- Initial state of the hop chain from the caller (rau_set_state_dev): c0, h0 DEVICE pointers to dense [n,R] elements
+-- of stype 'f32' (default), 'f16' or 'bf16', ordered by the caller in front of the ctx's stream.  It attaches to the
+-- resident batch: forward / graphStep start hop 0 from it, every backward leaves stateGrad() behind.  Both nil
+-- detach it, and so does the next setBatch* / useBatch / setBatchSize.  The copy is taken at the call, so c0, h0 may
+-- be the last hop's rows of stateDev(): carrying the state is one call.
+function RAU:setStateDev(c0, h0, stype)
+  local t = RAU.QUESTION_TYPES[stype or 'f32']
+  assert(t, 'setStateDev: stype is one of f32, f16, bf16')
+  check(C.rau_set_state_dev(self.h, c0, h0, t))
+  return self
+end
+function RAU:batchState()
+  local has = ffi.new('int[1]')
+  check(C.rau_batch_state(self.h, has))
+  return has[0] ~= 0
+end
+-- c' and h' of every hop of the last step-level forward in device memory: two const float* cdata [H,n,R]
+-- (rau_state_dev); valid until the next forward, ordered on the ctx's stream
+function RAU:stateDev()
+  local c, h = ffi.new('const float*[1]'), ffi.new('const float*[1]')
+  check(C.rau_state_dev(self.h, c, h))
+  return c[0], h[0]
+end
+-- backwardExt with the gradients of the caller's term at the hop states as well (rau_backward_state): sgrads =
+-- { h =, c_last = }, DEVICE float* to dense [H,n,R] (every hop's h') and [n,R] (the last hop's c'), or nil
+function RAU:backwardState(hop_w, select_w, att_w, merge_w, grads, sgrads)
+  local H = self.cfg.H
+  local w = hop_w and hop_array(H, hop_w) or nil
+  local sw = select_w and hop_array(H, select_w) or nil
+  local aw = att_w and hop_array(H, att_w) or nil
+  local mw = merge_w and merge_array(merge_w) or nil
+  local g, sg = nil, nil
+  if grads then
+    g = ffi.new('rau_out_grads')
+    g.d_logits, g.d_dopred, g.d_attprob = grads.logits, grads.dopred, grads.attprob
+  end
+  if sgrads then
+    sg = ffi.new('rau_state_grads')
+    sg.d_h, sg.d_c_last = sgrads.h, sgrads.c_last
+  end
+  check(C.rau_backward_state(self.h, w, sw, aw, mw, g, sg))
+end
+-- the last backward's gradient at the attached initial state in device memory: d_c0, d_h0, const float* cdata [n,R]
+-- (rau_state_grad_dev); valid until the next forward, ordered on the ctx's stream
+function RAU:stateGrad()
+  local dc, dh = ffi.new('const float*[1]'), ffi.new('const float*[1]')
+  check(C.rau_state_grad_dev(self.h, dc, dh))
+  return dc[0], dh[0]
 end
 
 -- zeroGradParameters (unless zero_grads == false) + forward + backward as one captured graph launch

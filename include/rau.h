@@ -976,6 +976,70 @@ int rau_batch_question(rau_ctx* ctx, int* has);
 int rau_question_grad_dev(rau_ctx* ctx, const float** dq /* [n,Q] f32 DEVICE */);
 int rau_get_question_grad(rau_ctx* ctx, float* host /* [n,Q] dense */);
 
+/* ---- the hop recurrence's two ends: initial state in, state gradients in and out ---------------------------------
+ * The answering unit is a recurrence: hop h reads the attention-LSTM state (c, h) of hop h-1.  The step path starts
+ * it from zeros and hands the last hop's c' / h' zero gradients (the reference's).  These calls open both ends, as
+ * every recurrent unit's interface does: (h0, c0) in, (hn, cn) out, gradients through both.  They add no parameter
+ * and no layout; a context that never attaches a state or passes state gradients allocates, launches and computes
+ * exactly what it did without them.
+ *   attaching    rau_set_state_dev attaches (c0, h0), each [n,R] dense in DEVICE memory, 16-byte aligned, to the
+ *                RESIDENT batch, by rau_set_question_dev's rules: type is RAU_FEAT_F32, RAU_FEAT_F16 or RAU_FEAT_BF16,
+ *                widened exactly; one launch (state_attach) on the ctx's stream at the call, no host wait; the caller
+ *                orders its producer in front of rau_stream and keeps the sources unchanged until the launch has run.
+ *                The copy is taken at the call, so the sources may be the context's own rau_state_dev rows of the
+ *                last hop: carrying the state into the next forward is one call.  The attached state survives any
+ *                number of forwards; attaching again replaces it.  A forward that ran before the call has no backward.
+ *   detaching    both pointers NULL detach: the next forward starts from zeros again (the launch's detaching form
+ *                writes them; a call without an attached state launches nothing).  Every call that makes another batch
+ *                current detaches too (rau_set_batch*, rau_use_batch, a rau_set_batch_size that changes the size);
+ *                the next forward then writes the zeros itself, as it always has.  rau_batch_state reports the flag.
+ *   forward      the hops read the state where they read the zeros; every launch is the detached path's, except that
+ *                the two clears of the initial-state rows are not issued.  Train and evaluate mode, every batch form,
+ *                region counts, tied dropout, bf16 mode and an attached question are unaffected.  An attached all-zero
+ *                state gives the detached forward's output bits.
+ *   rau_state_dev  ctx-owned DEVICE pointers to c' and h' of every hop of the last step-level forward, [H,n,R] f32
+ *                dense in the current n (hop H-1's rows are the final state), ordered on the ctx's stream, no
+ *                synchronisation; valid until the next forward, module-level call or rau_set_batch_size.
+ *                RAU_ERR_STATE without a step-level forward to read.
+ *   gradients in rau_backward_state is rau_backward_ext with sg: d_h [H,n,R] is dF/dh' of every hop, added to the
+ *                recurrent gradient inside that hop's cell backward (the operand the module-level path's dh_next
+ *                takes); d_c_last [n,R] is dF/dc' of the LAST hop, the recurrence's first dc_next.  Both f32 DEVICE,
+ *                16-byte aligned, read on the ctx's stream during the call's launches.  With either non-NULL every hop
+ *                is active (the host cannot see zero rows), hop_w may be NULL, and labels are needed only by a
+ *                built-in term.  sg NULL or both members NULL IS rau_backward_ext with the other five arguments: the
+ *                same launches, the same bits.  A gradient at c' of the hops BEFORE the last is not offered: it
+ *                would be a new addend in the cell kernel.  There is no captured variant, as for rau_backward_ext.
+ *   gradients out  with a state attached EVERY step-level backward (rau_backward, _select, _att, _merged, _ext,
+ *                _state, every rau_graph_step*) also leaves d_c0 and d_h0 [n,R]: hop 0 forms its three products
+ *                towards prev_h like every other hop, and one launch behind it (state_grad_finish) sums their
+ *                split-K partials in ascending order into d_h0 and copies the cell's dc_prev into d_c0.  No atomics:
+ *                repeated steps give the same bits, a captured step the eager step's.  Overwritten by each backward,
+ *                never accumulated; rau_zero_grads does not touch them; exact zeros when no hop is active.
+ *                rau_state_grad_dev hands out the ctx-owned DEVICE pointers (no synchronisation; valid until the next
+ *                forward or rau_set_batch_size), rau_get_state_grad downloads them (synchronises; either may be NULL).
+ *                Both are RAU_ERR_STATE without an attached state or before a backward of the current forward.
+ *                Hop 0 then takes the branch of the other hops (with M == R the batched dg launch), so the
+ *                parameter-gradient BITS of a step on an attached all-zero state need not equal a detached step's.
+ *   captured     "a state is attached" joins rau_graph_step's key.  A captured step holds the initial-state rows'
+ *                address, never their contents: a replay reads the state attached last.
+ *   errors       nothing launched, the previous state stays in force: a null ctx; a step being captured or no
+ *                resident batch (RAU_ERR_STATE); exactly one NULL pointer, a pointer that is not 16-byte aligned, an
+ *                fp8 or unknown type (RAU_ERR_INVALID).
+ *   unchanged    the module-level calls (they take the state from the caller already); the state is per sample,
+ *                also on a batch with an image table. */
+int rau_set_state_dev(rau_ctx* ctx, const void* c0_dev, const void* h0_dev /* [n,R] DEVICE; both NULL = detach */, int type);
+int rau_batch_state(rau_ctx* ctx, int* has);
+int rau_state_dev(rau_ctx* ctx, const float** c /* [H,n,R] f32 DEVICE */, const float** h /* [H,n,R] f32 DEVICE */);
+typedef struct rau_state_grads {
+  const float* d_h;       /* [H,n,R] DEVICE: dF/dh' of every hop;  NULL = none */
+  const float* d_c_last;  /* [n,R]   DEVICE: dF/dc' of the LAST hop; NULL = none */
+} rau_state_grads;
+int rau_backward_state(rau_ctx* ctx, const float* hop_w /* [H] host, NULL = zeros */, const float* select_w,
+                       const float* att_w, const float* merge_w, const rau_out_grads* g /* NULL = none */,
+                       const rau_state_grads* sg /* NULL = none */);
+int rau_state_grad_dev(rau_ctx* ctx, const float** d_c0 /* [n,R] f32 DEVICE */, const float** d_h0 /* [n,R] f32 DEVICE */);
+int rau_get_state_grad(rau_ctx* ctx, float* d_c0_host /* [n,R] dense */, float* d_h0_host /* [n,R] dense */);
+
 /* ---- module-level entry points: one call per nn.Module :forward / :backward -----
  * For hosts that keep feval's own loops (SS:443-596) and call the clones one by one.
  * t in [0,T) / h in [0,H) select the clone (the reference's embed_clones[t+1],

@@ -59,6 +59,11 @@ class RauOutGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("d_logits", "d_dopred", "d_attprob")]
 
 
+class RauStateGrads(C.Structure):
+    """Mirror of ``rau_state_grads`` (include/rau.h): device pointers, None = no such term."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_h", "d_c_last")]
+
+
 class RauError(RuntimeError):
     pass
 
@@ -195,6 +200,14 @@ _SIGS = {
     "rau_batch_question": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rau_question_grad_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_get_question_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # the hop recurrence's ends: initial state in, state gradients in and out
+    "rau_set_state_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "rau_batch_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rau_state_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "rau_backward_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(RauOutGrads), C.POINTER(RauStateGrads)]),
+    "rau_state_grad_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "rau_get_state_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     # module-level entry points: device pointers in, pointers to ctx-owned slots out
     "rau_embed_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_embed_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

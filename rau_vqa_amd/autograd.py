@@ -43,6 +43,17 @@ The backward returns a clone of ``rau.question_grad_tensor()`` for q, ordered wi
 gradient; the embed and rnn groups of the ctx receive nothing.  ``feats=`` and ``question=`` work together in one
 step and one ``loss.backward()``.
 
+``step(rau, ..., state=(c0, h0))`` opens the RECURRENCE: c0, h0 are the CUDA tensors [n,R] given to ``set_state`` -- the
+state a previous question about the same images left, or the final state of an earlier segment -- and receive the
+gradient at the initial state.  ``return_state=True`` adds the hop states to the outputs,
+(logits, dopred, attprob, h [H,n,R], c_last [n,R]), differentiable at all five: a torch head on the per-hop state h'
+(an answer-type classifier, a contrastive term) trains through the same backward, and chained segments hand the
+gradient at one segment's initial state to the previous segment's final state (truncated BPTT)::
+
+    rau.set_batch_dev(x, tokens, lens, labels, state=(c0, h0))
+    logits, dopred, attprob, h, c_last = autograd.step(rau, hop_w, state=(c0, h0), return_state=True)
+    (my_loss(logits) + head(h[-1]).logsumexp(1).mean()).backward()   # c0.grad, h0.grad flow on
+
 torch is plumbing here: the forward, the backward and the update are librau's kernels; torch evaluates the
 caller's loss and its gradient at the three outputs, on its own current stream.  The two streams are joined with
 events only (ExternalStream + wait_stream), never with a host synchronisation.
@@ -54,7 +65,7 @@ import torch
 
 class _Step(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, question, rau, hop_w, select_w, att_w, merge_w):
+    def forward(ctx, anchor, question, c0, h0, rau, hop_w, select_w, att_w, merge_w, return_state):
         dev = torch.device("cuda", rau.cfg.device_id)
         rau.forward()
         own = torch.cuda.ExternalStream(rau.stream(), device=dev)
@@ -62,24 +73,29 @@ class _Step(torch.autograd.Function):
         cur.wait_stream(own)                    # the outputs are ordered on the ctx's stream
         # clones: autograd owns what it hands out, the views die with the next forward
         outs = tuple(t.clone() for t in rau.output_tensors())
+        if return_state:                        # h' of every hop and the last hop's c'
+            cs, hs = rau.state_tensors()
+            outs = outs + (hs.clone(), cs[-1].clone())
         ctx.rau, ctx.weights, ctx.dev = rau, (hop_w, select_w, att_w, merge_w), dev
         ctx.has_feats = anchor.dim() == 3       # step(feats=x): x is the recorded input, not the scalar anchor
         ctx.q_dtype = None if question is None else question.dtype   # step(question=q): q is a recorded input too
+        ctx.s_dtype = None if c0 is None else c0.dtype   # step(state=(c0, h0)): so are c0 and h0
         ctx.set_materialize_grads(False)        # an unused output's gradient stays None instead of a zero tensor
         return outs
 
     @staticmethod
-    def backward(ctx, d_logits, d_dopred, d_attprob):
+    def backward(ctx, d_logits, d_dopred, d_attprob, d_h=None, d_c_last=None):
         rau = ctx.rau
         # an output the loss did not use arrives as None and goes to the library as NULL
         grads = {k: g.contiguous().float() for k, g in
                  (("logits", d_logits), ("dopred", d_dopred), ("attprob", d_attprob)) if g is not None}
         own = torch.cuda.ExternalStream(rau.stream(), device=ctx.dev)
         own.wait_stream(torch.cuda.current_stream(ctx.dev))   # the gradients were written on torch's stream
-        for g in grads.values():
+        sgrads = {k: g.contiguous().float() for k, g in (("h", d_h), ("c_last", d_c_last)) if g is not None}
+        for g in list(grads.values()) + list(sgrads.values()):
             g.record_stream(own)               # the caching allocator must not hand them out before the ctx has read them
         hop_w, select_w, att_w, merge_w = ctx.weights
-        rau.backward(hop_w, select_w, att_w, merge_w, out_grads=grads)
+        rau.backward(hop_w, select_w, att_w, merge_w, out_grads=grads, state_grads=sgrads or None)
         gx = None
         if ctx.has_feats:                       # the gradient at the feature map, for the graph in front of it
             torch.cuda.current_stream(ctx.dev).wait_stream(own)
@@ -90,10 +106,16 @@ class _Step(torch.autograd.Function):
             torch.cuda.current_stream(ctx.dev).wait_stream(own)
             gq = rau.question_grad_tensor().to(ctx.q_dtype, copy=True)   # [n,Q], in a 16-bit q's own type
             own.wait_stream(torch.cuda.current_stream(ctx.dev))   # the next step overwrites the buffer: behind the clone
-        return (gx, gq) + (None,) * 5           # parameter gradients live in the ctx's flat buffers
+        gc = gh = None
+        if ctx.s_dtype is not None:                  # the gradient at the attached initial state
+            torch.cuda.current_stream(ctx.dev).wait_stream(own)
+            gc, gh = (t.to(ctx.s_dtype, copy=True) for t in rau.state_grad_tensors())   # [n,R] each
+            own.wait_stream(torch.cuda.current_stream(ctx.dev))   # the next step overwrites the buffer: behind the clones
+        return (gx, gq, gc, gh) + (None,) * 6   # parameter gradients live in the ctx's flat buffers
 
 
-def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, feats=None, question=None):
+def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, *, state=None, return_state=False,
+         feats=None, question=None):
     """forward of the resident batch -> (logits, dopred, attprob), differentiable at those three outputs.
 
     hop_w, select_w, att_w, merge_w: the built-in terms of RAU.backward, added to whatever loss the caller builds
@@ -105,7 +127,24 @@ def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, feats=None, q
     resident image-table batch under want_feature_grad(per_image=True): the table [N,D,S].
 
     question: the CUDA tensor [n,Q] attached to the resident batch (RAU.set_question, set_batch_dev(question=)): it
-    becomes a recorded input and receives the gradient at the question state."""
+    becomes a recorded input and receives the gradient at the question state.
+
+    state: (c0, h0), the CUDA tensors [n,R] attached to the resident batch (RAU.set_state, set_batch_dev(state=)): they
+    become recorded inputs and receive the gradient at the initial state of the hop chain.
+
+    return_state: also return h [H,n,R] (h' of every hop) and c_last [n,R] (c' of the last hop), differentiable like
+    the three outputs; the default stays the 3-tuple."""
+    c0 = h0 = None
+    if state is not None:
+        c0, h0 = state
+        shape = (rau.batch_size, rau.cfg.R)
+        for t in (c0, h0):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and tuple(t.shape) == shape):
+                raise ValueError(f"state must be the CUDA tensors (c0, h0), each [n,R] = {shape}, given to set_state")
+        if not rau.batch_state:
+            raise ValueError("step(state=...) needs the state attached: call rau.set_state(c0, h0) first")
+        if not (c0.requires_grad or h0.requires_grad):   # (tensors nobody differentiates are just the attached state)
+            c0 = h0 = None
     x = None   # the recorded feature-map input, where there is one
     if question is not None:
         if not (isinstance(question, torch.Tensor) and question.is_cuda and
@@ -133,4 +172,4 @@ def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, feats=None, q
     if x is None:
         # a leaf that requires grad makes autograd record the node: the real leaves are the ctx's parameters
         x = torch.zeros((), device=torch.device("cuda", rau.cfg.device_id), requires_grad=True)
-    return _Step.apply(x, question, rau, hop_w, select_w, att_w, merge_w)
+    return _Step.apply(x, question, c0, h0, rau, hop_w, select_w, att_w, merge_w, bool(return_state))

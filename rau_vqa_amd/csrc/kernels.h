@@ -587,6 +587,15 @@ hipError_t ext_signal(hipStream_t st, int rows, int M, const float* dopred, cons
                       bool acc, float* s, float* add);
 hipError_t ext_da(hipStream_t st, int hops, int Bper, int S, const float* d, const int32_t* nreg, bool acc,
                   float* da, int d_rs);
+// The ends of the hop recurrence (state_io.hip, rau_set_state_dev / rau_state_grad_dev).  Each one launch, no atomics.
+// state_attach: cc[i] = widen(c0[i]), hh[i] = widen(h0[i]) for i < n_elems (a multiple of 4); type RAU_FEAT_F32 |
+// F16 | BF16; c0 and h0 both null: the detaching form, zero bits into both.  All bases 16-byte aligned.
+// state_grad_finish: d_h0[i] = part[0][i] + .. + part[ns-1][i] in ascending order (+0 with ns = 0), d_c0[i] =
+// dc_prev[i]; part is a span of split-K partials (checked like every consumer's: kSplitStateError).
+hipError_t state_attach(hipStream_t st, size_t n_elems, const void* c0, const void* h0, int type, float* cc,
+                        float* hh);
+hipError_t state_grad_finish(hipStream_t st, size_t n_elems, const float* part, int ns, const float* dc_prev,
+                             float* d_c0, float* d_h0);
 hipError_t scale_hops(hipStream_t st, int H, size_t per_hop, const float* w_dev, float* x);
 // x_i[h][0 .. p_i) *= w[h] for three hop-major tensors in one launch
 hipError_t scale_hops3(hipStream_t st, int H, const float* w_dev, size_t p0, float* x0, size_t p1, float* x1,

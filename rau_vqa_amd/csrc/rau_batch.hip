@@ -297,6 +297,7 @@ void hold(rau_ctx* ctx, int si, const Batch& b) {
   d.sample_w = false;      // ... and per-sample loss weights
   d.cand_C = 0;            // ... and multiple-choice candidates
   d.question = false;      // ... and the caller's question state
+  d.state = false;         // ... and the caller's initial state (the next forward clears the rows itself)
 }
 
 // rau_set_batch_images, or (b.bank_rows) the same batch with its table drawn from the bank
@@ -805,9 +806,11 @@ int rau_use_batch(rau_ctx* ctx, int slot) {
     p.consumed_valid = true;
   }
   cur_batch(ctx).held.question = false;   // a question is the resident batch's (rau_set_question_dev): it goes with it
+  cur_batch(ctx).held.state = false;      // ... and so is an initial state (rau_set_state_dev)
   ctx->cur_slot = slot;
   drop_forward(ctx);
   s.held.question = false;
+  s.held.state = false;
   // the bulk and weight-gradient streams start each step behind an event of the chain stream,
   // so ordering the chain stream behind the upload orders all three
   HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
@@ -1185,6 +1188,70 @@ int rau_get_question_grad(rau_ctx* ctx, float* host) {
   NEED(ctx && host, "null argument");
   if (int rc = question_grad_state(ctx, "rau_get_question_grad")) return rc;
   return d2h(ctx, host, ctx->dq, (size_t)ctx->cfg.B * ctx->Q * sizeof(float));
+}
+
+// The caller's initial state of the hop chain for the resident batch: one launch on the chain stream that widens
+// (c0, h0) into slot 0 of cc / hh, behind every launch that reads the previous contents; nothing waits for the
+// device.  The flag is the batch's (BatchDesc::state): the forward leaves the rows alone, the backward hands out the
+// gradient at them, the graph key carries it.  Everything is checked before anything moves.
+int rau_set_state_dev(rau_ctx* ctx, const void* c0_dev, const void* h0_dev, int type) {
+  NEED(ctx, "null ctx");
+  if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_state_dev: a step is being captured");
+  BatchSlot& s = cur_batch(ctx);
+  if (!s.held.have)
+    return fail(RAU_ERR_STATE, "rau_set_state_dev: no resident batch (upload the batch first)");
+  NEED((c0_dev == nullptr) == (h0_dev == nullptr), "rau_set_state_dev: c0 and h0 go together (both NULL = detach)");
+  const size_t nR = (size_t)ctx->cfg.B * ctx->cfg.R;
+  if (!c0_dev) {   // detach: the zeros of a fresh context are back in the rows before anything reads them
+    if (!s.held.state) return RAU_OK;
+    RUN("state_attach", 0, (double)nR * 8, state_attach(ctx->st, nR, nullptr, nullptr, RAU_FEAT_F32, ctx->cc, ctx->hh));
+    s.held.state = false;
+    ctx->bwd.dstate = false;   // ... nor is the gradient a backward left at it
+    drop_forward(ctx);   // a forward that read the state is not this batch's any more
+    return RAU_OK;
+  }
+  NEED(type == RAU_FEAT_F32 || type == RAU_FEAT_F16 || type == RAU_FEAT_BF16,
+       "rau_set_state_dev: type %d is none of RAU_FEAT_F32, RAU_FEAT_F16, RAU_FEAT_BF16", type);
+  NEED(((reinterpret_cast<uintptr_t>(c0_dev) | reinterpret_cast<uintptr_t>(h0_dev)) & 15u) == 0,
+       "rau_set_state_dev: c0_dev and h0_dev must be 16-byte aligned");
+  if (!ctx->sgrad)   // for the capacity, at the first attach; cleared by rau_set_batch_size like every activation
+    if (int rc = dalloc(ctx, &ctx->sgrad, (size_t)2 * ctx->cap * ctx->cfg.R)) return rc;
+  RUN("state_attach", 0, (double)nR * 2 * (4 + feat_elem_bytes(type)),
+      state_attach(ctx->st, nR, c0_dev, h0_dev, type, ctx->cc, ctx->hh));
+  s.held.state = true;
+  ctx->bwd.dstate = false;   // what an earlier backward left is the gradient at ANOTHER state (or batch)
+  drop_forward(ctx);   // a forward that ran on the batch did not read this state
+  return RAU_OK;
+}
+
+int rau_batch_state(rau_ctx* ctx, int* has) {
+  NEED(ctx && has, "null argument");
+  *has = cur_batch(ctx).held.state ? 1 : 0;
+  return RAU_OK;
+}
+
+static int state_grad_state(rau_ctx* ctx, const char* fn) {
+  if (!cur_batch(ctx).held.state || !ctx->bwd.dstate)
+    return fail(RAU_ERR_STATE, "%s: no backward on an attached initial state (rau_set_state_dev) has run since the "
+                "last forward", fn);
+  return RAU_OK;
+}
+int rau_state_grad_dev(rau_ctx* ctx, const float** d_c0, const float** d_h0) {
+  NEED(ctx, "null ctx");
+  if (int rc = state_grad_state(ctx, "rau_state_grad_dev")) return rc;
+  if (d_c0) *d_c0 = ctx->sgrad;
+  if (d_h0) *d_h0 = ctx->sgrad + (size_t)ctx->cap * ctx->cfg.R;
+  return RAU_OK;
+}
+int rau_get_state_grad(rau_ctx* ctx, float* d_c0_host, float* d_h0_host) {
+  NEED(ctx, "null ctx");
+  if (int rc = state_grad_state(ctx, "rau_get_state_grad")) return rc;
+  const size_t nR = (size_t)ctx->cfg.B * ctx->cfg.R;
+  if (d_c0_host)
+    if (int rc = d2h(ctx, d_c0_host, ctx->sgrad, nR * sizeof(float))) return rc;
+  if (d_h0_host)
+    if (int rc = d2h(ctx, d_h0_host, ctx->sgrad + (size_t)ctx->cap * ctx->cfg.R, nR * sizeof(float))) return rc;
+  return RAU_OK;
 }
 
 int rau_batch_feats(rau_ctx* ctx, float** feats_dev) {

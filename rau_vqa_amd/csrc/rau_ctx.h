@@ -108,6 +108,9 @@ struct BatchDesc {
   // question state from the caller (rau_set_question_dev): the slot's q_ext holds q [n][Q] and the step reads it in
   // place of the built-in encoder's output.  It belongs to the RESIDENT batch: hold() and rau_use_batch drop it.
   bool question = false;
+  // initial state of the hop chain from the caller (rau_set_state_dev): slot 0 of cc / hh holds (c0, h0) [n][R] and the
+  // forward leaves it there in place of writing the zeros.  It belongs to the RESIDENT batch like the question.
+  bool state = false;
 };
 // One of the two batch slots.  slot[cur_slot] is the resident batch (cur_batch() below): the only record of it.
 // Slot 0's device buffers exist from rau_create on; slot 1's, the pinned staging the loader may fill in place, the
@@ -244,6 +247,11 @@ struct StepLoss {
   rau_out_grads ext{nullptr, nullptr, nullptr};
   bool has_ext() const { return ext.d_logits || ext.d_dopred || ext.d_attprob; }
   bool hop_any = false;              // hop_w has a non-zero entry (an ext backward without one needs no labels)
+  // caller-supplied gradients at the hop states (rau_backward_state): DEVICE pointers, null = no such term.  d_h is
+  // every hop's HopGrad::dh_next, d_c_last the hop loop's first dc_next.  With either of them every hop is active.
+  rau_state_grads sg{nullptr, nullptr};
+  bool has_sg() const { return sg.d_h || sg.d_c_last; }
+  bool external() const { return has_ext() || has_sg(); }   // some gradient comes from the caller: needs no label
   // select_w, merge_w and the external gradients are per-row terms, which cannot be folded into what the forward
   // formed (one scale per hop): such a backward forms dpre / dhn itself from the final dl
   bool forms_dpre() const { return select_w || merge_w || has_ext(); }
@@ -281,12 +289,15 @@ struct StepKey {
                                 // or a null pointer (rau_set_sample_weights); a replay reads the current weights
   int cand_C = 0;               // ... against C candidates per sample (0 = none): another head kernel, which holds the
                                 // slot's list (rau_set_candidates); a replay reads the current list
+  bool state = false;           // ... and with an initial state attached (rau_set_state_dev) the forward does not clear
+                                // slot 0 of cc / hh and the backward ends hop 0 with the state gradient's launch; a
+                                // replay reads the slot's current contents
   int xnorm = 0;                // ... and with rau_set_feat_norm the image side starts with the normalisation pass (and
   uint32_t xnorm_eps = 0;       // the backward may end with its gradient), which holds eps as an argument: its bits
   auto tied() const {
     return std::tie(mode, max_len, active, zero, mexplicit[0], mexplicit[1], mexplicit[2], mexplicit[3], mexplicit[4],
                     slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg, tied_x, ans_loss,
-                    feat_grad, question, sample_w, cand_C, xnorm, xnorm_eps);
+                    feat_grad, question, sample_w, cand_C, state, xnorm, xnorm_eps);
   }
   bool operator==(const StepKey& o) const { return tied() == o.tied(); }
 };
@@ -326,6 +337,7 @@ struct BwdRecord {
   bool dq = false;                // rau_ctx::dq holds the gradient at the ATTACHED question (rau_question_grad_dev)
   bool dX = false;                // xg_dX holds the feature-map gradient (rau_get_feat_grad) ...
   int dX_rows = 0;                // ... its map count: n, or the table's N under RAU_FEAT_GRAD_IMAGES
+  bool dstate = false;            // rau_ctx::sgrad holds the gradient at the ATTACHED initial state (rau_state_grad_dev)
 };
 
 struct rau_ctx {
@@ -409,6 +421,9 @@ struct rau_ctx {
   void* xd16 = nullptr;  // RAU_BF16 step path, S % 4 == 0: the same maps stored as bf16 (xd stays unwritten)
   // feature-map dropout kind (rau_set_feat_dropout): RAU_XDROP_PER_HOP, or RAU_XDROP_TIED = one mask for all hops
   int xdrop = RAU_XDROP_PER_HOP;
+  // gradient at the attached initial state (rau_set_state_dev, state_io.hip): d_c0 | d_h0, [2][cap][R] with the halves
+  // dense in the current n, allocated at the first attach; every backward on an attached state overwrites it
+  float* sgrad = nullptr;
   float* dS_sum = nullptr;          // [cap][A][Sp] sum of the active hops' dS (tied_bwd.hip), allocated with the switch
   // feature-map gradient (rau_set_feat_grad, xgrad.hip): off = the step path as it is without it
   int feat_grad = RAU_FEAT_GRAD_OFF;   // the mode: _SAMPLES, or _IMAGES = per image where the batch has a table
@@ -545,6 +560,7 @@ inline StepKey step_key(const rau_ctx* ctx, const StepLoss& loss, bool zero) {
   key.question = d.question;
   key.sample_w = d.sample_w;
   key.cand_C = d.cand_C;
+  key.state = d.state;
   key.xnorm = ctx->xnorm;
   if (ctx->xnorm) std::memcpy(&key.xnorm_eps, &ctx->xnorm_eps, sizeof(float));
   return key;

@@ -184,7 +184,9 @@ static void plan_batch(rau_ctx* ctx, int B, BatchPlan* p) {
     // the slab (a quarter to a sixth), whatever its output width (4R, 4Rq, K, Q, M, A or S)
     size_t sl = (size_t)16 * B * std::max({4 * R, 4 * Rq, K, Q, M, A, S});
     for (auto& sh : shapes) sl = std::max(sl, gemm_tn_slab_floats(sh[0], sh[1], sh[2]));
-    p->ws[0] = sl;
+    // a multiple of 16 floats: the quarter shares the hop chain carves out of it (hop_backward's regions) then start
+    // on 16-byte boundaries, which state_grad_finish's quad loads of hop 0's partials rely on
+    p->ws[0] = (sl + 15) & ~(size_t)15;
     // the weight-gradient stream's workspace also holds the grouped launches' partial slabs
     p->ws[2] = std::max(sl, grp_floats);
   }
@@ -1580,6 +1582,7 @@ static int forward_impl(rau_ctx* ctx, bool bwd_forms_dpre) {
   if (!bs.held.have) return fail(RAU_ERR_STATE, "rau_forward: no batch (call rau_set_batch)");
   ctx->mg.valid = false;   // the hop outputs are being overwritten
   ctx->bwd.dX = ctx->bwd.dq = false;   // ... and the gradients at the maps and at an attached question another forward's
+  ctx->bwd.dstate = false;             // ... and the one at an attached initial state
   const rau_config& c = ctx->cfg;
   const int B = c.B, Rq = c.Rq, D = c.D, S = ctx->Sp, M = c.M, A = c.A, R = c.R, H = c.H, Q = ctx->Q;
   const int TL = bs.held.max_len;
@@ -1667,8 +1670,10 @@ static int forward_impl(rau_ctx* ctx, bool bwd_forms_dpre) {
                  ctx->Yq + (size_t)B * M, M, o));
     HIPC(hipEventRecord(ctx->evQ, ctx->st3));
   }
-  HIPC(hipMemsetAsync(ctx->cc, 0, BR_ * sizeof(float), st));  // att_c, att_h zeros SS:362-365
-  HIPC(hipMemsetAsync(ctx->hh, 0, BR_ * sizeof(float), st));
+  if (!bs.held.state) {   // (an attached initial state, rau_set_state_dev, lies in the two row blocks already)
+    HIPC(hipMemsetAsync(ctx->cc, 0, BR_ * sizeof(float), st));  // att_c, att_h zeros SS:362-365
+    HIPC(hipMemsetAsync(ctx->hh, 0, BR_ * sizeof(float), st));
+  }
   const Truth truth = step_truth(ctx);
   // RAU_SEAM & 1: the heads are followed by the backward's two head products, unless that backward forms them itself
   const bool dpre = bs.held.have_labels && ctx->mode == RAU_MODE_TRAIN && (ctx->policy.seam & 1) && !bwd_forms_dpre;
@@ -1755,7 +1760,7 @@ static int loss_gradients(rau_ctx* ctx, const StepLoss& loss, const Truth& t) {
   // dpred:mul(w[h])  SS:569 / MS:568-570 / Full:587-589
   if (!ctx->capturing)   // (rau_graph_step uploads the weights before it launches the graph)
     if (int rc = upload_hop_weights(ctx, loss)) return rc;
-  if (ext.d_logits || (loss.has_ext() && !ctx->fwd.dl))
+  if (ext.d_logits || (loss.external() && !ctx->fwd.dl))
     // one pass in scale_hops' place: dl * hop_w + d_logits; without a criterion gradient dl = d_logits (or +0)
     RUN("ext_dl", (double)H * B * K * (ctx->fwd.dl ? 2 : 0), (double)H * B * K * (ctx->fwd.dl ? 12 : 8),
         ext_dl(st, H, (size_t)B, K, Kp, ctx->fwd.dl ? ctx->hopw_d : nullptr, ext.d_logits, ctx->dl));
@@ -2024,6 +2029,7 @@ static void record_backward(rau_ctx* ctx, bool graph) {
   ctx->bwd.done = true;
   ctx->bwd.graph = graph;
   ctx->bwd.dq = d.question;
+  ctx->bwd.dstate = d.state;
   ctx->bwd.dX = ctx->feat_grad != RAU_FEAT_GRAD_OFF;
   ctx->bwd.dX_rows = xgrad_per_image(ctx) ? d.n_images : ctx->cfg.B;
 }
@@ -2052,9 +2058,9 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
                 "with the feature-map gradient on (rau_set_feat_grad) the backward regenerates the forward's "
                 "feature-map dropout bits from the key: run the forward again");
   // an external-only backward reads no label: hop_w zeros, no select_w, no merge_w (att_w reads the targets alone)
-  const bool builtin = !loss.has_ext() || loss.hop_any || sel || mrg;
+  const bool builtin = !loss.external() || loss.hop_any || sel || mrg;
   if (builtin && !bs.held.have_labels) return fail(RAU_ERR_STATE, "rau_backward: batch has no labels");
-  if (builtin && loss.has_ext() && !ctx->fwd.dl)
+  if (builtin && loss.external() && !ctx->fwd.dl)
     return fail(RAU_ERR_STATE, "rau_backward_ext: the forward ran on a batch without labels, so there is no "
                 "criterion gradient for a non-zero hop_w, select_w or merge_w");
   // the head's target is read from that forward's labels or answer set: they must still be there (a captured
@@ -2077,7 +2083,10 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
   drop_forward(ctx);      // dl is scaled in place below: one backward per forward
   bool dX_first = true;   // (feat_grad) the first launch that writes xg_dX stores, the others add
   if (int rc = loss_gradients(ctx, loss, t)) return rc;
-  const float* dc_next = nullptr;  // grad_att_c / grad_att_h zeros, SS:561-562
+  // grad_att_c / grad_att_h zeros, SS:561-562; or the caller's gradients at the states (rau_backward_state: every
+  // hop is active then, so the loop's first hop is the last one)
+  const float* dc_next = loss.sg.d_c_last;
+  const bool state = bs.held.state;   // an attached initial state (rau_set_state_dev): its gradient is a result
   float* dh_part = nullptr;        // gradient at next_h: K-split partials left by the previous hop
   int dh_part_ns = 0;
   // bf16 mode, train-mode step on 14x14 maps: dS goes out as bf16 (its consumers below read that)
@@ -2100,7 +2109,9 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
       // h is the first hop of its launch group: its conv gradients may start behind att_bwd, three launches
       // before the hop's backward is over (it matters for the first group: the forward / backward seam)
       g.ev_conv_ready = (gsz[h] && (ctx->policy.seam & 2)) ? ctx->evK[h] : nullptr;
-      g.dh_prev_dead = h == 0;   // hop 0's prev_h is the constant initial state: nothing reads its gradient
+      g.dh_next = loss.sg.d_h ? loss.sg.d_h + (size_t)h * BR_ : nullptr;
+      // hop 0's prev_h is the constant initial state: nothing reads its gradient -- but for an attached one's caller
+      g.dh_prev_dead = h == 0 && !state;
       g.da_out = has_da ? ctx->att_da + (size_t)h * BS_ : nullptr;
       g.ds16 = ds16;
       if (int rc = hop_backward(ctx, h, ctx->cc + (size_t)h * BR_,
@@ -2108,6 +2119,9 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
         return rc;
     }
     dc_next = dc_out;
+    if (h == 0 && state)   // d_h0 = hop 0's dh_prev partials summed, d_c0 = its dc_prev: out of the workspace at once
+      RUN("state_grad_finish", (double)dh_part_ns * BR_, (double)(dh_part_ns + 3) * BR_ * 4,
+          state_grad_finish(st, BR_, dh_part, dh_part_ns, dc_out, ctx->sgrad, ctx->sgrad + (size_t)ctx->cap * R));
     // dq's per-hop terms dq~_h Wq (ConcatTable backward, SS:579) do not feed the recurrence: the
     // rows of a finished hop group go to the weight-gradient stream (idle until the hop loop
     // ends); only the last group's stay on this stream, in front of dq_reduce below
@@ -2143,6 +2157,7 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
     RUN("dq_reduce", 0, (double)HA * B * Q * 4,
         dq_reduce(st, HA, (size_t)B * Q, ctx->dQD, m.q, m.s_q, ctx->dq));
   }
+  if (state && HA == 0) HIPC(hipMemsetAsync(ctx->sgrad, 0, (size_t)2 * ctx->cap * R * sizeof(float), st));
   // no active hop: the gradient is zero (n rows: all of a table's N <= n too, whichever N a replay meets)
   if (ctx->feat_grad && dX_first)
     HIPC(hipMemsetAsync(ctx->xg_dX, 0, (size_t)B * c.D * S * sizeof(float), ctx->st2));
@@ -2196,13 +2211,19 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
 // for rau_backward and rau_graph_step, which take it as it is: check_hop_w); a term without a non-zero entry
 // becomes null; a non-zero att_w needs the batch's targets; the scratch of every term left exists on return.
 static int step_loss(rau_ctx* ctx, const char* fn, bool check_hop_w, const float* hop_w, const float* select_w,
-                     const float* att_w, const float* merge_w, StepLoss* loss, const rau_out_grads* g = nullptr) {
+                     const float* att_w, const float* merge_w, StepLoss* loss, const rau_out_grads* g = nullptr,
+                     const rau_state_grads* sg = nullptr) {
   NEED(ctx && hop_w, "null argument");
   // the external record: all-null is absent (the caller's call then IS the one without it)
   rau_out_grads ext{nullptr, nullptr, nullptr};
   if (g) ext = *g;
   const bool has_ext = ext.d_logits || ext.d_dopred || ext.d_attprob;
   NEED((reinterpret_cast<uintptr_t>(ext.d_logits) & 15u) == 0, "%s: d_logits must be 16-byte aligned", fn);
+  rau_state_grads sgr{nullptr, nullptr};
+  if (sg) sgr = *sg;
+  NEED(((reinterpret_cast<uintptr_t>(sgr.d_h) | reinterpret_cast<uintptr_t>(sgr.d_c_last)) & 15u) == 0,
+       "%s: d_h and d_c_last must be 16-byte aligned", fn);
+  const bool has_sg = sgr.d_h || sgr.d_c_last;
   if (merge_w) {
     NEED(std::isfinite(merge_w[0]) && std::isfinite(merge_w[1]), "%s: merge_w is not finite", fn);
     if (merge_w[0] == 0.f && merge_w[1] == 0.f) merge_w = nullptr;
@@ -2239,7 +2260,7 @@ static int step_loss(rau_ctx* ctx, const char* fn, bool check_hop_w, const float
     if (int rc = dalloc(ctx, &ctx->sel_add, (size_t)H * ctx->cap * ctx->cfg.M)) return rc;
   }
   *loss = StepLoss{hop_w, any ? select_w : nullptr, any_att ? att_w : nullptr, merge_w,
-                   (merge_w || has_ext) ? H : active, ext, hop_any};
+                   (merge_w || has_ext || has_sg) ? H : active, ext, hop_any, sgr};
   return RAU_OK;
 }
 
@@ -2277,6 +2298,29 @@ int rau_backward_ext(rau_ctx* ctx, const float* hop_w, const float* select_w, co
                          hop_w ? hop_w : zeros.data(), select_w, att_w, merge_w, &loss, g))
     return rc;
   return backward_impl(ctx, loss);   // (the staging copy of hop_w is taken before it returns)
+}
+// The same with caller-supplied gradients at the hop states (StepLoss::sg): d_h joins every hop's cell backward as its
+// dh_next, d_c_last opens the recurrence.  sg null or all-null: rau_backward_ext, launch for launch.
+int rau_backward_state(rau_ctx* ctx, const float* hop_w, const float* select_w, const float* att_w,
+                       const float* merge_w, const rau_out_grads* g, const rau_state_grads* sg) {
+  NEED(ctx, "null ctx");
+  if (!sg || !(sg->d_h || sg->d_c_last)) return rau_backward_ext(ctx, hop_w, select_w, att_w, merge_w, g);
+  const std::vector<float> zeros((size_t)ctx->cfg.H, 0.f);
+  StepLoss loss;
+  if (int rc = step_loss(ctx, "rau_backward_state", true, hop_w ? hop_w : zeros.data(), select_w, att_w, merge_w,
+                         &loss, g, sg))
+    return rc;
+  return backward_impl(ctx, loss);   // (the staging copy of hop_w is taken before it returns)
+}
+// Device pointers to c' / h' of every hop of the last step-level forward: rows [H][n][R] behind the initial-state rows
+int rau_state_dev(rau_ctx* ctx, const float** c, const float** h) {
+  NEED(ctx, "null ctx");
+  if (!ctx->mg.valid)
+    return fail(RAU_ERR_STATE, "rau_state_dev: no step-level forward to read (call rau_forward first)");
+  const size_t BR_ = (size_t)ctx->cfg.B * ctx->cfg.R;
+  if (c) *c = ctx->cc + BR_;
+  if (h) *h = ctx->hh + BR_;
+  return RAU_OK;
 }
 // Device pointers to the outputs of the last step-level forward, for a caller that computes its own gradients on
 // the device.  Nothing is synchronised: the values are ordered on the ctx's stream.

@@ -913,21 +913,21 @@ class RAU:
         return (("", "_select", "_att", "_merged")[n],
                 [None if a is None else a.ctypes.data_as(C.c_void_p) for a in arrs[:n + 1]])
 
-    def _out_grad(self, out_grads, key, shape):
+    def _out_grad(self, out_grads, key, shape, what="out_grads"):
         """Device address of out_grads[key] (a contiguous float32 CUDA torch tensor of `shape`), None when absent."""
         t = out_grads.get(key)
         if t is None:
             return None
         import torch
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise ValueError(f"out_grads[{key!r}] must be a contiguous float32 CUDA torch tensor")
+            raise ValueError(f"{what}[{key!r}] must be a contiguous float32 CUDA torch tensor")
         if t.device.index != self.cfg.device_id:
-            raise ValueError(f"out_grads[{key!r}] is on {t.device}, the context on cuda:{self.cfg.device_id}")
+            raise ValueError(f"{what}[{key!r}] is on {t.device}, the context on cuda:{self.cfg.device_id}")
         if tuple(t.shape) != shape:
-            raise ValueError(f"out_grads[{key!r}] has shape {tuple(t.shape)}, expected {shape}")
+            raise ValueError(f"{what}[{key!r}] has shape {tuple(t.shape)}, expected {shape}")
         return t.data_ptr()
 
-    def backward(self, hop_w=None, select_w=None, att_w=None, merge_w=None, out_grads=None):
+    def backward(self, hop_w=None, select_w=None, att_w=None, merge_w=None, out_grads=None, state_grads=None):
         """select_w [H]: per-hop weight of the step-selection head's BCE gradient, the multiplier the
         reference fixes at 0 (SS:566); None is that zero (rau_backward).
         att_w [H]: per-hop weight of the attention supervision against the batch's targets (set_att_targets), where
@@ -937,7 +937,18 @@ class RAU:
         out_grads: a dict with any of "logits" [H,n,K], "dopred" [H,n], "attprob" [H,n,S] -- the gradients of a
         term of the caller's own at those outputs (output_tensors), contiguous float32 CUDA torch tensors that the
         ctx's stream may read (order it behind the stream that wrote them).  The call then goes through
-        rau_backward_ext, where hop_w may be None (zeros); without out_grads it is exactly what it was."""
+        rau_backward_ext, where hop_w may be None (zeros); without out_grads it is exactly what it was.
+        state_grads: a dict with any of "h" [H,n,R] (the gradient at h' of every hop, state_tensors()) and "c_last"
+        [n,R] (at c' of the last hop), tensors like those of out_grads.  The call then goes through
+        rau_backward_state; hop_w may be None again."""
+        if state_grads is not None:
+            unknown = set(state_grads) - {"h", "c_last"}
+            if unknown:
+                raise ValueError(f"state_grads has unknown keys {sorted(unknown)}")
+            if state_grads.get("h") is None and state_grads.get("c_last") is None:
+                state_grads = None
+        if state_grads is not None and out_grads is None:
+            out_grads = {}
         if out_grads is None:
             if hop_w is None:
                 raise ValueError("hop_w is required without out_grads")
@@ -956,7 +967,13 @@ class RAU:
                 None if att_w is None else self._hop_array(att_w, "att_w"),
                 None if merge_w is None else self._merge_array(merge_w)]
         ws = [None if a is None else a.ctypes.data_as(C.c_void_p) for a in arrs]
-        L.check(self._lib.rau_backward_ext(self._h, *ws, C.byref(g)))
+        if state_grads is None:
+            L.check(self._lib.rau_backward_ext(self._h, *ws, C.byref(g)))
+            return
+        R = self.cfg.R
+        sg = L.RauStateGrads(self._out_grad(state_grads, "h", (H, n, R), "state_grads"),
+                             self._out_grad(state_grads, "c_last", (n, R), "state_grads"))
+        L.check(self._lib.rau_backward_state(self._h, *ws, C.byref(g), C.byref(sg)))
 
     def output_tensors(self):
         """Zero-copy torch views of the last step-level forward's outputs in device memory (rau_outputs_dev):
@@ -1147,8 +1164,73 @@ class RAU:
         n, Q = self._n, self.cfg.Q
         return device_view(p.value, n * Q, self.cfg.device_id).view(n, Q)
 
+    # ---- the hop recurrence's ends (rau_set_state_dev, rau_backward_state): initial state in, state gradients out
+    def set_state(self, c0, h0):
+        """Attach the initial state (c0, h0), each [n,R], of the hop chain to the resident batch: contiguous CUDA torch
+        tensors of one dtype, float32, float16 or bfloat16, on the ctx's device (16-bit values are widened exactly).
+        One launch on the ctx's stream, no host synchronisation: set_question's ordering rule.  While it is attached
+        forward / graph_step start hop 0 from it, and every backward leaves state_grad() behind.  The next
+        set_batch* / use_batch / set_batch_size detaches it; attaching again replaces the contents."""
+        import torch
+        types = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
+        for name, t in (("c0", c0), ("h0", h0)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in types and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float32, float16 or bfloat16 CUDA torch tensor")
+            if t.device.index != self.cfg.device_id:
+                raise ValueError(f"{name} is on {t.device}, the context on cuda:{self.cfg.device_id}")
+            if tuple(t.shape) != (self._n, self.cfg.R):
+                raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {(self._n, self.cfg.R)}")
+        if c0.dtype != h0.dtype:
+            raise ValueError("c0 and h0 must have the same dtype")
+        L.check(self._lib.rau_set_state_dev(self._h, c0.data_ptr(), h0.data_ptr(), feat16.FEAT_TYPES[types[c0.dtype]]))
+
+    def clear_state(self):
+        """Detach the initial state: the next forward starts from zeros."""
+        L.check(self._lib.rau_set_state_dev(self._h, None, None, 0))
+
+    def carry_state(self):
+        """Attach the last forward's final state (c', h' of hop H-1) as the next forward's initial state: one launch,
+        the values never leave the device."""
+        c, h = C.c_void_p(), C.c_void_p()
+        L.check(self._lib.rau_state_dev(self._h, C.byref(c), C.byref(h)))
+        off = (self.cfg.H - 1) * self._n * self.cfg.R * 4
+        L.check(self._lib.rau_set_state_dev(self._h, c.value + off, h.value + off, feat16.FEAT_TYPES["f32"]))
+
+    @property
+    def batch_state(self) -> bool:
+        """The resident batch has an initial state attached (rau_batch_state)."""
+        has = C.c_int(0)
+        L.check(self._lib.rau_batch_state(self._h, C.byref(has)))
+        return bool(has.value)
+
+    def state_tensors(self):
+        """Zero-copy torch views (c, h), each [H,n,R], of the hop states the last step-level forward left in device
+        memory (rau_state_dev); row H-1 is the final state.  Valid until the next forward or set_batch_size, ordered
+        on the ctx's stream (stream()), read-only."""
+        from .dist import device_view
+        c, h = C.c_void_p(), C.c_void_p()
+        L.check(self._lib.rau_state_dev(self._h, C.byref(c), C.byref(h)))
+        H, n, R, dev = self.cfg.H, self._n, self.cfg.R, self.cfg.device_id
+        return (device_view(c.value, H * n * R, dev).view(H, n, R), device_view(h.value, H * n * R, dev).view(H, n, R))
+
+    def state_grad(self):
+        """The last backward's gradient (d_c0, d_h0), each [n,R], at the attached initial state (numpy; synchronises)."""
+        dc = np.empty((self._n, self.cfg.R), np.float32)
+        dh = np.empty((self._n, self.cfg.R), np.float32)
+        L.check(self._lib.rau_get_state_grad(self._h, dc.ctypes.data, dh.ctypes.data))
+        return dc, dh
+
+    def state_grad_tensors(self):
+        """Zero-copy torch views (d_c0, d_h0), each [n,R], of that gradient in device memory (rau_state_grad_dev).
+        Valid until the next forward or set_batch_size, ordered on the ctx's stream (stream()), read-only."""
+        from .dist import device_view
+        dc, dh = C.c_void_p(), C.c_void_p()
+        L.check(self._lib.rau_state_grad_dev(self._h, C.byref(dc), C.byref(dh)))
+        n, R, dev = self._n, self.cfg.R, self.cfg.device_id
+        return device_view(dc.value, n * R, dev).view(n, R), device_view(dh.value, n * R, dev).view(n, R)
+
     def set_batch_dev(self, feats_cuda, tokens, lens, labels=None, answers=None, regions=None, att_targets=None,
-                      image_of=None, question=None, sample_w=None, candidates=None):
+                      image_of=None, question=None, sample_w=None, candidates=None, state=None):
         """set_batch with the maps already on the device: feats_cuda a contiguous float32 CUDA torch tensor
         [n,D,S] on the ctx's device (rau_set_batch_dev: one copy on the ctx's stream, no host synchronisation).
         The ctx's stream must be ordered behind the stream that wrote the tensor (autograd.step's docstring shows
@@ -1157,7 +1239,8 @@ class RAU:
         regions may then be per image [N].  question: a CUDA tensor [n,Q] attached behind the upload (set_question);
         tokens / lens may then be None -- the step does not read them, and id 1 with length 1 is uploaded.
         sample_w [n]: set_sample_weights behind the upload.
-        candidates [n, C]: set_candidates behind the upload."""
+        candidates [n, C]: set_candidates behind the upload.
+        state: (c0, h0), CUDA tensors [n,R] attached behind the upload (set_state)."""
         import torch
         c = self.cfg
         if question is not None and (tokens is None or lens is None):
@@ -1214,6 +1297,8 @@ class RAU:
             self.set_candidates(candidates)
         if question is not None:
             self.set_question(question)
+        if state is not None:
+            self.set_state(*state)
 
     def graph_step(self, hop_w, zero_grads=True, select_w=None, att_w=None, merge_w=None):
         """zero_grads + forward + backward as one hipGraph launch (captured on first use); select_w, att_w and
