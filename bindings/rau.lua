@@ -258,6 +258,18 @@ int rau_ema_swap(rau_ctx* ctx);
 int rau_ema_state(rau_ctx* ctx, int* has, int* swapped);
 int rau_get_ema(rau_ctx* ctx, int group, float* host, size_t n);
 int rau_set_ema(rau_ctx* ctx, int group, const float* host, size_t n);
+typedef struct rau_layer_stat {
+  float sumsq[3];
+  float absmax[3];
+  int64_t nonfinite[3];
+  int64_t n;
+} rau_layer_stat;
+int rau_layer_stats_count(const rau_ctx* ctx);
+int rau_layer_stats(rau_ctx* ctx, int what, float eps, rau_layer_stat* out);
+int rau_layer_stats_dev(rau_ctx* ctx, int what, float eps, const rau_layer_stat** dev);
+int rau_set_update_guard(rau_ctx* ctx, int mode);
+int rau_update_guard(rau_ctx* ctx, int* mode, int64_t* skipped, int32_t* last_skipped,
+                     int64_t last_nonfinite[3]);
 int rau_stream(rau_ctx* ctx, void** hip_stream);
 int rau_wait_grads(rau_ctx* ctx, int group, void* hip_stream);
 int rau_comm_unique_id(void* id, size_t bytes);
@@ -923,6 +935,37 @@ function RAU:emaSwap()
   local sw = ffi.new('int[1]')
   check(C.rau_ema_state(self.h, nil, sw))
   return sw[0] == 1
+end
+
+-- per-layer statistics, computed on the device (rau_layer_stats): what = a sum of 1 (gradients), 2 (weights) and
+-- 4 (the rule's direction m / (sqrt(v) + eps) or adamax's m / u; needs an update to have run), eps = the rule's.
+-- Returns a 1-based table with one record per layout entry, embed then rnn then mult: { n =, sumsq = {g, p, d},
+-- absmax = {g, p, d}, nonfinite = {g, p, d} } over the FINITE elements; what was not asked for is 0.  Synchronises.
+function RAU:layerStats(what, eps)
+  local n = C.rau_layer_stats_count(self.h)
+  local rec = ffi.new('rau_layer_stat[?]', n)
+  check(C.rau_layer_stats(self.h, what or 1, eps or 1e-8, rec))
+  local out = {}
+  for i = 1, n do
+    local r = rec[i - 1]
+    out[i] = { n = tonumber(r.n), sumsq = { r.sumsq[0], r.sumsq[1], r.sumsq[2] },
+               absmax = { r.absmax[0], r.absmax[1], r.absmax[2] },
+               nonfinite = { tonumber(r.nonfinite[0]), tonumber(r.nonfinite[1]), tonumber(r.nonfinite[2]) } }
+  end
+  return out
+end
+-- the non-finite guard: mode 1 makes rau:update / updateWith / updateEx count the non-finite gradient elements first
+-- (one more read of the gradients and a stream synchronisation) and SKIP a poisoned step -- nothing changes, the
+-- norms come back NaN; mode 0 (the default) switches it off.  A NaN in accumulated gradients stays until
+-- rau:zeroGradParameters().
+function RAU:setUpdateGuard(mode) check(C.rau_set_update_guard(self.h, mode or 1)) end
+-- -> mode, updates skipped so far, whether the last update was skipped, and the non-finite counts that last skipped
+-- update found per group { embed, rnn, mult }
+function RAU:updateGuard()
+  local mode, skipped, last = ffi.new('int[1]'), ffi.new('int64_t[1]'), ffi.new('int32_t[1]')
+  local nf = ffi.new('int64_t[3]')
+  check(C.rau_update_guard(self.h, mode, skipped, last, nf))
+  return mode[0], tonumber(skipped[0]), last[0] == 1, { tonumber(nf[0]), tonumber(nf[1]), tonumber(nf[2]) }
 end
 
 -- optimizer state of one group: m, v (FloatTensors of the group's length, filled; v holds the u of adamax),

@@ -1443,6 +1443,63 @@ int rau_ema_state(rau_ctx* ctx, int* has, int* swapped);
 int rau_get_ema(rau_ctx* ctx, int group, float* host, size_t n);
 int rau_set_ema(rau_ctx* ctx, int group, const float* host, size_t n);
 
+/* ---- per-layer statistics of the flat vectors, and a non-finite guard in front of the update ------
+ * rau_layer_stats reads the flat buffers on the device and returns one record per layout entry, in rau_layout_entry's
+ * order group by group: EMBED, then RNN, then MULT (rau_layer_stats_count records: 35 today).  `what` is a sum of
+ *   RAU_STAT_GRAD   the gradient buffers as they stand
+ *   RAU_STAT_PARAM  the weight buffers as they stand (while rau_ema_swap is in force: the average)
+ *   RAU_STAT_DIR    the rule's direction from the moments as they stand: m / (sqrtf(v) + eps) for a group whose state
+ *                   RAU_OPT_ADAM owns, m / u for RAU_OPT_ADAMAX, with update.hip's divisions and sqrtf and the
+ *                   caller's eps.  ||dx|| of a unit is its step size, formed on the host as rau_update_ex forms it,
+ *                   times sqrtf(sumsq[2]).  A group with t == 0 has no moments: RAU_ERR_STATE.
+ * and the fields [0], [1], [2] of a record belong to them in that order; a source that is not requested leaves its
+ * three fields at 0, and eps is not read without RAU_STAT_DIR.  Frozen layers are reported like any other: this is a
+ * readout, not part of the update.
+ * The readout is finite-only: sumsq and absmax are taken over the finite elements and nonfinite counts the NaN and
+ * +-Inf ones, so three NaNs in a large embedding do not hide the norm of the rest.  sumsq is an f32 sum and may itself
+ * overflow to +Inf for finite elements above about 1e19, as torch.norm does in f32; absmax stays exact.  The sum has a
+ * fixed order (layer_stats.hip states it and the length L(n) of its longest chain of additions): no atomics, the same
+ * bits on every call, and a source's bits do not depend on which other sources were requested.  Against an exact sum
+ * the relative error of sumsq is at most (L(n) + 2) * 2^-24.
+ * Two launches on the context's stream, layer_stats_part and layer_stats_finish in rau_prof_entry; the work table is
+ * built at the first call and freed by rau_destroy.  rau_layer_stats synchronises; rau_layer_stats_dev does not and
+ * hands out the device array [count], ordered on the context's stream and valid until the next call of either.
+ * what == 0 or with unknown bits, eps negative or non-finite (also where it is not read): RAU_ERR_INVALID.  In every error
+ * case nothing is launched.
+ *
+ * The guard.  With RAU_GUARD_SKIP, rau_noise_clip_adam, rau_update and rau_update_ex first count the non-finite
+ * elements of the three gradient buffers (the gradients only; rau_update_ex leaves frozen layers out, which are not
+ * part of the model being updated): after argument validation and before anything else is launched, with the
+ * count-only form of the same two launches.  The three per-group totals are downloaded, 24 bytes, WHICH SYNCHRONISES
+ * THE STREAM in every guarded update.  All zero: the call proceeds exactly as without the guard, the same launches and
+ * the same bits.  Otherwise nothing of the update is launched: weights, gradients, moments, the average, t and the
+ * owning rule of all three groups keep their bits, out_norms (when given) receives NaN in every entry the call would
+ * have written, the call returns RAU_OK, `skipped` grows by one, last_skipped = 1 and last_nonfinite holds the
+ * totals.  An update that ran sets last_skipped = 0.  The next clean or unguarded update is bit for bit what it would
+ * have been had the skipped call never been made.
+ * Callers that accumulate gradients over several backward calls: a NaN stays in the buffer until rau_zero_grads, and
+ * every guarded update is skipped until then.  With a communicator the verdict is taken on the reduced gradients, so
+ * every rank decides alike (a NaN survives the average).  The mode survives rau_set_batch_size; `skipped` is neither
+ * part of the optimizer state nor of snapshots.  An unknown mode: RAU_ERR_INVALID.  The guard is not offered inside
+ * rau_graph_step*, which do not update. */
+#define RAU_STAT_GRAD 1
+#define RAU_STAT_PARAM 2
+#define RAU_STAT_DIR 4
+typedef struct rau_layer_stat {
+  float sumsq[3];        /* [grad, param, dir]: sum of squares of the FINITE elements */
+  float absmax[3];       /* largest |.| of the finite elements; +0 when there is none */
+  int64_t nonfinite[3];  /* NaN and +-Inf elements */
+  int64_t n;             /* elements of the entry */
+} rau_layer_stat;
+int rau_layer_stats_count(const rau_ctx* ctx);
+int rau_layer_stats(rau_ctx* ctx, int what, float eps, rau_layer_stat* out /* host [count] */);
+int rau_layer_stats_dev(rau_ctx* ctx, int what, float eps, const rau_layer_stat** dev /* device [count] */);
+#define RAU_GUARD_OFF 0    /* default */
+#define RAU_GUARD_SKIP 1
+int rau_set_update_guard(rau_ctx* ctx, int mode);
+int rau_update_guard(rau_ctx* ctx, int* mode, int64_t* skipped, int32_t* last_skipped,
+                     int64_t last_nonfinite[3] /* per group; any output may be NULL */);
+
 /* ---- data-parallel exchange (new: the reference is single-GPU) --------------------
  * One process and one rau_ctx per GPU.  Rank 0 obtains a communicator id and hands it to
  * the other ranks by any host channel (file, socket, MPI, torch.distributed); every rank

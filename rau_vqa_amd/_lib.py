@@ -54,6 +54,16 @@ class RauUpdateExtras(C.Structure):
     _fields_ = [("weight_decay", C.c_float), ("ema_decay", C.c_float)]
 
 
+STAT_GRAD, STAT_PARAM, STAT_DIR = 1, 2, 4
+GUARD_OFF, GUARD_SKIP = 0, 1
+
+
+class RauLayerStat(C.Structure):
+    """Mirror of ``rau_layer_stat`` (include/rau.h): one layout entry's statistics, [grad, param, dir]."""
+    _fields_ = [("sumsq", C.c_float * 3), ("absmax", C.c_float * 3), ("nonfinite", C.c_int64 * 3),
+                ("n", C.c_int64)]
+
+
 class RauOutGrads(C.Structure):
     """Mirror of ``rau_out_grads`` (include/rau.h): device pointers, None = no such term."""
     _fields_ = [(n, C.c_void_p) for n in ("d_logits", "d_dopred", "d_attprob")]
@@ -307,6 +317,13 @@ _SIGS = {
     "rau_ema_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rau_get_ema": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "rau_set_ema": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    # per-layer statistics on the device; the non-finite guard in front of the update
+    "rau_layer_stats_count": (C.c_int, [C.c_void_p]),
+    "rau_layer_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.POINTER(RauLayerStat)]),
+    "rau_layer_stats_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_void_p)]),
+    "rau_set_update_guard": (C.c_int, [C.c_void_p, C.c_int]),
+    "rau_update_guard": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int64)]),
     "rau_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_wait_grads": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "rau_comm_unique_id": (C.c_int, [C.c_void_p, C.c_size_t]),

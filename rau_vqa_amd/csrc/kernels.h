@@ -670,6 +670,40 @@ hipError_t ema_swap(hipStream_t st, float* const x[3], float* const e[3], const 
 // Adamax on one flat vector (rau_dev_adamax): adamax_elem on dx as it stands; any n, any 4-byte-aligned pointers
 hipError_t adamax_vec(hipStream_t st, size_t n, float* x, const float* dx, float* m, float* u, float stepsize,
                       float beta1, float beta2, float eps);
+// Per-layer statistics of the flat vectors and the update guard's count (layer_stats.hip, rau_layer_stats).  Every
+// layout entry is tiled by ITEMS of at most kStatChunk elements that start at the entry's start plus a multiple of
+// kStatChunk, so no item crosses an entry; the table is built once per context and lives in device memory.
+// layer_stats_part: one 256-thread workgroup per item reads the requested sources of its elements (16-byte loads
+// over the aligned middle, scalar loads for a head and a tail of at most 3) and leaves one partial record;
+// layer_stats_finish adds an entry's partials in ascending item order from +0 into rau_layer_stat records, and the
+// items' non-finite counts per group and source into totals [3 sources][3 groups].  The order and its chain length
+// L(n) are stated in layer_stats.hip's header.
+constexpr int kStatChunk = 8192;
+constexpr int kStatMaxEntries = 64;   // StatSrc::skip is one bit per entry (35 today)
+constexpr int kStatPartWords = 12;    // a partial record: sumsq[3] | absmax[3] | nonfinite[3] | pad[3], 32-bit words
+struct StatItem {     // 16 bytes
+  uint64_t start;     // first element, in its group's flat vector
+  uint32_t len;       // 1 .. kStatChunk
+  uint16_t group, entry;   // entry: index over the three groups' layouts, EMBED | RNN | MULT
+};
+struct StatEntry {    // 16 bytes
+  uint32_t first, items;   // its items are first .. first + items - 1
+  uint64_t n;              // elements
+};
+struct StatSrc {
+  const float *g[3], *x[3], *m[3], *v[3];   // per group; a source that is not requested is not read
+  int rule[3];        // rau_opt_rule of the group's moments (RAU_STAT_DIR)
+  float eps;
+  uint64_t skip;      // bit e: entry e's items read nothing and leave zeros (the guard under rau_update_ex: frozen)
+};
+// what: RAU_STAT_* bits; count_only: the non-finite counts alone (sumsq and absmax stay +0)
+hipError_t layer_stats_part(hipStream_t st, const StatSrc& S, int what, bool count_only, const StatItem* items,
+                            int n_items, uint32_t* partial /* [n_items][kStatPartWords] */);
+// out == null: the totals alone (the guard)
+hipError_t layer_stats_finish(hipStream_t st, const StatEntry* entries, int n_entries, const int group_first[4],
+                              const uint32_t* partial, rau_layer_stat* out /* [n_entries] or null */,
+                              int64_t* totals /* [3][3] */);
+
 // feval's statistics of the resident hop outputs (hop_merge.hip, SS:476-556): per-sample rows
 // rowf [B][H+2], rowi [B][4H+3], then one fixed-order batch reduction into
 // out = loss[H+2] | loss_do_pred[H] | int32 counts[4H+3]

@@ -501,6 +501,20 @@ struct rau_ctx {
   float *npart = nullptr, *norms_d = nullptr;
   float* upd_part = nullptr;     // rau_update's partial sums of squares, [3][kUpdParts]
   bool ema_swapped = false;      // rau_ema_swap: the weights' buffers hold the average and the other way round
+  // per-layer statistics and the update guard (layer_stats.hip); everything here comes with the first use
+  struct LayerStats {
+    StatItem* items = nullptr;          // device: the work table, fixed for the context's life
+    StatEntry* entries = nullptr;       // device [n_entries]
+    uint32_t* partial = nullptr;        // device [n_items][kStatPartWords]
+    rau_layer_stat* out = nullptr;      // device [n_entries]: what rau_layer_stats_dev hands out
+    int64_t* totals = nullptr;          // device [3 sources][3 groups] non-finite counts of the last pass
+    int n_items = 0, n_entries = 0;
+    int group_first[4] = {0, 0, 0, 0};  // group g's items are group_first[g] .. group_first[g + 1] - 1
+  } ls;
+  int guard_mode = RAU_GUARD_OFF;       // rau_set_update_guard; survives rau_set_batch_size
+  int64_t guard_skipped = 0;
+  int32_t guard_last_skipped = 0;
+  int64_t guard_last_nonfinite[3] = {0, 0, 0};
   FwdRecord fwd;                 // what the last step-level forward left for its backward
   BwdRecord bwd;                 // what the last step-level backward left for the getters
   // timing
@@ -834,5 +848,10 @@ __attribute__((visibility("hidden"))) int persist_check(rau_ctx* ctx);
 __attribute__((visibility("hidden"))) int d2h(rau_ctx* ctx, void* host, const void* dev, size_t bytes);
 }
 __attribute__((visibility("hidden"))) int merge_state(rau_ctx* ctx, const char* fn, bool need_labels);  // rau_merge.hip
+// layer_stats.hip: the guard in front of an update (rau_set_update_guard), called after argument validation and before
+// anything else is launched.  0: the update proceeds (guard off, or no non-finite gradient element; `ex`: frozen
+// layers are not looked at).  1: it is skipped -- the first n_norms entries of out_norms (may be null) hold NaN and the
+// caller returns RAU_OK with nothing launched.  < 0: an error code.
+__attribute__((visibility("hidden"))) int update_guard(rau_ctx* ctx, bool ex, float* out_norms, int n_norms);
 // rau_merge.hip: the statistics' scratch exists; ATT rows / results of `hops` hops of a [hops][B] attention block
 __attribute__((visibility("hidden"))) int att_stats_alloc(rau_ctx* ctx);

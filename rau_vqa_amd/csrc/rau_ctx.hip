@@ -2533,6 +2533,7 @@ int rau_noise_clip_adam(rau_ctx* ctx, int64_t step_t, float lr, float mult_lr, f
     if (ctx->grp[gi].adam_t > 0 && ctx->grp[gi].opt_rule != RAU_OPT_ADAM)
       return fail(RAU_ERR_STATE, "rau_noise_clip_adam: group %d holds Adamax state (t = %lld); reset it with "
                   "rau_set_opt_state first", gi, (long long)ctx->grp[gi].adam_t);
+  if (int rc = update_guard(ctx, false, out_norms, 3)) return rc < 0 ? rc : RAU_OK;   // rau_set_update_guard
   hipStream_t st = ctx->st;
   // SS:598-599: var = eta / ((step_t+1) * gamma)
   const float nstd = eta > 0.f ? std::sqrt(eta / ((float)(step_t + 1) * gamma)) : 0.f;

@@ -484,6 +484,7 @@ void rau_update_opts_default(rau_update_opts* o) {
 
 int rau_update(rau_ctx* ctx, int64_t step_t, const rau_update_opts* o, float* out_norms) {
   if (int rc = update_args(ctx, step_t, o)) return rc;
+  if (int rc = update_guard(ctx, false, out_norms, 4)) return rc < 0 ? rc : RAU_OK;   // rau_set_update_guard
   for (int gi = 0; gi < 3; ++gi)
     if (int rc = need_moments(ctx, ctx->grp[gi])) return rc;
   // SS:598-599: var = eta / ((step_t+1) * gamma)
@@ -539,6 +540,7 @@ int rau_update_ex(rau_ctx* ctx, int64_t step_t, const rau_update_opts* o, const 
     segs += (int)ctx->grp[gi].layout.size();
   }
   NEED(segs <= kUpdSegs, "rau_update_ex: too many segments");
+  if (int rc = update_guard(ctx, true, out_norms, 4)) return rc < 0 ? rc : RAU_OK;   // rau_set_update_guard
   for (int gi = 0; gi < 3; ++gi)
     if (int rc = need_moments(ctx, ctx->grp[gi])) return rc;
   const float nstd = o->eta > 0.f ? std::sqrt(o->eta / ((float)(step_t + 1) * o->gamma)) : 0.f;

@@ -124,7 +124,9 @@ def reduced_update(rau, allreduce, step_t, **update_args):
     included, so every rank computes the identical norms (the global one too: it is taken over the reduced
     gradients) and the identical step.  The keywords are forwarded as they are, weight_decay and ema_decay
     included; layer options (RAU.set_layer_opts, freeze) and the weight average live in each rank's context and are
-    not exchanged, so they must be set identically on every rank.  Returns RAU.update's norms."""
+    not exchanged, so they must be set identically on every rank.  With RAU.guard_updates() on (on every rank alike)
+    the guard's verdict is taken on the REDUCED gradients -- a NaN survives the average -- so every rank skips or
+    applies the same steps.  Returns RAU.update's norms."""
     if allreduce is not None:
         allreduce()
     return rau.update(step_t, **update_args)

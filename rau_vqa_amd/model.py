@@ -1317,7 +1317,8 @@ class RAU:
         clip_scope="global" (neither is in the reference) go through rau_update and return four norms: the groups'
         and the global one.  A non-zero weight_decay (decoupled, AdamW's order, under either rule) or ema_decay (the
         weight average: ema_reset first), or any layer option off its default (set_layer_opts, freeze), goes through
-        rau_update_ex and returns four norms as well; frozen layers are in none of them."""
+        rau_update_ex and returns four norms as well; frozen layers are in none of them.  With guard_updates() on, a
+        call that finds a non-finite gradient element is skipped and returns NaN norms (update_guard tells)."""
         if rule not in L.OPT_RULES:
             raise ValueError(f"update: rule {rule!r} is not one of {sorted(L.OPT_RULES)}")
         if clip_scope not in L.CLIP_SCOPES:
@@ -1338,6 +1339,104 @@ class RAU:
             return norms
         L.check(self._lib.rau_update(self._h, step_t, C.byref(o), norms.ctypes.data))
         return norms
+
+    # ---- per-layer statistics on the device (rau_layer_stats) and the non-finite guard (rau_set_update_guard)
+    def _stat_names(self):
+        """[(entry name, group)] in the records' order: rau_layout_entry's, EMBED then RNN then MULT."""
+        if getattr(self, "_stat_entries", None) is None:
+            self._stat_entries = [(e[0], g) for g in L.GROUPS for e in self.layout(g)]
+        return self._stat_entries
+
+    @staticmethod
+    def _stat_what(grads, params, direction):
+        what = (L.STAT_GRAD if grads else 0) | (L.STAT_PARAM if params else 0) | (L.STAT_DIR if direction else 0)
+        if not what:
+            raise ValueError("layer_stats: ask for at least one of grads, params, direction")
+        return what
+
+    def layer_stats(self, grads=True, params=False, direction=False, eps=1e-8):
+        """Statistics of every layout entry, computed on the device (two launches, one download of 35 records in
+        place of the flat vectors): a list of dicts in layout order with name, group, n and, per requested source
+        under "grad", "param", "dir", a dict of norm (sqrt of the f32 sum of squares of the FINITE elements, taken
+        in float64 here), sumsq, absmax (largest finite magnitude) and nonfinite (NaN and +-Inf elements).
+        direction: the rule's direction from the moments as they stand, m / (sqrt(v) + eps) or Adamax's m / u; it
+        needs an update to have run.  Frozen layers are reported like any other.  Synchronises."""
+        what = self._stat_what(grads, params, direction)
+        names = self._stat_names()
+        rec = (L.RauLayerStat * len(names))()
+        L.check(self._lib.rau_layer_stats(self._h, what, eps, rec))
+        out = []
+        for (name, g), r in zip(names, rec):
+            row = {"name": name, "group": g, "n": int(r.n)}
+            for k, (key, bit) in enumerate((("grad", L.STAT_GRAD), ("param", L.STAT_PARAM), ("dir", L.STAT_DIR))):
+                if what & bit:
+                    row[key] = {"norm": float(np.sqrt(np.float64(r.sumsq[k]))), "sumsq": np.float32(r.sumsq[k]),
+                                "absmax": np.float32(r.absmax[k]), "nonfinite": int(r.nonfinite[k])}
+            out.append(row)
+        return out
+
+    def layer_stats_tensor(self, grads=True, params=False, direction=False, eps=1e-8):
+        """The same records as zero-copy torch views of the device array (rau_layer_stats_dev), no synchronisation:
+        {"sumsq": [count, 3] float32, "absmax": [count, 3] float32, "nonfinite": [count, 3] int64, "n": [count]
+        int64}, the columns being grad, param, dir (0 where not requested).  Ordered on the ctx's stream (stream()),
+        valid until the next layer_stats / layer_stats_tensor call, read-only."""
+        import torch
+        from .dist import device_view
+        what = self._stat_what(grads, params, direction)
+        dev = C.c_void_p()
+        L.check(self._lib.rau_layer_stats_dev(self._h, what, eps, C.byref(dev)))
+        count, words = len(self._stat_names()), C.sizeof(L.RauLayerStat) // 4
+        raw = device_view(dev.value, count * words, self.cfg.device_id).view(count, words)
+        ints = raw[:, 6:].view(torch.int64)
+        return {"sumsq": raw[:, 0:3], "absmax": raw[:, 3:6], "nonfinite": ints[:, 0:3], "n": ints[:, 3]}
+
+    def update_ratios(self, lr=3e-3, mult_lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-8, rule="adam"):
+        """{layer name: step * ||dir|| / ||x||}: the size of the step the last update took in every unit (weight and
+        bias together) relative to its weights, from one layer_stats call.  The step size is formed as rau_update_ex
+        forms it, in double on the host, from the groups' update count t, the unit's lr_scale and the rule:
+        group_lr * lr_scale * sqrt(1 - beta2^t) / (1 - beta1^t) for "adam", group_lr * lr_scale / (1 - beta1^t) for
+        "adamax".  A unit whose weights are all zero gives inf; a frozen unit gives 0."""
+        if rule not in L.OPT_RULES:
+            raise ValueError(f"update_ratios: rule {rule!r} is not one of {sorted(L.OPT_RULES)}")
+        st = self.layer_stats(grads=False, params=True, direction=True, eps=eps)
+        sums = {}
+        for row in st:
+            base = row["name"].rsplit(".", 1)[0]
+            d, x = sums.get((base, row["group"]), (0.0, 0.0))
+            sums[(base, row["group"])] = (d + float(row["dir"]["sumsq"]), x + float(row["param"]["sumsq"]))
+        ts = {}
+        for g in L.GROUPS:
+            t = C.c_int64()
+            L.check(self._lib.rau_get_opt_state(self._h, L.GROUPS[g], None, None, C.byref(t), None))
+            ts[g] = int(t.value)
+        out = {}
+        for name, g, i in self.layers():
+            group_lr = mult_lr if g == "mult" else lr
+            bc1, bc2 = 1.0 - float(beta1) ** ts[g], 1.0 - float(beta2) ** ts[g]
+            scale = self._layer_get(g, i)[0]
+            step = group_lr * scale * np.sqrt(bc2) / bc1 if rule == "adam" else group_lr * scale / bc1
+            d, x = sums[(name, g)]
+            out[name] = float(np.float32(step) * np.sqrt(d) / np.sqrt(x)) if x > 0 else float("inf")
+        return out
+
+    def guard_updates(self, on=True):
+        """With the guard on, every update first counts the non-finite elements of the gradients on the device (one
+        more read of them and a stream synchronisation per update; frozen layers are left out where layer options
+        are in force).  A clean step runs exactly as without the guard.  A poisoned one is skipped: weights,
+        gradients, moments, the average and the update count keep their bits, update() returns NaN norms, and
+        update_guard counts it.  Gradients accumulated over several backward calls keep a NaN until zero_grads():
+        every update is skipped until then."""
+        L.check(self._lib.rau_set_update_guard(self._h, L.GUARD_SKIP if on else L.GUARD_OFF))
+
+    @property
+    def update_guard(self):
+        """{"mode": 0 | 1, "skipped": updates skipped so far, "last_skipped": whether the last update was,
+        "last_nonfinite": {group: non-finite gradient elements the last skipped update found}}."""
+        mode, skipped, last = C.c_int(), C.c_int64(), C.c_int32()
+        nf = (C.c_int64 * 3)()
+        L.check(self._lib.rau_update_guard(self._h, C.byref(mode), C.byref(skipped), C.byref(last), nf))
+        return {"mode": int(mode.value), "skipped": int(skipped.value), "last_skipped": bool(last.value),
+                "last_nonfinite": {g: int(nf[i]) for g, i in L.GROUPS.items()}}
 
     # ---- per-layer options (rau_set_layer_opts): a layer is a named unit, weight and bias, of the layout
     def layers(self):
