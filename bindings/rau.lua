@@ -146,6 +146,10 @@ int rau_backward_state(rau_ctx* ctx, const float* hop_w, const float* select_w, 
                        const float* merge_w, const rau_out_grads* g, const rau_state_grads* sg);
 int rau_state_grad_dev(rau_ctx* ctx, const float** d_c0, const float** d_h0);
 int rau_get_state_grad(rau_ctx* ctx, float* d_c0_host, float* d_h0_host);
+int rau_set_att_bias_dev(rau_ctx* ctx, const void* bias_dev, int type);
+int rau_batch_att_bias(rau_ctx* ctx, int* has);
+int rau_att_bias_grad_dev(rau_ctx* ctx, const float** d_bias, int32_t* pitch);
+int rau_get_att_bias_grad(rau_ctx* ctx, float* host);
 int rau_embed_forward(rau_ctx* ctx, int t, const int32_t* tokens_dev, float** we);
 int rau_embed_backward(rau_ctx* ctx, int t, const int32_t* tokens_dev, const float* d_we);
 int rau_deeplstm_forward(rau_ctx* ctx, int t, const float* x, const float* state,
@@ -159,6 +163,10 @@ int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const fl
                                    const float* c_prev, const float* h_prev, const int32_t* regions_dev,
                                    float** logits, float** do_pred, float** attprob, float** c_out,
                                    float** h_out);
+int rau_multimodal_forward_bias(rau_ctx* ctx, int h, const float* q, const float* X,
+                                const float* c_prev, const float* h_prev, const int32_t* regions_dev,
+                                const float* bias_dev, float** logits, float** do_pred, float** attprob,
+                                float** c_out, float** h_out);
 int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
                             const float* c_prev, const float* h_prev, const float* d_logits,
                             const float* d_do_pred, const float* d_attprob,
@@ -858,6 +866,29 @@ function RAU:stateGrad()
   local dc, dh = ffi.new('const float*[1]'), ffi.new('const float*[1]')
   check(C.rau_state_grad_dev(self.h, dc, dh))
   return dc[0], dh[0]
+end
+
+-- Additive attention bias from the caller (rau_set_att_bias_dev): b a DEVICE pointer to dense [n,S] elements of btype
+-- 'f32' (default), 'f16' or 'bf16', ordered by the caller in front of the ctx's stream; -inf = no attention there.  It
+-- attaches to the resident batch: every hop of forward / graphStep adds it to the attention scores, every backward
+-- leaves attBiasGrad() behind.  nil detaches it, and so does the next setBatch* / useBatch / setBatchSize.
+function RAU:setAttBiasDev(b, btype)
+  local t = RAU.QUESTION_TYPES[btype or 'f32']
+  assert(t, 'setAttBiasDev: btype is one of f32, f16, bf16')
+  check(C.rau_set_att_bias_dev(self.h, b, t))
+  return self
+end
+function RAU:batchAttBias()
+  local has = ffi.new('int[1]')
+  check(C.rau_batch_att_bias(self.h, has))
+  return has[0] ~= 0
+end
+-- the last backward's gradient at the attached bias in device memory: const float* cdata [n,pitch] and the row pitch
+-- in floats (rau_att_bias_grad_dev); valid until the next forward, ordered on the ctx's stream
+function RAU:attBiasGrad()
+  local d, pitch = ffi.new('const float*[1]'), ffi.new('int32_t[1]')
+  check(C.rau_att_bias_grad_dev(self.h, d, pitch))
+  return d[0], tonumber(pitch[0])
 end
 
 -- zeroGradParameters (unless zero_grads == false) + forward + backward as one captured graph launch

@@ -1040,6 +1040,65 @@ int rau_backward_state(rau_ctx* ctx, const float* hop_w /* [H] host, NULL = zero
 int rau_state_grad_dev(rau_ctx* ctx, const float** d_c0 /* [n,R] f32 DEVICE */, const float** d_h0 /* [n,R] f32 DEVICE */);
 int rau_get_state_grad(rau_ctx* ctx, float* d_c0_host /* [n,R] dense */, float* d_h0_host /* [n,R] dense */);
 
+/* ---- attention bias from the caller: masks and priors in, its gradient out ---------------------------------------
+ * Every hop adds the memory term zm[b,s] = (h_prev Wz^T)[b,s] + bz[s] to the content score before the softmax
+ * (SS:287-289).  These calls add one more addend there, per SAMPLE and shared by all hops: an arbitrary mask (-inf),
+ * a prior (log detector confidences, a saliency map, the previous round's attention), or the output of a small module
+ * of the caller's that trains through the step -- for which every backward leaves the gradient at the bias.  No GEMM
+ * and no backward kernel is involved: the forward attention kernels take one pointer, the gradient is a sum of rows
+ * the backward keeps anyway.
+ *   layout       bias_dev is [n,S] dense in DEVICE memory, n the current batch size (rau_set_batch_size), S the logical
+ *                position count.  One bias per batch, read by every hop.  It is always per SAMPLE, also on a batch
+ *                with an image table or bank rows (as the region counts are).
+ *   type         RAU_FEAT_F32, RAU_FEAT_F16 or RAU_FEAT_BF16, widened exactly.  The fp8 types and unknown values:
+ *                RAU_ERR_INVALID.
+ *   values       finite values and -inf.  -inf means attention exactly 0 at that position, in every hop, in train and
+ *                evaluate mode, and gradient exactly 0 there.  +inf and NaN are the caller's error.  A sample whose
+ *                attended range (all S positions, or those below its region count) holds no finite bias is a softmax
+ *                over nothing: the device form cannot check this, and that sample's attention row is then NaN (and so
+ *                is everything computed from it).  Values at or behind a sample's region count are never read.
+ *   arithmetic   score[b,s] = e[b,s] + bs + (zm[b,s] + bias[b,s]): one f32 add behind the finished memory term
+ *                (its split-K partials and bz[s] summed as before).  Nothing else changes.  A bias of all +0 gives the
+ *                bits of a step without one; a bias of -inf at s >= n[b] and 0 before gives rau_set_regions(n)'s.
+ *   attaching    rau_set_att_bias_dev attaches the bias to the RESIDENT batch by rau_set_question_dev's rules: one
+ *                launch (att_bias_attach) on the ctx's stream copies or widens it into a ctx-owned f32 buffer at the
+ *                attention's row pitch.  No host wait, no synchronisation.  The caller orders its producer in front of
+ *                rau_stream and keeps bias_dev unchanged until the launch has run.  The attached bias survives any
+ *                number of forwards.  Attaching again replaces the contents: the per-step call of a training loop.  A
+ *                forward that ran before the call has no backward (run it again).
+ *   detaching    bias_dev == NULL detaches.  Every call that makes another batch current detaches too: rau_set_batch*
+ *                (every form, the asynchronous ones when they fill the current slot), rau_use_batch, and a
+ *                rau_set_batch_size that changes the size.  rau_batch_att_bias reports whether the resident batch has
+ *                one.
+ *   gradient     with a bias attached EVERY step-level backward (rau_backward, _select, _att, _merged, _ext, _state,
+ *                every rau_graph_step*) also leaves d_bias[b,s] = sum over the backward's active hops, ascending, of
+ *                dz_h[b,s], the softmax backward's result: one launch (att_bias_grad) behind the hop loop.  The per-row
+ *                terms -- select_w, att_w, merge_w, external gradients, sample weights, 1/n -- are inside dz already.
+ *                OVERWRITTEN by each backward, never accumulated; rau_zero_grads does not touch it; no atomics:
+ *                repeated calls give the same bits, a captured step the eager step's.  With no active hop it is exact
+ *                zeros.  rau_att_bias_grad_dev hands out the ctx-owned DEVICE pointer [n,pitch] and the row pitch in
+ *                floats (pitch >= S; columns [S, pitch) hold +0), ordered on the ctx's stream; it synchronises nothing;
+ *                valid until the next forward or rau_set_batch_size.  rau_get_att_bias_grad: the download, dense
+ *                [n,S]; synchronises.  Both are RAU_ERR_STATE when the last backward did not run on an attached bias,
+ *                or no backward has run since the last forward.
+ *   captured     "a bias is attached" joins rau_graph_step's key: a step captured without a bias is never replayed
+ *                for a batch with one, nor the reverse.  A replay reads the buffer's current contents, so attaching
+ *                a new bias each step needs no recapture.  rau_set_att_bias_dev while a step is being captured:
+ *                RAU_ERR_STATE.
+ *   errors       nothing launched and nothing changed: a null ctx; no resident batch (RAU_ERR_STATE); a bias_dev that
+ *                is not 16-byte aligned (RAU_ERR_INVALID); an fp8 or unknown type (RAU_ERR_INVALID).
+ *   module level rau_multimodal_forward_bias (below) is the one-hop forward with counts and a bias in device memory.
+ *                The gradient at the bias is not offered there.
+ *   not offered  a bias per hop; a bias in the asynchronous upload slots or in the loader's feed; the gradient at
+ *                module level; an external gradient AT the bias beyond what d_attprob of rau_backward_ext already
+ *                offers.
+ *   unchanged    a context that never attaches a bias allocates, launches and computes exactly what it did: no launch's
+ *                grid, block or LDS request changes for anyone. */
+int rau_set_att_bias_dev(rau_ctx* ctx, const void* bias_dev /* [n,S] DEVICE, dense; NULL = detach */, int type);
+int rau_batch_att_bias(rau_ctx* ctx, int* has);
+int rau_att_bias_grad_dev(rau_ctx* ctx, const float** d_bias /* [n,pitch] f32 DEVICE */, int32_t* pitch);
+int rau_get_att_bias_grad(rau_ctx* ctx, float* host /* [n,S] dense */);
+
 /* ---- module-level entry points: one call per nn.Module :forward / :backward -----
  * For hosts that keep feval's own loops (SS:443-596) and call the clones one by one.
  * t in [0,T) / h in [0,H) select the clone (the reference's embed_clones[t+1],
@@ -1092,6 +1151,15 @@ int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const fl
                                    const float* c_prev, const float* h_prev, const int32_t* regions_dev,
                                    float** logits, float** do_pred, float** attprob, float** c_out,
                                    float** h_out);
+/* The same with an additive attention bias (see rau_set_att_bias_dev) in DEVICE memory: bias_dev [B,S] f32 dense,
+ * 16-byte aligned, NULL = none, which IS rau_multimodal_forward_regions launch for launch (the resident batch's own
+ * bias is NOT applied here).  One launch re-pitches the rows into a ctx-owned buffer.  Values at or behind a sample's
+ * count are never read; -inf gives attention exactly 0.  rau_multimodal_backward needs no sibling again: it reads the
+ * saved attention.  The gradient at the bias is not offered at module level. */
+int rau_multimodal_forward_bias(rau_ctx* ctx, int h, const float* q, const float* X,
+                                const float* c_prev, const float* h_prev, const int32_t* regions_dev,
+                                const float* bias_dev, float** logits, float** do_pred, float** attprob,
+                                float** c_out, float** h_out);
 int rau_multimodal_backward(rau_ctx* ctx, int h, const float* q, const float* X,
                             const float* c_prev, const float* h_prev, const float* d_logits,
                             const float* d_do_pred, const float* d_attprob,

@@ -218,6 +218,11 @@ _SIGS = {
                                      C.POINTER(RauOutGrads), C.POINTER(RauStateGrads)]),
     "rau_state_grad_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "rau_get_state_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    # attention bias from the caller: masks and priors in, its gradient out
+    "rau_set_att_bias_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "rau_batch_att_bias": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rau_att_bias_grad_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
+    "rau_get_att_bias_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
     # module-level entry points: device pointers in, pointers to ctx-owned slots out
     "rau_embed_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "rau_embed_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -229,6 +234,8 @@ _SIGS = {
                                [C.POINTER(C.c_void_p)] * 5),
     "rau_multimodal_forward_regions": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 +
                                        [C.POINTER(C.c_void_p)] * 5),
+    "rau_multimodal_forward_bias": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                                    [C.POINTER(C.c_void_p)] * 5),
     "rau_multimodal_backward": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 9 +
                                 [C.POINTER(C.c_void_p)] * 4),
     "rau_criterion_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,

@@ -54,6 +54,15 @@ gradient at one segment's initial state to the previous segment's final state (t
     logits, dopred, attprob, h, c_last = autograd.step(rau, hop_w, state=(c0, h0), return_state=True)
     (my_loss(logits) + head(h[-1]).logsumexp(1).mean()).backward()   # c0.grad, h0.grad flow on
 
+``step(rau, ..., att_bias=b)`` opens the ATTENTION SCORE: b is the CUDA tensor [n,S] given to ``set_att_bias`` -- the
+output of a small module of the caller's (box geometry -> score, a saliency head) -- and receives the gradient at the
+bias, the sum of every active hop's softmax backward, in the same ``loss.backward()`` as the others::
+
+    b = prior(geometry).float()                              # [n,S], requires grad through prior's parameters
+    rau.set_batch_dev(x, tokens, lens, labels, att_bias=b)
+    logits, dopred, attprob = autograd.step(rau, hop_w, att_bias=b)
+    my_loss(logits).backward()                               # b.grad flows on into prior's parameters
+
 torch is plumbing here: the forward, the backward and the update are librau's kernels; torch evaluates the
 caller's loss and its gradient at the three outputs, on its own current stream.  The two streams are joined with
 events only (ExternalStream + wait_stream), never with a host synchronisation.
@@ -65,7 +74,7 @@ import torch
 
 class _Step(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, question, c0, h0, rau, hop_w, select_w, att_w, merge_w, return_state):
+    def forward(ctx, anchor, question, c0, h0, att_bias, rau, hop_w, select_w, att_w, merge_w, return_state):
         dev = torch.device("cuda", rau.cfg.device_id)
         rau.forward()
         own = torch.cuda.ExternalStream(rau.stream(), device=dev)
@@ -80,6 +89,7 @@ class _Step(torch.autograd.Function):
         ctx.has_feats = anchor.dim() == 3       # step(feats=x): x is the recorded input, not the scalar anchor
         ctx.q_dtype = None if question is None else question.dtype   # step(question=q): q is a recorded input too
         ctx.s_dtype = None if c0 is None else c0.dtype   # step(state=(c0, h0)): so are c0 and h0
+        ctx.b_dtype = None if att_bias is None else att_bias.dtype   # step(att_bias=b): and so is b
         ctx.set_materialize_grads(False)        # an unused output's gradient stays None instead of a zero tensor
         return outs
 
@@ -111,11 +121,16 @@ class _Step(torch.autograd.Function):
             torch.cuda.current_stream(ctx.dev).wait_stream(own)
             gc, gh = (t.to(ctx.s_dtype, copy=True) for t in rau.state_grad_tensors())   # [n,R] each
             own.wait_stream(torch.cuda.current_stream(ctx.dev))   # the next step overwrites the buffer: behind the clones
-        return (gx, gq, gc, gh) + (None,) * 6   # parameter gradients live in the ctx's flat buffers
+        gb = None
+        if ctx.b_dtype is not None:                  # the gradient at the attached attention bias
+            torch.cuda.current_stream(ctx.dev).wait_stream(own)
+            gb = rau.att_bias_grad_tensor().to(ctx.b_dtype, copy=True).contiguous()   # [n,S], dense, in b's own type
+            own.wait_stream(torch.cuda.current_stream(ctx.dev))   # the next step overwrites the buffer: behind the clone
+        return (gx, gq, gc, gh, gb) + (None,) * 6   # parameter gradients live in the ctx's flat buffers
 
 
 def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, *, state=None, return_state=False,
-         feats=None, question=None):
+         att_bias=None, feats=None, question=None):
     """forward of the resident batch -> (logits, dopred, attprob), differentiable at those three outputs.
 
     hop_w, select_w, att_w, merge_w: the built-in terms of RAU.backward, added to whatever loss the caller builds
@@ -132,6 +147,9 @@ def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, *, state=None
     state: (c0, h0), the CUDA tensors [n,R] attached to the resident batch (RAU.set_state, set_batch_dev(state=)): they
     become recorded inputs and receive the gradient at the initial state of the hop chain.
 
+    att_bias: the CUDA tensor [n,S] attached to the resident batch (RAU.set_att_bias, set_batch_dev(att_bias=)): it
+    becomes a recorded input and receives the gradient at the attention bias.
+
     return_state: also return h [H,n,R] (h' of every hop) and c_last [n,R] (c' of the last hop), differentiable like
     the three outputs; the default stays the 3-tuple."""
     c0 = h0 = None
@@ -145,6 +163,15 @@ def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, *, state=None
             raise ValueError("step(state=...) needs the state attached: call rau.set_state(c0, h0) first")
         if not (c0.requires_grad or h0.requires_grad):   # (tensors nobody differentiates are just the attached state)
             c0 = h0 = None
+    if att_bias is not None:
+        if not (isinstance(att_bias, torch.Tensor) and att_bias.is_cuda and
+                tuple(att_bias.shape) == (rau.batch_size, rau.cfg.S)):
+            raise ValueError(f"att_bias must be the CUDA tensor [n,S] = {(rau.batch_size, rau.cfg.S)} given to "
+                             f"set_att_bias")
+        if not rau.batch_att_bias:
+            raise ValueError("step(att_bias=...) needs the bias attached: call rau.set_att_bias(b) first")
+        if not att_bias.requires_grad:   # (a tensor nobody differentiates is just the attached bias)
+            att_bias = None
     x = None   # the recorded feature-map input, where there is one
     if question is not None:
         if not (isinstance(question, torch.Tensor) and question.is_cuda and
@@ -172,4 +199,4 @@ def step(rau, hop_w=None, select_w=None, att_w=None, merge_w=None, *, state=None
     if x is None:
         # a leaf that requires grad makes autograd record the node: the real leaves are the ctx's parameters
         x = torch.zeros((), device=torch.device("cuda", rau.cfg.device_id), requires_grad=True)
-    return _Step.apply(x, question, c0, h0, rau, hop_w, select_w, att_w, merge_w, bool(return_state))
+    return _Step.apply(x, question, c0, h0, att_bias, rau, hop_w, select_w, att_w, merge_w, bool(return_state))

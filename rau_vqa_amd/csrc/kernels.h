@@ -320,7 +320,12 @@ struct AttPartials { int u_ns = 0; const float* u_bias = nullptr; int z_ns = 0; 
                      const int32_t* img = nullptr;
                      // per-sample region counts (forward only): sample b attends to positions [0, min(SL, nreg[b]))
                      // and gives the others attention exactly 0; indexed by the sample, never by img; null = none
-                     const int32_t* nreg = nullptr; };
+                     const int32_t* nreg = nullptr;
+                     // per-sample additive attention bias (forward only, rau_set_att_bias_dev): rows [nB][S] at the
+                     // attention's pitch; the score of (b, s) takes zadd[b * S + s] behind the finished memory term, one
+                     // f32 add; -inf = no attention there; indexed by the sample, never by img; never read at or
+                     // behind the sample's region count; null = none
+                     const float* zadd = nullptr; };
 // Which form an attention launch takes: an argument of the four launchers and of their predicates, computed by the
 // caller from its context (att_mode, policy.h).
 struct AttMode {
@@ -596,6 +601,14 @@ hipError_t state_attach(hipStream_t st, size_t n_elems, const void* c0, const vo
                         float* hh);
 hipError_t state_grad_finish(hipStream_t st, size_t n_elems, const float* part, int ns, const float* dc_prev,
                              float* d_c0, float* d_h0);
+// The caller's attention bias (att_bias.hip, rau_set_att_bias_dev / rau_att_bias_grad_dev).  Each one launch, no atomics.
+// att_bias_attach: dst[r][s] = widen(src[r][s]) for r < rows, s < SL; src dense [rows][SL] of type RAU_FEAT_F32 | F16 |
+// BF16, dst rows of `pitch` floats (pitch >= SL, a multiple of 4), pad columns [SL, pitch) written +0.
+// att_bias_grad: out[r][s] = ((dz_0[r][s] + dz_1[r][s]) + ..) + dz_{hops-1}[r][s], hop h's rows at dz + h * hop_stride,
+// all rows of `pitch` floats; columns [SL, pitch) and every column with hops = 0 written +0.
+hipError_t att_bias_attach(hipStream_t st, int rows, int SL, int pitch, const void* src, int type, float* dst);
+hipError_t att_bias_grad(hipStream_t st, int hops, int rows, int SL, int pitch, const float* dz, size_t hop_stride,
+                         float* out);
 hipError_t scale_hops(hipStream_t st, int H, size_t per_hop, const float* w_dev, float* x);
 // x_i[h][0 .. p_i) *= w[h] for three hop-major tensors in one launch
 hipError_t scale_hops3(hipStream_t st, int H, const float* w_dev, size_t p0, float* x0, size_t p1, float* x1,

@@ -450,6 +450,7 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_fused(
     for (int s = tid; s < SL; s += NW * 64) {
       float v = ap.z_bias[s];
       for (int sp = 0; sp < ap.z_ns; ++sp) v += zm[((size_t)sp * gridDim.x + b) * SL + s];
+      if (ap.zadd && s < SN) v += ap.zadd[(size_t)b * S + s];   // the caller's bias, behind the finished memory term
       zs[s] = v;
     }
   }
@@ -494,7 +495,8 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_fused(
   for (int s = tid; s < S; s += (NW * 64)) {
     float z = -INFINITY;   // pad positions take no attention (and so no gradient)
     if (s < SN) {
-      const float zmv = ap.z_ns ? zs[s] : zm[(size_t)b * S + s];
+      float zmv = ap.z_ns ? zs[s] : zm[(size_t)b * S + s];
+      if (ap.zadd && !ap.z_ns) zmv += ap.zadd[(size_t)b * S + s];   // (with partials the bias is in zs already)
       z = block_sum_ordered<NW>(red, S, s) + bs[0] + zmv;
     }
     as[s] = z;
@@ -598,6 +600,7 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_dma(
     for (int s = tid; s < SL; s += NW * 64) {
       float v = ap.z_bias[s];
       for (int sp = 0; sp < ap.z_ns; ++sp) v += zm[((size_t)sp * gridDim.x + b) * SL + s];
+      if (ap.zadd && s < SN) v += ap.zadd[(size_t)b * S + s];   // the caller's bias, behind the finished memory term
       zs[s] = v;
     }
   }
@@ -656,7 +659,8 @@ __global__ __launch_bounds__(NW * 64) void k_att_fwd_dma(
   for (int s = tid; s < S; s += (NW * 64)) {
     float z = -INFINITY;   // pad positions take no attention (and so no gradient)
     if (s < SN) {
-      const float zmv = ap.z_ns ? zs[s] : zm[(size_t)b * S + s];
+      float zmv = ap.z_ns ? zs[s] : zm[(size_t)b * S + s];
+      if (ap.zadd && !ap.z_ns) zmv += ap.zadd[(size_t)b * S + s];   // (with partials the bias is in zs already)
       z = block_sum_ordered<NW>(red, S, s) + bs[0] + zmv;
     }
     as[s] = z;
@@ -1172,6 +1176,7 @@ __global__ __launch_bounds__(256) void k_att_ctx(
       } else {
         zmv = zm[(size_t)b * S + s];
       }
+      if (ap.zadd) zmv += ap.zadd[(size_t)b * S + s];   // the caller's bias, behind the finished memory term
       float e = part[(size_t)b * NC * S + s];
       for (int cc = 1; cc < NC; ++cc) e += part[((size_t)b * NC + cc) * S + s];
       z = e + bs[0] + zmv;

@@ -298,6 +298,7 @@ void hold(rau_ctx* ctx, int si, const Batch& b) {
   d.cand_C = 0;            // ... and multiple-choice candidates
   d.question = false;      // ... and the caller's question state
   d.state = false;         // ... and the caller's initial state (the next forward clears the rows itself)
+  d.att_bias = false;      // ... and the caller's attention bias
 }
 
 // rau_set_batch_images, or (b.bank_rows) the same batch with its table drawn from the bank
@@ -807,10 +808,12 @@ int rau_use_batch(rau_ctx* ctx, int slot) {
   }
   cur_batch(ctx).held.question = false;   // a question is the resident batch's (rau_set_question_dev): it goes with it
   cur_batch(ctx).held.state = false;      // ... and so is an initial state (rau_set_state_dev)
+  cur_batch(ctx).held.att_bias = false;   // ... and an attention bias (rau_set_att_bias_dev)
   ctx->cur_slot = slot;
   drop_forward(ctx);
   s.held.question = false;
   s.held.state = false;
+  s.held.att_bias = false;
   // the bulk and weight-gradient streams start each step behind an event of the chain stream,
   // so ordering the chain stream behind the upload orders all three
   HIPC(hipStreamWaitEvent(ctx->st, s.uploaded, 0));
@@ -1188,6 +1191,70 @@ int rau_get_question_grad(rau_ctx* ctx, float* host) {
   NEED(ctx && host, "null argument");
   if (int rc = question_grad_state(ctx, "rau_get_question_grad")) return rc;
   return d2h(ctx, host, ctx->dq, (size_t)ctx->cfg.B * ctx->Q * sizeof(float));
+}
+
+// The caller's additive attention bias for the resident batch: one launch on the chain stream that copies (f32) or
+// widens exactly (16-bit) the dense rows [n][S] into the slot's zb_ext at the attention's pitch, behind every launch
+// that reads the previous contents; nothing waits for the device.  The flag is the batch's (BatchDesc::att_bias): the
+// hop chain hands the buffer to its attention kernels, the backward ends with the gradient's launch, the graph key
+// carries it.  Everything is checked before anything moves.
+int rau_set_att_bias_dev(rau_ctx* ctx, const void* bias_dev, int type) {
+  NEED(ctx, "null ctx");
+  if (ctx->capturing) return fail(RAU_ERR_STATE, "rau_set_att_bias_dev: a step is being captured");
+  BatchSlot& s = cur_batch(ctx);
+  if (!s.held.have)
+    return fail(RAU_ERR_STATE, "rau_set_att_bias_dev: no resident batch (upload the batch first)");
+  if (!bias_dev) {   // detach: the next step's attention kernels get a null pointer again
+    if (s.held.att_bias) drop_forward(ctx);   // a forward that read the bias is not this batch's any more
+    s.held.att_bias = false;
+    ctx->bwd.dbias = false;   // ... nor is the gradient a backward left at it
+    return RAU_OK;
+  }
+  NEED(type == RAU_FEAT_F32 || type == RAU_FEAT_F16 || type == RAU_FEAT_BF16,
+       "rau_set_att_bias_dev: type %d is none of RAU_FEAT_F32, RAU_FEAT_F16, RAU_FEAT_BF16", type);
+  NEED((reinterpret_cast<uintptr_t>(bias_dev) & 15u) == 0, "rau_set_att_bias_dev: bias_dev must be 16-byte aligned");
+  const int n = ctx->cfg.B, SL = ctx->cfg.S, Sp = ctx->Sp;
+  // for the capacity, at the first attach; cleared by rau_set_batch_size like every activation
+  if (!s.zb_ext)
+    if (int rc = dalloc(ctx, &s.zb_ext, (size_t)ctx->cap * Sp)) return rc;
+  if (!ctx->zbgrad)
+    if (int rc = dalloc(ctx, &ctx->zbgrad, (size_t)ctx->cap * Sp)) return rc;
+  RUN("att_bias_attach", 0, (double)n * SL * (4 + feat_elem_bytes(type)),
+      att_bias_attach(ctx->st, n, SL, Sp, bias_dev, type, s.zb_ext));
+  s.held.att_bias = true;
+  ctx->bwd.dbias = false;   // what an earlier backward left is the gradient at ANOTHER bias (or batch)
+  drop_forward(ctx);   // a forward that ran on the batch did not read this bias
+  return RAU_OK;
+}
+
+int rau_batch_att_bias(rau_ctx* ctx, int* has) {
+  NEED(ctx && has, "null argument");
+  *has = cur_batch(ctx).held.att_bias ? 1 : 0;
+  return RAU_OK;
+}
+
+static int att_bias_grad_state(rau_ctx* ctx, const char* fn) {
+  if (!cur_batch(ctx).held.att_bias || !ctx->bwd.dbias)
+    return fail(RAU_ERR_STATE, "%s: no backward on an attached attention bias (rau_set_att_bias_dev) has run since "
+                "the last forward", fn);
+  return RAU_OK;
+}
+int rau_att_bias_grad_dev(rau_ctx* ctx, const float** d_bias, int32_t* pitch) {
+  NEED(ctx, "null ctx");
+  if (int rc = att_bias_grad_state(ctx, "rau_att_bias_grad_dev")) return rc;
+  if (d_bias) *d_bias = ctx->zbgrad;
+  if (pitch) *pitch = ctx->Sp;
+  return RAU_OK;
+}
+int rau_get_att_bias_grad(rau_ctx* ctx, float* host) {
+  NEED(ctx && host, "null argument");
+  if (int rc = att_bias_grad_state(ctx, "rau_get_att_bias_grad")) return rc;
+  const size_t SL = (size_t)ctx->cfg.S, Sp = (size_t)ctx->Sp;
+  if (SL == Sp) return d2h(ctx, host, ctx->zbgrad, (size_t)ctx->cfg.B * SL * sizeof(float));
+  HIPC(hipMemcpy2DAsync(host, SL * sizeof(float), ctx->zbgrad, Sp * sizeof(float), SL * sizeof(float),
+                        (size_t)ctx->cfg.B, hipMemcpyDeviceToHost, ctx->st));
+  HIPC(hipStreamSynchronize(ctx->st));
+  return persist_check(ctx);   // d2h's check: never hand back such results as OK
 }
 
 // The caller's initial state of the hop chain for the resident batch: one launch on the chain stream that widens

@@ -111,6 +111,9 @@ struct BatchDesc {
   // initial state of the hop chain from the caller (rau_set_state_dev): slot 0 of cc / hh holds (c0, h0) [n][R] and the
   // forward leaves it there in place of writing the zeros.  It belongs to the RESIDENT batch like the question.
   bool state = false;
+  // additive attention bias from the caller (rau_set_att_bias_dev): the slot's zb_ext holds a row [Sp] per sample and
+  // every hop's attention kernel adds it to the score.  It belongs to the RESIDENT batch like the two above.
+  bool att_bias = false;
 };
 // One of the two batch slots.  slot[cur_slot] is the resident batch (cur_batch() below): the only record of it.
 // Slot 0's device buffers exist from rau_create on; slot 1's, the pinned staging the loader may fill in place, the
@@ -164,6 +167,9 @@ struct BatchSlot {
   // the caller's question state (rau_set_question_dev): device [capacity][Q] f32, allocated at the slot's first
   // attach (a captured step holds q_ext's address, never its contents)
   float* q_ext = nullptr;
+  // the caller's attention bias (rau_set_att_bias_dev): device [capacity][Sp] f32 at the attention's pitch, allocated
+  // at the slot's first attach (a captured step holds zb_ext's address, never its contents)
+  float* zb_ext = nullptr;
   // packed region rows (rau_set_batch_packed): the raw rows [sum(counts)][D] land in pk_rows_d (room for
   // [capacity * S][D] floats) and unpack_regions transposes them into `feats`; pk_meta_d holds off[n_maps] |
   // cnt[n_maps] (room for 2 * capacity), pk_meta_h is its pinned staging on the asynchronous path.  Allocated at
@@ -292,12 +298,15 @@ struct StepKey {
   bool state = false;           // ... and with an initial state attached (rau_set_state_dev) the forward does not clear
                                 // slot 0 of cc / hh and the backward ends hop 0 with the state gradient's launch; a
                                 // replay reads the slot's current contents
+  bool att_bias = false;        // ... and with an attention bias attached (rau_set_att_bias_dev) the attention kernels
+                                // hold the slot's zb_ext and the backward ends with the bias gradient's launch; a
+                                // replay reads the buffer's current contents
   int xnorm = 0;                // ... and with rau_set_feat_norm the image side starts with the normalisation pass (and
   uint32_t xnorm_eps = 0;       // the backward may end with its gradient), which holds eps as an argument: its bits
   auto tied() const {
     return std::tie(mode, max_len, active, zero, mexplicit[0], mexplicit[1], mexplicit[2], mexplicit[3], mexplicit[4],
                     slot, feat_type, table, bank, ans_G, B, sel, regions, att, att_targets, mrg, tied_x, ans_loss,
-                    feat_grad, question, sample_w, cand_C, state, xnorm, xnorm_eps);
+                    feat_grad, question, sample_w, cand_C, state, att_bias, xnorm, xnorm_eps);
   }
   bool operator==(const StepKey& o) const { return tied() == o.tied(); }
 };
@@ -337,6 +346,7 @@ struct BwdRecord {
   bool dq = false;                // rau_ctx::dq holds the gradient at the ATTACHED question (rau_question_grad_dev)
   bool dX = false;                // xg_dX holds the feature-map gradient (rau_get_feat_grad) ...
   int dX_rows = 0;                // ... its map count: n, or the table's N under RAU_FEAT_GRAD_IMAGES
+  bool dbias = false;             // rau_ctx::zbgrad holds the gradient at the ATTACHED attention bias (rau_att_bias_grad_dev)
   bool dstate = false;            // rau_ctx::sgrad holds the gradient at the ATTACHED initial state (rau_state_grad_dev)
 };
 
@@ -424,6 +434,10 @@ struct rau_ctx {
   // gradient at the attached initial state (rau_set_state_dev, state_io.hip): d_c0 | d_h0, [2][cap][R] with the halves
   // dense in the current n, allocated at the first attach; every backward on an attached state overwrites it
   float* sgrad = nullptr;
+  // gradient at the attached attention bias (rau_set_att_bias_dev, att_bias.hip): [cap][Sp], rows dense in the current
+  // n at the attention's pitch, allocated at the first attach; every backward on an attached bias overwrites it
+  float* zbgrad = nullptr;
+  float* m_zadd = nullptr;   // rau_multimodal_forward_bias: the caller's dense [n][S] rows at the pitch, [cap][Sp]
   float* dS_sum = nullptr;          // [cap][A][Sp] sum of the active hops' dS (tied_bwd.hip), allocated with the switch
   // feature-map gradient (rau_set_feat_grad, xgrad.hip): off = the step path as it is without it
   int feat_grad = RAU_FEAT_GRAD_OFF;   // the mode: _SAMPLES, or _IMAGES = per image where the batch has a table
@@ -575,6 +589,7 @@ inline StepKey step_key(const rau_ctx* ctx, const StepLoss& loss, bool zero) {
   key.sample_w = d.sample_w;
   key.cand_C = d.cand_C;
   key.state = d.state;
+  key.att_bias = d.att_bias;
   key.xnorm = ctx->xnorm;
   if (ctx->xnorm) std::memcpy(&key.xnorm_eps, &ctx->xnorm_eps, sizeof(float));
   return key;
@@ -809,11 +824,13 @@ struct HopGrad {
 };
 __attribute__((visibility("hidden"))) int hop_forward(rau_ctx* ctx, int h, const float* cp,
     const float* hp, float* c_out, float* h_out, const float* Ih, const float* Pin,
-    const Truth& truth, const int32_t* nreg = nullptr /* device [B] region counts, see hop_forward_chain */);
+    const Truth& truth, const int32_t* nreg = nullptr /* device [B] region counts, see hop_forward_chain */,
+    const float* zadd = nullptr /* device [B][Sp] attention bias, see hop_forward_chain */);
 __attribute__((visibility("hidden"))) int hop_forward_chain(rau_ctx* ctx, int h, const float* cp,
     const float* hp, float* c_out, float* h_out, const float* Ih, const float* Pin,
     const int32_t* img = nullptr /* device index: sample b's Ih / Pin tiles are row img[b] (image table) */,
-    const int32_t* nreg = nullptr /* device [B]: sample b attends to its first nreg[b] positions only */);
+    const int32_t* nreg = nullptr /* device [B]: sample b attends to its first nreg[b] positions only */,
+    const float* zadd = nullptr /* device [B][Sp]: added to sample b's attention scores (AttPartials::zadd) */);
 // The resident batch as per-sample maps [B][D][Sp] in its element type: the buffer itself, or for a batch
 // with an image table its expansion (expand_features on the chain stream, once per upload).
 __attribute__((visibility("hidden"))) int batch_maps(rau_ctx* ctx, const float** maps);

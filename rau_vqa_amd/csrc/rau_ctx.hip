@@ -1015,7 +1015,8 @@ int rau_set_batch_size(rau_ctx* ctx, int32_t n) {
 // rau_forward runs the heads on the weight-gradient stream (idle during the forward pass), so the
 // hop-to-hop critical path is the chain alone; the module-level entry points run both on st.
 int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, float* c_out,
-                      float* h_out, const float* Ih, const float* Pin, const int32_t* img, const int32_t* nreg) {
+                      float* h_out, const float* Ih, const float* Pin, const int32_t* img, const int32_t* nreg,
+                      const float* zadd) {
   const rau_config& c = ctx->cfg;
   const int B = c.B, S = ctx->Sp, SL = c.S, M = c.M, A = c.A, R = c.R;
   hipStream_t st = ctx->st;
@@ -1065,6 +1066,7 @@ int hop_forward_chain(rau_ctx* ctx, int h, const float* cp, const float* hp, flo
     const AttMode am = att_mode(ctx);
     ap.img = img;   // image table: Pin and Ih hold one tile per image, sample b reads row img[b]
     ap.nreg = nreg;   // region counts: per SAMPLE, also where the tiles are per image
+    ap.zadd = zadd;   // the caller's attention bias: per SAMPLE like the counts
     // (the profile tells the fused family's two kernels apart: the LDS-DMA one keeps the family's name)
     const char* fused_cls = att_fwd_dma_ok(am, M, A, S, false) ? "att_fwd_fused" : "att_fwd_fused_regs";
     if (!ctx->att_split)
@@ -1142,8 +1144,8 @@ int hop_forward_head(rau_ctx* ctx, const StreamWs& ws, int h0, int nh, const Tru
 }
 
 int hop_forward(rau_ctx* ctx, int h, const float* cp, const float* hp, float* c_out, float* h_out,
-                const float* Ih, const float* Pin, const Truth& truth, const int32_t* nreg) {
-  if (int rc = hop_forward_chain(ctx, h, cp, hp, c_out, h_out, Ih, Pin, nullptr, nreg)) return rc;
+                const float* Ih, const float* Pin, const Truth& truth, const int32_t* nreg, const float* zadd) {
+  if (int rc = hop_forward_chain(ctx, h, cp, hp, c_out, h_out, Ih, Pin, nullptr, nreg, zadd)) return rc;
   if (h_out != ctx->hh + (size_t)(h + 1) * ctx->cfg.B * ctx->cfg.R)
     return fail(RAU_ERR_INVALID, "hop_forward: h_out must be the ctx's hop slot");
   return hop_forward_head(ctx, ctx->ws_chain, h, 1, truth);
@@ -1583,6 +1585,7 @@ static int forward_impl(rau_ctx* ctx, bool bwd_forms_dpre) {
   ctx->mg.valid = false;   // the hop outputs are being overwritten
   ctx->bwd.dX = ctx->bwd.dq = false;   // ... and the gradients at the maps and at an attached question another forward's
   ctx->bwd.dstate = false;             // ... and the one at an attached initial state
+  ctx->bwd.dbias = false;              // ... and the one at an attached attention bias
   const rau_config& c = ctx->cfg;
   const int B = c.B, Rq = c.Rq, D = c.D, S = ctx->Sp, M = c.M, A = c.A, R = c.R, H = c.H, Q = ctx->Q;
   const int TL = bs.held.max_len;
@@ -1690,7 +1693,8 @@ static int forward_impl(rau_ctx* ctx, bool bwd_forms_dpre) {
                                    ctx->cc + (size_t)(h + 1) * BR_, ctx->hh + (size_t)(h + 1) * BR_,
                                    ctx->I + (ctx->fwd.I_shared ? 0 : (size_t)h * BM_ * S),
                                    ctx->fwd.I_shared ? ctx->P0 : ctx->T + (size_t)h * B * A * S, img,
-                                   bs.held.regions ? bs.nreg_d : nullptr))
+                                   bs.held.regions ? bs.nreg_d : nullptr,
+                                   bs.held.att_bias ? bs.zb_ext : nullptr))
       return rc;
     // classifier + criterion heads of the finished hops: nothing on the recurrence waits for
     // them, so they run on the weight-gradient stream (idle in the forward pass), batched over
@@ -2030,6 +2034,7 @@ static void record_backward(rau_ctx* ctx, bool graph) {
   ctx->bwd.graph = graph;
   ctx->bwd.dq = d.question;
   ctx->bwd.dstate = d.state;
+  ctx->bwd.dbias = d.att_bias;
   ctx->bwd.dX = ctx->feat_grad != RAU_FEAT_GRAD_OFF;
   ctx->bwd.dX_rows = xgrad_per_image(ctx) ? d.n_images : ctx->cfg.B;
 }
@@ -2158,6 +2163,11 @@ static int backward_impl(rau_ctx* ctx, const StepLoss& loss) {
         dq_reduce(st, HA, (size_t)B * Q, ctx->dQD, m.q, m.s_q, ctx->dq));
   }
   if (state && HA == 0) HIPC(hipMemsetAsync(ctx->sgrad, 0, (size_t)2 * ctx->cap * R * sizeof(float), st));
+  // an attached attention bias (rau_set_att_bias_dev): its gradient is the active hops' dz summed in ascending order,
+  // all of them resident behind the hop loop (mult_wgrads below reads the same rows); exact zeros without an active hop
+  if (bs.held.att_bias)
+    RUN("att_bias_grad", (double)HA * B * S, (double)(HA + 1) * B * S * 4,
+        att_bias_grad(st, HA, B, c.S, S, ctx->dz, (size_t)B * S, ctx->zbgrad));
   // no active hop: the gradient is zero (n rows: all of a table's N <= n too, whichever N a replay meets)
   if (ctx->feat_grad && dX_first)
     HIPC(hipMemsetAsync(ctx->xg_dX, 0, (size_t)B * c.D * S * sizeof(float), ctx->st2));

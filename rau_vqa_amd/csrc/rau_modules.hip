@@ -266,7 +266,17 @@ int rau_multimodal_forward(rau_ctx* ctx, int h, const float* q, const float* X, 
 int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const float* X, const float* c_prev,
                                    const float* h_prev, const int32_t* regions_dev, float** logits,
                                    float** do_pred, float** attprob, float** c_out, float** h_out) {
+  return rau_multimodal_forward_bias(ctx, h, q, X, c_prev, h_prev, regions_dev, nullptr, logits, do_pred, attprob,
+                                     c_out, h_out);
+}
+
+// bias_dev: [B,S] dense f32 device rows added to the attention scores (AttPartials::zadd; one launch re-pitches them
+// into m_zadd); NULL = none, which is rau_multimodal_forward_regions launch for launch
+int rau_multimodal_forward_bias(rau_ctx* ctx, int h, const float* q, const float* X, const float* c_prev,
+                                const float* h_prev, const int32_t* regions_dev, const float* bias_dev,
+                                float** logits, float** do_pred, float** attprob, float** c_out, float** h_out) {
   NEED(ctx && q, "null argument");
+  NEED(aligned16(bias_dev), "rau_multimodal_forward_bias: bias_dev must be 16-byte aligned");
   NEED_DENSE_K(ctx, "rau_multimodal_forward");
   const rau_config& c = ctx->cfg;
   NEED(h >= 0 && h < c.H, "rau_multimodal_forward: h=%d out of [0,%d)", h, c.H);
@@ -320,7 +330,14 @@ int rau_multimodal_forward_regions(rau_ctx* ctx, int h, const float* q, const fl
   if (int rc = image_forward(ctx, st, B, xin, false, Ih, Th)) return rc;
   float* co = ctx->cc + (size_t)(h + 1) * BR_;
   float* ho = ctx->hh + (size_t)(h + 1) * BR_;
-  if (int rc = hop_forward(ctx, h, c_prev, h_prev, co, ho, Ih, Th, Truth{}, regions_dev)) return rc;
+  const float* zadd = nullptr;
+  if (bias_dev) {
+    if (!ctx->m_zadd)
+      if (int rc = dalloc(ctx, &ctx->m_zadd, (size_t)ctx->cap * S)) return rc;
+    RUN("att_bias_attach", 0, (double)B * SL * 8, att_bias_attach(st, B, SL, S, bias_dev, RAU_FEAT_F32, ctx->m_zadd));
+    zadd = ctx->m_zadd;
+  }
+  if (int rc = hop_forward(ctx, h, c_prev, h_prev, co, ho, Ih, Th, Truth{}, regions_dev, zadd)) return rc;
   if (logits) *logits = ctx->logits + (size_t)h * B * K;
   if (do_pred) *do_pred = ctx->dopred + (size_t)h * B;
   if (attprob) {

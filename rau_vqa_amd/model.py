@@ -68,6 +68,33 @@ def regions_of(n_image, image_of):
     return np.ascontiguousarray(n_image[image_of], np.int32)
 
 
+def check_att_bias(bias, n, S, regions=None):
+    """The host-side check of an attention bias handed over as numpy (RAU.set_att_bias): bias [n,S] of float32,
+    float16 or float64 with finite values and -inf only, and in every row at least one finite entry among the positions
+    the sample attends to -- all S, or the first regions[b] (a softmax over nothing has no value).  Returns the bias as
+    contiguous float32; raises ValueError, touching no device, otherwise."""
+    b = np.asarray(bias)
+    if b.dtype.kind != "f":
+        raise ValueError(f"attention bias must be a floating-point array, got {b.dtype}")
+    if b.shape != (int(n), int(S)):
+        raise ValueError(f"attention bias has shape {b.shape}, expected {(int(n), int(S))}")
+    if np.isnan(b).any():
+        raise ValueError("attention bias holds NaN")
+    if np.isposinf(b).any():
+        raise ValueError("attention bias holds +inf (only finite values and -inf are allowed)")
+    finite = np.isfinite(b)
+    if regions is not None:
+        r = np.asarray(regions)
+        if r.shape != (int(n),) or r.min() < 1 or r.max() > int(S):
+            raise ValueError(f"regions must be [{int(n)}] counts in [1, {int(S)}]")
+        finite = finite & (np.arange(int(S))[None, :] < r[:, None])
+    empty = np.flatnonzero(~finite.any(axis=1))
+    if empty.size:
+        where = "below their region count" if regions is not None else "at all"
+        raise ValueError(f"attention bias rows {empty.tolist()} have no finite entry {where}: a softmax over nothing")
+    return np.ascontiguousarray(b, np.float32)
+
+
 def hop_weights(variant: str, H: int, epoch: int = 0):
     """Per-hop scale of the criterion gradient for the four training scripts.
 
@@ -1229,8 +1256,90 @@ class RAU:
         n, R, dev = self._n, self.cfg.R, self.cfg.device_id
         return device_view(dc.value, n * R, dev).view(n, R), device_view(dh.value, n * R, dev).view(n, R)
 
+    # ---- attention bias from the caller (rau_set_att_bias_dev): masks and priors in, the gradient at them out
+    def set_att_bias(self, bias, regions=None):
+        """Attach an additive attention bias [n,S] to the resident batch: bias[b,s] joins sample b's attention score at
+        position s in every hop; -inf gives attention (and gradient) exactly 0 there.  One bias per batch, always per
+        sample.  Three kinds of input:
+          * a contiguous CUDA torch tensor of float32, float16 or bfloat16 on the ctx's device: zero-copy, one launch
+            on the ctx's stream, no host synchronisation -- set_question's ordering rule.  Its values are not checked:
+            +inf and NaN are the caller's error, a row without a finite entry in its attended range gives NaN;
+          * a numpy array: checked first (check_att_bias: NaN, +inf, or a row with no finite entry among its attended
+            positions raise ValueError before anything is uploaded), then uploaded into a context-owned staging
+            buffer.  regions: the per-sample counts the batch carries, which the check needs (required when it has any);
+          * None: detaches (clear_att_bias).
+        While it is attached every backward leaves att_bias_grad() behind.  The next set_batch* / use_batch /
+        set_batch_size detaches it; attaching again replaces the contents."""
+        if bias is None:
+            return self.clear_att_bias()
+        n, S = self._n, self.cfg.S
+        if isinstance(bias, np.ndarray):
+            if regions is None and self._h and self.batch_regions():
+                raise ValueError("the resident batch carries region counts: pass them as regions= for the check")
+            b = check_att_bias(bias, n, S, regions)
+            if getattr(self, "_att_bias_stage", None) is None:   # [capacity,S] floats, the ctx's until it is destroyed
+                p = C.c_void_p()
+                L.check(self._lib.rau_dev_alloc(self._h, self.capacity * S, C.byref(p)))
+                self._att_bias_stage = p.value
+            L.check(self._lib.rau_dev_upload(self._h, self._att_bias_stage, b.ctypes.data, b.nbytes))
+            L.check(self._lib.rau_set_att_bias_dev(self._h, self._att_bias_stage, feat16.FEAT_TYPES["f32"]))
+            return
+        import torch
+        t = bias
+        types = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in types and t.is_contiguous()):
+            raise ValueError("bias must be a numpy array or a contiguous float32, float16 or bfloat16 CUDA torch tensor")
+        if t.device.index != self.cfg.device_id:
+            raise ValueError(f"bias is on {t.device}, the context on cuda:{self.cfg.device_id}")
+        if tuple(t.shape) != (n, S):
+            raise ValueError(f"bias has shape {tuple(t.shape)}, expected {(n, S)}")
+        L.check(self._lib.rau_set_att_bias_dev(self._h, t.data_ptr(), feat16.FEAT_TYPES[types[t.dtype]]))
+
+    def set_att_mask(self, allowed, regions=None):
+        """set_att_bias(where(allowed, 0, -inf)): allowed [n,S] of bool, a numpy array or a CUDA torch tensor."""
+        if isinstance(allowed, np.ndarray):
+            if allowed.dtype != np.bool_:
+                raise ValueError("allowed must be a bool array")
+            return self.set_att_bias(np.where(allowed, np.float32(0), np.float32(-np.inf)), regions=regions)
+        import torch
+        if not (isinstance(allowed, torch.Tensor) and allowed.dtype == torch.bool):
+            raise ValueError("allowed must be a bool numpy array or a bool CUDA torch tensor")
+        zero = torch.zeros((), dtype=torch.float32, device=allowed.device)
+        b = torch.where(allowed, zero, zero - float("inf")).contiguous()
+        own = torch.cuda.ExternalStream(self.stream(), device=allowed.device)
+        own.wait_stream(torch.cuda.current_stream(allowed.device))   # the bias was written on torch's stream
+        b.record_stream(own)                    # ... and is read by the ctx's: not handed out again before that
+        self.set_att_bias(b)
+
+    def clear_att_bias(self):
+        """Detach the attention bias: the resident batch's scores are the model's own again."""
+        L.check(self._lib.rau_set_att_bias_dev(self._h, None, 0))
+
+    @property
+    def batch_att_bias(self) -> bool:
+        """The resident batch has an attention bias attached (rau_batch_att_bias)."""
+        has = C.c_int(0)
+        L.check(self._lib.rau_batch_att_bias(self._h, C.byref(has)))
+        return bool(has.value)
+
+    def att_bias_grad(self):
+        """The last backward's gradient at the attached attention bias [n,S] (numpy; synchronises)."""
+        out = np.empty((self._n, self.cfg.S), np.float32)
+        L.check(self._lib.rau_get_att_bias_grad(self._h, out.ctypes.data))
+        return out
+
+    def att_bias_grad_tensor(self):
+        """Zero-copy torch view [n,S] (rows at the device pitch) of that gradient in device memory
+        (rau_att_bias_grad_dev).  Valid until the next forward or set_batch_size, ordered on the ctx's stream
+        (stream()), read-only; no synchronisation."""
+        from .dist import device_view
+        p, pitch = C.c_void_p(), C.c_int32()
+        L.check(self._lib.rau_att_bias_grad_dev(self._h, C.byref(p), C.byref(pitch)))
+        n, S, P = self._n, self.cfg.S, int(pitch.value)
+        return device_view(p.value, n * P, self.cfg.device_id).view(n, P)[:, :S]
+
     def set_batch_dev(self, feats_cuda, tokens, lens, labels=None, answers=None, regions=None, att_targets=None,
-                      image_of=None, question=None, sample_w=None, candidates=None, state=None):
+                      image_of=None, question=None, sample_w=None, candidates=None, state=None, att_bias=None):
         """set_batch with the maps already on the device: feats_cuda a contiguous float32 CUDA torch tensor
         [n,D,S] on the ctx's device (rau_set_batch_dev: one copy on the ctx's stream, no host synchronisation).
         The ctx's stream must be ordered behind the stream that wrote the tensor (autograd.step's docstring shows
@@ -1240,7 +1349,8 @@ class RAU:
         tokens / lens may then be None -- the step does not read them, and id 1 with length 1 is uploaded.
         sample_w [n]: set_sample_weights behind the upload.
         candidates [n, C]: set_candidates behind the upload.
-        state: (c0, h0), CUDA tensors [n,R] attached behind the upload (set_state)."""
+        state: (c0, h0), CUDA tensors [n,R] attached behind the upload (set_state).
+        att_bias: [n,S] attached behind the upload (set_att_bias; a numpy bias is checked against `regions`)."""
         import torch
         c = self.cfg
         if question is not None and (tokens is None or lens is None):
@@ -1299,6 +1409,8 @@ class RAU:
             self.set_question(question)
         if state is not None:
             self.set_state(*state)
+        if att_bias is not None:
+            self.set_att_bias(att_bias, regions=regions if isinstance(att_bias, np.ndarray) else None)
 
     def graph_step(self, hop_w, zero_grads=True, select_w=None, att_w=None, merge_w=None):
         """zero_grads + forward + backward as one hipGraph launch (captured on first use); select_w, att_w and

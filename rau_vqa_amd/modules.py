@@ -76,14 +76,23 @@ class DeepLSTMClone(_Clone):
 class MultimodalClone(_Clone):
     """multimodal_clones[h]: {q, X, c, h} -> {logits, do_pred, attprob, c', h'} (SS:292-307)."""
 
-    def forward(self, q, X, c_prev, h_prev, regions=None):
+    def forward(self, q, X, c_prev, h_prev, regions=None, bias=None):
         """regions: int32 CUDA tensor [B] of region counts (RAU.set_regions' meaning; the kernel clamps them into
-        [1, S]); None: every position.  backward() needs nothing more: it reads the attention saved here."""
+        [1, S]); None: every position.  bias: contiguous float32 CUDA tensor [B, S] added to the attention scores
+        (RAU.set_att_bias' meaning, rau_multimodal_forward_bias); None: none.  backward() needs nothing more: it reads
+        the attention saved here."""
         outs = [C.c_void_p() for _ in range(5)]
         if regions is not None and (regions.dtype != torch.int32 or regions.numel() != self.rau.batch_size):
             raise ValueError("regions must be an int32 tensor with one count per sample")
-        L.check(self._lib.rau_multimodal_forward_regions(self._h, self.i, _p(q), _p(X), _p(c_prev),
-                                                         _p(h_prev), _p(regions), *[C.byref(o) for o in outs]))
+        if bias is None:
+            L.check(self._lib.rau_multimodal_forward_regions(self._h, self.i, _p(q), _p(X), _p(c_prev),
+                                                             _p(h_prev), _p(regions), *[C.byref(o) for o in outs]))
+        else:
+            if not (bias.dtype == torch.float32 and bias.is_contiguous() and
+                    tuple(bias.shape) == (self.rau.batch_size, self.rau.cfg.S)):
+                raise ValueError("bias must be a contiguous float32 tensor [B, S]")
+            L.check(self._lib.rau_multimodal_forward_bias(self._h, self.i, _p(q), _p(X), _p(c_prev), _p(h_prev),
+                                                          _p(regions), _p(bias), *[C.byref(o) for o in outs]))
         c = self.rau.cfg
         return (self._view(outs[0], self.rau.batch_size, c.K), self._view(outs[1], self.rau.batch_size),
                 self._view(outs[2], self.rau.batch_size, c.S), self._view(outs[3], self.rau.batch_size, c.R),
